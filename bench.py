@@ -17,6 +17,11 @@ between barrier + synchronize; that is repeated `--reps` times and the MEDIAN re
 inter-quartile range `ms_per_step_iqr`; the repetitions are listed in `ms_per_step_reps`), so that one descheduled host
 thread does not decide the number.  When K is small the repetition count is raised until the timed regions add up to
 `--min-timed-seconds` (0.25 s): repetitions are free, a 1.5 ms sample is not a measurement.
+
+`--dump-outputs DIR` writes what step() returned in the K-th timed step — the last step of the FIRST timed region — as
+DIR/<name>.npy (float32): obs, reward, truncated, final_obs (cfg4: obs_multi too).  That step is preroll + W + K steps
+after reset() whatever the clock later makes of the repetition count, and seeds and actions are fixed, so the files
+depend on the arguments only: two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -232,6 +237,24 @@ def free_port():
         return s.getsockname()[1]
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """Write {name: array [B, ...]} as dirname/<name>.npy in float32.  More than `limit` bytes in all: the same seeded
+    sample of the env rows (ascending) of every array, so that the files still line up row for row."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n_env = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n_env
+    if n_env * row_bytes > limit:
+        rows = np.sort(np.random.default_rng(0).choice(n_env, size=max(1, limit // row_bytes), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -267,6 +290,9 @@ def parse():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="weak: --envs (default: the workload's) per GPU; strong: that many envs in TOTAL, split over "
                          "the N ranks (BASELINE.json's '4096 envs sharded across 8')")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays step() returned in the last step of the first timed region (preroll + warmup + "
+                         "steps after reset) as DIR/<name>.npy; rank 0 writes its shard")
     return ap.parse_args()
 
 
@@ -400,6 +426,12 @@ def main():
         flow_ms += f * n; glue_ms += g * n; n_launch += n
         flow_steps += fs; particles += pt; added += env.added_lookups()
         rep += 1
+        if rep == 1 and args.dump_outputs and rank == 0:
+            # copies, outside every timed region: the buffers are overwritten by the repetitions that follow
+            dump = {"obs": env.obs.clone(), "reward": env.reward.clone(), "truncated": env.truncated.clone(),
+                    "final_obs": env.final_obs.clone()}
+            if multi_out is not None:
+                dump["obs_multi"] = multi_out.clone()
         if rep == 1 and args.min_timed_seconds > 0:
             # (decided from the slowest rank's first repetition, so every rank runs the same count)
             n_reps = max(args.reps, min(2000, int(args.min_timed_seconds / max(rep_s[0], 1e-6)) + 1))
@@ -410,6 +442,8 @@ def main():
     if multi_out is not None:          # the fused buffer holds what an explicit wg_obs_multi returns (to summation order)
         assert (multi_out - env.obs_multi()).abs().max().item() <= 2e-6
     m = metrics.all_reduce()            # the only collective on the path: 8 floats
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in dump.items()})
 
     rs = sorted(rep_s)
     el_med = rs[len(rs) // 2]
