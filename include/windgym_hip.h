@@ -385,6 +385,97 @@ int wg_algorithmic_bytes(wg_handle h, double* bytes_per_step);
  * contexts (k_flow_env: one or two waves per env; with the lean glue, wg_step is then ONE kernel launch).                     */
 int wg_flow_variant(wg_handle h, int* block, int* compact, int* duo);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Learned policies on the device.  The reference evaluates a stable-baselines3 model on the host, one env at a time:
+ * `model.predict(obs, deterministic=...)[0]` every step of AgentEval.eval_single_fast (WindGym/AgentEval.py:179-190;
+ * examples/Example 2 Evaluate pretrained agent.ipynb: PPO.load("PPO_2975000")), and trains it through SB3's rollout
+ * collection (examples/longer_steps_example.py:212-240).  Here the policy is an MLP actor(-critic) evaluated by ONE kernel
+ * (k_policy, windgym_amd/csrc/wg_policy.hip) on device-resident observation rows, and wg_rollout alternates it with the
+ * step kernels without returning to the caller.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_policy_s* wg_policy;
+enum { WG_ACTV_TANH = 0, WG_ACTV_RELU = 1 };              /* SB3 MlpPolicy activation_fn: nn.Tanh (default) / nn.ReLU */
+#define WG_POLICY_MAX_HIDDEN 4
+
+/* Architecture of SB3's MlpPolicy with separate actor / critic nets (net_arch=dict(pi=[...], vf=[...]), SB3 >= 2.0):
+ * actor n_in -> hidden_pi... -> n_out, critic n_in -> hidden_vf... -> 1, state-independent log_std[n_out].
+ * Bounds (WG_ERR_UNSUPPORTED outside): n_in <= 2048, n_out <= 128, 0-4 hidden layers per net, widths <= 256.     */
+typedef struct wg_policy_desc {
+    int32_t n_in, n_out, activation;
+    int32_t n_hidden_pi, hidden_pi[WG_POLICY_MAX_HIDDEN];
+    int32_t n_hidden_vf, hidden_vf[WG_POLICY_MAX_HIDDEN];   /* n_hidden_vf < 0: no critic          */
+    int32_t has_log_std;                                     /* 0: deterministic use only, no logp  */
+} wg_policy_desc;
+
+/* PPO.load's counterpart (AgentEval.py:179-190 needs nothing else of the model): an empty policy of the given
+ * architecture on `device` (all parameters 0 until wg_policy_set_params).                                          */
+int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* out);
+int wg_policy_destroy(wg_policy p);
+
+/* All parameters as ONE flat f32 vector of wg_policy_n_params floats: actor hidden layers in order, each W [out][in]
+ * row-major (torch.nn.Linear.weight) then b [out]; actor head W [n_out][.], b; critic hidden layers, critic head W [1][.],
+ * b [1] (with a critic); log_std [n_out] (with has_log_std) — SB3's mlp_extractor.policy_net.*, action_net.*,
+ * mlp_extractor.value_net.*, value_net.*, log_std.  `params` is a host (on_device = 0; must stay valid until the stream
+ * reaches the copy) or device pointer; stream-ordered copy + repack into the kernel's layout, no synchronisation.  With a
+ * device pointer this is also how a trainer pushes the weights after an optimiser step
+ * (examples/longer_steps_example.py:232-240: model.learn).                                                         */
+int wg_policy_set_params(wg_policy p, const float* params, size_t n, int on_device, void* stream);
+int wg_policy_n_params(wg_policy p, size_t* n);
+
+/* model.predict(obs, deterministic)[0] (AgentEval.py:179-190) for n_rows observation rows obs_dev f32[n_rows, n_in], plus what
+ * SB3's rollout collection takes from policy.forward (examples/longer_steps_example.py:212-240):
+ *   mean = actor(obs); raw = mean (deterministic) or mean + exp(log_std) * eps, eps ~ N(0, 1) from Philox4x32-10 keyed by
+ *   (seed; row + row_offset, counter, output index) — wg_policy.h writes the stream down;
+ *   action_dev f32[n_rows, n_out] = clip(raw, -1, 1) (what predict() returns for a Box and wg_step expects),
+ *   raw_dev    f32[n_rows, n_out] = raw (what a PPO buffer stores),
+ *   logp_dev   f32[n_rows]        = sum_j (-eps_j^2 / 2 - log_std_j - log(2 pi) / 2)  (deterministic: the density at the mean),
+ *   value_dev  f32[n_rows]        = critic(obs).
+ * Every output may be NULL; a net none of whose outputs is requested is not evaluated.  fp32, bit-identical from run to run,
+ * and a row's outputs do not depend on n_rows or on the other rows: a batch sharded with row_offset = first global row
+ * computes what the unsharded batch computes.  Row-generic: a parameter-shared per-turbine policy on the buffer of
+ * wg_set_obs_multi_buffer is n_rows = B * N, n_out = 1.  One launch, asynchronous on `stream`, allocates and synchronises
+ * nothing (legal inside a stream capture).  WG_ERR_INVALID: a stochastic call or logp on a policy without log_std, a
+ * value on a policy without a critic.                                                                              */
+int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int deterministic,
+                  uint64_t seed, uint64_t counter, uint64_t row_offset,
+                  float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream);
+
+/* Caller-owned device buffers of wg_rollout, T = n_steps, B / N / O of the handle; NULL = not wanted where noted. */
+typedef struct wg_rollout_bufs {
+    float*   obs;          /* [T+1, B, O]  obs[0] is INPUT (the observation the env last returned); obs[t+1] after step t */
+    float*   actions;      /* [T, B, N]    what wg_step received (clipped)                                        */
+    float*   raw;          /* [T, B, N]    or NULL                                                               */
+    float*   logp;         /* [T, B]       or NULL                                                               */
+    float*   value;        /* [T, B]       or NULL: V(obs[t])                                                    */
+    float*   final_obs;    /* [T, B, O]    or NULL (required with final_value)                                    */
+    float*   final_value;  /* [T, B]       or NULL: V(final_obs[t]) — the value of the state step t ENDED in, also
+                            *              when the env was reset in the same step                                */
+    float*   reward;       /* [T, B]                                                                              */
+    uint8_t* truncated;    /* [T, B]                                                                              */
+    int32_t  n_info;       /* recorded info fields: info_out[i] is [T, <shape of wg_info_field info_fields[i]>]   */
+    const int32_t* info_fields;      /* host arrays of n_info entries                                             */
+    void* const*   info_out;
+} wg_rollout_bufs;
+
+/* The closed loop of AgentEval.eval_single_fast (AgentEval.py:179-212: predict, env.step, record) and of SB3's
+ * collect_rollouts (examples/longer_steps_example.py:212-240) for the whole batch, n_steps steps, enqueued on `stream`
+ * with no host synchronisation, no allocation and no return to the caller in between.  Buffers and the handle's state
+ * afterwards are BIT-IDENTICAL to
+ *     for t in 0 .. T-1:
+ *         wg_policy_act(p, B, obs[t], deterministic, seed, counter0 + t, row_offset, actions[t], raw[t], logp[t], value[t])
+ *         wg_step(h, actions[t], obs[t+1], reward[t], truncated[t], final_obs[t])
+ *         wg_get_info(h, info_fields[i], info_out[i] + t * <size of the field>)       for every i
+ *         wg_policy_act(p, B, final_obs[t], value only -> final_value[t])              if wanted
+ * Its steps count for wg_metrics, wg_kernel_timing and wg_check like wg_step calls; the step kernels are launched directly
+ * also when wg_set_step_graph is on.  This env never terminates (Wind_Farm_Env.py:1029): every episode ends by truncation,
+ * so an advantage estimate bootstraps from final_value:  delta_t = r_t + gamma * final_value_t - value_t,
+ * A_t = delta_t + gamma * lambda * (1 - truncated_t) * A_{t+1}.
+ * WG_ERR_INVALID: null / missing required buffers, p's n_in != the handle's obs_dim or n_out != n_turb, policy and handle on
+ * different devices, final_value without final_obs, value / final_value without a critic, stochastic without log_std, an
+ * unknown info field.                                                                                              */
+int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+               uint64_t row_offset, const wg_rollout_bufs* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

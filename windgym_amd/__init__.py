@@ -20,6 +20,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("ConstantAgent", "RandomAgent", "GreedyAgent", "BaseAgent"):
         from . import agents
         return getattr(agents, name)
+    if name in ("MlpPolicy", "read_sb3_zip"):
+        from . import policy
+        return getattr(policy, name)
     if name in ("PyWakeAgent", "SteadyStateYawAgent"):
         from . import steady
         return getattr(steady, name)

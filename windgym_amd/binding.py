@@ -33,9 +33,29 @@ ABI_SYMBOLS = (
     "wg_last_error", "wg_abi_version", "wg_create", "wg_destroy", "wg_obs_dim", "wg_hist_max",
     "wg_set_turbulence_box", "wg_set_turbulence_boxes", "wg_set_added_turbulence_box", "wg_set_deficit_table", "wg_set_box_ids", "wg_set_wind", "wg_set_wind_device", "wg_set_flow_script", "wg_reset", "wg_step", "wg_set_step_graph", "wg_check", "wg_obs_multi", "wg_set_obs_multi_buffer",
     "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
+    "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
 )
 
 _lib = None
+
+WG_POLICY_MAX_HIDDEN = 4
+ACTV = {"tanh": 0, "relu": 1}
+
+
+class CPolicyDesc(C.Structure):
+    """wg_policy_desc"""
+    _fields_ = [("n_in", C.c_int32), ("n_out", C.c_int32), ("activation", C.c_int32),
+                ("n_hidden_pi", C.c_int32), ("hidden_pi", C.c_int32 * WG_POLICY_MAX_HIDDEN),
+                ("n_hidden_vf", C.c_int32), ("hidden_vf", C.c_int32 * WG_POLICY_MAX_HIDDEN),
+                ("has_log_std", C.c_int32)]
+
+
+class CRolloutBufs(C.Structure):
+    """wg_rollout_bufs"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("raw", C.c_void_p), ("logp", C.c_void_p),
+                ("value", C.c_void_p), ("final_obs", C.c_void_p), ("final_value", C.c_void_p), ("reward", C.c_void_p),
+                ("truncated", C.c_void_p), ("n_info", C.c_int32), ("info_fields", C.POINTER(C.c_int32)),
+                ("info_out", C.POINTER(C.c_void_p))]
 
 
 class WindGymHipError(RuntimeError):
@@ -95,6 +115,14 @@ def load_library():
     L.wg_mann_beta_table.argtypes = [C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]
     L.wg_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.wg_flow_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.wg_policy_create.argtypes = [C.POINTER(CPolicyDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_policy_destroy.argtypes = [C.c_void_p]
+    L.wg_policy_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    L.wg_policy_n_params.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.wg_policy_act.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                             C.POINTER(CRolloutBufs), C.c_void_p]
     _lib = L
     return L
 
@@ -238,21 +266,30 @@ class HipBatch:
                                      self._stream()), "wg_get_windspeed")
         return out
 
-    def info(self, name):
+    def info_shape(self, name):
+        """(shape, torch dtype) of ``info(name)``."""
         t = self.torch
         per_turb = name in ("yaw_agent", "yaw_base", "ws_turb", "wd_turb", "power_turb_agent",
                             "power_turb_base", "ws_turb_base", "turb_x", "turb_y")
         if name == "wind_f64":
-            out = t.zeros((self.B, 3), dtype=t.float64, device=self.device)
-            _chk(self.L.wg_get_info(self._h, INFO[name], C.c_void_p(out.data_ptr()), self._stream()), "wg_get_info")
-            return out
+            return (self.B, 3), t.float64
         if name.startswith("rotor_uvw"):
             shape = (self.B, self.N, 3)
         elif per_turb:
             shape = (self.B, self.N)
         else:
             shape = (self.B,)
-        out = t.zeros(shape, dtype=t.int32 if name in INFO_INT else t.float32, device=self.device)
+        return shape, (t.int32 if name in INFO_INT else t.float32)
+
+    def info(self, name, out=None):
+        """One field of the lazy info dict as a new CUDA tensor, or written into ``out`` (a contiguous CUDA tensor of
+        ``info_shape(name)``, e.g. row 0 of a recording) and returned."""
+        t = self.torch
+        shape, dtype = self.info_shape(name)
+        if out is None:
+            out = t.zeros(shape, dtype=dtype, device=self.device)
+        elif not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape)):
+            raise ValueError(f"info({name!r}, out=): out must be a contiguous CUDA tensor of shape {shape} and dtype {dtype}")
         _chk(self.L.wg_get_info(self._h, INFO[name], C.c_void_p(out.data_ptr()), self._stream()), "wg_get_info")
         return out
 

@@ -15,6 +15,10 @@
 #include "wg_state.h"
 #include "wg_flow.h"
 #include "wg_steady.h"
+#include "wg_policy.h"
+
+extern "C" int wg_policy_act2_(wg_policy, int, const float*, int, uint64_t, uint64_t, uint64_t, float*, float*, float*, float*, const float*,
+                               float*, void*);      // wg_policy.hip
 
 extern "C" {
 void wg_launch_flow(const FlowP*, const FlowPtrs*, int, const float*, const uint8_t*, int, hipStream_t);
@@ -1203,6 +1207,68 @@ extern "C" int wg_get_info(wg_handle h, wg_info_field field, void* out_dev, void
     if (int rc = use_device(h)) return rc;
     if ((int)field < 0 || (int)field > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, "unknown info field");
     wg_launch_info(&h->p, &h->d, (int)field, out_dev, (hipStream_t)stream);
+    return 0;
+}
+
+// bytes of one wg_get_info() result (the stride of a recording in wg_rollout)
+static size_t info_bytes(const wg_env_s* h, int field) {
+    const size_t B = h->p.B, N = h->p.N;
+    switch (field) {
+    case WG_INFO_YAW_AGENT: case WG_INFO_YAW_BASE: case WG_INFO_WS_TURB: case WG_INFO_WD_TURB: case WG_INFO_POWER_TURB_AGENT:
+    case WG_INFO_POWER_TURB_BASE: case WG_INFO_WS_TURB_BASE: case WG_INFO_TURB_X: case WG_INFO_TURB_Y: return B * N * 4;
+    case WG_INFO_ROTOR_UVW_AGENT: case WG_INFO_ROTOR_UVW_BASE: return B * N * 3 * 4;
+    case WG_INFO_WIND_F64: return B * 3 * 8;
+    default: return B * 4;
+    }
+}
+
+// The closed loop policy -> step -> record for n_steps steps, enqueued from here (windgym_hip.h: wg_rollout).
+extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                          uint64_t row_offset, const wg_rollout_bufs* o, void* stream) {
+    if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout: null argument");
+    if (n_steps < 0) return fail(WG_ERR_INVALID, "wg_rollout: n_steps < 0");
+    if (!o->obs || !o->actions || !o->reward || !o->truncated)
+        return fail(WG_ERR_INVALID, "wg_rollout: obs, actions, reward and truncated buffers are required");
+    if (p->device != h->device) return fail(WG_ERR_INVALID, "wg_rollout: policy and handle live on different devices");
+    const int B = h->p.B, N = h->p.N, O = h->p.obs_dim;
+    if (p->P.n_in != O || p->P.n_out != N)
+        return fail(WG_ERR_INVALID, "wg_rollout: the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
+                                    ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N));
+    if (o->final_value && !o->final_obs) return fail(WG_ERR_INVALID, "wg_rollout: final_value needs final_obs");
+    if ((o->value || o->final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, "wg_rollout: value requested from a policy without a critic");
+    if (!p->P.has_log_std && (!deterministic || o->logp))
+        return fail(WG_ERR_INVALID, "wg_rollout: a stochastic rollout / log-probabilities need a policy with log_std");
+    if (o->n_info < 0 || (o->n_info > 0 && (!o->info_fields || !o->info_out))) return fail(WG_ERR_INVALID, "wg_rollout: bad info arguments");
+    for (int i = 0; i < o->n_info; ++i) {
+        if (o->info_fields[i] < 0 || o->info_fields[i] > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, "wg_rollout: unknown info field");
+        if (!o->info_out[i]) return fail(WG_ERR_INVALID, "wg_rollout: null info buffer");
+    }
+    if (int rc = use_device(h)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t sBO = (size_t)B * O, sBN = (size_t)B * N;
+    // final_value[t - 1] = V(final_obs[t - 1]) is computed by the launch that computes step t's actions (one more slot of
+    // k_policy's grid: a row's value does not depend on what else the launch computes), the last one by a launch of its own
+    for (int t = 0; t < n_steps; ++t) {
+        const bool fv = o->final_value && t > 0;
+        if (int rc = wg_policy_act2_(p, B, o->obs + t * sBO, deterministic, seed, counter0 + (uint64_t)t, row_offset, o->actions + t * sBN,
+                                     o->raw ? o->raw + t * sBN : nullptr, o->logp ? o->logp + (size_t)t * B : nullptr,
+                                     o->value ? o->value + (size_t)t * B : nullptr, fv ? o->final_obs + (t - 1) * sBO : nullptr,
+                                     fv ? o->final_value + (size_t)(t - 1) * B : nullptr, stream))
+            return rc;
+        // (direct launches also in graph mode: T distinct pointer sets would only churn the graph cache)
+        const bool sample = h->timing && (h->timing_phase++ % h->timing_period == 0);
+        h->n_step_launches++;
+        launch_step(h, o->actions + t * sBN, o->obs + (t + 1) * sBO, o->reward + (size_t)t * B, o->truncated + (size_t)t * B,
+                    o->final_obs ? o->final_obs + t * sBO : nullptr, st, sample);
+        for (int i = 0; i < o->n_info; ++i)
+            wg_launch_info(&h->p, &h->d, o->info_fields[i], (char*)o->info_out[i] + (size_t)t * info_bytes(h, o->info_fields[i]), st);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail(WG_ERR_HIP, std::string("wg_rollout: kernel launch failed: ") + hipGetErrorString(le));
+    }
+    if (o->final_value && n_steps > 0)
+        if (int rc = wg_policy_act(p, B, o->final_obs + (n_steps - 1) * sBO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
+                                   o->final_value + (size_t)(n_steps - 1) * B, stream))
+            return rc;
     return 0;
 }
 

@@ -1,0 +1,340 @@
+// wg_policy.hip — learned policies on the device: k_policy evaluates an MLP actor(-critic) on observation rows
+// (what `model.predict(obs, deterministic=...)` of a stable-baselines3 MlpPolicy computes, WindGym/AgentEval.py:179-190),
+// k_policy_pack builds the kernel's weight layout, and the wg_policy_* entries of include/windgym_hip.h wrap them.
+//
+// k_policy: one workgroup of 4 waves owns 32 observation rows of ONE net (blockIdx.y: actor / critic).  A layer is
+// D[neuron][row] = sum_k W[neuron][k] X[k][row] on v_mfma_f32_32x32x2_f32 — an exact k-ordered f32 fmaf chain, so a row's
+// outputs depend on nothing but that row and the weights (bitwise: no atomics, no cross-row reduction, fixed order).
+// X lives in LDS as [k][32 rows] (B operand: one conflict-free ds_read per k-step), the weights come packed from L2 as the A
+// operand (wg_policy.h), the 32 x 32 result tile of wave w (tiles w and w + 4) gets bias (accumulator init) and activation
+// and goes to the other LDS buffer: hidden activations never leave the CU.  The first layer streams the observations
+// through LDS in chunks of 256 inputs (n_in <= 2048).  The head's tile is the action mean / the value.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <string>
+
+#include "../../include/windgym_hip.h"
+#include "wg_policy.h"
+
+extern "C" int wg_set_last_error_(int code, const char* msg);      // wg_api.hip
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// Philox4x32-10 (the generator of wg_device.h's sensor noise) -> the first two output words
+__device__ inline void wgp_philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t& o0,
+                                  uint32_t& o1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o0 = c0; o1 = c1;
+}
+
+// eps_j of global row g (wg_policy.h: NOISE)
+__device__ inline float wgp_noise(uint64_t seed, uint64_t counter, uint64_t g, int j) {
+    uint32_t a, b;
+    wgp_philox((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)g, (uint32_t)counter, (uint32_t)(counter >> 32),
+               WGP_NOISE_TAG | ((uint32_t)(g >> 32) & 0xffffu) << 8 | (uint32_t)(j >> 1), a, b);
+    const float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    const float u2 = (float)(b >> 8) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.0f * logf(u1));
+    const float ph = 6.2831853071795864f * u2;
+    return r * ((j & 1) ? sinf(ph) : cosf(ph));
+}
+
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_policy(const WgPolicyP P, const float* __restrict__ packed,
+                                                           const float* __restrict__ obs, const int n_rows,
+                                                           const int deterministic, const uint64_t seed, const uint64_t counter,
+                                                           const uint64_t row_offset, float* __restrict__ action,
+                                                           float* __restrict__ raw, float* __restrict__ logp,
+                                                           float* __restrict__ value, const int net0,
+                                                           const float* __restrict__ obs2, float* __restrict__ value2) {
+    __shared__ float lds[2][WGP_KC * WGP_TILE];
+    // blockIdx.y: the requested nets on `obs`; with obs2, one more slot = the critic on a SECOND set of rows -> value2
+    // (wg_rollout: the value of step t - 1's final observations rides in the launch that computes step t's actions)
+    int net = net0 + blockIdx.y;
+    if (obs2 != nullptr && blockIdx.y == gridDim.y - 1) { net = 1; obs = obs2; value = value2; }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int row0 = blockIdx.x * WGP_TILE;
+    const int L = P.n_layers[net];
+    int cur = 0;                                  // LDS buffer that holds the running layer's input
+    for (int l = 0; l < L; ++l) {
+        const WgPolicyLayer ly = P.layer[net][l];
+        f32x16 acc[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int ot = wave + WGP_WAVES * t;
+            if (ot < ly.ntiles) {
+                const float* bp = packed + ly.b_packed + ot * 32 + 4 * h;
+#pragma unroll
+                for (int g = 0; g < 16; ++g) acc[t][g] = bp[(g & 3) + 8 * (g >> 2)];
+            }
+        }
+        const int nchunk = l == 0 ? (ly.K + WGP_KC - 1) / WGP_KC : 1;
+        for (int c = 0; c < nchunk; ++c) {
+            const int k0 = c * WGP_KC;
+            const int kc = min(WGP_KC, ly.K - k0), kcp = (kc + 4 * WGP_GROUP - 1) & ~(4 * WGP_GROUP - 1);
+            if (l == 0) {
+                // observations -> LDS [k][row]: a wave covers 32 rows x 2 inputs per pass (conflict-free stores; the 32 rows'
+                // cache lines are re-used from L1 by the following passes).  Rows past n_rows and the pad up to whole k-groups read as 0.
+                __syncthreads();
+                const int row = row0 + r;
+                const float* orow = obs + (size_t)row * P.n_in + k0;
+                for (int k = tid >> 5; k < kcp; k += WGP_WAVES * 2)
+                    lds[0][k * WGP_TILE + r] = (row < n_rows && k < kc) ? orow[k] : 0.0f;
+                __syncthreads();
+            }
+            const float* xb = lds[cur] + h * WGP_TILE + r;
+            const int nks = kcp >> 1;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int ot = wave + WGP_WAVES * t;
+                if (ot < ly.ntiles) {
+                    // k-steps in groups of WGP_GROUP: the A operands of group g + 1 (global loads, L2 latency) are requested
+                    // before the MFMAs of group g issue; the B operands are LDS reads of the group itself
+                    const float* wp = packed + ly.w_packed + ((size_t)ot * ly.nks + (k0 >> 1)) * 64 + lane;
+                    // (no bounds tests: a tile's k-steps are padded to whole groups with zero weights, the input rows behind them
+                    // hold zeros (k-steps come in PAIRS of groups), and the packed vector ends in one group of slack for the last prefetch;
+                    // the roles of a0 / a1 are fixed, so that no register copy waits for the prefetch)
+                    float a0[WGP_GROUP], a1[WGP_GROUP], b[WGP_GROUP];
+#pragma unroll
+                    for (int i = 0; i < WGP_GROUP; ++i) a0[i] = wp[i * 64];
+                    for (int ks0 = 0; ks0 < nks; ks0 += 2 * WGP_GROUP) {
+#pragma unroll
+                        for (int i = 0; i < WGP_GROUP; ++i) {
+                            a1[i] = wp[(size_t)(ks0 + WGP_GROUP + i) * 64];
+                            b[i] = xb[(ks0 + i) * 2 * WGP_TILE];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = 0; i < WGP_GROUP; ++i)
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b[i], acc[t], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = 0; i < WGP_GROUP; ++i) {
+                            a0[i] = wp[(size_t)(ks0 + 2 * WGP_GROUP + i) * 64];
+                            b[i] = xb[(ks0 + WGP_GROUP + i) * 2 * WGP_TILE];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = 0; i < WGP_GROUP; ++i)
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b[i], acc[t], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+        }
+        // D: lane = (row r, half h), register g = neuron 32 ot + (g & 3) + 8 (g >> 2) + 4 h
+        float* dst = lds[cur ^ 1];
+        const bool head = l == L - 1;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int ot = wave + WGP_WAVES * t;
+            if (ot < ly.ntiles) {
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    float v = acc[t][g];
+                    if (!head) v = P.activation == WG_ACTV_RELU ? fmaxf(v, 0.0f) : tanhf(v);
+                    dst[(ot * 32 + (g & 3) + 8 * (g >> 2) + 4 * h) * WGP_TILE + r] = v;
+                }
+            }
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    float* mb = lds[cur];                         // [output][row]: action means / the value
+    const int nvalid = min(WGP_TILE, n_rows - row0);
+    if (net == 1) {
+        if (tid < nvalid) value[row0 + tid] = mb[tid];
+        return;
+    }
+    const int n_out = P.n_out;
+    for (int idx = tid; idx < nvalid * n_out; idx += WGP_WAVES * 64) {      // idx = row * n_out + j: coalesced stores
+        const int row = idx / n_out, j = idx - row * n_out;
+        const float mean = mb[j * WGP_TILE + row];
+        const float ls = P.has_log_std ? packed[P.log_std_packed + j] : 0.0f;
+        const float eps = deterministic ? 0.0f : wgp_noise(seed, counter, row_offset + (uint64_t)(row0 + row), j);
+        const float rw = mean + expf(ls) * eps;
+        const size_t o = (size_t)row0 * n_out + idx;
+        if (raw) raw[o] = rw;
+        if (action) action[o] = fminf(fmaxf(rw, -1.0f), 1.0f);
+        mb[j * WGP_TILE + row] = -0.5f * eps * eps - ls - 0.91893853320467274f;
+    }
+    if (logp) {                                   // sum over j in index order by ONE thread per row
+        __syncthreads();
+        if (tid < nvalid) {
+            float s = 0.0f;
+            for (int j = 0; j < n_out; ++j) s += mb[j * WGP_TILE + tid];
+            logp[row0 + tid] = s;
+        }
+    }
+}
+
+// flat -> packed (wg_policy.h); one thread per packed float
+__global__ void k_policy_pack(const WgPolicyP P, const float* __restrict__ flat, float* __restrict__ packed) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= P.n_packed) return;
+    float v = 0.0f;
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < P.n_layers[net]; ++l) {
+            const WgPolicyLayer ly = P.layer[net][l];
+            const uint32_t wsize = (uint32_t)ly.ntiles * ly.nks * 64, bsize = (uint32_t)ly.ntiles * 32;
+            if (idx >= ly.w_packed && idx < ly.w_packed + wsize) {
+                const uint32_t e = idx - ly.w_packed, lane = e & 63, ks = (e >> 6) % ly.nks, ot = (e >> 6) / ly.nks;
+                const uint32_t i = ot * 32 + (lane & 31), k = 2 * ks + (lane >> 5);
+                if (i < (uint32_t)ly.M && k < (uint32_t)ly.K) v = flat[ly.w_flat + (size_t)i * ly.K + k];
+            } else if (idx >= ly.b_packed && idx < ly.b_packed + bsize) {
+                const uint32_t i = idx - ly.b_packed;
+                if (i < (uint32_t)ly.M) v = flat[ly.b_flat + i];
+            }
+        }
+    if (P.has_log_std && idx >= P.log_std_packed && idx < P.log_std_packed + (uint32_t)P.n_out)
+        v = flat[P.log_std_flat + (idx - P.log_std_packed)];
+    packed[idx] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+static int pfail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
+#define PHIPCHK(x)                                                                                  \
+    do {                                                                                            \
+        hipError_t _e = (x);                                                                        \
+        if (_e != hipSuccess) return pfail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+static int p_use_device(wg_policy_s* p) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != p->device) PHIPCHK(hipSetDevice(p->device));
+    return 0;
+}
+
+extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* out) {
+    if (!d || !out) return pfail(WG_ERR_INVALID, "wg_policy_create: null argument");
+    *out = nullptr;
+    if (d->n_in < 1 || d->n_out < 1) return pfail(WG_ERR_INVALID, "wg_policy_create: n_in and n_out must be >= 1");
+    if (d->n_in > WGP_MAX_IN) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_in = " + std::to_string(d->n_in) + " > " + std::to_string(WGP_MAX_IN));
+    if (d->n_out > WGP_MAX_OUT) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_out = " + std::to_string(d->n_out) + " > " + std::to_string(WGP_MAX_OUT));
+    if (d->activation != WG_ACTV_TANH && d->activation != WG_ACTV_RELU) return pfail(WG_ERR_INVALID, "wg_policy_create: unknown activation");
+    if (d->n_hidden_pi < 0) return pfail(WG_ERR_INVALID, "wg_policy_create: n_hidden_pi < 0");
+    const int nh[2] = {d->n_hidden_pi, d->n_hidden_vf};
+    const int32_t* hid[2] = {d->hidden_pi, d->hidden_vf};
+    for (int net = 0; net < 2; ++net) {
+        if (nh[net] > WG_POLICY_MAX_HIDDEN)
+            return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: " + std::to_string(nh[net]) + " hidden layers > " + std::to_string(WG_POLICY_MAX_HIDDEN));
+        for (int l = 0; l < nh[net]; ++l) {
+            if (hid[net][l] < 1) return pfail(WG_ERR_INVALID, "wg_policy_create: hidden width < 1");
+            if (hid[net][l] > WGP_MAX_WIDTH)
+                return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: hidden width " + std::to_string(hid[net][l]) + " > " + std::to_string(WGP_MAX_WIDTH));
+        }
+    }
+    wg_policy_s* p = new (std::nothrow) wg_policy_s();
+    if (!p) return pfail(WG_ERR_NOMEM, "wg_policy_create: out of host memory");
+    WgPolicyP& P = p->P;
+    P.n_in = d->n_in; P.n_out = d->n_out; P.activation = d->activation; P.has_log_std = d->has_log_std != 0;
+    uint32_t flat = 0, packed = 0;
+    for (int net = 0; net < 2; ++net) {
+        if (nh[net] < 0) { P.n_layers[net] = 0; continue; }        // (critic only: n_hidden_vf < 0 = none)
+        P.n_layers[net] = nh[net] + 1;
+        int K = d->n_in;
+        for (int l = 0; l <= nh[net]; ++l) {
+            WgPolicyLayer& ly = P.layer[net][l];
+            ly.K = K;
+            ly.M = l < nh[net] ? hid[net][l] : (net == 0 ? d->n_out : 1);
+            ly.nks = ((ly.K + 1) / 2 + 2 * WGP_GROUP - 1) / (2 * WGP_GROUP) * (2 * WGP_GROUP);
+            ly.ntiles = (ly.M + 31) / 32;
+            ly.w_flat = flat; flat += (uint32_t)ly.M * ly.K;
+            ly.b_flat = flat; flat += (uint32_t)ly.M;
+            ly.w_packed = packed; packed += (uint32_t)ly.ntiles * ly.nks * 64;
+            ly.b_packed = packed; packed += (uint32_t)ly.ntiles * 32;
+            K = ly.M;
+        }
+    }
+    P.log_std_flat = flat; P.log_std_packed = packed;
+    if (P.has_log_std) { flat += d->n_out; packed += d->n_out; }
+    packed += WGP_GROUP * 64;                                      // slack the MFMA loop's last prefetch reads
+    P.n_flat = flat; P.n_packed = packed;
+    p->device = device;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->packed, sizeof(float) * packed);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->flat_stage, sizeof(float) * flat);
+    if (e == hipSuccess) e = hipMemset(p->packed, 0, sizeof(float) * packed);
+    if (e != hipSuccess) {
+        if (p->packed) (void)hipFree(p->packed);
+        if (p->flat_stage) (void)hipFree(p->flat_stage);
+        delete p;
+        return pfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_policy_create: ") + hipGetErrorString(e));
+    }
+    *out = p;
+    return 0;
+}
+
+extern "C" int wg_policy_destroy(wg_policy p) {
+    if (!p) return 0;
+    if (hipSetDevice(p->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        (void)hipFree(p->packed);
+        (void)hipFree(p->flat_stage);
+    }
+    delete p;
+    return 0;
+}
+
+extern "C" int wg_policy_n_params(wg_policy p, size_t* n) {
+    if (!p || !n) return pfail(WG_ERR_INVALID, "wg_policy_n_params: null argument");
+    *n = p->P.n_flat;
+    return 0;
+}
+
+extern "C" int wg_policy_set_params(wg_policy p, const float* params, size_t n, int on_device, void* stream) {
+    if (!p || !params) return pfail(WG_ERR_INVALID, "wg_policy_set_params: null argument");
+    if (n != p->P.n_flat)
+        return pfail(WG_ERR_INVALID, "wg_policy_set_params: " + std::to_string(n) + " parameters given, the policy has " + std::to_string(p->P.n_flat));
+    if (int rc = p_use_device(p)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const float* src = params;
+    if (!on_device) {
+        PHIPCHK(hipMemcpyAsync(p->flat_stage, params, sizeof(float) * n, hipMemcpyHostToDevice, st));
+        src = p->flat_stage;
+    }
+    hipLaunchKernelGGL(k_policy_pack, dim3((p->P.n_packed + 255) / 256), dim3(256), 0, st, p->P, src, p->packed);
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
+// wg_policy_act + optionally the critic on a second set of n_rows rows (obs2_dev -> value2_dev) in the same launch
+extern "C" int wg_policy_act2_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
+                               uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev,
+                               const float* obs2_dev, float* value2_dev, void* stream) {
+    if (!p || !obs_dev) return pfail(WG_ERR_INVALID, "wg_policy_act: null argument");
+    if (n_rows < 0) return pfail(WG_ERR_INVALID, "wg_policy_act: n_rows < 0");
+    const bool actor = action_dev || raw_dev || logp_dev, critic = value_dev != nullptr;
+    if (!obs2_dev || !value2_dev) obs2_dev = nullptr, value2_dev = nullptr;
+    if ((critic || obs2_dev) && p->P.n_layers[1] == 0) return pfail(WG_ERR_INVALID, "wg_policy_act: value requested from a policy without a critic");
+    if (actor && !p->P.has_log_std && (!deterministic || logp_dev))
+        return pfail(WG_ERR_INVALID, "wg_policy_act: a stochastic action / a log-probability needs a policy with log_std");
+    if (n_rows == 0 || (!actor && !critic && !obs2_dev)) return 0;
+    if (int rc = p_use_device(p)) return rc;
+    const dim3 grid((n_rows + WGP_TILE - 1) / WGP_TILE, (actor ? 1 : 0) + (critic ? 1 : 0) + (obs2_dev ? 1 : 0));
+    hipLaunchKernelGGL(k_policy, grid, dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, p->P, p->packed, obs_dev, n_rows,
+                       deterministic ? 1 : 0, seed, counter, row_offset, action_dev, raw_dev, logp_dev, value_dev, actor ? 0 : 1, obs2_dev, value2_dev);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return pfail(WG_ERR_HIP, std::string("wg_policy_act: kernel launch failed: ") + hipGetErrorString(le));
+    return 0;
+}
+
+extern "C" int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
+                             uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev,
+                             void* stream) {
+    return wg_policy_act2_(p, n_rows, obs_dev, deterministic, seed, counter, row_offset, action_dev, raw_dev, logp_dev, value_dev,
+                           nullptr, nullptr, stream);
+}

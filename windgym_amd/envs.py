@@ -280,6 +280,83 @@ class WindFarmVecEnv(_gym_vector_base()):
         infos["_final_obs"] = trunc_b
         return self._out(obs), self._out(rew), self._out(term), trunc_b, infos
 
+    def rollout(self, policy, n_steps, *, deterministic=False, record=(), values=True):
+        """``n_steps`` closed-loop steps ``policy -> step`` enqueued by ONE library call (wg_rollout: no return to Python, no
+        host synchronisation in between).  Returns a dict of CUDA tensors, T = n_steps: ``obs [T+1, B, O]`` (``obs[0]`` = the
+        batch's current observation), ``actions`` / ``raw [T, B, N]``, ``logp``, ``value``, ``final_value``, ``reward [T, B]``,
+        ``truncated [T, B]`` (uint8), ``final_obs [T, B, O]`` and one ``[T, ...]`` entry per name in ``record`` (names of
+        ``config.INFO``).  The buffers are allocated on the first call for a given ``(T, record)`` and REUSED: the returned
+        tensors are valid until the next ``rollout()``.  Afterwards the batch's persistent outputs hold step T-1's, as if it
+        had been a ``step()``: the two interleave freely.
+
+        This env never terminates: every episode ends by truncation, so an advantage estimate bootstraps from
+        ``final_value[t] = V(final_obs[t])``, the value of the state step t ended in (also when the env was reset in the same
+        step):  ``delta_t = r_t + gamma * final_value_t - value_t``,
+        ``A_t = delta_t + gamma * lambda * (1 - truncated_t) * A_{t+1}``.
+
+        Noise: seed = the env's base seed, row offset = this shard's first global env, counter = a running count of policy
+        steps of this env.  With ``sample_site`` the site table is refreshed by torch ops between steps: there, and only there,
+        the equivalent loop of ``act`` + ``step`` runs from Python into the same buffers."""
+        import ctypes as C
+        from .binding import CRolloutBufs, _chk
+        from .config import INFO
+        t, b = self.torch, self.batch
+        T, B, N, O = int(n_steps), self.num_envs, self.n_turb, b.obs_dim
+        if T < 1:
+            raise ValueError("rollout(): n_steps must be >= 1")
+        if policy.n_in != O or policy.n_out != N:
+            raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, the env needs {O} -> {N}")
+        record = tuple(record)
+        for name in record:
+            if name not in INFO:
+                raise ValueError(f"rollout(): unknown info field {name!r}")
+        values = bool(values) and policy.has_critic
+        stochastic_ok = policy.desc["has_log_std"]
+        key = (T, record, values, stochastic_ok)
+        cache = self.__dict__.setdefault("_rollout_bufs", {})
+        bufs = cache.get(key)
+        if bufs is None:
+            f32 = dict(dtype=t.float32, device=b.device)
+            bufs = dict(obs=t.zeros((T + 1, B, O), **f32), actions=t.zeros((T, B, N), **f32), raw=t.zeros((T, B, N), **f32),
+                        reward=t.zeros((T, B), **f32), truncated=t.zeros((T, B), dtype=t.uint8, device=b.device),
+                        final_obs=t.zeros((T, B, O), **f32))
+            if stochastic_ok:
+                bufs["logp"] = t.zeros((T, B), **f32)
+            if values:
+                bufs["value"], bufs["final_value"] = t.zeros((T, B), **f32), t.zeros((T, B), **f32)
+            for name in record:
+                shape, dtype = b.info_shape(name)
+                bufs[name] = t.zeros((T,) + tuple(shape), dtype=dtype, device=b.device)
+            cache[key] = bufs
+        bufs["obs"][0].copy_(b.obs)
+        seed = 0 if self._base_seed is None else int(self._base_seed)
+        counter0 = getattr(self, "_policy_steps", 0)
+        self._policy_steps = counter0 + T
+        if self._site is not None:
+            for i in range(T):
+                policy.act(bufs["obs"][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
+                           row_offset=self._global_offset, value=values,
+                           out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
+                                bufs["value"][i] if values else None))
+                o, r, tr, f = self._step_device(bufs["actions"][i])
+                bufs["obs"][i + 1].copy_(o); bufs["reward"][i].copy_(r); bufs["truncated"][i].copy_(tr); bufs["final_obs"][i].copy_(f)
+                for name in record:
+                    b.info(name, out=bufs[name][i])
+                if values:
+                    policy.value(bufs["final_obs"][i], out=bufs["final_value"][i])
+            return dict(bufs)
+        ptr = lambda k: bufs[k].data_ptr() if k in bufs else None          # noqa: E731
+        cb = CRolloutBufs(ptr("obs"), ptr("actions"), ptr("raw"), ptr("logp"), ptr("value"), ptr("final_obs"),
+                          ptr("final_value"), ptr("reward"), ptr("truncated"), len(record),
+                          (C.c_int32 * max(1, len(record)))(*[INFO[n] for n in record]),
+                          (C.c_void_p * max(1, len(record)))(*[bufs[n].data_ptr() for n in record]))
+        _chk(b.L.wg_rollout(b._h, policy._h, T, int(bool(deterministic)), seed, counter0, self._global_offset,
+                            C.byref(cb), b._stream()), "wg_rollout")
+        # the persistent outputs follow, as after a step()
+        b.obs.copy_(bufs["obs"][T]); b.reward.copy_(bufs["reward"][T - 1]); b.truncated.copy_(bufs["truncated"][T - 1])
+        b.final_obs.copy_(bufs["final_obs"][T - 1])
+        return dict(bufs)
+
     def infos(self, step=False):
         """Lazy info dict: values are fetched from the device on first access (keys of _get_info).  After a step(),
         "Power agent" / "Power baseline" are the farm powers of the step just taken — for an env that truncated, the

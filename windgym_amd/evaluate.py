@@ -75,8 +75,35 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
             rec["yaw_b"][i] = _np(b.info("yaw_base"))
             rec["ws_b"][i] = np.linalg.norm(_np(b.info("rotor_uvw_base")), axis=-1)
 
-    snapshot(0, 0.0)                                               # AgentEval.py:131-147
-    for i in range(1, t_sim):
+    from .binding import HipBatch
+    from .policy import MlpPolicy
+    if isinstance(model, MlpPolicy) and isinstance(b, HipBatch) and t_sim > 1:
+        # Learned policy on the device: snapshot 0 goes into row 0 of device recordings, steps 1 .. t_sim-1 are ONE
+        # rollout (policy and step kernels alternate inside the library), and the recordings cross to the host once.
+        t = b.torch
+        names = dict(powerT_a="power_turb_agent", yaw_a="yaw_agent", ws_a="rotor_uvw_agent", time="fs_time")
+        if two:
+            names.update(powerT_b="power_turb_base", yaw_b="yaw_base", ws_b="rotor_uvw_base")
+        full = {}
+        for k, name in names.items():
+            shape, dtype = b.info_shape(name)
+            full[k] = t.zeros((t_sim,) + tuple(shape), dtype=dtype, device=b.device)
+            b.info(name, out=full[k][0])
+        out = env.rollout(model, t_sim - 1, deterministic=deterministic, record=tuple(names.values()), values=False)
+        for k, name in names.items():
+            full[k][1:].copy_(out[name])
+        host = {k: _np(v) for k, v in full.items()}
+        rec["reward"][1:] = _np(out["reward"])
+        time[:] = host["time"][:, 0]
+        for f in ("a", "b") if two else ("a",):
+            rec["powerT_" + f][:] = host["powerT_" + f]; rec["powerF_" + f][:] = rec["powerT_" + f].sum(-1)
+            rec["yaw_" + f][:] = host["yaw_" + f]
+            rec["ws_" + f][:] = np.linalg.norm(host["ws_" + f], axis=-1)
+        t_loop = 0
+    else:
+        t_loop = t_sim
+        snapshot(0, 0.0)                                           # AgentEval.py:131-147
+    for i in range(1, t_loop):
         action = model.predict(obs, deterministic=deterministic)[0]
         action = np.broadcast_to(np.asarray(action, dtype=np.float32), (B, N))
         obs, reward, _, _, _ = env.step(np.ascontiguousarray(action))

@@ -1,0 +1,322 @@
+"""Learned policies on the device: SB3 ``MlpPolicy`` checkpoints evaluated by the HIP kernel ``k_policy``.
+
+The reference evaluates a stable-baselines3 model on the host (``model.predict(obs, deterministic=...)[0]`` per step,
+WindGym/AgentEval.py:179-190; examples/Example 2: ``PPO.load("PPO_2975000")``).  :class:`MlpPolicy` is that model without
+stable-baselines3: the actor(-critic) MLP of SB3's default ``MlpPolicy`` (separate actor / critic nets, tanh or ReLU,
+state-independent ``log_std``) on CUDA tensors, one kernel launch per ``act()``, and the ``predict()`` protocol so that the
+object goes wherever the scripted agents of :mod:`windgym_amd.agents` go.
+
+:func:`read_sb3_zip` is pure host code and NEVER unpickles anything: ``policy.pth`` is read with
+``torch.load(weights_only=True)``, ``data`` as plain JSON whose ``":serialized:"`` cloudpickle blobs are not touched.
+
+Flat parameter order (``wg_policy_set_params``, include/windgym_hip.h): actor hidden layers (W ``[out][in]`` then b),
+actor head, critic hidden layers, critic head, ``log_std``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import io
+import json
+import re
+import zipfile
+
+import numpy as np
+
+MAX_HIDDEN = 4
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# architecture description + flat layout (host only)
+# ----------------------------------------------------------------------------------------------------------------------
+def make_desc(n_in, n_out, hidden_pi=(64, 64), hidden_vf=(64, 64), activation="tanh", has_log_std=True):
+    """Architecture dict; ``hidden_vf=None`` = no critic."""
+    if activation not in ("tanh", "relu"):
+        raise ValueError(f"activation must be 'tanh' or 'relu', not {activation!r}")
+    return dict(n_in=int(n_in), n_out=int(n_out), hidden_pi=tuple(int(h) for h in hidden_pi),
+                hidden_vf=None if hidden_vf is None else tuple(int(h) for h in hidden_vf),
+                activation=activation, has_log_std=bool(has_log_std))
+
+
+def param_layout(desc):
+    """[(SB3 state-dict name, shape)] in flat-vector order."""
+    out = []
+    k = desc["n_in"]
+    for i, h in enumerate(desc["hidden_pi"]):
+        out += [(f"mlp_extractor.policy_net.{2 * i}.weight", (h, k)), (f"mlp_extractor.policy_net.{2 * i}.bias", (h,))]
+        k = h
+    out += [("action_net.weight", (desc["n_out"], k)), ("action_net.bias", (desc["n_out"],))]
+    if desc["hidden_vf"] is not None:
+        k = desc["n_in"]
+        for i, h in enumerate(desc["hidden_vf"]):
+            out += [(f"mlp_extractor.value_net.{2 * i}.weight", (h, k)), (f"mlp_extractor.value_net.{2 * i}.bias", (h,))]
+            k = h
+        out += [("value_net.weight", (1, k)), ("value_net.bias", (1,))]
+    if desc["has_log_std"]:
+        out.append(("log_std", (desc["n_out"],)))
+    return out
+
+
+def n_params(desc):
+    return int(sum(int(np.prod(s)) for _, s in param_layout(desc)))
+
+
+def pack_params(desc, tensors):
+    """{name: array} -> flat float32 vector."""
+    parts = []
+    for name, shape in param_layout(desc):
+        if name not in tensors:
+            raise ValueError(f"missing tensor {name!r}")
+        a = np.asarray(tensors[name], dtype=np.float32)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(a.shape)}, expected {tuple(shape)}")
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts) if parts else np.zeros(0, np.float32)
+
+
+def unpack_params(desc, flat):
+    """flat vector -> {name: float32 array}."""
+    flat = np.asarray(flat, dtype=np.float32).reshape(-1)
+    if flat.size != n_params(desc):
+        raise ValueError(f"{flat.size} parameters given, the architecture has {n_params(desc)}")
+    out, o = {}, 0
+    for name, shape in param_layout(desc):
+        n = int(np.prod(shape))
+        out[name] = flat[o:o + n].reshape(shape).copy()
+        o += n
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# SB3 checkpoint reader (host only, no unpickling)
+# ----------------------------------------------------------------------------------------------------------------------
+def _chain(tensors, prefix, n_in, what):
+    idx = sorted({int(m.group(1)) for k in tensors for m in [re.fullmatch(re.escape(prefix) + r"\.(\d+)\.weight", k)] if m})
+    hidden, k = [], n_in
+    for i in idx:
+        w, b = tensors[f"{prefix}.{i}.weight"], tensors.get(f"{prefix}.{i}.bias")
+        if b is None:
+            raise ValueError(f"missing tensor {prefix}.{i}.bias")
+        if w.ndim != 2 or w.shape[1] != k or b.shape != (w.shape[0],):
+            raise ValueError(f"{what}: shapes do not chain at {prefix}.{i} (weight {w.shape}, bias {b.shape}, input width {k})")
+        hidden.append(int(w.shape[0]))
+        k = int(w.shape[0])
+    return hidden, k
+
+
+def read_sb3_zip(path, activation="tanh"):
+    """-> (desc, {SB3 name: float32 array}) of a stable-baselines3 >= 2.0 ``MlpPolicy`` checkpoint (PPO / A2C ``.zip``).
+
+    The architecture comes from the tensor names and shapes; the activation is not in the tensors (SB3's default: tanh).
+    Raises ValueError naming the reason for: ``use_sde``, a shared trunk, a non-flatten feature extractor, missing tensors,
+    shapes that do not chain."""
+    import torch
+    with zipfile.ZipFile(path) as z:
+        names = z.namelist()
+        if "policy.pth" not in names:
+            raise ValueError("not an SB3 checkpoint: no policy.pth in the archive")
+        if "data" in names:
+            data = json.loads(z.read("data").decode())          # plain JSON; ":serialized:" blobs stay strings
+            if isinstance(data, dict) and data.get("use_sde") is True:
+                raise ValueError("use_sde: true — state-dependent exploration is not supported")
+        sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+    tensors = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in sd.items()}
+    if any(k.startswith("mlp_extractor.shared_net.") for k in tensors):
+        raise ValueError("shared trunk (mlp_extractor.shared_net.*): only separate actor / critic nets are supported")
+    if any(k.startswith(("features_extractor.", "pi_features_extractor.", "vf_features_extractor.")) for k in tensors):
+        raise ValueError("non-flatten feature extractor (features_extractor.* parameters) is not supported")
+    for k in ("action_net.weight", "action_net.bias"):
+        if k not in tensors:
+            raise ValueError(f"missing tensor {k}")
+    aw = tensors["action_net.weight"]
+    first = tensors.get("mlp_extractor.policy_net.0.weight", aw)
+    n_in, n_out = int(first.shape[1]), int(aw.shape[0])
+    hidden_pi, k = _chain(tensors, "mlp_extractor.policy_net", n_in, "actor")
+    if aw.shape != (n_out, k) or tensors["action_net.bias"].shape != (n_out,):
+        raise ValueError(f"actor: shapes do not chain at action_net (weight {aw.shape}, input width {k})")
+    hidden_vf = None
+    if "value_net.weight" in tensors:
+        if "value_net.bias" not in tensors:
+            raise ValueError("missing tensor value_net.bias")
+        hidden_vf, k = _chain(tensors, "mlp_extractor.value_net", n_in, "critic")
+        if tensors["value_net.weight"].shape != (1, k) or tensors["value_net.bias"].shape != (1,):
+            raise ValueError(f"critic: shapes do not chain at value_net (weight {tensors['value_net.weight'].shape}, input width {k})")
+    elif any(k2.startswith("mlp_extractor.value_net.") for k2 in tensors):
+        raise ValueError("missing tensor value_net.weight")
+    has_ls = "log_std" in tensors
+    if has_ls and tensors["log_std"].shape != (n_out,):
+        raise ValueError(f"log_std: shape {tensors['log_std'].shape}, expected ({n_out},)")
+    desc = make_desc(n_in, n_out, hidden_pi, hidden_vf, activation, has_ls)
+    return desc, {name: tensors[name] for name, _ in param_layout(desc)}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the device object
+# ----------------------------------------------------------------------------------------------------------------------
+class MlpPolicy:
+    """SB3's default ``MlpPolicy`` (actor ``n_in -> hidden_pi -> n_out``, critic ``n_in -> hidden_vf -> 1``) on one GPU.
+
+    ``params`` is ONE flat float32 CUDA leaf tensor (a torch optimiser can own it); ``state_dict()`` returns views of it
+    under SB3's names.  The kernel reads its own packed copy: after changing ``params`` call :meth:`sync`.
+    Raises ``WindGymHipError`` without the built library or a GPU — there is no CPU fallback."""
+
+    def __init__(self, n_in, n_out, hidden_pi=(64, 64), hidden_vf=(64, 64), activation="tanh", device=None, seed=0,
+                 has_log_std=True):
+        import torch
+        from .binding import ACTV, CPolicyDesc, WindGymHipError, _chk, load_library
+        self.desc = make_desc(n_in, n_out, hidden_pi, hidden_vf, activation, has_log_std)
+        if len(self.desc["hidden_pi"]) > MAX_HIDDEN or len(self.desc["hidden_vf"] or ()) > MAX_HIDDEN:
+            raise NotImplementedError(f"at most {MAX_HIDDEN} hidden layers per net")
+        self.L = load_library()
+        if not torch.cuda.is_available():
+            raise WindGymHipError("no HIP device visible: MlpPolicy only runs on the GPU (no CPU fallback; the numpy "
+                                  "restatement under oracle/ is test-only)")
+        self.torch, self._chk = torch, _chk
+        self.device_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index)
+        d = CPolicyDesc()
+        d.n_in, d.n_out, d.activation = self.desc["n_in"], self.desc["n_out"], ACTV[activation]
+        d.n_hidden_pi = len(self.desc["hidden_pi"])
+        for i, h in enumerate(self.desc["hidden_pi"]):
+            d.hidden_pi[i] = h
+        d.n_hidden_vf = -1 if self.desc["hidden_vf"] is None else len(self.desc["hidden_vf"])
+        for i, h in enumerate(self.desc["hidden_vf"] or ()):
+            d.hidden_vf[i] = h
+        d.has_log_std = int(self.desc["has_log_std"])
+        h = C.c_void_p()
+        _chk(self.L.wg_policy_create(C.byref(d), self.device_index, C.byref(h)), "wg_policy_create")
+        self._h = h
+        n = C.c_size_t()
+        _chk(self.L.wg_policy_n_params(self._h, C.byref(n)), "wg_policy_n_params")
+        assert n.value == n_params(self.desc)
+        self.n_in, self.n_out, self.has_critic = self.desc["n_in"], self.desc["n_out"], self.desc["hidden_vf"] is not None
+        # seeded init: N(0, 1 / fan_in) weights, zero biases and log_std (SB3's orthogonal init is a trainer's business)
+        rng = np.random.default_rng(seed)
+        t = {name: (rng.standard_normal(shape) / np.sqrt(shape[1])).astype(np.float32) if len(shape) == 2
+             else np.zeros(shape, np.float32) for name, shape in param_layout(self.desc)}
+        self.params = torch.from_numpy(pack_params(self.desc, t)).to(self.device).requires_grad_(False)
+        self._views = None
+        self._out = {}
+        self.counter = 0            # running count of stochastic act() calls: no noise is ever reused
+        self.seed = int(seed)
+        self.sync()
+
+    @classmethod
+    def from_sb3_zip(cls, path, activation="tanh", device=None, seed=0):
+        desc, tensors = read_sb3_zip(path, activation=activation)
+        p = cls(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], activation, device=device, seed=seed,
+                has_log_std=desc["has_log_std"])
+        p.load_state_dict(tensors)
+        return p
+
+    # -- lifetime -----------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.wg_policy_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    # -- parameters ---------------------------------------------------------------------------------
+    def state_dict(self):
+        """{SB3 name: view of ``params``}."""
+        out, o = {}, 0
+        for name, shape in param_layout(self.desc):
+            n = int(np.prod(shape))
+            out[name] = self.params.detach()[o:o + n].view(shape)
+            o += n
+        return out
+
+    def load_state_dict(self, sd):
+        flat = pack_params(self.desc, {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in sd.items()})
+        with self.torch.no_grad():
+            self.params.copy_(self.torch.from_numpy(flat))
+        self.sync()
+        return self
+
+    def sync(self):
+        """Push ``params`` (device pointer, no host trip) into the kernel's packed copy — after an optimiser step."""
+        self._chk(self.L.wg_policy_set_params(self._h, C.c_void_p(self.params.data_ptr()), self.params.numel(), 1,
+                                              self._stream()), "wg_policy_set_params")
+
+    def torch_forward(self, obs):
+        """(mean, value) with ``F.linear`` / tanh on the same parameters — differentiable (a trainer's loss goes through
+        it); value is None without a critic."""
+        F = self.torch.nn.functional
+        act = self.torch.tanh if self.desc["activation"] == "tanh" else F.relu
+        views, o = {}, 0
+        for name, shape in param_layout(self.desc):
+            n = int(np.prod(shape))
+            views[name] = self.params[o:o + n].view(shape)
+            o += n
+
+        def net(prefix, n_hidden, head):
+            x = obs
+            for i in range(n_hidden):
+                x = act(F.linear(x, views[f"{prefix}.{2 * i}.weight"], views[f"{prefix}.{2 * i}.bias"]))
+            return F.linear(x, views[head + ".weight"], views[head + ".bias"])
+
+        mean = net("mlp_extractor.policy_net", len(self.desc["hidden_pi"]), "action_net")
+        value = net("mlp_extractor.value_net", len(self.desc["hidden_vf"]), "value_net")[..., 0] if self.has_critic else None
+        return mean, value
+
+    # -- evaluation ---------------------------------------------------------------------------------
+    def _buffers(self, n):
+        b = self._out.get(n)
+        if b is None:
+            t, f32 = self.torch, dict(dtype=self.torch.float32, device=self.device)
+            b = (t.zeros((n, self.n_out), **f32), t.zeros((n, self.n_out), **f32), t.zeros(n, **f32), t.zeros(n, **f32))
+            self._out[n] = b
+        return b
+
+    def act(self, obs, deterministic=False, counter=None, *, seed=None, row_offset=0, value=True, out=None):
+        """ONE launch of k_policy on a contiguous float32 CUDA tensor ``[..., n_in]`` -> persistent ``(action, raw, logp,
+        value)`` tensors (rows = the leading dimensions flattened; valid until the next ``act()`` on as many rows; value is
+        None without a critic or with ``value=False``).  No synchronisation.  ``counter`` defaults to a running count."""
+        t = self.torch
+        if not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
+                and obs.shape[-1] == self.n_in):
+            raise ValueError(f"act(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in}]")
+        n = obs.numel() // self.n_in
+        a, r, lp, v = out if out is not None else self._buffers(n)
+        want_v = value and self.has_critic
+        stochastic = not deterministic
+        if counter is None:
+            counter = self.counter
+            if stochastic:
+                self.counter += 1
+        ls = self.desc["has_log_std"]
+        rc = self.L.wg_policy_act(self._h, n, obs.data_ptr(), int(bool(deterministic)),
+                                  self.seed if seed is None else int(seed), int(counter), int(row_offset),
+                                  a.data_ptr(), r.data_ptr(), lp.data_ptr() if ls else None,
+                                  v.data_ptr() if want_v else None, self._stream())
+        if rc:
+            self._chk(rc, "wg_policy_act")
+        return a, r, (lp if ls else None), (v if want_v else None)
+
+    def value(self, obs, out=None):
+        """Critic only: V(obs) -> float32 CUDA tensor [rows]."""
+        t = self.torch
+        if not self.has_critic:
+            raise ValueError("value(): the policy has no critic")
+        n = obs.numel() // self.n_in
+        v = out if out is not None else t.zeros(n, dtype=t.float32, device=self.device)
+        self._chk(self.L.wg_policy_act(self._h, n, obs.data_ptr(), 1, 0, 0, 0, None, None, None, v.data_ptr(),
+                                       self._stream()), "wg_policy_act")
+        return v
+
+    def predict(self, obs, state=None, episode_start=None, deterministic=False):
+        """stable-baselines3's protocol: numpy or tensor, ``[O]`` or ``[B, O]`` -> ``(numpy action, None)``."""
+        t = self.torch
+        x = obs if isinstance(obs, t.Tensor) else t.from_numpy(np.ascontiguousarray(obs, dtype=np.float32))
+        single = x.ndim == 1
+        x = x.to(self.device, dtype=t.float32).reshape(-1, self.n_in).contiguous()
+        a = self.act(x, deterministic=deterministic, value=False)[0]
+        a = a.detach().cpu().numpy().copy()
+        return (a[0] if single else a), None
