@@ -476,6 +476,80 @@ typedef struct wg_rollout_bufs {
 int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                uint64_t row_offset, const wg_rollout_bufs* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training on the device: what `PPO("MlpPolicy", env, n_steps=2048).learn(...)` does between two rollouts
+ * (examples/longer_steps_example.py:212-240, examples/curriculum.py:544-560) — advantages, the clipped-surrogate loss and
+ * its gradient, gradient clipping and Adam — for the wg_policy above (windgym_amd/csrc/wg_ppo.hip).  fp32 throughout; every
+ * entry is asynchronous on `stream`, synchronises nothing and is bit-identical from run to run (no float atomics; every sum
+ * has an order fixed by the shapes alone).
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_ppo_s* wg_ppo;
+
+/* SB3's RolloutBuffer.compute_returns_and_advantage (longer_steps_example.py:232-240: model.learn) on wg_rollout's buffers
+ * [T, B], with the bootstrap this never-terminating env needs (wg_rollout above):
+ *   delta_t = r_t + gamma * final_value_t - value_t,   A_t = delta_t + gamma * lambda * (1 - truncated_t) * A_{t+1},  A_T = 0,
+ *   returns_t = A_t + value_t.   One launch on the current device.                                                 */
+int wg_gae(int T, int B, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+           const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out, void* stream);
+
+/* The optimiser of `p` (curriculum.py:544-560: PPO(...) owns torch.optim.Adam): Adam's moments and step count, the scratch
+ * of the gradient kernel.  `p` must outlive it.  WG_ERR_INVALID: a policy without a critic or without log_std.     */
+int wg_ppo_create(wg_policy p, wg_ppo* out);
+int wg_ppo_destroy(wg_ppo o);
+
+/* Checkpoint / resume (curriculum.py:544-560 saves and reloads models between stages): Adam's m then v as ONE host vector
+ * of n = 2 * wg_policy_n_params floats, and the step count.  Synchronises the device.                              */
+int wg_ppo_get_state(wg_ppo o, float* mv_host, size_t n, uint64_t* step);
+int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64_t step);
+
+/* A rollout flattened to n_rows = T * B rows (device pointers; wg_rollout's obs[0..T-1], raw, logp and wg_gae's outputs). */
+typedef struct wg_ppo_batch {
+    const float* obs;        /* [n_rows, n_in]  */
+    const float* raw;        /* [n_rows, n_out] the unclipped actions the buffer stores */
+    const float* logp;       /* [n_rows]        log-probability at collection time      */
+    const float* advantage;  /* [n_rows]        */
+    const float* returns;    /* [n_rows]        */
+    int64_t n_rows;
+} wg_ppo_batch;
+
+typedef struct wg_ppo_hyper {      /* SB3's PPO arguments of the same names (longer_steps_example.py:212-231) */
+    float clip_range, vf_coef, ent_coef;
+    int32_t normalize_advantage;   /* ignored for a minibatch of one row, as in SB3 */
+} wg_ppo_hyper;
+
+typedef struct wg_ppo_stats {      /* means over the minibatch: what SB3 logs as train/... */
+    float pi_loss, v_loss, entropy, approx_kl, clip_fraction, loss, adv_mean, adv_std;
+} wg_ppo_stats;
+
+/* One minibatch of SB3's PPO.train (longer_steps_example.py:232-240), loss and gradient only: rows index_dev[0 .. n-1] of
+ * the batch (int32, device; entries outside [0, n_rows) are skipped) or, with index_dev = NULL, rows first .. first + n - 1.
+ *   logp = sum_j (-((raw_j - mean_j) / exp(log_std_j))^2 / 2 - log_std_j - log(2 pi) / 2),   ratio = exp(logp - logp_old),
+ *   A^ = (A - mean_mb(A)) / (std_mb(A) + 1e-8) (unbiased std) with normalize_advantage, else A,
+ *   L_pi = -min(ratio A^, clip(ratio, 1 - eps, 1 + eps) A^),  L_v = (returns - V)^2,  H = sum_j (1/2 + log(2 pi)/2 + log_std_j),
+ *   loss = mean(L_pi) + vf_coef mean(L_v) - ent_coef mean(H),   approx_kl = mean((ratio - 1) - log ratio),
+ *   clip_fraction = mean(|ratio - 1| > eps).
+ * grad_out f32[wg_policy_n_params] = d loss / d params in the flat layout of wg_policy_set_params; stats_out (device, may be
+ * NULL) the record above.  params_dev must be the vector the policy was last given (wg_policy_set_params / wg_ppo_apply):
+ * the forward pass is k_policy's, so with unchanged parameters ratio = 1 to rounding.  A data-parallel trainer all-reduces
+ * grad_out between this call and wg_ppo_apply.                                                                       */
+int wg_ppo_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* batch, const int32_t* index_dev, int64_t first, int n,
+                const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream);
+
+/* torch.nn.utils.clip_grad_norm_(max_grad_norm) + torch.optim.Adam.step (betas 0.9 / 0.999, eps 1e-5 as SB3's PPO sets it,
+ * bias-corrected, no weight decay) on params_dev IN PLACE, then wg_policy_set_params(p, params_dev) in stream order:
+ * wg_policy_act / wg_rollout enqueued afterwards see the new weights (longer_steps_example.py:232-240).            */
+int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream);
+
+/* SB3's PPO.train for one rollout (longer_steps_example.py:232-240), enqueued by one call, no host synchronisation, no
+ * allocation: n_mb = ceil(n_rows / batch_size) minibatches per epoch, the last one shorter when batch_size does not divide
+ * n_rows (as SB3's RolloutBuffer.get yields it); perm_dev int32[n_epochs, n_rows] holds a permutation of 0 .. n_rows-1 per
+ * epoch; stats_out (device, may be NULL) is wg_ppo_stats[n_epochs, n_mb].  Bit-identical to
+ *     for e in 0 .. n_epochs-1:  for k in 0 .. n_mb-1:
+ *         wg_ppo_grad(o, params_dev, batch, perm_dev + e * n_rows + k * batch_size, 0, min(batch_size, n_rows - k * batch_size),
+ *                     hp, g, stats_out + e * n_mb + k);   wg_ppo_apply(o, params_dev, g, lr, max_grad_norm)                */
+int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
+                  int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,363 @@
+"""GPU tests of training on the device (windgym_amd/csrc/wg_ppo.hip, windgym_amd/ppo.py): k_gae, k_ppo_grad, the Adam step,
+wg_ppo_update and PPO.learn against oracle/ppo_oracle.py (float64, gradients from autograd) and a torch reference trainer."""
+import os
+
+import numpy as np
+import pytest
+
+from oracle import policy_oracle as po
+from oracle import ppo_oracle as oo
+from windgym_amd.policy import pack_params, param_layout
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(8, (64, 64), 4), (32, (64, 64), 16), (7, (33,), 1), (200, (128, 128, 128), 2), (1600, (256, 256), 16),
+          (160, (64, 64), 80), (32, (), 16)]                        # tests/test_gpu_policy.py's
+STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss")
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def make(n_in, hidden, n_out, activation="tanh", seed=3):
+    """A policy with every tensor away from its initial value (biases and log_std included) + its float64 state dict."""
+    from windgym_amd.policy import MlpPolicy
+    p = MlpPolicy(n_in, n_out, hidden, hidden, activation, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    sd = {}
+    for name, shape in param_layout(p.desc):
+        a = p.state_dict()[name].cpu().numpy()
+        if len(shape) == 1:
+            a = rng.uniform(-0.3, 0.3, shape).astype(np.float32)
+        sd[name] = a
+    p.load_state_dict(sd)
+    return p, {k: v.astype(np.float64) for k, v in sd.items()}
+
+
+def batch(sd, n_in, n_out, n, activation, seed=0):
+    """Random rows whose ratios straddle both clip bounds: logp_old = the true log-probability + N(0, 0.3)."""
+    rng = np.random.default_rng(seed)
+    obs = rng.uniform(-1, 1, (n, n_in)).astype(np.float32)
+    mean, value = po.forward(sd, obs, activation)
+    std = np.exp(sd["log_std"])
+    raw = (mean + std * rng.standard_normal((n, n_out))).astype(np.float32)
+    z = (raw - mean) / std
+    logp = np.sum(-0.5 * z * z - sd["log_std"] - 0.5 * np.log(2 * np.pi), axis=1)
+    logp_old = (logp + 0.3 * rng.standard_normal(n)).astype(np.float32)
+    adv = rng.standard_normal(n).astype(np.float32) * 2.0 + 0.5
+    ret = (value + rng.standard_normal(n)).astype(np.float32)
+    return obs, raw, logp_old, adv, ret
+
+
+def dev(*arrays):
+    t = _torch()
+    return [t.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+def flat_grad(desc, grads):
+    return pack_params(desc, {k: v.astype(np.float32) for k, v in grads.items()}).astype(np.float64)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T,B", [(1, 1), (7, 389), (128, 4096), (128, 1), (1, 4096)])
+def test_gae_vs_oracle(T, B):
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    p, _ = make(8, (16,), 2)
+    opt = PPOOptimizer(p)
+    rng = np.random.default_rng(T * 10007 + B)
+    r, v, fv = (rng.standard_normal((T, B)).astype(np.float32) for _ in range(3))
+    tr = (rng.uniform(size=(T, B)) < 0.1).astype(np.uint8)
+    adv, ret = opt.gae(*dev(r, v, fv, tr), 0.99, 0.95)
+    ra, rr = oo.gae(r, v, fv, tr, 0.99, 0.95)
+    assert np.allclose(adv.cpu().numpy(), ra, rtol=1e-5, atol=2e-5) and np.allclose(ret.cpu().numpy(), rr, rtol=1e-5, atol=2e-5)
+    t.cuda.synchronize()
+    opt.close(); p.close()
+
+
+@pytest.mark.parametrize("activation", ["tanh", "relu"])
+@pytest.mark.parametrize("shape", SHAPES, ids=[f"{a}-{'x'.join(map(str, h)) or 'none'}-{o}" for a, h, o in SHAPES])
+def test_grad_vs_autograd_oracle(shape, activation):
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    n_in, hidden, n_out = shape
+    p, sd = make(n_in, hidden, n_out, activation)
+    opt = PPOOptimizer(p)
+    # (n, index array?, normalise?); 65 536 rows of 1600 inputs would need a gigabyte for the float64 oracle: skipped there
+    cases = [(1, False, True), (33, True, True), (389, False, True), (4096, True, False)] + ([(65536, True, True)] if n_in <= 200 else [])
+    for n, use_index, norm in cases:
+        extra = 37
+        obs, raw, lpo, adv, ret = batch(sd, n_in, n_out, n + extra, activation, seed=n)
+        rng = np.random.default_rng(n + 1)
+        rows = rng.permutation(n + extra)[:n] if use_index else np.arange(5, 5 + n)
+        kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=norm)
+        d = dev(obs, raw, lpo, adv, ret)
+        if use_index:
+            g, st = opt.grad(*d, index=dev(rows.astype(np.int32))[0], **kw)
+        else:
+            g, st = opt.grad(*d, first=5, n=n, **kw)
+        g, st = g.cpu().numpy().astype(np.float64), st.cpu().numpy()
+        _, grads, rs, ratio = oo.loss_and_grad(sd, obs[rows], raw[rows], lpo[rows], adv[rows], ret[rows], activation=activation, **kw)
+        if n >= 389:
+            assert (ratio > 1.2).any() and (ratio < 0.8).any()           # both clip sides are exercised
+        ref = flat_grad(p.desc, grads)
+        err = np.abs(g - ref).max()
+        assert err <= 1e-4 * np.linalg.norm(ref) + 1e-6, (n, err, np.linalg.norm(ref))
+        for i, k in enumerate(STATS):
+            # (a ratio within rounding of a clip bound may fall on the other side in float32: two rows of slack there)
+            tol = 2.0 / n if k == "clip_fraction" else 1e-5 * max(1.0, abs(rs[k]))
+            assert abs(st[i] - rs[k]) <= tol, (n, k, st[i], rs[k])
+    opt.close(); p.close()
+
+
+def test_grad_is_bit_identical_from_run_to_run():
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    p, sd = make(32, (64, 64), 16)
+    opt = PPOOptimizer(p)
+    n = 20000
+    d = dev(*batch(sd, 32, 16, n, "tanh", seed=9))
+    idx = dev(np.random.default_rng(1).permutation(n).astype(np.int32))[0]
+    outs = []
+    for _ in range(3):
+        g, st = opt.grad(*d, index=idx, ent_coef=0.01)
+        outs.append((g.clone(), st.clone()))
+        opt.grad(*d, first=0, n=777)                                      # other work in between leaves no trace
+    for g, st in outs[1:]:
+        assert t.equal(g, outs[0][0]) and t.equal(st, outs[0][1])
+    opt.close(); p.close()
+
+
+def _venv(n_envs=64, **kw):
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.turbine import V80
+    args = dict(yaml_dict=presets.bench_cfg2_config(), seed=77, as_torch=True, turbtype="None", n_passthrough=1, n_rotor_pts=16)
+    args.update(kw)
+    v = WindFarmVecEnv(V80(), n_envs, **args)
+    v.reset(seed=77)
+    return v
+
+
+def test_unchanged_parameters_give_ratio_one():
+    """The forward recomputation is k_policy's: on a fresh rollout mean and V are the stored ones, so nothing is clipped."""
+    from windgym_amd.ppo import PPO
+    t = _torch()
+    v = _venv(64)
+    ppo = PPO("MlpPolicy", v, n_steps=16, seed=2)
+    with t.no_grad():
+        ppo.policy.params[-v.n_turb:].uniform_(-0.5, 0.2)                # log_std away from 0
+    ppo.policy.sync()
+    out = ppo.collect()
+    O, N = ppo.policy.n_in, ppo.policy.n_out
+    g, st = ppo.opt.grad(out["obs"][:16].view(-1, O), out["raw"].view(-1, N), out["logp"].view(-1), out["advantage"].view(-1),
+                         out["returns"].view(-1))
+    st = st.cpu().numpy()
+    assert abs(st[3]) <= 1e-9 and st[4] == 0.0, st
+    # the ratios themselves, from the float64 oracle on the same buffers
+    sd = {k: x.cpu().numpy().astype(np.float64) for k, x in ppo.policy.state_dict().items()}
+    arrs = [out[k].cpu().numpy() for k in ("raw", "logp", "advantage", "returns")]
+    _, _, _, ratio = oo.loss_and_grad(sd, out["obs"][:16].reshape(-1, O).cpu().numpy(), arrs[0].reshape(-1, N), arrs[1].reshape(-1),
+                                      arrs[2].reshape(-1), arrs[3].reshape(-1))
+    assert np.abs(ratio - 1.0).max() <= 1e-5
+    # and V: the value loss of the kernel is that of the stored values, to rounding
+    lv = float(((out["returns"] - out["value"]).double() ** 2).mean())
+    assert abs(st[1] - lv) <= 1e-6 * max(1.0, lv)
+    ppo.close(); ppo.policy.close(); v.close()
+
+
+@pytest.mark.parametrize("max_norm", [0.05, 1e6])
+def test_apply_vs_oracle_and_repack(max_norm):
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    p, sd = make(32, (64, 64), 16)
+    opt = PPOOptimizer(p)
+    rng = np.random.default_rng(4)
+    nf = p.params.numel()
+    ref, m, v = p.params.cpu().numpy().astype(np.float64), np.zeros(nf), np.zeros(nf)
+    x = dev(rng.uniform(-1, 1, (64, 32)).astype(np.float32))[0]
+    for step in range(1, 21):
+        gnp = (rng.standard_normal(nf) * 0.1).astype(np.float32)
+        before = p.act(x, deterministic=True)[1].clone()
+        opt.apply(dev(gnp)[0], learning_rate=1e-3, max_grad_norm=max_norm)
+        ref, m, v = oo.adam_step(ref, gnp, m, v, step, 1e-3, max_norm)
+        assert np.abs(p.params.cpu().numpy() - ref).max() <= 2e-6, step
+        after = p.act(x, deterministic=True)[1].clone()
+        assert not t.equal(after, before)
+        p.sync()                                                          # the repack already happened: sync() changes nothing
+        assert t.equal(p.act(x, deterministic=True)[1], after)
+    mv, s = opt.state()
+    assert s == 20 and np.allclose(mv[:nf], m, atol=1e-6) and np.allclose(mv[nf:], v, atol=1e-7)
+    opt.close(); p.close()
+
+
+def test_update_equals_the_documented_loop():
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    n, bs, E = 1000, 300, 3                                               # ragged: minibatches of 300, 300, 300, 100
+    pa, sd = make(32, (64, 64), 16)
+    pb, _ = make(32, (64, 64), 16)
+    oa, ob = PPOOptimizer(pa), PPOOptimizer(pb)
+    d = dev(*batch(sd, 32, 16, n, "tanh", seed=5))
+    perm = t.stack([t.randperm(n, device="cuda") for _ in range(E)]).to(t.int32).contiguous()
+    kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=True)
+    sa = oa.update(*d, perm, bs, learning_rate=1e-3, max_grad_norm=0.5, **kw)
+    assert tuple(sa.shape) == (E, 4, 8)
+    for e in range(E):
+        for k in range(4):
+            idx = perm[e, k * bs:min(n, (k + 1) * bs)].contiguous()
+            g, st = ob.grad(*d, index=idx, **kw)
+            assert t.equal(st, sa[e, k]), (e, k)
+            ob.apply(g, learning_rate=1e-3, max_grad_norm=0.5)
+    assert t.equal(pa.params, pb.params)
+    x = d[0][:64].contiguous()
+    assert t.equal(pa.act(x, deterministic=True)[1], pb.act(x, deterministic=True)[1])
+    assert oa.state()[1] == ob.state()[1] == 12
+    for o in (oa, ob):
+        o.close()
+    pa.close(); pb.close()
+
+
+def _torch_trainer(policy, out, adv, ret, perm, bs, lr, clip, vf_coef, ent_coef, max_norm):
+    """The reference trainer: torch_forward + autograd + torch.optim.Adam on a float32 copy of the parameters."""
+    t = _torch()
+    T = out["raw"].shape[0]
+    O, N = policy.n_in, policy.n_out
+    obs, raw, lpo = out["obs"][:T].reshape(-1, O), out["raw"].reshape(-1, N), out["logp"].reshape(-1)
+    adv, ret = adv.reshape(-1), ret.reshape(-1)
+    saved = policy.params
+    w = saved.detach().clone().requires_grad_(True)
+    policy.params = w
+    opt = t.optim.Adam([w], lr=lr, eps=1e-5)
+    try:
+        for e in range(perm.shape[0]):
+            for s in range(0, perm.shape[1], bs):
+                i = perm[e, s:s + bs].long()
+                mean, V = policy.torch_forward(obs[i])
+                ls = w[-N:]
+                z = (raw[i] - mean) / t.exp(ls)
+                logp = (-0.5 * z * z - ls - 0.5 * float(np.log(2 * np.pi))).sum(1)
+                ratio = t.exp(logp - lpo[i])
+                A = adv[i]
+                A = (A - A.mean()) / (A.std() + 1e-8)
+                l_pi = -t.min(ratio * A, t.clamp(ratio, 1 - clip, 1 + clip) * A).mean()
+                loss = l_pi + vf_coef * ((ret[i] - V) ** 2).mean() - ent_coef * (0.5 + 0.5 * float(np.log(2 * np.pi)) + ls).sum()
+                opt.zero_grad()
+                loss.backward()
+                t.nn.utils.clip_grad_norm_([w], max_norm)
+                opt.step()
+    finally:
+        policy.params = saved
+    return w.detach()
+
+
+def test_one_iteration_vs_torch_reference_trainer():
+    from windgym_amd.ppo import PPO
+    t = _torch()
+    v = _venv(512)
+    ppo = PPO("MlpPolicy", v, n_steps=32, n_epochs=2, batch_size=512 * 32 // 4, ent_coef=0.01, seed=3)
+    out = ppo.collect()
+    gen_state = ppo._gen.get_state()
+    before = ppo.policy.params.clone()
+    ppo.train(out, 3e-4, 0.2)
+    perm = ppo._perm.clone()
+    ppo._gen.set_state(gen_state)
+    with t.no_grad():
+        after = ppo.policy.params.clone()
+        ppo.policy.params.copy_(before)
+    ref = _torch_trainer(ppo.policy, out, ppo._adv, ppo._ret, perm, ppo.batch_size, 3e-4, 0.2, 0.5, 0.01, 0.5)
+    moved = (after - before).abs().max().item()
+    assert moved > 1e-4
+    err = ((after - ref).abs() / (ref.abs() + 1e-3)).max().item()
+    assert err <= 1e-5 * 10, err                                         # relative, with a floor of 1e-3 on |w|
+    assert (after - ref).abs().max().item() <= 1e-5
+    ppo.close(); ppo.policy.close(); v.close()
+
+
+def test_descent_on_a_fixed_batch():
+    from windgym_amd.ppo import PPOOptimizer
+    p, sd = make(32, (64, 64), 16)
+    opt = PPOOptimizer(p)
+    arrs = batch(sd, 32, 16, 2048, "tanh", seed=12)
+    d = dev(*arrs)
+    kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True)
+    l0 = oo.loss_and_grad(sd, *arrs, **kw)[0]
+    for _ in range(5):
+        g, _ = opt.grad(*d, **kw)
+        opt.apply(g, learning_rate=1e-4, max_grad_norm=0.5)
+    sd1 = {k: x.cpu().numpy().astype(np.float64) for k, x in p.state_dict().items()}
+    l1 = oo.loss_and_grad(sd1, *arrs, **kw)[0]
+    assert l1 < l0, (l0, l1)
+    opt.close(); p.close()
+
+
+def _two_turbine_venv(n_envs=32):
+    from windgym_amd import presets
+    d = presets.env1_config()
+    d["ActionMethod"] = "yaw"
+    return _venv(n_envs, yaml_dict=d)
+
+
+@pytest.mark.parametrize("which", ["two_turbine", "cfg2"])
+def test_learn_save_load_continue(which, tmp_path):
+    from windgym_amd.policy import MlpPolicy, read_sb3_zip
+    from windgym_amd.ppo import PPO
+    t = _torch()
+    mk = (lambda: _two_turbine_venv(32)) if which == "two_turbine" else (lambda: _venv(64))
+    T = 40
+    kw = dict(n_steps=T, n_epochs=2, ent_coef=0.001, seed=11)
+    # uninterrupted: 4 iterations
+    va = mk()
+    a = PPO("MlpPolicy", va, **kw)
+    calls = []
+    a.learn(4 * T * va.num_envs, callback=lambda p: calls.append(p.iteration))
+    assert calls == [1, 2, 3, 4] and a.num_timesteps == 4 * T * va.num_envs and len(a.log) == 4
+    for rec in a.log:
+        assert all(np.isfinite(float(x)) for x in rec.values()), rec
+    assert sum(r["n_episodes"] for r in a.log) >= 0 and a.log[-1]["fps"] > 0
+    va.batch.check()
+    # 2 iterations, save, load on the same env, 2 more
+    vb = mk()
+    b = PPO("MlpPolicy", vb, **kw)
+    b.learn(2 * T * vb.num_envs)
+    path = os.path.join(tmp_path, "ppo.zip")
+    b.save(path)
+    desc, tensors = read_sb3_zip(path)
+    assert desc == b.policy.desc and all(np.array_equal(tensors[k], x.cpu().numpy()) for k, x in b.policy.state_dict().items())
+    c = PPO.load(path, vb)
+    b.close(); b.policy.close()
+    c.learn(2 * T * vb.num_envs, reset_num_timesteps=False)
+    assert c.num_timesteps == a.num_timesteps and c.iteration == 4
+    assert t.equal(c.policy.params, a.policy.params)
+    ma, sa = a.opt.state()
+    mc, sc = c.opt.state()
+    assert sa == sc and np.array_equal(ma, mc)
+    vb.batch.check()
+    q = MlpPolicy.from_sb3_zip(path)
+    q.close()
+    for x in (a, c):
+        x.close(); x.policy.close()
+    va.close(); vb.close()
+
+
+def test_learn_across_same_step_autoresets_and_sample_site():
+    from windgym_amd.ppo import PPO
+    from windgym_amd.site import hornsrev1_site
+    t = _torch()
+    v = _venv(32)
+    ppo = PPO("MlpPolicy", v, n_steps=64, n_epochs=1, seed=1)
+    n_trunc = []
+    ppo.learn(6 * 64 * 32, callback=lambda p: n_trunc.append(int(list(p.venv._rollout_bufs.values())[0]["truncated"].sum())))
+    assert sum(n_trunc) > 0                                              # episodes ended (and were reset) inside the rollouts
+    assert all(np.isfinite(float(x)) for rec in ppo.log for x in rec.values())
+    assert sum(r["n_episodes"] for r in ppo.log) > 0
+    v.batch.check()
+    ppo.close(); ppo.policy.close(); v.close()
+    vs = _venv(16, sample_site=hornsrev1_site())
+    ps = PPO("MlpPolicy", vs, n_steps=8, n_epochs=1, seed=1)
+    ps.learn(2 * 8 * 16)
+    assert len(ps.log) == 2 and all(np.isfinite(float(x)) for rec in ps.log for x in rec.values())
+    vs.batch.check()
+    ps.close(); ps.policy.close(); vs.close()

@@ -1,0 +1,129 @@
+"""CPU tests of the training layer: the oracle itself (GAE against its brute-force definition, Adam against torch.optim.Adam,
+the loss on hand-computable rows), PPO's argument validation and SB3's initialisation.  The kernels are tested on the GPU
+(tests/test_gpu_ppo.py); the ABI test (tests/test_abi.py) picks the new entries up from the header."""
+import math
+
+import numpy as np
+import pytest
+
+from oracle import ppo_oracle as oo
+from windgym_amd.policy import make_desc, param_layout
+from windgym_amd.ppo import PPO, sb3_orthogonal_init
+
+
+@pytest.mark.parametrize("T,B,p", [(1, 3, 0.5), (7, 5, 0.3), (40, 4, 0.0), (40, 4, 1.0)])
+def test_gae_equals_its_definition(T, B, p):
+    rng = np.random.default_rng(T + B)
+    r, v, fv = (rng.standard_normal((T, B)) for _ in range(3))
+    tr = rng.uniform(size=(T, B)) < p
+    a, ret = oo.gae(r, v, fv, tr, 0.97, 0.9)
+    b, ret_b = oo.gae_brute(r, v, fv, tr, 0.97, 0.9)
+    assert np.allclose(a, b, rtol=1e-12, atol=1e-12) and np.allclose(ret, ret_b, rtol=1e-12, atol=1e-12)
+    # a truncated step's advantage is its own delta; lambda = 0 makes every step so
+    d = r + 0.97 * fv - v
+    assert np.allclose(a[tr], d[tr])
+    assert np.allclose(oo.gae(r, v, fv, tr, 0.97, 0.0)[0], d)
+
+
+@pytest.mark.parametrize("max_norm", [0.1, 1e9])
+def test_oracle_adam_equals_torch_adam(max_norm):
+    import torch
+    rng = np.random.default_rng(0)
+    w = torch.tensor(rng.standard_normal(50), dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([w], lr=1e-2, eps=1e-5)
+    p, m, v = w.detach().numpy().copy(), np.zeros(50), np.zeros(50)
+    for step in range(1, 8):
+        g = rng.standard_normal(50)
+        w.grad = torch.tensor(g)
+        torch.nn.utils.clip_grad_norm_([w], max_norm)
+        opt.step()
+        p, m, v = oo.adam_step(p, g, m, v, step, 1e-2, max_norm)
+        assert np.allclose(w.detach().numpy(), p, rtol=1e-12, atol=1e-13), step
+
+
+def _tiny():
+    """n_in 1 -> n_out 1 with no hidden layers: mean = w x + b, V = u x + c."""
+    return {"action_net.weight": np.array([[2.0]]), "action_net.bias": np.array([0.5]), "value_net.weight": np.array([[-1.0]]),
+            "value_net.bias": np.array([0.25]), "log_std": np.array([math.log(0.5)])}
+
+
+def test_loss_pieces_on_hand_computable_rows():
+    sd = _tiny()
+    obs = np.array([[1.0], [0.0], [-1.0]])
+    mean = np.array([2.5, 0.5, -1.5])
+    raw = (mean + 0.5 * np.array([0.0, 1.0, -2.0]))[:, None]             # z = 0, 1, -2
+    logp = -0.5 * np.array([0.0, 1.0, 4.0]) - math.log(0.5) - 0.5 * math.log(2 * math.pi)
+    ratio = np.array([1.0, 1.5, 0.5])
+    logp_old = logp - np.log(ratio)
+    adv, ret = np.array([1.0, 2.0, -1.0]), np.array([0.0, 1.0, 2.0])
+    total, grads, st, r = oo.loss_and_grad(sd, obs, raw, logp_old, adv, ret, clip_range=0.2, vf_coef=0.5, ent_coef=0.1,
+                                           normalize_advantage=False)
+    assert np.allclose(r, ratio)
+    l_pi = -np.minimum(ratio * adv, np.clip(ratio, 0.8, 1.2) * adv)       # -1, -2.4, +0.8 (the pessimistic branch)
+    assert np.allclose(l_pi, [-1.0, -2.4, 0.8]) and math.isclose(st["pi_loss"], l_pi.mean())
+    V = np.array([-0.75, 0.25, 1.25])
+    assert math.isclose(st["v_loss"], ((ret - V) ** 2).mean())
+    H = 0.5 + 0.5 * math.log(2 * math.pi) + math.log(0.5)
+    assert math.isclose(st["entropy"], H) and math.isclose(total, l_pi.mean() + 0.5 * st["v_loss"] - 0.1 * H)
+    assert math.isclose(st["clip_fraction"], 2 / 3) and math.isclose(st["approx_kl"], ((ratio - 1) - np.log(ratio)).mean())
+    # row 1 is clipped from above with a positive advantage: no gradient; row 2 (ratio 0.5, negative advantage) neither; only
+    # row 0 moves the actor: d/d mean = -A ratio z / std / n = 0 there (z = 0) -> the actor's weight gradient vanishes
+    assert np.allclose(grads["action_net.weight"], 0.0) and np.allclose(grads["action_net.bias"], 0.0)
+    assert np.allclose(grads["log_std"], -(1.0 * 1.0 * (0.0 - 1.0)) / 3 - 0.1)          # -A ratio (z^2 - 1) / n - ent_coef
+    assert np.allclose(grads["value_net.bias"], 0.5 * np.mean(2 * (V - ret)))
+    # normalisation uses the unbiased std
+    _, _, st2, _ = oo.loss_and_grad(sd, obs, raw, logp, adv, ret, normalize_advantage=True)
+    a = (adv - adv.mean()) / (adv.std(ddof=1) + 1e-8)
+    assert math.isclose(st2["pi_loss"], -a.mean(), abs_tol=1e-12)
+
+
+class _FakeEnv:
+    num_envs = 8
+
+
+def test_ppo_argument_validation():
+    for kw in (dict(target_kl=0.01), dict(clip_range_vf=0.2), dict(use_sde=True)):
+        with pytest.raises(NotImplementedError):
+            PPO("MlpPolicy", _FakeEnv(), **kw)
+    for kw in (dict(n_steps=0), dict(n_epochs=0), dict(gamma=1.5), dict(gae_lambda=-0.1), dict(max_grad_norm=0.0),
+               dict(batch_size=0), dict(n_steps=4, batch_size=33), dict(learning_rate=-1.0), dict(clip_range=-0.1)):
+        with pytest.raises(ValueError):
+            PPO("MlpPolicy", _FakeEnv(), **kw)
+    with pytest.raises(ValueError):
+        PPO("CnnPolicy", _FakeEnv())
+
+
+def test_sb3_orthogonal_init():
+    desc = make_desc(32, 16, (64, 48), (64, 64))
+    a, b = sb3_orthogonal_init(desc, 7), sb3_orthogonal_init(desc, 7)
+    assert all(np.array_equal(a[k], b[k]) for k in a) and not np.array_equal(a["action_net.weight"], sb3_orthogonal_init(desc, 8)["action_net.weight"])
+    for name, shape in param_layout(desc):
+        w = a[name].astype(np.float64)
+        assert w.shape == tuple(shape)
+        if w.ndim == 1:
+            assert not w.any()
+            continue
+        gain = 0.01 if name == "action_net.weight" else 1.0 if name == "value_net.weight" else math.sqrt(2.0)
+        g = w @ w.T if w.shape[0] <= w.shape[1] else w.T @ w              # the short side is orthonormal up to the gain
+        assert np.allclose(g, gain * gain * np.eye(g.shape[0]), atol=1e-5), name
+
+
+def test_checkpoint_policy_member_reads_back(tmp_path):
+    """The zip layout of PPO.save: policy.pth under SB3's names is what read_sb3_zip reads (the GPU test saves a real one)."""
+    import io
+    import zipfile
+
+    import torch
+
+    from windgym_amd.policy import read_sb3_zip
+    desc = make_desc(6, 2, (8,), (8, 4))
+    sd = sb3_orthogonal_init(desc, 1)
+    sd["log_std"] = np.array([-0.3, 0.1], np.float32)
+    b = io.BytesIO()
+    torch.save({k: torch.from_numpy(v) for k, v in sd.items()}, b)
+    path = tmp_path / "p.zip"
+    with zipfile.ZipFile(path, "w") as z:
+        z.writestr("policy.pth", b.getvalue())
+        z.writestr("windgym_ppo.json", "{}")
+    d2, t2 = read_sb3_zip(path)
+    assert d2 == desc and all(np.array_equal(t2[k], sd[k]) for k in sd)

@@ -1,0 +1,141 @@
+#!/usr/bin/env python
+"""Training throughput on the device: one PPO iteration (rollout + update) and its parts — one JSON line.
+
+Workload of tools/bench_policy.py: cfg2 (4x4 farm, 16 turbines, O = 32), `--envs` envs on one MI355X, SB3's default MlpPolicy
+shape (actor 32 -> 64 -> 64 -> 16, critic 32 -> 64 -> 64 -> 1, tanh), T = `--n-steps` steps per rollout, `--epochs` epochs.
+Every leg is warmed up once, then timed `--reps` times between two device synchronisations; the median is reported.  Legs:
+
+  rollout            venv.rollout(policy, T) + wg_gae                                      (env-steps/s)
+  update_torch_<mb>  the update in eager torch: torch_forward + autograd + clip_grad_norm_ + torch.optim.Adam, the same
+                     permutations and minibatches — what a user writes without wg_ppo_update   (trained samples/s)
+  update_hip_<mb>    wg_ppo_update (k_ppo_grad + clipping + Adam + repack per minibatch)        (trained samples/s)
+  learn_hip          PPO.learn end to end at the first minibatch size, log_interval=None      (trained samples/s, i.e.
+                     env-steps/s collected AND trained on for `epochs` epochs), with the share of an iteration spent collecting.
+
+<mb> = minibatch rows, `--minibatches` (default 4096 and a quarter of the rollout).
+usage: python tools/bench_ppo.py [--envs 4096] [--n-steps 128] [--epochs 10] [--reps 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+HALF_LOG_2PI = 0.9189385332046727
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--n-steps", type=int, default=128)
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--torch-reps", type=int, default=3, help="repetitions of the eager-torch legs (they are slow)")
+    ap.add_argument("--minibatches", type=int, nargs="*", default=None)
+    ap.add_argument("--preroll", type=int, default=300)
+    args = ap.parse_args()
+    import torch
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.ppo import PPO
+    from windgym_amd.turbine import V80
+    if not torch.cuda.is_available():
+        sys.exit("bench_ppo.py: no HIP device (there is no CPU path to time)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    B, T, E = args.envs, args.n_steps, args.epochs
+    n_rows = B * T
+    mbs = args.minibatches or sorted({min(4096, n_rows), max(1, n_rows // 4)})
+    venv = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
+                          n_passthrough=5, n_rotor_pts=16)
+    venv.reset(seed=1234)
+    ppo = PPO("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=mbs[0], seed=1234)
+    pol = ppo.policy
+    zero = torch.zeros((B, venv.n_turb), device=dev)
+    for _ in range(args.preroll):
+        venv.step(zero)
+
+    def timed(fn, reps):
+        fn()
+        torch.cuda.synchronize(dev)
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts), ts
+
+    out = {"metric": "PPO on the device, 16-turbine farm x %d envs x %d steps, %d epochs, one GPU" % (B, T, E),
+           "envs": B, "n_steps": T, "epochs": E, "rows": n_rows, "minibatches": mbs}
+    el, ts = timed(ppo.collect, args.reps)
+    out["rollout"] = {"value": n_rows / el, "unit": "env-steps/s", "ms": el * 1e3, "ms_all": [round(x * 1e3, 3) for x in ts]}
+    roll = ppo.collect()
+    torch.cuda.synchronize(dev)
+    O, N = pol.n_in, pol.n_out
+    obs, raw, lpo = roll["obs"][:T].reshape(-1, O), roll["raw"].reshape(-1, N), roll["logp"].reshape(-1)
+    adv, ret = ppo._adv.reshape(-1), ppo._ret.reshape(-1)
+    perm = torch.stack([torch.randperm(n_rows, device=dev) for _ in range(E)]).to(torch.int32).contiguous()
+    start = pol.params.clone()
+
+    def update_torch(bs):
+        w = start.clone().requires_grad_(True)
+        saved, pol.params = pol.params, w
+        opt = torch.optim.Adam([w], lr=3e-4, eps=1e-5)
+        try:
+            for e in range(E):
+                for s in range(0, n_rows, bs):
+                    i = perm[e, s:s + bs].long()
+                    mean, V = pol.torch_forward(obs[i])
+                    ls = w[-N:]
+                    z = (raw[i] - mean) / ls.exp()
+                    logp = (-0.5 * z * z - ls - HALF_LOG_2PI).sum(1)
+                    ratio = (logp - lpo[i]).exp()
+                    A = adv[i]
+                    A = (A - A.mean()) / (A.std() + 1e-8)
+                    loss = -torch.min(ratio * A, ratio.clamp(0.8, 1.2) * A).mean() + 0.5 * ((ret[i] - V) ** 2).mean()
+                    opt.zero_grad()
+                    loss.backward()
+                    torch.nn.utils.clip_grad_norm_([w], 0.5)
+                    opt.step()
+        finally:
+            pol.params = saved
+
+    def update_hip(bs):
+        with torch.no_grad():
+            pol.params.copy_(start)
+        pol.sync()
+        ppo.opt.load_state(torch.zeros(2 * start.numel()).numpy(), 0)
+        ppo.opt.update(obs, raw, lpo, adv, ret, perm, bs, learning_rate=3e-4, max_grad_norm=0.5)
+
+    for bs in mbs:
+        el, ts = timed(lambda: update_torch(bs), args.torch_reps)
+        out["update_torch_%d" % bs] = {"value": n_rows * E / el, "unit": "trained samples/s", "ms": el * 1e3,
+                                       "ms_all": [round(x * 1e3, 3) for x in ts]}
+        el, ts = timed(lambda: update_hip(bs), args.reps)
+        out["update_hip_%d" % bs] = {"value": n_rows * E / el, "unit": "trained samples/s", "ms": el * 1e3,
+                                     "ms_all": [round(x * 1e3, 3) for x in ts],
+                                     "speedup_vs_torch": out["update_torch_%d" % bs]["ms"] / (el * 1e3)}
+    with torch.no_grad():
+        pol.params.copy_(start)
+    pol.sync()
+    iters = 3
+    el, ts = timed(lambda: ppo.learn(iters * n_rows, log_interval=None), args.reps)
+    per_iter = el / iters
+    out["learn_hip"] = {"value": n_rows / per_iter, "unit": "trained samples/s", "ms_per_iteration": per_iter * 1e3,
+                        "minibatch": mbs[0], "collect_share": out["rollout"]["ms"] / (per_iter * 1e3),
+                        "ms_all": [round(x * 1e3 / iters, 3) for x in ts]}
+    venv.batch.check()
+    ppo.close()
+    pol.close()
+    venv.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

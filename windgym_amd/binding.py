@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "wg_set_turbulence_box", "wg_set_turbulence_boxes", "wg_set_added_turbulence_box", "wg_set_deficit_table", "wg_set_box_ids", "wg_set_wind", "wg_set_wind_device", "wg_set_flow_script", "wg_reset", "wg_step", "wg_set_step_graph", "wg_check", "wg_obs_multi", "wg_set_obs_multi_buffer",
     "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
     "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
+    "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
 )
 
 _lib = None
@@ -56,6 +57,20 @@ class CRolloutBufs(C.Structure):
                 ("value", C.c_void_p), ("final_obs", C.c_void_p), ("final_value", C.c_void_p), ("reward", C.c_void_p),
                 ("truncated", C.c_void_p), ("n_info", C.c_int32), ("info_fields", C.POINTER(C.c_int32)),
                 ("info_out", C.POINTER(C.c_void_p))]
+
+
+class CPpoBatch(C.Structure):
+    """wg_ppo_batch"""
+    _fields_ = [("obs", C.c_void_p), ("raw", C.c_void_p), ("logp", C.c_void_p), ("advantage", C.c_void_p),
+                ("returns", C.c_void_p), ("n_rows", C.c_int64)]
+
+
+class CPpoHyper(C.Structure):
+    """wg_ppo_hyper"""
+    _fields_ = [("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("normalize_advantage", C.c_int32)]
+
+
+PPO_STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss", "adv_mean", "adv_std")   # wg_ppo_stats
 
 
 class WindGymHipError(RuntimeError):
@@ -123,6 +138,17 @@ def load_library():
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
                              C.POINTER(CRolloutBufs), C.c_void_p]
+    L.wg_gae.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                         C.c_void_p, C.c_void_p]
+    L.wg_ppo_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.wg_ppo_destroy.argtypes = [C.c_void_p]
+    L.wg_ppo_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.wg_ppo_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]
+    L.wg_ppo_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int64, C.c_int,
+                              C.POINTER(CPpoHyper), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_ppo_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    L.wg_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int, C.c_int,
+                                C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -1,0 +1,55 @@
+// wg_ppo.h — the host object behind the `wg_ppo` handle and the constants of the training kernels (wg_ppo.hip).
+//
+// k_ppo_grad works on tiles of R rows (R = 32 when a net's activations fit the workgroup's LDS, else 16, 8, 4 or 2: a
+// function of the architecture alone).  Minibatch rows 0 .. n-1 form ceil(n / R) tiles; G = min(tiles, g_max) workgroups
+// per net, workgroup g takes tiles g, g + G, g + 2 G ... in that order and owns row g of the partials:
+//     part[g][n_flat]   the gradient of the SUM over its rows, in the flat parameter layout of wg_policy.h
+//                       (actor workgroup g writes the actor's entries and log_std, critic workgroup g the critic's),
+//     spart[g][4]       sums of L_pi, (ratio - 1) - log ratio, [|ratio - 1| > eps] (actor) and of L_v (critic).
+// k_ppo_reduce adds the rows g = 0 .. G-1 in index order.  n, R and g_max fix every summation order: results are
+// bit-identical from run to run and from device to device.
+#ifndef WG_PPO_H
+#define WG_PPO_H
+#include <stdint.h>
+
+#include "wg_policy.h"
+
+#define WGT_WAVES 4               // waves per workgroup of k_ppo_grad
+#define WGT_LDS_BYTES 65536       // LDS budget of one workgroup
+#define WGT_G_MAX 512             // most workgroups per net
+#define WGT_PART_BYTES (256u << 20)   // most bytes of gradient partials (bounds g_max for very large nets)
+#define WGT_NSTAT 8               // floats of a wg_ppo_stats record
+#define WGT_BLOCK 256             // threads of the element-wise kernels (reduce, sum of squares, Adam)
+
+// LDS map of one net (offsets in floats; S = R + 1 floats per feature row, conflict-free for row- and feature-major reads)
+struct WgPpoLds {
+    int32_t xin;                          // [min(n_in, 256)][S]   observation chunk
+    int32_t act[WGP_MAX_LAYERS];          // [M_l][S]              activations of hidden layer l; the head's output at act[L-1]
+    int32_t d[2];                         // [max M][S]            dZ of the running layer / of the one before it
+    int32_t rowv;                         // [4][32]               per-row scalars of the loss head
+    int32_t rid;                          // [32] int              gathered row of each tile row, -1 = none
+    int32_t total;
+};
+
+struct WgPpoK {                           // by-value kernel argument next to WgPolicyP
+    int32_t R;                            // rows per tile
+    WgPpoLds lds[2];
+};
+
+struct wg_ppo_s {
+    wg_policy_s* pol;
+    WgPpoK K;
+    int device;
+    int g_max;
+    uint32_t n_flat, n_blocks;            // n_blocks = ceil(n_flat / WGT_BLOCK)
+    uint64_t step;                        // Adam's step count
+    float *m, *v;                         // [n_flat] Adam moments
+    float *grad;                          // [n_flat] gradient of wg_ppo_update's running minibatch
+    float *part, *spart;                  // [g_max][n_flat], [g_max][4]
+    float *advstat;                       // [2] mean and unbiased std of the minibatch's advantages
+    float *blocksq;                       // [n_blocks] partial sums of squares of the gradient
+    float *stats;                         // [WGT_NSTAT] scratch record when the caller wants none
+    size_t lds_bytes;
+};
+
+#endif

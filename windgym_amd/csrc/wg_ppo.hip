@@ -1,0 +1,639 @@
+// wg_ppo.hip — training on the device: what `PPO("MlpPolicy", env).learn(...)` of stable-baselines3 does between two rollouts
+// (examples/longer_steps_example.py:212-240, examples/curriculum.py:544-560), for the MlpPolicy of wg_policy.hip.
+//
+//   k_gae          advantages and returns of a [T, B] rollout (wg_rollout's recurrence), one thread per env.
+//   k_ppo_advstat  mean and unbiased std of a minibatch's advantages, ONE workgroup, fixed-order sums.
+//   k_ppo_grad     one minibatch: gather, forward of actor / critic, PPO loss, backward, per-workgroup gradient partials.
+//   k_ppo_reduce   partials -> flat gradient + statistics record, summed in workgroup order.
+//   k_ppo_sumsq / k_ppo_adam   global L2 norm, clipping, Adam on the caller's flat parameters in place.
+//
+// k_ppo_grad: a workgroup of 4 waves owns ONE net (blockIdx.y: actor / critic — the two gradients share nothing but the
+// rows) and walks its tiles of R rows (wg_ppo.h).  All products run on v_mfma_f32_32x32x2_f32 with the tile's rows as the
+// 32 columns (forward, dX) or as the summation index (dW):
+//     forward   Z[i][row]  = b[i] + sum_k W[i][k] X[k][row]      A = k_policy's packed weights, B = X from LDS — the same
+//                                                                k-ordered fmaf chain as k_policy: bit-identical mean / V;
+//     dW        dW[i][k]  += sum_row dZ[i][row] X[k][row]        A = dZ, B = X, both from LDS; the accumulator starts from the
+//                                                                workgroup's own partial (no atomics: nobody else writes it);
+//     dX        dY[k][row] = sum_i W[i][k] dZ[i][row]            A = the caller's flat W[i][.] rows (coalesced), B = dZ from LDS.
+// Activations of every layer stay in LDS between forward and backward; the first layer streams the observations through LDS
+// in chunks of 256 inputs, once forward and once more for dW.  fp32 throughout.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <new>
+#include <string>
+
+#include "../../include/windgym_hip.h"
+#include "wg_ppo.h"
+
+extern "C" int wg_set_last_error_(int code, const char* msg);      // wg_api.hip
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+#define WGT_HALF_LOG_2PI 0.91893853320467274f
+
+// ---------------------------------------------------------------------------------------------------------------------
+// GAE
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void k_gae(const int T, const int B, const float* __restrict__ reward, const float* __restrict__ value,
+                      const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const float gamma,
+                      const float lambda, float* __restrict__ adv, float* __restrict__ ret) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float a = 0.0f;
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t o = (size_t)t * B + b;
+        const float v = value[o];
+        const float delta = reward[o] + gamma * final_value[o] - v;
+        a = delta + gamma * lambda * (truncated[o] ? 0.0f : 1.0f) * a;
+        adv[o] = a;
+        ret[o] = a + v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fixed-order block reductions (tree over threadIdx, the same shape on every device)
+// ---------------------------------------------------------------------------------------------------------------------
+template <int NT>
+__device__ inline float block_sum(float v, float* sh) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    sh[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__device__ inline int ppo_row(const int32_t* index, int64_t first, int n, int64_t n_total, int i) {
+    if (i >= n) return -1;
+    const int64_t id = index ? (int64_t)index[i] : first + i;
+    return (id < 0 || id >= n_total) ? -1 : (int)id;
+}
+
+// advstat[0] = mean, advstat[1] = unbiased std (torch.std) of the minibatch's advantages
+__global__ __launch_bounds__(1024) void k_ppo_advstat(const float* __restrict__ adv, const int32_t* __restrict__ index,
+                                                      const int64_t first, const int n, const int64_t n_total,
+                                                      float* __restrict__ advstat) {
+    __shared__ float sh[1024];
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int id = ppo_row(index, first, n, n_total, i);
+        if (id >= 0) s += adv[id];
+    }
+    const float mean = block_sum<1024>(s, sh) / (float)n;
+    float q = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int id = ppo_row(index, first, n, n_total, i);
+        if (id >= 0) { const float d = adv[id] - mean; q += d * d; }
+    }
+    const float var = block_sum<1024>(q, sh) / (float)(n - 1);
+    if (threadIdx.x == 0) { advstat[0] = mean; advstat[1] = sqrtf(var); }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_ppo_grad
+// ---------------------------------------------------------------------------------------------------------------------
+struct WgPpoArgs {
+    const float* packed;       // the policy's packed weights (forward)
+    const float* flat;         // the caller's flat parameters (dX, log_std)
+    const float* obs;          // [n_total, n_in]
+    const float* raw;          // [n_total, n_out]
+    const float* logp_old;     // [n_total]
+    const float* adv;          // [n_total]
+    const float* ret;          // [n_total]
+    const int32_t* index;      // [n] or null
+    int64_t first, n_total;
+    int32_t n, G, normalize;
+    float clip, vf_coef;
+    const float* advstat;
+    float* part;               // [G][n_flat]
+    float* spart;              // [G][4]
+};
+
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
+    extern __shared__ float lds[];
+    const int net = blockIdx.y, g = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int R = K.R, S = R + 1;
+    const WgPpoLds& M = K.lds[net];
+    const int L = P.n_layers[net];
+    float* xin = lds + M.xin;
+    float* rowv = lds + M.rowv;
+    int* rid = (int*)(lds + M.rid);
+    float* part = a.part + (size_t)g * P.n_flat;
+    const int ntile = (a.n + R - 1) / R;
+    const float inv_n = 1.0f / (float)a.n;
+    const bool tanh_act = P.activation != WG_ACTV_RELU;
+    float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f;             // thread 0: running sums of the statistics
+
+    for (int tile = g; tile < ntile; tile += a.G) {
+        const bool first = tile == g;
+        const int row0 = tile * R;
+        __syncthreads();                                   // the previous tile's readers are done with LDS
+        if (tid < 32) rid[tid] = tid < R ? ppo_row(a.index, a.first, a.n, a.n_total, row0 + tid) : -1;
+
+        // ---- forward --------------------------------------------------------------------------------------------
+        for (int l = 0; l < L; ++l) {
+            const WgPolicyLayer ly = P.layer[net][l];
+            f32x16 acc[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int ot = wave + WGT_WAVES * t;
+                if (ot < ly.ntiles) {
+                    const float* bp = a.packed + ly.b_packed + ot * 32 + 4 * h;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) acc[t][q] = bp[(q & 3) + 8 * (q >> 2)];
+                }
+            }
+            const int nchunk = l == 0 ? (ly.K + WGP_KC - 1) / WGP_KC : 1;
+            for (int c = 0; c < nchunk; ++c) {
+                const int k0 = c * WGP_KC, kc = min(WGP_KC, ly.K - k0);
+                if (l == 0) {
+                    __syncthreads();
+                    for (int idx = tid; idx < kc * R; idx += WGT_WAVES * 64) {      // consecutive threads: consecutive inputs of a row
+                        const int row = idx / kc, k = idx - row * kc, id = rid[row];
+                        xin[k * S + row] = id >= 0 ? a.obs[(size_t)id * P.n_in + k0 + k] : 0.0f;
+                    }
+                    __syncthreads();
+                }
+                const float* xb = l == 0 ? xin : lds + M.act[l - 1];
+                const int nks = (kc + 1) >> 1;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int ot = wave + WGT_WAVES * t;
+                    if (ot < ly.ntiles) {
+                        const float* wp = a.packed + ly.w_packed + ((size_t)ot * ly.nks + (k0 >> 1)) * 64 + lane;
+                        for (int ks = 0; ks < nks; ++ks) {
+                            const int k = 2 * ks + h;
+                            const float av = wp[(size_t)ks * 64];
+                            const float bv = (k < kc && r < R) ? xb[k * S + r] : 0.0f;
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            float* dst = lds + M.act[l];
+            const bool head = l == L - 1;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int ot = wave + WGT_WAVES * t;
+                if (ot < ly.ntiles) {
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int i = ot * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                        float v = acc[t][q];
+                        if (!head) v = tanh_act ? tanhf(v) : fmaxf(v, 0.0f);
+                        if (i < ly.M && r < R) dst[i * S + r] = v;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+
+        // ---- loss head: dZ of the head into d[0], per-row statistics into rowv ------------------------------------------
+        float* hb = lds + M.act[L - 1];                    // [output][row]
+        float* d0 = lds + M.d[0];
+        if (net == 0) {
+            const int n_out = P.n_out;
+            if (tid < R) {
+                const int id = rid[tid];
+                float dlogp = 0.0f, lpi = 0.0f, kl = 0.0f, cf = 0.0f;
+                if (id >= 0) {
+                    float lp = 0.0f;
+                    for (int j = 0; j < n_out; ++j) {
+                        const float ls = a.flat[P.log_std_flat + j];
+                        const float z = (a.raw[(size_t)id * n_out + j] - hb[j * S + tid]) / expf(ls);
+                        hb[j * S + tid] = z;
+                        lp += -0.5f * z * z - ls - WGT_HALF_LOG_2PI;
+                    }
+                    const float lr = lp - a.logp_old[id];
+                    const float ratio = expf(lr);
+                    float A = a.adv[id];
+                    if (a.normalize) A = (A - a.advstat[0]) / (a.advstat[1] + 1e-8f);
+                    const float rc = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
+                    const float s1 = ratio * A, s2 = rc * A;
+                    lpi = -fminf(s1, s2);
+                    kl = expm1f(lr) - lr;                   // (ratio - 1) - log ratio without the cancellation at ratio = 1
+                    cf = fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
+                    dlogp = (ratio == rc || s1 < s2) ? -A * ratio * inv_n : 0.0f;
+                } else {
+                    for (int j = 0; j < n_out; ++j) hb[j * S + tid] = 0.0f;
+                }
+                rowv[tid] = dlogp; rowv[32 + tid] = lpi; rowv[64 + tid] = kl; rowv[96 + tid] = cf;
+            }
+            __syncthreads();
+            for (int idx = tid; idx < n_out * R; idx += WGT_WAVES * 64) {
+                const int j = idx / R, row = idx - j * R;
+                d0[j * S + row] = rowv[row] * hb[j * S + row] / expf(a.flat[P.log_std_flat + j]);
+            }
+            if (tid < n_out) {                              // d loss / d log_std_j through logp: sum_row dlogp (z^2 - 1)
+                float s = 0.0f;
+                for (int row = 0; row < R; ++row) { const float z = hb[tid * S + row]; s += rowv[row] * (z * z - 1.0f); }
+                float* o = part + P.log_std_flat + tid;
+                *o = first ? s : *o + s;
+            }
+            if (tid == 0)
+                for (int row = 0; row < R; ++row) { st0 += rowv[32 + row]; st1 += rowv[64 + row]; st2 += rowv[96 + row]; }
+        } else {
+            if (tid < R) {
+                const int id = rid[tid];
+                float dv = 0.0f, lv = 0.0f;
+                if (id >= 0) {
+                    const float e = hb[tid] - a.ret[id];
+                    lv = e * e;
+                    dv = a.vf_coef * 2.0f * e * inv_n;
+                }
+                d0[tid] = dv;
+                rowv[tid] = lv;
+            }
+            __syncthreads();
+            if (tid == 0)
+                for (int row = 0; row < R; ++row) st0 += rowv[row];
+        }
+        __syncthreads();
+
+        // ---- backward ---------------------------------------------------------------------------------------------
+        int cur = 0;
+        for (int l = L - 1; l >= 0; --l) {
+            const WgPolicyLayer ly = P.layer[net][l];
+            const float* dz = lds + M.d[cur];
+            const int ntm = ly.ntiles;
+            // db[i] += sum_row dZ[i][row]
+            for (int i = tid; i < ly.M; i += WGT_WAVES * 64) {
+                float s = 0.0f;
+                for (int row = 0; row < R; ++row) s += dz[i * S + row];
+                float* o = part + ly.b_flat + i;
+                *o = first ? s : *o + s;
+            }
+            // dW[i][k] += sum_row dZ[i][row] X[k][row]
+            const int nchunk = l == 0 ? (ly.K + WGP_KC - 1) / WGP_KC : 1;
+            for (int c = 0; c < nchunk; ++c) {
+                const int k0 = c * WGP_KC, kc = min(WGP_KC, ly.K - k0);
+                if (l == 0 && nchunk > 1) {                 // (a single chunk is still in LDS from the forward pass)
+                    __syncthreads();
+                    for (int idx = tid; idx < kc * R; idx += WGT_WAVES * 64) {
+                        const int row = idx / kc, k = idx - row * kc, id = rid[row];
+                        xin[k * S + row] = id >= 0 ? a.obs[(size_t)id * P.n_in + k0 + k] : 0.0f;
+                    }
+                    __syncthreads();
+                }
+                const float* xb = l == 0 ? xin : lds + M.act[l - 1];
+                const int nkt = (kc + 31) >> 5;
+                for (int q = wave; q < ntm * nkt; q += WGT_WAVES) {
+                    const int ot = q / nkt, kt = q - ot * nkt;
+                    const int kk = kt * 32 + r;             // this lane's column of the output tile (input index within the chunk)
+                    float* wo = part + ly.w_flat + k0 + kk;
+                    f32x16 acc;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int i = ot * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                        acc[e] = (!first && i < ly.M && kk < kc) ? wo[(size_t)i * ly.K] : 0.0f;
+                    }
+                    const int ia = ot * 32 + r;
+                    for (int s = 0; s < (R >> 1); ++s) {
+                        const int row = 2 * s + h;
+                        const float av = ia < ly.M ? dz[ia * S + row] : 0.0f;
+                        const float bv = kk < kc ? xb[kk * S + row] : 0.0f;
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int i = ot * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                        if (i < ly.M && kk < kc) wo[(size_t)i * ly.K] = acc[e];
+                    }
+                }
+            }
+            // dZ of the layer before: (W^T dZ) * act'(Y)
+            if (l > 0) {
+                float* dp = lds + M.d[cur ^ 1];
+                const float* y = lds + M.act[l - 1];
+                const float* wf = a.flat + ly.w_flat;
+                const int nkt = (ly.K + 31) >> 5, nis = (ly.M + 1) >> 1;
+                for (int kt = wave; kt < nkt; kt += WGT_WAVES) {
+                    const int kk = kt * 32 + r;
+                    f32x16 acc;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+                    for (int s = 0; s < nis; ++s) {
+                        const int i = 2 * s + h;
+                        const float av = (i < ly.M && kk < ly.K) ? wf[(size_t)i * ly.K + kk] : 0.0f;
+                        const float bv = (i < ly.M && r < R) ? dz[i * S + r] : 0.0f;
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int k = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                        if (k < ly.K && r < R) {
+                            const float yv = y[k * S + r];
+                            dp[k * S + r] = acc[e] * (tanh_act ? 1.0f - yv * yv : (yv > 0.0f ? 1.0f : 0.0f));
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+    if (tid == 0) {
+        float* sp = a.spart + (size_t)g * 4;
+        if (net == 0) { sp[0] = st0; sp[1] = st1; sp[2] = st2; }
+        else sp[3] = st0;
+    }
+}
+
+// partials -> flat gradient (+ the entropy term's constant gradient on log_std) and the statistics record
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_reduce(const WgPolicyP P, const float* __restrict__ part,
+                                                           const float* __restrict__ spart, const int G, const int n,
+                                                           const float vf_coef, const float ent_coef, const int normalize,
+                                                           const float* __restrict__ advstat, const float* __restrict__ flat,
+                                                           float* __restrict__ grad, float* __restrict__ stats) {
+    const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
+    if (p < P.n_flat) {
+        float s = 0.0f;
+        int g = 0;
+        for (; g + 8 <= G; g += 8) {                       // eight loads in flight, added in index order
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(g + u) * P.n_flat + p];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += x[u];
+        }
+        for (; g < G; ++g) s += part[(size_t)g * P.n_flat + p];
+        if (p >= P.log_std_flat) s -= ent_coef;
+        grad[p] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int g = 0; g < G; ++g)
+            for (int k = 0; k < 4; ++k) s[k] += spart[(size_t)g * 4 + k];
+        float H = 0.0f;
+        for (int j = 0; j < P.n_out; ++j) H += 0.5f + WGT_HALF_LOG_2PI + flat[P.log_std_flat + j];
+        const float inv_n = 1.0f / (float)n;
+        const float lpi = s[0] * inv_n, lv = s[3] * inv_n;
+        stats[0] = lpi; stats[1] = lv; stats[2] = H; stats[3] = s[1] * inv_n; stats[4] = s[2] * inv_n;
+        stats[5] = lpi + vf_coef * lv - ent_coef * H;
+        stats[6] = normalize ? advstat[0] : 0.0f;
+        stats[7] = normalize ? advstat[1] : 1.0f;
+    }
+}
+
+// blocksq[b] = sum of squares of block b's 256 gradient entries (fixed tree)
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_sumsq(const float* __restrict__ grad, const uint32_t n_flat,
+                                                          float* __restrict__ blocksq) {
+    __shared__ float sh[WGT_BLOCK];
+    const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
+    const float gv = p < n_flat ? grad[p] : 0.0f;
+    const float s = block_sum<WGT_BLOCK>(gv * gv, sh);
+    if (threadIdx.x == 0) blocksq[blockIdx.x] = s;
+}
+
+// clip by the global norm, then torch.optim.Adam's step (no weight decay, no amsgrad) on params in place
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam(float* __restrict__ params, const float* __restrict__ grad,
+                                                         float* __restrict__ m, float* __restrict__ v, const uint32_t n_flat,
+                                                         const float* __restrict__ blocksq, const uint32_t n_blocks,
+                                                         const float max_norm, const float step_size, const float bc2_sqrt,
+                                                         const float omb1, const float beta2, const float omb2, const float eps) {
+    __shared__ float sh[WGT_BLOCK];
+    float s = 0.0f;
+    for (uint32_t b = threadIdx.x; b < n_blocks; b += WGT_BLOCK) s += blocksq[b];
+    const float norm = sqrtf(block_sum<WGT_BLOCK>(s, sh));
+    const float scale = fminf(1.0f, max_norm / (norm + 1e-6f));
+    const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
+    if (p >= n_flat) return;
+    const float gv = grad[p] * scale;
+    const float mv = m[p] + (gv - m[p]) * omb1;
+    const float vv = v[p] * beta2 + omb2 * (gv * gv);
+    m[p] = mv; v[p] = vv;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    params[p] = params[p] - step_size * (mv / denom);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+static int tfail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
+#define THIPCHK(x)                                                                                  \
+    do {                                                                                            \
+        hipError_t _e = (x);                                                                        \
+        if (_e != hipSuccess) return tfail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+static int t_use_device(int device) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != device) THIPCHK(hipSetDevice(device));
+    return 0;
+}
+
+// a device pointer of another GPU (or a host pointer) -> WG_ERR_INVALID
+static int t_on_device(const void* p, int device, const char* what) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return tfail(WG_ERR_INVALID, std::string(what) + " is not a device pointer");
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != device)
+        return tfail(WG_ERR_INVALID, std::string(what) + " is not memory of device " + std::to_string(device));
+    return 0;
+}
+
+extern "C" int wg_gae(int T, int B, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+                      const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out,
+                      void* stream) {
+    if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !advantage_out || !returns_out)
+        return tfail(WG_ERR_INVALID, "wg_gae: null argument");
+    if (T < 1 || B < 1) return tfail(WG_ERR_INVALID, "wg_gae: T and B must be >= 1");
+    hipLaunchKernelGGL(k_gae, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, reward_dev, value_dev,
+                       final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+// LDS map of both nets for tiles of R rows -> bytes of the larger one
+static size_t t_lds_map(const WgPolicyP& P, int R, WgPpoK* K) {
+    const int S = R + 1;
+    size_t most = 0;
+    K->R = R;
+    for (int net = 0; net < 2; ++net) {
+        WgPpoLds& m = K->lds[net];
+        int o = 0, maxw = 1;
+        m.xin = o; o += (P.n_in < WGP_KC ? P.n_in : WGP_KC) * S;
+        for (int l = 0; l < WGP_MAX_LAYERS; ++l) {
+            m.act[l] = o;
+            if (l < P.n_layers[net]) {
+                o += P.layer[net][l].M * S;
+                if (P.layer[net][l].M > maxw) maxw = P.layer[net][l].M;
+            }
+        }
+        m.d[0] = o; o += maxw * S;
+        m.d[1] = o; o += maxw * S;
+        m.rowv = o; o += 4 * 32;
+        m.rid = o; o += 32;
+        m.total = o;
+        if ((size_t)o * sizeof(float) > most) most = (size_t)o * sizeof(float);
+    }
+    return most;
+}
+
+extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
+    if (!p || !out) return tfail(WG_ERR_INVALID, "wg_ppo_create: null argument");
+    *out = nullptr;
+    const WgPolicyP& P = p->P;
+    if (P.n_layers[1] == 0) return tfail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with a critic");
+    if (!P.has_log_std) return tfail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with log_std");
+    wg_ppo_s* o = new (std::nothrow) wg_ppo_s();
+    if (!o) return tfail(WG_ERR_NOMEM, "wg_ppo_create: out of host memory");
+    o->pol = p;
+    o->device = p->device;
+    o->n_flat = P.n_flat;
+    o->n_blocks = (P.n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    int R = 32;
+    while ((o->lds_bytes = t_lds_map(P, R, &o->K)) > WGT_LDS_BYTES && R > 2) R >>= 1;
+    if (o->lds_bytes > WGT_LDS_BYTES) {
+        delete o;
+        return tfail(WG_ERR_UNSUPPORTED, "wg_ppo_create: the architecture's activations do not fit the workgroup's LDS");
+    }
+    size_t gm = WGT_PART_BYTES / (sizeof(float) * (size_t)P.n_flat);
+    o->g_max = (int)(gm < 1 ? 1 : gm > WGT_G_MAX ? WGT_G_MAX : gm);
+    const size_t nf = sizeof(float) * (size_t)P.n_flat;
+    hipError_t e = hipSetDevice(o->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->m, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->v, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->grad, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->part, nf * o->g_max);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->spart, sizeof(float) * 4 * o->g_max);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->advstat, sizeof(float) * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->blocksq, sizeof(float) * o->n_blocks);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->stats, sizeof(float) * WGT_NSTAT);
+    if (e == hipSuccess) e = hipMemset(o->m, 0, nf);
+    if (e == hipSuccess) e = hipMemset(o->v, 0, nf);
+    if (e == hipSuccess) e = hipMemset(o->spart, 0, sizeof(float) * 4 * o->g_max);
+    if (e == hipSuccess) e = hipMemset(o->advstat, 0, sizeof(float) * 2);
+    if (e != hipSuccess) {
+        wg_ppo_destroy(o);
+        return tfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
+    }
+    *out = o;
+    return 0;
+}
+
+extern "C" int wg_ppo_destroy(wg_ppo o) {
+    if (!o) return 0;
+    if (hipSetDevice(o->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        float* bufs[] = {o->m, o->v, o->grad, o->part, o->spart, o->advstat, o->blocksq, o->stats};
+        for (float* b : bufs)
+            if (b) (void)hipFree(b);
+    }
+    delete o;
+    return 0;
+}
+
+extern "C" int wg_ppo_get_state(wg_ppo o, float* mv_host, size_t n, uint64_t* step) {
+    if (!o || !mv_host || !step) return tfail(WG_ERR_INVALID, "wg_ppo_get_state: null argument");
+    if (n != 2 * (size_t)o->n_flat) return tfail(WG_ERR_INVALID, "wg_ppo_get_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
+    if (int rc = t_use_device(o->device)) return rc;
+    THIPCHK(hipDeviceSynchronize());
+    THIPCHK(hipMemcpy(mv_host, o->m, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
+    THIPCHK(hipMemcpy(mv_host + o->n_flat, o->v, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
+    *step = o->step;
+    return 0;
+}
+
+extern "C" int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64_t step) {
+    if (!o || !mv_host) return tfail(WG_ERR_INVALID, "wg_ppo_set_state: null argument");
+    if (n != 2 * (size_t)o->n_flat) return tfail(WG_ERR_INVALID, "wg_ppo_set_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
+    if (int rc = t_use_device(o->device)) return rc;
+    THIPCHK(hipDeviceSynchronize());
+    THIPCHK(hipMemcpy(o->m, mv_host, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
+    THIPCHK(hipMemcpy(o->v, mv_host + o->n_flat, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
+    o->step = step;
+    return 0;
+}
+
+static int t_check_batch(const char* who, const wg_ppo_batch* b, const wg_ppo_hyper* hp) {
+    if (!b || !hp) return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
+    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns)
+        return tfail(WG_ERR_INVALID, std::string(who) + ": a batch pointer is null");
+    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, std::string(who) + ": n_rows out of range");
+    if (!(hp->clip_range >= 0.0f)) return tfail(WG_ERR_INVALID, std::string(who) + ": clip_range < 0");
+    return 0;
+}
+
+// the launches of one gradient, no argument checks
+static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* b, const int32_t* index_dev, int64_t first, int n,
+                  const wg_ppo_hyper* hp, float* grad_out, float* stats_out, hipStream_t st) {
+    const WgPolicyP& P = o->pol->P;
+    const int R = o->K.R, ntile = (n + R - 1) / R, G = ntile < o->g_max ? ntile : o->g_max;
+    const int normalize = hp->normalize_advantage && n > 1;
+    if (normalize) hipLaunchKernelGGL(k_ppo_advstat, dim3(1), dim3(1024), 0, st, b->advantage, index_dev, first, n, b->n_rows, o->advstat);
+    WgPpoArgs a;
+    a.packed = o->pol->packed; a.flat = params_dev; a.obs = b->obs; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
+    a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G; a.normalize = normalize;
+    a.clip = hp->clip_range; a.vf_coef = hp->vf_coef; a.advstat = o->advstat; a.part = o->part; a.spart = o->spart;
+    hipLaunchKernelGGL(k_ppo_grad, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
+    hipLaunchKernelGGL(k_ppo_reduce, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, P, o->part, o->spart, G, n, hp->vf_coef,
+                       hp->ent_coef, normalize, o->advstat, params_dev, grad_out, stats_out ? stats_out : o->stats);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
+    const double b1 = 0.9, b2 = 0.999;
+    o->step += 1;
+    const double bc1 = 1.0 - std::pow(b1, (double)o->step), bc2 = 1.0 - std::pow(b2, (double)o->step);
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, o->n_flat, o->blocksq);
+    hipLaunchKernelGGL(k_ppo_adam, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, o->m, o->v, o->n_flat,
+                       o->blocksq, o->n_blocks, max_grad_norm, (float)((double)lr / bc1), (float)std::sqrt(bc2), (float)(1.0 - b1),
+                       (float)b2, (float)(1.0 - b2), 1e-5f);
+    THIPCHK(hipGetLastError());
+    return wg_policy_set_params(o->pol, params_dev, o->n_flat, 1, (void*)st);
+}
+
+extern "C" int wg_ppo_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* b, const int32_t* index_dev, int64_t first,
+                           int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
+    if (!o || !params_dev || !grad_out) return tfail(WG_ERR_INVALID, "wg_ppo_grad: null argument");
+    if (int rc = t_check_batch("wg_ppo_grad", b, hp)) return rc;
+    if (n < 1) return tfail(WG_ERR_INVALID, "wg_ppo_grad: n < 1");
+    if (!index_dev && (first < 0 || first + n > b->n_rows)) return tfail(WG_ERR_INVALID, "wg_ppo_grad: rows first .. first + n - 1 leave the batch");
+    if (int rc = t_use_device(o->device)) return rc;
+    if (int rc = t_on_device(params_dev, o->device, "wg_ppo_grad: params_dev")) return rc;
+    if (int rc = t_on_device(b->obs, o->device, "wg_ppo_grad: obs")) return rc;
+    return t_grad(o, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+}
+
+extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream) {
+    if (!o || !params_dev || !grad_dev) return tfail(WG_ERR_INVALID, "wg_ppo_apply: null argument");
+    if (!(max_grad_norm > 0.0f)) return tfail(WG_ERR_INVALID, "wg_ppo_apply: max_grad_norm must be > 0");
+    if (int rc = t_use_device(o->device)) return rc;
+    if (int rc = t_on_device(params_dev, o->device, "wg_ppo_apply: params_dev")) return rc;
+    if (int rc = t_on_device(grad_dev, o->device, "wg_ppo_apply: grad_dev")) return rc;
+    return t_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
+}
+
+extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
+                             int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out,
+                             void* stream) {
+    if (!o || !params_dev || !perm_dev) return tfail(WG_ERR_INVALID, "wg_ppo_update: null argument");
+    if (int rc = t_check_batch("wg_ppo_update", b, hp)) return rc;
+    if (n_epochs < 1 || batch_size < 1) return tfail(WG_ERR_INVALID, "wg_ppo_update: n_epochs and batch_size must be >= 1");
+    if (!(max_grad_norm > 0.0f)) return tfail(WG_ERR_INVALID, "wg_ppo_update: max_grad_norm must be > 0");
+    if (int rc = t_use_device(o->device)) return rc;
+    if (int rc = t_on_device(params_dev, o->device, "wg_ppo_update: params_dev")) return rc;
+    if (int rc = t_on_device(b->obs, o->device, "wg_ppo_update: obs")) return rc;
+    if (int rc = t_on_device(perm_dev, o->device, "wg_ppo_update: perm_dev")) return rc;
+    const int64_t n_rows = b->n_rows;
+    const int n_mb = (int)((n_rows + batch_size - 1) / batch_size);
+    for (int e = 0; e < n_epochs; ++e)
+        for (int k = 0; k < n_mb; ++k) {
+            const int64_t start = (int64_t)k * batch_size;
+            const int n = (int)(n_rows - start < batch_size ? n_rows - start : batch_size);
+            float* so = stats_out ? (float*)(stats_out + (size_t)e * n_mb + k) : nullptr;
+            if (int rc = t_grad(o, params_dev, b, perm_dev + (size_t)e * n_rows + start, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
+            if (int rc = t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream)) return rc;
+        }
+    return 0;
+}

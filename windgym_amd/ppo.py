@@ -1,0 +1,363 @@
+"""PPO for :class:`~windgym_amd.policy.MlpPolicy` on the device — the reference's training call,
+``PPO("MlpPolicy", env, n_steps=2048).learn(...)`` (examples/longer_steps_example.py:212-240, examples/curriculum.py:544-560),
+without stable-baselines3 and without leaving the GPU between rollout and update.
+
+One iteration of :meth:`PPO.learn` is ``venv.rollout`` (wg_rollout) -> ``wg_gae`` -> one ``torch.randperm`` per epoch from a
+seeded device generator -> ``wg_ppo_update`` (n_epochs x minibatches of k_ppo_grad + clipping + Adam + repack), with one
+device-to-host copy of the statistics per logged iteration.  :class:`PPOOptimizer` is the thin wrapper of the ``wg_ppo_*``
+entries of include/windgym_hip.h (gradient and optimiser step are separate calls: a data-parallel trainer all-reduces the
+flat gradient between them).  There is no CPU fallback: without the built library or a GPU the constructors raise.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import io
+import json
+import time
+import zipfile
+
+import numpy as np
+
+from .policy import MlpPolicy, param_layout
+
+HYPER = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
+         "learning_rate", "normalize_advantage")
+
+
+def sb3_orthogonal_init(desc, seed):
+    """{SB3 name: float32 array}: stable-baselines3's ``ortho_init`` — orthogonal weights with gain sqrt(2) for the hidden
+    layers, 0.01 for the action head, 1 for the value head, zero biases and ``log_std`` — drawn from a seeded CPU generator
+    (a normal matrix, QR, columns signed by R's diagonal: torch.nn.init.orthogonal_'s construction)."""
+    import torch
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    out = {}
+    for name, shape in param_layout(desc):
+        if len(shape) != 2:
+            out[name] = np.zeros(shape, np.float32)
+            continue
+        gain = 0.01 if name == "action_net.weight" else 1.0 if name == "value_net.weight" else float(np.sqrt(2.0))
+        rows, cols = shape
+        a = torch.randn((rows, cols), generator=g, dtype=torch.float32)
+        if rows < cols:
+            a = a.T
+        q, r = torch.linalg.qr(a)
+        q = q * torch.sign(torch.diagonal(r))
+        if rows < cols:
+            q = q.T
+        out[name] = (gain * q).contiguous().numpy().astype(np.float32)
+    return out
+
+
+class PPOOptimizer:
+    """The ``wg_ppo`` handle of one :class:`MlpPolicy`: Adam's state and the scratch of the gradient kernel.  All methods
+    enqueue on torch's current stream and synchronise nothing (``state()`` / ``load_state()`` excepted)."""
+
+    def __init__(self, policy):
+        from .binding import _chk
+        if not policy.has_critic or not policy.desc["has_log_std"]:
+            raise ValueError("training needs a policy with a critic and log_std")
+        self.policy, self.L, self._chk, self.torch = policy, policy.L, _chk, policy.torch
+        h = C.c_void_p()
+        _chk(self.L.wg_ppo_create(policy._h, C.byref(h)), "wg_ppo_create")
+        self._h = h
+        self.grad_buf = self.torch.zeros_like(policy.params)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.wg_ppo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _f32(self, x, shape, what):
+        t = self.torch
+        if not (isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float32 and x.is_contiguous() and x.numel() == int(np.prod(shape))):
+            raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of {int(np.prod(shape))} elements")
+        return x
+
+    def gae(self, reward, value, final_value, truncated, gamma, gae_lambda, out=None):
+        """wg_gae on ``[T, B]`` CUDA tensors (``truncated`` uint8) -> (advantage, returns)."""
+        t = self.torch
+        T, B = reward.shape
+        for x, w in ((reward, "reward"), (value, "value"), (final_value, "final_value")):
+            self._f32(x, (T, B), w)
+        if not (truncated.is_cuda and truncated.dtype == t.uint8 and truncated.is_contiguous() and tuple(truncated.shape) == (T, B)):
+            raise ValueError("truncated must be a contiguous uint8 CUDA tensor [T, B]")
+        adv, ret = out if out is not None else (t.empty_like(reward), t.empty_like(reward))
+        self._chk(self.L.wg_gae(T, B, reward.data_ptr(), value.data_ptr(), final_value.data_ptr(), truncated.data_ptr(),
+                                float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(), self.policy._stream()), "wg_gae")
+        return adv, ret
+
+    def _batch(self, obs, raw, logp, advantage, returns):
+        from .binding import CPpoBatch
+        p = self.policy
+        n = logp.numel()
+        self._f32(obs, (n, p.n_in), "obs"); self._f32(raw, (n, p.n_out), "raw"); self._f32(logp, (n,), "logp")
+        self._f32(advantage, (n,), "advantage"); self._f32(returns, (n,), "returns")
+        return CPpoBatch(obs.data_ptr(), raw.data_ptr(), logp.data_ptr(), advantage.data_ptr(), returns.data_ptr(), n), n
+
+    @staticmethod
+    def _hyper(clip_range, vf_coef, ent_coef, normalize_advantage):
+        from .binding import CPpoHyper
+        return CPpoHyper(float(clip_range), float(vf_coef), float(ent_coef), int(bool(normalize_advantage)))
+
+    def _index(self, index, n_min):
+        t = self.torch
+        if not (isinstance(index, t.Tensor) and index.is_cuda and index.dtype == t.int32 and index.is_contiguous() and index.numel() >= n_min):
+            raise ValueError("the index / permutation must be a contiguous int32 CUDA tensor")
+        return index
+
+    def grad(self, obs, raw, logp, advantage, returns, *, index=None, first=0, n=None, clip_range=0.2, vf_coef=0.5,
+             ent_coef=0.0, normalize_advantage=True, out=None, stats=None):
+        """wg_ppo_grad: one minibatch -> (flat gradient ``[n_params]``, statistics ``[8]`` in the order of binding.PPO_STATS)."""
+        t = self.torch
+        b, rows = self._batch(obs, raw, logp, advantage, returns)
+        if index is not None:
+            n = index.numel() if n is None else int(n)
+            self._index(index, n)
+        elif n is None:
+            n = rows - int(first)
+        g = self.grad_buf if out is None else out
+        st = t.zeros(8, dtype=t.float32, device=self.policy.device) if stats is None else stats
+        self._chk(self.L.wg_ppo_grad(self._h, self.policy.params.data_ptr(), C.byref(b), None if index is None else index.data_ptr(),
+                                     int(first), int(n), C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)),
+                                     g.data_ptr(), st.data_ptr(), self.policy._stream()), "wg_ppo_grad")
+        return g, st
+
+    def apply(self, grad=None, learning_rate=3e-4, max_grad_norm=0.5):
+        """wg_ppo_apply: clip, Adam on ``policy.params`` in place, repack — ``policy.act`` afterwards uses the new weights."""
+        g = self.grad_buf if grad is None else grad
+        self._chk(self.L.wg_ppo_apply(self._h, self.policy.params.data_ptr(), g.data_ptr(), float(learning_rate),
+                                      float(max_grad_norm), self.policy._stream()), "wg_ppo_apply")
+
+    def update(self, obs, raw, logp, advantage, returns, perm, batch_size, *, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
+               normalize_advantage=True, learning_rate=3e-4, max_grad_norm=0.5, stats=None):
+        """wg_ppo_update: ``perm`` int32 ``[n_epochs, n_rows]`` -> statistics ``[n_epochs, n_minibatches, 8]``."""
+        t = self.torch
+        b, rows = self._batch(obs, raw, logp, advantage, returns)
+        if perm.ndim != 2 or perm.shape[1] != rows:
+            raise ValueError(f"perm must be [n_epochs, {rows}]")
+        self._index(perm, rows)
+        n_epochs, n_mb = perm.shape[0], -(-rows // int(batch_size))
+        st = t.zeros((n_epochs, n_mb, 8), dtype=t.float32, device=self.policy.device) if stats is None else stats
+        self._chk(self.L.wg_ppo_update(self._h, self.policy.params.data_ptr(), C.byref(b), perm.data_ptr(), n_epochs, int(batch_size),
+                                       C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)),
+                                       float(learning_rate), float(max_grad_norm), st.data_ptr(), self.policy._stream()), "wg_ppo_update")
+        return st
+
+    def state(self):
+        """(Adam's m then v as one float32 numpy vector ``[2 n_params]``, step count)."""
+        n = 2 * self.policy.params.numel()
+        mv, step = np.zeros(n, np.float32), C.c_uint64()
+        self._chk(self.L.wg_ppo_get_state(self._h, mv.ctypes.data_as(C.c_void_p), n, C.byref(step)), "wg_ppo_get_state")
+        return mv, int(step.value)
+
+    def load_state(self, mv, step):
+        mv = np.ascontiguousarray(mv, dtype=np.float32)
+        self._chk(self.L.wg_ppo_set_state(self._h, mv.ctypes.data_as(C.c_void_p), mv.size, int(step)), "wg_ppo_set_state")
+
+
+def _schedule(x, name):
+    if callable(x):
+        return x
+    v = float(x)
+    if not v >= 0.0:
+        raise ValueError(f"{name} must be >= 0")
+    return lambda progress_remaining: v
+
+
+class PPO:
+    """Proximal policy optimisation with stable-baselines3's argument names and defaults, on a ``WindFarmVecEnv``.
+
+    Two defaults differ from SB3's, which sized them for a handful of host envs: ``n_steps`` = 128 (SB3: 2048) steps of EVERY env
+    of the batch per rollout, and ``batch_size`` = a quarter of the rollout (SB3: 64 rows).  ``policy`` is an
+    :class:`MlpPolicy` or the string ``"MlpPolicy"``; the string builds one for the env with SB3's orthogonal initialisation
+    (``policy_kwargs``: ``net_arch=dict(pi=[...], vf=[...])`` or a list for both, ``activation`` ``"tanh"`` / ``"relu"``).
+    ``learning_rate`` and ``clip_range`` may be callables of ``progress_remaining`` (1 -> 0), evaluated on the host once per
+    iteration.  Not implemented (``NotImplementedError``): ``target_kl``, ``clip_range_vf``, ``use_sde``.
+
+    ``save`` writes a zip whose ``policy.pth`` is a ``torch.save`` of the state dict under SB3's names (``read_sb3_zip`` and
+    ``MlpPolicy.from_sb3_zip`` read it), next to Adam's state, the counters and the hyper-parameters as npy / JSON; a zip that
+    SB3's own ``PPO.load`` accepts needs cloudpickled members and is out of scope."""
+
+    def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
+                 ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
+                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False):
+        for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
+            if v is not None:
+                raise NotImplementedError(f"{name} is not implemented")
+        if use_sde:
+            raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
+        n_steps, n_epochs = int(n_steps), int(n_epochs)
+        if n_steps < 1 or n_epochs < 1:
+            raise ValueError("n_steps and n_epochs must be >= 1")
+        if not 0.0 <= float(gamma) <= 1.0 or not 0.0 <= float(gae_lambda) <= 1.0:
+            raise ValueError("gamma and gae_lambda must lie in [0, 1]")
+        if not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be > 0")
+        n_rows = n_steps * int(venv.num_envs)
+        batch_size = max(1, n_rows // 4) if batch_size is None else int(batch_size)
+        if not 1 <= batch_size <= n_rows:
+            raise ValueError(f"batch_size must lie in [1, n_steps * num_envs = {n_rows}]")
+        self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
+        if isinstance(policy, str):
+            if policy != "MlpPolicy":
+                raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy'")
+            policy = self._build_policy(venv, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
+        elif policy_kwargs:
+            raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
+        if policy.n_in != venv.batch.obs_dim or policy.n_out != venv.n_turb:
+            raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, the env needs {venv.batch.obs_dim} -> {venv.n_turb}")
+        self.policy, self.venv, self.torch = policy, venv, policy.torch
+        self.n_steps, self.batch_size, self.n_epochs, self.n_rows = n_steps, batch_size, n_epochs, n_rows
+        self.gamma, self.gae_lambda, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(ent_coef), float(vf_coef)
+        self.max_grad_norm, self.normalize_advantage = float(max_grad_norm), bool(normalize_advantage)
+        self.learning_rate, self.clip_range = learning_rate, clip_range
+        self.seed = seed
+        self.opt = PPOOptimizer(policy)
+        t = self.torch
+        self._gen = t.Generator(device=policy.device)
+        self._gen.manual_seed(0 if seed is None else int(seed))
+        self._perm = t.zeros((n_epochs, n_rows), dtype=t.int32, device=policy.device)
+        self._adv = t.zeros((n_steps, venv.num_envs), dtype=t.float32, device=policy.device)
+        self._ret = t.zeros_like(self._adv)
+        self._stats = t.zeros((n_epochs, -(-n_rows // batch_size), 8), dtype=t.float32, device=policy.device)
+        self.num_timesteps, self.iteration, self.log = 0, 0, []
+
+    @staticmethod
+    def _build_policy(venv, kw, seed):
+        arch = kw.pop("net_arch", dict(pi=[64, 64], vf=[64, 64]))
+        activation = kw.pop("activation", "tanh")
+        if kw:
+            raise ValueError(f"unknown policy_kwargs: {sorted(kw)}")
+        pi, vf = (arch["pi"], arch["vf"]) if isinstance(arch, dict) else (arch, arch)
+        p = MlpPolicy(venv.batch.obs_dim, venv.n_turb, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed)
+        p.load_state_dict(sb3_orthogonal_init(p.desc, seed))
+        return p
+
+    # -- training -------------------------------------------------------------------------------------------------
+    def collect(self):
+        """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added."""
+        out = self.venv.rollout(self.policy, self.n_steps)
+        self.opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda,
+                     out=(self._adv, self._ret))
+        out["advantage"], out["returns"] = self._adv, self._ret
+        return out
+
+    def train(self, out, learning_rate, clip_range):
+        """SB3's ``PPO.train`` on a collected rollout: the epochs' permutations, then ONE wg_ppo_update."""
+        t = self.torch
+        for e in range(self.n_epochs):
+            self._perm[e].copy_(t.randperm(self.n_rows, generator=self._gen, device=self.policy.device))
+        T, O, N = self.n_steps, self.policy.n_in, self.policy.n_out
+        return self.opt.update(out["obs"][:T].view(-1, O), out["raw"].view(-1, N), out["logp"].view(-1), self._adv.view(-1),
+                               self._ret.view(-1), self._perm, self.batch_size, clip_range=clip_range, vf_coef=self.vf_coef,
+                               ent_coef=self.ent_coef, normalize_advantage=self.normalize_advantage,
+                               learning_rate=learning_rate, max_grad_norm=self.max_grad_norm, stats=self._stats)
+
+    def learn(self, total_timesteps, callback=None, log_interval=1, reset_num_timesteps=True):
+        """Iterations of rollout + update until ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``:
+        that many more).  ``callback(ppo) -> bool`` runs once per iteration; False stops.  Every ``log_interval``-th iteration
+        appends a record to ``self.log`` (one device-to-host copy; ``log_interval=None``: never, and no synchronisation)."""
+        from .binding import PPO_STATS
+        from .parallel import METRIC_NAMES, derive
+        t = self.torch
+        if reset_num_timesteps:
+            self.num_timesteps = 0
+        start, total = self.num_timesteps, int(total_timesteps) + (0 if reset_num_timesteps else self.num_timesteps)
+        t0 = time.perf_counter()
+        while self.num_timesteps < total:
+            progress = 1.0 - (self.num_timesteps - 0.0) / max(total, 1)
+            lr, clip = float(self._lr(progress)), float(self._clip(progress))
+            out = self.collect()
+            stats = self.train(out, lr, clip)
+            self.num_timesteps += self.n_rows
+            self.iteration += 1
+            if log_interval and self.iteration % int(log_interval) == 0:
+                ret, val = self._ret.double(), out["value"].double()
+                ev = 1.0 - (ret - val).var() / ret.var()
+                vec = t.cat([stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)])
+                host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
+                rec = dict(zip(PPO_STATS, host[:8].tolist()))
+                rec["explained_variance"] = float(host[8])
+                m = derive(host[9:9 + len(METRIC_NAMES)])
+                rec.update(iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr, clip_range=clip,
+                           n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
+                           mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"],
+                           fps=(self.num_timesteps - start) / max(time.perf_counter() - t0, 1e-9))
+                self.log.append(rec)
+            if callback is not None and callback(self) is False:
+                break
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic=False):
+        return self.policy.predict(obs, state, episode_start, deterministic)
+
+    # -- checkpoints ----------------------------------------------------------------------------------------------
+    def _hyper_json(self):
+        d = {k: getattr(self, k) for k in HYPER}
+        for k in ("learning_rate", "clip_range"):
+            if callable(d[k]):
+                d[k] = None                     # a schedule is code: pass it to load() again
+        return d
+
+    def save(self, path):
+        """Everything a bit-identical resume needs except the env itself (see the class docstring for the format)."""
+        import torch
+        mv, step = self.opt.state()
+        sd = {k: v.detach().cpu().clone() for k, v in self.policy.state_dict().items()}
+        pth = io.BytesIO()
+        torch.save(sd, pth)
+
+        def npy(a):
+            b = io.BytesIO()
+            np.save(b, a)
+            return b.getvalue()
+        meta = dict(format="windgym_amd.PPO/1", desc=dict(self.policy.desc), hyper=self._hyper_json(), seed=self.seed,
+                    policy_seed=self.policy.seed, policy_counter=self.policy.counter, num_timesteps=self.num_timesteps,
+                    iteration=self.iteration, adam_step=step, env_policy_steps=getattr(self.venv, "_policy_steps", 0), log=self.log)
+        with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+            z.writestr("policy.pth", pth.getvalue())
+            z.writestr("adam_state.npy", npy(mv))
+            z.writestr("generator_state.npy", npy(self._gen.get_state().cpu().numpy()))
+            z.writestr("windgym_ppo.json", json.dumps(meta))
+        return path
+
+    @classmethod
+    def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
+        """Resume: the policy, Adam's state, the permutation generator and every counter continue where ``save`` left them, so
+        that on an env in the same state ``learn(..., reset_num_timesteps=False)`` computes what the uninterrupted run would
+        have.  ``learning_rate`` / ``clip_range``: the schedules again, when the saved run used callables."""
+        import torch
+        from .policy import read_sb3_zip
+        with zipfile.ZipFile(path) as z:
+            if "windgym_ppo.json" not in z.namelist():
+                raise ValueError("not a windgym_amd PPO checkpoint (for an SB3 zip use MlpPolicy.from_sb3_zip)")
+            meta = json.loads(z.read("windgym_ppo.json").decode())
+            mv = np.load(io.BytesIO(z.read("adam_state.npy")))
+            gen = np.load(io.BytesIO(z.read("generator_state.npy")))
+        desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
+        pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
+                        device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"])
+        pol.load_state_dict(tensors)
+        pol.counter = int(meta["policy_counter"])
+        hyper = dict(meta["hyper"])
+        for k, v in (("learning_rate", learning_rate), ("clip_range", clip_range)):
+            if v is not None:
+                hyper[k] = v
+            elif hyper[k] is None:
+                raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
+        self = cls(pol, venv, seed=meta["seed"], **hyper)
+        self.opt.load_state(mv, meta["adam_step"])
+        self._gen.set_state(torch.from_numpy(gen))
+        self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
+        venv._policy_steps = int(meta["env_policy_steps"])
+        return self
+
+    def close(self):
+        self.opt.close()
