@@ -28,6 +28,7 @@
 #define WG_ENV_ABLATE 0     // profiling builds only: 1 = no bracket gathers, 2 = no advection pass, 4 = trivial advection arithmetic, 8 = no rotor-point loop
 #endif
 #include "wg_env_common.h"
+#include "wg_internal.h"
 
 #ifndef WG_ENV_S_UNROLL
 #define WG_ENV_S_UNROLL 0   // 1: the rotor-point loop of the pair evaluation unrolled by 4

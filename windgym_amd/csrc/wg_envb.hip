@@ -30,6 +30,7 @@
 
 #include "wg_env_common.h"
 #include "wg_box_dev.h"
+#include "wg_internal.h"
 
 #ifndef WG_ENVB_U
 #define WG_ENVB_U 2          // ring slots per lane and trip of the particle pass (their 6 streamed words and 4 box cells in flight together)

@@ -158,6 +158,8 @@ struct FlowPtrs {
 #define WG_ENV_SLOT_LDS_BYTES 160
 #define WG_ENV_FIXED_LDS_BYTES (3 * 64 * 16 + 2 * 64 * 8 + 4 * WG_ENV_SLOT_LDS_BYTES + 128)      // (+ the env header's 32 words)
 #define WG_ENV_CAP 256
+// ... and behind the waves' regions of its pass-wave instantiation, the pre-fetched glue inputs (layout: wg_glue_lean.h, LEAN_PRE_*)
+#define LEAN_PRE_BYTES 3584
 // k_flow_envb's LDS carve (wg_envb.hip): fixed part (per-lane turbine fields + row table + four slot records of 208 bytes + the lanes' parked registers) |
 // staged wakes float4[env_cap] | added TI float[env_cap] | candidate list (u16) | tables (FlowP::env_off_tab)
 #define WG_ENVB_FIXED_LDS_BYTES(nlp) ((93 + 48) * (nlp) + 4 * 208 + 128)      // nlp = lanes the per-lane arrays are sized for: 64, or 16 (four waves per env)

@@ -23,6 +23,7 @@
 
 #include "wg_flow_dev.h"
 #include "wg_box_dev.h"
+#include "wg_internal.h"
 #include <type_traits>
 
 struct __attribute__((aligned(8))) TurbLds {
@@ -2081,8 +2082,6 @@ static void launch_nt(const FlowP* p, const FlowPtrs* d, int mode, const float* 
 // One workgroup per farm slot.  Small farms (N <= 32): compact per-turbine rings + pair-major deficit phases, 64 or 128
 // threads; large farms: uniform rings with predicate pruning + (target, sample)-major deficit phases, 256 threads.
 // Chosen on the host (FlowP.res / FlowP.block).
-extern "C" void wg_launch_flow_env(const FlowP*, const FlowPtrs*, int, const float*, const uint8_t*, int, hipStream_t);
-extern "C" void wg_launch_flow_envb(const FlowP*, const FlowPtrs*, int, const float*, const uint8_t*, int, hipStream_t);
 extern "C" void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions,
                                const uint8_t* mask, int chunk, hipStream_t st) {
     if (p->envw && d->script_uvw == nullptr) {      // one / two waves per env: steady inflow (wg_env.hip) / frozen box (wg_envb.hip)

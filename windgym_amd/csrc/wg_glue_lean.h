@@ -323,8 +323,7 @@ struct LeanFused {
 #define LEAN_PRE_MET(lane) (768 + (lane))
 #define LEAN_PRE_FOLD 832
 #define LEAN_PRE_BOLD 833
-#define LEAN_PRE_FLAG 834
-#define LEAN_PRE_BYTES 3584
+#define LEAN_PRE_FLAG 834      // (the zone is LEAN_PRE_BYTES long: wg_flow.h, next to the carve it is appended to)
 
 // One env's glue after its flow step: power deques, window sums -> observation, reward, penalty, truncation, metrics, the
 // background episode's next share, and — at truncation — the swap.  One wave; `lane` 0 .. 63.

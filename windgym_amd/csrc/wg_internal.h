@@ -1,0 +1,48 @@
+// wg_internal.h — the library's internal functions that cross translation units: the launch wrappers of the kernels and two
+// helpers.  They have C linkage, so a caller's prototype that disagrees with the definition would still link; this is the one
+// declaration of each, included by the file that defines it and by every file that calls it, so that the compiler checks both.
+// (include after <hip/hip_runtime.h>; the parameter blocks are passed by pointer and need no definition here)
+#pragma once
+#include <stdint.h>
+
+#include "../../include/windgym_hip.h"
+
+struct FlowP;
+struct FlowPtrs;
+struct WgParams;
+struct WgPtrs;
+
+extern "C" {
+// wg_api.hip: the thread-local message behind wg_last_error; returns `code`
+int wg_set_last_error_(int code, const char* msg);
+// wg_policy.hip: wg_policy_act + optionally the critic on a second set of n_rows rows (obs2_dev -> value2_dev) in the same launch
+int wg_policy_act2_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
+                    float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, const float* obs2_dev, float* value2_dev,
+                    void* stream);
+// wg_flow.hip
+void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
+void wg_launch_windspeed(const FlowP* p, const FlowPtrs* d, int e, int farm, const float* xs, int nx, const float* ys, int ny, float z,
+                         int include_wakes, float* out, hipStream_t st);
+// wg_env.hip, wg_envb.hip
+void wg_launch_flow_env(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
+void wg_launch_flow_envb(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
+void wg_launch_step_env(const FlowP* p, const FlowPtrs* d, const WgParams* gp, const WgPtrs* gd, const float* actions, float* obs, float* reward,
+                        uint8_t* trunc, float* final_obs, hipStream_t st);
+void wg_launch_step_envb(const FlowP* p, const FlowPtrs* d, const WgParams* gp, const WgPtrs* gd, const float* actions, float* obs, float* reward,
+                         uint8_t* trunc, float* final_obs, hipStream_t st);
+// wg_kernels.hip
+void wg_launch_glue(const WgParams* p, const WgPtrs* d, int phase, const uint8_t* mask, float* obs, float* reward, uint8_t* trunc,
+                    float* final_obs, hipStream_t st, const WgParams* gp, const WgPtrs* gd);
+void wg_launch_init(const WgParams* p, const WgPtrs* d, const uint8_t* mask, const uint64_t* seeds, hipStream_t st);
+void wg_launch_create(const WgParams* p, const WgPtrs* d, hipStream_t st);
+void wg_launch_obs_multi(const WgParams* p, const WgPtrs* d, float* out, hipStream_t st);
+void wg_launch_info(const WgParams* p, const WgPtrs* d, int field, void* out, hipStream_t st);
+void wg_launch_metrics(const WgParams* p, const WgPtrs* d, float* out, int reset_after, hipStream_t st);
+void wg_launch_measurements(const WgParams* p, const WgPtrs* d, float* out, hipStream_t st);
+void wg_launch_unready(const WgParams* p, const WgPtrs* d, const uint8_t* mask, int* out, hipStream_t st);
+void wg_launch_box_repack(const float* planar, void* out, int nx, int ny, int nz, hipStream_t st);
+void wg_launch_box_coarsen(const void* fine, void* out, int nx, int ny, int nz, hipStream_t st);
+void wg_launch_box_stencil(const void* fine, void* out, int nx, int ny, int nz, hipStream_t st);
+// wg_steady.hip (sp: SteadyP, wg_steady.h)
+void wg_launch_steady(const void* sp, const float* ws, const float* wd, const float* ti, const float* yaw, float* power, hipStream_t st);
+}

@@ -12,6 +12,7 @@
 #include "wg_device.h"
 #include "wg_obs.h"
 #include "wg_glue_lean.h"
+#include "wg_internal.h"
 
 // copy one context's sensor rings into this wave's LDS region with coalesced loads (the window loops of
 // build_obs would otherwise issue long chains of dependent global loads); returns the bases to read from.

@@ -19,8 +19,8 @@
 #include <vector>
 
 #include "../../include/windgym_hip.h"
+#include "wg_internal.h"
 
-extern "C" int wg_set_last_error_(int code, const char* msg);      // wg_api.hip
 #define MCHK(x)                                                                                        \
     do {                                                                                               \
         hipError_t _e = (x);                                                                           \

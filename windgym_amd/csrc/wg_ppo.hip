@@ -25,8 +25,7 @@
 
 #include "../../include/windgym_hip.h"
 #include "wg_ppo.h"
-
-extern "C" int wg_set_last_error_(int code, const char* msg);      // wg_api.hip
+#include "wg_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -16,6 +16,7 @@
 
 #include "wg_device.h"
 #include "wg_steady.h"
+#include "wg_internal.h"
 
 __device__ __forceinline__ float st_interp(const float* __restrict__ xs, const float* __restrict__ ys, const int n, const float x) {
     if (!(x >= xs[0]) || x > xs[n - 1]) return 0.f;        // 0 outside the table (steady._interp)
