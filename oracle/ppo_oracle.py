@@ -4,7 +4,8 @@ wg_ppo_apply), written from the header's formulas and not from windgym_amd/csrc/
 * :func:`gae` is the backward recurrence, :func:`gae_brute` the per-env definition it is checked against;
 * :func:`loss` is the minibatch loss as a float64 torch expression on the CPU; :func:`loss_and_grad` takes its gradient from
   AUTOGRAD (the kernel's backward pass is hand-derived: the two share nothing);
-* :func:`adam_step` is gradient clipping by the global norm + one Adam step in numpy.
+* :func:`adam_step` is gradient clipping by the global norm + one Adam step in numpy;
+* :func:`tile_rows` is the row tile R of k_ppo_grad as windgym_amd/csrc/wg_ppo.h documents it (the LDS map of one net).
 
 Parameters are dicts under stable-baselines3's state-dict names (weights ``[out][in]``), as in policy_oracle.py.
 """
@@ -101,3 +102,22 @@ def adam_step(params, grad, m, v, step, lr, max_grad_norm, beta1=0.9, beta2=0.99
     mhat = m / (1.0 - beta1 ** step)
     denom = np.sqrt(v) / math.sqrt(1.0 - beta2 ** step) + eps
     return np.asarray(params, np.float64) - lr * mhat / denom, m, v
+
+
+def lds_floats(n_in, widths, rows, kc=256):
+    """Floats of wg_ppo.h's LDS map (WgPpoLds) of ONE net for tiles of ``rows`` rows; ``widths`` = the M of every layer, head
+    included.  S = rows + 1 floats per feature row: xin [min(n_in, kc)][S], act [sum M][S], d [2][max M][S], then rowv [4][32]
+    and rid [32]."""
+    s = rows + 1
+    return (min(n_in, kc) + sum(widths) + 2 * max(widths)) * s + 4 * 32 + 32
+
+
+def tile_rows(n_in, n_out, hidden_pi, hidden_vf, lds_bytes=65536, kc=256):
+    """-> (R, bytes of the larger net's map): the largest R of 32, 16, 8, 4, 2 at which the maps of BOTH nets (actor: hidden_pi +
+    [n_out], critic: hidden_vf + [1]) fit ``lds_bytes``; R is None when even R = 2 does not fit."""
+    nets = (list(hidden_pi) + [n_out], list(hidden_vf) + [1])
+    for rows in (32, 16, 8, 4, 2):
+        need = 4 * max(lds_floats(n_in, w, rows, kc) for w in nets)
+        if need <= lds_bytes:
+            return rows, need
+    return None, need

@@ -15,6 +15,26 @@ FIX = os.path.join(ROOT, "tests", "golden", "ppo_2975000_policy.npz")
 
 SHAPES = [(8, (64, 64), 4), (32, (64, 64), 16), (7, (33,), 1), (200, (128, 128, 128), 2), (1600, (256, 256), 16),
           (160, (64, 64), 80), (32, (), 16)]
+# the limits of wg_policy.h as (n_in, hidden_pi, hidden_vf, n_out): four hidden layers of 256 (five layers with the head), 2048 inputs
+# (eight full first-layer chunks), 256 / 257 inputs (a chunk of exactly one input), 128 outputs (four head tiles, a 128-term
+# log-probability sum), and actor / critic stacks of different depth and width (SB3's net_arch=dict(pi=[...], vf=[...]))
+DEEP = (256, 256, 256, 256)
+LIMIT_SHAPES = [(256, DEEP, DEEP, 16), (2048, DEEP, DEEP, 128), (257, (64,), (64,), 3), (256, (32,), (32,), 33), (2048, (), (), 128),
+                (256, (64, 64), DEEP, 16), (32, (64, 64), DEEP, 16), (256, DEEP, (64, 64), 16), (200, (128, 128, 128), (), 2),
+                (32, (), (33,), 16), (160, (256,), (64, 64), 80)]
+
+
+def _stack(h):
+    return "x".join(map(str, h)) or "none"
+
+
+def shape4(shape):
+    """(n_in, hidden, n_out) of SHAPES or (n_in, hidden_pi, hidden_vf, n_out) of LIMIT_SHAPES -> the latter"""
+    return shape if len(shape) == 4 else (shape[0], shape[1], shape[1], shape[2])
+
+
+def shape_id(shape):
+    return f"{shape[0]}-{_stack(shape[1])}-{shape[2]}" if len(shape) == 3 else f"{shape[0]}-pi{_stack(shape[1])}-vf{_stack(shape[2])}-{shape[3]}"
 
 
 def _torch():
@@ -40,11 +60,11 @@ def close(a, b, tol=2e-5, rel=0.0):
 
 
 @pytest.mark.parametrize("activation", ["tanh", "relu"])
-@pytest.mark.parametrize("shape", SHAPES, ids=[f"{a}-{'x'.join(map(str, h)) or 'none'}-{o}" for a, h, o in SHAPES])
+@pytest.mark.parametrize("shape", SHAPES + LIMIT_SHAPES, ids=shape_id)
 def test_kernel_vs_oracle_deterministic(shape, activation):
     t = _torch()
-    n_in, hidden, n_out = shape
-    p, sd = make(n_in, hidden, n_out, activation)
+    n_in, hidden, hidden_vf, n_out = shape4(shape)
+    p, sd = make(n_in, hidden, n_out, activation, hidden_vf=hidden_vf)
     rng = np.random.default_rng(11)
     for rows in (1, 389, 4096):
         x = rng.uniform(-1, 1, (rows, n_in)).astype(np.float32)
@@ -97,6 +117,23 @@ def test_stochastic_against_oracle_and_row_independence():
     p.close()
 
 
+@pytest.mark.parametrize("shape", LIMIT_SHAPES, ids=shape_id)
+def test_stochastic_against_oracle_at_the_limits(shape):
+    """Samples, log-probabilities and values of a stochastic call at the architecture limits, at a row offset and a counter that
+    use the high words of the noise stream's counter (global rows beyond 2^32)."""
+    t = _torch()
+    n_in, hidden, hidden_vf, n_out = shape4(shape)
+    p, sd = make(n_in, hidden, n_out, "tanh", hidden_vf=hidden_vf)
+    rows, row0, counter, seed = 389, (3 << 32) + 123457, (1 << 40) + 17, (0xABCDEF << 32) | 99
+    x = np.random.default_rng(6).uniform(-1, 1, (rows, n_in)).astype(np.float32)
+    a, raw, logp, v = (o.cpu().numpy() for o in p.act(t.from_numpy(x).cuda(), counter=counter, seed=seed, row_offset=row0))
+    ref = po.sample(sd, x, eps=po.policy_noise(seed, counter, row0 + np.arange(rows), n_out))
+    assert close(raw, ref["raw"], 1e-5 + 2e-5), np.abs(raw - ref["raw"]).max()
+    assert np.array_equal(a, np.clip(raw, -1, 1)) and close(logp, ref["logp"], 1e-4), np.abs(logp - ref["logp"]).max()
+    assert close(v, ref["value"], 2e-5, 2e-5), np.abs(v - ref["value"]).max()
+    p.close()
+
+
 def test_params_on_device_and_sync():
     t = _torch()
     p, sd = make(8, (64, 64), 4)
@@ -126,18 +163,21 @@ def _venv(n_envs=64, **kw):
     return v
 
 
-def test_rollout_equals_the_loop():
+def rollout_equals_the_loop(va, vb, p, T, rec=("power_agent", "yaw_agent"), out=None, min_trunc=None):
+    """va.rollout(p, T) == the Python loop of act + step on the twin vb, bit for bit: every buffer, the handle's state, the step
+    after it.  ``out``: va's rollout when the caller has already run it (va and vb were in the same state before it);
+    ``min_trunc``: truncations the T steps must contain (default: one per env).  Shared with tests/test_gpu_closed_loop.py, which
+    runs it on every step path."""
     t = _torch()
-    va, vb = _venv(), _venv()
-    O, N, B, T = va.batch.obs_dim, va.n_turb, va.num_envs, 300
-    p, _ = make(O, (64, 64), N)
-    rec = ("power_agent", "yaw_agent")
-    out = va.rollout(p, T, record=rec)
+    O, N, B = va.batch.obs_dim, va.n_turb, va.num_envs
+    seed, row0, counter0 = int(va._base_seed), va._global_offset, getattr(vb, "_policy_steps", 0)
+    if out is None:
+        out = va.rollout(p, T, record=rec)
     obs = vb.batch.obs.clone()
     assert t.equal(out["obs"][0], obs)
     n_trunc = 0
     for i in range(T):
-        a, raw, logp, v = p.act(obs, counter=i, seed=77, row_offset=0)
+        a, raw, logp, v = p.act(obs, counter=counter0 + i, seed=seed, row_offset=row0)
         assert t.equal(out["actions"][i], a) and t.equal(out["raw"][i], raw) and t.equal(out["logp"][i], logp) and t.equal(out["value"][i], v), i
         o, r, tr, f = vb.batch.step(a)
         assert t.equal(out["obs"][i + 1], o) and t.equal(out["reward"][i], r) and t.equal(out["truncated"][i], tr) and t.equal(out["final_obs"][i], f), i
@@ -146,21 +186,32 @@ def test_rollout_equals_the_loop():
         assert t.equal(out["final_value"][i], p.value(f)), i
         n_trunc += int(tr.sum())
         obs = o.clone()
-    assert n_trunc >= B, n_trunc                         # every env truncated and was swapped at least once
+    vb._policy_steps = counter0 + T
+    assert n_trunc >= (B if min_trunc is None else min_trunc), n_trunc      # default: every env truncated and was swapped at least once
     va.batch.check(); vb.batch.check()
     assert va.batch.get_state() == vb.batch.get_state()
     tr = out["truncated"][:-1].bool()
     assert t.equal(out["final_value"][:-1][~tr], out["value"][1:][~tr])
-    assert not t.equal(out["final_value"][:-1][tr], out["value"][1:][tr])
+    assert not tr.any() or not t.equal(out["final_value"][:-1][tr], out["value"][1:][tr])
     # a step() after a rollout() continues from obs[T]
     assert t.equal(va.batch.obs, out["obs"][T])
+    first = (out["obs"][0].clone(), out["raw"][0].clone())                 # (the buffers are reused by the next rollout)
     act = t.zeros((B, N), device="cuda")
     oa = va.step(act)[0].clone()
     ob = vb.step(act)[0]
     assert t.equal(oa, ob)
+    return out, first
+
+
+def test_rollout_equals_the_loop():
+    t = _torch()
+    va, vb = _venv(), _venv()
+    O, N, T = va.batch.obs_dim, va.n_turb, 300
+    p, _ = make(O, (64, 64), N)
+    out, (obs0, raw0) = rollout_equals_the_loop(va, vb, p, T)
     # the next rollout draws fresh noise
     out2 = va.rollout(p, 2)
-    assert not t.equal(out2["raw"][0] - p.torch_forward(out2["obs"][0])[0].detach(), out["raw"][0] - p.torch_forward(out["obs"][0])[0].detach())
+    assert not t.equal(out2["raw"][0] - p.torch_forward(out2["obs"][0])[0].detach(), raw0 - p.torch_forward(obs0)[0].detach())
     va.close(); vb.close(); p.close()
 
 

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import policy_oracle as po
 from oracle import ppo_oracle as oo
+from test_gpu_policy import LIMIT_SHAPES, shape4, shape_id
 from windgym_amd.policy import pack_params, param_layout
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +22,16 @@ def _torch():
     return torch
 
 
-def make(n_in, hidden, n_out, activation="tanh", seed=3):
+def tile_id(shape):
+    """the test id of a shape with the row tile R it must get (wg_ppo.h's LDS map, restated in oracle/ppo_oracle.py: tile_rows)"""
+    n_in, hidden, hidden_vf, n_out = shape4(shape)
+    return shape_id(shape) if len(shape) == 3 else f"{shape_id(shape)}-R{oo.tile_rows(n_in, n_out, hidden, hidden_vf)[0]}"
+
+
+def make(n_in, hidden, n_out, activation="tanh", seed=3, hidden_vf="same"):
     """A policy with every tensor away from its initial value (biases and log_std included) + its float64 state dict."""
     from windgym_amd.policy import MlpPolicy
-    p = MlpPolicy(n_in, n_out, hidden, hidden, activation, seed=seed)
+    p = MlpPolicy(n_in, n_out, hidden, hidden if hidden_vf == "same" else hidden_vf, activation, seed=seed)
     rng = np.random.default_rng(seed + 1)
     sd = {}
     for name, shape in param_layout(p.desc):
@@ -78,15 +85,19 @@ def test_gae_vs_oracle(T, B):
 
 
 @pytest.mark.parametrize("activation", ["tanh", "relu"])
-@pytest.mark.parametrize("shape", SHAPES, ids=[f"{a}-{'x'.join(map(str, h)) or 'none'}-{o}" for a, h, o in SHAPES])
+@pytest.mark.parametrize("shape", SHAPES + LIMIT_SHAPES, ids=tile_id)
 def test_grad_vs_autograd_oracle(shape, activation):
     from windgym_amd.ppo import PPOOptimizer
     t = _torch()
-    n_in, hidden, n_out = shape
-    p, sd = make(n_in, hidden, n_out, activation)
+    n_in, hidden, hidden_vf, n_out = shape4(shape)
+    p, sd = make(n_in, hidden, n_out, activation, hidden_vf=hidden_vf)
     opt = PPOOptimizer(p)
-    # (n, index array?, normalise?); 65 536 rows of 1600 inputs would need a gigabyte for the float64 oracle: skipped there
-    cases = [(1, False, True), (33, True, True), (389, False, True), (4096, True, False)] + ([(65536, True, True)] if n_in <= 200 else [])
+    R = oo.tile_rows(n_in, n_out, hidden, hidden_vf)[0]
+    # (n, index array?, normalise?); 65 536 rows of 1600 inputs would need a gigabyte for the float64 oracle: skipped there and at
+    # the limit shapes; a minibatch of exactly one tile, one row more and one row short of two tiles where the tile is smallest
+    cases = [(1, False, True), (33, True, True), (389, False, True), (4096, True, False)]
+    cases += [(65536, True, True)] if n_in <= 200 and len(shape) == 3 else []
+    cases += [(R, False, True), (R + 1, True, True), (2 * R - 1, False, False)] if R == 4 else []
     for n, use_index, norm in cases:
         extra = 37
         obs, raw, lpo, adv, ret = batch(sd, n_in, n_out, n + extra, activation, seed=n)
@@ -105,10 +116,80 @@ def test_grad_vs_autograd_oracle(shape, activation):
         ref = flat_grad(p.desc, grads)
         err = np.abs(g - ref).max()
         assert err <= 1e-4 * np.linalg.norm(ref) + 1e-6, (n, err, np.linalg.norm(ref))
+        # At the limit shapes the surrogate's statistics also carry the float32 resolution of the log-probability itself: a sum of up
+        # to 128 terms, |logp| up to 200, enters ratio = exp(logp - logp_old) and is weighted by the advantage, and a minibatch of a
+        # few rows averages nothing away.  Worst observed on an MI355X: 1.86e-5 on pi_loss at 7 rows of 128 outputs, 4.5 times less
+        # than this term there.  The shapes of SHAPES keep their bar as it was.
+        A = adv[rows] if not (norm and n > 1) else (adv[rows] - adv[rows].mean()) / (adv[rows].std(ddof=1) + 1e-8)
+        res = 2.0 ** -23 * np.abs(lpo[rows]).max() * max(1.0, np.abs(A).max()) if len(shape) == 4 else 0.0
         for i, k in enumerate(STATS):
             # (a ratio within rounding of a clip bound may fall on the other side in float32: two rows of slack there)
-            tol = 2.0 / n if k == "clip_fraction" else 1e-5 * max(1.0, abs(rs[k]))
+            tol = 2.0 / n if k == "clip_fraction" else 1e-5 * max(1.0, abs(rs[k])) + (res if k in ("pi_loss", "loss") else 0.0)
             assert abs(st[i] - rs[k]) <= tol, (n, k, st[i], rs[k])
+    opt.close(); p.close()
+
+
+EDGES = ["clip_0.05", "clip_0.5", "vf_coef_0", "ent_coef_0", "constant_advantage", "saturated_tanh", "dead_relu_layer", "log_std_-3",
+         "log_std_+1.5", "repeated_rows"]
+
+
+@pytest.mark.parametrize("edge", EDGES)
+def test_grad_loss_head_edges(edge):
+    """k_ppo_grad where the loss head or an activation's derivative degenerates, against the float64 autograd oracle, same bars."""
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    n_in, hidden, n_out, n, total = 32, (64, 64), 16, 1024, 1500
+    activation = "relu" if edge == "dead_relu_layer" else "tanh"
+    p, sd = make(n_in, hidden, n_out, activation)
+    kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=True)
+    kw.update({"clip_0.05": dict(clip_range=0.05), "clip_0.5": dict(clip_range=0.5), "vf_coef_0": dict(vf_coef=0.0),
+               "ent_coef_0": dict(ent_coef=0.0)}.get(edge, {}))
+    pre = "mlp_extractor.policy_net."
+    if edge == "saturated_tanh":                                         # |pre-activation| of every hidden unit far beyond tanh's range
+        for k in sd:
+            if k.startswith("mlp_extractor") and k.endswith("weight"):
+                sd[k] = sd[k] * 400.0
+    elif edge == "dead_relu_layer":                                      # no unit of either net's first hidden layer ever fires
+        sd[pre + "0.bias"][:] = -100.0
+        sd["mlp_extractor.value_net.0.bias"][:] = -100.0
+        sd[pre + "2.bias"][:] = np.abs(sd[pre + "2.bias"]) + 0.1         # (the layer behind it lives on its biases)
+    elif edge.startswith("log_std"):
+        sd["log_std"][:] = float(edge.split("_")[-1])
+    p.load_state_dict({k: v.astype(np.float32) for k, v in sd.items()})
+    opt = PPOOptimizer(p)
+    obs, raw, lpo, adv, ret = batch(sd, n_in, n_out, total, activation, seed=21)
+    rng = np.random.default_rng(22)
+    rows = rng.permutation(total)[:n]
+    if edge == "constant_advantage":
+        adv[:] = 0.5            # std 0: the divisor is 1e-8.  (0.5: the float32 mean of n copies is exact, as the float64 one is)
+    elif edge == "repeated_rows":
+        rows = rng.integers(0, 40, n)                                    # every one of 40 rows about 25 times
+        assert len(np.unique(rows)) < n
+    g, st = opt.grad(*dev(obs, raw, lpo, adv, ret), index=dev(rows.astype(np.int32))[0], **kw)
+    g, st = g.cpu().numpy().astype(np.float64), st.cpu().numpy()
+    _, grads, rs, ratio = oo.loss_and_grad(sd, obs[rows], raw[rows], lpo[rows], adv[rows], ret[rows], activation=activation, **kw)
+    ref = flat_grad(p.desc, grads)
+    err = np.abs(g - ref).max()
+    assert np.all(np.isfinite(g)) and err <= 1e-4 * np.linalg.norm(ref) + 1e-6, (err, np.linalg.norm(ref))
+    for i, k in enumerate(STATS):
+        tol = 2.0 / n if k == "clip_fraction" else 1e-5 * max(1.0, abs(rs[k]))
+        assert abs(st[i] - rs[k]) <= tol, (k, st[i], rs[k])
+    got = dict(zip([name for name, _ in param_layout(p.desc)], np.split(g, np.cumsum([int(np.prod(s)) for _, s in param_layout(p.desc)])[:-1])))
+    if edge == "clip_0.05":
+        assert rs["clip_fraction"] > 0.5
+    elif edge == "clip_0.5":
+        assert 0.0 < rs["clip_fraction"] < 0.2
+    elif edge == "constant_advantage":
+        assert all(np.all(got[k] == 0.0) for k in got if "policy_net" in k or k.startswith("action_net")) and st[0] == 0.0
+        assert np.all(got["log_std"] == -np.float32(kw["ent_coef"])) and np.abs(got["value_net.bias"]).max() > 0
+    elif edge == "saturated_tanh":
+        hid = np.tanh(obs[rows].astype(np.float64) @ sd[pre + "0.weight"].T + sd[pre + "0.bias"])
+        assert np.mean(np.abs(hid) > 1 - 1e-7) > 0.9 and np.abs(got["action_net.bias"]).max() > 0
+    elif edge == "dead_relu_layer":
+        for k in (pre + "0.weight", pre + "0.bias", pre + "2.weight", "mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
+                  "mlp_extractor.value_net.2.weight"):
+            assert np.all(got[k] == 0.0), k                              # exactly 0 upstream of the dead layer
+        assert np.abs(got["action_net.bias"]).max() > 0 and np.abs(got[pre + "2.bias"]).max() > 0 and np.abs(got["value_net.bias"]).max() > 0
     opt.close(); p.close()
 
 
@@ -253,11 +334,32 @@ def _torch_trainer(policy, out, adv, ret, perm, bs, lr, clip, vf_coef, ent_coef,
     return w.detach()
 
 
-def test_one_iteration_vs_torch_reference_trainer():
+def _small_box():
+    from windgym_amd.mann import generate_mann_box
+    return generate_mann_box((256, 64, 32), (3.0, 3.0, 3.0), seed=1234), (3.0, 3.0, 3.0)
+
+
+def _cfg5_venv(n_envs):
+    """cfg2's farm in a frozen Mann box (the small box of the spot checks): k_flow_envb"""
+    v = _venv(n_envs, turbtype="MannGenerate", turbulence_box=_small_box())
+    assert v.batch.flow_variant() == (64, True, 2)
+    return v
+
+
+def _cfg3_venv(n_envs):
+    """Horns Rev 1, 80 turbines: k_flow<256> + k_glue_lean, a policy of 160 inputs and 80 outputs"""
+    from windgym_amd import presets
+    x, y = presets.horns_rev1_layout()
+    v = _venv(n_envs, yaml_dict=presets.horns_rev_config(), x_pos=x, y_pos=y, n_passthrough=0.5)
+    assert v.batch.flow_variant() == (256, True, 0) and v.n_turb == 80
+    return v
+
+
+def _one_iteration_vs_torch_reference_trainer(v, rel_bar=1e-5 * 10):
     from windgym_amd.ppo import PPO
     t = _torch()
-    v = _venv(512)
-    ppo = PPO("MlpPolicy", v, n_steps=32, n_epochs=2, batch_size=512 * 32 // 4, ent_coef=0.01, seed=3)
+    B = v.num_envs
+    ppo = PPO("MlpPolicy", v, n_steps=32, n_epochs=2, batch_size=B * 32 // 4, ent_coef=0.01, seed=3)
     out = ppo.collect()
     gen_state = ppo._gen.get_state()
     before = ppo.policy.params.clone()
@@ -271,9 +373,29 @@ def test_one_iteration_vs_torch_reference_trainer():
     moved = (after - before).abs().max().item()
     assert moved > 1e-4
     err = ((after - ref).abs() / (ref.abs() + 1e-3)).max().item()
-    assert err <= 1e-5 * 10, err                                         # relative, with a floor of 1e-3 on |w|
+    assert err <= rel_bar, err                                           # relative, with a floor of 1e-3 on |w|
     assert (after - ref).abs().max().item() <= 1e-5
     ppo.close(); ppo.policy.close(); v.close()
+
+
+def test_one_iteration_vs_torch_reference_trainer():
+    _one_iteration_vs_torch_reference_trainer(_venv(512))
+
+
+@pytest.mark.parametrize("which", ["cfg5", "cfg3"])
+def test_one_iteration_vs_torch_reference_trainer_on_other_paths(which):
+    """the same iteration on the frozen-box kernel (256 envs) and on the large-farm kernels (64 envs, 80 outputs).
+
+    cfg5 keeps every bar.  On cfg3 the absolute bar (1e-5 on every parameter; worst observed on an MI355X 3.03e-6) stays, the relative
+    one is 1e-2 against a worst case of 2.53e-3: SB3 initialises the action head with gain 0.01, so its 80 x 64 weights are of the
+    order of the 1e-3 floor, and the worst entry (reference value -1.97e-4) is one whose gradient over the 512 rows of a minibatch nearly
+    cancels — Adam divides by that |g|, so the float32 summation orders of k_ppo_grad and of torch's autograd differ by 1.25e-3 of the
+    entry's movement.  The same fraction was measured at learning rates 3e-4 (clip fractions up to 0.16) and 3e-5 (nothing clipped):
+    it is not a row falling on the other side of a clip bound."""
+    if which == "cfg5":
+        _one_iteration_vs_torch_reference_trainer(_cfg5_venv(256))
+    else:
+        _one_iteration_vs_torch_reference_trainer(_cfg3_venv(64), rel_bar=1e-2)
 
 
 def test_descent_on_a_fixed_batch():
@@ -300,12 +422,12 @@ def _two_turbine_venv(n_envs=32):
     return _venv(n_envs, yaml_dict=d)
 
 
-@pytest.mark.parametrize("which", ["two_turbine", "cfg2"])
+@pytest.mark.parametrize("which", ["two_turbine", "cfg2", "cfg5"])
 def test_learn_save_load_continue(which, tmp_path):
     from windgym_amd.policy import MlpPolicy, read_sb3_zip
     from windgym_amd.ppo import PPO
     t = _torch()
-    mk = (lambda: _two_turbine_venv(32)) if which == "two_turbine" else (lambda: _venv(64))
+    mk = {"two_turbine": lambda: _two_turbine_venv(32), "cfg2": lambda: _venv(64), "cfg5": lambda: _cfg5_venv(64)}[which]
     T = 40
     kw = dict(n_steps=T, n_epochs=2, ent_coef=0.001, seed=11)
     # uninterrupted: 4 iterations

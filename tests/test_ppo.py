@@ -1,7 +1,10 @@
 """CPU tests of the training layer: the oracle itself (GAE against its brute-force definition, Adam against torch.optim.Adam,
 the loss on hand-computable rows), PPO's argument validation and SB3's initialisation.  The kernels are tested on the GPU
 (tests/test_gpu_ppo.py); the ABI test (tests/test_abi.py) picks the new entries up from the header."""
+import itertools
 import math
+import os
+import re
 
 import numpy as np
 import pytest
@@ -127,3 +130,40 @@ def test_checkpoint_policy_member_reads_back(tmp_path):
         z.writestr("windgym_ppo.json", "{}")
     d2, t2 = read_sb3_zip(path)
     assert d2 == desc and all(np.array_equal(t2[k], sd[k]) for k in sd)
+
+
+def _defines(header):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, *header)).read()
+    return {k: int(v) for k, v in re.findall(r"^#define\s+(\w+)\s+(\d+)\b", text, flags=re.M)}
+
+
+def test_row_tile_of_every_legal_architecture_corner():
+    """k_ppo_grad's row tile R (wg_ppo.h: 32 when a net's activations fit the workgroup's LDS, else 16, 8, 4 or 2) over the corners
+    of what wg_policy_create accepts — n_in, widths and depths of both nets, n_out at their smallest, largest and either side of
+    the 256-input chunk.  R = 32, 16, 8 and 4 occur.  Only an ACTOR of four hidden layers of 256 reaches R = 4, and only with
+    n_out + min(n_in, 256) > 266 (its map is (min(n_in, 256) + 1024 + n_out + 512) (R + 1) + 160 floats); a critic of that depth stays
+    at R = 8 whatever n_in is (256 + 1024 + 1 + 512 = 1793 <= 1802).  R = 2 is unreachable inside the limits: no map exceeds the
+    budget."""
+    pol, ppo, api = (_defines(h) for h in (("windgym_amd", "csrc", "wg_policy.h"), ("windgym_amd", "csrc", "wg_ppo.h"), ("include", "windgym_hip.h")))
+    KC, W, OUT, IN, H, LDS = pol["WGP_KC"], pol["WGP_MAX_WIDTH"], pol["WGP_MAX_OUT"], pol["WGP_MAX_IN"], api["WG_POLICY_MAX_HIDDEN"], ppo["WGT_LDS_BYTES"]
+    assert (KC, W, OUT, IN, H, LDS) == (256, 256, 128, 2048, 4, 65536) and pol["WGP_MAX_LAYERS"] == H + 1
+    stacks = [()] + [(w,) * n for n in range(1, H + 1) for w in (1, 33, 64, W)] + [(W, 1, W, 1), (1, W), (64, W, 64)]
+    seen = {}
+    for n_in, n_out, pi, vf in itertools.product((1, 32, KC - 1, KC, KC + 1, IN), (1, 16, 33, OUT), stacks, stacks):
+        R, need = oo.tile_rows(n_in, n_out, pi, vf, LDS, KC)
+        assert R is not None and need <= LDS, (n_in, n_out, pi, vf)
+        if R < 32:                                             # the next larger tile did not fit: R is the largest that does
+            assert 4 * max(oo.lds_floats(n_in, list(w) + [o], 2 * R, KC) for w, o in ((pi, n_out), (vf, 1))) > LDS
+        seen.setdefault(R, []).append((n_in, n_out, pi, vf))
+    assert sorted(seen) == [4, 8, 16, 32], sorted(seen)
+    for R, shapes in seen.items():
+        for n_in, n_out, pi, vf in shapes:
+            assert (R == 4) == (pi == (W,) * H and n_out + min(n_in, KC) > 266), (R, n_in, n_out, pi, vf)
+    # the worst case of the limits, by hand: (256 + 4 * 256 + 128 + 2 * 256) * 5 + 160 floats at R = 4
+    assert oo.tile_rows(IN, OUT, (W,) * H, (W,) * H, LDS, KC) == (4, 4 * (1920 * 5 + 160))
+    # and the shapes the GPU tests name in their ids
+    assert oo.tile_rows(8, 4, (64, 64), (64, 64))[0] == 32 and oo.tile_rows(1600, 16, (256, 256), (256, 256))[0] == 8
+    assert oo.tile_rows(200, 2, (128, 128, 128), (128, 128, 128))[0] == 16
+    assert oo.tile_rows(256, 16, (W,) * H, (W,) * H)[0] == 4 and oo.tile_rows(256, 16, (W,) * H, (64, 64))[0] == 4
+    assert oo.tile_rows(256, 16, (64, 64), (W,) * H)[0] == 8 and oo.tile_rows(32, 16, (64, 64), (W,) * H)[0] == 8
