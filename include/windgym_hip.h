@@ -300,6 +300,15 @@ int wg_obs_multi(wg_handle h, float* obs_dev, void* stream);
  * after the call) — WindFarmEnvMulti.step calls _get_obs_multi every step (WindEnvMulti.py:188-227).  NULL stops. */
 int wg_set_obs_multi_buffer(wg_handle h, float* obs_multi_dev);
 
+/* The per-agent observation an episode ENDED in (what a value bootstrap at truncation needs; the buffer above only ever
+ * holds the first observation of the next episode): a second caller-owned buffer f32[B,N,obs_dim_multi].  After every
+ * following wg_step, row (e, i) holds agent i's observation of the state the step ended in — for an env that truncated, the
+ * FINISHED episode's (its turbine block ++ the agents' farm block, as wg_obs_multi would have returned it before the
+ * reset); for every other env, bit for bit the row of the buffer above.  Needs that buffer registered (WG_ERR_INVALID
+ * otherwise; unregistering it drops this one too); same length bound.  Not written by wg_reset.  NULL stops, and a handle
+ * that never registered one computes exactly what it always did.                                                    */
+int wg_set_final_obs_multi_buffer(wg_handle h, float* final_obs_multi_dev);
+
 /* Unscaled, unclipped sensor values of the running episodes in the layout of the observation: f32[B,O]
  * (farm_measurements.get_*_turb() / get_*_farm(), the "... measured" entries of _get_info :529-537).   */
 int wg_get_measurements(wg_handle h, float* out_dev, void* stream);
@@ -476,6 +485,44 @@ typedef struct wg_rollout_bufs {
 int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                uint64_t row_offset, const wg_rollout_bufs* out, void* stream);
 
+/* Caller-owned device buffers of wg_rollout_multi, T = n_steps, B / N / O / Om = obs_dim_multi of the handle; one ROW per
+ * agent (env e, turbine i) = row e * N + i; NULL = not wanted where noted.                                          */
+typedef struct wg_rollout_multi_bufs {
+    float*   obs_multi;        /* [T+1, B, N, Om]  obs_multi[0] is INPUT (the per-agent observation the env last returned) */
+    float*   actions;          /* [T, B, N]        one yaw action per agent = what wg_step received (clipped)         */
+    float*   raw;              /* [T, B, N]        or NULL                                                           */
+    float*   logp;             /* [T, B, N]        or NULL                                                           */
+    float*   value;            /* [T, B, N]        or NULL: V(obs_multi[t]) per agent                                */
+    float*   final_obs_multi;  /* [T, B, N, Om]    or NULL (required with final_value): wg_set_final_obs_multi_buffer */
+    float*   final_value;      /* [T, B, N]        or NULL: V(final_obs_multi[t])                                    */
+    float*   reward;           /* [T, B]           the farm reward, shared by the env's agents                       */
+    uint8_t* truncated;        /* [T, B]                                                                              */
+    float*   obs;              /* [T+1, B, O]      or NULL: the flat observation; slot 0 is not touched               */
+    float*   final_obs;        /* [T, B, O]        or NULL                                                           */
+    int32_t  n_info;           /* recorded info fields, as in wg_rollout_bufs                                         */
+    const int32_t* info_fields;
+    void* const*   info_out;
+} wg_rollout_multi_bufs;
+
+/* wg_rollout for ONE policy shared by the turbines (WindGym/WindEnvMulti.py: one agent per turbine, each seeing its own
+ * turbine block plus the farm block, each sending one yaw action, all sharing the farm reward): `p` maps obs_dim_multi -> 1
+ * and is evaluated on B * N agent rows per step.  Enqueued on `stream` with no host synchronisation, no allocation and no
+ * return to the caller in between; buffers and the handle's state afterwards are BIT-IDENTICAL to
+ *     for t in 0 .. T-1:
+ *         wg_set_obs_multi_buffer(h, obs_multi[t+1]);  wg_set_final_obs_multi_buffer(h, final_obs_multi[t])
+ *         wg_policy_act(p, B * N, obs_multi[t], deterministic, seed, counter0 + t, row_offset * N, actions[t], raw[t], logp[t], value[t])
+ *         wg_step(h, actions[t], obs[t+1], reward[t], truncated[t], final_obs[t])
+ *         wg_get_info(h, info_fields[i], info_out[i] + t * <size of the field>)       for every i
+ *         wg_policy_act(p, B * N, final_obs_multi[t], value only -> final_value[t])    if wanted
+ * after which the handle's own two per-agent buffers are registered again (they are not written).  The noise row of agent i
+ * of env e is (row_offset + e) * N + i: a shard of the env axis computes what the unsharded batch computes.  Without `obs`
+ * the steps' flat observation goes to a buffer of the handle's own, allocated by the first such call before anything is
+ * enqueued.  Advantages: wg_gae_shared.
+ * WG_ERR_INVALID: as wg_rollout, with p's n_in != obs_dim_multi or n_out != 1, final_value without final_obs_multi, or no
+ * per-agent buffer registered on the handle.                                                                         */
+int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                     uint64_t row_offset, const wg_rollout_multi_bufs* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Training on the device: what `PPO("MlpPolicy", env, n_steps=2048).learn(...)` does between two rollouts
  * (examples/longer_steps_example.py:212-240, examples/curriculum.py:544-560) — advantages, the clipped-surrogate loss and
@@ -491,6 +538,13 @@ typedef struct wg_ppo_s* wg_ppo;
  *   returns_t = A_t + value_t.   One launch on the current device.                                                 */
 int wg_gae(int T, int B, const float* reward_dev, const float* value_dev, const float* final_value_dev,
            const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out, void* stream);
+
+/* The same for agents that share their env's reward (wg_rollout_multi's buffers): value / final_value / advantage / returns
+ * are [T, B, A], reward / truncated [T, B]; agent row (b, a) runs the recurrence above with reward[t, b] and truncated[t, b].
+ * A = 1 is wg_gae bit for bit.  The update is wg_ppo_update on the T * B * A agent rows: independent PPO with shared
+ * parameters, each agent's critic on its own observation.                                                          */
+int wg_gae_shared(int T, int B, int A, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+                  const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out, void* stream);
 
 /* The optimiser of `p` (curriculum.py:544-560: PPO(...) owns torch.optim.Adam): Adam's moments and step count, the scratch
  * of the gradient kernel.  `p` must outlive it.  WG_ERR_INVALID: a policy without a critic or without log_std.     */

@@ -32,6 +32,7 @@ UINT64_MAX = 0xFFFFFFFFFFFFFFFF
 ABI_SYMBOLS = (
     "wg_last_error", "wg_abi_version", "wg_create", "wg_destroy", "wg_obs_dim", "wg_hist_max",
     "wg_set_turbulence_box", "wg_set_turbulence_boxes", "wg_set_added_turbulence_box", "wg_set_deficit_table", "wg_set_box_ids", "wg_set_wind", "wg_set_wind_device", "wg_set_flow_script", "wg_reset", "wg_step", "wg_set_step_graph", "wg_check", "wg_obs_multi", "wg_set_obs_multi_buffer",
+    "wg_set_final_obs_multi_buffer", "wg_rollout_multi", "wg_gae_shared",
     "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
     "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
     "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
@@ -57,6 +58,14 @@ class CRolloutBufs(C.Structure):
                 ("value", C.c_void_p), ("final_obs", C.c_void_p), ("final_value", C.c_void_p), ("reward", C.c_void_p),
                 ("truncated", C.c_void_p), ("n_info", C.c_int32), ("info_fields", C.POINTER(C.c_int32)),
                 ("info_out", C.POINTER(C.c_void_p))]
+
+
+class CRolloutMultiBufs(C.Structure):
+    """wg_rollout_multi_bufs"""
+    _fields_ = [("obs_multi", C.c_void_p), ("actions", C.c_void_p), ("raw", C.c_void_p), ("logp", C.c_void_p),
+                ("value", C.c_void_p), ("final_obs_multi", C.c_void_p), ("final_value", C.c_void_p), ("reward", C.c_void_p),
+                ("truncated", C.c_void_p), ("obs", C.c_void_p), ("final_obs", C.c_void_p), ("n_info", C.c_int32),
+                ("info_fields", C.POINTER(C.c_int32)), ("info_out", C.POINTER(C.c_void_p))]
 
 
 class CPpoBatch(C.Structure):
@@ -138,6 +147,11 @@ def load_library():
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
                              C.POINTER(CRolloutBufs), C.c_void_p]
+    L.wg_set_final_obs_multi_buffer.argtypes = [C.c_void_p, C.c_void_p]
+    L.wg_rollout_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                   C.POINTER(CRolloutMultiBufs), C.c_void_p]
+    L.wg_gae_shared.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_gae.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
                          C.c_void_p, C.c_void_p]
     L.wg_ppo_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -265,12 +279,26 @@ class HipBatch:
         obs_multi() launch per step."""
         if not enable:
             _chk(self.L.wg_set_obs_multi_buffer(self._h, None), "wg_set_obs_multi_buffer")
-            self._multi_buf = None
+            self._multi_buf = self._multi_fin = None      # (the library drops the final buffer with it)
             return None
         t = self.torch
         self._multi_buf = t.zeros((self.B, self.N, self.obs_dim_multi), dtype=t.float32, device=self.device)
         _chk(self.L.wg_set_obs_multi_buffer(self._h, C.c_void_p(self._multi_buf.data_ptr())), "wg_set_obs_multi_buffer")
         return self._multi_buf
+
+    def fuse_final_obs_multi(self, enable=True):
+        """After ``fuse_obs_multi()``: let every following step() also write the per-agent observation of the state the step
+        ENDED in — a truncating env's finished episode, every other env's rows of the per-agent buffer — into a persistent
+        tensor [B, N, obs_dim_multi], returned here and updated in place (wg_set_final_obs_multi_buffer)."""
+        if not enable:
+            _chk(self.L.wg_set_final_obs_multi_buffer(self._h, None), "wg_set_final_obs_multi_buffer")
+            self._multi_fin = None
+            return None
+        t = self.torch
+        buf = t.zeros((self.B, self.N, self.obs_dim_multi), dtype=t.float32, device=self.device)
+        _chk(self.L.wg_set_final_obs_multi_buffer(self._h, C.c_void_p(buf.data_ptr())), "wg_set_final_obs_multi_buffer")
+        self._multi_fin = buf
+        return buf
 
     def measurements(self):
         """Unscaled sensor values in the layout of the observation, f32[B, O]."""

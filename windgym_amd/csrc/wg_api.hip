@@ -115,6 +115,7 @@ struct wg_env_s {
     int* unready_dev = nullptr;     // wg_reset: live slots of the masked envs that are not developed yet
     WgParams* p_dev = nullptr;      // device copies of p / d, read by the episode-initialisation path at the head of k_flow
     WgPtrs* d_dev = nullptr;
+    float* flat_scratch = nullptr;  // [B][obs_dim]: where wg_rollout_multi's steps put the flat observation nobody asked for
 };
 
 static const size_t WG_MAX_STEP_GRAPHS = 32;   // distinct (actions, obs, reward, truncated, final_obs) pointer sets cached
@@ -750,6 +751,7 @@ extern "C" int wg_set_obs_multi_buffer(wg_handle h, float* obs_multi_dev) {
                                         "per-agent packing (use wg_obs_multi)");
     if (h->d.multi_out != obs_multi_dev) drop_step_graphs(h);
     h->d.multi_out = obs_multi_dev;     // borrowed; written by k_glue in every following wg_step / wg_reset
+    if (!obs_multi_dev) h->d.multi_fin = nullptr;      // (the final buffer is written by the per-agent instantiations only)
     if (int rc = use_device(h)) return rc;
     // (the per-agent instantiation of k_glue neither consumes nor retires the prepared first observations of
     // WgPtrs::next_obs: switching between the two must not leave a flag of an episode that has since been replaced)
@@ -757,6 +759,20 @@ extern "C" int wg_set_obs_multi_buffer(wg_handle h, float* obs_multi_dev) {
         HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemset(h->d.next_obs_ok, 0, sizeof(int) * (size_t)h->p.B * 2));
     }
+    return sync_dev_params(h);
+}
+
+extern "C" int wg_set_final_obs_multi_buffer(wg_handle h, float* final_obs_multi_dev) {
+    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (final_obs_multi_dev && !h->d.multi_out)
+        return fail(WG_ERR_INVALID, "wg_set_final_obs_multi_buffer: register the per-agent buffer first (wg_set_obs_multi_buffer)");
+    // (same bound as wg_set_obs_multi_buffer: the farm block of a wave's agents is built once, in LDS, for both buffers)
+    if (final_obs_multi_dev && (size_t)h->p.farm_obs * 4 * WG_NWAVES > 65536)
+        return fail(WG_ERR_UNSUPPORTED, "wg_set_final_obs_multi_buffer: the farm-level observation block is too long for the fused "
+                                        "per-agent packing (use wg_obs_multi)");
+    if (h->d.multi_fin != final_obs_multi_dev) drop_step_graphs(h);
+    h->d.multi_fin = final_obs_multi_dev;     // borrowed; written by the glue of every following wg_step
+    if (int rc = use_device(h)) return rc;
     return sync_dev_params(h);
 }
 
@@ -852,6 +868,72 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
         if (int rc = wg_policy_act(p, B, o->final_obs + (n_steps - 1) * sBO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
                                    o->final_value + (size_t)(n_steps - 1) * B, stream))
             return rc;
+    return 0;
+}
+
+// The multi-agent closed loop (windgym_hip.h: wg_rollout_multi): wg_rollout's loop on agent rows.  The per-agent buffers of
+// step t are the kernel arguments of that step's launches (WgPtrs travels by value), so pointing the handle's two per-agent
+// pointers at slot t on the host between launches is all "wg_set_obs_multi_buffer per step" takes here: no device copy of
+// the parameter block is read for them, nothing is synchronised.
+extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                                uint64_t row_offset, const wg_rollout_multi_bufs* o, void* stream) {
+    if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout_multi: null argument");
+    if (n_steps < 0) return fail(WG_ERR_INVALID, "wg_rollout_multi: n_steps < 0");
+    if (!o->obs_multi || !o->actions || !o->reward || !o->truncated)
+        return fail(WG_ERR_INVALID, "wg_rollout_multi: obs_multi, actions, reward and truncated buffers are required");
+    if (p->device != h->device) return fail(WG_ERR_INVALID, "wg_rollout_multi: policy and handle live on different devices");
+    const int B = h->p.B, N = h->p.N, O = h->p.obs_dim, Om = h->p.obs_dim_multi;
+    if (p->P.n_in != Om || p->P.n_out != 1)
+        return fail(WG_ERR_INVALID, "wg_rollout_multi: the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
+                                    ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) + " -> 1");
+    if (!h->d.multi_out)
+        return fail(WG_ERR_INVALID, "wg_rollout_multi: register a per-agent buffer first (wg_set_obs_multi_buffer); obs_multi[0] is what it held");
+    if (o->final_value && !o->final_obs_multi) return fail(WG_ERR_INVALID, "wg_rollout_multi: final_value needs final_obs_multi");
+    if ((o->value || o->final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, "wg_rollout_multi: value requested from a policy without a critic");
+    if (!p->P.has_log_std && (!deterministic || o->logp))
+        return fail(WG_ERR_INVALID, "wg_rollout_multi: a stochastic rollout / log-probabilities need a policy with log_std");
+    if (o->n_info < 0 || (o->n_info > 0 && (!o->info_fields || !o->info_out))) return fail(WG_ERR_INVALID, "wg_rollout_multi: bad info arguments");
+    for (int i = 0; i < o->n_info; ++i) {
+        if (o->info_fields[i] < 0 || o->info_fields[i] > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, "wg_rollout_multi: unknown info field");
+        if (!o->info_out[i]) return fail(WG_ERR_INVALID, "wg_rollout_multi: null info buffer");
+    }
+    if ((long long)B * N > 0x7fffffffLL) return fail(WG_ERR_UNSUPPORTED, "wg_rollout_multi: more than 2^31 agent rows");
+    if (int rc = use_device(h)) return rc;
+    // the step kernels always build the flat observation: without a caller's buffer it goes to a row block of the handle's own
+    // (allocated by the first call that needs it, before anything is enqueued)
+    if (!o->obs && !h->flat_scratch)
+        if (int rc = dev_alloc(h, &h->flat_scratch, (size_t)B * O, false)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int R = B * N;
+    const size_t sBO = (size_t)B * O, sR = (size_t)R, sRO = sR * Om;
+    float* const multi0 = h->d.multi_out;
+    float* const fin0 = h->d.multi_fin;
+    int rc = 0;
+    for (int t = 0; t < n_steps && !rc; ++t) {
+        // (V of step t-1's final rows rides along with step t's actions, as in wg_rollout)
+        const bool fv = o->final_value && t > 0;
+        rc = wg_policy_act2_(p, R, o->obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)N,
+                             o->actions + t * sR, o->raw ? o->raw + t * sR : nullptr, o->logp ? o->logp + t * sR : nullptr,
+                             o->value ? o->value + t * sR : nullptr, fv ? o->final_obs_multi + (t - 1) * sRO : nullptr,
+                             fv ? o->final_value + (t - 1) * sR : nullptr, stream);
+        if (rc) break;
+        h->d.multi_out = o->obs_multi + (t + 1) * sRO;
+        h->d.multi_fin = o->final_obs_multi ? o->final_obs_multi + t * sRO : nullptr;
+        const bool sample = h->timing && (h->timing_phase++ % h->timing_period == 0);
+        h->n_step_launches++;
+        launch_step(h, o->actions + t * sR, o->obs ? o->obs + (t + 1) * sBO : h->flat_scratch, o->reward + (size_t)t * B,
+                    o->truncated + (size_t)t * B, o->final_obs ? o->final_obs + t * sBO : nullptr, st, sample);
+        for (int i = 0; i < o->n_info; ++i)
+            wg_launch_info(&h->p, &h->d, o->info_fields[i], (char*)o->info_out[i] + (size_t)t * info_bytes(h, o->info_fields[i]), st);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) rc = fail(WG_ERR_HIP, std::string("wg_rollout_multi: kernel launch failed: ") + hipGetErrorString(le));
+    }
+    h->d.multi_out = multi0;      // the handle's own per-agent buffers again (the device copies never changed)
+    h->d.multi_fin = fin0;
+    if (rc) return rc;
+    if (o->final_value && n_steps > 0)
+        return wg_policy_act(p, R, o->final_obs_multi + (n_steps - 1) * sRO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
+                             o->final_value + (n_steps - 1) * sR, stream);
     return 0;
 }
 

@@ -338,6 +338,8 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
     WgEnv& env = d.env[e];
     float* obs = obs_out ? obs_out + (size_t)e * p.obs_dim : nullptr;
     float* om = MULTI ? d.multi_out + (size_t)e * N * p.obs_dim_multi : nullptr;
+    // (optional second per-agent buffer: the observation of the state this step ENDS in, WgPtrs::multi_fin)
+    float* omf = (MULTI && d.multi_fin) ? d.multi_fin + (size_t)e * N * p.obs_dim_multi : nullptr;
     float* fq = d.farm_pow + (size_t)e * PA;
     float* bq = d.base_pow + (size_t)e * PA;
     const int own = lane < N ? lane : 0;          // this lane's first entity (lanes >= N: a valid dummy)
@@ -551,16 +553,18 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
     }
     // observation (:983): the window sums of the lane's turbine advance by one sample (S += newest - leaving), then the
     // blocks; an env that truncates with same-step autoreset keeps it as final_obs only (and leaves the sums alone: the new
-    // episode's replace them)
+    // episode's replace them).  With a per-agent final buffer the finished episode's agent rows go there, the rows of every
+    // other env to both per-agent buffers; a truncating env without final_obs then builds into `obs`, which the swap rewrites.
     {
-        float* o1 = swap_obs ? fin : obs;
+        float* o1 = swap_obs ? ((MULTI && omf && !fin) ? obs : fin) : obs;
         if (o1) {
             auto get = [&](const int ent) {
                 if (have2 && ent == lane + WG_WAVE) return wg_sums_apply<GEN>(p, d, ctx_id, ent, raw2, !swap_obs);
                 return wg_sums_apply<GEN>(p, d, ctx_id, ent, wg_sums_load<GEN>(p, d, e, ctx_id, ent, np_step), !swap_obs);
             };
             const ObsIn oi = wg_sums_apply<GEN>(p, d, ctx_id, own, raw, lane < N && !swap_obs);
-            build_obs_sums<MULTI, GEN>(p, lane, o1, swap_obs ? nullptr : fin, swap_obs ? nullptr : om, np_step + 1, mscr, oi, get);
+            build_obs_sums<MULTI, GEN>(p, lane, o1, swap_obs ? nullptr : fin, swap_obs ? omf : om, np_step + 1, mscr, oi, get,
+                                       swap_obs ? nullptr : omf);
         }
     }
 #if defined(WG_TIMELINE) && defined(WG_STAMP2)

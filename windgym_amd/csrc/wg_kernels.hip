@@ -259,12 +259,31 @@ k_glue(const WgParams p, const WgPtrs d, const int phase, const uint8_t* __restr
     // and not kept: requesting the next context's header, deferred deque entries and rings with the first staging
     // (swap block 12.7 k -> 7.7 k cycles, but the common path slowed by as much as the tail gained); s_setprio(3) for
     // the truncating wave: no effect.)
-    if (!swap_obs || fin) {
-        stage_rings<RL>(p, d, ctx_id, lane, my_lds, rbase, fbase, n_pushed_live);
-        if (WG_GLUE_ABLATE == 3) return;
-        if (swap_obs) build_obs<L>(p, d, ctx_id, lane, fin, nullptr, rbase, fbase, false, nullptr, n_pushed_live);
-        else build_obs<L>(p, d, ctx_id, lane, obs, fin, rbase, fbase, false,
-                       MULTI ? d.multi_out + (size_t)e * N * p.obs_dim_multi : nullptr, n_pushed_live, mscr);
+    if constexpr (!MULTI) {
+        if (!swap_obs || fin) {
+            stage_rings<RL>(p, d, ctx_id, lane, my_lds, rbase, fbase, n_pushed_live);
+            if (WG_GLUE_ABLATE == 3) return;
+            if (swap_obs) build_obs<L>(p, d, ctx_id, lane, fin, nullptr, rbase, fbase, false, nullptr, n_pushed_live);
+            else build_obs<L>(p, d, ctx_id, lane, obs, fin, rbase, fbase, false, nullptr, n_pushed_live, mscr);
+        }
+    } else {
+        // Per-agent buffers: the observation of the state the step ends in goes to multi_out — or, for an env that truncates
+        // with same-step autoreset, to the per-agent FINAL buffer (WgPtrs::multi_fin, optional) only: multi_out gets the next
+        // episode's rows below.  Such an env without final_obs builds into `obs`, which the swap rewrites.  The rows of every
+        // other env are copied to the final buffer once they are written (one builder, one more trip for those waves only
+        // when the buffer is registered; a second store target inside build_obs put every instantiation into scratch).
+        float* const om = d.multi_out + (size_t)e * N * p.obs_dim_multi;
+        float* const mfin = d.multi_fin ? d.multi_fin + (size_t)e * N * p.obs_dim_multi : nullptr;
+        float* const o1 = swap_obs ? (fin ? fin : (mfin ? obs : nullptr)) : obs;
+        if (o1) {
+            stage_rings<RL>(p, d, ctx_id, lane, my_lds, rbase, fbase, n_pushed_live);
+            if (WG_GLUE_ABLATE == 3) return;
+            build_obs<L>(p, d, ctx_id, lane, o1, swap_obs ? nullptr : fin, rbase, fbase, false, swap_obs ? mfin : om, n_pushed_live, mscr);
+            if (mfin && !swap_obs) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's own rows have landed
+                for (int i = lane; i < N * p.obs_dim_multi; i += WG_WAVE) mfin[i] = om[i];
+            }
+        }
     }
     if (WG_GLUE_ABLATE == 4) return;
     WG_GSTAMP(2);

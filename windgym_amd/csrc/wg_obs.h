@@ -310,14 +310,16 @@ __device__ __forceinline__ float wg_sums_ti(const OC& oc, const double S1, const
 }
 // One turbine's block of the observation (turb_mes.get_measurements(scaled=True) + clip, MesClass.py:328-340) from its
 // window sums S[WG_N_SUMS] and newest samples cur[WG_N_CH].
-// o / o2 / om: the block's place in obs, (optional) final_obs and (optional) the agent's row of the per-agent buffer.
+// o / o2 / om / om2: the block's place in obs, (optional) final_obs and (optional) the agent's row of the per-agent buffer
+// and of the per-agent final buffer.
 // GEN = false: instantiation for configurations without TI entries (the common case: no double-precision sqrt / division
 // in the kernel at all).
 template <bool GEN, typename OC>
 __device__ __forceinline__ int wg_obs_turbine(const OC& oc, const double* S, const float* cur, const int n_pushed,
-                                              float* __restrict__ o, float* __restrict__ o2, float* __restrict__ om) {
+                                              float* __restrict__ o, float* __restrict__ o2, float* __restrict__ om,
+                                              float* __restrict__ om2 = nullptr) {
     int n = 0;
-#define WG_EMIT(v_) do { const float _v = (v_); o[n] = _v; if (o2) o2[n] = _v; if (om) om[n] = _v; ++n; } while (0)
+#define WG_EMIT(v_) do { const float _v = (v_); o[n] = _v; if (o2) o2[n] = _v; if (om) om[n] = _v; if (om2) om2[n] = _v; ++n; } while (0)
 #pragma unroll
     for (int ch = 0; ch < WG_N_CH; ++ch) {
         if (GEN && ch == WG_CH_POWER && oc.turb_ti)
@@ -332,11 +334,12 @@ __device__ __forceinline__ int wg_obs_turbine(const OC& oc, const double* S, con
 
 // The whole observation from the sums.  `first`: the sums of entity `lane` (ignored for lanes >= N); get(ent): those of any
 // other entity — turbines beyond the 64th, the farm-level deques (step: update + store, swap / reset: summed afresh).
-// n_pushed: samples in the deques.
+// n_pushed: samples in the deques.  obs_m2 (MULTI, only with obs_m): receives the rows obs_m receives (WgPtrs::multi_fin).
 // GEN = false: nothing farm-level and no TI in the observation (wg_launch_glue decides) — the turbine blocks are all of it.
 template <bool MULTI, bool GEN, typename Get>
 __device__ inline void build_obs_sums(const WgParams& p, const int lane, float* __restrict__ obs, float* __restrict__ obs2,
-                                      float* __restrict__ obs_m, const int n_pushed, float* mscratch, const ObsIn& first, Get get) {
+                                      float* __restrict__ obs_m, const int n_pushed, float* mscratch, const ObsIn& first, Get get,
+                                      float* __restrict__ obs_m2 = nullptr) {
     const int N = p.N;
     float ti_sum = 0.f;
     int n_turb_vals = 0;
@@ -344,7 +347,8 @@ __device__ inline void build_obs_sums(const WgParams& p, const int lane, float* 
         const ObsIn oi = t == lane ? first : get(t);
         n_turb_vals = wg_obs_turbine<GEN>(p.oc, oi.S, oi.cur, n_pushed, obs + (size_t)t * p.turb_obs,
                                           obs2 ? obs2 + (size_t)t * p.turb_obs : nullptr,
-                                          (MULTI && obs_m) ? obs_m + (size_t)t * p.obs_dim_multi : nullptr);
+                                          (MULTI && obs_m) ? obs_m + (size_t)t * p.obs_dim_multi : nullptr,
+                                          (MULTI && obs_m2) ? obs_m2 + (size_t)t * p.obs_dim_multi : nullptr);
         // farm TI = mean of the *scaled* (unclipped) turbine TIs (MesClass.py:670-673)
         if (GEN && p.farm_ti) ti_sum += 2.0f * (wg_sums_ti(p.oc, oi.S[WG_SUM_TI1], oi.S[WG_SUM_TI2], n_pushed) - p.oc.ti_mn) * p.oc.inv_ti_rng - 1.0f;
     }
@@ -376,6 +380,7 @@ __device__ inline void build_obs_sums(const WgParams& p, const int lane, float* 
         for (int i = lane; i < N * m; i += WG_WAVE) {
             const int t = i / m, k = i - t * m;
             obs_m[(size_t)t * p.obs_dim_multi + nt + k] = mscratch[k];
+            if (obs_m2) obs_m2[(size_t)t * p.obs_dim_multi + nt + k] = mscratch[k];
         }
     }
     if (lane == 0 && p.farm_obs > 0) {

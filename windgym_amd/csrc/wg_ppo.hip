@@ -50,6 +50,27 @@ __global__ void k_gae(const int T, const int B, const float* __restrict__ reward
     }
 }
 
+// The same recurrence per AGENT row of a [T, B, A] rollout whose reward and truncation flag belong to the env (a farm's
+// turbines share the farm reward): one thread per (env, agent) — consecutive threads walk consecutive agent rows, the two
+// [B] arrays are read once per thread (the A threads of an env fetch the same word: one transaction).  A = 1 is k_gae.
+__global__ void k_gae_shared(const int T, const int B, const int A, const float* __restrict__ reward, const float* __restrict__ value,
+                             const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const float gamma,
+                             const float lambda, float* __restrict__ adv, float* __restrict__ ret) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int R = B * A;
+    if (r >= R) return;
+    const int b = r / A;
+    float a = 0.0f;
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t o = (size_t)t * R + r, e = (size_t)t * B + b;
+        const float v = value[o];
+        const float delta = reward[e] + gamma * final_value[o] - v;
+        a = delta + gamma * lambda * (truncated[e] ? 0.0f : 1.0f) * a;
+        adv[o] = a;
+        ret[o] = a + v;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // fixed-order block reductions (tree over threadIdx, the same shape on every device)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -446,6 +467,20 @@ extern "C" int wg_gae(int T, int B, const float* reward_dev, const float* value_
         return tfail(WG_ERR_INVALID, "wg_gae: null argument");
     if (T < 1 || B < 1) return tfail(WG_ERR_INVALID, "wg_gae: T and B must be >= 1");
     hipLaunchKernelGGL(k_gae, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, reward_dev, value_dev,
+                       final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_gae_shared(int T, int B, int A, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+                             const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out,
+                             void* stream) {
+    if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !advantage_out || !returns_out)
+        return tfail(WG_ERR_INVALID, "wg_gae_shared: null argument");
+    if (T < 1 || B < 1 || A < 1) return tfail(WG_ERR_INVALID, "wg_gae_shared: T, B and A must be >= 1");
+    if ((long long)B * A > 0x7fffffffLL - 256) return tfail(WG_ERR_UNSUPPORTED, "wg_gae_shared: more than 2^31 agent rows");
+    const int R = B * A;
+    hipLaunchKernelGGL(k_gae_shared, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, A, reward_dev, value_dev,
                        final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
     THIPCHK(hipGetLastError());
     return 0;

@@ -216,4 +216,8 @@ struct WgPtrs {
     const float* box;
     // replay
     const float *script_uvw, *script_power;
+    // optional [B][N][obs_dim_multi] (needs multi_out): per-agent observations of the state the step ENDED in — a truncating
+    // env's finished episode, every other env's multi_out rows (wg_set_final_obs_multi_buffer).  Last member: the layout of
+    // everything above is the one handles without it have always had.
+    float* multi_fin;
 };

@@ -1019,6 +1019,170 @@ class WindFarmEnvMulti(_ParallelEnvBase):
         self._env.close()
 
 
+class WindFarmVecEnvMulti:
+    """The batched counterpart of :class:`WindFarmEnvMulti`: ``n_envs`` farms, one agent per turbine, on CUDA tensors.
+
+    Agent ``i`` of env ``e`` sees its own turbine block followed by the agents' farm block (``obs_len`` values, the layout of
+    ``WindFarmEnvMulti``), sends ONE yaw action, and shares the farm's reward and truncation flag with the other agents of
+    its env.  Built by composition over a :class:`WindFarmVecEnv` (``.venv``; same keyword arguments, ``as_torch`` is always
+    on, ``extra_timestep_inc`` defaults to the multi-agent facade's double time step, WindEnvMulti.py:219).  No dict I/O: the
+    agent axis is a tensor axis, ``possible_agents[i]`` names row ``i``.
+
+    ``reset(seed=...) -> obs [B, N, obs_len]``;
+    ``step(actions [B, N] or [B, N, 1]) -> (obs [B, N, obs_len], reward [B], terminated [B], truncated [B], final_obs [B, N, obs_len])``
+    where ``final_obs`` is every agent's observation of the state the step ended in: for an env that truncated (and was reset
+    in the same step) the finished episode's, for every other env equal to ``obs``.  The returned tensors are persistent
+    and rewritten by the next call.  ``rollout(policy, T)`` runs the closed loop of ONE policy shared by the turbines
+    (``obs_len -> 1``) inside the library (wg_rollout_multi)."""
+
+    metadata = {"name": "MultiFarm_vec_environment_v0"}
+
+    def __init__(self, turbine, n_envs: int, yaml_path=None, **kwargs):
+        if int(n_envs) < 1:
+            raise ValueError("WindFarmVecEnvMulti: n_envs must be >= 1")
+        if not kwargs.pop("as_torch", True):
+            raise ValueError("WindFarmVecEnvMulti works on CUDA tensors only (as_torch=False is not supported)")
+        kwargs.setdefault("extra_timestep_inc", True)
+        self.venv = WindFarmVecEnv(turbine, int(n_envs), yaml_path, as_torch=True, **kwargs)
+        b = self.batch = self.venv.batch
+        self.torch, self.cfg = b.torch, self.venv.cfg
+        self.num_envs = self.n_envs = self.venv.num_envs
+        self.n_turb, self.act_var = self.venv.n_turb, 1
+        self.obs_var = self.cfg.multi_declared_obs_var()        # as the reference declares it (WindEnvMulti.py:65-69)
+        self.obs_len = b.obs_dim_multi                          # as produced (:79-103)
+        self.possible_agents = ["turbine_" + str(r) for r in range(self.n_turb)]
+        self.agent_name_mapping = dict(zip(self.possible_agents, range(self.n_turb)))
+        self._obs = b.fuse_obs_multi()
+        self._final_obs = b.fuse_final_obs_multi()
+        self._term = self.torch.zeros((self.num_envs,), dtype=self.torch.bool, device=b.device)
+
+    # (the counters the single-agent rollout keeps on its env live on the wrapped env: PPO.save / load find them there)
+    @property
+    def _policy_steps(self):
+        return getattr(self.venv, "_policy_steps", 0)
+
+    @_policy_steps.setter
+    def _policy_steps(self, v):
+        self.venv._policy_steps = int(v)
+
+    @property
+    def _global_offset(self):
+        return self.venv._global_offset
+
+    def observation_space(self, agent=None):
+        return Box(low=-1.0, high=1.0, shape=(self.obs_len,), dtype=np.float32)
+
+    def action_space(self, agent=None):
+        return Box(low=-1.0, high=1.0, shape=(self.act_var,), dtype=np.float32)
+
+    def shard(self, rank: int, world: int, n_envs_total: Optional[int] = None):
+        self.venv.shard(rank, world, n_envs_total)
+        return self
+
+    def reset(self, *, seed=None, options=None, mask=None):
+        self.venv.reset(seed=seed, options=options, mask=mask)      # (wg_reset writes the per-agent buffer too)
+        return self._obs
+
+    def step(self, actions):
+        t, B, N = self.torch, self.num_envs, self.n_turb
+        if isinstance(actions, t.Tensor):
+            if actions.numel() != B * N:
+                raise ValueError(f"step(): actions must be [{B}, {N}] or [{B}, {N}, 1]")
+            actions = actions.reshape(B, N)
+        else:
+            actions = np.asarray(actions, dtype=np.float32)
+            if actions.size != B * N:
+                raise ValueError(f"step(): actions must be [{B}, {N}] or [{B}, {N}, 1]")
+            actions = actions.reshape(B, N)
+        _, rew, trunc, _ = self.venv._step_device(actions)
+        return self._obs, rew, self._term, trunc.view(t.bool), self._final_obs
+
+    def rollout(self, policy, n_steps, *, deterministic=False, record=(), values=True):
+        """``n_steps`` closed-loop steps of ONE policy shared by the turbines, enqueued by one library call
+        (wg_rollout_multi).  Returns a dict of CUDA tensors, T = n_steps, Om = ``obs_len``: ``obs [T+1, B, N, Om]`` (``obs[0]``
+        = the current per-agent observation), ``actions`` / ``raw`` / ``logp`` / ``value`` / ``final_value [T, B, N]``,
+        ``final_obs [T, B, N, Om]``, ``reward`` / ``truncated [T, B]`` (shared by an env's agents), the flat single-agent
+        ``flat_obs [T+1, B, O]`` / ``flat_final_obs [T, B, O]`` (slot 0 of ``flat_obs`` = the batch's current one) and one
+        ``[T, ...]`` entry per name in ``record``.  Buffer reuse, the persistent outputs afterwards, the noise counter and the
+        ``sample_site`` fallback loop are those of :meth:`WindFarmVecEnv.rollout`; the noise row of agent i of env e is
+        ``(first global env of this shard + e) * N + i``.  Advantages: ``delta = r[t, e] + gamma * final_value[t, e, i] -
+        value[t, e, i]`` per agent row (wg_gae_shared)."""
+        import ctypes as C
+        from .binding import CRolloutMultiBufs, _chk
+        from .config import INFO
+        t, b, v = self.torch, self.batch, self.venv
+        T, B, N, O, Om = int(n_steps), self.num_envs, self.n_turb, b.obs_dim, self.obs_len
+        if T < 1:
+            raise ValueError("rollout(): n_steps must be >= 1")
+        if policy.n_in != Om or policy.n_out != 1:
+            raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, a policy shared by the turbines of "
+                             f"this env maps {Om} -> 1")
+        record = tuple(record)
+        for name in record:
+            if name not in INFO:
+                raise ValueError(f"rollout(): unknown info field {name!r}")
+        values = bool(values) and policy.has_critic
+        stochastic_ok = policy.desc["has_log_std"]
+        key = (T, record, values, stochastic_ok)
+        cache = self.__dict__.setdefault("_rollout_bufs", {})
+        bufs = cache.get(key)
+        if bufs is None:
+            f32 = dict(dtype=t.float32, device=b.device)
+            bufs = dict(obs=t.zeros((T + 1, B, N, Om), **f32), actions=t.zeros((T, B, N), **f32), raw=t.zeros((T, B, N), **f32),
+                        reward=t.zeros((T, B), **f32), truncated=t.zeros((T, B), dtype=t.uint8, device=b.device),
+                        final_obs=t.zeros((T, B, N, Om), **f32), flat_obs=t.zeros((T + 1, B, O), **f32),
+                        flat_final_obs=t.zeros((T, B, O), **f32))
+            if stochastic_ok:
+                bufs["logp"] = t.zeros((T, B, N), **f32)
+            if values:
+                bufs["value"], bufs["final_value"] = t.zeros((T, B, N), **f32), t.zeros((T, B, N), **f32)
+            for name in record:
+                shape, dtype = b.info_shape(name)
+                bufs[name] = t.zeros((T,) + tuple(shape), dtype=dtype, device=b.device)
+            cache[key] = bufs
+        bufs["obs"][0].copy_(self._obs)
+        bufs["flat_obs"][0].copy_(b.obs)
+        seed = 0 if v._base_seed is None else int(v._base_seed)
+        counter0 = self._policy_steps
+        self._policy_steps = counter0 + T
+        if v._site is not None:
+            for i in range(T):
+                policy.act(bufs["obs"][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
+                           row_offset=self._global_offset * N, value=values,
+                           out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
+                                bufs["value"][i] if values else None))
+                o, r, tr, f = v._step_device(bufs["actions"][i])
+                bufs["obs"][i + 1].copy_(self._obs); bufs["final_obs"][i].copy_(self._final_obs)
+                bufs["flat_obs"][i + 1].copy_(o); bufs["reward"][i].copy_(r); bufs["truncated"][i].copy_(tr)
+                bufs["flat_final_obs"][i].copy_(f)
+                for name in record:
+                    b.info(name, out=bufs[name][i])
+                if values:
+                    policy.value(bufs["final_obs"][i], out=bufs["final_value"][i])
+            return dict(bufs)
+        ptr = lambda k: bufs[k].data_ptr() if k in bufs else None          # noqa: E731
+        cb = CRolloutMultiBufs(ptr("obs"), ptr("actions"), ptr("raw"), ptr("logp"), ptr("value"), ptr("final_obs"),
+                               ptr("final_value"), ptr("reward"), ptr("truncated"), ptr("flat_obs"), ptr("flat_final_obs"),
+                               len(record), (C.c_int32 * max(1, len(record)))(*[INFO[n] for n in record]),
+                               (C.c_void_p * max(1, len(record)))(*[bufs[n].data_ptr() for n in record]))
+        _chk(b.L.wg_rollout_multi(b._h, policy._h, T, int(bool(deterministic)), seed, counter0, self._global_offset,
+                                  C.byref(cb), b._stream()), "wg_rollout_multi")
+        # the persistent outputs follow, as after a step()
+        self._obs.copy_(bufs["obs"][T]); self._final_obs.copy_(bufs["final_obs"][T - 1])
+        b.obs.copy_(bufs["flat_obs"][T]); b.reward.copy_(bufs["reward"][T - 1]); b.truncated.copy_(bufs["truncated"][T - 1])
+        b.final_obs.copy_(bufs["flat_final_obs"][T - 1])
+        return dict(bufs)
+
+    def infos(self, step=False):
+        return self.venv.infos(step=step)
+
+    def metrics(self, reset_after=True):
+        return self.venv.metrics(reset_after=reset_after)
+
+    def close(self):
+        self.venv.close()
+
+
 # ======================================================================================================
 class RecordEpisodeVals:
     """Episode statistics of a :class:`WindFarmVecEnv` (wrappers/recordEpisodeVals.py:8-64): per-env running

@@ -93,6 +93,22 @@ class PPOOptimizer:
                                 float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(), self.policy._stream()), "wg_gae")
         return adv, ret
 
+    def gae_shared(self, reward, value, final_value, truncated, gamma, gae_lambda, out=None):
+        """wg_gae_shared: ``value`` / ``final_value [T, B, A]`` per agent row, ``reward`` / ``truncated [T, B]`` shared by an
+        env's agents -> (advantage, returns) ``[T, B, A]``."""
+        t = self.torch
+        if value.ndim != 3:
+            raise ValueError("value must be [T, B, A]")
+        T, B, A = value.shape
+        self._f32(reward, (T, B), "reward"); self._f32(value, (T, B, A), "value"); self._f32(final_value, (T, B, A), "final_value")
+        if not (truncated.is_cuda and truncated.dtype == t.uint8 and truncated.is_contiguous() and tuple(truncated.shape) == (T, B)):
+            raise ValueError("truncated must be a contiguous uint8 CUDA tensor [T, B]")
+        adv, ret = out if out is not None else (t.empty_like(value), t.empty_like(value))
+        self._chk(self.L.wg_gae_shared(T, B, A, reward.data_ptr(), value.data_ptr(), final_value.data_ptr(), truncated.data_ptr(),
+                                       float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(), self.policy._stream()),
+                  "wg_gae_shared")
+        return adv, ret
+
     def _batch(self, obs, raw, logp, advantage, returns):
         from .binding import CPpoBatch
         p = self.policy
@@ -172,7 +188,11 @@ def _schedule(x, name):
 
 
 class PPO:
-    """Proximal policy optimisation with stable-baselines3's argument names and defaults, on a ``WindFarmVecEnv``.
+    """Proximal policy optimisation with stable-baselines3's argument names and defaults, on a ``WindFarmVecEnv``, or on a
+    ``WindFarmVecEnvMulti`` with ONE policy shared by the turbines (``obs_len -> 1``): there a row is an AGENT row — ``n_rows``
+    = ``n_steps * num_envs * n_turb``, the ``batch_size`` default and the permutations are in agent rows, advantages come
+    from wg_gae_shared (the farm reward is every agent's reward, each agent's critic sees its own observation: independent PPO
+    with shared parameters) — while ``num_timesteps``, ``fps`` and the episode means stay in env steps.
 
     Two defaults differ from SB3's, which sized them for a handful of host envs: ``n_steps`` = 128 (SB3: 2048) steps of EVERY env
     of the batch per rollout, and ``batch_size`` = a quarter of the rollout (SB3: 64 rows).  ``policy`` is an
@@ -200,10 +220,12 @@ class PPO:
             raise ValueError("gamma and gae_lambda must lie in [0, 1]")
         if not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be > 0")
-        n_rows = n_steps * int(venv.num_envs)
+        multi = getattr(venv, "possible_agents", None) is not None       # WindFarmVecEnvMulti: one row per (env, turbine)
+        n_agents = int(venv.n_turb) if multi else 1
+        n_rows = n_steps * int(venv.num_envs) * n_agents
         batch_size = max(1, n_rows // 4) if batch_size is None else int(batch_size)
         if not 1 <= batch_size <= n_rows:
-            raise ValueError(f"batch_size must lie in [1, n_steps * num_envs = {n_rows}]")
+            raise ValueError(f"batch_size must lie in [1, n_steps * num_envs{' * n_turb' if multi else ''} = {n_rows}]")
         self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
         if isinstance(policy, str):
             if policy != "MlpPolicy":
@@ -211,10 +233,14 @@ class PPO:
             policy = self._build_policy(venv, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
         elif policy_kwargs:
             raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
-        if policy.n_in != venv.batch.obs_dim or policy.n_out != venv.n_turb:
-            raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, the env needs {venv.batch.obs_dim} -> {venv.n_turb}")
+        want = (int(venv.obs_len), 1) if multi else (int(venv.batch.obs_dim), int(venv.n_turb))
+        if (policy.n_in, policy.n_out) != want:
+            raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, this env needs {want[0]} -> {want[1]} "
+                             "(accepted shapes: obs_dim -> n_turb on a WindFarmVecEnv, obs_len -> 1 — one policy shared by the "
+                             "turbines — on a WindFarmVecEnvMulti)")
         self.policy, self.venv, self.torch = policy, venv, policy.torch
         self.n_steps, self.batch_size, self.n_epochs, self.n_rows = n_steps, batch_size, n_epochs, n_rows
+        self.multi, self.n_agents, self.n_env_steps = multi, n_agents, n_steps * int(venv.num_envs)
         self.gamma, self.gae_lambda, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(ent_coef), float(vf_coef)
         self.max_grad_norm, self.normalize_advantage = float(max_grad_norm), bool(normalize_advantage)
         self.learning_rate, self.clip_range = learning_rate, clip_range
@@ -224,7 +250,7 @@ class PPO:
         self._gen = t.Generator(device=policy.device)
         self._gen.manual_seed(0 if seed is None else int(seed))
         self._perm = t.zeros((n_epochs, n_rows), dtype=t.int32, device=policy.device)
-        self._adv = t.zeros((n_steps, venv.num_envs), dtype=t.float32, device=policy.device)
+        self._adv = t.zeros((n_steps, venv.num_envs) + ((n_agents,) if multi else ()), dtype=t.float32, device=policy.device)
         self._ret = t.zeros_like(self._adv)
         self._stats = t.zeros((n_epochs, -(-n_rows // batch_size), 8), dtype=t.float32, device=policy.device)
         self.num_timesteps, self.iteration, self.log = 0, 0, []
@@ -236,16 +262,18 @@ class PPO:
         if kw:
             raise ValueError(f"unknown policy_kwargs: {sorted(kw)}")
         pi, vf = (arch["pi"], arch["vf"]) if isinstance(arch, dict) else (arch, arch)
-        p = MlpPolicy(venv.batch.obs_dim, venv.n_turb, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed)
+        n_in, n_out = (venv.obs_len, 1) if getattr(venv, "possible_agents", None) is not None else (venv.batch.obs_dim, venv.n_turb)
+        p = MlpPolicy(n_in, n_out, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed)
         p.load_state_dict(sb3_orthogonal_init(p.desc, seed))
         return p
 
     # -- training -------------------------------------------------------------------------------------------------
     def collect(self):
-        """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added."""
+        """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added
+        (``[T, B, N]`` from wg_gae_shared on a ``WindFarmVecEnvMulti``)."""
         out = self.venv.rollout(self.policy, self.n_steps)
-        self.opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda,
-                     out=(self._adv, self._ret))
+        gae = self.opt.gae_shared if self.multi else self.opt.gae
+        gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda, out=(self._adv, self._ret))
         out["advantage"], out["returns"] = self._adv, self._ret
         return out
 
@@ -276,7 +304,7 @@ class PPO:
             lr, clip = float(self._lr(progress)), float(self._clip(progress))
             out = self.collect()
             stats = self.train(out, lr, clip)
-            self.num_timesteps += self.n_rows
+            self.num_timesteps += self.n_env_steps
             self.iteration += 1
             if log_interval and self.iteration % int(log_interval) == 0:
                 ret, val = self._ret.double(), out["value"].double()
