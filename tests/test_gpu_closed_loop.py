@@ -24,9 +24,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from loop_twin import rollout_equals_the_loop
 from oracle import policy_oracle as po
 from oracle import ppo_oracle as oo
-from test_gpu_policy import make, rollout_equals_the_loop
+from test_gpu_policy import make
 from test_gpu_spotcheck import (N_SAMPLE, OBS_ATOL, TURB_OBS_ATOL, TURB_POW_ATOL, TURB_POW_RTOL, TURB_REW_ATOL, TURB_REW_RTOL,
                                 TURB_UVW_ATOL, TURB_UVW_RTOL)
 
@@ -294,7 +295,7 @@ def test_rollouts_interleaved_with_steps_equal_the_loop():
                    (40, ())):
         counter0 = va.__dict__.get("_policy_steps", 0)
         assert counter0 == vb.__dict__.get("_policy_steps", 0)
-        out, _ = rollout_equals_the_loop(va, vb, policy, T, rec, min_trunc=0)          # (ends with one step() on both)
+        out = rollout_equals_the_loop(va, vb, policy, T, rec, min_trunc=0)          # (ends with one step() on both)
         assert va._policy_steps == counter0 + T
         raws.append((out["raw"] - policy.torch_forward(out["obs"][:T])[0].detach()).clone())
     assert not t.equal(raws[0], raws[2]) and not t.equal(raws[2], raws[3])            # no noise is reused

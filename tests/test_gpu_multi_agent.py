@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+from loop_twin import rollout_equals_the_loop
 from multi_agent_ref import gae_shared
 from oracle import policy_oracle as po
 from test_gpu_closed_loop import (LOGP_ATOL, RAW_ATOL, SMALL_BOX, SMALL_BOX_SPACING, VAL_ATOL, VAL_RTOL, _ti_farm_history_100, plan_of,  # noqa: F401
@@ -162,58 +163,6 @@ def test_null_final_pointer_is_the_parent_bit_for_bit(name, small_box):       # 
         h.check(); h.close()
 
 
-def _loop_twin(vb, p, T, rec, counter0):
-    """The documented loop of wg_rollout_multi from Python on the twin env: dict of stacked recordings."""
-    t = _torch()
-    B, N = vb.num_envs, vb.n_turb
-    seed, row0 = int(vb.venv._base_seed), vb._global_offset
-    keys = ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward", "truncated", "flat_obs", "flat_final_obs") + tuple(rec)
-    out = {k: [] for k in keys}
-    out["obs"].append(vb._obs.clone()); out["flat_obs"].append(vb.batch.obs.clone())
-    for i in range(T):
-        a, raw, logp, v = p.act(out["obs"][-1], counter=counter0 + i, seed=seed, row_offset=row0 * N)
-        a = a.reshape(B, N).clone()
-        out["actions"].append(a); out["raw"].append(raw.reshape(B, N).clone()); out["logp"].append(logp.reshape(B, N).clone())
-        out["value"].append(v.reshape(B, N).clone())
-        o, r, _, tr, f = vb.step(a)
-        out["obs"].append(o.clone()); out["final_obs"].append(f.clone()); out["reward"].append(r.clone())
-        out["truncated"].append(vb.batch.truncated.clone())
-        out["flat_obs"].append(vb.batch.obs.clone()); out["flat_final_obs"].append(vb.batch.final_obs.clone())
-        for name in rec:
-            out[name].append(vb.batch.info(name))
-        out["final_value"].append(p.value(f).reshape(B, N).clone())
-    vb._policy_steps = counter0 + T
-    return {k: t.stack(v) for k, v in out.items()}
-
-
-def _rollout_multi_equals_the_loop(va, vb, p, T, rec=("power_agent", "yaw_agent"), min_trunc=None):
-    t = _torch()
-    B, N = va.num_envs, va.n_turb
-    counter0 = vb._policy_steps
-    assert va._policy_steps == counter0
-    out = va.rollout(p, T, record=rec)
-    ref = _loop_twin(vb, p, T, rec, counter0)
-    assert set(out) == set(ref)
-    for k in ref:
-        assert out[k].shape == ref[k].shape and t.equal(out[k], ref[k]), k
-    n_trunc = int(out["truncated"].sum())
-    assert n_trunc >= (B if min_trunc is None else min_trunc), n_trunc
-    tr = out["truncated"].bool()
-    assert t.equal(out["final_obs"][~tr], out["obs"][1:][~tr])
-    assert not tr.any() or not t.equal(out["final_obs"][tr], out["obs"][1:][tr])
-    va.batch.check(); vb.batch.check()
-    assert va.batch.get_state() == vb.batch.get_state()
-    assert va._policy_steps == counter0 + T
-    # the persistent outputs follow, and a step() continues from obs[T]
-    assert t.equal(va._obs, out["obs"][T]) and t.equal(va._final_obs, out["final_obs"][T - 1]) and t.equal(va.batch.obs, out["flat_obs"][T])
-    res = {k: v.clone() for k, v in out.items()}
-    act = t.zeros((B, N), device="cuda")
-    sa, sb = va.step(act), vb.step(act)
-    for x, y in zip(sa, sb):
-        assert t.equal(x, y)
-    return res
-
-
 @pytest.mark.parametrize("B", [2048, 389, 64])
 def test_rollout_multi_equals_its_loop_and_the_policy_oracle(B, plan_of):     # noqa: F811
     t = _torch()
@@ -224,7 +173,7 @@ def test_rollout_multi_equals_its_loop_and_the_policy_oracle(B, plan_of):     # 
     va.reset(seed=seed); vb.reset(seed=seed)
     N, Om = va.n_turb, va.obs_len
     p, sd = make(Om, (64, 64), 1, hidden_vf=(32, 32))
-    out = _rollout_multi_equals_the_loop(va, vb, p, T, min_trunc=B // 2)
+    out = rollout_equals_the_loop(va, vb, p, T, min_trunc=B // 2)
     # 16 sampled envs (all their agents) against the float64 policy oracle: noise row of agent i of env e = e * N + i
     idx = np.linspace(0, B - 1, 16).round().astype(int)
     it = t.as_tensor(idx, device="cuda")
@@ -310,7 +259,7 @@ def test_shard_invariance_and_interleaving_with_step(small_box):             # n
     va.reset(seed=5); vb.reset(seed=5)
     q, _ = make(va.obs_len, (64, 64), 1)
     for Ti, rec in ((40, ("power_agent",)), (25, ("timestep", "wind_f64")), (40, ("power_agent",)), (40, ())):
-        _rollout_multi_equals_the_loop(va, vb, q, Ti, rec, min_trunc=0)
+        rollout_equals_the_loop(va, vb, q, Ti, rec, min_trunc=0)
     assert int(va.batch.info("episode").sum()) >= 48
     va.close(); vb.close(); p.close(); q.close()
 

@@ -7,6 +7,7 @@ import sys
 import numpy as np
 import pytest
 
+from loop_twin import rollout_equals_the_loop
 from oracle import policy_oracle as po
 
 pytestmark = pytest.mark.gpu
@@ -163,52 +164,13 @@ def _venv(n_envs=64, **kw):
     return v
 
 
-def rollout_equals_the_loop(va, vb, p, T, rec=("power_agent", "yaw_agent"), out=None, min_trunc=None):
-    """va.rollout(p, T) == the Python loop of act + step on the twin vb, bit for bit: every buffer, the handle's state, the step
-    after it.  ``out``: va's rollout when the caller has already run it (va and vb were in the same state before it);
-    ``min_trunc``: truncations the T steps must contain (default: one per env).  Shared with tests/test_gpu_closed_loop.py, which
-    runs it on every step path."""
-    t = _torch()
-    O, N, B = va.batch.obs_dim, va.n_turb, va.num_envs
-    seed, row0, counter0 = int(va._base_seed), va._global_offset, getattr(vb, "_policy_steps", 0)
-    if out is None:
-        out = va.rollout(p, T, record=rec)
-    obs = vb.batch.obs.clone()
-    assert t.equal(out["obs"][0], obs)
-    n_trunc = 0
-    for i in range(T):
-        a, raw, logp, v = p.act(obs, counter=counter0 + i, seed=seed, row_offset=row0)
-        assert t.equal(out["actions"][i], a) and t.equal(out["raw"][i], raw) and t.equal(out["logp"][i], logp) and t.equal(out["value"][i], v), i
-        o, r, tr, f = vb.batch.step(a)
-        assert t.equal(out["obs"][i + 1], o) and t.equal(out["reward"][i], r) and t.equal(out["truncated"][i], tr) and t.equal(out["final_obs"][i], f), i
-        for name in rec:
-            assert t.equal(out[name][i], vb.batch.info(name)), (name, i)
-        assert t.equal(out["final_value"][i], p.value(f)), i
-        n_trunc += int(tr.sum())
-        obs = o.clone()
-    vb._policy_steps = counter0 + T
-    assert n_trunc >= (B if min_trunc is None else min_trunc), n_trunc      # default: every env truncated and was swapped at least once
-    va.batch.check(); vb.batch.check()
-    assert va.batch.get_state() == vb.batch.get_state()
-    tr = out["truncated"][:-1].bool()
-    assert t.equal(out["final_value"][:-1][~tr], out["value"][1:][~tr])
-    assert not tr.any() or not t.equal(out["final_value"][:-1][tr], out["value"][1:][tr])
-    # a step() after a rollout() continues from obs[T]
-    assert t.equal(va.batch.obs, out["obs"][T])
-    first = (out["obs"][0].clone(), out["raw"][0].clone())                 # (the buffers are reused by the next rollout)
-    act = t.zeros((B, N), device="cuda")
-    oa = va.step(act)[0].clone()
-    ob = vb.step(act)[0]
-    assert t.equal(oa, ob)
-    return out, first
-
-
 def test_rollout_equals_the_loop():
     t = _torch()
     va, vb = _venv(), _venv()
     O, N, T = va.batch.obs_dim, va.n_turb, 300
     p, _ = make(O, (64, 64), N)
-    out, (obs0, raw0) = rollout_equals_the_loop(va, vb, p, T)
+    out = rollout_equals_the_loop(va, vb, p, T)
+    obs0, raw0 = out["obs"][0].clone(), out["raw"][0].clone()              # (the buffers are reused by the next rollout)
     # the next rollout draws fresh noise
     out2 = va.rollout(p, 2)
     assert not t.equal(out2["raw"][0] - p.torch_forward(out2["obs"][0])[0].detach(), raw0 - p.torch_forward(obs0)[0].detach())

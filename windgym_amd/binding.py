@@ -258,6 +258,26 @@ class HipBatch:
             _chk(rc, "wg_step")
         return self.obs, self.reward, self.truncated, self.final_obs
 
+    def _rollout(self, entry, cls, keys, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
+        """The closed loop ``entry`` (wg_rollout / wg_rollout_multi) into contiguous CUDA tensors: ``bufs[k]`` for the pointer
+        fields of ``cls`` in order (``keys``; a missing one is NULL = not wanted), ``bufs[name]`` for every info name in
+        ``record``."""
+        n = len(record)
+        cb = cls(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n,
+                 (C.c_int32 * max(1, n))(*[INFO[r] for r in record]), (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))
+        _chk(getattr(self.L, entry)(self._h, policy._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
+                                    C.byref(cb), self._stream()), entry)
+
+    def rollout(self, *args):
+        """wg_rollout(policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset); ``bufs`` keyed by wg_rollout_bufs' fields."""
+        self._rollout("wg_rollout", CRolloutBufs, ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward",
+                                                   "truncated"), *args)
+
+    def rollout_multi(self, *args):
+        """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""
+        self._rollout("wg_rollout_multi", CRolloutMultiBufs, ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value",
+                                                              "reward", "truncated", "flat_obs", "flat_final_obs"), *args)
+
     def set_step_graph(self, enable=True):
         """step() as one hipGraphLaunch (captured per distinct set of I/O pointers) instead of direct launches."""
         _chk(self.L.wg_set_step_graph(self._h, int(bool(enable))), "wg_set_step_graph")

@@ -631,6 +631,12 @@ extern "C" int wg_reset(wg_handle h, const uint8_t* env_mask_host, const uint64_
     return 0;
 }
 
+// one more step for wg_kernel_timing's averages -> whether this one's kernels are bracketed with timing events
+static bool count_step(wg_env_s* h) {
+    h->n_step_launches++;
+    return h->timing && (h->timing_phase++ % h->timing_period == 0);
+}
+
 // the launches of one step(); `sample`: bracket the two kernels with timing events
 static void launch_step(wg_env_s* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* truncated_dev,
                         float* final_obs_dev, hipStream_t st, bool sample) {
@@ -656,8 +662,7 @@ extern "C" int wg_step(wg_handle h, const float* actions_dev, float* obs_dev, fl
     if (!h || !actions_dev || !obs_dev) return fail(WG_ERR_INVALID, "null argument");
     if (int rc = use_device(h)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool sample = h->timing && (h->timing_phase++ % h->timing_period == 0);
-    h->n_step_launches++;
+    const bool sample = count_step(h);
     if (!h->graph_mode || sample) {
         launch_step(h, actions_dev, obs_dev, reward_dev, truncated_dev, final_obs_dev, st, sample);
         // a rejected launch (bad configuration, out-of-resources) must not pass for a step that returned stale outputs
@@ -821,120 +826,110 @@ static size_t info_bytes(const wg_env_s* h, int field) {
     }
 }
 
-// The closed loop policy -> step -> record for n_steps steps, enqueued from here (windgym_hip.h: wg_rollout).
-extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
-                          uint64_t row_offset, const wg_rollout_bufs* o, void* stream) {
-    if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout: null argument");
-    if (n_steps < 0) return fail(WG_ERR_INVALID, "wg_rollout: n_steps < 0");
-    if (!o->obs || !o->actions || !o->reward || !o->truncated)
-        return fail(WG_ERR_INVALID, "wg_rollout: obs, actions, reward and truncated buffers are required");
-    if (p->device != h->device) return fail(WG_ERR_INVALID, "wg_rollout: policy and handle live on different devices");
-    const int B = h->p.B, N = h->p.N, O = h->p.obs_dim;
-    if (p->P.n_in != O || p->P.n_out != N)
-        return fail(WG_ERR_INVALID, "wg_rollout: the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
-                                    ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N));
-    if (o->final_value && !o->final_obs) return fail(WG_ERR_INVALID, "wg_rollout: final_value needs final_obs");
-    if ((o->value || o->final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, "wg_rollout: value requested from a policy without a critic");
-    if (!p->P.has_log_std && (!deterministic || o->logp))
-        return fail(WG_ERR_INVALID, "wg_rollout: a stochastic rollout / log-probabilities need a policy with log_std");
-    if (o->n_info < 0 || (o->n_info > 0 && (!o->info_fields || !o->info_out))) return fail(WG_ERR_INVALID, "wg_rollout: bad info arguments");
-    for (int i = 0; i < o->n_info; ++i) {
-        if (o->info_fields[i] < 0 || o->info_fields[i] > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, "wg_rollout: unknown info field");
-        if (!o->info_out[i]) return fail(WG_ERR_INVALID, "wg_rollout: null info buffer");
+// The closed loop policy -> step -> record (windgym_hip.h: wg_rollout, wg_rollout_multi) exists once; this is what differs
+// between the two entries.
+struct RolloutRows {
+    const char *who, *obs_name;    // prefix of every message; the buffer the policy reads, as the messages name it
+    int per_env, n_in, n_out;      // policy rows per env; the shape the policy must have ...
+    std::string needs;             // ... and the end of the message that says so
+    const char* unready;           // non-null: refused with this message
+    bool per_agent;                // the steps write the policy's rows through WgPtrs::multi_out / multi_fin, re-aimed per step
+    wg_rollout_multi_bufs o;       // obs_multi / final_obs_multi: what the policy reads; obs / final_obs: the steps' flat rows
+};
+
+static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
+    const wg_rollout_multi_bufs& o = g.o;
+    const std::string who = std::string(g.who) + ": ";
+    if (n_steps < 0) return fail(WG_ERR_INVALID, who + "n_steps < 0");
+    if (!o.obs_multi || !o.actions || !o.reward || !o.truncated)
+        return fail(WG_ERR_INVALID, who + g.obs_name + ", actions, reward and truncated buffers are required");
+    if (p->device != h->device) return fail(WG_ERR_INVALID, who + "policy and handle live on different devices");
+    if (p->P.n_in != g.n_in || p->P.n_out != g.n_out)
+        return fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) + g.needs);
+    if (g.unready) return fail(WG_ERR_INVALID, who + g.unready);
+    if (o.final_value && !o.final_obs_multi) return fail(WG_ERR_INVALID, who + "final_value needs final_" + g.obs_name);
+    if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
+    if (!p->P.has_log_std && (!deterministic || o.logp))
+        return fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
+    if (o.n_info < 0 || (o.n_info > 0 && (!o.info_fields || !o.info_out))) return fail(WG_ERR_INVALID, who + "bad info arguments");
+    for (int i = 0; i < o.n_info; ++i) {
+        if (o.info_fields[i] < 0 || o.info_fields[i] > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, who + "unknown info field");
+        if (!o.info_out[i]) return fail(WG_ERR_INVALID, who + "null info buffer");
     }
-    if (int rc = use_device(h)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t sBO = (size_t)B * O, sBN = (size_t)B * N;
-    // final_value[t - 1] = V(final_obs[t - 1]) is computed by the launch that computes step t's actions (one more slot of
-    // k_policy's grid: a row's value does not depend on what else the launch computes), the last one by a launch of its own
-    for (int t = 0; t < n_steps; ++t) {
-        const bool fv = o->final_value && t > 0;
-        if (int rc = wg_policy_act2_(p, B, o->obs + t * sBO, deterministic, seed, counter0 + (uint64_t)t, row_offset, o->actions + t * sBN,
-                                     o->raw ? o->raw + t * sBN : nullptr, o->logp ? o->logp + (size_t)t * B : nullptr,
-                                     o->value ? o->value + (size_t)t * B : nullptr, fv ? o->final_obs + (t - 1) * sBO : nullptr,
-                                     fv ? o->final_value + (size_t)(t - 1) * B : nullptr, stream))
-            return rc;
-        // (direct launches also in graph mode: T distinct pointer sets would only churn the graph cache)
-        const bool sample = h->timing && (h->timing_phase++ % h->timing_period == 0);
-        h->n_step_launches++;
-        launch_step(h, o->actions + t * sBN, o->obs + (t + 1) * sBO, o->reward + (size_t)t * B, o->truncated + (size_t)t * B,
-                    o->final_obs ? o->final_obs + t * sBO : nullptr, st, sample);
-        for (int i = 0; i < o->n_info; ++i)
-            wg_launch_info(&h->p, &h->d, o->info_fields[i], (char*)o->info_out[i] + (size_t)t * info_bytes(h, o->info_fields[i]), st);
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(WG_ERR_HIP, std::string("wg_rollout: kernel launch failed: ") + hipGetErrorString(le));
-    }
-    if (o->final_value && n_steps > 0)
-        if (int rc = wg_policy_act(p, B, o->final_obs + (n_steps - 1) * sBO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
-                                   o->final_value + (size_t)(n_steps - 1) * B, stream))
-            return rc;
     return 0;
 }
 
-// The multi-agent closed loop (windgym_hip.h: wg_rollout_multi): wg_rollout's loop on agent rows.  The per-agent buffers of
-// step t are the kernel arguments of that step's launches (WgPtrs travels by value), so pointing the handle's two per-agent
-// pointers at slot t on the host between launches is all "wg_set_obs_multi_buffer per step" takes here: no device copy of
-// the parameter block is read for them, nothing is synchronised.
+// The per-agent buffers of step t are the kernel arguments of that step's launches (WgPtrs travels by value), so pointing the
+// handle's two per-agent pointers at slot t on the host between launches is all "wg_set_obs_multi_buffer per step" takes: no
+// device copy of the parameter block is read for them, nothing is synchronised.
+static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                        uint64_t row_offset, const RolloutRows& g, void* stream) {
+    const wg_rollout_multi_bufs& o = g.o;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->p.B, R = B * g.per_env;
+    const size_t sBO = (size_t)B * h->p.obs_dim, sR = (size_t)R, sRO = sR * g.n_in, sRN = sR * g.n_out;
+    float* const multi0 = h->d.multi_out;
+    float* const fin0 = h->d.multi_fin;
+    int rc = 0;
+    // final_value[t - 1] = V(final rows of step t - 1) is computed by the launch that computes step t's actions (one more slot
+    // of k_policy's grid: a row's value does not depend on what else the launch computes), the last one by a launch of its own
+    for (int t = 0; t < n_steps && !rc; ++t) {
+        const bool fv = o.final_value && t > 0;
+        rc = wg_policy_act2_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
+                             o.actions + t * sRN, o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr,
+                             o.value ? o.value + t * sR : nullptr, fv ? o.final_obs_multi + (t - 1) * sRO : nullptr,
+                             fv ? o.final_value + (t - 1) * sR : nullptr, stream);
+        if (rc) break;
+        if (g.per_agent) {
+            h->d.multi_out = o.obs_multi + (t + 1) * sRO;
+            h->d.multi_fin = o.final_obs_multi ? o.final_obs_multi + t * sRO : nullptr;
+        }
+        // (direct launches also in graph mode: T distinct pointer sets would only churn the graph cache)
+        launch_step(h, o.actions + t * sRN, o.obs ? o.obs + (t + 1) * sBO : h->flat_scratch, o.reward + (size_t)t * B,
+                    o.truncated + (size_t)t * B, o.final_obs ? o.final_obs + t * sBO : nullptr, st, count_step(h));
+        for (int i = 0; i < o.n_info; ++i)
+            wg_launch_info(&h->p, &h->d, o.info_fields[i], (char*)o.info_out[i] + (size_t)t * info_bytes(h, o.info_fields[i]), st);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) rc = fail(WG_ERR_HIP, std::string(g.who) + ": kernel launch failed: " + hipGetErrorString(le));
+    }
+    h->d.multi_out = multi0;      // the handle's own per-agent buffers again, on every way out (the device copies never changed)
+    h->d.multi_fin = fin0;
+    if (!rc && o.final_value && n_steps > 0)
+        rc = wg_policy_act(p, R, o.final_obs_multi + (n_steps - 1) * sRO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
+                           o.final_value + (n_steps - 1) * sR, stream);
+    return rc;
+}
+
+extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                          uint64_t row_offset, const wg_rollout_bufs* o, void* stream) {
+    if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout: null argument");
+    const int N = h->p.N, O = h->p.obs_dim;
+    // one policy row per env: the rows the policy reads are the flat rows the steps write
+    const RolloutRows g = {"wg_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
+                           nullptr, false,
+                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
+                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out}};
+    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
+    if (int rc = use_device(h)) return rc;
+    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+}
+
 extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                 uint64_t row_offset, const wg_rollout_multi_bufs* o, void* stream) {
     if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout_multi: null argument");
-    if (n_steps < 0) return fail(WG_ERR_INVALID, "wg_rollout_multi: n_steps < 0");
-    if (!o->obs_multi || !o->actions || !o->reward || !o->truncated)
-        return fail(WG_ERR_INVALID, "wg_rollout_multi: obs_multi, actions, reward and truncated buffers are required");
-    if (p->device != h->device) return fail(WG_ERR_INVALID, "wg_rollout_multi: policy and handle live on different devices");
-    const int B = h->p.B, N = h->p.N, O = h->p.obs_dim, Om = h->p.obs_dim_multi;
-    if (p->P.n_in != Om || p->P.n_out != 1)
-        return fail(WG_ERR_INVALID, "wg_rollout_multi: the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
-                                    ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) + " -> 1");
-    if (!h->d.multi_out)
-        return fail(WG_ERR_INVALID, "wg_rollout_multi: register a per-agent buffer first (wg_set_obs_multi_buffer); obs_multi[0] is what it held");
-    if (o->final_value && !o->final_obs_multi) return fail(WG_ERR_INVALID, "wg_rollout_multi: final_value needs final_obs_multi");
-    if ((o->value || o->final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, "wg_rollout_multi: value requested from a policy without a critic");
-    if (!p->P.has_log_std && (!deterministic || o->logp))
-        return fail(WG_ERR_INVALID, "wg_rollout_multi: a stochastic rollout / log-probabilities need a policy with log_std");
-    if (o->n_info < 0 || (o->n_info > 0 && (!o->info_fields || !o->info_out))) return fail(WG_ERR_INVALID, "wg_rollout_multi: bad info arguments");
-    for (int i = 0; i < o->n_info; ++i) {
-        if (o->info_fields[i] < 0 || o->info_fields[i] > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, "wg_rollout_multi: unknown info field");
-        if (!o->info_out[i]) return fail(WG_ERR_INVALID, "wg_rollout_multi: null info buffer");
-    }
+    const int B = h->p.B, N = h->p.N, Om = h->p.obs_dim_multi;
+    const RolloutRows g = {"wg_rollout_multi", "obs_multi", N, Om, 1,
+                           ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) + " -> 1",
+                           h->d.multi_out ? nullptr : "register a per-agent buffer first (wg_set_obs_multi_buffer); obs_multi[0] is what it held",
+                           true, *o};
+    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if ((long long)B * N > 0x7fffffffLL) return fail(WG_ERR_UNSUPPORTED, "wg_rollout_multi: more than 2^31 agent rows");
     if (int rc = use_device(h)) return rc;
     // the step kernels always build the flat observation: without a caller's buffer it goes to a row block of the handle's own
     // (allocated by the first call that needs it, before anything is enqueued)
     if (!o->obs && !h->flat_scratch)
-        if (int rc = dev_alloc(h, &h->flat_scratch, (size_t)B * O, false)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int R = B * N;
-    const size_t sBO = (size_t)B * O, sR = (size_t)R, sRO = sR * Om;
-    float* const multi0 = h->d.multi_out;
-    float* const fin0 = h->d.multi_fin;
-    int rc = 0;
-    for (int t = 0; t < n_steps && !rc; ++t) {
-        // (V of step t-1's final rows rides along with step t's actions, as in wg_rollout)
-        const bool fv = o->final_value && t > 0;
-        rc = wg_policy_act2_(p, R, o->obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)N,
-                             o->actions + t * sR, o->raw ? o->raw + t * sR : nullptr, o->logp ? o->logp + t * sR : nullptr,
-                             o->value ? o->value + t * sR : nullptr, fv ? o->final_obs_multi + (t - 1) * sRO : nullptr,
-                             fv ? o->final_value + (t - 1) * sR : nullptr, stream);
-        if (rc) break;
-        h->d.multi_out = o->obs_multi + (t + 1) * sRO;
-        h->d.multi_fin = o->final_obs_multi ? o->final_obs_multi + t * sRO : nullptr;
-        const bool sample = h->timing && (h->timing_phase++ % h->timing_period == 0);
-        h->n_step_launches++;
-        launch_step(h, o->actions + t * sR, o->obs ? o->obs + (t + 1) * sBO : h->flat_scratch, o->reward + (size_t)t * B,
-                    o->truncated + (size_t)t * B, o->final_obs ? o->final_obs + t * sBO : nullptr, st, sample);
-        for (int i = 0; i < o->n_info; ++i)
-            wg_launch_info(&h->p, &h->d, o->info_fields[i], (char*)o->info_out[i] + (size_t)t * info_bytes(h, o->info_fields[i]), st);
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) rc = fail(WG_ERR_HIP, std::string("wg_rollout_multi: kernel launch failed: ") + hipGetErrorString(le));
-    }
-    h->d.multi_out = multi0;      // the handle's own per-agent buffers again (the device copies never changed)
-    h->d.multi_fin = fin0;
-    if (rc) return rc;
-    if (o->final_value && n_steps > 0)
-        return wg_policy_act(p, R, o->final_obs_multi + (n_steps - 1) * sRO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
-                             o->final_value + (n_steps - 1) * sR, stream);
-    return 0;
+        if (int rc = dev_alloc(h, &h->flat_scratch, (size_t)B * h->p.obs_dim, false)) return rc;
+    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
 }
 
 extern "C" int wg_metrics(wg_handle h, float* out_dev, int reset_after, void* stream) {

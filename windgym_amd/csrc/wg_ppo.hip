@@ -1,7 +1,7 @@
 // wg_ppo.hip — training on the device: what `PPO("MlpPolicy", env).learn(...)` of stable-baselines3 does between two rollouts
 // (examples/longer_steps_example.py:212-240, examples/curriculum.py:544-560), for the MlpPolicy of wg_policy.hip.
 //
-//   k_gae          advantages and returns of a [T, B] rollout (wg_rollout's recurrence), one thread per env.
+//   k_gae          advantages and returns of a [T, B, A] rollout (wg_rollout's recurrence), one thread per agent row.
 //   k_ppo_advstat  mean and unbiased std of a minibatch's advantages, ONE workgroup, fixed-order sums.
 //   k_ppo_grad     one minibatch: gather, forward of actor / critic, PPO loss, backward, per-workgroup gradient partials.
 //   k_ppo_reduce   partials -> flat gradient + statistics record, summed in workgroup order.
@@ -34,28 +34,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // ---------------------------------------------------------------------------------------------------------------------
 // GAE
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void k_gae(const int T, const int B, const float* __restrict__ reward, const float* __restrict__ value,
+// One thread per AGENT row of a [T, B, A] rollout whose reward and truncation flag belong to the env (a farm's turbines share
+// the farm reward; A = 1: one row per env, wg_gae): consecutive threads walk consecutive agent rows, the two [B] arrays are
+// read once per thread (the A threads of an env fetch the same word: one transaction).
+__global__ void k_gae(const int T, const int B, const int A, const float* __restrict__ reward, const float* __restrict__ value,
                       const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const float gamma,
                       const float lambda, float* __restrict__ adv, float* __restrict__ ret) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    float a = 0.0f;
-    for (int t = T - 1; t >= 0; --t) {
-        const size_t o = (size_t)t * B + b;
-        const float v = value[o];
-        const float delta = reward[o] + gamma * final_value[o] - v;
-        a = delta + gamma * lambda * (truncated[o] ? 0.0f : 1.0f) * a;
-        adv[o] = a;
-        ret[o] = a + v;
-    }
-}
-
-// The same recurrence per AGENT row of a [T, B, A] rollout whose reward and truncation flag belong to the env (a farm's
-// turbines share the farm reward): one thread per (env, agent) — consecutive threads walk consecutive agent rows, the two
-// [B] arrays are read once per thread (the A threads of an env fetch the same word: one transaction).  A = 1 is k_gae.
-__global__ void k_gae_shared(const int T, const int B, const int A, const float* __restrict__ reward, const float* __restrict__ value,
-                             const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const float gamma,
-                             const float lambda, float* __restrict__ adv, float* __restrict__ ret) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     const int R = B * A;
     if (r >= R) return;
@@ -460,30 +444,32 @@ static int t_on_device(const void* p, int device, const char* what) {
     return 0;
 }
 
-extern "C" int wg_gae(int T, int B, const float* reward_dev, const float* value_dev, const float* final_value_dev,
-                      const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out,
-                      void* stream) {
+// wg_gae (A = 1) and wg_gae_shared: `who` and `dims` name the caller and its sizes in the messages
+static int gae_launch(const char* who, const char* dims, int T, int B, int A, const float* reward_dev, const float* value_dev,
+                      const float* final_value_dev, const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out,
+                      float* returns_out, void* stream) {
     if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !advantage_out || !returns_out)
-        return tfail(WG_ERR_INVALID, "wg_gae: null argument");
-    if (T < 1 || B < 1) return tfail(WG_ERR_INVALID, "wg_gae: T and B must be >= 1");
-    hipLaunchKernelGGL(k_gae, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, reward_dev, value_dev,
+        return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
+    if (T < 1 || B < 1 || A < 1) return tfail(WG_ERR_INVALID, std::string(who) + ": " + dims + " must be >= 1");
+    if ((long long)B * A > 0x7fffffffLL - 256) return tfail(WG_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 agent rows");
+    hipLaunchKernelGGL(k_gae, dim3((B * A + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, A, reward_dev, value_dev,
                        final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
     THIPCHK(hipGetLastError());
     return 0;
 }
 
+extern "C" int wg_gae(int T, int B, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+                      const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out,
+                      void* stream) {
+    return gae_launch("wg_gae", "T and B", T, B, 1, reward_dev, value_dev, final_value_dev, truncated_dev, gamma, lambda,
+                      advantage_out, returns_out, stream);
+}
+
 extern "C" int wg_gae_shared(int T, int B, int A, const float* reward_dev, const float* value_dev, const float* final_value_dev,
                              const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out,
                              void* stream) {
-    if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !advantage_out || !returns_out)
-        return tfail(WG_ERR_INVALID, "wg_gae_shared: null argument");
-    if (T < 1 || B < 1 || A < 1) return tfail(WG_ERR_INVALID, "wg_gae_shared: T, B and A must be >= 1");
-    if ((long long)B * A > 0x7fffffffLL - 256) return tfail(WG_ERR_UNSUPPORTED, "wg_gae_shared: more than 2^31 agent rows");
-    const int R = B * A;
-    hipLaunchKernelGGL(k_gae_shared, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, A, reward_dev, value_dev,
-                       final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
-    THIPCHK(hipGetLastError());
-    return 0;
+    return gae_launch("wg_gae_shared", "T, B and A", T, B, A, reward_dev, value_dev, final_value_dev, truncated_dev, gamma, lambda,
+                      advantage_out, returns_out, stream);
 }
 
 // LDS map of both nets for tiles of R rows -> bytes of the larger one

@@ -13,6 +13,7 @@ All physics and sensor work happens in libwindgym_hip.so; nothing here computes 
 from __future__ import annotations
 
 import copy
+import math
 from collections import deque
 from typing import Optional
 
@@ -219,6 +220,9 @@ class WindFarmVecEnv(_gym_vector_base()):
         self.spec = None
         self.closed = False
         self._global_offset = 0          # first global env index of this shard (set by shard())
+        self._was_reset = False          # the first reset() without a seed uses the base seed
+        self._policy_steps = 0           # rollout()'s noise counter: policy steps taken so far (PPO.save / load keep it)
+        self._rollout_bufs = {}          # rollout()'s buffers by (rows, T, record, values, stochastic_ok)
         self._actions = self.torch.zeros((self.num_envs, self.n_turb), dtype=self.torch.float32,
                                          device=self.batch.device)
         self._term = None
@@ -243,7 +247,7 @@ class WindFarmVecEnv(_gym_vector_base()):
         return t if self.as_torch else _np(t).copy()
 
     def reset(self, *, seed=None, options=None, mask=None):
-        seeds = self._seeds(seed if seed is not None else (self._base_seed if not getattr(self, "_was_reset", False) else None))
+        seeds = self._seeds(seed if seed is not None else (self._base_seed if not self._was_reset else None))
         self._was_reset = True
         obs = self.batch.reset(seeds=seeds, mask=mask)
         return self._out(obs), self.infos()
@@ -297,64 +301,71 @@ class WindFarmVecEnv(_gym_vector_base()):
         Noise: seed = the env's base seed, row offset = this shard's first global env, counter = a running count of policy
         steps of this env.  With ``sample_site`` the site table is refreshed by torch ops between steps: there, and only there,
         the equivalent loop of ``act`` + ``step`` runs from Python into the same buffers."""
-        import ctypes as C
-        from .binding import CRolloutBufs, _chk
+        b = self.batch
+        return self._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs,),
+                             shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
+                             slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout)
+
+    def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run):
+        """``rollout()`` of this class and of :class:`WindFarmVecEnvMulti`.  ``rows``: the axes of the policy's rows, ``(B,)`` or
+        ``(B, N)``; ``shape`` / ``needs``: the ``(n_in, n_out)`` the policy must have and how the refusal says so; ``slots``: per
+        observation the steps write, ``(key, key of its final rows, persistent tensor, persistent final tensor)`` — slot 0 is
+        seeded from the persistent tensor, which receives slot T (final: T-1) afterwards; the policy reads ``"obs"``; ``run``: the
+        ``HipBatch`` call that enqueues the loop."""
         from .config import INFO
         t, b = self.torch, self.batch
-        T, B, N, O = int(n_steps), self.num_envs, self.n_turb, b.obs_dim
+        T, B, N = int(n_steps), self.num_envs, self.n_turb
         if T < 1:
             raise ValueError("rollout(): n_steps must be >= 1")
-        if policy.n_in != O or policy.n_out != N:
-            raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, the env needs {O} -> {N}")
+        if (policy.n_in, policy.n_out) != shape:
+            raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, {needs}")
         record = tuple(record)
         for name in record:
             if name not in INFO:
                 raise ValueError(f"rollout(): unknown info field {name!r}")
         values = bool(values) and policy.has_critic
         stochastic_ok = policy.desc["has_log_std"]
-        key = (T, record, values, stochastic_ok)
-        cache = self.__dict__.setdefault("_rollout_bufs", {})
-        bufs = cache.get(key)
+        key = (rows, T, record, values, stochastic_ok)
+        bufs = self._rollout_bufs.get(key)
         if bufs is None:
             f32 = dict(dtype=t.float32, device=b.device)
-            bufs = dict(obs=t.zeros((T + 1, B, O), **f32), actions=t.zeros((T, B, N), **f32), raw=t.zeros((T, B, N), **f32),
-                        reward=t.zeros((T, B), **f32), truncated=t.zeros((T, B), dtype=t.uint8, device=b.device),
-                        final_obs=t.zeros((T, B, O), **f32))
+            bufs = dict(actions=t.zeros((T, B, N), **f32), raw=t.zeros((T, B, N), **f32), reward=t.zeros((T, B), **f32),
+                        truncated=t.zeros((T, B), dtype=t.uint8, device=b.device))
+            for k, kf, cur, fin in slots:
+                bufs[k], bufs[kf] = t.zeros((T + 1,) + tuple(cur.shape), **f32), t.zeros((T,) + tuple(fin.shape), **f32)
             if stochastic_ok:
-                bufs["logp"] = t.zeros((T, B), **f32)
+                bufs["logp"] = t.zeros((T,) + rows, **f32)
             if values:
-                bufs["value"], bufs["final_value"] = t.zeros((T, B), **f32), t.zeros((T, B), **f32)
+                bufs["value"], bufs["final_value"] = t.zeros((T,) + rows, **f32), t.zeros((T,) + rows, **f32)
             for name in record:
-                shape, dtype = b.info_shape(name)
-                bufs[name] = t.zeros((T,) + tuple(shape), dtype=dtype, device=b.device)
-            cache[key] = bufs
-        bufs["obs"][0].copy_(b.obs)
+                info_shape, dtype = b.info_shape(name)
+                bufs[name] = t.zeros((T,) + tuple(info_shape), dtype=dtype, device=b.device)
+            self._rollout_bufs[key] = bufs
+        for k, _, cur, _ in slots:
+            bufs[k][0].copy_(cur)
         seed = 0 if self._base_seed is None else int(self._base_seed)
-        counter0 = getattr(self, "_policy_steps", 0)
+        counter0 = self._policy_steps
         self._policy_steps = counter0 + T
         if self._site is not None:
             for i in range(T):
                 policy.act(bufs["obs"][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
-                           row_offset=self._global_offset, value=values,
+                           row_offset=self._global_offset * math.prod(rows[1:]), value=values,
                            out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
                                 bufs["value"][i] if values else None))
-                o, r, tr, f = self._step_device(bufs["actions"][i])
-                bufs["obs"][i + 1].copy_(o); bufs["reward"][i].copy_(r); bufs["truncated"][i].copy_(tr); bufs["final_obs"][i].copy_(f)
+                _, r, tr, _ = self._step_device(bufs["actions"][i])
+                bufs["reward"][i].copy_(r); bufs["truncated"][i].copy_(tr)
+                for k, kf, cur, fin in slots:
+                    bufs[k][i + 1].copy_(cur); bufs[kf][i].copy_(fin)
                 for name in record:
                     b.info(name, out=bufs[name][i])
                 if values:
                     policy.value(bufs["final_obs"][i], out=bufs["final_value"][i])
             return dict(bufs)
-        ptr = lambda k: bufs[k].data_ptr() if k in bufs else None          # noqa: E731
-        cb = CRolloutBufs(ptr("obs"), ptr("actions"), ptr("raw"), ptr("logp"), ptr("value"), ptr("final_obs"),
-                          ptr("final_value"), ptr("reward"), ptr("truncated"), len(record),
-                          (C.c_int32 * max(1, len(record)))(*[INFO[n] for n in record]),
-                          (C.c_void_p * max(1, len(record)))(*[bufs[n].data_ptr() for n in record]))
-        _chk(b.L.wg_rollout(b._h, policy._h, T, int(bool(deterministic)), seed, counter0, self._global_offset,
-                            C.byref(cb), b._stream()), "wg_rollout")
+        run(policy, T, bufs, record, deterministic, seed, counter0, self._global_offset)
         # the persistent outputs follow, as after a step()
-        b.obs.copy_(bufs["obs"][T]); b.reward.copy_(bufs["reward"][T - 1]); b.truncated.copy_(bufs["truncated"][T - 1])
-        b.final_obs.copy_(bufs["final_obs"][T - 1])
+        for k, kf, cur, fin in slots:
+            cur.copy_(bufs[k][T]); fin.copy_(bufs[kf][T - 1])
+        b.reward.copy_(bufs["reward"][T - 1]); b.truncated.copy_(bufs["truncated"][T - 1])
         return dict(bufs)
 
     def infos(self, step=False):
@@ -1059,7 +1070,7 @@ class WindFarmVecEnvMulti:
     # (the counters the single-agent rollout keeps on its env live on the wrapped env: PPO.save / load find them there)
     @property
     def _policy_steps(self):
-        return getattr(self.venv, "_policy_steps", 0)
+        return self.venv._policy_steps
 
     @_policy_steps.setter
     def _policy_steps(self, v):
@@ -1107,71 +1118,12 @@ class WindFarmVecEnvMulti:
         ``sample_site`` fallback loop are those of :meth:`WindFarmVecEnv.rollout`; the noise row of agent i of env e is
         ``(first global env of this shard + e) * N + i``.  Advantages: ``delta = r[t, e] + gamma * final_value[t, e, i] -
         value[t, e, i]`` per agent row (wg_gae_shared)."""
-        import ctypes as C
-        from .binding import CRolloutMultiBufs, _chk
-        from .config import INFO
-        t, b, v = self.torch, self.batch, self.venv
-        T, B, N, O, Om = int(n_steps), self.num_envs, self.n_turb, b.obs_dim, self.obs_len
-        if T < 1:
-            raise ValueError("rollout(): n_steps must be >= 1")
-        if policy.n_in != Om or policy.n_out != 1:
-            raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, a policy shared by the turbines of "
-                             f"this env maps {Om} -> 1")
-        record = tuple(record)
-        for name in record:
-            if name not in INFO:
-                raise ValueError(f"rollout(): unknown info field {name!r}")
-        values = bool(values) and policy.has_critic
-        stochastic_ok = policy.desc["has_log_std"]
-        key = (T, record, values, stochastic_ok)
-        cache = self.__dict__.setdefault("_rollout_bufs", {})
-        bufs = cache.get(key)
-        if bufs is None:
-            f32 = dict(dtype=t.float32, device=b.device)
-            bufs = dict(obs=t.zeros((T + 1, B, N, Om), **f32), actions=t.zeros((T, B, N), **f32), raw=t.zeros((T, B, N), **f32),
-                        reward=t.zeros((T, B), **f32), truncated=t.zeros((T, B), dtype=t.uint8, device=b.device),
-                        final_obs=t.zeros((T, B, N, Om), **f32), flat_obs=t.zeros((T + 1, B, O), **f32),
-                        flat_final_obs=t.zeros((T, B, O), **f32))
-            if stochastic_ok:
-                bufs["logp"] = t.zeros((T, B, N), **f32)
-            if values:
-                bufs["value"], bufs["final_value"] = t.zeros((T, B, N), **f32), t.zeros((T, B, N), **f32)
-            for name in record:
-                shape, dtype = b.info_shape(name)
-                bufs[name] = t.zeros((T,) + tuple(shape), dtype=dtype, device=b.device)
-            cache[key] = bufs
-        bufs["obs"][0].copy_(self._obs)
-        bufs["flat_obs"][0].copy_(b.obs)
-        seed = 0 if v._base_seed is None else int(v._base_seed)
-        counter0 = self._policy_steps
-        self._policy_steps = counter0 + T
-        if v._site is not None:
-            for i in range(T):
-                policy.act(bufs["obs"][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
-                           row_offset=self._global_offset * N, value=values,
-                           out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
-                                bufs["value"][i] if values else None))
-                o, r, tr, f = v._step_device(bufs["actions"][i])
-                bufs["obs"][i + 1].copy_(self._obs); bufs["final_obs"][i].copy_(self._final_obs)
-                bufs["flat_obs"][i + 1].copy_(o); bufs["reward"][i].copy_(r); bufs["truncated"][i].copy_(tr)
-                bufs["flat_final_obs"][i].copy_(f)
-                for name in record:
-                    b.info(name, out=bufs[name][i])
-                if values:
-                    policy.value(bufs["final_obs"][i], out=bufs["final_value"][i])
-            return dict(bufs)
-        ptr = lambda k: bufs[k].data_ptr() if k in bufs else None          # noqa: E731
-        cb = CRolloutMultiBufs(ptr("obs"), ptr("actions"), ptr("raw"), ptr("logp"), ptr("value"), ptr("final_obs"),
-                               ptr("final_value"), ptr("reward"), ptr("truncated"), ptr("flat_obs"), ptr("flat_final_obs"),
-                               len(record), (C.c_int32 * max(1, len(record)))(*[INFO[n] for n in record]),
-                               (C.c_void_p * max(1, len(record)))(*[bufs[n].data_ptr() for n in record]))
-        _chk(b.L.wg_rollout_multi(b._h, policy._h, T, int(bool(deterministic)), seed, counter0, self._global_offset,
-                                  C.byref(cb), b._stream()), "wg_rollout_multi")
-        # the persistent outputs follow, as after a step()
-        self._obs.copy_(bufs["obs"][T]); self._final_obs.copy_(bufs["final_obs"][T - 1])
-        b.obs.copy_(bufs["flat_obs"][T]); b.reward.copy_(bufs["reward"][T - 1]); b.truncated.copy_(bufs["truncated"][T - 1])
-        b.final_obs.copy_(bufs["flat_final_obs"][T - 1])
-        return dict(bufs)
+        b = self.batch
+        return self.venv._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs, self.n_turb),
+                                  shape=(self.obs_len, 1),
+                                  needs=f"a policy shared by the turbines of this env maps {self.obs_len} -> 1",
+                                  slots=(("obs", "final_obs", self._obs, self._final_obs),
+                                         ("flat_obs", "flat_final_obs", b.obs, b.final_obs)), run=b.rollout_multi)
 
     def infos(self, step=False):
         return self.venv.infos(step=step)

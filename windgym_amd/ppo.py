@@ -81,33 +81,25 @@ class PPOOptimizer:
         return x
 
     def gae(self, reward, value, final_value, truncated, gamma, gae_lambda, out=None):
-        """wg_gae on ``[T, B]`` CUDA tensors (``truncated`` uint8) -> (advantage, returns)."""
+        """wg_gae on ``[T, B]`` CUDA tensors (``truncated`` uint8) -> (advantage, returns).  With ``value`` / ``final_value
+        [T, B, A]`` per agent row, ``reward`` / ``truncated [T, B]`` shared by an env's agents: wg_gae_shared -> ``[T, B, A]``."""
         t = self.torch
         T, B = reward.shape
-        for x, w in ((reward, "reward"), (value, "value"), (final_value, "final_value")):
-            self._f32(x, (T, B), w)
-        if not (truncated.is_cuda and truncated.dtype == t.uint8 and truncated.is_contiguous() and tuple(truncated.shape) == (T, B)):
-            raise ValueError("truncated must be a contiguous uint8 CUDA tensor [T, B]")
-        adv, ret = out if out is not None else (t.empty_like(reward), t.empty_like(reward))
-        self._chk(self.L.wg_gae(T, B, reward.data_ptr(), value.data_ptr(), final_value.data_ptr(), truncated.data_ptr(),
-                                float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(), self.policy._stream()), "wg_gae")
-        return adv, ret
-
-    def gae_shared(self, reward, value, final_value, truncated, gamma, gae_lambda, out=None):
-        """wg_gae_shared: ``value`` / ``final_value [T, B, A]`` per agent row, ``reward`` / ``truncated [T, B]`` shared by an
-        env's agents -> (advantage, returns) ``[T, B, A]``."""
-        t = self.torch
-        if value.ndim != 3:
-            raise ValueError("value must be [T, B, A]")
-        T, B, A = value.shape
-        self._f32(reward, (T, B), "reward"); self._f32(value, (T, B, A), "value"); self._f32(final_value, (T, B, A), "final_value")
+        dims = (T, B) + tuple(value.shape[2:] if value.ndim == 3 else ())          # [T, B, A]: wg_gae_shared
+        self._f32(reward, (T, B), "reward"); self._f32(value, dims, "value"); self._f32(final_value, dims, "final_value")
         if not (truncated.is_cuda and truncated.dtype == t.uint8 and truncated.is_contiguous() and tuple(truncated.shape) == (T, B)):
             raise ValueError("truncated must be a contiguous uint8 CUDA tensor [T, B]")
         adv, ret = out if out is not None else (t.empty_like(value), t.empty_like(value))
-        self._chk(self.L.wg_gae_shared(T, B, A, reward.data_ptr(), value.data_ptr(), final_value.data_ptr(), truncated.data_ptr(),
-                                       float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(), self.policy._stream()),
-                  "wg_gae_shared")
+        entry = ("wg_gae", "wg_gae_shared")[len(dims) - 2]
+        self._chk(getattr(self.L, entry)(*dims, reward.data_ptr(), value.data_ptr(), final_value.data_ptr(), truncated.data_ptr(),
+                                         float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(), self.policy._stream()), entry)
         return adv, ret
+
+    def gae_shared(self, reward, value, *args, **kwargs):
+        """:meth:`gae` for ``value [T, B, A]`` only (A = 1 included)."""
+        if value.ndim != 3:
+            raise ValueError("value must be [T, B, A]")
+        return self.gae(reward, value, *args, **kwargs)
 
     def _batch(self, obs, raw, logp, advantage, returns):
         from .binding import CPpoBatch
@@ -227,13 +219,13 @@ class PPO:
         if not 1 <= batch_size <= n_rows:
             raise ValueError(f"batch_size must lie in [1, n_steps * num_envs{' * n_turb' if multi else ''} = {n_rows}]")
         self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
-        if isinstance(policy, str):
-            if policy != "MlpPolicy":
-                raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy'")
-            policy = self._build_policy(venv, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
-        elif policy_kwargs:
+        if isinstance(policy, str) and policy != "MlpPolicy":
+            raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy'")
+        if policy_kwargs and not isinstance(policy, str):
             raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
-        want = (int(venv.obs_len), 1) if multi else (int(venv.batch.obs_dim), int(venv.n_turb))
+        want = (int(venv.obs_len), 1) if multi else (int(venv.batch.obs_dim), int(venv.n_turb))       # the policy's n_in -> n_out
+        if isinstance(policy, str):
+            policy = self._build_policy(venv, want, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
         if (policy.n_in, policy.n_out) != want:
             raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, this env needs {want[0]} -> {want[1]} "
                              "(accepted shapes: obs_dim -> n_turb on a WindFarmVecEnv, obs_len -> 1 — one policy shared by the "
@@ -256,14 +248,13 @@ class PPO:
         self.num_timesteps, self.iteration, self.log = 0, 0, []
 
     @staticmethod
-    def _build_policy(venv, kw, seed):
+    def _build_policy(venv, shape, kw, seed):
         arch = kw.pop("net_arch", dict(pi=[64, 64], vf=[64, 64]))
         activation = kw.pop("activation", "tanh")
         if kw:
             raise ValueError(f"unknown policy_kwargs: {sorted(kw)}")
         pi, vf = (arch["pi"], arch["vf"]) if isinstance(arch, dict) else (arch, arch)
-        n_in, n_out = (venv.obs_len, 1) if getattr(venv, "possible_agents", None) is not None else (venv.batch.obs_dim, venv.n_turb)
-        p = MlpPolicy(n_in, n_out, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed)
+        p = MlpPolicy(*shape, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed)
         p.load_state_dict(sb3_orthogonal_init(p.desc, seed))
         return p
 
@@ -272,8 +263,7 @@ class PPO:
         """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added
         (``[T, B, N]`` from wg_gae_shared on a ``WindFarmVecEnvMulti``)."""
         out = self.venv.rollout(self.policy, self.n_steps)
-        gae = self.opt.gae_shared if self.multi else self.opt.gae
-        gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda, out=(self._adv, self._ret))
+        self.opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda, out=(self._adv, self._ret))
         out["advantage"], out["returns"] = self._adv, self._ret
         return out
 
@@ -348,7 +338,7 @@ class PPO:
             return b.getvalue()
         meta = dict(format="windgym_amd.PPO/1", desc=dict(self.policy.desc), hyper=self._hyper_json(), seed=self.seed,
                     policy_seed=self.policy.seed, policy_counter=self.policy.counter, num_timesteps=self.num_timesteps,
-                    iteration=self.iteration, adam_step=step, env_policy_steps=getattr(self.venv, "_policy_steps", 0), log=self.log)
+                    iteration=self.iteration, adam_step=step, env_policy_steps=self.venv._policy_steps, log=self.log)
         with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
             z.writestr("policy.pth", pth.getvalue())
             z.writestr("adam_state.npy", npy(mv))
