@@ -419,6 +419,11 @@ typedef struct wg_policy_desc {
 /* PPO.load's counterpart (AgentEval.py:179-190 needs nothing else of the model): an empty policy of the given
  * architecture on `device` (all parameters 0 until wg_policy_set_params).                                          */
 int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* out);
+/* The same with a critic of its own input width, n_in_vf -> hidden_vf... -> 1 (1 <= n_in_vf <= 2048; the descriptor must have a
+ * critic): a SPLIT policy, whose critic reads other rows than its actor — the centralised critic of multi-agent PPO (MAPPO:
+ * the actor on each agent's observation, the critic on the env's flat one; wg_rollout_multi, wg_ppo_grad_shared).  The flat
+ * vector keeps its order, the critic's first W is [h][n_in_vf].  wg_policy_create(d, ...) is this with n_in_vf = d->n_in.  */
+int wg_policy_create_vf(const wg_policy_desc* d, int32_t n_in_vf, int device, wg_policy* out);
 int wg_policy_destroy(wg_policy p);
 
 /* All parameters as ONE flat f32 vector of wg_policy_n_params floats: actor hidden layers in order, each W [out][in]
@@ -443,8 +448,11 @@ int wg_policy_n_params(wg_policy p, size_t* n);
  * and a row's outputs do not depend on n_rows or on the other rows: a batch sharded with row_offset = first global row
  * computes what the unsharded batch computes.  Row-generic: a parameter-shared per-turbine policy on the buffer of
  * wg_set_obs_multi_buffer is n_rows = B * N, n_out = 1.  One launch, asynchronous on `stream`, allocates and synchronises
- * nothing (legal inside a stream capture).  WG_ERR_INVALID: a stochastic call or logp on a policy without log_std, a
- * value on a policy without a critic.                                                                              */
+ * nothing (legal inside a stream capture).  On a split policy (wg_policy_create_vf, n_in_vf != n_in) a call that asks for an
+ * actor output reads rows of n_in, a call that asks for the value alone reads obs_dev f32[n_rows, n_in_vf]; the actor's outputs
+ * are bit-identical to those of an equal-width policy holding the same actor parameters.  WG_ERR_INVALID: a stochastic call or
+ * logp on a policy without log_std, a value on a policy without a critic, actor outputs AND the value from one obs_dev on a
+ * split policy (the two nets read rows of different widths).                                                        */
 int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int deterministic,
                   uint64_t seed, uint64_t counter, uint64_t row_offset,
                   float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream);
@@ -492,13 +500,15 @@ typedef struct wg_rollout_multi_bufs {
     float*   actions;          /* [T, B, N]        one yaw action per agent = what wg_step received (clipped)         */
     float*   raw;              /* [T, B, N]        or NULL                                                           */
     float*   logp;             /* [T, B, N]        or NULL                                                           */
-    float*   value;            /* [T, B, N]        or NULL: V(obs_multi[t]) per agent                                */
-    float*   final_obs_multi;  /* [T, B, N, Om]    or NULL (required with final_value): wg_set_final_obs_multi_buffer */
-    float*   final_value;      /* [T, B, N]        or NULL: V(final_obs_multi[t])                                    */
+    float*   value;            /* [T, B, N]        or NULL: V(obs_multi[t]) per agent          (central: [T, B], V(obs[t]))  */
+    float*   final_obs_multi;  /* [T, B, N, Om]    or NULL (required with final_value; central: never required):
+                                *                  wg_set_final_obs_multi_buffer                                      */
+    float*   final_value;      /* [T, B, N]        or NULL: V(final_obs_multi[t])              (central: [T, B], V(final_obs[t])) */
     float*   reward;           /* [T, B]           the farm reward, shared by the env's agents                       */
     uint8_t* truncated;        /* [T, B]                                                                              */
-    float*   obs;              /* [T+1, B, O]      or NULL: the flat observation; slot 0 is not touched               */
-    float*   final_obs;        /* [T, B, O]        or NULL                                                           */
+    float*   obs;              /* [T+1, B, O]      or NULL: the flat observation; slot 0 is not touched
+                                *                  (central: REQUIRED, slot 0 is INPUT — the flat observation the env last returned) */
+    float*   final_obs;        /* [T, B, O]        or NULL                                     (central: required with final_value) */
     int32_t  n_info;           /* recorded info fields, as in wg_rollout_bufs                                         */
     const int32_t* info_fields;
     void* const*   info_out;
@@ -518,8 +528,25 @@ typedef struct wg_rollout_multi_bufs {
  * of env e is (row_offset + e) * N + i: a shard of the env axis computes what the unsharded batch computes.  Without `obs`
  * the steps' flat observation goes to a buffer of the handle's own, allocated by the first such call before anything is
  * enqueued.  Advantages: wg_gae_shared.
- * WG_ERR_INVALID: as wg_rollout, with p's n_in != obs_dim_multi or n_out != 1, final_value without final_obs_multi, or no
- * per-agent buffer registered on the handle.                                                                         */
+ *
+ * CENTRAL mode — a split policy (wg_policy_create_vf) that maps obs_dim_multi -> 1 with its critic on n_in_vf = obs_dim: the
+ * actor stays per agent, the critic reads the env's FLAT observation (centralised training, decentralised execution).  Same
+ * struct; value / final_value are [T, B], `obs` is required with slot 0 as input, final_obs is required with final_value and
+ * final_obs_multi with nothing.  Buffers and the handle's state afterwards are BIT-IDENTICAL to
+ *     for t in 0 .. T-1:
+ *         wg_set_obs_multi_buffer(h, obs_multi[t+1]);  wg_set_final_obs_multi_buffer(h, final_obs_multi[t])
+ *         wg_policy_act(p, B * N, obs_multi[t], deterministic, seed, counter0 + t, row_offset * N, actions[t], raw[t], logp[t], NULL)
+ *         wg_policy_act(p, B, obs[t], value only -> value[t])                          if wanted
+ *         wg_step(h, actions[t], obs[t+1], reward[t], truncated[t], final_obs[t])
+ *         wg_get_info(h, info_fields[i], info_out[i] + t * <size of the field>)       for every i
+ *         wg_policy_act(p, B, final_obs[t], value only -> final_value[t])              if wanted
+ * Advantages are then wg_gae on [T, B], shared by an env's agents; the update is wg_ppo_update_shared.  The mode is recognised by
+ * the critic's width alone (n_in_vf != n_in and n_in_vf == obs_dim), so it needs obs_dim != obs_dim_multi: on a handle whose flat
+ * and per-agent observations have one width (a farm of ONE turbine: one agent per env, nothing to centralise) every accepted
+ * policy runs in per-agent mode.
+ * WG_ERR_INVALID: as wg_rollout, with a policy that is neither obs_dim_multi -> 1 with its critic on obs_dim_multi (per agent)
+ * nor obs_dim_multi -> 1 with its critic on obs_dim (central); final_value without final_obs_multi (central: without final_obs);
+ * central mode without obs; no per-agent buffer registered on the handle.                                           */
 int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                      uint64_t row_offset, const wg_rollout_multi_bufs* out, void* stream);
 
@@ -542,7 +569,8 @@ int wg_gae(int T, int B, const float* reward_dev, const float* value_dev, const 
 /* The same for agents that share their env's reward (wg_rollout_multi's buffers): value / final_value / advantage / returns
  * are [T, B, A], reward / truncated [T, B]; agent row (b, a) runs the recurrence above with reward[t, b] and truncated[t, b].
  * A = 1 is wg_gae bit for bit.  The update is wg_ppo_update on the T * B * A agent rows: independent PPO with shared
- * parameters, each agent's critic on its own observation.                                                          */
+ * parameters, each agent's critic on its own observation.  (A centralised critic has ONE value per env: wg_gae on [T, B],
+ * then wg_ppo_update_shared.)                                                                                       */
 int wg_gae_shared(int T, int B, int A, const float* reward_dev, const float* value_dev, const float* final_value_dev,
                   const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out, float* returns_out, void* stream);
 
@@ -585,7 +613,9 @@ typedef struct wg_ppo_stats {      /* means over the minibatch: what SB3 logs as
  * grad_out f32[wg_policy_n_params] = d loss / d params in the flat layout of wg_policy_set_params; stats_out (device, may be
  * NULL) the record above.  params_dev must be the vector the policy was last given (wg_policy_set_params / wg_ppo_apply):
  * the forward pass is k_policy's, so with unchanged parameters ratio = 1 to rounding.  A data-parallel trainer all-reduces
- * grad_out between this call and wg_ppo_apply.                                                                       */
+ * grad_out between this call and wg_ppo_apply.  WG_ERR_INVALID: null / out-of-range arguments; a SPLIT policy
+ * (wg_policy_create_vf, n_in_vf != n_in) — its critic cannot read `obs`, whose rows have the actor's width: nothing is enqueued,
+ * the message names both widths and wg_ppo_grad_shared.                                                               */
 int wg_ppo_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* batch, const int32_t* index_dev, int64_t first, int n,
                 const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream);
 
@@ -600,9 +630,33 @@ int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, f
  * epoch; stats_out (device, may be NULL) is wg_ppo_stats[n_epochs, n_mb].  Bit-identical to
  *     for e in 0 .. n_epochs-1:  for k in 0 .. n_mb-1:
  *         wg_ppo_grad(o, params_dev, batch, perm_dev + e * n_rows + k * batch_size, 0, min(batch_size, n_rows - k * batch_size),
- *                     hp, g, stats_out + e * n_mb + k);   wg_ppo_apply(o, params_dev, g, lr, max_grad_norm)                */
+ *                     hp, g, stats_out + e * n_mb + k);   wg_ppo_apply(o, params_dev, g, lr, max_grad_norm)
+ * WG_ERR_INVALID: as wg_ppo_grad, a split policy included (nothing is enqueued; use wg_ppo_update_shared).                  */
 int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
                   int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
+
+/* A rollout of agents that share their env's critic (wg_rollout_multi's central mode): every minibatch entry is an AGENT row
+ * and carries its env's state — multi-agent PPO as published (MAPPO).  Agent row id belongs to env row e = id / agents.     */
+typedef struct wg_ppo_batch_shared {
+    wg_ppo_batch rows;     /* obs [n_rows, n_in], raw, logp [n_rows]: AGENT rows;  advantage, returns: [n_rows / agents] ENV rows */
+    const float* obs_vf;   /* [n_rows / agents, n_in_vf]  what the critic reads: the env rows' flat observation                   */
+    int32_t agents;        /* >= 1, divides n_rows                                                                               */
+} wg_ppo_batch_shared;
+
+/* wg_ppo_grad on such a batch.  For minibatch entry id, e = id / agents: the actor term uses obs[id], raw[id], logp[id] and
+ * A = advantage[e]; the advantage normalisation is the mean / unbiased std of advantage[id / agents] over the minibatch's entries;
+ * L_v = (returns[e] - V(obs_vf[e]))^2, averaged over the minibatch's ENTRIES (an env row drawn through two of its agents counts
+ * twice).  Everything else — index_dev / first / n in agent rows, the statistics record, the determinism contract — as
+ * wg_ppo_grad, which is this call on {*batch, batch->obs, 1}: with agents = 1, n_in_vf = n_in and obs_vf = obs the two are
+ * bit-identical (on an equal-width policy: a split one is only accepted here).  WG_ERR_INVALID also for agents < 1 or not
+ * dividing n_rows, a null obs_vf.                                                                                     */
+int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* batch, const int32_t* index_dev, int64_t first,
+                       int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream);
+
+/* wg_ppo_update on such a batch: perm_dev int32[n_epochs, n_rows] permutes AGENT rows, batch_size counts them.  Bit-identical to
+ * wg_ppo_update's loop with wg_ppo_grad_shared in place of wg_ppo_grad; wg_ppo_update is this call on {*batch, batch->obs, 1}. */
+int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared* batch, const int32_t* perm_dev, int n_epochs,
+                         int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
 #ifdef __cplusplus
 }

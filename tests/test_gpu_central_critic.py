@@ -1,0 +1,512 @@
+"""The centralised critic on the device (multi-agent PPO with ONE critic per env on the flat observation, MAPPO).
+
+* k_policy, split policy        the critic on rows of its own width against the float64 policy oracle, the actor bit-identical to an
+                                equal-width policy's, a row's value independent of the batch, the mixed call refused;
+* wg_rollout_multi, central     equals its documented loop of single calls bit for bit (buffers, state, the step after it), its values
+                                are ``policy.value`` of the flat rows, the trajectory does not depend on the critic, env-axis shards
+                                compute their slice, refusals, the ``sample_site`` fallback;
+* wg_ppo_grad_shared            against the float64 reference of tests/central_critic_ref.py; agents = 1 on one stream is wg_ppo_grad;
+* wg_ppo_update_shared          equals its loop of grad_shared + apply bit for bit;
+* PPO(critic="central")         equals a twin assembled from rollout, gae and update; save / load resume; the ValueErrors."""
+import copy
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from central_critic_ref import STATS, shared_loss_and_grad, tile_rows
+from oracle import policy_oracle as po
+from windgym_amd.policy import pack_params, param_layout
+
+pytestmark = pytest.mark.gpu
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def close(a, b, tol=2e-5, rel=0.0):                                          # test_gpu_policy.py's
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return bool(np.all(np.abs(a - b) <= tol + rel * np.abs(b)))
+
+
+def make(n_in, hidden, n_out, n_in_vf=None, hidden_vf=(64,), activation="tanh", seed=3):
+    """A policy (split when ``n_in_vf`` differs from ``n_in``) with every bias and log_std away from 0 + its float32 state dict."""
+    from windgym_amd.policy import MlpPolicy
+    p = MlpPolicy(n_in, n_out, hidden, hidden_vf, activation, seed=seed, n_in_vf=n_in_vf)
+    rng = np.random.default_rng(seed + 1)
+    sd = {k: v.cpu().numpy() for k, v in p.state_dict().items()}
+    for k in sd:
+        if k.endswith("bias") or k == "log_std":
+            sd[k] = rng.uniform(-0.3, 0.3, sd[k].shape).astype(np.float32)
+    p.load_state_dict(sd)
+    return p, sd
+
+
+def same_actor(p, sd, n_in_vf=None, hidden_vf=(64,)):
+    """A policy with p's actor parameters (and log_std) and a critic of its own on ``n_in_vf`` (default: the actor's width)."""
+    q, sq = make(p.n_in, p.desc["hidden_pi"], p.n_out, n_in_vf, hidden_vf, p.desc["activation"], seed=11)
+    sq.update({k: v for k, v in sd.items() if "value_net" not in k})
+    q.load_state_dict(sq)
+    return q, sq
+
+
+def dev(*arrays):
+    t = _torch()
+    return [t.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 1. k_policy on a split policy
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("activation", ["tanh", "relu"])
+@pytest.mark.parametrize("n_in_vf", [1, 33, 256, 257, 2048])
+def test_split_policy_critic_vs_oracle_and_actor_bits(n_in_vf, activation):
+    t = _torch()
+    p, sd = make(2, (64, 64), 3, n_in_vf, (64, 32), activation)
+    assert p.split and p.n_in_vf == n_in_vf and p.params.numel() == sum(int(np.prod(s)) for _, s in param_layout(p.desc))
+    q, _ = same_actor(p, sd, None, (16,))                                    # equal widths, another critic altogether
+    assert not q.split
+    rng = np.random.default_rng(n_in_vf)
+    whole = None
+    for rows in (4096, 389, 1):
+        xv = rng.uniform(-1, 1, (rows, n_in_vf)).astype(np.float32)
+        v = p.value(dev(xv)[0])
+        ref = po._net(sd, "mlp_extractor.value_net", "value_net", xv, activation)[:, 0]
+        assert close(v.cpu().numpy(), ref, 2e-5, 2e-5), (rows, np.abs(v.cpu().numpy() - ref).max())
+        if whole is None:
+            whole = (xv, v.clone())
+        xa = dev(rng.uniform(-1, 1, (rows, 2)).astype(np.float32))[0]
+        a = [o.clone() for o in p.act(xa, counter=5, seed=9, row_offset=7)[:3]]
+        assert p.act(xa, counter=5, seed=9, row_offset=7)[3] is None          # the actor alone: no value from these rows
+        b = q.act(xa, counter=5, seed=9, row_offset=7)
+        assert all(t.equal(x, y) for x, y in zip(a, b[:3]))
+        mean_t, v_t = p.torch_forward(xa, dev(xv)[0])
+        assert close(v.cpu().numpy(), v_t.detach().cpu().numpy(), 2e-5, 2e-5) and p.torch_forward(xa)[1] is None
+    # a row's value does not depend on the batch it is evaluated in
+    xv, v = whole
+    for lo, hi in ((0, 1), (100, 133), (4000, 4096)):
+        assert t.equal(p.value(dev(xv[lo:hi])[0]), v[lo:hi])
+    # actor outputs and the value from ONE obs_dev: refused, and the message says why
+    x2 = dev(rng.uniform(-1, 1, (8, 2)).astype(np.float32))[0]
+    o = t.zeros(64, device="cuda")
+    with pytest.raises(ValueError, match="one obs_dev cannot serve both"):
+        p._chk(p.L.wg_policy_act(p._h, 8, x2.data_ptr(), 1, 0, 0, 0, o.data_ptr(), None, None, o.data_ptr(), p._stream()), "wg_policy_act")
+    with pytest.raises(ValueError, match=str(n_in_vf)):
+        p.value(x2)                                                          # rows of the ACTOR's width
+    p.close(); q.close()
+
+
+def test_create_vf_refusals():
+    from windgym_amd.policy import MlpPolicy
+    with pytest.raises(NotImplementedError, match="n_in_vf"):
+        MlpPolicy(4, 1, (8,), (8,), n_in_vf=2049)
+    with pytest.raises(ValueError, match="critic"):
+        MlpPolicy(4, 1, (8,), None, n_in_vf=7)
+    p = MlpPolicy(4, 1, (8,), (8,), n_in_vf=4)                                # the same width spelled out: not split
+    assert not p.split and p.n_in_vf == 4
+    p.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 2. the closed loop
+# ----------------------------------------------------------------------------------------------------------------------
+def _menv(n_envs, seed, **over):
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnvMulti
+    from windgym_amd.turbine import V80
+    kw = dict(n_passthrough=0.3)
+    kw.update(over)
+    return WindFarmVecEnvMulti(V80(), n_envs, yaml_dict=copy.deepcopy(presets.multi_3x3_config()), seed=seed, turbtype="None", n_rotor_pts=16, **kw)
+
+
+def central_rollout_equals_the_loop(va, vb, p, T, rec=("power_agent",), min_trunc=1):
+    """tests/loop_twin.py for a split policy: va.rollout(p, T) == the loop of actor-only act, value on the flat rows, step, value on
+    the flat final rows, driven from Python on the twin vb — every buffer, the handle's state, the persistent outputs, the step after."""
+    t = _torch()
+    B, N = va.num_envs, va.n_turb
+    seed, row0, counter0 = int(va.venv._base_seed), va._global_offset, vb._policy_steps
+    assert va._policy_steps == counter0
+    out = va.rollout(p, T, record=rec)
+    cur = lambda v: {("obs", "final_obs"): (v._obs, v._final_obs), ("flat_obs", "flat_final_obs"): (v.batch.obs, v.batch.final_obs)}   # noqa: E731
+    ref = {k: [] for k in ("actions", "raw", "logp", "value", "final_value", "reward", "truncated") + tuple(rec)}
+    for (k, kf), (o, _) in cur(vb).items():
+        ref[k], ref[kf] = [o.clone()], []
+    for i in range(T):
+        a, raw, logp, v = p.act(ref["obs"][-1], counter=counter0 + i, seed=seed, row_offset=row0 * N)
+        assert v is None
+        a = a.reshape(B, N).clone()
+        ref["actions"].append(a); ref["raw"].append(raw.reshape(B, N).clone()); ref["logp"].append(logp.reshape(B, N).clone())
+        ref["value"].append(p.value(ref["flat_obs"][-1]).clone())
+        vb.step(a)
+        ref["reward"].append(vb.batch.reward.clone()); ref["truncated"].append(vb.batch.truncated.clone())
+        for (k, kf), (o, f) in cur(vb).items():
+            ref[k].append(o.clone()); ref[kf].append(f.clone())
+        for name in rec:
+            ref[name].append(vb.batch.info(name))
+        ref["final_value"].append(p.value(ref["flat_final_obs"][-1]).clone())
+    vb._policy_steps = counter0 + T
+    assert set(out) == set(ref)
+    for k, x in ref.items():
+        x = t.stack(x)
+        assert out[k].shape == x.shape and t.equal(out[k], x), k
+    assert tuple(out["value"].shape) == (T, B) == tuple(out["final_value"].shape) and tuple(out["logp"].shape) == (T, B, N)
+    tr = out["truncated"].bool()
+    assert int(tr.sum()) >= min_trunc, int(tr.sum())
+    va.batch.check(); vb.batch.check()
+    assert va.batch.get_state() == vb.batch.get_state() and va._policy_steps == counter0 + T
+    # an env that did not truncate ended the step in the state the next one starts from; one that did, did not
+    assert t.equal(out["final_value"][:-1][~tr[:-1]], out["value"][1:][~tr[:-1]])
+    assert not tr[:-1].any() or not t.equal(out["final_value"][:-1][tr[:-1]], out["value"][1:][tr[:-1]])
+    for (k, kf), (o, f) in cur(va).items():
+        assert t.equal(o, out[k][T]) and t.equal(f, out[kf][T - 1]), k
+    act = t.zeros((B, N), device="cuda")
+    for x, y in zip(va.step(act), vb.step(act)):
+        assert t.equal(x, y)
+    return out
+
+
+def test_central_rollout_equals_its_loop_and_does_not_steer_the_trajectory():
+    t = _torch()
+    B, T, seed = 40, 150, 1234                                               # (40 envs: two tiles of critic rows, the second ragged)
+    va, vb, vc = (_menv(B, seed) for _ in range(3))
+    for v in (va, vb, vc):
+        v.reset(seed=seed)
+    N, Om, O = va.n_turb, va.obs_len, va.batch.obs_dim
+    assert O != Om
+    p, sd = make(Om, (64, 64), 1, O, (64, 32))
+    out = central_rollout_equals_the_loop(va, vb, p, T)
+    assert int(out["truncated"].any(dim=0).sum()) >= B // 2                  # episodes ended inside the window
+    # the values ARE policy.value of the flat rows (whatever else the launch that computed them held), and the float64 oracle's
+    assert t.equal(out["value"], p.value(out["flat_obs"][:T].contiguous()).view(T, B))
+    assert t.equal(out["final_value"], p.value(out["flat_final_obs"]).view(T, B))
+    ref = po._net(sd, "mlp_extractor.value_net", "value_net", out["flat_obs"][:T].cpu().numpy(), "tanh")[..., 0]
+    assert close(out["value"].cpu().numpy(), ref, 2e-5, 2e-5)
+    # the critic cannot influence the trajectory: a per-agent-critic policy with the same actor and seed walks the same one
+    q, _ = same_actor(p, sd)
+    other = vc.rollout(q, T, record=("power_agent",))
+    assert tuple(other["value"].shape) == (T, B, N)
+    for k in ("obs", "flat_obs", "actions", "raw", "logp", "reward", "truncated", "final_obs", "flat_final_obs", "power_agent"):
+        assert t.equal(out[k], other[k]), k
+    # a second rollout with another record tuple and length, interleaved with the step() the twin check ends in
+    central_rollout_equals_the_loop(va, vb, p, 25, rec=("timestep", "yaw_agent"), min_trunc=0)
+    for v in (va, vb, vc):
+        v.close()
+    p.close(); q.close()
+
+
+def test_central_rollout_shards_refusals_and_site_fallback():
+    from windgym_amd.binding import CRolloutMultiBufs, _chk
+    from windgym_amd.site import hornsrev1_site
+    t = _torch()
+    T, seed = 60, 4321
+    whole = _menv(32, seed)
+    halves = [_menv(16, seed).shard(r, 2) for r in range(2)]
+    for v in [whole] + halves:
+        v.reset(seed=seed)
+    N, Om, O = whole.n_turb, whole.obs_len, whole.batch.obs_dim
+    p, sd = make(Om, (64,), 1, O, (32,))
+    out = {k: x.clone() for k, x in whole.rollout(p, T, record=("yaw_agent",)).items()}
+    for r, v in enumerate(halves):
+        part = v.rollout(p, T, record=("yaw_agent",))
+        assert set(part) == set(out)
+        for k, x in part.items():
+            assert t.equal(x, out[k][:, 16 * r:16 * (r + 1)]), (k, r)
+        v.batch.check()
+    # refusals, with their messages: a critic of neither accepted width (Python and ABI), central mode without obs / final_obs
+    bad, _ = make(Om, (64,), 1, O + 1, (32,))
+    with pytest.raises(ValueError, match="centralised critic"):
+        whole.rollout(bad, 4)
+    with pytest.raises(ValueError, match="critic reads"):
+        whole.venv.rollout(make(O, (8,), N, O + 1, (8,))[0], 4)              # the single-agent env takes no split policy
+    b = whole.batch
+    f32 = dict(dtype=t.float32, device="cuda")
+    bufs = dict(obs=t.zeros((5, 32, N, Om), **f32), actions=t.zeros((4, 32, N), **f32), value=t.zeros((4, 32), **f32),
+                final_value=t.zeros((4, 32), **f32), reward=t.zeros((4, 32), **f32), truncated=t.zeros((4, 32), dtype=t.uint8, device="cuda"),
+                flat=t.zeros((5, 32, O), **f32), flat_final=t.zeros((4, 32, O), **f32))
+
+    def call(pol, **ptr):
+        x = dict(obs_multi=bufs["obs"], actions=bufs["actions"], value=bufs["value"], final_value=bufs["final_value"], reward=bufs["reward"],
+                 truncated=bufs["truncated"], obs=bufs["flat"], final_obs=bufs["flat_final"])
+        x.update(ptr)
+        cb = CRolloutMultiBufs(**{k: (None if v is None else v.data_ptr()) for k, v in x.items()})
+        _chk(b.L.wg_rollout_multi(b._h, pol._h, 4, 1, seed, 0, 0, C.byref(cb), b._stream()), "wg_rollout_multi")
+
+    state = b.get_state()
+    with pytest.raises(ValueError, match="obs is required"):
+        call(p, obs=None)
+    with pytest.raises(ValueError, match="final_value needs final_obs "):
+        call(p, final_obs=None)
+    with pytest.raises(ValueError, match=r"critic reads \d+ inputs.*obs_dim_multi.*centralised critic"):
+        call(bad)
+    assert b.get_state() == state                                            # a refused call enqueues nothing
+    bufs["obs"][0].copy_(whole._obs); bufs["flat"][0].copy_(b.obs)
+    call(p)                                                                  # (final_obs_multi = NULL: not needed for final_value here)
+    b.check()
+    assert t.equal(bufs["value"], p.value(bufs["flat"][:4].contiguous()).view(4, 32))
+    assert t.equal(bufs["final_value"], p.value(bufs["flat_final"]).view(4, 32))
+    for v in [whole] + halves:
+        v.close()
+    # sample_site: the Python loop of act + step into the same buffers — the shapes and keys of the library loop, its values
+    vs = _menv(8, 5, sample_site=hornsrev1_site())
+    vs.reset(seed=5)
+    o = vs.rollout(p, 6)
+    assert {k: (x.ndim, tuple(x.shape[2:])) for k, x in o.items()} == {k: (x.ndim, tuple(x.shape[2:])) for k, x in out.items() if k != "yaw_agent"}
+    assert t.equal(o["value"], p.value(o["flat_obs"][:6].contiguous()).view(6, 8))
+    assert t.equal(o["final_value"], p.value(o["flat_final_obs"]).view(6, 8))
+    vs.batch.check(); vs.close()
+    p.close(); bad.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 3. / 4. the update
+# ----------------------------------------------------------------------------------------------------------------------
+def shared_batch(sd, n_in, n_in_vf, n_out, n_env, agents, activation, seed=0):
+    """Random agent rows whose ratios straddle both clip bounds + the env rows the critic reads, advantages and returns per env row."""
+    rng = np.random.default_rng(seed)
+    n = n_env * agents
+    obs = rng.uniform(-1, 1, (n, n_in)).astype(np.float32)
+    obs_vf = rng.uniform(-1, 1, (n_env, n_in_vf)).astype(np.float32)
+    mean = po._net(sd, "mlp_extractor.policy_net", "action_net", obs, activation)
+    value = po._net(sd, "mlp_extractor.value_net", "value_net", obs_vf, activation)[:, 0]
+    std = np.exp(sd["log_std"].astype(np.float64))
+    raw = (mean + std * rng.standard_normal((n, n_out))).astype(np.float32)
+    z = (raw - mean) / std
+    logp = np.sum(-0.5 * z * z - sd["log_std"] - 0.5 * np.log(2 * np.pi), axis=1)
+    logp_old = (logp + 0.3 * rng.standard_normal(n)).astype(np.float32)
+    adv = (rng.standard_normal(n_env) * 2.0 + 0.5).astype(np.float32)
+    ret = (value + rng.standard_normal(n_env)).astype(np.float32)
+    return obs, obs_vf, raw, logp_old, adv, ret
+
+
+def flat_grad(desc, grads):
+    return pack_params(desc, {k: v.astype(np.float32) for k, v in grads.items()}).astype(np.float64)
+
+
+GRAD_SHAPES = [(13, 31, (64, 64), (64, 64), 1), (2, 2048, (64,), (256, 256), 1), (2048, 2, (256, 256), (64,), 4), (8, 8, (33,), (33,), 3)]
+
+
+@pytest.mark.parametrize("activation", ["tanh", "relu"])
+@pytest.mark.parametrize("agents", [1, 3, 9])
+@pytest.mark.parametrize("shape", GRAD_SHAPES, ids=lambda s: f"{s[0]}-vf{s[1]}")
+def test_grad_shared_vs_float64_reference(shape, agents, activation):
+    from windgym_amd.ppo import PPOOptimizer
+    n_in, n_in_vf, hidden, hidden_vf, n_out = shape
+    p, sd = make(n_in, hidden, n_out, n_in_vf, hidden_vf, activation)
+    assert p.split == (n_in != n_in_vf)
+    sd64 = {k: v.astype(np.float64) for k, v in sd.items()}
+    opt = PPOOptimizer(p)
+    R = tile_rows(n_in, n_in_vf, n_out, hidden, hidden_vf)
+    assert R is not None
+    n_env = 120
+    n_total = n_env * agents
+    arrays = shared_batch(sd64, n_in, n_in_vf, n_out, n_env, agents, activation, seed=agents)
+    obs, obs_vf, raw, lpo, adv, ret = arrays
+    d = dev(*arrays)
+    rng = np.random.default_rng(5)
+    # (entries, normalise?): a permutation prefix with a ragged last tile; one env row drawn through SEVERAL of its agents (and
+    # twice through the same one); entries outside the batch, skipped; a contiguous range; a single entry
+    perm = rng.permutation(n_total)
+    ragged = perm[:min(n_total, 5 * R + 1)]
+    several = np.concatenate([np.arange(agents) + 7 * agents, [7 * agents], perm[:2 * R]]) if agents > 1 else np.concatenate([[7, 7], perm[:2 * R]])
+    outside = np.concatenate([perm[:R + 3], [-1, n_total, n_total + 5, 2 ** 31 - 1], perm[R + 3:2 * R]])
+    cases = [(ragged, True), (several, True), (outside, True), (several, False), (np.arange(5, 5 + min(60, n_total - 5)), False), (perm[:1], True)]
+    for k, (ids, norm) in enumerate(cases):
+        kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=norm)
+        if k == 4:
+            g, st = opt.grad(d[0], d[2], d[3], d[4], d[5], first=5, n=len(ids), obs_vf=d[1], agents=agents, **kw)
+        else:
+            g, st = opt.grad(d[0], d[2], d[3], d[4], d[5], index=dev(ids.astype(np.int32))[0], obs_vf=d[1], agents=agents, **kw)
+        g, st = g.cpu().numpy().astype(np.float64), st.cpu().numpy()
+        _, grads, rs = shared_loss_and_grad(sd64, obs, obs_vf, raw, lpo, adv, ret, ids, agents, activation=activation, **kw)
+        ref = flat_grad(p.desc, grads)
+        err = np.abs(g - ref).max()
+        assert np.all(np.isfinite(g)) and err <= 1e-4 * np.linalg.norm(ref) + 1e-6, (k, err, np.linalg.norm(ref))     # test_gpu_ppo.py's bars
+        n = len(ids)
+        for i, name in enumerate(STATS):
+            tol = 2.0 / n if name == "clip_fraction" else 1e-5 * max(1.0, abs(rs[name]))
+            assert abs(st[i] - rs[name]) <= tol, (k, name, st[i], rs[name])
+    # the critic's gradient is there at all, and two runs are the same bits
+    idx = dev(several.astype(np.int32))[0]
+    g1, s1 = (x.clone() for x in opt.grad(d[0], d[2], d[3], d[4], d[5], index=idx, obs_vf=d[1], agents=agents))
+    opt.grad(d[0], d[2], d[3], d[4], d[5], first=0, n=17, obs_vf=d[1], agents=agents)      # other work in between leaves no trace
+    g2, s2 = opt.grad(d[0], d[2], d[3], d[4], d[5], index=idx, obs_vf=d[1], agents=agents)
+    t = _torch()
+    assert t.equal(g1, g2) and t.equal(s1, s2) and g1[-p.n_out - 1].abs().item() > 0       # (value_net.bias sits before log_std)
+    opt.close(); p.close()
+
+
+def test_shared_entries_with_one_agent_on_one_stream_are_the_plain_ones():
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    pa, sd = make(32, (64, 64), 16, None, (64, 64))
+    pb, _ = make(32, (64, 64), 16, None, (64, 64))
+    oa, ob = PPOOptimizer(pa), PPOOptimizer(pb)
+    sd64 = {k: v.astype(np.float64) for k, v in sd.items()}
+    n = 1000
+    obs, _, raw, lpo, adv, ret = shared_batch(sd64, 32, 32, 16, n, 1, "tanh", seed=2)
+    d = dev(obs, raw, lpo, adv, ret)
+    idx = dev(np.random.default_rng(1).permutation(n)[:777].astype(np.int32))[0]
+    for kw in (dict(index=idx), dict(first=3, n=500), dict(index=idx, normalize_advantage=False)):
+        g0, s0 = (x.clone() for x in oa.grad(*d, ent_coef=0.01, **kw))
+        g1, s1 = oa.grad(*d, ent_coef=0.01, obs_vf=d[0], agents=1, **kw)
+        assert t.equal(g0, g1) and t.equal(s0, s1)
+    E, bs = 2, 300
+    perm = t.stack([t.randperm(n, device="cuda") for _ in range(E)]).to(t.int32).contiguous()
+    sa = oa.update(*d, perm, bs, learning_rate=1e-3, ent_coef=0.01)
+    sb = ob.update(*d, perm, bs, learning_rate=1e-3, ent_coef=0.01, obs_vf=d[0], agents=1)
+    assert t.equal(sa, sb) and t.equal(pa.params, pb.params)
+    # refusals
+    with pytest.raises(ValueError, match="agents"):
+        oa.grad(*d, obs_vf=d[0], agents=3)                                   # 1000 rows are not a multiple of 3
+    with pytest.raises(ValueError, match="obs_vf"):
+        oa.grad(d[0], d[1], d[2], d[3][:500].contiguous(), d[4][:500].contiguous(), agents=2)
+    for o in (oa, ob):
+        o.close()
+    pa.close(); pb.close()
+
+
+def test_update_shared_equals_its_loop():
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    agents, n_env, bs, E = 9, 111, 300, 3                                    # 999 agent rows: minibatches of 300, 300, 300, 99
+    pa, sd = make(13, (64, 64), 1, 31, (64, 32))
+    pb, _ = make(13, (64, 64), 1, 31, (64, 32))
+    oa, ob = PPOOptimizer(pa), PPOOptimizer(pb)
+    obs, obs_vf, raw, lpo, adv, ret = dev(*shared_batch({k: v.astype(np.float64) for k, v in sd.items()}, 13, 31, 1, n_env, agents, "tanh", seed=5))
+    n = n_env * agents
+    perm = t.stack([t.randperm(n, device="cuda") for _ in range(E)]).to(t.int32).contiguous()
+    kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=True, obs_vf=obs_vf, agents=agents)
+    sa = oa.update(obs, raw, lpo, adv, ret, perm, bs, learning_rate=1e-3, max_grad_norm=0.5, **kw)
+    assert tuple(sa.shape) == (E, 4, 8)
+    for e in range(E):
+        for k in range(4):
+            idx = perm[e, k * bs:min(n, (k + 1) * bs)].contiguous()
+            g, st = ob.grad(obs, raw, lpo, adv, ret, index=idx, **kw)
+            assert t.equal(st, sa[e, k]), (e, k)
+            ob.apply(g, learning_rate=1e-3, max_grad_norm=0.5)
+    assert t.equal(pa.params, pb.params) and oa.state()[1] == ob.state()[1] == 12
+    assert t.equal(pa.value(obs_vf), pb.value(obs_vf))                       # the repacked weights too
+    with pytest.raises(ValueError, match="obs_vf"):                          # a split policy has no plain batch
+        oa.update(obs, raw, lpo, adv, ret, perm, bs)
+    for o in (oa, ob):
+        o.close()
+    pa.close(); pb.close()
+
+
+def test_plain_entries_refuse_a_split_policy_through_the_abi():
+    """wg_ppo_grad / wg_ppo_update on a split policy (a wg_ppo_batch has ONE stream, of the actor's width: the critic would gather rows of
+    n_in_vf from it): WG_ERR_INVALID with a message naming the shared entry and both widths, and nothing enqueued — gradient buffer,
+    statistics, parameters and Adam's state are what they were.  The raw entries: PPOOptimizer raises before it reaches them."""
+    from windgym_amd.binding import CPpoBatch, CPpoHyper, _chk
+    from windgym_amd.ppo import PPOOptimizer
+    t = _torch()
+    n_in, n_in_vf, agents, n_env = 2, 18, 9, 40
+    p, sd = make(n_in, (64, 64), 1, n_in_vf, (64, 64))
+    opt = PPOOptimizer(p)
+    obs, obs_vf, raw, lpo, adv, ret = dev(*shared_batch({k: v.astype(np.float64) for k, v in sd.items()}, n_in, n_in_vf, 1, n_env, agents, "tanh"))
+    n = n_env * agents
+    # a batch that obeys wg_ppo_batch's documented shapes: obs [n, n_in], everything else [n]
+    adv_n, ret_n = adv.repeat_interleave(agents).contiguous(), ret.repeat_interleave(agents).contiguous()
+    b = CPpoBatch(obs.data_ptr(), raw.data_ptr(), lpo.data_ptr(), adv_n.data_ptr(), ret_n.data_ptr(), n)
+    hp = CPpoHyper(0.2, 0.5, 0.0, 1)
+    grad, stats = t.full_like(p.params, 7.0), t.full((2, 3, 8), 7.0, device="cuda")
+    perm = t.stack([t.randperm(n, device="cuda") for _ in range(2)]).to(t.int32).contiguous()
+    before, state = p.params.clone(), opt.state()
+    value_before = p.value(obs_vf).clone()
+    with pytest.raises(ValueError, match=rf"wg_ppo_grad: .*rows of {n_in_vf} inputs.*rows of {n_in}.*wg_ppo_grad_shared"):
+        _chk(p.L.wg_ppo_grad(opt._h, p.params.data_ptr(), C.byref(b), None, 0, n, C.byref(hp), grad.data_ptr(), stats.data_ptr(), p._stream()),
+             "wg_ppo_grad")
+    with pytest.raises(ValueError, match=rf"wg_ppo_update: .*rows of {n_in_vf} inputs.*rows of {n_in}.*wg_ppo_update_shared"):
+        _chk(p.L.wg_ppo_update(opt._h, p.params.data_ptr(), C.byref(b), perm.data_ptr(), 2, n // 3, C.byref(hp), 3e-4, 0.5, stats.data_ptr(),
+                               p._stream()), "wg_ppo_update")
+    t.cuda.synchronize()
+    assert bool((grad == 7.0).all()) and bool((stats == 7.0).all()) and t.equal(p.params, before)
+    after = opt.state()
+    assert after[1] == state[1] == 0 and np.array_equal(after[0], state[0])
+    assert t.equal(p.value(obs_vf), value_before)
+    # the same handle, the shared entry, the same buffers with the critic's own stream: accepted
+    g, st = opt.grad(obs, raw, lpo, adv, ret, obs_vf=obs_vf, agents=agents)
+    assert bool(t.isfinite(g).all()) and g.abs().max().item() > 0
+    # an equal-width policy still takes the plain entries (every existing test of them runs this way)
+    q, sq = make(n_in, (64, 64), 1, None, (64, 64))
+    oq = PPOOptimizer(q)
+    gq = t.zeros_like(q.params)
+    _chk(q.L.wg_ppo_grad(oq._h, q.params.data_ptr(), C.byref(b), None, 0, n, C.byref(hp), gq.data_ptr(), None, q._stream()), "wg_ppo_grad")
+    assert gq.abs().max().item() > 0
+    for o in (opt, oq):
+        o.close()
+    p.close(); q.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 5. PPO(critic="central")
+# ----------------------------------------------------------------------------------------------------------------------
+def test_ppo_central_equals_a_twin_of_rollout_gae_update(tmp_path):
+    from windgym_amd.ppo import PPO, PPOOptimizer, sb3_orthogonal_init
+    from windgym_amd.policy import MlpPolicy
+    t = _torch()
+    B, T, seed = 48, 40, 9
+    kw = dict(n_steps=T, n_epochs=2, ent_coef=0.001, seed=11)
+    va, vb = _menv(B, seed), _menv(B, seed)
+    va.reset(seed=seed); vb.reset(seed=seed)
+    N, Om, O = va.n_turb, va.obs_len, va.batch.obs_dim
+    a = PPO("MlpPolicy", va, critic="central", **kw)
+    assert a.central and a.critic == "central" and (a.policy.n_in, a.policy.n_out, a.policy.n_in_vf) == (Om, 1, O)
+    assert a.n_rows == T * B * N and a.batch_size == a.n_rows // 4 and tuple(a._adv.shape) == (T, B)
+    a.learn(2 * T * B)
+    assert a.iteration == 2 and a.num_timesteps == 2 * T * B and len(a.log) == 2
+    for rec in a.log:
+        assert all(np.isfinite(float(x)) for x in rec.values()), rec
+    # the twin: the same policy by hand, then per iteration rollout -> wg_gae on [T, B] -> permutations -> update_shared
+    q = MlpPolicy(Om, 1, (64, 64), (64, 64), "tanh", seed=11, n_in_vf=O)
+    q.load_state_dict(sb3_orthogonal_init(q.desc, 11))
+    opt = PPOOptimizer(q)
+    gen = t.Generator(device="cuda")
+    gen.manual_seed(11)
+    n_trunc = 0
+    for _ in range(2):
+        out = vb.rollout(q, T)
+        n_trunc += int(out["truncated"].sum())
+        adv, ret = opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], 0.99, 0.95)
+        assert tuple(adv.shape) == (T, B)
+        perm = t.stack([t.randperm(T * B * N, generator=gen, device="cuda") for _ in range(2)]).to(t.int32).contiguous()
+        opt.update(out["obs"][:T].view(-1, Om), out["raw"].view(-1, 1), out["logp"].view(-1), adv.view(-1), ret.view(-1), perm, T * B * N // 4,
+                   ent_coef=0.001, obs_vf=out["flat_obs"][:T].view(-1, O), agents=N)
+    assert n_trunc > 0
+    assert t.equal(a.policy.params, q.params)
+    assert a.opt.state()[1] == opt.state()[1] and np.array_equal(a.opt.state()[0], opt.state()[0])
+    opt.close(); q.close()
+    # save / load / continue == the uninterrupted run
+    a.learn(2 * T * B, reset_num_timesteps=False)
+    vc = _menv(B, seed)
+    vc.reset(seed=seed)
+    c = PPO("MlpPolicy", vc, critic="central", **kw)
+    c.learn(2 * T * B)
+    path = os.path.join(tmp_path, "ppo_central.zip")
+    c.save(path)
+    r = PPO.load(path, vc)
+    assert r.central and r.critic == "central" and r.policy.n_in_vf == O and r.policy.desc == c.policy.desc
+    c.close(); c.policy.close()
+    r.learn(2 * T * B, reset_num_timesteps=False)
+    assert r.num_timesteps == a.num_timesteps and r.iteration == 4 and t.equal(r.policy.params, a.policy.params)
+    assert a.opt.state()[1] == r.opt.state()[1] and np.array_equal(a.opt.state()[0], r.opt.state()[0])
+    # the mode is the policy's; what contradicts it, or has nothing to centralise, is a ValueError
+    with pytest.raises(ValueError, match="contradicts"):
+        PPO(r.policy, vc, critic="agent", **kw)
+    per_agent = MlpPolicy(Om, 1, (8,), (8,))
+    with pytest.raises(ValueError, match="contradicts"):
+        PPO(per_agent, vc, critic="central", **kw)
+    with pytest.raises(ValueError, match="nothing to centralise"):
+        PPO("MlpPolicy", vc.venv, critic="central", **kw)
+    with pytest.raises(ValueError, match="critic must be"):
+        PPO("MlpPolicy", vc, critic="global", **kw)
+    b = PPO("MlpPolicy", vc, critic="agent", **kw)                            # today's path under its new name
+    assert not b.central and b.critic == "agent" and tuple(b._adv.shape) == (T, B, N)
+    for x in (a, r, b):
+        x.close(); x.policy.close()
+    per_agent.close()
+    for v in (va, vb, vc):
+        v.close()

@@ -12,7 +12,13 @@ of 200 calls after a synchronisation.  The policy is stable-baselines3's default
   closed_loop_hip_policy    venv.step(policy.act(obs)[0]): one k_policy launch per step
   rollout_hip_policy        venv.rollout(policy, api_steps): the whole loop inside the library, with final_value
 
-usage: python tools/bench_policy.py [--envs 4096] [--api-steps 2000]
+With --multi the workload is cfg4 instead (3x3 farm, one agent per turbine, `presets.multi_3x3_config()`, 2048 envs by default) and
+ONE policy shared by the turbines (obs_len -> 64 -> 64 -> 1), its critic per agent (`--critic agent`: obs_len -> 64 -> 64 -> 1) or
+centralised on the flat observation (`--critic central`: obs_dim -> 64 -> 64 -> 1).  Legs: `vecenv_multi` (step with pre-made
+actions), `loop_hip_policy` (the loop of single calls the rollout is documented as: act, value, step, value of the final rows) and
+`rollout_hip_policy` (WindFarmVecEnvMulti.rollout: the same inside the library).
+
+usage: python tools/bench_policy.py [--envs 4096] [--api-steps 2000] [--multi [--critic agent|central]]
 """
 import argparse
 import json
@@ -25,13 +31,83 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def multi(args):
+    """--multi: cfg4, one policy shared by the turbines, per-agent or centralised critic"""
+    import torch
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnvMulti
+    from windgym_amd.policy import MlpPolicy
+    from windgym_amd.turbine import V80
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    B, steps = args.envs or 2048, args.api_steps
+    menv = WindFarmVecEnvMulti(V80(), B, yaml_dict=presets.multi_3x3_config(), seed=1234, device=0, turbtype="None", n_passthrough=5,
+                               n_rotor_pts=16)
+    obs = menv.reset(seed=1234)
+    N, Om, O = menv.n_turb, menv.obs_len, menv.batch.obs_dim
+    central = args.critic == "central"
+    policy = MlpPolicy(Om, 1, (64, 64), (64, 64), "tanh", device=0, seed=1234, n_in_vf=O if central else None)
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    acts = list((torch.rand((16, B, N), generator=gen) * 2 - 1).to(dev).contiguous())
+    for i in range(args.preroll):
+        menv.step(acts[i % 16])
+
+    def timed(fn):
+        for i in range(50):
+            fn(i)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i in range(steps):
+            fn(i)
+        torch.cuda.synchronize(dev)
+        el = time.perf_counter() - t0
+        return {"value": B * steps / el, "unit": "env-steps/s", "ms_per_step": el / steps * 1e3}
+
+    flat, flat_fin = menv.batch.obs, menv.batch.final_obs
+    vbuf, fvbuf = (torch.zeros(B if central else B * N, device=dev) for _ in range(2))
+
+    def loop_step(i):
+        a = policy.act(obs)[0]
+        if central:
+            policy.value(flat, out=vbuf)
+        fin = menv.step(a.view(B, N))[4]
+        policy.value(flat_fin if central else fin, out=fvbuf)
+
+    out = {"metric": "env-steps/s with ONE learned policy shared by the turbines, 3x3 farm x %d envs (%d agent rows), one GPU" % (B, B * N),
+           "envs": B, "steps": steps, "critic": args.critic}
+    out["vecenv_multi"] = timed(lambda i: menv.step(acts[i % 16]))
+    out["loop_hip_policy"] = timed(loop_step)
+    menv.rollout(policy, steps)                      # warm-up: allocates the buffers for this T
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    menv.rollout(policy, steps)
+    torch.cuda.synchronize(dev)
+    el = time.perf_counter() - t0
+    out["rollout_hip_policy"] = {"value": B * steps / el, "unit": "env-steps/s", "ms_per_step": el / steps * 1e3}
+    out["policy"] = {"n_in": Om, "n_out": 1, "n_in_vf": policy.n_in_vf, "hidden_pi": [64, 64], "hidden_vf": [64, 64], "activation": "tanh"}
+    for k in ("loop_hip_policy", "rollout_hip_policy"):
+        out[k]["frac_of_vecenv_multi"] = out[k]["value"] / out["vecenv_multi"]["value"]
+    out["rollout_hip_policy"]["speedup_vs_loop"] = out["rollout_hip_policy"]["value"] / out["loop_hip_policy"]["value"]
+    menv.batch.check()
+    policy.close()
+    menv.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--envs", type=int, default=None, help="default: 4096 (--multi: 2048)")
+    ap.add_argument("--multi", action="store_true", help="cfg4: one policy shared by the turbines of a 3x3 farm")
+    ap.add_argument("--critic", choices=("agent", "central"), default="agent", help="with --multi: what the critic reads")
     ap.add_argument("--api-steps", type=int, default=2000, help="timed steps of each leg")
     ap.add_argument("--preroll", type=int, default=300, help="untimed steps that take the batch out of its synchronised start")
     args = ap.parse_args()
     import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_policy.py: no HIP device (there is no CPU path to time)")
+    if args.multi:
+        return multi(args)
+    args.envs = args.envs or 4096
     from windgym_amd import binding, presets
     from windgym_amd.config import EnvConfig
     from windgym_amd.envs import WindFarmVecEnv

@@ -13,7 +13,13 @@ Every leg is warmed up once, then timed `--reps` times between two device synchr
                      env-steps/s collected AND trained on for `epochs` epochs), with the share of an iteration spent collecting.
 
 <mb> = minibatch rows, `--minibatches` (default 4096 and a quarter of the rollout).
-usage: python tools/bench_ppo.py [--envs 4096] [--n-steps 128] [--epochs 10] [--reps 5]
+
+With --multi the workload is cfg4 instead (3x3 farm, one agent per turbine, `presets.multi_3x3_config()`, 2048 envs by default), ONE
+policy shared by the turbines and rows = AGENT rows (envs x steps x 9).  `--critic agent`: each agent's critic on its own observation
+(wg_gae_shared + wg_ppo_update); `--critic central`: one critic per env on the flat observation (wg_gae on [T, B] +
+wg_ppo_update_shared; the eager-torch leg gathers the env row of every minibatch entry the same way).
+
+usage: python tools/bench_ppo.py [--envs 4096] [--n-steps 128] [--epochs 10] [--reps 5] [--multi [--critic agent|central]]
 """
 import argparse
 import json
@@ -31,7 +37,9 @@ HALF_LOG_2PI = 0.9189385332046727
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--envs", type=int, default=None, help="default: 4096 (--multi: 2048)")
+    ap.add_argument("--multi", action="store_true", help="cfg4: one policy shared by the turbines of a 3x3 farm")
+    ap.add_argument("--critic", choices=("agent", "central"), default="agent", help="with --multi: what the critic reads")
     ap.add_argument("--n-steps", type=int, default=128)
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
@@ -41,20 +49,26 @@ def main():
     args = ap.parse_args()
     import torch
     from windgym_amd import presets
-    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.envs import WindFarmVecEnv, WindFarmVecEnvMulti
     from windgym_amd.ppo import PPO
     from windgym_amd.turbine import V80
     if not torch.cuda.is_available():
         sys.exit("bench_ppo.py: no HIP device (there is no CPU path to time)")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    B, T, E = args.envs, args.n_steps, args.epochs
-    n_rows = B * T
+    B, T, E = args.envs or (2048 if args.multi else 4096), args.n_steps, args.epochs
+    central = args.multi and args.critic == "central"
+    if args.multi:
+        venv = WindFarmVecEnvMulti(V80(), B, yaml_dict=presets.multi_3x3_config(), seed=1234, device=0, turbtype="None", n_passthrough=5,
+                                   n_rotor_pts=16)
+    else:
+        venv = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
+                              n_passthrough=5, n_rotor_pts=16)
+    A = venv.n_turb if args.multi else 1                    # agent rows per env step
+    n_rows = B * T * A
     mbs = args.minibatches or sorted({min(4096, n_rows), max(1, n_rows // 4)})
-    venv = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
-                          n_passthrough=5, n_rotor_pts=16)
     venv.reset(seed=1234)
-    ppo = PPO("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=mbs[0], seed=1234)
+    ppo = PPO("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=mbs[0], seed=1234, critic=args.critic if args.multi else None)
     pol = ppo.policy
     zero = torch.zeros((B, venv.n_turb), device=dev)
     for _ in range(args.preroll):
@@ -71,15 +85,21 @@ def main():
             ts.append(time.perf_counter() - t0)
         return statistics.median(ts), ts
 
-    out = {"metric": "PPO on the device, 16-turbine farm x %d envs x %d steps, %d epochs, one GPU" % (B, T, E),
+    out = {"metric": "PPO on the device, %s x %d envs x %d steps, %d epochs, one GPU"
+                     % ("3x3 farm, one policy shared by 9 agents, critic per %s" % ("env (central)" if central else "agent") if args.multi
+                        else "16-turbine farm", B, T, E),
            "envs": B, "n_steps": T, "epochs": E, "rows": n_rows, "minibatches": mbs}
+    if args.multi:
+        out["critic"] = args.critic
     el, ts = timed(ppo.collect, args.reps)
-    out["rollout"] = {"value": n_rows / el, "unit": "env-steps/s", "ms": el * 1e3, "ms_all": [round(x * 1e3, 3) for x in ts]}
+    out["rollout"] = {"value": B * T / el, "unit": "env-steps/s", "ms": el * 1e3, "ms_all": [round(x * 1e3, 3) for x in ts]}
     roll = ppo.collect()
     torch.cuda.synchronize(dev)
     O, N = pol.n_in, pol.n_out
     obs, raw, lpo = roll["obs"][:T].reshape(-1, O), roll["raw"].reshape(-1, N), roll["logp"].reshape(-1)
     adv, ret = ppo._adv.reshape(-1), ppo._ret.reshape(-1)
+    obs_vf = roll["flat_obs"][:T].reshape(-1, pol.n_in_vf) if central else None     # [T * B, O]: the env rows the critic reads
+    shared = dict(obs_vf=obs_vf, agents=A) if central else {}
     perm = torch.stack([torch.randperm(n_rows, device=dev) for _ in range(E)]).to(torch.int32).contiguous()
     start = pol.params.clone()
 
@@ -91,14 +111,19 @@ def main():
             for e in range(E):
                 for s in range(0, n_rows, bs):
                     i = perm[e, s:s + bs].long()
-                    mean, V = pol.torch_forward(obs[i])
+                    if central:                          # entry i is an agent row of env row i // A
+                        r = i // A
+                        mean, V = pol.torch_forward(obs[i], obs_vf[r])
+                        adv_i, ret_i = adv[r], ret[r]
+                    else:
+                        mean, V = pol.torch_forward(obs[i])
+                        adv_i, ret_i = adv[i], ret[i]
                     ls = w[-N:]
                     z = (raw[i] - mean) / ls.exp()
                     logp = (-0.5 * z * z - ls - HALF_LOG_2PI).sum(1)
                     ratio = (logp - lpo[i]).exp()
-                    A = adv[i]
-                    A = (A - A.mean()) / (A.std() + 1e-8)
-                    loss = -torch.min(ratio * A, ratio.clamp(0.8, 1.2) * A).mean() + 0.5 * ((ret[i] - V) ** 2).mean()
+                    An = (adv_i - adv_i.mean()) / (adv_i.std() + 1e-8)
+                    loss = -torch.min(ratio * An, ratio.clamp(0.8, 1.2) * An).mean() + 0.5 * ((ret_i - V) ** 2).mean()
                     opt.zero_grad()
                     loss.backward()
                     torch.nn.utils.clip_grad_norm_([w], 0.5)
@@ -111,7 +136,7 @@ def main():
             pol.params.copy_(start)
         pol.sync()
         ppo.opt.load_state(torch.zeros(2 * start.numel()).numpy(), 0)
-        ppo.opt.update(obs, raw, lpo, adv, ret, perm, bs, learning_rate=3e-4, max_grad_norm=0.5)
+        ppo.opt.update(obs, raw, lpo, adv, ret, perm, bs, learning_rate=3e-4, max_grad_norm=0.5, **shared)
 
     for bs in mbs:
         el, ts = timed(lambda: update_torch(bs), args.torch_reps)
@@ -125,7 +150,7 @@ def main():
         pol.params.copy_(start)
     pol.sync()
     iters = 3
-    el, ts = timed(lambda: ppo.learn(iters * n_rows, log_interval=None), args.reps)
+    el, ts = timed(lambda: ppo.learn(iters * B * T, log_interval=None), args.reps)
     per_iter = el / iters
     out["learn_hip"] = {"value": n_rows / per_iter, "unit": "trained samples/s", "ms_per_iteration": per_iter * 1e3,
                         "minibatch": mbs[0], "collect_share": out["rollout"]["ms"] / (per_iter * 1e3),

@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
     "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
     "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
+    "wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared",
 )
 
 _lib = None
@@ -72,6 +73,11 @@ class CPpoBatch(C.Structure):
     """wg_ppo_batch"""
     _fields_ = [("obs", C.c_void_p), ("raw", C.c_void_p), ("logp", C.c_void_p), ("advantage", C.c_void_p),
                 ("returns", C.c_void_p), ("n_rows", C.c_int64)]
+
+
+class CPpoBatchShared(C.Structure):
+    """wg_ppo_batch_shared"""
+    _fields_ = [("rows", CPpoBatch), ("obs_vf", C.c_void_p), ("agents", C.c_int32)]
 
 
 class CPpoHyper(C.Structure):
@@ -140,6 +146,7 @@ def load_library():
     L.wg_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.wg_flow_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.wg_policy_create.argtypes = [C.POINTER(CPolicyDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_policy_create_vf.argtypes = [C.POINTER(CPolicyDesc), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
     L.wg_policy_destroy.argtypes = [C.c_void_p]
     L.wg_policy_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     L.wg_policy_n_params.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
@@ -163,6 +170,8 @@ def load_library():
     L.wg_ppo_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     L.wg_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int, C.c_int,
                                 C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.wg_ppo_grad_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_grad.argtypes[3:]
+    L.wg_ppo_update_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_update.argtypes[3:]
     _lib = L
     return L
 

@@ -827,14 +827,19 @@ static size_t info_bytes(const wg_env_s* h, int field) {
 }
 
 // The closed loop policy -> step -> record (windgym_hip.h: wg_rollout, wg_rollout_multi) exists once; this is what differs
-// between the two entries.
+// between the two entries and, for wg_rollout_multi, between its per-agent and its central mode.
 struct RolloutRows {
     const char *who, *obs_name;    // prefix of every message; the buffer the policy reads, as the messages name it
     int per_env, n_in, n_out;      // policy rows per env; the shape the policy must have ...
     std::string needs;             // ... and the end of the message that says so
     const char* unready;           // non-null: refused with this message
     bool per_agent;                // the steps write the policy's rows through WgPtrs::multi_out / multi_fin, re-aimed per step
-    wg_rollout_multi_bufs o;       // obs_multi / final_obs_multi: what the policy reads; obs / final_obs: the steps' flat rows
+    wg_rollout_multi_bufs o;       // obs_multi / final_obs_multi: what the ACTOR reads; obs / final_obs: the steps' flat rows
+    // what the CRITIC reads: v_env rows per env of v_in inputs, slots [T+1] of v_obs and [T] of v_fin (null: no final rows given,
+    // named fin_name in the refusal) — the actor's own rows, or the flat rows under a centralised critic
+    int v_env, v_in;
+    const float *v_obs, *v_fin;
+    const char* fin_name;
 };
 
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
@@ -844,10 +849,12 @@ static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, i
     if (!o.obs_multi || !o.actions || !o.reward || !o.truncated)
         return fail(WG_ERR_INVALID, who + g.obs_name + ", actions, reward and truncated buffers are required");
     if (p->device != h->device) return fail(WG_ERR_INVALID, who + "policy and handle live on different devices");
-    if (p->P.n_in != g.n_in || p->P.n_out != g.n_out)
-        return fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) + g.needs);
+    if (p->P.n_in != g.n_in || p->P.n_out != g.n_out || (p->P.n_layers[1] != 0 && p->P.n_in_vf != g.v_in))
+        return fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
+                                        (p->P.n_in_vf != p->P.n_in ? " (its critic reads " + std::to_string(p->P.n_in_vf) + " inputs)" : std::string()) + g.needs);
     if (g.unready) return fail(WG_ERR_INVALID, who + g.unready);
-    if (o.final_value && !o.final_obs_multi) return fail(WG_ERR_INVALID, who + "final_value needs final_" + g.obs_name);
+    if (!g.v_obs) return fail(WG_ERR_INVALID, who + "a centralised critic reads the flat observation: obs is required (slot 0 is input)");
+    if (o.final_value && !g.v_fin) return fail(WG_ERR_INVALID, who + "final_value needs " + g.fin_name);
     if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
     if (!p->P.has_log_std && (!deterministic || o.logp))
         return fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
@@ -866,19 +873,22 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
                         uint64_t row_offset, const RolloutRows& g, void* stream) {
     const wg_rollout_multi_bufs& o = g.o;
     hipStream_t st = (hipStream_t)stream;
-    const int B = h->p.B, R = B * g.per_env;
+    const int B = h->p.B, R = B * g.per_env, V = B * g.v_env;
     const size_t sBO = (size_t)B * h->p.obs_dim, sR = (size_t)R, sRO = sR * g.n_in, sRN = sR * g.n_out;
+    const size_t sV = (size_t)V, sVO = sV * g.v_in;
     float* const multi0 = h->d.multi_out;
     float* const fin0 = h->d.multi_fin;
     int rc = 0;
-    // final_value[t - 1] = V(final rows of step t - 1) is computed by the launch that computes step t's actions (one more slot
-    // of k_policy's grid: a row's value does not depend on what else the launch computes), the last one by a launch of its own
+    // ONE launch of k_policy per step: the actor on step t's rows and, as further slots, the critic on its rows of step t and
+    // final_value[t - 1] = V(final rows of step t - 1) (a row's value does not depend on what else the launch computes); the last
+    // final_value by a launch of its own
     for (int t = 0; t < n_steps && !rc; ++t) {
-        const bool fv = o.final_value && t > 0;
-        rc = wg_policy_act2_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
-                             o.actions + t * sRN, o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr,
-                             o.value ? o.value + t * sR : nullptr, fv ? o.final_obs_multi + (t - 1) * sRO : nullptr,
-                             fv ? o.final_value + (t - 1) * sR : nullptr, stream);
+        WgValueRows v[2];
+        int nv = 0;
+        if (o.value) v[nv++] = {g.v_obs + t * sVO, o.value + t * sV, V};
+        if (o.final_value && t > 0) v[nv++] = {g.v_fin + (t - 1) * sVO, o.final_value + (t - 1) * sV, V};
+        rc = wg_policy_eval_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
+                             o.actions + t * sRN, o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
         if (rc) break;
         if (g.per_agent) {
             h->d.multi_out = o.obs_multi + (t + 1) * sRO;
@@ -894,9 +904,10 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     }
     h->d.multi_out = multi0;      // the handle's own per-agent buffers again, on every way out (the device copies never changed)
     h->d.multi_fin = fin0;
-    if (!rc && o.final_value && n_steps > 0)
-        rc = wg_policy_act(p, R, o.final_obs_multi + (n_steps - 1) * sRO, 1, 0, 0, 0, nullptr, nullptr, nullptr,
-                           o.final_value + (n_steps - 1) * sR, stream);
+    if (!rc && o.final_value && n_steps > 0) {
+        const WgValueRows v = {g.v_fin + (n_steps - 1) * sVO, o.final_value + (n_steps - 1) * sV, V};
+        rc = wg_policy_eval_(p, 0, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, &v, 1, stream);
+    }
     return rc;
 }
 
@@ -908,7 +919,8 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
     const RolloutRows g = {"wg_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
                            nullptr, false,
                            {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
-                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out}};
+                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
+                           1, O, o->obs, o->final_obs, "final_obs"};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = use_device(h)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
@@ -917,11 +929,17 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
 extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                 uint64_t row_offset, const wg_rollout_multi_bufs* o, void* stream) {
     if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout_multi: null argument");
-    const int B = h->p.B, N = h->p.N, Om = h->p.obs_dim_multi;
+    const int B = h->p.B, N = h->p.N, O = h->p.obs_dim, Om = h->p.obs_dim_multi;
+    // central mode: the policy's critic has the flat observation's width (and not the actor's): it reads the steps' flat rows
+    const bool central = p->P.n_layers[1] != 0 && p->P.n_in_vf != p->P.n_in && p->P.n_in_vf == O;
     const RolloutRows g = {"wg_rollout_multi", "obs_multi", N, Om, 1,
-                           ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) + " -> 1",
+                           ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) +
+                               " -> 1, its critic on the same " + std::to_string(Om) + " inputs (one value per agent) or on obs_dim = " +
+                               std::to_string(O) + " (a centralised critic: wg_policy_create_vf)",
                            h->d.multi_out ? nullptr : "register a per-agent buffer first (wg_set_obs_multi_buffer); obs_multi[0] is what it held",
-                           true, *o};
+                           true, *o,
+                           central ? 1 : N, central ? O : Om, central ? o->obs : o->obs_multi, central ? o->final_obs : o->final_obs_multi,
+                           central ? "final_obs (a centralised critic reads the flat rows)" : "final_obs_multi"};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if ((long long)B * N > 0x7fffffffLL) return fail(WG_ERR_UNSUPPORTED, "wg_rollout_multi: more than 2^31 agent rows");
     if (int rc = use_device(h)) return rc;

@@ -11,14 +11,19 @@ struct FlowP;
 struct FlowPtrs;
 struct WgParams;
 struct WgPtrs;
+struct WgValueRows {           // the critic on n_rows rows: obs [n_rows][critic's input width] -> value [n_rows]
+    const float* obs;
+    float* value;
+    int n_rows;
+};
 
 extern "C" {
 // wg_api.hip: the thread-local message behind wg_last_error; returns `code`
 int wg_set_last_error_(int code, const char* msg);
-// wg_policy.hip: wg_policy_act + optionally the critic on a second set of n_rows rows (obs2_dev -> value2_dev) in the same launch
-int wg_policy_act2_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
-                    float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, const float* obs2_dev, float* value2_dev,
-                    void* stream);
+// wg_policy.hip: ONE launch of k_policy — the actor on n_rows rows of obs_dev (when action / raw / logp is wanted) and the critic on
+// each of n_v <= 2 row sets of its own (rows of the critic's input width -> value); a set of no rows is skipped
+int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
+                    float* action_dev, float* raw_dev, float* logp_dev, const WgValueRows* v, int n_v, void* stream);
 // wg_flow.hip
 void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
 void wg_launch_windspeed(const FlowP* p, const FlowPtrs* d, int e, int farm, const float* xs, int nx, const float* ys, int ny, float z,

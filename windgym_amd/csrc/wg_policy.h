@@ -1,8 +1,9 @@
 // wg_policy.h — parameter block of k_policy (wg_policy.hip) and the host object behind the `wg_policy` handle.
 //
 // A policy is up to two independent MLPs ("nets"): 0 = actor (n_in -> hidden_pi... -> n_out), 1 = critic
-// (n_in -> hidden_vf... -> 1).  Layer l of a net maps K inputs to M outputs; PyTorch's Linear.weight orientation
-// W[M][K] in the caller's flat vector.
+// (n_in_vf -> hidden_vf... -> 1; n_in_vf = n_in unless the policy was built by wg_policy_create_vf: a "split" policy, whose
+// critic reads other rows than its actor).  Layer l of a net maps K inputs to M outputs; PyTorch's Linear.weight orientation
+// W[M][K] in the caller's flat vector.  A net's input width — the stride of the rows it reads — is its first layer's K.
 //
 // FLAT parameter vector (what wg_policy_set_params takes; windgym_amd/policy.py and oracle/policy_oracle.py restate it):
 //     actor hidden layers in order, each W [M][K] row-major then b [M]; actor head W [n_out][K], b [n_out];
@@ -32,6 +33,7 @@
 #define WGP_MAX_OUT 128
 #define WGP_MAX_WIDTH 256
 #define WGP_NOISE_TAG 0x50000000u
+#define WGP_MAX_SLOTS 3      // row sets of one k_policy launch: the actor's, the critic's, the critic's on a second set
 
 struct WgPolicyLayer {
     int32_t K, M;              // inputs, outputs
@@ -42,10 +44,20 @@ struct WgPolicyLayer {
 
 struct WgPolicyP {
     int32_t n_in, n_out, activation, has_log_std;
+    int32_t n_in_vf;           // the critic's input width (= layer[1][0].K; n_in where there is no critic)
     int32_t n_layers[2];       // per net, head included; 0 = the net does not exist
     WgPolicyLayer layer[2][WGP_MAX_LAYERS];
     uint32_t log_std_flat, log_std_packed;
     uint32_t n_flat, n_packed;
+};
+
+// One launch of k_policy = up to WGP_MAX_SLOTS slots, each ONE net on its own rows: slot s owns the workgroups
+// [end[s - 1], end[s]) of a 1-D grid (end[-1] = 0), ceil(n_rows[s] / 32) of them, so no workgroup is launched past a slot's rows.
+// Only the actor has outputs besides `value`, and a launch holds at most one actor slot: those pointers are kernel arguments.
+struct WgPolicySlots {
+    const float* obs[WGP_MAX_SLOTS];     // [n_rows][the net's input width]
+    float* value[WGP_MAX_SLOTS];         // [n_rows] (critic slots)
+    int32_t n_rows[WGP_MAX_SLOTS], net[WGP_MAX_SLOTS], end[WGP_MAX_SLOTS];
 };
 
 struct wg_policy_s {

@@ -2,7 +2,7 @@
 // (what `model.predict(obs, deterministic=...)` of a stable-baselines3 MlpPolicy computes, WindGym/AgentEval.py:179-190),
 // k_policy_pack builds the kernel's weight layout, and the wg_policy_* entries of include/windgym_hip.h wrap them.
 //
-// k_policy: one workgroup of 4 waves owns 32 observation rows of ONE net (blockIdx.y: actor / critic).  A layer is
+// k_policy: one workgroup of 4 waves owns 32 observation rows of ONE net (a launch is up to three slots of (net, rows)).  A layer is
 // D[neuron][row] = sum_k W[neuron][k] X[k][row] on v_mfma_f32_32x32x2_f32 — an exact k-ordered f32 fmaf chain, so a row's
 // outputs depend on nothing but that row and the weights (bitwise: no atomics, no cross-row reduction, fixed order).
 // X lives in LDS as [k][32 rows] (B operand: one conflict-free ds_read per k-step), the weights come packed from L2 as the A
@@ -51,19 +51,22 @@ __device__ inline float wgp_noise(uint64_t seed, uint64_t counter, uint64_t g, i
 }
 
 __global__ __launch_bounds__(WGP_WAVES * 64) void k_policy(const WgPolicyP P, const float* __restrict__ packed,
-                                                           const float* __restrict__ obs, const int n_rows,
-                                                           const int deterministic, const uint64_t seed, const uint64_t counter,
-                                                           const uint64_t row_offset, float* __restrict__ action,
-                                                           float* __restrict__ raw, float* __restrict__ logp,
-                                                           float* __restrict__ value, const int net0,
-                                                           const float* __restrict__ obs2, float* __restrict__ value2) {
+                                                           const WgPolicySlots S, const int deterministic, const uint64_t seed,
+                                                           const uint64_t counter, const uint64_t row_offset,
+                                                           float* __restrict__ action, float* __restrict__ raw,
+                                                           float* __restrict__ logp) {
     __shared__ float lds[2][WGP_KC * WGP_TILE];
-    // blockIdx.y: the requested nets on `obs`; with obs2, one more slot = the critic on a SECOND set of rows -> value2
-    // (wg_rollout: the value of step t - 1's final observations rides in the launch that computes step t's actions)
-    int net = net0 + blockIdx.y;
-    if (obs2 != nullptr && blockIdx.y == gridDim.y - 1) { net = 1; obs = obs2; value = value2; }
+    // blockIdx.x -> (slot, tile of 32 rows): slot s owns the workgroups [end[s - 1], end[s]) (wg_policy.h: WgPolicySlots; an unused
+    // slot has end[s] = end[s - 1]).  A 1-D grid of exactly the tiles each slot has: the slots of the closed loop differ by a factor
+    // n_turb in rows (the actor on B * N agent rows, the critic on B env rows, wg_rollout_multi's central mode), so a 2-D grid
+    // (tiles of the largest slot) x slots would launch mostly workgroups that have nothing to do.
+    const int bid = blockIdx.x;
+    const int slot = (bid >= S.end[0] ? 1 : 0) + (bid >= S.end[1] ? 1 : 0);
+    const int net = S.net[slot], n_rows = S.n_rows[slot];
+    const float* __restrict__ obs = S.obs[slot];
+    float* __restrict__ value = S.value[slot];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int row0 = blockIdx.x * WGP_TILE;
+    const int row0 = (bid - (slot ? S.end[slot - 1] : 0)) * WGP_TILE;
     const int L = P.n_layers[net];
     int cur = 0;                                  // LDS buffer that holds the running layer's input
     for (int l = 0; l < L; ++l) {
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_policy(const WgPolicyP P, co
                 // cache lines are re-used from L1 by the following passes).  Rows past n_rows and the pad up to whole k-groups read as 0.
                 __syncthreads();
                 const int row = row0 + r;
-                const float* orow = obs + (size_t)row * P.n_in + k0;
+                const float* orow = obs + (size_t)row * ly.K + k0;      // (a net's row stride is its first layer's K)
                 for (int k = tid >> 5; k < kcp; k += WGP_WAVES * 2)
                     lds[0][k * WGP_TILE + r] = (row < n_rows && k < kc) ? orow[k] : 0.0f;
                 __syncthreads();
@@ -217,7 +220,7 @@ static int p_use_device(wg_policy_s* p) {
     return 0;
 }
 
-extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* out) {
+extern "C" int wg_policy_create_vf(const wg_policy_desc* d, int32_t n_in_vf, int device, wg_policy* out) {
     if (!d || !out) return pfail(WG_ERR_INVALID, "wg_policy_create: null argument");
     *out = nullptr;
     if (d->n_in < 1 || d->n_out < 1) return pfail(WG_ERR_INVALID, "wg_policy_create: n_in and n_out must be >= 1");
@@ -225,6 +228,10 @@ extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* 
     if (d->n_out > WGP_MAX_OUT) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_out = " + std::to_string(d->n_out) + " > " + std::to_string(WGP_MAX_OUT));
     if (d->activation != WG_ACTV_TANH && d->activation != WG_ACTV_RELU) return pfail(WG_ERR_INVALID, "wg_policy_create: unknown activation");
     if (d->n_hidden_pi < 0) return pfail(WG_ERR_INVALID, "wg_policy_create: n_hidden_pi < 0");
+    if (d->n_hidden_vf < 0 && n_in_vf != d->n_in)
+        return pfail(WG_ERR_INVALID, "wg_policy_create_vf: n_in_vf is the input width of the critic, and this policy has none (n_hidden_vf < 0)");
+    if (n_in_vf < 1) return pfail(WG_ERR_INVALID, "wg_policy_create_vf: n_in_vf must be >= 1");
+    if (n_in_vf > WGP_MAX_IN) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create_vf: n_in_vf = " + std::to_string(n_in_vf) + " > " + std::to_string(WGP_MAX_IN));
     const int nh[2] = {d->n_hidden_pi, d->n_hidden_vf};
     const int32_t* hid[2] = {d->hidden_pi, d->hidden_vf};
     for (int net = 0; net < 2; ++net) {
@@ -240,11 +247,12 @@ extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* 
     if (!p) return pfail(WG_ERR_NOMEM, "wg_policy_create: out of host memory");
     WgPolicyP& P = p->P;
     P.n_in = d->n_in; P.n_out = d->n_out; P.activation = d->activation; P.has_log_std = d->has_log_std != 0;
+    P.n_in_vf = n_in_vf;
     uint32_t flat = 0, packed = 0;
     for (int net = 0; net < 2; ++net) {
         if (nh[net] < 0) { P.n_layers[net] = 0; continue; }        // (critic only: n_hidden_vf < 0 = none)
         P.n_layers[net] = nh[net] + 1;
-        int K = d->n_in;
+        int K = net == 0 ? d->n_in : n_in_vf;
         for (int l = 0; l <= nh[net]; ++l) {
             WgPolicyLayer& ly = P.layer[net][l];
             ly.K = K;
@@ -275,6 +283,11 @@ extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* 
     }
     *out = p;
     return 0;
+}
+
+extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* out) {
+    if (!d || !out) return pfail(WG_ERR_INVALID, "wg_policy_create: null argument");
+    return wg_policy_create_vf(d, d->n_in, device, out);
 }
 
 extern "C" int wg_policy_destroy(wg_policy p) {
@@ -310,22 +323,34 @@ extern "C" int wg_policy_set_params(wg_policy p, const float* params, size_t n, 
     return 0;
 }
 
-// wg_policy_act + optionally the critic on a second set of n_rows rows (obs2_dev -> value2_dev) in the same launch
-extern "C" int wg_policy_act2_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
-                               uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev,
-                               const float* obs2_dev, float* value2_dev, void* stream) {
-    if (!p || !obs_dev) return pfail(WG_ERR_INVALID, "wg_policy_act: null argument");
-    if (n_rows < 0) return pfail(WG_ERR_INVALID, "wg_policy_act: n_rows < 0");
-    const bool actor = action_dev || raw_dev || logp_dev, critic = value_dev != nullptr;
-    if (!obs2_dev || !value2_dev) obs2_dev = nullptr, value2_dev = nullptr;
-    if ((critic || obs2_dev) && p->P.n_layers[1] == 0) return pfail(WG_ERR_INVALID, "wg_policy_act: value requested from a policy without a critic");
+// One launch of k_policy: the actor on n_rows rows of n_in (when one of its outputs is wanted) and the critic on each of the
+// n_v <= 2 row sets of v (rows of n_in_vf).  What wg_policy_act checks about the policy is checked here.
+extern "C" int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
+                               uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, const WgValueRows* v, int n_v,
+                               void* stream) {
+    if (!p) return pfail(WG_ERR_INVALID, "wg_policy_act: null argument");
+    if (n_v < 0 || n_v > WGP_MAX_SLOTS - 1 || (n_v > 0 && !v))
+        return pfail(WG_ERR_INVALID, "wg_policy_act: a launch takes at most " + std::to_string(WGP_MAX_SLOTS - 1) + " row sets for the critic");
+    const bool actor = action_dev || raw_dev || logp_dev;
+    if (n_v > 0 && p->P.n_layers[1] == 0) return pfail(WG_ERR_INVALID, "wg_policy_act: value requested from a policy without a critic");
     if (actor && !p->P.has_log_std && (!deterministic || logp_dev))
         return pfail(WG_ERR_INVALID, "wg_policy_act: a stochastic action / a log-probability needs a policy with log_std");
-    if (n_rows == 0 || (!actor && !critic && !obs2_dev)) return 0;
+    WgPolicySlots S = {};
+    int ns = 0, end = 0;
+    if (actor && n_rows > 0) {
+        S.obs[ns] = obs_dev; S.n_rows[ns] = n_rows; S.net[ns] = 0;
+        S.end[ns++] = end += (n_rows + WGP_TILE - 1) / WGP_TILE;
+    }
+    for (int i = 0; i < n_v; ++i) {
+        if (v[i].n_rows <= 0) continue;
+        S.obs[ns] = v[i].obs; S.value[ns] = v[i].value; S.n_rows[ns] = v[i].n_rows; S.net[ns] = 1;
+        S.end[ns++] = end += (v[i].n_rows + WGP_TILE - 1) / WGP_TILE;
+    }
+    if (ns == 0) return 0;
+    for (int i = ns; i < WGP_MAX_SLOTS; ++i) S.end[i] = end;
     if (int rc = p_use_device(p)) return rc;
-    const dim3 grid((n_rows + WGP_TILE - 1) / WGP_TILE, (actor ? 1 : 0) + (critic ? 1 : 0) + (obs2_dev ? 1 : 0));
-    hipLaunchKernelGGL(k_policy, grid, dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, p->P, p->packed, obs_dev, n_rows,
-                       deterministic ? 1 : 0, seed, counter, row_offset, action_dev, raw_dev, logp_dev, value_dev, actor ? 0 : 1, obs2_dev, value2_dev);
+    hipLaunchKernelGGL(k_policy, dim3(end), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, p->P, p->packed, S, deterministic ? 1 : 0,
+                       seed, counter, row_offset, action_dev, raw_dev, logp_dev);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return pfail(WG_ERR_HIP, std::string("wg_policy_act: kernel launch failed: ") + hipGetErrorString(le));
     return 0;
@@ -334,6 +359,13 @@ extern "C" int wg_policy_act2_(wg_policy p, int n_rows, const float* obs_dev, in
 extern "C" int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
                              uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev,
                              void* stream) {
-    return wg_policy_act2_(p, n_rows, obs_dev, deterministic, seed, counter, row_offset, action_dev, raw_dev, logp_dev, value_dev,
-                           nullptr, nullptr, stream);
+    if (!p || !obs_dev) return pfail(WG_ERR_INVALID, "wg_policy_act: null argument");
+    if (n_rows < 0) return pfail(WG_ERR_INVALID, "wg_policy_act: n_rows < 0");
+    if (value_dev && (action_dev || raw_dev || logp_dev) && p->P.n_layers[1] != 0 && p->P.n_in_vf != p->P.n_in)
+        return pfail(WG_ERR_INVALID, "wg_policy_act: the actor of this policy reads rows of " + std::to_string(p->P.n_in) +
+                                         " inputs and its critic rows of " + std::to_string(p->P.n_in_vf) +
+                                         ", so one obs_dev cannot serve both: ask for the value in a call of its own");
+    const WgValueRows v = {obs_dev, value_dev, n_rows};
+    return wg_policy_eval_(p, n_rows, obs_dev, deterministic, seed, counter, row_offset, action_dev, raw_dev, logp_dev, &v,
+                           value_dev ? 1 : 0, stream);
 }

@@ -1,7 +1,7 @@
 // wg_ppo.h — the host object behind the `wg_ppo` handle and the constants of the training kernels (wg_ppo.hip).
 //
 // k_ppo_grad works on tiles of R rows (R = 32 when a net's activations fit the workgroup's LDS, else 16, 8, 4 or 2: a
-// function of the architecture alone).  Minibatch rows 0 .. n-1 form ceil(n / R) tiles; G = min(tiles, g_max) workgroups
+// function of the architecture alone — each net's map with its own input width, n_in / n_in_vf).  Minibatch rows 0 .. n-1 form ceil(n / R) tiles; G = min(tiles, g_max) workgroups
 // per net, workgroup g takes tiles g, g + G, g + 2 G ... in that order and owns row g of the partials:
 //     part[g][n_flat]   the gradient of the SUM over its rows, in the flat parameter layout of wg_policy.h
 //                       (actor workgroup g writes the actor's entries and log_std, critic workgroup g the critic's),
@@ -23,11 +23,12 @@
 
 // LDS map of one net (offsets in floats; S = R + 1 floats per feature row, conflict-free for row- and feature-major reads)
 struct WgPpoLds {
-    int32_t xin;                          // [min(n_in, 256)][S]   observation chunk
+    int32_t xin;                          // [min(the net's input width, 256)][S]   observation chunk
     int32_t act[WGP_MAX_LAYERS];          // [M_l][S]              activations of hidden layer l; the head's output at act[L-1]
     int32_t d[2];                         // [max M][S]            dZ of the running layer / of the one before it
     int32_t rowv;                         // [4][32]               per-row scalars of the loss head
-    int32_t rid;                          // [32] int              gathered row of each tile row, -1 = none
+    int32_t rid;                          // [32] int              the row this net gathers for each tile row (actor: agent row,
+                                          //                       critic: its env row), -1 = none
     int32_t total;
 };
 

@@ -4,6 +4,9 @@
 //   k_gae          advantages and returns of a [T, B, A] rollout (wg_rollout's recurrence), one thread per agent row.
 //   k_ppo_advstat  mean and unbiased std of a minibatch's advantages, ONE workgroup, fixed-order sums.
 //   k_ppo_grad     one minibatch: gather, forward of actor / critic, PPO loss, backward, per-workgroup gradient partials.
+//                  A minibatch entry is an AGENT row; with a centralised critic (wg_ppo_batch_shared: agents > 1 or a critic
+//                  of another input width) the critic gathers the entry's ENV row = entry / agents from a stream of its own, and
+//                  advantage / returns are indexed by env row.  agents = 1 on one stream is the plain batch.
 //   k_ppo_reduce   partials -> flat gradient + statistics record, summed in workgroup order.
 //   k_ppo_sumsq / k_ppo_adam   global L2 norm, clipping, Adam on the caller's flat parameters in place.
 //
@@ -78,21 +81,22 @@ __device__ inline int ppo_row(const int32_t* index, int64_t first, int n, int64_
     return (id < 0 || id >= n_total) ? -1 : (int)id;
 }
 
-// advstat[0] = mean, advstat[1] = unbiased std (torch.std) of the minibatch's advantages
+// advstat[0] = mean, advstat[1] = unbiased std (torch.std) of the minibatch's advantages; entry id (an agent row) carries the
+// advantage of its env row id / agents (agents = 1: its own)
 __global__ __launch_bounds__(1024) void k_ppo_advstat(const float* __restrict__ adv, const int32_t* __restrict__ index,
-                                                      const int64_t first, const int n, const int64_t n_total,
+                                                      const int64_t first, const int n, const int64_t n_total, const int agents,
                                                       float* __restrict__ advstat) {
     __shared__ float sh[1024];
     float s = 0.0f;
     for (int i = threadIdx.x; i < n; i += 1024) {
         const int id = ppo_row(index, first, n, n_total, i);
-        if (id >= 0) s += adv[id];
+        if (id >= 0) s += adv[id / agents];
     }
     const float mean = block_sum<1024>(s, sh) / (float)n;
     float q = 0.0f;
     for (int i = threadIdx.x; i < n; i += 1024) {
         const int id = ppo_row(index, first, n, n_total, i);
-        if (id >= 0) { const float d = adv[id] - mean; q += d * d; }
+        if (id >= 0) { const float d = adv[id / agents] - mean; q += d * d; }
     }
     const float var = block_sum<1024>(q, sh) / (float)(n - 1);
     if (threadIdx.x == 0) { advstat[0] = mean; advstat[1] = sqrtf(var); }
@@ -104,14 +108,14 @@ __global__ __launch_bounds__(1024) void k_ppo_advstat(const float* __restrict__ 
 struct WgPpoArgs {
     const float* packed;       // the policy's packed weights (forward)
     const float* flat;         // the caller's flat parameters (dX, log_std)
-    const float* obs;          // [n_total, n_in]
+    const float* obs[2];       // what each net gathers: [n_total, n_in] agent rows (actor), [n_total / agents, n_in_vf] env rows (critic)
     const float* raw;          // [n_total, n_out]
     const float* logp_old;     // [n_total]
-    const float* adv;          // [n_total]
-    const float* ret;          // [n_total]
+    const float* adv;          // [n_total / agents]
+    const float* ret;          // [n_total / agents]
     const int32_t* index;      // [n] or null
-    int64_t first, n_total;
-    int32_t n, G, normalize;
+    int64_t first, n_total;    // (n_total: AGENT rows)
+    int32_t n, G, normalize, agents;
     float clip, vf_coef;
     const float* advstat;
     float* part;               // [G][n_flat]
@@ -125,6 +129,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
     const int R = K.R, S = R + 1;
     const WgPpoLds& M = K.lds[net];
     const int L = P.n_layers[net];
+    const float* __restrict__ xsrc = a.obs[net];
     float* xin = lds + M.xin;
     float* rowv = lds + M.rowv;
     int* rid = (int*)(lds + M.rid);
@@ -138,7 +143,13 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
         const bool first = tile == g;
         const int row0 = tile * R;
         __syncthreads();                                   // the previous tile's readers are done with LDS
-        if (tid < 32) rid[tid] = tid < R ? ppo_row(a.index, a.first, a.n, a.n_total, row0 + tid) : -1;
+        // rid = the row THIS net gathers: the minibatch entry (an agent row) for the actor, its env row for the critic — the one
+        // division per tile row; the gather loops below only multiply
+        if (tid < 32) {
+            int id = tid < R ? ppo_row(a.index, a.first, a.n, a.n_total, row0 + tid) : -1;
+            if (net == 1 && id >= 0) id /= a.agents;
+            rid[tid] = id;
+        }
 
         // ---- forward --------------------------------------------------------------------------------------------
         for (int l = 0; l < L; ++l) {
@@ -160,7 +171,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                     __syncthreads();
                     for (int idx = tid; idx < kc * R; idx += WGT_WAVES * 64) {      // consecutive threads: consecutive inputs of a row
                         const int row = idx / kc, k = idx - row * kc, id = rid[row];
-                        xin[k * S + row] = id >= 0 ? a.obs[(size_t)id * P.n_in + k0 + k] : 0.0f;
+                        xin[k * S + row] = id >= 0 ? xsrc[(size_t)id * ly.K + k0 + k] : 0.0f;
                     }
                     __syncthreads();
                 }
@@ -216,7 +227,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                     }
                     const float lr = lp - a.logp_old[id];
                     const float ratio = expf(lr);
-                    float A = a.adv[id];
+                    float A = a.adv[id / a.agents];       // the env row's advantage, shared by its agents
                     if (a.normalize) A = (A - a.advstat[0]) / (a.advstat[1] + 1e-8f);
                     const float rc = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
                     const float s1 = ratio * A, s2 = rc * A;
@@ -281,7 +292,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                     __syncthreads();
                     for (int idx = tid; idx < kc * R; idx += WGT_WAVES * 64) {
                         const int row = idx / kc, k = idx - row * kc, id = rid[row];
-                        xin[k * S + row] = id >= 0 ? a.obs[(size_t)id * P.n_in + k0 + k] : 0.0f;
+                        xin[k * S + row] = id >= 0 ? xsrc[(size_t)id * ly.K + k0 + k] : 0.0f;
                     }
                     __syncthreads();
                 }
@@ -480,7 +491,8 @@ static size_t t_lds_map(const WgPolicyP& P, int R, WgPpoK* K) {
     for (int net = 0; net < 2; ++net) {
         WgPpoLds& m = K->lds[net];
         int o = 0, maxw = 1;
-        m.xin = o; o += (P.n_in < WGP_KC ? P.n_in : WGP_KC) * S;
+        const int n_in = net == 0 ? P.n_in : P.n_in_vf;          // each net's own input width
+        m.xin = o; o += (n_in < WGP_KC ? n_in : WGP_KC) * S;
         for (int l = 0; l < WGP_MAX_LAYERS; ++l) {
             m.act[l] = o;
             if (l < P.n_layers[net]) {
@@ -574,24 +586,29 @@ extern "C" int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64
     return 0;
 }
 
-static int t_check_batch(const char* who, const wg_ppo_batch* b, const wg_ppo_hyper* hp) {
-    if (!b || !hp) return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
-    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns)
+// (`who` is the entry the CALLER used: wg_ppo_grad is wg_ppo_grad_shared on {*batch, batch->obs, 1} and reports under its own name)
+static int t_check_batch(const char* who, const wg_ppo_batch_shared* sb, const wg_ppo_hyper* hp) {
+    if (!sb || !hp) return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
+    const wg_ppo_batch* b = &sb->rows;
+    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !sb->obs_vf)
         return tfail(WG_ERR_INVALID, std::string(who) + ": a batch pointer is null");
     if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, std::string(who) + ": n_rows out of range");
+    if (sb->agents < 1 || b->n_rows % sb->agents != 0)
+        return tfail(WG_ERR_INVALID, std::string(who) + ": agents must be >= 1 and divide n_rows (" + std::to_string(b->n_rows) + ")");
     if (!(hp->clip_range >= 0.0f)) return tfail(WG_ERR_INVALID, std::string(who) + ": clip_range < 0");
     return 0;
 }
 
 // the launches of one gradient, no argument checks
-static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* b, const int32_t* index_dev, int64_t first, int n,
+static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* sb, const int32_t* index_dev, int64_t first, int n,
                   const wg_ppo_hyper* hp, float* grad_out, float* stats_out, hipStream_t st) {
     const WgPolicyP& P = o->pol->P;
+    const wg_ppo_batch* b = &sb->rows;
     const int R = o->K.R, ntile = (n + R - 1) / R, G = ntile < o->g_max ? ntile : o->g_max;
     const int normalize = hp->normalize_advantage && n > 1;
-    if (normalize) hipLaunchKernelGGL(k_ppo_advstat, dim3(1), dim3(1024), 0, st, b->advantage, index_dev, first, n, b->n_rows, o->advstat);
+    if (normalize) hipLaunchKernelGGL(k_ppo_advstat, dim3(1), dim3(1024), 0, st, b->advantage, index_dev, first, n, b->n_rows, sb->agents, o->advstat);
     WgPpoArgs a;
-    a.packed = o->pol->packed; a.flat = params_dev; a.obs = b->obs; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
+    a.packed = o->pol->packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = sb->obs_vf; a.agents = sb->agents; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
     a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G; a.normalize = normalize;
     a.clip = hp->clip_range; a.vf_coef = hp->vf_coef; a.advstat = o->advstat; a.part = o->part; a.spart = o->spart;
     hipLaunchKernelGGL(k_ppo_grad, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
@@ -613,16 +630,42 @@ static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr,
     return wg_policy_set_params(o->pol, params_dev, o->n_flat, 1, (void*)st);
 }
 
+static int grad_entry(const char* who, wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b, const int32_t* index_dev,
+                      int64_t first, int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
+    const std::string w = who;
+    if (!o || !params_dev || !grad_out) return tfail(WG_ERR_INVALID, w + ": null argument");
+    if (int rc = t_check_batch(who, b, hp)) return rc;
+    if (n < 1) return tfail(WG_ERR_INVALID, w + ": n < 1");
+    if (!index_dev && (first < 0 || first + n > b->rows.n_rows)) return tfail(WG_ERR_INVALID, w + ": rows first .. first + n - 1 leave the batch");
+    if (int rc = t_use_device(o->device)) return rc;
+    if (int rc = t_on_device(params_dev, o->device, (w + ": params_dev").c_str())) return rc;
+    if (int rc = t_on_device(b->rows.obs, o->device, (w + ": obs").c_str())) return rc;
+    if (b->obs_vf != b->rows.obs)
+        if (int rc = t_on_device(b->obs_vf, o->device, (w + ": obs_vf").c_str())) return rc;
+    return t_grad(o, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+}
+
+extern "C" int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b, const int32_t* index_dev,
+                                  int64_t first, int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
+    return grad_entry("wg_ppo_grad_shared", o, params_dev, b, index_dev, first, n, hp, grad_out, stats_out, stream);
+}
+
+// A plain wg_ppo_batch has ONE observation stream of n_in inputs per row: the critic of a split policy cannot read it (it would
+// gather rows of n_in_vf from a buffer of rows of n_in).  Refused here, before anything is enqueued.
+static int t_refuse_split(const char* who, wg_ppo o) {
+    const WgPolicyP& P = o->pol->P;
+    if (P.n_in_vf == P.n_in) return 0;
+    return tfail(WG_ERR_INVALID, std::string(who) + ": the policy's critic reads rows of " + std::to_string(P.n_in_vf) + " inputs, its actor rows of " +
+                                     std::to_string(P.n_in) + ", and a wg_ppo_batch has one obs stream of the actor's width: use " + who +
+                                     "_shared with the critic's rows as obs_vf");
+}
+
 extern "C" int wg_ppo_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* b, const int32_t* index_dev, int64_t first,
                            int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
-    if (!o || !params_dev || !grad_out) return tfail(WG_ERR_INVALID, "wg_ppo_grad: null argument");
-    if (int rc = t_check_batch("wg_ppo_grad", b, hp)) return rc;
-    if (n < 1) return tfail(WG_ERR_INVALID, "wg_ppo_grad: n < 1");
-    if (!index_dev && (first < 0 || first + n > b->n_rows)) return tfail(WG_ERR_INVALID, "wg_ppo_grad: rows first .. first + n - 1 leave the batch");
-    if (int rc = t_use_device(o->device)) return rc;
-    if (int rc = t_on_device(params_dev, o->device, "wg_ppo_grad: params_dev")) return rc;
-    if (int rc = t_on_device(b->obs, o->device, "wg_ppo_grad: obs")) return rc;
-    return t_grad(o, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+    if (!o || !b) return tfail(WG_ERR_INVALID, "wg_ppo_grad: null argument");
+    if (int rc = t_refuse_split("wg_ppo_grad", o)) return rc;
+    const wg_ppo_batch_shared sb = {*b, b->obs, 1};
+    return grad_entry("wg_ppo_grad", o, params_dev, &sb, index_dev, first, n, hp, grad_out, stats_out, stream);
 }
 
 extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream) {
@@ -634,18 +677,20 @@ extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, 
     return t_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
 }
 
-extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
-                             int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out,
-                             void* stream) {
-    if (!o || !params_dev || !perm_dev) return tfail(WG_ERR_INVALID, "wg_ppo_update: null argument");
-    if (int rc = t_check_batch("wg_ppo_update", b, hp)) return rc;
-    if (n_epochs < 1 || batch_size < 1) return tfail(WG_ERR_INVALID, "wg_ppo_update: n_epochs and batch_size must be >= 1");
-    if (!(max_grad_norm > 0.0f)) return tfail(WG_ERR_INVALID, "wg_ppo_update: max_grad_norm must be > 0");
+static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
+                        int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream) {
+    const std::string w = who;
+    if (!o || !params_dev || !perm_dev) return tfail(WG_ERR_INVALID, w + ": null argument");
+    if (int rc = t_check_batch(who, b, hp)) return rc;
+    if (n_epochs < 1 || batch_size < 1) return tfail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
+    if (!(max_grad_norm > 0.0f)) return tfail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
     if (int rc = t_use_device(o->device)) return rc;
-    if (int rc = t_on_device(params_dev, o->device, "wg_ppo_update: params_dev")) return rc;
-    if (int rc = t_on_device(b->obs, o->device, "wg_ppo_update: obs")) return rc;
-    if (int rc = t_on_device(perm_dev, o->device, "wg_ppo_update: perm_dev")) return rc;
-    const int64_t n_rows = b->n_rows;
+    if (int rc = t_on_device(params_dev, o->device, (w + ": params_dev").c_str())) return rc;
+    if (int rc = t_on_device(b->rows.obs, o->device, (w + ": obs").c_str())) return rc;
+    if (b->obs_vf != b->rows.obs)
+        if (int rc = t_on_device(b->obs_vf, o->device, (w + ": obs_vf").c_str())) return rc;
+    if (int rc = t_on_device(perm_dev, o->device, (w + ": perm_dev").c_str())) return rc;
+    const int64_t n_rows = b->rows.n_rows;
     const int n_mb = (int)((n_rows + batch_size - 1) / batch_size);
     for (int e = 0; e < n_epochs; ++e)
         for (int k = 0; k < n_mb; ++k) {
@@ -656,4 +701,19 @@ extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b,
             if (int rc = t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream)) return rc;
         }
     return 0;
+}
+
+extern "C" int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
+                                    int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out,
+                                    void* stream) {
+    return update_entry("wg_ppo_update_shared", o, params_dev, b, perm_dev, n_epochs, batch_size, hp, lr, max_grad_norm, stats_out, stream);
+}
+
+extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
+                             int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out,
+                             void* stream) {
+    if (!o || !b) return tfail(WG_ERR_INVALID, "wg_ppo_update: null argument");
+    if (int rc = t_refuse_split("wg_ppo_update", o)) return rc;
+    const wg_ppo_batch_shared sb = {*b, b->obs, 1};
+    return update_entry("wg_ppo_update", o, params_dev, &sb, perm_dev, n_epochs, batch_size, hp, lr, max_grad_norm, stats_out, stream);
 }

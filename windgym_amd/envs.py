@@ -306,12 +306,13 @@ class WindFarmVecEnv(_gym_vector_base()):
                              shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
                              slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout)
 
-    def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run):
+    def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run, critic=None):
         """``rollout()`` of this class and of :class:`WindFarmVecEnvMulti`.  ``rows``: the axes of the policy's rows, ``(B,)`` or
         ``(B, N)``; ``shape`` / ``needs``: the ``(n_in, n_out)`` the policy must have and how the refusal says so; ``slots``: per
         observation the steps write, ``(key, key of its final rows, persistent tensor, persistent final tensor)`` — slot 0 is
         seeded from the persistent tensor, which receives slot T (final: T-1) afterwards; the policy reads ``"obs"``; ``run``: the
-        ``HipBatch`` call that enqueues the loop."""
+        ``HipBatch`` call that enqueues the loop.  ``critic``: ``(key, key of its final rows, axes of its rows)`` of what a SPLIT
+        policy's critic reads (its width must be that buffer's); ``None``: a split policy is refused."""
         from .config import INFO
         t, b = self.torch, self.batch
         T, B, N = int(n_steps), self.num_envs, self.n_turb
@@ -319,13 +320,17 @@ class WindFarmVecEnv(_gym_vector_base()):
             raise ValueError("rollout(): n_steps must be >= 1")
         if (policy.n_in, policy.n_out) != shape:
             raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, {needs}")
+        split = policy.has_critic and policy.split
+        vk, vkf, vrows = critic if split and critic is not None else ("obs", "final_obs", rows)
+        if split and (critic is None or policy.n_in_vf != dict((k, cur) for k, _, cur, _ in slots)[vk].shape[-1]):
+            raise ValueError(f"rollout(): the policy's critic reads {policy.n_in_vf} inputs, {needs}")
         record = tuple(record)
         for name in record:
             if name not in INFO:
                 raise ValueError(f"rollout(): unknown info field {name!r}")
         values = bool(values) and policy.has_critic
         stochastic_ok = policy.desc["has_log_std"]
-        key = (rows, T, record, values, stochastic_ok)
+        key = (rows, vrows, T, record, values, stochastic_ok)
         bufs = self._rollout_bufs.get(key)
         if bufs is None:
             f32 = dict(dtype=t.float32, device=b.device)
@@ -336,7 +341,7 @@ class WindFarmVecEnv(_gym_vector_base()):
             if stochastic_ok:
                 bufs["logp"] = t.zeros((T,) + rows, **f32)
             if values:
-                bufs["value"], bufs["final_value"] = t.zeros((T,) + rows, **f32), t.zeros((T,) + rows, **f32)
+                bufs["value"], bufs["final_value"] = t.zeros((T,) + vrows, **f32), t.zeros((T,) + vrows, **f32)
             for name in record:
                 info_shape, dtype = b.info_shape(name)
                 bufs[name] = t.zeros((T,) + tuple(info_shape), dtype=dtype, device=b.device)
@@ -352,6 +357,8 @@ class WindFarmVecEnv(_gym_vector_base()):
                            row_offset=self._global_offset * math.prod(rows[1:]), value=values,
                            out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
                                 bufs["value"][i] if values else None))
+                if values and split:                   # (act() on a split policy is the actor alone: the critic reads its own rows)
+                    policy.value(bufs[vk][i], out=bufs["value"][i])
                 _, r, tr, _ = self._step_device(bufs["actions"][i])
                 bufs["reward"][i].copy_(r); bufs["truncated"][i].copy_(tr)
                 for k, kf, cur, fin in slots:
@@ -359,7 +366,7 @@ class WindFarmVecEnv(_gym_vector_base()):
                 for name in record:
                     b.info(name, out=bufs[name][i])
                 if values:
-                    policy.value(bufs["final_obs"][i], out=bufs["final_value"][i])
+                    policy.value(bufs[vkf][i], out=bufs["final_value"][i])
             return dict(bufs)
         run(policy, T, bufs, record, deterministic, seed, counter0, self._global_offset)
         # the persistent outputs follow, as after a step()
@@ -1117,13 +1124,21 @@ class WindFarmVecEnvMulti:
         ``[T, ...]`` entry per name in ``record``.  Buffer reuse, the persistent outputs afterwards, the noise counter and the
         ``sample_site`` fallback loop are those of :meth:`WindFarmVecEnv.rollout`; the noise row of agent i of env e is
         ``(first global env of this shard + e) * N + i``.  Advantages: ``delta = r[t, e] + gamma * final_value[t, e, i] -
-        value[t, e, i]`` per agent row (wg_gae_shared)."""
+        value[t, e, i]`` per agent row (wg_gae_shared).
+
+        With a split policy whose critic reads the flat observation (``MlpPolicy(obs_len, 1, ..., n_in_vf=obs_dim)``: a
+        CENTRALISED critic) ``value`` / ``final_value`` are ``[T, B]`` = ``V(flat_obs[t])`` / ``V(flat_final_obs[t])``, one per env
+        and shared by its agents; everything else is unchanged and does not depend on the critic.  Advantages: wg_gae on
+        ``[T, B]``."""
         b = self.batch
         return self.venv._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs, self.n_turb),
                                   shape=(self.obs_len, 1),
-                                  needs=f"a policy shared by the turbines of this env maps {self.obs_len} -> 1",
+                                  needs=f"a policy shared by the turbines of this env maps {self.obs_len} -> 1, its critic on the "
+                                        f"same {self.obs_len} inputs (one value per agent) or on the flat observation's "
+                                        f"{b.obs_dim} (a centralised critic)",
                                   slots=(("obs", "final_obs", self._obs, self._final_obs),
-                                         ("flat_obs", "flat_final_obs", b.obs, b.final_obs)), run=b.rollout_multi)
+                                         ("flat_obs", "flat_final_obs", b.obs, b.final_obs)), run=b.rollout_multi,
+                                  critic=("flat_obs", "flat_final_obs", (self.num_envs,)))
 
     def infos(self, step=False):
         return self.venv.infos(step=step)

@@ -11,6 +11,10 @@ object goes wherever the scripted agents of :mod:`windgym_amd.agents` go.
 
 Flat parameter order (``wg_policy_set_params``, include/windgym_hip.h): actor hidden layers (W ``[out][in]`` then b),
 actor head, critic hidden layers, critic head, ``log_std``.
+
+A policy may be SPLIT: its critic maps ``n_in_vf`` inputs, not the actor's ``n_in`` (``wg_policy_create_vf``) — the centralised
+critic of multi-agent PPO, which reads the env's flat observation while the actor reads one agent's.  ``desc["n_in_vf"]`` is
+``None`` (or absent, as in every dict written before it existed) for the critic on the actor's width.
 """
 from __future__ import annotations
 
@@ -28,13 +32,24 @@ MAX_HIDDEN = 4
 # ----------------------------------------------------------------------------------------------------------------------
 # architecture description + flat layout (host only)
 # ----------------------------------------------------------------------------------------------------------------------
-def make_desc(n_in, n_out, hidden_pi=(64, 64), hidden_vf=(64, 64), activation="tanh", has_log_std=True):
-    """Architecture dict; ``hidden_vf=None`` = no critic."""
+def make_desc(n_in, n_out, hidden_pi=(64, 64), hidden_vf=(64, 64), activation="tanh", has_log_std=True, n_in_vf=None):
+    """Architecture dict; ``hidden_vf=None`` = no critic; ``n_in_vf``: the critic's own input width (``None`` = ``n_in``)."""
     if activation not in ("tanh", "relu"):
         raise ValueError(f"activation must be 'tanh' or 'relu', not {activation!r}")
+    if n_in_vf is not None:
+        if hidden_vf is None:
+            raise ValueError("n_in_vf is the input width of the critic: the policy needs one (hidden_vf is None)")
+        if int(n_in_vf) < 1:
+            raise ValueError("n_in_vf must be >= 1")
     return dict(n_in=int(n_in), n_out=int(n_out), hidden_pi=tuple(int(h) for h in hidden_pi),
                 hidden_vf=None if hidden_vf is None else tuple(int(h) for h in hidden_vf),
-                activation=activation, has_log_std=bool(has_log_std))
+                activation=activation, has_log_std=bool(has_log_std), n_in_vf=None if n_in_vf is None else int(n_in_vf))
+
+
+def critic_width(desc):
+    """The critic's input width: ``desc["n_in_vf"]``, or ``n_in`` where it is ``None`` or absent."""
+    w = desc.get("n_in_vf")
+    return int(desc["n_in"] if w is None else w)
 
 
 def param_layout(desc):
@@ -46,7 +61,7 @@ def param_layout(desc):
         k = h
     out += [("action_net.weight", (desc["n_out"], k)), ("action_net.bias", (desc["n_out"],))]
     if desc["hidden_vf"] is not None:
-        k = desc["n_in"]
+        k = critic_width(desc)
         for i, h in enumerate(desc["hidden_vf"]):
             out += [(f"mlp_extractor.value_net.{2 * i}.weight", (h, k)), (f"mlp_extractor.value_net.{2 * i}.bias", (h,))]
             k = h
@@ -133,11 +148,15 @@ def read_sb3_zip(path, activation="tanh"):
     hidden_pi, k = _chain(tensors, "mlp_extractor.policy_net", n_in, "actor")
     if aw.shape != (n_out, k) or tensors["action_net.bias"].shape != (n_out,):
         raise ValueError(f"actor: shapes do not chain at action_net (weight {aw.shape}, input width {k})")
-    hidden_vf = None
+    hidden_vf, n_in_vf = None, None
     if "value_net.weight" in tensors:
         if "value_net.bias" not in tensors:
             raise ValueError("missing tensor value_net.bias")
-        hidden_vf, k = _chain(tensors, "mlp_extractor.value_net", n_in, "critic")
+        # the critic's input width is its own first layer's (SB3 itself always writes the actor's; a split policy's differs)
+        vfirst = tensors.get("mlp_extractor.value_net.0.weight", tensors["value_net.weight"])
+        if vfirst.ndim == 2 and int(vfirst.shape[1]) != n_in:
+            n_in_vf = int(vfirst.shape[1])
+        hidden_vf, k = _chain(tensors, "mlp_extractor.value_net", n_in if n_in_vf is None else n_in_vf, "critic")
         if tensors["value_net.weight"].shape != (1, k) or tensors["value_net.bias"].shape != (1,):
             raise ValueError(f"critic: shapes do not chain at value_net (weight {tensors['value_net.weight'].shape}, input width {k})")
     elif any(k2.startswith("mlp_extractor.value_net.") for k2 in tensors):
@@ -145,7 +164,7 @@ def read_sb3_zip(path, activation="tanh"):
     has_ls = "log_std" in tensors
     if has_ls and tensors["log_std"].shape != (n_out,):
         raise ValueError(f"log_std: shape {tensors['log_std'].shape}, expected ({n_out},)")
-    desc = make_desc(n_in, n_out, hidden_pi, hidden_vf, activation, has_ls)
+    desc = make_desc(n_in, n_out, hidden_pi, hidden_vf, activation, has_ls, n_in_vf)
     return desc, {name: tensors[name] for name, _ in param_layout(desc)}
 
 
@@ -154,16 +173,18 @@ def read_sb3_zip(path, activation="tanh"):
 # ----------------------------------------------------------------------------------------------------------------------
 class MlpPolicy:
     """SB3's default ``MlpPolicy`` (actor ``n_in -> hidden_pi -> n_out``, critic ``n_in -> hidden_vf -> 1``) on one GPU.
+    With ``n_in_vf`` the critic maps ``n_in_vf -> hidden_vf -> 1`` instead (a split policy: ``act()`` evaluates the actor only,
+    ``value()`` takes rows of ``n_in_vf``).
 
     ``params`` is ONE flat float32 CUDA leaf tensor (a torch optimiser can own it); ``state_dict()`` returns views of it
     under SB3's names.  The kernel reads its own packed copy: after changing ``params`` call :meth:`sync`.
     Raises ``WindGymHipError`` without the built library or a GPU — there is no CPU fallback."""
 
     def __init__(self, n_in, n_out, hidden_pi=(64, 64), hidden_vf=(64, 64), activation="tanh", device=None, seed=0,
-                 has_log_std=True):
+                 has_log_std=True, n_in_vf=None):
         import torch
         from .binding import ACTV, CPolicyDesc, WindGymHipError, _chk, load_library
-        self.desc = make_desc(n_in, n_out, hidden_pi, hidden_vf, activation, has_log_std)
+        self.desc = make_desc(n_in, n_out, hidden_pi, hidden_vf, activation, has_log_std, n_in_vf)
         if len(self.desc["hidden_pi"]) > MAX_HIDDEN or len(self.desc["hidden_vf"] or ()) > MAX_HIDDEN:
             raise NotImplementedError(f"at most {MAX_HIDDEN} hidden layers per net")
         self.L = load_library()
@@ -183,12 +204,17 @@ class MlpPolicy:
             d.hidden_vf[i] = h
         d.has_log_std = int(self.desc["has_log_std"])
         h = C.c_void_p()
-        _chk(self.L.wg_policy_create(C.byref(d), self.device_index, C.byref(h)), "wg_policy_create")
+        if self.desc["n_in_vf"] is None:
+            _chk(self.L.wg_policy_create(C.byref(d), self.device_index, C.byref(h)), "wg_policy_create")
+        else:
+            _chk(self.L.wg_policy_create_vf(C.byref(d), self.desc["n_in_vf"], self.device_index, C.byref(h)), "wg_policy_create_vf")
         self._h = h
         n = C.c_size_t()
         _chk(self.L.wg_policy_n_params(self._h, C.byref(n)), "wg_policy_n_params")
         assert n.value == n_params(self.desc)
         self.n_in, self.n_out, self.has_critic = self.desc["n_in"], self.desc["n_out"], self.desc["hidden_vf"] is not None
+        self.n_in_vf = critic_width(self.desc)          # what value() reads
+        self.split = self.n_in_vf != self.n_in          # the critic reads other rows than the actor
         # seeded init: N(0, 1 / fan_in) weights, zero biases and log_std (SB3's orthogonal init is a trainer's business)
         rng = np.random.default_rng(seed)
         t = {name: (rng.standard_normal(shape) / np.sqrt(shape[1])).astype(np.float32) if len(shape) == 2
@@ -204,7 +230,7 @@ class MlpPolicy:
     def from_sb3_zip(cls, path, activation="tanh", device=None, seed=0):
         desc, tensors = read_sb3_zip(path, activation=activation)
         p = cls(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], activation, device=device, seed=seed,
-                has_log_std=desc["has_log_std"])
+                has_log_std=desc["has_log_std"], n_in_vf=desc["n_in_vf"])
         p.load_state_dict(tensors)
         return p
 
@@ -245,9 +271,10 @@ class MlpPolicy:
         self._chk(self.L.wg_policy_set_params(self._h, C.c_void_p(self.params.data_ptr()), self.params.numel(), 1,
                                               self._stream()), "wg_policy_set_params")
 
-    def torch_forward(self, obs):
+    def torch_forward(self, obs, obs_vf=None):
         """(mean, value) with ``F.linear`` / tanh on the same parameters — differentiable (a trainer's loss goes through
-        it); value is None without a critic."""
+        it); value is None without a critic.  The critic reads ``obs_vf`` (rows of ``n_in_vf``) when given, else ``obs``; on a
+        split policy without ``obs_vf`` there is nothing it could read and value is None."""
         F = self.torch.nn.functional
         act = self.torch.tanh if self.desc["activation"] == "tanh" else F.relu
         views, o = {}, 0
@@ -256,14 +283,14 @@ class MlpPolicy:
             views[name] = self.params[o:o + n].view(shape)
             o += n
 
-        def net(prefix, n_hidden, head):
-            x = obs
+        def net(prefix, n_hidden, head, x):
             for i in range(n_hidden):
                 x = act(F.linear(x, views[f"{prefix}.{2 * i}.weight"], views[f"{prefix}.{2 * i}.bias"]))
             return F.linear(x, views[head + ".weight"], views[head + ".bias"])
 
-        mean = net("mlp_extractor.policy_net", len(self.desc["hidden_pi"]), "action_net")
-        value = net("mlp_extractor.value_net", len(self.desc["hidden_vf"]), "value_net")[..., 0] if self.has_critic else None
+        mean = net("mlp_extractor.policy_net", len(self.desc["hidden_pi"]), "action_net", obs)
+        xv = obs_vf if obs_vf is not None else None if self.split else obs
+        value = net("mlp_extractor.value_net", len(self.desc["hidden_vf"]), "value_net", xv)[..., 0] if self.has_critic and xv is not None else None
         return mean, value
 
     # -- evaluation ---------------------------------------------------------------------------------
@@ -278,14 +305,15 @@ class MlpPolicy:
     def act(self, obs, deterministic=False, counter=None, *, seed=None, row_offset=0, value=True, out=None):
         """ONE launch of k_policy on a contiguous float32 CUDA tensor ``[..., n_in]`` -> persistent ``(action, raw, logp,
         value)`` tensors (rows = the leading dimensions flattened; valid until the next ``act()`` on as many rows; value is
-        None without a critic or with ``value=False``).  No synchronisation.  ``counter`` defaults to a running count."""
+        None without a critic, with ``value=False`` or on a split policy, whose critic reads other rows: :meth:`value`).  No
+        synchronisation.  ``counter`` defaults to a running count."""
         t = self.torch
         if not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
                 and obs.shape[-1] == self.n_in):
             raise ValueError(f"act(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in}]")
         n = obs.numel() // self.n_in
         a, r, lp, v = out if out is not None else self._buffers(n)
-        want_v = value and self.has_critic
+        want_v = value and self.has_critic and not self.split
         stochastic = not deterministic
         if counter is None:
             counter = self.counter
@@ -301,11 +329,14 @@ class MlpPolicy:
         return a, r, (lp if ls else None), (v if want_v else None)
 
     def value(self, obs, out=None):
-        """Critic only: V(obs) -> float32 CUDA tensor [rows]."""
+        """Critic only: V(obs) on a contiguous float32 CUDA tensor ``[..., n_in_vf]`` -> float32 CUDA tensor [rows]."""
         t = self.torch
         if not self.has_critic:
             raise ValueError("value(): the policy has no critic")
-        n = obs.numel() // self.n_in
+        if self.split and not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
+                               and obs.shape[-1] == self.n_in_vf):
+            raise ValueError(f"value(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in_vf}] (the critic's input width)")
+        n = obs.numel() // self.n_in_vf
         v = out if out is not None else t.zeros(n, dtype=t.float32, device=self.device)
         self._chk(self.L.wg_policy_act(self._h, n, obs.data_ptr(), 1, 0, 0, 0, None, None, None, v.data_ptr(),
                                        self._stream()), "wg_policy_act")

@@ -2,7 +2,7 @@
 ``PPO("MlpPolicy", env, n_steps=2048).learn(...)`` (examples/longer_steps_example.py:212-240, examples/curriculum.py:544-560),
 without stable-baselines3 and without leaving the GPU between rollout and update.
 
-One iteration of :meth:`PPO.learn` is ``venv.rollout`` (wg_rollout) -> ``wg_gae`` -> one ``torch.randperm`` per epoch from a
+One iteration of :meth:`PPO.learn` is ``venv.rollout`` (wg_rollout; wg_rollout_multi on a multi-agent env) -> ``wg_gae`` -> one ``torch.randperm`` per epoch from a
 seeded device generator -> ``wg_ppo_update`` (n_epochs x minibatches of k_ppo_grad + clipping + Adam + repack), with one
 device-to-host copy of the statistics per logged iteration.  :class:`PPOOptimizer` is the thin wrapper of the ``wg_ppo_*``
 entries of include/windgym_hip.h (gradient and optimiser step are separate calls: a data-parallel trainer all-reduces the
@@ -101,13 +101,27 @@ class PPOOptimizer:
             raise ValueError("value must be [T, B, A]")
         return self.gae(reward, value, *args, **kwargs)
 
-    def _batch(self, obs, raw, logp, advantage, returns):
-        from .binding import CPpoBatch
+    def _batch(self, obs, raw, logp, advantage, returns, obs_vf=None, agents=1):
+        """-> (batch struct, agent rows, shared?).  ``obs_vf`` / ``agents``: the critic's own stream ``[n / agents, n_in_vf]`` of a
+        centralised critic (wg_ppo_batch_shared, taken by wg_ppo_grad_shared / wg_ppo_update_shared; ``advantage`` / ``returns`` are
+        then per ENV row); without them the plain wg_ppo_batch of wg_ppo_grad / wg_ppo_update."""
+        from .binding import CPpoBatch, CPpoBatchShared
         p = self.policy
-        n = logp.numel()
+        n, agents = logp.numel(), int(agents)
+        if agents < 1 or n % agents:
+            raise ValueError(f"agents must be >= 1 and divide the {n} rows")
+        if obs_vf is None and p.split:
+            raise ValueError(f"the policy's critic reads {p.n_in_vf} inputs: pass its rows as obs_vf")
+        ne = n // agents
         self._f32(obs, (n, p.n_in), "obs"); self._f32(raw, (n, p.n_out), "raw"); self._f32(logp, (n,), "logp")
-        self._f32(advantage, (n,), "advantage"); self._f32(returns, (n,), "returns")
-        return CPpoBatch(obs.data_ptr(), raw.data_ptr(), logp.data_ptr(), advantage.data_ptr(), returns.data_ptr(), n), n
+        self._f32(advantage, (ne,), "advantage"); self._f32(returns, (ne,), "returns")
+        b = CPpoBatch(obs.data_ptr(), raw.data_ptr(), logp.data_ptr(), advantage.data_ptr(), returns.data_ptr(), n)
+        if obs_vf is None and agents == 1:
+            return b, n, False
+        if obs_vf is None:
+            raise ValueError("agents > 1 needs obs_vf, the env rows the critic reads")
+        self._f32(obs_vf, (ne, p.n_in_vf), "obs_vf")
+        return CPpoBatchShared(b, obs_vf.data_ptr(), agents), n, True
 
     @staticmethod
     def _hyper(clip_range, vf_coef, ent_coef, normalize_advantage):
@@ -121,10 +135,13 @@ class PPOOptimizer:
         return index
 
     def grad(self, obs, raw, logp, advantage, returns, *, index=None, first=0, n=None, clip_range=0.2, vf_coef=0.5,
-             ent_coef=0.0, normalize_advantage=True, out=None, stats=None):
-        """wg_ppo_grad: one minibatch -> (flat gradient ``[n_params]``, statistics ``[8]`` in the order of binding.PPO_STATS)."""
+             ent_coef=0.0, normalize_advantage=True, out=None, stats=None, obs_vf=None, agents=1):
+        """wg_ppo_grad: one minibatch -> (flat gradient ``[n_params]``, statistics ``[8]`` in the order of binding.PPO_STATS).
+        With ``obs_vf [rows / agents, n_in_vf]`` (and ``advantage`` / ``returns [rows / agents]``): wg_ppo_grad_shared, the
+        centralised critic — entry ``id`` is an agent row of env row ``id // agents``."""
         t = self.torch
-        b, rows = self._batch(obs, raw, logp, advantage, returns)
+        b, rows, shared = self._batch(obs, raw, logp, advantage, returns, obs_vf, agents)
+        entry = "wg_ppo_grad_shared" if shared else "wg_ppo_grad"
         if index is not None:
             n = index.numel() if n is None else int(n)
             self._index(index, n)
@@ -132,9 +149,10 @@ class PPOOptimizer:
             n = rows - int(first)
         g = self.grad_buf if out is None else out
         st = t.zeros(8, dtype=t.float32, device=self.policy.device) if stats is None else stats
-        self._chk(self.L.wg_ppo_grad(self._h, self.policy.params.data_ptr(), C.byref(b), None if index is None else index.data_ptr(),
-                                     int(first), int(n), C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)),
-                                     g.data_ptr(), st.data_ptr(), self.policy._stream()), "wg_ppo_grad")
+        self._chk(getattr(self.L, entry)(
+            self._h, self.policy.params.data_ptr(), C.byref(b), None if index is None else index.data_ptr(), int(first), int(n),
+            C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)), g.data_ptr(), st.data_ptr(),
+            self.policy._stream()), entry)
         return g, st
 
     def apply(self, grad=None, learning_rate=3e-4, max_grad_norm=0.5):
@@ -144,18 +162,21 @@ class PPOOptimizer:
                                       float(max_grad_norm), self.policy._stream()), "wg_ppo_apply")
 
     def update(self, obs, raw, logp, advantage, returns, perm, batch_size, *, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
-               normalize_advantage=True, learning_rate=3e-4, max_grad_norm=0.5, stats=None):
-        """wg_ppo_update: ``perm`` int32 ``[n_epochs, n_rows]`` -> statistics ``[n_epochs, n_minibatches, 8]``."""
+               normalize_advantage=True, learning_rate=3e-4, max_grad_norm=0.5, stats=None, obs_vf=None, agents=1):
+        """wg_ppo_update: ``perm`` int32 ``[n_epochs, n_rows]`` -> statistics ``[n_epochs, n_minibatches, 8]``.  ``obs_vf`` /
+        ``agents`` as in :meth:`grad` (wg_ppo_update_shared; ``perm`` and ``batch_size`` stay in agent rows)."""
         t = self.torch
-        b, rows = self._batch(obs, raw, logp, advantage, returns)
+        b, rows, shared = self._batch(obs, raw, logp, advantage, returns, obs_vf, agents)
+        entry = "wg_ppo_update_shared" if shared else "wg_ppo_update"
         if perm.ndim != 2 or perm.shape[1] != rows:
             raise ValueError(f"perm must be [n_epochs, {rows}]")
         self._index(perm, rows)
         n_epochs, n_mb = perm.shape[0], -(-rows // int(batch_size))
         st = t.zeros((n_epochs, n_mb, 8), dtype=t.float32, device=self.policy.device) if stats is None else stats
-        self._chk(self.L.wg_ppo_update(self._h, self.policy.params.data_ptr(), C.byref(b), perm.data_ptr(), n_epochs, int(batch_size),
-                                       C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)),
-                                       float(learning_rate), float(max_grad_norm), st.data_ptr(), self.policy._stream()), "wg_ppo_update")
+        self._chk(getattr(self.L, entry)(
+            self._h, self.policy.params.data_ptr(), C.byref(b), perm.data_ptr(), n_epochs, int(batch_size),
+            C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)), float(learning_rate), float(max_grad_norm),
+            st.data_ptr(), self.policy._stream()), entry)
         return st
 
     def state(self):
@@ -185,6 +206,13 @@ class PPO:
     = ``n_steps * num_envs * n_turb``, the ``batch_size`` default and the permutations are in agent rows, advantages come
     from wg_gae_shared (the farm reward is every agent's reward, each agent's critic sees its own observation: independent PPO
     with shared parameters) — while ``num_timesteps``, ``fps`` and the episode means stay in env steps.
+    ``critic="central"`` on a ``WindFarmVecEnvMulti`` is multi-agent PPO with a CENTRALISED critic (MAPPO: centralised training,
+    decentralised execution): the actor still maps one agent's ``obs_len -> 1``, the critic reads the env's flat observation
+    (``MlpPolicy(obs_len, 1, pi, vf, n_in_vf=obs_dim)``), there is one value and one advantage per env (wg_gae on ``[T, B]``),
+    shared by its agents, and the update is wg_ppo_update_shared on the same agent rows.  With a policy OBJECT the mode is the
+    policy's (``n_in_vf == obs_dim``: central); ``critic=None`` / ``"agent"`` with the string is the per-agent critic.  The mode
+    is told by the critic's width, so it needs ``obs_dim != obs_len``: on a farm of ONE turbine (one agent per env) there is nothing
+    to centralise and ``critic="central"`` is a ``ValueError``.
 
     Two defaults differ from SB3's, which sized them for a handful of host envs: ``n_steps`` = 128 (SB3: 2048) steps of EVERY env
     of the batch per rollout, and ``batch_size`` = a quarter of the rollout (SB3: 64 rows).  ``policy`` is an
@@ -199,7 +227,7 @@ class PPO:
 
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
-                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False):
+                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None):
         for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
             if v is not None:
                 raise NotImplementedError(f"{name} is not implemented")
@@ -224,12 +252,29 @@ class PPO:
         if policy_kwargs and not isinstance(policy, str):
             raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
         want = (int(venv.obs_len), 1) if multi else (int(venv.batch.obs_dim), int(venv.n_turb))       # the policy's n_in -> n_out
+        if critic not in (None, "agent", "central"):
+            raise ValueError(f"critic must be None, 'agent' or 'central', not {critic!r}")
+        if critic == "central" and not multi:
+            raise ValueError("critic='central' needs a WindFarmVecEnvMulti: on a WindFarmVecEnv the one agent's critic already reads "
+                             "the flat observation, there is nothing to centralise")
+        if critic == "central" and int(venv.batch.obs_dim) == want[0]:
+            raise ValueError(f"critic='central' needs a farm of more than one turbine: here the flat observation and an agent's have "
+                             f"the same {want[0]} values (one agent per env), there is nothing to centralise")
         if isinstance(policy, str):
-            policy = self._build_policy(venv, want, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
+            policy = self._build_policy(venv, want, dict(policy_kwargs or {}), 0 if seed is None else int(seed),
+                                        int(venv.batch.obs_dim) if critic == "central" else None)
         if (policy.n_in, policy.n_out) != want:
             raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, this env needs {want[0]} -> {want[1]} "
                              "(accepted shapes: obs_dim -> n_turb on a WindFarmVecEnv, obs_len -> 1 — one policy shared by the "
                              "turbines — on a WindFarmVecEnvMulti)")
+        central = bool(multi and policy.has_critic and policy.split)
+        if policy.has_critic and policy.split and (not multi or policy.n_in_vf != int(venv.batch.obs_dim)):
+            raise ValueError(f"the policy's critic reads {policy.n_in_vf} inputs: a split policy only fits a WindFarmVecEnvMulti, as "
+                             f"its centralised critic on the flat observation (n_in_vf = obs_dim)")
+        if critic is not None and (critic == "central") != central:
+            raise ValueError(f"critic={critic!r} contradicts the policy, whose critic reads {policy.n_in_vf} inputs "
+                             f"({'central' if central else 'agent'}): with a policy object the mode is the policy's")
+        self.central, self.critic = central, "central" if central else "agent" if multi else None
         self.policy, self.venv, self.torch = policy, venv, policy.torch
         self.n_steps, self.batch_size, self.n_epochs, self.n_rows = n_steps, batch_size, n_epochs, n_rows
         self.multi, self.n_agents, self.n_env_steps = multi, n_agents, n_steps * int(venv.num_envs)
@@ -242,26 +287,26 @@ class PPO:
         self._gen = t.Generator(device=policy.device)
         self._gen.manual_seed(0 if seed is None else int(seed))
         self._perm = t.zeros((n_epochs, n_rows), dtype=t.int32, device=policy.device)
-        self._adv = t.zeros((n_steps, venv.num_envs) + ((n_agents,) if multi else ()), dtype=t.float32, device=policy.device)
+        self._adv = t.zeros((n_steps, venv.num_envs) + ((n_agents,) if multi and not central else ()), dtype=t.float32, device=policy.device)
         self._ret = t.zeros_like(self._adv)
         self._stats = t.zeros((n_epochs, -(-n_rows // batch_size), 8), dtype=t.float32, device=policy.device)
         self.num_timesteps, self.iteration, self.log = 0, 0, []
 
     @staticmethod
-    def _build_policy(venv, shape, kw, seed):
+    def _build_policy(venv, shape, kw, seed, n_in_vf=None):
         arch = kw.pop("net_arch", dict(pi=[64, 64], vf=[64, 64]))
         activation = kw.pop("activation", "tanh")
         if kw:
             raise ValueError(f"unknown policy_kwargs: {sorted(kw)}")
         pi, vf = (arch["pi"], arch["vf"]) if isinstance(arch, dict) else (arch, arch)
-        p = MlpPolicy(*shape, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed)
+        p = MlpPolicy(*shape, tuple(pi), tuple(vf), activation, device=venv.batch.device.index, seed=seed, n_in_vf=n_in_vf)
         p.load_state_dict(sb3_orthogonal_init(p.desc, seed))
         return p
 
     # -- training -------------------------------------------------------------------------------------------------
     def collect(self):
         """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added
-        (``[T, B, N]`` from wg_gae_shared on a ``WindFarmVecEnvMulti``)."""
+        (``[T, B, N]`` from wg_gae_shared on a ``WindFarmVecEnvMulti``; ``[T, B]`` again under its centralised critic)."""
         out = self.venv.rollout(self.policy, self.n_steps)
         self.opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda, out=(self._adv, self._ret))
         out["advantage"], out["returns"] = self._adv, self._ret
@@ -273,10 +318,11 @@ class PPO:
         for e in range(self.n_epochs):
             self._perm[e].copy_(t.randperm(self.n_rows, generator=self._gen, device=self.policy.device))
         T, O, N = self.n_steps, self.policy.n_in, self.policy.n_out
+        shared = dict(obs_vf=out["flat_obs"][:T].view(-1, self.policy.n_in_vf), agents=self.n_agents) if self.central else {}
         return self.opt.update(out["obs"][:T].view(-1, O), out["raw"].view(-1, N), out["logp"].view(-1), self._adv.view(-1),
                                self._ret.view(-1), self._perm, self.batch_size, clip_range=clip_range, vf_coef=self.vf_coef,
                                ent_coef=self.ent_coef, normalize_advantage=self.normalize_advantage,
-                               learning_rate=learning_rate, max_grad_norm=self.max_grad_norm, stats=self._stats)
+                               learning_rate=learning_rate, max_grad_norm=self.max_grad_norm, stats=self._stats, **shared)
 
     def learn(self, total_timesteps, callback=None, log_interval=1, reset_num_timesteps=True):
         """Iterations of rollout + update until ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``:
@@ -338,7 +384,8 @@ class PPO:
             return b.getvalue()
         meta = dict(format="windgym_amd.PPO/1", desc=dict(self.policy.desc), hyper=self._hyper_json(), seed=self.seed,
                     policy_seed=self.policy.seed, policy_counter=self.policy.counter, num_timesteps=self.num_timesteps,
-                    iteration=self.iteration, adam_step=step, env_policy_steps=self.venv._policy_steps, log=self.log)
+                    iteration=self.iteration, adam_step=step, env_policy_steps=self.venv._policy_steps, log=self.log,
+                    critic=self.critic)
         with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
             z.writestr("policy.pth", pth.getvalue())
             z.writestr("adam_state.npy", npy(mv))
@@ -361,7 +408,8 @@ class PPO:
             gen = np.load(io.BytesIO(z.read("generator_state.npy")))
         desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
         pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
-                        device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"])
+                        device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"],
+                        n_in_vf=desc["n_in_vf"])
         pol.load_state_dict(tensors)
         pol.counter = int(meta["policy_counter"])
         hyper = dict(meta["hyper"])
@@ -370,7 +418,7 @@ class PPO:
                 hyper[k] = v
             elif hyper[k] is None:
                 raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
-        self = cls(pol, venv, seed=meta["seed"], **hyper)
+        self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), **hyper)      # (no key: written before there was a choice)
         self.opt.load_state(mv, meta["adam_step"])
         self._gen.set_state(torch.from_numpy(gen))
         self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
