@@ -658,6 +658,64 @@ int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_ppo_batch_sha
 int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared* batch, const int32_t* perm_dev, int n_epochs,
                          int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
+/* -----------------------------------------------------------------------------------------------------------------
+ * Populations: P policies of ONE architecture collected and trained in the kernel launches of one (seeds of a result,
+ * a sweep of gamma / learning rate / ent_coef: longer_steps_example.py + submit.sh run such sweeps as job arrays).
+ * A population is P existing handles plus a small object that lets the kernels find them; the members stay ordinary
+ * wg_policy / wg_ppo handles (wg_policy_act, wg_policy_set_params, wg_ppo_get_state ... work on a member as before).
+ * Member m owns rows [m * Bm, (m + 1) * Bm) of every [.., B, ..] buffer, Bm = B / P.  CONTRACT: every entry below is
+ * bit-identical, per member, to the loop of single-policy calls its comment names — a member's results depend neither on
+ * P, nor on its index m, nor on what the other members hold (no float atomics, every sum in the single call's order).
+ * A population is used on ONE stream at a time (its device tables are rewritten in stream order by each call).
+ * Out of scope: wg_rollout_multi (per-agent and central), members of differing architectures.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define WG_POP_MAX 16
+typedef struct wg_pop_s* wg_pop;
+
+/* members[0 .. P-1]: policies of ONE architecture (equal wg_policy_desc) on one device; opts[m] = the wg_ppo of members[m],
+ * or opts = NULL for a population that only acts.  The handles must outlive the population.  WG_ERR_INVALID (the message
+ * names the member): P outside 1 .. WG_POP_MAX, differing architectures or devices, a member listed twice, an opts[m] that
+ * is not members[m]'s, a split policy (wg_policy_create_vf with another critic width).                                */
+int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P, wg_pop* out);
+int wg_pop_destroy(wg_pop q);
+
+/* ONE launch of the policy kernel for all members: bit-identical to, for m in 0 .. P-1 with Bm = n_rows / P,
+ *     wg_policy_act(members[m], Bm, obs_dev + m * Bm * n_in, deterministic, seeds[m], counter, row_offsets[m],
+ *                   action_dev + m * Bm * n_out, raw_dev + m * Bm * n_out, logp_dev + m * Bm, value_dev + m * Bm, stream)
+ * (null outputs are skipped for every member; row_offsets = NULL: all 0; seeds may be NULL when no actor output is wanted).
+ * WG_ERR_INVALID, nothing enqueued: P does not divide n_rows; what wg_policy_act refuses.                               */
+int wg_pop_act(wg_pop q, int n_rows, const float* obs_dev, int deterministic, const uint64_t* seeds, uint64_t counter,
+               const uint64_t* row_offsets, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream);
+
+/* wg_rollout with the population in the policy's place: the same buffers [T (+ 1), B, ..], member m on the envs (columns)
+ * [m * Bm, (m + 1) * Bm).  Bit-identical (buffers and handle state) to wg_rollout's documented loop with each wg_policy_act
+ * replaced by the P calls above (noise key of member m: seeds[m], counter0 + t, row_offsets[m] + its env's index in the
+ * member) — still one launch of the policy kernel per step.  WG_ERR_INVALID: P does not divide the handle's n_envs; what
+ * wg_rollout refuses.                                                                                                     */
+int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
+                   const uint64_t* row_offsets, const wg_rollout_bufs* bufs, void* stream);
+
+/* wg_gae on [T, B] with column b's member m = b / (B / P) choosing gamma[m] / lambda[m] (host arrays [P]): bit-identical to
+ * wg_gae on the member's columns; with equal values it is wg_gae bit for bit.  WG_ERR_INVALID: P outside 1 .. WG_POP_MAX or
+ * not dividing B.                                                                                                         */
+int wg_gae_pop(int T, int B, int P, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+               const uint8_t* truncated_dev, const float* gamma, const float* lambda, float* advantage_out, float* returns_out,
+               void* stream);
+
+/* SB3's PPO.train for every member on ONE batch (wg_rollout's buffers flattened to n_rows = T * B rows), in the launches of
+ * one wg_ppo_update: rows_m = n_rows / P rows per member, perm_dev int32[P, n_epochs, rows_m] holds per member and epoch a
+ * permutation of ITS rows as GLOBAL row ids of the batch (row r of member m of a [T, B] rollout: (r / Bm) * B + m * Bm + r % Bm),
+ * the same n_mb = ceil(rows_m / batch_size) minibatches for every member (the launches run in lockstep); hp, lr and
+ * max_grad_norm are host arrays [P]; params_dev[m] (host array of device pointers) is the flat vector members[m] was last
+ * given; stats_out (device, may be NULL) is wg_ppo_stats[P, n_epochs, n_mb].  Bit-identical, per member, to
+ *     wg_ppo_update(opts[m], params_dev[m], <the member's rows as a contiguous batch>, <the same permutations as local row ids>,
+ *                   n_epochs, batch_size, &hp[m], lr[m], max_grad_norm[m], stats_out + m * n_epochs * n_mb, stream)
+ * and Adam's step count advances in every member's own wg_ppo.  WG_ERR_INVALID, nothing enqueued: a population created
+ * without opts, P not dividing n_rows, what wg_ppo_update refuses (the message names the member).                        */
+int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
+                  int batch_size, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm, wg_ppo_stats* stats_out,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

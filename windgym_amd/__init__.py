@@ -26,6 +26,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("PPO", "PPOOptimizer"):
         from . import ppo
         return getattr(ppo, name)
+    if name in ("PPOPopulation", "Population"):
+        from . import population
+        return getattr(population, name)
     if name in ("PyWakeAgent", "SteadyStateYawAgent"):
         from . import steady
         return getattr(steady, name)

@@ -37,11 +37,13 @@ ABI_SYMBOLS = (
     "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
     "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
     "wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared",
+    "wg_pop_create", "wg_pop_destroy", "wg_pop_act", "wg_pop_rollout", "wg_gae_pop", "wg_pop_update",
 )
 
 _lib = None
 
 WG_POLICY_MAX_HIDDEN = 4
+WG_POP_MAX = 16
 ACTV = {"tanh": 0, "relu": 1}
 
 
@@ -172,6 +174,16 @@ def load_library():
                                 C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     L.wg_ppo_grad_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_grad.argtypes[3:]
     L.wg_ppo_update_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_update.argtypes[3:]
+    L.wg_pop_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_pop_destroy.argtypes = [C.c_void_p]
+    L.wg_pop_act.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_pop_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                                 C.POINTER(CRolloutBufs), C.c_void_p]
+    L.wg_gae_pop.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float),
+                             C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_pop_update.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(CPpoBatch), C.c_void_p, C.c_int, C.c_int,
+                                C.POINTER(CPpoHyper), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -281,6 +293,18 @@ class HipBatch:
         """wg_rollout(policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset); ``bufs`` keyed by wg_rollout_bufs' fields."""
         self._rollout("wg_rollout", CRolloutBufs, ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward",
                                                    "truncated"), *args)
+
+    def rollout_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
+        """wg_pop_rollout, the arguments of :meth:`rollout` with a ``population.Population`` in the policy's place: every member
+        samples with the one ``seed``, member ``m``'s noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
+        n, P = len(record), pop.n_members
+        keys = ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward", "truncated")
+        cb = CRolloutBufs(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n,
+                          (C.c_int32 * max(1, n))(*[INFO[r] for r in record]), (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))
+        Bm = self.B // P
+        _chk(self.L.wg_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), (C.c_uint64 * P)(*[int(seed)] * P), counter0,
+                                   (C.c_uint64 * P)(*[int(row_offset) + m * Bm for m in range(P)]), C.byref(cb), self._stream()),
+             "wg_pop_rollout")
 
     def rollout_multi(self, *args):
         """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""

@@ -840,6 +840,9 @@ struct RolloutRows {
     int v_env, v_in;
     const float *v_obs, *v_fin;
     const char* fin_name;
+    // non-null: a population acts in the policy's place (wg_pop_rollout) — its slot table is prepared for these buffers, and a
+    // step's one launch of the policy kernel is wg_pop_launch_ on it instead of wg_policy_eval_
+    wg_pop_s* pop;
 };
 
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
@@ -887,8 +890,11 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
         int nv = 0;
         if (o.value) v[nv++] = {g.v_obs + t * sVO, o.value + t * sV, V};
         if (o.final_value && t > 0) v[nv++] = {g.v_fin + (t - 1) * sVO, o.final_value + (t - 1) * sV, V};
-        rc = wg_policy_eval_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
-                             o.actions + t * sRN, o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
+        if (g.pop)      // (the same rows, found through the population's slot table: step t's own and the final rows of t - 1)
+            rc = wg_pop_launch_(g.pop, 1, t > 0, t, deterministic, counter0 + (uint64_t)t, stream);
+        else
+            rc = wg_policy_eval_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
+                                 o.actions + t * sRN, o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
         if (rc) break;
         if (g.per_agent) {
             h->d.multi_out = o.obs_multi + (t + 1) * sRO;
@@ -906,7 +912,8 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     h->d.multi_fin = fin0;
     if (!rc && o.final_value && n_steps > 0) {
         const WgValueRows v = {g.v_fin + (n_steps - 1) * sVO, o.final_value + (n_steps - 1) * sV, V};
-        rc = wg_policy_eval_(p, 0, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, &v, 1, stream);
+        if (g.pop) rc = wg_pop_launch_(g.pop, 0, 1, n_steps, 1, 0, stream);
+        else rc = wg_policy_eval_(p, 0, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, &v, 1, stream);
     }
     return rc;
 }
@@ -924,6 +931,27 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = use_device(h)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+}
+
+// The population in the policy's place: the checks are wg_rollout's on member 0 (the members share one architecture and device),
+// the loop is rollout_loop with the population's slot table prepared for these buffers.
+extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
+                              const uint64_t* row_offsets, const wg_rollout_bufs* o, void* stream) {
+    if (!h || !q || !o || !seeds) return fail(WG_ERR_INVALID, "wg_pop_rollout: null argument");
+    const int N = h->p.N, O = h->p.obs_dim, B = h->p.B;
+    const RolloutRows g = {"wg_pop_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
+                           nullptr, false,
+                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
+                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
+                           1, O, o->obs, o->final_obs, "final_obs", q};
+    if (int rc = rollout_check(h, q->pol[0], n_steps, deterministic, g)) return rc;
+    if (B % q->P != 0)
+        return fail(WG_ERR_INVALID, "wg_pop_rollout: the " + std::to_string(q->P) + " members own equal shares of the envs, and n_envs = " +
+                                        std::to_string(B) + " does not divide by " + std::to_string(q->P));
+    if (int rc = use_device(h)) return rc;
+    const WgPopRows r = {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, B, 1};
+    if (int rc = wg_pop_prepare_(q, "wg_pop_rollout", B, seeds, row_offsets, &r, stream)) return rc;
+    return rollout_loop(h, q->pol[0], n_steps, deterministic, 0, counter0, 0, g, stream);
 }
 
 extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,

@@ -11,6 +11,9 @@ struct FlowP;
 struct FlowPtrs;
 struct WgParams;
 struct WgPtrs;
+struct WgPopRows;
+struct WgPolicyP;
+struct WgPopMember;
 struct WgValueRows {           // the critic on n_rows rows: obs [n_rows][critic's input width] -> value [n_rows]
     const float* obs;
     float* value;
@@ -24,6 +27,14 @@ int wg_set_last_error_(int code, const char* msg);
 // each of n_v <= 2 row sets of its own (rows of the critic's input width -> value); a set of no rows is skipped
 int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
                     float* action_dev, float* raw_dev, float* logp_dev, const WgValueRows* v, int n_v, void* stream);
+// wg_policy.hip, populations (wg_policy.h): `bytes` (a multiple of 4) of a host table -> device memory by kernel launches in stream
+// order; the slot table of k_policy_pop for n_rows rows shared out among the members (refusals reported as `who`); one launch on it
+int wg_pop_store_(void* dst_dev, const void* src_host, size_t bytes, void* stream);
+int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const WgPopRows* r,
+                    void* stream);
+int wg_pop_launch_(wg_pop q, int head, int fin, int t, int deterministic, uint64_t counter, void* stream);
+// k_policy_pack for each of the n_members rows of a member table (device)
+void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_members, void* stream);
 // wg_flow.hip
 void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
 void wg_launch_windspeed(const FlowP* p, const FlowPtrs* d, int e, int farm, const float* xs, int nx, const float* ys, int ny, float z,

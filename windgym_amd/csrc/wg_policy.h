@@ -67,4 +67,56 @@ struct wg_policy_s {
     float* flat_stage;         // [P.n_flat] staging copy for host-pointer wg_policy_set_params
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Populations (wg_pop): P policies of ONE architecture (one WgPolicyP for all), member m on rows [m Bm, (m + 1) Bm) of every buffer.
+// ---------------------------------------------------------------------------------------------------------------------
+#define WGP_POP_MAX 16       // = WG_POP_MAX of windgym_hip.h
+#define WGP_POP_SLOTS (3 * WGP_POP_MAX)
+
+// One slot of a k_policy_pop launch: ONE net of ONE member on that member's Bm rows.  The table lives in device memory (48
+// slots by value would be 4.5 KB of kernel arguments) and is written once per wg_pop_act / wg_pop_rollout; the pointers are those
+// of step 0, a step t of a rollout reads / writes at pointer + (t + t_shift) * step.  Every slot of a launch has the same number
+// of rows, so blockIdx.x -> (slot, tile) is one scalar division: slot s owns exactly ceil(Bm / 32) workgroups.
+struct WgPopSlot {
+    const float* packed;       // the member's packed weights
+    const float* obs;          // [Bm][the net's input width]
+    float* value;              // [Bm] (critic slots)
+    float *action, *raw, *logp;   // actor slots: the member's first row of the shared [.., B, ..] arrays (null: not wanted)
+    int64_t obs_step, act_step, row_step;   // floats from one step to the next of obs / action, raw / logp, value (0: one call)
+    uint64_t seed, row_offset; // the member's noise key and the global row of its first row
+    int32_t net, t_shift;      // t_shift = -1: the critic on the final rows of the step before
+};
+
+// One member of the training kernels' table (wg_ppo.hip: k_ppo_*_pop, k_policy_pack_pop), written per wg_pop_update
+struct WgPopMember {
+    const float* packed;       // (k_policy_pack_pop writes it)
+    float* params;             // the caller's flat parameters of this member
+    float *m, *v, *grad, *part, *spart, *advstat, *blocksq;   // the member's own wg_ppo buffers
+    const int32_t* perm;       // [n_epochs][rows_m] GLOBAL row ids of the batch
+    float* stats;              // [n_epochs][n_mb][WGT_NSTAT], or the wg_ppo's scratch record with stats_step = 0
+    float clip, vf_coef, ent_coef, max_norm;
+    int32_t normalize, stats_step;
+};
+
+struct wg_ppo_s;
+struct wg_pop_s {
+    int P, device;
+    wg_policy_s* pol[WGP_POP_MAX];
+    wg_ppo_s* opt[WGP_POP_MAX];    // all null: a population that only acts
+    WgPopSlot* slots_dev;          // [WGP_POP_SLOTS]
+    // the slot table's current shape: kinds in the order actor, critic, critic on the final rows; P slots of Bm rows per kind
+    int n_head, has_final, Bm;     // n_head = kinds of a step's own rows (actor and / or critic)
+    void* upd_dev;                 // [WGP_POP_MAX] WgPopMember: the member table of the running wg_pop_update
+};
+
+// what the slots of a population launch read and write; `B` = rows of one step of every buffer (the stride of a rollout's steps)
+struct WgPopRows {
+    const float* obs;
+    float *action, *raw, *logp, *value;
+    const float* final_obs;
+    float* final_value;
+    int64_t B;
+    int stepped;                   // 1: the buffers are a rollout's [T (+ 1), B, ..]; 0: one call, steps are 0
+};
+
 #endif

@@ -11,6 +11,7 @@
 // through LDS in chunks of 256 inputs (n_in <= 2048).  The head's tile is the action mean / the value.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <new>
 #include <string>
 
@@ -50,23 +51,14 @@ __device__ inline float wgp_noise(uint64_t seed, uint64_t counter, uint64_t g, i
     return r * ((j & 1) ? sinf(ph) : cosf(ph));
 }
 
-__global__ __launch_bounds__(WGP_WAVES * 64) void k_policy(const WgPolicyP P, const float* __restrict__ packed,
-                                                           const WgPolicySlots S, const int deterministic, const uint64_t seed,
-                                                           const uint64_t counter, const uint64_t row_offset,
-                                                           float* __restrict__ action, float* __restrict__ raw,
-                                                           float* __restrict__ logp) {
+// One workgroup of k_policy / k_policy_pop: 32 rows (from row0) of ONE net on `n_rows` rows of `obs`.  The actor's outputs and the
+// noise rows are relative to the slot: action / raw / logp point at the slot's first row, row_offset is that row's global index.
+__device__ __forceinline__ void wgp_tile(const WgPolicyP& P, const float* __restrict__ packed, const float* __restrict__ obs,
+                                         float* __restrict__ value, const int net, const int n_rows, const int row0,
+                                         const int deterministic, const uint64_t seed, const uint64_t counter, const uint64_t row_offset,
+                                         float* __restrict__ action, float* __restrict__ raw, float* __restrict__ logp) {
     __shared__ float lds[2][WGP_KC * WGP_TILE];
-    // blockIdx.x -> (slot, tile of 32 rows): slot s owns the workgroups [end[s - 1], end[s]) (wg_policy.h: WgPolicySlots; an unused
-    // slot has end[s] = end[s - 1]).  A 1-D grid of exactly the tiles each slot has: the slots of the closed loop differ by a factor
-    // n_turb in rows (the actor on B * N agent rows, the critic on B env rows, wg_rollout_multi's central mode), so a 2-D grid
-    // (tiles of the largest slot) x slots would launch mostly workgroups that have nothing to do.
-    const int bid = blockIdx.x;
-    const int slot = (bid >= S.end[0] ? 1 : 0) + (bid >= S.end[1] ? 1 : 0);
-    const int net = S.net[slot], n_rows = S.n_rows[slot];
-    const float* __restrict__ obs = S.obs[slot];
-    float* __restrict__ value = S.value[slot];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int row0 = (bid - (slot ? S.end[slot - 1] : 0)) * WGP_TILE;
     const int L = P.n_layers[net];
     int cur = 0;                                  // LDS buffer that holds the running layer's input
     for (int l = 0; l < L; ++l) {
@@ -181,8 +173,41 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_policy(const WgPolicyP P, co
     }
 }
 
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_policy(const WgPolicyP P, const float* __restrict__ packed,
+                                                           const WgPolicySlots S, const int deterministic, const uint64_t seed,
+                                                           const uint64_t counter, const uint64_t row_offset,
+                                                           float* __restrict__ action, float* __restrict__ raw,
+                                                           float* __restrict__ logp) {
+    // blockIdx.x -> (slot, tile of 32 rows): slot s owns the workgroups [end[s - 1], end[s]) (wg_policy.h: WgPolicySlots; an unused
+    // slot has end[s] = end[s - 1]).  A 1-D grid of exactly the tiles each slot has: the slots of the closed loop differ by a factor
+    // n_turb in rows (the actor on B * N agent rows, the critic on B env rows, wg_rollout_multi's central mode), so a 2-D grid
+    // (tiles of the largest slot) x slots would launch mostly workgroups that have nothing to do.
+    const int bid = blockIdx.x;
+    const int slot = (bid >= S.end[0] ? 1 : 0) + (bid >= S.end[1] ? 1 : 0);
+    const int row0 = (bid - (slot ? S.end[slot - 1] : 0)) * WGP_TILE;
+    wgp_tile(P, packed, S.obs[slot], S.value[slot], S.net[slot], S.n_rows[slot], row0, deterministic, seed, counter, row_offset, action,
+             raw, logp);
+}
+
+// The population's launch: slots [first_slot, first_slot + gridDim.x / tiles) of the table, each a member's net on ITS n_rows rows
+// with ITS weights, seed and row offset (wg_policy.h: WgPopSlot).  The slot is a function of blockIdx.x alone, so the table is
+// read through scalar loads; what a workgroup then computes is wgp_tile on the member's pointers — the arithmetic of k_policy.
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_policy_pop(const WgPolicyP P, const WgPopSlot* __restrict__ slots,
+                                                               const int first_slot, const int tiles, const int n_rows, const int t,
+                                                               const int deterministic, const uint64_t counter) {
+    const int bid = blockIdx.x, sl = bid / tiles;
+    const WgPopSlot* __restrict__ s = slots + first_slot + sl;
+    const int64_t tt = (int64_t)t + s->t_shift;
+    float* const value = s->value ? s->value + tt * s->row_step : nullptr;
+    float* const action = s->action ? s->action + tt * s->act_step : nullptr;
+    float* const raw = s->raw ? s->raw + tt * s->act_step : nullptr;
+    float* const logp = s->logp ? s->logp + tt * s->row_step : nullptr;
+    wgp_tile(P, s->packed, s->obs + tt * s->obs_step, value, s->net, n_rows, (bid - sl * tiles) * WGP_TILE, deterministic, s->seed,
+             counter, s->row_offset, action, raw, logp);
+}
+
 // flat -> packed (wg_policy.h); one thread per packed float
-__global__ void k_policy_pack(const WgPolicyP P, const float* __restrict__ flat, float* __restrict__ packed) {
+__device__ __forceinline__ void wgp_pack(const WgPolicyP& P, const float* __restrict__ flat, float* __restrict__ packed) {
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P.n_packed) return;
     float v = 0.0f;
@@ -202,6 +227,14 @@ __global__ void k_policy_pack(const WgPolicyP P, const float* __restrict__ flat,
     if (P.has_log_std && idx >= P.log_std_packed && idx < P.log_std_packed + (uint32_t)P.n_out)
         v = flat[P.log_std_flat + (idx - P.log_std_packed)];
     packed[idx] = v;
+}
+
+__global__ void k_policy_pack(const WgPolicyP P, const float* __restrict__ flat, float* __restrict__ packed) { wgp_pack(P, flat, packed); }
+
+// every member of a population: blockIdx.y = member, params -> its policy's packed copy
+__global__ void k_policy_pack_pop(const WgPolicyP P, const WgPopMember* __restrict__ mt) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.y;
+    wgp_pack(P, M->params, const_cast<float*>(M->packed));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -368,4 +401,110 @@ extern "C" int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int 
     const WgValueRows v = {obs_dev, value_dev, n_rows};
     return wg_policy_eval_(p, n_rows, obs_dev, deterministic, seed, counter, row_offset, action_dev, raw_dev, logp_dev, &v,
                            value_dev ? 1 : 0, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// populations: the slot table of k_policy_pop and its launches (wg_pop_create / wg_pop_destroy: wg_ppo.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+static int pop_use_device(wg_pop_s* q) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != q->device) PHIPCHK(hipSetDevice(q->device));
+    return 0;
+}
+
+// A host table -> device memory in stream order WITHOUT a copy engine or a host synchronisation (a hipMemcpyAsync from pageable
+// memory waits for the stream): the bytes travel as kernel arguments, 2 KB per launch, and one thread per word stores them.
+struct WgPopWords { uint32_t w[512]; };
+__global__ void k_pop_store(const WgPopWords c, uint32_t* __restrict__ dst, const int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = c.w[i];
+}
+
+extern "C" int wg_pop_store_(void* dst_dev, const void* src_host, size_t bytes, void* stream) {
+    for (size_t o = 0; o < bytes; o += sizeof(WgPopWords)) {
+        WgPopWords c;
+        const size_t nb = bytes - o < sizeof(WgPopWords) ? bytes - o : sizeof(WgPopWords);
+        memcpy(c.w, (const char*)src_host + o, nb);
+        hipLaunchKernelGGL(k_pop_store, dim3(2), dim3(256), 0, (hipStream_t)stream, c, (uint32_t*)((char*)dst_dev + o), (int)((nb + 3) / 4));
+    }
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
+// k_policy_pack for every member of the table (wg_pop_update: after Adam's step)
+extern "C" void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_members, void* stream) {
+    hipLaunchKernelGGL(k_policy_pack_pop, dim3((P->n_packed + 255) / 256, n_members), dim3(256), 0, (hipStream_t)stream, *P, mt);
+}
+
+// Write the slot table for `n_rows` rows split evenly among the members: P actor slots (when an actor output is wanted), P critic
+// slots (r->value), P critic slots on the final rows (r->final_value), in this order, stored in stream order (launches enqueued
+// before on the same stream still read the old table: a population is used on one stream at a time).
+extern "C" int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets,
+                               const WgPopRows* r, void* stream) {
+    const std::string w = who;
+    const WgPolicyP& P = q->pol[0]->P;
+    if (n_rows < 0) return pfail(WG_ERR_INVALID, w + ": n_rows < 0");
+    if (n_rows % q->P != 0)
+        return pfail(WG_ERR_INVALID, w + ": the " + std::to_string(q->P) + " members own equal shares of the rows, and " +
+                                         std::to_string(n_rows) + " rows do not divide by " + std::to_string(q->P));
+    const bool actor = r->action || r->raw || r->logp;
+    if ((r->value || r->final_value) && P.n_layers[1] == 0) return pfail(WG_ERR_INVALID, w + ": value requested from policies without a critic");
+    if (actor && !seeds) return pfail(WG_ERR_INVALID, w + ": seeds[P] is required");
+    const int Bm = n_rows / q->P;
+    const int64_t step = r->stepped ? r->B : 0;
+    WgPopSlot tab[WGP_POP_SLOTS] = {};
+    int ns = 0;
+    for (int kind = 0; kind < 3; ++kind) {
+        if (kind == 0 ? !actor : kind == 1 ? !r->value : !r->final_value) continue;
+        for (int m = 0; m < q->P; ++m) {
+            WgPopSlot& s = tab[ns++];
+            const size_t row = (size_t)m * Bm;
+            const int width = kind == 0 ? P.n_in : P.n_in_vf;
+            s.packed = q->pol[m]->packed;
+            s.obs = (kind == 2 ? r->final_obs : r->obs) + row * width;
+            s.obs_step = step * width; s.act_step = step * P.n_out; s.row_step = step;
+            s.net = kind == 0 ? 0 : 1;
+            s.t_shift = kind == 2 ? -1 : 0;
+            if (kind == 0) {
+                s.action = r->action ? r->action + row * P.n_out : nullptr;
+                s.raw = r->raw ? r->raw + row * P.n_out : nullptr;
+                s.logp = r->logp ? r->logp + row : nullptr;
+                s.seed = seeds[m];
+                s.row_offset = row_offsets ? row_offsets[m] : 0;
+            } else {
+                s.value = (kind == 1 ? r->value : r->final_value) + row;
+            }
+        }
+    }
+    q->n_head = (actor ? 1 : 0) + (r->value ? 1 : 0);
+    q->has_final = r->final_value ? 1 : 0;
+    q->Bm = Bm;
+    if (ns == 0 || Bm == 0) return 0;
+    if (int rc = pop_use_device(q)) return rc;
+    return wg_pop_store_(q->slots_dev, tab, sizeof(WgPopSlot) * ns, stream);
+}
+
+// ONE launch of k_policy_pop on the prepared table: the kinds of step t's own rows (`head`: actor and / or critic) and / or the
+// critic on the final rows of step t - 1 (`fin`)
+extern "C" int wg_pop_launch_(wg_pop q, int head, int fin, int t, int deterministic, uint64_t counter, void* stream) {
+    const int kinds = (head ? q->n_head : 0) + (fin ? q->has_final : 0);
+    if (kinds == 0 || q->Bm == 0) return 0;
+    const int first = head ? 0 : q->n_head * q->P, tiles = (q->Bm + WGP_TILE - 1) / WGP_TILE;
+    if (int rc = pop_use_device(q)) return rc;
+    hipLaunchKernelGGL(k_policy_pop, dim3(kinds * q->P * tiles), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, q->pol[0]->P, q->slots_dev,
+                       first, tiles, q->Bm, t, deterministic ? 1 : 0, counter);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return pfail(WG_ERR_HIP, std::string("wg_pop: kernel launch failed: ") + hipGetErrorString(le));
+    return 0;
+}
+
+extern "C" int wg_pop_act(wg_pop q, int n_rows, const float* obs_dev, int deterministic, const uint64_t* seeds, uint64_t counter,
+                          const uint64_t* row_offsets, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream) {
+    if (!q || !obs_dev) return pfail(WG_ERR_INVALID, "wg_pop_act: null argument");
+    const WgPolicyP& P = q->pol[0]->P;
+    if ((action_dev || raw_dev || logp_dev) && !P.has_log_std && (!deterministic || logp_dev))
+        return pfail(WG_ERR_INVALID, "wg_pop_act: a stochastic action / a log-probability needs policies with log_std");
+    const WgPopRows r = {obs_dev, action_dev, raw_dev, logp_dev, value_dev, nullptr, nullptr, n_rows, 0};
+    if (int rc = wg_pop_prepare_(q, "wg_pop_act", n_rows, seeds, row_offsets, &r, stream)) return rc;
+    return wg_pop_launch_(q, 1, 0, 0, deterministic, counter, stream);
 }

@@ -40,12 +40,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // One thread per AGENT row of a [T, B, A] rollout whose reward and truncation flag belong to the env (a farm's turbines share
 // the farm reward; A = 1: one row per env, wg_gae): consecutive threads walk consecutive agent rows, the two [B] arrays are
 // read once per thread (the A threads of an env fetch the same word: one transaction).
-__global__ void k_gae(const int T, const int B, const int A, const float* __restrict__ reward, const float* __restrict__ value,
-                      const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const float gamma,
-                      const float lambda, float* __restrict__ adv, float* __restrict__ ret) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void gae_row(const int T, const int B, const int A, const int r, const float* __restrict__ reward,
+                                        const float* __restrict__ value, const float* __restrict__ final_value,
+                                        const uint8_t* __restrict__ truncated, const float gamma, const float lambda,
+                                        float* __restrict__ adv, float* __restrict__ ret) {
     const int R = B * A;
-    if (r >= R) return;
     const int b = r / A;
     float a = 0.0f;
     for (int t = T - 1; t >= 0; --t) {
@@ -56,6 +55,25 @@ __global__ void k_gae(const int T, const int B, const int A, const float* __rest
         adv[o] = a;
         ret[o] = a + v;
     }
+}
+
+__global__ void k_gae(const int T, const int B, const int A, const float* __restrict__ reward, const float* __restrict__ value,
+                      const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const float gamma,
+                      const float lambda, float* __restrict__ adv, float* __restrict__ ret) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= B * A) return;
+    gae_row(T, B, A, r, reward, value, final_value, truncated, gamma, lambda, adv, ret);
+}
+
+// a population's [T, B]: column r belongs to member r / Bm and runs the recurrence with that member's gamma and lambda
+struct WgPopGae { float gamma[WGP_POP_MAX], lambda[WGP_POP_MAX]; };
+__global__ void k_gae_pop(const int T, const int B, const int Bm, const float* __restrict__ reward, const float* __restrict__ value,
+                          const float* __restrict__ final_value, const uint8_t* __restrict__ truncated, const WgPopGae hy,
+                          float* __restrict__ adv, float* __restrict__ ret) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= B) return;
+    const int m = r / Bm;
+    gae_row(T, B, 1, r, reward, value, final_value, truncated, hy.gamma[m], hy.lambda[m], adv, ret);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -83,9 +101,8 @@ __device__ inline int ppo_row(const int32_t* index, int64_t first, int n, int64_
 
 // advstat[0] = mean, advstat[1] = unbiased std (torch.std) of the minibatch's advantages; entry id (an agent row) carries the
 // advantage of its env row id / agents (agents = 1: its own)
-__global__ __launch_bounds__(1024) void k_ppo_advstat(const float* __restrict__ adv, const int32_t* __restrict__ index,
-                                                      const int64_t first, const int n, const int64_t n_total, const int agents,
-                                                      float* __restrict__ advstat) {
+__device__ __forceinline__ void ppo_advstat(const float* __restrict__ adv, const int32_t* __restrict__ index, const int64_t first,
+                                            const int n, const int64_t n_total, const int agents, float* __restrict__ advstat) {
     __shared__ float sh[1024];
     float s = 0.0f;
     for (int i = threadIdx.x; i < n; i += 1024) {
@@ -100,6 +117,22 @@ __global__ __launch_bounds__(1024) void k_ppo_advstat(const float* __restrict__ 
     }
     const float var = block_sum<1024>(q, sh) / (float)(n - 1);
     if (threadIdx.x == 0) { advstat[0] = mean; advstat[1] = sqrtf(var); }
+}
+
+__global__ __launch_bounds__(1024) void k_ppo_advstat(const float* __restrict__ adv, const int32_t* __restrict__ index,
+                                                      const int64_t first, const int n, const int64_t n_total, const int agents,
+                                                      float* __restrict__ advstat) {
+    ppo_advstat(adv, index, first, n, n_total, agents, advstat);
+}
+
+// The population's kernels (k_*_pop): one more grid axis = member, whose row of the member table (wg_policy.h: WgPopMember) gives
+// the pointers and hyper-parameters that the single-policy kernel takes as arguments; the arithmetic is the shared body's.  The
+// minibatch of member m is perm[off .. off + n) of ITS permutations; `mb` is the minibatch's ordinal e * n_mb + k.
+__global__ __launch_bounds__(1024) void k_ppo_advstat_pop(const WgPopMember* __restrict__ mt, const float* __restrict__ adv,
+                                                          const int64_t off, const int n, const int64_t n_total) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.x;
+    if (!(M->normalize && n > 1)) return;
+    ppo_advstat(adv, M->perm + off, 0, n, n_total, 1, M->advstat);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -122,7 +155,10 @@ struct WgPpoArgs {
     float* spart;              // [G][4]
 };
 
-__global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
+// (`a`: what the launch's workgroups share; the remaining arguments are `a`'s own for one policy, the member's for a population)
+__device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, const WgPpoArgs& a, const float* a_packed,
+                                         const float* a_flat, const int32_t* a_index, const int a_normalize, const float a_clip,
+                                         const float a_vf_coef, const float* a_advstat, float* a_part, float* a_spart) {
     extern __shared__ float lds[];
     const int net = blockIdx.y, g = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
@@ -133,7 +169,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
     float* xin = lds + M.xin;
     float* rowv = lds + M.rowv;
     int* rid = (int*)(lds + M.rid);
-    float* part = a.part + (size_t)g * P.n_flat;
+    float* part = a_part + (size_t)g * P.n_flat;
     const int ntile = (a.n + R - 1) / R;
     const float inv_n = 1.0f / (float)a.n;
     const bool tanh_act = P.activation != WG_ACTV_RELU;
@@ -146,7 +182,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
         // rid = the row THIS net gathers: the minibatch entry (an agent row) for the actor, its env row for the critic — the one
         // division per tile row; the gather loops below only multiply
         if (tid < 32) {
-            int id = tid < R ? ppo_row(a.index, a.first, a.n, a.n_total, row0 + tid) : -1;
+            int id = tid < R ? ppo_row(a_index, a.first, a.n, a.n_total, row0 + tid) : -1;
             if (net == 1 && id >= 0) id /= a.agents;
             rid[tid] = id;
         }
@@ -159,7 +195,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
             for (int t = 0; t < 2; ++t) {
                 const int ot = wave + WGT_WAVES * t;
                 if (ot < ly.ntiles) {
-                    const float* bp = a.packed + ly.b_packed + ot * 32 + 4 * h;
+                    const float* bp = a_packed + ly.b_packed + ot * 32 + 4 * h;
 #pragma unroll
                     for (int q = 0; q < 16; ++q) acc[t][q] = bp[(q & 3) + 8 * (q >> 2)];
                 }
@@ -181,7 +217,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                 for (int t = 0; t < 2; ++t) {
                     const int ot = wave + WGT_WAVES * t;
                     if (ot < ly.ntiles) {
-                        const float* wp = a.packed + ly.w_packed + ((size_t)ot * ly.nks + (k0 >> 1)) * 64 + lane;
+                        const float* wp = a_packed + ly.w_packed + ((size_t)ot * ly.nks + (k0 >> 1)) * 64 + lane;
                         for (int ks = 0; ks < nks; ++ks) {
                             const int k = 2 * ks + h;
                             const float av = wp[(size_t)ks * 64];
@@ -220,7 +256,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                 if (id >= 0) {
                     float lp = 0.0f;
                     for (int j = 0; j < n_out; ++j) {
-                        const float ls = a.flat[P.log_std_flat + j];
+                        const float ls = a_flat[P.log_std_flat + j];
                         const float z = (a.raw[(size_t)id * n_out + j] - hb[j * S + tid]) / expf(ls);
                         hb[j * S + tid] = z;
                         lp += -0.5f * z * z - ls - WGT_HALF_LOG_2PI;
@@ -228,12 +264,12 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                     const float lr = lp - a.logp_old[id];
                     const float ratio = expf(lr);
                     float A = a.adv[id / a.agents];       // the env row's advantage, shared by its agents
-                    if (a.normalize) A = (A - a.advstat[0]) / (a.advstat[1] + 1e-8f);
-                    const float rc = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
+                    if (a_normalize) A = (A - a_advstat[0]) / (a_advstat[1] + 1e-8f);
+                    const float rc = fminf(fmaxf(ratio, 1.0f - a_clip), 1.0f + a_clip);
                     const float s1 = ratio * A, s2 = rc * A;
                     lpi = -fminf(s1, s2);
                     kl = expm1f(lr) - lr;                   // (ratio - 1) - log ratio without the cancellation at ratio = 1
-                    cf = fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
+                    cf = fabsf(ratio - 1.0f) > a_clip ? 1.0f : 0.0f;
                     dlogp = (ratio == rc || s1 < s2) ? -A * ratio * inv_n : 0.0f;
                 } else {
                     for (int j = 0; j < n_out; ++j) hb[j * S + tid] = 0.0f;
@@ -243,7 +279,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
             __syncthreads();
             for (int idx = tid; idx < n_out * R; idx += WGT_WAVES * 64) {
                 const int j = idx / R, row = idx - j * R;
-                d0[j * S + row] = rowv[row] * hb[j * S + row] / expf(a.flat[P.log_std_flat + j]);
+                d0[j * S + row] = rowv[row] * hb[j * S + row] / expf(a_flat[P.log_std_flat + j]);
             }
             if (tid < n_out) {                              // d loss / d log_std_j through logp: sum_row dlogp (z^2 - 1)
                 float s = 0.0f;
@@ -260,7 +296,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
                 if (id >= 0) {
                     const float e = hb[tid] - a.ret[id];
                     lv = e * e;
-                    dv = a.vf_coef * 2.0f * e * inv_n;
+                    dv = a_vf_coef * 2.0f * e * inv_n;
                 }
                 d0[tid] = dv;
                 rowv[tid] = lv;
@@ -326,7 +362,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
             if (l > 0) {
                 float* dp = lds + M.d[cur ^ 1];
                 const float* y = lds + M.act[l - 1];
-                const float* wf = a.flat + ly.w_flat;
+                const float* wf = a_flat + ly.w_flat;
                 const int nkt = (ly.K + 31) >> 5, nis = (ly.M + 1) >> 1;
                 for (int kt = wave; kt < nkt; kt += WGT_WAVES) {
                     const int kk = kt * 32 + r;
@@ -354,18 +390,28 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, 
         }
     }
     if (tid == 0) {
-        float* sp = a.spart + (size_t)g * 4;
+        float* sp = a_spart + (size_t)g * 4;
         if (net == 0) { sp[0] = st0; sp[1] = st1; sp[2] = st2; }
         else sp[3] = st0;
     }
 }
 
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
+    ppo_grad(P, K, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+}
+
+// grid (G, 2, P); `c` carries what the members share (the batch, n, G), the member's row the rest
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_pop(const WgPolicyP P, const WgPpoK K, const WgPpoArgs c,
+                                                                 const WgPopMember* __restrict__ mt, const int64_t off) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.z;
+    ppo_grad(P, K, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+}
+
 // partials -> flat gradient (+ the entropy term's constant gradient on log_std) and the statistics record
-__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_reduce(const WgPolicyP P, const float* __restrict__ part,
-                                                           const float* __restrict__ spart, const int G, const int n,
-                                                           const float vf_coef, const float ent_coef, const int normalize,
-                                                           const float* __restrict__ advstat, const float* __restrict__ flat,
-                                                           float* __restrict__ grad, float* __restrict__ stats) {
+__device__ __forceinline__ void ppo_reduce(const WgPolicyP& P, const float* __restrict__ part, const float* __restrict__ spart,
+                                           const int G, const int n, const float vf_coef, const float ent_coef, const int normalize,
+                                           const float* __restrict__ advstat, const float* __restrict__ flat,
+                                           float* __restrict__ grad, float* __restrict__ stats) {
     const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
     if (p < P.n_flat) {
         float s = 0.0f;
@@ -396,9 +442,23 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_reduce(const WgPolicyP P, con
     }
 }
 
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_reduce(const WgPolicyP P, const float* __restrict__ part,
+                                                           const float* __restrict__ spart, const int G, const int n,
+                                                           const float vf_coef, const float ent_coef, const int normalize,
+                                                           const float* __restrict__ advstat, const float* __restrict__ flat,
+                                                           float* __restrict__ grad, float* __restrict__ stats) {
+    ppo_reduce(P, part, spart, G, n, vf_coef, ent_coef, normalize, advstat, flat, grad, stats);
+}
+
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_reduce_pop(const WgPolicyP P, const WgPopMember* __restrict__ mt, const int G,
+                                                               const int n, const int mb) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.y;
+    ppo_reduce(P, M->part, M->spart, G, n, M->vf_coef, M->ent_coef, M->normalize && n > 1, M->advstat, M->params, M->grad,
+               M->stats + (size_t)mb * M->stats_step);
+}
+
 // blocksq[b] = sum of squares of block b's 256 gradient entries (fixed tree)
-__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_sumsq(const float* __restrict__ grad, const uint32_t n_flat,
-                                                          float* __restrict__ blocksq) {
+__device__ __forceinline__ void ppo_sumsq(const float* __restrict__ grad, const uint32_t n_flat, float* __restrict__ blocksq) {
     __shared__ float sh[WGT_BLOCK];
     const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
     const float gv = p < n_flat ? grad[p] : 0.0f;
@@ -406,12 +466,21 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_sumsq(const float* __restrict
     if (threadIdx.x == 0) blocksq[blockIdx.x] = s;
 }
 
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_sumsq(const float* __restrict__ grad, const uint32_t n_flat,
+                                                          float* __restrict__ blocksq) {
+    ppo_sumsq(grad, n_flat, blocksq);
+}
+
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_sumsq_pop(const WgPopMember* __restrict__ mt, const uint32_t n_flat) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.y;
+    ppo_sumsq(M->grad, n_flat, M->blocksq);
+}
+
 // clip by the global norm, then torch.optim.Adam's step (no weight decay, no amsgrad) on params in place
-__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam(float* __restrict__ params, const float* __restrict__ grad,
-                                                         float* __restrict__ m, float* __restrict__ v, const uint32_t n_flat,
-                                                         const float* __restrict__ blocksq, const uint32_t n_blocks,
-                                                         const float max_norm, const float step_size, const float bc2_sqrt,
-                                                         const float omb1, const float beta2, const float omb2, const float eps) {
+__device__ __forceinline__ void ppo_adam(float* __restrict__ params, const float* __restrict__ grad, float* __restrict__ m,
+                                         float* __restrict__ v, const uint32_t n_flat, const float* __restrict__ blocksq,
+                                         const uint32_t n_blocks, const float max_norm, const float step_size, const float bc2_sqrt,
+                                         const float omb1, const float beta2, const float omb2, const float eps) {
     __shared__ float sh[WGT_BLOCK];
     float s = 0.0f;
     for (uint32_t b = threadIdx.x; b < n_blocks; b += WGT_BLOCK) s += blocksq[b];
@@ -425,6 +494,24 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam(float* __restrict__ para
     m[p] = mv; v[p] = vv;
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
     params[p] = params[p] - step_size * (mv / denom);
+}
+
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam(float* __restrict__ params, const float* __restrict__ grad,
+                                                         float* __restrict__ m, float* __restrict__ v, const uint32_t n_flat,
+                                                         const float* __restrict__ blocksq, const uint32_t n_blocks,
+                                                         const float max_norm, const float step_size, const float bc2_sqrt,
+                                                         const float omb1, const float beta2, const float omb2, const float eps) {
+    ppo_adam(params, grad, m, v, n_flat, blocksq, n_blocks, max_norm, step_size, bc2_sqrt, omb1, beta2, omb2, eps);
+}
+
+// (step size and bias correction depend on the member's own step count and learning rate: computed by the host, as for one policy)
+struct WgPopAdam { float step_size[WGP_POP_MAX], bc2_sqrt[WGP_POP_MAX]; };
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam_pop(const WgPopMember* __restrict__ mt, const uint32_t n_flat,
+                                                             const uint32_t n_blocks, const WgPopAdam A, const float omb1,
+                                                             const float beta2, const float omb2, const float eps) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.y;
+    ppo_adam(M->params, M->grad, M->m, M->v, n_flat, M->blocksq, n_blocks, M->max_norm, A.step_size[blockIdx.y], A.bc2_sqrt[blockIdx.y],
+             omb1, beta2, omb2, eps);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -716,4 +803,153 @@ extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b,
     if (int rc = t_refuse_split("wg_ppo_update", o)) return rc;
     const wg_ppo_batch_shared sb = {*b, b->obs, 1};
     return update_entry("wg_ppo_update", o, params_dev, &sb, perm_dev, n_epochs, batch_size, hp, lr, max_grad_norm, stats_out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// populations (windgym_hip.h: wg_pop_*; the slot table and the launches of the policy kernel: wg_policy.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P, wg_pop* out) {
+    if (!members || !out) return tfail(WG_ERR_INVALID, "wg_pop_create: null argument");
+    *out = nullptr;
+    if (P < 1 || P > WG_POP_MAX)
+        return tfail(WG_ERR_INVALID, "wg_pop_create: a population has 1 .. " + std::to_string(WG_POP_MAX) + " members, not " + std::to_string(P));
+    for (int m = 0; m < P; ++m) {
+        const std::string who = "wg_pop_create: member " + std::to_string(m);
+        if (!members[m]) return tfail(WG_ERR_INVALID, who + " is null");
+        const WgPolicyP &A = members[0]->P, &Q = members[m]->P;
+        if (Q.n_layers[1] != 0 && Q.n_in_vf != Q.n_in)
+            return tfail(WG_ERR_INVALID, who + " is a split policy (its critic reads " + std::to_string(Q.n_in_vf) + " inputs, its actor " +
+                                             std::to_string(Q.n_in) + "): populations take policies whose nets read the same rows");
+        if (members[m]->device != members[0]->device)
+            return tfail(WG_ERR_INVALID, who + " lives on device " + std::to_string(members[m]->device) + ", member 0 on device " +
+                                             std::to_string(members[0]->device));
+        // the layer table is a function of the wg_policy_desc alone: equal descs <=> equal tables
+        bool same = Q.n_in == A.n_in && Q.n_out == A.n_out && Q.activation == A.activation && Q.has_log_std == A.has_log_std &&
+                    Q.n_in_vf == A.n_in_vf && Q.n_layers[0] == A.n_layers[0] && Q.n_layers[1] == A.n_layers[1] && Q.n_flat == A.n_flat;
+        for (int net = 0; net < 2 && same; ++net)
+            for (int l = 0; l < Q.n_layers[net]; ++l) same = same && Q.layer[net][l].K == A.layer[net][l].K && Q.layer[net][l].M == A.layer[net][l].M;
+        if (!same) return tfail(WG_ERR_INVALID, who + " has another architecture than member 0: the members of a population share one");
+        for (int k = 0; k < m; ++k)
+            if (members[k] == members[m]) return tfail(WG_ERR_INVALID, who + " is the same policy as member " + std::to_string(k));
+        if (opts) {
+            if (!opts[m]) return tfail(WG_ERR_INVALID, who + ": its wg_ppo is null (opts = NULL makes a population that only acts)");
+            if (opts[m]->pol != members[m]) return tfail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another policy");
+        }
+    }
+    wg_pop_s* q = new (std::nothrow) wg_pop_s();
+    if (!q) return tfail(WG_ERR_NOMEM, "wg_pop_create: out of host memory");
+    q->P = P;
+    q->device = members[0]->device;
+    for (int m = 0; m < P; ++m) { q->pol[m] = members[m]; q->opt[m] = opts ? opts[m] : nullptr; }
+    hipError_t e = hipSetDevice(q->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&q->slots_dev, sizeof(WgPopSlot) * WGP_POP_SLOTS);
+    if (e == hipSuccess) e = hipMalloc(&q->upd_dev, sizeof(WgPopMember) * WGP_POP_MAX);
+    if (e != hipSuccess) {
+        wg_pop_destroy(q);
+        return tfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_pop_create: ") + hipGetErrorString(e));
+    }
+    *out = q;
+    return 0;
+}
+
+extern "C" int wg_pop_destroy(wg_pop q) {
+    if (!q) return 0;
+    if (hipSetDevice(q->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        if (q->slots_dev) (void)hipFree(q->slots_dev);
+        if (q->upd_dev) (void)hipFree(q->upd_dev);
+    }
+    delete q;
+    return 0;
+}
+
+extern "C" int wg_gae_pop(int T, int B, int P, const float* reward_dev, const float* value_dev, const float* final_value_dev,
+                          const uint8_t* truncated_dev, const float* gamma, const float* lambda, float* advantage_out,
+                          float* returns_out, void* stream) {
+    if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !gamma || !lambda || !advantage_out || !returns_out)
+        return tfail(WG_ERR_INVALID, "wg_gae_pop: null argument");
+    if (T < 1 || B < 1) return tfail(WG_ERR_INVALID, "wg_gae_pop: T and B must be >= 1");
+    if (P < 1 || P > WG_POP_MAX || B % P != 0)
+        return tfail(WG_ERR_INVALID, "wg_gae_pop: P = " + std::to_string(P) + " must lie in 1 .. " + std::to_string(WG_POP_MAX) +
+                                         " and divide B = " + std::to_string(B));
+    if (B > 0x7fffffff - 256) return tfail(WG_ERR_UNSUPPORTED, "wg_gae_pop: more than 2^31 rows");
+    WgPopGae hy = {};
+    for (int m = 0; m < P; ++m) { hy.gamma[m] = gamma[m]; hy.lambda[m] = lambda[m]; }
+    hipLaunchKernelGGL(k_gae_pop, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, B / P, reward_dev, value_dev,
+                       final_value_dev, truncated_dev, hy, advantage_out, returns_out);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
+                             int batch_size, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm,
+                             wg_ppo_stats* stats_out, void* stream) {
+    if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return tfail(WG_ERR_INVALID, "wg_pop_update: null argument");
+    const int P = q->P;
+    if (!q->opt[0]) return tfail(WG_ERR_INVALID, "wg_pop_update: the population was created without optimisers (opts = NULL): it only acts");
+    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns) return tfail(WG_ERR_INVALID, "wg_pop_update: a batch pointer is null");
+    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, "wg_pop_update: n_rows out of range");
+    if (b->n_rows % P != 0)
+        return tfail(WG_ERR_INVALID, "wg_pop_update: the " + std::to_string(P) + " members own equal shares of the batch, and " +
+                                         std::to_string(b->n_rows) + " rows do not divide by " + std::to_string(P));
+    if (n_epochs < 1 || batch_size < 1) return tfail(WG_ERR_INVALID, "wg_pop_update: n_epochs and batch_size must be >= 1");
+    if (int rc = t_use_device(q->device)) return rc;
+    for (int m = 0; m < P; ++m) {
+        const std::string who = "wg_pop_update: member " + std::to_string(m);
+        if (!params_dev[m]) return tfail(WG_ERR_INVALID, who + ": params_dev is null");
+        if (!(hp[m].clip_range >= 0.0f)) return tfail(WG_ERR_INVALID, who + ": clip_range < 0");
+        if (!(max_grad_norm[m] > 0.0f)) return tfail(WG_ERR_INVALID, who + ": max_grad_norm must be > 0");
+        if (int rc = t_on_device(params_dev[m], q->device, (who + ": params_dev").c_str())) return rc;
+    }
+    if (int rc = t_on_device(b->obs, q->device, "wg_pop_update: obs")) return rc;
+    if (int rc = t_on_device(perm_dev, q->device, "wg_pop_update: perm_dev")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rows_m = b->n_rows / P;
+    const int n_mb = (int)((rows_m + batch_size - 1) / batch_size);
+    WgPopMember tab[WGP_POP_MAX] = {};
+    for (int m = 0; m < P; ++m) {
+        wg_ppo_s* o = q->opt[m];
+        WgPopMember& M = tab[m];
+        M.packed = o->pol->packed; M.params = params_dev[m];
+        M.m = o->m; M.v = o->v; M.grad = o->grad; M.part = o->part; M.spart = o->spart; M.advstat = o->advstat; M.blocksq = o->blocksq;
+        M.perm = perm_dev + (size_t)m * n_epochs * rows_m;
+        M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->stats;
+        M.stats_step = stats_out ? WGT_NSTAT : 0;
+        M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef; M.max_norm = max_grad_norm[m];
+        M.normalize = hp[m].normalize_advantage != 0;
+    }
+    const WgPopMember* mt = (const WgPopMember*)q->upd_dev;
+    if (int rc = wg_pop_store_(q->upd_dev, tab, sizeof(WgPopMember) * P, stream)) return rc;
+    // every member has the architecture of member 0: one layer table, one LDS map, one G per minibatch size
+    const wg_ppo_s* o0 = q->opt[0];
+    const WgPolicyP& PP = o0->pol->P;
+    bool any_norm = false;
+    for (int m = 0; m < P; ++m) any_norm = any_norm || tab[m].normalize;
+    const double b1 = 0.9, b2 = 0.999;
+    for (int e = 0; e < n_epochs; ++e)
+        for (int k = 0; k < n_mb; ++k) {
+            const int64_t start = (int64_t)k * batch_size, off = (int64_t)e * rows_m + start;
+            const int n = (int)(rows_m - start < batch_size ? rows_m - start : batch_size), mb = e * n_mb + k;
+            const int R = o0->K.R, ntile = (n + R - 1) / R, G = ntile < o0->g_max ? ntile : o0->g_max;
+            if (any_norm && n > 1) hipLaunchKernelGGL(k_ppo_advstat_pop, dim3(P), dim3(1024), 0, st, mt, b->advantage, off, n, b->n_rows);
+            WgPpoArgs a = {};
+            a.obs[0] = b->obs; a.obs[1] = b->obs; a.agents = 1; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage; a.ret = b->returns;
+            a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
+            hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), o0->lds_bytes, st, PP, o0->K, a, mt, off);
+            hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
+            WgPopAdam A = {};
+            for (int m = 0; m < P; ++m) {                  // (t_apply's arithmetic, per member)
+                wg_ppo_s* o = q->opt[m];
+                o->step += 1;
+                const double bc1 = 1.0 - std::pow(b1, (double)o->step), bc2 = 1.0 - std::pow(b2, (double)o->step);
+                A.step_size[m] = (float)((double)lr[m] / bc1);
+                A.bc2_sqrt[m] = (float)std::sqrt(bc2);
+            }
+            hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat);
+            hipLaunchKernelGGL(k_ppo_adam_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat, o0->n_blocks, A,
+                               (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-5f);
+            wg_policy_pack_pop_(&PP, mt, P, stream);
+            THIPCHK(hipGetLastError());
+        }
+    return 0;
 }

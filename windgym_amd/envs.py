@@ -300,11 +300,19 @@ class WindFarmVecEnv(_gym_vector_base()):
 
         Noise: seed = the env's base seed, row offset = this shard's first global env, counter = a running count of policy
         steps of this env.  With ``sample_site`` the site table is refreshed by torch ops between steps: there, and only there,
-        the equivalent loop of ``act`` + ``step`` runs from Python into the same buffers."""
+        the equivalent loop of ``act`` + ``step`` runs from Python into the same buffers.
+
+        ``policy`` may be a ``population.Population`` (or a ``PPOPopulation``): its P members act on the envs
+        ``[m * Bm, (m + 1) * Bm)`` of the same buffers, still one policy launch per step (wg_pop_rollout), with this method's noise
+        rule — a population whose members hold the same weights fills the buffers one policy would."""
         b = self.batch
-        return self._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs,),
+        pop = getattr(policy, "population", None)      # a population.Population / PPOPopulation: wg_pop_rollout, member m on its envs
+        if pop is not None and self.num_envs % pop.n_members:
+            raise ValueError(f"rollout(): the {pop.n_members} members own equal shares of the envs: num_envs = {self.num_envs} "
+                             f"does not divide by {pop.n_members}")
+        return self._rollout(policy if pop is None else pop, n_steps, deterministic, record, values, rows=(self.num_envs,),
                              shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
-                             slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout)
+                             slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout if pop is None else b.rollout_pop)
 
     def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run, critic=None):
         """``rollout()`` of this class and of :class:`WindFarmVecEnvMulti`.  ``rows``: the axes of the policy's rows, ``(B,)`` or

@@ -1,0 +1,339 @@
+"""Populations: P policies of one architecture collected and trained in the kernel launches of one (include/windgym_hip.h:
+``wg_pop_*``) — the seeds of a result or a sweep of ``gamma`` / ``learning_rate`` / ``ent_coef`` (the reference runs such sweeps
+as job arrays: examples/longer_steps_example.py + submit.sh) on ONE env batch, member ``m`` owning the envs
+``[m * Bm, (m + 1) * Bm)``, ``Bm = num_envs / P``.
+
+The contract is the library's usual one, applied across policies: whatever a member computes — its rollout columns, its
+parameters after any number of iterations — is, to the bit, what it would have computed alone on its shard of the batch.
+:class:`Population` is the acting object (``venv.rollout(pop, T)``), :class:`PPOPopulation` the trainer; the members stay
+ordinary :class:`~windgym_amd.policy.MlpPolicy` objects.  There is no CPU fallback; the helpers :func:`broadcast_hyper` and
+:func:`global_rows` are pure host functions.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import time
+
+import numpy as np
+
+from .ppo import PPO, PPOOptimizer, _schedule
+
+POP_MAX = 16            # WG_POP_MAX
+PER_MEMBER = ("gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "learning_rate", "normalize_advantage")
+SHARED = ("n_steps", "n_epochs", "batch_size")
+
+
+def broadcast_hyper(name, value, n_members):
+    """A per-member hyper-parameter as a list of ``n_members`` entries: a scalar (or a schedule, a callable) is every member's,
+    a list / tuple / array must have one entry per member."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n_members:
+            raise ValueError(f"{name}: {len(value)} values for {n_members} members (a scalar, or one value per member)")
+        return list(value)
+    return [value] * n_members
+
+
+def global_rows(local, member, n_envs, n_envs_member):
+    """Row ids of a ``[T, B]`` rollout flattened to ``T * B`` rows, for the LOCAL row ids ``r`` in ``[0, T * Bm)`` that member
+    ``member`` would use on its own ``[T, Bm]`` shard: ``(r // Bm) * B + member * Bm + r % Bm``.  Works on numpy arrays and torch
+    tensors alike."""
+    B, Bm = int(n_envs), int(n_envs_member)
+    return (local // Bm) * B + int(member) * Bm + local % Bm
+
+
+def check_population_shape(n_members, n_envs):
+    """-> envs per member; raises ``ValueError`` for what wg_pop_create / wg_pop_rollout would refuse."""
+    P, B = int(n_members), int(n_envs)
+    if not 1 <= P <= POP_MAX:
+        raise ValueError(f"a population has 1 .. {POP_MAX} members, not {P}")
+    if B % P:
+        raise ValueError(f"the {P} members own equal shares of the envs: num_envs = {B} does not divide by {P}")
+    return B // P
+
+
+class Population:
+    """``P`` :class:`MlpPolicy` objects of one architecture behind one ``wg_pop`` handle: ``act`` / ``value`` are ONE launch of
+    the policy kernel for all members, member ``m`` on rows ``[m * Bm, (m + 1) * Bm)``; ``venv.rollout(pop, T)`` is wg_pop_rollout.
+    ``optimizers``: the members' :class:`PPOOptimizer` objects (needed by wg_pop_update only)."""
+
+    def __init__(self, members, optimizers=None):
+        from .binding import _chk
+        members = list(members)
+        if not 1 <= len(members) <= POP_MAX:
+            raise ValueError(f"a population has 1 .. {POP_MAX} members, not {len(members)}")
+        p0 = members[0]
+        self.members, self.optimizers = members, None if optimizers is None else list(optimizers)
+        self.L, self._chk, self.torch, self.device = p0.L, _chk, p0.torch, p0.device
+        self.n_members = P = len(members)
+        self.desc, self.n_in, self.n_out, self.n_in_vf = p0.desc, p0.n_in, p0.n_out, p0.n_in_vf
+        self.has_critic, self.split = p0.has_critic, p0.split
+        hs = (C.c_void_p * P)(*[m._h.value for m in members])
+        os_ = None if optimizers is None else (C.c_void_p * P)(*[o._h.value for o in self.optimizers])
+        h = C.c_void_p()
+        _chk(self.L.wg_pop_create(hs, os_, P, C.byref(h)), "wg_pop_create")
+        self._h = h
+        self._out = {}
+
+    population = property(lambda self: self)      # (what venv.rollout looks for)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.wg_pop_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _u64(self, x, default):
+        P = self.n_members
+        v = broadcast_hyper("seed / row_offset", default if x is None else x, P)
+        return (C.c_uint64 * P)(*[int(i) for i in v])
+
+    def act(self, obs, deterministic=False, counter=0, *, seed=None, row_offset=0, value=True, out=None):
+        """wg_pop_act on a contiguous float32 CUDA tensor ``[..., n_in]`` whose rows divide evenly among the members ->
+        ``(action, raw, logp, value)`` as :meth:`MlpPolicy.act`.  ``seed``: one per member (or a scalar for all; default: the
+        members' own seeds); ``row_offset``: a list per member, or a scalar = the global row of member 0's first row, member
+        ``m``'s being ``row_offset + m * Bm`` — with one seed for all, the noise of one policy on the whole batch."""
+        t = self.torch
+        if not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous() and obs.shape[-1] == self.n_in):
+            raise ValueError(f"act(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in}]")
+        n = obs.numel() // self.n_in
+        Bm = check_population_shape(self.n_members, n)
+        if out is None:
+            out = self._out.get(n)
+            if out is None:
+                f32 = dict(dtype=t.float32, device=self.device)
+                out = self._out[n] = (t.zeros((n, self.n_out), **f32), t.zeros((n, self.n_out), **f32), t.zeros(n, **f32), t.zeros(n, **f32))
+        a, r, lp, v = out
+        want_v = value and self.has_critic
+        ls = self.desc["has_log_std"]
+        offs = row_offset if isinstance(row_offset, (list, tuple, np.ndarray)) else [int(row_offset) + m * Bm for m in range(self.n_members)]
+        self._chk(self.L.wg_pop_act(self._h, n, obs.data_ptr(), int(bool(deterministic)), self._u64(seed, [m.seed for m in self.members]),
+                                    int(counter), self._u64(offs, 0), a.data_ptr(), r.data_ptr(), lp.data_ptr() if ls else None,
+                                    v.data_ptr() if want_v else None, self._stream()), "wg_pop_act")
+        return a, r, (lp if ls else None), (v if want_v else None)
+
+    def value(self, obs, out=None):
+        """Critics only: member ``m``'s V on its share of the rows -> float32 CUDA tensor [rows]."""
+        t = self.torch
+        if not self.has_critic:
+            raise ValueError("value(): the policies have no critic")
+        n = obs.numel() // self.n_in_vf
+        v = out if out is not None else t.zeros(n, dtype=t.float32, device=self.device)
+        self._chk(self.L.wg_pop_act(self._h, n, obs.data_ptr(), 1, None, 0, None, None, None, None, v.data_ptr(), self._stream()),
+                  "wg_pop_act")
+        return v
+
+
+class _MemberCheckpoint:
+    """What ``PPO.save`` reads, for ONE member: its zip is a plain PPO checkpoint of a run on the member's shard of the batch."""
+    _hyper_json = PPO._hyper_json
+    critic = None
+
+    def __init__(self, policy, opt, gen, venv, hyper, seed, num_timesteps, iteration, log):
+        self.policy, self.opt, self._gen, self.venv, self.seed = policy, opt, gen, venv, seed
+        self.num_timesteps, self.iteration, self.log = num_timesteps, iteration, log
+        for k, v in hyper.items():
+            setattr(self, k, v)
+
+    save = PPO.save
+
+
+class PPOPopulation:
+    """``P`` independent PPO runs of one architecture on ONE ``WindFarmVecEnv``, in the kernel launches of one run: member ``m``
+    trains on the envs ``[m * Bm, (m + 1) * Bm)`` exactly as ``PPO`` would on that shard alone (same seed and
+    hyper-parameters => the same parameters, to the bit, after any number of iterations).
+
+    ``policy``: ``"MlpPolicy"`` (then ``n_members`` policies are built with SB3's orthogonal initialisation from the members'
+    seeds) or a list of :class:`MlpPolicy` objects of one architecture.  ``n_steps``, ``n_epochs`` and ``batch_size`` (in rows of
+    ONE member; default a quarter of ``n_steps * Bm``) are shared — the members' launches run in lockstep; ``gamma``,
+    ``gae_lambda``, ``clip_range``, ``ent_coef``, ``vf_coef``, ``max_grad_norm``, ``learning_rate`` (schedules included),
+    ``normalize_advantage`` and ``seed`` are a scalar for all or one value per member.  A member's ``seed`` is what ``PPO``'s is:
+    initial weights and minibatch permutations; action noise follows ``venv.rollout``'s rule (the env's base seed, its running
+    count of policy steps, the global index of each env).
+
+    ``learn(total_timesteps)`` counts env steps PER MEMBER; ``log`` holds one list of per-member records per logged iteration,
+    computed on the device from the member's columns of the rollout (``mean_episode_power`` is not among them: the rollout
+    records no powers).  ``members[m]`` is an ordinary policy; ``save(dir)`` writes ``member_00.zip`` ...: plain ``PPO`` zips
+    (``PPO.load(zip, shard venv)`` resumes a member alone)."""
+
+    def __init__(self, policy, venv, n_members=None, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95,
+                 clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True,
+                 policy_kwargs=None, seed=None):
+        if getattr(venv, "possible_agents", None) is not None:
+            raise NotImplementedError("populations train on a WindFarmVecEnv: a WindFarmVecEnvMulti (wg_rollout_multi) is out of scope")
+        objects = not isinstance(policy, str)
+        if objects:
+            policy = list(policy)
+            if n_members is not None and int(n_members) != len(policy):
+                raise ValueError(f"n_members = {n_members} contradicts the {len(policy)} policies given")
+            n_members = len(policy)
+            if policy_kwargs:
+                raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
+        elif policy != "MlpPolicy":
+            raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy' or a list of MlpPolicy objects")
+        elif n_members is None:
+            raise ValueError("policy='MlpPolicy' needs n_members")
+        self.n_members = P = int(n_members)
+        self.n_envs = B = int(venv.num_envs)
+        self.n_envs_member = Bm = check_population_shape(P, B)
+        n_steps, n_epochs = int(n_steps), int(n_epochs)
+        if n_steps < 1 or n_epochs < 1:
+            raise ValueError("n_steps and n_epochs must be >= 1")
+        self.n_rows = rows_m = n_steps * Bm                                # rows of ONE member
+        batch_size = max(1, rows_m // 4) if batch_size is None else int(batch_size)
+        if not 1 <= batch_size <= rows_m:
+            raise ValueError(f"batch_size must lie in [1, n_steps * num_envs / n_members = {rows_m}]")
+        self.n_steps, self.n_epochs, self.batch_size = n_steps, n_epochs, batch_size
+        hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
+                     max_grad_norm=max_grad_norm, learning_rate=learning_rate, normalize_advantage=normalize_advantage)
+        for k in PER_MEMBER:
+            setattr(self, k, broadcast_hyper(k, hyper[k], P))
+        self.seed = broadcast_hyper("seed", seed, P)
+        for m in range(P):
+            if not 0.0 <= float(self.gamma[m]) <= 1.0 or not 0.0 <= float(self.gae_lambda[m]) <= 1.0:
+                raise ValueError(f"member {m}: gamma and gae_lambda must lie in [0, 1]")
+            if not float(self.max_grad_norm[m]) > 0.0:
+                raise ValueError(f"member {m}: max_grad_norm must be > 0")
+        self._lr = [_schedule(x, "learning_rate") for x in self.learning_rate]
+        self._clip = [_schedule(x, "clip_range") for x in self.clip_range]
+        self.venv = venv
+        want = (int(venv.batch.obs_dim), int(venv.n_turb))
+        if not objects:
+            policy = [PPO._build_policy(venv, want, dict(policy_kwargs or {}), 0 if s is None else int(s)) for s in self.seed]
+        for m, p in enumerate(policy):
+            if (p.n_in, p.n_out) != want:
+                raise ValueError(f"member {m} maps {p.n_in} -> {p.n_out}, this env needs {want[0]} -> {want[1]}")
+        self.members = policy
+        self.torch = t = policy[0].torch
+        dev = policy[0].device
+        self.opts = [PPOOptimizer(p) for p in policy]
+        self.population = Population(policy, self.opts)
+        self._gens = []
+        for s in self.seed:
+            g = t.Generator(device=dev)
+            g.manual_seed(0 if s is None else int(s))
+            self._gens.append(g)
+        self.n_minibatches = n_mb = -(-rows_m // batch_size)
+        self._perm = t.zeros((P, n_epochs, rows_m), dtype=t.int32, device=dev)
+        self._adv = t.zeros((n_steps, B), dtype=t.float32, device=dev)
+        self._ret = t.zeros_like(self._adv)
+        self._stats = t.zeros((P, n_epochs, n_mb, 8), dtype=t.float32, device=dev)
+        self._ep_return = t.zeros(B, dtype=t.float64, device=dev)          # running return of every env's open episode (for the log)
+        self.num_timesteps, self.iteration, self.log = 0, 0, []
+        self.n_env_steps = n_steps * Bm
+
+    # -- training -------------------------------------------------------------------------------------------------
+    def _floats(self, xs):
+        return (C.c_float * self.n_members)(*[float(x) for x in xs])
+
+    def collect(self):
+        """One rollout of ``n_steps`` steps of the whole batch (wg_pop_rollout) + wg_gae_pop -> the rollout dict ``[T, B, ..]``
+        with ``advantage`` / ``returns`` added; member ``m`` = columns ``m * Bm : (m + 1) * Bm``."""
+        pop = self.population
+        out = self.venv.rollout(pop, self.n_steps)
+        pop._chk(pop.L.wg_gae_pop(self.n_steps, self.n_envs, self.n_members, out["reward"].data_ptr(), out["value"].data_ptr(),
+                                  out["final_value"].data_ptr(), out["truncated"].data_ptr(), self._floats(self.gamma),
+                                  self._floats(self.gae_lambda), self._adv.data_ptr(), self._ret.data_ptr(), pop._stream()), "wg_gae_pop")
+        out["advantage"], out["returns"] = self._adv, self._ret
+        return out
+
+    def train(self, out, learning_rate, clip_range):
+        """Every member's ``PPO.train`` on its columns of a collected rollout: the members' permutations (drawn as ``PPO`` draws
+        them on ``n_steps * Bm`` rows, mapped to the batch's rows by :func:`global_rows`), then ONE wg_pop_update."""
+        from .binding import CPpoBatch, CPpoHyper
+        t, pop, P = self.torch, self.population, self.n_members
+        for m in range(P):
+            for e in range(self.n_epochs):
+                local = t.randperm(self.n_rows, generator=self._gens[m], device=pop.device)
+                self._perm[m, e].copy_(global_rows(local, m, self.n_envs, self.n_envs_member))
+        T, O, N = self.n_steps, pop.n_in, pop.n_out
+        b = CPpoBatch(out["obs"][:T].data_ptr(), out["raw"].data_ptr(), out["logp"].data_ptr(), self._adv.data_ptr(),
+                      self._ret.data_ptr(), T * self.n_envs)
+        hp = (CPpoHyper * P)(*[CPpoHyper(float(clip_range[m]), float(self.vf_coef[m]), float(self.ent_coef[m]),
+                                         int(bool(self.normalize_advantage[m]))) for m in range(P)])
+        params = (C.c_void_p * P)(*[p.params.data_ptr() for p in self.members])
+        pop._chk(pop.L.wg_pop_update(pop._h, params, C.byref(b), self._perm.data_ptr(), self.n_epochs, self.batch_size, hp,
+                                     self._floats(learning_rate), self._floats(self.max_grad_norm), self._stats.data_ptr(),
+                                     pop._stream()), "wg_pop_update")
+        return self._stats
+
+    def _member_metrics(self, out):
+        """[P, 5] float64 on the device: explained variance, episodes ended, sum of their returns, sum of rewards, steps."""
+        t, P, Bm = self.torch, self.n_members, self.n_envs_member
+        ret, val = self._ret.double().view(-1, P, Bm), out["value"].double().view(-1, P, Bm)
+        ev = 1.0 - (ret - val).transpose(0, 1).reshape(P, -1).var(dim=1) / ret.transpose(0, 1).reshape(P, -1).var(dim=1)
+        rew, tr = out["reward"].double(), out["truncated"].bool()
+        c = rew.cumsum(dim=0)                                              # [T, B]
+        T = rew.shape[0]
+        last = t.where(tr, t.arange(T, device=rew.device).view(-1, 1).expand_as(tr), t.full_like(tr, -1, dtype=t.long)).max(dim=0).values
+        any_end = last >= 0
+        c_last = c.gather(0, last.clamp(min=0).view(1, -1))[0]
+        ep_sum = t.where(any_end, self._ep_return + c_last, t.zeros_like(c_last))     # returns of all episodes that ended, per env
+        self._ep_return = t.where(any_end, c[-1] - c_last, self._ep_return + c[-1])
+        per = lambda x: x.view(P, Bm).sum(dim=1)                           # noqa: E731
+        return t.stack([ev, per(tr.sum(dim=0).double()), per(ep_sum), per(rew.sum(dim=0)), t.full((P,), float(T * Bm), dtype=t.float64, device=rew.device)], dim=1)
+
+    def learn(self, total_timesteps, callback=None, log_interval=1, reset_num_timesteps=True):
+        """Iterations of rollout + update until every member collected ``total_timesteps`` env steps on its own envs.
+        ``callback(pop) -> bool`` runs once per iteration; False stops.  Every ``log_interval``-th iteration appends a list of
+        one record per member to ``self.log`` (ONE device-to-host copy for the whole population)."""
+        from .binding import PPO_STATS
+        t, P = self.torch, self.n_members
+        if reset_num_timesteps:
+            self.num_timesteps = 0
+        start, total = self.num_timesteps, int(total_timesteps) + (0 if reset_num_timesteps else self.num_timesteps)
+        t0 = time.perf_counter()
+        while self.num_timesteps < total:
+            progress = 1.0 - (self.num_timesteps - 0.0) / max(total, 1)
+            lr, clip = [float(f(progress)) for f in self._lr], [float(f(progress)) for f in self._clip]
+            out = self.collect()
+            stats = self.train(out, lr, clip)
+            self.num_timesteps += self.n_env_steps
+            self.iteration += 1
+            if log_interval and self.iteration % int(log_interval) == 0:
+                self.venv.batch.metrics(reset_after=True)                 # (whole-batch sums, not used: consumed as PPO.learn does)
+                host = t.cat([stats.double().mean(dim=(1, 2)), self._member_metrics(out)], dim=1).cpu().numpy()   # the one copy
+                fps = (self.num_timesteps - start) / max(time.perf_counter() - t0, 1e-9)
+                recs = []
+                for m in range(P):
+                    rec = dict(zip(PPO_STATS, host[m, :8].tolist()))
+                    ev, n_ep, ep_sum, rew_sum, n_st = host[m, 8:13].tolist()
+                    rec.update(member=m, explained_variance=ev, iteration=self.iteration, num_timesteps=self.num_timesteps,
+                               learning_rate=lr[m], clip_range=clip[m], n_episodes=n_ep, mean_episode_return=ep_sum / max(n_ep, 1.0),
+                               mean_step_reward=rew_sum / max(n_st, 1.0), fps=fps)
+                    recs.append(rec)
+                self.log.append(recs)
+            if callback is not None and callback(self) is False:
+                break
+        return self
+
+    # -- checkpoints ----------------------------------------------------------------------------------------------
+    def member_hyper(self, m):
+        """The ``PPO`` arguments of member ``m``."""
+        d = {k: getattr(self, k) for k in SHARED}
+        d.update({k: getattr(self, k)[m] for k in PER_MEMBER})
+        return d
+
+    def save(self, directory):
+        """``directory/member_00.zip`` ...: each a plain ``PPO`` checkpoint (see :meth:`PPO.save`) of the member's run on its shard."""
+        os.makedirs(directory, exist_ok=True)
+        paths = []
+        for m in range(self.n_members):
+            log = [recs[m] for recs in self.log]
+            ck = _MemberCheckpoint(self.members[m], self.opts[m], self._gens[m], self.venv, self.member_hyper(m), self.seed[m],
+                                   self.num_timesteps, self.iteration, log)
+            paths.append(ck.save(os.path.join(directory, f"member_{m:02d}.zip")))
+        return paths
+
+    def close(self):
+        self.population.close()
+        for o in self.opts:
+            o.close()
