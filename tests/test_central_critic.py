@@ -1,6 +1,6 @@
 """CPU-side checks of the centralised-critic path: the flat layout of a split policy (a critic with its own input width), the
 checkpoint reader, the ctypes mirror of wg_ppo_batch_shared, and the float64 references the GPU tests lean on, pinned by
-themselves (tests/central_critic_ref.py against finite differences and against oracle/ppo_oracle.py where the two must agree)."""
+themselves (oracle/ppo_oracle.py: the shared forms against finite differences and against the plain ones, which call them)."""
 import ctypes as C
 import io
 import os
@@ -10,8 +10,6 @@ import zipfile
 import numpy as np
 import pytest
 
-import central_critic_ref as cr
-from multi_agent_ref import gae_shared
 from oracle import ppo_oracle as oo
 from windgym_amd import binding
 from windgym_amd.policy import critic_width, make_desc, n_params, pack_params, param_layout, read_sb3_zip, unpack_params
@@ -119,9 +117,9 @@ def test_reference_gradient_against_central_differences(agents, normalize):
     # env row 2 through all of its agents and once more, an entry outside the batch, the rest in scrambled order
     ids = np.concatenate([np.arange(agents) + 2 * agents, [2 * agents, n + 3, -1], np.random.default_rng(1).permutation(n)[:7]])
     kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=normalize)
-    total, grads, stats = cr.shared_loss_and_grad(params, *arrays, ids, agents, **kw)
-    assert abs(total - cr.shared_loss_value(params, *arrays, ids, agents, **kw)) <= 1e-12 and abs(total - stats["loss"]) <= 1e-12
-    fd = cr.finite_difference_grad(params, *arrays, ids, agents, **kw)
+    total, grads, stats, _ = oo.shared_loss_and_grad(params, *arrays, ids, agents, **kw)
+    assert abs(total - oo.shared_loss_value(params, *arrays, ids, agents, **kw)) <= 1e-12 and abs(total - stats["loss"]) <= 1e-12
+    fd = oo.finite_difference_grad(params, *arrays, ids, agents, **kw)
     for k in params:
         assert np.abs(fd[k] - grads[k]).max() <= 1e-6 * max(1.0, np.abs(grads[k]).max()), k
     assert any(np.abs(grads[k]).max() > 1e-3 for k in grads if "value_net" in k)
@@ -139,18 +137,24 @@ def test_reference_is_the_plain_loss_with_one_agent_on_one_stream():
     ids = rng.permutation(n)[:25]
     for norm in (True, False):
         kw = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=norm)
-        total, grads, stats = cr.shared_loss_and_grad(params, obs, obs, raw, lpo, adv, ret, ids, 1, **kw)
+        total, grads, stats, _ = oo.shared_loss_and_grad(params, obs, obs, raw, lpo, adv, ret, ids, 1, **kw)
         t0, g0, s0, _ = oo.loss_and_grad(params, obs[ids], raw[ids], lpo[ids], adv[ids], ret[ids], **kw)
         assert abs(total - t0) <= 1e-12 and all(abs(stats[k] - s0[k]) <= 1e-12 for k in s0)
         assert all(np.abs(grads[k] - g0[k]).max() <= 1e-12 for k in g0)
+        # the plain forms ARE the shared ones on every row once, one agent per env, the critic on the actor's rows: exactly
+        import torch
+        tp = {k: torch.tensor(v) for k, v in params.items()}
+        rows = [torch.tensor(x) for x in (obs, raw, lpo, adv, ret)]
+        plain, shared = oo.loss(tp, *rows, **kw), oo.shared_loss(tp, rows[0], *rows, np.arange(n), 1, **kw)
+        assert plain[0] == shared[0] and plain[1] == shared[1] and torch.equal(plain[2], shared[2])
 
 
 def test_an_env_row_drawn_through_two_agents_counts_twice():
     params, arrays = _tiny(3, seed=9)
     kw = dict(vf_coef=1.0, normalize_advantage=False)
-    one = cr.shared_loss_and_grad(params, *arrays, [6], 3, **kw)[2]["v_loss"]            # env row 2 through agent 0
-    other = cr.shared_loss_and_grad(params, *arrays, [0], 3, **kw)[2]["v_loss"]          # env row 0
-    both = cr.shared_loss_and_grad(params, *arrays, [6, 7, 0], 3, **kw)[2]["v_loss"]     # env row 2 twice, env row 0 once
+    one = oo.shared_loss_and_grad(params, *arrays, [6], 3, **kw)[2]["v_loss"]            # env row 2 through agent 0
+    other = oo.shared_loss_and_grad(params, *arrays, [0], 3, **kw)[2]["v_loss"]          # env row 0
+    both = oo.shared_loss_and_grad(params, *arrays, [6, 7, 0], 3, **kw)[2]["v_loss"]     # env row 2 twice, env row 0 once
     assert abs(both - (2 * one + other) / 3) <= 1e-12
 
 
@@ -161,21 +165,26 @@ def test_central_advantages_are_the_per_agent_recurrence_with_a_shared_value():
     tr = rng.uniform(size=(T, B)) < 0.15
     adv, ret = oo.gae(r, v, fv, tr, 0.99, 0.95)
     bc = lambda x: np.repeat(x[:, :, None], A, axis=2)                       # noqa: E731
-    sa, sr = gae_shared(r, bc(v), bc(fv), tr, 0.99, 0.95)
+    sa, sr = oo.gae_shared(r, bc(v), bc(fv), tr, 0.99, 0.95)
     assert np.array_equal(sa, bc(adv)) and np.array_equal(sr, bc(ret))
+    # wg_gae is wg_gae_shared with one agent per env, and so are their references (recurrence and brute force): exactly
+    for plain, shared in ((oo.gae, oo.gae_shared), (oo.gae_brute, oo.gae_shared_brute)):
+        one = shared(r, v[..., None], fv[..., None], tr, 0.99, 0.95)
+        assert all(np.array_equal(x, y[..., 0]) for x, y in zip(plain(r, v, fv, tr, 0.99, 0.95), one))
 
 
 def test_tile_rows_with_the_critics_own_width():
-    """Pins a TEST HELPER, not the library: ``central_critic_ref.tile_rows`` restates wg_ppo.h's LDS map in Python (the GPU gradient test
-    sizes its ragged and out-of-range index cases by it) and is held here to oracle/ppo_oracle.py's restatement at equal widths and to
-    hand-computed values.  The library's own R is not exposed; a wrong per-net map in wg_ppo.hip is caught BY VALUE on the GPU, where
+    """Pins a TEST HELPER, not the library: ``ppo_oracle.tile_rows`` restates wg_ppo.h's LDS map in Python (the GPU gradient test
+    sizes its ragged and out-of-range index cases by it) and is held here to its own default (the actor's width) at equal widths and
+    to hand-computed values.  The library's own R is not exposed; a wrong per-net map in wg_ppo.hip is caught BY VALUE on the GPU, where
     ``n_in`` = 2 beside ``n_in_vf`` = 2048 and the reverse would overflow the observation chunk and corrupt the gradient."""
     for n_in, hidden, hidden_vf, n_out in ((32, (64, 64), (64, 64), 16), (256, (256,) * 4, (256,) * 4, 16), (2048, (256, 256), (64,), 4)):
-        assert cr.tile_rows(n_in, n_in, n_out, hidden, hidden_vf) == oo.tile_rows(n_in, n_out, hidden, hidden_vf)[0]
+        assert oo.tile_rows(n_in, n_out, hidden, hidden_vf, n_in_vf=n_in) == oo.tile_rows(n_in, n_out, hidden, hidden_vf)
     # each net's map counts its OWN input chunk: a wide critic beside a narrow actor can halve the tile, and the reverse
-    assert cr.tile_rows(2, 2, 1, (64,), (64, 64)) == 32 and cr.tile_rows(2, 2048, 1, (64,), (64, 64)) == 16
-    assert cr.tile_rows(2048, 2, 1, (64, 64), (64,)) == 16 and cr.tile_rows(2048, 2, 4, (256, 256), (64,)) == 8
-    assert cr.lds_floats(300, [8, 1], 32) == cr.lds_floats(256, [8, 1], 32) == oo.lds_floats(256, [8, 1], 32)
+    R = lambda n_in, n_in_vf, *net: oo.tile_rows(n_in, *net, n_in_vf=n_in_vf)[0]                # noqa: E731
+    assert R(2, 2, 1, (64,), (64, 64)) == 32 and R(2, 2048, 1, (64,), (64, 64)) == 16
+    assert R(2048, 2, 1, (64, 64), (64,)) == 16 and R(2048, 2, 4, (256, 256), (64,)) == 8
+    assert oo.lds_floats(300, [8, 1], 32) == oo.lds_floats(256, [8, 1], 32)
 
 
 def test_central_on_a_one_turbine_farm_says_so():

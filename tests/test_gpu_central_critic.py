@@ -5,7 +5,7 @@
 * wg_rollout_multi, central     equals its documented loop of single calls bit for bit (buffers, state, the step after it), its values
                                 are ``policy.value`` of the flat rows, the trajectory does not depend on the critic, env-axis shards
                                 compute their slice, refusals, the ``sample_site`` fallback;
-* wg_ppo_grad_shared            against the float64 reference of tests/central_critic_ref.py; agents = 1 on one stream is wg_ppo_grad;
+* wg_ppo_grad_shared            against the float64 reference of oracle/ppo_oracle.py; agents = 1 on one stream is wg_ppo_grad;
 * wg_ppo_update_shared          equals its loop of grad_shared + apply bit for bit;
 * PPO(critic="central")         equals a twin assembled from rollout, gae and update; save / load resume; the ValueErrors."""
 import copy
@@ -15,47 +15,12 @@ import os
 import numpy as np
 import pytest
 
-from central_critic_ref import STATS, shared_loss_and_grad, tile_rows
 from oracle import policy_oracle as po
-from windgym_amd.policy import pack_params, param_layout
+from oracle.ppo_oracle import STATS, shared_loss_and_grad, tile_rows
+from rl_helpers import _torch, close, dev, flat_grad, make, rollout_equals_the_loop, same_actor, shared_batch
+from windgym_amd.policy import param_layout
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def close(a, b, tol=2e-5, rel=0.0):                                          # test_gpu_policy.py's
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return bool(np.all(np.abs(a - b) <= tol + rel * np.abs(b)))
-
-
-def make(n_in, hidden, n_out, n_in_vf=None, hidden_vf=(64,), activation="tanh", seed=3):
-    """A policy (split when ``n_in_vf`` differs from ``n_in``) with every bias and log_std away from 0 + its float32 state dict."""
-    from windgym_amd.policy import MlpPolicy
-    p = MlpPolicy(n_in, n_out, hidden, hidden_vf, activation, seed=seed, n_in_vf=n_in_vf)
-    rng = np.random.default_rng(seed + 1)
-    sd = {k: v.cpu().numpy() for k, v in p.state_dict().items()}
-    for k in sd:
-        if k.endswith("bias") or k == "log_std":
-            sd[k] = rng.uniform(-0.3, 0.3, sd[k].shape).astype(np.float32)
-    p.load_state_dict(sd)
-    return p, sd
-
-
-def same_actor(p, sd, n_in_vf=None, hidden_vf=(64,)):
-    """A policy with p's actor parameters (and log_std) and a critic of its own on ``n_in_vf`` (default: the actor's width)."""
-    q, sq = make(p.n_in, p.desc["hidden_pi"], p.n_out, n_in_vf, hidden_vf, p.desc["activation"], seed=11)
-    sq.update({k: v for k, v in sd.items() if "value_net" not in k})
-    q.load_state_dict(sq)
-    return q, sq
-
-
-def dev(*arrays):
-    t = _torch()
-    return [t.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -65,7 +30,7 @@ def dev(*arrays):
 @pytest.mark.parametrize("n_in_vf", [1, 33, 256, 257, 2048])
 def test_split_policy_critic_vs_oracle_and_actor_bits(n_in_vf, activation):
     t = _torch()
-    p, sd = make(2, (64, 64), 3, n_in_vf, (64, 32), activation)
+    p, sd = make(2, (64, 64), 3, activation, hidden_vf=(64, 32), n_in_vf=n_in_vf)
     assert p.split and p.n_in_vf == n_in_vf and p.params.numel() == sum(int(np.prod(s)) for _, s in param_layout(p.desc))
     q, _ = same_actor(p, sd, None, (16,))                                    # equal widths, another critic altogether
     assert not q.split
@@ -122,52 +87,6 @@ def _menv(n_envs, seed, **over):
     return WindFarmVecEnvMulti(V80(), n_envs, yaml_dict=copy.deepcopy(presets.multi_3x3_config()), seed=seed, turbtype="None", n_rotor_pts=16, **kw)
 
 
-def central_rollout_equals_the_loop(va, vb, p, T, rec=("power_agent",), min_trunc=1):
-    """tests/loop_twin.py for a split policy: va.rollout(p, T) == the loop of actor-only act, value on the flat rows, step, value on
-    the flat final rows, driven from Python on the twin vb — every buffer, the handle's state, the persistent outputs, the step after."""
-    t = _torch()
-    B, N = va.num_envs, va.n_turb
-    seed, row0, counter0 = int(va.venv._base_seed), va._global_offset, vb._policy_steps
-    assert va._policy_steps == counter0
-    out = va.rollout(p, T, record=rec)
-    cur = lambda v: {("obs", "final_obs"): (v._obs, v._final_obs), ("flat_obs", "flat_final_obs"): (v.batch.obs, v.batch.final_obs)}   # noqa: E731
-    ref = {k: [] for k in ("actions", "raw", "logp", "value", "final_value", "reward", "truncated") + tuple(rec)}
-    for (k, kf), (o, _) in cur(vb).items():
-        ref[k], ref[kf] = [o.clone()], []
-    for i in range(T):
-        a, raw, logp, v = p.act(ref["obs"][-1], counter=counter0 + i, seed=seed, row_offset=row0 * N)
-        assert v is None
-        a = a.reshape(B, N).clone()
-        ref["actions"].append(a); ref["raw"].append(raw.reshape(B, N).clone()); ref["logp"].append(logp.reshape(B, N).clone())
-        ref["value"].append(p.value(ref["flat_obs"][-1]).clone())
-        vb.step(a)
-        ref["reward"].append(vb.batch.reward.clone()); ref["truncated"].append(vb.batch.truncated.clone())
-        for (k, kf), (o, f) in cur(vb).items():
-            ref[k].append(o.clone()); ref[kf].append(f.clone())
-        for name in rec:
-            ref[name].append(vb.batch.info(name))
-        ref["final_value"].append(p.value(ref["flat_final_obs"][-1]).clone())
-    vb._policy_steps = counter0 + T
-    assert set(out) == set(ref)
-    for k, x in ref.items():
-        x = t.stack(x)
-        assert out[k].shape == x.shape and t.equal(out[k], x), k
-    assert tuple(out["value"].shape) == (T, B) == tuple(out["final_value"].shape) and tuple(out["logp"].shape) == (T, B, N)
-    tr = out["truncated"].bool()
-    assert int(tr.sum()) >= min_trunc, int(tr.sum())
-    va.batch.check(); vb.batch.check()
-    assert va.batch.get_state() == vb.batch.get_state() and va._policy_steps == counter0 + T
-    # an env that did not truncate ended the step in the state the next one starts from; one that did, did not
-    assert t.equal(out["final_value"][:-1][~tr[:-1]], out["value"][1:][~tr[:-1]])
-    assert not tr[:-1].any() or not t.equal(out["final_value"][:-1][tr[:-1]], out["value"][1:][tr[:-1]])
-    for (k, kf), (o, f) in cur(va).items():
-        assert t.equal(o, out[k][T]) and t.equal(f, out[kf][T - 1]), k
-    act = t.zeros((B, N), device="cuda")
-    for x, y in zip(va.step(act), vb.step(act)):
-        assert t.equal(x, y)
-    return out
-
-
 def test_central_rollout_equals_its_loop_and_does_not_steer_the_trajectory():
     t = _torch()
     B, T, seed = 40, 150, 1234                                               # (40 envs: two tiles of critic rows, the second ragged)
@@ -176,8 +95,8 @@ def test_central_rollout_equals_its_loop_and_does_not_steer_the_trajectory():
         v.reset(seed=seed)
     N, Om, O = va.n_turb, va.obs_len, va.batch.obs_dim
     assert O != Om
-    p, sd = make(Om, (64, 64), 1, O, (64, 32))
-    out = central_rollout_equals_the_loop(va, vb, p, T)
+    p, sd = make(Om, (64, 64), 1, hidden_vf=(64, 32), n_in_vf=O)
+    out = rollout_equals_the_loop(va, vb, p, T, rec=("power_agent",), min_trunc=1)
     assert int(out["truncated"].any(dim=0).sum()) >= B // 2                  # episodes ended inside the window
     # the values ARE policy.value of the flat rows (whatever else the launch that computed them held), and the float64 oracle's
     assert t.equal(out["value"], p.value(out["flat_obs"][:T].contiguous()).view(T, B))
@@ -191,7 +110,7 @@ def test_central_rollout_equals_its_loop_and_does_not_steer_the_trajectory():
     for k in ("obs", "flat_obs", "actions", "raw", "logp", "reward", "truncated", "final_obs", "flat_final_obs", "power_agent"):
         assert t.equal(out[k], other[k]), k
     # a second rollout with another record tuple and length, interleaved with the step() the twin check ends in
-    central_rollout_equals_the_loop(va, vb, p, 25, rec=("timestep", "yaw_agent"), min_trunc=0)
+    rollout_equals_the_loop(va, vb, p, 25, rec=("timestep", "yaw_agent"), min_trunc=0)
     for v in (va, vb, vc):
         v.close()
     p.close(); q.close()
@@ -207,7 +126,7 @@ def test_central_rollout_shards_refusals_and_site_fallback():
     for v in [whole] + halves:
         v.reset(seed=seed)
     N, Om, O = whole.n_turb, whole.obs_len, whole.batch.obs_dim
-    p, sd = make(Om, (64,), 1, O, (32,))
+    p, sd = make(Om, (64,), 1, hidden_vf=(32,), n_in_vf=O)
     out = {k: x.clone() for k, x in whole.rollout(p, T, record=("yaw_agent",)).items()}
     for r, v in enumerate(halves):
         part = v.rollout(p, T, record=("yaw_agent",))
@@ -216,11 +135,11 @@ def test_central_rollout_shards_refusals_and_site_fallback():
             assert t.equal(x, out[k][:, 16 * r:16 * (r + 1)]), (k, r)
         v.batch.check()
     # refusals, with their messages: a critic of neither accepted width (Python and ABI), central mode without obs / final_obs
-    bad, _ = make(Om, (64,), 1, O + 1, (32,))
+    bad, _ = make(Om, (64,), 1, hidden_vf=(32,), n_in_vf=O + 1)
     with pytest.raises(ValueError, match="centralised critic"):
         whole.rollout(bad, 4)
     with pytest.raises(ValueError, match="critic reads"):
-        whole.venv.rollout(make(O, (8,), N, O + 1, (8,))[0], 4)              # the single-agent env takes no split policy
+        whole.venv.rollout(make(O, (8,), N, hidden_vf=(8,), n_in_vf=O + 1)[0], 4)              # the single-agent env takes no split policy
     b = whole.batch
     f32 = dict(dtype=t.float32, device="cuda")
     bufs = dict(obs=t.zeros((5, 32, N, Om), **f32), actions=t.zeros((4, 32, N), **f32), value=t.zeros((4, 32), **f32),
@@ -263,28 +182,6 @@ def test_central_rollout_shards_refusals_and_site_fallback():
 # ----------------------------------------------------------------------------------------------------------------------
 # 3. / 4. the update
 # ----------------------------------------------------------------------------------------------------------------------
-def shared_batch(sd, n_in, n_in_vf, n_out, n_env, agents, activation, seed=0):
-    """Random agent rows whose ratios straddle both clip bounds + the env rows the critic reads, advantages and returns per env row."""
-    rng = np.random.default_rng(seed)
-    n = n_env * agents
-    obs = rng.uniform(-1, 1, (n, n_in)).astype(np.float32)
-    obs_vf = rng.uniform(-1, 1, (n_env, n_in_vf)).astype(np.float32)
-    mean = po._net(sd, "mlp_extractor.policy_net", "action_net", obs, activation)
-    value = po._net(sd, "mlp_extractor.value_net", "value_net", obs_vf, activation)[:, 0]
-    std = np.exp(sd["log_std"].astype(np.float64))
-    raw = (mean + std * rng.standard_normal((n, n_out))).astype(np.float32)
-    z = (raw - mean) / std
-    logp = np.sum(-0.5 * z * z - sd["log_std"] - 0.5 * np.log(2 * np.pi), axis=1)
-    logp_old = (logp + 0.3 * rng.standard_normal(n)).astype(np.float32)
-    adv = (rng.standard_normal(n_env) * 2.0 + 0.5).astype(np.float32)
-    ret = (value + rng.standard_normal(n_env)).astype(np.float32)
-    return obs, obs_vf, raw, logp_old, adv, ret
-
-
-def flat_grad(desc, grads):
-    return pack_params(desc, {k: v.astype(np.float32) for k, v in grads.items()}).astype(np.float64)
-
-
 GRAD_SHAPES = [(13, 31, (64, 64), (64, 64), 1), (2, 2048, (64,), (256, 256), 1), (2048, 2, (256, 256), (64,), 4), (8, 8, (33,), (33,), 3)]
 
 
@@ -294,11 +191,11 @@ GRAD_SHAPES = [(13, 31, (64, 64), (64, 64), 1), (2, 2048, (64,), (256, 256), 1),
 def test_grad_shared_vs_float64_reference(shape, agents, activation):
     from windgym_amd.ppo import PPOOptimizer
     n_in, n_in_vf, hidden, hidden_vf, n_out = shape
-    p, sd = make(n_in, hidden, n_out, n_in_vf, hidden_vf, activation)
+    p, sd = make(n_in, hidden, n_out, activation, hidden_vf=hidden_vf, n_in_vf=n_in_vf)
     assert p.split == (n_in != n_in_vf)
     sd64 = {k: v.astype(np.float64) for k, v in sd.items()}
     opt = PPOOptimizer(p)
-    R = tile_rows(n_in, n_in_vf, n_out, hidden, hidden_vf)
+    R = tile_rows(n_in, n_out, hidden, hidden_vf, n_in_vf=n_in_vf)[0]
     assert R is not None
     n_env = 120
     n_total = n_env * agents
@@ -320,7 +217,7 @@ def test_grad_shared_vs_float64_reference(shape, agents, activation):
         else:
             g, st = opt.grad(d[0], d[2], d[3], d[4], d[5], index=dev(ids.astype(np.int32))[0], obs_vf=d[1], agents=agents, **kw)
         g, st = g.cpu().numpy().astype(np.float64), st.cpu().numpy()
-        _, grads, rs = shared_loss_and_grad(sd64, obs, obs_vf, raw, lpo, adv, ret, ids, agents, activation=activation, **kw)
+        _, grads, rs, _ = shared_loss_and_grad(sd64, obs, obs_vf, raw, lpo, adv, ret, ids, agents, activation=activation, **kw)
         ref = flat_grad(p.desc, grads)
         err = np.abs(g - ref).max()
         assert np.all(np.isfinite(g)) and err <= 1e-4 * np.linalg.norm(ref) + 1e-6, (k, err, np.linalg.norm(ref))     # test_gpu_ppo.py's bars
@@ -341,8 +238,8 @@ def test_grad_shared_vs_float64_reference(shape, agents, activation):
 def test_shared_entries_with_one_agent_on_one_stream_are_the_plain_ones():
     from windgym_amd.ppo import PPOOptimizer
     t = _torch()
-    pa, sd = make(32, (64, 64), 16, None, (64, 64))
-    pb, _ = make(32, (64, 64), 16, None, (64, 64))
+    pa, sd = make(32, (64, 64), 16, hidden_vf=(64, 64))
+    pb, _ = make(32, (64, 64), 16, hidden_vf=(64, 64))
     oa, ob = PPOOptimizer(pa), PPOOptimizer(pb)
     sd64 = {k: v.astype(np.float64) for k, v in sd.items()}
     n = 1000
@@ -372,8 +269,8 @@ def test_update_shared_equals_its_loop():
     from windgym_amd.ppo import PPOOptimizer
     t = _torch()
     agents, n_env, bs, E = 9, 111, 300, 3                                    # 999 agent rows: minibatches of 300, 300, 300, 99
-    pa, sd = make(13, (64, 64), 1, 31, (64, 32))
-    pb, _ = make(13, (64, 64), 1, 31, (64, 32))
+    pa, sd = make(13, (64, 64), 1, hidden_vf=(64, 32), n_in_vf=31)
+    pb, _ = make(13, (64, 64), 1, hidden_vf=(64, 32), n_in_vf=31)
     oa, ob = PPOOptimizer(pa), PPOOptimizer(pb)
     obs, obs_vf, raw, lpo, adv, ret = dev(*shared_batch({k: v.astype(np.float64) for k, v in sd.items()}, 13, 31, 1, n_env, agents, "tanh", seed=5))
     n = n_env * agents
@@ -404,7 +301,7 @@ def test_plain_entries_refuse_a_split_policy_through_the_abi():
     from windgym_amd.ppo import PPOOptimizer
     t = _torch()
     n_in, n_in_vf, agents, n_env = 2, 18, 9, 40
-    p, sd = make(n_in, (64, 64), 1, n_in_vf, (64, 64))
+    p, sd = make(n_in, (64, 64), 1, hidden_vf=(64, 64), n_in_vf=n_in_vf)
     opt = PPOOptimizer(p)
     obs, obs_vf, raw, lpo, adv, ret = dev(*shared_batch({k: v.astype(np.float64) for k, v in sd.items()}, n_in, n_in_vf, 1, n_env, agents, "tanh"))
     n = n_env * agents
@@ -431,7 +328,7 @@ def test_plain_entries_refuse_a_split_policy_through_the_abi():
     g, st = opt.grad(obs, raw, lpo, adv, ret, obs_vf=obs_vf, agents=agents)
     assert bool(t.isfinite(g).all()) and g.abs().max().item() > 0
     # an equal-width policy still takes the plain entries (every existing test of them runs this way)
-    q, sq = make(n_in, (64, 64), 1, None, (64, 64))
+    q, sq = make(n_in, (64, 64), 1, hidden_vf=(64, 64))
     oq = PPOOptimizer(q)
     gq = t.zeros_like(q.params)
     _chk(q.L.wg_ppo_grad(oq._h, q.params.data_ptr(), C.byref(b), None, 0, n, C.byref(hp), gq.data_ptr(), None, q._stream()), "wg_ppo_grad")

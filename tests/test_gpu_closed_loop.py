@@ -17,6 +17,7 @@ Each case asserts the kernel variant it claims: ``flow_variant()`` of the live h
 (fused step, window-sums mode, waves per env), the host-side plan of windgym_amd/csrc/wg_plan.h for the same configuration
 (tests/plan_shim.cpp, as tests/test_plan.py builds it).  The bitwise loop check of test_gpu_policy.py runs on the same rollout."""
 import copy
+import functools
 import ctypes as C
 import os
 import subprocess
@@ -24,14 +25,15 @@ import subprocess
 import numpy as np
 import pytest
 
-from loop_twin import rollout_equals_the_loop
+import rl_helpers
 from oracle import policy_oracle as po
 from oracle import ppo_oracle as oo
-from test_gpu_policy import make
-from test_gpu_spotcheck import (N_SAMPLE, OBS_ATOL, TURB_OBS_ATOL, TURB_POW_ATOL, TURB_POW_RTOL, TURB_REW_ATOL, TURB_REW_RTOL,
-                                TURB_UVW_ATOL, TURB_UVW_RTOL)
+from rl_helpers import (LOGP_ATOL, N_SAMPLE, OBS_ATOL, RAW_ATOL, SMALL_BOX, SMALL_BOX_SPACING, TURB_OBS_ATOL, TURB_POW_ATOL, TURB_POW_RTOL,
+                        TURB_REW_ATOL, TURB_REW_RTOL, TURB_UVW_ATOL, TURB_UVW_RTOL, VAL_ATOL, VAL_RTOL, _ti_farm_history_100, _torch,
+                        rollout_equals_the_loop)
 
 pytestmark = pytest.mark.gpu
+make = functools.partial(rl_helpers.make, draw="normal")        # (test_gpu_policy.py's policies)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORD = ("power_agent", "yaw_agent", "rotor_uvw_agent", "wind_f64", "timestep")     # one field of every layout of info_shape
 # bars of the step outputs per inflow: obs atol, reward (rtol, atol), rotor wind (rtol, atol), power (rtol, atol).  "steady" and "box"
@@ -39,29 +41,6 @@ RECORD = ("power_agent", "yaw_agent", "rotor_uvw_agent", "wind_f64", "timestep")
 BARS = {"steady": (OBS_ATOL, (1e-4, OBS_ATOL), (1e-4, 1e-4), (4e-4, 20.0)),
         "box": (TURB_OBS_ATOL, (TURB_REW_RTOL, TURB_REW_ATOL), (TURB_UVW_RTOL, TURB_UVW_ATOL), (TURB_POW_RTOL, TURB_POW_ATOL)),
         "random": (5e-4, (1e-3, 1e-3), (2e-4, 2e-3), (TURB_POW_RTOL, TURB_POW_ATOL))}
-# policy outputs: the bars of test_gpu_policy.py's stochastic test (raw 1e-5 + 2e-5, logp 1e-4) and of its value checks
-RAW_ATOL, LOGP_ATOL, VAL_ATOL, VAL_RTOL = 3e-5, 1e-4, 2e-5, 2e-5
-SMALL_BOX, SMALL_BOX_SPACING = (256, 64, 32), (3.0, 3.0, 3.0)
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _ti_farm_history_100():
-    """test_gpu_parity.py's generic_ti_farm_current dict (TI and farm-level sensors on every channel) with 2turb.yaml's 100-sample wind
-    speed history: a rolling mean with history_N != 1, which the running window sums cannot serve — the ring-staging k_glue."""
-    from windgym_amd.presets import env1_config
-    d = copy.deepcopy(env1_config())
-    d["ActionMethod"] = "yaw"
-    d["farm"].update(nx=3, ny=2)
-    d["mes_level"].update(turb_ws=True, turb_wd=True, turb_TI=True, turb_power=True, farm_ws=True, farm_wd=True, farm_TI=True, farm_power=True)
-    d["ws_mes"].update(ws_current=True, ws_rolling_mean=True, ws_history_N=100, ws_history_length=100, ws_window_length=1)
-    d["wd_mes"].update(wd_current=True, wd_rolling_mean=True, wd_history_N=1, wd_history_length=8, wd_window_length=8)
-    d["power_mes"].update(power_current=True, power_rolling_mean=True, power_history_N=1, power_history_length=20, power_window_length=30)
-    d["yaw_mes"].update(yaw_current=True, yaw_rolling_mean=False)
-    return d
 
 
 def _case(name):
@@ -285,7 +264,7 @@ def test_shard_invariance_of_every_rollout_buffer(small_box):
 def test_rollouts_interleaved_with_steps_equal_the_loop():
     """rollout(T1), step, rollout(T2) with another record tuple, rollout(T1) again (its cached buffers reused) == one twin driven by the
     loop of act + step: the buffer cache's keys and the running count of policy steps that numbers the noise."""
-    from test_gpu_policy import _venv as venv77
+    from rl_helpers import _venv as venv77
     t = _torch()
     va, vb = venv77(48, n_passthrough=0.3), venv77(48, n_passthrough=0.3)      # episodes of 30 to 65 steps
     O, N, B = va.batch.obs_dim, va.n_turb, va.num_envs

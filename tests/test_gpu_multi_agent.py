@@ -7,29 +7,25 @@
 * NULL final pointer            outputs and ``get_state()`` equal a handle that never registered one, bit for bit;
 * wg_rollout_multi              equals its documented loop bit for bit (every buffer, the state, the step after it), meets the float64
                                 policy oracle on sampled envs, is shard-invariant and interleaves with ``step()``;
-* wg_gae_shared                 against the float64 reference of tests/multi_agent_ref.py and, at A = 1, wg_gae bit for bit;
+* wg_gae_shared                 against the float64 reference of oracle/ppo_oracle.py and, at A = 1, wg_gae bit for bit;
 * PPO on the multi-agent env    one iteration against the torch reference trainer on the flattened agent rows, save / load resume,
                                 a 20-iteration run without a NaN."""
 import copy
+import functools
 import os
 
 import numpy as np
 import pytest
 
-from loop_twin import rollout_equals_the_loop
-from multi_agent_ref import gae_shared
+import rl_helpers
 from oracle import policy_oracle as po
-from test_gpu_closed_loop import (LOGP_ATOL, RAW_ATOL, SMALL_BOX, SMALL_BOX_SPACING, VAL_ATOL, VAL_RTOL, _ti_farm_history_100, plan_of,  # noqa: F401
-                                  small_box)
-from test_gpu_policy import make
-from test_gpu_spotcheck import OBS_ATOL, TURB_OBS_ATOL
+from oracle.ppo_oracle import gae_shared
+from rl_helpers import (LOGP_ATOL, OBS_ATOL, RAW_ATOL, SMALL_BOX, SMALL_BOX_SPACING, TURB_OBS_ATOL, VAL_ATOL, VAL_RTOL, _ti_farm_history_100,
+                        _torch, rollout_equals_the_loop)
+from test_gpu_closed_loop import plan_of, small_box  # noqa: F401  (module-scoped fixtures, used by name)
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
+make = functools.partial(rl_helpers.make, draw="normal")        # (test_gpu_policy.py's policies)
 
 
 def _case(name):
@@ -289,7 +285,7 @@ def test_gae_shared_vs_reference_and_wg_gae(T, B, A):
 
 
 def test_ppo_one_iteration_vs_torch_reference_trainer_on_agent_rows():
-    from test_gpu_ppo import _torch_trainer
+    from rl_helpers import _torch_trainer
     from windgym_amd.ppo import PPO
     t = _torch()
     c = _case("cfg4_fused")

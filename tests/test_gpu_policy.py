@@ -1,4 +1,5 @@
 """GPU tests of k_policy, the wg_policy_* ABI, MlpPolicy and WindFarmVecEnv.rollout."""
+import functools
 import json
 import os
 import subprocess
@@ -7,8 +8,9 @@ import sys
 import numpy as np
 import pytest
 
-from loop_twin import rollout_equals_the_loop
+import rl_helpers
 from oracle import policy_oracle as po
+from rl_helpers import LIMIT_SHAPES, _torch, _venv, close, rollout_equals_the_loop, shape4, shape_id
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,50 +18,7 @@ FIX = os.path.join(ROOT, "tests", "golden", "ppo_2975000_policy.npz")
 
 SHAPES = [(8, (64, 64), 4), (32, (64, 64), 16), (7, (33,), 1), (200, (128, 128, 128), 2), (1600, (256, 256), 16),
           (160, (64, 64), 80), (32, (), 16)]
-# the limits of wg_policy.h as (n_in, hidden_pi, hidden_vf, n_out): four hidden layers of 256 (five layers with the head), 2048 inputs
-# (eight full first-layer chunks), 256 / 257 inputs (a chunk of exactly one input), 128 outputs (four head tiles, a 128-term
-# log-probability sum), and actor / critic stacks of different depth and width (SB3's net_arch=dict(pi=[...], vf=[...]))
-DEEP = (256, 256, 256, 256)
-LIMIT_SHAPES = [(256, DEEP, DEEP, 16), (2048, DEEP, DEEP, 128), (257, (64,), (64,), 3), (256, (32,), (32,), 33), (2048, (), (), 128),
-                (256, (64, 64), DEEP, 16), (32, (64, 64), DEEP, 16), (256, DEEP, (64, 64), 16), (200, (128, 128, 128), (), 2),
-                (32, (), (33,), 16), (160, (256,), (64, 64), 80)]
-
-
-def _stack(h):
-    return "x".join(map(str, h)) or "none"
-
-
-def shape4(shape):
-    """(n_in, hidden, n_out) of SHAPES or (n_in, hidden_pi, hidden_vf, n_out) of LIMIT_SHAPES -> the latter"""
-    return shape if len(shape) == 4 else (shape[0], shape[1], shape[1], shape[2])
-
-
-def shape_id(shape):
-    return f"{shape[0]}-{_stack(shape[1])}-{shape[2]}" if len(shape) == 3 else f"{shape[0]}-pi{_stack(shape[1])}-vf{_stack(shape[2])}-{shape[3]}"
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def make(n_in, hidden, n_out, activation="tanh", seed=3, hidden_vf="same"):
-    from windgym_amd.policy import MlpPolicy
-    p = MlpPolicy(n_in, n_out, hidden, hidden if hidden_vf == "same" else hidden_vf, activation, seed=seed)
-    rng = np.random.default_rng(seed + 1)
-    sd = {k: v.cpu().numpy() for k, v in p.state_dict().items()}
-    for k in sd:                                  # non-zero biases and log_std
-        if k.endswith("bias") or k == "log_std":
-            sd[k] = (0.3 * rng.standard_normal(sd[k].shape)).astype(np.float32)
-    p.load_state_dict(sd)
-    return p, sd
-
-
-def close(a, b, tol=2e-5, rel=0.0):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return bool(np.all(np.abs(a - b) <= tol + rel * np.abs(b)))
-
-
+make = functools.partial(rl_helpers.make, draw="normal")        # this file's cases were written for normal biases
 @pytest.mark.parametrize("activation", ["tanh", "relu"])
 @pytest.mark.parametrize("shape", SHAPES + LIMIT_SHAPES, ids=shape_id)
 def test_kernel_vs_oracle_deterministic(shape, activation):
@@ -151,17 +110,6 @@ def test_params_on_device_and_sync():
     assert close(got[1].cpu().numpy(), ref["raw"]) and close(got[3].cpu().numpy(), ref["value"], 2e-5, 2e-5)
     assert not t.equal(got[1], before)
     p.close()
-
-
-def _venv(n_envs=64, **kw):
-    from windgym_amd import presets
-    from windgym_amd.envs import WindFarmVecEnv
-    from windgym_amd.turbine import V80
-    args = dict(yaml_dict=presets.bench_cfg2_config(), seed=77, as_torch=True, turbtype="None", n_passthrough=1, n_rotor_pts=16)
-    args.update(kw)
-    v = WindFarmVecEnv(V80(), n_envs, **args)
-    v.reset(seed=77)
-    return v
 
 
 def test_rollout_equals_the_loop():

@@ -1,18 +1,16 @@
 """GPU tests of populations (wg_pop_*: windgym_amd/csrc/wg_policy.hip, wg_ppo.hip, wg_api.hip; windgym_amd/population.py): every
 population entry against the loop of single-policy calls it documents, by BIT equality."""
+import functools
+
 import numpy as np
 import pytest
 
-from loop_twin import rollout_equals_the_loop
+import rl_helpers
 from population_twin import MemberLoop, twin_rollout, twin_train
-from test_gpu_ppo import _venv, make
+from rl_helpers import _torch, _venv, rollout_equals_the_loop
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
+make = functools.partial(rl_helpers.make, dtype=np.float64)        # (test_gpu_ppo.py's policies)
 
 
 def _members(P, n_in=32, hidden=(64, 64), n_out=16, seed0=3):
@@ -186,7 +184,7 @@ def test_update_is_permuted_with_the_members():
     from windgym_amd.ppo import PPOOptimizer
     from windgym_amd.binding import CPpoBatch, CPpoHyper
     import ctypes as C
-    from test_gpu_ppo import batch, dev
+    from rl_helpers import batch, dev
     t = _torch()
     P, Bm, T, E, bs = 2, 40, 5, 2, 64
     B, rows_m = P * Bm, T * Bm

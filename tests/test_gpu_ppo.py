@@ -1,70 +1,28 @@
 """GPU tests of training on the device (windgym_amd/csrc/wg_ppo.hip, windgym_amd/ppo.py): k_gae, k_ppo_grad, the Adam step,
 wg_ppo_update and PPO.learn against oracle/ppo_oracle.py (float64, gradients from autograd) and a torch reference trainer."""
+import functools
 import os
 
 import numpy as np
 import pytest
 
-from oracle import policy_oracle as po
+import rl_helpers
 from oracle import ppo_oracle as oo
-from test_gpu_policy import LIMIT_SHAPES, shape4, shape_id
-from windgym_amd.policy import pack_params, param_layout
+from rl_helpers import LIMIT_SHAPES, _torch, _torch_trainer, _venv, batch, dev, flat_grad, shape4, shape_id
+from windgym_amd.policy import param_layout
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(8, (64, 64), 4), (32, (64, 64), 16), (7, (33,), 1), (200, (128, 128, 128), 2), (1600, (256, 256), 16),
           (160, (64, 64), 80), (32, (), 16)]                        # tests/test_gpu_policy.py's
+make = functools.partial(rl_helpers.make, dtype=np.float64)        # (the float64 state dict the oracle takes)
 STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss")
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def tile_id(shape):
     """the test id of a shape with the row tile R it must get (wg_ppo.h's LDS map, restated in oracle/ppo_oracle.py: tile_rows)"""
     n_in, hidden, hidden_vf, n_out = shape4(shape)
     return shape_id(shape) if len(shape) == 3 else f"{shape_id(shape)}-R{oo.tile_rows(n_in, n_out, hidden, hidden_vf)[0]}"
-
-
-def make(n_in, hidden, n_out, activation="tanh", seed=3, hidden_vf="same"):
-    """A policy with every tensor away from its initial value (biases and log_std included) + its float64 state dict."""
-    from windgym_amd.policy import MlpPolicy
-    p = MlpPolicy(n_in, n_out, hidden, hidden if hidden_vf == "same" else hidden_vf, activation, seed=seed)
-    rng = np.random.default_rng(seed + 1)
-    sd = {}
-    for name, shape in param_layout(p.desc):
-        a = p.state_dict()[name].cpu().numpy()
-        if len(shape) == 1:
-            a = rng.uniform(-0.3, 0.3, shape).astype(np.float32)
-        sd[name] = a
-    p.load_state_dict(sd)
-    return p, {k: v.astype(np.float64) for k, v in sd.items()}
-
-
-def batch(sd, n_in, n_out, n, activation, seed=0):
-    """Random rows whose ratios straddle both clip bounds: logp_old = the true log-probability + N(0, 0.3)."""
-    rng = np.random.default_rng(seed)
-    obs = rng.uniform(-1, 1, (n, n_in)).astype(np.float32)
-    mean, value = po.forward(sd, obs, activation)
-    std = np.exp(sd["log_std"])
-    raw = (mean + std * rng.standard_normal((n, n_out))).astype(np.float32)
-    z = (raw - mean) / std
-    logp = np.sum(-0.5 * z * z - sd["log_std"] - 0.5 * np.log(2 * np.pi), axis=1)
-    logp_old = (logp + 0.3 * rng.standard_normal(n)).astype(np.float32)
-    adv = rng.standard_normal(n).astype(np.float32) * 2.0 + 0.5
-    ret = (value + rng.standard_normal(n)).astype(np.float32)
-    return obs, raw, logp_old, adv, ret
-
-
-def dev(*arrays):
-    t = _torch()
-    return [t.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
-
-
-def flat_grad(desc, grads):
-    return pack_params(desc, {k: v.astype(np.float32) for k, v in grads.items()}).astype(np.float64)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -211,17 +169,6 @@ def test_grad_is_bit_identical_from_run_to_run():
     opt.close(); p.close()
 
 
-def _venv(n_envs=64, **kw):
-    from windgym_amd import presets
-    from windgym_amd.envs import WindFarmVecEnv
-    from windgym_amd.turbine import V80
-    args = dict(yaml_dict=presets.bench_cfg2_config(), seed=77, as_torch=True, turbtype="None", n_passthrough=1, n_rotor_pts=16)
-    args.update(kw)
-    v = WindFarmVecEnv(V80(), n_envs, **args)
-    v.reset(seed=77)
-    return v
-
-
 def test_unchanged_parameters_give_ratio_one():
     """The forward recomputation is k_policy's: on a fresh rollout mean and V are the stored ones, so nothing is clipped."""
     from windgym_amd.ppo import PPO
@@ -299,39 +246,6 @@ def test_update_equals_the_documented_loop():
     for o in (oa, ob):
         o.close()
     pa.close(); pb.close()
-
-
-def _torch_trainer(policy, out, adv, ret, perm, bs, lr, clip, vf_coef, ent_coef, max_norm):
-    """The reference trainer: torch_forward + autograd + torch.optim.Adam on a float32 copy of the parameters."""
-    t = _torch()
-    T = out["raw"].shape[0]
-    O, N = policy.n_in, policy.n_out
-    obs, raw, lpo = out["obs"][:T].reshape(-1, O), out["raw"].reshape(-1, N), out["logp"].reshape(-1)
-    adv, ret = adv.reshape(-1), ret.reshape(-1)
-    saved = policy.params
-    w = saved.detach().clone().requires_grad_(True)
-    policy.params = w
-    opt = t.optim.Adam([w], lr=lr, eps=1e-5)
-    try:
-        for e in range(perm.shape[0]):
-            for s in range(0, perm.shape[1], bs):
-                i = perm[e, s:s + bs].long()
-                mean, V = policy.torch_forward(obs[i])
-                ls = w[-N:]
-                z = (raw[i] - mean) / t.exp(ls)
-                logp = (-0.5 * z * z - ls - 0.5 * float(np.log(2 * np.pi))).sum(1)
-                ratio = t.exp(logp - lpo[i])
-                A = adv[i]
-                A = (A - A.mean()) / (A.std() + 1e-8)
-                l_pi = -t.min(ratio * A, t.clamp(ratio, 1 - clip, 1 + clip) * A).mean()
-                loss = l_pi + vf_coef * ((ret[i] - V) ** 2).mean() - ent_coef * (0.5 + 0.5 * float(np.log(2 * np.pi)) + ls).sum()
-                opt.zero_grad()
-                loss.backward()
-                t.nn.utils.clip_grad_norm_([w], max_norm)
-                opt.step()
-    finally:
-        policy.params = saved
-    return w.detach()
 
 
 def _small_box():

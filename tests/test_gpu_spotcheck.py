@@ -12,18 +12,13 @@ import sys
 import numpy as np
 import pytest
 
+from rl_helpers import (N_SAMPLE, OBS_ATOL, TURB_OBS_ATOL, TURB_POW_ATOL, TURB_POW_RTOL, TURB_REW_ATOL, TURB_REW_RTOL, TURB_UVW_ATOL,
+                        TURB_UVW_RTOL)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-OBS_ATOL = 2e-4
-# Frozen-box inflow (cfg5), with the worst error observed on an MI355X over the 16 sampled envs x 300 steps of the two cfg5 tests below
-# (small box / reference box) next to each bar; every bar was 30 to 70 times its worst case and is now 3.5 to 5 times it:
-TURB_OBS_ATOL = 8e-5                         # was 5e-4: worst 1.66e-5 / 1.57e-5
-TURB_REW_RTOL, TURB_REW_ATOL = 1e-4, 8e-5    # was 1e-3, 1e-3: worst 1.68e-5 / 1.54e-5
-TURB_UVW_RTOL, TURB_UVW_ATOL = 1e-4, 1.5e-3  # was 2e-3, 2e-3: worst 4.25e-4 / 4.21e-4 m/s (the wake deficits in float32, about 5e-5 of U)
-TURB_POW_RTOL, TURB_POW_ATOL = 4e-4, 400.0   # was 5e-3, 2000 W: worst 113 / 117 W
-N_SAMPLE = 16
 STEPS = 300
 
 

@@ -1,6 +1,6 @@
 """CPU tests of the multi-agent path (one agent per turbine, one shared policy): the new ABI entries and their buffer struct
 are the same in the header, the built library and the ctypes mirror; the float64 shared-reward GAE reference
-(tests/multi_agent_ref.py) against its definition and against the single-agent oracle; argument validation of
+(oracle/ppo_oracle.py) against its definition and against the single-agent oracle; argument validation of
 ``WindFarmVecEnvMulti`` and of ``PPO`` on a multi-agent env that needs no device.  The kernels are tested on the GPU
 (tests/test_gpu_multi_agent.py)."""
 import ctypes as C
@@ -12,8 +12,8 @@ import types
 import numpy as np
 import pytest
 
-from multi_agent_ref import gae_shared, gae_shared_brute
 from oracle import ppo_oracle as oo
+from oracle.ppo_oracle import gae_shared, gae_shared_brute
 from windgym_amd import binding, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -73,6 +73,7 @@ def test_member_checkpoint_is_a_plain_ppo_zip(tmp_path):
 
     import torch
     from windgym_amd.policy import make_desc, n_params, param_layout, read_sb3_zip
+    from windgym_amd.ppo import write_checkpoint
     desc = make_desc(6, 2, (8,), (8,), "tanh", True, None)
     flat = torch.arange(n_params(desc), dtype=torch.float32) * 0.01
 
@@ -95,8 +96,7 @@ def test_member_checkpoint_is_a_plain_ppo_zip(tmp_path):
     g.manual_seed(5)
     hyper = dict(n_steps=16, batch_size=32, n_epochs=3, gamma=0.9, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
                  max_grad_norm=0.5, learning_rate=lambda p: 1e-3, normalize_advantage=True)
-    ck = pop._MemberCheckpoint(Pol(), Opt(), g, type("V", (), dict(_policy_steps=48))(), hyper, 5, 384, 3, [dict(member=1, loss=0.5)])
-    path = ck.save(str(tmp_path / "member_01.zip"))
+    path = write_checkpoint(str(tmp_path / "member_01.zip"), Pol(), Opt(), g, hyper, 5, 384, 3, [dict(member=1, loss=0.5)], None, 48)
     d, tensors = read_sb3_zip(path)
     assert d["n_in"] == 6 and d["n_out"] == 2 and d["hidden_pi"] == (8,)
     assert np.array_equal(np.asarray(tensors["log_std"]), flat[-2:].numpy())

@@ -279,28 +279,30 @@ class HipBatch:
             _chk(rc, "wg_step")
         return self.obs, self.reward, self.truncated, self.final_obs
 
-    def _rollout(self, entry, cls, keys, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
-        """The closed loop ``entry`` (wg_rollout / wg_rollout_multi) into contiguous CUDA tensors: ``bufs[k]`` for the pointer
-        fields of ``cls`` in order (``keys``; a missing one is NULL = not wanted), ``bufs[name]`` for every info name in
-        ``record``."""
+    ROLLOUT_KEYS = ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward", "truncated")   # wg_rollout_bufs
+
+    @staticmethod
+    def _rollout_bufs(cls, keys, bufs, record):
+        """``cls`` (wg_rollout_bufs / wg_rollout_multi_bufs) from contiguous CUDA tensors: ``bufs[k]`` for its pointer fields in
+        order (``keys``; a missing one is NULL = not wanted), ``bufs[name]`` for every info name in ``record``."""
         n = len(record)
-        cb = cls(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n,
-                 (C.c_int32 * max(1, n))(*[INFO[r] for r in record]), (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))
+        return cls(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n,
+                   (C.c_int32 * max(1, n))(*[INFO[r] for r in record]), (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))
+
+    def _rollout(self, entry, cls, keys, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
+        """The closed loop ``entry`` (wg_rollout / wg_rollout_multi) into the tensors of :meth:`_rollout_bufs`."""
+        cb = self._rollout_bufs(cls, keys, bufs, record)
         _chk(getattr(self.L, entry)(self._h, policy._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
                                     C.byref(cb), self._stream()), entry)
 
     def rollout(self, *args):
         """wg_rollout(policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset); ``bufs`` keyed by wg_rollout_bufs' fields."""
-        self._rollout("wg_rollout", CRolloutBufs, ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward",
-                                                   "truncated"), *args)
+        self._rollout("wg_rollout", CRolloutBufs, self.ROLLOUT_KEYS, *args)
 
     def rollout_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
         """wg_pop_rollout, the arguments of :meth:`rollout` with a ``population.Population`` in the policy's place: every member
         samples with the one ``seed``, member ``m``'s noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
-        n, P = len(record), pop.n_members
-        keys = ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward", "truncated")
-        cb = CRolloutBufs(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n,
-                          (C.c_int32 * max(1, n))(*[INFO[r] for r in record]), (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))
+        P, cb = pop.n_members, self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
         Bm = self.B // P
         _chk(self.L.wg_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), (C.c_uint64 * P)(*[int(seed)] * P), counter0,
                                    (C.c_uint64 * P)(*[int(row_offset) + m * Bm for m in range(P)]), C.byref(cb), self._stream()),
@@ -308,8 +310,7 @@ class HipBatch:
 
     def rollout_multi(self, *args):
         """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""
-        self._rollout("wg_rollout_multi", CRolloutMultiBufs, ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value",
-                                                              "reward", "truncated", "flat_obs", "flat_final_obs"), *args)
+        self._rollout("wg_rollout_multi", CRolloutMultiBufs, self.ROLLOUT_KEYS + ("flat_obs", "flat_final_obs"), *args)
 
     def set_step_graph(self, enable=True):
         """step() as one hipGraphLaunch (captured per distinct set of I/O pointers) instead of direct launches."""

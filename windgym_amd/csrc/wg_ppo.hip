@@ -542,14 +542,26 @@ static int t_on_device(const void* p, int device, const char* what) {
     return 0;
 }
 
-// wg_gae (A = 1) and wg_gae_shared: `who` and `dims` name the caller and its sizes in the messages
+// The argument checks of every wg_gae* entry.  `who`, `dims` and `rows` name the caller, its sizes and its B * A rows in the
+// messages; `all_there`: no pointer argument is null; P: the members the B envs divide among (1: one policy, always passes).
+static int gae_check(const char* who, const char* dims, const char* rows, bool all_there, int T, int B, int A, int P) {
+    const std::string w = who;
+    if (!all_there) return tfail(WG_ERR_INVALID, w + ": null argument");
+    if (T < 1 || B < 1 || A < 1) return tfail(WG_ERR_INVALID, w + ": " + dims + " must be >= 1");
+    if (P < 1 || P > WG_POP_MAX || B % P != 0)
+        return tfail(WG_ERR_INVALID, w + ": P = " + std::to_string(P) + " must lie in 1 .. " + std::to_string(WG_POP_MAX) +
+                                         " and divide B = " + std::to_string(B));
+    if ((long long)B * A > 0x7fffffffLL - 256) return tfail(WG_ERR_UNSUPPORTED, w + ": more than 2^31 " + rows);
+    return 0;
+}
+
+// wg_gae (A = 1) and wg_gae_shared
 static int gae_launch(const char* who, const char* dims, int T, int B, int A, const float* reward_dev, const float* value_dev,
                       const float* final_value_dev, const uint8_t* truncated_dev, float gamma, float lambda, float* advantage_out,
                       float* returns_out, void* stream) {
-    if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !advantage_out || !returns_out)
-        return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
-    if (T < 1 || B < 1 || A < 1) return tfail(WG_ERR_INVALID, std::string(who) + ": " + dims + " must be >= 1");
-    if ((long long)B * A > 0x7fffffffLL - 256) return tfail(WG_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 agent rows");
+    if (int rc = gae_check(who, dims, "agent rows", reward_dev && value_dev && final_value_dev && truncated_dev && advantage_out && returns_out,
+                           T, B, A, 1))
+        return rc;
     hipLaunchKernelGGL(k_gae, dim3((B * A + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, A, reward_dev, value_dev,
                        final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
     THIPCHK(hipGetLastError());
@@ -673,17 +685,29 @@ extern "C" int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64
     return 0;
 }
 
+// the rows of a batch and the critic's stream (a plain batch: its obs), for every entry that takes one
+static int t_check_rows(const char* who, const wg_ppo_batch* b, const float* obs_vf) {
+    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !obs_vf)
+        return tfail(WG_ERR_INVALID, std::string(who) + ": a batch pointer is null");
+    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, std::string(who) + ": n_rows out of range");
+    return 0;
+}
+
 // (`who` is the entry the CALLER used: wg_ppo_grad is wg_ppo_grad_shared on {*batch, batch->obs, 1} and reports under its own name)
 static int t_check_batch(const char* who, const wg_ppo_batch_shared* sb, const wg_ppo_hyper* hp) {
     if (!sb || !hp) return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
     const wg_ppo_batch* b = &sb->rows;
-    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !sb->obs_vf)
-        return tfail(WG_ERR_INVALID, std::string(who) + ": a batch pointer is null");
-    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, std::string(who) + ": n_rows out of range");
+    if (int rc = t_check_rows(who, b, sb->obs_vf)) return rc;
     if (sb->agents < 1 || b->n_rows % sb->agents != 0)
         return tfail(WG_ERR_INVALID, std::string(who) + ": agents must be >= 1 and divide n_rows (" + std::to_string(b->n_rows) + ")");
     if (!(hp->clip_range >= 0.0f)) return tfail(WG_ERR_INVALID, std::string(who) + ": clip_range < 0");
     return 0;
+}
+
+// workgroups per net of a gradient launch on n rows: one per tile of R rows, at most as many as the partial sums have room for
+static int t_grid(const wg_ppo_s* o, int n) {
+    const int R = o->K.R, ntile = (n + R - 1) / R;
+    return ntile < o->g_max ? ntile : o->g_max;
 }
 
 // the launches of one gradient, no argument checks
@@ -691,7 +715,7 @@ static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* 
                   const wg_ppo_hyper* hp, float* grad_out, float* stats_out, hipStream_t st) {
     const WgPolicyP& P = o->pol->P;
     const wg_ppo_batch* b = &sb->rows;
-    const int R = o->K.R, ntile = (n + R - 1) / R, G = ntile < o->g_max ? ntile : o->g_max;
+    const int G = t_grid(o, n);
     const int normalize = hp->normalize_advantage && n > 1;
     if (normalize) hipLaunchKernelGGL(k_ppo_advstat, dim3(1), dim3(1024), 0, st, b->advantage, index_dev, first, n, b->n_rows, sb->agents, o->advstat);
     WgPpoArgs a;
@@ -705,14 +729,23 @@ static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* 
     return 0;
 }
 
-static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
-    const double b1 = 0.9, b2 = 0.999;
+// Adam's constants (the kernels take 1 - beta1, beta2, 1 - beta2 and eps) and, per step, the two scalars of t_adam_step
+static const double ADAM_B1 = 0.9, ADAM_B2 = 0.999;
+static const float ADAM_EPS = 1e-5f;
+struct AdamStep { float step_size, bc2_sqrt; };          // lr / (1 - beta1^step), sqrt(1 - beta2^step)
+
+// counts one more step of `o` and -> that step's scalars (bias corrections in double, rounded once)
+static AdamStep t_adam_step(wg_ppo_s* o, float lr) {
     o->step += 1;
-    const double bc1 = 1.0 - std::pow(b1, (double)o->step), bc2 = 1.0 - std::pow(b2, (double)o->step);
+    const double bc1 = 1.0 - std::pow(ADAM_B1, (double)o->step), bc2 = 1.0 - std::pow(ADAM_B2, (double)o->step);
+    return {(float)((double)lr / bc1), (float)std::sqrt(bc2)};
+}
+
+static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
+    const AdamStep s = t_adam_step(o, lr);
     hipLaunchKernelGGL(k_ppo_sumsq, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, o->n_flat, o->blocksq);
     hipLaunchKernelGGL(k_ppo_adam, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, o->m, o->v, o->n_flat,
-                       o->blocksq, o->n_blocks, max_grad_norm, (float)((double)lr / bc1), (float)std::sqrt(bc2), (float)(1.0 - b1),
-                       (float)b2, (float)(1.0 - b2), 1e-5f);
+                       o->blocksq, o->n_blocks, max_grad_norm, s.step_size, s.bc2_sqrt, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
     THIPCHK(hipGetLastError());
     return wg_policy_set_params(o->pol, params_dev, o->n_flat, 1, (void*)st);
 }
@@ -764,6 +797,22 @@ extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, 
     return t_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
 }
 
+// One update: n_epochs passes over `rows` rows (one row of the permutation each) in minibatches of batch_size, the last one of
+// an epoch shorter.  f(mb, off, n) runs once per minibatch, in order: mb = its index in the update (the slot of its
+// statistics), off = its offset into the permutation, n = its rows.
+static int t_n_minibatches(int64_t rows, int batch_size) { return (int)((rows + batch_size - 1) / batch_size); }
+template <class F>
+static int t_each_minibatch(int64_t rows, int n_epochs, int batch_size, F f) {
+    const int n_mb = t_n_minibatches(rows, batch_size);
+    for (int e = 0; e < n_epochs; ++e)
+        for (int k = 0; k < n_mb; ++k) {
+            const int64_t start = (int64_t)k * batch_size;
+            const int n = (int)(rows - start < batch_size ? rows - start : batch_size);
+            if (int rc = f(e * n_mb + k, (int64_t)e * rows + start, n)) return rc;
+        }
+    return 0;
+}
+
 static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
                         int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream) {
     const std::string w = who;
@@ -777,17 +826,11 @@ static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_p
     if (b->obs_vf != b->rows.obs)
         if (int rc = t_on_device(b->obs_vf, o->device, (w + ": obs_vf").c_str())) return rc;
     if (int rc = t_on_device(perm_dev, o->device, (w + ": perm_dev").c_str())) return rc;
-    const int64_t n_rows = b->rows.n_rows;
-    const int n_mb = (int)((n_rows + batch_size - 1) / batch_size);
-    for (int e = 0; e < n_epochs; ++e)
-        for (int k = 0; k < n_mb; ++k) {
-            const int64_t start = (int64_t)k * batch_size;
-            const int n = (int)(n_rows - start < batch_size ? n_rows - start : batch_size);
-            float* so = stats_out ? (float*)(stats_out + (size_t)e * n_mb + k) : nullptr;
-            if (int rc = t_grad(o, params_dev, b, perm_dev + (size_t)e * n_rows + start, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
-            if (int rc = t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream)) return rc;
-        }
-    return 0;
+    return t_each_minibatch(b->rows.n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
+        float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
+        if (int rc = t_grad(o, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        return t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
+    });
 }
 
 extern "C" int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
@@ -866,13 +909,9 @@ extern "C" int wg_pop_destroy(wg_pop q) {
 extern "C" int wg_gae_pop(int T, int B, int P, const float* reward_dev, const float* value_dev, const float* final_value_dev,
                           const uint8_t* truncated_dev, const float* gamma, const float* lambda, float* advantage_out,
                           float* returns_out, void* stream) {
-    if (!reward_dev || !value_dev || !final_value_dev || !truncated_dev || !gamma || !lambda || !advantage_out || !returns_out)
-        return tfail(WG_ERR_INVALID, "wg_gae_pop: null argument");
-    if (T < 1 || B < 1) return tfail(WG_ERR_INVALID, "wg_gae_pop: T and B must be >= 1");
-    if (P < 1 || P > WG_POP_MAX || B % P != 0)
-        return tfail(WG_ERR_INVALID, "wg_gae_pop: P = " + std::to_string(P) + " must lie in 1 .. " + std::to_string(WG_POP_MAX) +
-                                         " and divide B = " + std::to_string(B));
-    if (B > 0x7fffffff - 256) return tfail(WG_ERR_UNSUPPORTED, "wg_gae_pop: more than 2^31 rows");
+    if (int rc = gae_check("wg_gae_pop", "T and B", "rows", reward_dev && value_dev && final_value_dev && truncated_dev && gamma && lambda &&
+                           advantage_out && returns_out, T, B, 1, P))
+        return rc;
     WgPopGae hy = {};
     for (int m = 0; m < P; ++m) { hy.gamma[m] = gamma[m]; hy.lambda[m] = lambda[m]; }
     hipLaunchKernelGGL(k_gae_pop, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, B / P, reward_dev, value_dev,
@@ -887,8 +926,7 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return tfail(WG_ERR_INVALID, "wg_pop_update: null argument");
     const int P = q->P;
     if (!q->opt[0]) return tfail(WG_ERR_INVALID, "wg_pop_update: the population was created without optimisers (opts = NULL): it only acts");
-    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns) return tfail(WG_ERR_INVALID, "wg_pop_update: a batch pointer is null");
-    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, "wg_pop_update: n_rows out of range");
+    if (int rc = t_check_rows("wg_pop_update", b, b->obs)) return rc;
     if (b->n_rows % P != 0)
         return tfail(WG_ERR_INVALID, "wg_pop_update: the " + std::to_string(P) + " members own equal shares of the batch, and " +
                                          std::to_string(b->n_rows) + " rows do not divide by " + std::to_string(P));
@@ -905,7 +943,7 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     if (int rc = t_on_device(perm_dev, q->device, "wg_pop_update: perm_dev")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows_m = b->n_rows / P;
-    const int n_mb = (int)((rows_m + batch_size - 1) / batch_size);
+    const int n_mb = t_n_minibatches(rows_m, batch_size);
     WgPopMember tab[WGP_POP_MAX] = {};
     for (int m = 0; m < P; ++m) {
         wg_ppo_s* o = q->opt[m];
@@ -925,31 +963,24 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     const WgPolicyP& PP = o0->pol->P;
     bool any_norm = false;
     for (int m = 0; m < P; ++m) any_norm = any_norm || tab[m].normalize;
-    const double b1 = 0.9, b2 = 0.999;
-    for (int e = 0; e < n_epochs; ++e)
-        for (int k = 0; k < n_mb; ++k) {
-            const int64_t start = (int64_t)k * batch_size, off = (int64_t)e * rows_m + start;
-            const int n = (int)(rows_m - start < batch_size ? rows_m - start : batch_size), mb = e * n_mb + k;
-            const int R = o0->K.R, ntile = (n + R - 1) / R, G = ntile < o0->g_max ? ntile : o0->g_max;
-            if (any_norm && n > 1) hipLaunchKernelGGL(k_ppo_advstat_pop, dim3(P), dim3(1024), 0, st, mt, b->advantage, off, n, b->n_rows);
-            WgPpoArgs a = {};
-            a.obs[0] = b->obs; a.obs[1] = b->obs; a.agents = 1; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage; a.ret = b->returns;
-            a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
-            hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), o0->lds_bytes, st, PP, o0->K, a, mt, off);
-            hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
-            WgPopAdam A = {};
-            for (int m = 0; m < P; ++m) {                  // (t_apply's arithmetic, per member)
-                wg_ppo_s* o = q->opt[m];
-                o->step += 1;
-                const double bc1 = 1.0 - std::pow(b1, (double)o->step), bc2 = 1.0 - std::pow(b2, (double)o->step);
-                A.step_size[m] = (float)((double)lr[m] / bc1);
-                A.bc2_sqrt[m] = (float)std::sqrt(bc2);
-            }
-            hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat);
-            hipLaunchKernelGGL(k_ppo_adam_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat, o0->n_blocks, A,
-                               (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-5f);
-            wg_policy_pack_pop_(&PP, mt, P, stream);
-            THIPCHK(hipGetLastError());
+    return t_each_minibatch(rows_m, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
+        const int G = t_grid(o0, n);
+        if (any_norm && n > 1) hipLaunchKernelGGL(k_ppo_advstat_pop, dim3(P), dim3(1024), 0, st, mt, b->advantage, off, n, b->n_rows);
+        WgPpoArgs a = {};
+        a.obs[0] = b->obs; a.obs[1] = b->obs; a.agents = 1; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage; a.ret = b->returns;
+        a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
+        hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), o0->lds_bytes, st, PP, o0->K, a, mt, off);
+        hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
+        WgPopAdam A = {};
+        for (int m = 0; m < P; ++m) {
+            const AdamStep s = t_adam_step(q->opt[m], lr[m]);
+            A.step_size[m] = s.step_size;
+            A.bc2_sqrt[m] = s.bc2_sqrt;
         }
-    return 0;
+        hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat);
+        hipLaunchKernelGGL(k_ppo_adam_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat, o0->n_blocks, A, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+        wg_policy_pack_pop_(&PP, mt, P, stream);
+        THIPCHK(hipGetLastError());
+        return 0;
+    });
 }

@@ -171,6 +171,22 @@ def read_sb3_zip(path, activation="tanh"):
 # ----------------------------------------------------------------------------------------------------------------------
 # the device object
 # ----------------------------------------------------------------------------------------------------------------------
+def device_tensor(x, dtype):
+    """What every tensor handed to the library must be: a contiguous CUDA tensor of ``dtype`` (its size is the caller's to check)."""
+    import torch
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous()
+
+
+def act_buffers(owner, n):
+    """The persistent ``(action, raw, logp, value)`` outputs of ``act()`` on ``n`` rows, made once per ``n`` and kept in
+    ``owner._out`` (``owner``: a policy or a population — ``torch``, ``device``, ``n_out``)."""
+    b = owner._out.get(n)
+    if b is None:
+        t, f32 = owner.torch, dict(dtype=owner.torch.float32, device=owner.device)
+        b = owner._out[n] = (t.zeros((n, owner.n_out), **f32), t.zeros((n, owner.n_out), **f32), t.zeros(n, **f32), t.zeros(n, **f32))
+    return b
+
+
 class MlpPolicy:
     """SB3's default ``MlpPolicy`` (actor ``n_in -> hidden_pi -> n_out``, critic ``n_in -> hidden_vf -> 1``) on one GPU.
     With ``n_in_vf`` the critic maps ``n_in_vf -> hidden_vf -> 1`` instead (a split policy: ``act()`` evaluates the actor only,
@@ -294,25 +310,16 @@ class MlpPolicy:
         return mean, value
 
     # -- evaluation ---------------------------------------------------------------------------------
-    def _buffers(self, n):
-        b = self._out.get(n)
-        if b is None:
-            t, f32 = self.torch, dict(dtype=self.torch.float32, device=self.device)
-            b = (t.zeros((n, self.n_out), **f32), t.zeros((n, self.n_out), **f32), t.zeros(n, **f32), t.zeros(n, **f32))
-            self._out[n] = b
-        return b
-
     def act(self, obs, deterministic=False, counter=None, *, seed=None, row_offset=0, value=True, out=None):
         """ONE launch of k_policy on a contiguous float32 CUDA tensor ``[..., n_in]`` -> persistent ``(action, raw, logp,
         value)`` tensors (rows = the leading dimensions flattened; valid until the next ``act()`` on as many rows; value is
         None without a critic, with ``value=False`` or on a split policy, whose critic reads other rows: :meth:`value`).  No
         synchronisation.  ``counter`` defaults to a running count."""
         t = self.torch
-        if not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
-                and obs.shape[-1] == self.n_in):
+        if not (device_tensor(obs, t.float32) and obs.shape[-1] == self.n_in):
             raise ValueError(f"act(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in}]")
         n = obs.numel() // self.n_in
-        a, r, lp, v = out if out is not None else self._buffers(n)
+        a, r, lp, v = out if out is not None else act_buffers(self, n)
         want_v = value and self.has_critic and not self.split
         stochastic = not deterministic
         if counter is None:
@@ -333,8 +340,7 @@ class MlpPolicy:
         t = self.torch
         if not self.has_critic:
             raise ValueError("value(): the policy has no critic")
-        if self.split and not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
-                               and obs.shape[-1] == self.n_in_vf):
+        if self.split and not (device_tensor(obs, t.float32) and obs.shape[-1] == self.n_in_vf):
             raise ValueError(f"value(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in_vf}] (the critic's input width)")
         n = obs.numel() // self.n_in_vf
         v = out if out is not None else t.zeros(n, dtype=t.float32, device=self.device)

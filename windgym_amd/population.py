@@ -13,11 +13,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import time
 
 import numpy as np
 
-from .ppo import PPO, PPOOptimizer, _schedule
+from .policy import act_buffers, device_tensor
+from .ppo import PPO, PPOOptimizer, _schedule, check_batch_size, check_hyper, learn_loop, write_checkpoint
 
 POP_MAX = 16            # WG_POP_MAX
 PER_MEMBER = ("gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "learning_rate", "normalize_advantage")
@@ -102,16 +102,11 @@ class Population:
         members' own seeds); ``row_offset``: a list per member, or a scalar = the global row of member 0's first row, member
         ``m``'s being ``row_offset + m * Bm`` — with one seed for all, the noise of one policy on the whole batch."""
         t = self.torch
-        if not (isinstance(obs, t.Tensor) and obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous() and obs.shape[-1] == self.n_in):
+        if not (device_tensor(obs, t.float32) and obs.shape[-1] == self.n_in):
             raise ValueError(f"act(): obs must be a contiguous float32 CUDA tensor [..., {self.n_in}]")
         n = obs.numel() // self.n_in
         Bm = check_population_shape(self.n_members, n)
-        if out is None:
-            out = self._out.get(n)
-            if out is None:
-                f32 = dict(dtype=t.float32, device=self.device)
-                out = self._out[n] = (t.zeros((n, self.n_out), **f32), t.zeros((n, self.n_out), **f32), t.zeros(n, **f32), t.zeros(n, **f32))
-        a, r, lp, v = out
+        a, r, lp, v = out if out is not None else act_buffers(self, n)
         want_v = value and self.has_critic
         ls = self.desc["has_log_std"]
         offs = row_offset if isinstance(row_offset, (list, tuple, np.ndarray)) else [int(row_offset) + m * Bm for m in range(self.n_members)]
@@ -130,20 +125,6 @@ class Population:
         self._chk(self.L.wg_pop_act(self._h, n, obs.data_ptr(), 1, None, 0, None, None, None, None, v.data_ptr(), self._stream()),
                   "wg_pop_act")
         return v
-
-
-class _MemberCheckpoint:
-    """What ``PPO.save`` reads, for ONE member: its zip is a plain PPO checkpoint of a run on the member's shard of the batch."""
-    _hyper_json = PPO._hyper_json
-    critic = None
-
-    def __init__(self, policy, opt, gen, venv, hyper, seed, num_timesteps, iteration, log):
-        self.policy, self.opt, self._gen, self.venv, self.seed = policy, opt, gen, venv, seed
-        self.num_timesteps, self.iteration, self.log = num_timesteps, iteration, log
-        for k, v in hyper.items():
-            setattr(self, k, v)
-
-    save = PPO.save
 
 
 class PPOPopulation:
@@ -184,24 +165,17 @@ class PPOPopulation:
         self.n_members = P = int(n_members)
         self.n_envs = B = int(venv.num_envs)
         self.n_envs_member = Bm = check_population_shape(P, B)
-        n_steps, n_epochs = int(n_steps), int(n_epochs)
-        if n_steps < 1 or n_epochs < 1:
-            raise ValueError("n_steps and n_epochs must be >= 1")
-        self.n_rows = rows_m = n_steps * Bm                                # rows of ONE member
-        batch_size = max(1, rows_m // 4) if batch_size is None else int(batch_size)
-        if not 1 <= batch_size <= rows_m:
-            raise ValueError(f"batch_size must lie in [1, n_steps * num_envs / n_members = {rows_m}]")
-        self.n_steps, self.n_epochs, self.batch_size = n_steps, n_epochs, batch_size
         hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
                      max_grad_norm=max_grad_norm, learning_rate=learning_rate, normalize_advantage=normalize_advantage)
         for k in PER_MEMBER:
             setattr(self, k, broadcast_hyper(k, hyper[k], P))
         self.seed = broadcast_hyper("seed", seed, P)
         for m in range(P):
-            if not 0.0 <= float(self.gamma[m]) <= 1.0 or not 0.0 <= float(self.gae_lambda[m]) <= 1.0:
-                raise ValueError(f"member {m}: gamma and gae_lambda must lie in [0, 1]")
-            if not float(self.max_grad_norm[m]) > 0.0:
-                raise ValueError(f"member {m}: max_grad_norm must be > 0")
+            check_hyper(n_steps, n_epochs, self.gamma[m], self.gae_lambda[m], self.max_grad_norm[m], f"member {m}: ")
+        n_steps, n_epochs = int(n_steps), int(n_epochs)
+        self.n_rows = rows_m = n_steps * Bm                                # rows of ONE member
+        batch_size = check_batch_size(batch_size, rows_m, "n_steps * num_envs / n_members")
+        self.n_steps, self.n_epochs, self.batch_size = n_steps, n_epochs, batch_size
         self._lr = [_schedule(x, "learning_rate") for x in self.learning_rate]
         self._clip = [_schedule(x, "clip_range") for x in self.clip_range]
         self.venv = venv
@@ -285,35 +259,24 @@ class PPOPopulation:
         """Iterations of rollout + update until every member collected ``total_timesteps`` env steps on its own envs.
         ``callback(pop) -> bool`` runs once per iteration; False stops.  Every ``log_interval``-th iteration appends a list of
         one record per member to ``self.log`` (ONE device-to-host copy for the whole population)."""
+        return learn_loop(self, total_timesteps, callback, log_interval, reset_num_timesteps,
+                          lambda progress: ([float(f(progress)) for f in self._lr], [float(f(progress)) for f in self._clip]), self._record)
+
+    def _record(self, out, stats, lr, clip, fps):
         from .binding import PPO_STATS
-        t, P = self.torch, self.n_members
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-        start, total = self.num_timesteps, int(total_timesteps) + (0 if reset_num_timesteps else self.num_timesteps)
-        t0 = time.perf_counter()
-        while self.num_timesteps < total:
-            progress = 1.0 - (self.num_timesteps - 0.0) / max(total, 1)
-            lr, clip = [float(f(progress)) for f in self._lr], [float(f(progress)) for f in self._clip]
-            out = self.collect()
-            stats = self.train(out, lr, clip)
-            self.num_timesteps += self.n_env_steps
-            self.iteration += 1
-            if log_interval and self.iteration % int(log_interval) == 0:
-                self.venv.batch.metrics(reset_after=True)                 # (whole-batch sums, not used: consumed as PPO.learn does)
-                host = t.cat([stats.double().mean(dim=(1, 2)), self._member_metrics(out)], dim=1).cpu().numpy()   # the one copy
-                fps = (self.num_timesteps - start) / max(time.perf_counter() - t0, 1e-9)
-                recs = []
-                for m in range(P):
-                    rec = dict(zip(PPO_STATS, host[m, :8].tolist()))
-                    ev, n_ep, ep_sum, rew_sum, n_st = host[m, 8:13].tolist()
-                    rec.update(member=m, explained_variance=ev, iteration=self.iteration, num_timesteps=self.num_timesteps,
-                               learning_rate=lr[m], clip_range=clip[m], n_episodes=n_ep, mean_episode_return=ep_sum / max(n_ep, 1.0),
-                               mean_step_reward=rew_sum / max(n_st, 1.0), fps=fps)
-                    recs.append(rec)
-                self.log.append(recs)
-            if callback is not None and callback(self) is False:
-                break
-        return self
+        t = self.torch
+        self.venv.batch.metrics(reset_after=True)                 # (whole-batch sums, not used: consumed as PPO.learn does)
+        host = t.cat([stats.double().mean(dim=(1, 2)), self._member_metrics(out)], dim=1).cpu().numpy()   # the one copy
+        fps = fps()
+        recs = []
+        for m in range(self.n_members):
+            rec = dict(zip(PPO_STATS, host[m, :8].tolist()))
+            ev, n_ep, ep_sum, rew_sum, n_st = host[m, 8:13].tolist()
+            rec.update(member=m, explained_variance=ev, iteration=self.iteration, num_timesteps=self.num_timesteps,
+                       learning_rate=lr[m], clip_range=clip[m], n_episodes=n_ep, mean_episode_return=ep_sum / max(n_ep, 1.0),
+                       mean_step_reward=rew_sum / max(n_st, 1.0), fps=fps)
+            recs.append(rec)
+        return recs
 
     # -- checkpoints ----------------------------------------------------------------------------------------------
     def member_hyper(self, m):
@@ -325,13 +288,9 @@ class PPOPopulation:
     def save(self, directory):
         """``directory/member_00.zip`` ...: each a plain ``PPO`` checkpoint (see :meth:`PPO.save`) of the member's run on its shard."""
         os.makedirs(directory, exist_ok=True)
-        paths = []
-        for m in range(self.n_members):
-            log = [recs[m] for recs in self.log]
-            ck = _MemberCheckpoint(self.members[m], self.opts[m], self._gens[m], self.venv, self.member_hyper(m), self.seed[m],
-                                   self.num_timesteps, self.iteration, log)
-            paths.append(ck.save(os.path.join(directory, f"member_{m:02d}.zip")))
-        return paths
+        return [write_checkpoint(os.path.join(directory, f"member_{m:02d}.zip"), self.members[m], self.opts[m], self._gens[m],
+                                 self.member_hyper(m), self.seed[m], self.num_timesteps, self.iteration, [recs[m] for recs in self.log],
+                                 None, self.venv._policy_steps) for m in range(self.n_members)]
 
     def close(self):
         self.population.close()

@@ -18,7 +18,7 @@ import zipfile
 
 import numpy as np
 
-from .policy import MlpPolicy, param_layout
+from .policy import MlpPolicy, device_tensor, param_layout
 
 HYPER = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
          "learning_rate", "normalize_advantage")
@@ -75,8 +75,7 @@ class PPOOptimizer:
             pass
 
     def _f32(self, x, shape, what):
-        t = self.torch
-        if not (isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float32 and x.is_contiguous() and x.numel() == int(np.prod(shape))):
+        if not (device_tensor(x, self.torch.float32) and x.numel() == int(np.prod(shape))):
             raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of {int(np.prod(shape))} elements")
         return x
 
@@ -87,7 +86,7 @@ class PPOOptimizer:
         T, B = reward.shape
         dims = (T, B) + tuple(value.shape[2:] if value.ndim == 3 else ())          # [T, B, A]: wg_gae_shared
         self._f32(reward, (T, B), "reward"); self._f32(value, dims, "value"); self._f32(final_value, dims, "final_value")
-        if not (truncated.is_cuda and truncated.dtype == t.uint8 and truncated.is_contiguous() and tuple(truncated.shape) == (T, B)):
+        if not (device_tensor(truncated, t.uint8) and tuple(truncated.shape) == (T, B)):
             raise ValueError("truncated must be a contiguous uint8 CUDA tensor [T, B]")
         adv, ret = out if out is not None else (t.empty_like(value), t.empty_like(value))
         entry = ("wg_gae", "wg_gae_shared")[len(dims) - 2]
@@ -129,8 +128,7 @@ class PPOOptimizer:
         return CPpoHyper(float(clip_range), float(vf_coef), float(ent_coef), int(bool(normalize_advantage)))
 
     def _index(self, index, n_min):
-        t = self.torch
-        if not (isinstance(index, t.Tensor) and index.is_cuda and index.dtype == t.int32 and index.is_contiguous() and index.numel() >= n_min):
+        if not (device_tensor(index, self.torch.int32) and index.numel() >= n_min):
             raise ValueError("the index / permutation must be a contiguous int32 CUDA tensor")
         return index
 
@@ -200,6 +198,83 @@ def _schedule(x, name):
     return lambda progress_remaining: v
 
 
+def check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm, who=""):
+    """``ValueError`` for what no trainer accepts; ``who`` (``"member 3: "``) prefixes the messages about the values a population
+    holds per member."""
+    if int(n_steps) < 1 or int(n_epochs) < 1:
+        raise ValueError("n_steps and n_epochs must be >= 1")
+    if not 0.0 <= float(gamma) <= 1.0 or not 0.0 <= float(gae_lambda) <= 1.0:
+        raise ValueError(f"{who}gamma and gae_lambda must lie in [0, 1]")
+    if not float(max_grad_norm) > 0.0:
+        raise ValueError(f"{who}max_grad_norm must be > 0")
+
+
+def check_batch_size(batch_size, n_rows, rows_are):
+    """-> the minibatch size in rows: a quarter of the rollout's ``n_rows`` by default (``rows_are`` spells ``n_rows`` in the message)."""
+    batch_size = max(1, n_rows // 4) if batch_size is None else int(batch_size)
+    if not 1 <= batch_size <= n_rows:
+        raise ValueError(f"batch_size must lie in [1, {rows_are} = {n_rows}]")
+    return batch_size
+
+
+def learn_loop(trainer, total_timesteps, callback, log_interval, reset_num_timesteps, schedules, record):
+    """``learn`` of :class:`PPO` and ``PPOPopulation``: iterations of ``trainer.collect()`` + ``trainer.train()`` until
+    ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``: that many more).  ``schedules(progress_remaining)
+    -> (learning_rate, clip_range)`` as ``train`` takes them; ``record(out, stats, learning_rate, clip_range, fps) -> log entry``
+    runs every ``log_interval``-th iteration, ``fps()`` being the env steps per second so far WHEN it is called (after the
+    record's device-to-host copy, so that it counts finished work)."""
+    if reset_num_timesteps:
+        trainer.num_timesteps = 0
+    start, total = trainer.num_timesteps, int(total_timesteps) + (0 if reset_num_timesteps else trainer.num_timesteps)
+    t0 = time.perf_counter()
+    while trainer.num_timesteps < total:
+        lr, clip = schedules(1.0 - (trainer.num_timesteps - 0.0) / max(total, 1))
+        out = trainer.collect()
+        stats = trainer.train(out, lr, clip)
+        trainer.num_timesteps += trainer.n_env_steps
+        trainer.iteration += 1
+        if log_interval and trainer.iteration % int(log_interval) == 0:
+            trainer.log.append(record(out, stats, lr, clip,
+                                      lambda: (trainer.num_timesteps - start) / max(time.perf_counter() - t0, 1e-9)))
+        if callback is not None and callback(trainer) is False:
+            break
+    return trainer
+
+
+def hyper_json(hyper):
+    """The ``PPO`` arguments of ``HYPER`` as a checkpoint stores them."""
+    d = {k: hyper[k] for k in HYPER}
+    for k in ("learning_rate", "clip_range"):
+        if callable(d[k]):
+            d[k] = None                     # a schedule is code: pass it to load() again
+    return d
+
+
+def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps):
+    """The zip of :meth:`PPO.save` (format: the class docstring) from what it holds: the policy, its :class:`PPOOptimizer`, the
+    permutation generator, the ``HYPER`` dict, the trainer's seed, its counters and log, the critic mode and the env's count of
+    policy steps."""
+    import torch
+    mv, step = opt.state()
+    sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
+    pth = io.BytesIO()
+    torch.save(sd, pth)
+
+    def npy(a):
+        b = io.BytesIO()
+        np.save(b, a)
+        return b.getvalue()
+    meta = dict(format="windgym_amd.PPO/1", desc=dict(policy.desc), hyper=hyper_json(hyper), seed=seed,
+                policy_seed=policy.seed, policy_counter=policy.counter, num_timesteps=num_timesteps,
+                iteration=iteration, adam_step=step, env_policy_steps=env_policy_steps, log=log, critic=critic)
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        z.writestr("policy.pth", pth.getvalue())
+        z.writestr("adam_state.npy", npy(mv))
+        z.writestr("generator_state.npy", npy(gen.get_state().cpu().numpy()))
+        z.writestr("windgym_ppo.json", json.dumps(meta))
+    return path
+
+
 class PPO:
     """Proximal policy optimisation with stable-baselines3's argument names and defaults, on a ``WindFarmVecEnv``, or on a
     ``WindFarmVecEnvMulti`` with ONE policy shared by the turbines (``obs_len -> 1``): there a row is an AGENT row — ``n_rows``
@@ -233,19 +308,12 @@ class PPO:
                 raise NotImplementedError(f"{name} is not implemented")
         if use_sde:
             raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
+        check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm)
         n_steps, n_epochs = int(n_steps), int(n_epochs)
-        if n_steps < 1 or n_epochs < 1:
-            raise ValueError("n_steps and n_epochs must be >= 1")
-        if not 0.0 <= float(gamma) <= 1.0 or not 0.0 <= float(gae_lambda) <= 1.0:
-            raise ValueError("gamma and gae_lambda must lie in [0, 1]")
-        if not float(max_grad_norm) > 0.0:
-            raise ValueError("max_grad_norm must be > 0")
         multi = getattr(venv, "possible_agents", None) is not None       # WindFarmVecEnvMulti: one row per (env, turbine)
         n_agents = int(venv.n_turb) if multi else 1
         n_rows = n_steps * int(venv.num_envs) * n_agents
-        batch_size = max(1, n_rows // 4) if batch_size is None else int(batch_size)
-        if not 1 <= batch_size <= n_rows:
-            raise ValueError(f"batch_size must lie in [1, n_steps * num_envs{' * n_turb' if multi else ''} = {n_rows}]")
+        batch_size = check_batch_size(batch_size, n_rows, f"n_steps * num_envs{' * n_turb' if multi else ''}")
         self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
         if isinstance(policy, str) and policy != "MlpPolicy":
             raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy'")
@@ -328,70 +396,33 @@ class PPO:
         """Iterations of rollout + update until ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``:
         that many more).  ``callback(ppo) -> bool`` runs once per iteration; False stops.  Every ``log_interval``-th iteration
         appends a record to ``self.log`` (one device-to-host copy; ``log_interval=None``: never, and no synchronisation)."""
+        return learn_loop(self, total_timesteps, callback, log_interval, reset_num_timesteps,
+                          lambda progress: (float(self._lr(progress)), float(self._clip(progress))), self._record)
+
+    def _record(self, out, stats, lr, clip, fps):
         from .binding import PPO_STATS
         from .parallel import METRIC_NAMES, derive
         t = self.torch
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-        start, total = self.num_timesteps, int(total_timesteps) + (0 if reset_num_timesteps else self.num_timesteps)
-        t0 = time.perf_counter()
-        while self.num_timesteps < total:
-            progress = 1.0 - (self.num_timesteps - 0.0) / max(total, 1)
-            lr, clip = float(self._lr(progress)), float(self._clip(progress))
-            out = self.collect()
-            stats = self.train(out, lr, clip)
-            self.num_timesteps += self.n_env_steps
-            self.iteration += 1
-            if log_interval and self.iteration % int(log_interval) == 0:
-                ret, val = self._ret.double(), out["value"].double()
-                ev = 1.0 - (ret - val).var() / ret.var()
-                vec = t.cat([stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)])
-                host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
-                rec = dict(zip(PPO_STATS, host[:8].tolist()))
-                rec["explained_variance"] = float(host[8])
-                m = derive(host[9:9 + len(METRIC_NAMES)])
-                rec.update(iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr, clip_range=clip,
-                           n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
-                           mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"],
-                           fps=(self.num_timesteps - start) / max(time.perf_counter() - t0, 1e-9))
-                self.log.append(rec)
-            if callback is not None and callback(self) is False:
-                break
-        return self
+        ret, val = self._ret.double(), out["value"].double()
+        ev = 1.0 - (ret - val).var() / ret.var()
+        vec = t.cat([stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)])
+        host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
+        rec = dict(zip(PPO_STATS, host[:8].tolist()))
+        rec["explained_variance"] = float(host[8])
+        m = derive(host[9:9 + len(METRIC_NAMES)])
+        rec.update(iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr, clip_range=clip,
+                   n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
+                   mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"], fps=fps())
+        return rec
 
     def predict(self, obs, state=None, episode_start=None, deterministic=False):
         return self.policy.predict(obs, state, episode_start, deterministic)
 
     # -- checkpoints ----------------------------------------------------------------------------------------------
-    def _hyper_json(self):
-        d = {k: getattr(self, k) for k in HYPER}
-        for k in ("learning_rate", "clip_range"):
-            if callable(d[k]):
-                d[k] = None                     # a schedule is code: pass it to load() again
-        return d
-
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself (see the class docstring for the format)."""
-        import torch
-        mv, step = self.opt.state()
-        sd = {k: v.detach().cpu().clone() for k, v in self.policy.state_dict().items()}
-        pth = io.BytesIO()
-        torch.save(sd, pth)
-
-        def npy(a):
-            b = io.BytesIO()
-            np.save(b, a)
-            return b.getvalue()
-        meta = dict(format="windgym_amd.PPO/1", desc=dict(self.policy.desc), hyper=self._hyper_json(), seed=self.seed,
-                    policy_seed=self.policy.seed, policy_counter=self.policy.counter, num_timesteps=self.num_timesteps,
-                    iteration=self.iteration, adam_step=step, env_policy_steps=self.venv._policy_steps, log=self.log,
-                    critic=self.critic)
-        with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
-            z.writestr("policy.pth", pth.getvalue())
-            z.writestr("adam_state.npy", npy(mv))
-            z.writestr("generator_state.npy", npy(self._gen.get_state().cpu().numpy()))
-            z.writestr("windgym_ppo.json", json.dumps(meta))
-        return path
+        return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
+                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps)
 
     @classmethod
     def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
