@@ -30,6 +30,14 @@ def test_header_symbols_are_exported(lib_path):
     assert L.wg_abi_version() == 4
 
 
+def test_every_bound_symbol_is_defined_by_a_listed_source():
+    """Builds nothing: every name the binding needs is defined at file scope in a translation unit of build.SOURCES (a
+    source missing from that list links a library that load_library() cannot load)."""
+    text = "".join(open(os.path.join(build.CSRC, s)).read() for s in build.SOURCES)
+    bound = set(re.findall(r"\bL\.(wg_\w+)\.argtypes", open(binding.__file__).read())) | set(binding.ABI_SYMBOLS)
+    assert not [n for n in sorted(bound) if not re.search(r"^[A-Za-z][\w\"* ]*\b%s\(" % n, text, re.M)]
+
+
 def test_config_struct_layout_matches_c(tmp_path):
     """sizeof/offsetof of wg_config as gcc sees it == the ctypes mirror."""
     src = tmp_path / "l.c"

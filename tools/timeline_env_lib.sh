@@ -1,4 +1,4 @@
-# usage (GPU box): WL=cfg2 bash tools/timeline_env_lib.sh <variant built with tools/envvariant.sh <name> -DWG_TIMELINE> [extra bench args]
+# usage (GPU box): WL=cfg2 bash tools/timeline_env_lib.sh <variant built with tools/build_variant.sh <name> -DWG_TIMELINE> [extra bench args]
 # -> per-phase cycles of k_flow_env's waves (wave 0 of every env: the main wave of context 0), from a prebuilt variant library
 cd $GRAFT_REPO_ROOT
 export WG_DEBUG_HOOKS=1 WG_FLOW_ENV=1

@@ -1,5 +1,5 @@
 # usage (GPU box): WL=cfg3 bash tools/timeline_wall_lib.sh <variant built with -DWG_TIMELINE -DWG_TIMELINE_WALL> ...  -> wall-clock life of
-# every k_flow workgroup of the last launch (prebuilt variant libraries: tools/fastbuild.sh windgym_amd/variants/lib_<name>.so -D...)
+# every k_flow workgroup of the last launch (prebuilt variant libraries: tools/build_variant.sh <name> -D...)
 cd $GRAFT_REPO_ROOT
 for n in "$@"; do
 WG_DEBUG_HOOKS=1 WG_LIB=$PWD/windgym_amd/variants/lib_$n.so WG_TIMELINE_OUT=gpurun_out/timeline_wall_$n.bin python bench.py --workload ${WL:-cfg3} --reps 1 --no-cpu 2>/dev/null | python tools/benchline.py $n | cut -c1-70

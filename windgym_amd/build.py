@@ -4,7 +4,6 @@ from __future__ import annotations
 import glob
 import os
 import subprocess
-import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -26,11 +25,14 @@ def needs_build() -> bool:
     return any(os.path.getmtime(f) > t for f in [os.path.join(CSRC, f) for f in SOURCES] + _headers())
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
+def build(force: bool = False, verbose: bool = False, out: str | None = None) -> str:
     """Compile the translation units in parallel (wg_flow.hip and wg_kernels.hip take about a minute each: they
-    hold all the kernel instantiations) and link them; objects go to a temporary directory, only the .so stays in-tree."""
-    if not force and not needs_build():
-        return LIB
+    hold all the kernel instantiations) and link them; objects go to a temporary directory, only the .so stays in-tree.
+    `out`: link a variant library there instead (always built: WG_HIPCC_FLAGS carries its extra flags, WG_LIB selects it)."""
+    if out is None:
+        if not force and not needs_build():
+            return LIB
+        out = LIB
     import tempfile
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra = os.environ.get("WG_HIPCC_FLAGS", "").split()
@@ -53,10 +55,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
                         other.kill()
                 raise subprocess.CalledProcessError(pr.returncode, cmd)
         # (hipFFT: the one library call on the box-generation path, wg_mann.hip)
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lhipfft"], check=True)
-    return LIB
+        subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + ["-lhipfft"], check=True)
+    return out
 
 
 if __name__ == "__main__":
-    build(force=True, verbose="-v" in sys.argv)
-    print(LIB)
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("-v", action="store_true", help="print the compile commands and every kernel's resource usage")
+    ap.add_argument("--out", metavar="PATH", help="write a variant library to PATH instead of the in-tree one")
+    args = ap.parse_args()
+    print(build(force=True, verbose=args.v, out=args.out))

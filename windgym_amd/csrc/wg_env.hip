@@ -30,14 +30,6 @@
 #include "wg_env_common.h"
 #include "wg_internal.h"
 
-#ifndef WG_ENV_S_UNROLL
-#define WG_ENV_S_UNROLL 0   // 1: the rotor-point loop of the pair evaluation unrolled by 4
-#endif
-#ifndef WG_ENV_PP
-#define WG_ENV_PP 0         // bit 0: two alternating request buffers in the advection pass, bit 1: in the evaluation (0: one buffer + a
-                            // register copy per trip).  Measured, cfg2 x 4096 / cfg4 x 2048, same box: 0: 67.8 / 53.5, 1: 66.0, 2: 68.0, 3: 63.0 / 50.9 M
-                            // env-steps/s — the second copy of the inlined phase costs more than the moves it saves
-#endif
 // Per-slot record in LDS.  Everything here is uniform over the N lanes of a slot: kept in LDS (written by the slot's lane
 // t = 0, read by broadcast) instead of one VGPR per word in every lane — the kernel lives at 128 VGPRs (4 waves per SIMD:
 // 4096 envs = one dispatch round) and would need ~180 with the slot state in registers.
@@ -268,7 +260,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             const int bg_pending = WPE == 2 ? (is_live_c ? 0 : __shfl(init_pending, 0, 64)) : __shfl(init_pending, (env_live ^ 1) * F * N, 64);
             out.bg_init_pending = autoreset && bg_pending;
             if (SPLIT == 2 && role == 1 && out.bg_init_pending) return;      // (an episode set-up in this launch: the context runs unsplit)
-            if (autoreset && bg_pending && WPE == 1 && (WG_ENV_DEFER_INIT != 0) && !out.truncates) {
+            if (autoreset && bg_pending && WPE == 1 && !out.truncates) {
                 // rare path (one context per truncation): the retired context's next episode is set up AFTER this wave's step
                 // (below) — its background lanes rest in this launch, the set-up needs no reload of the wave's state, and the
                 // wave is no longer the launch's straggler (at the head of the launch it lived 55 us against 40 for the rest).
@@ -288,10 +280,12 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 const int tm = WPE == 2 ? ki->d.ctx[e * 2 + env_live].time_max : __shfl(time_max_c, env_live * F * N, 64);
                 const long total = (long)((tm + inc - 1) / inc) + 1;
                 const int dev0 = __shfl(dev_rem, WPE == 2 ? 0 : (env_live ^ 1) * F * N, 64);
+                // (the per-context share, overwritten by the per-farm one below: dead, yet without it the compiler schedules every
+                // instantiation differently — other SGPR spill counts, the pass-wave kernels 41 instructions shorter.  It stays
+                // until the kernel has been measured without it.)
                 budget = wg_shadow_share(dev0 + gp.K * fill_max, total - env_steps_done, env_steps_done, e);
-                if (WG_ENV_SPLIT_PLAN != 0)
-                    budget = wg_shadow_share(dev_rem + gp.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u);
-            } else if (WG_ENV_SPLIT_PLAN != 0) {
+                budget = wg_shadow_share(dev_rem + gp.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u);
+            } else {
                 // The background episode's share of this step, planned per FARM: the flow steps its farm still needs over the env
                 // steps left (wg_shadow_share: dithered, so the expected share is exact), the baseline farm's dither half a period
                 // after the agent farm's — below one flow step per two env steps the two never step in the same launch, and a wave
@@ -300,8 +294,6 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 const int inc = k0->p.env_inc;
                 const long total = (long)((env_time_max_live + inc - 1) / inc) + 1;
                 budget = role_dev ? wg_shadow_share(dev_rem + k0->p.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u) : 0;
-            } else {
-                budget = env_shadow_iters;
             }
         } else {
             role_dev = is_live_c && !masked_out;
@@ -321,7 +313,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             if (!__ballot(any_work)) {
                 // (two waves per env: the resting background wave of an episode completed in an EARLIER launch prepares its
                 // first observation now — see the end of this function)
-                if (WPE == 2 && (WG_ENV_FIRST_OBS_LATER != 0) && mode == WG_MODE_STEP && !is_live_c && autoreset && role == 0) {
+                if (WPE == 2 && mode == WG_MODE_STEP && !is_live_c && autoreset && role == 0) {
                     const int d0 = __shfl(dev_rem, 0, 64), f0 = __shfl(fill_rem, 0, 64), np0 = __shfl(n_pushed, 0, 64);
                     const KArgsPtr kf = wg_cold_args();
                     if (d0 == 0 && f0 == 0 && kf->d.gd->next_obs_ok != nullptr && kf->d.gd->next_obs_ok[ctx_id] == 0) {
@@ -332,23 +324,6 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 return;
             }
         }
-#if WG_ENV_PRIO
-        static_assert(WPE == 1, "WG_ENV_PRIO: one wave per env only");
-        // The launch lasts as long as its slowest wave, and with ONE wave per env and one dispatch round the slowest waves are
-        // the handful per launch on a rare path — episode set-up at the head of the launch, a background context that takes
-        // two or more flow steps, the first observation of a completed episode, the swap at truncation (cfg2 x 4096: their
-        // waves lived 51-58 us against 40 for the rest and WERE the kernel's last 7 us; cfg4: 28-33 against 21).  They are
-        // known here, before the work starts: such a wave raises its issue priority over the three it shares its SIMD with.
-        if (mode == WG_MODE_STEP) {
-            const int bl = (env_live ^ 1) * F * N;              // the background context's agent-farm lane 0
-            const int b_dev = __shfl(dev_rem, bl, 64), b_fill = __shfl(fill_rem, bl, 64);
-            const bool bg_active = role_dev_any(autoreset, b_dev, b_fill);
-            const bool multi_round = bg_active && budget >= 2 && b_dev + b_fill >= 2;
-            const bool completes = bg_active && b_dev + k0->p.K * b_fill <= budget;
-            const bool truncates = out.truncates != 0;
-            if (out.bg_init_pending || multi_round || completes || truncates) __builtin_amdgcn_s_setprio(3);
-        }
-#endif
 
         // ---- state into LDS ---------------------------------------------------------------------------------------------
         const KArgsPtr k1 = wg_cold_args();
@@ -491,7 +466,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         int cbeg, nc;
         {
             const int cnt = __popc(cmask);
-            const int inc = env_scan(cnt, tid);
+            const int inc = wg_wave_scan_i(cnt);
             cbeg = inc - cnt;
             nc = __builtin_amdgcn_readlane(inc, 63);
             unsigned m = cmask;
@@ -663,22 +638,14 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             for (int c0 = 0; c0 < nc; c0 += WG_ENV_CAP) {
                 const int c1 = min(nc, c0 + WG_ENV_CAP);
                 if (c0 > 0) { lds_barrier<64>(); issue(ca, c0 + tid, c0, c1); }
-                // (two candidate buffers, alternating: the next batch's gathers are in flight while this one is evaluated)
-#if WG_ENV_PP & 2
-                for (int cb = c0; cb < c1; cb += 128) {
-                    issue(cb_, cb + 64 + tid, c0, c1);
-                    eval_cand(ca, cb - c0 + tid);
-                    if (cb + 64 >= c1) break;
-                    issue(ca, cb + 128 + tid, c0, c1);
-                    eval_cand(cb_, cb + 64 - c0 + tid);
-                }
-#else
+                // (the next batch's gathers are in flight while this one is evaluated.  One request buffer + a register copy per
+                // trip, here and in the advection pass: two alternating buffers are a second copy of the inlined phase, which costs
+                // more than the moves it saves — cfg2 x 4096 / cfg4 x 2048 same box, 67.8 / 53.5 against 63.0 / 50.9 M env-steps/s)
                 for (int cb = c0; cb < c1; cb += 64) {
                     cb_ = ca;
                     issue(ca, cb + 64 + tid, c0, c1);
                     eval_cand(cb_, cb - c0 + tid);
                 }
-#endif
                 lds_barrier<64>();
                 // this target's slice of the round, in list order = ascending source order
                 if (stepping) {
@@ -748,7 +715,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                         }
                     }
                 }
-                const int inc = env_scan(cnt, tid);
+                const int inc = wg_wave_scan_i(cnt);
                 nlist = (WG_ENV_ABLATE & 2) ? 0 : __builtin_amdgcn_readlane(inc, 63);
                 if (full) {
                     const int base = inc - cnt;
@@ -832,21 +799,11 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             if (SPLIT && role == 1) {      // (its first trip is in flight; no store before the main wave's gathers have landed)
                 if (!env_flag_wait(reinterpret_cast<int*>(smem + WG_ENV_OFF_HDR))) atomicOr(kp->d.status, WG_STATUS_BIT_STATE);
             }
-#if WG_ENV_PP & 1
-            for (int base = 0; base < nlist; base += 128) {
-                request(qb, base + 64 + tid);
-                advect_quad(qa, base + tid);
-                if (base + 64 >= nlist) break;
-                request(qa, base + 128 + tid);
-                advect_quad(qb, base + 64 + tid);
-            }
-#else
             for (int base = 0; base < nlist; base += 64) {
                 qb = qa;
                 request(qa, base + 64 + tid);
                 advect_quad(qb, base + tid);
             }
-#endif
         }
         lds_barrier<64>();
         WG_STAMP(3);
@@ -1012,7 +969,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
     }
     WG_STAMP(8);
     // A background episode whose development is complete: its window sums and first observation are prepared for the swap
-    // (wg_first_obs, see k_flow) — in the launch AFTER the one that completed it (WG_ENV_FIRST_OBS_LATER; development ends
+    // (wg_first_obs, see k_flow) — in the launch AFTER the one that completed it (development ends
     // WG_SHADOW_MARGIN steps early, so there is one): its slots rest then, and the wave that builds the observation is not also
     // the one that took the episode's last flow steps.  An episode that completes in the very launch of the truncating step is
     // prepared at once (one wave per env) or summed by the swap itself (lean_swap's fallback).
@@ -1020,10 +977,8 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         const EnvSlotLds& bs = SL[WPE == 2 ? 0 : (env_live ^ 1) * F];      // the background context's agent farm
         const int bctx = e * 2 + (env_live ^ 1);
         bool build = false;
-        if (ke->p.autoreset && bs.dev_rem == 0 && bs.fill_rem == 0) {
-            if (WG_ENV_FIRST_OBS_LATER != 0) build = bs.n_flow == 0 ? (ke->d.gd->next_obs_ok != nullptr && ke->d.gd->next_obs_ok[bctx] == 0) : out.truncates != 0;
-            else build = bs.n_flow > 0;
-        }
+        if (ke->p.autoreset && bs.dev_rem == 0 && bs.fill_rem == 0)
+            build = bs.n_flow == 0 ? (ke->d.gd->next_obs_ok != nullptr && ke->d.gd->next_obs_ok[bctx] == 0) : out.truncates != 0;
         if (build) {
             const int np = bs.n_pushed;
             out.first_obs = 1;
@@ -1098,11 +1053,7 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
                     const EnvSlotLds* const SLb = reinterpret_cast<const EnvSlotLds*>(sm + WG_ENV_OFF_SL);
                     int work = 0;
                     for (int f = 0; f < F; ++f) work = max(work, SLb[f].dev_rem + K * SLb[f].fill_rem);
-                    const int steps_done = fo.steps_done + 1, time_max = fo.time_max_live;      // (as the glue sees them: from the prologue's
-                                                                                              // copy — the live wave may have rewritten the header by now)
-                    const int inc = 1 + (kb->gp.extra_inc ? 1 : 0);
-                    const long total = (long)((time_max + inc - 1) / inc) + 1;
-                    kb->d.env_rw[e].shadow_iters = work == 0 ? 0 : wg_shadow_share(work, total - steps_done, steps_done, e);
+                    env_bg_plan(kb, work, fo, e);
                 }
                 if (fo.bg_init_pending && (threadIdx.x & 63) == 0) kb->d.ctx[e * 2 + wv].init_pending = 0;
                 if (fo.truncates) __builtin_amdgcn_s_waitcnt(0x0070);       // (its last stores, before the barrier releases the glue)
@@ -1110,21 +1061,15 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
             if (fo.truncates) __syncthreads();
         }
         if (WPE == 1 || wv == fo.env_live) {
-            // (the glue's parameter blocks are read where they are used, through the opaque kernarg pointer: by value they were
-            // all fetched at the kernel's entry and 130 of them parked in VGPR lanes across the flow step)
             const EnvKArgsPtr kg = (EnvKArgsPtr)wg_cold_args();
             const int F = kg->p.F, K = kg->p.K;
             const EnvSlotLds* const SLa = reinterpret_cast<const EnvSlotLds*>(sm + WG_ENV_OFF_SL);      // the live context's slots
             const int la = WPE == 2 ? 0 : fo.env_live * F, lb = (fo.env_live ^ 1) * F;
-            LeanFused fz;
-            fz.fp = SLa[la].out_pw;
-            fz.bp = F == 2 ? SLa[la + 1].out_pw : 0.f;
+            const float fp = SLa[la].out_pw, bp = F == 2 ? SLa[la + 1].out_pw : 0.f;
             int work = 0;
             if (WPE == 1) for (int f = 0; f < F; ++f) work = max(work, SLa[lb + f].dev_rem + K * SLa[lb + f].fill_rem);
-            fz.work = work;
-            fz.bg_init_pending = WPE == 2 ? 0 : fo.bg_init_pending;
-            fz.plan_elsewhere = WPE == 2;
-            fz.hw = reinterpret_cast<const int*>(sm + WG_ENV_OFF_HDR)[threadIdx.x & 31];
+            const int hw = reinterpret_cast<const int*>(sm + WG_ENV_OFF_HDR)[threadIdx.x & 31];
+            LeanFused fz;
             fz.pre = nullptr;
             if (SPLIT) {
                 // the glue's inputs: the step's own from this wave's registers, the rest from the pass wave's fetch (long done)
@@ -1136,8 +1081,7 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
                 fz.yaw = fo.g_yaw; fz.old_yaw = fo.g_old; fz.pw = fo.g_pw; fz.pwb = fo.g_pwb;
             }
             WG_STAMP(12);
-            lean_step<GLUE == 2, false, true>(*(const WgParams*)&kg->gp, *(const WgPtrs*)&kg->gd, kg->d.gp, kg->d.gd, (int)blockIdx.x,
-                                              (int)(threadIdx.x & 63), kg->obs, kg->reward, kg->trunc, kg->final_obs, nullptr, fz);
+            env_glue<GLUE, WPE>(kg, fz, fp, bp, work, fo, hw);
             WG_STAMP(13);
         }
     }
@@ -1157,33 +1101,38 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
 #endif
 }
 
+// launch table: (noise, glue, waves per env, pass waves) -> instantiation; 64 threads and FlowP::env_lds bytes of LDS per wave (+ the
+// pre-fetched glue inputs behind the regions of an instantiation with pass waves).  Pass waves exist with a glue tail only.
+template <bool NZ, int G>
+static EnvKernel env_kernel(const int wpe, const int split) {
+    if constexpr (G != 0) {
+        if (split == 2) return k_flow_env<NZ, G, 2, 2>;
+        if (split == 1) return k_flow_env<NZ, G, 2, 1>;
+    }
+    return wpe == 2 ? k_flow_env<NZ, G, 2> : k_flow_env<NZ, G, 1>;
+}
+static void env_launch(const FlowP* p, const FlowPtrs* d, const int glue, const int mode, const float* actions, const uint8_t* mask,
+                       const int chunk, const WgParams* gp, const WgPtrs* gd, float* obs, float* reward, uint8_t* trunc,
+                       float* final_obs, hipStream_t st) {
+    const int wpe = p->env_wpe == 2 ? 2 : 1;
+    const int split = glue != 0 && wpe == 2 && (p->env_split == 1 || p->env_split == 2) ? p->env_split : 0;
+    const size_t lds = (size_t)p->env_lds * (wpe + split) + (split ? LEAN_PRE_BYTES : 0);
+    const EnvKernel k = glue == 2 ? (p->noise ? env_kernel<true, 2>(wpe, split) : env_kernel<false, 2>(wpe, split))
+                      : glue == 1 ? (p->noise ? env_kernel<true, 1>(wpe, split) : env_kernel<false, 1>(wpe, split))
+                                  : (p->noise ? env_kernel<true, 0>(wpe, split) : env_kernel<false, 0>(wpe, split));
+    hipLaunchKernelGGL(k, dim3(p->B), dim3(64 * (wpe + split)), lds, st, *p, *d, mode, actions, mask, chunk, *gp, *gd, obs, reward, trunc, final_obs);
+}
+
+// the flow step alone: the table's glue == 0 row, no glue arguments
 extern "C" void wg_launch_flow_env(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask,
                                    int chunk, hipStream_t st) {
-    const int grid = p->B, wpe = p->env_wpe == 2 ? 2 : 1;
-    const size_t lds = (size_t)p->env_lds * wpe;
     static const WgParams gp0{};
     static const WgPtrs gd0{};
-#define WG_FLOW_ENV(NZ, W) hipLaunchKernelGGL((k_flow_env<NZ, 0, W>), dim3(grid), dim3(64 * W), lds, st, *p, *d, mode, actions, mask, chunk, gp0, gd0, \
-                                              (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, (float*)nullptr)
-    if (wpe == 2) { if (p->noise) WG_FLOW_ENV(true, 2); else WG_FLOW_ENV(false, 2); }
-    else { if (p->noise) WG_FLOW_ENV(true, 1); else WG_FLOW_ENV(false, 1); }
-#undef WG_FLOW_ENV
+    env_launch(p, d, 0, mode, actions, mask, chunk, &gp0, &gd0, nullptr, nullptr, nullptr, nullptr, st);
 }
 
 // step() as one launch (wg_api.hip: launch_step, handles with FlowP::env_fused)
 extern "C" void wg_launch_step_env(const FlowP* p, const FlowPtrs* d, const WgParams* gp, const WgPtrs* gd, const float* actions,
                                    float* obs, float* reward, uint8_t* trunc, float* final_obs, hipStream_t st) {
-    const int grid = p->B, wpe = p->env_wpe == 2 ? 2 : 1;
-    const size_t lds = (size_t)p->env_lds * wpe;
-#define WG_STEP_ENV(NZ, G, W) hipLaunchKernelGGL((k_flow_env<NZ, G, W>), dim3(grid), dim3(64 * W), lds, st, *p, *d, (int)WG_MODE_STEP, actions, \
-                                                 (const uint8_t*)nullptr, 0, *gp, *gd, obs, reward, trunc, final_obs)
-#define WG_STEP_ENV_S(NZ, G, SP) hipLaunchKernelGGL((k_flow_env<NZ, G, 2, SP>), dim3(grid), dim3(64 * (2 + SP)), (size_t)p->env_lds * (2 + SP) + LEAN_PRE_BYTES, st, \
-                                                    *p, *d, (int)WG_MODE_STEP, actions, (const uint8_t*)nullptr, 0, *gp, *gd, obs, reward, trunc, final_obs)
-#define WG_STEP_ENV_W(NZ, G) do { if (wpe == 2 && p->env_split == 2) WG_STEP_ENV_S(NZ, G, 2); else if (wpe == 2 && p->env_split == 1) WG_STEP_ENV_S(NZ, G, 1); \
-                                  else if (wpe == 2) WG_STEP_ENV(NZ, G, 2); else WG_STEP_ENV(NZ, G, 1); } while (0)
-    if (gd->multi_out) { if (p->noise) WG_STEP_ENV_W(true, 2); else WG_STEP_ENV_W(false, 2); }
-    else { if (p->noise) WG_STEP_ENV_W(true, 1); else WG_STEP_ENV_W(false, 1); }
-#undef WG_STEP_ENV_W
-#undef WG_STEP_ENV_S
-#undef WG_STEP_ENV
+    env_launch(p, d, gd->multi_out ? 2 : 1, WG_MODE_STEP, actions, nullptr, 0, gp, gd, obs, reward, trunc, final_obs, st);
 }

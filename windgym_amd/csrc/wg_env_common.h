@@ -1,28 +1,12 @@
 // wg_env_common.h — what the one-wave-per-env step kernels share (wg_env.hip: k_flow_env, steady inflow; wg_envb.hip: k_flow_envb,
 // frozen-box inflow): the kernel-argument view, the rare paths (episode set-up, first observation of a completed background
-// episode) and small wave helpers.  Everything is inline per translation unit.
+// episode), small wave helpers and the glue tail of the one-launch instantiations.  Everything is inline per translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "wg_flow_dev.h"
 #include "wg_glue_lean.h"
 
-#ifndef WG_ENV_DPP_SCAN
-#define WG_ENV_DPP_SCAN 1   // list offsets from DPP prefix sums (0: __shfl_up ladders, for A/B builds: 67.0 / 52.2 against 67.8 / 53.5)
-#endif
-#ifndef WG_ENV_DEFER_INIT
-#define WG_ENV_DEFER_INIT 1       // one wave per env: a retired context's next episode is set up after the wave's step, not before it
-#endif
-#ifndef WG_ENV_SPLIT_PLAN
-#define WG_ENV_SPLIT_PLAN 1       // the background episode's farms are planned one by one, half a period apart (see the prologue)
-#endif
-#ifndef WG_ENV_FIRST_OBS_LATER
-#define WG_ENV_FIRST_OBS_LATER 1  // a completed background episode's first observation is built in the launch after the completing one
-#endif
-#ifndef WG_ENV_PRIO
-#define WG_ENV_PRIO 0       // 1: waves on a rare, long path raise their issue priority — measured slightly SLOWER (cfg2 65.2 vs 66.5, cfg4
-                            // 54.3 vs 54.9 M env-steps/s): their extra time is their own latency chain, not contention
-#endif
 #ifndef WG_ENV_WAVES
 #define WG_ENV_WAVES 4      // 128 VGPRs: 4096 envs = the chip's 4096 wave slots at 4 waves per SIMD, one dispatch round
 #endif
@@ -43,17 +27,6 @@ static __device__ __attribute__((noinline)) void env_init_episode_mem(const WgPa
 struct EnvKArgs;
 template <bool KARG>
 __device__ __forceinline__ void env_init_episode(const int e, const int c, const int lane);
-
-__device__ __forceinline__ int env_scan(const int v, const int tid) {
-#if WG_ENV_DPP_SCAN
-    return wg_wave_scan_i(v);
-#else
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int w = __shfl_up(inc, o, 64); if (tid >= o) inc += w; }
-    return inc;
-#endif
-}
 
 // uniform-grid table lookup (linear interpolation, 0 outside): tab_lookup with its parameters as scalars
 __device__ __forceinline__ float env_tab(const float* __restrict__ ys, const float x0, const float inv_dx, const int n_tab, const float x) {
@@ -193,3 +166,36 @@ struct EnvFlowOut {          // what the flow part hands to the glue tail of k_s
     // agent-farm turbine pushed into its rings, its yaw before / after, its power and its baseline twin's
     float g_nw[WG_N_CH], g_yaw, g_old, g_pw, g_pwb;
 };
+
+// ---- the tail of the one-launch kernels (k_flow_env / k_flow_envb<., GLUE != 0>), after the flow part ---------------------------
+// None of the waits, barriers and LDS flags that order these blocks is in here: they stay in the __global__ bodies, in order.
+
+// Two or more waves per env, lane 0 of the background context's wave: the context plans its own next share (WgEnv::shadow_iters)
+// — what the glue does for one wave per env.  Only with autoreset, and not when the env truncates in this step (the swap plans
+// then).  `work`: the largest dev_rem + K fill_rem over the context's farms.
+__device__ __forceinline__ void env_bg_plan(const EnvKArgsPtr kb, const int work, const EnvFlowOut& fo, const int e) {
+    const int steps_done = fo.steps_done + 1, time_max = fo.time_max_live;      // (as the glue sees them: from the prologue's copy —
+                                                                              // the live wave may have rewritten the header by now)
+    const int inc = 1 + (kb->gp.extra_inc ? 1 : 0);
+    const long total = (long)((time_max + inc - 1) / inc) + 1;
+    kb->d.env_rw[e].shadow_iters = work == 0 ? 0 : wg_shadow_share(work, total - steps_done, steps_done, e);
+}
+
+// The glue (lean_step) as the tail of the live wave's flow step.  fp / bp: the step's farm powers (agent / baseline farm); work:
+// the background context's remaining work where this wave plans it (WPE 1), else 0; hw: the lane's word of the env header as the
+// prologue loaded it; fz: `pre` and what goes with it, set by the caller (k_flow_env's pass-wave zone, or nullptr).
+// (kg: the glue's parameter blocks are read where they are used, through the opaque kernarg pointer: by value they were all
+// fetched at the kernel's entry and 130 of them parked in VGPR lanes across the flow step.)
+template <int GLUE, int WPE>
+__device__ __forceinline__ void env_glue(const EnvKArgsPtr kg, LeanFused& fz, const float fp, const float bp, const int work,
+                                         const EnvFlowOut& fo, const int hw) {
+    fz.fp = fp; fz.bp = bp; fz.work = work;
+    fz.bg_init_pending = WPE >= 2 ? 0 : fo.bg_init_pending;
+    fz.plan_elsewhere = WPE >= 2;
+    fz.hw = hw;
+    lean_step<GLUE == 2, false, true>(*(const WgParams*)&kg->gp, *(const WgPtrs*)&kg->gd, kg->d.gp, kg->d.gd, (int)blockIdx.x,
+                                      (int)(threadIdx.x & 63), kg->obs, kg->reward, kg->trunc, kg->final_obs, nullptr, fz);
+}
+
+// host: a kernel of either family, as its launch table hands it out
+typedef void (*EnvKernel)(FlowP, FlowPtrs, int, const float*, const uint8_t*, int, WgParams, WgPtrs, float*, float*, uint8_t*, float*);

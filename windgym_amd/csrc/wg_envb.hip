@@ -321,7 +321,7 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
             role_dev = !is_live_c && autoreset != 0;
             const int bg_pending = WPE >= 2 ? (is_live_c ? 0 : __shfl(init_pending, 0, 64)) : __shfl(init_pending, bg_lane, 64);
             out.bg_init_pending = autoreset && bg_pending;
-            if (autoreset && bg_pending && WPE == 1 && (WG_ENV_DEFER_INIT != 0) && !out.truncates) {
+            if (autoreset && bg_pending && WPE == 1 && !out.truncates) {
                 defer_init = true;      // rare path: the retired context's next episode is set up AFTER this wave's step (env_flow)
                 budget = 0;
             } else if (autoreset && bg_pending) {
@@ -359,7 +359,7 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
         {   // nothing to do for the whole wave (masked out in RESET mode, finished env without autoreset, idle background)
             const bool any_work = valid && (role_live || (role_dev && budget > 0 && (dev_rem > 0 || fill_rem > 0)));
             if (!__ballot(any_work)) {
-                if (WPE >= 2 && (WPE == 2 || farm == 0) && (WG_ENV_FIRST_OBS_LATER != 0) && mode == WG_MODE_STEP && !is_live_c && autoreset) {
+                if (WPE >= 2 && (WPE == 2 || farm == 0) && mode == WG_MODE_STEP && !is_live_c && autoreset) {
                     const int d0 = __shfl(dev_rem, 0, 64), f0 = __shfl(fill_rem, 0, 64), np0 = __shfl(n_pushed, 0, 64);
                     const KArgsPtr kf = wg_cold_args();
                     if (d0 == 0 && f0 == 0 && kf->d.gd->next_obs_ok != nullptr && kf->d.gd->next_obs_ok[ctx_id] == 0) {
@@ -673,7 +673,7 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
         unsigned short* const cl = reinterpret_cast<unsigned short*>(smem + wg_cold_args()->p.envb_off_cl);
         {
             const int cnt = __popc(cmask);
-            inc = env_scan(cnt, tid);
+            inc = wg_wave_scan_i(cnt);
             cbeg = inc - cnt;
             nc = __builtin_amdgcn_readlane(inc, 63);
             unsigned m = cmask;
@@ -1024,10 +1024,8 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
         const EnvbSlotLds& bs = SL[WPE >= 2 ? 0 : (env_live ^ 1) * F];      // the background context's agent farm
         const int bctx = e * 2 + (env_live ^ 1);
         bool build = false;
-        if (ke->p.autoreset && bs.dev_rem == 0 && bs.fill_rem == 0) {
-            if (WG_ENV_FIRST_OBS_LATER != 0) build = bs.n_flow == 0 ? (ke->d.gd->next_obs_ok != nullptr && ke->d.gd->next_obs_ok[bctx] == 0) : out.truncates != 0;
-            else build = bs.n_flow > 0;
-        }
+        if (ke->p.autoreset && bs.dev_rem == 0 && bs.fill_rem == 0)
+            build = bs.n_flow == 0 ? (ke->d.gd->next_obs_ok != nullptr && ke->d.gd->next_obs_ok[bctx] == 0) : out.truncates != 0;
         if (build) {
             const int np = bs.n_pushed;
             out.first_obs = 1;
@@ -1093,10 +1091,7 @@ k_flow_envb(const FlowP p_, const FlowPtrs d_, const int mode, const float* __re
                         const EnvbSlotLds* const SLb = reinterpret_cast<const EnvbSlotLds*>(sm + LO::SL);
                         for (int f = 0; f < F; ++f) work = max(work, SLb[f].dev_rem + K * SLb[f].fill_rem);
                     }
-                    const int steps_done = fo.steps_done + 1, time_max = fo.time_max_live;      // (as the glue sees them)
-                    const int inc = 1 + (kb->gp.extra_inc ? 1 : 0);
-                    const long total = (long)((time_max + inc - 1) / inc) + 1;
-                    kb->d.env_rw[e].shadow_iters = work == 0 ? 0 : wg_shadow_share(work, total - steps_done, steps_done, e);
+                    env_bg_plan(kb, work, fo, e);
                 }
                 if (fo.bg_init_pending && lane0) kb->d.ctx[e * 2 + c_w].init_pending = 0;
             }
@@ -1105,56 +1100,54 @@ k_flow_envb(const FlowP p_, const FlowPtrs d_, const int mode, const float* __re
         }
         if (WPE == 1 || (c_w == fo.env_live && farm_w == 0)) {
             const EnvKArgsPtr kg = (EnvKArgsPtr)wg_cold_args();
-            LeanFused fz;
-            fz.pre = nullptr;
+            float fp, bp;
+            int work = 0;
             if (WPE == 4) {
                 // the running episode's agent-farm wave: its baseline farm's wave is the next one
                 if (F == 2 && !envb_flag_wait(flags + wv + 1)) { if (lane0) atomicOr(kg->d.status, WG_STATUS_BIT_STATE); }
-                fz.fp = reinterpret_cast<const EnvbSlotLds*>(sm + LO::SL)->out_pw;
-                fz.bp = F == 2 ? reinterpret_cast<const EnvbSlotLds*>(sm + lds_wave + LO::SL)->out_pw : 0.f;
-                fz.work = 0;
+                fp = reinterpret_cast<const EnvbSlotLds*>(sm + LO::SL)->out_pw;
+                bp = F == 2 ? reinterpret_cast<const EnvbSlotLds*>(sm + lds_wave + LO::SL)->out_pw : 0.f;
             } else {
                 const EnvbSlotLds* const SLa = reinterpret_cast<const EnvbSlotLds*>(sm + LO::SL);      // the live context's slots
                 const int la = WPE == 2 ? 0 : fo.env_live * F, lb = (fo.env_live ^ 1) * F;
-                fz.fp = SLa[la].out_pw;
-                fz.bp = F == 2 ? SLa[la + 1].out_pw : 0.f;
-                int work = 0;
+                fp = SLa[la].out_pw;
+                bp = F == 2 ? SLa[la + 1].out_pw : 0.f;
                 if (WPE == 1) for (int f = 0; f < F; ++f) work = max(work, SLa[lb + f].dev_rem + K * SLa[lb + f].fill_rem);
-                fz.work = work;
             }
-            fz.bg_init_pending = WPE >= 2 ? 0 : fo.bg_init_pending;
-            fz.plan_elsewhere = WPE >= 2;
-            fz.hw = reinterpret_cast<const int*>(sm + LO::HDR)[threadIdx.x & 31];
-            lean_step<GLUE == 2, false, true>(*(const WgParams*)&kg->gp, *(const WgPtrs*)&kg->gd, kg->d.gp, kg->d.gd, (int)blockIdx.x,
-                                              (int)(threadIdx.x & 63), kg->obs, kg->reward, kg->trunc, kg->final_obs, nullptr, fz);
+            LeanFused fz;
+            fz.pre = nullptr;
+            env_glue<GLUE, WPE>(kg, fz, fp, bp, work, fo, reinterpret_cast<const int*>(sm + LO::HDR)[threadIdx.x & 31]);
         }
     }
 }
 
+// launch table: (noise, glue, waves per env) -> instantiation; 64 threads and FlowP::env_lds bytes of LDS per wave (+ the flags of
+// four waves per env)
+template <bool NZ, int G>
+static EnvKernel envb_kernel(const int wpe) {
+    return wpe == 4 ? k_flow_envb<NZ, G, 4> : wpe == 2 ? k_flow_envb<NZ, G, 2> : k_flow_envb<NZ, G, 1>;
+}
+static void envb_launch(const FlowP* p, const FlowPtrs* d, const int glue, const int mode, const float* actions, const uint8_t* mask,
+                        const int chunk, const WgParams* gp, const WgPtrs* gd, float* obs, float* reward, uint8_t* trunc,
+                        float* final_obs, hipStream_t st) {
+    const int wpe = p->env_wpe == 4 ? 4 : (p->env_wpe == 2 ? 2 : 1);
+    const size_t lds = (size_t)p->env_lds * wpe + (wpe == 4 ? WG_ENVB_FLAG_BYTES : 0);
+    const EnvKernel k = glue == 2 ? (p->noise ? envb_kernel<true, 2>(wpe) : envb_kernel<false, 2>(wpe))
+                      : glue == 1 ? (p->noise ? envb_kernel<true, 1>(wpe) : envb_kernel<false, 1>(wpe))
+                                  : (p->noise ? envb_kernel<true, 0>(wpe) : envb_kernel<false, 0>(wpe));
+    hipLaunchKernelGGL(k, dim3(p->B), dim3(64 * wpe), lds, st, *p, *d, mode, actions, mask, chunk, *gp, *gd, obs, reward, trunc, final_obs);
+}
+
+// the flow step alone: the table's glue == 0 row, no glue arguments
 extern "C" void wg_launch_flow_envb(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask,
                                     int chunk, hipStream_t st) {
-    const int grid = p->B, wpe = p->env_wpe == 4 ? 4 : (p->env_wpe == 2 ? 2 : 1);
-    const size_t lds = (size_t)p->env_lds * wpe + (wpe == 4 ? WG_ENVB_FLAG_BYTES : 0);
     static const WgParams gp0{};
     static const WgPtrs gd0{};
-#define WG_FLOW_ENVB(NZ, W) hipLaunchKernelGGL((k_flow_envb<NZ, 0, W>), dim3(grid), dim3(64 * W), lds, st, *p, *d, mode, actions, mask, chunk, gp0, gd0, \
-                                               (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, (float*)nullptr)
-    if (wpe == 4) { if (p->noise) WG_FLOW_ENVB(true, 4); else WG_FLOW_ENVB(false, 4); }
-    else if (wpe == 2) { if (p->noise) WG_FLOW_ENVB(true, 2); else WG_FLOW_ENVB(false, 2); }
-    else { if (p->noise) WG_FLOW_ENVB(true, 1); else WG_FLOW_ENVB(false, 1); }
-#undef WG_FLOW_ENVB
+    envb_launch(p, d, 0, mode, actions, mask, chunk, &gp0, &gd0, nullptr, nullptr, nullptr, nullptr, st);
 }
 
 // step() as one launch (wg_api.hip: launch_step, handles with FlowP::env_fused and frozen-box inflow)
 extern "C" void wg_launch_step_envb(const FlowP* p, const FlowPtrs* d, const WgParams* gp, const WgPtrs* gd, const float* actions,
                                     float* obs, float* reward, uint8_t* trunc, float* final_obs, hipStream_t st) {
-    const int grid = p->B, wpe = p->env_wpe == 4 ? 4 : (p->env_wpe == 2 ? 2 : 1);
-    const size_t lds = (size_t)p->env_lds * wpe + (wpe == 4 ? WG_ENVB_FLAG_BYTES : 0);
-#define WG_STEP_ENVB(NZ, G, W) hipLaunchKernelGGL((k_flow_envb<NZ, G, W>), dim3(grid), dim3(64 * W), lds, st, *p, *d, (int)WG_MODE_STEP, actions, \
-                                                  (const uint8_t*)nullptr, 0, *gp, *gd, obs, reward, trunc, final_obs)
-#define WG_STEP_ENVB_W(NZ, G) do { if (wpe == 4) WG_STEP_ENVB(NZ, G, 4); else if (wpe == 2) WG_STEP_ENVB(NZ, G, 2); else WG_STEP_ENVB(NZ, G, 1); } while (0)
-    if (gd->multi_out) { if (p->noise) WG_STEP_ENVB_W(true, 2); else WG_STEP_ENVB_W(false, 2); }
-    else { if (p->noise) WG_STEP_ENVB_W(true, 1); else WG_STEP_ENVB_W(false, 1); }
-#undef WG_STEP_ENVB_W
-#undef WG_STEP_ENVB
+    envb_launch(p, d, gd->multi_out ? 2 : 1, WG_MODE_STEP, actions, nullptr, 0, gp, gd, obs, reward, trunc, final_obs, st);
 }

@@ -18,48 +18,19 @@
 #ifndef WG_FLOW_WAVES
 #define WG_FLOW_WAVES 5   // min waves/SIMD the register allocator must leave room for (5 -> <= 96 VGPRs; measured best)
 #endif
-
-#ifndef WG_GLDS
-#define WG_GLDS 1         // single-wave steady compact variant: deficit-phase gathers as early LDS-DMA requests (0 = register gathers, for A/B builds)
-#endif
-#ifndef WG_ADV_PIPE
-#define WG_ADV_PIPE 1      // GL variant: software-pipelined advection pass (first quad requested before the deficit evaluation, the next
-                           // quad before the current one is computed): cfg2 k_flow 61.5 -> 58.8 us same box (0 = plain loop, for A/B builds)
-#endif
-#ifndef WG_ADV_PIPE_LF
-#define WG_ADV_PIPE_LF 1   // 256-thread compact steady variant (large farms): quads requested ahead in its advection pass
-                           // (cfg3 same-box: 0 / 1 / 2 quads ahead = 3.80 / 4.04 / 3.93 M env-steps/s).  vmcnt counts
-                           // loads and stores in ONE in-order queue: a plain load-compute-store loop waits for the previous trip's
-                           // stores whenever it waits for its loads — two round trips per trip (cfg3: 20 trips of ~2 us).  Requested
-                           // before the stores, the next quads' loads no longer queue behind them.
-#endif
 #ifndef WG_FLOW_WAVES_LF
-#define WG_FLOW_WAVES_LF 3  // ... built at 3 waves per SIMD (168 VGPRs, nothing spilled): bandwidth-bound, so three resident workgroups per
-                            // CU do (cfg3 same-box, 4 / 3 waves: 3.88 / 4.00 M env-steps/s; its LDS carve allows 4: 34 KB each)
+#define WG_FLOW_WAVES_LF 3  // 256-thread compact steady variant (large farms): built at 3 waves per SIMD (168 VGPRs, nothing spilled):
+                            // bandwidth-bound, so three resident workgroups per CU do (cfg3 same-box, 4 / 3 waves: 3.88 / 4.00 M
+                            // env-steps/s; its LDS carve allows 4: 34 KB each)
 #endif
-#ifndef WG_LF_PAIR
-#define WG_LF_PAIR 1      // 256-thread compact steady variant: pair phase over the whole farm at once — per-target source masks built
-                          // without ballots or LDS atomics, candidate list from a prefix sum (ascending (target, source) order),
-                          // results staged per CANDIDATE (0 = the chunked, densely staged phase shared with the small-farm variants)
-#endif
+// That variant's pair phase runs over the whole farm at once — per-target source masks built without ballots or LDS atomics,
+// candidate list from a prefix sum (ascending (target, source) order), results staged per CANDIDATE (lf_pair_phase).
 // LDS layout of that phase inside the staging region (bytes; n = turbines): packed sources | masks | list offsets + wave totals |
 // candidate list (worst case n (n - 1) / 2 entries) | per-candidate deficit, added TI (lf_cap each)
 #define WG_LF_OFF_TM(n) (16 * (size_t)(n))
 #define WG_LF_OFF_BASE(n) (32 * (size_t)(n))
 #define WG_LF_OFF_CL(n) ((36 * (size_t)(n) + 4 * 8 + 15) & ~(size_t)15)
 #define WG_LF_OFF_DEF(n) ((WG_LF_OFF_CL(n) + (size_t)(n) * ((n) - 1) + 15) & ~(size_t)15)
-#ifndef WG_S_UNROLL_ALL
-#define WG_S_UNROLL_ALL 0   // 1: the rotor-point loop of the Gaussian pair evaluation unrolled by 4 in every variant (A/B builds)
-#endif
-#ifndef WG_GL_POSTPASS_WAIT
-#define WG_GL_POSTPASS_WAIT 1   // GL variant: the compiler-visible vmcnt(0) right after the pipelined advection pass (0: A/B builds)
-#endif
-#ifndef WG_BOX_XCD_PAIRS
-#define WG_BOX_XCD_PAIRS 1   // frozen-box variants: the two farms of an env on the same XCD (0 = adjacent block indices, for A/B builds)
-#endif
-#ifndef WG_PAIR_FIRST
-#define WG_PAIR_FIRST 1   // steady compact variant: deficit phase BEFORE the advection pass (0 = round-2 order, for A/B builds)
-#endif
 
 struct FlowP {
     int B, N, F, K, P, S, S_pad, S_shift, NP, n_tab;
@@ -68,7 +39,7 @@ struct FlowP {
     int res;                      // 1: compact per-turbine rings + pair-major deficit phases (small farms), 0: legacy streaming variant
     int pstride;                  // floats between the particle blocks of consecutive farm slots (>= NP, see wg_create)
     int target_chunk;             // targets whose pair parameters are staged in LDS at once
-    int lf_cap;                   // large-farm steady variant (WG_LF_PAIR): candidates whose results fit the staging region at once
+    int lf_cap;                   // large-farm steady variant (lf_pair_phase): candidates whose results fit the staging region at once
     int lds_off_turb, lds_off_tab, lds_bytes;
     int rec_il;                   // the packed emission record is ONE interleaved array (rec_a[2 i] = ct|k, rec_a[2 i + 1] = u_e|hv; rec_b = rec_a + 1):
                                   // steady compact handles (GL / k_flow_env, LF) — a bracket pair is 16 contiguous bytes of the array

@@ -78,16 +78,8 @@ struct TurbCtx {
 
 // streamed particle state of the turbulent pass: touched once per launch -> non-temporal, so that it does not evict
 // the meandering box from L2
-#ifdef WG_NO_NT
-#define WG_LDS(p) (*(p))
-#define WG_STS(p, v) (*(p) = (v))
-#else
 #define WG_LDS(p) __builtin_nontemporal_load(p)
 #define WG_STS(p, v) __builtin_nontemporal_store((v), (p))
-#endif
-#ifndef WG_NT_PY
-#define WG_NT_PY 0
-#endif
 #ifndef WG_ABLATE
 #define WG_ABLATE 0   // profiling only: 1 = no advection pass, 2 = no deficit phases
 #endif
@@ -126,7 +118,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
     // staging of the compact variants' deficit phases (the `pair` region, per chunk of TC targets):
     // cl[TC*N] u16 candidate list | def[TC*N] rotor-mean deficit | tiav[TC*N] added TI
     // (LF, the large-farm steady variant: staged per candidate, see lf_pair_phase)
-    constexpr bool LF = NT == 256 && RES && TURB == WG_TURB_NONE && (WG_PAIR_FIRST != 0) && (WG_LF_PAIR != 0);
+    constexpr bool LF = NT == 256 && RES && TURB == WG_TURB_NONE;
     unsigned short* cl = LF ? reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(pair) + WG_LF_OFF_CL(N)) : reinterpret_cast<unsigned short*>(pair);
     float* def = LF ? reinterpret_cast<float*>(reinterpret_cast<char*>(pair) + WG_LF_OFF_DEF(N)) : reinterpret_cast<float*>(cl + ((TC * N + 7) & ~7));
     float* tiav = LF ? def + p.lf_cap : def + TC * N;
@@ -144,8 +136,8 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
     // and quad list (LDS / ALU work, ~5 k cycles = one loaded round trip) -> the deficit evaluation reads the landed
     // words from LDS.  (The bounds are those BEFORE this step's records: they cover every particle already in the
     // rings; a pair close enough to be bracketed by a particle released in this step is a candidate unconditionally.)
-    constexpr bool PRE = RES && TURB == WG_TURB_NONE && (WG_PAIR_FIRST != 0);
-    constexpr bool GL = PRE && NT == WG_WAVE && (WG_GLDS != 0);
+    constexpr bool PRE = RES && TURB == WG_TURB_NONE;
+    constexpr bool GL = PRE && NT == WG_WAVE;
     // interleaved record array (FlowP::rec_il; the host sets it for exactly these variants): a bracket pair is 16 contiguous
     // bytes of the array the advection pass streams
     constexpr bool IL = GL || LF;
@@ -428,7 +420,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                     const float rn = r2 > 0.f ? fast_pow(r2 * iD2, 0.5f * nsg) : 0.f;
                     acc += amp * __expf(-rn * inv2sp2);
                 }
-            } else if (LF || (WG_S_UNROLL_ALL != 0)) {
+            } else if (LF) {
                 // (unrolled by 4: the LDS reads of the rotor-point offsets are in flight together — the rolled loop waits
                 // for two dependent LDS reads per point; same additions in the same order)
 #pragma unroll 4
@@ -553,9 +545,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                 const int tl = it >> p.S_shift, s = it & (p.S_pad - 1);
                 if (s >= p.S || !gflag[tl]) continue;
                 const int t = t0 + tl;
-#ifndef WG_NO_ADD_COUNT
                 ++add_acc;                    // (roofline accounting: one 8-corner lookup of the isotropic box)
-#endif
                 float g3[3];
                 abox_lookup(p, d, T[t].xr - tc.ws * sr.time + tc.ox, T[t].yr + (double)(rdy[s] * T[t].cg) + tc.oy,
                             p.hub_d + (double)rdz[s], g3);
@@ -951,16 +941,20 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
         WG_STAMP(10);
         // pipelined advection (GLP): the loads of a lane's first listed quad are requested before the deficit evaluation
         // (its ~4 k cycles of ALU work hide their round trip), and inside the pass every lane requests its next quad
-        // before it computes the current one.  Costs 12 + 12 registers: this variant is built at 4 waves per SIMD.
-        constexpr bool LFP = !GL && NT == 256 && (WG_ADV_PIPE_LF != 0);     // (large farms: see WG_ADV_PIPE_LF)
-        constexpr bool GLP = (GL && (WG_ADV_PIPE != 0)) || LFP;
+        // before it computes the current one (cfg2 k_flow 61.5 -> 58.8 us same box against the plain loop).  Costs 12 + 12
+        // registers: this variant is built at 4 waves per SIMD.
+        // LFP, the 256-thread variant (large farms), requests its quads one ahead inside the pass only (cfg3 same-box: 0 / 1 / 2
+        // quads ahead = 3.80 / 4.04 / 3.93 M env-steps/s).  vmcnt counts loads and stores in ONE in-order queue: a plain
+        // load-compute-store loop waits for the previous trip's stores whenever it waits for its loads — two round trips per
+        // trip (cfg3: 20 trips of ~2 us).  Requested before the stores, the next quad's loads no longer queue behind them.
+        constexpr bool LFP = !GL && NT == 256;
+        constexpr bool GLP = GL || LFP;
         const int nlist_pre = GL ? gl_nlist : 0;
-        // (two quads ahead when WG_ADV_PIPE = 2: `n_*` is the lane's next quad, `m_*` the one after it)
         struct QuadReq { float4 py; uint4 ra, rb; int t, kq, q; };
-        QuadReq nq_, mq_;
-        nq_.py = mq_.py = make_float4(0.f, 0.f, 0.f, 0.f);
-        nq_.ra = nq_.rb = mq_.ra = mq_.rb = make_uint4(0u, 0u, 0u, 0u);
-        nq_.t = nq_.kq = nq_.q = mq_.t = mq_.kq = mq_.q = 0;
+        QuadReq nq_;      // the lane's next quad
+        nq_.py = make_float4(0.f, 0.f, 0.f, 0.f);
+        nq_.ra = nq_.rb = make_uint4(0u, 0u, 0u, 0u);
+        nq_.t = nq_.kq = nq_.q = 0;
         auto adv_request_to = [&](QuadReq& r, const int c, const bool valid) __attribute__((always_inline)) {
             const unsigned ent = valid ? ql[c] : 0u;
             r.t = (int)(ent >> qsh); r.kq = (int)(ent & ((1u << qsh) - 1u));
@@ -969,7 +963,6 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             r.ra = reinterpret_cast<const uint4*>(pl.ra)[IL ? 2 * r.q : r.q];
             r.rb = IL ? reinterpret_cast<const uint4*>(pl.ra)[2 * r.q + 1] : reinterpret_cast<const uint4*>(pl.rb)[r.q];
         };
-        constexpr bool GLP2 = (GL && (WG_ADV_PIPE >= 2)) || (LFP && (WG_ADV_PIPE_LF >= 2));
         if (GL) {
             // deficit phase, part 2: the gathers issued before the records have landed (or do so now)
             for (int t = tid; t < N; t += NT) { T[t].u = ws_f; T[t].v = 0.f; T[t].w = 0.f; }
@@ -985,8 +978,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             float g_py0 = gat[256 + l], g_py1 = gat[320 + l];
             // (GLP: the first quad of the advection pass is requested now — its round trip runs under the deficit
             // evaluation below)
-            if (GLP) adv_request_to(nq_, tid, tid < nlist_pre);
-            if (GLP2) adv_request_to(mq_, tid + NT, tid + NT < nlist_pre);
+            adv_request_to(nq_, tid, tid < nlist_pre);
             for (int c0 = 0; c0 < gl_nc; c0 += NT) {
                 const int c = c0 + tid;
                 if (c0 > 0) {      // (more than 64 candidates: not the common case) the next batch lands in the same words
@@ -1031,19 +1023,13 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             WG_STAMP(9);
         }
         const int nlist = GL ? gl_nlist : *nq;
-        if (LFP) {
-            adv_request_to(nq_, tid, tid < nlist);
-            if (GLP2) adv_request_to(mq_, tid + NT, tid + NT < nlist);
-        }
+        if (LFP) adv_request_to(nq_, tid, tid < nlist);
         for (int c = tid; c < nlist; c += NT) {
             int t, kq, q;
             float4 py; uint4 ra, rb;
             if (GLP) {
                 t = nq_.t; kq = nq_.kq; q = nq_.q; py = nq_.py; ra = nq_.ra; rb = nq_.rb;
-                if (GLP2) {
-                    nq_ = mq_;
-                    if (c + 2 * NT < nlist) adv_request_to(mq_, c + 2 * NT, true);
-                } else if (c + NT < nlist) adv_request_to(nq_, c + NT, true);
+                if (c + NT < nlist) adv_request_to(nq_, c + NT, true);
             } else {
                 const unsigned ent = ql[c];
                 t = (int)(ent >> qsh); kq = (int)(ent & ((1u << qsh) - 1u));
@@ -1084,16 +1070,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                     reinterpret_cast<uint4*>(pl.rb)[q] = make_uint4(rbv[0], rbv[1], rbv[2], rbv[3]);
                 }
             }
-#if WG_NT_PY
-            {   // (streamed once per launch and not read again before the next launch: non-temporal, so that the lines do not
-                // sit dirty in L2 until the end-of-kernel write-back)
-                typedef float f4v __attribute__((ext_vector_type(4)));
-                f4v pv = {pyv[0], pyv[1], pyv[2], pyv[3]};
-                __builtin_nontemporal_store(pv, reinterpret_cast<f4v*>(pl.py) + q);
-            }
-#else
             reinterpret_cast<float4*>(pl.py)[q] = make_float4(pyv[0], pyv[1], pyv[2], pyv[3]);
-#endif
             // (excursion bound over the VALID particles of the quad only: a slot that holds no particle yet keeps whatever
             // an earlier episode left there, and one such value would loosen the chain's bound for the whole episode)
             float ex = 0.f;
@@ -1305,11 +1282,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
         // quads in flight per lane and occupancy are tuned together per workgroup size (measured, cfg2 / cfg3 / cfg4):
         // 128 threads: QB = 1 at 6 waves/SIMD (80 VGPRs) beats QB = 2 at 5 waves (96 VGPRs) by 6 %; 256 threads (large
         // farms, long streaming loops): QB = 2 at 5 waves is 8 % better; 64 threads: no difference
-#ifdef WG_QB
-        constexpr int QB = WG_QB;
-#else
         constexpr int QB = (NT == 128) ? 1 : 2;
-#endif
         const int stride = NT * 4;
         for (int b0 = tid * 4; b0 < p.NP; b0 += stride * QB) {
             uint4 rb[QB];
@@ -1393,7 +1366,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
     // (GLP: a wait the compiler's bookkeeping sees, right after the pipelined pass — the last trip's conditional request
     // otherwise stays "possibly pending" in its view around the flow-step loop and it orders the next step's register
     // writes behind it with vmcnt(0) waits that drain the LDS-DMA gathers)
-    if (RES && TURB == WG_TURB_NONE && NT == WG_WAVE && (WG_GLDS != 0) && (WG_PAIR_FIRST != 0) && (WG_ADV_PIPE != 0) && (WG_GL_POSTPASS_WAIT != 0)) wg_wait_vmem();
+    if (GL) wg_wait_vmem();
     sr.head = new_head; sr.n_valid = new_valid; sr.s_off = s_new; sr.time += p.dt_d; sr.istep += 1u;
     sr.n_emitted += (unsigned)n_emit;
     WG_STAMP(3);
@@ -1604,7 +1577,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
     // (farm-major: -4 % on cfg5).
     int farm, ec;
     if (TURB == WG_TURB_BOX) {
-        if (F == 2 && (WG_BOX_XCD_PAIRS != 0) && (gridDim.x & 15u) == 0u) {
+        if (F == 2 && (gridDim.x & 15u) == 0u) {
             // (workgroup i runs on XCD i % 8, each XCD has its own L2: the two farms of an env are 8 apart in the block order,
             // so that they land on the SAME XCD one dispatch round apart — adjacent indices share nothing but the MALL)
             farm = (bid >> 3) & 1;
@@ -1664,9 +1637,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
     const uint8_t masked_out = use_mask ? (uint8_t)(mask_byte == 0) : (uint8_t)0;
     // An idle background workgroup (its context has no share of work in this launch: ~28 % of the workgroups of a cfg2
     // launch) leaves on its header alone, before any state is requested (round 4: 0 ... +1.6 % same-box, 9 MB of reads less)
-#ifndef WG_NO_IDLE_EARLY
     if (mode == WG_MODE_STEP && c != env_live && !init_pending && env_shadow_iters <= 0) return;
-#endif
     const int t_own = tid < N ? tid : 0;
     int dev_rem, fill_rem, cursor, n_pushed, pend_farm_n, pend_base_n;
     unsigned part0, flow0;       // accounting counters: read with the headers, so that the epilogue only stores
@@ -1735,11 +1706,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
             if (env_done) return;
         } else {
             if (!p.autoreset) return;
-#ifdef WG_NO_INIT_PATH
-            if (false) {
-#else
             if (init_pending) {
-#endif
                 // Rare path (one context per truncation): the episode this context will hold has not been set up yet
                 // — k_glue flagged it when it retired the finished episode.  Wave 0 of BOTH farm workgroups runs the
                 // same initialisation from the generator snapshot k_glue left in the context: identical context-level
@@ -1867,7 +1834,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
     // (GL variant: a further flow step of the launch gathers what this step's advection pass stored — the wait sits on the
     // loop's back edge, where the compiler's wait-count pass sees it on every path around the loop; a live step with K = 1
     // leaves the loop without it)
-    constexpr bool GLK = RES && TURB == WG_TURB_NONE && NT == WG_WAVE && (WG_GLDS != 0) && (WG_PAIR_FIRST != 0);
+    constexpr bool GLK = RES && TURB == WG_TURB_NONE && NT == WG_WAVE;
     auto back_edge = [&]() __attribute__((always_inline)) { if (GLK) full_barrier<NT>(); };
     for (;; back_edge()) {
         if (!live_step && sub == 0 && (budget <= 0 || (dev_rem == 0 && fill_rem == 0))) break;

@@ -312,7 +312,7 @@ inline WgFlowCarve wg_plan_flow_carve(const WgParams& p, const WgHooks& hk, cons
         }
         // (+ 12 bytes per pair for the added-turbulence contributions when that model is on)
         off = std::max(ql, ((size_t)(added ? 22 : 10) * tc * p.N + 16 + 15) & ~(size_t)15);
-        if ((WG_LF_PAIR != 0) && (WG_PAIR_FIRST != 0) && block == 256 && p.turb_mode == WG_TURB_NONE) {
+        if (block == 256 && p.turb_mode == WG_TURB_NONE) {
             // large-farm steady variant: results staged per candidate (layout: wg_flow.h, WG_LF_OFF_*); at least 512
             // candidates at once, whatever the chunked carve would have taken otherwise
             const size_t fixed = WG_LF_OFF_DEF(p.N);
@@ -324,7 +324,7 @@ inline WgFlowCarve wg_plan_flow_carve(const WgParams& p, const WgHooks& hk, cons
         // single-wave steady variant: the deficit phase's gathers are LDS-DMA requests issued before the record /
         // quad-list phases, so the candidate list and the quad list are alive together (no aliasing) and the
         // gathers need a landing zone
-        if ((WG_GLDS != 0) && (WG_PAIR_FIRST != 0) && block == 64 && p.turb_mode == WG_TURB_NONE) {
+        if (block == 64 && p.turb_mode == WG_TURB_NONE) {
             k.gl = 1;
             off = ((size_t)10 * tc * p.N + 16 + 15) & ~(size_t)15;
             k.lds_off_ql = (int)off; off += ql;
@@ -549,7 +549,7 @@ inline int wg_plan_create(const wg_config* c, const WgHooks& hk, int lds_limit, 
     if (hk.lds_pad.set) f.lds_bytes = std::min(lds_limit, f.lds_bytes + hk.lds_pad.v);      // (measurement: what a workgroup's LDS size alone costs)
     // packed emission record: two arrays, or one interleaved (ct|k, u_e|hv) array for the steady compact variants whose
     // deficit phase gathers bracket pairs from it (GL / k_flow_env: 64 threads; LF: 256 threads)
-    f.rec_il = (f.gl || (f.res && f.block == 256 && p.turb_mode == WG_TURB_NONE && (WG_LF_PAIR != 0) && (WG_PAIR_FIRST != 0))) ? 1 : 0;
+    f.rec_il = (f.gl || (f.res && f.block == 256 && p.turb_mode == WG_TURB_NONE)) ? 1 : 0;
 
     wg_plan_step_kernels(c, hk, p, f, v.small, lds_limit);
     out->envw_eligible = f.envw; out->fused_eligible = f.env_fused;
