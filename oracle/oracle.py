@@ -226,4 +226,4 @@ def mann_noise(seed, Nxyz):
     L.wgo_mann_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
     L.wgo_mann_noise.restype = None
     L.wgo_mann_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(cells), out.ctypes.data_as(C.c_void_p))
-    return (out[..., 0] + 1j * out[..., 1]).reshape((3,) + tuple(int(n) for n in Nxyz))
+    return out.view(np.complex64).reshape((3,) + tuple(int(n) for n in Nxyz))

@@ -26,10 +26,13 @@ double wgo_rng_noise(uint64_t key, uint32_t push_idx, uint32_t turbine, uint32_t
 }
 
 /* the Philox stream of wg_generate_mann_box (windgym_amd/csrc/wg_mann.hip: mann_noise): complex standard normal of
- * (component c, cell idx), E|n|^2 = 1 — out[(c * cells + idx) * 2 + {0, 1}] = (re, im); float arithmetic like the kernel's */
+ * (component c, cell idx), E|n|^2 = 1 — out[(c * cells + idx) * 2 + {0, 1}] = (re, im); float arithmetic like the kernel's.
+ * Every sample is a function of (seed, c, idx) alone, so the cells are shared out between threads (2^26 cells x 3: the
+ * shipped box sizes of tests/test_mann_generator.py). */
 void wgo_mann_noise(uint64_t seed, uint64_t cells, float* out) {
     const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
     for (uint32_t c = 0; c < 3; ++c)
+#pragma omp parallel for schedule(static)
         for (uint64_t idx = 0; idx < cells; ++idx) {
             const uint32_t ctr[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), c, 0x4d414e4eu};
             uint32_t o[4];

@@ -94,7 +94,7 @@ def blondel_centre_deficit(ct, sigma, n):
     return a1 - math.sqrt(max(a2 - n * ct / (16.0 * math.gamma(2.0 / n) * sigma ** (4.0 / n)), 0.0))
 
 
-def blondel_jimenez_power(x, y, ws, wd, ti, yaw, tab_ws, tab_power, tab_ct, diameter, n_quad=20):
+def blondel_jimenez_power(x, y, ws, wd, ti, yaw, tab_ws, tab_power, tab_ct, diameter, n_quad=20, jimenez_beta=JIMENEZ_BETA):
     """per-turbine power [N] (W) of ONE case with the reference agent's wake model (rotor-centre deficit, linear
     superposition on the free-stream speed, ambient TI in the wake width, Jimenez deflection with beta = 0.1)"""
     x, y, yaw = (np.asarray(a, dtype=np.float64) for a in (x, y, yaw))
@@ -115,7 +115,7 @@ def blondel_jimenez_power(x, y, ws, wd, ti, yaw, tab_ws, tab_power, tab_ct, diam
             n = BC_A_F * math.exp(BC_B_F * xd) + BC_C_F
             C = blondel_centre_deficit(ct[s], sigma, n)
             xq = dx * s01
-            alpha = (cg[s] ** 2 * sg[s] * ct[s] * 0.5) / (1.0 + JIMENEZ_BETA * xq / D) ** 2
+            alpha = (cg[s] ** 2 * sg[s] * ct[s] * 0.5) / (1.0 + jimenez_beta * xq / D) ** 2
             sa = np.sin(alpha)
             defl = -float(np.sum(0.5 * (sa[1:] + sa[:-1]) * np.diff(xq)))
             r = abs(yr[t] - (yr[s] + defl)) / D

@@ -39,20 +39,20 @@ def _beta_from_table(kL, table):
     return table[i0] * (1.0 - w) + table[i0 + 1] * w
 
 
-def mann_field_from_noise(noise, dxyz=(3.0, 3.0, 3.0), alphaepsilon=0.1, L=33.6, Gamma=3.9, beta_table=None):
-    """The spectral part of the generator for GIVEN complex white noise ``noise`` [3, Nx, Ny, Nz] (E|n|^2 = 1): sheared
-    von Karman tensor times the noise, inverse FFT, unit standard deviation of u.  float64 numpy — the CPU restatement
-    the HIP generator (``generate_mann_box_hip(noise=...)``) is pinned against cell by cell (tests/test_mann_generator.py).
-    ``beta_table``: interpolate the eddy lifetime in this table (as the kernel does) instead of evaluating 2F1 per cell."""
-    noise = np.asarray(noise)
+def _mann_dz(noise, i0, i1, dxyz, alphaepsilon, L, Gamma, beta_table):
+    """dZ of the three velocity components (complex128 [i1 - i0, Ny, Nz] each) on the wave-number planes i0 <= i < i1 of x:
+    sheared von Karman tensor times the complex white noise ``noise`` [3, Nx, Ny, Nz].  Every operation is per cell, so a
+    box may be evaluated whole or slab by slab."""
     _, Nx, Ny, Nz = noise.shape
     dx, dy, dz = (float(d) for d in dxyz)
-    k1 = 2 * np.pi * np.fft.fftfreq(Nx, dx)[:, None, None]
+    n = noise[:, i0:i1]
+    nx = i1 - i0
+    k1 = 2 * np.pi * np.fft.fftfreq(Nx, dx)[i0:i1, None, None]
     k2 = 2 * np.pi * np.fft.fftfreq(Ny, dy)[None, :, None]
     k3 = 2 * np.pi * np.fft.fftfreq(Nz, dz)[None, None, :]
-    k1 = np.broadcast_to(k1, (Nx, Ny, Nz)).astype(np.float64)
-    k2 = np.broadcast_to(k2, (Nx, Ny, Nz)).astype(np.float64)
-    k3 = np.broadcast_to(k3, (Nx, Ny, Nz)).astype(np.float64)
+    k1 = np.broadcast_to(k1, (nx, Ny, Nz)).astype(np.float64)
+    k2 = np.broadcast_to(k2, (nx, Ny, Nz)).astype(np.float64)
+    k3 = np.broadcast_to(k3, (nx, Ny, Nz)).astype(np.float64)
     kk = np.sqrt(k1 ** 2 + k2 ** 2 + k3 ** 2)
     beta = _eddy_lifetime_beta(kk * L, Gamma) if beta_table is None else _beta_from_table(kk * L, np.asarray(beta_table, np.float64))
     k30 = k3 + beta * k1
@@ -72,23 +72,70 @@ def mann_field_from_noise(noise, dxyz=(3.0, 3.0, 3.0), alphaepsilon=0.1, L=33.6,
     zeta2 = k2 / k1s * C1 + C2
     zeta1 = np.where(k1 == 0, -beta, zeta1)
     zeta2 = np.where(k1 == 0, 0.0, zeta2)
-    n = noise
     # isotropic incompressible field dZ_iso = amp * (k0 x n), then sheared
     a1 = amp * (k2 * n[2] - k30 * n[1])
     a2 = amp * (k30 * n[0] - k1 * n[2])
     a3 = amp * (k1 * n[1] - k2 * n[0])
     r = (k0 / kk_s) ** 2
-    dZ1 = a1 + zeta1 * a3
-    dZ2 = a2 + zeta2 * a3
-    dZ3 = r * a3
+    dZ = [a1 + zeta1 * a3, a2 + zeta2 * a3, r * a3]
+    if i0 == 0:
+        for z in dZ:
+            z[0, 0, 0] = 0.0
+    return dZ
+
+
+def mann_field_from_noise(noise, dxyz=(3.0, 3.0, 3.0), alphaepsilon=0.1, L=33.6, Gamma=3.9, beta_table=None):
+    """The spectral part of the generator for GIVEN complex white noise ``noise`` [3, Nx, Ny, Nz] (E|n|^2 = 1): sheared
+    von Karman tensor times the noise, inverse FFT, unit standard deviation of u.  float64 numpy — the CPU restatement
+    the HIP generator (``generate_mann_box_hip(noise=...)``) is pinned against cell by cell (tests/test_mann_generator.py).
+    ``beta_table``: interpolate the eddy lifetime in this table (as the kernel does) instead of evaluating 2F1 per cell."""
+    noise = np.asarray(noise)
+    _, Nx, Ny, Nz = noise.shape
+    dx, dy, dz = (float(d) for d in dxyz)
     dV = (2 * np.pi) ** 3 / (Nx * dx * Ny * dy * Nz * dz)
     out = np.empty((3, Nx, Ny, Nz), dtype=np.float64)
-    for c, dZ in enumerate((dZ1, dZ2, dZ3)):
-        dZ = dZ.copy()
-        dZ[0, 0, 0] = 0.0
+    for c, dZ in enumerate(_mann_dz(noise, 0, Nx, dxyz, alphaepsilon, L, Gamma, beta_table)):
         out[c] = (np.fft.ifftn(dZ) * (Nx * Ny * Nz) * np.sqrt(dV)).real
     out /= float(out[0].std())
     return out
+
+
+def mann_field_components(noise, dxyz=(3.0, 3.0, 3.0), alphaepsilon=0.1, L=33.6, Gamma=3.9, beta_table=None, slab=16, workers=None):
+    """:func:`mann_field_from_noise` for boxes whose float64 intermediates do not fit in memory at once (2048 x 512 x 64 and
+    up): yields u, v, w (float64 [Nx, Ny, Nz], already divided by the standard deviation of u) one at a time.  The spectral
+    tensor is evaluated in slabs of ``slab`` x-planes (``noise`` may stay complex64), each component is transformed and
+    handed out before the next one, and the caller drops it when done: the peak is the three complex128 dZ arrays plus one
+    transform.  ``workers`` = None: slabs in turn and numpy's FFT — bit-equal to :func:`mann_field_from_noise` (asserted in
+    tests/test_mann_generator.py); an integer: that many threads for the slabs and scipy.fft.ifftn(workers=...)."""
+    noise = np.asarray(noise)
+    _, Nx, Ny, Nz = noise.shape
+    dx, dy, dz = (float(d) for d in dxyz)
+    dV = (2 * np.pi) ** 3 / (Nx * dx * Ny * dy * Nz * dz)
+    dZ = [np.empty((Nx, Ny, Nz), dtype=np.complex128) for _ in range(3)]
+
+    def fill(i0):
+        for full, part in zip(dZ, _mann_dz(noise, i0, min(i0 + slab, Nx), dxyz, alphaepsilon, L, Gamma, beta_table)):
+            full[i0:i0 + slab] = part
+
+    if workers is None:
+        for i0 in range(0, Nx, slab):
+            fill(i0)
+        ifftn = np.fft.ifftn
+    else:
+        import functools
+        from concurrent.futures import ThreadPoolExecutor
+        import scipy.fft
+        with ThreadPoolExecutor(int(workers)) as pool:
+            list(pool.map(fill, range(0, Nx, slab)))
+        ifftn = functools.partial(scipy.fft.ifftn, workers=int(workers), overwrite_x=True)
+    sd = None
+    for c in range(3):
+        f = (ifftn(dZ[c]) * (Nx * Ny * Nz) * np.sqrt(dV)).real
+        dZ[c] = None
+        if sd is None:
+            sd = float(f.std())
+        f /= sd
+        yield f
 
 
 def generate_mann_box(Nxyz=(1024, 128, 32), dxyz=(3.0, 3.0, 3.0), alphaepsilon=0.1, L=33.6, Gamma=3.9, seed=1234):
