@@ -376,6 +376,20 @@ int wg_mann_beta_table(double Gamma, int n, double log10_lo, double log10_hi, do
 int wg_steady_power(wg_handle h, int model, int n_cases, const float* ws_dev, const float* wd_dev, const float* ti_dev,
                     const float* yaw_dev, float* power_dev, void* stream);
 
+/* The whole Serial-Refine yaw optimisation (WindGym/Agents/PyWakeAgent.py:144-288, yaw_optimizer_srf_vect) of n_cond wind
+ * conditions in ONE kernel launch (k_steady_srf: one workgroup per condition, yaw_n waves), enqueued on `stream` without a
+ * host synchronisation; ws / wd / ti f32[n_cond] may have been written earlier on the same stream.  models as wg_steady_power.
+ * With P(yaw) = the sum over the turbines, in index order and in double precision, of the powers wg_steady_power returns for
+ * (ws, wd, ti, (float) yaw):  yaw = 0, best = P(yaw);  for pass r < refine_pass_n, for every turbine t from upstream to
+ * downstream (k_steady's order: rank by fp32 flow-frame x, ties by index):  candidates yaw_j = yaw with yaw_j[t] = yaw[t] +
+ * offsets_dev[r][j] (f64[refine_pass_n][yaw_n], degrees; the add in double);  j* = the first j with the largest P(yaw_j);  if
+ * P(yaw_j*) > best, yaw = yaw_j* and best = P(yaw_j*).  Outputs: yaw_dev f64[n_cond][n_turb] = yaw clamped to +-yaw_clip,
+ * power_dev f64[n_cond] = best (may be NULL), order_dev i32[n_cond][n_turb] = the visiting order (may be NULL).
+ * Limits: 2 <= yaw_n <= 16, 1 <= refine_pass_n <= 16.                                                                    */
+int wg_steady_optimize(wg_handle h, int model, int n_cond, const float* ws_dev, const float* wd_dev, const float* ti_dev,
+                       int refine_pass_n, int yaw_n, const double* offsets_dev, double yaw_clip, double* yaw_dev,
+                       double* power_dev, int32_t* order_dev, void* stream);
+
 /* Rotor points at which one flow launch looked the wake-added turbulence box up (8 corners x (u, v, w) = 96 bytes each:
  * only the rotors of targets with a candidate source wake do), averaged over the window the LAST wg_kernel_timing call
  * closed — the a7 term of bench.py's algorithmic bytes.  0 without wg_config.added_turbulence.

@@ -29,7 +29,7 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("PPOPopulation", "Population"):
         from . import population
         return getattr(population, name)
-    if name in ("PyWakeAgent", "SteadyStateYawAgent"):
+    if name in ("PyWakeAgent", "SteadyStateYawAgent", "PyWakeVecAgent", "SteadyStateYawVecAgent"):
         from . import steady
         return getattr(steady, name)
     raise AttributeError(name)

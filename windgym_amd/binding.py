@@ -33,7 +33,7 @@ ABI_SYMBOLS = (
     "wg_last_error", "wg_abi_version", "wg_create", "wg_destroy", "wg_obs_dim", "wg_hist_max",
     "wg_set_turbulence_box", "wg_set_turbulence_boxes", "wg_set_added_turbulence_box", "wg_set_deficit_table", "wg_set_box_ids", "wg_set_wind", "wg_set_wind_device", "wg_set_flow_script", "wg_reset", "wg_step", "wg_set_step_graph", "wg_check", "wg_obs_multi", "wg_set_obs_multi_buffer",
     "wg_set_final_obs_multi_buffer", "wg_rollout_multi", "wg_gae_shared",
-    "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
+    "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_steady_optimize", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
     "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
     "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
     "wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared",
@@ -144,6 +144,8 @@ def load_library():
     L.wg_generate_mann_box.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                        C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p]
     L.wg_steady_power.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    L.wg_steady_optimize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_mann_beta_table.argtypes = [C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]
     L.wg_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.wg_flow_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -532,6 +534,36 @@ class HipBatch:
         _chk(self.L.wg_steady_power(self._h, {"m0": 0, "blondel_jimenez": 1}[model], n, ws.data_ptr(), wd.data_ptr(),
                                     ti.data_ptr(), yaw.data_ptr(), out.data_ptr(), self._stream()), "wg_steady_power")
         return out
+
+    def steady_optimize(self, ws, wd, ti, model="m0", refine_pass_n=8, yaw_n=9, yaw_max=30.0, return_order=False):
+        """Serial-Refine optimal yaws for the wind conditions ws / wd / ti [C] (host arrays or CUDA tensors) in ONE launch of
+        k_steady_srf (wg_steady_optimize), enqueued on the current stream: -> (yaw [C, N] float64 degrees, farm power [C]
+        float64) CUDA tensors, and the visiting order [C, N] int32 with ``return_order``.  The result is what
+        ``steady.yaw_optimizer_srf(..., batch=self)`` computes with one launch of k_steady per refine step; like it, this
+        adds 1e-3 deg to wd (the tie of perfectly aligned rows)."""
+        from .steady import MODEL_IDS, srf_offsets
+        t = self.torch
+        f = lambda a: (a.to(self.device, t.float64) if isinstance(a, t.Tensor) else                    # noqa: E731
+                       t.as_tensor(np.array(a, dtype=np.float64), device=self.device)).reshape(-1)
+        ws, wd, ti = f(ws), f(wd), f(ti)
+        n = max(ws.numel(), wd.numel(), ti.numel())
+        ws, wd, ti = (a.expand(n).to(t.float32).contiguous() for a in (ws, wd + 1e-3, ti))
+        offs = srf_offsets(refine_pass_n, yaw_n, yaw_max).to(self.device)
+        N = self.cfg.n_turb
+        yaw = t.empty((n, N), dtype=t.float64, device=self.device)
+        power = t.empty((n,), dtype=t.float64, device=self.device)
+        order = t.empty((n, N), dtype=t.int32, device=self.device) if return_order else None
+        _chk(self.L.wg_steady_optimize(self._h, MODEL_IDS[model], n, ws.data_ptr(), wd.data_ptr(), ti.data_ptr(), int(refine_pass_n),
+                                       int(yaw_n), offs.data_ptr(), float(yaw_max), yaw.data_ptr(), power.data_ptr(),
+                                       order.data_ptr() if return_order else None, self._stream()), "wg_steady_optimize")
+        return (yaw, power, order) if return_order else (yaw, power)
+
+    def optimal_yaws(self, model="m0", refine_pass_n=8, yaw_n=9, yaw_max=30.0):
+        """Serial-Refine optimal yaws [B, N] (float64 degrees, CUDA) for the CURRENT wind of every env of this handle: the winds
+        are read on the device (info "wind_f64"), no host copy, one launch (``steady_optimize``)."""
+        w = self.info("wind_f64")
+        return self.steady_optimize(w[:, 0], w[:, 1], w[:, 2], model=model, refine_pass_n=refine_pass_n, yaw_n=yaw_n,
+                                    yaw_max=yaw_max)[0]
 
     def added_lookups(self):
         """Rotor points per flow launch at which the wake-added turbulence box was looked up (window of the last

@@ -1101,29 +1101,58 @@ extern "C" int wg_kernel_timing(wg_handle h, int enable, double* flow_ms_avg, do
     return 0;
 }
 
-extern "C" int wg_steady_power(wg_handle h, int model, int n_cases, const float* ws_dev, const float* wd_dev, const float* ti_dev,
-                               const float* yaw_dev, float* power_dev, void* stream) {
-    if (!h || !ws_dev || !wd_dev || !ti_dev || !yaw_dev || !power_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (model != 0 && model != 1) return fail(WG_ERR_INVALID, "wg_steady_power: model must be 0 (steady state of M0) or 1 (Blondel-Cathelain + Jimenez)");
-    if (n_cases < 1) return fail(WG_ERR_INVALID, "wg_steady_power: n_cases must be >= 1");
+// what wg_steady_power and wg_steady_optimize check alike, and the parameter block their kernels share
+static int steady_params(wg_handle h, const char* who, int model, int n_cases, SteadyP* sp) {
+    const std::string w(who);
+    if (model != 0 && model != 1) return fail(WG_ERR_INVALID, w + ": model must be 0 (steady state of M0) or 1 (Blondel-Cathelain + Jimenez)");
+    if (n_cases < 1) return fail(WG_ERR_INVALID, w + ": " + (w == "wg_steady_power" ? "n_cases" : "n_cond") + " must be >= 1");
     // model 0 is documented as the steady state of THIS handle's flow model; k_steady carries the Gaussian M0 with TI folding
     // only — a handle created with another deficit / without the folding must not get Gaussian powers silently
     if (model == 0 && (h->fp.deficit_model != 0 || h->fp.no_ti_fold))
-        return fail(WG_ERR_UNSUPPORTED, "wg_steady_power: model 0 (steady state of the handle's flow model) is implemented for the Gaussian deficit "
+        return fail(WG_ERR_UNSUPPORTED, w + ": model 0 (steady state of the handle's flow model) is implemented for the Gaussian deficit "
                                         "with wake-TI folding only; this handle uses deficit_model " + std::to_string(h->fp.deficit_model) +
                                         (h->fp.no_ti_fold ? " without TI folding" : ""));
-    if (int rc = use_device(h)) return rc;
+    memset(sp, 0, sizeof(*sp));
+    sp->n_cases = n_cases; sp->N = h->p.N; sp->S = h->p.S; sp->n_tab = h->p.n_tab; sp->model = model;
+    sp->n_quad = model == 0 ? 48 : 20;      // quadrature of the deflection integral (steady.py's defaults)
+    sp->D = h->p.D; sp->hub = h->p.hub; sp->R = 0.5f * h->p.D;
+    sp->ka = h->p.ka; sp->kb = h->p.kb; sp->eps0 = h->p.eps0; sp->hill = h->p.hill;
+    sp->tia = h->p.tia; sp->tib = h->p.tib; sp->tic = h->p.tic; sp->tid = h->p.tid;
+    sp->cx0 = h->p.cx0; sp->cy0 = h->p.cy0;
+    sp->x_pos = h->d.x_pos; sp->y_pos = h->d.y_pos; sp->rotor_dy = h->d.rotor_dy; sp->rotor_dz = h->d.rotor_dz;
+    sp->tab_ws = h->d.tab_ws; sp->tab_power = h->d.tab_power; sp->tab_ct = h->d.tab_ct;
+    return 0;
+}
+
+extern "C" int wg_steady_power(wg_handle h, int model, int n_cases, const float* ws_dev, const float* wd_dev, const float* ti_dev,
+                               const float* yaw_dev, float* power_dev, void* stream) {
+    if (!h || !ws_dev || !wd_dev || !ti_dev || !yaw_dev || !power_dev) return fail(WG_ERR_INVALID, "null argument");
     SteadyP sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.n_cases = n_cases; sp.N = h->p.N; sp.S = h->p.S; sp.n_tab = h->p.n_tab; sp.model = model;
-    sp.n_quad = model == 0 ? 48 : 20;      // quadrature of the deflection integral (steady.py's defaults)
-    sp.D = h->p.D; sp.hub = h->p.hub; sp.R = 0.5f * h->p.D;
-    sp.ka = h->p.ka; sp.kb = h->p.kb; sp.eps0 = h->p.eps0; sp.hill = h->p.hill;
-    sp.tia = h->p.tia; sp.tib = h->p.tib; sp.tic = h->p.tic; sp.tid = h->p.tid;
-    sp.cx0 = h->p.cx0; sp.cy0 = h->p.cy0;
-    sp.x_pos = h->d.x_pos; sp.y_pos = h->d.y_pos; sp.rotor_dy = h->d.rotor_dy; sp.rotor_dz = h->d.rotor_dz;
-    sp.tab_ws = h->d.tab_ws; sp.tab_power = h->d.tab_power; sp.tab_ct = h->d.tab_ct;
+    if (int rc = steady_params(h, "wg_steady_power", model, n_cases, &sp)) return rc;
+    if (int rc = use_device(h)) return rc;
     wg_launch_steady(&sp, ws_dev, wd_dev, ti_dev, yaw_dev, power_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_steady_optimize(wg_handle h, int model, int n_cond, const float* ws_dev, const float* wd_dev, const float* ti_dev,
+                                  int refine_pass_n, int yaw_n, const double* offsets_dev, double yaw_clip, double* yaw_dev,
+                                  double* power_dev, int32_t* order_dev, void* stream) {
+    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (yaw_n < 2 || yaw_n > 16) return fail(WG_ERR_INVALID, "wg_steady_optimize: yaw_n must be 2 .. 16 (one wave per candidate), got " + std::to_string(yaw_n));
+    if (refine_pass_n < 1 || refine_pass_n > 16)
+        return fail(WG_ERR_INVALID, "wg_steady_optimize: refine_pass_n must be 1 .. 16, got " + std::to_string(refine_pass_n));
+    if (!(yaw_clip >= 0.0)) return fail(WG_ERR_INVALID, "wg_steady_optimize: yaw_clip must be >= 0");
+    if (!ws_dev || !wd_dev || !ti_dev || !offsets_dev || !yaw_dev)
+        return fail(WG_ERR_INVALID, "wg_steady_optimize: null argument (only power_dev and order_dev may be NULL)");
+    SteadyP sp;
+    if (int rc = steady_params(h, "wg_steady_optimize", model, n_cond, &sp)) return rc;
+    if (wg_steady_srf_lds(sp.N, yaw_n) > 65536)
+        return fail(WG_ERR_UNSUPPORTED, "wg_steady_optimize: " + std::to_string(sp.N) + " turbines x " + std::to_string(yaw_n) +
+                                        " candidates do not fit the 64 KB of LDS of a workgroup");
+    if (int rc = use_device(h)) return rc;
+    wg_launch_steady_srf(&sp, ws_dev, wd_dev, ti_dev, refine_pass_n, yaw_n, offsets_dev, yaw_clip, yaw_dev, power_dev, order_dev,
+                         (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

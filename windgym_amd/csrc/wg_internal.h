@@ -61,4 +61,7 @@ void wg_launch_box_coarsen(const void* fine, void* out, int nx, int ny, int nz, 
 void wg_launch_box_stencil(const void* fine, void* out, int nx, int ny, int nz, hipStream_t st);
 // wg_steady.hip (sp: SteadyP, wg_steady.h)
 void wg_launch_steady(const void* sp, const float* ws, const float* wd, const float* ti, const float* yaw, float* power, hipStream_t st);
+size_t wg_steady_srf_lds(int N, int yaw_n);      // bytes of LDS a k_steady_srf workgroup takes
+void wg_launch_steady_srf(const void* sp, const float* ws, const float* wd, const float* ti, int refine_pass_n, int yaw_n,
+                          const double* offsets, double yaw_clip, double* yaw, double* power, int* order, hipStream_t st);
 }

@@ -1,4 +1,4 @@
-// wg_steady.h — parameter block of k_steady (wg_steady.hip), filled by wg_steady_power (wg_api.hip).
+// wg_steady.h — parameter block of k_steady / k_steady_srf (wg_steady.hip), filled by wg_steady_power / wg_steady_optimize (wg_api.hip).
 #pragma once
 struct SteadyP {
     int n_cases, N, S, n_tab, model, n_quad;

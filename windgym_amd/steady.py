@@ -172,6 +172,7 @@ def blondel_jimenez_power(x, y, ws, wd, ti, yaw, turbine=None, n_quad=20, device
 
 
 WAKE_MODELS = {"m0": None, "blondel_jimenez": blondel_jimenez_power}
+MODEL_IDS = {"m0": 0, "blondel_jimenez": 1}        # `model` of wg_steady_power / wg_steady_optimize
 
 
 def hip_batch_for(x, y, turbine=None, n_rotor_pts=16, device=None, deficit=None, model_constants=None):
@@ -194,14 +195,31 @@ def hip_batch_for(x, y, turbine=None, n_rotor_pts=16, device=None, deficit=None,
     return HipBatch(cfg, device=device)
 
 
+def srf_offsets(refine_pass_n, yaw_n, yaw_max):
+    """The candidate offsets of every Serial-Refine pass, float64 [refine_pass_n, yaw_n] degrees: row r is the linspace over
+    +-yaw_max / 2**r that `yaw_optimizer_srf` walks (the table wg_steady_optimize is handed, so that the device does not
+    restate torch.linspace)."""
+    import torch
+    rows = [torch.linspace(-float(yaw_max) / 2.0 ** r, float(yaw_max) / 2.0 ** r, int(yaw_n), dtype=torch.float64)
+            for r in range(int(refine_pass_n))]
+    return torch.stack(rows) if rows else torch.zeros((0, int(yaw_n)), dtype=torch.float64)
+
+
 def yaw_optimizer_srf(x, y, ws, wd, ti, turbine=None, refine_pass_n=8, yaw_n=9, yaw_max=30.0, device="cpu",
-                      model="m0", batch=None):
+                      model="m0", batch=None, fused=False):
     """Serial-Refine yaw optimisation (PyWakeAgent.py:144-288) for a batch of wind conditions at once.
     ws, wd, ti: arrays of the same length C.  Returns yaw [C, N] in degrees.  model: "m0" (steady state of the build's
     dynamic model) or "blondel_jimenez" (the reference agent's py_wake model).
     ``batch``: a HipBatch of the same layout / turbine — every refine step is then ONE launch of the HIP kernel k_steady
-    over [conditions x candidates] cases (wg_steady_power) instead of the torch restatement."""
+    over [conditions x candidates] cases (wg_steady_power) instead of the torch restatement.  ``fused=True`` (needs
+    ``batch``): the whole optimisation of all conditions is ONE launch of k_steady_srf (HipBatch.steady_optimize) — the same
+    rules, candidate powers bit-equal to k_steady's, no host round trip per refine step."""
     import torch
+    if fused:
+        if batch is None:
+            raise ValueError("yaw_optimizer_srf(fused=True) runs on the device: pass batch= (steady.hip_batch_for)")
+        return batch.steady_optimize(ws, wd, ti, model=model, refine_pass_n=refine_pass_n, yaw_n=yaw_n,
+                                     yaw_max=yaw_max)[0].cpu().numpy()
     fn = WAKE_MODELS[model]
     steady_state_power = fn if fn is not None else globals()["steady_state_power"]
     if batch is not None:
@@ -243,9 +261,12 @@ class SteadyStateYawAgent(BaseAgent):
     model = "m0"
 
     def __init__(self, x_pos, y_pos, wind_speed=8, wind_dir=270, TI=0.07, yaw_max=45, yaw_min=-45, refine_pass_n=8,
-                 yaw_n=9, turbine=None, device="cpu", model=None, deficit=None, model_constants=None):
+                 yaw_n=9, turbine=None, device="cpu", model=None, deficit=None, model_constants=None, fused=False):
         if model is not None:
             self.model = model
+        if fused and not str(device).startswith(("cuda", "hip")):
+            raise ValueError('fused=True is the one-launch optimiser on the device: it needs device="cuda"')
+        self.fused = bool(fused)
         super().__init__(yaw_max, yaw_min)
         self.pywakeagent = True
         self.optimized = False
@@ -285,7 +306,7 @@ class SteadyStateYawAgent(BaseAgent):
     def optimize(self):
         self.optimized_yaws = yaw_optimizer_srf(self.x_pos, self.y_pos, self.wsp, self.wdir, [self.TI], self.turbine,
                                                 self.refine_pass_n, self.yaw_n, device="cpu" if self._batch is not None else self.device,
-                                                model=self.model, batch=self._batch)[0]
+                                                model=self.model, batch=self._batch, fused=self.fused and self._batch is not None)[0]
         self.action = self.scale_yaw(self.optimized_yaws).astype(np.float32)
         self.optimized = True
 
@@ -307,4 +328,59 @@ class PyWakeAgent(SteadyStateYawAgent):
     """The reference's PyWakeAgent (WindGym/Agents/PyWakeAgent.py): Serial-Refine over Blondel-Cathelain (2020) +
     Jimenez deflection, restated from the publications (py_wake itself is not installed: values are not pinned against
     py_wake, only against the equations — tests/test_steady_optimizer.py)."""
+    model = "blondel_jimenez"
+
+
+class SteadyStateYawVecAgent(BaseAgent):
+    """The Serial-Refine yaw agent for a whole batch of envs (`WindFarmVecEnv`, or anything with a `.batch` / `._batch`
+    HipBatch): `predict` returns `scale_yaw` of the optimal yaws of every env's CURRENT wind, float32 [B, N].  The winds are
+    read on the device and all envs are optimised by ONE launch (HipBatch.optimal_yaws -> k_steady_srf); the agent optimises
+    again whenever an env's episode counter (info "episode") has moved since the last call, so it follows autoresets.
+    `UseEnv`: `eval_sweep` binds it to the sweep's env, and every condition of the sweep gets its own yaws.
+    `optimized_yaws` [B, N] float64 degrees stays on the device; the actions are a numpy array unless the env works on CUDA
+    tensors (`as_torch`)."""
+    model = "m0"
+
+    def __init__(self, env=None, model=None, refine_pass_n=8, yaw_n=9, yaw_max=45, yaw_min=-45, search_yaw_max=30.0):
+        if model is not None:
+            self.model = model
+        super().__init__(yaw_max, yaw_min)
+        self.UseEnv = True
+        self.pywakeagent = True
+        self.env = env
+        self.refine_pass_n, self.yaw_n, self.search_yaw_max = refine_pass_n, yaw_n, search_yaw_max
+        self.reset()
+
+    def reset(self):
+        """forget the optimum: the next `predict` optimises again"""
+        self.optimized_yaws = None
+        self._episode = self._batch_seen = None
+
+    def _batch(self):
+        if self.env is None:
+            raise ValueError(f"{type(self).__name__} needs an env (env=, or eval_sweep binds it)")
+        b = getattr(self.env, "batch", None)
+        return b if b is not None else getattr(self.env, "_batch")
+
+    def optimize(self):
+        b = self._batch()
+        self.optimized_yaws = b.optimal_yaws(model=self.model, refine_pass_n=self.refine_pass_n, yaw_n=self.yaw_n,
+                                             yaw_max=self.search_yaw_max)
+        self._batch_seen = b
+
+    def predict(self, *args, **kwargs):
+        b = self._batch()
+        episode = b.info("episode")
+        if (self.optimized_yaws is None or self._batch_seen is not b or self._episode is None
+                or tuple(episode.shape) != tuple(self._episode.shape) or not bool((episode == self._episode).all())):
+            self.optimize()
+            self._episode = episode
+        a = ((self.optimized_yaws - self.yaw_min) / (self.yaw_max - self.yaw_min) * 2 - 1).float()      # scale_yaw, on the device
+        if not getattr(self.env, "as_torch", False):
+            a = a.cpu().numpy()
+        return (a if hasattr(self.env, "batch") else a[0]), None
+
+
+class PyWakeVecAgent(SteadyStateYawVecAgent):
+    """`SteadyStateYawVecAgent` over the reference PyWakeAgent's wake model (Blondel-Cathelain 2020 + Jimenez)."""
     model = "blondel_jimenez"
