@@ -45,7 +45,7 @@ static WgHooks wg_hooks_read() {
     k.flow_block = num("WG_FLOW_BLOCK"); k.flow_res = num("WG_FLOW_RES"); k.flow_env = num("WG_FLOW_ENV");
     k.env_wpe = num("WG_ENV_WPE"); k.env_split = num("WG_ENV_SPLIT"); k.step_fused = num("WG_STEP_FUSED");
     k.sums = num("WG_SUMS"); k.lds_pad = num("WG_LDS_PAD"); k.lf_cap = num("WG_LF_CAP"); k.pstride_pad = num("WG_PSTRIDE_PAD");
-    k.step_graph = num("WG_STEP_GRAPH");
+    k.step_graph = num("WG_STEP_GRAPH"); k.share_dev = num("WG_ENV_SHARE_DEV");
     k.first_obs_gl_only = wg_hook("WG_FIRST_OBS_GL_ONLY") != nullptr;
     k.no_box8 = wg_hook("WG_NO_BOX8") != nullptr;
     k.debug = wg_hook("WG_DEBUG") != nullptr;
@@ -334,9 +334,9 @@ extern "C" int wg_create(const wg_config* c, int device, wg_handle* out) {
                 f.envw && f.env_split ? " + a pass wave for the running episode's context" : "",
                 f.block, f.envw ? f.env_lds : f.lds_bytes, f.pstride);
         fprintf(stderr, "[windgym] plan: res %d block %d gl %d rec_il %d target_chunk %d lf_cap %d lds_bytes %d | envw %d env_wpe %d env_split %d env_fused %d "
-                        "env_lds %d env_off_tab %d | sums_mode %d first_obs %d reset_launches %d\n",
-                f.res, f.block, f.gl, f.rec_il, f.target_chunk, f.lf_cap, f.lds_bytes, f.envw, f.env_wpe, f.env_split, f.env_fused, f.env_lds,
-                f.env_off_tab, h->p.sums_mode, h->plan.first_obs, h->plan.reset_launches);
+                        "env_share %d env_lds %d env_off_tab %d | sums_mode %d first_obs %d reset_launches %d\n",
+                f.res, f.block, f.gl, f.rec_il, f.target_chunk, f.lf_cap, f.lds_bytes, f.envw, f.env_wpe, f.env_split, f.env_fused, f.env_share,
+                f.env_lds, f.env_off_tab, h->p.sums_mode, h->plan.first_obs, h->plan.reset_launches);
     }
     *out = owner.release();
     return 0;

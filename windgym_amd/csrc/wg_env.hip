@@ -9,7 +9,8 @@
 // cfg4), every turbine-indexed phase runs once for all of them, the candidate pairs and ring quads of all stepping slots
 // share one work list each, and the turbine state of an env is ONE contiguous run of lanes in every array (slot-major
 // layout: slot_id * N + t = env * 2 F N + lane).  The wave owns the whole env, so the env's glue can follow in the same
-// wave (k_step_env below: step() as one launch, no cross-workgroup dependency).
+// wave (k_flow_env<., GLUE != 0> below: step() as one launch, no cross-workgroup dependency).  A background episode's two farms are
+// twins until its window fill starts: the wave develops the agent farm only and clones it (env_clone_dev, FlowP::env_share).
 //
 // Same state layout (interleaved packed record + 16-byte gather copy: FlowP::rec_il), same arithmetic per element and the
 // same summation orders as k_flow<64, NONE, false, NOISE, true> (GL): the two kernels are interchangeable launch by
@@ -94,6 +95,66 @@ __device__ __forceinline__ float env_slot_sums(const float v, const int N, const
     return __shfl(s, k << 5, 64);
 }
 
+// Shared development (FlowP::env_share).  The reference builds the baseline farm of a new episode as a twin of the agent farm —
+// same site and wind, the agent's initial yaws, fs_baseline.run(t_developed) like fs.run(t_developed), no controller during the
+// fill (Wind_Farm_Env.py:781-792) — and under steady inflow the flow step is deterministic: until the episode's window fill
+// starts the two farms are the same state, bit for bit.  So a developing context's baseline slot is PARKED (it takes no flow
+// step) while its agent slot still has development steps to take, and at the top of the round after the agent's last one the
+// agent slot is cloned into it, here: the context's compact ring extent (py + interleaved record: the farms of a context share
+// roff), the chain bounds and ring heads, the slot's clock words; the turbine registers follow in the caller.  Both farms then
+// take their own fill steps (their power sums differ: K > 1, noise).
+// Parked is a function of state words alone — the baseline slot has never stepped in this episode (istep == 0) and still has
+// its development to do, and so has its agent twin — so a checkpoint taken mid-development replays, and a baseline slot some
+// other kernel has partly developed simply develops on its own.  The accounting counters (part_count, flow_count, add_count)
+// are NOT cloned: they count work done.
+// ~6 of 4096 waves clone per launch, for the price of about one advection pass.  Inlined on purpose: as a call at the top of the
+// round loop (noinline, like the episode set-up) it made every value that lives across the loop compete for the callee-saved
+// registers — 1 to 7 VGPRs spilled in every step instantiation, reloaded inside the step's phases; inlined, the branch needs
+// registers only where few are live and the step kernels keep 0 spilled VGPRs (profiles/r13_share_dev_kres.txt).
+// kd: the baseline slot of the wave (its agent twin: kd - 1); src / dst: the two slots' particle offsets in the env's block.
+static __device__ __forceinline__ void env_clone_dev(char* const smem, const int kd, const int N, const int P, const double dt_d,
+                                                               float* const py_env, unsigned* const ra_env, const unsigned src,
+                                                               const unsigned dst, const int lane) {
+    float4* const Lsrc4 = reinterpret_cast<float4*>(smem + WG_ENV_OFF_SRC4);
+    int4* const Lring = reinterpret_cast<int4*>(smem + WG_ENV_OFF_RING);
+    float2* const Lsrc2 = reinterpret_cast<float2*>(smem + WG_ENV_OFF_SRC2);
+    EnvSlotLds* const SL = reinterpret_cast<EnvSlotLds*>(smem + WG_ENV_OFF_SL);
+    const int ga = (kd - 1) * N, gb = kd * N;
+    const int4 last = Lring[ga + N - 1];
+    const int nq = (last.x + last.y) >> 2;                  // quads of the context's ring extent (roff[N]; every R_t is a multiple of 4)
+    {
+        const float4* const ps = reinterpret_cast<const float4*>(py_env + src);
+        float4* const pd = reinterpret_cast<float4*>(py_env + dst);
+        const uint4* const rs = reinterpret_cast<const uint4*>(ra_env + 2 * (size_t)src);
+        uint4* const rd = reinterpret_cast<uint4*>(ra_env + 2 * (size_t)dst);
+#pragma unroll 2
+        for (int q = lane; q < nq; q += 64) {
+            const float4 y = ps[q];
+            const uint4 r0 = rs[q], r1 = rs[q + nq];
+            pd[q] = y; rd[q] = r0; rd[q + nq] = r1;
+        }
+    }
+    if (lane < N) {      // chain bounds (positions are the context's: equal already), excursion bound + last moving emission, ring head
+        Lsrc4[gb + lane] = Lsrc4[ga + lane];
+        Lsrc2[gb + lane] = Lsrc2[ga + lane];
+        Lring[gb + lane].z = Lring[ga + lane].z;
+    }
+    if (lane == 0) {
+        const EnvSlotLds& a = SL[kd - 1];
+        EnvSlotLds& b = SL[kd];
+        b.n_valid = a.n_valid; b.n_emitted = a.n_emitted; b.s_off = a.s_off;
+        b.dev_rem = 0; b.sub = 0;
+        b.budget = a.budget;                                // (the rounds this launch still has: the two farms fill side by side)
+        // what the epilogue adds this launch's own steps to (time: the same chain of additions the agent slot's clock took)
+        double tm = a.c_time;
+        for (int i = 0; i < a.n_flow; ++i) tm += dt_d;
+        b.c_time = tm;
+        int hd = a.c_head + (int)((a.n_emitted - a.n_emitted0) % (unsigned)P); if (hd >= P) hd -= P;
+        b.c_head = hd; b.n_emitted0 = a.n_emitted;
+        b.c_istep = a.c_istep + (unsigned)a.n_flow;
+    }
+}
+
 // WPE = waves per env.  1: one wave serves all 2 F slots of the env (lane = slot * N + turbine).  2: a workgroup of two waves
 // per env, wave c serves the F slots of context c (lane = farm * N + turbine) in its own LDS region — the running episode's
 // step and the background episode's development then run side by side instead of one after the other, and the rare long
@@ -145,6 +206,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
     typedef const __attribute__((address_space(4))) WgEnv* CEnvPtr;
     int env_live;
     bool role_live = false, role_dev = false, defer_init = false, split_on = false;
+    bool parked = false;      // (shared development, env_clone_dev) this lane's baseline slot waits for its agent twin's development
     float yaw, tu, tti, oyaw;
     {
         const KArgsPtr k0 = wg_cold_args();
@@ -252,6 +314,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         const bool is_live_c = (c == env_live);
         const int autoreset = k0->p.autoreset;
         int budget = 0;
+        long plan_left = 0;      // env steps the background plan spreads its work over (STEP mode)
         if (mode == WG_MODE_STEP) {
             role_live = is_live_c && !env_done;
             role_dev = !is_live_c && autoreset != 0;
@@ -285,6 +348,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 // until the kernel has been measured without it.)
                 budget = wg_shadow_share(dev0 + gp.K * fill_max, total - env_steps_done, env_steps_done, e);
                 budget = wg_shadow_share(dev_rem + gp.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u);
+                plan_left = total - env_steps_done;
             } else {
                 // The background episode's share of this step, planned per FARM: the flow steps its farm still needs over the env
                 // steps left (wg_shadow_share: dithered, so the expected share is exact), the baseline farm's dither half a period
@@ -294,15 +358,32 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 const int inc = k0->p.env_inc;
                 const long total = (long)((env_time_max_live + inc - 1) / inc) + 1;
                 budget = role_dev ? wg_shadow_share(dev_rem + k0->p.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u) : 0;
+                plan_left = total - env_steps_done;
             }
         } else {
             role_dev = is_live_c && !masked_out;
             budget = chunk;
         }
+        bool clone_here = false;      // (an agent-farm lane) its slot can finish its development in this launch with its twin parked
+        if (k0->p.env_share) {
+            // Shared development (env_clone_dev).  A baseline slot that has never stepped in this episode is parked while its agent
+            // twin develops; that one's share covers the critical path meanwhile: its own development, then the longer of the two
+            // fills — the baseline's only starts at the clone.  After the clone each farm plans from its own remaining work, as
+            // before.  (F = 2: the twin's lanes are N lanes away; the words are the ones the prologue loaded.)
+            const int dev_a = __shfl(dev_rem, (tid - N) & 63, 64);
+            parked = valid && role_dev && farm == 1 && dev_rem > 0 && c_istep == 0u && dev_a > 0;
+            const int twin_fill = __shfl(parked ? fill_rem + 1 : 0, (tid + N) & 63, 64);      // (agent lanes) > 0: the twin is parked; its fill steps + 1
+            const bool lead = valid && role_dev && farm == 0 && twin_fill > 0;
+            if (lead && mode == WG_MODE_STEP && !defer_init)
+                budget = wg_shadow_share(dev_rem + k0->p.K * max(fill_rem, twin_fill - 1), plan_left, env_steps_done, e);
+            if (parked) budget = 0;      // (it gets what is left of its twin's at the clone)
+            clone_here = lead && budget >= dev_rem;
+        }
         if (SPLIT) {
             // exactly one flow step for every slot of the wave that steps at all, no episode set-up in this launch
             const bool two = valid && role_dev && budget >= 2;
-            split_on = mode == WG_MODE_STEP && k0->p.K == 1 && (is_live_c || (SPLIT == 2 && !out.bg_init_pending)) && !defer_init && !__ballot(two);
+            split_on = mode == WG_MODE_STEP && k0->p.K == 1 && (is_live_c || (SPLIT == 2 && !out.bg_init_pending)) && !defer_init && !__ballot(two) &&
+                       !__ballot(clone_here);      // (the clone copies what the pass of this very launch stores: one wave does both)
             if (role == 1 && !split_on) return;
         }
         if (WPE == 2 && valid && t == 0) {      // (what the other wave's glue reads of this one, also if it has nothing to do)
@@ -388,6 +469,29 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
     for (int round = 0;; ++round) {
         bool stepping, is_dev;
         int sub, K;
+        if (__ballot(parked)) {
+            // shared development: the agent twin of a parked slot has taken its last development step -> clone it, before either
+            // farm takes a fill step (rare: once per episode and env)
+            bool due = parked && SL[k - 1].dev_rem == 0;      // (parked: farm 1, so k >= 1)
+            unsigned long long due_m = __ballot(due);
+            if (due_m) {
+                full_barrier<64>();      // the agent slot's last pass has left the wave
+                const KArgsPtr kc = wg_cold_args();
+                const unsigned pstride = (unsigned)kc->p.pstride;
+                const size_t pb_env = (size_t)(e * 2 * F + kbase) * pstride;
+                const int src_lane = (tid - N) & 63;
+                const float c_tu = __shfl(tu, src_lane, 64), c_tti = __shfl(tti, src_lane, 64), c_pw = __shfl(tpow, src_lane, 64);
+                const float c_ct = __shfl(tct, src_lane, 64), c_cg = __shfl(cg, src_lane, 64);
+                if (due) { tu = c_tu; tti = c_tti; tpow = c_pw; tct = c_ct; cg = c_cg; stepped = true; parked = false; }
+                while (due_m) {
+                    const int kd = __builtin_amdgcn_readlane(k, __builtin_ctzll(due_m));
+                    env_clone_dev(smem, kd, N, kc->p.P, kc->p.dt_d, kc->d.py + pb_env, kc->d.rec_a + 2 * pb_env, (unsigned)(kd - 1) * pstride,
+                                  (unsigned)kd * pstride, tid);
+                    due_m &= ~(((1ull << N) - 1ull) << (kd * N));
+                }
+                lds_barrier<64>();
+            }
+        }
         {
             const KArgsPtr kr = wg_cold_args();
             K = kr->p.K;

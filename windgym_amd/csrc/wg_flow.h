@@ -59,6 +59,9 @@ struct FlowP {
     int env_inc;                      // env time steps per step(): 1 + extra_timestep_inc (the background plan's steps left)
     float env_eps_max;                // widest initial wake width a record can hold: min(1, eps0 sqrt(beta(ct = 0.96)))
     float dt, D, inv_D, hub, dpart_f, R_rot, inv_N, inv_S, inv_P;
+    int env_share;                    // k_flow_env, F = 2: a developing episode's baseline farm is parked and cloned from its agent twin when that
+                                      // one's development steps are done (wg_env.hip; WG_ENV_SHARE_DEV).  (In what was padding in front of the
+                                      // doubles: no other member moves.)
     double dt_d, dpart, inv_dpart;
     float yaw_min, yaw_max, yaw_step;
     float ka, kb, eps0, hill, tia, tib, tic, tid;

@@ -21,7 +21,7 @@ struct WgHookInt {
     int v = 0;      // atoi of the variable's text
 };
 struct WgHooks {
-    WgHookInt flow_block, flow_res, flow_env, env_wpe, env_split, step_fused, sums, lds_pad, lf_cap, pstride_pad, step_graph;
+    WgHookInt flow_block, flow_res, flow_env, env_wpe, env_split, step_fused, sums, lds_pad, lf_cap, pstride_pad, step_graph, share_dev;
     bool first_obs_gl_only = false, no_box8 = false, debug = false, timeline = false;
     std::string timeline_out;
 };
@@ -446,6 +446,13 @@ inline void wg_plan_step_kernels(const wg_config* c, const WgHooks& hk, const Wg
     f.env_split = (split_ok && p.B <= 1024 && qf >= 256) ? (p.B <= 512 ? 2 : 1) : 0;
     if (hk.env_split.set) f.env_split = (hk.env_split.v != 0 && split_ok && p.B <= 2048) ? (hk.env_split.v == 2 ? 2 : 1) : 0;
     if (envb_ok) f.env_wpe = envb_wpe;
+    // Shared development (wg_env.hip): until a background episode goes live its baseline farm is a bit-for-bit twin of its agent
+    // farm (same wind, the agent's initial yaws, no controller during development), so k_flow_env develops the agent slot alone
+    // and clones it — 14 % of cfg2's farm flow-steps.  Only that kernel knows how (k_flow_envb and the per-slot kernels develop
+    // both farms), and only a handle with a baseline farm has anything to share; a flow script never reaches the env kernels
+    // (wg_launch_flow).  WG_ENV_SHARE_DEV=0: both farms develop, for A/B runs and the tests that compare the two.
+    f.env_share = (f.envw && env_ok && p.F == 2) ? 1 : 0;
+    if (hk.share_dev.set && hk.share_dev.v == 0) f.env_share = 0;
     // one launch per step where the env kernel runs and the lean glue's specialised instantiation applies
     const bool gen = p.turb_ti || p.farm_ti || p.farm_obs > 0 || (p.sum_mask_f | p.cur_mask_f) != 0;
     f.env_fused = (f.envw && p.sums_mode && !gen && p.power_avg <= 64) ? 1 : 0;
