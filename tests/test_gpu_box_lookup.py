@@ -258,7 +258,7 @@ def _cfg5_shape(turbtype, B):
 @pytest.mark.parametrize("block", BLOCKS)
 @pytest.mark.parametrize("cells", list(BIG))
 def test_rotor_winds_per_slot_kernels_bricks_match_float64_oracle(hip, oracle_lib, noise, cells, block):
-    """k_flow<64 / 128 / 256, BOX>: rotor points through box_lookup (brick order, 64-bit offsets), particles through the block-averaged
+    """k_flow<64 / 256, BOX>: rotor points through box_lookup (brick order, 64-bit offsets), particles through the block-averaged
     meandering copy, wake-added turbulence through abox_lookup — 5 envs x 120 steps, every step, on white noise"""
     shape, spacing, turbtype = BIG[cells]
     B = 5

@@ -24,13 +24,14 @@ def hip():
     return binding
 
 
-# every k_flow variant the host can select (wg_flow.hip): one workgroup of 64 / 128 / 256 threads per farm slot
-BLOCKS = [64, 128, 256]
+# every k_flow variant the host can select for a small farm (wg_flow.hip's launch table): one workgroup per farm slot, 64 threads on
+# compact rings or 256 threads on uniform rings
+BLOCKS = [64, 256]
 # "env" = k_flow_env, one or two waves per env with lane = farm slot x turbine (small farms: what cfg2 / cfg4 run);
 # "env1" = the same kernel forced to ONE wave per env (WG_ENV_WPE=1: what a batch of more than 2048 envs runs — the headline)
 STEADY_BLOCKS = BLOCKS + ["env", "env1"]
 # frozen-box inflow: the per-slot instantiations and "envb" = k_flow_envb (wg_envb.hip), the one-launch env kernel cfg5 runs
-BOX_BLOCKS = BLOCKS + ["envb4", "envb", "envb1"]      # (four waves per env = one per farm slot: what cfg5 x 1024 runs; two; one)
+BOX_BLOCKS = BLOCKS + ["envb4", "envb", "envb1"]      # (four waves per env = one per farm slot: hook only, WG_ENV_WPE=4; two: what cfg5 x 1024 runs; one)
 
 
 def _make_env(hip, cfg, block=None):
@@ -143,7 +144,8 @@ def _compare_step(env, orc, a, step, check_flow=True, power_rtol=2e-4):
 @pytest.mark.parametrize("block", STEADY_BLOCKS)
 def test_hip_physics_matches_oracle_step_for_step(hip, oracle_lib, block):
     """cfg2-shaped farm (4x4, yaw action, two farms), B=6, 300 steps on identical seeds and actions — in each of the
-    three workgroup-size instantiations of k_flow (128 is what cfg2 / cfg4 run, 256 what cfg3 runs)."""
+    per-slot instantiations of k_flow a small farm can run (64 threads: the compact single-wave kernel, on whose state cfg2 / cfg4's
+    env kernel runs; 256: uniform rings) and in that env kernel at two waves and one wave per env."""
     B = 6
     cfg = _physics_cfg(B, autoreset=False, n_passthrough=5)
     env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)

@@ -102,12 +102,13 @@ def test_large_turbulent_farm_and_model_options(shim):
 def test_hooks(shim):
     c2, c3, c5 = (bench.make_cfg(n, workload=w) for n, w in ((1024, "cfg2"), (64, "cfg3"), (1024, "cfg5")))
     assert pick(shim(c2, flow_block=64), "res", "block", "gl", "envw") == (1, 64, 1, 0)
-    assert pick(shim(c2, flow_block=128), "res", "block", "gl", "rec_il", "envw") == (1, 128, 0, 0, 0)
+    # (128 threads is not built: the value is ignored like any unknown one — the no-hook variant, the env kernels off as for every set hook)
+    assert pick(shim(c2, flow_block=128), "res", "block", "gl", "rec_il", "envw") == pick(shim(c2), "res", "block", "gl", "rec_il") + (0,) == (1, 64, 1, 1, 0)
     assert pick(shim(c2, flow_block=256), "res", "block", "rec_il", "envw") == (0, 256, 0, 0)
     assert pick(shim(c2, flow_block=64, flow_env=1), "block", "envw") == (64, 1)
     assert pick(shim(c2, flow_res=0), "res", "block", "envw") == (0, 256, 0)
     assert pick(shim(c3, flow_res=0), "res", "block", "rec_il", "lf_cap") == (0, 256, 0, 0)
-    assert pick(shim(grid_cfg(8, 5, 64, "MannGenerate"), flow_res=1), "res", "block") == (1, 256)
+    assert pick(shim(grid_cfg(8, 5, 64, "MannGenerate"), flow_res=1), "res", "block") == (0, 256)      # (no compact kernel for large turbulent farms)
     assert pick(shim(c2, flow_env=0), "envw", "env_fused", "block", "gl") == (0, 0, 64, 1)
     assert pick(shim(c2, flow_env=1), "envw", "env_fused") == (1, 1)
     assert shim(c3, flow_env=1)["envw"] == 0              # (only where eligible)
@@ -141,7 +142,7 @@ def test_invariants_over_a_grid(shim):
             assert d[k] % 16 == 0, (k, d)
         assert d["lds_bytes"] <= lds and d["res"] == d["compact"]
         assert d["pstride"] >= d["NP"] and d["pstride"] % 64 == 0 and (d["pstride"] // 64) % 2 == 1
-        assert d["block"] in (64, 128, 256) and (d["res"] or d["block"] == 256)
+        assert d["block"] in (64, 256) and (d["res"] or d["block"] == 256)
         if d["envw"]:
             assert d["env_wpe"] * d["env_lds"] <= lds and d["env_lds"] <= 32768
             if d["env_split"]:      # what the pass-wave launch requests: the waves' regions + the pre-fetched glue inputs
@@ -154,6 +155,28 @@ def test_invariants_over_a_grid(shim):
         seen_fallback += small and d["res"] == 0          # res 1 did not fit: the uniform-ring carve
         seen_envb_stepdown += tt == "MannGenerate" and d["envw"] and B <= 2048 and d["env_wpe"] == 1
     assert seen_fallback and seen_refused and seen_envb_stepdown
+
+
+# wg_flow.hip's launch table: (threads, compact rings, turbulent inflow) of every k_flow that is built
+BUILT = {(64, 1, False), (64, 1, True), (256, 1, False), (256, 0, False), (256, 0, True)}
+
+
+def test_no_hook_names_a_kernel_that_is_not_built(shim):
+    """The grid of test_invariants_over_a_grid x WG_FLOW_BLOCK x WG_FLOW_RES: every accepted plan is a row of the launch table."""
+    layouts = [(1, 1), (2, 2), (4, 4), (5, 5), (6, 5), (8, 5), (10, 8), (12, 10)]
+    n_plans = 0
+    for (nx, ny), P, S, f2, B, tt, lds in itertools.product(layouts, (None, 128, 8192), (4, 16, 64), (True, False), (24, 1024, 4096),
+                                                            ("None", "Random", "MannGenerate"), (65536, 32768)):
+        cfg = grid_cfg(nx, ny, B, tt, farms2=f2, n_rotor_pts=S, **({"n_particles": P} if P else {})).to_c()
+        for fb, fr in itertools.product((None, 64, 128, 256), (None, 0, 1)):
+            hooks = {k: v for k, v in (("flow_block", fb), ("flow_res", fr)) if v is not None}
+            d = shim(cfg, lds_limit=lds, **hooks)
+            if d["rc"]:
+                continue
+            n_plans += 1
+            assert (d["block"], d["res"], tt != "None") in BUILT, (nx, ny, P, S, f2, B, tt, lds, hooks, pick(d, "block", "res"))
+            assert d["rec_il"] == (d["res"] and tt == "None") and d["gl"] == (d["rec_il"] and d["block"] == 64)
+    assert n_plans > 20000
 
 
 def test_envb_wave_count_steps_down_with_the_lds(shim):

@@ -25,6 +25,9 @@ B = int(sys.argv[3]) if len(sys.argv) > 3 else 48
 steps = int(sys.argv[4]) if len(sys.argv) > 4 else 500
 cfg = bench.make_cfg(B, autoreset=True, farms2=True, workload=wl)
 env = binding.HipBatch(cfg, device=0)
+if wl == "cfg5":      # frozen-box inflow: a box made on the host, the same under every build
+    from windgym_amd.mann import generate_mann_box
+    env.set_turbulence_box(generate_mann_box((256, 64, 32), (3.0, 3.0, 3.0), seed=1234), (3.0, 3.0, 3.0))
 obs0 = env.reset(seeds=7 + np.arange(B))
 gen = torch.Generator(device="cpu").manual_seed(3)
 acts = (torch.rand((16, B, cfg.n_turb), generator=gen) * 2 - 1).to("cuda").contiguous()

@@ -5,18 +5,12 @@
 #ifndef WG_BOX_WAVES
 #define WG_BOX_WAVES 2    // turbulent variants: measured best with the full register budget (no spills, deeper gather ILP)
 #endif
-#ifndef WG_FLOW_WAVES_128
-#define WG_FLOW_WAVES_128 6   // 128-thread variants stream one quad per lane at a time (QB = 1): 80 VGPRs, 6 waves/SIMD
-#endif
-#ifndef WG_FLOW_WAVES_CG
-#define WG_FLOW_WAVES_CG 5    // small-farm variants (compact rings, 64 / 128 threads): 96 VGPRs; measured 4 / 5 / 6 waves: 104 / 93.5 / 96 us on cfg2
-#endif
 #ifndef WG_FLOW_WAVES_GL
 #define WG_FLOW_WAVES_GL 4    // single-wave steady variant (GL): 128 VGPRs, no spills — room for the pipelined advection pass's second quad;
                               // 4 vs 5 waves per SIMD measured equal without the pipeline (the launch is not occupancy-bound), -4.5 % with it
 #endif
 #ifndef WG_FLOW_WAVES
-#define WG_FLOW_WAVES 5   // min waves/SIMD the register allocator must leave room for (5 -> <= 96 VGPRs; measured best)
+#define WG_FLOW_WAVES 5   // uniform-ring variant, steady inflow: min waves/SIMD the register allocator must leave room for (5 -> <= 96 VGPRs; measured best)
 #endif
 #ifndef WG_FLOW_WAVES_LF
 #define WG_FLOW_WAVES_LF 3  // 256-thread compact steady variant (large farms): built at 3 waves per SIMD (168 VGPRs, nothing spilled):
@@ -35,14 +29,15 @@
 struct FlowP {
     int B, N, F, K, P, S, S_pad, S_shift, NP, n_tab;
     int autoreset, action_method, base_controller, power_avg, script_rows, noise;
-    int block;                    // threads per workgroup: 64, 128 or 256
-    int res;                      // 1: compact per-turbine rings + pair-major deficit phases (small farms), 0: legacy streaming variant
+    int block;                    // threads per workgroup: 64 or 256
+    int res;                      // 1: compact per-turbine rings + pair-major deficit phases (small farms at 64 threads; large steady ones at 256),
+                                  // 0: uniform rings, sample-major phases (256 threads) — the three rows of wg_flow.hip's launch table
     int pstride;                  // floats between the particle blocks of consecutive farm slots (>= NP, see wg_create)
     int target_chunk;             // targets whose pair parameters are staged in LDS at once
     int lf_cap;                   // large-farm steady variant (lf_pair_phase): candidates whose results fit the staging region at once
     int lds_off_turb, lds_off_tab, lds_bytes;
     int rec_il;                   // the packed emission record is ONE interleaved array (rec_a[2 i] = ct|k, rec_a[2 i + 1] = u_e|hv; rec_b = rec_a + 1):
-                                  // steady compact handles (GL / k_flow_env, LF) — a bracket pair is 16 contiguous bytes of the array
+                                  // compact and steady handles (GL / k_flow_env, LF) — a bracket pair is 16 contiguous bytes of the array
                                   // the advection pass streams, an emission writes one sector
     int gl;                       // the launch runs the GL variant of k_flow (LDS-DMA gathers; no per-target source masks in LDS)
     int lds_off_ql, lds_off_gat;  // single-wave steady compact variant: quad list of its own (0 = aliases the pair staging) and the

@@ -1,6 +1,6 @@
 // wg_flow.hip — k_flow, the dominant kernel of libwindgym_hip.so (gfx950, wave64).
 //
-// One workgroup per farm slot (env x ctx x farm); 64 / 128 / 256 threads chosen on the host from N x P (k_flow<NT,...>:
+// One workgroup per farm slot (env x ctx x farm); 64 or 256 threads chosen on the host from N x P (k_flow<NT,...>:
 // each size has its own tuning — quads in flight per lane, occupancy target, record layout for the deficit gathers,
 // chain pruning).  Which slot a workgroup serves is a hashed / reordered function of blockIdx (see k_flow) so that
 // live farms and background episodes are spread over all XCDs, shader engines and CUs.  Per flow step it
@@ -24,6 +24,8 @@
 #include "wg_flow_dev.h"
 #include "wg_box_dev.h"
 #include "wg_internal.h"
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 
 struct __attribute__((aligned(8))) TurbLds {
@@ -54,12 +56,15 @@ struct SlotRegs {
 // A farm's particle state in the compact-ring layout (small farms): SoA over the concatenated per-turbine rings of
 // the farm slot, in global memory
 struct PartLds {
-    float* py; unsigned* ra; unsigned* rb;      // (interleaved record, FlowP::rec_il: rb == ra + 1 and particle i's words are ra[2 i], ra[2 i + 1])
+    float* py; unsigned* ra; unsigned* rb;      // (steady inflow: ONE interleaved record, FlowP::rec_il — rb == ra + 1 and particle i's words are ra[2 i], ra[2 i + 1])
     float *pz, *vl, *wl;        // turbulent inflow only
     const uint8_t* own;         // [L/4] owner turbine of a quad
     int L;                      // ring slots of the farm = roff[N]
     int il;                     // 1: interleaved record
     // the packed emission record (rec_a, rec_b) of ring slot i, whichever way it is stored
+    // (a run-time select although each caller's variant fixes it — LF: interleaved, turbulent: two arrays.  Reading the record
+    // without it moved the register allocation of the turbulent variants: scratch 196 -> 244 bytes on <64, Random, deficit
+    // model 2>, spilled VGPRs 8 -> 10 on <64, box, NOISE, 1> — EXPERIMENTS.md)
     __device__ __forceinline__ uint2 rec(const int i) const {
         return il ? *reinterpret_cast<const uint2*>(ra + 2 * i) : make_uint2(ra[i], rb[i]);
     }
@@ -100,6 +105,9 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                                           const size_t pbase, const double ws,
                                           const float ti_f, const float ti_pow, const TurbCtx& tc, SlotRegs& sr,
                                           const PartLds& pl, const bool first_step, int& add_acc) {
+    // the variants that exist (wg_launch_flow's table; wg_plan_flow_variant names no other):
+    //   GL  <64, compact, steady>   LF  <256, compact, steady>   <64, compact, Random / box>   <256, uniform rings, any inflow>
+    static_assert(RES ? (NT == WG_WAVE || (NT == 256 && TURB == WG_TURB_NONE)) : NT == 256, "k_flow: not a variant of the launch table");
     const int tid = threadIdx.x;
     const int N = p.N, P = p.P;
     if (RES) __builtin_assume(N <= NT);
@@ -115,10 +123,15 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
     int new_valid = n_valid + n_emit; if (new_valid > P) new_valid = P;
     const float s_off_f = (float)sr.s_off;
 
+    // PRE: the steady compact variants, GL (one wave) and LF (256 threads) — their deficit phase runs on the PRE-step particle
+    // state, before the advection pass, and their record is ONE interleaved array (FlowP::rec_il, set by the host for exactly
+    // these): a bracket pair is 16 contiguous bytes of the array the advection pass streams
+    constexpr bool PRE = RES && TURB == WG_TURB_NONE;
+    constexpr bool GL = PRE && NT == WG_WAVE;
+    constexpr bool LF = PRE && NT == 256;
     // staging of the compact variants' deficit phases (the `pair` region, per chunk of TC targets):
     // cl[TC*N] u16 candidate list | def[TC*N] rotor-mean deficit | tiav[TC*N] added TI
     // (LF, the large-farm steady variant: staged per candidate, see lf_pair_phase)
-    constexpr bool LF = NT == 256 && RES && TURB == WG_TURB_NONE;
     unsigned short* cl = LF ? reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(pair) + WG_LF_OFF_CL(N)) : reinterpret_cast<unsigned short*>(pair);
     float* def = LF ? reinterpret_cast<float*>(reinterpret_cast<char*>(pair) + WG_LF_OFF_DEF(N)) : reinterpret_cast<float*>(cl + ((TC * N + 7) & ~7));
     float* tiav = LF ? def + p.lf_cap : def + TC * N;
@@ -136,11 +149,6 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
     // and quad list (LDS / ALU work, ~5 k cycles = one loaded round trip) -> the deficit evaluation reads the landed
     // words from LDS.  (The bounds are those BEFORE this step's records: they cover every particle already in the
     // rings; a pair close enough to be bracketed by a particle released in this step is a candidate unconditionally.)
-    constexpr bool PRE = RES && TURB == WG_TURB_NONE;
-    constexpr bool GL = PRE && NT == WG_WAVE;
-    // interleaved record array (FlowP::rec_il; the host sets it for exactly these variants): a bracket pair is 16 contiguous
-    // bytes of the array the advection pass streams
-    constexpr bool IL = GL || LF;
     const float ws_f = (float)ws;
     const float ue_max = p.ue_scale * ws_f, ue_inv = __builtin_amdgcn_rcpf(ue_max);      // (scale of the record's u_e field)
     float* gat = reinterpret_cast<float*>(reinterpret_cast<char*>(pair) + p.lds_off_gat);
@@ -370,7 +378,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                 }
                 if (ADDED) { addv[i] = a0_ * p.inv_S; addv[TC * N + i] = a1_ * p.inv_S; addv[2 * TC * N + i] = a2_ * p.inv_S; }
                 def[i] = acc_ * p.inv_S;
-                if (!GL && !LF) atomicOr(&tmask[tl * WG_MASK_WORDS + (s2 >> 5)], 1u << (s2 & 31));
+                if (!PRE) atomicOr(&tmask[tl * WG_MASK_WORDS + (s2 >> 5)], 1u << (s2 & 31));
                 return;
             }
             float nsg = 2.0f, cf;
@@ -435,19 +443,17 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                 }
             }
             def[i] = acc * p.inv_S;
-            if (!GL && !LF) atomicOr(&tmask[tl * WG_MASK_WORDS + (s2 >> 5)], 1u << (s2 & 31));
+            if (!PRE) atomicOr(&tmask[tl * WG_MASK_WORDS + (s2 >> 5)], 1u << (s2 & 31));
     };
-    // (3)+(4) rotor-averaged inflow of the compact variants, as a closure: the steady variant runs it BEFORE the advection
-    // pass (PRE), the turbulent ones after it.
-    // PRE (steady inflow): the bracketing particles are gathered in their PRE-step state and advanced by the same
-    // m0_advect() the advection pass applies (a particle's step is a function of its own record and age only; a particle
-    // emitted in this step is the turbine's record in LDS).  The phase then depends on nothing the advection pass writes:
-    // no wait for the pass's stores, the gathers are in flight before the streaming loads of the same lines (which then
-    // hit in L2 instead of the other way round, after L2 has lost them), and a live workgroup's latency chain is three
-    // memory round trips (state, gathers, stream) instead of five.
-    auto res_pair_phase = [&](auto pre_tag) __attribute__((always_inline)) {
-        constexpr bool PREV = decltype(pre_tag)::value;
-        const float move_max = fabsf(p.hill) * ws_f * p.dt;
+    // (3)+(4) rotor-averaged inflow of the turbulent compact variants (64 threads), as a closure: it runs AFTER the advection
+    // pass, on the particles the pass stored.
+    // (The steady variants, GL and LF, have phases of their own that run BEFORE the pass (PRE): the bracketing particles are
+    // gathered in their PRE-step state and advanced by the same m0_advect() the advection pass applies — a particle's step is
+    // a function of its own record and age only; a particle emitted in this step is the turbine's record in LDS.  Such a
+    // phase depends on nothing the advection pass writes: no wait for the pass's stores, the gathers are in flight before the
+    // streaming loads of the same lines (which then hit in L2 instead of the other way round, after L2 has lost them), and a
+    // live workgroup's latency chain is three memory round trips (state, gathers, stream) instead of five.)
+    auto res_pair_phase = [&]() __attribute__((always_inline)) {
         const float* xf_ = reinterpret_cast<const float*>(jnl + 2 * N + 4);
         const float* yf_ = xf_ + N;
         // small-farm variant: PAIR-major.  In a small farm only a few (target, source) pairs interact (the same
@@ -513,10 +519,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                 if (cand) {
                     const TurbLds& src = T[s2];
                     const float sig_max = (src.bk * (dxf * p.inv_D) + src.be) * p.D;
-                    // PRE: src.bd is the excursion bound BEFORE this step's advection; a particle moves by
-                    // |hv C| dt <= |hill| u_e dt <= |hill| U dt in one step (steady inflow: u_e <= U, C <= 1)
-                    const float bd = PREV ? src.bd + (src.mvl != 0u ? move_max : 0.f) : src.bd;
-                    const float gap = fabsf(yf_[tg] - yf_[s2]) - (p.R_rot + 5.0f * sig_max + bd);
+                    const float gap = fabsf(yf_[tg] - yf_[s2]) - (p.R_rot + 5.0f * sig_max + src.bd);
                     cand = gap <= 1.0e-3f * p.D;      // small margin for fp32 rounding of the bound itself
                 }
             }
@@ -570,41 +573,12 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             if (j < 0) { j = 0; wgt = 0.f; }
             if (j + 1 > new_valid - 1) continue;          // the chain has not reached the target yet
             const int Rs = src.rlen;
-            float py0, py1, pz0 = 0.f, pz1 = 0.f;
-            unsigned a0, a1, b0_, b1_;
-            if (PREV) {
-                // ages j, j + 1 after the step are ages jp, jp + 1 = j - n_emit, ... before it (negative: released in this
-                // step — the turbine's record, at the turbine)
-                const int jp0 = j - n_emit, jp1 = jp0 + 1;
-                int r0 = src.head - jp0; if (r0 < 0) r0 += Rs;
-                int r1 = src.head - jp1; if (r1 < 0) r1 += Rs;
-                if (jp0 < 0) r0 = 0;      // (released in this step: nothing to fetch — any slot of the ring will do)
-                if (jp1 < 0) r1 = 0;
-                const int i0 = src.roff + r0, i1 = src.roff + r1;
-                const bool g0 = jp0 >= 0, g1 = jp1 >= 0;
-                py0 = py1 = (float)src.yr;
-                a0 = a1 = pack_a(src.rct, src.rk); b0_ = b1_ = pack_b(src.rue * ue_inv, src.rhv);
-                {
-                    // (both brackets requested together, whether needed or not — i0 / i1 are valid ring slots either way:
-                    // loads under `if (g0)` / `if (g1)` came out as two round trips, one behind the other)
-                    const uint2 q0 = pl.rec(i0), q1 = pl.rec(i1);
-                    const float y0l = pl.py[i0], y1l = pl.py[i1];
-                    if (g0) { a0 = q0.x; b0_ = q0.y; py0 = y0l; }
-                    if (g1) { a1 = q1.x; b1_ = q1.y; py1 = y1l; }
-                }
-                if (g0 && jp0 < n_valid) py0 = m0_advect(py0, a0, b0_, jp0, s_off_f, p.dpart_f, p.inv_D, p.dt, p.eps0);
-                if (g1 && jp1 < n_valid) py1 = m0_advect(py1, a1, b1_, jp1, s_off_f, p.dpart_f, p.inv_D, p.dt, p.eps0);
-            } else {
-                int r0 = src.head_n - j; if (r0 < 0) r0 += Rs;
-                int r1 = r0 - 1; if (r1 < 0) r1 += Rs;
-                const int i0 = src.roff + r0, i1 = src.roff + r1;
-                py0 = pl.py[i0]; py1 = pl.py[i1];
-                if (TURB != WG_TURB_NONE) { pz0 = pl.pz[i0]; pz1 = pl.pz[i1]; }
-                {
-                    const uint2 g0 = pl.rec(i0), g1 = pl.rec(i1);
-                    a0 = g0.x; b0_ = g0.y; a1 = g1.x; b1_ = g1.y;
-                }
-            }
+            int r0 = src.head_n - j; if (r0 < 0) r0 += Rs;
+            int r1 = r0 - 1; if (r1 < 0) r1 += Rs;
+            const int i0 = src.roff + r0, i1 = src.roff + r1;
+            const float py0 = pl.py[i0], py1 = pl.py[i1], pz0 = pl.pz[i0], pz1 = pl.pz[i1];
+            const uint2 g0 = pl.rec(i0), g1 = pl.rec(i1);
+            const unsigned a0 = g0.x, b0_ = g0.y, a1 = g1.x, b1_ = g1.y;
             eval_pair(i, tl, s2, t, dx, wgt, py0, py1, pz0, pz1, a0, a1, b0_, b1_);
         }
         lds_barrier<NT>();
@@ -659,7 +633,8 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             const int sb = wv % nsb, s2 = 64 * sb + lane;
             const bool sv = s2 < N;
             const TurbLds& src = T[sv ? s2 : 0];
-            // PRE: src.bd is the excursion bound BEFORE this step's advection (see res_pair_phase)
+            // PRE: src.bd is the excursion bound BEFORE this step's advection; a particle moves by
+            // |hv C| dt <= |hill| u_e dt <= |hill| U dt in one step (steady inflow: u_e <= U, C <= 1)
             const float bd = src.bd + (src.mvl != 0u ? move_max : 0.f);
             const float sx = xf_[sv ? s2 : 0], sy = yf_[sv ? s2 : 0], sz = 5.0f * src.bk;
             const float sw = p.R_rot + 5.0f * src.be * p.D + bd + 1.0e-3f * p.D;
@@ -788,11 +763,11 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
         }
         lds_barrier<NT>();
     };
-    if (PRE && !GL) {
+    if constexpr (LF) {
         // (a further flow step of the same launch — background development, reset — gathers what the previous step's
         // advection pass stored)
         if (!first_step) full_barrier<NT>();
-        if constexpr (LF) lf_pair_phase(); else res_pair_phase(std::true_type{});
+        lf_pair_phase();
         WG_STAMP(9);
     }
 
@@ -812,144 +787,85 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
         // and whether a chain does is known WITHOUT reading it: TurbLds::mvl remembers the emission count at the
         // chain's last moving emission, and that particle is still in the ring while fewer than R_t particles
         // followed it.  Pass A (LDS only): turbine t lists its quads — all of them if the chain may move, otherwise
-        // just the quads that receive this step's new particles.  Pass B: one listed quad per lane, its three words
+        // none: this step's new particles are stored straight to their slots.  Pass B: one listed quad per lane, its three words
         // (py, rec_a, rec_b) requested together — one memory round trip per 64 quads, none for a resting chain.
         // (16-bit list entries: turbine << ql_shift | quad index inside the turbine's ring; the host selects this variant
         // only where both fit)
         unsigned short* ql = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(pair) + (GL ? p.lds_off_ql : 0));
         const int qsh = p.ql_shift;
-        // (not GL: the same word serves as the candidate counter of the deficit phase, the list aliases its staging)
+        // (LF: the length of its list, in the word that is the turbulent variants' candidate counter; the list aliases the staging)
         int* nq = jnl + N + 1;
         // (2^lsh adjacent lanes share a turbine: the listing loop of a moving chain — up to P / 4 entries — is split
         // between them; the host chose lsh with N << lsh <= NT)
         const int lsh = p.ql_lpt_shift, lpt = 1 << lsh;
         const int t = tid >> lsh, kl = tid & (lpt - 1);
-        int gl_nlist = 0;
+        // Turbine t counts its quads — all of them if the chain may move, none if it rests — and the list positions come from a
+        // prefix sum over the turbines, not from an LDS counter: up to 40 lanes of a wave hitting ONE counter with atomicAdd
+        // are serialised one by one (LF), and the compiler orders an LDS atomic behind every pending LDS-DMA request
+        // (s_waitcnt vmcnt(0)), which would put the gathers' round trip back on the chain right here (GL).
+        int cnt = 0, nqd = 0;
+        bool full = false;
+        unsigned tag = 0u;
+        if (t < ((WG_ABLATE & 1) ? 0 : N)) {
+            const TurbLds& tq = T[t];
+            const int R = tq.rlen;
+            nqd = R >> 2;
+            const bool moving = tq.mvl != 0u && (int)(sr.n_emitted - tq.mvl) < R;
+            tag = (unsigned)t << qsh;
+            full = moving || n_emit >= 4 || n_emit >= R;
+            if (full) cnt = nqd;
+            else if (kl == 0) {
+                // A resting chain only receives this step's new particles (at most 3 here).  They are written straight to
+                // their ring slots — py and the interleaved record: two small stores per particle, no load —
+                // instead of listing their quads for the advection pass, which read-modify-writes whole quads (two or three
+                // lines fetched to change 28 bytes).  The slots hold the chain's oldest particles (pre-step ages >= R -
+                // n_emit), which no bracket of this step can touch, so the stores need not wait for the gathers in flight.
+                // (cfg3: +4 %, the baseline farms' workgroups are the tail of the launch and their pass was one exposed
+                // round trip)
+                const float y0 = (float)tq.yr;
+                const unsigned na = pack_a(tq.rct, tq.rk), nb = pack_b(tq.rue * ue_inv, tq.rhv);
+#pragma unroll
+                for (int e = 0; e < 3; ++e) {
+                    if (e < n_emit) {
+                        int r = tq.head + 1 + e; if (r >= R) r -= R;
+                        const int ix = tq.roff + r;
+                        pl.py[ix] = y0;
+                        reinterpret_cast<uint2*>(pl.ra)[ix] = make_uint2(na, nb);
+                    }
+                }
+            }
+        }
+        const int mine = kl == 0 ? cnt : 0;
+        int inc = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if ((tid & 63) >= o) inc += v; }
+        int gl_nlist = 0, base;
         if (GL) {
-            // single wave: list positions from a wave-level prefix sum, no LDS atomics — the compiler orders an LDS
-            // atomic behind every pending LDS-DMA request (s_waitcnt vmcnt(0)), which would put the gathers' round trip
-            // back on the chain right here
-            int cnt = 0, nqd = 0;
-            bool full = false;
-            unsigned tag = 0u;
-            if (t < ((WG_ABLATE & 1) ? 0 : N)) {
-                const TurbLds& tq = T[t];
-                const int R = tq.rlen;
-                nqd = R >> 2;
-                const bool moving = tq.mvl != 0u && (int)(sr.n_emitted - tq.mvl) < R;
-                tag = (unsigned)t << qsh;
-                full = moving || n_emit >= 4 || n_emit >= R;
-                if (full) cnt = nqd;
-                else if (kl == 0) {
-                    // A resting chain only receives this step's new particles (at most 3 here).  They are written straight to
-                    // their ring slots — py and the interleaved record: two small stores per particle, no load —
-                    // instead of listing their quads for the advection pass, which read-modify-writes whole quads (two or three
-                    // lines fetched to change 28 bytes).  The slots hold the chain's oldest particles (pre-step ages >= R -
-                    // n_emit), which no bracket of this step can touch, so the stores need not wait for the gathers in flight.
-                    const float y0 = (float)tq.yr;
-                    const unsigned na = pack_a(tq.rct, tq.rk), nb = pack_b(tq.rue * ue_inv, tq.rhv);
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) {
-                        if (e < n_emit) {
-                            int r = tq.head + 1 + e; if (r >= R) r -= R;
-                            const int ix = tq.roff + r;
-                            pl.py[ix] = y0;
-                            reinterpret_cast<uint2*>(pl.ra)[ix] = make_uint2(na, nb);
-                        }
-                    }
-                }
-            }
-            const int mine = kl == 0 ? cnt : 0;
-            int inc = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if ((tid & 63) >= o) inc += v; }
+            // single wave: the wave's scan is the whole prefix sum
             gl_nlist = __shfl(inc, 63, 64);
-            const int base = __shfl(inc - mine, (tid & 63) & ~(lpt - 1), 64);
-            if (full) {
-                for (int i = kl; i < nqd; i += lpt) ql[base + i] = (unsigned short)(tag | (unsigned)i);
-            }
-        } else if (LF) {
-            // large farms: list offsets from a prefix sum over the turbines (wave scans + the wave totals in jnl[0..3], which the
-            // compact variants do not use otherwise) — up to 40 lanes of a wave hitting ONE LDS counter with atomicAdd are
-            // serialised one by one
-            int cnt = 0, nqd = 0;
-            bool full = false;
-            unsigned tag = 0u;
-            if (t < ((WG_ABLATE & 1) ? 0 : N)) {
-                const TurbLds& tq = T[t];
-                const int R = tq.rlen;
-                nqd = R >> 2;
-                const bool moving = tq.mvl != 0u && (int)(sr.n_emitted - tq.mvl) < R;
-                tag = (unsigned)t << qsh;
-                full = moving || n_emit >= 4 || n_emit >= R;
-                if (full) cnt = nqd;
-                else if (kl == 0) {
-                    // (a resting chain only receives this step's new particles: stored straight to their ring slots, as in the
-                    // single-wave variant above — no load, no trip through the pass; cfg3: +4 %, the baseline farms' workgroups
-                    // are the tail of the launch and their pass was one exposed round trip)
-                    const float y0 = (float)tq.yr;
-                    const unsigned na = pack_a(tq.rct, tq.rk), nb = pack_b(tq.rue * ue_inv, tq.rhv);
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) {
-                        if (e < n_emit) {
-                            int r = tq.head + 1 + e; if (r >= R) r -= R;
-                            const int ix = tq.roff + r;
-                            pl.py[ix] = y0;
-                            reinterpret_cast<uint2*>(pl.ra)[ix] = make_uint2(na, nb);
-                        }
-                    }
-                }
-            }
-            const int mine = kl == 0 ? cnt : 0;
-            int inc = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if ((tid & 63) >= o) inc += v; }
+            base = __shfl(inc - mine, (tid & 63) & ~(lpt - 1), 64);
+        } else {
+            // 256 threads: wave scans + the wave totals in jnl[0..3], which the compact variants do not use otherwise
             if ((tid & 63) == 63) jnl[tid >> 6] = inc;
             lds_barrier<NT>();
             int woff = 0;
             for (int w = 0; w < (tid >> 6); ++w) woff += jnl[w];
             if (tid == NT - 1) *nq = woff + inc;
-            const int base = woff + __shfl(inc - mine, (tid & 63) & ~(lpt - 1), 64);
-            if (full) {
-                for (int i = kl; i < nqd; i += lpt) ql[base + i] = (unsigned short)(tag | (unsigned)i);
-            }
-        } else {
-        if (tid == 0) *nq = 0;
-        lds_barrier<NT>();
-        if (t < ((WG_ABLATE & 1) ? 0 : N)) {
-            const TurbLds& tq = T[t];
-            const int R = tq.rlen, nqd = R >> 2;
-            const bool moving = tq.mvl != 0u && (int)(sr.n_emitted - tq.mvl) < R;
-            const unsigned tag = (unsigned)t << qsh;
-            if (moving || n_emit >= 4 || n_emit >= R) {
-                int base = 0;
-                if (kl == 0) base = atomicAdd(nq, nqd);
-                base = __shfl(base, (tid & 63) & ~(lpt - 1), 64);
-                for (int i = kl; i < nqd; i += lpt) ql[base + i] = (unsigned short)(tag | (unsigned)i);
-            } else if (n_emit > 0 && kl == 0) {
-                int prev = -1;
-                for (int e = 0; e < n_emit; ++e) {
-                    int r = tq.head + 1 + e; if (r >= R) r -= R;
-                    const int qd = r >> 2;
-                    if (qd != prev) ql[atomicAdd(nq, 1)] = (unsigned short)(tag | (unsigned)qd);
-                    prev = qd;
-                }
-            }
+            base = woff + __shfl(inc - mine, (tid & 63) & ~(lpt - 1), 64);
         }
+        if (full) {
+            for (int i = kl; i < nqd; i += lpt) ql[base + i] = (unsigned short)(tag | (unsigned)i);
         }
         lds_barrier<NT>();
         WG_STAMP(10);
-        // pipelined advection (GLP): the loads of a lane's first listed quad are requested before the deficit evaluation
+        // pipelined advection.  GL: the loads of a lane's first listed quad are requested before the deficit evaluation
         // (its ~4 k cycles of ALU work hide their round trip), and inside the pass every lane requests its next quad
         // before it computes the current one (cfg2 k_flow 61.5 -> 58.8 us same box against the plain loop).  Costs 12 + 12
         // registers: this variant is built at 4 waves per SIMD.
-        // LFP, the 256-thread variant (large farms), requests its quads one ahead inside the pass only (cfg3 same-box: 0 / 1 / 2
+        // LF, the 256-thread variant (large farms), requests its quads one ahead inside the pass only (cfg3 same-box: 0 / 1 / 2
         // quads ahead = 3.80 / 4.04 / 3.93 M env-steps/s).  vmcnt counts loads and stores in ONE in-order queue: a plain
         // load-compute-store loop waits for the previous trip's stores whenever it waits for its loads — two round trips per
         // trip (cfg3: 20 trips of ~2 us).  Requested before the stores, the next quad's loads no longer queue behind them.
-        constexpr bool LFP = !GL && NT == 256;
-        constexpr bool GLP = GL || LFP;
-        const int nlist_pre = GL ? gl_nlist : 0;
         struct QuadReq { float4 py; uint4 ra, rb; int t, kq, q; };
         QuadReq nq_;      // the lane's next quad
         nq_.py = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -960,8 +876,9 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             r.t = (int)(ent >> qsh); r.kq = (int)(ent & ((1u << qsh) - 1u));
             r.q = valid ? (T[r.t].roff >> 2) + r.kq : 0;
             r.py = reinterpret_cast<const float4*>(pl.py)[r.q];
-            r.ra = reinterpret_cast<const uint4*>(pl.ra)[IL ? 2 * r.q : r.q];
-            r.rb = IL ? reinterpret_cast<const uint4*>(pl.ra)[2 * r.q + 1] : reinterpret_cast<const uint4*>(pl.rb)[r.q];
+            // (the quad's interleaved records: (a0 b0 a1 b1) (a2 b2 a3 b3))
+            r.ra = reinterpret_cast<const uint4*>(pl.ra)[2 * r.q];
+            r.rb = reinterpret_cast<const uint4*>(pl.ra)[2 * r.q + 1];
         };
         if (GL) {
             // deficit phase, part 2: the gathers issued before the records have landed (or do so now)
@@ -976,9 +893,9 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             const unsigned* gatu = reinterpret_cast<const unsigned*>(gat);
             uint2 g_q0 = make_uint2(gatu[l], gatu[64 + l]), g_q1 = make_uint2(gatu[128 + l], gatu[192 + l]);
             float g_py0 = gat[256 + l], g_py1 = gat[320 + l];
-            // (GLP: the first quad of the advection pass is requested now — its round trip runs under the deficit
+            // (the first quad of the advection pass is requested now — its round trip runs under the deficit
             // evaluation below)
-            adv_request_to(nq_, tid, tid < nlist_pre);
+            adv_request_to(nq_, tid, tid < gl_nlist);
             for (int c0 = 0; c0 < gl_nc; c0 += NT) {
                 const int c = c0 + tid;
                 if (c0 > 0) {      // (more than 64 candidates: not the common case) the next batch lands in the same words
@@ -1023,21 +940,12 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             WG_STAMP(9);
         }
         const int nlist = GL ? gl_nlist : *nq;
-        if (LFP) adv_request_to(nq_, tid, tid < nlist);
+        if (LF) adv_request_to(nq_, tid, tid < nlist);
         for (int c = tid; c < nlist; c += NT) {
-            int t, kq, q;
-            float4 py; uint4 ra, rb;
-            if (GLP) {
-                t = nq_.t; kq = nq_.kq; q = nq_.q; py = nq_.py; ra = nq_.ra; rb = nq_.rb;
-                if (c + NT < nlist) adv_request_to(nq_, c + NT, true);
-            } else {
-                const unsigned ent = ql[c];
-                t = (int)(ent >> qsh); kq = (int)(ent & ((1u << qsh) - 1u));
-                q = (T[t].roff >> 2) + kq;
-                py = reinterpret_cast<const float4*>(pl.py)[q];
-                ra = reinterpret_cast<const uint4*>(pl.ra)[IL ? 2 * q : q];
-                rb = IL ? reinterpret_cast<const uint4*>(pl.ra)[2 * q + 1] : reinterpret_cast<const uint4*>(pl.rb)[q];
-            }
+            const int t = nq_.t, kq = nq_.kq, q = nq_.q;
+            const float4 py = nq_.py;
+            const uint4 ra = nq_.ra, rb = nq_.rb;
+            if (c + NT < nlist) adv_request_to(nq_, c + NT, true);
             TurbLds& tq = T[t];
             const int R = tq.rlen, hd = tq.head;
             const int r0 = 4 * kq;
@@ -1045,9 +953,8 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             int e0 = r0 - hd - 1; if (e0 < 0) e0 += R;         // emission index of slot r0 (r0+i: e0+i)
             const bool emits = (e0 < n_emit) || (n_emit > 0 && e0 + 3 >= R);   // wraps past R-1 -> 0
             float pyv[4] = {py.x, py.y, py.z, py.w};
-            // (IL: `ra` / `rb` hold the quad's interleaved records (a0 b0 a1 b1) (a2 b2 a3 b3))
-            unsigned rav[4] = {ra.x, IL ? ra.z : ra.y, IL ? rb.x : ra.z, IL ? rb.z : ra.w};
-            unsigned rbv[4] = {IL ? ra.y : rb.x, IL ? ra.w : rb.y, IL ? rb.y : rb.z, rb.w};
+            unsigned rav[4] = {ra.x, ra.z, rb.x, rb.z};
+            unsigned rbv[4] = {ra.y, ra.w, rb.y, rb.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 int j = j0 - i; if (j < 0) j += R;
@@ -1062,13 +969,8 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
                         pyv[i] = y0; rav[i] = pack_a(tq.rct, tq.rk); rbv[i] = pack_b(tq.rue * ue_inv, tq.rhv);
                     }
                 }
-                if (IL) {
-                    reinterpret_cast<uint4*>(pl.ra)[2 * q] = make_uint4(rav[0], rbv[0], rav[1], rbv[1]);
-                    reinterpret_cast<uint4*>(pl.ra)[2 * q + 1] = make_uint4(rav[2], rbv[2], rav[3], rbv[3]);
-                } else {
-                    reinterpret_cast<uint4*>(pl.ra)[q] = make_uint4(rav[0], rav[1], rav[2], rav[3]);
-                    reinterpret_cast<uint4*>(pl.rb)[q] = make_uint4(rbv[0], rbv[1], rbv[2], rbv[3]);
-                }
+                reinterpret_cast<uint4*>(pl.ra)[2 * q] = make_uint4(rav[0], rbv[0], rav[1], rbv[1]);
+                reinterpret_cast<uint4*>(pl.ra)[2 * q + 1] = make_uint4(rav[2], rbv[2], rav[3], rbv[3]);
             }
             reinterpret_cast<float4*>(pl.py)[q] = make_float4(pyv[0], pyv[1], pyv[2], pyv[3]);
             // (excursion bound over the VALID particles of the quad only: a slot that holds no particle yet keeps whatever
@@ -1279,10 +1181,9 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
         //   stage 1: rec_b (eps|hv) of all QB quads -> which quads move (any hv != 0) or receive a new particle
         //   stage 2: py and rec_a (ct|k) of those quads -> all issued before the first use
         // A quad that neither moves nor emits costs only its rec_b read (4 B per particle).
-        // quads in flight per lane and occupancy are tuned together per workgroup size (measured, cfg2 / cfg3 / cfg4):
-        // 128 threads: QB = 1 at 6 waves/SIMD (80 VGPRs) beats QB = 2 at 5 waves (96 VGPRs) by 6 %; 256 threads (large
-        // farms, long streaming loops): QB = 2 at 5 waves is 8 % better; 64 threads: no difference
-        constexpr int QB = (NT == 128) ? 1 : 2;
+        // quads in flight per lane and occupancy were tuned together (measured, cfg3 — 256 threads, large farms, long streaming
+        // loops: QB = 2 at 5 waves/SIMD is 8 % better)
+        constexpr int QB = 2;
         const int stride = NT * 4;
         for (int b0 = tid * 4; b0 < p.NP; b0 += stride * QB) {
             uint4 rb[QB];
@@ -1363,7 +1264,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
             }
         }
     }
-    // (GLP: a wait the compiler's bookkeeping sees, right after the pipelined pass — the last trip's conditional request
+    // (GL: a wait the compiler's bookkeeping sees, right after the pipelined pass — the last trip's conditional request
     // otherwise stays "possibly pending" in its view around the flow-step loop and it orders the next step's register
     // writes behind it with vmcnt(0) waits that drain the LDS-DMA gathers)
     if (GL) wg_wait_vmem();
@@ -1374,7 +1275,7 @@ __device__ __forceinline__ void flow_step(const FlowP& p, const FlowPtrs& d, Tur
 
     // (3)+(4) rotor-averaged inflow
     if (RES) {
-        if (!PRE) res_pair_phase(std::false_type{});
+        if (!PRE) res_pair_phase();
         return;
     }
     for (int t0 = 0; t0 < ((WG_ABLATE & 2) ? 0 : N); t0 += TC) {
@@ -1562,7 +1463,7 @@ __device__ __forceinline__ void script_step(const FlowP& p, const FlowPtrs& d, T
     }())
 
 template <int NT, int TURB, bool REPLAY, bool NOISE, bool RES, int SGM = 0>
-__global__ void __launch_bounds__(NT, TURB != WG_TURB_NONE ? WG_BOX_WAVES : (RES ? (NT == WG_WAVE ? WG_FLOW_WAVES_GL : (NT == 256 ? WG_FLOW_WAVES_LF : WG_FLOW_WAVES_CG)) : WG_FLOW_WAVES))
+__global__ void __launch_bounds__(NT, TURB != WG_TURB_NONE ? WG_BOX_WAVES : (RES ? (NT == WG_WAVE ? WG_FLOW_WAVES_GL : WG_FLOW_WAVES_LF) : WG_FLOW_WAVES))
 k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict__ actions,
        const uint8_t* __restrict__ mask, const int chunk) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1750,7 +1651,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
     PartLds pl;
     if (RES) {
         pl.py = d.py + pbase;
-        if (p.rec_il) { pl.ra = d.rec_a + 2 * pbase; pl.rb = pl.ra + 1; }      // interleaved record (GL handles)
+        if (p.rec_il) { pl.ra = d.rec_a + 2 * pbase; pl.rb = pl.ra + 1; }      // interleaved record (steady handles: GL, LF)
         else { pl.ra = d.rec_a + pbase; pl.rb = d.rec_b + pbase; }
         pl.il = p.rec_il;
         pl.pz = TURB != WG_TURB_NONE ? d.pz + pbase : nullptr;
@@ -2012,42 +1913,49 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
 #endif
 }
 
-template <int NT, bool RES>
-static void launch_nt(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask,
-                      int chunk, hipStream_t st) {
+// The launch table: every k_flow that is built, and nothing a plan cannot name (wg_plan_flow_variant; tests/test_plan.py).
+//   NT   rings          inflow                instantiated over
+//   64   compact (RES)  None (GL), Random, box   NOISE x deficit model 0 / 1 / 2, + replay x NOISE
+//   256  compact (RES)  None only (LF)           NOISE x deficit model 0 / 1 / 2, + replay x NOISE
+//   256  uniform        None, Random, box        NOISE, + replay x NOISE
+// TURBULENT: the row has Random / box instantiations; DEFICITS: it has the super-Gaussian / eddy-viscosity ones.
+template <int NT, bool RES, bool TURBULENT, bool DEFICITS>
+static void launch_row(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask,
+                       int chunk, hipStream_t st) {
     const int grid = p->B * 2 * p->F;
     const size_t lds = p->lds_bytes;
     const bool replay = d->script_uvw != nullptr, noise = p->noise != 0;
-#define WG_LAUNCH(TURB, REPLAY, NOISE) \
-    hipLaunchKernelGGL((k_flow<NT, TURB, REPLAY, NOISE, RES>), dim3(grid), dim3(NT), lds, st, *p, *d, mode, actions, mask, chunk)
+#define WG_LAUNCH(TURB, REPLAY, NOISE, DM) \
+    hipLaunchKernelGGL((k_flow<NT, TURB, REPLAY, NOISE, RES, DM>), dim3(grid), dim3(NT), lds, st, *p, *d, mode, actions, mask, chunk)
+#define WG_LAUNCH_N(TURB, REPLAY, DM) do { if (noise) WG_LAUNCH(TURB, REPLAY, true, DM); else WG_LAUNCH(TURB, REPLAY, false, DM); } while (0)
     const int turb = (p->turb_mode >= WG_TURB_BOX) ? WG_TURB_BOX : p->turb_mode;
-    if constexpr (RES) {
-        if (p->deficit_model != 0 && !replay) {      // super-Gaussian / eddy-viscosity instantiations (compact variants only)
-#define WG_LAUNCH_DM(TURB, NOISE, DM) \
-    hipLaunchKernelGGL((k_flow<NT, TURB, false, NOISE, true, DM>), dim3(grid), dim3(NT), lds, st, *p, *d, mode, actions, mask, chunk)
-#define WG_LAUNCH_SG(TURB, NOISE) do { if (p->deficit_model == 1) WG_LAUNCH_DM(TURB, NOISE, 1); else WG_LAUNCH_DM(TURB, NOISE, 2); } while (0)
-            if (turb == WG_TURB_NONE) { if (noise) WG_LAUNCH_SG(WG_TURB_NONE, true); else WG_LAUNCH_SG(WG_TURB_NONE, false); }
-            else if (turb == WG_TURB_RANDOM) { if (noise) WG_LAUNCH_SG(WG_TURB_RANDOM, true); else WG_LAUNCH_SG(WG_TURB_RANDOM, false); }
-            else { if (noise) WG_LAUNCH_SG(WG_TURB_BOX, true); else WG_LAUNCH_SG(WG_TURB_BOX, false); }
-#undef WG_LAUNCH_SG
+    if (replay) { WG_LAUNCH_N(WG_TURB_NONE, true, 0); return; }      // replay mode ignores the physics
+    if constexpr (DEFICITS) {
+        if (p->deficit_model != 0) {
+#define WG_LAUNCH_DM(TURB) do { if (p->deficit_model == 1) WG_LAUNCH_N(TURB, false, 1); else WG_LAUNCH_N(TURB, false, 2); } while (0)
+            if (turb == WG_TURB_NONE) { WG_LAUNCH_DM(WG_TURB_NONE); return; }
+            if constexpr (TURBULENT) {
+                if (turb == WG_TURB_RANDOM) WG_LAUNCH_DM(WG_TURB_RANDOM); else WG_LAUNCH_DM(WG_TURB_BOX);
+                return;
+            }
 #undef WG_LAUNCH_DM
-            return;
         }
     }
-    if (replay) {                       // replay mode ignores the physics
-        if (noise) WG_LAUNCH(WG_TURB_NONE, true, true); else WG_LAUNCH(WG_TURB_NONE, true, false);
-    } else if (turb == WG_TURB_NONE) {
-        if (noise) WG_LAUNCH(WG_TURB_NONE, false, true); else WG_LAUNCH(WG_TURB_NONE, false, false);
-    } else if (turb == WG_TURB_RANDOM) {
-        if (noise) WG_LAUNCH(WG_TURB_RANDOM, false, true); else WG_LAUNCH(WG_TURB_RANDOM, false, false);
-    } else {
-        if (noise) WG_LAUNCH(WG_TURB_BOX, false, true); else WG_LAUNCH(WG_TURB_BOX, false, false);
+    if (turb == WG_TURB_NONE) { WG_LAUNCH_N(WG_TURB_NONE, false, 0); return; }
+    if constexpr (TURBULENT) {
+        if (turb == WG_TURB_RANDOM) WG_LAUNCH_N(WG_TURB_RANDOM, false, 0); else WG_LAUNCH_N(WG_TURB_BOX, false, 0);
+        return;
     }
+#undef WG_LAUNCH_N
 #undef WG_LAUNCH
+    // (a plan never asks the steady-only row for turbulent inflow: wg_plan_flow_variant)
+    fprintf(stderr, "wg_launch_flow: no k_flow<%d, %s> for turb_mode %d\n", NT, RES ? "compact" : "uniform", p->turb_mode);
+    abort();
 }
 
-// One workgroup per farm slot.  Small farms (N <= 32): compact per-turbine rings + pair-major deficit phases, 64 or 128
-// threads; large farms: uniform rings with predicate pruning + (target, sample)-major deficit phases, 256 threads.
+// One workgroup per farm slot.  Small farms (N <= 32): compact per-turbine rings + pair-major deficit phases, 64 threads;
+// large farms with steady inflow: the same at 256 threads; other large farms (and WG_FLOW_BLOCK=256 / WG_FLOW_RES=0):
+// uniform rings with predicate pruning + (target, sample)-major deficit phases, 256 threads.
 // Chosen on the host (FlowP.res / FlowP.block).
 extern "C" void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions,
                                const uint8_t* mask, int chunk, hipStream_t st) {
@@ -2056,13 +1964,9 @@ extern "C" void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, cons
         else wg_launch_flow_envb(p, d, mode, actions, mask, chunk, st);
         return;
     }
-    if (p->res) {
-        if (p->block == 64) launch_nt<64, true>(p, d, mode, actions, mask, chunk, st);
-        else if (p->block == 128) launch_nt<128, true>(p, d, mode, actions, mask, chunk, st);
-        else launch_nt<256, true>(p, d, mode, actions, mask, chunk, st);
-    } else {
-        launch_nt<256, false>(p, d, mode, actions, mask, chunk, st);
-    }
+    if (!p->res) launch_row<256, false, true, false>(p, d, mode, actions, mask, chunk, st);
+    else if (p->block == 64) launch_row<64, true, true, true>(p, d, mode, actions, mask, chunk, st);
+    else launch_row<256, true, false, true>(p, d, mode, actions, mask, chunk, st);
 }
 
 // ===================================================================================================

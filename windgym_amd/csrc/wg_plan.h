@@ -255,9 +255,10 @@ struct WgFlowVariant {
     int ql_shift, ql_lpt_shift;
 };
 
-// Kernel variant.  Small farms (N <= 32: all N x N pairs are staged at once): compact per-turbine rings +
-// pair-major deficit phases, single-wave workgroups (128 threads selectable for tests).  Large farms: uniform P-slot rings with
-// predicate pruning, (target, sample)-major deficit phases, 256 threads.
+// Kernel variant: one of the three rows of wg_flow.hip's launch table, (res, block) = (1, 64), (1, 256) or (0, 256) — no hook
+// names anything else (tests/test_plan.py).  Small farms (N <= 32: all N x N pairs are staged at once): compact per-turbine
+// rings + pair-major deficit phases, single-wave workgroups.  Large farms: the same at 256 threads for steady inflow, else
+// uniform P-slot rings with predicate pruning, (target, sample)-major deficit phases, 256 threads.
 inline WgFlowVariant wg_plan_flow_variant(const WgParams& p, const WgHooks& hk) {
     WgFlowVariant v;
     int tc = 1024 / p.N; if (tc < 1) tc = 1; if (tc > p.N) tc = p.N;
@@ -265,19 +266,14 @@ inline WgFlowVariant wg_plan_flow_variant(const WgParams& p, const WgHooks& hk) 
     v.tc0 = tc;
     v.small = p.N <= 32 && tc == p.N;
     v.res = v.small ? 1 : 0;
-    v.block = v.small ? 64 : 256;        // small farms: single-wave workgroups (no s_barrier at all): cfg2 80 vs 91 us at 128 threads
+    v.block = v.small ? 64 : 256;        // small farms: single-wave workgroups (no s_barrier at all): cfg2 80 vs 91 us at 128 threads (no longer built)
     // large farms with steady inflow: the compact / pair-major variant at 256 threads, pairs staged per chunk of
     // targets (cfg3: 206 vs 224 us once the candidate pre-check is tight — the compacted candidate list then holds
     // ~520 of the 6400 pairs, which the sample-major phases walk in full); turbulent large farms keep the legacy one
     if (!v.small && p.N <= 255 && p.turb_mode == WG_TURB_NONE) v.res = 1;
-    if (hk.flow_block.set) {       // tests: force an instantiation
-        const int b = hk.flow_block.v;
-        if (b == 256) { v.res = 0; v.block = 256; }
-        else if ((b == 64 || b == 128) && v.small) { v.res = 1; v.block = b; }
-    }
-    if (hk.flow_res.set) {          // experiments: compact / pair-major variant for any farm size
-        if (hk.flow_res.v != 0 && p.N <= 255) { v.res = 1; if (!v.small) v.block = 256; } else if (hk.flow_res.v == 0) { v.res = 0; v.block = 256; }
-    }
+    // tests: WG_FLOW_BLOCK=256 / WG_FLOW_RES=0 force the uniform-ring kernel.  WG_FLOW_BLOCK=64 is what a small farm runs anyway
+    // (set, it only switches the env kernels off: wg_plan_step_kernels); any other value names no kernel that is built: ignored.
+    if ((hk.flow_block.set && hk.flow_block.v == 256) || (hk.flow_res.set && hk.flow_res.v == 0)) { v.res = 0; v.block = 256; }
     // the compact steady advection lists (turbine, quad-in-ring) in 16 bits: both must fit, whatever the hooks ask for
     v.ql_shift = 0;
     while ((1 << v.ql_shift) < p.P / 4) ++v.ql_shift;
@@ -296,7 +292,8 @@ struct WgFlowCarve {
 // advection pass (one 16-bit entry per quad of the farm's rings: at most NP / 2 bytes).
 // Compact variant: the staging of a chunk of targets is 10 bytes per (target, source) pair (16-bit candidate
 // list, deficit, added TI) and the per-pair added-TI array of the sample-major phases is not needed — large farms
-// spend that room on more targets per chunk (cfg3: 27 instead of 12 -> 3 chunks instead of 7, same LDS).
+// (compact for steady inflow only: no wake-added field there) spend that room on more targets per chunk (cfg3: 27
+// instead of 12 -> 3 chunks instead of 7, same LDS).
 inline WgFlowCarve wg_plan_flow_carve(const WgParams& p, const WgHooks& hk, const WgFlowVariant& v, int res, int block, int n_tab_u, int S_shift,
                                       int added) {
     WgFlowCarve k;
@@ -307,14 +304,14 @@ inline WgFlowCarve wg_plan_flow_carve(const WgParams& p, const WgHooks& hk, cons
         const size_t ql = ((size_t)p.NP / 2 + 15) & ~(size_t)15;
         if (!v.small) {
             const size_t budget = std::max(ql, off) + sizeof(float) * (size_t)tc * p.N;
-            const int fit = (int)((budget - 16) / ((added ? 22 : 10) * (size_t)p.N));
+            const int fit = (int)((budget - 16) / (10 * (size_t)p.N));
             tc = std::max(tc, std::min(p.N, fit));
         }
-        // (+ 12 bytes per pair for the added-turbulence contributions when that model is on)
+        // (+ 12 bytes per pair for the added-turbulence contributions when that model is on: small turbulent farms)
         off = std::max(ql, ((size_t)(added ? 22 : 10) * tc * p.N + 16 + 15) & ~(size_t)15);
-        if (block == 256 && p.turb_mode == WG_TURB_NONE) {
-            // large-farm steady variant: results staged per candidate (layout: wg_flow.h, WG_LF_OFF_*); at least 512
-            // candidates at once, whatever the chunked carve would have taken otherwise
+        if (block == 256) {
+            // large-farm steady variant (LF, the one compact kernel at 256 threads): results staged per candidate (layout:
+            // wg_flow.h, WG_LF_OFF_*); at least 512 candidates at once, whatever the chunked carve would have taken otherwise
             const size_t fixed = WG_LF_OFF_DEF(p.N);
             off = std::max(off, (fixed + 8 * 512 + 15) & ~(size_t)15);
             k.lf_cap = (int)((off - fixed) / 8);
@@ -429,7 +426,7 @@ inline void wg_plan_step_kernels(const wg_config* c, const WgHooks& hk, const Wg
     const bool envb_ok = wg_plan_envb(p, hk, f, small, lds_limit, &envb_wpe);
     f.env_inc = 1 + (p.extra_inc ? 1 : 0);
     f.env_eps_max = std::min(1.0f, (float)(p.eps0 * std::sqrt(3.0))) + 2.0f / 65535.0f;
-    // A hook that asks for a specific older variant (WG_FLOW_BLOCK / WG_FLOW_RES) switches the env kernels off; WG_FLOW_ENV=0 / 1
+    // WG_FLOW_BLOCK / WG_FLOW_RES, set to any value, ask for a per-slot k_flow and switch the env kernels off; WG_FLOW_ENV=0 / 1
     // forces them off / on where eligible (tests run all of them).
     f.envw = ((env_ok || envb_ok) && !hk.flow_block.set && !hk.flow_res.set) ? 1 : 0;
     if (hk.flow_env.set) f.envw = ((env_ok || envb_ok) && hk.flow_env.v != 0) ? 1 : 0;
@@ -554,9 +551,9 @@ inline int wg_plan_create(const wg_config* c, const WgHooks& hk, int lds_limit, 
     f.lds_off_turb = k.lds_off_turb; f.lds_off_tab = k.lds_off_tab;
     f.lds_bytes = (int)k.bytes;
     if (hk.lds_pad.set) f.lds_bytes = std::min(lds_limit, f.lds_bytes + hk.lds_pad.v);      // (measurement: what a workgroup's LDS size alone costs)
-    // packed emission record: two arrays, or one interleaved (ct|k, u_e|hv) array for the steady compact variants whose
-    // deficit phase gathers bracket pairs from it (GL / k_flow_env: 64 threads; LF: 256 threads)
-    f.rec_il = (f.gl || (f.res && f.block == 256 && p.turb_mode == WG_TURB_NONE)) ? 1 : 0;
+    // packed emission record: two arrays, or one interleaved (ct|k, u_e|hv) array where the handle is compact and steady — the
+    // variants whose deficit phase gathers bracket pairs from it (GL / k_flow_env: 64 threads; LF: 256 threads)
+    f.rec_il = (f.res && p.turb_mode == WG_TURB_NONE) ? 1 : 0;
 
     wg_plan_step_kernels(c, hk, p, f, v.small, lds_limit);
     out->envw_eligible = f.envw; out->fused_eligible = f.env_fused;
