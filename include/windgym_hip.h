@@ -730,6 +730,68 @@ int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_batch* batch,
                   int batch_size, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm, wg_ppo_stats* stats_out,
                   void* stream);
 
+/* -----------------------------------------------------------------------------------------------------------------
+ * Yaw-curriculum reward shaping: the reference's CurriculumWrapper + CurriculumCallback (examples/curriculum.py:335-429) as a
+ * POST-PASS over a rollout's buffers, like wg_gae — the policy never reads the reward while it collects, so nothing is added
+ * to the step kernels or to wg_rollout (windgym_amd/csrc/wg_curriculum.hip).  Per env, with state that lives in the
+ * wg_curriculum and, as in the wrapper, is never cleared (not by an episode's end either; MODEL.md lists the quirks):
+ *     y = the yaws the agent farm held after the step's actuation, BEFORE a same-step autoreset;  g = the target yaws of the
+ *     episode the step belongs to (Serial-Refine optimum of its wind: wg_steady_optimize);  r = the env's reward;  n = steps
+ *     shaped so far;
+ *     d = mean_i |y_i - g_i|;  sim = 1 / (1 + d);  pen = 0
+ *     if n >= 1:  c_i = |y_i - yprev_i|;  pen += 0.3 * mean_i(c_i) / yaw_max;  cum += sum_i c_i
+ *                 if n >= 2:  osc += sum_i |sign(c_i) - sprev_i|;  pen += 0.2 * osc / ((n - 1) * N)
+ *                 if n >= 5:  pen += 0.1 * (cum / N) / yaw_max
+ *                 sprev_i = sign(c_i)
+ *     yprev = y;  n += 1
+ *     cur = (1 - w) * (sim - pen / 600) + w * r;   out = last = momentum * last + (1 - momentum) * cur
+ * fp64 arithmetic and state (osc and n are integers), sums over the turbines in index order, no atomics; the fp32 outputs are
+ * rounded once at the store.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_curriculum_s* wg_curriculum;
+
+/* Per-env state for the B envs x N turbines of `h`, on its device, all zero (yprev, sprev, n, osc, cum, last and the running
+ * targets g).  The batch geometry and the yaw actuation (yaw_min / yaw_max / yaw_step, action method) are copied from `h`:
+ * the curriculum does not need the handle afterwards.                                                                  */
+int wg_curriculum_create(wg_handle h, wg_curriculum* out);
+int wg_curriculum_destroy(wg_curriculum c);
+
+/* Checkpoint: the whole state as one host blob (call with host == NULL for the size) behind a header (magic, B, N);
+ * wg_curriculum_set_state refuses a blob of another geometry.  Both synchronise the device.  wg_curriculum_get_state is also
+ * where an ep_row_dev entry >= C met by an earlier wg_curriculum_shape is reported (that call is asynchronous and cannot
+ * return what only the device saw: the kernel skips such an entry and latches it): WG_ERR_INVALID once, naming ep_row_dev. */
+int wg_curriculum_get_state(wg_curriculum c, void* host, size_t* size);
+int wg_curriculum_set_state(wg_curriculum c, const void* host, size_t size);
+
+/* The running targets g of every env (CurriculumWrapper.reset for the whole batch): yaw_dev f64[B, N], copied in stream order. */
+int wg_curriculum_set_targets(wg_curriculum c, const double* yaw_dev /* [B, N] */, void* stream);
+
+/* Shape T steps of a rollout: ONE launch of k_curriculum (one thread per env walks its T steps), asynchronous on `stream`,
+ * allocates nothing.  Shaping T steps in one call is bit-identical to shaping them in two.
+ * WG_INFO_YAW_AGENT recorded after a truncating step is already the next episode's initial yaw, so the kernel restates the
+ * env's fp32 actuation (WindFarmEnv._adjust_yaws, both action methods): y_t = adjust(prev, action_t) with prev = yaw0 for
+ * t = 0 and yaw_after[t - 1] afterwards — which also carries a new episode's initial yaws.  On the step that truncates the
+ * reward uses the old episode's g; where truncated_dev[t, b] != 0 and ep_row_dev[t, b] >= 0, g becomes row ep_row_dev[t, b] of
+ * ep_target_dev from step t + 1 on (ep_row_dev is read only there; -1 keeps the target).  weight_dev[t] is w of step t.
+ * WG_ERR_INVALID, nothing enqueued, the message naming the argument: a null required buffer (ep_target_dev may be NULL with
+ * C == 0), T < 0, C < 0, momentum outside [0, 1), a buffer that is not device memory of the curriculum's device (the device of
+ * the handle it was created on).  T == 0 does nothing.                                                                  */
+int wg_curriculum_shape(wg_curriculum c, int T,
+        const float* yaw0_dev,          /* [B, N]    yaws before the first step                              */
+        const float* actions_dev,       /* [T, B, N] what wg_step received                                   */
+        const float* yaw_after_dev,     /* [T, B, N] WG_INFO_YAW_AGENT recorded per step (AFTER an autoreset) */
+        const uint8_t* truncated_dev,   /* [T, B]                                                            */
+        const int32_t* ep_row_dev,      /* [T, B]    -1, or the row of ep_target that applies from step t + 1 */
+        const double* ep_target_dev,    /* [C, N]                                                            */
+        int C,
+        const double* weight_dev,       /* [T]                                                               */
+        double momentum,
+        const float* reward_dev,        /* [T, B]                                                            */
+        float* shaped_out,              /* [T, B]    may alias reward_dev                                    */
+        float* yaw_diff_out,            /* [T, B]    or NULL: d of every step                                */
+        float* yaw_out,                 /* [T, B, N] or NULL: y of every step                                */
+        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

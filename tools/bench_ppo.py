@@ -19,7 +19,13 @@ policy shared by the turbines and rows = AGENT rows (envs x steps x 9).  `--crit
 (wg_gae_shared + wg_ppo_update); `--critic central`: one critic per env on the flat observation (wg_gae on [T, B] +
 wg_ppo_update_shared; the eager-torch leg gathers the env row of every minibatch entry the same way).
 
-usage: python tools/bench_ppo.py [--envs 4096] [--n-steps 128] [--epochs 10] [--reps 5] [--multi [--critic agent|central]]
+With --curriculum (single-agent workload only) the tool measures what the yaw curriculum adds instead: PPO.learn per iteration with
+``curriculum=None`` and with a ``YawCurriculum``, the two ALTERNATING in one process (`--reps` pairs; medians and every sample are
+reported), then `--reps` instrumented rollouts (``YawCurriculum.rollout(timing=...)``: device synchronisations between the parts)
+that split the curriculum's share into the Serial-Refine launch (with the number of conditions C it served), k_curriculum and the
+torch plumbing (the compaction's host synchronisation included).  The eager-torch legs are skipped.
+
+usage: python tools/bench_ppo.py [--envs 4096] [--n-steps 128] [--epochs 10] [--reps 5] [--multi [--critic agent|central]] [--curriculum]
 """
 import argparse
 import json
@@ -46,7 +52,10 @@ def main():
     ap.add_argument("--torch-reps", type=int, default=3, help="repetitions of the eager-torch legs (they are slow)")
     ap.add_argument("--minibatches", type=int, nargs="*", default=None)
     ap.add_argument("--preroll", type=int, default=300)
+    ap.add_argument("--curriculum", action="store_true", help="measure PPO with and without a YawCurriculum, and the curriculum's parts")
     args = ap.parse_args()
+    if args.curriculum and args.multi:
+        ap.error("--curriculum measures the single-agent workload")
     import torch
     from windgym_amd import presets
     from windgym_amd.envs import WindFarmVecEnv, WindFarmVecEnvMulti
@@ -84,6 +93,45 @@ def main():
             torch.cuda.synchronize(dev)
             ts.append(time.perf_counter() - t0)
         return statistics.median(ts), ts
+
+    if args.curriculum:
+        from windgym_amd.curriculum import YawCurriculum
+        iters = 3
+        cur = YawCurriculum(venv, curriculum_steps=100 * B * T, pure_similarity_steps=10 * B * T)
+        ppo_c = PPO("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=mbs[0], seed=1234, curriculum=cur)
+        legs = {"plain": ppo, "curriculum": ppo_c}
+        for x in legs.values():                                  # warm-up: every shape, both trainers
+            x.learn(B * T, log_interval=None)
+        torch.cuda.synchronize(dev)
+        ms = {k: [] for k in legs}
+        for _ in range(args.reps):                               # A/B in one process, alternating
+            for k, x in legs.items():
+                t0 = time.perf_counter()
+                x.learn(iters * B * T, log_interval=None)
+                torch.cuda.synchronize(dev)
+                ms[k].append((time.perf_counter() - t0) * 1e3 / iters)
+        parts = []
+        for _ in range(args.reps):
+            d = {}
+            cur.rollout(ppo_c.policy, T, num_timesteps=ppo_c.num_timesteps, timing=d)
+            d.pop("_t")
+            d["C"] = cur.last_n_targets
+            parts.append({k: round(v, 3) if k != "C" else v for k, v in d.items()})
+        med = lambda xs: statistics.median(xs)                  # noqa: E731
+        res = {"metric": "PPO on the device with and without the yaw curriculum, 16-turbine farm x %d envs x %d steps, %d epochs, one GPU" % (B, T, E),
+               "envs": B, "n_steps": T, "epochs": E, "minibatch": mbs[0], "iterations_per_sample": iters,
+               "learn_plain": {"ms_per_iteration": med(ms["plain"]), "ms_all": [round(x, 3) for x in ms["plain"]]},
+               "learn_curriculum": {"ms_per_iteration": med(ms["curriculum"]), "ms_all": [round(x, 3) for x in ms["curriculum"]]},
+               "added_ms_per_iteration": med(ms["curriculum"]) - med(ms["plain"]),
+               "curriculum_rollout_parts_ms": {k: med([p.get(k, 0.0) for p in parts]) for k in ("rollout", "serial_refine", "k_curriculum", "plumbing", "C")},
+               "curriculum_rollout_parts_all": parts,
+               "model": cur.model, "refine_pass_n": cur.refine_pass_n, "yaw_n": cur.yaw_n}
+        venv.batch.check()
+        for x in legs.values():
+            x.close(); x.policy.close()
+        cur.close(); venv.close()
+        print(json.dumps(res))
+        return
 
     out = {"metric": "PPO on the device, %s x %d envs x %d steps, %d epochs, one GPU"
                      % ("3x3 farm, one policy shared by 9 agents, critic per %s" % ("env (central)" if central else "agent") if args.multi

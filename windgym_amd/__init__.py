@@ -29,6 +29,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("PPOPopulation", "Population"):
         from . import population
         return getattr(population, name)
+    if name == "YawCurriculum":
+        from .curriculum import YawCurriculum
+        return YawCurriculum
     if name in ("PyWakeAgent", "SteadyStateYawAgent", "PyWakeVecAgent", "SteadyStateYawVecAgent"):
         from . import steady
         return getattr(steady, name)

@@ -38,6 +38,8 @@ ABI_SYMBOLS = (
     "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
     "wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared",
     "wg_pop_create", "wg_pop_destroy", "wg_pop_act", "wg_pop_rollout", "wg_gae_pop", "wg_pop_update",
+    "wg_curriculum_create", "wg_curriculum_destroy", "wg_curriculum_get_state", "wg_curriculum_set_state", "wg_curriculum_set_targets",
+    "wg_curriculum_shape",
 )
 
 _lib = None
@@ -186,6 +188,12 @@ def load_library():
                              C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_pop_update.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(CPpoBatch), C.c_void_p, C.c_int, C.c_int,
                                 C.POINTER(CPpoHyper), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    L.wg_curriculum_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.wg_curriculum_destroy.argtypes = [C.c_void_p]
+    L.wg_curriculum_get_state.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.wg_curriculum_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.wg_curriculum_set_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_curriculum_shape.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_double] + [C.c_void_p] * 5
     _lib = L
     return L
 
@@ -583,3 +591,71 @@ class HipBatch:
         b, r, d = C.c_int(), C.c_int(), C.c_int()
         _chk(self.L.wg_flow_variant(self._h, C.byref(b), C.byref(r), C.byref(d)), "wg_flow_variant")
         return b.value, bool(r.value), d.value
+
+
+class Curriculum:
+    """The ``wg_curriculum`` handle of one :class:`HipBatch`: the per-env state of the yaw-curriculum reward shaping and its one
+    kernel, k_curriculum (include/windgym_hip.h states the recurrence; ``windgym_amd.curriculum.YawCurriculum`` is the user-facing
+    class).  ``set_targets`` and ``shape`` enqueue on torch's current stream and synchronise nothing."""
+
+    HEADER_BYTES = 16        # the state blob: (magic, B, N, reserved) int32, then yprev f64[B, N], the targets g f64[B, N], ...
+
+    def __init__(self, batch: HipBatch):
+        self.batch, self.L, self.torch = batch, batch.L, batch.torch
+        self.B, self.N = batch.B, batch.N
+        h = C.c_void_p()
+        _chk(self.L.wg_curriculum_create(batch._h, C.byref(h)), "wg_curriculum_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.wg_curriculum_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def state(self) -> bytes:
+        """The state blob (synchronises).  ``ValueError`` once, naming ``ep_row_dev``, when an earlier :meth:`shape` met an
+        ``ep_row`` entry that was no row of ``ep_target`` (the kernel skipped it)."""
+        n = C.c_size_t(0)
+        _chk(self.L.wg_curriculum_get_state(self._h, None, C.byref(n)), "wg_curriculum_get_state")
+        buf = (C.c_char * n.value)()
+        _chk(self.L.wg_curriculum_get_state(self._h, buf, C.byref(n)), "wg_curriculum_get_state")
+        return bytes(buf)
+
+    def load_state(self, blob: bytes):
+        _chk(self.L.wg_curriculum_set_state(self._h, blob, len(blob)), "wg_curriculum_set_state")
+
+    def targets_of(self, blob: bytes):
+        """The running targets ``[B, N]`` (float64 numpy) a state blob of this geometry holds."""
+        n = self.B * self.N
+        return np.frombuffer(blob, dtype=np.float64, count=n, offset=self.HEADER_BYTES + 8 * n).reshape(self.B, self.N).copy()
+
+    def set_targets(self, yaw):
+        """wg_curriculum_set_targets: ``yaw`` float64 CUDA ``[B, N]``."""
+        t = self.torch
+        if not (t.is_tensor(yaw) and yaw.is_cuda and yaw.dtype == t.float64 and yaw.is_contiguous() and tuple(yaw.shape) == (self.B, self.N)):
+            raise ValueError(f"set_targets(): yaw must be a contiguous float64 CUDA tensor [{self.B}, {self.N}]")
+        _chk(self.L.wg_curriculum_set_targets(self._h, yaw.data_ptr(), self.batch._stream()), "wg_curriculum_set_targets")
+
+    def shape(self, T, yaw0, actions, yaw_after, truncated, ep_row, ep_target, n_targets, weight, momentum, reward, shaped,
+              yaw_diff=None, yaw_out=None):
+        """wg_curriculum_shape on contiguous CUDA tensors (``None`` = NULL); their sizes are checked here, their values by the
+        library."""
+        t, B, N, T = self.torch, self.B, self.N, int(T)
+        ptrs = []
+        for name, x, dtype, numel in (("yaw0", yaw0, t.float32, B * N), ("actions", actions, t.float32, T * B * N),
+                                      ("yaw_after", yaw_after, t.float32, T * B * N), ("truncated", truncated, t.uint8, T * B),
+                                      ("ep_row", ep_row, t.int32, T * B), ("ep_target", ep_target, t.float64, int(n_targets) * N),
+                                      ("weight", weight, t.float64, T), ("reward", reward, t.float32, T * B),
+                                      ("shaped", shaped, t.float32, T * B), ("yaw_diff", yaw_diff, t.float32, T * B),
+                                      ("yaw_out", yaw_out, t.float32, T * B * N)):
+            if x is not None and not (t.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= max(numel, 0)):
+                raise ValueError(f"shape(): {name} must be a contiguous {dtype} CUDA tensor of at least {numel} elements")
+            ptrs.append(None if x is None else x.data_ptr())
+        _chk(self.L.wg_curriculum_shape(self._h, T, *ptrs[:6], int(n_targets), ptrs[6], float(momentum), *ptrs[7:], self.batch._stream()),
+             "wg_curriculum_shape")

@@ -1171,6 +1171,13 @@ extern "C" int wg_flow_variant(wg_handle h, int* block, int* compact, int* duo) 
     return 0;
 }
 
+extern "C" int wg_handle_actuation_(wg_handle h, WgActuation* out) {
+    if (!h || !out) return fail(WG_ERR_INVALID, "null handle");
+    out->B = h->p.B; out->N = h->p.N; out->action_method = h->p.action_method; out->device = h->device;
+    out->yaw_min = h->p.yaw_min; out->yaw_max = h->p.yaw_max; out->yaw_step = h->p.yaw_step; out->yaw_max_d = h->p.yaw_max_d;
+    return 0;
+}
+
 extern "C" int wg_algorithmic_bytes(wg_handle h, double* bytes_per_step) {
     if (!h || !bytes_per_step) return fail(WG_ERR_INVALID, "null argument");
     *bytes_per_step = h->plan.alg_bytes;

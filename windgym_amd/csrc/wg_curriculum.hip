@@ -1,0 +1,294 @@
+// wg_curriculum.hip — yaw-curriculum reward shaping on the device: the reference's CurriculumWrapper.step and the weight its
+// CurriculumCallback sets (examples/curriculum.py:335-429) as a post-pass over a rollout's buffers (include/windgym_hip.h states
+// the recurrence).  The policy never reads the reward while wg_rollout collects, so the shaped reward is computed afterwards,
+// exactly as wg_gae computes advantages afterwards: no step kernel, no policy kernel and no part of the closed loop knows of it.
+//
+// k_curriculum: ONE thread per env walks the env's T steps in order (the recurrence is serial in t: the smoothing, the running
+// sums of the change history), the turbines in index order inside a step — every sum has one order, fixed by the shapes alone,
+// and shaping T steps in one launch or in several gives the same bits.  Per-turbine state (the previous yaws, the previous
+// change signs, the running targets) lives in global memory, [B][N]: N is whatever the handle has (Horns Rev: 80), nothing is
+// sized by it at compile time.  A step reads 2 N floats of the rollout and reads / writes 2 N state words, all of which stay
+// in the cache between steps; the launch is latency bound and small next to anything else an iteration does.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+#include <string>
+
+#include "../../include/windgym_hip.h"
+#include "wg_internal.h"
+
+namespace {
+
+struct CurP {
+    int B, N, T, C, action_method;
+    float yaw_min, yaw_max, yaw_step;
+    double yaw_max_d, momentum;
+};
+
+// the per-env state, carved out of one allocation in this order (= the payload of the state blob)
+struct CurState {
+    double* yprev;      // [B][N] the yaws of the last shaped step (previous_yaws)
+    double* g;          // [B][N] the running targets (pywake_yaws)
+    double* cum;        // [B]    sum of every change so far (np.sum(yaw_change_history))
+    double* last;       // [B]    last_reward
+    long long* n;       // [B]    steps shaped so far; the change history holds max(n - 1, 0) entries
+    long long* osc;     // [B]    sum of |diff(sign(history))| so far
+    int32_t* sprev;     // [B][N] sign of the last change (0 / 1: a change is an absolute value)
+};
+
+struct CurHeader {
+    uint32_t magic;
+    int32_t B, N, reserved;
+};
+const uint32_t CUR_MAGIC = 0x52554357u;      // "WCUR"
+
+// WindFarmEnv._adjust_yaws (Wind_Farm_Env.py:822-864) in float32, as the step kernels evaluate it (wg_flow.hip, wg_env.hip,
+// wg_envb.hip): the yaw an actuation step leaves, from the yaw before it and the action
+__device__ __forceinline__ float cur_adjust_yaw(float yaw, const float a, const CurP& p) {
+    if (p.action_method == WG_ACT_YAW) {
+        yaw = fminf(fmaxf(yaw + a * p.yaw_step, p.yaw_min), p.yaw_max);
+    } else {
+        float tf = a + 1.0f;
+        tf = tf * 0.5f;
+        tf = tf * (p.yaw_max - p.yaw_min);
+        tf = tf + p.yaw_min;
+        const float ny = fminf(fmaxf(tf, yaw - p.yaw_step), yaw + p.yaw_step);
+        yaw = fminf(fmaxf(ny, p.yaw_min), p.yaw_max);
+    }
+    return yaw;
+}
+
+__global__ __launch_bounds__(64) void k_curriculum(const CurP p, const CurState s, int* __restrict__ err, const float* __restrict__ yaw0,
+                                                   const float* __restrict__ actions, const float* __restrict__ yaw_after,
+                                                   const uint8_t* __restrict__ truncated, const int32_t* __restrict__ ep_row,
+                                                   const double* __restrict__ ep_target, const double* __restrict__ weight,
+                                                   const float* reward, float* shaped, float* __restrict__ yaw_diff,
+                                                   float* __restrict__ yaw_out) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= p.B) return;
+    const int N = p.N;
+    const size_t sb = (size_t)b * N;
+    double* const yprev = s.yprev + sb;
+    double* const g = s.g + sb;
+    int32_t* const sprev = s.sprev + sb;
+    long long n = s.n[b], osc = s.osc[b];
+    double cum = s.cum[b], last = s.last[b];
+    const double dN = (double)N;
+    for (int t = 0; t < p.T; ++t) {
+        const size_t row = (size_t)t * p.B + b;
+        const float* const prev = t == 0 ? yaw0 + sb : yaw_after + (row - p.B) * N;
+        const float* const act = actions + row * N;
+        double d = 0.0, csum = 0.0;
+        long long dosc = 0;
+        for (int i = 0; i < N; ++i) {
+            const float yf = cur_adjust_yaw(prev[i], act[i], p);
+            if (yaw_out) yaw_out[row * N + i] = yf;
+            const double y = (double)yf;
+            d += fabs(y - g[i]);
+            if (n >= 1) {
+                const double c = fabs(y - yprev[i]);
+                csum += c;
+                const int32_t sg = c > 0.0 ? 1 : 0;
+                if (n >= 2) dosc += sg > sprev[i] ? sg - sprev[i] : sprev[i] - sg;
+                sprev[i] = sg;
+            }
+            yprev[i] = y;
+        }
+        d = d / dN;
+        const double sim = 1.0 / (1.0 + d);
+        double pen = 0.0;
+        if (n >= 1) {
+            pen += 0.3 * (csum / dN / p.yaw_max_d);
+            cum += csum;
+            if (n >= 2) {
+                osc += dosc;
+                pen += (double)osc / ((double)(n - 1) * dN) * 0.2;
+            }
+            if (n >= 5) pen += cum / dN / p.yaw_max_d * 0.1;
+        }
+        n += 1;
+        const double w = weight[t];
+        const double cur = (1.0 - w) * (sim - pen / 600.0) + w * (double)reward[row];
+        last = p.momentum * last + (1.0 - p.momentum) * cur;
+        shaped[row] = (float)last;
+        if (yaw_diff) yaw_diff[row] = (float)d;
+        // CurriculumWrapper.reset: the episode that begins after this step brings its own target
+        if (truncated[row]) {
+            const int r = ep_row[row];
+            if (r >= p.C) {
+                if (atomicCAS(&err[0], 0, 1) == 0) { err[1] = t; err[2] = b; err[3] = r; }      // the first offender is the one reported
+            } else if (r >= 0) {
+                const double* const src = ep_target + (size_t)r * N;
+                for (int i = 0; i < N; ++i) g[i] = src[i];
+            }
+        }
+    }
+    s.n[b] = n; s.osc[b] = osc; s.cum[b] = cum; s.last[b] = last;
+}
+
+int fail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
+
+}  // namespace
+
+struct wg_curriculum_s {
+    WgActuation a;
+    void* mem = nullptr;        // the state: one allocation, CurState points into it
+    size_t bytes = 0;
+    CurState s;
+    int* err = nullptr;         // device: {latched, t, b, row} of an ep_row entry >= C
+};
+
+#define CUR_HIPCHK(x)                                                                          \
+    do {                                                                                       \
+        hipError_t _e = (x);                                                                   \
+        if (_e != hipSuccess) return fail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+static int cur_use_device(wg_curriculum c) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != c->a.device) CUR_HIPCHK(hipSetDevice(c->a.device));
+    return 0;
+}
+
+extern "C" int wg_curriculum_create(wg_handle h, wg_curriculum* out) {
+    if (!h || !out) return fail(WG_ERR_INVALID, "wg_curriculum_create: null argument");
+    wg_curriculum_s* c = new (std::nothrow) wg_curriculum_s;
+    if (!c) return fail(WG_ERR_NOMEM, "wg_curriculum_create: out of memory");
+    if (int rc = wg_handle_actuation_(h, &c->a)) { delete c; return rc; }
+    const size_t B = (size_t)c->a.B, BN = B * (size_t)c->a.N;
+    c->bytes = 8 * (2 * BN + 4 * B) + 4 * BN;
+    if (int rc = cur_use_device(c)) { delete c; return rc; }
+    hipError_t e = hipMalloc(&c->mem, c->bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->err, 4 * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(c->mem, 0, c->bytes);
+    if (e == hipSuccess) e = hipMemset(c->err, 0, 4 * sizeof(int));
+    if (e != hipSuccess) {
+        wg_curriculum_destroy(c);
+        return fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_curriculum_create: ") + hipGetErrorString(e));
+    }
+    char* m = (char*)c->mem;
+    c->s.yprev = (double*)m; m += 8 * BN;
+    c->s.g = (double*)m; m += 8 * BN;
+    c->s.cum = (double*)m; m += 8 * B;
+    c->s.last = (double*)m; m += 8 * B;
+    c->s.n = (long long*)m; m += 8 * B;
+    c->s.osc = (long long*)m; m += 8 * B;
+    c->s.sprev = (int32_t*)m;
+    *out = c;
+    return 0;
+}
+
+extern "C" int wg_curriculum_destroy(wg_curriculum c) {
+    if (!c) return 0;
+    if (c->mem || c->err) {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || cur != c->a.device) hipSetDevice(c->a.device);
+        hipDeviceSynchronize();
+        if (c->mem) hipFree(c->mem);
+        if (c->err) hipFree(c->err);
+    }
+    delete c;
+    return 0;
+}
+
+static CurHeader cur_header(wg_curriculum c) {
+    CurHeader hd;
+    hd.magic = CUR_MAGIC; hd.B = c->a.B; hd.N = c->a.N; hd.reserved = 0;
+    return hd;
+}
+
+extern "C" int wg_curriculum_get_state(wg_curriculum c, void* host, size_t* size) {
+    if (!c || !size) return fail(WG_ERR_INVALID, "wg_curriculum_get_state: null argument");
+    const size_t total = sizeof(CurHeader) + c->bytes;
+    if (!host) {
+        *size = total;
+        return 0;
+    }
+    if (*size < total) return fail(WG_ERR_INVALID, "wg_curriculum_get_state: state buffer too small");
+    if (int rc = cur_use_device(c)) return rc;
+    CUR_HIPCHK(hipDeviceSynchronize());
+    int err[4];
+    CUR_HIPCHK(hipMemcpy(err, c->err, sizeof(err), hipMemcpyDeviceToHost));
+    if (err[0]) {
+        CUR_HIPCHK(hipMemset(c->err, 0, sizeof(err)));
+        return fail(WG_ERR_INVALID, "wg_curriculum_shape: ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
+                                        std::to_string(err[3]) + " is not a row of ep_target_dev (C rows); the entry was skipped");
+    }
+    const CurHeader hd = cur_header(c);
+    memcpy(host, &hd, sizeof(hd));
+    CUR_HIPCHK(hipMemcpy((char*)host + sizeof(hd), c->mem, c->bytes, hipMemcpyDeviceToHost));
+    *size = total;
+    return 0;
+}
+
+extern "C" int wg_curriculum_set_state(wg_curriculum c, const void* host, size_t size) {
+    if (!c || !host) return fail(WG_ERR_INVALID, "wg_curriculum_set_state: null argument");
+    if (size < sizeof(CurHeader)) return fail(WG_ERR_INVALID, "wg_curriculum_set_state: state blob too small");
+    CurHeader got;
+    memcpy(&got, host, sizeof(got));
+    if (got.magic != CUR_MAGIC) return fail(WG_ERR_INVALID, "wg_curriculum_set_state: not a curriculum state blob");
+    const CurHeader want = cur_header(c);
+    if (memcmp(&got, &want, sizeof(got)) || size != sizeof(CurHeader) + c->bytes)
+        return fail(WG_ERR_INVALID, "wg_curriculum_set_state: the blob was taken from a curriculum of " + std::to_string(got.B) + " envs x " +
+                                        std::to_string(got.N) + " turbines, this one has " + std::to_string(want.B) + " x " + std::to_string(want.N));
+    if (int rc = cur_use_device(c)) return rc;
+    CUR_HIPCHK(hipDeviceSynchronize());
+    CUR_HIPCHK(hipMemcpy(c->mem, (const char*)host + sizeof(CurHeader), c->bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// a buffer the kernel will touch must be device memory of the curriculum's device (the device of the handle it was created on)
+static int cur_on_device(wg_curriculum c, const void* ptr, const char* name) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not a device pointer");
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != c->a.device)
+        return fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not memory of device " + std::to_string(c->a.device) +
+                                        ", the device of the handle the curriculum was created on");
+    return 0;
+}
+
+extern "C" int wg_curriculum_set_targets(wg_curriculum c, const double* yaw_dev, void* stream) {
+    if (!c) return fail(WG_ERR_INVALID, "wg_curriculum_set_targets: null curriculum");
+    if (!yaw_dev) return fail(WG_ERR_INVALID, "wg_curriculum_set_targets: yaw_dev is null");
+    if (int rc = cur_on_device(c, yaw_dev, "yaw_dev")) return rc;
+    if (int rc = cur_use_device(c)) return rc;
+    CUR_HIPCHK(hipMemcpyAsync(c->s.g, yaw_dev, sizeof(double) * (size_t)c->a.B * c->a.N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int wg_curriculum_shape(wg_curriculum c, int T, const float* yaw0_dev, const float* actions_dev, const float* yaw_after_dev,
+                                   const uint8_t* truncated_dev, const int32_t* ep_row_dev, const double* ep_target_dev, int C,
+                                   const double* weight_dev, double momentum, const float* reward_dev, float* shaped_out,
+                                   float* yaw_diff_out, float* yaw_out, void* stream) {
+    if (!c) return fail(WG_ERR_INVALID, "wg_curriculum_shape: null curriculum");
+    if (T < 0) return fail(WG_ERR_INVALID, "wg_curriculum_shape: T must be >= 0, got " + std::to_string(T));
+    if (C < 0) return fail(WG_ERR_INVALID, "wg_curriculum_shape: C must be >= 0, got " + std::to_string(C));
+    if (!(momentum >= 0.0 && momentum < 1.0))
+        return fail(WG_ERR_INVALID, "wg_curriculum_shape: momentum must lie in [0, 1), got " + std::to_string(momentum));
+    const struct { const void* ptr; const char* name; bool required; } args[] = {
+        {yaw0_dev, "yaw0_dev", true}, {actions_dev, "actions_dev", true}, {yaw_after_dev, "yaw_after_dev", true},
+        {truncated_dev, "truncated_dev", true}, {ep_row_dev, "ep_row_dev", true}, {ep_target_dev, "ep_target_dev", C > 0},
+        {weight_dev, "weight_dev", true}, {reward_dev, "reward_dev", true}, {shaped_out, "shaped_out", true},
+        {yaw_diff_out, "yaw_diff_out", false}, {yaw_out, "yaw_out", false}};
+    for (const auto& a : args) {
+        if (!a.ptr) {
+            if (a.required) return fail(WG_ERR_INVALID, std::string("wg_curriculum_shape: ") + a.name + " is null");
+            continue;
+        }
+        if (int rc = cur_on_device(c, a.ptr, a.name)) return rc;
+    }
+    if (T == 0) return 0;
+    if (int rc = cur_use_device(c)) return rc;
+    CurP p;
+    p.B = c->a.B; p.N = c->a.N; p.T = T; p.C = C; p.action_method = c->a.action_method;
+    p.yaw_min = c->a.yaw_min; p.yaw_max = c->a.yaw_max; p.yaw_step = c->a.yaw_step;
+    p.yaw_max_d = c->a.yaw_max_d; p.momentum = momentum;
+    hipLaunchKernelGGL(k_curriculum, dim3((p.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, p, c->s, c->err, yaw0_dev, actions_dev,
+                       yaw_after_dev, truncated_dev, ep_row_dev, ep_target_dev, weight_dev, reward_dev, shaped_out, yaw_diff_out, yaw_out);
+    CUR_HIPCHK(hipGetLastError());
+    return 0;
+}

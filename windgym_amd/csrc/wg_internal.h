@@ -20,9 +20,17 @@ struct WgValueRows {           // the critic on n_rows rows: obs [n_rows][critic
     int n_rows;
 };
 
+struct WgActuation {           // what a wg_curriculum copies from the handle it is created on: the batch and the yaw actuation rule
+    int B, N, action_method, device;
+    float yaw_min, yaw_max, yaw_step;      // as the step kernels hold them
+    double yaw_max_d;                      // wg_config.yaw_max
+};
+
 extern "C" {
 // wg_api.hip: the thread-local message behind wg_last_error; returns `code`
 int wg_set_last_error_(int code, const char* msg);
+// wg_api.hip: the handle's batch geometry, device and yaw actuation (wg_curriculum.hip)
+int wg_handle_actuation_(wg_handle h, WgActuation* out);
 // wg_policy.hip: ONE launch of k_policy — the actor on n_rows rows of obs_dev (when action / raw / logp is wanted) and the critic on
 // each of n_v <= 2 row sets of its own (rows of the critic's input width -> value); a set of no rows is skipped
 int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,

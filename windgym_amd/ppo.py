@@ -250,10 +250,11 @@ def hyper_json(hyper):
     return d
 
 
-def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps):
+def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps, curriculum=None):
     """The zip of :meth:`PPO.save` (format: the class docstring) from what it holds: the policy, its :class:`PPOOptimizer`, the
     permutation generator, the ``HYPER`` dict, the trainer's seed, its counters and log, the critic mode and the env's count of
-    policy steps."""
+    policy steps; with a ``curriculum`` (a ``YawCurriculum``) also its arguments (JSON key ``curriculum``) and its state blob
+    (member ``curriculum_state.bin``)."""
     import torch
     mv, step = opt.state()
     sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
@@ -267,11 +268,15 @@ def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iterati
     meta = dict(format="windgym_amd.PPO/1", desc=dict(policy.desc), hyper=hyper_json(hyper), seed=seed,
                 policy_seed=policy.seed, policy_counter=policy.counter, num_timesteps=num_timesteps,
                 iteration=iteration, adam_step=step, env_policy_steps=env_policy_steps, log=log, critic=critic)
+    if curriculum is not None:
+        meta["curriculum"] = curriculum.args()
     with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
         z.writestr("policy.pth", pth.getvalue())
         z.writestr("adam_state.npy", npy(mv))
         z.writestr("generator_state.npy", npy(gen.get_state().cpu().numpy()))
         z.writestr("windgym_ppo.json", json.dumps(meta))
+        if curriculum is not None:
+            z.writestr("curriculum_state.bin", curriculum.state())
     return path
 
 
@@ -296,13 +301,19 @@ class PPO:
     ``learning_rate`` and ``clip_range`` may be callables of ``progress_remaining`` (1 -> 0), evaluated on the host once per
     iteration.  Not implemented (``NotImplementedError``): ``target_kl``, ``clip_range_vf``, ``use_sde``.
 
+    ``curriculum``: a ``curriculum.YawCurriculum`` of this env, or a dict of its arguments — the reference's
+    examples/curriculum.py: rollouts come from ``curriculum.rollout`` (one host synchronisation per rollout, see there), GAE and the
+    update run on the shaped reward, the log gains ``curriculum_weight`` (mean of the rollout) and ``mean_yaw_diff`` while
+    ``mean_step_reward`` / ``mean_episode_return`` stay the env's own.  ``None`` changes nothing.
+
     ``save`` writes a zip whose ``policy.pth`` is a ``torch.save`` of the state dict under SB3's names (``read_sb3_zip`` and
-    ``MlpPolicy.from_sb3_zip`` read it), next to Adam's state, the counters and the hyper-parameters as npy / JSON; a zip that
+    ``MlpPolicy.from_sb3_zip`` read it), next to Adam's state, the counters and the hyper-parameters as npy / JSON (with a
+    curriculum: its arguments under the JSON key ``curriculum`` and its state blob as ``curriculum_state.bin``); a zip that
     SB3's own ``PPO.load`` accepts needs cloudpickled members and is out of scope."""
 
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
-                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None):
+                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None):
         for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
             if v is not None:
                 raise NotImplementedError(f"{name} is not implemented")
@@ -359,6 +370,13 @@ class PPO:
         self._ret = t.zeros_like(self._adv)
         self._stats = t.zeros((n_epochs, -(-n_rows // batch_size), 8), dtype=t.float32, device=policy.device)
         self.num_timesteps, self.iteration, self.log = 0, 0, []
+        self._owns_curriculum = isinstance(curriculum, dict)       # built here: closed with the trainer
+        if self._owns_curriculum:
+            from .curriculum import YawCurriculum
+            curriculum = YawCurriculum(venv, **curriculum)
+        if curriculum is not None and curriculum.venv is not venv:
+            raise ValueError("the curriculum was built for another env")
+        self.curriculum = curriculum
 
     @staticmethod
     def _build_policy(venv, shape, kw, seed, n_in_vf=None):
@@ -375,7 +393,10 @@ class PPO:
     def collect(self):
         """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added
         (``[T, B, N]`` from wg_gae_shared on a ``WindFarmVecEnvMulti``; ``[T, B]`` again under its centralised critic)."""
-        out = self.venv.rollout(self.policy, self.n_steps)
+        if self.curriculum is None:
+            out = self.venv.rollout(self.policy, self.n_steps)
+        else:
+            out = self.curriculum.rollout(self.policy, self.n_steps, num_timesteps=self.num_timesteps)
         self.opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda, out=(self._adv, self._ret))
         out["advantage"], out["returns"] = self._adv, self._ret
         return out
@@ -405,7 +426,10 @@ class PPO:
         t = self.torch
         ret, val = self._ret.double(), out["value"].double()
         ev = 1.0 - (ret - val).var() / ret.var()
-        vec = t.cat([stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)])
+        parts = [stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)]
+        if self.curriculum is not None:
+            parts += [out["curriculum_weight"].mean().reshape(1), out["yaw_diff"].double().mean().reshape(1)]
+        vec = t.cat(parts)
         host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
         rec = dict(zip(PPO_STATS, host[:8].tolist()))
         rec["explained_variance"] = float(host[8])
@@ -413,6 +437,8 @@ class PPO:
         rec.update(iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr, clip_range=clip,
                    n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
                    mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"], fps=fps())
+        if self.curriculum is not None:
+            rec.update(curriculum_weight=float(host[-2]), mean_yaw_diff=float(host[-1]))
         return rec
 
     def predict(self, obs, state=None, episode_start=None, deterministic=False):
@@ -422,7 +448,7 @@ class PPO:
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself (see the class docstring for the format)."""
         return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
-                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps)
+                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps, self.curriculum)
 
     @classmethod
     def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
@@ -437,6 +463,7 @@ class PPO:
             meta = json.loads(z.read("windgym_ppo.json").decode())
             mv = np.load(io.BytesIO(z.read("adam_state.npy")))
             gen = np.load(io.BytesIO(z.read("generator_state.npy")))
+            cur_state = z.read("curriculum_state.bin") if "curriculum_state.bin" in z.namelist() else None
         desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
         pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
                         device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"],
@@ -449,7 +476,9 @@ class PPO:
                 hyper[k] = v
             elif hyper[k] is None:
                 raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
-        self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), **hyper)      # (no key: written before there was a choice)
+        self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), curriculum=meta.get("curriculum"), **hyper)   # (no key: written before there was one)
+        if self.curriculum is not None and cur_state is not None:
+            self.curriculum.load_state(cur_state)
         self.opt.load_state(mv, meta["adam_step"])
         self._gen.set_state(torch.from_numpy(gen))
         self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
@@ -458,3 +487,5 @@ class PPO:
 
     def close(self):
         self.opt.close()
+        if self._owns_curriculum:
+            self.curriculum.close()
