@@ -792,6 +792,84 @@ int wg_curriculum_shape(wg_curriculum c, int T,
         float* yaw_out,                 /* [T, B, N] or NULL: y of every step                                */
         void* stream);
 
+/* -----------------------------------------------------------------------------------------------------------------
+ * VecNormalize: running observation / return statistics for PPO, restated from stable-baselines3 2.x
+ * (common/vec_env/vec_normalize.py, common/running_mean_std.py; windgym_amd/csrc/wg_norm.hip).
+ *   RunningMeanStd(shape): mean = 0, var = 1, count = 1e-4 (float64).  update(batch [n, ...]):
+ *       bm = mean(batch, 0);  bv = var(batch, 0) (population variance about bm);  delta = bm - mean;  tot = count + n
+ *       mean += delta * n / tot;  var = (var * count + bv * n + delta^2 * count * n / tot) / tot;  count = tot
+ *   A wg_norm keeps obs_rms = RunningMeanStd((O,)), ret_rms = RunningMeanStd(()) and returns f64[B] = 0.
+ *       normalize_obs(x)    = clip((x - obs_rms.mean) / sqrt(obs_rms.var + epsilon), +-clip_obs)        (identity: norm_obs == 0)
+ *       normalize_reward(r) = clip(r / sqrt(ret_rms.var + epsilon), +-clip_reward)                      (identity: norm_reward == 0)
+ *   One step of the wrapper, in this order (done = truncated: this env never terminates):
+ *       1  obs, r, done = venv.step(a)              (obs: after an autoreset the NEW episode's first observation)
+ *       2  if training and norm_obs: obs_rms.update(obs)
+ *       3  obs_n = normalize_obs(obs)
+ *       4  if training: returns = returns * gamma + r;  ret_rms.update(returns)
+ *       5  r_n = normalize_reward(r)
+ *       6  the terminal (final) rows = normalize_obs(.) with the statistics as they now stand; they never enter an update
+ *       7  returns[done] = 0
+ *   reset(): returns = 0; if training and norm_obs: obs_rms.update(obs); normalize_obs(obs).
+ * Arithmetic: statistics and returns are float64; batch moments are computed in float64 from the float32 rows, the mean first,
+ * then the squares about it; every sum has an order fixed by (n_rows, O) alone (no float atomics); a normalised value is
+ * computed in float64, clipped and rounded to float32 once.  A wg_norm is used on one stream at a time.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_norm_s* wg_norm;
+typedef struct wg_norm_desc {
+    int32_t n_obs, n_envs;         /* O and B                                                                         */
+    int32_t norm_obs, norm_reward; /* 0: that half is the identity (and obs_rms is never updated when norm_obs == 0)  */
+    float   clip_obs, clip_reward; /* > 0                                                                             */
+    double  gamma, epsilon;        /* gamma in [0, 1]; epsilon in (0, 1)                                               */
+} wg_norm_desc;
+
+/* Fresh statistics on `device`, training on.  WG_ERR_INVALID: null argument, n_obs / n_envs < 1, a clip <= 0, gamma or
+ * epsilon out of range.                                                                                               */
+int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out);
+int wg_norm_destroy(wg_norm n);
+
+/* Checkpoint: one host blob (host == NULL: the size) = a header (magic, O, B, 0: int32) and then float64 obs mean [O], obs
+ * var [O], obs count, ret mean, ret var, ret count, returns [B].  Both synchronise the device; wg_norm_set_state refuses a
+ * blob of other widths (WG_ERR_INVALID).                                                                              */
+int wg_norm_get_state(wg_norm n, void* host, size_t* size);
+int wg_norm_set_state(wg_norm n, const void* host, size_t size);
+
+/* training = 0 freezes both statistics (evaluation); normalisation goes on.  Takes effect for calls made afterwards.  */
+int wg_norm_set_training(wg_norm n, int training);
+
+/* returns = 0 for the envs whose byte of env_mask_host [B] is non-zero (NULL: all), in stream order: reset()'s step 2.  */
+int wg_norm_reset_returns(wg_norm n, const uint8_t* env_mask_host /* NULL: all */, void* stream);
+
+/* The observation half of one step (rules 2, 3 and 6): if training && norm_obs, obs_rms.update(the n_rows rows of obs_dev); then
+ * out = normalize_obs(obs) and extra_out = normalize_obs(extra) (extra_dev / extra_out_dev may both be NULL: the final rows),
+ * both with the statistics AFTER the update.  At most two launches (k_norm_part, k_norm_apply), asynchronous on `stream`, no
+ * allocation, no host synchronisation.  Rows are [n_rows, O] float32.
+ * WG_ERR_INVALID: null n / obs_dev / out_dev, one of extra_dev / extra_out_dev without the other, n_rows < 0, an update of more
+ * than n_envs rows (a frozen wg_norm, or one with norm_obs == 0, takes any number).  n_rows == 0 does nothing.          */
+int wg_norm_obs(wg_norm n, int n_rows, const float* obs_dev, float* out_dev, const float* extra_dev, float* extra_out_dev,
+                void* stream);
+
+/* The reward half of T steps as a post-pass over [T, B] (rules 4, 5 and 7 for t = 0 .. T-1 in order), like wg_gae: the policy
+ * never reads the reward while it collects.  out_dev may alias reward_dev.  T steps in one call are bit-identical to T calls
+ * of one step.  Asynchronous on `stream`; the fp64 scratch [T, B] is the wg_norm's and grows BEFORE anything is enqueued when T
+ * exceeds every earlier call's (that call synchronises the device).  Equivalent loop:
+ *     for t in 0 .. T-1:
+ *         if training: returns = returns * gamma + reward[t];  ret_rms.update(returns)
+ *         out[t] = normalize_reward(reward[t]);  returns[truncated[t] != 0] = 0
+ * WG_ERR_INVALID: a null argument, T < 0.  T == 0 does nothing.                                                        */
+int wg_norm_reward(wg_norm n, int T, const float* reward_dev, const uint8_t* truncated_dev, float* out_dev, void* stream);
+
+/* wg_rollout with the policy reading NORMALISED rows whose statistics move inside the loop: buffers, the handle's state and the
+ * wg_norm's state afterwards are BIT-IDENTICAL to wg_rollout's documented loop with obs[t] -> norm_obs[t] in the inputs of both
+ * wg_policy_act calls (final_obs[t] -> norm_final_obs[t]) and, after each wg_step,
+ *     wg_norm_obs(n, B, bufs->obs[t+1], norm_obs[t+1], bufs->final_obs[t], norm_final_obs[t])
+ * norm_obs_dev [T+1, B, O] (slot 0 is INPUT: the normalised current observation), norm_final_obs_dev [T, B, O]; bufs->obs and
+ * bufs->final_obs are required and hold the env's own rows.  With norm_obs == 0 the normalised buffers are copies and bufs is
+ * filled bit for bit as wg_rollout fills it.  The reward is the env's: wg_norm_reward is a call of its own afterwards.
+ * WG_ERR_INVALID: what wg_rollout refuses; a null wg_norm; one whose n_obs / n_envs are not the handle's obs_dim / n_envs or
+ * that lives on another device; bufs->obs, bufs->final_obs, norm_obs_dev or norm_final_obs_dev missing.                  */
+int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                    uint64_t row_offset, const wg_rollout_bufs* bufs, float* norm_obs_dev, float* norm_final_obs_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name == "YawCurriculum":
         from .curriculum import YawCurriculum
         return YawCurriculum
+    if name == "VecNormalize":
+        from .normalize import VecNormalize
+        return VecNormalize
     if name in ("PyWakeAgent", "SteadyStateYawAgent", "PyWakeVecAgent", "SteadyStateYawVecAgent"):
         from . import steady
         return getattr(steady, name)

@@ -40,6 +40,8 @@ ABI_SYMBOLS = (
     "wg_pop_create", "wg_pop_destroy", "wg_pop_act", "wg_pop_rollout", "wg_gae_pop", "wg_pop_update",
     "wg_curriculum_create", "wg_curriculum_destroy", "wg_curriculum_get_state", "wg_curriculum_set_state", "wg_curriculum_set_targets",
     "wg_curriculum_shape",
+    "wg_norm_create", "wg_norm_destroy", "wg_norm_get_state", "wg_norm_set_state", "wg_norm_set_training", "wg_norm_reset_returns",
+    "wg_norm_obs", "wg_norm_reward", "wg_rollout_norm",
 )
 
 _lib = None
@@ -87,6 +89,12 @@ class CPpoBatchShared(C.Structure):
 class CPpoHyper(C.Structure):
     """wg_ppo_hyper"""
     _fields_ = [("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("normalize_advantage", C.c_int32)]
+
+
+class CNormDesc(C.Structure):
+    """wg_norm_desc"""
+    _fields_ = [("n_obs", C.c_int32), ("n_envs", C.c_int32), ("norm_obs", C.c_int32), ("norm_reward", C.c_int32),
+                ("clip_obs", C.c_float), ("clip_reward", C.c_float), ("gamma", C.c_double), ("epsilon", C.c_double)]
 
 
 PPO_STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss", "adv_mean", "adv_std")   # wg_ppo_stats
@@ -194,6 +202,16 @@ def load_library():
     L.wg_curriculum_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.wg_curriculum_set_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_curriculum_shape.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_double] + [C.c_void_p] * 5
+    L.wg_norm_create.argtypes = [C.POINTER(CNormDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_norm_destroy.argtypes = [C.c_void_p]
+    L.wg_norm_get_state.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.wg_norm_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.wg_norm_set_training.argtypes = [C.c_void_p, C.c_int]
+    L.wg_norm_reset_returns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_norm_obs.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    L.wg_norm_reward.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.wg_rollout_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                  C.POINTER(CRolloutBufs), C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -317,6 +335,14 @@ class HipBatch:
         _chk(self.L.wg_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), (C.c_uint64 * P)(*[int(seed)] * P), counter0,
                                    (C.c_uint64 * P)(*[int(row_offset) + m * Bm for m in range(P)]), C.byref(cb), self._stream()),
              "wg_pop_rollout")
+
+    def rollout_norm(self, norm, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
+        """wg_rollout_norm, the arguments of :meth:`rollout` after a :class:`Norm`: ``bufs`` also holds ``norm_obs`` ``[T+1, B, O]``
+        (slot 0 is input) and ``norm_final_obs`` ``[T, B, O]``, the rows the policy reads."""
+        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
+        _chk(self.L.wg_rollout_norm(self._h, policy._h, norm._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
+                                    C.byref(cb), bufs["norm_obs"].data_ptr(), bufs["norm_final_obs"].data_ptr(), self._stream()),
+             "wg_rollout_norm")
 
     def rollout_multi(self, *args):
         """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""
@@ -659,3 +685,111 @@ class Curriculum:
             ptrs.append(None if x is None else x.data_ptr())
         _chk(self.L.wg_curriculum_shape(self._h, T, *ptrs[:6], int(n_targets), ptrs[6], float(momentum), *ptrs[7:], self.batch._stream()),
              "wg_curriculum_shape")
+
+
+class Norm:
+    """A ``wg_norm`` handle: SB3's VecNormalize statistics on the device (include/windgym_hip.h restates the rules;
+    ``windgym_amd.normalize.VecNormalize`` is the user-facing class).  ``obs``, ``reward`` and ``reset_returns`` enqueue on torch's
+    current stream and synchronise nothing; ``state`` / ``load_state`` synchronise."""
+
+    HEADER_BYTES = 16        # the state blob: (magic, O, B, 0) int32, then float64 obs mean [O], var [O], count, ret mean, var, count, returns [B]
+
+    def __init__(self, n_obs, n_envs, device, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99,
+                 epsilon=1e-8):
+        import torch
+        self.torch, self.L = torch, load_library()
+        self.O, self.B = int(n_obs), int(n_envs)
+        self.device = torch.device("cuda", int(device))
+        d = CNormDesc(self.O, self.B, int(bool(norm_obs)), int(bool(norm_reward)), float(clip_obs), float(clip_reward), float(gamma),
+                      float(epsilon))
+        h = C.c_void_p()
+        _chk(self.L.wg_norm_create(C.byref(d), int(device), C.byref(h)), "wg_norm_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.wg_norm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def state(self) -> bytes:
+        n = C.c_size_t(0)
+        _chk(self.L.wg_norm_get_state(self._h, None, C.byref(n)), "wg_norm_get_state")
+        buf = (C.c_char * n.value)()
+        _chk(self.L.wg_norm_get_state(self._h, buf, C.byref(n)), "wg_norm_get_state")
+        return bytes(buf)
+
+    def load_state(self, blob: bytes):
+        _chk(self.L.wg_norm_set_state(self._h, blob, len(blob)), "wg_norm_set_state")
+
+    def stats(self):
+        """The state blob's float64 payload as a dict of numpy arrays: ``obs_mean`` / ``obs_var`` ``[O]``, ``obs_count``,
+        ``ret_mean``, ``ret_var``, ``ret_count`` and ``returns`` ``[B]`` (synchronises)."""
+        return unpack_norm_state(self.state(), self.O, self.B)
+
+    def set_training(self, training):
+        _chk(self.L.wg_norm_set_training(self._h, int(bool(training))), "wg_norm_set_training")
+
+    def reset_returns(self, mask=None):
+        mp = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(self.B))
+            mp = m.ctypes.data_as(C.c_void_p)
+        _chk(self.L.wg_norm_reset_returns(self._h, mp, self._stream()), "wg_norm_reset_returns")
+
+    def _rows(self, name, x, dtype, numel=None):
+        t = self.torch
+        if not (t.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == dtype and x.is_contiguous()
+                and (numel is None or x.numel() == numel)):
+            raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor on {self.device}"
+                             + ("" if numel is None else f" of {numel} elements"))
+        return x.data_ptr()
+
+    def obs(self, obs, out, extra=None, extra_out=None):
+        """wg_norm_obs on ``[n_rows, O]`` float32 tensors (``extra`` / ``extra_out``: the final rows, or both ``None``)."""
+        t = self.torch
+        if obs.numel() % self.O:
+            raise ValueError(f"obs must hold rows of {self.O} entries")
+        n = obs.numel() // self.O
+        ptrs = [self._rows("obs", obs, t.float32), self._rows("out", out, t.float32, n * self.O),
+                None if extra is None else self._rows("extra", extra, t.float32, n * self.O),
+                None if extra_out is None else self._rows("extra_out", extra_out, t.float32, n * self.O)]
+        _chk(self.L.wg_norm_obs(self._h, n, *ptrs, self._stream()), "wg_norm_obs")
+        return out
+
+    def reward(self, reward, truncated, out):
+        """wg_norm_reward on ``[T, B]`` tensors (``reward`` / ``out`` float32, ``truncated`` uint8); ``out`` may be ``reward``."""
+        t = self.torch
+        if reward.numel() % self.B:
+            raise ValueError(f"reward must be [T, {self.B}]")
+        T = reward.numel() // self.B
+        ptrs = [self._rows("reward", reward, t.float32), self._rows("truncated", truncated, t.uint8, T * self.B),
+                self._rows("out", out, t.float32, T * self.B)]
+        _chk(self.L.wg_norm_reward(self._h, T, *ptrs, self._stream()), "wg_norm_reward")
+        return out
+
+
+def unpack_norm_state(blob, n_obs, n_envs):
+    """The float64 payload of a ``wg_norm`` state blob of these widths as a dict of numpy arrays (copies)."""
+    O, B = int(n_obs), int(n_envs)
+    a = np.frombuffer(blob, dtype=np.float64, count=2 * O + 4 + B, offset=Norm.HEADER_BYTES).copy()
+    return dict(obs_mean=a[:O], obs_var=a[O:2 * O], obs_count=a[2 * O], ret_mean=a[2 * O + 1], ret_var=a[2 * O + 2],
+                ret_count=a[2 * O + 3], returns=a[2 * O + 4:])
+
+
+def pack_norm_state(n_obs, n_envs, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count, returns):
+    """The inverse of :func:`unpack_norm_state`: a blob ``wg_norm_set_state`` accepts."""
+    O, B = int(n_obs), int(n_envs)
+    a = np.concatenate([np.asarray(obs_mean, np.float64).reshape(-1), np.asarray(obs_var, np.float64).reshape(-1),
+                        np.array([obs_count, ret_mean, ret_var, ret_count], np.float64), np.asarray(returns, np.float64).reshape(-1)])
+    if a.size != 2 * O + 4 + B:
+        raise ValueError(f"statistics of the wrong width: obs_mean / obs_var must hold {O} entries and returns {B}")
+    return np.array([0x4d524e57, O, B, 0], np.uint32).tobytes() + a.tobytes()

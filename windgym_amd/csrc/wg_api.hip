@@ -843,6 +843,9 @@ struct RolloutRows {
     // non-null: a population acts in the policy's place (wg_pop_rollout) — its slot table is prepared for these buffers, and a
     // step's one launch of the policy kernel is wg_pop_launch_ on it instead of wg_policy_eval_
     wg_pop_s* pop;
+    // non-null: the policy's rows are NORMALISED copies of the steps' flat rows (wg_rollout_norm) — after every step the
+    // observation half of this wg_norm is enqueued: o.obs[t + 1] -> o.obs_multi[t + 1], o.final_obs[t] -> o.final_obs_multi[t]
+    wg_norm_s* norm;
 };
 
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
@@ -907,6 +910,9 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
             wg_launch_info(&h->p, &h->d, o.info_fields[i], (char*)o.info_out[i] + (size_t)t * info_bytes(h, o.info_fields[i]), st);
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) rc = fail(WG_ERR_HIP, std::string(g.who) + ": kernel launch failed: " + hipGetErrorString(le));
+        if (g.norm && !rc)
+            rc = wg_norm_obs(g.norm, B, o.obs + (t + 1) * sBO, o.obs_multi + (t + 1) * sRO, o.final_obs + t * sBO,
+                             o.final_obs_multi + t * sRO, stream);
     }
     h->d.multi_out = multi0;      // the handle's own per-agent buffers again, on every way out (the device copies never changed)
     h->d.multi_fin = fin0;
@@ -928,6 +934,31 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
                            {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
                             o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
                            1, O, o->obs, o->final_obs, "final_obs"};
+    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
+    if (int rc = use_device(h)) return rc;
+    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+}
+
+// The policy on normalised rows: the actor and the critic read norm_obs / norm_final_obs, the steps write bufs->obs / final_obs,
+// and the wg_norm's observation half runs after every step (its statistics move inside the loop).
+extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                               uint64_t row_offset, const wg_rollout_bufs* o, float* norm_obs_dev, float* norm_final_obs_dev, void* stream) {
+    if (!h || !p || !n || !o) return fail(WG_ERR_INVALID, "wg_rollout_norm: null argument");
+    const int N = h->p.N, O = h->p.obs_dim;
+    int n_obs = 0, n_envs = 0, n_device = 0;
+    if (int rc = wg_norm_geometry_(n, &n_obs, &n_envs, &n_device)) return rc;
+    if (n_obs != O || n_envs != h->p.B)
+        return fail(WG_ERR_INVALID, "wg_rollout_norm: the wg_norm holds statistics of " + std::to_string(n_obs) + " observation entries x " +
+                                        std::to_string(n_envs) + " envs, the handle's obs_dim / n_envs are " + std::to_string(O) + " / " +
+                                        std::to_string(h->p.B));
+    if (n_device != h->device) return fail(WG_ERR_INVALID, "wg_rollout_norm: wg_norm and handle live on different devices");
+    if (!o->obs || !o->final_obs || !norm_final_obs_dev)
+        return fail(WG_ERR_INVALID, "wg_rollout_norm: obs, final_obs (the env's own rows) and norm_final_obs are required");
+    const RolloutRows g = {"wg_rollout_norm", "norm_obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
+                           nullptr, false,
+                           {norm_obs_dev, o->actions, o->raw, o->logp, o->value, norm_final_obs_dev, o->final_value, o->reward, o->truncated,
+                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
+                           1, O, norm_obs_dev, norm_final_obs_dev, "norm_final_obs", nullptr, n};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = use_device(h)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);

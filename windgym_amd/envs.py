@@ -234,6 +234,7 @@ class WindFarmVecEnv(_gym_vector_base()):
         lo, hi = shard_range(total, rank, world)
         assert hi - lo == self.num_envs, "construct the env with this rank's share of the env axis"
         self._global_offset = lo
+        self._sharded = int(world) > 1          # (normalize.VecNormalize refuses a shard: its statistics would need an all-reduce)
         return self
 
     def _seeds(self, seed):
@@ -314,13 +315,16 @@ class WindFarmVecEnv(_gym_vector_base()):
                              shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
                              slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout if pop is None else b.rollout_pop)
 
-    def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run, critic=None):
+    def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run, critic=None, norm=None):
         """``rollout()`` of this class and of :class:`WindFarmVecEnvMulti`.  ``rows``: the axes of the policy's rows, ``(B,)`` or
         ``(B, N)``; ``shape`` / ``needs``: the ``(n_in, n_out)`` the policy must have and how the refusal says so; ``slots``: per
         observation the steps write, ``(key, key of its final rows, persistent tensor, persistent final tensor)`` — slot 0 is
         seeded from the persistent tensor, which receives slot T (final: T-1) afterwards; the policy reads ``"obs"``; ``run``: the
         ``HipBatch`` call that enqueues the loop.  ``critic``: ``(key, key of its final rows, axes of its rows)`` of what a SPLIT
-        policy's critic reads (its width must be that buffer's); ``None``: a split policy is refused."""
+        policy's critic reads (its width must be that buffer's); ``None``: a split policy is refused.  ``norm``: ``(binding.Norm,
+        normalised current observation)`` of a ``normalize.VecNormalize`` — the policy then reads ``norm_obs`` / ``norm_final_obs``,
+        two further buffers that ``run`` fills (wg_rollout_norm) next to the env's own rows; slot 0 is seeded from the given
+        tensor, which receives slot T afterwards."""
         from .config import INFO
         t, b = self.torch, self.batch
         T, B, N = int(n_steps), self.num_envs, self.n_turb
@@ -338,7 +342,7 @@ class WindFarmVecEnv(_gym_vector_base()):
                 raise ValueError(f"rollout(): unknown info field {name!r}")
         values = bool(values) and policy.has_critic
         stochastic_ok = policy.desc["has_log_std"]
-        key = (rows, vrows, T, record, values, stochastic_ok)
+        key = (rows, vrows, T, record, values, stochastic_ok, norm is not None)
         bufs = self._rollout_bufs.get(key)
         if bufs is None:
             f32 = dict(dtype=t.float32, device=b.device)
@@ -346,6 +350,8 @@ class WindFarmVecEnv(_gym_vector_base()):
                         truncated=t.zeros((T, B), dtype=t.uint8, device=b.device))
             for k, kf, cur, fin in slots:
                 bufs[k], bufs[kf] = t.zeros((T + 1,) + tuple(cur.shape), **f32), t.zeros((T,) + tuple(fin.shape), **f32)
+            if norm is not None:
+                bufs["norm_obs"], bufs["norm_final_obs"] = t.zeros_like(bufs["obs"]), t.zeros_like(bufs["final_obs"])
             if stochastic_ok:
                 bufs["logp"] = t.zeros((T,) + rows, **f32)
             if values:
@@ -356,12 +362,16 @@ class WindFarmVecEnv(_gym_vector_base()):
             self._rollout_bufs[key] = bufs
         for k, _, cur, _ in slots:
             bufs[k][0].copy_(cur)
+        pk, pkf = ("obs", "final_obs") if norm is None else ("norm_obs", "norm_final_obs")       # the rows the policy reads
+        if norm is not None:
+            bufs[pk][0].copy_(norm[1])
+            vk, vkf = pk, pkf
         seed = 0 if self._base_seed is None else int(self._base_seed)
         counter0 = self._policy_steps
         self._policy_steps = counter0 + T
         if self._site is not None:
             for i in range(T):
-                policy.act(bufs["obs"][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
+                policy.act(bufs[pk][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
                            row_offset=self._global_offset * math.prod(rows[1:]), value=values,
                            out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
                                 bufs["value"][i] if values else None))
@@ -373,10 +383,16 @@ class WindFarmVecEnv(_gym_vector_base()):
                     bufs[k][i + 1].copy_(cur); bufs[kf][i].copy_(fin)
                 for name in record:
                     b.info(name, out=bufs[name][i])
+                if norm is not None:
+                    norm[0].obs(bufs["obs"][i + 1], bufs[pk][i + 1], bufs["final_obs"][i], bufs[pkf][i])
                 if values:
                     policy.value(bufs[vkf][i], out=bufs["final_value"][i])
+            if norm is not None:
+                norm[1].copy_(bufs[pk][T])
             return dict(bufs)
         run(policy, T, bufs, record, deterministic, seed, counter0, self._global_offset)
+        if norm is not None:
+            norm[1].copy_(bufs[pk][T])
         # the persistent outputs follow, as after a step()
         for k, kf, cur, fin in slots:
             cur.copy_(bufs[k][T]); fin.copy_(bufs[kf][T - 1])

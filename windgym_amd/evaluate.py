@@ -19,10 +19,13 @@ from .envs import WindFarmVecEnv, _np
 def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windspeeds=(10.0,),
                turbintensities=(0.05,), t_sim=100, turbtype="None", turbbox="Default", model_step=1,
                Baseline_comp=True, yaw_init="Zeros", deterministic=True, seed=1, device=None, flow_script=None,
-               turbboxes=None, **env_kwargs):
+               turbboxes=None, normalize=None, **env_kwargs):
     """Roll `model` (anything with predict(obs) -> (action, state)) for t_sim steps under every combination of
     the given wind directions, speeds and turbulence intensities at once.  ``flow_script`` = (uvw [F,T,B,N,3],
-    power [F,T,B,N]): replay mode (test hook — the golden vectors recorded from the reference's eval_single_fast)."""
+    power [F,T,B,N]): replay mode (test hook — the golden vectors recorded from the reference's eval_single_fast).
+    ``normalize``: a ``normalize.VecNormalize``, or the path of its npz, for a ``model`` (an ``MlpPolicy``) that was trained on
+    normalised rows — the env is wrapped FROZEN (``training=False``, ``norm_reward=False``) and the rollout goes through the wrapper;
+    the dataset is unchanged, it is built from info fields and the env's own reward."""
     # `turbboxes`: the reference's eval_multiple loops over turbulence-box files too (AgentEval.py:579-617,
     # FarmEval.update_tf).  Every entry — a TF_* file path or a (box [3, Nx, Ny, Nz], spacing) pair — becomes one box of
     # the device-resident pool, and every (condition, box) pair one env pinned to its box (wg_set_box_ids).
@@ -44,6 +47,11 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
     if turbboxes:
         box_ids = np.array([c[3] for c in conds4], dtype=np.int32)
     B = len(conds)
+    from .policy import MlpPolicy
+    if normalize is not None:
+        if not (isinstance(model, MlpPolicy) and t_sim > 1):
+            raise ValueError("normalize applies to the device rollout of an MlpPolicy (t_sim > 1)")
+        env_kwargs = dict(env_kwargs, as_torch=True)
     env = WindFarmVecEnv(turbine, B, yaml_path=yaml_path, turbtype=turbtype, Baseline_comp=Baseline_comp,
                          yaw_init=yaw_init, never_truncate=True, autoreset=False, seed=seed, device=device,
                          **env_kwargs)
@@ -76,7 +84,6 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
             rec["ws_b"][i] = np.linalg.norm(_np(b.info("rotor_uvw_base")), axis=-1)
 
     from .binding import HipBatch
-    from .policy import MlpPolicy
     if isinstance(model, MlpPolicy) and isinstance(b, HipBatch) and t_sim > 1:
         # Learned policy on the device: snapshot 0 goes into row 0 of device recordings, steps 1 .. t_sim-1 are ONE
         # rollout (policy and step kernels alternate inside the library), and the recordings cross to the host once.
@@ -89,7 +96,16 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
             shape, dtype = b.info_shape(name)
             full[k] = t.zeros((t_sim,) + tuple(shape), dtype=dtype, device=b.device)
             b.info(name, out=full[k][0])
-        out = env.rollout(model, t_sim - 1, deterministic=deterministic, record=tuple(names.values()), values=False)
+        if normalize is None:
+            out = env.rollout(model, t_sim - 1, deterministic=deterministic, record=tuple(names.values()), values=False)
+        else:
+            from .normalize import as_frozen
+            vn, mine = as_frozen(normalize, env)
+            out = dict(vn.rollout(model, t_sim - 1, deterministic=deterministic, record=tuple(names.values()), values=False,
+                                  normalize_reward=False))
+            if mine:
+                b.torch.cuda.synchronize(b.device)
+                vn.close()
         for k, name in names.items():
             full[k][1:].copy_(out[name])
         host = {k: _np(v) for k, v in full.items()}
@@ -144,7 +160,7 @@ class AgentEval:
     ``env`` may be a :class:`FarmEval` / :class:`WindFarmEnv` (its turbine, YAML and constructor kwargs are reused) or
     None with ``turbine`` / ``yaml_path`` given explicitly."""
 
-    def __init__(self, env=None, model=None, name="NoName", t_sim=1000, *, turbine=None, yaml_path=None, **env_kwargs):
+    def __init__(self, env=None, model=None, name="NoName", t_sim=1000, *, turbine=None, yaml_path=None, normalize=None, **env_kwargs):
         self.ws, self.ti, self.wd, self.yaw, self.turbbox = 10.0, 0.05, 270, 0.0, "Default"
         self.t_sim = t_sim
         self.winddirs, self.windspeeds, self.turbintensities, self.turbboxes = [270], [10], [0.05], ["Default"]
@@ -156,6 +172,7 @@ class AgentEval:
         self._env_kwargs = dict(turbtype=kw.get("turbtype", "None"), yaml_dict=kw.get("yaml_dict"),
                                 n_passthrough=kw.get("n_passthrough", 5))
         self._env_kwargs.update(env_kwargs)
+        self.normalize = normalize          # a VecNormalize or the path of its npz: eval_sweep(normalize=)
         if self._turbine is None:
             raise ValueError("AgentEval needs an env (FarmEval / WindFarmEnv) or turbine= and yaml_path=")
 
@@ -186,7 +203,8 @@ class AgentEval:
                                            # (the reference calls set_condition(turbbox=box) for EVERY entry, also a single one: a real path is
                                            # loaded and pinned, only the placeholder "Default" means the env's own inflow)
                                            turbboxes=self.turbboxes if any(not (isinstance(tb, str) and tb == "Default")
-                                                                           for tb in self.turbboxes) else None, **kw)
+                                                                           for tb in self.turbboxes) else None,
+                                           normalize=self.normalize, **kw)
         self.multiple_eval = True
         return self.multiple_eval_ds
 

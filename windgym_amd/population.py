@@ -147,9 +147,12 @@ class PPOPopulation:
 
     def __init__(self, policy, venv, n_members=None, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95,
                  clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True,
-                 policy_kwargs=None, seed=None, curriculum=None):
+                 policy_kwargs=None, seed=None, curriculum=None, normalize=None):
         if curriculum is not None:
             raise NotImplementedError("a curriculum for a population is not implemented (use PPO(..., curriculum=...))")
+        if normalize is not None:
+            raise NotImplementedError("normalize for a population is not implemented: its members would need statistics of their own "
+                                      "(use PPO(..., normalize=...))")
         if getattr(venv, "possible_agents", None) is not None:
             raise NotImplementedError("populations train on a WindFarmVecEnv: a WindFarmVecEnvMulti (wg_rollout_multi) is out of scope")
         objects = not isinstance(policy, str)

@@ -250,11 +250,13 @@ def hyper_json(hyper):
     return d
 
 
-def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps, curriculum=None):
+def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps, curriculum=None,
+                     normalize=None):
     """The zip of :meth:`PPO.save` (format: the class docstring) from what it holds: the policy, its :class:`PPOOptimizer`, the
     permutation generator, the ``HYPER`` dict, the trainer's seed, its counters and log, the critic mode and the env's count of
     policy steps; with a ``curriculum`` (a ``YawCurriculum``) also its arguments (JSON key ``curriculum``) and its state blob
-    (member ``curriculum_state.bin``)."""
+    (member ``curriculum_state.bin``); with ``normalize`` (a ``VecNormalize``) its arguments (JSON key ``normalize``) and its state
+    blob (member ``normalize_state.bin``)."""
     import torch
     mv, step = opt.state()
     sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
@@ -270,6 +272,8 @@ def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iterati
                 iteration=iteration, adam_step=step, env_policy_steps=env_policy_steps, log=log, critic=critic)
     if curriculum is not None:
         meta["curriculum"] = curriculum.args()
+    if normalize is not None:
+        meta["normalize"] = normalize.args()
     with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
         z.writestr("policy.pth", pth.getvalue())
         z.writestr("adam_state.npy", npy(mv))
@@ -277,6 +281,8 @@ def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iterati
         z.writestr("windgym_ppo.json", json.dumps(meta))
         if curriculum is not None:
             z.writestr("curriculum_state.bin", curriculum.state())
+        if normalize is not None:
+            z.writestr("normalize_state.bin", normalize.state())
     return path
 
 
@@ -306,14 +312,21 @@ class PPO:
     update run on the shaped reward, the log gains ``curriculum_weight`` (mean of the rollout) and ``mean_yaw_diff`` while
     ``mean_step_reward`` / ``mean_episode_return`` stay the env's own.  ``None`` changes nothing.
 
+    ``normalize``: a ``normalize.VecNormalize`` of this env (a ``WindFarmVecEnv``), or a dict of its arguments — SB3's usual
+    set-up around the env: rollouts come from its ``rollout`` (the statistics move inside the closed loop), GAE and the update run
+    on the normalised rows and reward, ``predict`` normalises the rows it is given, the log gains ``mean_norm_reward`` and
+    ``ret_rms_var`` while ``mean_step_reward`` / ``mean_episode_return`` stay the env's own.  Not together with ``curriculum``
+    (``NotImplementedError``).  ``None`` changes nothing.
+
     ``save`` writes a zip whose ``policy.pth`` is a ``torch.save`` of the state dict under SB3's names (``read_sb3_zip`` and
     ``MlpPolicy.from_sb3_zip`` read it), next to Adam's state, the counters and the hyper-parameters as npy / JSON (with a
-    curriculum: its arguments under the JSON key ``curriculum`` and its state blob as ``curriculum_state.bin``); a zip that
+    curriculum: its arguments under the JSON key ``curriculum`` and its state blob as ``curriculum_state.bin``; with ``normalize``:
+    the JSON key ``normalize`` and ``normalize_state.bin``); a zip that
     SB3's own ``PPO.load`` accepts needs cloudpickled members and is out of scope."""
 
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
-                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None):
+                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None, normalize=None):
         for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
             if v is not None:
                 raise NotImplementedError(f"{name} is not implemented")
@@ -321,6 +334,16 @@ class PPO:
             raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
         check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm)
         n_steps, n_epochs = int(n_steps), int(n_epochs)
+        if normalize is not None:
+            from .normalize import VecNormalize, check_env
+            if curriculum is not None:
+                raise NotImplementedError("curriculum and normalize together are not implemented (VecNormalize.reward_pass is the seam "
+                                          "for shaping the reward before it is normalised)")
+            check_env(venv, "normalize")
+            if not isinstance(normalize, (dict, VecNormalize)):
+                raise ValueError("normalize must be a VecNormalize of this env or a dict of its arguments")
+            if isinstance(normalize, VecNormalize) and normalize.venv is not venv:
+                raise ValueError("normalize: the VecNormalize was built for another env")
         multi = getattr(venv, "possible_agents", None) is not None       # WindFarmVecEnvMulti: one row per (env, turbine)
         n_agents = int(venv.n_turb) if multi else 1
         n_rows = n_steps * int(venv.num_envs) * n_agents
@@ -377,6 +400,11 @@ class PPO:
         if curriculum is not None and curriculum.venv is not venv:
             raise ValueError("the curriculum was built for another env")
         self.curriculum = curriculum
+        self._owns_normalize = isinstance(normalize, dict)         # built here: closed with the trainer
+        if self._owns_normalize:
+            from .normalize import VecNormalize
+            normalize = VecNormalize(venv, **normalize)
+        self.normalize = normalize
 
     @staticmethod
     def _build_policy(venv, shape, kw, seed, n_in_vf=None):
@@ -393,7 +421,9 @@ class PPO:
     def collect(self):
         """One rollout of ``n_steps`` steps + wg_gae -> the rollout dict with ``advantage`` / ``returns`` ``[T, B]`` added
         (``[T, B, N]`` from wg_gae_shared on a ``WindFarmVecEnvMulti``; ``[T, B]`` again under its centralised critic)."""
-        if self.curriculum is None:
+        if self.normalize is not None:
+            out = self.normalize.rollout(self.policy, self.n_steps)
+        elif self.curriculum is None:
             out = self.venv.rollout(self.policy, self.n_steps)
         else:
             out = self.curriculum.rollout(self.policy, self.n_steps, num_timesteps=self.num_timesteps)
@@ -429,6 +459,8 @@ class PPO:
         parts = [stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)]
         if self.curriculum is not None:
             parts += [out["curriculum_weight"].mean().reshape(1), out["yaw_diff"].double().mean().reshape(1)]
+        if self.normalize is not None:
+            parts += [out["reward"].double().mean().reshape(1)]
         vec = t.cat(parts)
         host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
         rec = dict(zip(PPO_STATS, host[:8].tolist()))
@@ -439,16 +471,21 @@ class PPO:
                    mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"], fps=fps())
         if self.curriculum is not None:
             rec.update(curriculum_weight=float(host[-2]), mean_yaw_diff=float(host[-1]))
+        if self.normalize is not None:
+            rec.update(mean_norm_reward=float(host[-1]), ret_rms_var=self.normalize.ret_rms[1])      # (the statistics: a copy of their own)
         return rec
 
     def predict(self, obs, state=None, episode_start=None, deterministic=False):
+        if self.normalize is not None:
+            obs = self.normalize.normalize_obs(obs)
         return self.policy.predict(obs, state, episode_start, deterministic)
 
     # -- checkpoints ----------------------------------------------------------------------------------------------
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself (see the class docstring for the format)."""
         return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
-                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps, self.curriculum)
+                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps, self.curriculum,
+                                self.normalize)
 
     @classmethod
     def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
@@ -464,6 +501,7 @@ class PPO:
             mv = np.load(io.BytesIO(z.read("adam_state.npy")))
             gen = np.load(io.BytesIO(z.read("generator_state.npy")))
             cur_state = z.read("curriculum_state.bin") if "curriculum_state.bin" in z.namelist() else None
+            norm_state = z.read("normalize_state.bin") if "normalize_state.bin" in z.namelist() else None
         desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
         pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
                         device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"],
@@ -476,7 +514,10 @@ class PPO:
                 hyper[k] = v
             elif hyper[k] is None:
                 raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
-        self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), curriculum=meta.get("curriculum"), **hyper)   # (no key: written before there was one)
+        self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), curriculum=meta.get("curriculum"),
+                   normalize=meta.get("normalize"), **hyper)   # (no key: written before there was one)
+        if self.normalize is not None and norm_state is not None:
+            self.normalize.load_state(norm_state)
         if self.curriculum is not None and cur_state is not None:
             self.curriculum.load_state(cur_state)
         self.opt.load_state(mv, meta["adam_step"])
@@ -489,3 +530,5 @@ class PPO:
         self.opt.close()
         if self._owns_curriculum:
             self.curriculum.close()
+        if self._owns_normalize:
+            self.normalize.close()
