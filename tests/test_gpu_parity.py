@@ -592,8 +592,9 @@ def _compare_turb(env, orc, steps, rng, n_turb, B):
 
 @pytest.mark.parametrize("block", BLOCKS)
 def test_random_inflow_matches_oracle(hip, oracle_lib, block):
-    """turbtype "Random": counter-based gusts at the rotors and at the wake particles (meandering); every
-    k_flow<NT, RANDOM> instantiation."""
+    """turbtype "Random": counter-based gusts at the rotors and at the wake particles (meandering); the two k_flow<NT, RANDOM>
+    instantiations without sensor noise and with the Gaussian deficit, <64, compact> and <256, uniform rings> (the other six:
+    tests/test_gpu_variant_census.py)."""
     B = 6
     cfg = _turb_cfg("Random", B)
     env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
