@@ -968,7 +968,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                         const int H = kc->p.hlen[ch];
                         rbase[(unsigned)(kc->p.ring_off[ch] + fast_mod(n_pushed, H, kc->p.inv_hlen[ch]) * N + t)] = val[ch];      // (time-major: WgRing)
                     }
-                    if (SPLIT) {      // (what the glue would read back from the rings)
+                    if (GLUE != 0) {      // (what the glue would read back from the rings)
 #pragma unroll
                         for (int ch = 0; ch < WG_N_CH; ++ch) out.g_nw[ch] = val[ch];
                     }
@@ -1040,6 +1040,9 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         const unsigned tb = (unsigned)((e * 2 * F + kbase) * N + g);
         const float4 s4 = Lsrc4[g];
         const float2 s2 = Lsrc2[g];
+        // (the v / w stores stay although this kernel only ever writes zeros: the arrays have writers that do not — wg_ctx_init
+        // copies script_uvw's v, w under a flow script, whose launches go to the per-slot k_flow (it stores q.v, q.w), and
+        // wg_set_state restores whatever the blob holds — so a handle can come back to this kernel with other values in them)
         ke->d.yaw[tb] = yaw; ke->d.u[tb] = tu; ke->d.v[tb] = 0.f; ke->d.w[tb] = 0.f;
         ke->d.ti_loc[tb] = tti; ke->d.power[tb] = tpow; ke->d.ct[tb] = tct;
         if (SPLIT && split_on) {      // (the excursion bound is the pass wave's)
@@ -1067,7 +1070,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             if (farm == F - 1) cx.pend_base_n = my.pend_base_n;
         }
     }
-    if (SPLIT) {      // (the running episode's main wave: lane t of the agent farm is the glue's lane t)
+    if (GLUE != 0) {      // (the running episode's agent farm: its lane of turbine t holds what the glue's lane t would read back)
         out.g_yaw = yaw; out.g_old = oyaw; out.g_pw = tpow;
         out.g_pwb = F == 2 ? __shfl(tpow, min(tid + N, 63), 64) : 0.f;
     }
@@ -1141,9 +1144,24 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
         return;
     }
     if (GLUE != 0) {
-        // (every store of the flow part — rings, turbine state, headers, a prepared first observation — has left the wave
-        // before anything reads it back; LDS still holds the slots' records)
-        full_barrier<64>();
+        // The flow part's stores — rings, turbine state, slot / context headers, a prepared first observation — are waited for
+        // only where the glue reads some of them back: on a truncating step (the swap reads the other context's header, its
+        // next_obs / next_obs_ok, pend_farm / pend_base, slot words and — lean_swap's fallback — its rings and window sums), and
+        // in the kernels with a pass wave, which stay as they were.  On every other step the glue takes what this launch produced
+        // from the flow part's registers (LeanFused::regs: newest ring samples, yaw before / after, powers) and LDS (farm powers,
+        // the background slots' work, the header as the prologue loaded it), and its remaining loads are of words no store of
+        // the flow part aliases.  The walk through lean_step<., false, true> (the compiler checks none of this):
+        //   * wsum[live ctx] (old window sums): written by wg_sums_apply / the swaps alone — the glue itself; env_first_obs and
+        //     the episode set-up write the BACKGROUND context's sums;
+        //   * ring[live ctx], the leaving samples, row (np - W) % cap: the step pushed row np % cap, and W <= H < cap = H + 1
+        //     (sums mode: the ring holds one sample more than its deque), so the rows differ;
+        //   * farm_pow / base_pow [e] (oldest deque entries; the whole deque for the Power_diff reward): written by the glue and
+        //     the swaps — the flow part writes step_farm_pow / step_base_pow and the background context's pend_farm / pend_base;
+        //   * metrics[e]: the glue alone;
+        //   * the parameter blocks and the kernel's arguments: never written.
+        // Stores to a word both parts write (the background context's init_pending) leave the wave in program order.
+        // env_first_obs and the deferred set-up keep their own barriers (env_flow); LDS still holds the slots' records.
+        if (SPLIT != 0 || fo.truncates) full_barrier<64>();
         if (WPE == 2) {
             // Two waves per env.  The glue needs nothing of the background context's wave unless the env truncates in this step
             // (then it swaps that context in): the waves meet at a workgroup barrier ONLY then — both know from the env's header
@@ -1174,15 +1192,24 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
             if (WPE == 1) for (int f = 0; f < F; ++f) work = max(work, SLa[lb + f].dev_rem + K * SLa[lb + f].fill_rem);
             const int hw = reinterpret_cast<const int*>(sm + WG_ENV_OFF_HDR)[threadIdx.x & 31];
             LeanFused fz;
-            fz.pre = nullptr;
+            fz.pre = nullptr; fz.regs = SPLIT == 0;
+            // the glue's inputs: the step's own from the flow part's registers; the rest from the pass wave's fetch (long done) or,
+            // without a pass wave, by the glue's own loads
             if (SPLIT) {
-                // the glue's inputs: the step's own from this wave's registers, the rest from the pass wave's fetch (long done)
                 if (!env_flag_wait(reinterpret_cast<int*>(zone) + LEAN_PRE_FLAG)) atomicOr(kg->d.status, WG_STATUS_BIT_STATE);
-                const int gl = (int)(threadIdx.x & 63), own = gl < kg->p.N ? gl : 0;
                 fz.pre = zone;
+            }
+            const int gl = (int)(threadIdx.x & 63), own = gl < kg->p.N ? gl : 0;
+            if (WPE == 2) {      // (lane t of the live context's wave is the glue's lane t)
 #pragma unroll
                 for (int ch = 0; ch < WG_N_CH; ++ch) fz.nw[ch] = __shfl(fo.g_nw[ch], own, 64);
                 fz.yaw = fo.g_yaw; fz.old_yaw = fo.g_old; fz.pw = fo.g_pw; fz.pwb = fo.g_pwb;
+            } else {             // (one wave per env: the running episode's agent farm sits in lanes env_live * F * N + t)
+                const int src = fo.env_live * F * kg->p.N + own;
+#pragma unroll
+                for (int ch = 0; ch < WG_N_CH; ++ch) fz.nw[ch] = __shfl(fo.g_nw[ch], src, 64);
+                fz.yaw = __shfl(fo.g_yaw, src, 64); fz.old_yaw = __shfl(fo.g_old, src, 64);
+                fz.pw = __shfl(fo.g_pw, src, 64); fz.pwb = __shfl(fo.g_pwb, src, 64);
             }
             WG_STAMP(12);
             env_glue<GLUE, WPE>(kg, fz, fp, bp, work, fo, hw);

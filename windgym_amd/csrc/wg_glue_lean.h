@@ -315,6 +315,10 @@ struct LeanFused {
     // window sums, leaving samples, oldest deque entries, metrics — was fetched by the pass wave while the step ran and waits in
     // LDS (`pre`, layout LEAN_PRE_*; nullptr: the glue loads everything itself).
     const float* pre;
+    // k_flow_env without a pass wave (`regs`, with pre == nullptr): the same registers, and the glue loads what the step did not
+    // touch itself — none of it is written by the flow part, so these loads need not wait for that part's stores (the walk
+    // through them: k_flow_env, wg_env.hip).
+    int regs;
     float nw[WG_N_CH], yaw, old_yaw, pw, pwb;
 };
 // LDS zone of the pre-fetched glue inputs (floats; lane = the glue's lane): S[s] as doubles | lv[s] | metrics | deque entries | flag
@@ -328,7 +332,9 @@ struct LeanFused {
 // One env's glue after its flow step: power deques, window sums -> observation, reward, penalty, truncation, metrics, the
 // background episode's next share, and — at truncation — the swap.  One wave; `lane` 0 .. 63.
 // GEN = false: no TI and nothing farm-level in the observation — the instantiation of the shipped sensor sets.
-// FUSED: called by the env's own flow wave at the end of k_step_env (all of that wave's stores have been waited for).
+// FUSED: called by the env's own flow wave at the end of k_step_env.  That wave's stores have been waited for where this function
+// reads some of them back: always in k_flow_envb and in k_flow_env's pass-wave kernels, on a truncating step only in k_flow_env
+// without a pass wave (LeanFused::regs).
 template <bool MULTI, bool GEN, bool FUSED>
 __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, const WgParams* gp, const WgPtrs* gd, const int e,
                                           const int lane, float* __restrict__ obs_out, float* __restrict__ reward_out,
@@ -383,6 +389,7 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
     }
     // ---- every load of the step, issued together ----
     const bool pre = FUSED && !GEN && fz.pre != nullptr;
+    const bool regs = FUSED && !GEN && !pre && fz.regs != 0;
     SumsRaw raw;
     // (farms with more than 64 turbines, cfg3: the lane's SECOND turbine is requested with the first — the observation loop
     // below would otherwise take a second memory round trip for it)
@@ -399,27 +406,29 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
         // (the same values the loads below would return: the registers hold what this wave has just stored, the LDS zone what
         // nothing in this launch writes before the glue does)
         const double* const zs = reinterpret_cast<const double*>(fz.pre);
-        const unsigned msk = p.sum_mask_t | p.cur_mask_t;
 #pragma unroll
         for (int s = 0; s < WG_N_SUMS; ++s) { raw.S[s] = 0.0; raw.lv[s] = 0.f; }
 #pragma unroll
         for (int s = 0; s < WG_N_CH; ++s) {
             if ((p.sum_mask_t >> s) & 1u) { raw.S[s] = zs[LEAN_PRE_S(s, lane)]; raw.lv[s] = fz.pre[LEAN_PRE_LV(s, lane)]; }
         }
-#pragma unroll
-        for (int ch = 0; ch < WG_N_CH; ++ch) raw.nw[ch] = ((msk >> ch) & 1u) ? fz.nw[ch] : 0.f;
-        if (lane < N) { l_yaw = fz.yaw; l_old = fz.old_yaw; l_pow = fz.pw; if (F == 2) l_powb = fz.pwb; }
         f_old = wg_uni(fz.pre[LEAN_PRE_FOLD]); b_old = F == 2 ? wg_uni(fz.pre[LEAN_PRE_BOLD]) : 0.f;
         l_met = lane < WG_N_METRICS ? fz.pre[LEAN_PRE_MET(lane)] : 0.f;
     } else {
-        raw = wg_sums_load<GEN>(p, d, e, ctx_id, own, n_pushed_live);
+        raw = regs ? wg_sums_load<GEN, false>(p, d, e, ctx_id, own, n_pushed_live) : wg_sums_load<GEN>(p, d, e, ctx_id, own, n_pushed_live);
         if (have2) raw2 = wg_sums_load<GEN>(p, d, e, ctx_id, lane + WG_WAVE, n_pushed_live);
-        if (lane < N) {
+        if (!regs && lane < N) {
             l_yaw = d.yaw[tb_a + lane]; l_old = d.old_yaw[(size_t)e * N + lane]; l_pow = d.power[tb_a + lane];
             if (F == 2) l_powb = d.power[tb_a + N + lane];
         }
         f_old = wg_uni(fq[fslot]); b_old = F == 2 ? wg_uni(bq[bslot]) : 0.f;
         l_met = lane < WG_N_METRICS ? met[lane] : 0.f;
+    }
+    if (pre || regs) {      // what the step produced: the flow part's registers
+        const unsigned msk = p.sum_mask_t | p.cur_mask_t;
+#pragma unroll
+        for (int ch = 0; ch < WG_N_CH; ++ch) raw.nw[ch] = ((msk >> ch) & 1u) ? fz.nw[ch] : 0.f;
+        if (lane < N) { l_yaw = fz.yaw; l_old = fz.old_yaw; l_pow = fz.pw; if (F == 2) l_powb = fz.pwb; }
     }
     // background episode: remaining work of its farms (plan of the next step's share), pending set-up flag
     int work = 0;
