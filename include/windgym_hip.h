@@ -870,6 +870,86 @@ int wg_norm_reward(wg_norm n, int T, const float* reward_dev, const uint8_t* tru
 int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                     uint64_t row_offset, const wg_rollout_bufs* bufs, float* norm_obs_dev, float* norm_final_obs_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Recurrent policies: the LSTM front of sb3-contrib's MlpLstmPolicy (the reference's own trainer puts an nn.LSTM in front of its
+ * actor and critic, examples/curriculum.py:109-146).  A wg_lstm is one (shared_lstm) or two (lstm_actor, lstm_critic) one-layer
+ * LSTMs n_in -> hidden evaluated by ONE kernel (k_lstm, windgym_amd/csrc/wg_lstm.hip); the MLP behind it is an ordinary wg_policy
+ * that maps hidden -> n_out with its critic on hidden.  The cell is torch.nn.LSTM's (gate order i, f, g, o):
+ *     (h, c) <- (0, 0) for rows with episode_start != 0
+ *     z = (b_ih + b_hh) + [W_ih | W_hh] (x ‖ h);  c' = sigmoid(z_f) c + sigmoid(z_i) tanh(z_g);  h' = sigmoid(z_o) tanh(c')
+ * The episode-start mask is a SELECT: such a row does not depend on its incoming state at all, also where that state holds NaN
+ * (sb3-contrib multiplies the state by 1 - episode_start; for finite states the two agree).  The two biases are added once, when
+ * the parameters are packed, and the sum starts the k-ordered f32 accumulation over x then h.  Inference only: training through
+ * time is not part of this ABI yet — wg_rollout_lstm records what it will need (the initial state, the episode starts).
+ * Bounds (WG_ERR_UNSUPPORTED outside): n_in <= 2048, 1 <= hidden <= 256.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_lstm_s* wg_lstm;
+typedef struct wg_lstm_desc {
+    int32_t n_in, hidden;
+    int32_t n_nets;            /* 2: actor and critic LSTMs; 1: one LSTM whose h' both MLPs read (shared_lstm)       */
+} wg_lstm_desc;
+enum { WG_LSTM_ACTOR = 1, WG_LSTM_CRITIC = 2 };            /* bits of wg_lstm_step's net_mask                         */
+
+int wg_lstm_create(const wg_lstm_desc* d, int device, wg_lstm* out);      /* all parameters 0 until wg_lstm_set_params */
+int wg_lstm_destroy(wg_lstm l);
+int wg_lstm_n_params(wg_lstm l, size_t* n);
+/* All parameters as ONE flat f32 vector of wg_lstm_n_params floats: per net, the actor's first, weight_ih [4 hidden][n_in],
+ * weight_hh [4 hidden][hidden], bias_ih [4 hidden], bias_hh [4 hidden] (torch.nn.LSTM's *_l0 tensors, rows in gate order
+ * i, f, g, o).  Host (on_device = 0; must stay valid until the stream reaches the copy) or device pointer; stream-ordered copy +
+ * repack into the kernel's layout, no synchronisation.                                                                */
+int wg_lstm_set_params(wg_lstm l, const float* params, size_t n, int on_device, void* stream);
+
+/* One step of the nets in net_mask (0 = all the handle has) on n_rows rows: x_dev f32[n_rows, n_in], episode_start_dev
+ * u8[n_rows] or NULL (no row starts an episode), state_in_dev f32[n_nets][2][n_rows][hidden] (per net h then c; the planes of a
+ * net that is masked out are neither read nor written) -> state_out_dev in the same layout and h_pi_dev / h_vf_dev
+ * f32[n_rows, hidden], the new h of the actor's / the critic's LSTM.  state_out_dev may BE state_in_dev (in place), and may be
+ * NULL: h' is computed and the new state discarded (what a bootstrap value of a final observation needs).  h_pi_dev / h_vf_dev
+ * may be NULL.  fp32, bit-identical from run to run, and a row's result does not depend on n_rows, on the other rows or on
+ * which nets the call evaluates.  One launch, asynchronous on `stream`, allocates and synchronises nothing.
+ * WG_ERR_INVALID: a null x_dev / state_in_dev, n_rows < 0, a net_mask bit or an h output of a net the call does not evaluate. */
+int wg_lstm_step(wg_lstm l, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
+                 float* state_out_dev, float* h_pi_dev, float* h_vf_dev, int net_mask, void* stream);
+
+/* The recurrent policy's wg_policy_act: `p` is an ordinary wg_policy that maps the LSTM's hidden size H -> n_out with its critic on H.
+ * Two launches, bit-identical to
+ *     wg_lstm_step(l, n_rows, x, episode_start, state_in, state_out, h_pi, h_vf, actor | (critic if value_dev and l has two nets))
+ *     wg_policy_act(p, n_rows, h_pi, deterministic, seed, counter, row_offset, action, raw, logp, NULL)
+ *     wg_policy_act(p, n_rows, h_vf, value only -> value_dev)            if wanted (a shared LSTM: h_vf = h_pi)
+ * with h_pi = h_dev, h_vf = h_dev + n_rows * H: h_dev f32[2][n_rows][H] is the caller's scratch for the two h' row sets.  Without
+ * value_dev the critic's LSTM is not evaluated and its planes of state_out_dev are not written.
+ * WG_ERR_INVALID: what the two calls refuse; p's n_in or its critic's width != H; l and p on different devices.               */
+int wg_lstm_act(wg_lstm l, wg_policy p, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
+                float* state_out_dev, float* h_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
+                float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream);
+
+/* Caller-owned device buffers of wg_rollout_lstm besides wg_rollout_bufs; B of the handle, H / nets of the wg_lstm. */
+typedef struct wg_rollout_lstm_bufs {
+    float*   state;          /* [nets][2][B][H]  in / out: the LSTM state the loop starts from and ends in                */
+    float*   state0;         /* [nets][2][B][H]  or NULL: a copy of the incoming state (what a trainer unrolls from)      */
+    uint8_t* episode_start;  /* [T+1, B]         slot 0 is INPUT; slot t+1 = truncated[t]                                  */
+    float*   scratch;        /* [3][B][H]        the loop's h_pi, h_vf and the critic's h' on the final rows               */
+} wg_rollout_lstm_bufs;
+
+/* wg_rollout for a recurrent policy: `lstm` reads the observation rows, `p` is an ordinary wg_policy that maps H -> n_turb with
+ * its critic on H.  Buffers, the handle's state and lstm_bufs->state afterwards are BIT-IDENTICAL to
+ *     state0 = state                                                                        if wanted
+ *     for t in 0 .. T-1:
+ *         wg_lstm_step(lstm, B, obs[t], episode_start[t], state, state, h_pi, h_vf, all nets)       (a shared LSTM: h_vf = h_pi)
+ *         wg_policy_act(p, B, h_pi, deterministic, seed, counter0 + t, row_offset, actions[t], raw[t], logp[t], NULL)
+ *         wg_policy_act(p, B, h_vf, value only -> value[t])                                 if wanted
+ *         wg_step(h, actions[t], obs[t+1], reward[t], truncated[t], final_obs[t])
+ *         wg_get_info(h, info_fields[i], info_out[i] + t * <size of the field>)             for every i
+ *         episode_start[t+1] = truncated[t]
+ *         wg_lstm_step(lstm, B, final_obs[t], NULL, state, NULL, critic's net only -> h_fin)  \ if final_value
+ *         wg_policy_act(p, B, h_fin, value only -> final_value[t])                            / is wanted
+ * final_value[t] is sb3-contrib's bootstrap from the terminal LSTM state: the critic on (final_obs[t], the state after step t,
+ * no episode start), that state left as it is.  For an env that was not truncated this is the arithmetic of step t+1's value.
+ * A row's results do not depend on which launch computes them: the loop itself runs the final rows of step t-1 in front of step t.
+ * WG_ERR_INVALID: what wg_rollout refuses, with p's n_in / its critic's width != lstm's hidden, lstm's n_in != the handle's
+ * obs_dim, lstm on another device than the handle, a null lstm_bufs or one without state / episode_start / scratch.            */
+int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                    uint64_t row_offset, const wg_rollout_bufs* bufs, const wg_rollout_lstm_bufs* lstm_bufs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,12 @@ centralised on the flat observation (`--critic central`: obs_dim -> 64 -> 64 -> 
 actions), `loop_hip_policy` (the loop of single calls the rollout is documented as: act, value, step, value of the final rows) and
 `rollout_hip_policy` (WindFarmVecEnvMulti.rollout: the same inside the library).
 
-usage: python tools/bench_policy.py [--envs 4096] [--api-steps 2000] [--multi [--critic agent|central]]
+With --lstm H the same workload is also run with a recurrent policy (recurrent.MlpLstmPolicy: two LSTMs 32 -> H in front of the MLP
+H -> 64 -> 64 -> 16 / 1), its legs beside the MLP's: `lstm_closed_loop_torch_policy` (torch_forward + sample + step in eager torch),
+`lstm_closed_loop_hip_policy` (act + step: k_lstm, k_policy and the step kernel per step) and `lstm_rollout_hip_policy`
+(venv.rollout: wg_rollout_lstm, with final_value).
+
+usage: python tools/bench_policy.py [--envs 4096] [--api-steps 2000] [--lstm H] [--multi [--critic agent|central]]
 """
 import argparse
 import json
@@ -99,6 +104,7 @@ def main():
     ap.add_argument("--envs", type=int, default=None, help="default: 4096 (--multi: 2048)")
     ap.add_argument("--multi", action="store_true", help="cfg4: one policy shared by the turbines of a 3x3 farm")
     ap.add_argument("--critic", choices=("agent", "central"), default="agent", help="with --multi: what the critic reads")
+    ap.add_argument("--lstm", type=int, default=0, metavar="H", help="also time a recurrent policy with LSTMs of hidden size H (off: 0)")
     ap.add_argument("--api-steps", type=int, default=2000, help="timed steps of each leg")
     ap.add_argument("--preroll", type=int, default=300, help="untimed steps that take the batch out of its synchronised start")
     args = ap.parse_args()
@@ -187,10 +193,52 @@ def main():
     out["rollout_hip_policy"] = {"value": B * steps / el, "unit": "env-steps/s", "ms_per_step": el / steps * 1e3,
                                  "host_us_per_call": host / steps * 1e6}
     out["policy"] = {"n_in": o_dim, "n_out": venv.n_turb, "hidden_pi": [64, 64], "hidden_vf": [64, 64], "activation": "tanh"}
+    legs = ["vecenv_torch", "closed_loop_torch_policy", "closed_loop_hip_policy", "rollout_hip_policy"]
+    if args.lstm:
+        from windgym_amd.recurrent import MlpLstmPolicy
+        rp = MlpLstmPolicy(o_dim, venv.n_turb, args.lstm, (64, 64), (64, 64), device=0, seed=1234)
+        r_log_std = rp.state_dict()["log_std"]
+        rs = {"obs": venv.batch.obs, "h": rp.initial_state(B), "start": torch.zeros(B, dtype=torch.uint8, device=dev)}
+
+        def lstm_torch_step(i):
+            with torch.no_grad():
+                mean, value, rs["h"] = rp.torch_forward(rs["obs"], rs["h"], rs["start"])
+                eps = torch.randn_like(mean)
+                raw = mean + r_log_std.exp() * eps
+                logp = (-0.5 * eps * eps - r_log_std - 0.9189385332046727).sum(-1)     # noqa: F841
+                rs["obs"], _, _, trunc, _ = venv.step(raw.clamp(-1.0, 1.0))
+                rs["start"] = trunc.view(torch.uint8)
+
+        def lstm_hip_step(i):
+            (a, _, _, _), _ = rp.act(rs["obs"], rs["h"], rs["start"], state_out=rs["h"])
+            rs["obs"], _, _, trunc, _ = venv.step(a)
+            rs["start"].copy_(trunc.view(torch.uint8))
+
+        out["lstm_closed_loop_torch_policy"] = measure(lstm_torch_step)
+        rs.update(obs=venv.batch.obs, h=rp.initial_state(B), start=torch.zeros(B, dtype=torch.uint8, device=dev))
+        out["lstm_closed_loop_hip_policy"] = measure(lstm_hip_step)
+        venv.rollout(rp, steps)                      # warm-up: allocates the buffers for this T
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        venv.rollout(rp, steps)
+        host = time.perf_counter() - t0
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        venv.rollout(rp, steps)
+        torch.cuda.synchronize(dev)
+        el = time.perf_counter() - t0
+        out["lstm_rollout_hip_policy"] = {"value": B * steps / el, "unit": "env-steps/s", "ms_per_step": el / steps * 1e3,
+                                          "host_us_per_call": host / steps * 1e6,
+                                          "speedup_vs_torch": B * steps / el / out["lstm_closed_loop_torch_policy"]["value"],
+                                          "frac_of_mlp_rollout": B * steps / el / out["rollout_hip_policy"]["value"]}
+        out["lstm_policy"] = {"n_in": o_dim, "n_out": venv.n_turb, "lstm_hidden_size": args.lstm, "hidden_pi": [64, 64], "hidden_vf": [64, 64],
+                              "shared_lstm": False, "activation": "tanh"}
+        legs += ["lstm_closed_loop_torch_policy", "lstm_closed_loop_hip_policy", "lstm_rollout_hip_policy"]
+        rp.close()
     venv.batch.check()
     policy.close()
     venv.close()
-    for k in ("vecenv_torch", "closed_loop_torch_policy", "closed_loop_hip_policy", "rollout_hip_policy"):
+    for k in legs:
         out[k]["frac_of_abi"] = out[k]["value"] / out["abi"]["value"]
     print(json.dumps(out))
 

@@ -23,6 +23,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("MlpPolicy", "read_sb3_zip"):
         from . import policy
         return getattr(policy, name)
+    if name in ("MlpLstmPolicy", "read_sb3_lstm_zip"):
+        from . import recurrent
+        return getattr(recurrent, name)
     if name in ("PPO", "PPOOptimizer"):
         from . import ppo
         return getattr(ppo, name)

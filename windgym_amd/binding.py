@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "wg_curriculum_shape",
     "wg_norm_create", "wg_norm_destroy", "wg_norm_get_state", "wg_norm_set_state", "wg_norm_set_training", "wg_norm_reset_returns",
     "wg_norm_obs", "wg_norm_reward", "wg_rollout_norm",
+    "wg_lstm_create", "wg_lstm_destroy", "wg_lstm_n_params", "wg_lstm_set_params", "wg_lstm_step", "wg_lstm_act", "wg_rollout_lstm",
 )
 
 _lib = None
@@ -97,6 +98,17 @@ class CNormDesc(C.Structure):
                 ("clip_obs", C.c_float), ("clip_reward", C.c_float), ("gamma", C.c_double), ("epsilon", C.c_double)]
 
 
+class CLstmDesc(C.Structure):
+    """wg_lstm_desc"""
+    _fields_ = [("n_in", C.c_int32), ("hidden", C.c_int32), ("n_nets", C.c_int32)]
+
+
+class CRolloutLstmBufs(C.Structure):
+    """wg_rollout_lstm_bufs"""
+    _fields_ = [("state", C.c_void_p), ("state0", C.c_void_p), ("episode_start", C.c_void_p), ("scratch", C.c_void_p)]
+
+
+LSTM_ACTOR, LSTM_CRITIC = 1, 2          # WG_LSTM_ACTOR / WG_LSTM_CRITIC
 PPO_STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss", "adv_mean", "adv_std")   # wg_ppo_stats
 
 
@@ -212,6 +224,14 @@ def load_library():
     L.wg_norm_reward.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
     L.wg_rollout_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
                                   C.POINTER(CRolloutBufs), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_lstm_create.argtypes = [C.POINTER(CLstmDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_lstm_destroy.argtypes = [C.c_void_p]
+    L.wg_lstm_n_params.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.wg_lstm_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    L.wg_lstm_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+    L.wg_lstm_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
+    L.wg_rollout_lstm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                  C.POINTER(CRolloutBufs), C.POINTER(CRolloutLstmBufs), C.c_void_p]
     _lib = L
     return L
 
@@ -343,6 +363,15 @@ class HipBatch:
         _chk(self.L.wg_rollout_norm(self._h, policy._h, norm._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
                                     C.byref(cb), bufs["norm_obs"].data_ptr(), bufs["norm_final_obs"].data_ptr(), self._stream()),
              "wg_rollout_norm")
+
+    def rollout_lstm(self, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
+        """wg_rollout_lstm, the arguments of :meth:`rollout` with a ``recurrent.MlpLstmPolicy``: ``bufs`` also holds ``lstm_state``
+        (in / out), ``lstm_state0``, ``episode_start`` ``[T+1, B]`` (slot 0 is input) and ``lstm_scratch``."""
+        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
+        lb = CRolloutLstmBufs(bufs["lstm_state"].data_ptr(), bufs["lstm_state0"].data_ptr(), bufs["episode_start"].data_ptr(),
+                              bufs["lstm_scratch"].data_ptr())
+        _chk(self.L.wg_rollout_lstm(self._h, policy._lstm, policy.mlp._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
+                                    C.byref(cb), C.byref(lb), self._stream()), "wg_rollout_lstm")
 
     def rollout_multi(self, *args):
         """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""

@@ -846,6 +846,10 @@ struct RolloutRows {
     // non-null: the policy's rows are NORMALISED copies of the steps' flat rows (wg_rollout_norm) — after every step the
     // observation half of this wg_norm is enqueued: o.obs[t + 1] -> o.obs_multi[t + 1], o.final_obs[t] -> o.final_obs_multi[t]
     wg_norm_s* norm;
+    // non-null: a recurrent policy (wg_rollout_lstm) — the observation rows go through this wg_lstm first (state and episode starts
+    // in `lb`), and the policy, which maps the LSTM's hidden size, reads the h' rows of lb->scratch instead of the observations
+    wg_lstm_s* lstm;
+    const wg_rollout_lstm_bufs* lb;
 };
 
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
@@ -872,6 +876,12 @@ static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, i
     return 0;
 }
 
+static int lstm_nets(const RolloutRows& g) {
+    int n_in = 0, H = 0, nets = 0, dev = 0;
+    (void)wg_lstm_geometry_(g.lstm, &n_in, &H, &nets, &dev);
+    return nets;
+}
+
 // The per-agent buffers of step t are the kernel arguments of that step's launches (WgPtrs travels by value), so pointing the
 // handle's two per-agent pointers at slot t on the host between launches is all "wg_set_obs_multi_buffer per step" takes: no
 // device copy of the parameter block is read for them, nothing is synchronised.
@@ -880,20 +890,46 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     const wg_rollout_multi_bufs& o = g.o;
     hipStream_t st = (hipStream_t)stream;
     const int B = h->p.B, R = B * g.per_env, V = B * g.v_env;
-    const size_t sBO = (size_t)B * h->p.obs_dim, sR = (size_t)R, sRO = sR * g.n_in, sRN = sR * g.n_out;
+    const size_t sBO = (size_t)B * h->p.obs_dim, sR = (size_t)R, sRO = g.lstm ? sBO : sR * g.n_in, sRN = sR * g.n_out;
     const size_t sV = (size_t)V, sVO = sV * g.v_in;
     float* const multi0 = h->d.multi_out;
     float* const fin0 = h->d.multi_fin;
     int rc = 0;
+    // a recurrent policy: the rows the policy reads are the LSTMs' h' of the step (scratch: h_pi, h_vf, h_fin); a shared LSTM's
+    // critic reads h_pi, and its "critic net" is the one net it has
+    const bool two = g.lstm && lstm_nets(g) == 2;
+    const size_t sH = g.lstm ? (size_t)B * g.n_in : 0;
+    float* const h_pi = g.lstm ? g.lb->scratch : nullptr;
+    float* const h_vf = two ? h_pi + sH : h_pi;
+    float* const h_fin = g.lstm ? h_pi + 2 * sH : nullptr;
+    // the critic's LSTM on the final rows of step t, from the state after step t, which stays as it is -> h_fin
+    auto lstm_final = [&](int t) {
+        return wg_lstm_step(g.lstm, B, o.final_obs + t * sBO, nullptr, g.lb->state, nullptr, two ? nullptr : h_fin, two ? h_fin : nullptr,
+                            two ? WG_LSTM_CRITIC : WG_LSTM_ACTOR, stream);
+    };
+    if (g.lstm && g.lb->state0 && n_steps > 0) {
+        const hipError_t ce = hipMemcpyAsync(g.lb->state0, g.lb->state, sizeof(float) * (two ? 2 : 1) * 2 * sH, hipMemcpyDeviceToDevice, st);
+        if (ce != hipSuccess) return fail(WG_ERR_HIP, std::string(g.who) + ": copy of the initial state failed: " + hipGetErrorString(ce));
+    }
     // ONE launch of k_policy per step: the actor on step t's rows and, as further slots, the critic on its rows of step t and
     // final_value[t - 1] = V(final rows of step t - 1) (a row's value does not depend on what else the launch computes); the last
     // final_value by a launch of its own
     for (int t = 0; t < n_steps && !rc; ++t) {
         WgValueRows v[2];
         int nv = 0;
-        if (o.value) v[nv++] = {g.v_obs + t * sVO, o.value + t * sV, V};
-        if (o.final_value && t > 0) v[nv++] = {g.v_fin + (t - 1) * sVO, o.final_value + (t - 1) * sV, V};
-        if (g.pop)      // (the same rows, found through the population's slot table: step t's own and the final rows of t - 1)
+        if (o.value) v[nv++] = {g.lstm ? h_vf : g.v_obs + t * sVO, o.value + t * sV, V};
+        if (o.final_value && t > 0) v[nv++] = {g.lstm ? h_fin : g.v_fin + (t - 1) * sVO, o.final_value + (t - 1) * sV, V};
+        if (g.lstm) {
+            // (the final rows of step t - 1 first: they read the state that step t's launch then advances in place; the episode
+            // starts of step t > 0 are read where the step before wrote them, truncated[t - 1] = what episode_start[t] will hold)
+            if (o.final_value && t > 0) rc = lstm_final(t - 1);
+            if (!rc)
+                rc = wg_lstm_step(g.lstm, B, o.obs_multi + t * sRO, t == 0 ? g.lb->episode_start : o.truncated + (size_t)(t - 1) * B,
+                                  g.lb->state, g.lb->state, h_pi, two ? h_vf : nullptr, 0, stream);
+            if (!rc)
+                rc = wg_policy_eval_(p, R, h_pi, deterministic, seed, counter0 + (uint64_t)t, row_offset, o.actions + t * sRN,
+                                     o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
+        } else if (g.pop)      // (the same rows, found through the population's slot table: step t's own and the final rows of t - 1)
             rc = wg_pop_launch_(g.pop, 1, t > 0, t, deterministic, counter0 + (uint64_t)t, stream);
         else
             rc = wg_policy_eval_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
@@ -916,8 +952,13 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     }
     h->d.multi_out = multi0;      // the handle's own per-agent buffers again, on every way out (the device copies never changed)
     h->d.multi_fin = fin0;
+    if (!rc && g.lstm && n_steps > 0) {      // episode_start[t + 1] = truncated[t] for every t: one contiguous block
+        const hipError_t ce = hipMemcpyAsync(g.lb->episode_start + B, o.truncated, (size_t)n_steps * B, hipMemcpyDeviceToDevice, st);
+        if (ce != hipSuccess) rc = fail(WG_ERR_HIP, std::string(g.who) + ": copy of the episode starts failed: " + hipGetErrorString(ce));
+        if (!rc && o.final_value) rc = lstm_final(n_steps - 1);
+    }
     if (!rc && o.final_value && n_steps > 0) {
-        const WgValueRows v = {g.v_fin + (n_steps - 1) * sVO, o.final_value + (n_steps - 1) * sV, V};
+        const WgValueRows v = {g.lstm ? h_fin : g.v_fin + (n_steps - 1) * sVO, o.final_value + (n_steps - 1) * sV, V};
         if (g.pop) rc = wg_pop_launch_(g.pop, 0, 1, n_steps, 1, 0, stream);
         else rc = wg_policy_eval_(p, 0, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, &v, 1, stream);
     }
@@ -1006,6 +1047,31 @@ extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deter
     // (allocated by the first call that needs it, before anything is enqueued)
     if (!o->obs && !h->flat_scratch)
         if (int rc = dev_alloc(h, &h->flat_scratch, (size_t)B * h->p.obs_dim, false)) return rc;
+    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+}
+
+// A recurrent policy: the checks are wg_rollout's with the policy on the LSTM's hidden rows, the loop is rollout_loop with the LSTM's
+// launches in front of the policy's.
+extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
+                               uint64_t row_offset, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
+    if (!h || !lstm || !p || !o || !lb) return fail(WG_ERR_INVALID, "wg_rollout_lstm: null argument");
+    const int N = h->p.N, O = h->p.obs_dim;
+    int l_in = 0, H = 0, nets = 0, l_device = 0;
+    if (int rc = wg_lstm_geometry_(lstm, &l_in, &H, &nets, &l_device)) return rc;
+    if (l_in != O)
+        return fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm reads rows of " + std::to_string(l_in) + " inputs, the handle's obs_dim is " + std::to_string(O));
+    if (l_device != h->device) return fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm and handle live on different devices");
+    if (!lb->state || !lb->episode_start || !lb->scratch)
+        return fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm_bufs needs state, episode_start and scratch");
+    if (p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, "wg_rollout_lstm: p needs a critic (on the LSTM's hidden rows)");
+    const RolloutRows g = {"wg_rollout_lstm", "obs", 1, H, N,
+                           ": p reads the LSTM's hidden rows, and lstm's hidden size / the handle's n_turb are " + std::to_string(H) + " / " + std::to_string(N),
+                           nullptr, false,
+                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
+                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
+                           1, H, o->obs, o->final_obs, "final_obs", nullptr, nullptr, lstm, lb};
+    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
+    if (int rc = use_device(h)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
 }
 

@@ -33,6 +33,8 @@ int wg_set_last_error_(int code, const char* msg);
 int wg_handle_actuation_(wg_handle h, WgActuation* out);
 // wg_norm.hip: the widths a wg_norm was created for and its device (wg_rollout_norm's checks)
 int wg_norm_geometry_(wg_norm n, int* n_obs, int* n_envs, int* device);
+// wg_lstm.hip: the shape a wg_lstm was created for and its device (wg_rollout_lstm's checks)
+int wg_lstm_geometry_(wg_lstm l, int* n_in, int* hidden, int* n_nets, int* device);
 // wg_policy.hip: ONE launch of k_policy — the actor on n_rows rows of obs_dev (when action / raw / logp is wanted) and the critic on
 // each of n_v <= 2 row sets of its own (rows of the critic's input width -> value); a set of no rows is skipped
 int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,

@@ -18,6 +18,8 @@ import time
 
 import numpy as np
 
+from .policy import refuse_recurrent
+
 ARGS = ("curriculum_steps", "pure_similarity_steps", "model", "refine_pass_n", "yaw_n", "search_yaw_max", "reward_momentum")
 
 
@@ -178,6 +180,7 @@ class YawCurriculum:
         ``venv.rollout``'s: valid until the next call.  ``timing``: a dict that receives the milliseconds of the parts
         (``rollout``, ``serial_refine``, ``k_curriculum``, ``plumbing`` = everything else), measured between device
         synchronisations — tools/bench_ppo.py's split; it slows the call."""
+        refuse_recurrent(policy, "YawCurriculum.rollout()")
         if getattr(policy, "population", None) is not None:
             raise NotImplementedError("a curriculum for a population is not implemented")
         t, b = self.torch, self.batch

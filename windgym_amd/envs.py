@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import copy
 import math
+import weakref
 from collections import deque
 from typing import Optional
 
@@ -223,6 +224,7 @@ class WindFarmVecEnv(_gym_vector_base()):
         self._was_reset = False          # the first reset() without a seed uses the base seed
         self._policy_steps = 0           # rollout()'s noise counter: policy steps taken so far (PPO.save / load keep it)
         self._rollout_bufs = {}          # rollout()'s buffers by (rows, T, record, values, stochastic_ok)
+        self._lstm = {}                  # rollout() of recurrent policies: id(policy) -> [weakref, LSTM state, pending episode starts]
         self._actions = self.torch.zeros((self.num_envs, self.n_turb), dtype=self.torch.float32,
                                          device=self.batch.device)
         self._term = None
@@ -251,6 +253,11 @@ class WindFarmVecEnv(_gym_vector_base()):
         seeds = self._seeds(seed if seed is not None else (self._base_seed if not self._was_reset else None))
         self._was_reset = True
         obs = self.batch.reset(seeds=seeds, mask=mask)
+        for ent in self._lstm.values():          # the next rollout() of a recurrent policy starts these envs' episodes
+            if mask is None:
+                ent[2].fill_(1)
+            else:
+                ent[2].masked_fill_(self.torch.from_numpy(np.asarray(mask).reshape(-1) != 0).to(ent[2].device), 1)
         return self._out(obs), self.infos()
 
     def _step_device(self, actions):
@@ -285,7 +292,7 @@ class WindFarmVecEnv(_gym_vector_base()):
         infos["_final_obs"] = trunc_b
         return self._out(obs), self._out(rew), self._out(term), trunc_b, infos
 
-    def rollout(self, policy, n_steps, *, deterministic=False, record=(), values=True):
+    def rollout(self, policy, n_steps, *, deterministic=False, record=(), values=True, state=None):
         """``n_steps`` closed-loop steps ``policy -> step`` enqueued by ONE library call (wg_rollout: no return to Python, no
         host synchronisation in between).  Returns a dict of CUDA tensors, T = n_steps: ``obs [T+1, B, O]`` (``obs[0]`` = the
         batch's current observation), ``actions`` / ``raw [T, B, N]``, ``logp``, ``value``, ``final_value``, ``reward [T, B]``,
@@ -305,8 +312,20 @@ class WindFarmVecEnv(_gym_vector_base()):
 
         ``policy`` may be a ``population.Population`` (or a ``PPOPopulation``): its P members act on the envs
         ``[m * Bm, (m + 1) * Bm)`` of the same buffers, still one policy launch per step (wg_pop_rollout), with this method's noise
-        rule — a population whose members hold the same weights fills the buffers one policy would."""
+        rule — a population whose members hold the same weights fills the buffers one policy would.
+
+        ``policy`` may be a ``recurrent.MlpLstmPolicy`` (wg_rollout_lstm).  The dict then also holds ``episode_start [T+1, B]``
+        (uint8; slot 0 = the starts this rollout began with, slot t+1 = ``truncated[t]``), ``lstm_state0`` and ``lstm_state``
+        ``[nets, 2, B, H]``: the LSTM state before and after.  The state of a (policy, env) pair is KEPT between rollouts — a
+        second ``rollout()`` continues the first; ``reset()`` marks every env (of its mask) as an episode start, a pair's first
+        rollout starts every env.  ``state=`` (a tensor like ``lstm_state``) overrides the kept state.  ``step()`` calls in between
+        do NOT advance it: the policy never saw those observations.  ``final_value[t]`` bootstraps from the LSTM state after step
+        t (sb3-contrib's rule).  ``sample_site`` is not supported with a recurrent policy."""
         b = self.batch
+        if getattr(policy, "recurrent", False):
+            return self._rollout_recurrent(policy, n_steps, deterministic, record, values, state)
+        if state is not None:
+            raise ValueError("rollout(): state= applies to a recurrent policy (MlpLstmPolicy)")
         pop = getattr(policy, "population", None)      # a population.Population / PPOPopulation: wg_pop_rollout, member m on its envs
         if pop is not None and self.num_envs % pop.n_members:
             raise ValueError(f"rollout(): the {pop.n_members} members own equal shares of the envs: num_envs = {self.num_envs} "
@@ -314,6 +333,36 @@ class WindFarmVecEnv(_gym_vector_base()):
         return self._rollout(policy if pop is None else pop, n_steps, deterministic, record, values, rows=(self.num_envs,),
                              shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
                              slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout if pop is None else b.rollout_pop)
+
+    def _rollout_recurrent(self, policy, n_steps, deterministic, record, values, state):
+        """``rollout()`` of an ``MlpLstmPolicy``: :meth:`_rollout` with wg_rollout_lstm as the loop, around the pair's kept state."""
+        t, b = self.torch, self.batch
+        T, B = int(n_steps), self.num_envs
+        if self._site is not None:
+            raise NotImplementedError("rollout(): a recurrent policy with sample_site is not implemented")
+        ent = self._lstm.get(id(policy))
+        if ent is None or ent[0]() is not policy:
+            self._lstm = {k: e for k, e in self._lstm.items() if e[0]() is not None}
+            ent = self._lstm[id(policy)] = [weakref.ref(policy), policy.initial_state(B),
+                                            t.ones(B, dtype=t.uint8, device=b.device), {}]
+        if state is not None:
+            if not (isinstance(state, t.Tensor) and tuple(state.shape) == tuple(ent[1].shape)):
+                raise ValueError(f"rollout(): state must be a tensor {tuple(ent[1].shape)} (nets, h | c, envs, H)")
+            ent[1].copy_(state)
+        if T < 1:
+            raise ValueError("rollout(): n_steps must be >= 1")
+        extra = ent[3].get(T)
+        if extra is None:
+            extra = ent[3][T] = dict(lstm_state=ent[1], lstm_state0=t.zeros_like(ent[1]),
+                                     episode_start=t.zeros((T + 1, B), dtype=t.uint8, device=b.device),
+                                     lstm_scratch=t.zeros((3, B, policy.H), dtype=t.float32, device=b.device))
+        extra["episode_start"][0].copy_(ent[2])
+        out = self._rollout(policy, T, deterministic, record, values, rows=(B,), shape=(b.obs_dim, self.n_turb),
+                            needs=f"the env needs {b.obs_dim} -> {self.n_turb}", slots=(("obs", "final_obs", b.obs, b.final_obs),),
+                            run=lambda pol, n, bufs, *a: b.rollout_lstm(pol, n, {**bufs, **extra}, *a))
+        ent[2].copy_(extra["episode_start"][T])
+        out.update(episode_start=extra["episode_start"], lstm_state0=extra["lstm_state0"], lstm_state=ent[1])
+        return out
 
     def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run, critic=None, norm=None):
         """``rollout()`` of this class and of :class:`WindFarmVecEnvMulti`.  ``rows``: the axes of the policy's rows, ``(B,)`` or
@@ -1154,6 +1203,8 @@ class WindFarmVecEnvMulti:
         CENTRALISED critic) ``value`` / ``final_value`` are ``[T, B]`` = ``V(flat_obs[t])`` / ``V(flat_final_obs[t])``, one per env
         and shared by its agents; everything else is unchanged and does not depend on the critic.  Advantages: wg_gae on
         ``[T, B]``."""
+        if getattr(policy, "recurrent", False):
+            raise NotImplementedError("WindFarmVecEnvMulti.rollout(): a recurrent policy (MlpLstmPolicy) shared by the turbines is not implemented")
         b = self.batch
         return self.venv._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs, self.n_turb),
                                   shape=(self.obs_len, 1),

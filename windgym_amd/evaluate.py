@@ -48,6 +48,7 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
         box_ids = np.array([c[3] for c in conds4], dtype=np.int32)
     B = len(conds)
     from .policy import MlpPolicy
+    recurrent = bool(getattr(model, "recurrent", False))          # a recurrent.MlpLstmPolicy: the device path takes it too
     if normalize is not None:
         if not (isinstance(model, MlpPolicy) and t_sim > 1):
             raise ValueError("normalize applies to the device rollout of an MlpPolicy (t_sim > 1)")
@@ -84,7 +85,7 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
             rec["ws_b"][i] = np.linalg.norm(_np(b.info("rotor_uvw_base")), axis=-1)
 
     from .binding import HipBatch
-    if isinstance(model, MlpPolicy) and isinstance(b, HipBatch) and t_sim > 1:
+    if (isinstance(model, MlpPolicy) or recurrent) and isinstance(b, HipBatch) and t_sim > 1:
         # Learned policy on the device: snapshot 0 goes into row 0 of device recordings, steps 1 .. t_sim-1 are ONE
         # rollout (policy and step kernels alternate inside the library), and the recordings cross to the host once.
         t = b.torch
@@ -119,8 +120,17 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
     else:
         t_loop = t_sim
         snapshot(0, 0.0)                                           # AgentEval.py:131-147
+    # the host loop threads a recurrent model's state (sb3-contrib's predict protocol: state in, state out, episode_start marks the
+    # envs whose episode begins — all of them at the first step, none afterwards: a sweep's envs never truncate); a predict() that
+    # takes neither argument is called as before
+    state, starts = None, np.ones(B, dtype=bool)
+    stateful = t_loop > 1 and _takes_state(model.predict)
     for i in range(1, t_loop):
-        action = model.predict(obs, deterministic=deterministic)[0]
+        if stateful:
+            action, state = model.predict(obs, state=state, episode_start=starts, deterministic=deterministic)[:2]
+            starts = np.zeros(B, dtype=bool)
+        else:
+            action = model.predict(obs, deterministic=deterministic)[0]
         action = np.broadcast_to(np.asarray(action, dtype=np.float32), (B, N))
         obs, reward, _, _, _ = env.step(np.ascontiguousarray(action))
         snapshot(i, np.asarray(reward))
@@ -149,6 +159,16 @@ def eval_sweep(turbine, yaml_path=None, model=None, *, winddirs=(270.0,), windsp
         return xr.Dataset({k: (dims5 if v.ndim == 7 else dims4, v) for k, v in data.items()}, coords=coords)
     except Exception:
         return dict(coords=coords, dims={k: (dims5 if v.ndim == 7 else dims4) for k, v in data.items()}, data=data)
+
+
+def _takes_state(predict):
+    """Whether ``predict`` accepts ``state=`` and ``episode_start=`` (by name or through ``**kwargs``)."""
+    import inspect
+    try:
+        ps = inspect.signature(predict).parameters
+    except (TypeError, ValueError):
+        return False
+    return any(p.kind is p.VAR_KEYWORD for p in ps.values()) or ("state" in ps and "episode_start" in ps)
 
 
 class AgentEval:

@@ -12,6 +12,8 @@ import json
 
 import numpy as np
 
+from .policy import refuse_recurrent
+
 ARGS = ("norm_obs", "norm_reward", "clip_obs", "clip_reward", "gamma", "epsilon", "training")
 
 
@@ -212,6 +214,7 @@ class VecNormalize:
         """``venv.rollout(policy, n_steps)`` with the policy reading normalised rows (wg_rollout_norm; with ``sample_site`` the
         equivalent loop of ``act``, ``step``, wg_norm_obs from Python, as ``venv.rollout`` does).  ``normalize_reward=False`` leaves
         ``reward`` the env's and the return statistics untouched: :meth:`reward_pass` is then the caller's to run."""
+        refuse_recurrent(policy, "VecNormalize.rollout()")
         if getattr(policy, "population", None) is not None:
             raise NotImplementedError("VecNormalize.rollout(): policy is a population — per-member statistics are not implemented")
         v, b = self.venv, self.batch

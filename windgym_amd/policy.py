@@ -135,6 +135,9 @@ def read_sb3_zip(path, activation="tanh"):
                 raise ValueError("use_sde: true — state-dependent exploration is not supported")
         sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
     tensors = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in sd.items()}
+    if any(k.startswith("lstm_actor.") for k in tensors):
+        raise ValueError("recurrent checkpoint (lstm_actor.* tensors: sb3-contrib's RecurrentPPO): load it with "
+                         "MlpLstmPolicy.from_sb3_zip (windgym_amd.recurrent)")
     if any(k.startswith("mlp_extractor.shared_net.") for k in tensors):
         raise ValueError("shared trunk (mlp_extractor.shared_net.*): only separate actor / critic nets are supported")
     if any(k.startswith(("features_extractor.", "pi_features_extractor.", "vf_features_extractor.")) for k in tensors):
@@ -175,6 +178,13 @@ def device_tensor(x, dtype):
     """What every tensor handed to the library must be: a contiguous CUDA tensor of ``dtype`` (its size is the caller's to check)."""
     import torch
     return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous()
+
+
+def refuse_recurrent(policy, who):
+    """What the trainers and the wrappers say to a ``recurrent.MlpLstmPolicy`` (or a list holding one): they are not built for it."""
+    if any(getattr(p, "recurrent", False) for p in (policy if isinstance(policy, (list, tuple)) else (policy,))):
+        raise NotImplementedError(f"{who}: training / wrapping a recurrent policy (MlpLstmPolicy) is not implemented; "
+                                  "venv.rollout(policy, T) and eval_sweep run it")
 
 
 def act_buffers(owner, n):

@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from .policy import act_buffers, device_tensor
+from .policy import act_buffers, device_tensor, refuse_recurrent
 from .ppo import PPO, PPOOptimizer, _schedule, check_batch_size, check_hyper, learn_loop, write_checkpoint
 
 POP_MAX = 16            # WG_POP_MAX
@@ -148,6 +148,7 @@ class PPOPopulation:
     def __init__(self, policy, venv, n_members=None, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95,
                  clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True,
                  policy_kwargs=None, seed=None, curriculum=None, normalize=None):
+        refuse_recurrent(policy, "PPOPopulation")
         if curriculum is not None:
             raise NotImplementedError("a curriculum for a population is not implemented (use PPO(..., curriculum=...))")
         if normalize is not None:

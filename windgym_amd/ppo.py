@@ -18,7 +18,7 @@ import zipfile
 
 import numpy as np
 
-from .policy import MlpPolicy, device_tensor, param_layout
+from .policy import MlpPolicy, device_tensor, param_layout, refuse_recurrent
 
 HYPER = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
          "learning_rate", "normalize_advantage")
@@ -327,6 +327,7 @@ class PPO:
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
                  seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None, normalize=None):
+        refuse_recurrent(policy, "PPO")
         for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
             if v is not None:
                 raise NotImplementedError(f"{name} is not implemented")
