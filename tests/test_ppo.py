@@ -146,6 +146,7 @@ def test_row_tile_of_every_legal_architecture_corner():
     at R = 8 whatever n_in is (256 + 1024 + 1 + 512 = 1793 <= 1802).  R = 2 is unreachable inside the limits: no map exceeds the
     budget."""
     pol, ppo, api = (_defines(h) for h in (("windgym_amd", "csrc", "wg_policy.h"), ("windgym_amd", "csrc", "wg_ppo.h"), ("include", "windgym_hip.h")))
+    pol.update(_defines(("windgym_amd", "csrc", "wg_tile.h")))        # (the tile constants: WGP_KC)
     KC, W, OUT, IN, H, LDS = pol["WGP_KC"], pol["WGP_MAX_WIDTH"], pol["WGP_MAX_OUT"], pol["WGP_MAX_IN"], api["WG_POLICY_MAX_HIDDEN"], ppo["WGT_LDS_BYTES"]
     assert (KC, W, OUT, IN, H, LDS) == (256, 256, 128, 2048, 4, 65536) and pol["WGP_MAX_LAYERS"] == H + 1
     stacks = [()] + [(w,) * n for n in range(1, H + 1) for w in (1, 33, 64, W)] + [(W, 1, W, 1), (1, W), (64, W, 64)]

@@ -1,6 +1,7 @@
-"""GPU box: one fixed scenario (seeds, actions) through step(); every output of every step goes to an .npz — run it under two
-builds (WG_LIB=... with WG_DEBUG_HOOKS=1) and compare the files bit for bit:
-    python tools/dump_run.py out_a.npz [workload] [n_envs] [steps];  python tools/dump_run.py --compare out_a.npz out_b.npz"""
+"""GPU box: one fixed scenario (seeds, actions) through step(), or through the policy kernels; every output goes to an .npz — run it
+under two builds (WG_LIB=... with WG_DEBUG_HOOKS=1) and compare the files bit for bit:
+    python tools/dump_run.py out_a.npz [workload] [n_envs] [steps];  python tools/dump_run.py --compare out_a.npz out_b.npz
+    python tools/dump_run.py policy out_a.npz      k_policy / k_policy_pop / k_lstm at the kernels' edge shapes + 8-step closed loops"""
 import os
 import sys
 
@@ -19,6 +20,74 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from windgym_amd import binding  # noqa: E402
 
+MLP_SHAPES = [(7, (33,), 1, 33), (257, (64,), 3, 389), (2048, (256, 256), 128, 32)]        # (n_in, hidden, n_out, rows)
+LSTM_SHAPES = [(3, 1, 1, False), (7, 40, 31, True), (257, 64, 389, False), (300, 256, 33, False)]     # (n_in, H, rows, shared_lstm)
+
+
+def dump_policy(out):
+    """MlpPolicy.act (deterministic, stochastic with value) and Population.act (P = 3, on the rows that divide by 3) per MLP shape,
+    three chained MlpLstmPolicy.act per LSTM shape, then one 8-step venv.rollout of a policy, of a population (P = 2: the members
+    own equal shares of the 4 envs) and of a recurrent policy on 4 envs of the 2-turbine preset.  Every weight and input is drawn
+    on the host from fixed seeds."""
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.policy import MlpPolicy
+    from windgym_amd.population import Population
+    from windgym_amd.recurrent import MlpLstmPolicy
+    from windgym_amd.turbine import V80
+    rng, A = np.random.default_rng(20), {}
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")          # noqa: E731
+    names = ("action", "raw", "logp", "value")
+
+    def keep(tag, tensors):
+        for n, x in zip(names, tensors):
+            A[f"{tag}_{n}"] = np.atleast_1d(x.cpu().numpy())
+
+    for n_in, hidden, n_out, rows in MLP_SHAPES:
+        tag = f"mlp{n_in}"
+        ms = [MlpPolicy(n_in, n_out, hidden, hidden, "tanh", device=0, seed=5 + m) for m in range(3)]
+        obs = dev(rng.uniform(-1, 1, (rows, n_in)).astype(np.float32))
+        keep(tag + "_det", ms[0].act(obs, deterministic=True, counter=1))
+        keep(tag + "_sto", ms[0].act(obs, counter=2))
+        pop = Population(ms)
+        keep(tag + "_pop", pop.act(obs[:rows // 3 * 3].contiguous(), counter=3))
+        pop.close()
+        for m in ms:
+            m.close()
+    for n_in, H, rows, shared in LSTM_SHAPES:
+        tag = f"lstm{n_in}"
+        p = MlpLstmPolicy(n_in, 3, H, (32,), (32,), shared_lstm=shared, device=0, seed=9)
+        state = dev(rng.uniform(-1, 1, (p.nets, 2, rows, H)).astype(np.float32))
+        for i in range(3):
+            start = dev((rng.random(rows) < 0.3).astype(np.uint8))
+            outs, state = p.act(dev(rng.uniform(-1, 1, (rows, n_in)).astype(np.float32)), state, start, counter=i)
+            keep(f"{tag}_t{i}", outs)
+            A[f"{tag}_t{i}_state"] = state.cpu().numpy()
+            state = state.clone()
+        p.close()
+
+    def venv():
+        v = WindFarmVecEnv(V80(), 4, yaml_dict=presets.two_turb_config(), seed=77, as_torch=True, turbtype="None", n_passthrough=1)
+        v.reset(seed=77)
+        return v
+
+    v = venv()
+    O, N = v.batch.obs_dim, v.n_turb
+    ms = [MlpPolicy(O, N, (64, 64), (64, 64), "tanh", device=0, seed=31 + m) for m in range(2)]
+    pop, rec = Population(ms), MlpLstmPolicy(O, N, 64, (32,), (32,), device=0, seed=33)
+    for tag, pol in (("roll_mlp", ms[0]), ("roll_pop", pop), ("roll_lstm", rec)):
+        for k, x in v.rollout(pol, 8).items():
+            A[f"{tag}_{k}"] = np.atleast_1d(x.cpu().numpy())
+        v.close()
+        v = venv()
+    v.close()
+    np.savez(out, **A)
+    print("wrote", out, len(A), "arrays")
+
+
+if sys.argv[1] == "policy":
+    dump_policy(sys.argv[2])
+    sys.exit(0)
 out = sys.argv[1]
 wl = sys.argv[2] if len(sys.argv) > 2 else "cfg2"
 B = int(sys.argv[3]) if len(sys.argv) > 3 else 48

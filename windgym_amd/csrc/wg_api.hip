@@ -16,7 +16,7 @@
 #include "wg_plan.h"
 #include "wg_steady.h"
 #include "wg_policy.h"
-#include "wg_internal.h"
+#include "wg_host.h"
 
 // Measurement / test hooks (environment variables that select kernel variants): honoured ONLY with WG_DEBUG_HOOKS=1 — a
 // stray WG_FLOW_BLOCK in a user's shell must not silently change the kernel — and announced once on stderr when used.
@@ -54,18 +54,11 @@ static WgHooks wg_hooks_read() {
 }
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
-    g_err = msg;
+// (every translation unit of the library reports through this thread-local message: wg_host.h's wg_fail, wg_mann.hip)
+extern "C" int wg_set_last_error_(int code, const char* msg) {
+    g_err = msg ? msg : "";
     return code;
 }
-// (other translation units of the library report through the same thread-local message: wg_mann.hip)
-extern "C" int wg_set_last_error_(int code, const char* msg) { return fail(code, msg ? msg : ""); }
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t _e = (x);                                                                        \
-        if (_e != hipSuccess)                                                                       \
-            return fail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e));                \
-    } while (0)
 
 struct Alloc {
     void* ptr;
@@ -135,16 +128,7 @@ static void drop_step_graphs(wg_env_s* h) {
 static int sync_dev_params(wg_env_s* h) {
     hipError_t e = hipMemcpy(h->p_dev, &h->p, sizeof(WgParams), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(h->d_dev, &h->d, sizeof(WgPtrs), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(WG_ERR_HIP, std::string("hipMemcpy(params): ") + hipGetErrorString(e));
-    return 0;
-}
-
-static int use_device(wg_env_s* h) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) {
-        hipError_t e = hipSetDevice(h->device);
-        if (e != hipSuccess) return fail(WG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("hipMemcpy(params): ") + hipGetErrorString(e));
     return 0;
 }
 
@@ -153,10 +137,10 @@ static int dev_alloc(wg_env_s* h, T** out, size_t n, bool state, bool zero = tru
     size_t bytes = sizeof(T) * (n ? n : 1);
     void* ptr = nullptr;
     hipError_t e = hipMalloc(&ptr, bytes);
-    if (e != hipSuccess) return fail(WG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return wg_fail(WG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
     if (zero) {
         e = hipMemset(ptr, 0, bytes);
-        if (e != hipSuccess) return fail(WG_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
     }
     h->allocs.push_back({ptr, bytes});
     if (state) h->state_idx.push_back(h->allocs.size() - 1);
@@ -170,7 +154,7 @@ static int dev_upload(wg_env_s* h, const T** out, const S* src, size_t n) {
     T* p = nullptr;
     int rc = dev_alloc(h, &p, n, false, false);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(p, tmp.data(), sizeof(T) * (n ? n : 1), hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(p, tmp.data(), sizeof(T) * (n ? n : 1), hipMemcpyHostToDevice));
     *out = p;
     return 0;
 }
@@ -291,10 +275,10 @@ static void apply_step_path(wg_env_s* h) {
 }
 
 extern "C" int wg_create(const wg_config* c, int device, wg_handle* out) {
-    if (!c || !out) return fail(WG_ERR_INVALID, "null argument");
+    if (!c || !out) return wg_fail(WG_ERR_INVALID, "null argument");
     std::string err;
-    if (int rc = wg_validate_config(c, &err)) return fail(rc, err);
-    HIPCHK(hipSetDevice(device));
+    if (int rc = wg_validate_config(c, &err)) return wg_fail(rc, err);
+    WG_HIPCHK(hipSetDevice(device));
     int lds_limit = 65536;
     {
         int v = 0;
@@ -305,7 +289,7 @@ extern "C" int wg_create(const wg_config* c, int device, wg_handle* out) {
     wg_env_s* h = owner.get();
     h->device = device;
     h->hooks = wg_hooks_read();
-    if (int rc = wg_plan_create(c, h->hooks, lds_limit, &h->plan, &err)) return fail(rc, err);
+    if (int rc = wg_plan_create(c, h->hooks, lds_limit, &h->plan, &err)) return wg_fail(rc, err);
     h->p = h->plan.p;
     h->fp = h->plan.f;
     apply_step_path(h);
@@ -323,7 +307,7 @@ extern "C" int wg_create(const wg_config* c, int device, wg_handle* out) {
     {
         hipError_t e = hipDeviceSynchronize();
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return fail(WG_ERR_HIP, std::string("wg_create: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_create: ") + hipGetErrorString(e));
     }
     if (h->hooks.step_graph.set) h->graph_mode = h->hooks.step_graph.v != 0;
     if (h->hooks.debug) {
@@ -367,13 +351,13 @@ extern "C" int wg_destroy(wg_handle h) {
 }
 
 extern "C" int wg_obs_dim(wg_handle h, int* obs_dim, int* obs_dim_multi) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     if (obs_dim) *obs_dim = h->p.obs_dim;
     if (obs_dim_multi) *obs_dim_multi = h->p.obs_dim_multi;
     return 0;
 }
 extern "C" int wg_hist_max(wg_handle h, int* hist_max) {
-    if (!h || !hist_max) return fail(WG_ERR_INVALID, "null argument");
+    if (!h || !hist_max) return wg_fail(WG_ERR_INVALID, "null argument");
     *hist_max = h->p.hist_max;
     return 0;
 }
@@ -397,31 +381,31 @@ static int build_stencil_records(wg_env_s* h, void** owned, const float4** kerne
     if (hipMalloc(owned, bytes) != hipSuccess) { *owned = nullptr; (void)hipGetLastError(); return skip("hipMalloc failed"); }
     for (int k = 0; k < n_boxes; ++k)
         wg_launch_box_stencil((const char*)box4 + (size_t)k * n_cells * 16, (char*)*owned + (size_t)k * n_cells * 128, nx, ny, nz, nullptr);
-    HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipDeviceSynchronize());
     *kernel_ptr = (const float4*)*owned;
     return 0;
 }
 
 extern "C" int wg_set_turbulence_boxes(wg_handle h, const float* const* boxes_dev, int n_boxes, int nx, int ny, int nz,
                                        double dx, double dy, double dz) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     if (!boxes_dev || n_boxes < 1 || n_boxes > 64 || nx < 2 || ny < 2 || nz < 2 || !(dx > 0) || !(dy > 0) || !(dz > 0))
-        return fail(WG_ERR_INVALID, "turbulence box: null pointer, bad pool size (1..64) or bad dimensions");
+        return wg_fail(WG_ERR_INVALID, "turbulence box: null pointer, bad pool size (1..64) or bad dimensions");
     for (int k = 0; k < n_boxes; ++k)
-        if (!boxes_dev[k]) return fail(WG_ERR_INVALID, "turbulence box: null pointer in the pool");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+        if (!boxes_dev[k]) return wg_fail(WG_ERR_INVALID, "turbulence box: null pointer in the pool");
+    WG_HIPCHK(hipSetDevice(h->device));
+    WG_HIPCHK(hipDeviceSynchronize());
     drop_step_graphs(h);           // the kernel arguments captured in them are about to change
     // the kernel-side pointers are cleared first: a failure below must not leave them dangling
     h->d.box = nullptr; h->fd.box4 = nullptr; h->fd.box4c = nullptr; h->fd.box8 = nullptr; h->fp.coarse = 0;
-    if (h->box8) { void* q = h->box8; h->box8 = nullptr; HIPCHK(hipFree(q)); }
-    if (h->box4) { void* q = h->box4; h->box4 = nullptr; HIPCHK(hipFree(q)); }
-    if (h->box4c) { void* q = h->box4c; h->box4c = nullptr; HIPCHK(hipFree(q)); }
+    if (h->box8) { void* q = h->box8; h->box8 = nullptr; WG_HIPCHK(hipFree(q)); }
+    if (h->box4) { void* q = h->box4; h->box4 = nullptr; WG_HIPCHK(hipFree(q)); }
+    if (h->box4c) { void* q = h->box4c; h->box4c = nullptr; WG_HIPCHK(hipFree(q)); }
     const size_t n_cells = (size_t)nx * ny * nz;
-    HIPCHK(hipMalloc(&h->box4, n_cells * 16 * (size_t)n_boxes));
+    WG_HIPCHK(hipMalloc(&h->box4, n_cells * 16 * (size_t)n_boxes));
     for (int k = 0; k < n_boxes; ++k)
         wg_launch_box_repack(boxes_dev[k], (char*)h->box4 + (size_t)k * n_cells * 16, nx, ny, nz, nullptr);
-    HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipDeviceSynchronize());
     h->d.box = boxes_dev[0];
     h->p.n_boxes = n_boxes;
     h->p.bnx = nx; h->p.bny = ny; h->p.bnz = nz; h->p.bdx = dx; h->p.bdy = dy; h->p.bdz = dz;
@@ -434,11 +418,11 @@ extern "C" int wg_set_turbulence_boxes(wg_handle h, const float* const* boxes_de
     if (h->fp.coarse) {
         const int cx = nx / 4, cy = ny / 4, cz = nz / 4;
         const size_t c_cells = (size_t)cx * cy * cz;
-        HIPCHK(hipMalloc(&h->box4c, c_cells * 16 * (size_t)n_boxes));
+        WG_HIPCHK(hipMalloc(&h->box4c, c_cells * 16 * (size_t)n_boxes));
         for (int k = 0; k < n_boxes; ++k)
             wg_launch_box_coarsen((const char*)h->box4 + (size_t)k * n_cells * 16, (char*)h->box4c + (size_t)k * c_cells * 16,
                                   nx, ny, nz, nullptr);
-        HIPCHK(hipDeviceSynchronize());
+        WG_HIPCHK(hipDeviceSynchronize());
         h->fp.cnx = cx; h->fp.cny = cy; h->fp.cnz = cz; h->fp.cbox_cells = (long long)c_cells;
         h->fp.cbox_pow2 = ((cx & (cx - 1)) == 0) && ((cy & (cy - 1)) == 0) && ((cz & (cz - 1)) == 0);
         h->fd.box4c = (const float4*)h->box4c;
@@ -452,17 +436,17 @@ extern "C" int wg_set_turbulence_boxes(wg_handle h, const float* const* boxes_de
 extern "C" int wg_set_added_turbulence_box(wg_handle h, const float* box_dev, int nx, int ny, int nz, double dx,
                                            double dy, double dz) {
     if (!h || !box_dev || nx < 2 || ny < 2 || nz < 2 || !(dx > 0) || !(dy > 0) || !(dz > 0))
-        return fail(WG_ERR_INVALID, "added-turbulence box: null pointer or bad dimensions");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+        return wg_fail(WG_ERR_INVALID, "added-turbulence box: null pointer or bad dimensions");
+    WG_HIPCHK(hipSetDevice(h->device));
+    WG_HIPCHK(hipDeviceSynchronize());
     drop_step_graphs(h);
     h->fd.abox4 = nullptr; h->fd.abox8 = nullptr;
-    if (h->abox8) { void* q = h->abox8; h->abox8 = nullptr; HIPCHK(hipFree(q)); }
-    if (h->abox4) { void* q = h->abox4; h->abox4 = nullptr; HIPCHK(hipFree(q)); }
+    if (h->abox8) { void* q = h->abox8; h->abox8 = nullptr; WG_HIPCHK(hipFree(q)); }
+    if (h->abox4) { void* q = h->abox4; h->abox4 = nullptr; WG_HIPCHK(hipFree(q)); }
     const size_t n_cells = (size_t)nx * ny * nz;
-    HIPCHK(hipMalloc(&h->abox4, n_cells * 16));
+    WG_HIPCHK(hipMalloc(&h->abox4, n_cells * 16));
     wg_launch_box_repack(box_dev, h->abox4, nx, ny, nz, nullptr);
-    HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipDeviceSynchronize());
     h->fd.abox4 = (const float4*)h->abox4;
     h->fp.anx = nx; h->fp.any = ny; h->fp.anz = nz;
     apply_step_path(h);
@@ -477,10 +461,10 @@ extern "C" int wg_set_deficit_table(wg_handle h, const float* table_dev, int n_c
                                     double ti1, int n_x, double x_max_D, int n_r, double r_max_R) {
     if (!h || !table_dev || n_ct < 2 || n_ti < 2 || n_x < 2 || n_r < 2 || !(ct1 > ct0) || !(ti0 > 0) || !(ti1 > ti0) || !(x_max_D > 0) ||
         !(r_max_R > 0))
-        return fail(WG_ERR_INVALID, "wg_set_deficit_table: null pointer or bad grid");
-    if ((long long)n_ct * n_ti * n_x * n_r >= (1ll << 30)) return fail(WG_ERR_INVALID, "wg_set_deficit_table: table too large");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+        return wg_fail(WG_ERR_INVALID, "wg_set_deficit_table: null pointer or bad grid");
+    if ((long long)n_ct * n_ti * n_x * n_r >= (1ll << 30)) return wg_fail(WG_ERR_INVALID, "wg_set_deficit_table: table too large");
+    WG_HIPCHK(hipSetDevice(h->device));
+    WG_HIPCHK(hipDeviceSynchronize());
     drop_step_graphs(h);
     FlowP& f = h->fp;
     h->fd.dtab = table_dev;            // borrowed: the caller keeps the buffer alive
@@ -494,14 +478,14 @@ extern "C" int wg_set_deficit_table(wg_handle h, const float* table_dev, int n_c
 extern "C" int wg_set_turbulence_box(wg_handle h, const float* box_dev, int nx, int ny, int nz, double dx,
                                      double dy, double dz) {
     const float* one[1] = {box_dev};
-    if (!box_dev) return fail(WG_ERR_INVALID, "turbulence box: null pointer or bad dimensions");
+    if (!box_dev) return wg_fail(WG_ERR_INVALID, "turbulence box: null pointer or bad dimensions");
     return wg_set_turbulence_boxes(h, one, 1, nx, ny, nz, dx, dy, dz);
 }
 
 extern "C" int wg_set_wind(wg_handle h, const double* wind_host) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
+    WG_HIPCHK(hipSetDevice(h->device));
+    WG_HIPCHK(hipDeviceSynchronize());
     drop_step_graphs(h);
     if (!wind_host) { h->d.wind_override = nullptr; return sync_dev_params(h); }
     if (!h->wind_dev) {
@@ -510,24 +494,24 @@ extern "C" int wg_set_wind(wg_handle h, const double* wind_host) {
         if (rc) return rc;
         h->wind_dev = w;
     }
-    HIPCHK(hipMemcpy(h->wind_dev, wind_host, sizeof(double) * 3 * (size_t)h->p.B, hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(h->wind_dev, wind_host, sizeof(double) * 3 * (size_t)h->p.B, hipMemcpyHostToDevice));
     h->d.wind_override = h->wind_dev;
     return sync_dev_params(h);
 }
 
 extern "C" int wg_set_box_ids(wg_handle h, const int32_t* ids_host) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
+    WG_HIPCHK(hipSetDevice(h->device));
+    WG_HIPCHK(hipDeviceSynchronize());
     drop_step_graphs(h);
     if (!ids_host) { h->d.box_override = nullptr; return sync_dev_params(h); }
     // (a caller error must not produce results labelled with the wrong box: wg_ctx_init would fold a bad id to box 0 and
     // ignores the table without a pool)
     if (h->p.turb_mode != WG_TURB_BOX_POOL || h->p.n_boxes < 1)
-        return fail(WG_ERR_INVALID, "wg_set_box_ids: the handle has no box pool (turb_mode WG_TURB_BOX_POOL + wg_set_turbulence_boxes first)");
+        return wg_fail(WG_ERR_INVALID, "wg_set_box_ids: the handle has no box pool (turb_mode WG_TURB_BOX_POOL + wg_set_turbulence_boxes first)");
     for (int b = 0; b < h->p.B; ++b)
         if (ids_host[b] >= h->p.n_boxes)
-            return fail(WG_ERR_INVALID, "wg_set_box_ids: env " + std::to_string(b) + " asks for box " + std::to_string(ids_host[b]) +
+            return wg_fail(WG_ERR_INVALID, "wg_set_box_ids: env " + std::to_string(b) + " asks for box " + std::to_string(ids_host[b]) +
                                             " of a pool of " + std::to_string(h->p.n_boxes));
     if (!h->box_ids_dev) {
         int* w = nullptr;
@@ -535,21 +519,21 @@ extern "C" int wg_set_box_ids(wg_handle h, const int32_t* ids_host) {
         if (rc) return rc;
         h->box_ids_dev = w;
     }
-    HIPCHK(hipMemcpy(h->box_ids_dev, ids_host, sizeof(int) * (size_t)h->p.B, hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(h->box_ids_dev, ids_host, sizeof(int) * (size_t)h->p.B, hipMemcpyHostToDevice));
     h->d.box_override = h->box_ids_dev;
     return sync_dev_params(h);
 }
 
 extern "C" int wg_set_wind_device(wg_handle h, const double* wind_dev) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     if (h->d.wind_override != wind_dev) drop_step_graphs(h);
     h->d.wind_override = wind_dev;      // borrowed; read by wg_ctx_init (k_init / head of k_flow) in stream order
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     return sync_dev_params(h);
 }
 
 extern "C" int wg_set_flow_script(wg_handle h, const float* uvw_dev, const float* power_dev, int n_rows) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     drop_step_graphs(h);
     h->d.script_uvw = uvw_dev;
     h->d.script_power = power_dev;
@@ -557,7 +541,7 @@ extern "C" int wg_set_flow_script(wg_handle h, const float* uvw_dev, const float
     h->fd.script_uvw = uvw_dev;
     h->fd.script_power = power_dev;
     h->fp.script_rows = n_rows;
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     return sync_dev_params(h);
 }
 
@@ -576,30 +560,30 @@ static void time_end(wg_env_s* h, hipStream_t st) {
 
 extern "C" int wg_reset(wg_handle h, const uint8_t* env_mask_host, const uint64_t* seeds_host, float* obs_dev,
                         void* stream) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    WG_HIPCHK(hipSetDevice(h->device));
     if (h->p.turb_mode >= WG_TURB_BOX && !h->d.box)
-        return fail(WG_ERR_INVALID, "turbtype Mann*: call wg_set_turbulence_box before wg_reset");
+        return wg_fail(WG_ERR_INVALID, "turbtype Mann*: call wg_set_turbulence_box before wg_reset");
     if (h->fp.added && !h->fd.abox4)
-        return fail(WG_ERR_INVALID, "added_turbulence: call wg_set_added_turbulence_box before wg_reset");
+        return wg_fail(WG_ERR_INVALID, "added_turbulence: call wg_set_added_turbulence_box before wg_reset");
     if (h->fp.deficit_model == 2 && !h->fd.dtab)
-        return fail(WG_ERR_INVALID, "deficit_model 2: call wg_set_deficit_table before wg_reset");
+        return wg_fail(WG_ERR_INVALID, "deficit_model 2: call wg_set_deficit_table before wg_reset");
     const uint8_t* mask = nullptr;
     const uint64_t* seeds = nullptr;
     bool all = true;
     if (env_mask_host) {
         for (int b = 0; b < h->p.B; ++b) all = all && env_mask_host[b] != 0;
-        HIPCHK(hipMemcpyAsync(h->mask_dev, env_mask_host, (size_t)h->p.B, hipMemcpyHostToDevice, st));
+        WG_HIPCHK(hipMemcpyAsync(h->mask_dev, env_mask_host, (size_t)h->p.B, hipMemcpyHostToDevice, st));
         mask = h->mask_dev;
     }
     if (seeds_host) {
-        HIPCHK(hipMemcpyAsync(h->seeds_dev, seeds_host, sizeof(uint64_t) * (size_t)h->p.B, hipMemcpyHostToDevice, st));
+        WG_HIPCHK(hipMemcpyAsync(h->seeds_dev, seeds_host, sizeof(uint64_t) * (size_t)h->p.B, hipMemcpyHostToDevice, st));
         seeds = h->seeds_dev;
     }
     // the sticky error word is cleared only by a reset of the whole batch: a masked reset must not drop an error
     // another env latched
-    if (all) HIPCHK(hipMemsetAsync(h->d.status, 0, sizeof(int), st));
+    if (all) WG_HIPCHK(hipMemsetAsync(h->d.status, 0, sizeof(int), st));
     wg_launch_init(&h->p, &h->d, mask, seeds, st);
     // RESET-mode launches develop the masked envs' episodes (fs.run(t_developed) + window fill).  The planned count
     // covers every episode the config's wind range can produce; a wind override (wg_set_wind / wg_set_wind_device,
@@ -613,21 +597,21 @@ extern "C" int wg_reset(wg_handle h, const uint8_t* env_mask_host, const uint64_
         for (int i = 0; i < batch; ++i) wg_launch_flow(&h->fp, &h->fd, WG_MODE_RESET, nullptr, mask, h->plan.reset_chunk, st);
         {
             const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return fail(WG_ERR_HIP, std::string("wg_reset: k_flow launch failed: ") + hipGetErrorString(le));
+            if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_reset: k_flow launch failed: ") + hipGetErrorString(le));
         }
         launched += batch;
         int unready = 0;
-        HIPCHK(hipMemsetAsync(h->unready_dev, 0, sizeof(int), st));
+        WG_HIPCHK(hipMemsetAsync(h->unready_dev, 0, sizeof(int), st));
         wg_launch_unready(&h->p, &h->d, mask, h->unready_dev, st);
-        HIPCHK(hipMemcpyAsync(&unready, h->unready_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        WG_HIPCHK(hipMemcpyAsync(&unready, h->unready_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+        WG_HIPCHK(hipStreamSynchronize(st));
         if (unready == 0) break;
         if (launched > 4000000L / h->plan.reset_chunk)
-            return fail(WG_ERR_STATE, "wg_reset: episode development does not terminate (wind speed override ~ 0?)");
+            return wg_fail(WG_ERR_STATE, "wg_reset: episode development does not terminate (wind speed override ~ 0?)");
         batch = std::max(8, n_plan / 4);
     }
     wg_launch_glue(&h->p, &h->d, 1, mask, obs_dev, nullptr, nullptr, nullptr, st, h->p_dev, h->d_dev);
-    HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -659,15 +643,15 @@ static void launch_step(wg_env_s* h, const float* actions_dev, float* obs_dev, f
 
 extern "C" int wg_step(wg_handle h, const float* actions_dev, float* obs_dev, float* reward_dev,
                        uint8_t* truncated_dev, float* final_obs_dev, void* stream) {
-    if (!h || !actions_dev || !obs_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (int rc = use_device(h)) return rc;
+    if (!h || !actions_dev || !obs_dev) return wg_fail(WG_ERR_INVALID, "null argument");
+    if (int rc = wg_use_device(h->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool sample = count_step(h);
     if (!h->graph_mode || sample) {
         launch_step(h, actions_dev, obs_dev, reward_dev, truncated_dev, final_obs_dev, st, sample);
         // a rejected launch (bad configuration, out-of-resources) must not pass for a step that returned stale outputs
         const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(WG_ERR_HIP, std::string("wg_step: kernel launch failed: ") + hipGetErrorString(le));
+        if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_step: kernel launch failed: ") + hipGetErrorString(le));
         return 0;
     }
     // graph mode: one hipGraphLaunch per step.  A graph is captured once per distinct set of I/O pointers (a training
@@ -712,104 +696,104 @@ extern "C" int wg_step(wg_handle h, const float* actions_dev, float* obs_dev, fl
             if (h->hooks.debug) fprintf(stderr, "[windgym] step-graph capture failed; using direct launches\n");
             launch_step(h, actions_dev, obs_dev, reward_dev, truncated_dev, final_obs_dev, st, false);
             const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return fail(WG_ERR_HIP, std::string("wg_step: kernel launch failed: ") + hipGetErrorString(le));
+            if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_step: kernel launch failed: ") + hipGetErrorString(le));
             return 0;
         }
         h->graphs.push_back(ng);
         g = &h->graphs.back();
     }
     g->last_use = ++h->graph_clock;
-    HIPCHK(hipGraphLaunch(g->exec, st));
+    WG_HIPCHK(hipGraphLaunch(g->exec, st));
     return 0;
 }
 
 extern "C" int wg_set_step_graph(wg_handle h, int enable) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     h->graph_mode = enable != 0;
     if (!h->graph_mode) drop_step_graphs(h);
     return 0;
 }
 
 extern "C" int wg_check(wg_handle h, void* stream) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
-    if (int rc = use_device(h)) return rc;
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
+    if (int rc = wg_use_device(h->device)) return rc;
     int status = 0;
-    HIPCHK(hipMemcpyAsync(&status, h->d.status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipMemcpyAsync(&status, h->d.status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    WG_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    WG_HIPCHK(hipGetLastError());
     // (a bit mask: reported by priority — the reference treats the first two as fatal exceptions)
-    if (status & WG_STATUS_BIT_NAN_POWER) return fail(WG_ERR_NAN_POWER, "NaN Power");
+    if (status & WG_STATUS_BIT_NAN_POWER) return wg_fail(WG_ERR_NAN_POWER, "NaN Power");
     if (status & WG_STATUS_BIT_STATE)
-        return fail(WG_ERR_STATE, "step() on a truncated env without reset (or background episode not ready)");
+        return wg_fail(WG_ERR_STATE, "step() on a truncated env without reset (or background episode not ready)");
     if (status & WG_STATUS_BIT_RANGE)
-        return fail(WG_ERR_RANGE, "a wake particle's emission record left its 16-bit range (k > 0.25: local TI > 0.65, or |hv| > 16 m/s: "
+        return wg_fail(WG_ERR_RANGE, "a wake particle's emission record left its 16-bit range (k > 0.25: local TI > 0.65, or |hv| > 16 m/s: "
                             "rotor wind speed > 40 m/s) and was saturated");
     return 0;
 }
 
 extern "C" int wg_set_obs_multi_buffer(wg_handle h, float* obs_multi_dev) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     // k_glue keeps one farm block per wave in LDS for the per-agent packing (wg_launch_glue): it must fit a workgroup's
     // 64 KB by itself (the staged rings give way first)
     if (obs_multi_dev && (size_t)h->p.farm_obs * 4 * WG_NWAVES > 65536)
-        return fail(WG_ERR_UNSUPPORTED, "wg_set_obs_multi_buffer: the farm-level observation block is too long for the fused "
+        return wg_fail(WG_ERR_UNSUPPORTED, "wg_set_obs_multi_buffer: the farm-level observation block is too long for the fused "
                                         "per-agent packing (use wg_obs_multi)");
     if (h->d.multi_out != obs_multi_dev) drop_step_graphs(h);
     h->d.multi_out = obs_multi_dev;     // borrowed; written by k_glue in every following wg_step / wg_reset
     if (!obs_multi_dev) h->d.multi_fin = nullptr;      // (the final buffer is written by the per-agent instantiations only)
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     // (the per-agent instantiation of k_glue neither consumes nor retires the prepared first observations of
     // WgPtrs::next_obs: switching between the two must not leave a flag of an episode that has since been replaced)
     if (h->d.next_obs_ok) {
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemset(h->d.next_obs_ok, 0, sizeof(int) * (size_t)h->p.B * 2));
+        WG_HIPCHK(hipDeviceSynchronize());
+        WG_HIPCHK(hipMemset(h->d.next_obs_ok, 0, sizeof(int) * (size_t)h->p.B * 2));
     }
     return sync_dev_params(h);
 }
 
 extern "C" int wg_set_final_obs_multi_buffer(wg_handle h, float* final_obs_multi_dev) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     if (final_obs_multi_dev && !h->d.multi_out)
-        return fail(WG_ERR_INVALID, "wg_set_final_obs_multi_buffer: register the per-agent buffer first (wg_set_obs_multi_buffer)");
+        return wg_fail(WG_ERR_INVALID, "wg_set_final_obs_multi_buffer: register the per-agent buffer first (wg_set_obs_multi_buffer)");
     // (same bound as wg_set_obs_multi_buffer: the farm block of a wave's agents is built once, in LDS, for both buffers)
     if (final_obs_multi_dev && (size_t)h->p.farm_obs * 4 * WG_NWAVES > 65536)
-        return fail(WG_ERR_UNSUPPORTED, "wg_set_final_obs_multi_buffer: the farm-level observation block is too long for the fused "
+        return wg_fail(WG_ERR_UNSUPPORTED, "wg_set_final_obs_multi_buffer: the farm-level observation block is too long for the fused "
                                         "per-agent packing (use wg_obs_multi)");
     if (h->d.multi_fin != final_obs_multi_dev) drop_step_graphs(h);
     h->d.multi_fin = final_obs_multi_dev;     // borrowed; written by the glue of every following wg_step
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     return sync_dev_params(h);
 }
 
 extern "C" int wg_obs_multi(wg_handle h, float* obs_dev, void* stream) {
-    if (!h || !obs_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (int rc = use_device(h)) return rc;
+    if (!h || !obs_dev) return wg_fail(WG_ERR_INVALID, "null argument");
+    if (int rc = wg_use_device(h->device)) return rc;
     wg_launch_obs_multi(&h->p, &h->d, obs_dev, (hipStream_t)stream);
     return 0;
 }
 
 extern "C" int wg_get_measurements(wg_handle h, float* out_dev, void* stream) {
-    if (!h || !out_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (int rc = use_device(h)) return rc;
+    if (!h || !out_dev) return wg_fail(WG_ERR_INVALID, "null argument");
+    if (int rc = wg_use_device(h->device)) return rc;
     wg_launch_measurements(&h->p, &h->d, out_dev, (hipStream_t)stream);
     return 0;
 }
 
 extern "C" int wg_get_windspeed(wg_handle h, int env, int farm, const float* x_dev, int nx, const float* y_dev, int ny,
                                 float z, int include_wakes, float* uvw_dev, void* stream) {
-    if (!h || !x_dev || !y_dev || !uvw_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (int rc = use_device(h)) return rc;
-    if (env < 0 || env >= h->p.B || farm < 0 || farm >= h->p.F) return fail(WG_ERR_INVALID, "env / farm index out of range");
-    if (nx <= 0 || ny <= 0 || (long long)nx * ny > (1ll << 30)) return fail(WG_ERR_INVALID, "bad grid size");
-    if (h->fp.script_rows > 0) return fail(WG_ERR_UNSUPPORTED, "no flow field in flow-script replay mode");
+    if (!h || !x_dev || !y_dev || !uvw_dev) return wg_fail(WG_ERR_INVALID, "null argument");
+    if (int rc = wg_use_device(h->device)) return rc;
+    if (env < 0 || env >= h->p.B || farm < 0 || farm >= h->p.F) return wg_fail(WG_ERR_INVALID, "env / farm index out of range");
+    if (nx <= 0 || ny <= 0 || (long long)nx * ny > (1ll << 30)) return wg_fail(WG_ERR_INVALID, "bad grid size");
+    if (h->fp.script_rows > 0) return wg_fail(WG_ERR_UNSUPPORTED, "no flow field in flow-script replay mode");
     wg_launch_windspeed(&h->fp, &h->fd, env, farm, x_dev, nx, y_dev, ny, z, include_wakes, uvw_dev, (hipStream_t)stream);
     return 0;
 }
 
 extern "C" int wg_get_info(wg_handle h, wg_info_field field, void* out_dev, void* stream) {
-    if (!h || !out_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (int rc = use_device(h)) return rc;
-    if ((int)field < 0 || (int)field > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, "unknown info field");
+    if (!h || !out_dev) return wg_fail(WG_ERR_INVALID, "null argument");
+    if (int rc = wg_use_device(h->device)) return rc;
+    if ((int)field < 0 || (int)field > WG_INFO_BOX_ID) return wg_fail(WG_ERR_INVALID, "unknown info field");
     wg_launch_info(&h->p, &h->d, (int)field, out_dev, (hipStream_t)stream);
     return 0;
 }
@@ -855,23 +839,23 @@ struct RolloutRows {
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
     const wg_rollout_multi_bufs& o = g.o;
     const std::string who = std::string(g.who) + ": ";
-    if (n_steps < 0) return fail(WG_ERR_INVALID, who + "n_steps < 0");
+    if (n_steps < 0) return wg_fail(WG_ERR_INVALID, who + "n_steps < 0");
     if (!o.obs_multi || !o.actions || !o.reward || !o.truncated)
-        return fail(WG_ERR_INVALID, who + g.obs_name + ", actions, reward and truncated buffers are required");
-    if (p->device != h->device) return fail(WG_ERR_INVALID, who + "policy and handle live on different devices");
+        return wg_fail(WG_ERR_INVALID, who + g.obs_name + ", actions, reward and truncated buffers are required");
+    if (p->w.device != h->device) return wg_fail(WG_ERR_INVALID, who + "policy and handle live on different devices");
     if (p->P.n_in != g.n_in || p->P.n_out != g.n_out || (p->P.n_layers[1] != 0 && p->P.n_in_vf != g.v_in))
-        return fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
+        return wg_fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
                                         (p->P.n_in_vf != p->P.n_in ? " (its critic reads " + std::to_string(p->P.n_in_vf) + " inputs)" : std::string()) + g.needs);
-    if (g.unready) return fail(WG_ERR_INVALID, who + g.unready);
-    if (!g.v_obs) return fail(WG_ERR_INVALID, who + "a centralised critic reads the flat observation: obs is required (slot 0 is input)");
-    if (o.final_value && !g.v_fin) return fail(WG_ERR_INVALID, who + "final_value needs " + g.fin_name);
-    if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
+    if (g.unready) return wg_fail(WG_ERR_INVALID, who + g.unready);
+    if (!g.v_obs) return wg_fail(WG_ERR_INVALID, who + "a centralised critic reads the flat observation: obs is required (slot 0 is input)");
+    if (o.final_value && !g.v_fin) return wg_fail(WG_ERR_INVALID, who + "final_value needs " + g.fin_name);
+    if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
     if (!p->P.has_log_std && (!deterministic || o.logp))
-        return fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
-    if (o.n_info < 0 || (o.n_info > 0 && (!o.info_fields || !o.info_out))) return fail(WG_ERR_INVALID, who + "bad info arguments");
+        return wg_fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
+    if (o.n_info < 0 || (o.n_info > 0 && (!o.info_fields || !o.info_out))) return wg_fail(WG_ERR_INVALID, who + "bad info arguments");
     for (int i = 0; i < o.n_info; ++i) {
-        if (o.info_fields[i] < 0 || o.info_fields[i] > WG_INFO_BOX_ID) return fail(WG_ERR_INVALID, who + "unknown info field");
-        if (!o.info_out[i]) return fail(WG_ERR_INVALID, who + "null info buffer");
+        if (o.info_fields[i] < 0 || o.info_fields[i] > WG_INFO_BOX_ID) return wg_fail(WG_ERR_INVALID, who + "unknown info field");
+        if (!o.info_out[i]) return wg_fail(WG_ERR_INVALID, who + "null info buffer");
     }
     return 0;
 }
@@ -909,7 +893,7 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     };
     if (g.lstm && g.lb->state0 && n_steps > 0) {
         const hipError_t ce = hipMemcpyAsync(g.lb->state0, g.lb->state, sizeof(float) * (two ? 2 : 1) * 2 * sH, hipMemcpyDeviceToDevice, st);
-        if (ce != hipSuccess) return fail(WG_ERR_HIP, std::string(g.who) + ": copy of the initial state failed: " + hipGetErrorString(ce));
+        if (ce != hipSuccess) return wg_fail(WG_ERR_HIP, std::string(g.who) + ": copy of the initial state failed: " + hipGetErrorString(ce));
     }
     // ONE launch of k_policy per step: the actor on step t's rows and, as further slots, the critic on its rows of step t and
     // final_value[t - 1] = V(final rows of step t - 1) (a row's value does not depend on what else the launch computes); the last
@@ -945,7 +929,7 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
         for (int i = 0; i < o.n_info; ++i)
             wg_launch_info(&h->p, &h->d, o.info_fields[i], (char*)o.info_out[i] + (size_t)t * info_bytes(h, o.info_fields[i]), st);
         const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) rc = fail(WG_ERR_HIP, std::string(g.who) + ": kernel launch failed: " + hipGetErrorString(le));
+        if (le != hipSuccess) rc = wg_fail(WG_ERR_HIP, std::string(g.who) + ": kernel launch failed: " + hipGetErrorString(le));
         if (g.norm && !rc)
             rc = wg_norm_obs(g.norm, B, o.obs + (t + 1) * sBO, o.obs_multi + (t + 1) * sRO, o.final_obs + t * sBO,
                              o.final_obs_multi + t * sRO, stream);
@@ -954,7 +938,7 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     h->d.multi_fin = fin0;
     if (!rc && g.lstm && n_steps > 0) {      // episode_start[t + 1] = truncated[t] for every t: one contiguous block
         const hipError_t ce = hipMemcpyAsync(g.lb->episode_start + B, o.truncated, (size_t)n_steps * B, hipMemcpyDeviceToDevice, st);
-        if (ce != hipSuccess) rc = fail(WG_ERR_HIP, std::string(g.who) + ": copy of the episode starts failed: " + hipGetErrorString(ce));
+        if (ce != hipSuccess) rc = wg_fail(WG_ERR_HIP, std::string(g.who) + ": copy of the episode starts failed: " + hipGetErrorString(ce));
         if (!rc && o.final_value) rc = lstm_final(n_steps - 1);
     }
     if (!rc && o.final_value && n_steps > 0) {
@@ -967,7 +951,7 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
 
 extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                           uint64_t row_offset, const wg_rollout_bufs* o, void* stream) {
-    if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout: null argument");
+    if (!h || !p || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout: null argument");
     const int N = h->p.N, O = h->p.obs_dim;
     // one policy row per env: the rows the policy reads are the flat rows the steps write
     const RolloutRows g = {"wg_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
@@ -976,7 +960,7 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
                             o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
                            1, O, o->obs, o->final_obs, "final_obs"};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
 }
 
@@ -984,24 +968,24 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
 // and the wg_norm's observation half runs after every step (its statistics move inside the loop).
 extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                uint64_t row_offset, const wg_rollout_bufs* o, float* norm_obs_dev, float* norm_final_obs_dev, void* stream) {
-    if (!h || !p || !n || !o) return fail(WG_ERR_INVALID, "wg_rollout_norm: null argument");
+    if (!h || !p || !n || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: null argument");
     const int N = h->p.N, O = h->p.obs_dim;
     int n_obs = 0, n_envs = 0, n_device = 0;
     if (int rc = wg_norm_geometry_(n, &n_obs, &n_envs, &n_device)) return rc;
     if (n_obs != O || n_envs != h->p.B)
-        return fail(WG_ERR_INVALID, "wg_rollout_norm: the wg_norm holds statistics of " + std::to_string(n_obs) + " observation entries x " +
+        return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: the wg_norm holds statistics of " + std::to_string(n_obs) + " observation entries x " +
                                         std::to_string(n_envs) + " envs, the handle's obs_dim / n_envs are " + std::to_string(O) + " / " +
                                         std::to_string(h->p.B));
-    if (n_device != h->device) return fail(WG_ERR_INVALID, "wg_rollout_norm: wg_norm and handle live on different devices");
+    if (n_device != h->device) return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: wg_norm and handle live on different devices");
     if (!o->obs || !o->final_obs || !norm_final_obs_dev)
-        return fail(WG_ERR_INVALID, "wg_rollout_norm: obs, final_obs (the env's own rows) and norm_final_obs are required");
+        return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: obs, final_obs (the env's own rows) and norm_final_obs are required");
     const RolloutRows g = {"wg_rollout_norm", "norm_obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
                            nullptr, false,
                            {norm_obs_dev, o->actions, o->raw, o->logp, o->value, norm_final_obs_dev, o->final_value, o->reward, o->truncated,
                             o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
                            1, O, norm_obs_dev, norm_final_obs_dev, "norm_final_obs", nullptr, n};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
 }
 
@@ -1009,7 +993,7 @@ extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps,
 // the loop is rollout_loop with the population's slot table prepared for these buffers.
 extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
                               const uint64_t* row_offsets, const wg_rollout_bufs* o, void* stream) {
-    if (!h || !q || !o || !seeds) return fail(WG_ERR_INVALID, "wg_pop_rollout: null argument");
+    if (!h || !q || !o || !seeds) return wg_fail(WG_ERR_INVALID, "wg_pop_rollout: null argument");
     const int N = h->p.N, O = h->p.obs_dim, B = h->p.B;
     const RolloutRows g = {"wg_pop_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
                            nullptr, false,
@@ -1018,9 +1002,9 @@ extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int determinis
                            1, O, o->obs, o->final_obs, "final_obs", q};
     if (int rc = rollout_check(h, q->pol[0], n_steps, deterministic, g)) return rc;
     if (B % q->P != 0)
-        return fail(WG_ERR_INVALID, "wg_pop_rollout: the " + std::to_string(q->P) + " members own equal shares of the envs, and n_envs = " +
+        return wg_fail(WG_ERR_INVALID, "wg_pop_rollout: the " + std::to_string(q->P) + " members own equal shares of the envs, and n_envs = " +
                                         std::to_string(B) + " does not divide by " + std::to_string(q->P));
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     const WgPopRows r = {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, B, 1};
     if (int rc = wg_pop_prepare_(q, "wg_pop_rollout", B, seeds, row_offsets, &r, stream)) return rc;
     return rollout_loop(h, q->pol[0], n_steps, deterministic, 0, counter0, 0, g, stream);
@@ -1028,7 +1012,7 @@ extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int determinis
 
 extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                 uint64_t row_offset, const wg_rollout_multi_bufs* o, void* stream) {
-    if (!h || !p || !o) return fail(WG_ERR_INVALID, "wg_rollout_multi: null argument");
+    if (!h || !p || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout_multi: null argument");
     const int B = h->p.B, N = h->p.N, O = h->p.obs_dim, Om = h->p.obs_dim_multi;
     // central mode: the policy's critic has the flat observation's width (and not the actor's): it reads the steps' flat rows
     const bool central = p->P.n_layers[1] != 0 && p->P.n_in_vf != p->P.n_in && p->P.n_in_vf == O;
@@ -1041,8 +1025,8 @@ extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deter
                            central ? 1 : N, central ? O : Om, central ? o->obs : o->obs_multi, central ? o->final_obs : o->final_obs_multi,
                            central ? "final_obs (a centralised critic reads the flat rows)" : "final_obs_multi"};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if ((long long)B * N > 0x7fffffffLL) return fail(WG_ERR_UNSUPPORTED, "wg_rollout_multi: more than 2^31 agent rows");
-    if (int rc = use_device(h)) return rc;
+    if ((long long)B * N > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, "wg_rollout_multi: more than 2^31 agent rows");
+    if (int rc = wg_use_device(h->device)) return rc;
     // the step kernels always build the flat observation: without a caller's buffer it goes to a row block of the handle's own
     // (allocated by the first call that needs it, before anything is enqueued)
     if (!o->obs && !h->flat_scratch)
@@ -1054,16 +1038,16 @@ extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deter
 // launches in front of the policy's.
 extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                uint64_t row_offset, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
-    if (!h || !lstm || !p || !o || !lb) return fail(WG_ERR_INVALID, "wg_rollout_lstm: null argument");
+    if (!h || !lstm || !p || !o || !lb) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: null argument");
     const int N = h->p.N, O = h->p.obs_dim;
     int l_in = 0, H = 0, nets = 0, l_device = 0;
     if (int rc = wg_lstm_geometry_(lstm, &l_in, &H, &nets, &l_device)) return rc;
     if (l_in != O)
-        return fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm reads rows of " + std::to_string(l_in) + " inputs, the handle's obs_dim is " + std::to_string(O));
-    if (l_device != h->device) return fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm and handle live on different devices");
+        return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm reads rows of " + std::to_string(l_in) + " inputs, the handle's obs_dim is " + std::to_string(O));
+    if (l_device != h->device) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm and handle live on different devices");
     if (!lb->state || !lb->episode_start || !lb->scratch)
-        return fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm_bufs needs state, episode_start and scratch");
-    if (p->P.n_layers[1] == 0) return fail(WG_ERR_INVALID, "wg_rollout_lstm: p needs a critic (on the LSTM's hidden rows)");
+        return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm_bufs needs state, episode_start and scratch");
+    if (p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: p needs a critic (on the LSTM's hidden rows)");
     const RolloutRows g = {"wg_rollout_lstm", "obs", 1, H, N,
                            ": p reads the LSTM's hidden rows, and lstm's hidden size / the handle's n_turb are " + std::to_string(H) + " / " + std::to_string(N),
                            nullptr, false,
@@ -1071,13 +1055,13 @@ extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_ste
                             o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
                            1, H, o->obs, o->final_obs, "final_obs", nullptr, nullptr, lstm, lb};
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
 }
 
 extern "C" int wg_metrics(wg_handle h, float* out_dev, int reset_after, void* stream) {
-    if (!h || !out_dev) return fail(WG_ERR_INVALID, "null argument");
-    if (int rc = use_device(h)) return rc;
+    if (!h || !out_dev) return wg_fail(WG_ERR_INVALID, "null argument");
+    if (int rc = wg_use_device(h->device)) return rc;
     wg_launch_metrics(&h->p, &h->d, out_dev, reset_after, (hipStream_t)stream);
     return 0;
 }
@@ -1105,41 +1089,41 @@ static StateHeader state_header(const wg_env_s* h) {
 }
 
 extern "C" int wg_get_state(wg_handle h, void* blob_host, size_t* size) {
-    if (!h || !size) return fail(WG_ERR_INVALID, "null argument");
+    if (!h || !size) return wg_fail(WG_ERR_INVALID, "null argument");
     const StateHeader sh = state_header(h);
     const size_t total = sizeof(StateHeader) + sh.payload;
     if (!blob_host) {
         *size = total;
         return 0;
     }
-    if (*size < total) return fail(WG_ERR_INVALID, "state buffer too small");
-    if (int rc = use_device(h)) return rc;
-    HIPCHK(hipDeviceSynchronize());
+    if (*size < total) return wg_fail(WG_ERR_INVALID, "state buffer too small");
+    if (int rc = wg_use_device(h->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
     char* o = (char*)blob_host;
     memcpy(o, &sh, sizeof(sh));
     o += sizeof(sh);
     for (size_t i : h->state_idx) {
-        HIPCHK(hipMemcpy(o, h->allocs[i].ptr, h->allocs[i].bytes, hipMemcpyDeviceToHost));
+        WG_HIPCHK(hipMemcpy(o, h->allocs[i].ptr, h->allocs[i].bytes, hipMemcpyDeviceToHost));
         o += h->allocs[i].bytes;
     }
     *size = total;
     return 0;
 }
 extern "C" int wg_set_state(wg_handle h, const void* blob_host, size_t size) {
-    if (!h || !blob_host) return fail(WG_ERR_INVALID, "null argument");
+    if (!h || !blob_host) return wg_fail(WG_ERR_INVALID, "null argument");
     const StateHeader want = state_header(h);
-    if (size < sizeof(StateHeader)) return fail(WG_ERR_INVALID, "state blob too small");
+    if (size < sizeof(StateHeader)) return wg_fail(WG_ERR_INVALID, "state blob too small");
     StateHeader got;
     memcpy(&got, blob_host, sizeof(got));
-    if (got.magic != WG_STATE_MAGIC) return fail(WG_ERR_INVALID, "not a windgym state blob");
+    if (got.magic != WG_STATE_MAGIC) return wg_fail(WG_ERR_INVALID, "not a windgym state blob");
     if (memcmp(&got, &want, sizeof(got)) || size != sizeof(StateHeader) + want.payload)
-        return fail(WG_ERR_INVALID, "state blob was taken from a differently configured handle (or another ABI version)");
-    if (int rc = use_device(h)) return rc;
-    HIPCHK(hipDeviceSynchronize());
+        return wg_fail(WG_ERR_INVALID, "state blob was taken from a differently configured handle (or another ABI version)");
+    if (int rc = wg_use_device(h->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
     const char* o = (const char*)blob_host + sizeof(StateHeader);
-    if (h->d.next_obs_ok) HIPCHK(hipMemset(h->d.next_obs_ok, 0, sizeof(int) * (size_t)h->p.B * 2));      // (derived data, not in the blob)
+    if (h->d.next_obs_ok) WG_HIPCHK(hipMemset(h->d.next_obs_ok, 0, sizeof(int) * (size_t)h->p.B * 2));      // (derived data, not in the blob)
     for (size_t i : h->state_idx) {
-        HIPCHK(hipMemcpy(h->allocs[i].ptr, o, h->allocs[i].bytes, hipMemcpyHostToDevice));
+        WG_HIPCHK(hipMemcpy(h->allocs[i].ptr, o, h->allocs[i].bytes, hipMemcpyHostToDevice));
         o += h->allocs[i].bytes;
     }
     return 0;
@@ -1147,19 +1131,19 @@ extern "C" int wg_set_state(wg_handle h, const void* blob_host, size_t size) {
 
 extern "C" int wg_kernel_timing(wg_handle h, int enable, double* flow_ms_avg, double* glue_ms_avg, int* n_launches,
                                 double* flow_steps_per_launch, double* particles_per_launch) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
-    HIPCHK(hipDeviceSynchronize());
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
+    WG_HIPCHK(hipDeviceSynchronize());
     unsigned long long fs_now = 0, pt_now = 0, ad_now = 0;
     {
         const size_t n_slots = (size_t)h->p.B * 2 * h->p.F;
         std::vector<WgSlot> slots(n_slots);
-        HIPCHK(hipMemcpy(slots.data(), h->d.slot, sizeof(WgSlot) * n_slots, hipMemcpyDeviceToHost));
+        WG_HIPCHK(hipMemcpy(slots.data(), h->d.slot, sizeof(WgSlot) * n_slots, hipMemcpyDeviceToHost));
         for (const WgSlot& s : slots) { fs_now += s.flow_count; pt_now += s.part_count; ad_now += s.add_count; }
     }
     double fsum = 0, gsum = 0;
     int nf = 0, ng = 0;
     if (h->ev_used) {
-        HIPCHK(hipDeviceSynchronize());
+        WG_HIPCHK(hipDeviceSynchronize());
         for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]) != hipSuccess) continue;
@@ -1190,7 +1174,7 @@ extern "C" int wg_kernel_timing(wg_handle h, int enable, double* flow_ms_avg, do
     if (h->timing && h->ev.empty()) {          // the event pool, created here so that no timed region ever pays for it
         for (size_t i = 0; i < WG_MAX_TIMING_EVENTS; ++i) {
             hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
+            WG_HIPCHK(hipEventCreate(&e));
             h->ev.push_back(e);
         }
         h->ev_kind.assign(WG_MAX_TIMING_EVENTS / 2, 0);
@@ -1201,12 +1185,12 @@ extern "C" int wg_kernel_timing(wg_handle h, int enable, double* flow_ms_avg, do
 // what wg_steady_power and wg_steady_optimize check alike, and the parameter block their kernels share
 static int steady_params(wg_handle h, const char* who, int model, int n_cases, SteadyP* sp) {
     const std::string w(who);
-    if (model != 0 && model != 1) return fail(WG_ERR_INVALID, w + ": model must be 0 (steady state of M0) or 1 (Blondel-Cathelain + Jimenez)");
-    if (n_cases < 1) return fail(WG_ERR_INVALID, w + ": " + (w == "wg_steady_power" ? "n_cases" : "n_cond") + " must be >= 1");
+    if (model != 0 && model != 1) return wg_fail(WG_ERR_INVALID, w + ": model must be 0 (steady state of M0) or 1 (Blondel-Cathelain + Jimenez)");
+    if (n_cases < 1) return wg_fail(WG_ERR_INVALID, w + ": " + (w == "wg_steady_power" ? "n_cases" : "n_cond") + " must be >= 1");
     // model 0 is documented as the steady state of THIS handle's flow model; k_steady carries the Gaussian M0 with TI folding
     // only — a handle created with another deficit / without the folding must not get Gaussian powers silently
     if (model == 0 && (h->fp.deficit_model != 0 || h->fp.no_ti_fold))
-        return fail(WG_ERR_UNSUPPORTED, w + ": model 0 (steady state of the handle's flow model) is implemented for the Gaussian deficit "
+        return wg_fail(WG_ERR_UNSUPPORTED, w + ": model 0 (steady state of the handle's flow model) is implemented for the Gaussian deficit "
                                         "with wake-TI folding only; this handle uses deficit_model " + std::to_string(h->fp.deficit_model) +
                                         (h->fp.no_ti_fold ? " without TI folding" : ""));
     memset(sp, 0, sizeof(*sp));
@@ -1223,45 +1207,45 @@ static int steady_params(wg_handle h, const char* who, int model, int n_cases, S
 
 extern "C" int wg_steady_power(wg_handle h, int model, int n_cases, const float* ws_dev, const float* wd_dev, const float* ti_dev,
                                const float* yaw_dev, float* power_dev, void* stream) {
-    if (!h || !ws_dev || !wd_dev || !ti_dev || !yaw_dev || !power_dev) return fail(WG_ERR_INVALID, "null argument");
+    if (!h || !ws_dev || !wd_dev || !ti_dev || !yaw_dev || !power_dev) return wg_fail(WG_ERR_INVALID, "null argument");
     SteadyP sp;
     if (int rc = steady_params(h, "wg_steady_power", model, n_cases, &sp)) return rc;
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     wg_launch_steady(&sp, ws_dev, wd_dev, ti_dev, yaw_dev, power_dev, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int wg_steady_optimize(wg_handle h, int model, int n_cond, const float* ws_dev, const float* wd_dev, const float* ti_dev,
                                   int refine_pass_n, int yaw_n, const double* offsets_dev, double yaw_clip, double* yaw_dev,
                                   double* power_dev, int32_t* order_dev, void* stream) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
-    if (yaw_n < 2 || yaw_n > 16) return fail(WG_ERR_INVALID, "wg_steady_optimize: yaw_n must be 2 .. 16 (one wave per candidate), got " + std::to_string(yaw_n));
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
+    if (yaw_n < 2 || yaw_n > 16) return wg_fail(WG_ERR_INVALID, "wg_steady_optimize: yaw_n must be 2 .. 16 (one wave per candidate), got " + std::to_string(yaw_n));
     if (refine_pass_n < 1 || refine_pass_n > 16)
-        return fail(WG_ERR_INVALID, "wg_steady_optimize: refine_pass_n must be 1 .. 16, got " + std::to_string(refine_pass_n));
-    if (!(yaw_clip >= 0.0)) return fail(WG_ERR_INVALID, "wg_steady_optimize: yaw_clip must be >= 0");
+        return wg_fail(WG_ERR_INVALID, "wg_steady_optimize: refine_pass_n must be 1 .. 16, got " + std::to_string(refine_pass_n));
+    if (!(yaw_clip >= 0.0)) return wg_fail(WG_ERR_INVALID, "wg_steady_optimize: yaw_clip must be >= 0");
     if (!ws_dev || !wd_dev || !ti_dev || !offsets_dev || !yaw_dev)
-        return fail(WG_ERR_INVALID, "wg_steady_optimize: null argument (only power_dev and order_dev may be NULL)");
+        return wg_fail(WG_ERR_INVALID, "wg_steady_optimize: null argument (only power_dev and order_dev may be NULL)");
     SteadyP sp;
     if (int rc = steady_params(h, "wg_steady_optimize", model, n_cond, &sp)) return rc;
     if (wg_steady_srf_lds(sp.N, yaw_n) > 65536)
-        return fail(WG_ERR_UNSUPPORTED, "wg_steady_optimize: " + std::to_string(sp.N) + " turbines x " + std::to_string(yaw_n) +
+        return wg_fail(WG_ERR_UNSUPPORTED, "wg_steady_optimize: " + std::to_string(sp.N) + " turbines x " + std::to_string(yaw_n) +
                                         " candidates do not fit the 64 KB of LDS of a workgroup");
-    if (int rc = use_device(h)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
     wg_launch_steady_srf(&sp, ws_dev, wd_dev, ti_dev, refine_pass_n, yaw_n, offsets_dev, yaw_clip, yaw_dev, power_dev, order_dev,
                          (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int wg_added_lookups(wg_handle h, double* rotor_points_per_launch) {
-    if (!h || !rotor_points_per_launch) return fail(WG_ERR_INVALID, "null argument");
+    if (!h || !rotor_points_per_launch) return wg_fail(WG_ERR_INVALID, "null argument");
     *rotor_points_per_launch = h->added_per_launch;
     return 0;
 }
 
 extern "C" int wg_flow_variant(wg_handle h, int* block, int* compact, int* duo) {
-    if (!h) return fail(WG_ERR_INVALID, "null handle");
+    if (!h) return wg_fail(WG_ERR_INVALID, "null handle");
     if (block) *block = h->fp.block;
     if (compact) *compact = h->fp.res;
     if (duo) *duo = h->fp.envw ? 2 : 0;      // 0: one farm slot per workgroup, 2: k_flow_env (one or two waves per env)
@@ -1269,14 +1253,14 @@ extern "C" int wg_flow_variant(wg_handle h, int* block, int* compact, int* duo) 
 }
 
 extern "C" int wg_handle_actuation_(wg_handle h, WgActuation* out) {
-    if (!h || !out) return fail(WG_ERR_INVALID, "null handle");
+    if (!h || !out) return wg_fail(WG_ERR_INVALID, "null handle");
     out->B = h->p.B; out->N = h->p.N; out->action_method = h->p.action_method; out->device = h->device;
     out->yaw_min = h->p.yaw_min; out->yaw_max = h->p.yaw_max; out->yaw_step = h->p.yaw_step; out->yaw_max_d = h->p.yaw_max_d;
     return 0;
 }
 
 extern "C" int wg_algorithmic_bytes(wg_handle h, double* bytes_per_step) {
-    if (!h || !bytes_per_step) return fail(WG_ERR_INVALID, "null argument");
+    if (!h || !bytes_per_step) return wg_fail(WG_ERR_INVALID, "null argument");
     *bytes_per_step = h->plan.alg_bytes;
     return 0;
 }

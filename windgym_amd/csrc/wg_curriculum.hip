@@ -16,7 +16,7 @@
 #include <string>
 
 #include "../../include/windgym_hip.h"
-#include "wg_internal.h"
+#include "wg_host.h"
 
 namespace {
 
@@ -127,7 +127,6 @@ __global__ __launch_bounds__(64) void k_curriculum(const CurP p, const CurState 
     s.n[b] = n; s.osc[b] = osc; s.cum[b] = cum; s.last[b] = last;
 }
 
-int fail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
 
 }  // namespace
 
@@ -139,33 +138,21 @@ struct wg_curriculum_s {
     int* err = nullptr;         // device: {latched, t, b, row} of an ep_row entry >= C
 };
 
-#define CUR_HIPCHK(x)                                                                          \
-    do {                                                                                       \
-        hipError_t _e = (x);                                                                   \
-        if (_e != hipSuccess) return fail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-static int cur_use_device(wg_curriculum c) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != c->a.device) CUR_HIPCHK(hipSetDevice(c->a.device));
-    return 0;
-}
-
 extern "C" int wg_curriculum_create(wg_handle h, wg_curriculum* out) {
-    if (!h || !out) return fail(WG_ERR_INVALID, "wg_curriculum_create: null argument");
+    if (!h || !out) return wg_fail(WG_ERR_INVALID, "wg_curriculum_create: null argument");
     wg_curriculum_s* c = new (std::nothrow) wg_curriculum_s;
-    if (!c) return fail(WG_ERR_NOMEM, "wg_curriculum_create: out of memory");
+    if (!c) return wg_fail(WG_ERR_NOMEM, "wg_curriculum_create: out of memory");
     if (int rc = wg_handle_actuation_(h, &c->a)) { delete c; return rc; }
     const size_t B = (size_t)c->a.B, BN = B * (size_t)c->a.N;
     c->bytes = 8 * (2 * BN + 4 * B) + 4 * BN;
-    if (int rc = cur_use_device(c)) { delete c; return rc; }
+    if (int rc = wg_use_device(c->a.device)) { delete c; return rc; }
     hipError_t e = hipMalloc(&c->mem, c->bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&c->err, 4 * sizeof(int));
     if (e == hipSuccess) e = hipMemset(c->mem, 0, c->bytes);
     if (e == hipSuccess) e = hipMemset(c->err, 0, 4 * sizeof(int));
     if (e != hipSuccess) {
         wg_curriculum_destroy(c);
-        return fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_curriculum_create: ") + hipGetErrorString(e));
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_curriculum_create: ") + hipGetErrorString(e));
     }
     char* m = (char*)c->mem;
     c->s.yprev = (double*)m; m += 8 * BN;
@@ -199,42 +186,42 @@ static CurHeader cur_header(wg_curriculum c) {
 }
 
 extern "C" int wg_curriculum_get_state(wg_curriculum c, void* host, size_t* size) {
-    if (!c || !size) return fail(WG_ERR_INVALID, "wg_curriculum_get_state: null argument");
+    if (!c || !size) return wg_fail(WG_ERR_INVALID, "wg_curriculum_get_state: null argument");
     const size_t total = sizeof(CurHeader) + c->bytes;
     if (!host) {
         *size = total;
         return 0;
     }
-    if (*size < total) return fail(WG_ERR_INVALID, "wg_curriculum_get_state: state buffer too small");
-    if (int rc = cur_use_device(c)) return rc;
-    CUR_HIPCHK(hipDeviceSynchronize());
+    if (*size < total) return wg_fail(WG_ERR_INVALID, "wg_curriculum_get_state: state buffer too small");
+    if (int rc = wg_use_device(c->a.device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
     int err[4];
-    CUR_HIPCHK(hipMemcpy(err, c->err, sizeof(err), hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy(err, c->err, sizeof(err), hipMemcpyDeviceToHost));
     if (err[0]) {
-        CUR_HIPCHK(hipMemset(c->err, 0, sizeof(err)));
-        return fail(WG_ERR_INVALID, "wg_curriculum_shape: ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
+        WG_HIPCHK(hipMemset(c->err, 0, sizeof(err)));
+        return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
                                         std::to_string(err[3]) + " is not a row of ep_target_dev (C rows); the entry was skipped");
     }
     const CurHeader hd = cur_header(c);
     memcpy(host, &hd, sizeof(hd));
-    CUR_HIPCHK(hipMemcpy((char*)host + sizeof(hd), c->mem, c->bytes, hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy((char*)host + sizeof(hd), c->mem, c->bytes, hipMemcpyDeviceToHost));
     *size = total;
     return 0;
 }
 
 extern "C" int wg_curriculum_set_state(wg_curriculum c, const void* host, size_t size) {
-    if (!c || !host) return fail(WG_ERR_INVALID, "wg_curriculum_set_state: null argument");
-    if (size < sizeof(CurHeader)) return fail(WG_ERR_INVALID, "wg_curriculum_set_state: state blob too small");
+    if (!c || !host) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: null argument");
+    if (size < sizeof(CurHeader)) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: state blob too small");
     CurHeader got;
     memcpy(&got, host, sizeof(got));
-    if (got.magic != CUR_MAGIC) return fail(WG_ERR_INVALID, "wg_curriculum_set_state: not a curriculum state blob");
+    if (got.magic != CUR_MAGIC) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: not a curriculum state blob");
     const CurHeader want = cur_header(c);
     if (memcmp(&got, &want, sizeof(got)) || size != sizeof(CurHeader) + c->bytes)
-        return fail(WG_ERR_INVALID, "wg_curriculum_set_state: the blob was taken from a curriculum of " + std::to_string(got.B) + " envs x " +
+        return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: the blob was taken from a curriculum of " + std::to_string(got.B) + " envs x " +
                                         std::to_string(got.N) + " turbines, this one has " + std::to_string(want.B) + " x " + std::to_string(want.N));
-    if (int rc = cur_use_device(c)) return rc;
-    CUR_HIPCHK(hipDeviceSynchronize());
-    CUR_HIPCHK(hipMemcpy(c->mem, (const char*)host + sizeof(CurHeader), c->bytes, hipMemcpyHostToDevice));
+    if (int rc = wg_use_device(c->a.device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipMemcpy(c->mem, (const char*)host + sizeof(CurHeader), c->bytes, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -243,20 +230,20 @@ static int cur_on_device(wg_curriculum c, const void* ptr, const char* name) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not a device pointer");
+        return wg_fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not a device pointer");
     }
     if (at.type != hipMemoryTypeDevice || at.device != c->a.device)
-        return fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not memory of device " + std::to_string(c->a.device) +
+        return wg_fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not memory of device " + std::to_string(c->a.device) +
                                         ", the device of the handle the curriculum was created on");
     return 0;
 }
 
 extern "C" int wg_curriculum_set_targets(wg_curriculum c, const double* yaw_dev, void* stream) {
-    if (!c) return fail(WG_ERR_INVALID, "wg_curriculum_set_targets: null curriculum");
-    if (!yaw_dev) return fail(WG_ERR_INVALID, "wg_curriculum_set_targets: yaw_dev is null");
+    if (!c) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_targets: null curriculum");
+    if (!yaw_dev) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_targets: yaw_dev is null");
     if (int rc = cur_on_device(c, yaw_dev, "yaw_dev")) return rc;
-    if (int rc = cur_use_device(c)) return rc;
-    CUR_HIPCHK(hipMemcpyAsync(c->s.g, yaw_dev, sizeof(double) * (size_t)c->a.B * c->a.N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (int rc = wg_use_device(c->a.device)) return rc;
+    WG_HIPCHK(hipMemcpyAsync(c->s.g, yaw_dev, sizeof(double) * (size_t)c->a.B * c->a.N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -264,11 +251,11 @@ extern "C" int wg_curriculum_shape(wg_curriculum c, int T, const float* yaw0_dev
                                    const uint8_t* truncated_dev, const int32_t* ep_row_dev, const double* ep_target_dev, int C,
                                    const double* weight_dev, double momentum, const float* reward_dev, float* shaped_out,
                                    float* yaw_diff_out, float* yaw_out, void* stream) {
-    if (!c) return fail(WG_ERR_INVALID, "wg_curriculum_shape: null curriculum");
-    if (T < 0) return fail(WG_ERR_INVALID, "wg_curriculum_shape: T must be >= 0, got " + std::to_string(T));
-    if (C < 0) return fail(WG_ERR_INVALID, "wg_curriculum_shape: C must be >= 0, got " + std::to_string(C));
+    if (!c) return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: null curriculum");
+    if (T < 0) return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: T must be >= 0, got " + std::to_string(T));
+    if (C < 0) return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: C must be >= 0, got " + std::to_string(C));
     if (!(momentum >= 0.0 && momentum < 1.0))
-        return fail(WG_ERR_INVALID, "wg_curriculum_shape: momentum must lie in [0, 1), got " + std::to_string(momentum));
+        return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: momentum must lie in [0, 1), got " + std::to_string(momentum));
     const struct { const void* ptr; const char* name; bool required; } args[] = {
         {yaw0_dev, "yaw0_dev", true}, {actions_dev, "actions_dev", true}, {yaw_after_dev, "yaw_after_dev", true},
         {truncated_dev, "truncated_dev", true}, {ep_row_dev, "ep_row_dev", true}, {ep_target_dev, "ep_target_dev", C > 0},
@@ -276,19 +263,19 @@ extern "C" int wg_curriculum_shape(wg_curriculum c, int T, const float* yaw0_dev
         {yaw_diff_out, "yaw_diff_out", false}, {yaw_out, "yaw_out", false}};
     for (const auto& a : args) {
         if (!a.ptr) {
-            if (a.required) return fail(WG_ERR_INVALID, std::string("wg_curriculum_shape: ") + a.name + " is null");
+            if (a.required) return wg_fail(WG_ERR_INVALID, std::string("wg_curriculum_shape: ") + a.name + " is null");
             continue;
         }
         if (int rc = cur_on_device(c, a.ptr, a.name)) return rc;
     }
     if (T == 0) return 0;
-    if (int rc = cur_use_device(c)) return rc;
+    if (int rc = wg_use_device(c->a.device)) return rc;
     CurP p;
     p.B = c->a.B; p.N = c->a.N; p.T = T; p.C = C; p.action_method = c->a.action_method;
     p.yaw_min = c->a.yaw_min; p.yaw_max = c->a.yaw_max; p.yaw_step = c->a.yaw_step;
     p.yaw_max_d = c->a.yaw_max_d; p.momentum = momentum;
     hipLaunchKernelGGL(k_curriculum, dim3((p.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, p, c->s, c->err, yaw0_dev, actions_dev,
                        yaw_after_dev, truncated_dev, ep_row_dev, ep_target_dev, weight_dev, reward_dev, shaped_out, yaw_diff_out, yaw_out);
-    CUR_HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }

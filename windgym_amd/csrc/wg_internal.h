@@ -14,6 +14,7 @@ struct WgPtrs;
 struct WgPopRows;
 struct WgPolicyP;
 struct WgPopMember;
+struct WgPacked;
 struct WgValueRows {           // the critic on n_rows rows: obs [n_rows][critic's input width] -> value [n_rows]
     const float* obs;
     float* value;
@@ -35,6 +36,12 @@ int wg_handle_actuation_(wg_handle h, WgActuation* out);
 int wg_norm_geometry_(wg_norm n, int* n_obs, int* n_envs, int* device);
 // wg_lstm.hip: the shape a wg_lstm was created for and its device (wg_rollout_lstm's checks)
 int wg_lstm_geometry_(wg_lstm l, int* n_in, int* hidden, int* n_nets, int* device);
+// wg_policy.hip: a handle's device copies of its parameters (wg_tile.h: WgPacked) — allocate on `device` (the packed copy zeroed;
+// on failure nothing is left allocated, WG_ERR_NOMEM / WG_ERR_HIP reported as `who`), free after a device synchronisation, and the
+// pointer a set_params' pack kernel reads: `params` itself, or the stage after an asynchronous copy of a host pointer
+int wg_packed_alloc_(WgPacked* w, int device, uint32_t n_flat, uint32_t n_packed, const char* who);
+void wg_packed_free_(WgPacked* w);
+int wg_packed_source_(WgPacked* w, const float* params, int on_device, hipStream_t st, const float** src);
 // wg_policy.hip: ONE launch of k_policy — the actor on n_rows rows of obs_dev (when action / raw / logp is wanted) and the critic on
 // each of n_v <= 2 row sets of its own (rows of the critic's input width -> value); a set of no rows is skipped
 int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,

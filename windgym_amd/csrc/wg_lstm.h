@@ -14,16 +14,15 @@
 // PACKED copy (what the kernel reads; owned by the handle, written by k_lstm_pack): the step is ONE GEMM per net with K = n_in + H
 // and M = 4H, whose output tile 4u + q holds gate q of the hidden units 32u .. 32u + 31 — so the wave that owns the tiles
 // 4u .. 4u + 3 holds all four gates of its units in registers and finishes the cell there.  Per net
-//     Wp[tile][ks][lane] = Wcat[q H + 32 u + (lane & 31)][2 ks + (lane >> 5)]     (0 for units >= H and k >= K; ks < nks)
-//         — the A operand of v_mfma_f32_32x32x2_f32, as wg_policy.h's,
-//     bp[tile][j]        = b_ih[q H + 32 u + j] + b_hh[q H + 32 u + j]            (0 for units >= H): the two biases are added
-//         ONCE, here, in this order, and the sum initialises the accumulator,
-// then one k-group of zeros behind the last net.  Padding lives here, never in the caller's tensors.
+//     weight block (wg_tile.h) with row(tile, j) = wgl_tile_row: row q H + 32 u + j of Wcat, padding for units 32 u + j >= H,
+//     bias block     bp[tile][j] = b_ih[row] + b_hh[row]: the two biases are added ONCE, here, in this order, and the sum
+//         initialises the accumulator,
+// then the slack behind the last net.  Padding lives here, never in the caller's tensors.
 #ifndef WG_LSTM_H
 #define WG_LSTM_H
 #include <stdint.h>
 
-#include "wg_policy.h"       // the tile constants: WGP_TILE, WGP_KC, WGP_WAVES, WGP_GROUP, WGP_MAX_IN
+#include "wg_policy.h"       // WGP_MAX_IN; wg_tile.h: the tile constants and the packed layout
 
 #define WGL_MAX_H 256        // = 8 unit blocks of 32: wave w owns the blocks w and w + 4
 
@@ -35,17 +34,41 @@ struct WgLstmNet {
 struct WgLstmP {
     int32_t n_in, H, n_nets;
     int32_t K;                 // n_in + H
-    int32_t nks;               // k-steps = ceil(K / 2) rounded up to PAIRS of groups of WGP_GROUP
+    int32_t nks;               // wg_tile_nks(K)
     int32_t nub;               // unit blocks = ceil(H / 32); a net has 4 nub output tiles
     WgLstmNet net[2];
     uint32_t n_flat, n_packed;
 };
 
+// the gate-to-tile map: element j of output tile 4u + q is row q H + 32 u + j of [4H] (gate q of unit 32 u + j); -1: padding
+WG_TILE_HD int32_t wgl_tile_row(uint32_t tile, uint32_t j, int32_t H) {
+    const int32_t unit = 32 * (int32_t)(tile >> 2) + (int32_t)j;
+    return unit < H ? (int32_t)(tile & 3) * H + unit : -1;
+}
+
+// Both layouts of a (validated) shape: the flat order above, a block pair per net in the packed vector
+inline void wgl_fill_layout(WgLstmP& P, const wg_lstm_desc* d) {
+    P.n_in = d->n_in; P.H = d->hidden; P.n_nets = d->n_nets;
+    P.K = P.n_in + P.H;
+    P.nks = wg_tile_nks(P.K);
+    P.nub = wg_tile_count(P.H);
+    uint32_t flat = 0, packed = 0;
+    const uint32_t H4 = 4u * P.H;
+    for (int net = 0; net < P.n_nets; ++net) {
+        WgLstmNet& nt = P.net[net];
+        nt.wih_flat = flat; flat += H4 * P.n_in;
+        nt.whh_flat = flat; flat += H4 * P.H;
+        nt.bih_flat = flat; flat += H4;
+        nt.bhh_flat = flat; flat += H4;
+        nt.w_packed = packed; packed += wg_tile_wsize(4 * P.nub, P.nks);
+        nt.b_packed = packed; packed += wg_tile_bsize(4 * P.nub);
+    }
+    P.n_flat = flat; P.n_packed = packed + WGP_SLACK;
+}
+
 struct wg_lstm_s {
     WgLstmP P;
-    int device;
-    float* packed;             // [P.n_packed]
-    float* flat_stage;         // [P.n_flat] staging copy for host-pointer wg_lstm_set_params
+    WgPacked w;                // [P.n_flat] / [P.n_packed]
 };
 
 #endif

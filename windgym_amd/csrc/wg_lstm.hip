@@ -3,7 +3,7 @@
 // them (wg_lstm.h states the model and both layouts).
 //
 // k_lstm: one workgroup of 4 waves owns 32 rows of ONE net.  The step is one GEMM D[4H][row] = Wcat[4H][K] xcat[K][row], K = n_in + H,
-// on v_mfma_f32_32x32x2_f32 — the k-ordered f32 fmaf chain of k_policy (wg_policy.hip: wgp_tile), so a row's result depends on
+// on the tile core of wg_tile.h — the k-ordered f32 fmaf chain of k_policy, so a row's result depends on
 // nothing but that row, its state and the weights (no atomics, no cross-row sum, an order fixed by the shapes alone).  The row
 // x ‖ select(start, 0, h) streams through LDS as [k][32 rows] in chunks of 256 (conflict-free stores and one ds_read per k-step);
 // the weights come packed from L2 as the A operand, output tile 4u + q = gate q of the units 32u .. 32u + 31.  Wave w accumulates
@@ -16,39 +16,7 @@
 
 #include "../../include/windgym_hip.h"
 #include "wg_lstm.h"
-#include "wg_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// One output tile over one staged chunk: nks k-steps (a multiple of 2 WGP_GROUP) of A operands from wp (this lane's), B operands
-// from xb (this lane's).  k-steps in groups of WGP_GROUP: the A operands of group g + 1 (global loads, L2 latency) are requested
-// before the MFMAs of group g issue (wg_policy.hip).  No bounds tests: a tile's k-steps are padded to pairs of groups with zero
-// weights, the staged rows behind them hold zeros, and the packed vector ends in one group of slack for the last prefetch.
-__device__ __forceinline__ void wgl_gemm(f32x16& acc, const float* __restrict__ wp, const float* __restrict__ xb, const int nks) {
-    float a0[WGP_GROUP], a1[WGP_GROUP], b[WGP_GROUP];
-#pragma unroll
-    for (int i = 0; i < WGP_GROUP; ++i) a0[i] = wp[i * 64];
-    for (int ks0 = 0; ks0 < nks; ks0 += 2 * WGP_GROUP) {
-#pragma unroll
-        for (int i = 0; i < WGP_GROUP; ++i) {
-            a1[i] = wp[(size_t)(ks0 + WGP_GROUP + i) * 64];
-            b[i] = xb[(ks0 + i) * 2 * WGP_TILE];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < WGP_GROUP; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b[i], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < WGP_GROUP; ++i) {
-            a0[i] = wp[(size_t)(ks0 + 2 * WGP_GROUP + i) * 64];
-            b[i] = xb[(ks0 + WGP_GROUP + i) * 2 * WGP_TILE];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < WGP_GROUP; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b[i], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
+#include "wg_host.h"
 
 __device__ __forceinline__ float wgl_sigmoid(const float z) { return 1.0f / (1.0f + expf(-z)); }
 
@@ -80,42 +48,34 @@ __global__ __launch_bounds__(WGP_WAVES * 64, 2) void k_lstm(const WgLstmP P, con
         const int ub = wave + WGP_WAVES * t;
         if (ub < P.nub) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float* bp = packed + nt.b_packed + (4 * ub + q) * 32 + 4 * hh;
-#pragma unroll
-                for (int g = 0; g < 16; ++g) acc[t][q][g] = bp[(g & 3) + 8 * (g >> 2)];
-            }
+            for (int q = 0; q < 4; ++q) wg_tile_bias(acc[t][q], packed + nt.b_packed + (4 * ub + q) * 32, hh);
         }
     }
     const float* xrow = x + (size_t)row * n_in;
     const float* hrow = h_in + (size_t)row * H;
     const float* xb = lds + hh * WGP_TILE + r;
     for (int k0 = 0; k0 < K; k0 += WGP_KC) {
-        const int kc = min(WGP_KC, K - k0), kcp = (kc + 4 * WGP_GROUP - 1) & ~(4 * WGP_GROUP - 1);
-        // x ‖ h -> LDS [k][row]: a wave covers 32 rows x 2 inputs per pass.  Rows past n_rows, the pad up to whole pairs of k-groups
-        // and the h of a fresh row are zeros.
-        __syncthreads();
-        for (int k = tid >> 5; k < kcp; k += WGP_WAVES * 2) {
+        const int kc = min(WGP_KC, K - k0), kcp = wg_tile_kpad(kc);
+        // x ‖ h -> LDS: rows past n_rows, the pad behind kc and the h of a fresh row are zeros
+        wg_tile_stage(lds, tid, kcp, [&](const int k) {
             const int kk = k0 + k;
             float v = 0.0f;
             if (valid && k < kc) {
                 if (kk < n_in) v = xrow[kk];
                 else if (!fresh) v = hrow[kk - n_in];
             }
-            lds[k * WGP_TILE + r] = v;
-        }
-        __syncthreads();
+            return v;
+        });
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int ub = wave + WGP_WAVES * t;
             if (ub < P.nub) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    wgl_gemm(acc[t][q], packed + nt.w_packed + ((size_t)(4 * ub + q) * P.nks + (k0 >> 1)) * 64 + lane, xb, kcp >> 1);
+                    wg_tile_gemm(acc[t][q], packed + nt.w_packed + ((size_t)(4 * ub + q) * P.nks + (k0 >> 1)) * 64 + lane, xb, kcp >> 1);
             }
         }
     }
-    // D: lane = (row r, half hh), register g = unit 32 ub + (g & 3) + 8 (g >> 2) + 4 hh — of each of the four gates
     float* h_new = state_out ? state_out + (size_t)net * 2 * plane : nullptr;
     float* c_new = h_new ? h_new + plane : nullptr;
     float* h_out = net == 0 ? h_out0 : h_out1;
@@ -126,7 +86,7 @@ __global__ __launch_bounds__(WGP_WAVES * 64, 2) void k_lstm(const WgLstmP P, con
         if (ub < P.nub) {
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const int unit = 32 * ub + (g & 3) + 8 * (g >> 2) + 4 * hh;
+                const int unit = 32 * ub + wg_tile_drow(g, hh);       // of each of the four gates
                 if (unit < H) {
                     const size_t o = (size_t)row * H + unit;
                     const float c = fresh ? 0.0f : c_in[o];
@@ -145,20 +105,19 @@ __global__ void k_lstm_pack(const WgLstmP P, const float* __restrict__ flat, flo
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P.n_packed) return;
     const uint32_t H = P.H, n_in = P.n_in, K = P.K, nks = P.nks;
-    const uint32_t wsize = 4u * P.nub * nks * 64, bsize = 4u * P.nub * 32;
+    const uint32_t wsize = wg_tile_wsize(4 * P.nub, nks), bsize = wg_tile_bsize(4 * P.nub);
     float v = 0.0f;
     for (int net = 0; net < P.n_nets; ++net) {
         const WgLstmNet nt = P.net[net];
         if (idx >= nt.w_packed && idx < nt.w_packed + wsize) {
-            const uint32_t e = idx - nt.w_packed, lane = e & 63, ks = (e >> 6) % nks, tile = (e >> 6) / nks;
-            const uint32_t unit = 32 * (tile >> 2) + (lane & 31), q = tile & 3, k = 2 * ks + (lane >> 5);
-            if (unit < H && k < K) {
-                const size_t i = (size_t)q * H + unit;
-                v = k < n_in ? flat[nt.wih_flat + i * n_in + k] : flat[nt.whh_flat + i * H + (k - n_in)];
-            }
+            const WgTileElem e = wg_tile_decode(idx - nt.w_packed, nks);
+            const int32_t i = wgl_tile_row(e.tile, e.j, H);
+            if (i >= 0 && e.k < K)
+                v = e.k < n_in ? flat[nt.wih_flat + (size_t)i * n_in + e.k] : flat[nt.whh_flat + (size_t)i * H + (e.k - n_in)];
         } else if (idx >= nt.b_packed && idx < nt.b_packed + bsize) {
-            const uint32_t e = idx - nt.b_packed, tile = e >> 5, unit = 32 * (tile >> 2) + (e & 31), q = tile & 3;
-            if (unit < H) v = flat[nt.bih_flat + q * H + unit] + flat[nt.bhh_flat + q * H + unit];
+            const uint32_t e = idx - nt.b_packed;
+            const int32_t i = wgl_tile_row(e >> 5, e & 31, H);
+            if (i >= 0) v = flat[nt.bih_flat + i] + flat[nt.bhh_flat + i];
         }
     }
     packed[idx] = v;
@@ -167,56 +126,19 @@ __global__ void k_lstm_pack(const WgLstmP P, const float* __restrict__ flat, flo
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-static int lfail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
-#define LHIPCHK(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t _e = (x);                                                                        \
-        if (_e != hipSuccess) return lfail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-static int l_use_device(wg_lstm_s* l) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != l->device) LHIPCHK(hipSetDevice(l->device));
-    return 0;
-}
-
 extern "C" int wg_lstm_create(const wg_lstm_desc* d, int device, wg_lstm* out) {
-    if (!d || !out) return lfail(WG_ERR_INVALID, "wg_lstm_create: null argument");
+    if (!d || !out) return wg_fail(WG_ERR_INVALID, "wg_lstm_create: null argument");
     *out = nullptr;
-    if (d->n_in < 1 || d->hidden < 1) return lfail(WG_ERR_INVALID, "wg_lstm_create: n_in and hidden must be >= 1");
-    if (d->n_nets != 1 && d->n_nets != 2) return lfail(WG_ERR_INVALID, "wg_lstm_create: n_nets must be 1 (shared) or 2 (actor, critic)");
-    if (d->n_in > WGP_MAX_IN) return lfail(WG_ERR_UNSUPPORTED, "wg_lstm_create: n_in = " + std::to_string(d->n_in) + " > " + std::to_string(WGP_MAX_IN));
-    if (d->hidden > WGL_MAX_H) return lfail(WG_ERR_UNSUPPORTED, "wg_lstm_create: hidden = " + std::to_string(d->hidden) + " > " + std::to_string(WGL_MAX_H));
+    if (d->n_in < 1 || d->hidden < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_create: n_in and hidden must be >= 1");
+    if (d->n_nets != 1 && d->n_nets != 2) return wg_fail(WG_ERR_INVALID, "wg_lstm_create: n_nets must be 1 (shared) or 2 (actor, critic)");
+    if (d->n_in > WGP_MAX_IN) return wg_fail(WG_ERR_UNSUPPORTED, "wg_lstm_create: n_in = " + std::to_string(d->n_in) + " > " + std::to_string(WGP_MAX_IN));
+    if (d->hidden > WGL_MAX_H) return wg_fail(WG_ERR_UNSUPPORTED, "wg_lstm_create: hidden = " + std::to_string(d->hidden) + " > " + std::to_string(WGL_MAX_H));
     wg_lstm_s* l = new (std::nothrow) wg_lstm_s();
-    if (!l) return lfail(WG_ERR_NOMEM, "wg_lstm_create: out of host memory");
-    WgLstmP& P = l->P;
-    P.n_in = d->n_in; P.H = d->hidden; P.n_nets = d->n_nets;
-    P.K = P.n_in + P.H;
-    P.nks = ((P.K + 1) / 2 + 2 * WGP_GROUP - 1) / (2 * WGP_GROUP) * (2 * WGP_GROUP);
-    P.nub = (P.H + 31) / 32;
-    uint32_t flat = 0, packed = 0;
-    const uint32_t H4 = 4u * P.H;
-    for (int net = 0; net < P.n_nets; ++net) {
-        WgLstmNet& nt = P.net[net];
-        nt.wih_flat = flat; flat += H4 * P.n_in;
-        nt.whh_flat = flat; flat += H4 * P.H;
-        nt.bih_flat = flat; flat += H4;
-        nt.bhh_flat = flat; flat += H4;
-        nt.w_packed = packed; packed += 4u * P.nub * P.nks * 64;
-        nt.b_packed = packed; packed += 4u * P.nub * 32;
-    }
-    packed += WGP_GROUP * 64;                                      // slack the MFMA loop's last prefetch reads
-    P.n_flat = flat; P.n_packed = packed;
-    l->device = device;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void**)&l->packed, sizeof(float) * packed);
-    if (e == hipSuccess) e = hipMalloc((void**)&l->flat_stage, sizeof(float) * flat);
-    if (e == hipSuccess) e = hipMemset(l->packed, 0, sizeof(float) * packed);
-    if (e != hipSuccess) {
-        if (l->packed) (void)hipFree(l->packed);
-        if (l->flat_stage) (void)hipFree(l->flat_stage);
+    if (!l) return wg_fail(WG_ERR_NOMEM, "wg_lstm_create: out of host memory");
+    wgl_fill_layout(l->P, d);
+    if (int rc = wg_packed_alloc_(&l->w, device, l->P.n_flat, l->P.n_packed, "wg_lstm_create")) {
         delete l;
-        return lfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_lstm_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = l;
     return 0;
@@ -224,62 +146,54 @@ extern "C" int wg_lstm_create(const wg_lstm_desc* d, int device, wg_lstm* out) {
 
 extern "C" int wg_lstm_destroy(wg_lstm l) {
     if (!l) return 0;
-    if (hipSetDevice(l->device) == hipSuccess) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(l->packed);
-        (void)hipFree(l->flat_stage);
-    }
+    wg_packed_free_(&l->w);
     delete l;
     return 0;
 }
 
 extern "C" int wg_lstm_n_params(wg_lstm l, size_t* n) {
-    if (!l || !n) return lfail(WG_ERR_INVALID, "wg_lstm_n_params: null argument");
+    if (!l || !n) return wg_fail(WG_ERR_INVALID, "wg_lstm_n_params: null argument");
     *n = l->P.n_flat;
     return 0;
 }
 
 extern "C" int wg_lstm_geometry_(wg_lstm l, int* n_in, int* hidden, int* n_nets, int* device) {
-    if (!l) return lfail(WG_ERR_INVALID, "wg_lstm: null handle");
-    *n_in = l->P.n_in; *hidden = l->P.H; *n_nets = l->P.n_nets; *device = l->device;
+    if (!l) return wg_fail(WG_ERR_INVALID, "wg_lstm: null handle");
+    *n_in = l->P.n_in; *hidden = l->P.H; *n_nets = l->P.n_nets; *device = l->w.device;
     return 0;
 }
 
 extern "C" int wg_lstm_set_params(wg_lstm l, const float* params, size_t n, int on_device, void* stream) {
-    if (!l || !params) return lfail(WG_ERR_INVALID, "wg_lstm_set_params: null argument");
+    if (!l || !params) return wg_fail(WG_ERR_INVALID, "wg_lstm_set_params: null argument");
     if (n != l->P.n_flat)
-        return lfail(WG_ERR_INVALID, "wg_lstm_set_params: " + std::to_string(n) + " parameters given, the LSTM has " + std::to_string(l->P.n_flat));
-    if (int rc = l_use_device(l)) return rc;
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_set_params: " + std::to_string(n) + " parameters given, the LSTM has " + std::to_string(l->P.n_flat));
     hipStream_t st = (hipStream_t)stream;
-    const float* src = params;
-    if (!on_device) {
-        LHIPCHK(hipMemcpyAsync(l->flat_stage, params, sizeof(float) * n, hipMemcpyHostToDevice, st));
-        src = l->flat_stage;
-    }
-    hipLaunchKernelGGL(k_lstm_pack, dim3((l->P.n_packed + 255) / 256), dim3(256), 0, st, l->P, src, l->packed);
-    LHIPCHK(hipGetLastError());
+    const float* src;
+    if (int rc = wg_packed_source_(&l->w, params, on_device, st, &src)) return rc;
+    hipLaunchKernelGGL(k_lstm_pack, dim3((l->P.n_packed + 255) / 256), dim3(256), 0, st, l->P, src, l->w.packed);
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int wg_lstm_step(wg_lstm l, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
                             float* state_out_dev, float* h_pi_dev, float* h_vf_dev, int net_mask, void* stream) {
-    if (!l || !x_dev || !state_in_dev) return lfail(WG_ERR_INVALID, "wg_lstm_step: null argument (x_dev and state_in_dev are required)");
-    if (n_rows < 0) return lfail(WG_ERR_INVALID, "wg_lstm_step: n_rows < 0");
+    if (!l || !x_dev || !state_in_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_step: null argument (x_dev and state_in_dev are required)");
+    if (n_rows < 0) return wg_fail(WG_ERR_INVALID, "wg_lstm_step: n_rows < 0");
     const int all = l->P.n_nets == 2 ? (WG_LSTM_ACTOR | WG_LSTM_CRITIC) : WG_LSTM_ACTOR;
     if (net_mask == 0) net_mask = all;
     if (net_mask & ~all)
-        return lfail(WG_ERR_INVALID, "wg_lstm_step: net_mask = " + std::to_string(net_mask) + " names a net this LSTM does not have (n_nets = " +
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_step: net_mask = " + std::to_string(net_mask) + " names a net this LSTM does not have (n_nets = " +
                                          std::to_string(l->P.n_nets) + ")");
-    if (!(net_mask & WG_LSTM_ACTOR) && h_pi_dev) return lfail(WG_ERR_INVALID, "wg_lstm_step: h_pi_dev given, but net_mask leaves the actor's LSTM out");
+    if (!(net_mask & WG_LSTM_ACTOR) && h_pi_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_step: h_pi_dev given, but net_mask leaves the actor's LSTM out");
     if (!(net_mask & WG_LSTM_CRITIC) && h_vf_dev)
-        return lfail(WG_ERR_INVALID, "wg_lstm_step: h_vf_dev given, but net_mask leaves the critic's LSTM out (a shared LSTM has none: the critic reads h_pi)");
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_step: h_vf_dev given, but net_mask leaves the critic's LSTM out (a shared LSTM has none: the critic reads h_pi)");
     if (n_rows == 0) return 0;
-    if (int rc = l_use_device(l)) return rc;
+    if (int rc = wg_use_device(l->w.device)) return rc;
     const int net0 = (net_mask & WG_LSTM_ACTOR) ? 0 : 1, nn = net_mask == (WG_LSTM_ACTOR | WG_LSTM_CRITIC) ? 2 : 1;
-    hipLaunchKernelGGL(k_lstm, dim3((n_rows + WGP_TILE - 1) / WGP_TILE, nn), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, l->P, l->packed,
+    hipLaunchKernelGGL(k_lstm, dim3((n_rows + WGP_TILE - 1) / WGP_TILE, nn), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, l->P, l->w.packed,
                        x_dev, episode_start_dev, state_in_dev, state_out_dev, h_pi_dev, h_vf_dev, n_rows, net0);
     const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return lfail(WG_ERR_HIP, std::string("wg_lstm_step: kernel launch failed: ") + hipGetErrorString(le));
+    if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_lstm_step: kernel launch failed: ") + hipGetErrorString(le));
     return 0;
 }
 
@@ -287,12 +201,12 @@ extern "C" int wg_lstm_step(wg_lstm l, int n_rows, const float* x_dev, const uin
 extern "C" int wg_lstm_act(wg_lstm l, wg_policy p, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
                            float* state_out_dev, float* h_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
                            float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream) {
-    if (!l || !p || !h_dev) return lfail(WG_ERR_INVALID, "wg_lstm_act: null argument (l, p and h_dev are required)");
+    if (!l || !p || !h_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_act: null argument (l, p and h_dev are required)");
     if (p->P.n_in != l->P.H || p->P.n_layers[1] == 0 || p->P.n_in_vf != l->P.H)
-        return lfail(WG_ERR_INVALID, "wg_lstm_act: p must map the LSTM's hidden size (" + std::to_string(l->P.H) + ") with its critic on the same width; it maps " +
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_act: p must map the LSTM's hidden size (" + std::to_string(l->P.H) + ") with its critic on the same width; it maps " +
                                          std::to_string(p->P.n_in) + " inputs, its critic " + std::to_string(p->P.n_layers[1] ? p->P.n_in_vf : 0));
-    if (p->device != l->device) return lfail(WG_ERR_INVALID, "wg_lstm_act: lstm and policy live on different devices");
-    if (n_rows < 0) return lfail(WG_ERR_INVALID, "wg_lstm_act: n_rows < 0");
+    if (p->w.device != l->w.device) return wg_fail(WG_ERR_INVALID, "wg_lstm_act: lstm and policy live on different devices");
+    if (n_rows < 0) return wg_fail(WG_ERR_INVALID, "wg_lstm_act: n_rows < 0");
     const bool two = l->P.n_nets == 2, critic = two && value_dev;
     float* const h_pi = h_dev;
     float* const h_vf = two ? h_dev + (size_t)n_rows * l->P.H : h_dev;

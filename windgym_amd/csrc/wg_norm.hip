@@ -21,7 +21,7 @@
 #include <string>
 
 #include "../../include/windgym_hip.h"
-#include "wg_internal.h"
+#include "wg_host.h"
 
 namespace {
 
@@ -35,7 +35,6 @@ struct NormHeader {
 };
 const uint32_t NORM_MAGIC = 0x4d524e57u;      // "WNRM"
 
-int fail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
 
 // ((a + b) + (c + d)) of the four waves' partial sums of one feature
 __device__ __forceinline__ double sum4(const double (*sh)[64], const int lane) {
@@ -279,18 +278,6 @@ struct wg_norm_s {
     int scr_T = 0;
 };
 
-#define NORM_HIPCHK(x)                                                                         \
-    do {                                                                                       \
-        hipError_t _e = (x);                                                                   \
-        if (_e != hipSuccess) return fail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-static int norm_use_device(wg_norm n) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != n->device) NORM_HIPCHK(hipSetDevice(n->device));
-    return 0;
-}
-
 static size_t norm_state_doubles(const wg_norm_s* n) { return 2 * (size_t)n->d.n_obs + 1 + 3 + (size_t)n->d.n_envs; }
 
 // the fresh statistics: mean 0, var 1, count 1e-4; returns 0
@@ -306,21 +293,21 @@ static void norm_fresh(const wg_norm_s* n, double* s) {
 // the blob's payload (obs mean / var / count, ret mean / var / count, returns) -> the device, into half 0
 static int norm_upload(wg_norm n, const double* s) {
     const size_t O = n->d.n_obs, B = n->d.n_envs;
-    NORM_HIPCHK(hipMemcpy(n->stat[0], s, sizeof(double) * (2 * O + 1), hipMemcpyHostToDevice));
-    NORM_HIPCHK(hipMemcpy(n->ret, s + 2 * O + 1, sizeof(double) * (3 + B), hipMemcpyHostToDevice));      // (returns follow ret)
+    WG_HIPCHK(hipMemcpy(n->stat[0], s, sizeof(double) * (2 * O + 1), hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(n->ret, s + 2 * O + 1, sizeof(double) * (3 + B), hipMemcpyHostToDevice));      // (returns follow ret)
     n->cur = 0;
     return 0;
 }
 
 extern "C" int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out) {
-    if (!d || !out) return fail(WG_ERR_INVALID, "wg_norm_create: null argument");
+    if (!d || !out) return wg_fail(WG_ERR_INVALID, "wg_norm_create: null argument");
     *out = nullptr;
-    if (d->n_obs < 1 || d->n_envs < 1) return fail(WG_ERR_INVALID, "wg_norm_create: n_obs and n_envs must be >= 1");
-    if (!(d->clip_obs > 0.0f) || !(d->clip_reward > 0.0f)) return fail(WG_ERR_INVALID, "wg_norm_create: clip_obs and clip_reward must be > 0");
-    if (!(d->gamma >= 0.0 && d->gamma <= 1.0)) return fail(WG_ERR_INVALID, "wg_norm_create: gamma must lie in [0, 1]");
-    if (!(d->epsilon > 0.0) || !(d->epsilon < 1.0)) return fail(WG_ERR_INVALID, "wg_norm_create: epsilon must lie in (0, 1)");
+    if (d->n_obs < 1 || d->n_envs < 1) return wg_fail(WG_ERR_INVALID, "wg_norm_create: n_obs and n_envs must be >= 1");
+    if (!(d->clip_obs > 0.0f) || !(d->clip_reward > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_norm_create: clip_obs and clip_reward must be > 0");
+    if (!(d->gamma >= 0.0 && d->gamma <= 1.0)) return wg_fail(WG_ERR_INVALID, "wg_norm_create: gamma must lie in [0, 1]");
+    if (!(d->epsilon > 0.0) || !(d->epsilon < 1.0)) return wg_fail(WG_ERR_INVALID, "wg_norm_create: epsilon must lie in (0, 1)");
     wg_norm_s* n = new (std::nothrow) wg_norm_s;
-    if (!n) return fail(WG_ERR_NOMEM, "wg_norm_create: out of host memory");
+    if (!n) return wg_fail(WG_ERR_NOMEM, "wg_norm_create: out of host memory");
     n->d = *d;
     n->d.norm_obs = d->norm_obs != 0; n->d.norm_reward = d->norm_reward != 0;
     n->device = device;
@@ -332,7 +319,7 @@ extern "C" int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out) {
     if (e == hipSuccess) e = hipMemset(n->mem, 0, sizeof(double) * words);
     if (e != hipSuccess) {
         wg_norm_destroy(n);
-        return fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_norm_create: ") + hipGetErrorString(e));
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_norm_create: ") + hipGetErrorString(e));
     }
     double* m = n->mem;
     n->stat[0] = m; m += 2 * O + 1;
@@ -342,7 +329,7 @@ extern "C" int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out) {
     n->pmean = m; m += C * O;
     n->pm2 = m;
     double* s = new (std::nothrow) double[norm_state_doubles(n)];
-    if (!s) { wg_norm_destroy(n); return fail(WG_ERR_NOMEM, "wg_norm_create: out of host memory"); }
+    if (!s) { wg_norm_destroy(n); return wg_fail(WG_ERR_NOMEM, "wg_norm_create: out of host memory"); }
     norm_fresh(n, s);
     const int rc = norm_upload(n, s);
     delete[] s;
@@ -366,47 +353,47 @@ extern "C" int wg_norm_destroy(wg_norm n) {
 }
 
 extern "C" int wg_norm_geometry_(wg_norm n, int* n_obs, int* n_envs, int* device) {
-    if (!n) return fail(WG_ERR_INVALID, "null wg_norm");
+    if (!n) return wg_fail(WG_ERR_INVALID, "null wg_norm");
     *n_obs = n->d.n_obs; *n_envs = n->d.n_envs; *device = n->device;
     return 0;
 }
 
 extern "C" int wg_norm_get_state(wg_norm n, void* host, size_t* size) {
-    if (!n || !size) return fail(WG_ERR_INVALID, "wg_norm_get_state: null argument");
+    if (!n || !size) return wg_fail(WG_ERR_INVALID, "wg_norm_get_state: null argument");
     const size_t O = n->d.n_obs, B = n->d.n_envs;
     const size_t total = sizeof(NormHeader) + sizeof(double) * norm_state_doubles(n);
     if (!host) {
         *size = total;
         return 0;
     }
-    if (*size < total) return fail(WG_ERR_INVALID, "wg_norm_get_state: state buffer too small");
-    if (int rc = norm_use_device(n)) return rc;
-    NORM_HIPCHK(hipDeviceSynchronize());
+    if (*size < total) return wg_fail(WG_ERR_INVALID, "wg_norm_get_state: state buffer too small");
+    if (int rc = wg_use_device(n->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
     const NormHeader hd = {NORM_MAGIC, n->d.n_obs, n->d.n_envs, 0};
     memcpy(host, &hd, sizeof(hd));
     char* at = (char*)host + sizeof(hd);
-    NORM_HIPCHK(hipMemcpy(at, n->stat[n->cur], sizeof(double) * (2 * O + 1), hipMemcpyDeviceToHost));
-    NORM_HIPCHK(hipMemcpy(at + sizeof(double) * (2 * O + 1), n->ret, sizeof(double) * (3 + B), hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy(at, n->stat[n->cur], sizeof(double) * (2 * O + 1), hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy(at + sizeof(double) * (2 * O + 1), n->ret, sizeof(double) * (3 + B), hipMemcpyDeviceToHost));
     *size = total;
     return 0;
 }
 
 extern "C" int wg_norm_set_state(wg_norm n, const void* host, size_t size) {
-    if (!n || !host) return fail(WG_ERR_INVALID, "wg_norm_set_state: null argument");
-    if (size < sizeof(NormHeader)) return fail(WG_ERR_INVALID, "wg_norm_set_state: state blob too small");
+    if (!n || !host) return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: null argument");
+    if (size < sizeof(NormHeader)) return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: state blob too small");
     NormHeader got;
     memcpy(&got, host, sizeof(got));
-    if (got.magic != NORM_MAGIC) return fail(WG_ERR_INVALID, "wg_norm_set_state: not a wg_norm state blob");
+    if (got.magic != NORM_MAGIC) return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: not a wg_norm state blob");
     if (got.O != n->d.n_obs || got.B != n->d.n_envs || size != sizeof(NormHeader) + sizeof(double) * norm_state_doubles(n))
-        return fail(WG_ERR_INVALID, "wg_norm_set_state: the blob holds statistics of " + std::to_string(got.O) + " observation entries x " +
+        return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: the blob holds statistics of " + std::to_string(got.O) + " observation entries x " +
                                         std::to_string(got.B) + " envs, this wg_norm has " + std::to_string(n->d.n_obs) + " x " +
                                         std::to_string(n->d.n_envs));
-    if (int rc = norm_use_device(n)) return rc;
-    NORM_HIPCHK(hipDeviceSynchronize());
+    if (int rc = wg_use_device(n->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
     // (the payload is copied out first: a blob inside a Python bytes object need not be aligned for doubles)
     const size_t nd = norm_state_doubles(n);
     double* s = new (std::nothrow) double[nd];
-    if (!s) return fail(WG_ERR_NOMEM, "wg_norm_set_state: out of host memory");
+    if (!s) return wg_fail(WG_ERR_NOMEM, "wg_norm_set_state: out of host memory");
     memcpy(s, (const char*)host + sizeof(NormHeader), sizeof(double) * nd);
     const int rc = norm_upload(n, s);
     delete[] s;
@@ -414,38 +401,38 @@ extern "C" int wg_norm_set_state(wg_norm n, const void* host, size_t size) {
 }
 
 extern "C" int wg_norm_set_training(wg_norm n, int training) {
-    if (!n) return fail(WG_ERR_INVALID, "wg_norm_set_training: null wg_norm");
+    if (!n) return wg_fail(WG_ERR_INVALID, "wg_norm_set_training: null wg_norm");
     n->training = training != 0;
     return 0;
 }
 
 extern "C" int wg_norm_reset_returns(wg_norm n, const uint8_t* env_mask_host, void* stream) {
-    if (!n) return fail(WG_ERR_INVALID, "wg_norm_reset_returns: null wg_norm");
-    if (int rc = norm_use_device(n)) return rc;
+    if (!n) return wg_fail(WG_ERR_INVALID, "wg_norm_reset_returns: null wg_norm");
+    if (int rc = wg_use_device(n->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int B = n->d.n_envs;
     if (!env_mask_host) {
-        NORM_HIPCHK(hipMemsetAsync(n->returns, 0, sizeof(double) * (size_t)B, st));
+        WG_HIPCHK(hipMemsetAsync(n->returns, 0, sizeof(double) * (size_t)B, st));
         return 0;
     }
-    NORM_HIPCHK(hipMemcpyAsync(n->mask, env_mask_host, (size_t)B, hipMemcpyHostToDevice, st));
+    WG_HIPCHK(hipMemcpyAsync(n->mask, env_mask_host, (size_t)B, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_ret_zero, dim3((B + 255) / 256), dim3(256), 0, st, B, n->mask, n->returns);
-    NORM_HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int wg_norm_obs(wg_norm n, int n_rows, const float* obs_dev, float* out_dev, const float* extra_dev, float* extra_out_dev,
                            void* stream) {
-    if (!n || !obs_dev || !out_dev) return fail(WG_ERR_INVALID, "wg_norm_obs: null argument (obs_dev and out_dev are required)");
+    if (!n || !obs_dev || !out_dev) return wg_fail(WG_ERR_INVALID, "wg_norm_obs: null argument (obs_dev and out_dev are required)");
     if ((extra_dev == nullptr) != (extra_out_dev == nullptr))
-        return fail(WG_ERR_INVALID, "wg_norm_obs: extra_dev and extra_out_dev go together");
-    if (n_rows < 0) return fail(WG_ERR_INVALID, "wg_norm_obs: n_rows < 0");
+        return wg_fail(WG_ERR_INVALID, "wg_norm_obs: extra_dev and extra_out_dev go together");
+    if (n_rows < 0) return wg_fail(WG_ERR_INVALID, "wg_norm_obs: n_rows < 0");
     const bool update = n->training && n->d.norm_obs;
     if (update && n_rows > n->d.n_envs)
-        return fail(WG_ERR_INVALID, "wg_norm_obs: an update takes at most n_envs = " + std::to_string(n->d.n_envs) + " rows, got " +
+        return wg_fail(WG_ERR_INVALID, "wg_norm_obs: an update takes at most n_envs = " + std::to_string(n->d.n_envs) + " rows, got " +
                                         std::to_string(n_rows));
     if (n_rows == 0) return 0;
-    if (int rc = norm_use_device(n)) return rc;
+    if (int rc = wg_use_device(n->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int O = n->d.n_obs;
     const dim3 block(64, WGN_Y), grid((n_rows + WGN_ROWS - 1) / WGN_ROWS, (O + 63) / 64);
@@ -458,24 +445,24 @@ extern "C" int wg_norm_obs(wg_norm n, int n_rows, const float* obs_dev, float* o
     p.clip = (double)n->d.clip_obs; p.eps = n->d.epsilon;
     p.obs = obs_dev; p.extra = extra_dev; p.out = out_dev; p.eout = extra_out_dev;
     hipLaunchKernelGGL(k_norm_apply, grid, block, 0, st, p);
-    NORM_HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     if (update) n->cur ^= 1;
     return 0;
 }
 
 extern "C" int wg_norm_reward(wg_norm n, int T, const float* reward_dev, const uint8_t* truncated_dev, float* out_dev, void* stream) {
     if (!n || !reward_dev || !truncated_dev || !out_dev)
-        return fail(WG_ERR_INVALID, "wg_norm_reward: null argument (reward_dev, truncated_dev and out_dev are required)");
-    if (T < 0) return fail(WG_ERR_INVALID, "wg_norm_reward: T < 0");
+        return wg_fail(WG_ERR_INVALID, "wg_norm_reward: null argument (reward_dev, truncated_dev and out_dev are required)");
+    if (T < 0) return wg_fail(WG_ERR_INVALID, "wg_norm_reward: T < 0");
     if (T == 0) return 0;
-    if (int rc = norm_use_device(n)) return rc;
+    if (int rc = wg_use_device(n->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int B = n->d.n_envs;
     if (n->training && T > n->scr_T) {          // grown here, before anything is enqueued (hipFree waits for what still reads the old one)
-        if (n->scr) NORM_HIPCHK(hipFree(n->scr));
+        if (n->scr) WG_HIPCHK(hipFree(n->scr));
         n->scr = nullptr; n->scr_T = 0;
         const hipError_t e = hipMalloc((void**)&n->scr, sizeof(double) * ((size_t)T * B + 3 * (size_t)T));
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_norm_reward: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_norm_reward: ") + hipGetErrorString(e));
         n->scr_T = T;
     }
     double* const mom = n->scr ? n->scr + (size_t)n->scr_T * B : nullptr;
@@ -489,6 +476,6 @@ extern "C" int wg_norm_reward(wg_norm n, int T, const float* reward_dev, const u
     const long long total = (long long)T * B;
     hipLaunchKernelGGL(k_ret_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, B, n->d.norm_reward,
                        n->training ? var_t : n->ret + 1, n->training ? 1 : 0, (double)n->d.clip_reward, n->d.epsilon, reward_dev, out_dev);
-    NORM_HIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }

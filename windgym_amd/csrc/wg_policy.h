@@ -9,11 +9,9 @@
 //     actor hidden layers in order, each W [M][K] row-major then b [M]; actor head W [n_out][K], b [n_out];
 //     critic hidden layers, critic head W [1][K], b [1] (only with a critic); log_std [n_out] (only with has_log_std).
 //
-// PACKED copy (what the kernel reads; owned by the policy object, written by k_policy_pack): per layer
-//     Wp[tile][ks][lane]  = W[32 tile + (lane & 31)][2 ks + (lane >> 5)]   (0 outside M x K; ks < nks, 16 k-steps at a time)
-//         — the A operand of v_mfma_f32_32x32x2_f32 for output tile `tile`, k-step `ks`: one coalesced 256-byte load;
-//     bp[i], i < 32 n_tiles = b[i]                                              (0 from M on),
-// then log_std [n_out] and one k-group of zeros.  Padding lives here, never in the caller's tensors.
+// PACKED copy (what the kernel reads; owned by the policy object, written by k_policy_pack): per layer one weight block and one
+// bias block of wg_tile.h (row(tile, j) = neuron 32 tile + j, ceil(M / 32) tiles), then log_std [n_out] and the slack.  Padding
+// lives here, never in the caller's tensors.
 //
 // NOISE of a stochastic call (restated in oracle/policy_oracle.py: policy_noise): Philox4x32-10 with
 //     key     = (seed lo, seed hi)
@@ -24,10 +22,9 @@
 #define WG_POLICY_H
 #include <stdint.h>
 
-#define WGP_TILE 32          // rows of a workgroup's batch tile = columns of one MFMA; output neurons per MFMA tile
-#define WGP_KC 256           // inputs staged per chunk of the first layer = widest hidden layer
-#define WGP_WAVES 4          // waves per workgroup; wave w computes output tiles w and w + 4
-#define WGP_GROUP 8          // k-steps per software-pipeline group of the MFMA loop
+#include "../../include/windgym_hip.h"
+#include "wg_tile.h"         // the tile constants WGP_TILE, WGP_KC, WGP_WAVES, WGP_GROUP and the packed layout
+
 #define WGP_MAX_LAYERS 5     // WG_POLICY_MAX_HIDDEN + the head
 #define WGP_MAX_IN 2048
 #define WGP_MAX_OUT 128
@@ -37,7 +34,7 @@
 
 struct WgPolicyLayer {
     int32_t K, M;              // inputs, outputs
-    int32_t nks, ntiles;       // k-steps = ceil(K / 2) rounded up to PAIRS of groups of WGP_GROUP, output tiles = ceil(M / 32)
+    int32_t nks, ntiles;       // wg_tile_nks(K), wg_tile_count(M)
     uint32_t w_flat, b_flat;   // offsets (floats) into the flat vector
     uint32_t w_packed, b_packed;
 };
@@ -60,11 +57,38 @@ struct WgPolicySlots {
     int32_t n_rows[WGP_MAX_SLOTS], net[WGP_MAX_SLOTS], end[WGP_MAX_SLOTS];
 };
 
+// Both layouts of a (validated) architecture: the walk of the flat order above, a block pair per layer in the packed vector
+inline void wgp_fill_layout(WgPolicyP& P, const wg_policy_desc* d, int32_t n_in_vf) {
+    const int nh[2] = {d->n_hidden_pi, d->n_hidden_vf};
+    const int32_t* hid[2] = {d->hidden_pi, d->hidden_vf};
+    P.n_in = d->n_in; P.n_out = d->n_out; P.activation = d->activation; P.has_log_std = d->has_log_std != 0;
+    P.n_in_vf = n_in_vf;
+    uint32_t flat = 0, packed = 0;
+    for (int net = 0; net < 2; ++net) {
+        if (nh[net] < 0) { P.n_layers[net] = 0; continue; }        // (critic only: n_hidden_vf < 0 = none)
+        P.n_layers[net] = nh[net] + 1;
+        int K = net == 0 ? d->n_in : n_in_vf;
+        for (int l = 0; l <= nh[net]; ++l) {
+            WgPolicyLayer& ly = P.layer[net][l];
+            ly.K = K;
+            ly.M = l < nh[net] ? hid[net][l] : (net == 0 ? d->n_out : 1);
+            ly.nks = wg_tile_nks(ly.K);
+            ly.ntiles = wg_tile_count(ly.M);
+            ly.w_flat = flat; flat += (uint32_t)ly.M * ly.K;
+            ly.b_flat = flat; flat += (uint32_t)ly.M;
+            ly.w_packed = packed; packed += wg_tile_wsize(ly.ntiles, ly.nks);
+            ly.b_packed = packed; packed += wg_tile_bsize(ly.ntiles);
+            K = ly.M;
+        }
+    }
+    P.log_std_flat = flat; P.log_std_packed = packed;
+    if (P.has_log_std) { flat += d->n_out; packed += d->n_out; }
+    P.n_flat = flat; P.n_packed = packed + WGP_SLACK;
+}
+
 struct wg_policy_s {
     WgPolicyP P;
-    int device;
-    float* packed;             // [P.n_packed]
-    float* flat_stage;         // [P.n_flat] staging copy for host-pointer wg_policy_set_params
+    WgPacked w;                // [P.n_flat] / [P.n_packed]
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -3,10 +3,10 @@
 // k_policy_pack builds the kernel's weight layout, and the wg_policy_* entries of include/windgym_hip.h wrap them.
 //
 // k_policy: one workgroup of 4 waves owns 32 observation rows of ONE net (a launch is up to three slots of (net, rows)).  A layer is
-// D[neuron][row] = sum_k W[neuron][k] X[k][row] on v_mfma_f32_32x32x2_f32 — an exact k-ordered f32 fmaf chain, so a row's
+// D[neuron][row] = sum_k W[neuron][k] X[k][row] on the tile core of wg_tile.h — an exact k-ordered f32 fmaf chain, so a row's
 // outputs depend on nothing but that row and the weights (bitwise: no atomics, no cross-row reduction, fixed order).
-// X lives in LDS as [k][32 rows] (B operand: one conflict-free ds_read per k-step), the weights come packed from L2 as the A
-// operand (wg_policy.h), the 32 x 32 result tile of wave w (tiles w and w + 4) gets bias (accumulator init) and activation
+// X lives in LDS as [k][32 rows], the weights come packed from L2 as the A operand,
+// the 32 x 32 result tile of wave w (tiles w and w + 4) gets bias (accumulator init) and activation
 // and goes to the other LDS buffer: hidden activations never leave the CU.  The first layer streams the observations
 // through LDS in chunks of 256 inputs (n_in <= 2048).  The head's tile is the action mean / the value.
 #include <hip/hip_runtime.h>
@@ -17,9 +17,7 @@
 
 #include "../../include/windgym_hip.h"
 #include "wg_policy.h"
-#include "wg_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "wg_host.h"
 
 // Philox4x32-10 (the generator of wg_device.h's sensor noise) -> the first two output words
 __device__ inline void wgp_philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t& o0,
@@ -67,67 +65,26 @@ __device__ __forceinline__ void wgp_tile(const WgPolicyP& P, const float* __rest
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int ot = wave + WGP_WAVES * t;
-            if (ot < ly.ntiles) {
-                const float* bp = packed + ly.b_packed + ot * 32 + 4 * h;
-#pragma unroll
-                for (int g = 0; g < 16; ++g) acc[t][g] = bp[(g & 3) + 8 * (g >> 2)];
-            }
+            if (ot < ly.ntiles) wg_tile_bias(acc[t], packed + ly.b_packed + ot * 32, h);
         }
         const int nchunk = l == 0 ? (ly.K + WGP_KC - 1) / WGP_KC : 1;
         for (int c = 0; c < nchunk; ++c) {
             const int k0 = c * WGP_KC;
-            const int kc = min(WGP_KC, ly.K - k0), kcp = (kc + 4 * WGP_GROUP - 1) & ~(4 * WGP_GROUP - 1);
+            const int kc = min(WGP_KC, ly.K - k0), kcp = wg_tile_kpad(kc);
             if (l == 0) {
-                // observations -> LDS [k][row]: a wave covers 32 rows x 2 inputs per pass (conflict-free stores; the 32 rows'
-                // cache lines are re-used from L1 by the following passes).  Rows past n_rows and the pad up to whole k-groups read as 0.
-                __syncthreads();
+                // observations -> LDS (the 32 rows' cache lines are re-used from L1 by the following passes); rows past n_rows read as 0
                 const int row = row0 + r;
                 const float* orow = obs + (size_t)row * ly.K + k0;      // (a net's row stride is its first layer's K)
-                for (int k = tid >> 5; k < kcp; k += WGP_WAVES * 2)
-                    lds[0][k * WGP_TILE + r] = (row < n_rows && k < kc) ? orow[k] : 0.0f;
-                __syncthreads();
+                wg_tile_stage(lds[0], tid, kcp, [&](const int k) { return (row < n_rows && k < kc) ? orow[k] : 0.0f; });
             }
             const float* xb = lds[cur] + h * WGP_TILE + r;
-            const int nks = kcp >> 1;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int ot = wave + WGP_WAVES * t;
-                if (ot < ly.ntiles) {
-                    // k-steps in groups of WGP_GROUP: the A operands of group g + 1 (global loads, L2 latency) are requested
-                    // before the MFMAs of group g issue; the B operands are LDS reads of the group itself
-                    const float* wp = packed + ly.w_packed + ((size_t)ot * ly.nks + (k0 >> 1)) * 64 + lane;
-                    // (no bounds tests: a tile's k-steps are padded to whole groups with zero weights, the input rows behind them
-                    // hold zeros (k-steps come in PAIRS of groups), and the packed vector ends in one group of slack for the last prefetch;
-                    // the roles of a0 / a1 are fixed, so that no register copy waits for the prefetch)
-                    float a0[WGP_GROUP], a1[WGP_GROUP], b[WGP_GROUP];
-#pragma unroll
-                    for (int i = 0; i < WGP_GROUP; ++i) a0[i] = wp[i * 64];
-                    for (int ks0 = 0; ks0 < nks; ks0 += 2 * WGP_GROUP) {
-#pragma unroll
-                        for (int i = 0; i < WGP_GROUP; ++i) {
-                            a1[i] = wp[(size_t)(ks0 + WGP_GROUP + i) * 64];
-                            b[i] = xb[(ks0 + i) * 2 * WGP_TILE];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int i = 0; i < WGP_GROUP; ++i)
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b[i], acc[t], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int i = 0; i < WGP_GROUP; ++i) {
-                            a0[i] = wp[(size_t)(ks0 + 2 * WGP_GROUP + i) * 64];
-                            b[i] = xb[(ks0 + WGP_GROUP + i) * 2 * WGP_TILE];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int i = 0; i < WGP_GROUP; ++i)
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b[i], acc[t], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
+                if (ot < ly.ntiles)
+                    wg_tile_gemm(acc[t], packed + ly.w_packed + ((size_t)ot * ly.nks + (k0 >> 1)) * 64 + lane, xb, kcp >> 1);
             }
         }
-        // D: lane = (row r, half h), register g = neuron 32 ot + (g & 3) + 8 (g >> 2) + 4 h
         float* dst = lds[cur ^ 1];
         const bool head = l == L - 1;
 #pragma unroll
@@ -138,7 +95,7 @@ __device__ __forceinline__ void wgp_tile(const WgPolicyP& P, const float* __rest
                 for (int g = 0; g < 16; ++g) {
                     float v = acc[t][g];
                     if (!head) v = P.activation == WG_ACTV_RELU ? fmaxf(v, 0.0f) : tanhf(v);
-                    dst[(ot * 32 + (g & 3) + 8 * (g >> 2) + 4 * h) * WGP_TILE + r] = v;
+                    dst[(ot * 32 + wg_tile_drow(g, h)) * WGP_TILE + r] = v;
                 }
             }
         }
@@ -214,12 +171,11 @@ __device__ __forceinline__ void wgp_pack(const WgPolicyP& P, const float* __rest
     for (int net = 0; net < 2; ++net)
         for (int l = 0; l < P.n_layers[net]; ++l) {
             const WgPolicyLayer ly = P.layer[net][l];
-            const uint32_t wsize = (uint32_t)ly.ntiles * ly.nks * 64, bsize = (uint32_t)ly.ntiles * 32;
-            if (idx >= ly.w_packed && idx < ly.w_packed + wsize) {
-                const uint32_t e = idx - ly.w_packed, lane = e & 63, ks = (e >> 6) % ly.nks, ot = (e >> 6) / ly.nks;
-                const uint32_t i = ot * 32 + (lane & 31), k = 2 * ks + (lane >> 5);
-                if (i < (uint32_t)ly.M && k < (uint32_t)ly.K) v = flat[ly.w_flat + (size_t)i * ly.K + k];
-            } else if (idx >= ly.b_packed && idx < ly.b_packed + bsize) {
+            if (idx >= ly.w_packed && idx < ly.w_packed + wg_tile_wsize(ly.ntiles, ly.nks)) {
+                const WgTileElem e = wg_tile_decode(idx - ly.w_packed, ly.nks);
+                const uint32_t i = e.tile * 32 + e.j;
+                if (i < (uint32_t)ly.M && e.k < (uint32_t)ly.K) v = flat[ly.w_flat + (size_t)i * ly.K + e.k];
+            } else if (idx >= ly.b_packed && idx < ly.b_packed + wg_tile_bsize(ly.ntiles)) {
                 const uint32_t i = idx - ly.b_packed;
                 if (i < (uint32_t)ly.M) v = flat[ly.b_flat + i];
             }
@@ -240,119 +196,97 @@ __global__ void k_policy_pack_pop(const WgPolicyP P, const WgPopMember* __restri
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-static int pfail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
-#define PHIPCHK(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t _e = (x);                                                                        \
-        if (_e != hipSuccess) return pfail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-    } while (0)
+// A handle's device copies (wg_tile.h: WgPacked): the zeroed packed vector and the staging copy, on `device`
+extern "C" int wg_packed_alloc_(WgPacked* w, int device, uint32_t n_flat, uint32_t n_packed, const char* who) {
+    *w = WgPacked{device, nullptr, nullptr, n_flat, n_packed};
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void**)&w->packed, sizeof(float) * n_packed);
+    if (e == hipSuccess) e = hipMalloc((void**)&w->flat_stage, sizeof(float) * n_flat);
+    if (e == hipSuccess) e = hipMemset(w->packed, 0, sizeof(float) * n_packed);
+    if (e == hipSuccess) return 0;
+    if (w->packed) (void)hipFree(w->packed);
+    if (w->flat_stage) (void)hipFree(w->flat_stage);
+    return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
 
-static int p_use_device(wg_policy_s* p) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != p->device) PHIPCHK(hipSetDevice(p->device));
+extern "C" void wg_packed_free_(WgPacked* w) {
+    if (hipSetDevice(w->device) != hipSuccess) return;
+    (void)hipDeviceSynchronize();
+    (void)hipFree(w->packed);
+    (void)hipFree(w->flat_stage);
+}
+
+// what the pack kernel of a set_params reads: a device pointer itself, a host pointer's copy in the stage (in stream order)
+extern "C" int wg_packed_source_(WgPacked* w, const float* params, int on_device, hipStream_t st, const float** src) {
+    if (int rc = wg_use_device(w->device)) return rc;
+    *src = params;
+    if (on_device) return 0;
+    WG_HIPCHK(hipMemcpyAsync(w->flat_stage, params, sizeof(float) * w->n_flat, hipMemcpyHostToDevice, st));
+    *src = w->flat_stage;
     return 0;
 }
 
 extern "C" int wg_policy_create_vf(const wg_policy_desc* d, int32_t n_in_vf, int device, wg_policy* out) {
-    if (!d || !out) return pfail(WG_ERR_INVALID, "wg_policy_create: null argument");
+    if (!d || !out) return wg_fail(WG_ERR_INVALID, "wg_policy_create: null argument");
     *out = nullptr;
-    if (d->n_in < 1 || d->n_out < 1) return pfail(WG_ERR_INVALID, "wg_policy_create: n_in and n_out must be >= 1");
-    if (d->n_in > WGP_MAX_IN) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_in = " + std::to_string(d->n_in) + " > " + std::to_string(WGP_MAX_IN));
-    if (d->n_out > WGP_MAX_OUT) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_out = " + std::to_string(d->n_out) + " > " + std::to_string(WGP_MAX_OUT));
-    if (d->activation != WG_ACTV_TANH && d->activation != WG_ACTV_RELU) return pfail(WG_ERR_INVALID, "wg_policy_create: unknown activation");
-    if (d->n_hidden_pi < 0) return pfail(WG_ERR_INVALID, "wg_policy_create: n_hidden_pi < 0");
+    if (d->n_in < 1 || d->n_out < 1) return wg_fail(WG_ERR_INVALID, "wg_policy_create: n_in and n_out must be >= 1");
+    if (d->n_in > WGP_MAX_IN) return wg_fail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_in = " + std::to_string(d->n_in) + " > " + std::to_string(WGP_MAX_IN));
+    if (d->n_out > WGP_MAX_OUT) return wg_fail(WG_ERR_UNSUPPORTED, "wg_policy_create: n_out = " + std::to_string(d->n_out) + " > " + std::to_string(WGP_MAX_OUT));
+    if (d->activation != WG_ACTV_TANH && d->activation != WG_ACTV_RELU) return wg_fail(WG_ERR_INVALID, "wg_policy_create: unknown activation");
+    if (d->n_hidden_pi < 0) return wg_fail(WG_ERR_INVALID, "wg_policy_create: n_hidden_pi < 0");
     if (d->n_hidden_vf < 0 && n_in_vf != d->n_in)
-        return pfail(WG_ERR_INVALID, "wg_policy_create_vf: n_in_vf is the input width of the critic, and this policy has none (n_hidden_vf < 0)");
-    if (n_in_vf < 1) return pfail(WG_ERR_INVALID, "wg_policy_create_vf: n_in_vf must be >= 1");
-    if (n_in_vf > WGP_MAX_IN) return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create_vf: n_in_vf = " + std::to_string(n_in_vf) + " > " + std::to_string(WGP_MAX_IN));
+        return wg_fail(WG_ERR_INVALID, "wg_policy_create_vf: n_in_vf is the input width of the critic, and this policy has none (n_hidden_vf < 0)");
+    if (n_in_vf < 1) return wg_fail(WG_ERR_INVALID, "wg_policy_create_vf: n_in_vf must be >= 1");
+    if (n_in_vf > WGP_MAX_IN) return wg_fail(WG_ERR_UNSUPPORTED, "wg_policy_create_vf: n_in_vf = " + std::to_string(n_in_vf) + " > " + std::to_string(WGP_MAX_IN));
     const int nh[2] = {d->n_hidden_pi, d->n_hidden_vf};
     const int32_t* hid[2] = {d->hidden_pi, d->hidden_vf};
     for (int net = 0; net < 2; ++net) {
         if (nh[net] > WG_POLICY_MAX_HIDDEN)
-            return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: " + std::to_string(nh[net]) + " hidden layers > " + std::to_string(WG_POLICY_MAX_HIDDEN));
+            return wg_fail(WG_ERR_UNSUPPORTED, "wg_policy_create: " + std::to_string(nh[net]) + " hidden layers > " + std::to_string(WG_POLICY_MAX_HIDDEN));
         for (int l = 0; l < nh[net]; ++l) {
-            if (hid[net][l] < 1) return pfail(WG_ERR_INVALID, "wg_policy_create: hidden width < 1");
+            if (hid[net][l] < 1) return wg_fail(WG_ERR_INVALID, "wg_policy_create: hidden width < 1");
             if (hid[net][l] > WGP_MAX_WIDTH)
-                return pfail(WG_ERR_UNSUPPORTED, "wg_policy_create: hidden width " + std::to_string(hid[net][l]) + " > " + std::to_string(WGP_MAX_WIDTH));
+                return wg_fail(WG_ERR_UNSUPPORTED, "wg_policy_create: hidden width " + std::to_string(hid[net][l]) + " > " + std::to_string(WGP_MAX_WIDTH));
         }
     }
     wg_policy_s* p = new (std::nothrow) wg_policy_s();
-    if (!p) return pfail(WG_ERR_NOMEM, "wg_policy_create: out of host memory");
-    WgPolicyP& P = p->P;
-    P.n_in = d->n_in; P.n_out = d->n_out; P.activation = d->activation; P.has_log_std = d->has_log_std != 0;
-    P.n_in_vf = n_in_vf;
-    uint32_t flat = 0, packed = 0;
-    for (int net = 0; net < 2; ++net) {
-        if (nh[net] < 0) { P.n_layers[net] = 0; continue; }        // (critic only: n_hidden_vf < 0 = none)
-        P.n_layers[net] = nh[net] + 1;
-        int K = net == 0 ? d->n_in : n_in_vf;
-        for (int l = 0; l <= nh[net]; ++l) {
-            WgPolicyLayer& ly = P.layer[net][l];
-            ly.K = K;
-            ly.M = l < nh[net] ? hid[net][l] : (net == 0 ? d->n_out : 1);
-            ly.nks = ((ly.K + 1) / 2 + 2 * WGP_GROUP - 1) / (2 * WGP_GROUP) * (2 * WGP_GROUP);
-            ly.ntiles = (ly.M + 31) / 32;
-            ly.w_flat = flat; flat += (uint32_t)ly.M * ly.K;
-            ly.b_flat = flat; flat += (uint32_t)ly.M;
-            ly.w_packed = packed; packed += (uint32_t)ly.ntiles * ly.nks * 64;
-            ly.b_packed = packed; packed += (uint32_t)ly.ntiles * 32;
-            K = ly.M;
-        }
-    }
-    P.log_std_flat = flat; P.log_std_packed = packed;
-    if (P.has_log_std) { flat += d->n_out; packed += d->n_out; }
-    packed += WGP_GROUP * 64;                                      // slack the MFMA loop's last prefetch reads
-    P.n_flat = flat; P.n_packed = packed;
-    p->device = device;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->packed, sizeof(float) * packed);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->flat_stage, sizeof(float) * flat);
-    if (e == hipSuccess) e = hipMemset(p->packed, 0, sizeof(float) * packed);
-    if (e != hipSuccess) {
-        if (p->packed) (void)hipFree(p->packed);
-        if (p->flat_stage) (void)hipFree(p->flat_stage);
+    if (!p) return wg_fail(WG_ERR_NOMEM, "wg_policy_create: out of host memory");
+    wgp_fill_layout(p->P, d, n_in_vf);
+    if (int rc = wg_packed_alloc_(&p->w, device, p->P.n_flat, p->P.n_packed, "wg_policy_create")) {
         delete p;
-        return pfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_policy_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = p;
     return 0;
 }
 
 extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* out) {
-    if (!d || !out) return pfail(WG_ERR_INVALID, "wg_policy_create: null argument");
+    if (!d || !out) return wg_fail(WG_ERR_INVALID, "wg_policy_create: null argument");
     return wg_policy_create_vf(d, d->n_in, device, out);
 }
 
 extern "C" int wg_policy_destroy(wg_policy p) {
     if (!p) return 0;
-    if (hipSetDevice(p->device) == hipSuccess) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(p->packed);
-        (void)hipFree(p->flat_stage);
-    }
+    wg_packed_free_(&p->w);
     delete p;
     return 0;
 }
 
 extern "C" int wg_policy_n_params(wg_policy p, size_t* n) {
-    if (!p || !n) return pfail(WG_ERR_INVALID, "wg_policy_n_params: null argument");
+    if (!p || !n) return wg_fail(WG_ERR_INVALID, "wg_policy_n_params: null argument");
     *n = p->P.n_flat;
     return 0;
 }
 
 extern "C" int wg_policy_set_params(wg_policy p, const float* params, size_t n, int on_device, void* stream) {
-    if (!p || !params) return pfail(WG_ERR_INVALID, "wg_policy_set_params: null argument");
+    if (!p || !params) return wg_fail(WG_ERR_INVALID, "wg_policy_set_params: null argument");
     if (n != p->P.n_flat)
-        return pfail(WG_ERR_INVALID, "wg_policy_set_params: " + std::to_string(n) + " parameters given, the policy has " + std::to_string(p->P.n_flat));
-    if (int rc = p_use_device(p)) return rc;
+        return wg_fail(WG_ERR_INVALID, "wg_policy_set_params: " + std::to_string(n) + " parameters given, the policy has " + std::to_string(p->P.n_flat));
     hipStream_t st = (hipStream_t)stream;
-    const float* src = params;
-    if (!on_device) {
-        PHIPCHK(hipMemcpyAsync(p->flat_stage, params, sizeof(float) * n, hipMemcpyHostToDevice, st));
-        src = p->flat_stage;
-    }
-    hipLaunchKernelGGL(k_policy_pack, dim3((p->P.n_packed + 255) / 256), dim3(256), 0, st, p->P, src, p->packed);
-    PHIPCHK(hipGetLastError());
+    const float* src;
+    if (int rc = wg_packed_source_(&p->w, params, on_device, st, &src)) return rc;
+    hipLaunchKernelGGL(k_policy_pack, dim3((p->P.n_packed + 255) / 256), dim3(256), 0, st, p->P, src, p->w.packed);
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -361,13 +295,13 @@ extern "C" int wg_policy_set_params(wg_policy p, const float* params, size_t n, 
 extern "C" int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
                                uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, const WgValueRows* v, int n_v,
                                void* stream) {
-    if (!p) return pfail(WG_ERR_INVALID, "wg_policy_act: null argument");
+    if (!p) return wg_fail(WG_ERR_INVALID, "wg_policy_act: null argument");
     if (n_v < 0 || n_v > WGP_MAX_SLOTS - 1 || (n_v > 0 && !v))
-        return pfail(WG_ERR_INVALID, "wg_policy_act: a launch takes at most " + std::to_string(WGP_MAX_SLOTS - 1) + " row sets for the critic");
+        return wg_fail(WG_ERR_INVALID, "wg_policy_act: a launch takes at most " + std::to_string(WGP_MAX_SLOTS - 1) + " row sets for the critic");
     const bool actor = action_dev || raw_dev || logp_dev;
-    if (n_v > 0 && p->P.n_layers[1] == 0) return pfail(WG_ERR_INVALID, "wg_policy_act: value requested from a policy without a critic");
+    if (n_v > 0 && p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_policy_act: value requested from a policy without a critic");
     if (actor && !p->P.has_log_std && (!deterministic || logp_dev))
-        return pfail(WG_ERR_INVALID, "wg_policy_act: a stochastic action / a log-probability needs a policy with log_std");
+        return wg_fail(WG_ERR_INVALID, "wg_policy_act: a stochastic action / a log-probability needs a policy with log_std");
     WgPolicySlots S = {};
     int ns = 0, end = 0;
     if (actor && n_rows > 0) {
@@ -381,21 +315,21 @@ extern "C" int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, in
     }
     if (ns == 0) return 0;
     for (int i = ns; i < WGP_MAX_SLOTS; ++i) S.end[i] = end;
-    if (int rc = p_use_device(p)) return rc;
-    hipLaunchKernelGGL(k_policy, dim3(end), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, p->P, p->packed, S, deterministic ? 1 : 0,
+    if (int rc = wg_use_device(p->w.device)) return rc;
+    hipLaunchKernelGGL(k_policy, dim3(end), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, p->P, p->w.packed, S, deterministic ? 1 : 0,
                        seed, counter, row_offset, action_dev, raw_dev, logp_dev);
     const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return pfail(WG_ERR_HIP, std::string("wg_policy_act: kernel launch failed: ") + hipGetErrorString(le));
+    if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_policy_act: kernel launch failed: ") + hipGetErrorString(le));
     return 0;
 }
 
 extern "C" int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter,
                              uint64_t row_offset, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev,
                              void* stream) {
-    if (!p || !obs_dev) return pfail(WG_ERR_INVALID, "wg_policy_act: null argument");
-    if (n_rows < 0) return pfail(WG_ERR_INVALID, "wg_policy_act: n_rows < 0");
+    if (!p || !obs_dev) return wg_fail(WG_ERR_INVALID, "wg_policy_act: null argument");
+    if (n_rows < 0) return wg_fail(WG_ERR_INVALID, "wg_policy_act: n_rows < 0");
     if (value_dev && (action_dev || raw_dev || logp_dev) && p->P.n_layers[1] != 0 && p->P.n_in_vf != p->P.n_in)
-        return pfail(WG_ERR_INVALID, "wg_policy_act: the actor of this policy reads rows of " + std::to_string(p->P.n_in) +
+        return wg_fail(WG_ERR_INVALID, "wg_policy_act: the actor of this policy reads rows of " + std::to_string(p->P.n_in) +
                                          " inputs and its critic rows of " + std::to_string(p->P.n_in_vf) +
                                          ", so one obs_dev cannot serve both: ask for the value in a call of its own");
     const WgValueRows v = {obs_dev, value_dev, n_rows};
@@ -406,12 +340,6 @@ extern "C" int wg_policy_act(wg_policy p, int n_rows, const float* obs_dev, int 
 // ---------------------------------------------------------------------------------------------------------------------
 // populations: the slot table of k_policy_pop and its launches (wg_pop_create / wg_pop_destroy: wg_ppo.hip)
 // ---------------------------------------------------------------------------------------------------------------------
-static int pop_use_device(wg_pop_s* q) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != q->device) PHIPCHK(hipSetDevice(q->device));
-    return 0;
-}
-
 // A host table -> device memory in stream order WITHOUT a copy engine or a host synchronisation (a hipMemcpyAsync from pageable
 // memory waits for the stream): the bytes travel as kernel arguments, 2 KB per launch, and one thread per word stores them.
 struct WgPopWords { uint32_t w[512]; };
@@ -427,7 +355,7 @@ extern "C" int wg_pop_store_(void* dst_dev, const void* src_host, size_t bytes, 
         memcpy(c.w, (const char*)src_host + o, nb);
         hipLaunchKernelGGL(k_pop_store, dim3(2), dim3(256), 0, (hipStream_t)stream, c, (uint32_t*)((char*)dst_dev + o), (int)((nb + 3) / 4));
     }
-    PHIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -443,13 +371,13 @@ extern "C" int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint
                                const WgPopRows* r, void* stream) {
     const std::string w = who;
     const WgPolicyP& P = q->pol[0]->P;
-    if (n_rows < 0) return pfail(WG_ERR_INVALID, w + ": n_rows < 0");
+    if (n_rows < 0) return wg_fail(WG_ERR_INVALID, w + ": n_rows < 0");
     if (n_rows % q->P != 0)
-        return pfail(WG_ERR_INVALID, w + ": the " + std::to_string(q->P) + " members own equal shares of the rows, and " +
+        return wg_fail(WG_ERR_INVALID, w + ": the " + std::to_string(q->P) + " members own equal shares of the rows, and " +
                                          std::to_string(n_rows) + " rows do not divide by " + std::to_string(q->P));
     const bool actor = r->action || r->raw || r->logp;
-    if ((r->value || r->final_value) && P.n_layers[1] == 0) return pfail(WG_ERR_INVALID, w + ": value requested from policies without a critic");
-    if (actor && !seeds) return pfail(WG_ERR_INVALID, w + ": seeds[P] is required");
+    if ((r->value || r->final_value) && P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, w + ": value requested from policies without a critic");
+    if (actor && !seeds) return wg_fail(WG_ERR_INVALID, w + ": seeds[P] is required");
     const int Bm = n_rows / q->P;
     const int64_t step = r->stepped ? r->B : 0;
     WgPopSlot tab[WGP_POP_SLOTS] = {};
@@ -460,7 +388,7 @@ extern "C" int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint
             WgPopSlot& s = tab[ns++];
             const size_t row = (size_t)m * Bm;
             const int width = kind == 0 ? P.n_in : P.n_in_vf;
-            s.packed = q->pol[m]->packed;
+            s.packed = q->pol[m]->w.packed;
             s.obs = (kind == 2 ? r->final_obs : r->obs) + row * width;
             s.obs_step = step * width; s.act_step = step * P.n_out; s.row_step = step;
             s.net = kind == 0 ? 0 : 1;
@@ -480,7 +408,7 @@ extern "C" int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint
     q->has_final = r->final_value ? 1 : 0;
     q->Bm = Bm;
     if (ns == 0 || Bm == 0) return 0;
-    if (int rc = pop_use_device(q)) return rc;
+    if (int rc = wg_use_device(q->device)) return rc;
     return wg_pop_store_(q->slots_dev, tab, sizeof(WgPopSlot) * ns, stream);
 }
 
@@ -490,20 +418,20 @@ extern "C" int wg_pop_launch_(wg_pop q, int head, int fin, int t, int determinis
     const int kinds = (head ? q->n_head : 0) + (fin ? q->has_final : 0);
     if (kinds == 0 || q->Bm == 0) return 0;
     const int first = head ? 0 : q->n_head * q->P, tiles = (q->Bm + WGP_TILE - 1) / WGP_TILE;
-    if (int rc = pop_use_device(q)) return rc;
+    if (int rc = wg_use_device(q->device)) return rc;
     hipLaunchKernelGGL(k_policy_pop, dim3(kinds * q->P * tiles), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, q->pol[0]->P, q->slots_dev,
                        first, tiles, q->Bm, t, deterministic ? 1 : 0, counter);
     const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return pfail(WG_ERR_HIP, std::string("wg_pop: kernel launch failed: ") + hipGetErrorString(le));
+    if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_pop: kernel launch failed: ") + hipGetErrorString(le));
     return 0;
 }
 
 extern "C" int wg_pop_act(wg_pop q, int n_rows, const float* obs_dev, int deterministic, const uint64_t* seeds, uint64_t counter,
                           const uint64_t* row_offsets, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream) {
-    if (!q || !obs_dev) return pfail(WG_ERR_INVALID, "wg_pop_act: null argument");
+    if (!q || !obs_dev) return wg_fail(WG_ERR_INVALID, "wg_pop_act: null argument");
     const WgPolicyP& P = q->pol[0]->P;
     if ((action_dev || raw_dev || logp_dev) && !P.has_log_std && (!deterministic || logp_dev))
-        return pfail(WG_ERR_INVALID, "wg_pop_act: a stochastic action / a log-probability needs policies with log_std");
+        return wg_fail(WG_ERR_INVALID, "wg_pop_act: a stochastic action / a log-probability needs policies with log_std");
     const WgPopRows r = {obs_dev, action_dev, raw_dev, logp_dev, value_dev, nullptr, nullptr, n_rows, 0};
     if (int rc = wg_pop_prepare_(q, "wg_pop_act", n_rows, seeds, row_offsets, &r, stream)) return rc;
     return wg_pop_launch_(q, 1, 0, 0, deterministic, counter, stream);

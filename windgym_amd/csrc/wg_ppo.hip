@@ -28,9 +28,7 @@
 
 #include "../../include/windgym_hip.h"
 #include "wg_ppo.h"
-#include "wg_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "wg_host.h"
 
 #define WGT_HALF_LOG_2PI 0.91893853320467274f
 
@@ -194,11 +192,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int ot = wave + WGT_WAVES * t;
-                if (ot < ly.ntiles) {
-                    const float* bp = a_packed + ly.b_packed + ot * 32 + 4 * h;
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) acc[t][q] = bp[(q & 3) + 8 * (q >> 2)];
-                }
+                if (ot < ly.ntiles) wg_tile_bias(acc[t], a_packed + ly.b_packed + ot * 32, h);
             }
             const int nchunk = l == 0 ? (ly.K + WGP_KC - 1) / WGP_KC : 1;
             for (int c = 0; c < nchunk; ++c) {
@@ -235,7 +229,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                 if (ot < ly.ntiles) {
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const int i = ot * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                        const int i = ot * 32 + wg_tile_drow(q, h);
                         float v = acc[t][q];
                         if (!head) v = tanh_act ? tanhf(v) : fmaxf(v, 0.0f);
                         if (i < ly.M && r < R) dst[i * S + r] = v;
@@ -341,7 +335,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                     f32x16 acc;
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int i = ot * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                        const int i = ot * 32 + wg_tile_drow(e, h);
                         acc[e] = (!first && i < ly.M && kk < kc) ? wo[(size_t)i * ly.K] : 0.0f;
                     }
                     const int ia = ot * 32 + r;
@@ -353,7 +347,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                     }
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int i = ot * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                        const int i = ot * 32 + wg_tile_drow(e, h);
                         if (i < ly.M && kk < kc) wo[(size_t)i * ly.K] = acc[e];
                     }
                 }
@@ -377,7 +371,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                     }
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int k = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                        const int k = kt * 32 + wg_tile_drow(e, h);
                         if (k < ly.K && r < R) {
                             const float yv = y[k * S + r];
                             dp[k * S + r] = acc[e] * (tanh_act ? 1.0f - yv * yv : (yv > 0.0f ? 1.0f : 0.0f));
@@ -517,28 +511,15 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam_pop(const WgPopMember* _
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-static int tfail(int code, const std::string& msg) { return wg_set_last_error_(code, msg.c_str()); }
-#define THIPCHK(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t _e = (x);                                                                        \
-        if (_e != hipSuccess) return tfail(WG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-static int t_use_device(int device) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device) THIPCHK(hipSetDevice(device));
-    return 0;
-}
-
 // a device pointer of another GPU (or a host pointer) -> WG_ERR_INVALID
 static int t_on_device(const void* p, int device, const char* what) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
         (void)hipGetLastError();
-        return tfail(WG_ERR_INVALID, std::string(what) + " is not a device pointer");
+        return wg_fail(WG_ERR_INVALID, std::string(what) + " is not a device pointer");
     }
     if (at.type != hipMemoryTypeDevice || at.device != device)
-        return tfail(WG_ERR_INVALID, std::string(what) + " is not memory of device " + std::to_string(device));
+        return wg_fail(WG_ERR_INVALID, std::string(what) + " is not memory of device " + std::to_string(device));
     return 0;
 }
 
@@ -546,12 +527,12 @@ static int t_on_device(const void* p, int device, const char* what) {
 // messages; `all_there`: no pointer argument is null; P: the members the B envs divide among (1: one policy, always passes).
 static int gae_check(const char* who, const char* dims, const char* rows, bool all_there, int T, int B, int A, int P) {
     const std::string w = who;
-    if (!all_there) return tfail(WG_ERR_INVALID, w + ": null argument");
-    if (T < 1 || B < 1 || A < 1) return tfail(WG_ERR_INVALID, w + ": " + dims + " must be >= 1");
+    if (!all_there) return wg_fail(WG_ERR_INVALID, w + ": null argument");
+    if (T < 1 || B < 1 || A < 1) return wg_fail(WG_ERR_INVALID, w + ": " + dims + " must be >= 1");
     if (P < 1 || P > WG_POP_MAX || B % P != 0)
-        return tfail(WG_ERR_INVALID, w + ": P = " + std::to_string(P) + " must lie in 1 .. " + std::to_string(WG_POP_MAX) +
+        return wg_fail(WG_ERR_INVALID, w + ": P = " + std::to_string(P) + " must lie in 1 .. " + std::to_string(WG_POP_MAX) +
                                          " and divide B = " + std::to_string(B));
-    if ((long long)B * A > 0x7fffffffLL - 256) return tfail(WG_ERR_UNSUPPORTED, w + ": more than 2^31 " + rows);
+    if ((long long)B * A > 0x7fffffffLL - 256) return wg_fail(WG_ERR_UNSUPPORTED, w + ": more than 2^31 " + rows);
     return 0;
 }
 
@@ -564,7 +545,7 @@ static int gae_launch(const char* who, const char* dims, int T, int B, int A, co
         return rc;
     hipLaunchKernelGGL(k_gae, dim3((B * A + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, A, reward_dev, value_dev,
                        final_value_dev, truncated_dev, gamma, lambda, advantage_out, returns_out);
-    THIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -610,22 +591,22 @@ static size_t t_lds_map(const WgPolicyP& P, int R, WgPpoK* K) {
 }
 
 extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
-    if (!p || !out) return tfail(WG_ERR_INVALID, "wg_ppo_create: null argument");
+    if (!p || !out) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: null argument");
     *out = nullptr;
     const WgPolicyP& P = p->P;
-    if (P.n_layers[1] == 0) return tfail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with a critic");
-    if (!P.has_log_std) return tfail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with log_std");
+    if (P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with a critic");
+    if (!P.has_log_std) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with log_std");
     wg_ppo_s* o = new (std::nothrow) wg_ppo_s();
-    if (!o) return tfail(WG_ERR_NOMEM, "wg_ppo_create: out of host memory");
+    if (!o) return wg_fail(WG_ERR_NOMEM, "wg_ppo_create: out of host memory");
     o->pol = p;
-    o->device = p->device;
+    o->device = p->w.device;
     o->n_flat = P.n_flat;
     o->n_blocks = (P.n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
     int R = 32;
     while ((o->lds_bytes = t_lds_map(P, R, &o->K)) > WGT_LDS_BYTES && R > 2) R >>= 1;
     if (o->lds_bytes > WGT_LDS_BYTES) {
         delete o;
-        return tfail(WG_ERR_UNSUPPORTED, "wg_ppo_create: the architecture's activations do not fit the workgroup's LDS");
+        return wg_fail(WG_ERR_UNSUPPORTED, "wg_ppo_create: the architecture's activations do not fit the workgroup's LDS");
     }
     size_t gm = WGT_PART_BYTES / (sizeof(float) * (size_t)P.n_flat);
     o->g_max = (int)(gm < 1 ? 1 : gm > WGT_G_MAX ? WGT_G_MAX : gm);
@@ -645,7 +626,7 @@ extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
     if (e == hipSuccess) e = hipMemset(o->advstat, 0, sizeof(float) * 2);
     if (e != hipSuccess) {
         wg_ppo_destroy(o);
-        return tfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
     }
     *out = o;
     return 0;
@@ -664,23 +645,23 @@ extern "C" int wg_ppo_destroy(wg_ppo o) {
 }
 
 extern "C" int wg_ppo_get_state(wg_ppo o, float* mv_host, size_t n, uint64_t* step) {
-    if (!o || !mv_host || !step) return tfail(WG_ERR_INVALID, "wg_ppo_get_state: null argument");
-    if (n != 2 * (size_t)o->n_flat) return tfail(WG_ERR_INVALID, "wg_ppo_get_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
-    if (int rc = t_use_device(o->device)) return rc;
-    THIPCHK(hipDeviceSynchronize());
-    THIPCHK(hipMemcpy(mv_host, o->m, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
-    THIPCHK(hipMemcpy(mv_host + o->n_flat, o->v, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
+    if (!o || !mv_host || !step) return wg_fail(WG_ERR_INVALID, "wg_ppo_get_state: null argument");
+    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_ppo_get_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
+    if (int rc = wg_use_device(o->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipMemcpy(mv_host, o->m, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy(mv_host + o->n_flat, o->v, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
     *step = o->step;
     return 0;
 }
 
 extern "C" int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64_t step) {
-    if (!o || !mv_host) return tfail(WG_ERR_INVALID, "wg_ppo_set_state: null argument");
-    if (n != 2 * (size_t)o->n_flat) return tfail(WG_ERR_INVALID, "wg_ppo_set_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
-    if (int rc = t_use_device(o->device)) return rc;
-    THIPCHK(hipDeviceSynchronize());
-    THIPCHK(hipMemcpy(o->m, mv_host, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
-    THIPCHK(hipMemcpy(o->v, mv_host + o->n_flat, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
+    if (!o || !mv_host) return wg_fail(WG_ERR_INVALID, "wg_ppo_set_state: null argument");
+    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_ppo_set_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
+    if (int rc = wg_use_device(o->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipMemcpy(o->m, mv_host, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(o->v, mv_host + o->n_flat, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
     o->step = step;
     return 0;
 }
@@ -688,19 +669,19 @@ extern "C" int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64
 // the rows of a batch and the critic's stream (a plain batch: its obs), for every entry that takes one
 static int t_check_rows(const char* who, const wg_ppo_batch* b, const float* obs_vf) {
     if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !obs_vf)
-        return tfail(WG_ERR_INVALID, std::string(who) + ": a batch pointer is null");
-    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return tfail(WG_ERR_INVALID, std::string(who) + ": n_rows out of range");
+        return wg_fail(WG_ERR_INVALID, std::string(who) + ": a batch pointer is null");
+    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return wg_fail(WG_ERR_INVALID, std::string(who) + ": n_rows out of range");
     return 0;
 }
 
 // (`who` is the entry the CALLER used: wg_ppo_grad is wg_ppo_grad_shared on {*batch, batch->obs, 1} and reports under its own name)
 static int t_check_batch(const char* who, const wg_ppo_batch_shared* sb, const wg_ppo_hyper* hp) {
-    if (!sb || !hp) return tfail(WG_ERR_INVALID, std::string(who) + ": null argument");
+    if (!sb || !hp) return wg_fail(WG_ERR_INVALID, std::string(who) + ": null argument");
     const wg_ppo_batch* b = &sb->rows;
     if (int rc = t_check_rows(who, b, sb->obs_vf)) return rc;
     if (sb->agents < 1 || b->n_rows % sb->agents != 0)
-        return tfail(WG_ERR_INVALID, std::string(who) + ": agents must be >= 1 and divide n_rows (" + std::to_string(b->n_rows) + ")");
-    if (!(hp->clip_range >= 0.0f)) return tfail(WG_ERR_INVALID, std::string(who) + ": clip_range < 0");
+        return wg_fail(WG_ERR_INVALID, std::string(who) + ": agents must be >= 1 and divide n_rows (" + std::to_string(b->n_rows) + ")");
+    if (!(hp->clip_range >= 0.0f)) return wg_fail(WG_ERR_INVALID, std::string(who) + ": clip_range < 0");
     return 0;
 }
 
@@ -719,13 +700,13 @@ static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* 
     const int normalize = hp->normalize_advantage && n > 1;
     if (normalize) hipLaunchKernelGGL(k_ppo_advstat, dim3(1), dim3(1024), 0, st, b->advantage, index_dev, first, n, b->n_rows, sb->agents, o->advstat);
     WgPpoArgs a;
-    a.packed = o->pol->packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = sb->obs_vf; a.agents = sb->agents; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
+    a.packed = o->pol->w.packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = sb->obs_vf; a.agents = sb->agents; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
     a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G; a.normalize = normalize;
     a.clip = hp->clip_range; a.vf_coef = hp->vf_coef; a.advstat = o->advstat; a.part = o->part; a.spart = o->spart;
     hipLaunchKernelGGL(k_ppo_grad, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
     hipLaunchKernelGGL(k_ppo_reduce, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, P, o->part, o->spart, G, n, hp->vf_coef,
                        hp->ent_coef, normalize, o->advstat, params_dev, grad_out, stats_out ? stats_out : o->stats);
-    THIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -746,18 +727,18 @@ static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr,
     hipLaunchKernelGGL(k_ppo_sumsq, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, o->n_flat, o->blocksq);
     hipLaunchKernelGGL(k_ppo_adam, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, o->m, o->v, o->n_flat,
                        o->blocksq, o->n_blocks, max_grad_norm, s.step_size, s.bc2_sqrt, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
-    THIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return wg_policy_set_params(o->pol, params_dev, o->n_flat, 1, (void*)st);
 }
 
 static int grad_entry(const char* who, wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b, const int32_t* index_dev,
                       int64_t first, int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
     const std::string w = who;
-    if (!o || !params_dev || !grad_out) return tfail(WG_ERR_INVALID, w + ": null argument");
+    if (!o || !params_dev || !grad_out) return wg_fail(WG_ERR_INVALID, w + ": null argument");
     if (int rc = t_check_batch(who, b, hp)) return rc;
-    if (n < 1) return tfail(WG_ERR_INVALID, w + ": n < 1");
-    if (!index_dev && (first < 0 || first + n > b->rows.n_rows)) return tfail(WG_ERR_INVALID, w + ": rows first .. first + n - 1 leave the batch");
-    if (int rc = t_use_device(o->device)) return rc;
+    if (n < 1) return wg_fail(WG_ERR_INVALID, w + ": n < 1");
+    if (!index_dev && (first < 0 || first + n > b->rows.n_rows)) return wg_fail(WG_ERR_INVALID, w + ": rows first .. first + n - 1 leave the batch");
+    if (int rc = wg_use_device(o->device)) return rc;
     if (int rc = t_on_device(params_dev, o->device, (w + ": params_dev").c_str())) return rc;
     if (int rc = t_on_device(b->rows.obs, o->device, (w + ": obs").c_str())) return rc;
     if (b->obs_vf != b->rows.obs)
@@ -775,23 +756,23 @@ extern "C" int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_pp
 static int t_refuse_split(const char* who, wg_ppo o) {
     const WgPolicyP& P = o->pol->P;
     if (P.n_in_vf == P.n_in) return 0;
-    return tfail(WG_ERR_INVALID, std::string(who) + ": the policy's critic reads rows of " + std::to_string(P.n_in_vf) + " inputs, its actor rows of " +
+    return wg_fail(WG_ERR_INVALID, std::string(who) + ": the policy's critic reads rows of " + std::to_string(P.n_in_vf) + " inputs, its actor rows of " +
                                      std::to_string(P.n_in) + ", and a wg_ppo_batch has one obs stream of the actor's width: use " + who +
                                      "_shared with the critic's rows as obs_vf");
 }
 
 extern "C" int wg_ppo_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch* b, const int32_t* index_dev, int64_t first,
                            int n, const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
-    if (!o || !b) return tfail(WG_ERR_INVALID, "wg_ppo_grad: null argument");
+    if (!o || !b) return wg_fail(WG_ERR_INVALID, "wg_ppo_grad: null argument");
     if (int rc = t_refuse_split("wg_ppo_grad", o)) return rc;
     const wg_ppo_batch_shared sb = {*b, b->obs, 1};
     return grad_entry("wg_ppo_grad", o, params_dev, &sb, index_dev, first, n, hp, grad_out, stats_out, stream);
 }
 
 extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream) {
-    if (!o || !params_dev || !grad_dev) return tfail(WG_ERR_INVALID, "wg_ppo_apply: null argument");
-    if (!(max_grad_norm > 0.0f)) return tfail(WG_ERR_INVALID, "wg_ppo_apply: max_grad_norm must be > 0");
-    if (int rc = t_use_device(o->device)) return rc;
+    if (!o || !params_dev || !grad_dev) return wg_fail(WG_ERR_INVALID, "wg_ppo_apply: null argument");
+    if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_ppo_apply: max_grad_norm must be > 0");
+    if (int rc = wg_use_device(o->device)) return rc;
     if (int rc = t_on_device(params_dev, o->device, "wg_ppo_apply: params_dev")) return rc;
     if (int rc = t_on_device(grad_dev, o->device, "wg_ppo_apply: grad_dev")) return rc;
     return t_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
@@ -816,11 +797,11 @@ static int t_each_minibatch(int64_t rows, int n_epochs, int batch_size, F f) {
 static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
                         int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream) {
     const std::string w = who;
-    if (!o || !params_dev || !perm_dev) return tfail(WG_ERR_INVALID, w + ": null argument");
+    if (!o || !params_dev || !perm_dev) return wg_fail(WG_ERR_INVALID, w + ": null argument");
     if (int rc = t_check_batch(who, b, hp)) return rc;
-    if (n_epochs < 1 || batch_size < 1) return tfail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
-    if (!(max_grad_norm > 0.0f)) return tfail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
-    if (int rc = t_use_device(o->device)) return rc;
+    if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
+    if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
+    if (int rc = wg_use_device(o->device)) return rc;
     if (int rc = t_on_device(params_dev, o->device, (w + ": params_dev").c_str())) return rc;
     if (int rc = t_on_device(b->rows.obs, o->device, (w + ": obs").c_str())) return rc;
     if (b->obs_vf != b->rows.obs)
@@ -842,7 +823,7 @@ extern "C" int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_ba
 extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
                              int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out,
                              void* stream) {
-    if (!o || !b) return tfail(WG_ERR_INVALID, "wg_ppo_update: null argument");
+    if (!o || !b) return wg_fail(WG_ERR_INVALID, "wg_ppo_update: null argument");
     if (int rc = t_refuse_split("wg_ppo_update", o)) return rc;
     const wg_ppo_batch_shared sb = {*b, b->obs, 1};
     return update_entry("wg_ppo_update", o, params_dev, &sb, perm_dev, n_epochs, batch_size, hp, lr, max_grad_norm, stats_out, stream);
@@ -852,44 +833,44 @@ extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b,
 // populations (windgym_hip.h: wg_pop_*; the slot table and the launches of the policy kernel: wg_policy.hip)
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P, wg_pop* out) {
-    if (!members || !out) return tfail(WG_ERR_INVALID, "wg_pop_create: null argument");
+    if (!members || !out) return wg_fail(WG_ERR_INVALID, "wg_pop_create: null argument");
     *out = nullptr;
     if (P < 1 || P > WG_POP_MAX)
-        return tfail(WG_ERR_INVALID, "wg_pop_create: a population has 1 .. " + std::to_string(WG_POP_MAX) + " members, not " + std::to_string(P));
+        return wg_fail(WG_ERR_INVALID, "wg_pop_create: a population has 1 .. " + std::to_string(WG_POP_MAX) + " members, not " + std::to_string(P));
     for (int m = 0; m < P; ++m) {
         const std::string who = "wg_pop_create: member " + std::to_string(m);
-        if (!members[m]) return tfail(WG_ERR_INVALID, who + " is null");
+        if (!members[m]) return wg_fail(WG_ERR_INVALID, who + " is null");
         const WgPolicyP &A = members[0]->P, &Q = members[m]->P;
         if (Q.n_layers[1] != 0 && Q.n_in_vf != Q.n_in)
-            return tfail(WG_ERR_INVALID, who + " is a split policy (its critic reads " + std::to_string(Q.n_in_vf) + " inputs, its actor " +
+            return wg_fail(WG_ERR_INVALID, who + " is a split policy (its critic reads " + std::to_string(Q.n_in_vf) + " inputs, its actor " +
                                              std::to_string(Q.n_in) + "): populations take policies whose nets read the same rows");
-        if (members[m]->device != members[0]->device)
-            return tfail(WG_ERR_INVALID, who + " lives on device " + std::to_string(members[m]->device) + ", member 0 on device " +
-                                             std::to_string(members[0]->device));
+        if (members[m]->w.device != members[0]->w.device)
+            return wg_fail(WG_ERR_INVALID, who + " lives on device " + std::to_string(members[m]->w.device) + ", member 0 on device " +
+                                             std::to_string(members[0]->w.device));
         // the layer table is a function of the wg_policy_desc alone: equal descs <=> equal tables
         bool same = Q.n_in == A.n_in && Q.n_out == A.n_out && Q.activation == A.activation && Q.has_log_std == A.has_log_std &&
                     Q.n_in_vf == A.n_in_vf && Q.n_layers[0] == A.n_layers[0] && Q.n_layers[1] == A.n_layers[1] && Q.n_flat == A.n_flat;
         for (int net = 0; net < 2 && same; ++net)
             for (int l = 0; l < Q.n_layers[net]; ++l) same = same && Q.layer[net][l].K == A.layer[net][l].K && Q.layer[net][l].M == A.layer[net][l].M;
-        if (!same) return tfail(WG_ERR_INVALID, who + " has another architecture than member 0: the members of a population share one");
+        if (!same) return wg_fail(WG_ERR_INVALID, who + " has another architecture than member 0: the members of a population share one");
         for (int k = 0; k < m; ++k)
-            if (members[k] == members[m]) return tfail(WG_ERR_INVALID, who + " is the same policy as member " + std::to_string(k));
+            if (members[k] == members[m]) return wg_fail(WG_ERR_INVALID, who + " is the same policy as member " + std::to_string(k));
         if (opts) {
-            if (!opts[m]) return tfail(WG_ERR_INVALID, who + ": its wg_ppo is null (opts = NULL makes a population that only acts)");
-            if (opts[m]->pol != members[m]) return tfail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another policy");
+            if (!opts[m]) return wg_fail(WG_ERR_INVALID, who + ": its wg_ppo is null (opts = NULL makes a population that only acts)");
+            if (opts[m]->pol != members[m]) return wg_fail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another policy");
         }
     }
     wg_pop_s* q = new (std::nothrow) wg_pop_s();
-    if (!q) return tfail(WG_ERR_NOMEM, "wg_pop_create: out of host memory");
+    if (!q) return wg_fail(WG_ERR_NOMEM, "wg_pop_create: out of host memory");
     q->P = P;
-    q->device = members[0]->device;
+    q->device = members[0]->w.device;
     for (int m = 0; m < P; ++m) { q->pol[m] = members[m]; q->opt[m] = opts ? opts[m] : nullptr; }
     hipError_t e = hipSetDevice(q->device);
     if (e == hipSuccess) e = hipMalloc((void**)&q->slots_dev, sizeof(WgPopSlot) * WGP_POP_SLOTS);
     if (e == hipSuccess) e = hipMalloc(&q->upd_dev, sizeof(WgPopMember) * WGP_POP_MAX);
     if (e != hipSuccess) {
         wg_pop_destroy(q);
-        return tfail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_pop_create: ") + hipGetErrorString(e));
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_pop_create: ") + hipGetErrorString(e));
     }
     *out = q;
     return 0;
@@ -916,27 +897,27 @@ extern "C" int wg_gae_pop(int T, int B, int P, const float* reward_dev, const fl
     for (int m = 0; m < P; ++m) { hy.gamma[m] = gamma[m]; hy.lambda[m] = lambda[m]; }
     hipLaunchKernelGGL(k_gae_pop, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, B, B / P, reward_dev, value_dev,
                        final_value_dev, truncated_dev, hy, advantage_out, returns_out);
-    THIPCHK(hipGetLastError());
+    WG_HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
                              int batch_size, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm,
                              wg_ppo_stats* stats_out, void* stream) {
-    if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return tfail(WG_ERR_INVALID, "wg_pop_update: null argument");
+    if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return wg_fail(WG_ERR_INVALID, "wg_pop_update: null argument");
     const int P = q->P;
-    if (!q->opt[0]) return tfail(WG_ERR_INVALID, "wg_pop_update: the population was created without optimisers (opts = NULL): it only acts");
+    if (!q->opt[0]) return wg_fail(WG_ERR_INVALID, "wg_pop_update: the population was created without optimisers (opts = NULL): it only acts");
     if (int rc = t_check_rows("wg_pop_update", b, b->obs)) return rc;
     if (b->n_rows % P != 0)
-        return tfail(WG_ERR_INVALID, "wg_pop_update: the " + std::to_string(P) + " members own equal shares of the batch, and " +
+        return wg_fail(WG_ERR_INVALID, "wg_pop_update: the " + std::to_string(P) + " members own equal shares of the batch, and " +
                                          std::to_string(b->n_rows) + " rows do not divide by " + std::to_string(P));
-    if (n_epochs < 1 || batch_size < 1) return tfail(WG_ERR_INVALID, "wg_pop_update: n_epochs and batch_size must be >= 1");
-    if (int rc = t_use_device(q->device)) return rc;
+    if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, "wg_pop_update: n_epochs and batch_size must be >= 1");
+    if (int rc = wg_use_device(q->device)) return rc;
     for (int m = 0; m < P; ++m) {
         const std::string who = "wg_pop_update: member " + std::to_string(m);
-        if (!params_dev[m]) return tfail(WG_ERR_INVALID, who + ": params_dev is null");
-        if (!(hp[m].clip_range >= 0.0f)) return tfail(WG_ERR_INVALID, who + ": clip_range < 0");
-        if (!(max_grad_norm[m] > 0.0f)) return tfail(WG_ERR_INVALID, who + ": max_grad_norm must be > 0");
+        if (!params_dev[m]) return wg_fail(WG_ERR_INVALID, who + ": params_dev is null");
+        if (!(hp[m].clip_range >= 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": clip_range < 0");
+        if (!(max_grad_norm[m] > 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": max_grad_norm must be > 0");
         if (int rc = t_on_device(params_dev[m], q->device, (who + ": params_dev").c_str())) return rc;
     }
     if (int rc = t_on_device(b->obs, q->device, "wg_pop_update: obs")) return rc;
@@ -948,7 +929,7 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     for (int m = 0; m < P; ++m) {
         wg_ppo_s* o = q->opt[m];
         WgPopMember& M = tab[m];
-        M.packed = o->pol->packed; M.params = params_dev[m];
+        M.packed = o->pol->w.packed; M.params = params_dev[m];
         M.m = o->m; M.v = o->v; M.grad = o->grad; M.part = o->part; M.spart = o->spart; M.advstat = o->advstat; M.blocksq = o->blocksq;
         M.perm = perm_dev + (size_t)m * n_epochs * rows_m;
         M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->stats;
@@ -980,7 +961,7 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
         hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat);
         hipLaunchKernelGGL(k_ppo_adam_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat, o0->n_blocks, A, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
         wg_policy_pack_pop_(&PP, mt, P, stream);
-        THIPCHK(hipGetLastError());
+        WG_HIPCHK(hipGetLastError());
         return 0;
     });
 }

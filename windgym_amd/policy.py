@@ -71,14 +71,15 @@ def param_layout(desc):
     return out
 
 
-def n_params(desc):
-    return int(sum(int(np.prod(s)) for _, s in param_layout(desc)))
+def layout_n_params(layout):
+    """Floats of a ``[(name, shape)]`` layout (``param_layout`` here, ``recurrent.param_layout``)."""
+    return int(sum(int(np.prod(s)) for _, s in layout))
 
 
-def pack_params(desc, tensors):
-    """{name: array} -> flat float32 vector."""
+def layout_pack(layout, tensors):
+    """{name: array} -> flat float32 vector in the layout's order."""
     parts = []
-    for name, shape in param_layout(desc):
+    for name, shape in layout:
         if name not in tensors:
             raise ValueError(f"missing tensor {name!r}")
         a = np.asarray(tensors[name], dtype=np.float32)
@@ -88,17 +89,31 @@ def pack_params(desc, tensors):
     return np.concatenate(parts) if parts else np.zeros(0, np.float32)
 
 
-def unpack_params(desc, flat):
+def layout_unpack(layout, flat):
     """flat vector -> {name: float32 array}."""
     flat = np.asarray(flat, dtype=np.float32).reshape(-1)
-    if flat.size != n_params(desc):
-        raise ValueError(f"{flat.size} parameters given, the architecture has {n_params(desc)}")
+    if flat.size != layout_n_params(layout):
+        raise ValueError(f"{flat.size} parameters given, the architecture has {layout_n_params(layout)}")
     out, o = {}, 0
-    for name, shape in param_layout(desc):
+    for name, shape in layout:
         n = int(np.prod(shape))
         out[name] = flat[o:o + n].reshape(shape).copy()
         o += n
     return out
+
+
+def n_params(desc):
+    return layout_n_params(param_layout(desc))
+
+
+def pack_params(desc, tensors):
+    """{name: array} -> flat float32 vector."""
+    return layout_pack(param_layout(desc), tensors)
+
+
+def unpack_params(desc, flat):
+    """flat vector -> {name: float32 array}."""
+    return layout_unpack(param_layout(desc), flat)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -118,12 +133,9 @@ def _chain(tensors, prefix, n_in, what):
     return hidden, k
 
 
-def read_sb3_zip(path, activation="tanh"):
-    """-> (desc, {SB3 name: float32 array}) of a stable-baselines3 >= 2.0 ``MlpPolicy`` checkpoint (PPO / A2C ``.zip``).
-
-    The architecture comes from the tensor names and shapes; the activation is not in the tensors (SB3's default: tanh).
-    Raises ValueError naming the reason for: ``use_sde``, a shared trunk, a non-flatten feature extractor, missing tensors,
-    shapes that do not chain."""
+def _read_policy_pth(path):
+    """{name: float32 array} of the ``policy.pth`` of an SB3 / sb3-contrib ``.zip``.  Nothing is unpickled: the tensors by
+    ``torch.load(weights_only=True)``, ``data`` as plain JSON (read only to refuse ``use_sde``)."""
     import torch
     with zipfile.ZipFile(path) as z:
         names = z.namelist()
@@ -134,7 +146,16 @@ def read_sb3_zip(path, activation="tanh"):
             if isinstance(data, dict) and data.get("use_sde") is True:
                 raise ValueError("use_sde: true — state-dependent exploration is not supported")
         sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
-    tensors = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in sd.items()}
+    return {k: v.detach().cpu().numpy().astype(np.float32) for k, v in sd.items()}
+
+
+def read_sb3_zip(path, activation="tanh"):
+    """-> (desc, {SB3 name: float32 array}) of a stable-baselines3 >= 2.0 ``MlpPolicy`` checkpoint (PPO / A2C ``.zip``).
+
+    The architecture comes from the tensor names and shapes; the activation is not in the tensors (SB3's default: tanh).
+    Raises ValueError naming the reason for: ``use_sde``, a shared trunk, a non-flatten feature extractor, missing tensors,
+    shapes that do not chain."""
+    tensors = _read_policy_pth(path)
     if any(k.startswith("lstm_actor.") for k in tensors):
         raise ValueError("recurrent checkpoint (lstm_actor.* tensors: sb3-contrib's RecurrentPPO): load it with "
                          "MlpLstmPolicy.from_sb3_zip (windgym_amd.recurrent)")

@@ -31,9 +31,6 @@ of ``wg_lstm_step``.  Flat parameter order: per LSTM (the actor's first) ``weigh
 from __future__ import annotations
 
 import ctypes as C
-import io
-import json
-import zipfile
 
 import numpy as np
 
@@ -79,33 +76,17 @@ def param_layout(desc):
 
 
 def n_params(desc):
-    return int(sum(int(np.prod(s)) for _, s in param_layout(desc)))
+    return _mlp.layout_n_params(param_layout(desc))
 
 
 def pack_params(desc, tensors):
     """{name: array} -> flat float32 vector."""
-    parts = []
-    for name, shape in param_layout(desc):
-        if name not in tensors:
-            raise ValueError(f"missing tensor {name!r}")
-        a = np.asarray(tensors[name], dtype=np.float32)
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(a.shape)}, expected {tuple(shape)}")
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
+    return _mlp.layout_pack(param_layout(desc), tensors)
 
 
 def unpack_params(desc, flat):
     """flat vector -> {name: float32 array}."""
-    flat = np.asarray(flat, dtype=np.float32).reshape(-1)
-    if flat.size != n_params(desc):
-        raise ValueError(f"{flat.size} parameters given, the architecture has {n_params(desc)}")
-    out, o = {}, 0
-    for name, shape in param_layout(desc):
-        n = int(np.prod(shape))
-        out[name] = flat[o:o + n].reshape(shape).copy()
-        o += n
-    return out
+    return _mlp.layout_unpack(param_layout(desc), flat)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -118,17 +99,7 @@ def read_sb3_lstm_zip(path, activation="tanh"):
     the tensor names and shapes; the activation is not in the tensors (default: tanh).  Raises ValueError naming the reason for:
     more than one LSTM layer, the Linear critic of ``enable_critic_lstm=False``, a feature extractor, ``use_sde``, a shared MLP
     trunk, missing tensors, shapes that do not chain."""
-    import torch
-    with zipfile.ZipFile(path) as z:
-        names = z.namelist()
-        if "policy.pth" not in names:
-            raise ValueError("not an SB3 checkpoint: no policy.pth in the archive")
-        if "data" in names:
-            data = json.loads(z.read("data").decode())          # plain JSON; ":serialized:" blobs stay strings
-            if isinstance(data, dict) and data.get("use_sde") is True:
-                raise ValueError("use_sde: true — state-dependent exploration is not supported")
-        sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
-    tensors = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in sd.items()}
+    tensors = _mlp._read_policy_pth(path)
     if not any(k.startswith("lstm_actor.") for k in tensors):
         raise ValueError("not a recurrent checkpoint: no lstm_actor.* tensors (an MlpPolicy zip loads with MlpPolicy.from_sb3_zip)")
     for net in ("lstm_actor", "lstm_critic"):
