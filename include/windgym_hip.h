@@ -879,8 +879,8 @@ int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps, int determ
  *     z = (b_ih + b_hh) + [W_ih | W_hh] (x ‖ h);  c' = sigmoid(z_f) c + sigmoid(z_i) tanh(z_g);  h' = sigmoid(z_o) tanh(c')
  * The episode-start mask is a SELECT: such a row does not depend on its incoming state at all, also where that state holds NaN
  * (sb3-contrib multiplies the state by 1 - episode_start; for finite states the two agree).  The two biases are added once, when
- * the parameters are packed, and the sum starts the k-ordered f32 accumulation over x then h.  Inference only: training through
- * time is not part of this ABI yet — wg_rollout_lstm records what it will need (the initial state, the episode starts).
+ * the parameters are packed, and the sum starts the k-ordered f32 accumulation over x then h.  Training through time is wg_lstm_ppo below, on what
+ * wg_rollout_lstm records for it (the initial state, the episode starts).
  * Bounds (WG_ERR_UNSUPPORTED outside): n_in <= 2048, 1 <= hidden <= 256.
  * --------------------------------------------------------------------------------------------------------------- */
 typedef struct wg_lstm_s* wg_lstm;
@@ -949,6 +949,72 @@ typedef struct wg_rollout_lstm_bufs {
  * obs_dim, lstm on another device than the handle, a null lstm_bufs or one without state / episode_start / scratch.            */
 int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                     uint64_t row_offset, const wg_rollout_bufs* bufs, const wg_rollout_lstm_bufs* lstm_bufs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training recurrent policies: sb3-contrib's RecurrentPPO.train for the wg_lstm + wg_policy pair above, by backpropagation through
+ * time in HIP (windgym_amd/csrc/wg_lstm_ppo.hip).  fp32 throughout; every entry is asynchronous on `stream`, synchronises nothing
+ * and is bit-identical from run to run (no atomics; every sum's order is fixed by T, the minibatch's size and the shapes).
+ * ONE flat parameter vector of wg_lstm_ppo_n_params floats: the LSTM's (wg_lstm_set_params' order), then the MLP's
+ * (wg_policy_set_params' order).
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_lstm_ppo_s* wg_lstm_ppo;
+
+/* One rollout as wg_rollout_lstm leaves it (device pointers), advantage / returns from wg_gae on [T, B]. */
+typedef struct wg_lstm_ppo_batch {
+    const float*   obs;            /* [T (+ 1), B, n_in]   the first T slots are read                                  */
+    const float*   raw;            /* [T, B, n_out]                                                                   */
+    const float*   logp;           /* [T, B]                                                                          */
+    const float*   advantage;      /* [T, B]                                                                          */
+    const float*   returns;        /* [T, B]                                                                          */
+    const uint8_t* episode_start;  /* [T (+ 1), B]         the first T slots are read                                  */
+    const float*   lstm_state0;    /* [nets][2][B][H]      the state the rollout began from                            */
+    int32_t T, B;
+} wg_lstm_ppo_batch;
+
+/* The optimiser of the pair (l, p): Adam's moments and step count over the ONE flat vector, and the buffers of the sequence kernels
+ * for minibatches of up to Bm_max envs x T_max steps (their size: wg_lstm_ppo.h).  l and p must outlive it.  WG_ERR_INVALID: null
+ * arguments, p's n_in or its critic's width != l's hidden, a policy without critic or log_std, different devices, T_max or Bm_max
+ * < 1.  WG_ERR_UNSUPPORTED, naming T_max and Bm_max: buffers beyond 16 GiB or more than 2^24 rows per minibatch.          */
+int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max, wg_lstm_ppo* out);
+int wg_lstm_ppo_destroy(wg_lstm_ppo o);
+int wg_lstm_ppo_n_params(wg_lstm_ppo o, size_t* n);
+
+/* Adam's m then v as ONE host vector of 2 * wg_lstm_ppo_n_params floats, and the step count.  Synchronises the device. */
+int wg_lstm_ppo_get_state(wg_lstm_ppo o, float* mv_host, size_t n, uint64_t* step);
+int wg_lstm_ppo_set_state(wg_lstm_ppo o, const float* mv_host, size_t n, uint64_t step);
+
+/* Loss and gradient of ONE minibatch of WHOLE env sequences: the envs envs_dev[0 .. n_envs-1] (int32, device; an entry outside
+ * [0, B) counts as rows of zeros and is never dereferenced) with all T steps of each, n = T * n_envs rows.
+ *   forward:  per env and net, (h, c) starts from lstm_state0[net][., env] — DATA, not a function of the parameters — and runs
+ *     wg_lstm_step's cell over t = 0 .. T-1 with episode_start[t] as its SELECT (a fresh row reads zeros in place of its state,
+ *     also where lstm_state0 holds NaN);
+ *   loss:  wg_ppo_grad's, unchanged, on the n rows, the actor's MLP on the actor LSTM's h_t and the critic's on the critic LSTM's
+ *     (the same rows when the LSTM is shared); normalize_advantage uses the mean and unbiased std of the minibatch's n rows;
+ *   backward through time:  the gradient flows from (h_t, c_t) to (h_{t-1}, c_{t-1}) except across a step with episode_start[t] != 0,
+ *     where it stops (the W_hh columns of such a step see h = 0); with a shared LSTM dh_t is the actor head's input gradient plus
+ *     the critic head's, added in that order.
+ * With whole-env minibatches this is sb3-contrib's sequence rule (sequences cut at episode starts, initial states from the rollout).
+ * grad_out f32[wg_lstm_ppo_n_params] = d loss / d params; stats_out (device, may be NULL) wg_ppo_grad's record.  params_dev must be
+ * the vector both handles were last given (wg_lstm_set_params + wg_policy_set_params, or wg_lstm_ppo_apply).
+ * WG_ERR_INVALID: null arguments, T / B / n_envs < 1, clip_range < 0.  WG_ERR_UNSUPPORTED: T > T_max or n_envs > Bm_max.        */
+int wg_lstm_ppo_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_batch* batch, const int32_t* envs_dev, int n_envs,
+                     const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream);
+
+/* wg_ppo_apply's rule on the ONE flat vector: clipping by the global norm of the whole gradient, Adam (betas 0.9 / 0.999, eps 1e-5,
+ * bias-corrected) on params_dev IN PLACE, then wg_lstm_set_params(l, params_dev) and wg_policy_set_params(p, params_dev + the
+ * LSTM's count) in stream order.  WG_ERR_INVALID: null arguments, max_grad_norm <= 0.                                          */
+int wg_lstm_ppo_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream);
+
+/* All epochs and minibatches of one rollout, enqueued by one call with no host round trip: perm_dev int32[n_epochs, B] holds a
+ * permutation of the envs 0 .. B-1 per epoch, n_mb = ceil(B / envs_per_batch) minibatches per epoch, the last one shorter when
+ * envs_per_batch does not divide B; stats_out (device, may be NULL) is wg_ppo_stats[n_epochs, n_mb].  Bit-identical to
+ *     for e in 0 .. n_epochs-1:  for k in 0 .. n_mb-1:
+ *         wg_lstm_ppo_grad(o, params_dev, batch, perm_dev + e * B + k * envs_per_batch, min(envs_per_batch, B - k * envs_per_batch),
+ *                          hp, g, stats_out + e * n_mb + k);   wg_lstm_ppo_apply(o, params_dev, g, lr, max_grad_norm)
+ * lstm_state0 stays the rollout's: after the first minibatch it is stale, as in sb3-contrib.
+ * WG_ERR_INVALID / WG_ERR_UNSUPPORTED: what the two calls refuse, n_epochs < 1.                                                 */
+int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
+                       int envs_per_batch, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("PPO", "PPOOptimizer"):
         from . import ppo
         return getattr(ppo, name)
+    if name in ("RecurrentPPO", "RecurrentPPOOptimizer"):
+        from . import recurrent_ppo
+        return getattr(recurrent_ppo, name)
     if name in ("PPOPopulation", "Population"):
         from . import population
         return getattr(population, name)

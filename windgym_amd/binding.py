@@ -43,6 +43,8 @@ ABI_SYMBOLS = (
     "wg_norm_create", "wg_norm_destroy", "wg_norm_get_state", "wg_norm_set_state", "wg_norm_set_training", "wg_norm_reset_returns",
     "wg_norm_obs", "wg_norm_reward", "wg_rollout_norm",
     "wg_lstm_create", "wg_lstm_destroy", "wg_lstm_n_params", "wg_lstm_set_params", "wg_lstm_step", "wg_lstm_act", "wg_rollout_lstm",
+    "wg_lstm_ppo_create", "wg_lstm_ppo_destroy", "wg_lstm_ppo_n_params", "wg_lstm_ppo_get_state", "wg_lstm_ppo_set_state",
+    "wg_lstm_ppo_grad", "wg_lstm_ppo_apply", "wg_lstm_ppo_update",
 )
 
 _lib = None
@@ -109,6 +111,12 @@ class CRolloutLstmBufs(C.Structure):
 
 
 LSTM_ACTOR, LSTM_CRITIC = 1, 2          # WG_LSTM_ACTOR / WG_LSTM_CRITIC
+class CLstmPpoBatch(C.Structure):
+    """wg_lstm_ppo_batch"""
+    _fields_ = [("obs", C.c_void_p), ("raw", C.c_void_p), ("logp", C.c_void_p), ("advantage", C.c_void_p), ("returns", C.c_void_p),
+                ("episode_start", C.c_void_p), ("lstm_state0", C.c_void_p), ("T", C.c_int32), ("B", C.c_int32)]
+
+
 PPO_STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss", "adv_mean", "adv_std")   # wg_ppo_stats
 
 
@@ -232,6 +240,16 @@ def load_library():
     L.wg_lstm_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
     L.wg_rollout_lstm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
                                   C.POINTER(CRolloutBufs), C.POINTER(CRolloutLstmBufs), C.c_void_p]
+    L.wg_lstm_ppo_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_lstm_ppo_destroy.argtypes = [C.c_void_p]
+    L.wg_lstm_ppo_n_params.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.wg_lstm_ppo_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.wg_lstm_ppo_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]
+    L.wg_lstm_ppo_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.POINTER(CPpoHyper),
+                                   C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_lstm_ppo_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    L.wg_lstm_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.c_int,
+                                     C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -52,6 +52,15 @@ int wg_pop_store_(void* dst_dev, const void* src_host, size_t bytes, void* strea
 int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const WgPopRows* r,
                     void* stream);
 int wg_pop_launch_(wg_pop q, int head, int fin, int t, int deterministic, uint64_t counter, void* stream);
+// wg_ppo.hip, for the recurrent trainer (wg_lstm_ppo.hip).  The heads: k_ppo_grad's loss on n rows whose actor reads h_pi [n][H] and
+// whose critic reads h_vf [n][H], raw / logp / adv / ret indexed by the same row -> the MLP's flat gradient, the stats record and the
+// gradients of the rows, dh_pi / dh_vf [n][H] (k_ppo_grad_dh).  Adam: clipping by the global norm of grad_dev [n_flat] and step number
+// `step` of Adam with wg_ppo.hip's constants on params_dev in place (k_ppo_sumsq + k_ppo_adam; blocksq: ceil(n_flat / 256) floats)
+int wg_ppo_heads_grad_(wg_ppo o, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw, const float* logp,
+                       const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi, float* dh_vf, float* grad_out,
+                       float* stats_out, void* stream);
+int wg_ppo_adam_(float* params_dev, const float* grad_dev, float* m, float* v, uint32_t n_flat, float* blocksq, uint64_t step, float lr,
+                 float max_grad_norm, void* stream);
 // k_policy_pack for each of the n_members rows of a member table (device)
 void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_members, void* stream);
 // wg_flow.hip

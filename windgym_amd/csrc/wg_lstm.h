@@ -66,6 +66,11 @@ inline void wgl_fill_layout(WgLstmP& P, const wg_lstm_desc* d) {
     P.n_flat = flat; P.n_packed = packed + WGP_SLACK;
 }
 
+#ifdef __HIPCC__
+// the cell's sigmoid, one statement of it for k_lstm and the sequence kernels of wg_lstm_ppo.hip
+__device__ __forceinline__ float wgl_sigmoid(const float z) { return 1.0f / (1.0f + expf(-z)); }
+#endif
+
 struct wg_lstm_s {
     WgLstmP P;
     WgPacked w;                // [P.n_flat] / [P.n_packed]

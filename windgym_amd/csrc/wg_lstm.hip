@@ -18,8 +18,6 @@
 #include "wg_lstm.h"
 #include "wg_host.h"
 
-__device__ __forceinline__ float wgl_sigmoid(const float z) { return 1.0f / (1.0f + expf(-z)); }
-
 // grid (tiles of 32 rows, nets evaluated): net = net0 + blockIdx.y.  state_in / state_out [net][h | c][n_rows][H] (state_out may be
 // state_in: a workgroup has read every h it needs before its first store, and a (row, unit)'s c is read and written by one lane;
 // null: the new state is discarded), h_out[net] [n_rows][H] (null: not wanted).

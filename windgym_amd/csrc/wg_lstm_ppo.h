@@ -1,0 +1,66 @@
+// wg_lstm_ppo.h — the host object behind the `wg_lstm_ppo` handle and the buffers of the BPTT kernels (wg_lstm_ppo.hip), next to
+// wg_lstm.h, whose model, flat order and packed layout they build on.
+//
+// A minibatch is Bm ENVS, each with all T steps.  Minibatch row (t, j) is env envs[j] at step t; the env tile `tile` holds the rows
+// j = 32 tile .. 32 tile + 31 and NT = ceil(Bm / 32).  BLOCK (t, tile) = t NT + tile.
+//
+// THE STASH (device memory of the handle, sized for the T_max and Bm_max it was created with; NTm = ceil(Bm_max / 32)):
+//     gates [net][T_max NTm][4H][32]   block-major, a block's 32 rows minor: the post-activation gates i, f, g, o of the forward pass
+//                                      at feature q H + unit (torch's row order of [4H]); the backward pass overwrites a block IN
+//                                      PLACE with dz, the gradient of the pre-activations, and with zeros for rows j >= Bm — so the
+//                                      weight-gradient GEMM reads whole blocks with no row mask;
+//     c     [net][T_max NTm][H][32]    c_t, same block layout;
+//     h     [net][T_max Bm_max][H]     h_t row-major, row t Bm + j: the input rows of the heads, and h_{t-1} of the weight gradient;
+//     dh    [2][T_max Bm_max][H]       d loss / d h rows from the actor's and the critic's head (k_ppo_grad_dh);
+//     raw, logp, adv, ret              the minibatch's rows of the rollout gathered into row order t Bm + j.
+// Floats: nets (5 H) 32 T_max NTm + (nets + 2) H T_max Bm_max + (n_out + 3) T_max Bm_max; with T = 128, Bm = 1024, H = 256 and two nets
+// that is 1.9 GB.  A handle whose stash would exceed WGLP_STASH_BYTES is refused by name.
+//
+// THE TRANSPOSED PACKED BLOCK (written by k_lstm_ppo_pack from the flat parameters at the head of every gradient): the recurrent
+// term W_hh^T dz is a GEMM with M = H, K = 4H, so its A operand is a weight block of wg_tile.h over nksT = wg_tile_nks(4H) k-steps
+// with row(tile, j) = hidden unit 32 tile + j and k = the row i of W_hh in torch's order:
+//     WhhT[net][tile][ks][lane] = W_hh[2 ks + (lane >> 5)][32 tile + (lane & 31)]         (0 for units >= H and rows >= 4H),
+// nets back to back, WGP_SLACK zeros behind the last.
+#ifndef WG_LSTM_PPO_H
+#define WG_LSTM_PPO_H
+#include <stdint.h>
+
+#include "wg_lstm.h"
+#include "wg_ppo.h"
+
+#define WGLP_STASH_BYTES (16ull << 30)     // most bytes of stash a handle may ask for
+#define WGLP_ROWS_MAX (1 << 24)            // most rows T_max * Bm_max of a minibatch
+#define WGLP_SPLIT 8                       // most splits of the weight gradient's sum over the blocks: part[WGLP_SPLIT][n_lstm] floats, at
+                                           // the policy's limits (two nets, n_in = 2048, H = 256) 151 MB — under wg_ppo.h's WGT_PART_BYTES
+
+// what the three sequence kernels share (by value)
+struct WgLstmSeq {
+    const float* obs;          // [T][B][n_in]
+    const uint8_t* start;      // [T (+ 1)][B]
+    const float* state0;       // [nets][2][B][H]
+    const int32_t* envs;       // [Bm] env of minibatch column j; an entry outside [0, B) is a column of zeros
+    int32_t T, B, Bm, NT, shared;
+    float *gates, *c, *h;      // the stash
+    size_t net_gates, net_c, net_h;        // floats from one net to the next
+    const float* dh[2];        // [T Bm][H] from the actor's / the critic's head
+    const float* whhT;         // the transposed packed blocks
+    uint32_t whhT_net;         // floats of one net's block
+    int32_t nksT;
+};
+
+struct wg_lstm_ppo_s {
+    wg_lstm_s* lstm;
+    wg_policy_s* pol;
+    wg_ppo_s* heads;           // the MLP's gradient kernel and its scratch (its own Adam state is not used)
+    int device, T_max, Bm_max, NT_max;
+    uint32_t n_lstm, n_flat, n_blocks;
+    uint64_t step;             // Adam's step count
+    float *m, *v, *grad, *blocksq, *stats;
+    float *gates, *c, *h, *dh, *rows;      // the stash; rows = raw | logp | adv | ret
+    float* whhT;
+    float* wpart;              // [WGLP_SPLIT][n_lstm] the weight gradient's partial sums
+    uint32_t whhT_net, whhT_all;
+    int32_t nksT;
+};
+
+#endif

@@ -1,0 +1,529 @@
+// wg_lstm_ppo.hip — training recurrent policies on the device: backpropagation through time over one rollout of wg_rollout_lstm, for
+// the LSTMs of wg_lstm.hip in front of the MLP heads of wg_policy.hip, and the wg_lstm_ppo_* entries of include/windgym_hip.h
+// (wg_lstm_ppo.h states the stash and the transposed packed block).
+//
+// THE RULE.  A minibatch is Bm envs with all T steps of each; row (t, j) is env envs[j] at step t, n = T Bm rows.
+//   forward    per net, (h, c)_{-1} = lstm_state0[net][., env] — data, not a function of the parameters; for t = 0 .. T-1:
+//                  (h, c) <- (0, 0) where episode_start[t][env] != 0            (wg_lstm.h's SELECT: such a row reads no state)
+//                  z = (b_ih + b_hh) + [W_ih | W_hh] (x_t ‖ h),  c_t = s(z_f) c + s(z_i) tanh(z_g),  h_t = s(z_o) tanh(c_t)
+//   heads      k_ppo_grad's loss, unchanged, on the n rows with obs[0] = the actor LSTM's h rows and obs[1] = the critic LSTM's (the
+//              same rows when the LSTM is shared), normalize_advantage over the minibatch's n rows; it returns the MLP's gradient,
+//              the 8-float stats record and dH = W0^T dZ0 per head and row (k_ppo_grad_dh)
+//   backward   for t = T-1 .. 0:   dh_t = dH[t] (shared LSTM: the actor head's + the critic head's, in that order) + W_hh^T dz_{t+1},
+//                  the recurrent term and the carried dc dropped where episode_start[t+1] != 0: the gradient stops there;
+//                  do = dh tanh(c_t),  dc = dc_carry + dh o (1 - tanh^2 c_t),  di = dc g,  dg = dc i,  df = dc c_{t-1},  dc_carry = dc f,
+//                  dz = (di i (1 - i), df f (1 - f), dg (1 - g^2), do o (1 - o))
+//   weights    dWcat[4H][n_in + H] = sum over rows in the order t, j of dz ⊗ (x_t ‖ select(start_t, 0, h_{t-1})),  db_ih = db_hh = sum dz
+//   gradient   flat: the LSTM tensors, then the MLP's (the entropy constant on log_std included), recurrent.param_layout's order.
+// Every sum has an order fixed by T, Bm and the shapes: no atomics, the same bits from run to run.
+//
+// k_lstm_seq_fwd / k_lstm_seq_bwd: one workgroup of 4 waves owns 32 env columns of ONE net (blockIdx.y) for the WHOLE sequence — the
+// time loop is inside the kernel.  Forward is k_lstm's step (one GEMM on wg_tile.h, the four gates of a unit in one lane) with h in
+// LDS and c in registers between steps.  Backward keeps dc in registers and the recurrent term in LDS, does the cell's backward
+// element-wise, and runs W_hh^T dz as a GEMM over the transposed packed block with dz staged through LDS in chunks of 256 (dz of a
+// tile is 128 KB at H = 256).  Both: 64 KB of LDS.  k_lstm_wgrad: output-stationary, a workgroup owns 128 rows x 32 columns of dWcat
+// and walks the blocks of its split in index order; at most WGLP_SPLIT rows of partials, added in order by k_lstm_wgrad_reduce.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <string>
+
+#include "../../include/windgym_hip.h"
+#include "wg_lstm_ppo.h"
+#include "wg_host.h"
+
+// the env of minibatch column j, -1: none (j >= Bm or an entry outside the rollout)
+__device__ __forceinline__ int wglp_env(const WgLstmSeq& q, const int j) {
+    if (j >= q.Bm) return -1;
+    const int e = q.envs[j];
+    return (e < 0 || e >= q.B) ? -1 : e;
+}
+
+// grid (NT, nets)
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd(const WgLstmP P, const float* __restrict__ packed, const WgLstmSeq q) {
+    __shared__ float lds[WGP_KC * WGP_TILE];
+    __shared__ float hbuf[WGL_MAX_H * WGP_TILE];           // h_{t-1} as [unit][32 columns]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+    const int net = blockIdx.y, tile = blockIdx.x;
+    const int H = P.H, n_in = P.n_in, K = P.K, H4 = 4 * P.H;
+    const WgLstmNet nt = P.net[net];
+    const int j = tile * WGP_TILE + r, env = wglp_env(q, j);
+    const bool valid = env >= 0;
+    const float* h0 = q.state0 + (size_t)net * 2 * q.B * H;
+    const float* c0 = h0 + (size_t)q.B * H;
+    for (int unit = tid >> 5; unit < H; unit += 2 * WGP_WAVES) hbuf[unit * WGP_TILE + r] = valid ? h0[(size_t)env * H + unit] : 0.0f;
+    float creg[2][16];
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+        const int ub = wave + WGP_WAVES * t2;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int unit = 32 * ub + wg_tile_drow(g, hh);
+            creg[t2][g] = (valid && unit < H) ? c0[(size_t)env * H + unit] : 0.0f;
+        }
+    }
+    const float* xb = lds + hh * WGP_TILE + r;
+    float* gates = q.gates + (size_t)net * q.net_gates;
+    float* cst = q.c + (size_t)net * q.net_c;
+    float* hst = q.h + (size_t)net * q.net_h;
+
+    for (int t = 0; t < q.T; ++t) {
+        const bool fresh = valid && q.start[(size_t)t * q.B + env] != 0;
+        const float* xrow = q.obs + ((size_t)t * q.B + (valid ? env : 0)) * n_in;
+        f32x16 acc[2][4];
+        // (the offset is opaque per step, so that the 128 bias loads stay inside the step instead of being hoisted out of the time
+        // loop and held in registers across it)
+        uint32_t b_off = nt.b_packed;
+        asm volatile("" : "+v"(b_off));
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            const int ub = wave + WGP_WAVES * t2;
+            if (ub < P.nub) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) wg_tile_bias(acc[t2][g], packed + b_off + (4 * ub + g) * 32, hh);
+            }
+        }
+        for (int k0 = 0; k0 < K; k0 += WGP_KC) {
+            const int kc = min(WGP_KC, K - k0), kcp = wg_tile_kpad(kc);
+            // x_t ‖ h_{t-1} -> LDS: columns without an env, the pad behind kc and the h of a fresh row are zeros
+            wg_tile_stage(lds, tid, kcp, [&](const int k) {
+                const int kk = k0 + k;
+                float v = 0.0f;
+                if (valid && k < kc) {
+                    if (kk < n_in) v = xrow[kk];
+                    else if (!fresh) v = hbuf[(kk - n_in) * WGP_TILE + r];
+                }
+                return v;
+            });
+#pragma unroll
+            for (int t2 = 0; t2 < 2; ++t2) {
+                const int ub = wave + WGP_WAVES * t2;
+                if (ub < P.nub) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        wg_tile_gemm(acc[t2][g], packed + nt.w_packed + ((size_t)(4 * ub + g) * P.nks + (k0 >> 1)) * 64 + lane, xb, kcp >> 1);
+                }
+            }
+        }
+        // the cell, in the lane that holds the unit's four gates; every column of the tile is written (one without an env ran on zeros).
+        // (The lane's column is made opaque per step and every address is a uniform base + a 32-bit offset: left to itself the compiler
+        // keeps one 64-bit pointer per store of the unrolled loop alive across the time loop, about 200 of them, and spills.)
+        const size_t blk = (size_t)t * q.NT + tile;
+        float* G = gates + blk * H4 * WGP_TILE;
+        float* Cs = cst + blk * H * WGP_TILE;
+        float* hr = hst + (size_t)t * q.Bm * H;
+        uint32_t ro = r;
+        asm volatile("" : "+v"(ro));
+        const uint32_t jo = (uint32_t)tile * WGP_TILE + ro, HT = (uint32_t)H * WGP_TILE;
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            const int ub = wave + WGP_WAVES * t2;
+            if (ub < P.nub) {
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int unit = 32 * ub + wg_tile_drow(g, hh);
+                    if (unit < H) {
+                        const float c = fresh ? 0.0f : creg[t2][g];
+                        const float gi = wgl_sigmoid(acc[t2][0][g]), gf = wgl_sigmoid(acc[t2][1][g]), gg = tanhf(acc[t2][2][g]),
+                                    go = wgl_sigmoid(acc[t2][3][g]);
+                        const float cn = gf * c + gi * gg;
+                        const float hn = go * tanhf(cn);
+                        const uint32_t o = (uint32_t)unit * WGP_TILE + ro;
+                        G[o] = gi;
+                        G[HT + o] = gf;
+                        G[2 * HT + o] = gg;
+                        G[3 * HT + o] = go;
+                        Cs[o] = cn;
+                        if (valid) hr[jo * (uint32_t)H + unit] = hn;
+                        hbuf[o] = hn;                          // (read again only behind the next step's barrier)
+                        creg[t2][g] = cn;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// grid (NT, nets).  Thread (r = tid & 31, u = tid >> 5) owns the units u, u + 8, ... of column r at every step: its dc never leaves
+// its registers.
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd(const WgLstmP P, const WgLstmSeq q) {
+    __shared__ float lds[WGP_KC * WGP_TILE];
+    __shared__ float rec[WGL_MAX_H * WGP_TILE];            // W_hh^T dz_{t+1} as [unit][32 columns]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5, u0 = tid >> 5;
+    const int net = blockIdx.y, tile = blockIdx.x;
+    const int H = P.H, H4 = 4 * P.H;
+    const int j = tile * WGP_TILE + r, env = wglp_env(q, j);
+    const bool valid = env >= 0;
+    const float* c0 = q.state0 + ((size_t)net * 2 + 1) * q.B * H;
+    float* gates = q.gates + (size_t)net * q.net_gates;
+    const float* cst = q.c + (size_t)net * q.net_c;
+    const float* dh0 = q.dh[net];
+    const float* dh1 = q.shared ? q.dh[1] : nullptr;
+    const float* wT = q.whhT + (size_t)net * q.whhT_net;
+    const float* xb = lds + hh * WGP_TILE + r;
+    float dc[WGL_MAX_H / 8];
+#pragma unroll
+    for (int m = 0; m < WGL_MAX_H / 8; ++m) dc[m] = 0.0f;
+    bool cut = true;                                       // no recurrent term reaches this step (the last step; a fresh step behind it)
+
+    for (int t = q.T - 1; t >= 0; --t) {
+        const bool fresh = valid && q.start[(size_t)t * q.B + env] != 0;
+        const size_t blk = (size_t)t * q.NT + tile;
+        float* G = gates + blk * H4 * WGP_TILE;
+        const float* Cs = cst + blk * H * WGP_TILE;
+        const float* Cp = t > 0 ? cst + (blk - q.NT) * H * WGP_TILE : Cs;   // c_{t-1} (t = 0: c0 instead)
+        const size_t row = (size_t)t * q.Bm + j;
+        __syncthreads();                                   // rec of step t + 1 is complete
+#pragma unroll
+        for (int m = 0; m < WGL_MAX_H / 8; ++m) {
+            const int unit = u0 + 8 * m;
+            if (unit < H) {
+                const size_t o = (size_t)unit * WGP_TILE + r;
+                float zi = 0.0f, zf = 0.0f, zg = 0.0f, zo = 0.0f;
+                if (valid) {
+                    float dh = dh0[row * H + unit];
+                    if (dh1) dh += dh1[row * H + unit];
+                    if (!cut) dh += rec[o];
+                    const float gi = G[o], gf = G[(size_t)H * WGP_TILE + o], gg = G[(size_t)2 * H * WGP_TILE + o], go = G[(size_t)3 * H * WGP_TILE + o];
+                    const float cp = fresh ? 0.0f : (t > 0 ? Cp[o] : c0[(size_t)env * H + unit]);
+                    const float tc = tanhf(Cs[o]);
+                    const float d_o = dh * tc;
+                    const float dct = dc[m] + dh * go * (1.0f - tc * tc);
+                    zi = dct * gg * gi * (1.0f - gi);
+                    zf = dct * cp * gf * (1.0f - gf);
+                    zg = dct * gi * (1.0f - gg * gg);
+                    zo = d_o * go * (1.0f - go);
+                    dc[m] = fresh ? 0.0f : dct * gf;
+                }
+                G[o] = zi; G[(size_t)H * WGP_TILE + o] = zf; G[(size_t)2 * H * WGP_TILE + o] = zg; G[(size_t)3 * H * WGP_TILE + o] = zo;
+            }
+        }
+        cut = fresh;
+        if (t == 0) break;
+        // rec = W_hh^T dz_t: M = H (wave w: unit tiles w and w + 4), K = 4H through LDS in chunks (the stage's barrier orders the
+        // block's stores above before its loads)
+        f32x16 acc[2];
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) acc[t2][g] = 0.0f;
+        for (int k0 = 0; k0 < H4; k0 += WGP_KC) {
+            const int kc = min(WGP_KC, H4 - k0), kcp = wg_tile_kpad(kc);
+            wg_tile_stage(lds, tid, kcp, [&](const int k) { return k < kc ? G[(size_t)(k0 + k) * WGP_TILE + r] : 0.0f; });
+#pragma unroll
+            for (int t2 = 0; t2 < 2; ++t2) {
+                const int ot = wave + WGP_WAVES * t2;
+                if (ot < P.nub) wg_tile_gemm(acc[t2], wT + ((size_t)ot * q.nksT + (k0 >> 1)) * 64 + lane, xb, kcp >> 1);
+            }
+        }
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            const int ot = wave + WGP_WAVES * t2;
+            if (ot < P.nub) {
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int unit = 32 * ot + wg_tile_drow(g, hh);
+                    if (unit < H) rec[unit * WGP_TILE + r] = acc[t2][g];
+                }
+            }
+        }
+    }
+}
+
+// grid (ceil(K / 32), ceil(4H / 128), nets * S): wave w of workgroup (kt, it) owns rows 128 it + 32 w .. + 31, columns 32 kt .. + 31
+// of dWcat and sums over its SPLIT's blocks in index order, 32 rows per block on v_mfma_f32_32x32x2_f32 (A = dz, B = xcat, both from
+// LDS with a row stride of 33 floats).  The workgroups kt = 0 also sum the biases.  Split sp of S = min(WGLP_SPLIT, T NT) takes the
+// blocks [sp per, (sp + 1) per), per = ceil(T NT / S), and writes row sp of part[S][n_lstm] (the LSTM's flat layout);
+// k_lstm_wgrad_reduce adds the rows in index order.  S and per are functions of T and NT alone: the order of every sum is fixed.  One
+// workgroup per output tile alone is latency-bound — two barriers and one round of global loads per 16 MFMAs — and leaves CUs idle;
+// the split is there for workgroups per CU, not for the arithmetic.
+#define WGLP_WI 128
+#define WGLP_S 33
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_wgrad(const WgLstmP P, const WgLstmSeq q, float* __restrict__ part, const int S) {
+    __shared__ float ds[WGLP_WI * WGLP_S];
+    __shared__ float xs[32 * WGLP_S];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+    const int kt = blockIdx.x, i0 = blockIdx.y * WGLP_WI, net = blockIdx.z / S, sp = blockIdx.z - net * S;
+    const int H = P.H, n_in = P.n_in, K = P.K, H4 = 4 * P.H;
+    const WgLstmNet nt = P.net[net];
+    float* __restrict__ grad = part + (size_t)sp * P.n_flat;
+    const float* gates = q.gates + (size_t)net * q.net_gates;
+    const float* hst = q.h + (size_t)net * q.net_h;
+    const float* h0 = q.state0 + (size_t)net * 2 * q.B * H;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    float db = 0.0f;
+    const int nblk = q.T * q.NT, per = (nblk + S - 1) / S;
+    const int blk1 = min(nblk, (sp + 1) * per);
+    for (int blk = sp * per; blk < blk1; ++blk) {
+        const int t = blk / q.NT, tile = blk - t * q.NT;
+        const float* G = gates + (size_t)blk * H4 * WGP_TILE;
+        __syncthreads();
+        for (int idx = tid; idx < WGLP_WI * 32; idx += WGP_WAVES * 64) {
+            const int il = idx >> 5, row = idx & 31, i = i0 + il;
+            ds[il * WGLP_S + row] = i < H4 ? G[(size_t)i * WGP_TILE + row] : 0.0f;
+        }
+        for (int idx = tid; idx < 32 * 32; idx += WGP_WAVES * 64) {     // consecutive threads: consecutive inputs of a row
+            const int row = idx >> 5, kl = idx & 31, kk = kt * 32 + kl, j = tile * WGP_TILE + row;
+            const int env = wglp_env(q, j);
+            float v = 0.0f;
+            if (env >= 0 && kk < K) {
+                if (kk < n_in) v = q.obs[((size_t)t * q.B + env) * n_in + kk];
+                else if (q.start[(size_t)t * q.B + env] == 0)
+                    v = t > 0 ? hst[((size_t)(t - 1) * q.Bm + j) * H + (kk - n_in)] : h0[(size_t)env * H + (kk - n_in)];
+            }
+            xs[kl * WGLP_S + row] = v;
+        }
+        __syncthreads();
+        if (kt == 0 && tid < WGLP_WI) {
+            for (int row = 0; row < 32; ++row) db += ds[tid * WGLP_S + row];
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int row = 2 * s + hh;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ds[(wave * 32 + r) * WGLP_S + row], xs[r * WGLP_S + row], acc, 0, 0, 0);
+        }
+    }
+    const int k = kt * 32 + r;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int i = i0 + wave * 32 + wg_tile_drow(e, hh);
+        if (i < H4 && k < K) {
+            if (k < n_in) grad[nt.wih_flat + (size_t)i * n_in + k] = acc[e];
+            else grad[nt.whh_flat + (size_t)i * H + (k - n_in)] = acc[e];
+        }
+    }
+    if (kt == 0 && tid < WGLP_WI && i0 + tid < H4) {
+        grad[nt.bih_flat + i0 + tid] = db;
+        grad[nt.bhh_flat + i0 + tid] = db;
+    }
+}
+
+// the splits' rows -> the LSTM's entries of the flat gradient, added in index order
+__global__ void k_lstm_wgrad_reduce(const float* __restrict__ part, const uint32_t n, const int S, float* __restrict__ grad) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    float s = part[p];
+    for (int g = 1; g < S; ++g) s += part[(size_t)g * n + p];
+    grad[p] = s;
+}
+
+// flat -> the transposed packed blocks (wg_lstm_ppo.h); one thread per float, the slack included
+__global__ void k_lstm_ppo_pack(const WgLstmP P, const float* __restrict__ flat, float* __restrict__ whhT, const uint32_t per_net,
+                                const uint32_t total, const uint32_t nksT) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t net = idx / per_net;
+    float v = 0.0f;
+    if (net < (uint32_t)P.n_nets) {
+        const WgTileElem e = wg_tile_decode(idx - net * per_net, nksT);
+        const uint32_t unit = 32 * e.tile + e.j;
+        if (unit < (uint32_t)P.H && e.k < 4u * P.H) v = flat[P.net[net].whh_flat + (size_t)e.k * P.H + unit];
+    }
+    whhT[idx] = v;
+}
+
+// the minibatch's rows of raw / logp / advantage / returns [T, B] -> row order t Bm + j (a column without an env: zeros)
+__global__ void k_lstm_ppo_gather(const WgLstmSeq q, const int n_out, const float* __restrict__ raw, const float* __restrict__ logp,
+                                  const float* __restrict__ adv, const float* __restrict__ ret, float* __restrict__ raw_o,
+                                  float* __restrict__ logp_o, float* __restrict__ adv_o, float* __restrict__ ret_o) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= q.T * q.Bm) return;
+    const int t = row / q.Bm, j = row - t * q.Bm, env = wglp_env(q, j);
+    const size_t src = (size_t)t * q.B + (env >= 0 ? env : 0);
+    logp_o[row] = env >= 0 ? logp[src] : 0.0f;
+    adv_o[row] = env >= 0 ? adv[src] : 0.0f;
+    ret_o[row] = env >= 0 ? ret[src] : 0.0f;
+    for (int a = 0; a < n_out; ++a) raw_o[(size_t)row * n_out + a] = env >= 0 ? raw[src * n_out + a] : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max, wg_lstm_ppo* out) {
+    if (!l || !p || !out) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_create: null argument");
+    *out = nullptr;
+    const WgLstmP& L = l->P;
+    if (p->P.n_in != L.H || p->P.n_layers[1] == 0 || p->P.n_in_vf != L.H)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_create: p must map the LSTM's hidden size (" + std::to_string(L.H) +
+                                         ") with its critic on the same width; it maps " + std::to_string(p->P.n_in) + " inputs, its critic " +
+                                         std::to_string(p->P.n_layers[1] ? p->P.n_in_vf : 0));
+    if (p->w.device != l->w.device) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_create: lstm and policy live on different devices");
+    if (T_max < 1 || Bm_max < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_create: T_max and Bm_max must be >= 1");
+    const size_t NT = ((size_t)Bm_max + WGP_TILE - 1) / WGP_TILE, n_max = (size_t)T_max * Bm_max, npad = (size_t)T_max * NT * WGP_TILE;
+    const size_t H = L.H, nets = L.n_nets, n_out = p->P.n_out;
+    const size_t f_gates = nets * npad * 4 * H, f_c = nets * npad * H, f_h = nets * n_max * H, f_dh = 2 * n_max * H, f_rows = n_max * (n_out + 3);
+    if ((size_t)T_max > WGLP_ROWS_MAX || (size_t)Bm_max > WGLP_ROWS_MAX || n_max > WGLP_ROWS_MAX ||
+        sizeof(float) * (f_gates + f_c + f_h + f_dh + f_rows) > WGLP_STASH_BYTES)
+        return wg_fail(WG_ERR_UNSUPPORTED, "wg_lstm_ppo_create: T_max = " + std::to_string(T_max) + " steps of Bm_max = " + std::to_string(Bm_max) +
+                                             " envs need a stash of " + std::to_string(sizeof(float) * (f_gates + f_c + f_h + f_dh + f_rows)) +
+                                             " bytes; the limits are " + std::to_string(WGLP_STASH_BYTES) + " bytes and " +
+                                             std::to_string(WGLP_ROWS_MAX) + " rows per minibatch");
+    wg_ppo heads = nullptr;
+    if (int rc = wg_ppo_create(p, &heads)) return rc;
+    wg_lstm_ppo_s* o = new (std::nothrow) wg_lstm_ppo_s();
+    if (!o) {
+        wg_ppo_destroy(heads);
+        return wg_fail(WG_ERR_NOMEM, "wg_lstm_ppo_create: out of host memory");
+    }
+    o->lstm = l; o->pol = p; o->heads = heads;
+    o->device = l->w.device; o->T_max = T_max; o->Bm_max = Bm_max; o->NT_max = (int)NT;
+    o->n_lstm = L.n_flat; o->n_flat = L.n_flat + p->P.n_flat;
+    o->n_blocks = (o->n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    o->nksT = wg_tile_nks(4 * L.H);
+    o->whhT_net = wg_tile_wsize(L.nub, o->nksT);
+    o->whhT_all = o->whhT_net * L.n_nets + WGP_SLACK;
+    const size_t nf = sizeof(float) * (size_t)o->n_flat;
+    hipError_t e = hipSetDevice(o->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->m, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->v, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->grad, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->blocksq, sizeof(float) * o->n_blocks);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->stats, sizeof(float) * WGT_NSTAT);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->gates, sizeof(float) * f_gates);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->c, sizeof(float) * f_c);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->h, sizeof(float) * f_h);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dh, sizeof(float) * f_dh);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->rows, sizeof(float) * f_rows);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->whhT, sizeof(float) * o->whhT_all);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->wpart, sizeof(float) * (size_t)WGLP_SPLIT * o->n_lstm);
+    if (e == hipSuccess) e = hipMemset(o->m, 0, nf);
+    if (e == hipSuccess) e = hipMemset(o->v, 0, nf);
+    if (e != hipSuccess) {
+        wg_lstm_ppo_destroy(o);
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_lstm_ppo_create: ") + hipGetErrorString(e));
+    }
+    *out = o;
+    return 0;
+}
+
+extern "C" int wg_lstm_ppo_destroy(wg_lstm_ppo o) {
+    if (!o) return 0;
+    if (hipSetDevice(o->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        float* bufs[] = {o->m, o->v, o->grad, o->blocksq, o->stats, o->gates, o->c, o->h, o->dh, o->rows, o->whhT, o->wpart};
+        for (float* b : bufs)
+            if (b) (void)hipFree(b);
+    }
+    wg_ppo_destroy(o->heads);
+    delete o;
+    return 0;
+}
+
+extern "C" int wg_lstm_ppo_n_params(wg_lstm_ppo o, size_t* n) {
+    if (!o || !n) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_n_params: null argument");
+    *n = o->n_flat;
+    return 0;
+}
+
+extern "C" int wg_lstm_ppo_get_state(wg_lstm_ppo o, float* mv_host, size_t n, uint64_t* step) {
+    if (!o || !mv_host || !step) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_get_state: null argument");
+    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_get_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
+    if (int rc = wg_use_device(o->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipMemcpy(mv_host, o->m, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy(mv_host + o->n_flat, o->v, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
+    *step = o->step;
+    return 0;
+}
+
+extern "C" int wg_lstm_ppo_set_state(wg_lstm_ppo o, const float* mv_host, size_t n, uint64_t step) {
+    if (!o || !mv_host) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_set_state: null argument");
+    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_set_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
+    if (int rc = wg_use_device(o->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipMemcpy(o->m, mv_host, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(o->v, mv_host + o->n_flat, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
+    o->step = step;
+    return 0;
+}
+
+// what grad and update check of a batch and the hyper-parameters; `who` names the entry
+static int lp_check(const std::string& who, wg_lstm_ppo o, const wg_lstm_ppo_batch* b, const wg_ppo_hyper* hp, int n_envs) {
+    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !b->episode_start || !b->lstm_state0)
+        return wg_fail(WG_ERR_INVALID, who + ": a batch pointer is null");
+    if (b->T < 1 || b->B < 1) return wg_fail(WG_ERR_INVALID, who + ": T and B must be >= 1");
+    if (n_envs < 1) return wg_fail(WG_ERR_INVALID, who + ": a minibatch has at least one env");
+    if (b->T > o->T_max)
+        return wg_fail(WG_ERR_UNSUPPORTED, who + ": T = " + std::to_string(b->T) + " > the T_max = " + std::to_string(o->T_max) + " the handle was created for");
+    if (n_envs > o->Bm_max)
+        return wg_fail(WG_ERR_UNSUPPORTED, who + ": " + std::to_string(n_envs) + " envs in a minibatch > the Bm_max = " + std::to_string(o->Bm_max) +
+                                             " the handle was created for");
+    if ((long long)b->T * b->B > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, who + ": more than 2^31 rows T * B");
+    if (!(hp->clip_range >= 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": clip_range < 0");
+    return 0;
+}
+
+// the launches of one gradient, no argument checks
+static int lp_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_batch* b, const int32_t* envs_dev, int Bm, const wg_ppo_hyper* hp,
+                   float* grad_out, float* stats_out, hipStream_t st) {
+    const WgLstmP& L = o->lstm->P;
+    const int T = b->T, n = T * Bm, n_out = o->pol->P.n_out;
+    const size_t n_max = (size_t)o->T_max * o->Bm_max, npad = (size_t)o->T_max * o->NT_max * WGP_TILE, H = L.H;
+    WgLstmSeq q = {};
+    q.obs = b->obs; q.start = b->episode_start; q.state0 = b->lstm_state0; q.envs = envs_dev;
+    q.T = T; q.B = b->B; q.Bm = Bm; q.NT = (Bm + WGP_TILE - 1) / WGP_TILE; q.shared = L.n_nets == 1;
+    q.gates = o->gates; q.c = o->c; q.h = o->h;
+    q.net_gates = npad * 4 * H; q.net_c = npad * H; q.net_h = n_max * H;
+    q.dh[0] = o->dh; q.dh[1] = o->dh + n_max * H;
+    q.whhT = o->whhT; q.whhT_net = o->whhT_net; q.nksT = o->nksT;
+    float *raw = o->rows, *logp = raw + n_max * n_out, *adv = logp + n_max, *ret = adv + n_max;
+    hipLaunchKernelGGL(k_lstm_ppo_pack, dim3((o->whhT_all + 255) / 256), dim3(256), 0, st, L, params_dev, o->whhT, o->whhT_net, o->whhT_all,
+                       (uint32_t)o->nksT);
+    hipLaunchKernelGGL(k_lstm_ppo_gather, dim3((n + 255) / 256), dim3(256), 0, st, q, n_out, b->raw, b->logp, b->advantage, b->returns, raw, logp,
+                       adv, ret);
+    hipLaunchKernelGGL(k_lstm_seq_fwd, dim3(q.NT, L.n_nets), dim3(WGP_WAVES * 64), 0, st, L, o->lstm->w.packed, q);
+    WG_HIPCHK(hipGetLastError());
+    if (int rc = wg_ppo_heads_grad_(o->heads, params_dev + o->n_lstm, o->h, o->h + (size_t)(L.n_nets - 1) * q.net_h, raw, logp, adv, ret, n, hp,
+                                    o->dh, o->dh + n_max * H, grad_out + o->n_lstm, stats_out ? stats_out : o->stats, (void*)st))
+        return rc;
+    hipLaunchKernelGGL(k_lstm_seq_bwd, dim3(q.NT, L.n_nets), dim3(WGP_WAVES * 64), 0, st, L, q);
+    const int nblk = T * q.NT, S = nblk < WGLP_SPLIT ? nblk : WGLP_SPLIT;
+    hipLaunchKernelGGL(k_lstm_wgrad, dim3((L.K + 31) / 32, (4 * L.H + WGLP_WI - 1) / WGLP_WI, L.n_nets * S), dim3(WGP_WAVES * 64), 0, st, L, q,
+                       o->wpart, S);
+    hipLaunchKernelGGL(k_lstm_wgrad_reduce, dim3((o->n_lstm + 255) / 256), dim3(256), 0, st, o->wpart, o->n_lstm, S, grad_out);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int lp_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
+    o->step += 1;
+    if (int rc = wg_ppo_adam_(params_dev, grad_dev, o->m, o->v, o->n_flat, o->blocksq, o->step, lr, max_grad_norm, (void*)st)) return rc;
+    if (int rc = wg_lstm_set_params(o->lstm, params_dev, o->n_lstm, 1, (void*)st)) return rc;
+    return wg_policy_set_params(o->pol, params_dev + o->n_lstm, o->n_flat - o->n_lstm, 1, (void*)st);
+}
+
+extern "C" int wg_lstm_ppo_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_batch* b, const int32_t* envs_dev, int n_envs,
+                                const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
+    if (!o || !params_dev || !b || !envs_dev || !hp || !grad_out) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_grad: null argument");
+    if (int rc = lp_check("wg_lstm_ppo_grad", o, b, hp, n_envs)) return rc;
+    if (int rc = wg_use_device(o->device)) return rc;
+    return lp_grad(o, params_dev, b, envs_dev, n_envs, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+}
+
+extern "C" int wg_lstm_ppo_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream) {
+    if (!o || !params_dev || !grad_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_apply: null argument");
+    if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_apply: max_grad_norm must be > 0");
+    if (int rc = wg_use_device(o->device)) return rc;
+    return lp_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
+}
+
+extern "C" int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
+                                  int envs_per_batch, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out,
+                                  void* stream) {
+    if (!o || !params_dev || !b || !perm_dev || !hp) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_update: null argument");
+    if (n_epochs < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_update: n_epochs must be >= 1");
+    if (int rc = lp_check("wg_lstm_ppo_update", o, b, hp, envs_per_batch)) return rc;
+    if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_update: max_grad_norm must be > 0");
+    if (int rc = wg_use_device(o->device)) return rc;
+    const int B = b->B, n_mb = (B + envs_per_batch - 1) / envs_per_batch;
+    for (int e = 0; e < n_epochs; ++e)
+        for (int k = 0; k < n_mb; ++k) {
+            const int first = k * envs_per_batch, Bm = B - first < envs_per_batch ? B - first : envs_per_batch;
+            float* so = stats_out ? (float*)(stats_out + (size_t)e * n_mb + k) : nullptr;
+            if (int rc = lp_grad(o, params_dev, b, perm_dev + (size_t)e * B + first, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
+            if (int rc = lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream)) return rc;
+        }
+    return 0;
+}

@@ -151,9 +151,14 @@ struct WgPpoArgs {
     const float* advstat;
     float* part;               // [G][n_flat]
     float* spart;              // [G][4]
+    float* dh[2];              // k_ppo_grad_dh only: per net [n_total][the net's input width] d loss / d obs rows (wg_lstm_ppo.hip)
 };
 
 // (`a`: what the launch's workgroups share; the remaining arguments are `a`'s own for one policy, the member's for a population)
+// DH: also the gradient with respect to the net's INPUT rows, dX[row][k] = sum_i W0[i][k] dZ0[i][row], into a.dh[net] — what the
+// LSTMs in front of a recurrent policy's heads backpropagate (each gathered row is written once, by the one tile that holds it).
+// With DH = false the code is what it was before the flag: the same instructions, the same bits.
+template <bool DH>
 __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, const WgPpoArgs& a, const float* a_packed,
                                          const float* a_flat, const int32_t* a_index, const int a_normalize, const float a_clip,
                                          const float a_vf_coef, const float* a_advstat, float* a_part, float* a_spart) {
@@ -352,10 +357,10 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                     }
                 }
             }
-            // dZ of the layer before: (W^T dZ) * act'(Y)
-            if (l > 0) {
+            // dZ of the layer before: (W^T dZ) * act'(Y); DH: at the first layer W^T dZ itself, the gradient of the gathered rows
+            if (l > 0 || DH) {
                 float* dp = lds + M.d[cur ^ 1];
-                const float* y = lds + M.act[l - 1];
+                const float* y = lds + M.act[l > 0 ? l - 1 : 0];
                 const float* wf = a_flat + ly.w_flat;
                 const int nkt = (ly.K + 31) >> 5, nis = (ly.M + 1) >> 1;
                 for (int kt = wave; kt < nkt; kt += WGT_WAVES) {
@@ -373,8 +378,12 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                     for (int e = 0; e < 16; ++e) {
                         const int k = kt * 32 + wg_tile_drow(e, h);
                         if (k < ly.K && r < R) {
-                            const float yv = y[k * S + r];
-                            dp[k * S + r] = acc[e] * (tanh_act ? 1.0f - yv * yv : (yv > 0.0f ? 1.0f : 0.0f));
+                            if (!DH || l > 0) {
+                                const float yv = y[k * S + r];
+                                dp[k * S + r] = acc[e] * (tanh_act ? 1.0f - yv * yv : (yv > 0.0f ? 1.0f : 0.0f));
+                            } else if (rid[r] >= 0) {
+                                a.dh[net][(size_t)rid[r] * ly.K + k] = acc[e];
+                            }
                         }
                     }
                 }
@@ -391,14 +400,19 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
 }
 
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
-    ppo_grad(P, K, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+    ppo_grad<false>(P, K, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+}
+
+// k_ppo_grad with the input-row gradients (a.dh) as well: the heads of a recurrent policy on the LSTMs' h rows
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_dh(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
+    ppo_grad<true>(P, K, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
 }
 
 // grid (G, 2, P); `c` carries what the members share (the batch, n, G), the member's row the rest
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_pop(const WgPolicyP P, const WgPpoK K, const WgPpoArgs c,
                                                                  const WgPopMember* __restrict__ mt, const int64_t off) {
     const WgPopMember* __restrict__ M = mt + blockIdx.z;
-    ppo_grad(P, K, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+    ppo_grad<false>(P, K, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
 }
 
 // partials -> flat gradient (+ the entropy term's constant gradient on log_std) and the statistics record
@@ -692,8 +706,9 @@ static int t_grid(const wg_ppo_s* o, int n) {
 }
 
 // the launches of one gradient, no argument checks
+// (dh_pi / dh_vf both given: k_ppo_grad_dh, which also writes the gradients of the gathered rows — wg_ppo_heads_grad_)
 static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* sb, const int32_t* index_dev, int64_t first, int n,
-                  const wg_ppo_hyper* hp, float* grad_out, float* stats_out, hipStream_t st) {
+                  const wg_ppo_hyper* hp, float* grad_out, float* stats_out, hipStream_t st, float* dh_pi = nullptr, float* dh_vf = nullptr) {
     const WgPolicyP& P = o->pol->P;
     const wg_ppo_batch* b = &sb->rows;
     const int G = t_grid(o, n);
@@ -703,7 +718,9 @@ static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* 
     a.packed = o->pol->w.packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = sb->obs_vf; a.agents = sb->agents; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
     a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G; a.normalize = normalize;
     a.clip = hp->clip_range; a.vf_coef = hp->vf_coef; a.advstat = o->advstat; a.part = o->part; a.spart = o->spart;
-    hipLaunchKernelGGL(k_ppo_grad, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
+    a.dh[0] = dh_pi; a.dh[1] = dh_vf;
+    if (dh_pi && dh_vf) hipLaunchKernelGGL(k_ppo_grad_dh, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
+    else hipLaunchKernelGGL(k_ppo_grad, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
     hipLaunchKernelGGL(k_ppo_reduce, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, P, o->part, o->spart, G, n, hp->vf_coef,
                        hp->ent_coef, normalize, o->advstat, params_dev, grad_out, stats_out ? stats_out : o->stats);
     WG_HIPCHK(hipGetLastError());
@@ -729,6 +746,26 @@ static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr,
                        o->blocksq, o->n_blocks, max_grad_norm, s.step_size, s.bc2_sqrt, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
     WG_HIPCHK(hipGetLastError());
     return wg_policy_set_params(o->pol, params_dev, o->n_flat, 1, (void*)st);
+}
+
+// wg_internal.h: the heads of a recurrent policy (wg_lstm_ppo.hip)
+extern "C" int wg_ppo_heads_grad_(wg_ppo o, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw,
+                                  const float* logp, const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi,
+                                  float* dh_vf, float* grad_out, float* stats_out, void* stream) {
+    const wg_ppo_batch_shared sb = {{h_pi, raw, logp, adv, ret, n}, h_vf, 1};
+    return t_grad(o, mlp_params_dev, &sb, nullptr, 0, n, hp, grad_out, stats_out, (hipStream_t)stream, dh_pi, dh_vf);
+}
+
+extern "C" int wg_ppo_adam_(float* params_dev, const float* grad_dev, float* m, float* v, uint32_t n_flat, float* blocksq, uint64_t step,
+                            float lr, float max_grad_norm, void* stream) {
+    const double bc1 = 1.0 - std::pow(ADAM_B1, (double)step), bc2 = 1.0 - std::pow(ADAM_B2, (double)step);
+    const uint32_t n_blocks = (n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, n_flat, blocksq);
+    hipLaunchKernelGGL(k_ppo_adam, dim3(n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, m, v, n_flat, blocksq, n_blocks, max_grad_norm,
+                       (float)((double)lr / bc1), (float)std::sqrt(bc2), (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
 }
 
 static int grad_entry(const char* who, wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b, const int32_t* index_dev,

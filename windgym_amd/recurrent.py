@@ -20,9 +20,9 @@ The episode-start mask is a SELECT: such a row does not depend on its incoming s
 sb3-contrib multiplies the state by ``1 - episode_start``; for finite states the two agree.
 
 Not supported, refused by name: ``n_lstm_layers > 1``, the Linear critic of ``enable_critic_lstm=False`` without ``shared_lstm``,
-feature extractors, ``use_sde``.  Limits: ``n_in <= 2048``, ``1 <= H <= 256``.  Inference only: training (backpropagation through
-time) is not built; ``venv.rollout`` records what it will need (``lstm_state0``, ``episode_start``) and ``torch_forward`` is the
-differentiable restatement a trainer goes through.
+feature extractors, ``use_sde``.  Limits: ``n_in <= 2048``, ``1 <= H <= 256``.  Training is ``recurrent_ppo.RecurrentPPO``
+(backpropagation through time in HIP, wg_lstm_ppo.hip) on what ``venv.rollout`` records for it (``lstm_state0``, ``episode_start``);
+``torch_forward`` is the differentiable restatement an eager-torch trainer goes through.
 
 A STATE is one float32 CUDA tensor ``[nets, 2, n, H]`` (per net ``h`` then ``c``; nets = 2, or 1 with ``shared_lstm``) — the layout
 of ``wg_lstm_step``.  Flat parameter order: per LSTM (the actor's first) ``weight_ih_l0 [4H, n_in]``, ``weight_hh_l0 [4H, H]``,
