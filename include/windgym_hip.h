@@ -984,7 +984,10 @@ int wg_lstm_ppo_get_state(wg_lstm_ppo o, float* mv_host, size_t n, uint64_t* ste
 int wg_lstm_ppo_set_state(wg_lstm_ppo o, const float* mv_host, size_t n, uint64_t step);
 
 /* Loss and gradient of ONE minibatch of WHOLE env sequences: the envs envs_dev[0 .. n_envs-1] (int32, device; an entry outside
- * [0, B) counts as rows of zeros and is never dereferenced) with all T steps of each, n = T * n_envs rows.
+ * [0, B) is never dereferenced: the rule below) with all T steps of each, n = T * n_envs rows.
+ *   an entry outside [0, B):  its T rows enter the heads as h = 0 with raw = logp = advantage = returns = 0; they count in n and in
+ *     the advantage statistics like any row, and send no gradient into the LSTM.  The result does not depend on what the handle
+ *     computed before;
  *   forward:  per env and net, (h, c) starts from lstm_state0[net][., env] — DATA, not a function of the parameters — and runs
  *     wg_lstm_step's cell over t = 0 .. T-1 with episode_start[t] as its SELECT (a fresh row reads zeros in place of its state,
  *     also where lstm_state0 holds NaN);

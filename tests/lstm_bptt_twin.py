@@ -13,6 +13,10 @@ The rule, for a minibatch of the envs ``envs`` with ALL ``T`` steps of each (row
     loss = wg_ppo_grad's on the T * len(envs) rows (normalize_advantage: mean / unbiased std of those rows)
 
 The gradient stops at an episode start by construction: ``where`` selects a constant there.
+
+An entry of ``envs`` outside ``[0, B)`` is a column without an env: its ``T`` rows enter the heads as ``h = 0`` with ``raw = logp =
+advantage = returns = 0``; they count in the ``T * len(envs)`` rows of every mean and of the advantage statistics, and send no gradient
+into the LSTM (``where`` selects the constant 0 there too).
 """
 import math
 
@@ -113,14 +117,21 @@ def loss(spec, flat, roll, envs, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, norm
     T = roll["raw"].shape[0]
     envs = torch.as_tensor(np.asarray(envs), dtype=torch.long)
     r = {k: _t(v, dt) for k, v in roll.items()}
+    inside = (envs >= 0) & (envs < roll["raw"].shape[1])
+    if not bool(inside.all()):
+        # a column without an env: evaluated on env 0 so that every index is valid, then replaced by the constant 0 where it is read
+        envs = torch.where(inside, envs, torch.zeros_like(envs))
     p = views(spec, flat)
     hs, _ = unroll(spec, p, r["obs"][:T], r["episode_start"][:T], r["lstm_state0"].detach(), envs)
+    if not bool(inside.all()):
+        hs = [torch.where(inside.reshape(1, -1, 1), h, torch.zeros_like(h)) for h in hs]
     H = spec["H"]
     sel = slice(None) if steps is None else torch.as_tensor(list(steps), dtype=torch.long)
     pick = lambda x: x[sel].reshape((-1,) + tuple(x.shape[2:]))
     mean = _mlp(p, "policy_net", "action_net", pick(hs[0]).reshape(-1, H), spec["activation"])
     V = _mlp(p, "value_net", "value_net", pick(hs[-1]).reshape(-1, H), spec["activation"])[:, 0]
-    raw, lpo, A, ret = (pick(r[k][:, envs]) for k in ("raw", "logp", "advantage", "returns"))
+    rows = lambda x: torch.where(inside.reshape((1, -1) + (1,) * (x.ndim - 2)), x, torch.zeros_like(x))
+    raw, lpo, A, ret = (pick(rows(r[k][:, envs])) for k in ("raw", "logp", "advantage", "returns"))
     ls = p["log_std"]
     z = (raw - mean) / torch.exp(ls)
     logp = (-0.5 * z * z - ls - HALF_LOG_2PI).sum(1)

@@ -14,6 +14,8 @@
 //                  do = dh tanh(c_t),  dc = dc_carry + dh o (1 - tanh^2 c_t),  di = dc g,  dg = dc i,  df = dc c_{t-1},  dc_carry = dc f,
 //                  dz = (di i (1 - i), df f (1 - f), dg (1 - g^2), do o (1 - o))
 //   weights    dWcat[4H][n_in + H] = sum over rows in the order t, j of dz ⊗ (x_t ‖ select(start_t, 0, h_{t-1})),  db_ih = db_hh = sum dz
+//   no env     a column whose envs[j] is outside [0, B): its rows reach the heads as h = 0 with raw = logp = advantage = returns = 0
+//              (k_lstm_seq_fwd stores the zeros, k_lstm_ppo_gather the rest), count in n, and have dz = 0 at every step
 //   gradient   flat: the LSTM tensors, then the MLP's (the entropy constant on log_std included), recurrent.param_layout's order.
 // Every sum has an order fixed by T, Bm and the shapes: no atomics, the same bits from run to run.
 //
@@ -134,7 +136,8 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd(const WgLstmP P
                         G[2 * HT + o] = gg;
                         G[3 * HT + o] = go;
                         Cs[o] = cn;
-                        if (valid) hr[jo * (uint32_t)H + unit] = hn;
+                        // (the heads read all T Bm rows: a column whose entry is outside the rollout is a row of zeros, not the stash's past)
+                        if (jo < (uint32_t)q.Bm) hr[jo * (uint32_t)H + unit] = valid ? hn : 0.0f;
                         hbuf[o] = hn;                          // (read again only behind the next step's barrier)
                         creg[t2][g] = cn;
                     }
