@@ -132,6 +132,86 @@ def test_checkpoint_policy_member_reads_back(tmp_path):
     assert d2 == desc and all(np.array_equal(t2[k], sd[k]) for k in sd)
 
 
+def _fake_checkpoint(path, learning_rate=1e-3, **extra):
+    """write_checkpoint on a fake policy / optimiser / generator (no device) -> what was written, by member"""
+    import torch
+    desc = make_desc(6, 2, (8,), (8,))
+    sd = {k: torch.from_numpy(v) for k, v in sb3_orthogonal_init(desc, 3).items()}
+    pol = type("Pol", (), dict(desc=desc, seed=5, counter=9, state_dict=lambda self: sd))()
+    mv = np.arange(2 * sum(v.numel() for v in sd.values()), dtype=np.float32) * 0.5
+    opt = type("Opt", (), dict(state=lambda self: (mv, 12)))()
+    g = torch.Generator()
+    g.manual_seed(5)
+    hyper = dict(n_steps=16, batch_size=32, n_epochs=3, gamma=0.9, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
+                 max_grad_norm=0.5, learning_rate=learning_rate, normalize_advantage=True)
+    log = [dict(iteration=1, loss=0.5)]
+    from windgym_amd.ppo import write_checkpoint
+    write_checkpoint(path, pol, opt, g, hyper, 5, 384, 3, log, "agent", 48, **extra)
+    return dict(sd=sd, mv=mv, gen=g.get_state().numpy(), hyper=hyper, log=log, desc=desc)
+
+
+def test_checkpoint_round_trip_without_a_device(tmp_path):
+    """write_checkpoint -> read_checkpoint: the JSON, every npy member as the array and every other member as the bytes that went in."""
+    import io
+    import types
+
+    import torch
+
+    from windgym_amd.ppo import read_checkpoint
+    path = str(tmp_path / "a.zip")
+    cur = types.SimpleNamespace(args=lambda: dict(n_passes=2), state=lambda: b"curriculum-blob")
+    vn = types.SimpleNamespace(args=lambda: dict(gamma=0.9), state=lambda: b"\x00norm\xff")
+    state = torch.arange(24, dtype=torch.float32).reshape(2, 2, 3, 2) / 7
+    w = _fake_checkpoint(path, curriculum=cur, normalize=vn, tensors={"lstm_state.npy": state})
+    meta, members = read_checkpoint(path, needs=("lstm_state.npy",))
+    assert set(members) == {"policy.pth", "adam_state.npy", "generator_state.npy", "curriculum_state.bin", "normalize_state.bin",
+                            "lstm_state.npy"}
+    assert members["lstm_state.npy"].dtype == np.float32 and np.array_equal(members["lstm_state.npy"], state.numpy())
+    assert members["adam_state.npy"].dtype == np.float32 and np.array_equal(members["adam_state.npy"], w["mv"])
+    assert members["generator_state.npy"].dtype == w["gen"].dtype and np.array_equal(members["generator_state.npy"], w["gen"])
+    assert members["curriculum_state.bin"] == b"curriculum-blob" and members["normalize_state.bin"] == b"\x00norm\xff"
+    sd = torch.load(io.BytesIO(members["policy.pth"]))
+    assert set(sd) == set(w["sd"]) and all(torch.equal(sd[k], w["sd"][k]) for k in sd)
+    assert meta["hyper"] == w["hyper"] and meta["desc"] == {k: (list(v) if isinstance(v, tuple) else v) for k, v in w["desc"].items()}
+    assert (meta["format"], meta["seed"], meta["policy_seed"], meta["policy_counter"]) == ("windgym_amd.PPO/1", 5, 5, 9)
+    assert (meta["num_timesteps"], meta["iteration"], meta["adam_step"], meta["env_policy_steps"]) == (384, 3, 12, 48)
+    assert meta["log"] == w["log"] and meta["critic"] == "agent"
+    assert meta["curriculum"] == dict(n_passes=2) and meta["normalize"] == dict(gamma=0.9)
+    # a plain one has neither blob nor key, and arguments passed to load() win over stored numbers
+    plain = str(tmp_path / "b.zip")
+    _fake_checkpoint(plain)
+    meta, members = read_checkpoint(plain, learning_rate=0.5)
+    assert set(members) == {"policy.pth", "adam_state.npy", "generator_state.npy"} and "curriculum" not in meta and "normalize" not in meta
+    assert meta["hyper"]["learning_rate"] == 0.5 and meta["hyper"]["clip_range"] == 0.2
+
+
+def test_checkpoint_schedules_and_refusals(tmp_path):
+    import zipfile
+
+    from windgym_amd.ppo import read_checkpoint
+    from windgym_amd.recurrent_ppo import RecurrentPPO
+    path = str(tmp_path / "s.zip")
+    _fake_checkpoint(path, learning_rate=lambda p: 1e-3 * p)
+    with pytest.raises(ValueError, match=r"^the checkpoint was trained with a learning_rate schedule: pass it to load\(\)$"):
+        read_checkpoint(path)
+    with pytest.raises(ValueError, match=r"^the checkpoint was trained with a learning_rate schedule: pass it to load\(\)$"):
+        PPO.load(path, None)
+    sched = lambda p: 2e-3 * p                                   # noqa: E731
+    meta, _ = read_checkpoint(path, learning_rate=sched)
+    assert meta["hyper"]["learning_rate"] is sched
+    # PPO's zip has no lstm_state.npy: RecurrentPPO.load refuses it by name, PPO.load a zip without the JSON
+    with pytest.raises(ValueError) as e:
+        RecurrentPPO.load(path, None, learning_rate=sched)
+    assert str(e.value) == ("not a windgym_amd RecurrentPPO checkpoint (an sb3-contrib zip loads with MlpLstmPolicy.from_sb3_zip, "
+                            "a PPO checkpoint with PPO.load)")
+    other = str(tmp_path / "o.zip")
+    with zipfile.ZipFile(other, "w") as z:
+        z.writestr("policy.pth", b"")
+    with pytest.raises(ValueError) as e:
+        PPO.load(other, None)
+    assert str(e.value) == "not a windgym_amd PPO checkpoint (for an SB3 zip use MlpPolicy.from_sb3_zip)"
+
+
 def _defines(header):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = open(os.path.join(root, *header)).read()

@@ -1,7 +1,8 @@
 """GPU box: one fixed scenario (seeds, actions) through step(), or through the policy kernels; every output goes to an .npz — run it
 under two builds (WG_LIB=... with WG_DEBUG_HOOKS=1) and compare the files bit for bit:
     python tools/dump_run.py out_a.npz [workload] [n_envs] [steps];  python tools/dump_run.py --compare out_a.npz out_b.npz
-    python tools/dump_run.py policy out_a.npz      k_policy / k_policy_pop / k_lstm at the kernels' edge shapes + 8-step closed loops"""
+    python tools/dump_run.py policy out_a.npz      k_policy / k_policy_pop / k_lstm at the kernels' edge shapes + 8-step closed loops
+    python tools/dump_run.py train out_a.npz       two learn iterations of every trainer: parameters, Adam's state, statistics, logs"""
 import os
 import sys
 
@@ -85,8 +86,59 @@ def dump_policy(out):
     print("wrote", out, len(A), "arrays")
 
 
-if sys.argv[1] == "policy":
-    dump_policy(sys.argv[2])
+def dump_train(out):
+    """Two ``learn`` iterations (n_steps = 8, 2 epochs, fixed seeds) on 4 envs of the 2-turbine preset of: PPO; PPO on the multi-agent
+    env with the per-agent and with the centralised critic; PPO(normalize={}); PPOPopulation with P = 2; RecurrentPPO (H = 40) with an
+    LSTM per net and with a shared one.  Kept per trainer: the parameters, ``opt.state()``, ``_stats``, ``_perm`` and the logged
+    records without ``fps``."""
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv, WindFarmVecEnvMulti
+    from windgym_amd.population import PPOPopulation
+    from windgym_amd.ppo import PPO
+    from windgym_amd.recurrent_ppo import RecurrentPPO
+    from windgym_amd.turbine import V80
+    A, T, B = {}, 8, 4
+    env_kw = dict(yaml_dict=presets.two_turb_config(), seed=77, turbtype="None", n_passthrough=1)
+    kw = dict(n_steps=T, n_epochs=2, ent_coef=0.001)
+
+    def single():
+        return WindFarmVecEnv(V80(), B, as_torch=True, **env_kw)
+
+    def multi():
+        return WindFarmVecEnvMulti(V80(), B, **env_kw)
+
+    def lstm(shared):
+        return dict(policy_kwargs=dict(lstm_hidden_size=40, net_arch=[16], shared_lstm=shared))
+
+    runs = [("ppo", single, PPO, "MlpPolicy", dict(seed=11)),
+            ("ppo_multi_agent", multi, PPO, "MlpPolicy", dict(seed=12, critic="agent")),
+            ("ppo_multi_central", multi, PPO, "MlpPolicy", dict(seed=13, critic="central")),
+            ("ppo_normalize", single, PPO, "MlpPolicy", dict(seed=14, normalize={})),
+            ("population", single, PPOPopulation, "MlpPolicy", dict(n_members=2, seed=[15, 16], learning_rate=[3e-4, 1e-3])),
+            ("recurrent", single, RecurrentPPO, "MlpLstmPolicy", dict(seed=17, **lstm(False))),
+            ("recurrent_shared", single, RecurrentPPO, "MlpLstmPolicy", dict(seed=18, **lstm(True)))]
+    for tag, make, cls, policy, extra in runs:
+        v = make()
+        v.reset(seed=77)
+        tr = cls(policy, v, **kw, **extra)
+        tr.learn(2 * tr.n_env_steps)
+        pairs = list(zip(tr.members, tr.opts)) if hasattr(tr, "opts") else [(tr.policy, tr.opt)]
+        for m, (pol, opt) in enumerate(pairs):
+            mv, step = opt.state()
+            A[f"{tag}_{m}_params"], A[f"{tag}_{m}_adam"], A[f"{tag}_{m}_step"] = pol.params.cpu().numpy(), mv, np.array([step])
+        A[f"{tag}_stats"], A[f"{tag}_perm"] = tr._stats.cpu().numpy(), tr._perm.cpu().numpy()
+        assert len(tr.log) == 2
+        recs = tr.log if isinstance(tr.log[0], dict) else [r for it in tr.log for r in it]
+        keys = sorted(k for k in recs[0] if k != "fps")
+        A[f"{tag}_log"] = np.array([[float("nan") if r[k] is None else float(r[k]) for k in keys] for r in recs], np.float64)
+        tr.close()
+        v.close()
+    np.savez(out, **A)
+    print("wrote", out, len(A), "arrays")
+
+
+if sys.argv[1] in ("policy", "train"):
+    (dump_policy if sys.argv[1] == "policy" else dump_train)(sys.argv[2])
     sys.exit(0)
 out = sys.argv[1]
 wl = sys.argv[2] if len(sys.argv) > 2 else "cfg2"

@@ -196,12 +196,13 @@ def load_library():
     L.wg_gae.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
                          C.c_void_p, C.c_void_p]
     L.wg_ppo_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.wg_ppo_destroy.argtypes = [C.c_void_p]
-    L.wg_ppo_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-    L.wg_ppo_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]
+    for fam in ("wg_ppo", "wg_lstm_ppo"):                       # what the two optimiser handles share (ppo.HandleOptimizer)
+        getattr(L, fam + "_destroy").argtypes = [C.c_void_p]
+        getattr(L, fam + "_get_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        getattr(L, fam + "_set_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]
+        getattr(L, fam + "_apply").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     L.wg_ppo_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int64, C.c_int,
                               C.POINTER(CPpoHyper), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.wg_ppo_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     L.wg_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int, C.c_int,
                                 C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     L.wg_ppo_grad_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_grad.argtypes[3:]
@@ -241,13 +242,9 @@ def load_library():
     L.wg_rollout_lstm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
                                   C.POINTER(CRolloutBufs), C.POINTER(CRolloutLstmBufs), C.c_void_p]
     L.wg_lstm_ppo_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.wg_lstm_ppo_destroy.argtypes = [C.c_void_p]
     L.wg_lstm_ppo_n_params.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
-    L.wg_lstm_ppo_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-    L.wg_lstm_ppo_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]
     L.wg_lstm_ppo_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.POINTER(CPpoHyper),
                                    C.c_void_p, C.c_void_p, C.c_void_p]
-    L.wg_lstm_ppo_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     L.wg_lstm_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.c_int,
                                      C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     _lib = L

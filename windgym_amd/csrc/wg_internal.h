@@ -15,6 +15,8 @@ struct WgPopRows;
 struct WgPolicyP;
 struct WgPopMember;
 struct WgPacked;
+struct WgAdam;
+struct WgPpoGrad;
 struct WgValueRows {           // the critic on n_rows rows: obs [n_rows][critic's input width] -> value [n_rows]
     const float* obs;
     float* value;
@@ -52,15 +54,24 @@ int wg_pop_store_(void* dst_dev, const void* src_host, size_t bytes, void* strea
 int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const WgPopRows* r,
                     void* stream);
 int wg_pop_launch_(wg_pop q, int head, int fin, int t, int deterministic, uint64_t counter, void* stream);
-// wg_ppo.hip, for the recurrent trainer (wg_lstm_ppo.hip).  The heads: k_ppo_grad's loss on n rows whose actor reads h_pi [n][H] and
+// wg_ppo.hip: Adam over one flat vector (wg_train.h: WgAdam).  alloc: moments zeroed, step 0; free (and wg_ppo_grad_free_): on the
+// current, synchronised device — a failed alloc / init leaves the freeing to the caller; get / set_state: the public *_get_state /
+// *_set_state entries, reported as `who`, a null `a` included; apply: counts one step, then clipping by the global norm of grad_dev
+// [n_flat] and that step of Adam on params_dev in place (k_ppo_sumsq + k_ppo_adam)
+hipError_t wg_adam_alloc_(WgAdam* a, int device, uint32_t n_flat);
+void wg_adam_free_(WgAdam* a);
+int wg_adam_get_state_(WgAdam* a, const char* who, float* mv_host, size_t n, uint64_t* step);
+int wg_adam_set_state_(WgAdam* a, const char* who, const float* mv_host, size_t n, uint64_t step);
+int wg_adam_apply_(WgAdam* a, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st);
+// wg_ppo.hip: the gradient kernel's side of policy p (wg_ppo.h: WgPpoGrad) — the first half of wg_ppo_create, reported under that
+// name.  heads_grad, the heads of a recurrent policy (wg_lstm_ppo.hip): k_ppo_grad's loss on n rows whose actor reads h_pi [n][H] and
 // whose critic reads h_vf [n][H], raw / logp / adv / ret indexed by the same row -> the MLP's flat gradient, the stats record and the
-// gradients of the rows, dh_pi / dh_vf [n][H] (k_ppo_grad_dh).  Adam: clipping by the global norm of grad_dev [n_flat] and step number
-// `step` of Adam with wg_ppo.hip's constants on params_dev in place (k_ppo_sumsq + k_ppo_adam; blocksq: ceil(n_flat / 256) floats)
-int wg_ppo_heads_grad_(wg_ppo o, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw, const float* logp,
+// gradients of the rows, dh_pi / dh_vf [n][H] (k_ppo_grad_dh)
+int wg_ppo_grad_init_(WgPpoGrad* g, wg_policy p);
+void wg_ppo_grad_free_(WgPpoGrad* g);
+int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw, const float* logp,
                        const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi, float* dh_vf, float* grad_out,
                        float* stats_out, void* stream);
-int wg_ppo_adam_(float* params_dev, const float* grad_dev, float* m, float* v, uint32_t n_flat, float* blocksq, uint64_t step, float lr,
-                 float max_grad_norm, void* stream);
 // k_policy_pack for each of the n_members rows of a member table (device)
 void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_members, void* stream);
 // wg_flow.hip

@@ -51,11 +51,11 @@ struct WgLstmSeq {
 struct wg_lstm_ppo_s {
     wg_lstm_s* lstm;
     wg_policy_s* pol;
-    wg_ppo_s* heads;           // the MLP's gradient kernel and its scratch (its own Adam state is not used)
-    int device, T_max, Bm_max, NT_max;
-    uint32_t n_lstm, n_flat, n_blocks;
-    uint64_t step;             // Adam's step count
-    float *m, *v, *grad, *blocksq, *stats;
+    WgPpoGrad heads;           // the MLP's gradient kernel and its scratch
+    WgAdam adam;               // over the policy's one flat vector: the LSTM's n_lstm floats, then the MLP's
+    int T_max, Bm_max, NT_max;
+    uint32_t n_lstm;
+    float *grad, *stats;       // [n_flat] gradient of wg_lstm_ppo_update's running minibatch; scratch stats record
     float *gates, *c, *h, *dh, *rows;      // the stash; rows = raw | logp | adv | ret
     float* whhT;
     float* wpart;              // [WGLP_SPLIT][n_lstm] the weight gradient's partial sums

@@ -363,26 +363,21 @@ extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max,
                                              " envs need a stash of " + std::to_string(sizeof(float) * (f_gates + f_c + f_h + f_dh + f_rows)) +
                                              " bytes; the limits are " + std::to_string(WGLP_STASH_BYTES) + " bytes and " +
                                              std::to_string(WGLP_ROWS_MAX) + " rows per minibatch");
-    wg_ppo heads = nullptr;
-    if (int rc = wg_ppo_create(p, &heads)) return rc;
     wg_lstm_ppo_s* o = new (std::nothrow) wg_lstm_ppo_s();
-    if (!o) {
-        wg_ppo_destroy(heads);
-        return wg_fail(WG_ERR_NOMEM, "wg_lstm_ppo_create: out of host memory");
+    if (!o) return wg_fail(WG_ERR_NOMEM, "wg_lstm_ppo_create: out of host memory");
+    o->lstm = l; o->pol = p;
+    o->adam.device = l->w.device; o->T_max = T_max; o->Bm_max = Bm_max; o->NT_max = (int)NT;
+    o->n_lstm = L.n_flat;
+    if (int rc = wg_ppo_grad_init_(&o->heads, p)) {
+        wg_lstm_ppo_destroy(o);
+        return rc;
     }
-    o->lstm = l; o->pol = p; o->heads = heads;
-    o->device = l->w.device; o->T_max = T_max; o->Bm_max = Bm_max; o->NT_max = (int)NT;
-    o->n_lstm = L.n_flat; o->n_flat = L.n_flat + p->P.n_flat;
-    o->n_blocks = (o->n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
     o->nksT = wg_tile_nks(4 * L.H);
     o->whhT_net = wg_tile_wsize(L.nub, o->nksT);
     o->whhT_all = o->whhT_net * L.n_nets + WGP_SLACK;
-    const size_t nf = sizeof(float) * (size_t)o->n_flat;
-    hipError_t e = hipSetDevice(o->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->m, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->v, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->grad, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->blocksq, sizeof(float) * o->n_blocks);
+    const uint32_t n_flat = L.n_flat + p->P.n_flat;
+    hipError_t e = wg_adam_alloc_(&o->adam, l->w.device, n_flat);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->grad, sizeof(float) * (size_t)n_flat);
     if (e == hipSuccess) e = hipMalloc((void**)&o->stats, sizeof(float) * WGT_NSTAT);
     if (e == hipSuccess) e = hipMalloc((void**)&o->gates, sizeof(float) * f_gates);
     if (e == hipSuccess) e = hipMalloc((void**)&o->c, sizeof(float) * f_c);
@@ -391,8 +386,6 @@ extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max,
     if (e == hipSuccess) e = hipMalloc((void**)&o->rows, sizeof(float) * f_rows);
     if (e == hipSuccess) e = hipMalloc((void**)&o->whhT, sizeof(float) * o->whhT_all);
     if (e == hipSuccess) e = hipMalloc((void**)&o->wpart, sizeof(float) * (size_t)WGLP_SPLIT * o->n_lstm);
-    if (e == hipSuccess) e = hipMemset(o->m, 0, nf);
-    if (e == hipSuccess) e = hipMemset(o->v, 0, nf);
     if (e != hipSuccess) {
         wg_lstm_ppo_destroy(o);
         return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_lstm_ppo_create: ") + hipGetErrorString(e));
@@ -403,43 +396,30 @@ extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max,
 
 extern "C" int wg_lstm_ppo_destroy(wg_lstm_ppo o) {
     if (!o) return 0;
-    if (hipSetDevice(o->device) == hipSuccess) {
+    if (hipSetDevice(o->adam.device) == hipSuccess) {
         (void)hipDeviceSynchronize();
-        float* bufs[] = {o->m, o->v, o->grad, o->blocksq, o->stats, o->gates, o->c, o->h, o->dh, o->rows, o->whhT, o->wpart};
+        wg_ppo_grad_free_(&o->heads);
+        wg_adam_free_(&o->adam);
+        float* bufs[] = {o->grad, o->stats, o->gates, o->c, o->h, o->dh, o->rows, o->whhT, o->wpart};
         for (float* b : bufs)
             if (b) (void)hipFree(b);
     }
-    wg_ppo_destroy(o->heads);
     delete o;
     return 0;
 }
 
 extern "C" int wg_lstm_ppo_n_params(wg_lstm_ppo o, size_t* n) {
     if (!o || !n) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_n_params: null argument");
-    *n = o->n_flat;
+    *n = o->adam.n_flat;
     return 0;
 }
 
 extern "C" int wg_lstm_ppo_get_state(wg_lstm_ppo o, float* mv_host, size_t n, uint64_t* step) {
-    if (!o || !mv_host || !step) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_get_state: null argument");
-    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_get_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
-    if (int rc = wg_use_device(o->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
-    WG_HIPCHK(hipMemcpy(mv_host, o->m, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
-    WG_HIPCHK(hipMemcpy(mv_host + o->n_flat, o->v, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
-    *step = o->step;
-    return 0;
+    return wg_adam_get_state_(o ? &o->adam : nullptr, "wg_lstm_ppo_get_state", mv_host, n, step);
 }
 
 extern "C" int wg_lstm_ppo_set_state(wg_lstm_ppo o, const float* mv_host, size_t n, uint64_t step) {
-    if (!o || !mv_host) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_set_state: null argument");
-    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_set_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
-    if (int rc = wg_use_device(o->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
-    WG_HIPCHK(hipMemcpy(o->m, mv_host, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
-    WG_HIPCHK(hipMemcpy(o->v, mv_host + o->n_flat, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
-    o->step = step;
-    return 0;
+    return wg_adam_set_state_(o ? &o->adam : nullptr, "wg_lstm_ppo_set_state", mv_host, n, step);
 }
 
 // what grad and update check of a batch and the hyper-parameters; `who` names the entry
@@ -478,7 +458,7 @@ static int lp_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_bat
                        adv, ret);
     hipLaunchKernelGGL(k_lstm_seq_fwd, dim3(q.NT, L.n_nets), dim3(WGP_WAVES * 64), 0, st, L, o->lstm->w.packed, q);
     WG_HIPCHK(hipGetLastError());
-    if (int rc = wg_ppo_heads_grad_(o->heads, params_dev + o->n_lstm, o->h, o->h + (size_t)(L.n_nets - 1) * q.net_h, raw, logp, adv, ret, n, hp,
+    if (int rc = wg_ppo_heads_grad_(&o->heads, params_dev + o->n_lstm, o->h, o->h + (size_t)(L.n_nets - 1) * q.net_h, raw, logp, adv, ret, n, hp,
                                     o->dh, o->dh + n_max * H, grad_out + o->n_lstm, stats_out ? stats_out : o->stats, (void*)st))
         return rc;
     hipLaunchKernelGGL(k_lstm_seq_bwd, dim3(q.NT, L.n_nets), dim3(WGP_WAVES * 64), 0, st, L, q);
@@ -491,24 +471,23 @@ static int lp_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_bat
 }
 
 static int lp_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
-    o->step += 1;
-    if (int rc = wg_ppo_adam_(params_dev, grad_dev, o->m, o->v, o->n_flat, o->blocksq, o->step, lr, max_grad_norm, (void*)st)) return rc;
+    if (int rc = wg_adam_apply_(&o->adam, params_dev, grad_dev, lr, max_grad_norm, st)) return rc;
     if (int rc = wg_lstm_set_params(o->lstm, params_dev, o->n_lstm, 1, (void*)st)) return rc;
-    return wg_policy_set_params(o->pol, params_dev + o->n_lstm, o->n_flat - o->n_lstm, 1, (void*)st);
+    return wg_policy_set_params(o->pol, params_dev + o->n_lstm, o->adam.n_flat - o->n_lstm, 1, (void*)st);
 }
 
 extern "C" int wg_lstm_ppo_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_batch* b, const int32_t* envs_dev, int n_envs,
                                 const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
     if (!o || !params_dev || !b || !envs_dev || !hp || !grad_out) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_grad: null argument");
     if (int rc = lp_check("wg_lstm_ppo_grad", o, b, hp, n_envs)) return rc;
-    if (int rc = wg_use_device(o->device)) return rc;
+    if (int rc = wg_use_device(o->adam.device)) return rc;
     return lp_grad(o, params_dev, b, envs_dev, n_envs, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
 }
 
 extern "C" int wg_lstm_ppo_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream) {
     if (!o || !params_dev || !grad_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_apply: null argument");
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_apply: max_grad_norm must be > 0");
-    if (int rc = wg_use_device(o->device)) return rc;
+    if (int rc = wg_use_device(o->adam.device)) return rc;
     return lp_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
 }
 
@@ -519,14 +498,10 @@ extern "C" int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lst
     if (n_epochs < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_update: n_epochs must be >= 1");
     if (int rc = lp_check("wg_lstm_ppo_update", o, b, hp, envs_per_batch)) return rc;
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_update: max_grad_norm must be > 0");
-    if (int rc = wg_use_device(o->device)) return rc;
-    const int B = b->B, n_mb = (B + envs_per_batch - 1) / envs_per_batch;
-    for (int e = 0; e < n_epochs; ++e)
-        for (int k = 0; k < n_mb; ++k) {
-            const int first = k * envs_per_batch, Bm = B - first < envs_per_batch ? B - first : envs_per_batch;
-            float* so = stats_out ? (float*)(stats_out + (size_t)e * n_mb + k) : nullptr;
-            if (int rc = lp_grad(o, params_dev, b, perm_dev + (size_t)e * B + first, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
-            if (int rc = lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream)) return rc;
-        }
-    return 0;
+    if (int rc = wg_use_device(o->adam.device)) return rc;
+    return wg_each_minibatch(b->B, n_epochs, envs_per_batch, [&](int mb, int64_t off, int Bm) {
+        float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
+        if (int rc = lp_grad(o, params_dev, b, perm_dev + off, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        return lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
+    });
 }

@@ -1,4 +1,5 @@
-// wg_ppo.h — the host object behind the `wg_ppo` handle and the constants of the training kernels (wg_ppo.hip).
+// wg_ppo.h — the host objects behind the `wg_ppo` handle (the gradient kernel's side, WgPpoGrad, and the optimiser's: wg_train.h's
+// WgAdam and the gradient vector) and the constants of the training kernels (wg_ppo.hip).
 //
 // k_ppo_grad works on tiles of R rows (R = 32 when a net's activations fit the workgroup's LDS, else 16, 8, 4 or 2: a
 // function of the architecture alone — each net's map with its own input width, n_in / n_in_vf).  Minibatch rows 0 .. n-1 form ceil(n / R) tiles; G = min(tiles, g_max) workgroups
@@ -13,6 +14,7 @@
 #include <stdint.h>
 
 #include "wg_policy.h"
+#include "wg_train.h"
 
 #define WGT_WAVES 4               // waves per workgroup of k_ppo_grad
 #define WGT_LDS_BYTES 65536       // LDS budget of one workgroup
@@ -37,20 +39,23 @@ struct WgPpoK {                           // by-value kernel argument next to Wg
     WgPpoLds lds[2];
 };
 
-struct wg_ppo_s {
+// the gradient kernel's side of a policy: its LDS map, its grid limit and its scratch — all k_ppo_grad* needs on the host.  The
+// recurrent trainer holds one by value for its heads (wg_lstm_ppo.h); wg_ppo_grad_init_ / wg_ppo_grad_free_ of wg_internal.h
+struct WgPpoGrad {
     wg_policy_s* pol;
     WgPpoK K;
-    int device;
+    size_t lds_bytes;
     int g_max;
-    uint32_t n_flat, n_blocks;            // n_blocks = ceil(n_flat / WGT_BLOCK)
-    uint64_t step;                        // Adam's step count
-    float *m, *v;                         // [n_flat] Adam moments
-    float *grad;                          // [n_flat] gradient of wg_ppo_update's running minibatch
+    uint32_t n_blocks;                    // ceil(the policy's n_flat / WGT_BLOCK): k_ppo_reduce's grid
     float *part, *spart;                  // [g_max][n_flat], [g_max][4]
     float *advstat;                       // [2] mean and unbiased std of the minibatch's advantages
-    float *blocksq;                       // [n_blocks] partial sums of squares of the gradient
     float *stats;                         // [WGT_NSTAT] scratch record when the caller wants none
-    size_t lds_bytes;
+};
+
+struct wg_ppo_s {
+    WgPpoGrad g;
+    WgAdam adam;                          // over the policy's flat vector, on the policy's device
+    float* grad;                          // [n_flat] gradient of wg_ppo_update's running minibatch
 };
 
 #endif

@@ -604,43 +604,103 @@ static size_t t_lds_map(const WgPolicyP& P, int R, WgPpoK* K) {
     return most;
 }
 
-extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
-    if (!p || !out) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: null argument");
-    *out = nullptr;
+// WgAdam (wg_train.h) and WgPpoGrad (wg_ppo.h): wg_internal.h states what each function does
+extern "C" hipError_t wg_adam_alloc_(WgAdam* a, int device, uint32_t n_flat) {
+    *a = {device, n_flat, (n_flat + WGT_BLOCK - 1) / WGT_BLOCK, 0, nullptr, nullptr, nullptr};
+    const size_t nf = sizeof(float) * (size_t)n_flat;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void**)&a->m, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&a->v, nf);
+    if (e == hipSuccess) e = hipMalloc((void**)&a->blocksq, sizeof(float) * a->n_blocks);
+    if (e == hipSuccess) e = hipMemset(a->m, 0, nf);
+    if (e == hipSuccess) e = hipMemset(a->v, 0, nf);
+    return e;
+}
+
+extern "C" void wg_adam_free_(WgAdam* a) {
+    for (float* b : {a->m, a->v, a->blocksq})
+        if (b) (void)hipFree(b);
+}
+
+// what get_state / set_state check before they copy: the arguments, the size, the device idle
+static int adam_state_ready(const WgAdam* a, const std::string& who, bool all_there, size_t n) {
+    if (!a || !all_there) return wg_fail(WG_ERR_INVALID, who + ": null argument");
+    if (n != 2 * (size_t)a->n_flat) return wg_fail(WG_ERR_INVALID, who + ": the state has " + std::to_string(2 * (size_t)a->n_flat) + " floats");
+    if (int rc = wg_use_device(a->device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+extern "C" int wg_adam_get_state_(WgAdam* a, const char* who, float* mv_host, size_t n, uint64_t* step) {
+    if (int rc = adam_state_ready(a, who, mv_host && step, n)) return rc;
+    WG_HIPCHK(hipMemcpy(mv_host, a->m, sizeof(float) * a->n_flat, hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy(mv_host + a->n_flat, a->v, sizeof(float) * a->n_flat, hipMemcpyDeviceToHost));
+    *step = a->step;
+    return 0;
+}
+
+extern "C" int wg_adam_set_state_(WgAdam* a, const char* who, const float* mv_host, size_t n, uint64_t step) {
+    if (int rc = adam_state_ready(a, who, mv_host, n)) return rc;
+    WG_HIPCHK(hipMemcpy(a->m, mv_host, sizeof(float) * a->n_flat, hipMemcpyHostToDevice));
+    WG_HIPCHK(hipMemcpy(a->v, mv_host + a->n_flat, sizeof(float) * a->n_flat, hipMemcpyHostToDevice));
+    a->step = step;
+    return 0;
+}
+
+extern "C" int wg_adam_apply_(WgAdam* a, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
+    const WgAdamStep s = wg_adam_count(a, lr);
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(a->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, a->n_flat, a->blocksq);
+    hipLaunchKernelGGL(k_ppo_adam, dim3(a->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, a->m, a->v, a->n_flat,
+                       a->blocksq, a->n_blocks, max_grad_norm, s.step_size, s.bc2_sqrt, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_ppo_grad_init_(WgPpoGrad* g, wg_policy p) {
     const WgPolicyP& P = p->P;
     if (P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with a critic");
     if (!P.has_log_std) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with log_std");
+    g->pol = p;
+    g->n_blocks = (P.n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    int R = 32;
+    while ((g->lds_bytes = t_lds_map(P, R, &g->K)) > WGT_LDS_BYTES && R > 2) R >>= 1;
+    if (g->lds_bytes > WGT_LDS_BYTES)
+        return wg_fail(WG_ERR_UNSUPPORTED, "wg_ppo_create: the architecture's activations do not fit the workgroup's LDS");
+    size_t gm = WGT_PART_BYTES / (sizeof(float) * (size_t)P.n_flat);
+    g->g_max = (int)(gm < 1 ? 1 : gm > WGT_G_MAX ? WGT_G_MAX : gm);
+    hipError_t e = hipSetDevice(p->w.device);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->part, sizeof(float) * (size_t)P.n_flat * g->g_max);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->spart, sizeof(float) * 4 * g->g_max);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->advstat, sizeof(float) * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->stats, sizeof(float) * WGT_NSTAT);
+    if (e == hipSuccess) e = hipMemset(g->spart, 0, sizeof(float) * 4 * g->g_max);
+    if (e == hipSuccess) e = hipMemset(g->advstat, 0, sizeof(float) * 2);
+    if (e != hipSuccess)
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" void wg_ppo_grad_free_(WgPpoGrad* g) {
+    for (float* b : {g->part, g->spart, g->advstat, g->stats})
+        if (b) (void)hipFree(b);
+}
+
+extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
+    if (!p || !out) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: null argument");
+    *out = nullptr;
     wg_ppo_s* o = new (std::nothrow) wg_ppo_s();
     if (!o) return wg_fail(WG_ERR_NOMEM, "wg_ppo_create: out of host memory");
-    o->pol = p;
-    o->device = p->w.device;
-    o->n_flat = P.n_flat;
-    o->n_blocks = (P.n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
-    int R = 32;
-    while ((o->lds_bytes = t_lds_map(P, R, &o->K)) > WGT_LDS_BYTES && R > 2) R >>= 1;
-    if (o->lds_bytes > WGT_LDS_BYTES) {
-        delete o;
-        return wg_fail(WG_ERR_UNSUPPORTED, "wg_ppo_create: the architecture's activations do not fit the workgroup's LDS");
+    o->adam.device = p->w.device;
+    int rc = wg_ppo_grad_init_(&o->g, p);
+    if (!rc) {
+        hipError_t e = wg_adam_alloc_(&o->adam, p->w.device, p->P.n_flat);
+        if (e == hipSuccess) e = hipMalloc((void**)&o->grad, sizeof(float) * (size_t)p->P.n_flat);
+        if (e != hipSuccess)
+            rc = wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
     }
-    size_t gm = WGT_PART_BYTES / (sizeof(float) * (size_t)P.n_flat);
-    o->g_max = (int)(gm < 1 ? 1 : gm > WGT_G_MAX ? WGT_G_MAX : gm);
-    const size_t nf = sizeof(float) * (size_t)P.n_flat;
-    hipError_t e = hipSetDevice(o->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->m, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->v, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->grad, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->part, nf * o->g_max);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->spart, sizeof(float) * 4 * o->g_max);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->advstat, sizeof(float) * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->blocksq, sizeof(float) * o->n_blocks);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->stats, sizeof(float) * WGT_NSTAT);
-    if (e == hipSuccess) e = hipMemset(o->m, 0, nf);
-    if (e == hipSuccess) e = hipMemset(o->v, 0, nf);
-    if (e == hipSuccess) e = hipMemset(o->spart, 0, sizeof(float) * 4 * o->g_max);
-    if (e == hipSuccess) e = hipMemset(o->advstat, 0, sizeof(float) * 2);
-    if (e != hipSuccess) {
+    if (rc) {
         wg_ppo_destroy(o);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = o;
     return 0;
@@ -648,36 +708,22 @@ extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
 
 extern "C" int wg_ppo_destroy(wg_ppo o) {
     if (!o) return 0;
-    if (hipSetDevice(o->device) == hipSuccess) {
+    if (hipSetDevice(o->adam.device) == hipSuccess) {
         (void)hipDeviceSynchronize();
-        float* bufs[] = {o->m, o->v, o->grad, o->part, o->spart, o->advstat, o->blocksq, o->stats};
-        for (float* b : bufs)
-            if (b) (void)hipFree(b);
+        wg_ppo_grad_free_(&o->g);
+        wg_adam_free_(&o->adam);
+        if (o->grad) (void)hipFree(o->grad);
     }
     delete o;
     return 0;
 }
 
 extern "C" int wg_ppo_get_state(wg_ppo o, float* mv_host, size_t n, uint64_t* step) {
-    if (!o || !mv_host || !step) return wg_fail(WG_ERR_INVALID, "wg_ppo_get_state: null argument");
-    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_ppo_get_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
-    if (int rc = wg_use_device(o->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
-    WG_HIPCHK(hipMemcpy(mv_host, o->m, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
-    WG_HIPCHK(hipMemcpy(mv_host + o->n_flat, o->v, sizeof(float) * o->n_flat, hipMemcpyDeviceToHost));
-    *step = o->step;
-    return 0;
+    return wg_adam_get_state_(o ? &o->adam : nullptr, "wg_ppo_get_state", mv_host, n, step);
 }
 
 extern "C" int wg_ppo_set_state(wg_ppo o, const float* mv_host, size_t n, uint64_t step) {
-    if (!o || !mv_host) return wg_fail(WG_ERR_INVALID, "wg_ppo_set_state: null argument");
-    if (n != 2 * (size_t)o->n_flat) return wg_fail(WG_ERR_INVALID, "wg_ppo_set_state: the state has " + std::to_string(2 * (size_t)o->n_flat) + " floats");
-    if (int rc = wg_use_device(o->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
-    WG_HIPCHK(hipMemcpy(o->m, mv_host, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
-    WG_HIPCHK(hipMemcpy(o->v, mv_host + o->n_flat, sizeof(float) * o->n_flat, hipMemcpyHostToDevice));
-    o->step = step;
-    return 0;
+    return wg_adam_set_state_(o ? &o->adam : nullptr, "wg_ppo_set_state", mv_host, n, step);
 }
 
 // the rows of a batch and the critic's stream (a plain batch: its obs), for every entry that takes one
@@ -700,14 +746,14 @@ static int t_check_batch(const char* who, const wg_ppo_batch_shared* sb, const w
 }
 
 // workgroups per net of a gradient launch on n rows: one per tile of R rows, at most as many as the partial sums have room for
-static int t_grid(const wg_ppo_s* o, int n) {
-    const int R = o->K.R, ntile = (n + R - 1) / R;
-    return ntile < o->g_max ? ntile : o->g_max;
+static int t_grid(const WgPpoGrad* g, int n) {
+    const int R = g->K.R, ntile = (n + R - 1) / R;
+    return ntile < g->g_max ? ntile : g->g_max;
 }
 
 // the launches of one gradient, no argument checks
 // (dh_pi / dh_vf both given: k_ppo_grad_dh, which also writes the gradients of the gathered rows — wg_ppo_heads_grad_)
-static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* sb, const int32_t* index_dev, int64_t first, int n,
+static int t_grad(WgPpoGrad* o, const float* params_dev, const wg_ppo_batch_shared* sb, const int32_t* index_dev, int64_t first, int n,
                   const wg_ppo_hyper* hp, float* grad_out, float* stats_out, hipStream_t st, float* dh_pi = nullptr, float* dh_vf = nullptr) {
     const WgPolicyP& P = o->pol->P;
     const wg_ppo_batch* b = &sb->rows;
@@ -727,44 +773,25 @@ static int t_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* 
     return 0;
 }
 
-// Adam's constants (the kernels take 1 - beta1, beta2, 1 - beta2 and eps) and, per step, the two scalars of t_adam_step
-static const double ADAM_B1 = 0.9, ADAM_B2 = 0.999;
-static const float ADAM_EPS = 1e-5f;
-struct AdamStep { float step_size, bc2_sqrt; };          // lr / (1 - beta1^step), sqrt(1 - beta2^step)
-
-// counts one more step of `o` and -> that step's scalars (bias corrections in double, rounded once)
-static AdamStep t_adam_step(wg_ppo_s* o, float lr) {
-    o->step += 1;
-    const double bc1 = 1.0 - std::pow(ADAM_B1, (double)o->step), bc2 = 1.0 - std::pow(ADAM_B2, (double)o->step);
-    return {(float)((double)lr / bc1), (float)std::sqrt(bc2)};
-}
-
 static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st) {
-    const AdamStep s = t_adam_step(o, lr);
-    hipLaunchKernelGGL(k_ppo_sumsq, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, o->n_flat, o->blocksq);
-    hipLaunchKernelGGL(k_ppo_adam, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, o->m, o->v, o->n_flat,
-                       o->blocksq, o->n_blocks, max_grad_norm, s.step_size, s.bc2_sqrt, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
-    WG_HIPCHK(hipGetLastError());
-    return wg_policy_set_params(o->pol, params_dev, o->n_flat, 1, (void*)st);
+    if (int rc = wg_adam_apply_(&o->adam, params_dev, grad_dev, lr, max_grad_norm, st)) return rc;
+    return wg_policy_set_params(o->g.pol, params_dev, o->adam.n_flat, 1, (void*)st);
 }
 
 // wg_internal.h: the heads of a recurrent policy (wg_lstm_ppo.hip)
-extern "C" int wg_ppo_heads_grad_(wg_ppo o, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw,
+extern "C" int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw,
                                   const float* logp, const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi,
                                   float* dh_vf, float* grad_out, float* stats_out, void* stream) {
     const wg_ppo_batch_shared sb = {{h_pi, raw, logp, adv, ret, n}, h_vf, 1};
-    return t_grad(o, mlp_params_dev, &sb, nullptr, 0, n, hp, grad_out, stats_out, (hipStream_t)stream, dh_pi, dh_vf);
+    return t_grad(g, mlp_params_dev, &sb, nullptr, 0, n, hp, grad_out, stats_out, (hipStream_t)stream, dh_pi, dh_vf);
 }
 
-extern "C" int wg_ppo_adam_(float* params_dev, const float* grad_dev, float* m, float* v, uint32_t n_flat, float* blocksq, uint64_t step,
-                            float lr, float max_grad_norm, void* stream) {
-    const double bc1 = 1.0 - std::pow(ADAM_B1, (double)step), bc2 = 1.0 - std::pow(ADAM_B2, (double)step);
-    const uint32_t n_blocks = (n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ppo_sumsq, dim3(n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, n_flat, blocksq);
-    hipLaunchKernelGGL(k_ppo_adam, dim3(n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, m, v, n_flat, blocksq, n_blocks, max_grad_norm,
-                       (float)((double)lr / bc1), (float)std::sqrt(bc2), (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
-    WG_HIPCHK(hipGetLastError());
+// the handle's device becomes the current one; the parameters and the batch's observation streams must live on it
+static int t_use_device(const std::string& w, wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b) {
+    if (int rc = wg_use_device(o->adam.device)) return rc;
+    if (int rc = t_on_device(params_dev, o->adam.device, (w + ": params_dev").c_str())) return rc;
+    if (int rc = t_on_device(b->rows.obs, o->adam.device, (w + ": obs").c_str())) return rc;
+    if (b->obs_vf != b->rows.obs) return t_on_device(b->obs_vf, o->adam.device, (w + ": obs_vf").c_str());
     return 0;
 }
 
@@ -775,12 +802,8 @@ static int grad_entry(const char* who, wg_ppo o, const float* params_dev, const 
     if (int rc = t_check_batch(who, b, hp)) return rc;
     if (n < 1) return wg_fail(WG_ERR_INVALID, w + ": n < 1");
     if (!index_dev && (first < 0 || first + n > b->rows.n_rows)) return wg_fail(WG_ERR_INVALID, w + ": rows first .. first + n - 1 leave the batch");
-    if (int rc = wg_use_device(o->device)) return rc;
-    if (int rc = t_on_device(params_dev, o->device, (w + ": params_dev").c_str())) return rc;
-    if (int rc = t_on_device(b->rows.obs, o->device, (w + ": obs").c_str())) return rc;
-    if (b->obs_vf != b->rows.obs)
-        if (int rc = t_on_device(b->obs_vf, o->device, (w + ": obs_vf").c_str())) return rc;
-    return t_grad(o, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+    if (int rc = t_use_device(w, o, params_dev, b)) return rc;
+    return t_grad(&o->g, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
 }
 
 extern "C" int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b, const int32_t* index_dev,
@@ -791,7 +814,7 @@ extern "C" int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_pp
 // A plain wg_ppo_batch has ONE observation stream of n_in inputs per row: the critic of a split policy cannot read it (it would
 // gather rows of n_in_vf from a buffer of rows of n_in).  Refused here, before anything is enqueued.
 static int t_refuse_split(const char* who, wg_ppo o) {
-    const WgPolicyP& P = o->pol->P;
+    const WgPolicyP& P = o->g.pol->P;
     if (P.n_in_vf == P.n_in) return 0;
     return wg_fail(WG_ERR_INVALID, std::string(who) + ": the policy's critic reads rows of " + std::to_string(P.n_in_vf) + " inputs, its actor rows of " +
                                      std::to_string(P.n_in) + ", and a wg_ppo_batch has one obs stream of the actor's width: use " + who +
@@ -809,26 +832,10 @@ extern "C" int wg_ppo_grad(wg_ppo o, const float* params_dev, const wg_ppo_batch
 extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, void* stream) {
     if (!o || !params_dev || !grad_dev) return wg_fail(WG_ERR_INVALID, "wg_ppo_apply: null argument");
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_ppo_apply: max_grad_norm must be > 0");
-    if (int rc = wg_use_device(o->device)) return rc;
-    if (int rc = t_on_device(params_dev, o->device, "wg_ppo_apply: params_dev")) return rc;
-    if (int rc = t_on_device(grad_dev, o->device, "wg_ppo_apply: grad_dev")) return rc;
+    if (int rc = wg_use_device(o->adam.device)) return rc;
+    if (int rc = t_on_device(params_dev, o->adam.device, "wg_ppo_apply: params_dev")) return rc;
+    if (int rc = t_on_device(grad_dev, o->adam.device, "wg_ppo_apply: grad_dev")) return rc;
     return t_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
-}
-
-// One update: n_epochs passes over `rows` rows (one row of the permutation each) in minibatches of batch_size, the last one of
-// an epoch shorter.  f(mb, off, n) runs once per minibatch, in order: mb = its index in the update (the slot of its
-// statistics), off = its offset into the permutation, n = its rows.
-static int t_n_minibatches(int64_t rows, int batch_size) { return (int)((rows + batch_size - 1) / batch_size); }
-template <class F>
-static int t_each_minibatch(int64_t rows, int n_epochs, int batch_size, F f) {
-    const int n_mb = t_n_minibatches(rows, batch_size);
-    for (int e = 0; e < n_epochs; ++e)
-        for (int k = 0; k < n_mb; ++k) {
-            const int64_t start = (int64_t)k * batch_size;
-            const int n = (int)(rows - start < batch_size ? rows - start : batch_size);
-            if (int rc = f(e * n_mb + k, (int64_t)e * rows + start, n)) return rc;
-        }
-    return 0;
 }
 
 static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
@@ -838,15 +845,11 @@ static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_p
     if (int rc = t_check_batch(who, b, hp)) return rc;
     if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
-    if (int rc = wg_use_device(o->device)) return rc;
-    if (int rc = t_on_device(params_dev, o->device, (w + ": params_dev").c_str())) return rc;
-    if (int rc = t_on_device(b->rows.obs, o->device, (w + ": obs").c_str())) return rc;
-    if (b->obs_vf != b->rows.obs)
-        if (int rc = t_on_device(b->obs_vf, o->device, (w + ": obs_vf").c_str())) return rc;
-    if (int rc = t_on_device(perm_dev, o->device, (w + ": perm_dev").c_str())) return rc;
-    return t_each_minibatch(b->rows.n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
+    if (int rc = t_use_device(w, o, params_dev, b)) return rc;
+    if (int rc = t_on_device(perm_dev, o->adam.device, (w + ": perm_dev").c_str())) return rc;
+    return wg_each_minibatch(b->rows.n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
-        if (int rc = t_grad(o, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        if (int rc = t_grad(&o->g, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
         return t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
     });
 }
@@ -894,7 +897,7 @@ extern "C" int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P
             if (members[k] == members[m]) return wg_fail(WG_ERR_INVALID, who + " is the same policy as member " + std::to_string(k));
         if (opts) {
             if (!opts[m]) return wg_fail(WG_ERR_INVALID, who + ": its wg_ppo is null (opts = NULL makes a population that only acts)");
-            if (opts[m]->pol != members[m]) return wg_fail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another policy");
+            if (opts[m]->g.pol != members[m]) return wg_fail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another policy");
         }
     }
     wg_pop_s* q = new (std::nothrow) wg_pop_s();
@@ -961,15 +964,15 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     if (int rc = t_on_device(perm_dev, q->device, "wg_pop_update: perm_dev")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows_m = b->n_rows / P;
-    const int n_mb = t_n_minibatches(rows_m, batch_size);
+    const int n_mb = wg_n_minibatches(rows_m, batch_size);
     WgPopMember tab[WGP_POP_MAX] = {};
     for (int m = 0; m < P; ++m) {
         wg_ppo_s* o = q->opt[m];
         WgPopMember& M = tab[m];
-        M.packed = o->pol->w.packed; M.params = params_dev[m];
-        M.m = o->m; M.v = o->v; M.grad = o->grad; M.part = o->part; M.spart = o->spart; M.advstat = o->advstat; M.blocksq = o->blocksq;
+        M.packed = o->g.pol->w.packed; M.params = params_dev[m];
+        M.m = o->adam.m; M.v = o->adam.v; M.grad = o->grad; M.part = o->g.part; M.spart = o->g.spart; M.advstat = o->g.advstat; M.blocksq = o->adam.blocksq;
         M.perm = perm_dev + (size_t)m * n_epochs * rows_m;
-        M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->stats;
+        M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->g.stats;
         M.stats_step = stats_out ? WGT_NSTAT : 0;
         M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef; M.max_norm = max_grad_norm[m];
         M.normalize = hp[m].normalize_advantage != 0;
@@ -977,26 +980,27 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     const WgPopMember* mt = (const WgPopMember*)q->upd_dev;
     if (int rc = wg_pop_store_(q->upd_dev, tab, sizeof(WgPopMember) * P, stream)) return rc;
     // every member has the architecture of member 0: one layer table, one LDS map, one G per minibatch size
-    const wg_ppo_s* o0 = q->opt[0];
-    const WgPolicyP& PP = o0->pol->P;
+    const WgPpoGrad* g0 = &q->opt[0]->g;
+    const WgAdam* a0 = &q->opt[0]->adam;
+    const WgPolicyP& PP = g0->pol->P;
     bool any_norm = false;
     for (int m = 0; m < P; ++m) any_norm = any_norm || tab[m].normalize;
-    return t_each_minibatch(rows_m, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
-        const int G = t_grid(o0, n);
+    return wg_each_minibatch(rows_m, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
+        const int G = t_grid(g0, n);
         if (any_norm && n > 1) hipLaunchKernelGGL(k_ppo_advstat_pop, dim3(P), dim3(1024), 0, st, mt, b->advantage, off, n, b->n_rows);
         WgPpoArgs a = {};
         a.obs[0] = b->obs; a.obs[1] = b->obs; a.agents = 1; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage; a.ret = b->returns;
         a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
-        hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), o0->lds_bytes, st, PP, o0->K, a, mt, off);
-        hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
+        hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), g0->lds_bytes, st, PP, g0->K, a, mt, off);
+        hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(g0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
         WgPopAdam A = {};
         for (int m = 0; m < P; ++m) {
-            const AdamStep s = t_adam_step(q->opt[m], lr[m]);
+            const WgAdamStep s = wg_adam_count(&q->opt[m]->adam, lr[m]);
             A.step_size[m] = s.step_size;
             A.bc2_sqrt[m] = s.bc2_sqrt;
         }
-        hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat);
-        hipLaunchKernelGGL(k_ppo_adam_pop, dim3(o0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, o0->n_flat, o0->n_blocks, A, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+        hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(a0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, a0->n_flat);
+        hipLaunchKernelGGL(k_ppo_adam_pop, dim3(a0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, a0->n_flat, a0->n_blocks, A, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
         wg_policy_pack_pop_(&PP, mt, P, stream);
         WG_HIPCHK(hipGetLastError());
         return 0;

@@ -49,23 +49,30 @@ def sb3_orthogonal_init(desc, seed):
     return out
 
 
-class PPOOptimizer:
-    """The ``wg_ppo`` handle of one :class:`MlpPolicy`: Adam's state and the scratch of the gradient kernel.  All methods
-    enqueue on torch's current stream and synchronise nothing (``state()`` / ``load_state()`` excepted)."""
+class HandleOptimizer:
+    """What the ``wg_ppo`` (:class:`PPOOptimizer`) and ``wg_lstm_ppo`` (``recurrent_ppo.RecurrentPPOOptimizer``) handles share: the
+    handle's lifetime, the argument checks, wg_gae, the optimiser step and Adam's state.  ``prefix`` names the family's entries,
+    ``index_is`` what ``_index`` calls its argument.  All methods enqueue on torch's current stream and synchronise nothing
+    (``state()`` / ``load_state()`` excepted)."""
 
-    def __init__(self, policy):
+    prefix, index_is = None, None
+
+    def _open(self, policy, *create_args):
+        """``<prefix>_create(*create_args, &handle)`` and the gradient buffer of ``policy.params``."""
         from .binding import _chk
-        if not policy.has_critic or not policy.desc["has_log_std"]:
-            raise ValueError("training needs a policy with a critic and log_std")
         self.policy, self.L, self._chk, self.torch = policy, policy.L, _chk, policy.torch
         h = C.c_void_p()
-        _chk(self.L.wg_ppo_create(policy._h, C.byref(h)), "wg_ppo_create")
+        self._call("create", *create_args, C.byref(h))
         self._h = h
         self.grad_buf = self.torch.zeros_like(policy.params)
 
+    def _call(self, entry, *args):
+        name = f"{self.prefix}_{entry}"
+        self._chk(getattr(self.L, name)(*args), name)
+
     def close(self):
         if getattr(self, "_h", None):
-            self.L.wg_ppo_destroy(self._h)
+            getattr(self.L, self.prefix + "_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -78,6 +85,16 @@ class PPOOptimizer:
         if not (device_tensor(x, self.torch.float32) and x.numel() == int(np.prod(shape))):
             raise ValueError(f"{what} must be a contiguous float32 CUDA tensor of {int(np.prod(shape))} elements")
         return x
+
+    def _index(self, index, n_min):
+        if not (device_tensor(index, self.torch.int32) and index.numel() >= n_min):
+            raise ValueError(f"the {self.index_is} / permutation must be a contiguous int32 CUDA tensor")
+        return index
+
+    @staticmethod
+    def _hyper(clip_range, vf_coef, ent_coef, normalize_advantage):
+        from .binding import CPpoHyper
+        return CPpoHyper(float(clip_range), float(vf_coef), float(ent_coef), int(bool(normalize_advantage)))
 
     def gae(self, reward, value, final_value, truncated, gamma, gae_lambda, out=None):
         """wg_gae on ``[T, B]`` CUDA tensors (``truncated`` uint8) -> (advantage, returns).  With ``value`` / ``final_value
@@ -99,6 +116,34 @@ class PPOOptimizer:
         if value.ndim != 3:
             raise ValueError("value must be [T, B, A]")
         return self.gae(reward, value, *args, **kwargs)
+
+    def apply(self, grad=None, learning_rate=3e-4, max_grad_norm=0.5):
+        """``<prefix>_apply``: clip, Adam on ``policy.params`` in place, repack — ``policy.act`` afterwards uses the new weights."""
+        g = self.grad_buf if grad is None else grad
+        self._call("apply", self._h, self.policy.params.data_ptr(), g.data_ptr(), float(learning_rate), float(max_grad_norm),
+                   self.policy._stream())
+
+    def state(self):
+        """(Adam's m then v as one float32 numpy vector ``[2 n_params]``, step count)."""
+        n = 2 * self.policy.params.numel()
+        mv, step = np.zeros(n, np.float32), C.c_uint64()
+        self._call("get_state", self._h, mv.ctypes.data_as(C.c_void_p), n, C.byref(step))
+        return mv, int(step.value)
+
+    def load_state(self, mv, step):
+        mv = np.ascontiguousarray(mv, dtype=np.float32)
+        self._call("set_state", self._h, mv.ctypes.data_as(C.c_void_p), mv.size, int(step))
+
+
+class PPOOptimizer(HandleOptimizer):
+    """The ``wg_ppo`` handle of one :class:`MlpPolicy`: Adam's state and the scratch of the gradient kernel."""
+
+    prefix, index_is = "wg_ppo", "index"
+
+    def __init__(self, policy):
+        if not policy.has_critic or not policy.desc["has_log_std"]:
+            raise ValueError("training needs a policy with a critic and log_std")
+        self._open(policy, policy._h)
 
     def _batch(self, obs, raw, logp, advantage, returns, obs_vf=None, agents=1):
         """-> (batch struct, agent rows, shared?).  ``obs_vf`` / ``agents``: the critic's own stream ``[n / agents, n_in_vf]`` of a
@@ -122,16 +167,6 @@ class PPOOptimizer:
         self._f32(obs_vf, (ne, p.n_in_vf), "obs_vf")
         return CPpoBatchShared(b, obs_vf.data_ptr(), agents), n, True
 
-    @staticmethod
-    def _hyper(clip_range, vf_coef, ent_coef, normalize_advantage):
-        from .binding import CPpoHyper
-        return CPpoHyper(float(clip_range), float(vf_coef), float(ent_coef), int(bool(normalize_advantage)))
-
-    def _index(self, index, n_min):
-        if not (device_tensor(index, self.torch.int32) and index.numel() >= n_min):
-            raise ValueError("the index / permutation must be a contiguous int32 CUDA tensor")
-        return index
-
     def grad(self, obs, raw, logp, advantage, returns, *, index=None, first=0, n=None, clip_range=0.2, vf_coef=0.5,
              ent_coef=0.0, normalize_advantage=True, out=None, stats=None, obs_vf=None, agents=1):
         """wg_ppo_grad: one minibatch -> (flat gradient ``[n_params]``, statistics ``[8]`` in the order of binding.PPO_STATS).
@@ -153,12 +188,6 @@ class PPOOptimizer:
             self.policy._stream()), entry)
         return g, st
 
-    def apply(self, grad=None, learning_rate=3e-4, max_grad_norm=0.5):
-        """wg_ppo_apply: clip, Adam on ``policy.params`` in place, repack — ``policy.act`` afterwards uses the new weights."""
-        g = self.grad_buf if grad is None else grad
-        self._chk(self.L.wg_ppo_apply(self._h, self.policy.params.data_ptr(), g.data_ptr(), float(learning_rate),
-                                      float(max_grad_norm), self.policy._stream()), "wg_ppo_apply")
-
     def update(self, obs, raw, logp, advantage, returns, perm, batch_size, *, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
                normalize_advantage=True, learning_rate=3e-4, max_grad_norm=0.5, stats=None, obs_vf=None, agents=1):
         """wg_ppo_update: ``perm`` int32 ``[n_epochs, n_rows]`` -> statistics ``[n_epochs, n_minibatches, 8]``.  ``obs_vf`` /
@@ -176,17 +205,6 @@ class PPOOptimizer:
             C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)), float(learning_rate), float(max_grad_norm),
             st.data_ptr(), self.policy._stream()), entry)
         return st
-
-    def state(self):
-        """(Adam's m then v as one float32 numpy vector ``[2 n_params]``, step count)."""
-        n = 2 * self.policy.params.numel()
-        mv, step = np.zeros(n, np.float32), C.c_uint64()
-        self._chk(self.L.wg_ppo_get_state(self._h, mv.ctypes.data_as(C.c_void_p), n, C.byref(step)), "wg_ppo_get_state")
-        return mv, int(step.value)
-
-    def load_state(self, mv, step):
-        mv = np.ascontiguousarray(mv, dtype=np.float32)
-        self._chk(self.L.wg_ppo_set_state(self._h, mv.ctypes.data_as(C.c_void_p), mv.size, int(step)), "wg_ppo_set_state")
 
 
 def _schedule(x, name):
@@ -251,12 +269,12 @@ def hyper_json(hyper):
 
 
 def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps, curriculum=None,
-                     normalize=None):
+                     normalize=None, tensors=None):
     """The zip of :meth:`PPO.save` (format: the class docstring) from what it holds: the policy, its :class:`PPOOptimizer`, the
     permutation generator, the ``HYPER`` dict, the trainer's seed, its counters and log, the critic mode and the env's count of
     policy steps; with a ``curriculum`` (a ``YawCurriculum``) also its arguments (JSON key ``curriculum``) and its state blob
     (member ``curriculum_state.bin``); with ``normalize`` (a ``VecNormalize``) its arguments (JSON key ``normalize``) and its state
-    blob (member ``normalize_state.bin``)."""
+    blob (member ``normalize_state.bin``); ``tensors``: {member name: tensor}, written as further npy members."""
     import torch
     mv, step = opt.state()
     sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
@@ -283,10 +301,120 @@ def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iterati
             z.writestr("curriculum_state.bin", curriculum.state())
         if normalize is not None:
             z.writestr("normalize_state.bin", normalize.state())
+        for name, x in (tensors or {}).items():
+            z.writestr(name, npy(x.detach().cpu().numpy()))
     return path
 
 
-class PPO:
+def read_checkpoint(path, learning_rate=None, clip_range=None, needs=(), refusal="not a windgym_amd PPO checkpoint"):
+    """The zip of :func:`write_checkpoint` -> (the JSON, {member name: npy members as arrays, every other member as bytes}).
+    ``learning_rate`` / ``clip_range``: the schedules again when the run was saved with callables — the JSON's ``hyper`` comes back with
+    them filled in, and a stored ``None`` with nothing passed is a ``ValueError``.  A zip without the JSON or one of the members
+    ``needs`` is a ``ValueError(refusal)``."""
+    with zipfile.ZipFile(path) as z:
+        names = z.namelist()
+        if any(k not in names for k in ("windgym_ppo.json",) + tuple(needs)):
+            raise ValueError(refusal)
+        meta = json.loads(z.read("windgym_ppo.json").decode())
+        members = {k: z.read(k) for k in names if k != "windgym_ppo.json"}
+    members = {k: np.load(io.BytesIO(v)) if k.endswith(".npy") else v for k, v in members.items()}
+    for k, v in (("learning_rate", learning_rate), ("clip_range", clip_range)):
+        if v is not None:
+            meta["hyper"][k] = v
+        elif meta["hyper"][k] is None:
+            raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
+    return meta, members
+
+
+class Trainer:
+    """What :class:`PPO` and ``recurrent_ppo.RecurrentPPO`` share: the refusals, the hyper-parameters and schedules, the seeded
+    permutation generator and the update's buffers, ``learn``, the log record, ``predict`` and the counters of a checkpoint.  A
+    subclass sets ``policy`` / ``venv`` / ``torch`` / ``opt`` / ``n_rows`` / ``n_env_steps`` / ``batch_size`` and has ``collect`` and
+    ``train``; ``curriculum`` / ``normalize`` / ``critic`` stay ``None`` where a trainer offers none."""
+
+    curriculum = normalize = critic = None
+
+    def _setup(self, n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
+               normalize_advantage, seed, target_kl, clip_range_vf, use_sde):
+        for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
+            if v is not None:
+                raise NotImplementedError(f"{name} is not implemented")
+        if use_sde:
+            raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
+        check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm)
+        self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
+        self.n_steps, self.n_epochs = int(n_steps), int(n_epochs)
+        self.gamma, self.gae_lambda, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(ent_coef), float(vf_coef)
+        self.max_grad_norm, self.normalize_advantage = float(max_grad_norm), bool(normalize_advantage)
+        self.learning_rate, self.clip_range, self.seed = learning_rate, clip_range, seed
+        self.num_timesteps, self.iteration, self.log = 0, 0, []
+
+    def _alloc(self, perm_width, adv_shape, n_minibatches):
+        """The generator of the permutations (seeded) and the buffers of one update: ``_perm [n_epochs, perm_width]``, ``_adv`` /
+        ``_ret [*adv_shape]``, ``_stats [n_epochs, n_minibatches, 8]``."""
+        t, dev = self.torch, self.policy.device
+        self._gen = t.Generator(device=dev)
+        self._gen.manual_seed(0 if self.seed is None else int(self.seed))
+        self._perm = t.zeros((self.n_epochs, perm_width), dtype=t.int32, device=dev)
+        self._adv = t.zeros(adv_shape, dtype=t.float32, device=dev)
+        self._ret = t.zeros_like(self._adv)
+        self._stats = t.zeros((self.n_epochs, n_minibatches, 8), dtype=t.float32, device=dev)
+
+    def learn(self, total_timesteps, callback=None, log_interval=1, reset_num_timesteps=True):
+        """Iterations of rollout + update until ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``:
+        that many more).  ``callback(trainer) -> bool`` runs once per iteration; False stops.  Every ``log_interval``-th iteration
+        appends a record to ``self.log`` (one device-to-host copy; ``log_interval=None``: never, and no synchronisation)."""
+        return learn_loop(self, total_timesteps, callback, log_interval, reset_num_timesteps,
+                          lambda progress: (float(self._lr(progress)), float(self._clip(progress))), self._record)
+
+    def _record(self, out, stats, lr, clip, fps):
+        from .binding import PPO_STATS
+        from .parallel import METRIC_NAMES, derive
+        t = self.torch
+        ret, val = self._ret.double(), out["value"].double()
+        ev = 1.0 - (ret - val).var() / ret.var()
+        parts = [stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)]
+        if self.curriculum is not None:
+            parts += [out["curriculum_weight"].mean().reshape(1), out["yaw_diff"].double().mean().reshape(1)]
+        if self.normalize is not None:
+            parts += [out["reward"].double().mean().reshape(1)]
+        vec = t.cat(parts)
+        host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
+        rec = dict(zip(PPO_STATS, host[:8].tolist()))
+        rec["explained_variance"] = float(host[8])
+        m = derive(host[9:9 + len(METRIC_NAMES)])
+        rec.update(iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr, clip_range=clip,
+                   n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
+                   mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"], fps=fps())
+        if self.curriculum is not None:
+            rec.update(curriculum_weight=float(host[-2]), mean_yaw_diff=float(host[-1]))
+        if self.normalize is not None:
+            rec.update(mean_norm_reward=float(host[-1]), ret_rms_var=self.normalize.ret_rms[1])      # (the statistics: a copy of their own)
+        return rec
+
+    def predict(self, obs, state=None, episode_start=None, deterministic=False):
+        if self.normalize is not None:
+            obs = self.normalize.normalize_obs(obs)
+        return self.policy.predict(obs, state, episode_start, deterministic)
+
+    def save(self, path, tensors=None):
+        """Everything a bit-identical resume needs except the env itself (the class docstring states the format)."""
+        return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
+                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps, self.curriculum,
+                                self.normalize, tensors)
+
+    def _restore(self, meta, members):
+        """Adam's state, the generator and the counters of a checkpoint (:func:`read_checkpoint`)."""
+        self.opt.load_state(members["adam_state.npy"], meta["adam_step"])
+        self._gen.set_state(self.torch.from_numpy(members["generator_state.npy"]))
+        self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
+        self.venv._policy_steps = int(meta["env_policy_steps"])
+
+    def close(self):
+        self.opt.close()
+
+
+class PPO(Trainer):
     """Proximal policy optimisation with stable-baselines3's argument names and defaults, on a ``WindFarmVecEnv``, or on a
     ``WindFarmVecEnvMulti`` with ONE policy shared by the turbines (``obs_len -> 1``): there a row is an AGENT row — ``n_rows``
     = ``n_steps * num_envs * n_turb``, the ``batch_size`` default and the permutations are in agent rows, advantages come
@@ -328,13 +456,9 @@ class PPO:
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
                  seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None, normalize=None):
         refuse_recurrent(policy, "PPO")
-        for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
-            if v is not None:
-                raise NotImplementedError(f"{name} is not implemented")
-        if use_sde:
-            raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
-        check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm)
-        n_steps, n_epochs = int(n_steps), int(n_epochs)
+        self._setup(n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
+                    normalize_advantage, seed, target_kl, clip_range_vf, use_sde)
+        n_steps = self.n_steps
         if normalize is not None:
             from .normalize import VecNormalize, check_env
             if curriculum is not None:
@@ -349,7 +473,6 @@ class PPO:
         n_agents = int(venv.n_turb) if multi else 1
         n_rows = n_steps * int(venv.num_envs) * n_agents
         batch_size = check_batch_size(batch_size, n_rows, f"n_steps * num_envs{' * n_turb' if multi else ''}")
-        self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
         if isinstance(policy, str) and policy != "MlpPolicy":
             raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy'")
         if policy_kwargs and not isinstance(policy, str):
@@ -379,21 +502,10 @@ class PPO:
                              f"({'central' if central else 'agent'}): with a policy object the mode is the policy's")
         self.central, self.critic = central, "central" if central else "agent" if multi else None
         self.policy, self.venv, self.torch = policy, venv, policy.torch
-        self.n_steps, self.batch_size, self.n_epochs, self.n_rows = n_steps, batch_size, n_epochs, n_rows
+        self.batch_size, self.n_rows = batch_size, n_rows
         self.multi, self.n_agents, self.n_env_steps = multi, n_agents, n_steps * int(venv.num_envs)
-        self.gamma, self.gae_lambda, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(ent_coef), float(vf_coef)
-        self.max_grad_norm, self.normalize_advantage = float(max_grad_norm), bool(normalize_advantage)
-        self.learning_rate, self.clip_range = learning_rate, clip_range
-        self.seed = seed
         self.opt = PPOOptimizer(policy)
-        t = self.torch
-        self._gen = t.Generator(device=policy.device)
-        self._gen.manual_seed(0 if seed is None else int(seed))
-        self._perm = t.zeros((n_epochs, n_rows), dtype=t.int32, device=policy.device)
-        self._adv = t.zeros((n_steps, venv.num_envs) + ((n_agents,) if multi and not central else ()), dtype=t.float32, device=policy.device)
-        self._ret = t.zeros_like(self._adv)
-        self._stats = t.zeros((n_epochs, -(-n_rows // batch_size), 8), dtype=t.float32, device=policy.device)
-        self.num_timesteps, self.iteration, self.log = 0, 0, []
+        self._alloc(n_rows, (n_steps, venv.num_envs) + ((n_agents,) if multi and not central else ()), -(-n_rows // batch_size))
         self._owns_curriculum = isinstance(curriculum, dict)       # built here: closed with the trainer
         if self._owns_curriculum:
             from .curriculum import YawCurriculum
@@ -444,91 +556,32 @@ class PPO:
                                ent_coef=self.ent_coef, normalize_advantage=self.normalize_advantage,
                                learning_rate=learning_rate, max_grad_norm=self.max_grad_norm, stats=self._stats, **shared)
 
-    def learn(self, total_timesteps, callback=None, log_interval=1, reset_num_timesteps=True):
-        """Iterations of rollout + update until ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``:
-        that many more).  ``callback(ppo) -> bool`` runs once per iteration; False stops.  Every ``log_interval``-th iteration
-        appends a record to ``self.log`` (one device-to-host copy; ``log_interval=None``: never, and no synchronisation)."""
-        return learn_loop(self, total_timesteps, callback, log_interval, reset_num_timesteps,
-                          lambda progress: (float(self._lr(progress)), float(self._clip(progress))), self._record)
-
-    def _record(self, out, stats, lr, clip, fps):
-        from .binding import PPO_STATS
-        from .parallel import METRIC_NAMES, derive
-        t = self.torch
-        ret, val = self._ret.double(), out["value"].double()
-        ev = 1.0 - (ret - val).var() / ret.var()
-        parts = [stats.double().mean(dim=(0, 1)), ev.reshape(1), self.venv.batch.metrics(reset_after=True).double().reshape(-1)]
-        if self.curriculum is not None:
-            parts += [out["curriculum_weight"].mean().reshape(1), out["yaw_diff"].double().mean().reshape(1)]
-        if self.normalize is not None:
-            parts += [out["reward"].double().mean().reshape(1)]
-        vec = t.cat(parts)
-        host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
-        rec = dict(zip(PPO_STATS, host[:8].tolist()))
-        rec["explained_variance"] = float(host[8])
-        m = derive(host[9:9 + len(METRIC_NAMES)])
-        rec.update(iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr, clip_range=clip,
-                   n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
-                   mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"], fps=fps())
-        if self.curriculum is not None:
-            rec.update(curriculum_weight=float(host[-2]), mean_yaw_diff=float(host[-1]))
-        if self.normalize is not None:
-            rec.update(mean_norm_reward=float(host[-1]), ret_rms_var=self.normalize.ret_rms[1])      # (the statistics: a copy of their own)
-        return rec
-
-    def predict(self, obs, state=None, episode_start=None, deterministic=False):
-        if self.normalize is not None:
-            obs = self.normalize.normalize_obs(obs)
-        return self.policy.predict(obs, state, episode_start, deterministic)
-
     # -- checkpoints ----------------------------------------------------------------------------------------------
-    def save(self, path):
-        """Everything a bit-identical resume needs except the env itself (see the class docstring for the format)."""
-        return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
-                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps, self.curriculum,
-                                self.normalize)
-
     @classmethod
     def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
         """Resume: the policy, Adam's state, the permutation generator and every counter continue where ``save`` left them, so
         that on an env in the same state ``learn(..., reset_num_timesteps=False)`` computes what the uninterrupted run would
         have.  ``learning_rate`` / ``clip_range``: the schedules again, when the saved run used callables."""
-        import torch
         from .policy import read_sb3_zip
-        with zipfile.ZipFile(path) as z:
-            if "windgym_ppo.json" not in z.namelist():
-                raise ValueError("not a windgym_amd PPO checkpoint (for an SB3 zip use MlpPolicy.from_sb3_zip)")
-            meta = json.loads(z.read("windgym_ppo.json").decode())
-            mv = np.load(io.BytesIO(z.read("adam_state.npy")))
-            gen = np.load(io.BytesIO(z.read("generator_state.npy")))
-            cur_state = z.read("curriculum_state.bin") if "curriculum_state.bin" in z.namelist() else None
-            norm_state = z.read("normalize_state.bin") if "normalize_state.bin" in z.namelist() else None
+        meta, members = read_checkpoint(path, learning_rate, clip_range,
+                                        refusal="not a windgym_amd PPO checkpoint (for an SB3 zip use MlpPolicy.from_sb3_zip)")
         desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
         pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
                         device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"],
                         n_in_vf=desc["n_in_vf"])
         pol.load_state_dict(tensors)
         pol.counter = int(meta["policy_counter"])
-        hyper = dict(meta["hyper"])
-        for k, v in (("learning_rate", learning_rate), ("clip_range", clip_range)):
-            if v is not None:
-                hyper[k] = v
-            elif hyper[k] is None:
-                raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
         self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), curriculum=meta.get("curriculum"),
-                   normalize=meta.get("normalize"), **hyper)   # (no key: written before there was one)
-        if self.normalize is not None and norm_state is not None:
-            self.normalize.load_state(norm_state)
-        if self.curriculum is not None and cur_state is not None:
-            self.curriculum.load_state(cur_state)
-        self.opt.load_state(mv, meta["adam_step"])
-        self._gen.set_state(torch.from_numpy(gen))
-        self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
-        venv._policy_steps = int(meta["env_policy_steps"])
+                   normalize=meta.get("normalize"), **meta["hyper"])   # (no key: written before there was one)
+        if self.normalize is not None and "normalize_state.bin" in members:
+            self.normalize.load_state(members["normalize_state.bin"])
+        if self.curriculum is not None and "curriculum_state.bin" in members:
+            self.curriculum.load_state(members["curriculum_state.bin"])
+        self._restore(meta, members)
         return self
 
     def close(self):
-        self.opt.close()
+        super().close()
         if self._owns_curriculum:
             self.curriculum.close()
         if self._owns_normalize:

@@ -21,15 +21,10 @@ fallback: without the built library or a GPU the constructors raise.
 from __future__ import annotations
 
 import ctypes as C
-import io
-import json
 import weakref
-import zipfile
-
-import numpy as np
 
 from .policy import device_tensor
-from .ppo import HYPER, PPO, PPOOptimizer, _schedule, check_hyper, sb3_orthogonal_init, write_checkpoint
+from .ppo import HandleOptimizer, Trainer, read_checkpoint, sb3_orthogonal_init
 from .recurrent import MlpLstmPolicy
 
 
@@ -48,39 +43,20 @@ def envs_per_minibatch(batch_size, n_steps, num_envs):
     return batch_size // n_steps
 
 
-class RecurrentPPOOptimizer:
+class RecurrentPPOOptimizer(HandleOptimizer):
     """The ``wg_lstm_ppo`` handle of one :class:`MlpLstmPolicy` for minibatches of up to ``max_envs`` envs x ``max_steps`` steps: Adam's
     state over ``policy.params`` and the buffers of the sequence kernels.  A ROLLOUT is the dict of ``venv.rollout(policy, T)`` with
-    ``advantage`` / ``returns`` ``[T, B]`` added.  All methods enqueue on torch's current stream and synchronise nothing (``state()`` /
-    ``load_state()`` excepted)."""
+    ``advantage`` / ``returns`` ``[T, B]`` added."""
 
-    gae = PPOOptimizer.gae
-    _f32 = PPOOptimizer._f32
-    _hyper = staticmethod(PPOOptimizer._hyper)
+    prefix, index_is = "wg_lstm_ppo", "env list"
 
     def __init__(self, policy, max_steps, max_envs):
-        from .binding import _chk
         if not getattr(policy, "recurrent", False):
             raise ValueError("RecurrentPPOOptimizer needs a recurrent policy (MlpLstmPolicy); PPOOptimizer trains an MlpPolicy")
-        self.policy, self.L, self._chk, self.torch = policy, policy.L, _chk, policy.torch
-        h = C.c_void_p()
-        _chk(self.L.wg_lstm_ppo_create(policy._lstm, policy.mlp._h, int(max_steps), int(max_envs), C.byref(h)), "wg_lstm_ppo_create")
-        self._h = h
+        self._open(policy, policy._lstm, policy.mlp._h, int(max_steps), int(max_envs))
         n = C.c_size_t()
-        _chk(self.L.wg_lstm_ppo_n_params(self._h, C.byref(n)), "wg_lstm_ppo_n_params")
+        self._call("n_params", self._h, C.byref(n))
         assert int(n.value) == policy.params.numel()
-        self.grad_buf = self.torch.zeros_like(policy.params)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_lstm_ppo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _batch(self, roll):
         from .binding import CLstmPpoBatch
@@ -99,11 +75,6 @@ class RecurrentPPOOptimizer:
         return CLstmPpoBatch(obs.data_ptr(), roll["raw"].data_ptr(), roll["logp"].data_ptr(), roll["advantage"].data_ptr(),
                              roll["returns"].data_ptr(), es.data_ptr(), s0.data_ptr(), int(T), int(B)), T, B
 
-    def _index(self, index, n_min):
-        if not (device_tensor(index, self.torch.int32) and index.numel() >= n_min):
-            raise ValueError("the env list / permutation must be a contiguous int32 CUDA tensor")
-        return index
-
     def grad(self, roll, envs, *, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True, out=None, stats=None):
         """wg_lstm_ppo_grad: the minibatch of the envs ``envs`` (int32 CUDA) with all their steps -> (flat gradient ``[n_params]``,
         statistics ``[8]`` in the order of binding.PPO_STATS)."""
@@ -116,12 +87,6 @@ class RecurrentPPOOptimizer:
                                           C.byref(self._hyper(clip_range, vf_coef, ent_coef, normalize_advantage)), g.data_ptr(),
                                           st.data_ptr(), self.policy._stream()), "wg_lstm_ppo_grad")
         return g, st
-
-    def apply(self, grad=None, learning_rate=3e-4, max_grad_norm=0.5):
-        """wg_lstm_ppo_apply: clip, Adam on ``policy.params`` in place, repack — ``policy.act`` afterwards uses the new weights."""
-        g = self.grad_buf if grad is None else grad
-        self._chk(self.L.wg_lstm_ppo_apply(self._h, self.policy.params.data_ptr(), g.data_ptr(), float(learning_rate), float(max_grad_norm),
-                                           self.policy._stream()), "wg_lstm_ppo_apply")
 
     def update(self, roll, perm, envs_per_batch, *, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True,
                learning_rate=3e-4, max_grad_norm=0.5, stats=None):
@@ -139,19 +104,8 @@ class RecurrentPPOOptimizer:
                                             float(max_grad_norm), st.data_ptr(), self.policy._stream()), "wg_lstm_ppo_update")
         return st
 
-    def state(self):
-        """(Adam's m then v as one float32 numpy vector ``[2 n_params]``, step count)."""
-        n = 2 * self.policy.params.numel()
-        mv, step = np.zeros(n, np.float32), C.c_uint64()
-        self._chk(self.L.wg_lstm_ppo_get_state(self._h, mv.ctypes.data_as(C.c_void_p), n, C.byref(step)), "wg_lstm_ppo_get_state")
-        return mv, int(step.value)
 
-    def load_state(self, mv, step):
-        mv = np.ascontiguousarray(mv, dtype=np.float32)
-        self._chk(self.L.wg_lstm_ppo_set_state(self._h, mv.ctypes.data_as(C.c_void_p), mv.size, int(step)), "wg_lstm_ppo_set_state")
-
-
-class RecurrentPPO:
+class RecurrentPPO(Trainer):
     """sb3-contrib's ``RecurrentPPO`` on a ``WindFarmVecEnv``: :class:`~windgym_amd.ppo.PPO`'s arguments, defaults, schedules, ``log``
     records, ``learn`` callback and checkpoint layout, for an :class:`MlpLstmPolicy` (the module docstring states the minibatch rule
     and how it relates to sb3-contrib's).
@@ -172,19 +126,11 @@ class RecurrentPPO:
     Adam's state, the generator and the counters — plus the pair's LSTM state (``lstm_state.npy``) and the pending episode starts
     (``episode_start.npy``); ``load`` resumes on the same env object bit-identically."""
 
-    learn = PPO.learn
-    _record = PPO._record
-    curriculum = normalize = None
-    critic = None
-
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
                  seed=None, target_kl=None, clip_range_vf=None, use_sde=False):
-        for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
-            if v is not None:
-                raise NotImplementedError(f"{name} is not implemented")
-        if use_sde:
-            raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
+        self._setup(n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
+                    normalize_advantage, seed, target_kl, clip_range_vf, use_sde)
         if getattr(venv, "possible_agents", None) is not None:
             raise NotImplementedError("RecurrentPPO on a WindFarmVecEnvMulti (a recurrent policy shared by the turbines) is not implemented")
         if isinstance(policy, str):
@@ -194,31 +140,18 @@ class RecurrentPPO:
             raise ValueError("RecurrentPPO needs a recurrent policy (MlpLstmPolicy): PPO trains an MlpPolicy")
         elif policy_kwargs:
             raise ValueError("policy_kwargs only applies to policy='MlpLstmPolicy'")
-        check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm)
-        n_steps, n_epochs, B = int(n_steps), int(n_epochs), int(venv.num_envs)
+        n_steps, B = self.n_steps, int(venv.num_envs)
         self.envs_per_batch = envs_per_minibatch(batch_size, n_steps, B)
-        self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
         want = (int(venv.batch.obs_dim), int(venv.n_turb))
         if isinstance(policy, str):
             policy = self._build_policy(venv, want, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
         if (policy.n_in, policy.n_out) != want:
             raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, this env needs {want[0]} -> {want[1]}")
         self.policy, self.venv, self.torch = policy, venv, policy.torch
-        self.n_steps, self.batch_size, self.n_epochs = n_steps, self.envs_per_batch * n_steps, n_epochs
+        self.batch_size = self.envs_per_batch * n_steps
         self.n_rows = self.n_env_steps = n_steps * B
-        self.gamma, self.gae_lambda, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(ent_coef), float(vf_coef)
-        self.max_grad_norm, self.normalize_advantage = float(max_grad_norm), bool(normalize_advantage)
-        self.learning_rate, self.clip_range = learning_rate, clip_range
-        self.seed = seed
         self.opt = RecurrentPPOOptimizer(policy, n_steps, self.envs_per_batch)
-        t = self.torch
-        self._gen = t.Generator(device=policy.device)
-        self._gen.manual_seed(0 if seed is None else int(seed))
-        self._perm = t.zeros((n_epochs, B), dtype=t.int32, device=policy.device)
-        self._adv = t.zeros((n_steps, B), dtype=t.float32, device=policy.device)
-        self._ret = t.zeros_like(self._adv)
-        self._stats = t.zeros((n_epochs, -(-B // self.envs_per_batch), 8), dtype=t.float32, device=policy.device)
-        self.num_timesteps, self.iteration, self.log = 0, 0, []
+        self._alloc(B, (n_steps, B), -(-B // self.envs_per_batch))
 
     @staticmethod
     def _build_policy(venv, shape, kw, seed):
@@ -258,9 +191,6 @@ class RecurrentPPO:
                                normalize_advantage=self.normalize_advantage, learning_rate=learning_rate, max_grad_norm=self.max_grad_norm,
                                stats=self._stats)
 
-    def predict(self, obs, state=None, episode_start=None, deterministic=False):
-        return self.policy.predict(obs, state, episode_start, deterministic)
-
     # -- checkpoints ----------------------------------------------------------------------------------------------
     def _pair(self):
         """The env's entry of this (policy, env) pair — [weakref, LSTM state, pending episode starts, buffers] — made as
@@ -274,47 +204,23 @@ class RecurrentPPO:
 
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself (the class docstring)."""
-        write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed, self.num_timesteps,
-                         self.iteration, self.log, None, self.venv._policy_steps)
         ent = self._pair()
-        with zipfile.ZipFile(path, "a", zipfile.ZIP_DEFLATED) as z:
-            for name, x in (("lstm_state.npy", ent[1]), ("episode_start.npy", ent[2])):
-                b = io.BytesIO()
-                np.save(b, x.detach().cpu().numpy())
-                z.writestr(name, b.getvalue())
-        return path
+        return super().save(path, {"lstm_state.npy": ent[1], "episode_start.npy": ent[2]})
 
     @classmethod
     def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
         """Resume: the policy, Adam's state, the generator, every counter and the pair's LSTM state continue where ``save`` left them.
         ``learning_rate`` / ``clip_range``: the schedules again, when the saved run used callables."""
         import torch
-        with zipfile.ZipFile(path) as z:
-            names = z.namelist()
-            if "windgym_ppo.json" not in names or "lstm_state.npy" not in names:
-                raise ValueError("not a windgym_amd RecurrentPPO checkpoint (an sb3-contrib zip loads with MlpLstmPolicy.from_sb3_zip, "
-                                 "a PPO checkpoint with PPO.load)")
-            meta = json.loads(z.read("windgym_ppo.json").decode())
-            mv, gen, state, starts = (np.load(io.BytesIO(z.read(k))) for k in ("adam_state.npy", "generator_state.npy", "lstm_state.npy",
-                                                                               "episode_start.npy"))
+        meta, members = read_checkpoint(path, learning_rate, clip_range, needs=("lstm_state.npy",),
+                                        refusal="not a windgym_amd RecurrentPPO checkpoint (an sb3-contrib zip loads with "
+                                                "MlpLstmPolicy.from_sb3_zip, a PPO checkpoint with PPO.load)")
         pol = MlpLstmPolicy.from_sb3_zip(path, activation=meta["desc"]["activation"], device=venv.batch.device.index if device is None else device,
                                          seed=meta["policy_seed"])
         pol.counter = int(meta["policy_counter"])
-        hyper = dict(meta["hyper"])
-        for k, v in (("learning_rate", learning_rate), ("clip_range", clip_range)):
-            if v is not None:
-                hyper[k] = v
-            elif hyper[k] is None:
-                raise ValueError(f"the checkpoint was trained with a {k} schedule: pass it to load()")
-        self = cls(pol, venv, seed=meta["seed"], **hyper)
-        self.opt.load_state(mv, meta["adam_step"])
-        self._gen.set_state(torch.from_numpy(gen))
-        self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
-        venv._policy_steps = int(meta["env_policy_steps"])
+        self = cls(pol, venv, seed=meta["seed"], **meta["hyper"])
+        self._restore(meta, members)
         ent = self._pair()
-        ent[1].copy_(torch.from_numpy(state))
-        ent[2].copy_(torch.from_numpy(starts))
+        ent[1].copy_(torch.from_numpy(members["lstm_state.npy"]))
+        ent[2].copy_(torch.from_numpy(members["episode_start.npy"]))
         return self
-
-    def close(self):
-        self.opt.close()
