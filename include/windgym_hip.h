@@ -1019,6 +1019,64 @@ int wg_lstm_ppo_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, f
 int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
                        int envs_per_batch, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Populations of recurrent policies: P pairs (wg_lstm, wg_policy) of ONE architecture — the same n_in, hidden size, number of
+ * LSTMs, heads and activation — collected and trained in the kernel launches of one (a seed sweep of small recurrent runs, each of
+ * which leaves most of the device idle: one workgroup of the sequence kernels owns 32 envs for all T steps).  The population
+ * contract above holds unchanged: member m owns rows / envs [m * Bm, (m + 1) * Bm), Bm = B / P, of every [.., B, ..] buffer, and
+ * every entry below is bit-identical, per member, to the loop of single calls its comment names; a member's results depend neither
+ * on P, nor on m, nor on what the other members hold (no float atomics, every sum in the single call's order).  The members stay
+ * ordinary handles.  LSTM STATE of a population: [P][nets][2][Bm][H] — entry m is exactly the member's own wg_lstm_step state.
+ * Used on ONE stream at a time.  Out of scope: wg_rollout_multi, members of differing architectures, HIP-graph capture.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_lstm_pop_s* wg_lstm_pop;
+
+/* lstms[m] / heads[m]: member m's pair, as wg_lstm_act takes it; opts[m] = the wg_lstm_ppo created for that pair, or opts = NULL
+ * for a population that only acts.  The handles must outlive the population.  WG_ERR_INVALID (the message names the member): P
+ * outside 1 .. WG_POP_MAX; a member with another n_in, hidden size, number of nets or head architecture than member 0; a head
+ * that does not map the hidden size with its critic on the same width; another device; the same handle twice; an opts[m] made
+ * for another pair.                                                                                                        */
+int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, const wg_lstm_ppo* opts, int P, wg_lstm_pop* out);
+int wg_lstm_pop_destroy(wg_lstm_pop q);
+
+/* ONE launch of k_lstm and ONE of the policy kernel for all members: bit-identical to, for m in 0 .. P-1 with Bm = n_rows / P,
+ *     wg_lstm_act(lstms[m], heads[m], Bm, x_dev + m * Bm * n_in, episode_start_dev + m * Bm, state_in_dev + m * S, state_out_dev + m * S,
+ *                 <h rows>, deterministic, seeds[m], counter, row_offsets[m], action_dev + m * Bm * n_out, raw_dev + m * Bm * n_out,
+ *                 logp_dev + m * Bm, value_dev + m * Bm, stream)                       S = nets * 2 * Bm * H floats
+ * h_dev [2][n_rows][H] is scratch (member m's h rows are rows [m * Bm, (m + 1) * Bm) of each plane).  Null outputs are skipped for
+ * every member; row_offsets = NULL: all 0.  WG_ERR_INVALID, nothing enqueued: P does not divide n_rows; seeds = NULL with an actor
+ * output wanted; what wg_lstm_act refuses.                                                                                  */
+int wg_lstm_pop_act(wg_lstm_pop q, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
+                    float* state_out_dev, float* h_dev, int deterministic, const uint64_t* seeds, uint64_t counter,
+                    const uint64_t* row_offsets, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream);
+
+/* wg_rollout_lstm with the population in the pair's place: the same buffers [T (+ 1), B, ..], member m on the envs (columns)
+ * [m * Bm, (m + 1) * Bm); lstm_bufs->state and ->state0 in the population's layout [P][nets][2][Bm][H].  Bit-identical (buffers, the
+ * handle's state, the LSTM state) to wg_rollout_lstm's documented loop with each wg_lstm_step / wg_policy_act replaced by the P
+ * calls on the members' rows (noise key of member m: seeds[m], counter0 + t, row_offsets[m] + its env's index in the member) —
+ * per step the launches of wg_rollout_lstm, no more.  WG_ERR_INVALID: P does not divide the handle's n_envs; what
+ * wg_rollout_lstm refuses.                                                                                                 */
+int wg_lstm_pop_rollout(wg_handle h, wg_lstm_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
+                        const uint64_t* row_offsets, const wg_rollout_bufs* bufs, const wg_rollout_lstm_bufs* lstm_bufs, void* stream);
+
+/* sb3-contrib's RecurrentPPO.train for every member on ONE rollout, in the launches of one wg_lstm_ppo_update.  `batch` is the
+ * whole rollout [T, B] as wg_lstm_pop_rollout leaves it (lstm_state0 in the population's layout), advantage / returns from
+ * wg_gae_pop; Bm = B / P envs per member; perm_dev int32[P, n_epochs, Bm] holds per member and epoch a permutation of ITS envs as
+ * GLOBAL env ids (env e of member m: m * Bm + e); the same n_mb = ceil(Bm / envs_per_batch) minibatches for every member (the
+ * launches run in lockstep); hp, lr and max_grad_norm are host arrays [P]; params_dev[m] (host array of device pointers) is the flat
+ * vector member m's handles were last given; stats_out (device, may be NULL) is wg_ppo_stats[P, n_epochs, n_mb].  Bit-identical,
+ * per member, to
+ *     wg_lstm_ppo_update(opts[m], params_dev[m], <the member's columns as a contiguous batch [T, Bm], lstm_state0 = entry m>,
+ *                        <the same permutations as local env ids>, n_epochs, envs_per_batch, &hp[m], lr[m], max_grad_norm[m],
+ *                        stats_out + m * n_epochs * n_mb, stream)
+ * and Adam's step count advances in every member's own wg_lstm_ppo.  An env id outside [0, B) is a column of zeros, as in
+ * wg_lstm_ppo_grad; one inside [0, B) but outside the member's own envs is not checked (nothing is read out of bounds, but the rows are
+ * another member's).  WG_ERR_INVALID / WG_ERR_UNSUPPORTED, nothing enqueued: a population created without opts, P not dividing B,
+ * what wg_lstm_ppo_update refuses (T > T_max or envs_per_batch > Bm_max of a member's handle: the message names the member).  */
+int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const wg_lstm_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
+                       int envs_per_batch, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm, wg_ppo_stats* stats_out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,16 @@ Legs, each in a child process of its own under a time limit of its own (`--leg-t
            the rollout (a fused sequence call cannot reset single rows mid-way), so it is a lower bound of what a correct trainer on
            that path costs; reported with no bar.
 
+With ``--members P`` the sizes are envs PER MEMBER and the legs are the two ways to run P recurrent runs of that size, one JSON line
+per size (``rollout_*_ms`` / ``train_*_ms`` of ONE iteration of all P runs, medians of `--reps`, and their ratios):
+
+  pop      a RecurrentPPOPopulation of P members on P x envs envs: venv.rollout + wg_gae_pop, and ONE wg_lstm_pop_update
+  seq      the same P runs one after another: P RecurrentPPO objects, each on a shard env of its own — the sum of their rollouts (+
+           wg_gae) and of their wg_lstm_ppo_update calls.  It uses single-policy entries only, so it also runs from a checkout of an
+           earlier commit (`--legs seq`), which is how the population is compared against the build before it.
+
 usage: python tools/bench_recurrent_ppo.py [--sizes 4096x256 256x64] [--n-steps 128] [--epochs 10] [--minibatches 4] [--reps 3]
+       python tools/bench_recurrent_ppo.py --members 16 --sizes 256x64 [--legs pop seq]
 """
 import argparse
 import json
@@ -136,6 +145,111 @@ def leg(args):
     print("LEG " + json.dumps(out))
 
 
+def members_leg(args):
+    """The `pop` / `seq` leg of ``--members P``: P runs of `--leg-size` (envs per member x H) -> rollout and train of one iteration."""
+    import torch
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.turbine import V80
+    if not torch.cuda.is_available():
+        sys.exit("bench_recurrent_ppo.py: no HIP device (there is no CPU path to time)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    P = args.members
+    Bm, H = (int(x) for x in args.leg_size.split("x"))
+    T, E = args.n_steps, args.epochs
+    epb = -(-Bm // args.minibatches)
+    kw = dict(n_steps=T, n_epochs=E, batch_size=epb * T, policy_kwargs=dict(lstm_hidden_size=H))
+    seeds = [1234 + m for m in range(P)]
+
+    def env(n):
+        return WindFarmVecEnv(V80(), n, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
+                              n_passthrough=5, n_rotor_pts=16)
+    if args.leg == "pop":
+        from windgym_amd.recurrent_population import RecurrentPPOPopulation
+        venvs = [env(P * Bm)]
+        venvs[0].reset(seed=1234)
+        runs = [RecurrentPPOPopulation("MlpLstmPolicy", venvs[0], n_members=P, seed=seeds, **kw)]
+        policies, opts = runs[0].members, runs[0].opts
+    else:
+        from windgym_amd.recurrent_ppo import RecurrentPPO
+        venvs = [env(Bm).shard(m, P) for m in range(P)]
+        for v in venvs:
+            v.reset(seed=1234)
+        runs = [RecurrentPPO("MlpLstmPolicy", v, seed=s, **kw) for v, s in zip(venvs, seeds)]
+        policies, opts = [r.policy for r in runs], [r.opt for r in runs]
+    for v in venvs:
+        zero = torch.zeros((v.num_envs, v.n_turb), device=dev)
+        for _ in range(args.preroll):
+            v.step(zero)
+
+    def timed(fn, before=None):
+        ts = []
+        for i in range(args.reps + 1):               # (the first one warms up)
+            if before is not None:
+                before()
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return {"ms": statistics.median(ts[1:]), "ms_all": [round(x, 3) for x in ts[1:]]}
+
+    out = {"rollout": timed(lambda: [r.collect() for r in runs])}
+    rolls = [r.collect() for r in runs]
+    start = [p.params.clone() for p in policies]
+
+    def reset():                                      # every repetition trains the same weights from Adam's zero state
+        for p, o, w in zip(policies, opts, start):
+            with torch.no_grad():
+                p.params.copy_(w)
+            p.sync()
+            o.load_state(torch.zeros(2 * w.numel()).numpy(), 0)
+
+    def train():
+        for r, roll in zip(runs, rolls):
+            r.train(roll, [3e-4] * P if args.leg == "pop" else 3e-4, [0.2] * P if args.leg == "pop" else 0.2)
+    out["train"] = timed(train, reset)
+    for v in venvs:
+        v.batch.check()
+    for x in runs + list(policies) + venvs:
+        x.close()
+    print("LEG " + json.dumps(out))
+
+
+def members_main(args):
+    legs = [x for x in args.legs if x in ("pop", "seq")] or ["pop", "seq"]
+    for size in args.sizes:
+        Bm, H = (int(x) for x in size.split("x"))
+        res = {"metric": "%d recurrent PPO runs of %d envs x %d steps, LSTM H = %d, %d epochs x %d minibatches, 16-turbine farm, one GPU: a "
+                         "population (pop) against the runs one after another (seq), per iteration of all runs"
+                         % (args.members, Bm, args.n_steps, H, args.epochs, args.minibatches),
+               "members": args.members, "envs_per_member": Bm, "hidden": H, "n_steps": args.n_steps, "epochs": args.epochs,
+               "minibatches": args.minibatches}
+        for name in legs:
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--leg-size", size, "--members", str(args.members), "--n-steps",
+                   str(args.n_steps), "--epochs", str(args.epochs), "--minibatches", str(args.minibatches), "--reps", str(args.reps),
+                   "--preroll", str(args.preroll)]
+            try:
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.leg_timeout)
+                lines = [x for x in r.stdout.splitlines() if x.startswith("LEG ")]
+                got = json.loads(lines[-1][4:]) if r.returncode == 0 and lines else {"error": (r.stderr or r.stdout)[-400:]}
+            except subprocess.TimeoutExpired:
+                got = "timeout"
+            if isinstance(got, dict) and "train" in got:
+                for k in ("rollout", "train"):
+                    res["%s_%s_ms" % (k, name)], res["%s_%s_ms_all" % (k, name)] = got[k]["ms"], got[k]["ms_all"]
+            else:
+                res[name] = got
+                break                                            # a leg that hung or died: start nothing more on the device
+        for k in ("rollout", "train"):
+            if "%s_pop_ms" % k in res and "%s_seq_ms" % k in res:
+                res["%s_seq_over_pop" % k] = res["%s_seq_ms" % k] / res["%s_pop_ms" % k]
+        print(json.dumps(res), flush=True)
+        if any(k in res for k in legs):
+            break
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="*", default=["4096x256", "256x64"], help="<envs>x<lstm_hidden_size>")
@@ -147,9 +261,12 @@ def main():
     ap.add_argument("--preroll", type=int, default=300)
     ap.add_argument("--legs", nargs="*", default=["hip", "torch_a", "torch_b"])
     ap.add_argument("--leg-timeout", type=float, default=240.0, help="seconds each leg's process may take")
+    ap.add_argument("--members", type=int, default=0, help="P > 0: the sizes are envs per member, the legs `pop` and `seq` (module docstring)")
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--leg-size", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.members:
+        return members_leg(args) if args.leg else members_main(args)
     if args.leg:
         return leg(args)
     for size in args.sizes:

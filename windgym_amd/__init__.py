@@ -35,6 +35,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name in ("PPOPopulation", "Population"):
         from . import population
         return getattr(population, name)
+    if name in ("RecurrentPPOPopulation", "RecurrentPopulation"):
+        from . import recurrent_population
+        return getattr(recurrent_population, name)
     if name == "YawCurriculum":
         from .curriculum import YawCurriculum
         return YawCurriculum

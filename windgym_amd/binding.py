@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "wg_lstm_create", "wg_lstm_destroy", "wg_lstm_n_params", "wg_lstm_set_params", "wg_lstm_step", "wg_lstm_act", "wg_rollout_lstm",
     "wg_lstm_ppo_create", "wg_lstm_ppo_destroy", "wg_lstm_ppo_n_params", "wg_lstm_ppo_get_state", "wg_lstm_ppo_set_state",
     "wg_lstm_ppo_grad", "wg_lstm_ppo_apply", "wg_lstm_ppo_update",
+    "wg_lstm_pop_create", "wg_lstm_pop_destroy", "wg_lstm_pop_act", "wg_lstm_pop_rollout", "wg_lstm_pop_update",
 )
 
 _lib = None
@@ -247,6 +248,13 @@ def load_library():
                                    C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_lstm_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.c_int,
                                      C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.wg_lstm_pop_create.argtypes = [C.POINTER(C.c_void_p)] * 3 + [C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_lstm_pop_destroy.argtypes = [C.c_void_p]
+    L.wg_lstm_pop_act.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)] + [C.c_void_p] * 5
+    L.wg_lstm_pop_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.POINTER(CRolloutBufs), C.POINTER(CRolloutLstmBufs), C.c_void_p]
+    L.wg_lstm_pop_update.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.c_int,
+                                     C.POINTER(CPpoHyper), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -387,6 +395,18 @@ class HipBatch:
                               bufs["lstm_scratch"].data_ptr())
         _chk(self.L.wg_rollout_lstm(self._h, policy._lstm, policy.mlp._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
                                     C.byref(cb), C.byref(lb), self._stream()), "wg_rollout_lstm")
+
+    def rollout_lstm_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
+        """wg_lstm_pop_rollout, the arguments of :meth:`rollout_lstm` with a ``recurrent_population.RecurrentPopulation`` in the policy's
+        place (``lstm_state`` / ``lstm_state0`` ``[P, nets, 2, Bm, H]``): every member samples with the one ``seed``, member ``m``'s
+        noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
+        P, cb = pop.n_members, self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
+        Bm = self.B // P
+        lb = CRolloutLstmBufs(bufs["lstm_state"].data_ptr(), bufs["lstm_state0"].data_ptr(), bufs["episode_start"].data_ptr(),
+                              bufs["lstm_scratch"].data_ptr())
+        _chk(self.L.wg_lstm_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), (C.c_uint64 * P)(*[int(seed)] * P), counter0,
+                                        (C.c_uint64 * P)(*[int(row_offset) + m * Bm for m in range(P)]), C.byref(cb), C.byref(lb),
+                                        self._stream()), "wg_lstm_pop_rollout")
 
     def rollout_multi(self, *args):
         """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""

@@ -16,6 +16,7 @@
 #include "wg_plan.h"
 #include "wg_steady.h"
 #include "wg_policy.h"
+#include "wg_lstm.h"
 #include "wg_host.h"
 
 // Measurement / test hooks (environment variables that select kernel variants): honoured ONLY with WG_DEBUG_HOOKS=1 — a
@@ -834,6 +835,9 @@ struct RolloutRows {
     // in `lb`), and the policy, which maps the LSTM's hidden size, reads the h' rows of lb->scratch instead of the observations
     wg_lstm_s* lstm;
     const wg_rollout_lstm_bufs* lb;
+    // non-null: a population of recurrent policies (wg_lstm_pop_rollout) — `lstm` is member 0's (the members share its shape), the
+    // LSTMs' launches are wg_lstm_pop_step_ on lb's state in the population's layout, and `pop` is its heads' slot table
+    wg_lstm_pop_s* lpop;
 };
 
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
@@ -887,9 +891,12 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     float* const h_vf = two ? h_pi + sH : h_pi;
     float* const h_fin = g.lstm ? h_pi + 2 * sH : nullptr;
     // the critic's LSTM on the final rows of step t, from the state after step t, which stays as it is -> h_fin
+    auto lstm_step = [&](const float* x, const uint8_t* start, float* state_out, float* hp, float* hv, int net_mask) {
+        return g.lpop ? wg_lstm_pop_step_(g.lpop, B, x, start, g.lb->state, state_out, hp, hv, net_mask, stream)
+                      : wg_lstm_step(g.lstm, B, x, start, g.lb->state, state_out, hp, hv, net_mask, stream);
+    };
     auto lstm_final = [&](int t) {
-        return wg_lstm_step(g.lstm, B, o.final_obs + t * sBO, nullptr, g.lb->state, nullptr, two ? nullptr : h_fin, two ? h_fin : nullptr,
-                            two ? WG_LSTM_CRITIC : WG_LSTM_ACTOR, stream);
+        return lstm_step(o.final_obs + t * sBO, nullptr, nullptr, two ? nullptr : h_fin, two ? h_fin : nullptr, two ? WG_LSTM_CRITIC : WG_LSTM_ACTOR);
     };
     if (g.lstm && g.lb->state0 && n_steps > 0) {
         const hipError_t ce = hipMemcpyAsync(g.lb->state0, g.lb->state, sizeof(float) * (two ? 2 : 1) * 2 * sH, hipMemcpyDeviceToDevice, st);
@@ -908,9 +915,10 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
             // starts of step t > 0 are read where the step before wrote them, truncated[t - 1] = what episode_start[t] will hold)
             if (o.final_value && t > 0) rc = lstm_final(t - 1);
             if (!rc)
-                rc = wg_lstm_step(g.lstm, B, o.obs_multi + t * sRO, t == 0 ? g.lb->episode_start : o.truncated + (size_t)(t - 1) * B,
-                                  g.lb->state, g.lb->state, h_pi, two ? h_vf : nullptr, 0, stream);
-            if (!rc)
+                rc = lstm_step(o.obs_multi + t * sRO, t == 0 ? g.lb->episode_start : o.truncated + (size_t)(t - 1) * B, g.lb->state, h_pi,
+                               two ? h_vf : nullptr, two ? WG_LSTM_ACTOR | WG_LSTM_CRITIC : WG_LSTM_ACTOR);
+            if (!rc && g.pop) rc = wg_pop_launch_(g.pop, 1, t > 0, t, deterministic, counter0 + (uint64_t)t, stream);
+            else if (!rc)
                 rc = wg_policy_eval_(p, R, h_pi, deterministic, seed, counter0 + (uint64_t)t, row_offset, o.actions + t * sRN,
                                      o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
         } else if (g.pop)      // (the same rows, found through the population's slot table: step t's own and the final rows of t - 1)
@@ -1057,6 +1065,41 @@ extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_ste
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+}
+
+// A population of recurrent policies in the pair's place: the checks are wg_rollout_lstm's on member 0 (the members share one
+// architecture and device), the loop is rollout_loop with the members' LSTM launches and the heads' slot table.
+extern "C" int wg_lstm_pop_rollout(wg_handle h, wg_lstm_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
+                                   const uint64_t* row_offsets, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
+    if (!h || !q || !o || !lb || !seeds) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: null argument");
+    const int N = h->p.N, O = h->p.obs_dim, B = h->p.B;
+    wg_lstm_s* lstm = q->lstm[0];
+    wg_policy_s* p = q->head[0];
+    const int H = lstm->P.H;
+    if (lstm->P.n_in != O)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: the LSTMs read rows of " + std::to_string(lstm->P.n_in) + " inputs, the handle's obs_dim is " +
+                                        std::to_string(O));
+    if (q->device != h->device) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: population and handle live on different devices");
+    if (!lb->state || !lb->episode_start || !lb->scratch)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: lstm_bufs needs state, episode_start and scratch");
+    const RolloutRows g = {"wg_lstm_pop_rollout", "obs", 1, H, N,
+                           ": the heads read the LSTMs' hidden rows, and their hidden size / the handle's n_turb are " + std::to_string(H) + " / " +
+                               std::to_string(N),
+                           nullptr, false,
+                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
+                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
+                           1, H, o->obs, o->final_obs, "final_obs", &q->heads, nullptr, lstm, lb, q};
+    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
+    if (B % q->P != 0)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: the " + std::to_string(q->P) + " members own equal shares of the envs, and n_envs = " +
+                                        std::to_string(B) + " does not divide by " + std::to_string(q->P));
+    if (int rc = wg_use_device(h->device)) return rc;
+    float* const h_pi = lb->scratch;
+    const size_t sH = (size_t)B * H;
+    if (int rc = wg_lstm_pop_slots_(q, B, seeds, row_offsets, h_pi, lstm->P.n_nets == 2 ? h_pi + sH : h_pi, h_pi + 2 * sH, o->actions, o->raw, o->logp,
+                                    o->value, o->final_value, B, stream))
+        return rc;
+    return rollout_loop(h, p, n_steps, deterministic, 0, counter0, 0, g, stream);
 }
 
 extern "C" int wg_metrics(wg_handle h, float* out_dev, int reset_after, void* stream) {

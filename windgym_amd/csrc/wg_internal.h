@@ -14,6 +14,7 @@ struct WgPtrs;
 struct WgPopRows;
 struct WgPolicyP;
 struct WgPopMember;
+struct WgPopHeadRows;
 struct WgPacked;
 struct WgAdam;
 struct WgPpoGrad;
@@ -74,6 +75,24 @@ int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h
                        float* stats_out, void* stream);
 // k_policy_pack for each of the n_members rows of a member table (device)
 void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_members, void* stream);
+// wg_ppo.hip: wg_ppo_heads_grad_ for the n_members heads of a recurrent population in the launches of one — member m's scratch, flat
+// MLP parameters, gradient and stats slot are row m of `mt` (device), the rows it reads and the dh rows it writes row m of `rt`
+// (device), n rows each; `g0`: the gradient side of member 0's heads (one architecture: one LDS map, one grid); `mb`: the
+// minibatch's ordinal (its stats slot); any_norm: some member normalises its advantages
+int wg_ppo_heads_grad_pop_(const WgPpoGrad* g0, const WgPopMember* mt, const WgPopHeadRows* rt, int n_members, int any_norm, int n, int mb,
+                           void* stream);
+// Adam over each of the n_members rows of a member table (device): clipping by the member's own norm, then the step with the
+// member's own scalars step_size[m] / bc2_sqrt[m] (k_ppo_sumsq_pop + k_ppo_adam_pop) on vectors of n_flat floats
+int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, uint32_t n_flat, const float* step_size, const float* bc2_sqrt, void* stream);
+// wg_lstm.hip, populations of recurrent policies (wg_lstm.h): wg_lstm_step for every member in ONE launch of k_lstm_pop on n_rows =
+// P Bm rows; k_lstm_pack for every member in one launch (params_dev[m]: host array of the members' flat vectors); the heads' slot
+// table on the h rows of the running step (outputs strided by `step` floats-rows per rollout step, 0: one call)
+int wg_lstm_pop_step_(wg_lstm_pop q, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
+                      float* state_out_dev, float* h_pi_dev, float* h_vf_dev, int net_mask, void* stream);
+int wg_lstm_pack_pop_(wg_lstm_pop q, const float* const* params_dev, void* stream);
+int wg_lstm_pop_slots_(wg_lstm_pop q, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* h_pi, const float* h_vf,
+                       const float* h_fin, float* action, float* raw, float* logp, float* value, float* final_value, int64_t step,
+                       void* stream);
 // wg_flow.hip
 void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
 void wg_launch_windspeed(const FlowP* p, const FlowPtrs* d, int e, int farm, const float* xs, int nx, const float* ys, int ny, float z,

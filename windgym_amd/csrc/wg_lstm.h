@@ -76,4 +76,27 @@ struct wg_lstm_s {
     WgPacked w;                // [P.n_flat] / [P.n_packed]
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Populations of recurrent policies (wg_lstm_pop): P pairs (wg_lstm, wg_policy) of ONE architecture, member m on rows
+// [m Bm, (m + 1) Bm) of every buffer and with a state of its own, [P][nets][2][Bm][H]: state[m] is the member's state alone.
+// ---------------------------------------------------------------------------------------------------------------------
+// the members' weights for k_lstm_pop / k_lstm_pack_pop, a kernel argument by value (256 bytes): the member's packed copy and,
+// for the pack, the flat LSTM parameters it is built from
+struct WgLstmPopW {
+    const float* packed[WGP_POP_MAX];
+    const float* flat[WGP_POP_MAX];
+};
+
+struct wg_lstm_ppo_s;
+struct wg_lstm_pop_s {
+    int P, device;
+    wg_lstm_s* lstm[WGP_POP_MAX];
+    wg_policy_s* head[WGP_POP_MAX];
+    wg_lstm_ppo_s* opt[WGP_POP_MAX];     // all null: a population that only acts
+    wg_pop_s heads;                       // the heads as k_policy_pop sees them: its slot table on the LSTMs' h rows (no optimisers)
+    void* seq_dev;                        // [WGP_POP_MAX] WgLstmPopMember: the sequence kernels' member table of the running update
+    void* upd_dev;                        // [2][WGP_POP_MAX] WgPopMember of that update: the heads' view (MLP part), Adam's (whole vector)
+    void* rows_dev;                       // [WGP_POP_MAX] WgPopHeadRows
+};
+
 #endif

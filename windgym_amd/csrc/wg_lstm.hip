@@ -9,6 +9,7 @@
 // the weights come packed from L2 as the A operand, output tile 4u + q = gate q of the units 32u .. 32u + 31.  Wave w accumulates
 // the eight tiles of its unit blocks w and w + 4 (128 accumulator registers), so it holds z_i, z_f, z_g, z_o of a (unit, row) in
 // ONE lane and finishes c' and h' there: no gate array in LDS, no second pass.  LDS: 32 KB static (k_policy: 64 KB).
+// k_lstm_pop / k_lstm_pack_pop: the same bodies with one more grid axis = the member of a population (wg_lstm.h: wg_lstm_pop_s).
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -24,13 +25,14 @@
 // (Two waves per SIMD asked for: without the bound the compiler spreads the accumulators over 145 VGPRs + 144 AGPRs and one workgroup
 // fills a CU; with it 202 VGPRs, nothing spilled, and two workgroups of 32 KB LDS share the CU.  One unit block per wave in workgroups
 // of 8 waves — 121 VGPRs, occupancy 4 — was measured too and was no faster at 256 envs and 10 % slower at 4096: DESIGN §4.)
-__global__ __launch_bounds__(WGP_WAVES * 64, 2) void k_lstm(const WgLstmP P, const float* __restrict__ packed, const float* __restrict__ x,
-                                                            const uint8_t* __restrict__ start, const float* state_in, float* state_out,
-                                                            float* __restrict__ h_out0, float* __restrict__ h_out1, const int n_rows,
-                                                            const int net0) {
+// (one workgroup of k_lstm / k_lstm_pop: the 32 rows from blockIdx.x's tile of ONE net on `n_rows` rows; every pointer is the first
+// row's, the state's the first net's)
+__device__ __forceinline__ void wgl_step(const WgLstmP& P, const float* __restrict__ packed, const float* __restrict__ x,
+                                         const uint8_t* __restrict__ start, const float* state_in, float* state_out,
+                                         float* __restrict__ h_out0, float* __restrict__ h_out1, const int n_rows, const int net) {
     __shared__ float lds[WGP_KC * WGP_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-    const int net = net0 + blockIdx.y, row0 = blockIdx.x * WGP_TILE;
+    const int row0 = blockIdx.x * WGP_TILE;
     const int H = P.H, n_in = P.n_in, K = P.K;
     const WgLstmNet nt = P.net[net];
     const size_t plane = (size_t)n_rows * H;
@@ -98,8 +100,29 @@ __global__ __launch_bounds__(WGP_WAVES * 64, 2) void k_lstm(const WgLstmP P, con
     }
 }
 
+__global__ __launch_bounds__(WGP_WAVES * 64, 2) void k_lstm(const WgLstmP P, const float* __restrict__ packed, const float* __restrict__ x,
+                                                            const uint8_t* __restrict__ start, const float* state_in, float* state_out,
+                                                            float* __restrict__ h_out0, float* __restrict__ h_out1, const int n_rows,
+                                                            const int net0) {
+    wgl_step(P, packed, x, start, state_in, state_out, h_out0, h_out1, n_rows, net0 + blockIdx.y);
+}
+
+// A population's step (wg_lstm_pop): grid (tiles of 32 rows of ONE member, nets evaluated, members).  Member m = blockIdx.z owns the
+// rows [m Bm, (m + 1) Bm) of x, start and h_out, its own state [nets][2][Bm][H] at state + m nets 2 Bm H, and its own packed weights;
+// a tile never straddles two members.  The member is a function of blockIdx alone, so its pointers are wave-uniform (the packed
+// pointers travel as kernel arguments: 16 of them, read by one scalar load), and what a workgroup computes is wgl_step on them — the
+// arithmetic of k_lstm on the member's rows alone.
+__global__ __launch_bounds__(WGP_WAVES * 64, 2) void k_lstm_pop(const WgLstmP P, const WgLstmPopW W, const float* __restrict__ x,
+                                                                const uint8_t* __restrict__ start, const float* state_in, float* state_out,
+                                                                float* __restrict__ h_out0, float* __restrict__ h_out1, const int Bm,
+                                                                const int net0) {
+    const size_t m = blockIdx.z, r0 = m * Bm, s0 = m * P.n_nets * 2 * Bm * P.H;
+    wgl_step(P, W.packed[m], x + r0 * P.n_in, start ? start + r0 : nullptr, state_in + s0, state_out ? state_out + s0 : nullptr,
+             h_out0 ? h_out0 + r0 * P.H : nullptr, h_out1 ? h_out1 + r0 * P.H : nullptr, Bm, net0 + blockIdx.y);
+}
+
 // flat -> packed (wg_lstm.h); one thread per packed float.  b_ih + b_hh is added HERE, once.
-__global__ void k_lstm_pack(const WgLstmP P, const float* __restrict__ flat, float* __restrict__ packed) {
+__device__ __forceinline__ void wgl_pack(const WgLstmP& P, const float* __restrict__ flat, float* __restrict__ packed) {
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P.n_packed) return;
     const uint32_t H = P.H, n_in = P.n_in, K = P.K, nks = P.nks;
@@ -120,6 +143,11 @@ __global__ void k_lstm_pack(const WgLstmP P, const float* __restrict__ flat, flo
     }
     packed[idx] = v;
 }
+
+__global__ void k_lstm_pack(const WgLstmP P, const float* __restrict__ flat, float* __restrict__ packed) { wgl_pack(P, flat, packed); }
+
+// every member of a population: blockIdx.y = member, its flat parameters -> its LSTM's packed copy
+__global__ void k_lstm_pack_pop(const WgLstmP P, const WgLstmPopW W) { wgl_pack(P, W.flat[blockIdx.y], const_cast<float*>(W.packed[blockIdx.y])); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
@@ -213,4 +241,104 @@ extern "C" int wg_lstm_act(wg_lstm l, wg_policy p, int n_rows, const float* x_de
         return rc;
     const WgValueRows v = {h_vf, value_dev, n_rows};
     return wg_policy_eval_(p, n_rows, h_pi, deterministic, seed, counter, row_offset, action_dev, raw_dev, logp_dev, &v, value_dev ? 1 : 0, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// populations of recurrent policies: the step and the heads' slot table (wg_lstm_pop_create / _update: wg_lstm_ppo.hip; the closed
+// loop: wg_api.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+static WgLstmPopW lpop_weights(const wg_lstm_pop_s* q, const float* const* params_dev) {
+    WgLstmPopW W = {};
+    for (int m = 0; m < q->P; ++m) {
+        W.packed[m] = q->lstm[m]->w.packed;
+        W.flat[m] = params_dev ? params_dev[m] : nullptr;
+    }
+    return W;
+}
+
+// wg_lstm_step for every member in ONE launch of k_lstm_pop: n_rows = P Bm rows, member m on its own rows, state and weights
+extern "C" int wg_lstm_pop_step_(wg_lstm_pop q, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
+                                 float* state_out_dev, float* h_pi_dev, float* h_vf_dev, int net_mask, void* stream) {
+    const WgLstmP& P = q->lstm[0]->P;
+    const int Bm = n_rows / q->P;
+    if (Bm == 0) return 0;
+    if (int rc = wg_use_device(q->device)) return rc;
+    const int net0 = (net_mask & WG_LSTM_ACTOR) ? 0 : 1, nn = net_mask == (WG_LSTM_ACTOR | WG_LSTM_CRITIC) ? 2 : 1;
+    hipLaunchKernelGGL(k_lstm_pop, dim3((Bm + WGP_TILE - 1) / WGP_TILE, nn, q->P), dim3(WGP_WAVES * 64), 0, (hipStream_t)stream, P,
+                       lpop_weights(q, nullptr), x_dev, episode_start_dev, state_in_dev, state_out_dev, h_pi_dev, h_vf_dev, Bm, net0);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("wg_lstm_pop: kernel launch failed: ") + hipGetErrorString(le));
+    return 0;
+}
+
+// k_lstm_pack for every member in ONE launch: params_dev[m] (the member's flat vector, the LSTM's part first) -> its packed copy
+extern "C" int wg_lstm_pack_pop_(wg_lstm_pop q, const float* const* params_dev, void* stream) {
+    const WgLstmP& P = q->lstm[0]->P;
+    hipLaunchKernelGGL(k_lstm_pack_pop, dim3((P.n_packed + 255) / 256, q->P), dim3(256), 0, (hipStream_t)stream, P, lpop_weights(q, params_dev));
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The heads' slot table (wg_policy.h: WgPopSlot) on the LSTMs' h rows: P actor slots on h_pi (when an actor output is wanted), P
+// critic slots on h_vf (value), P critic slots on h_fin (final_value), member m on rows [m Bm, (m + 1) Bm).  The h rows are the
+// running step's (no step stride); the outputs are one call's (`step` = 0) or a rollout's [T, B, ..] (`step` = B).
+extern "C" int wg_lstm_pop_slots_(wg_lstm_pop q, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* h_pi,
+                                  const float* h_vf, const float* h_fin, float* action, float* raw, float* logp, float* value,
+                                  float* final_value, int64_t step, void* stream) {
+    const WgPolicyP& P = q->head[0]->P;
+    const int Bm = n_rows / q->P, H = q->lstm[0]->P.H;
+    const bool actor = action || raw || logp;
+    WgPopSlot tab[WGP_POP_SLOTS] = {};
+    int ns = 0;
+    for (int kind = 0; kind < 3; ++kind) {
+        if (kind == 0 ? !actor : kind == 1 ? !value : !final_value) continue;
+        for (int m = 0; m < q->P; ++m) {
+            WgPopSlot& s = tab[ns++];
+            const size_t row = (size_t)m * Bm;
+            s.packed = q->head[m]->w.packed;
+            s.obs = (kind == 0 ? h_pi : kind == 1 ? h_vf : h_fin) + row * H;
+            s.obs_step = 0; s.act_step = step * P.n_out; s.row_step = step;
+            s.net = kind == 0 ? 0 : 1;
+            s.t_shift = kind == 2 ? -1 : 0;
+            if (kind == 0) {
+                s.action = action ? action + row * P.n_out : nullptr;
+                s.raw = raw ? raw + row * P.n_out : nullptr;
+                s.logp = logp ? logp + row : nullptr;
+                s.seed = seeds[m];
+                s.row_offset = row_offsets ? row_offsets[m] : 0;
+            } else {
+                s.value = (kind == 1 ? value : final_value) + row;
+            }
+        }
+    }
+    q->heads.n_head = (actor ? 1 : 0) + (value ? 1 : 0);
+    q->heads.has_final = final_value ? 1 : 0;
+    q->heads.Bm = Bm;
+    if (ns == 0 || Bm == 0) return 0;
+    if (int rc = wg_use_device(q->device)) return rc;
+    return wg_pop_store_(q->heads.slots_dev, tab, sizeof(WgPopSlot) * ns, stream);
+}
+
+// The members' LSTM steps and the MLPs behind them: two launches.  The critics' LSTMs run only when the value is wanted.
+extern "C" int wg_lstm_pop_act(wg_lstm_pop q, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
+                               float* state_out_dev, float* h_dev, int deterministic, const uint64_t* seeds, uint64_t counter,
+                               const uint64_t* row_offsets, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream) {
+    if (!q || !x_dev || !state_in_dev || !h_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: null argument (q, x_dev, state_in_dev and h_dev are required)");
+    if (n_rows < 0) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: n_rows < 0");
+    if (n_rows % q->P != 0)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: the " + std::to_string(q->P) + " members own equal shares of the rows, and " +
+                                         std::to_string(n_rows) + " rows do not divide by " + std::to_string(q->P));
+    if ((action_dev || raw_dev || logp_dev) && !seeds) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: seeds[P] is required");
+    if ((action_dev || raw_dev || logp_dev) && !q->head[0]->P.has_log_std && (!deterministic || logp_dev))
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: a stochastic action / a log-probability needs policies with log_std");
+    const WgLstmP& L = q->lstm[0]->P;
+    const bool two = L.n_nets == 2, critic = two && value_dev;
+    float* const h_pi = h_dev;
+    float* const h_vf = two ? h_dev + (size_t)n_rows * L.H : h_dev;
+    if (int rc = wg_lstm_pop_slots_(q, n_rows, seeds, row_offsets, h_pi, h_vf, nullptr, action_dev, raw_dev, logp_dev, value_dev, nullptr, 0, stream))
+        return rc;
+    if (int rc = wg_lstm_pop_step_(q, n_rows, x_dev, episode_start_dev, state_in_dev, state_out_dev, h_pi, critic ? h_vf : nullptr,
+                                   WG_LSTM_ACTOR | (critic ? WG_LSTM_CRITIC : 0), stream))
+        return rc;
+    return wg_pop_launch_(&q->heads, 1, 0, 0, deterministic, counter, stream);
 }

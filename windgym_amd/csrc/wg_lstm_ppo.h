@@ -40,12 +40,28 @@ struct WgLstmSeq {
     const float* state0;       // [nets][2][B][H]
     const int32_t* envs;       // [Bm] env of minibatch column j; an entry outside [0, B) is a column of zeros
     int32_t T, B, Bm, NT, shared;
+    int32_t sB;                // populations only (wg_lstm_pop_update): envs of ONE member = rows of a plane of ITS state0
     float *gates, *c, *h;      // the stash
     size_t net_gates, net_c, net_h;        // floats from one net to the next
     const float* dh[2];        // [T Bm][H] from the actor's / the critic's head
     const float* whhT;         // the transposed packed blocks
     uint32_t whhT_net;         // floats of one net's block
     int32_t nksT;
+};
+
+// One member of the sequence kernels' table of a population (k_lstm_*_pop; written once per wg_lstm_pop_update, device memory).
+// `q` is the WgLstmSeq the member's own wg_lstm_ppo_update would pass, on the WHOLE rollout [T, B] and with
+//     q.envs   = the member's permutations [n_epochs][sB] of GLOBAL env ids (the kernels add the minibatch's offset; Bm and NT of
+//                the running minibatch are kernel arguments: the members run in lockstep),
+//     q.state0 = the member's own [nets][2][sB][H] MINUS m sB H floats, so that the global env id indexes a plane of sB rows,
+// and the rest is what the single-policy launches take as arguments.
+struct WgLstmPopMember {
+    WgLstmSeq q;
+    const float* packed;       // the member's LSTM, packed (k_lstm_seq_fwd)
+    const float* params;       // the caller's flat vector of the member (k_lstm_ppo_pack reads the LSTM part)
+    float* whhT;               // = q.whhT, to write
+    float *wpart, *grad;       // the weight gradient's partial sums; the member's flat gradient
+    float *raw, *logp, *adv, *ret;   // the gathered rows
 };
 
 struct wg_lstm_ppo_s {

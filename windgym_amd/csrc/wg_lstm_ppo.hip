@@ -25,6 +25,9 @@
 // element-wise, and runs W_hh^T dz as a GEMM over the transposed packed block with dz staged through LDS in chunks of 256 (dz of a
 // tile is 128 KB at H = 256).  Both: 64 KB of LDS.  k_lstm_wgrad: output-stationary, a workgroup owns 128 rows x 32 columns of dWcat
 // and walks the blocks of its split in index order; at most WGLP_SPLIT rows of partials, added in order by k_lstm_wgrad_reduce.
+//
+// POPULATIONS (wg_lstm_pop_update): every kernel here has a sibling k_*_pop with one more grid axis = member that runs the same
+// __device__ body on the member's row of a device table — P small runs in the launches of one, each bit-identical to its own update.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -41,8 +44,14 @@ __device__ __forceinline__ int wglp_env(const WgLstmSeq& q, const int j) {
     return (e < 0 || e >= q.B) ? -1 : e;
 }
 
+// The bodies below are shared by the single-policy kernels and the population's (k_*_pop, behind them): POP only selects the plane of
+// state0, q.sB rows (a member's own state) instead of q.B — with POP = false the code is what it was before the flag.
+template <bool POP>
+__device__ __forceinline__ int wglp_plane(const WgLstmSeq& q) { return POP ? q.sB : q.B; }
+
 // grid (NT, nets)
-__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd(const WgLstmP P, const float* __restrict__ packed, const WgLstmSeq q) {
+template <bool POP>
+__device__ __forceinline__ void lstm_seq_fwd(const WgLstmP& P, const float* __restrict__ packed, const WgLstmSeq& q) {
     __shared__ float lds[WGP_KC * WGP_TILE];
     __shared__ float hbuf[WGL_MAX_H * WGP_TILE];           // h_{t-1} as [unit][32 columns]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -51,8 +60,8 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd(const WgLstmP P
     const WgLstmNet nt = P.net[net];
     const int j = tile * WGP_TILE + r, env = wglp_env(q, j);
     const bool valid = env >= 0;
-    const float* h0 = q.state0 + (size_t)net * 2 * q.B * H;
-    const float* c0 = h0 + (size_t)q.B * H;
+    const float* h0 = q.state0 + (size_t)net * 2 * wglp_plane<POP>(q) * H;
+    const float* c0 = h0 + (size_t)wglp_plane<POP>(q) * H;
     for (int unit = tid >> 5; unit < H; unit += 2 * WGP_WAVES) hbuf[unit * WGP_TILE + r] = valid ? h0[(size_t)env * H + unit] : 0.0f;
     float creg[2][16];
 #pragma unroll
@@ -147,9 +156,14 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd(const WgLstmP P
     }
 }
 
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd(const WgLstmP P, const float* __restrict__ packed, const WgLstmSeq q) {
+    lstm_seq_fwd<false>(P, packed, q);
+}
+
 // grid (NT, nets).  Thread (r = tid & 31, u = tid >> 5) owns the units u, u + 8, ... of column r at every step: its dc never leaves
 // its registers.
-__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd(const WgLstmP P, const WgLstmSeq q) {
+template <bool POP>
+__device__ __forceinline__ void lstm_seq_bwd(const WgLstmP& P, const WgLstmSeq& q) {
     __shared__ float lds[WGP_KC * WGP_TILE];
     __shared__ float rec[WGL_MAX_H * WGP_TILE];            // W_hh^T dz_{t+1} as [unit][32 columns]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5, u0 = tid >> 5;
@@ -157,10 +171,11 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd(const WgLstmP P
     const int H = P.H, H4 = 4 * P.H;
     const int j = tile * WGP_TILE + r, env = wglp_env(q, j);
     const bool valid = env >= 0;
-    const float* c0 = q.state0 + ((size_t)net * 2 + 1) * q.B * H;
+    const float* c0 = q.state0 + ((size_t)net * 2 + 1) * wglp_plane<POP>(q) * H;
     float* gates = q.gates + (size_t)net * q.net_gates;
     const float* cst = q.c + (size_t)net * q.net_c;
-    const float* dh0 = q.dh[net];
+    // (a member's q is a copy in registers: no index by `net` there)
+    const float* dh0 = POP ? (net ? q.dh[1] : q.dh[0]) : q.dh[net];
     const float* dh1 = q.shared ? q.dh[1] : nullptr;
     const float* wT = q.whhT + (size_t)net * q.whhT_net;
     const float* xb = lds + hh * WGP_TILE + r;
@@ -233,6 +248,8 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd(const WgLstmP P
     }
 }
 
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd(const WgLstmP P, const WgLstmSeq q) { lstm_seq_bwd<false>(P, q); }
+
 // grid (ceil(K / 32), ceil(4H / 128), nets * S): wave w of workgroup (kt, it) owns rows 128 it + 32 w .. + 31, columns 32 kt .. + 31
 // of dWcat and sums over its SPLIT's blocks in index order, 32 rows per block on v_mfma_f32_32x32x2_f32 (A = dz, B = xcat, both from
 // LDS with a row stride of 33 floats).  The workgroups kt = 0 also sum the biases.  Split sp of S = min(WGLP_SPLIT, T NT) takes the
@@ -242,17 +259,19 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd(const WgLstmP P
 // the split is there for workgroups per CU, not for the arithmetic.
 #define WGLP_WI 128
 #define WGLP_S 33
-__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_wgrad(const WgLstmP P, const WgLstmSeq q, float* __restrict__ part, const int S) {
+// (`z`: the workgroup's index along (net, split), blockIdx.z of the single-policy grid)
+template <bool POP>
+__device__ __forceinline__ void lstm_wgrad(const WgLstmP& P, const WgLstmSeq& q, float* __restrict__ part, const int S, const int z) {
     __shared__ float ds[WGLP_WI * WGLP_S];
     __shared__ float xs[32 * WGLP_S];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-    const int kt = blockIdx.x, i0 = blockIdx.y * WGLP_WI, net = blockIdx.z / S, sp = blockIdx.z - net * S;
+    const int kt = blockIdx.x, i0 = blockIdx.y * WGLP_WI, net = z / S, sp = z - net * S;
     const int H = P.H, n_in = P.n_in, K = P.K, H4 = 4 * P.H;
     const WgLstmNet nt = P.net[net];
     float* __restrict__ grad = part + (size_t)sp * P.n_flat;
     const float* gates = q.gates + (size_t)net * q.net_gates;
     const float* hst = q.h + (size_t)net * q.net_h;
-    const float* h0 = q.state0 + (size_t)net * 2 * q.B * H;
+    const float* h0 = q.state0 + (size_t)net * 2 * wglp_plane<POP>(q) * H;
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
@@ -303,8 +322,12 @@ __global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_wgrad(const WgLstmP P, 
     }
 }
 
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_wgrad(const WgLstmP P, const WgLstmSeq q, float* __restrict__ part, const int S) {
+    lstm_wgrad<false>(P, q, part, S, blockIdx.z);
+}
+
 // the splits' rows -> the LSTM's entries of the flat gradient, added in index order
-__global__ void k_lstm_wgrad_reduce(const float* __restrict__ part, const uint32_t n, const int S, float* __restrict__ grad) {
+__device__ __forceinline__ void lstm_wgrad_reduce(const float* __restrict__ part, const uint32_t n, const int S, float* __restrict__ grad) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     float s = part[p];
@@ -312,9 +335,13 @@ __global__ void k_lstm_wgrad_reduce(const float* __restrict__ part, const uint32
     grad[p] = s;
 }
 
+__global__ void k_lstm_wgrad_reduce(const float* __restrict__ part, const uint32_t n, const int S, float* __restrict__ grad) {
+    lstm_wgrad_reduce(part, n, S, grad);
+}
+
 // flat -> the transposed packed blocks (wg_lstm_ppo.h); one thread per float, the slack included
-__global__ void k_lstm_ppo_pack(const WgLstmP P, const float* __restrict__ flat, float* __restrict__ whhT, const uint32_t per_net,
-                                const uint32_t total, const uint32_t nksT) {
+__device__ __forceinline__ void lstm_ppo_pack(const WgLstmP& P, const float* __restrict__ flat, float* __restrict__ whhT, const uint32_t per_net,
+                                              const uint32_t total, const uint32_t nksT) {
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const uint32_t net = idx / per_net;
@@ -327,10 +354,15 @@ __global__ void k_lstm_ppo_pack(const WgLstmP P, const float* __restrict__ flat,
     whhT[idx] = v;
 }
 
+__global__ void k_lstm_ppo_pack(const WgLstmP P, const float* __restrict__ flat, float* __restrict__ whhT, const uint32_t per_net,
+                                const uint32_t total, const uint32_t nksT) {
+    lstm_ppo_pack(P, flat, whhT, per_net, total, nksT);
+}
+
 // the minibatch's rows of raw / logp / advantage / returns [T, B] -> row order t Bm + j (a column without an env: zeros)
-__global__ void k_lstm_ppo_gather(const WgLstmSeq q, const int n_out, const float* __restrict__ raw, const float* __restrict__ logp,
-                                  const float* __restrict__ adv, const float* __restrict__ ret, float* __restrict__ raw_o,
-                                  float* __restrict__ logp_o, float* __restrict__ adv_o, float* __restrict__ ret_o) {
+__device__ __forceinline__ void lstm_ppo_gather(const WgLstmSeq& q, const int n_out, const float* __restrict__ raw, const float* __restrict__ logp,
+                                                const float* __restrict__ adv, const float* __restrict__ ret, float* __restrict__ raw_o,
+                                                float* __restrict__ logp_o, float* __restrict__ adv_o, float* __restrict__ ret_o) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= q.T * q.Bm) return;
     const int t = row / q.Bm, j = row - t * q.Bm, env = wglp_env(q, j);
@@ -339,6 +371,65 @@ __global__ void k_lstm_ppo_gather(const WgLstmSeq q, const int n_out, const floa
     adv_o[row] = env >= 0 ? adv[src] : 0.0f;
     ret_o[row] = env >= 0 ? ret[src] : 0.0f;
     for (int a = 0; a < n_out; ++a) raw_o[(size_t)row * n_out + a] = env >= 0 ? raw[src * n_out + a] : 0.0f;
+}
+
+__global__ void k_lstm_ppo_gather(const WgLstmSeq q, const int n_out, const float* __restrict__ raw, const float* __restrict__ logp,
+                                  const float* __restrict__ adv, const float* __restrict__ ret, float* __restrict__ raw_o,
+                                  float* __restrict__ logp_o, float* __restrict__ adv_o, float* __restrict__ ret_o) {
+    lstm_ppo_gather(q, n_out, raw, logp, adv, ret, raw_o, logp_o, adv_o, ret_o);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The population's kernels: one more grid axis = member, whose row of the member table (wg_lstm_ppo.h: WgLstmPopMember) holds what
+// the single-policy kernel takes as arguments.  The member is a function of blockIdx alone, so the row is read by scalar loads into
+// the registers the kernel arguments would occupy: nothing per-member is live across a time loop that was not live before.  `off`
+// is the running minibatch's offset into every member's permutations, Bm / NT its size.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ WgLstmSeq wglp_member(const WgLstmPopMember* __restrict__ M, const int64_t off, const int Bm, const int NT) {
+    WgLstmSeq q = M->q;
+    q.envs += off; q.Bm = Bm; q.NT = NT;
+    return q;
+}
+
+// grid (ceil(whhT_all / 256), P)
+__global__ void k_lstm_ppo_pack_pop(const WgLstmP P, const WgLstmPopMember* __restrict__ mt, const uint32_t per_net, const uint32_t total,
+                                    const uint32_t nksT) {
+    const WgLstmPopMember* __restrict__ M = mt + blockIdx.y;
+    lstm_ppo_pack(P, M->params, M->whhT, per_net, total, nksT);
+}
+
+// grid (ceil(T Bm / 256), P); raw / logp / adv / ret: the whole rollout's [T, B]
+__global__ void k_lstm_ppo_gather_pop(const WgLstmPopMember* __restrict__ mt, const int64_t off, const int Bm, const int NT, const int n_out,
+                                      const float* __restrict__ raw, const float* __restrict__ logp, const float* __restrict__ adv,
+                                      const float* __restrict__ ret) {
+    const WgLstmPopMember* __restrict__ M = mt + blockIdx.y;
+    lstm_ppo_gather(wglp_member(M, off, Bm, NT), n_out, raw, logp, adv, ret, M->raw, M->logp, M->adv, M->ret);
+}
+
+// grid (NT, nets, P)
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_fwd_pop(const WgLstmP P, const WgLstmPopMember* __restrict__ mt, const int64_t off,
+                                                                     const int Bm, const int NT) {
+    const WgLstmPopMember* __restrict__ M = mt + blockIdx.z;
+    lstm_seq_fwd<true>(P, M->packed, wglp_member(M, off, Bm, NT));
+}
+
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_seq_bwd_pop(const WgLstmP P, const WgLstmPopMember* __restrict__ mt, const int64_t off,
+                                                                     const int Bm, const int NT) {
+    lstm_seq_bwd<true>(P, wglp_member(mt + blockIdx.z, off, Bm, NT));
+}
+
+// grid (ceil(K / 32), ceil(4H / 128), P * nets * S): member = blockIdx.z / (nets S)
+__global__ __launch_bounds__(WGP_WAVES * 64) void k_lstm_wgrad_pop(const WgLstmP P, const WgLstmPopMember* __restrict__ mt, const int64_t off,
+                                                                   const int Bm, const int NT, const int S) {
+    const int per = P.n_nets * S, m = blockIdx.z / per;
+    const WgLstmPopMember* __restrict__ M = mt + m;
+    lstm_wgrad<true>(P, wglp_member(M, off, Bm, NT), M->wpart, S, blockIdx.z - m * per);
+}
+
+// grid (ceil(n_lstm / 256), P)
+__global__ void k_lstm_wgrad_reduce_pop(const WgLstmPopMember* __restrict__ mt, const uint32_t n, const int S) {
+    const WgLstmPopMember* __restrict__ M = mt + blockIdx.y;
+    lstm_wgrad_reduce(M->wpart, n, S, M->grad);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -503,5 +594,169 @@ extern "C" int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lst
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
         if (int rc = lp_grad(o, params_dev, b, perm_dev + off, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
         return lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// populations of recurrent policies (windgym_hip.h: wg_lstm_pop_*; the step and the heads' slot table: wg_lstm.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, const wg_lstm_ppo* opts, int P, wg_lstm_pop* out) {
+    if (!lstms || !heads || !out) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_create: null argument");
+    *out = nullptr;
+    if (P < 1 || P > WG_POP_MAX)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_create: a population has 1 .. " + std::to_string(WG_POP_MAX) + " members, not " + std::to_string(P));
+    for (int m = 0; m < P; ++m) {
+        const std::string who = "wg_lstm_pop_create: member " + std::to_string(m);
+        if (!lstms[m] || !heads[m]) return wg_fail(WG_ERR_INVALID, who + " is null");
+        const WgLstmP &L0 = lstms[0]->P, &L = lstms[m]->P;
+        const WgPolicyP &A = heads[0]->P, &Q = heads[m]->P;
+        if (Q.n_in != L.H || Q.n_layers[1] == 0 || Q.n_in_vf != L.H)
+            return wg_fail(WG_ERR_INVALID, who + ": its head must map the LSTM's hidden size (" + std::to_string(L.H) + ") with its critic on the same width; it maps " +
+                                             std::to_string(Q.n_in) + " inputs, its critic " + std::to_string(Q.n_layers[1] ? Q.n_in_vf : 0));
+        if (L.n_in != L0.n_in || L.H != L0.H || L.n_nets != L0.n_nets)
+            return wg_fail(WG_ERR_INVALID, who + "'s LSTM maps " + std::to_string(L.n_in) + " -> " + std::to_string(L.H) + " with " + std::to_string(L.n_nets) +
+                                             " net(s), member 0's " + std::to_string(L0.n_in) + " -> " + std::to_string(L0.H) + " with " +
+                                             std::to_string(L0.n_nets) + ": the members of a population share one n_in, hidden size and number of nets");
+        // the layer table is a function of the wg_policy_desc alone: equal descs <=> equal tables
+        bool same = Q.n_out == A.n_out && Q.activation == A.activation && Q.has_log_std == A.has_log_std && Q.n_layers[0] == A.n_layers[0] &&
+                    Q.n_layers[1] == A.n_layers[1] && Q.n_flat == A.n_flat;
+        for (int net = 0; net < 2 && same; ++net)
+            for (int l = 0; l < Q.n_layers[net]; ++l) same = same && Q.layer[net][l].K == A.layer[net][l].K && Q.layer[net][l].M == A.layer[net][l].M;
+        if (!same) return wg_fail(WG_ERR_INVALID, who + "'s head has another architecture than member 0's: the members of a population share one");
+        if (lstms[m]->w.device != lstms[0]->w.device || heads[m]->w.device != lstms[0]->w.device)
+            return wg_fail(WG_ERR_INVALID, who + " lives on device " + std::to_string(lstms[m]->w.device) + " / " + std::to_string(heads[m]->w.device) +
+                                             " (LSTM / head), member 0 on device " + std::to_string(lstms[0]->w.device));
+        for (int k = 0; k < m; ++k)
+            if (lstms[k] == lstms[m] || heads[k] == heads[m])
+                return wg_fail(WG_ERR_INVALID, who + " holds the same handle as member " + std::to_string(k));
+        if (opts) {
+            if (!opts[m]) return wg_fail(WG_ERR_INVALID, who + ": its wg_lstm_ppo is null (opts = NULL makes a population that only acts)");
+            if (opts[m]->lstm != lstms[m] || opts[m]->pol != heads[m])
+                return wg_fail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another pair");
+        }
+    }
+    wg_lstm_pop_s* q = new (std::nothrow) wg_lstm_pop_s();
+    if (!q) return wg_fail(WG_ERR_NOMEM, "wg_lstm_pop_create: out of host memory");
+    q->P = q->heads.P = P;
+    q->device = q->heads.device = lstms[0]->w.device;
+    for (int m = 0; m < P; ++m) { q->lstm[m] = lstms[m]; q->head[m] = q->heads.pol[m] = heads[m]; q->opt[m] = opts ? opts[m] : nullptr; }
+    hipError_t e = hipSetDevice(q->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&q->heads.slots_dev, sizeof(WgPopSlot) * WGP_POP_SLOTS);
+    if (e == hipSuccess) e = hipMalloc(&q->seq_dev, sizeof(WgLstmPopMember) * WGP_POP_MAX);
+    if (e == hipSuccess) e = hipMalloc(&q->upd_dev, sizeof(WgPopMember) * 2 * WGP_POP_MAX);
+    if (e == hipSuccess) e = hipMalloc(&q->rows_dev, sizeof(WgPopHeadRows) * WGP_POP_MAX);
+    if (e != hipSuccess) {
+        wg_lstm_pop_destroy(q);
+        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_lstm_pop_create: ") + hipGetErrorString(e));
+    }
+    *out = q;
+    return 0;
+}
+
+extern "C" int wg_lstm_pop_destroy(wg_lstm_pop q) {
+    if (!q) return 0;
+    if (hipSetDevice(q->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        for (void* b : {(void*)q->heads.slots_dev, q->seq_dev, q->upd_dev, q->rows_dev})
+            if (b) (void)hipFree(b);
+    }
+    delete q;
+    return 0;
+}
+
+extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const wg_lstm_ppo_batch* b, const int32_t* perm_dev, int n_epochs,
+                                  int envs_per_batch, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm,
+                                  wg_ppo_stats* stats_out, void* stream) {
+    if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: null argument");
+    const int P = q->P;
+    if (!q->opt[0])
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: the population was created without optimisers (opts = NULL): it only acts");
+    if (n_epochs < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: n_epochs must be >= 1");
+    for (int m = 0; m < P; ++m) {
+        const std::string who = "wg_lstm_pop_update: member " + std::to_string(m);
+        if (!params_dev[m]) return wg_fail(WG_ERR_INVALID, who + ": params_dev is null");
+        if (int rc = lp_check(who, q->opt[m], b, &hp[m], envs_per_batch)) return rc;
+        if (!(max_grad_norm[m] > 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": max_grad_norm must be > 0");
+    }
+    if (b->B % P != 0)
+        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: the " + std::to_string(P) + " members own equal shares of the envs, and B = " +
+                                         std::to_string(b->B) + " does not divide by " + std::to_string(P));
+    if (int rc = wg_use_device(q->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const WgLstmP& L = q->lstm[0]->P;
+    const WgPpoGrad* g0 = &q->opt[0]->heads;
+    const WgPolicyP& PP = g0->pol->P;
+    const int T = b->T, sB = b->B / P, n_out = PP.n_out, n_mb = wg_n_minibatches(sB, envs_per_batch);
+    const size_t H = L.H;
+    // the three member tables: the sequence kernels', and for the heads and Adam two views of the member as the plain population's
+    // kernels see one — the MLP part of its vectors with the heads' scratch, and its whole flat vector
+    WgLstmPopMember seq[WGP_POP_MAX] = {};
+    WgPopMember upd[2 * WGP_POP_MAX] = {};
+    WgPopHeadRows rows[WGP_POP_MAX] = {};
+    bool any_norm = false;
+    for (int m = 0; m < P; ++m) {
+        wg_lstm_ppo_s* o = q->opt[m];
+        const size_t n_max = (size_t)o->T_max * o->Bm_max, npad = (size_t)o->T_max * o->NT_max * WGP_TILE;
+        WgLstmPopMember& S = seq[m];
+        WgLstmSeq& s = S.q;
+        s.obs = b->obs; s.start = b->episode_start; s.envs = perm_dev + (size_t)m * n_epochs * sB;
+        s.state0 = b->lstm_state0 + (size_t)m * L.n_nets * 2 * sB * H - (size_t)m * sB * H;
+        s.T = T; s.B = b->B; s.sB = sB; s.shared = L.n_nets == 1;
+        s.gates = o->gates; s.c = o->c; s.h = o->h;
+        s.net_gates = npad * 4 * H; s.net_c = npad * H; s.net_h = n_max * H;
+        s.dh[0] = o->dh; s.dh[1] = o->dh + n_max * H;
+        s.whhT = o->whhT; s.whhT_net = o->whhT_net; s.nksT = o->nksT;
+        S.packed = o->lstm->w.packed; S.params = params_dev[m]; S.whhT = o->whhT; S.wpart = o->wpart; S.grad = o->grad;
+        S.raw = o->rows; S.logp = S.raw + n_max * n_out; S.adv = S.logp + n_max; S.ret = S.adv + n_max;
+        WgPopHeadRows& R = rows[m];
+        R.obs[0] = o->h; R.obs[1] = o->h + (size_t)(L.n_nets - 1) * s.net_h;
+        R.raw = S.raw; R.logp_old = S.logp; R.adv = S.adv; R.ret = S.ret;
+        R.dh[0] = o->dh; R.dh[1] = o->dh + n_max * H;
+        WgPopMember& M = upd[m];
+        M.packed = o->pol->w.packed; M.params = params_dev[m] + o->n_lstm; M.grad = o->grad + o->n_lstm;
+        M.part = o->heads.part; M.spart = o->heads.spart; M.advstat = o->heads.advstat;
+        M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->stats;
+        M.stats_step = stats_out ? WGT_NSTAT : 0;
+        M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef;
+        M.normalize = hp[m].normalize_advantage != 0;
+        any_norm = any_norm || M.normalize;
+        WgPopMember& A = upd[WGP_POP_MAX + m];
+        A.params = params_dev[m]; A.grad = o->grad; A.m = o->adam.m; A.v = o->adam.v; A.blocksq = o->adam.blocksq; A.max_norm = max_grad_norm[m];
+    }
+    const WgLstmPopMember* mt = (const WgLstmPopMember*)q->seq_dev;
+    const WgPopMember* ht = (const WgPopMember*)q->upd_dev;
+    const WgPopHeadRows* rt = (const WgPopHeadRows*)q->rows_dev;
+    if (int rc = wg_pop_store_(q->seq_dev, seq, sizeof(WgLstmPopMember) * P, stream)) return rc;
+    if (int rc = wg_pop_store_(q->upd_dev, upd, sizeof(upd), stream)) return rc;
+    if (int rc = wg_pop_store_(q->rows_dev, rows, sizeof(WgPopHeadRows) * P, stream)) return rc;
+    const wg_lstm_ppo_s* o0 = q->opt[0];
+    const uint32_t n_flat = o0->adam.n_flat;
+    // every member has the architecture of member 0: per minibatch the launches of lp_grad and lp_apply, each with the member axis
+    return wg_each_minibatch(sB, n_epochs, envs_per_batch, [&](int mb, int64_t off, int Bm) {
+        const int n = T * Bm, NT = (Bm + WGP_TILE - 1) / WGP_TILE;
+        hipLaunchKernelGGL(k_lstm_ppo_pack_pop, dim3((o0->whhT_all + 255) / 256, P), dim3(256), 0, st, L, mt, o0->whhT_net, o0->whhT_all,
+                           (uint32_t)o0->nksT);
+        hipLaunchKernelGGL(k_lstm_ppo_gather_pop, dim3((n + 255) / 256, P), dim3(256), 0, st, mt, off, Bm, NT, n_out, b->raw, b->logp,
+                           b->advantage, b->returns);
+        hipLaunchKernelGGL(k_lstm_seq_fwd_pop, dim3(NT, L.n_nets, P), dim3(WGP_WAVES * 64), 0, st, L, mt, off, Bm, NT);
+        WG_HIPCHK(hipGetLastError());
+        if (int rc = wg_ppo_heads_grad_pop_(g0, ht, rt, P, any_norm, n, mb, stream)) return rc;
+        hipLaunchKernelGGL(k_lstm_seq_bwd_pop, dim3(NT, L.n_nets, P), dim3(WGP_WAVES * 64), 0, st, L, mt, off, Bm, NT);
+        const int nblk = T * NT, S = nblk < WGLP_SPLIT ? nblk : WGLP_SPLIT;
+        hipLaunchKernelGGL(k_lstm_wgrad_pop, dim3((L.K + 31) / 32, (4 * L.H + WGLP_WI - 1) / WGLP_WI, P * L.n_nets * S), dim3(WGP_WAVES * 64), 0,
+                           st, L, mt, off, Bm, NT, S);
+        hipLaunchKernelGGL(k_lstm_wgrad_reduce_pop, dim3((o0->n_lstm + 255) / 256, P), dim3(256), 0, st, mt, o0->n_lstm, S);
+        WG_HIPCHK(hipGetLastError());
+        float step_size[WGP_POP_MAX], bc2_sqrt[WGP_POP_MAX];
+        for (int m = 0; m < P; ++m) {
+            const WgAdamStep s = wg_adam_count(&q->opt[m]->adam, lr[m]);
+            step_size[m] = s.step_size;
+            bc2_sqrt[m] = s.bc2_sqrt;
+        }
+        if (int rc = wg_adam_apply_pop_(ht + WGP_POP_MAX, P, n_flat, step_size, bc2_sqrt, stream)) return rc;
+        if (int rc = wg_lstm_pack_pop_(q, params_dev, stream)) return rc;
+        wg_policy_pack_pop_(&PP, ht, P, stream);
+        WG_HIPCHK(hipGetLastError());
+        return 0;
     });
 }

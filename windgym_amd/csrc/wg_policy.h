@@ -122,6 +122,14 @@ struct WgPopMember {
     int32_t normalize, stats_step;
 };
 
+// What the heads of one member of a RECURRENT population read and write in k_ppo_grad_dh_pop (wg_lstm_ppo.hip fills the table): the
+// member's own stash rows in minibatch row order — in a plain population these are the one batch all members share
+struct WgPopHeadRows {
+    const float* obs[2];       // [n][H] the h rows of the actor's / the critic's LSTM
+    const float *raw, *logp_old, *adv, *ret;
+    float* dh[2];              // [n][H] d loss / d h rows per head
+};
+
 struct wg_ppo_s;
 struct wg_pop_s {
     int P, device;

@@ -158,8 +158,10 @@ struct WgPpoArgs {
 // DH: also the gradient with respect to the net's INPUT rows, dX[row][k] = sum_i W0[i][k] dZ0[i][row], into a.dh[net] — what the
 // LSTMs in front of a recurrent policy's heads backpropagate (each gathered row is written once, by the one tile that holds it).
 // With DH = false the code is what it was before the flag: the same instructions, the same bits.
-template <bool DH>
-__device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, const WgPpoArgs& a, const float* a_packed,
+// `rw`: the rows a workgroup reads and the dh rows it writes (obs, raw, logp_old, adv, ret, dh) — `a` itself, or the member's row of
+// a recurrent population's table (WgPopHeadRows), read where it lies: the nets index obs and dh by blockIdx.y.
+template <bool DH, class Rows>
+__device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, const WgPpoArgs& a, const Rows& rw, const float* a_packed,
                                          const float* a_flat, const int32_t* a_index, const int a_normalize, const float a_clip,
                                          const float a_vf_coef, const float* a_advstat, float* a_part, float* a_spart) {
     extern __shared__ float lds[];
@@ -168,7 +170,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
     const int R = K.R, S = R + 1;
     const WgPpoLds& M = K.lds[net];
     const int L = P.n_layers[net];
-    const float* __restrict__ xsrc = a.obs[net];
+    const float* __restrict__ xsrc = rw.obs[net];
     float* xin = lds + M.xin;
     float* rowv = lds + M.rowv;
     int* rid = (int*)(lds + M.rid);
@@ -256,13 +258,13 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                     float lp = 0.0f;
                     for (int j = 0; j < n_out; ++j) {
                         const float ls = a_flat[P.log_std_flat + j];
-                        const float z = (a.raw[(size_t)id * n_out + j] - hb[j * S + tid]) / expf(ls);
+                        const float z = (rw.raw[(size_t)id * n_out + j] - hb[j * S + tid]) / expf(ls);
                         hb[j * S + tid] = z;
                         lp += -0.5f * z * z - ls - WGT_HALF_LOG_2PI;
                     }
-                    const float lr = lp - a.logp_old[id];
+                    const float lr = lp - rw.logp_old[id];
                     const float ratio = expf(lr);
-                    float A = a.adv[id / a.agents];       // the env row's advantage, shared by its agents
+                    float A = rw.adv[id / a.agents];       // the env row's advantage, shared by its agents
                     if (a_normalize) A = (A - a_advstat[0]) / (a_advstat[1] + 1e-8f);
                     const float rc = fminf(fmaxf(ratio, 1.0f - a_clip), 1.0f + a_clip);
                     const float s1 = ratio * A, s2 = rc * A;
@@ -293,7 +295,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                 const int id = rid[tid];
                 float dv = 0.0f, lv = 0.0f;
                 if (id >= 0) {
-                    const float e = hb[tid] - a.ret[id];
+                    const float e = hb[tid] - rw.ret[id];
                     lv = e * e;
                     dv = a_vf_coef * 2.0f * e * inv_n;
                 }
@@ -382,7 +384,7 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
                                 const float yv = y[k * S + r];
                                 dp[k * S + r] = acc[e] * (tanh_act ? 1.0f - yv * yv : (yv > 0.0f ? 1.0f : 0.0f));
                             } else if (rid[r] >= 0) {
-                                a.dh[net][(size_t)rid[r] * ly.K + k] = acc[e];
+                                rw.dh[net][(size_t)rid[r] * ly.K + k] = acc[e];
                             }
                         }
                     }
@@ -400,19 +402,35 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
 }
 
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
-    ppo_grad<false>(P, K, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+    ppo_grad<false>(P, K, a, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
 }
 
 // k_ppo_grad with the input-row gradients (a.dh) as well: the heads of a recurrent policy on the LSTMs' h rows
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_dh(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
-    ppo_grad<true>(P, K, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+    ppo_grad<true>(P, K, a, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
 }
 
 // grid (G, 2, P); `c` carries what the members share (the batch, n, G), the member's row the rest
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_pop(const WgPolicyP P, const WgPpoK K, const WgPpoArgs c,
                                                                  const WgPopMember* __restrict__ mt, const int64_t off) {
     const WgPopMember* __restrict__ M = mt + blockIdx.z;
-    ppo_grad<false>(P, K, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+    ppo_grad<false>(P, K, c, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+}
+
+// The heads of a recurrent population: grid (G, 2, P); member blockIdx.z reads ITS rows (row m of `rt`: the h rows of its LSTMs and
+// its gathered raw / logp / advantage / returns, n rows in order, no index) and `c` carries what the members share (n, G)
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_dh_pop(const WgPolicyP P, const WgPpoK K, const WgPpoArgs c,
+                                                                    const WgPopMember* __restrict__ mt,
+                                                                    const WgPopHeadRows* __restrict__ rt) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.z;
+    ppo_grad<true>(P, K, c, rt[blockIdx.z], M->packed, M->params, nullptr, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+}
+
+__global__ __launch_bounds__(1024) void k_ppo_advstat_rows_pop(const WgPopMember* __restrict__ mt, const WgPopHeadRows* __restrict__ rt,
+                                                               const int n) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.x;
+    if (!(M->normalize && n > 1)) return;
+    ppo_advstat(rt[blockIdx.x].adv, nullptr, 0, n, n, 1, M->advstat);
 }
 
 // partials -> flat gradient (+ the entropy term's constant gradient on log_std) and the statistics record
@@ -786,6 +804,34 @@ extern "C" int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, con
     return t_grad(g, mlp_params_dev, &sb, nullptr, 0, n, hp, grad_out, stats_out, (hipStream_t)stream, dh_pi, dh_vf);
 }
 
+// wg_internal.h: the heads of a recurrent population (wg_lstm_ppo.hip) — t_grad's three launches with the member axis
+extern "C" int wg_ppo_heads_grad_pop_(const WgPpoGrad* g0, const WgPopMember* mt, const WgPopHeadRows* rt, int n_members, int any_norm,
+                                      int n, int mb, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const WgPolicyP& P = g0->pol->P;
+    const int G = t_grid(g0, n);
+    if (any_norm && n > 1) hipLaunchKernelGGL(k_ppo_advstat_rows_pop, dim3(n_members), dim3(1024), 0, st, mt, rt, n);
+    WgPpoArgs a = {};
+    a.agents = 1; a.first = 0; a.n_total = n; a.n = n; a.G = G;
+    hipLaunchKernelGGL(k_ppo_grad_dh_pop, dim3(G, 2, n_members), dim3(WGT_WAVES * 64), g0->lds_bytes, st, P, g0->K, a, mt, rt);
+    hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(g0->n_blocks, n_members), dim3(WGT_BLOCK), 0, st, P, mt, G, n, mb);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, uint32_t n_flat, const float* step_size, const float* bc2_sqrt,
+                                  void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_blocks = (n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    WgPopAdam A = {};
+    for (int m = 0; m < n_members; ++m) { A.step_size[m] = step_size[m]; A.bc2_sqrt[m] = bc2_sqrt[m]; }
+    hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat);
+    hipLaunchKernelGGL(k_ppo_adam_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat, n_blocks, A, (float)(1.0 - ADAM_B1),
+                       (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // the handle's device becomes the current one; the parameters and the batch's observation streams must live on it
 static int t_use_device(const std::string& w, wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b) {
     if (int rc = wg_use_device(o->adam.device)) return rc;
@@ -993,14 +1039,13 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
         a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
         hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), g0->lds_bytes, st, PP, g0->K, a, mt, off);
         hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(g0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
-        WgPopAdam A = {};
+        float step_size[WGP_POP_MAX], bc2_sqrt[WGP_POP_MAX];
         for (int m = 0; m < P; ++m) {
             const WgAdamStep s = wg_adam_count(&q->opt[m]->adam, lr[m]);
-            A.step_size[m] = s.step_size;
-            A.bc2_sqrt[m] = s.bc2_sqrt;
+            step_size[m] = s.step_size;
+            bc2_sqrt[m] = s.bc2_sqrt;
         }
-        hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(a0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, a0->n_flat);
-        hipLaunchKernelGGL(k_ppo_adam_pop, dim3(a0->n_blocks, P), dim3(WGT_BLOCK), 0, st, mt, a0->n_flat, a0->n_blocks, A, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+        if (int rc = wg_adam_apply_pop_(mt, P, a0->n_flat, step_size, bc2_sqrt, stream)) return rc;
         wg_policy_pack_pop_(&PP, mt, P, stream);
         WG_HIPCHK(hipGetLastError());
         return 0;

@@ -320,34 +320,47 @@ class WindFarmVecEnv(_gym_vector_base()):
         second ``rollout()`` continues the first; ``reset()`` marks every env (of its mask) as an episode start, a pair's first
         rollout starts every env.  ``state=`` (a tensor like ``lstm_state``) overrides the kept state.  ``step()`` calls in between
         do NOT advance it: the policy never saw those observations.  ``final_value[t]`` bootstraps from the LSTM state after step
-        t (sb3-contrib's rule).  ``sample_site`` is not supported with a recurrent policy."""
+        t (sb3-contrib's rule).  ``sample_site`` is not supported with a recurrent policy.
+
+        ``policy`` may be a ``recurrent_population.RecurrentPopulation`` (or a ``RecurrentPPOPopulation``): wg_lstm_pop_rollout, the
+        dict of a recurrent rollout with ``lstm_state0`` / ``lstm_state`` ``[P, nets, 2, Bm, H]`` — entry ``m`` is exactly the
+        member's tensor alone — and the state of the (population, env) pair kept as for one policy."""
         b = self.batch
-        if getattr(policy, "recurrent", False):
-            return self._rollout_recurrent(policy, n_steps, deterministic, record, values, state)
-        if state is not None:
-            raise ValueError("rollout(): state= applies to a recurrent policy (MlpLstmPolicy)")
-        pop = getattr(policy, "population", None)      # a population.Population / PPOPopulation: wg_pop_rollout, member m on its envs
+        pop = getattr(policy, "population", None)      # a population / its trainer: wg_pop_rollout / wg_lstm_pop_rollout, member m on its envs
         if pop is not None and self.num_envs % pop.n_members:
             raise ValueError(f"rollout(): the {pop.n_members} members own equal shares of the envs: num_envs = {self.num_envs} "
                              f"does not divide by {pop.n_members}")
+        if getattr(policy if pop is None else pop, "recurrent", False):
+            return self._rollout_recurrent(policy if pop is None else pop, n_steps, deterministic, record, values, state)
+        if state is not None:
+            raise ValueError("rollout(): state= applies to a recurrent policy (MlpLstmPolicy)")
         return self._rollout(policy if pop is None else pop, n_steps, deterministic, record, values, rows=(self.num_envs,),
                              shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
                              slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout if pop is None else b.rollout_pop)
 
-    def _rollout_recurrent(self, policy, n_steps, deterministic, record, values, state):
-        """``rollout()`` of an ``MlpLstmPolicy``: :meth:`_rollout` with wg_rollout_lstm as the loop, around the pair's kept state."""
-        t, b = self.torch, self.batch
-        T, B = int(n_steps), self.num_envs
-        if self._site is not None:
-            raise NotImplementedError("rollout(): a recurrent policy with sample_site is not implemented")
+    def _lstm_pair(self, policy):
+        """This env's entry of the (policy, env) pair — [weakref, LSTM state, pending episode starts, buffers] — made on first use:
+        the zero state, every env an episode start.  ``policy``: an ``MlpLstmPolicy`` or a ``RecurrentPopulation``."""
+        t, B = self.torch, self.num_envs
         ent = self._lstm.get(id(policy))
         if ent is None or ent[0]() is not policy:
             self._lstm = {k: e for k, e in self._lstm.items() if e[0]() is not None}
             ent = self._lstm[id(policy)] = [weakref.ref(policy), policy.initial_state(B),
-                                            t.ones(B, dtype=t.uint8, device=b.device), {}]
+                                            t.ones(B, dtype=t.uint8, device=self.batch.device), {}]
+        return ent
+
+    def _rollout_recurrent(self, policy, n_steps, deterministic, record, values, state):
+        """``rollout()`` of an ``MlpLstmPolicy`` or a ``RecurrentPopulation``: :meth:`_rollout` with wg_rollout_lstm /
+        wg_lstm_pop_rollout as the loop, around the pair's kept state."""
+        t, b = self.torch, self.batch
+        T, B = int(n_steps), self.num_envs
+        if self._site is not None:
+            raise NotImplementedError("rollout(): a recurrent policy with sample_site is not implemented")
+        ent = self._lstm_pair(policy)
+        loop = b.rollout_lstm_pop if getattr(policy, "population", None) is not None else b.rollout_lstm
         if state is not None:
             if not (isinstance(state, t.Tensor) and tuple(state.shape) == tuple(ent[1].shape)):
-                raise ValueError(f"rollout(): state must be a tensor {tuple(ent[1].shape)} (nets, h | c, envs, H)")
+                raise ValueError(f"rollout(): state must be a tensor {tuple(ent[1].shape)} ((members,) nets, h | c, envs, H)")
             ent[1].copy_(state)
         if T < 1:
             raise ValueError("rollout(): n_steps must be >= 1")
@@ -359,7 +372,7 @@ class WindFarmVecEnv(_gym_vector_base()):
         extra["episode_start"][0].copy_(ent[2])
         out = self._rollout(policy, T, deterministic, record, values, rows=(B,), shape=(b.obs_dim, self.n_turb),
                             needs=f"the env needs {b.obs_dim} -> {self.n_turb}", slots=(("obs", "final_obs", b.obs, b.final_obs),),
-                            run=lambda pol, n, bufs, *a: b.rollout_lstm(pol, n, {**bufs, **extra}, *a))
+                            run=lambda pol, n, bufs, *a: loop(pol, n, {**bufs, **extra}, *a))
         ent[2].copy_(extra["episode_start"][T])
         out.update(episode_start=extra["episode_start"], lstm_state0=extra["lstm_state0"], lstm_state=ent[1])
         return out

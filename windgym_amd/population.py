@@ -145,10 +145,29 @@ class PPOPopulation:
     records no powers).  ``members[m]`` is an ordinary policy; ``save(dir)`` writes ``member_00.zip`` ...: plain ``PPO`` zips
     (``PPO.load(zip, shard venv)`` resumes a member alone)."""
 
+    # what recurrent_population.RecurrentPPOPopulation states differently: the policy class by name, and the four hooks below
+    policy_name = "MlpPolicy"
+
+    def _check_policy(self, policy):
+        refuse_recurrent(policy, "PPOPopulation")
+
+    def _minibatches(self, batch_size):
+        """``batch_size`` as given -> (rows of a minibatch, width of a member's permutation, minibatches per epoch)."""
+        batch_size = check_batch_size(batch_size, self.n_rows, "n_steps * num_envs / n_members")
+        return batch_size, self.n_rows, -(-self.n_rows // batch_size)
+
+    def _build_member(self, venv, shape, policy_kwargs, seed):
+        return PPO._build_policy(venv, shape, policy_kwargs, seed)
+
+    def _open(self, members):
+        """The members' optimisers and the population object over both."""
+        self.opts = [PPOOptimizer(p) for p in members]
+        self.population = Population(members, self.opts)
+
     def __init__(self, policy, venv, n_members=None, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95,
                  clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True,
                  policy_kwargs=None, seed=None, curriculum=None, normalize=None):
-        refuse_recurrent(policy, "PPOPopulation")
+        self._check_policy(policy)
         if curriculum is not None:
             raise NotImplementedError("a curriculum for a population is not implemented (use PPO(..., curriculum=...))")
         if normalize is not None:
@@ -163,11 +182,11 @@ class PPOPopulation:
                 raise ValueError(f"n_members = {n_members} contradicts the {len(policy)} policies given")
             n_members = len(policy)
             if policy_kwargs:
-                raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
-        elif policy != "MlpPolicy":
-            raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy' or a list of MlpPolicy objects")
+                raise ValueError(f"policy_kwargs only applies to policy='{self.policy_name}'")
+        elif policy != self.policy_name:
+            raise ValueError(f"unknown policy {policy!r}: only '{self.policy_name}' or a list of {self.policy_name} objects")
         elif n_members is None:
-            raise ValueError("policy='MlpPolicy' needs n_members")
+            raise ValueError(f"policy='{self.policy_name}' needs n_members")
         self.n_members = P = int(n_members)
         self.n_envs = B = int(venv.num_envs)
         self.n_envs_member = Bm = check_population_shape(P, B)
@@ -179,30 +198,29 @@ class PPOPopulation:
         for m in range(P):
             check_hyper(n_steps, n_epochs, self.gamma[m], self.gae_lambda[m], self.max_grad_norm[m], f"member {m}: ")
         n_steps, n_epochs = int(n_steps), int(n_epochs)
-        self.n_rows = rows_m = n_steps * Bm                                # rows of ONE member
-        batch_size = check_batch_size(batch_size, rows_m, "n_steps * num_envs / n_members")
-        self.n_steps, self.n_epochs, self.batch_size = n_steps, n_epochs, batch_size
+        self.n_rows = n_steps * Bm                                         # rows of ONE member
+        self.n_steps, self.n_epochs = n_steps, n_epochs
+        self.batch_size, perm_width, n_mb = self._minibatches(batch_size)
         self._lr = [_schedule(x, "learning_rate") for x in self.learning_rate]
         self._clip = [_schedule(x, "clip_range") for x in self.clip_range]
         self.venv = venv
         want = (int(venv.batch.obs_dim), int(venv.n_turb))
         if not objects:
-            policy = [PPO._build_policy(venv, want, dict(policy_kwargs or {}), 0 if s is None else int(s)) for s in self.seed]
+            policy = [self._build_member(venv, want, dict(policy_kwargs or {}), 0 if s is None else int(s)) for s in self.seed]
         for m, p in enumerate(policy):
             if (p.n_in, p.n_out) != want:
                 raise ValueError(f"member {m} maps {p.n_in} -> {p.n_out}, this env needs {want[0]} -> {want[1]}")
         self.members = policy
         self.torch = t = policy[0].torch
         dev = policy[0].device
-        self.opts = [PPOOptimizer(p) for p in policy]
-        self.population = Population(policy, self.opts)
+        self._open(policy)
         self._gens = []
         for s in self.seed:
             g = t.Generator(device=dev)
             g.manual_seed(0 if s is None else int(s))
             self._gens.append(g)
-        self.n_minibatches = n_mb = -(-rows_m // batch_size)
-        self._perm = t.zeros((P, n_epochs, rows_m), dtype=t.int32, device=dev)
+        self.n_minibatches = n_mb
+        self._perm = t.zeros((P, n_epochs, perm_width), dtype=t.int32, device=dev)
         self._adv = t.zeros((n_steps, B), dtype=t.float32, device=dev)
         self._ret = t.zeros_like(self._adv)
         self._stats = t.zeros((P, n_epochs, n_mb, 8), dtype=t.float32, device=dev)

@@ -21,7 +21,6 @@ fallback: without the built library or a GPU the constructors raise.
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 
 from .policy import device_tensor
 from .ppo import HandleOptimizer, Trainer, read_checkpoint, sb3_orthogonal_init
@@ -193,14 +192,9 @@ class RecurrentPPO(Trainer):
 
     # -- checkpoints ----------------------------------------------------------------------------------------------
     def _pair(self):
-        """The env's entry of this (policy, env) pair — [weakref, LSTM state, pending episode starts, buffers] — made as
-        ``venv.rollout`` makes it when there is none yet."""
-        t, v = self.torch, self.venv
-        ent = v._lstm.get(id(self.policy))
-        if ent is None or ent[0]() is not self.policy:
-            ent = v._lstm[id(self.policy)] = [weakref.ref(self.policy), self.policy.initial_state(v.num_envs),
-                                              t.ones(v.num_envs, dtype=t.uint8, device=v.batch.device), {}]
-        return ent
+        """The env's entry of this (policy, env) pair — [weakref, LSTM state, pending episode starts, buffers] — as ``venv.rollout``
+        keeps it."""
+        return self.venv._lstm_pair(self.policy)
 
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself (the class docstring)."""
