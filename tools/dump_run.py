@@ -27,14 +27,15 @@ LSTM_SHAPES = [(3, 1, 1, False), (7, 40, 31, True), (257, 64, 389, False), (300,
 
 def dump_policy(out):
     """MlpPolicy.act (deterministic, stochastic with value) and Population.act (P = 3, on the rows that divide by 3) per MLP shape,
-    three chained MlpLstmPolicy.act per LSTM shape, then one 8-step venv.rollout of a policy, of a population (P = 2: the members
-    own equal shares of the 4 envs) and of a recurrent policy on 4 envs of the 2-turbine preset.  Every weight and input is drawn
-    on the host from fixed seeds."""
+    three chained MlpLstmPolicy.act and RecurrentPopulation.act (P = 3, on the rows that divide by 3) per LSTM shape, then one 8-step
+    venv.rollout of a policy, of a population (P = 2: the members own equal shares of the 4 envs), of a recurrent policy and of a
+    recurrent population (P = 2) on 4 envs of the 2-turbine preset.  Every weight and input is drawn on the host from fixed seeds."""
     from windgym_amd import presets
     from windgym_amd.envs import WindFarmVecEnv
     from windgym_amd.policy import MlpPolicy
     from windgym_amd.population import Population
     from windgym_amd.recurrent import MlpLstmPolicy
+    from windgym_amd.recurrent_population import RecurrentPopulation
     from windgym_amd.turbine import V80
     rng, A = np.random.default_rng(20), {}
     dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")          # noqa: E731
@@ -66,6 +67,21 @@ def dump_policy(out):
             A[f"{tag}_t{i}_state"] = state.cpu().numpy()
             state = state.clone()
         p.close()
+        n = rows // 3 * 3
+        if n == 0:
+            continue
+        ms = [MlpLstmPolicy(n_in, 3, H, (32,), (32,), shared_lstm=shared, device=0, seed=40 + m) for m in range(3)]
+        pop = RecurrentPopulation(ms)
+        state = dev(rng.uniform(-1, 1, (3, pop.nets, 2, n // 3, H)).astype(np.float32))
+        for i in range(3):
+            start = dev((rng.random(n) < 0.3).astype(np.uint8))
+            outs, state = pop.act(dev(rng.uniform(-1, 1, (n, n_in)).astype(np.float32)), state, start, counter=i)
+            keep(f"{tag}_pop_t{i}", outs)
+            A[f"{tag}_pop_t{i}_state"] = state.cpu().numpy()
+            state = state.clone()
+        pop.close()
+        for m in ms:
+            m.close()
 
     def venv():
         v = WindFarmVecEnv(V80(), 4, yaml_dict=presets.two_turb_config(), seed=77, as_torch=True, turbtype="None", n_passthrough=1)
@@ -76,7 +92,8 @@ def dump_policy(out):
     O, N = v.batch.obs_dim, v.n_turb
     ms = [MlpPolicy(O, N, (64, 64), (64, 64), "tanh", device=0, seed=31 + m) for m in range(2)]
     pop, rec = Population(ms), MlpLstmPolicy(O, N, 64, (32,), (32,), device=0, seed=33)
-    for tag, pol in (("roll_mlp", ms[0]), ("roll_pop", pop), ("roll_lstm", rec)):
+    rpop = RecurrentPopulation([MlpLstmPolicy(O, N, 64, (32,), (32,), device=0, seed=34 + m) for m in range(2)])
+    for tag, pol in (("roll_mlp", ms[0]), ("roll_pop", pop), ("roll_lstm", rec), ("roll_lstm_pop", rpop)):
         for k, x in v.rollout(pol, 8).items():
             A[f"{tag}_{k}"] = np.atleast_1d(x.cpu().numpy())
         v.close()
@@ -89,12 +106,13 @@ def dump_policy(out):
 def dump_train(out):
     """Two ``learn`` iterations (n_steps = 8, 2 epochs, fixed seeds) on 4 envs of the 2-turbine preset of: PPO; PPO on the multi-agent
     env with the per-agent and with the centralised critic; PPO(normalize={}); PPOPopulation with P = 2; RecurrentPPO (H = 40) with an
-    LSTM per net and with a shared one.  Kept per trainer: the parameters, ``opt.state()``, ``_stats``, ``_perm`` and the logged
+    LSTM per net and with a shared one; RecurrentPPOPopulation with P = 2 (H = 40).  Kept per trainer: the parameters, ``opt.state()``, ``_stats``, ``_perm`` and the logged
     records without ``fps``."""
     from windgym_amd import presets
     from windgym_amd.envs import WindFarmVecEnv, WindFarmVecEnvMulti
     from windgym_amd.population import PPOPopulation
     from windgym_amd.ppo import PPO
+    from windgym_amd.recurrent_population import RecurrentPPOPopulation
     from windgym_amd.recurrent_ppo import RecurrentPPO
     from windgym_amd.turbine import V80
     A, T, B = {}, 8, 4
@@ -116,7 +134,9 @@ def dump_train(out):
             ("ppo_normalize", single, PPO, "MlpPolicy", dict(seed=14, normalize={})),
             ("population", single, PPOPopulation, "MlpPolicy", dict(n_members=2, seed=[15, 16], learning_rate=[3e-4, 1e-3])),
             ("recurrent", single, RecurrentPPO, "MlpLstmPolicy", dict(seed=17, **lstm(False))),
-            ("recurrent_shared", single, RecurrentPPO, "MlpLstmPolicy", dict(seed=18, **lstm(True)))]
+            ("recurrent_shared", single, RecurrentPPO, "MlpLstmPolicy", dict(seed=18, **lstm(True))),
+            ("recurrent_population", single, RecurrentPPOPopulation, "MlpLstmPolicy",
+             dict(n_members=2, seed=[19, 20], learning_rate=[3e-4, 1e-3], **lstm(False)))]
     for tag, make, cls, policy, extra in runs:
         v = make()
         v.reset(seed=77)

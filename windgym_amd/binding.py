@@ -373,11 +373,19 @@ class HipBatch:
     def rollout_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
         """wg_pop_rollout, the arguments of :meth:`rollout` with a ``population.Population`` in the policy's place: every member
         samples with the one ``seed``, member ``m``'s noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
-        P, cb = pop.n_members, self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        Bm = self.B // P
-        _chk(self.L.wg_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), (C.c_uint64 * P)(*[int(seed)] * P), counter0,
-                                   (C.c_uint64 * P)(*[int(row_offset) + m * Bm for m in range(P)]), C.byref(cb), self._stream()),
+        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
+        seeds, offs = self._pop_noise(pop, seed, row_offset)
+        _chk(self.L.wg_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), seeds, counter0, offs, C.byref(cb), self._stream()),
              "wg_pop_rollout")
+
+    def _pop_noise(self, pop, seed, row_offset):
+        """``seeds[P]`` / ``row_offsets[P]`` of a population's rollout that samples as ONE policy on the whole batch would."""
+        P = pop.n_members
+        return (C.c_uint64 * P)(*[int(seed)] * P), (C.c_uint64 * P)(*[int(row_offset) + m * (self.B // P) for m in range(P)])
+
+    @staticmethod
+    def _lstm_bufs(bufs):
+        return CRolloutLstmBufs(*[bufs[k].data_ptr() for k in ("lstm_state", "lstm_state0", "episode_start", "lstm_scratch")])
 
     def rollout_norm(self, norm, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
         """wg_rollout_norm, the arguments of :meth:`rollout` after a :class:`Norm`: ``bufs`` also holds ``norm_obs`` ``[T+1, B, O]``
@@ -391,8 +399,7 @@ class HipBatch:
         """wg_rollout_lstm, the arguments of :meth:`rollout` with a ``recurrent.MlpLstmPolicy``: ``bufs`` also holds ``lstm_state``
         (in / out), ``lstm_state0``, ``episode_start`` ``[T+1, B]`` (slot 0 is input) and ``lstm_scratch``."""
         cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        lb = CRolloutLstmBufs(bufs["lstm_state"].data_ptr(), bufs["lstm_state0"].data_ptr(), bufs["episode_start"].data_ptr(),
-                              bufs["lstm_scratch"].data_ptr())
+        lb = self._lstm_bufs(bufs)
         _chk(self.L.wg_rollout_lstm(self._h, policy._lstm, policy.mlp._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
                                     C.byref(cb), C.byref(lb), self._stream()), "wg_rollout_lstm")
 
@@ -400,12 +407,9 @@ class HipBatch:
         """wg_lstm_pop_rollout, the arguments of :meth:`rollout_lstm` with a ``recurrent_population.RecurrentPopulation`` in the policy's
         place (``lstm_state`` / ``lstm_state0`` ``[P, nets, 2, Bm, H]``): every member samples with the one ``seed``, member ``m``'s
         noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
-        P, cb = pop.n_members, self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        Bm = self.B // P
-        lb = CRolloutLstmBufs(bufs["lstm_state"].data_ptr(), bufs["lstm_state0"].data_ptr(), bufs["episode_start"].data_ptr(),
-                              bufs["lstm_scratch"].data_ptr())
-        _chk(self.L.wg_lstm_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), (C.c_uint64 * P)(*[int(seed)] * P), counter0,
-                                        (C.c_uint64 * P)(*[int(row_offset) + m * Bm for m in range(P)]), C.byref(cb), C.byref(lb),
+        cb, lb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record), self._lstm_bufs(bufs)
+        seeds, offs = self._pop_noise(pop, seed, row_offset)
+        _chk(self.L.wg_lstm_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), seeds, counter0, offs, C.byref(cb), C.byref(lb),
                                         self._stream()), "wg_lstm_pop_rollout")
 
     def rollout_multi(self, *args):

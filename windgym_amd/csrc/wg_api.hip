@@ -957,16 +957,30 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     return rc;
 }
 
+// One policy row per env (every closed-loop entry but wg_rollout_multi): the rows the policy reads (`rows` / `fin`, named obs_name /
+// fin_name) are the steps' flat rows or stand in their place; the policy maps n_in -> n_turb, or the refusal ends in `needs`
+static RolloutRows env_rows(const wg_env_s* h, const wg_rollout_bufs* o, const char* who, int n_in, const std::string& needs, float* rows,
+                            float* fin, const char* obs_name = "obs", const char* fin_name = "final_obs") {
+    return {who, obs_name, 1, n_in, h->p.N, needs + std::to_string(n_in) + " / " + std::to_string(h->p.N), nullptr, false,
+            {rows, o->actions, o->raw, o->logp, o->value, fin, o->final_value, o->reward, o->truncated, o->obs, o->final_obs, o->n_info,
+             o->info_fields, o->info_out},
+            1, n_in, rows, fin, fin_name};
+}
+
+// the LSTM side of a recurrent entry: lstm_bufs, and an LSTM (or the population's: `whose` words both) that reads the handle's rows
+static int lstm_rows_check(const std::string& who, const wg_env_s* h, const wg_rollout_lstm_bufs* lb, int l_in, int l_device,
+                           const char* reads, const char* whose) {
+    if (l_in != h->p.obs_dim)
+        return wg_fail(WG_ERR_INVALID, who + reads + " rows of " + std::to_string(l_in) + " inputs, the handle's obs_dim is " + std::to_string(h->p.obs_dim));
+    if (l_device != h->device) return wg_fail(WG_ERR_INVALID, who + whose + " and handle live on different devices");
+    if (!lb->state || !lb->episode_start || !lb->scratch) return wg_fail(WG_ERR_INVALID, who + ": lstm_bufs needs state, episode_start and scratch");
+    return 0;
+}
+
 extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                           uint64_t row_offset, const wg_rollout_bufs* o, void* stream) {
     if (!h || !p || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout: null argument");
-    const int N = h->p.N, O = h->p.obs_dim;
-    // one policy row per env: the rows the policy reads are the flat rows the steps write
-    const RolloutRows g = {"wg_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
-                           nullptr, false,
-                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
-                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
-                           1, O, o->obs, o->final_obs, "final_obs"};
+    const RolloutRows g = env_rows(h, o, "wg_rollout", h->p.obs_dim, ", the handle's obs_dim / n_turb are ", o->obs, o->final_obs);
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
@@ -977,7 +991,7 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
 extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                uint64_t row_offset, const wg_rollout_bufs* o, float* norm_obs_dev, float* norm_final_obs_dev, void* stream) {
     if (!h || !p || !n || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: null argument");
-    const int N = h->p.N, O = h->p.obs_dim;
+    const int O = h->p.obs_dim;
     int n_obs = 0, n_envs = 0, n_device = 0;
     if (int rc = wg_norm_geometry_(n, &n_obs, &n_envs, &n_device)) return rc;
     if (n_obs != O || n_envs != h->p.B)
@@ -987,11 +1001,8 @@ extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps,
     if (n_device != h->device) return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: wg_norm and handle live on different devices");
     if (!o->obs || !o->final_obs || !norm_final_obs_dev)
         return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: obs, final_obs (the env's own rows) and norm_final_obs are required");
-    const RolloutRows g = {"wg_rollout_norm", "norm_obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
-                           nullptr, false,
-                           {norm_obs_dev, o->actions, o->raw, o->logp, o->value, norm_final_obs_dev, o->final_value, o->reward, o->truncated,
-                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
-                           1, O, norm_obs_dev, norm_final_obs_dev, "norm_final_obs", nullptr, n};
+    RolloutRows g = env_rows(h, o, "wg_rollout_norm", O, ", the handle's obs_dim / n_turb are ", norm_obs_dev, norm_final_obs_dev, "norm_obs", "norm_final_obs");
+    g.norm = n;
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
@@ -1002,19 +1013,14 @@ extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps,
 extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
                               const uint64_t* row_offsets, const wg_rollout_bufs* o, void* stream) {
     if (!h || !q || !o || !seeds) return wg_fail(WG_ERR_INVALID, "wg_pop_rollout: null argument");
-    const int N = h->p.N, O = h->p.obs_dim, B = h->p.B;
-    const RolloutRows g = {"wg_pop_rollout", "obs", 1, O, N, ", the handle's obs_dim / n_turb are " + std::to_string(O) + " / " + std::to_string(N),
-                           nullptr, false,
-                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
-                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
-                           1, O, o->obs, o->final_obs, "final_obs", q};
+    const int B = h->p.B;
+    RolloutRows g = env_rows(h, o, "wg_pop_rollout", h->p.obs_dim, ", the handle's obs_dim / n_turb are ", o->obs, o->final_obs);
+    g.pop = q;
     if (int rc = rollout_check(h, q->pol[0], n_steps, deterministic, g)) return rc;
-    if (B % q->P != 0)
-        return wg_fail(WG_ERR_INVALID, "wg_pop_rollout: the " + std::to_string(q->P) + " members own equal shares of the envs, and n_envs = " +
-                                        std::to_string(B) + " does not divide by " + std::to_string(q->P));
+    if (int rc = wg_pop_shares(g.who, q->P, B, "envs", "n_envs = ", " does")) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
-    const WgPopRows r = {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, B, 1};
-    if (int rc = wg_pop_prepare_(q, "wg_pop_rollout", B, seeds, row_offsets, &r, stream)) return rc;
+    const WgPopOuts out = {o->actions, o->raw, o->logp, o->value, o->final_value, B};
+    if (int rc = wg_pop_prepare_(q, "wg_pop_rollout", B, seeds, row_offsets, o->obs, o->final_obs, &out, stream)) return rc;
     return rollout_loop(h, q->pol[0], n_steps, deterministic, 0, counter0, 0, g, stream);
 }
 
@@ -1047,21 +1053,12 @@ extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deter
 extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                uint64_t row_offset, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
     if (!h || !lstm || !p || !o || !lb) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: null argument");
-    const int N = h->p.N, O = h->p.obs_dim;
     int l_in = 0, H = 0, nets = 0, l_device = 0;
     if (int rc = wg_lstm_geometry_(lstm, &l_in, &H, &nets, &l_device)) return rc;
-    if (l_in != O)
-        return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm reads rows of " + std::to_string(l_in) + " inputs, the handle's obs_dim is " + std::to_string(O));
-    if (l_device != h->device) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm and handle live on different devices");
-    if (!lb->state || !lb->episode_start || !lb->scratch)
-        return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: lstm_bufs needs state, episode_start and scratch");
+    if (int rc = lstm_rows_check("wg_rollout_lstm", h, lb, l_in, l_device, ": lstm reads", ": lstm")) return rc;
     if (p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: p needs a critic (on the LSTM's hidden rows)");
-    const RolloutRows g = {"wg_rollout_lstm", "obs", 1, H, N,
-                           ": p reads the LSTM's hidden rows, and lstm's hidden size / the handle's n_turb are " + std::to_string(H) + " / " + std::to_string(N),
-                           nullptr, false,
-                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
-                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
-                           1, H, o->obs, o->final_obs, "final_obs", nullptr, nullptr, lstm, lb};
+    RolloutRows g = env_rows(h, o, "wg_rollout_lstm", H, ": p reads the LSTM's hidden rows, and lstm's hidden size / the handle's n_turb are ", o->obs, o->final_obs);
+    g.lstm = lstm; g.lb = lb;
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
@@ -1072,33 +1069,21 @@ extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_ste
 extern "C" int wg_lstm_pop_rollout(wg_handle h, wg_lstm_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
                                    const uint64_t* row_offsets, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
     if (!h || !q || !o || !lb || !seeds) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: null argument");
-    const int N = h->p.N, O = h->p.obs_dim, B = h->p.B;
+    const int B = h->p.B;
     wg_lstm_s* lstm = q->lstm[0];
-    wg_policy_s* p = q->head[0];
+    wg_policy_s* p = q->heads.pol[0];
     const int H = lstm->P.H;
-    if (lstm->P.n_in != O)
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: the LSTMs read rows of " + std::to_string(lstm->P.n_in) + " inputs, the handle's obs_dim is " +
-                                        std::to_string(O));
-    if (q->device != h->device) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: population and handle live on different devices");
-    if (!lb->state || !lb->episode_start || !lb->scratch)
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: lstm_bufs needs state, episode_start and scratch");
-    const RolloutRows g = {"wg_lstm_pop_rollout", "obs", 1, H, N,
-                           ": the heads read the LSTMs' hidden rows, and their hidden size / the handle's n_turb are " + std::to_string(H) + " / " +
-                               std::to_string(N),
-                           nullptr, false,
-                           {o->obs, o->actions, o->raw, o->logp, o->value, o->final_obs, o->final_value, o->reward, o->truncated,
-                            o->obs, o->final_obs, o->n_info, o->info_fields, o->info_out},
-                           1, H, o->obs, o->final_obs, "final_obs", &q->heads, nullptr, lstm, lb, q};
+    if (int rc = lstm_rows_check("wg_lstm_pop_rollout", h, lb, lstm->P.n_in, q->device, ": the LSTMs read", ": population")) return rc;
+    RolloutRows g = env_rows(h, o, "wg_lstm_pop_rollout", H, ": the heads read the LSTMs' hidden rows, and their hidden size / the handle's n_turb are ", o->obs,
+                             o->final_obs);
+    g.pop = &q->heads; g.lstm = lstm; g.lb = lb; g.lpop = q;
     if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (B % q->P != 0)
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: the " + std::to_string(q->P) + " members own equal shares of the envs, and n_envs = " +
-                                        std::to_string(B) + " does not divide by " + std::to_string(q->P));
+    if (int rc = wg_pop_shares(g.who, q->P, B, "envs", "n_envs = ", " does")) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
     float* const h_pi = lb->scratch;
     const size_t sH = (size_t)B * H;
-    if (int rc = wg_lstm_pop_slots_(q, B, seeds, row_offsets, h_pi, lstm->P.n_nets == 2 ? h_pi + sH : h_pi, h_pi + 2 * sH, o->actions, o->raw, o->logp,
-                                    o->value, o->final_value, B, stream))
-        return rc;
+    const WgPopOuts out = {o->actions, o->raw, o->logp, o->value, o->final_value, B};
+    if (int rc = wg_lstm_pop_slots_(q, B, seeds, row_offsets, h_pi, lstm->P.n_nets == 2 ? h_pi + sH : h_pi, h_pi + 2 * sH, &out, stream)) return rc;
     return rollout_loop(h, p, n_steps, deterministic, 0, counter0, 0, g, stream);
 }
 

@@ -11,7 +11,8 @@ struct FlowP;
 struct FlowPtrs;
 struct WgParams;
 struct WgPtrs;
-struct WgPopRows;
+struct WgPopKind;
+struct WgPopOuts;
 struct WgPolicyP;
 struct WgPopMember;
 struct WgPopHeadRows;
@@ -50,10 +51,12 @@ int wg_packed_source_(WgPacked* w, const float* params, int on_device, hipStream
 int wg_policy_eval_(wg_policy p, int n_rows, const float* obs_dev, int deterministic, uint64_t seed, uint64_t counter, uint64_t row_offset,
                     float* action_dev, float* raw_dev, float* logp_dev, const WgValueRows* v, int n_v, void* stream);
 // wg_policy.hip, populations (wg_policy.h): `bytes` (a multiple of 4) of a host table -> device memory by kernel launches in stream
-// order; the slot table of k_policy_pop for n_rows rows shared out among the members (refusals reported as `who`); one launch on it
+// order; the slot table of k_policy_pop (wg_policy.h: wgp_pop_slots) for Bm rows per member of the rows `kinds` describes, no
+// refusals; that table on n_rows rows of observations shared out among the members (refusals reported as `who`); one launch on it
 int wg_pop_store_(void* dst_dev, const void* src_host, size_t bytes, void* stream);
-int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const WgPopRows* r,
-                    void* stream);
+int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* obs,
+                    const float* final_obs, const WgPopOuts* o, void* stream);
+int wg_pop_slots_(wg_pop q, int Bm, const WgPopKind* kinds, const WgPopOuts* o, const uint64_t* seeds, const uint64_t* row_offsets, void* stream);
 int wg_pop_launch_(wg_pop q, int head, int fin, int t, int deterministic, uint64_t counter, void* stream);
 // wg_ppo.hip: Adam over one flat vector (wg_train.h: WgAdam).  alloc: moments zeroed, step 0; free (and wg_ppo_grad_free_): on the
 // current, synchronised device — a failed alloc / init leaves the freeing to the caller; get / set_state: the public *_get_state /
@@ -81,18 +84,17 @@ void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_member
 // minibatch's ordinal (its stats slot); any_norm: some member normalises its advantages
 int wg_ppo_heads_grad_pop_(const WgPpoGrad* g0, const WgPopMember* mt, const WgPopHeadRows* rt, int n_members, int any_norm, int n, int mb,
                            void* stream);
-// Adam over each of the n_members rows of a member table (device): clipping by the member's own norm, then the step with the
-// member's own scalars step_size[m] / bc2_sqrt[m] (k_ppo_sumsq_pop + k_ppo_adam_pop) on vectors of n_flat floats
-int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, uint32_t n_flat, const float* step_size, const float* bc2_sqrt, void* stream);
+// Adam over each of the n_members rows of a member table (device): counts one step of adam[m], then clipping by the member's own
+// norm and that step with the member's own lr[m] (k_ppo_sumsq_pop + k_ppo_adam_pop) on vectors of adam[0]->n_flat floats
+int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, WgAdam* const* adam, const float* lr, void* stream);
 // wg_lstm.hip, populations of recurrent policies (wg_lstm.h): wg_lstm_step for every member in ONE launch of k_lstm_pop on n_rows =
 // P Bm rows; k_lstm_pack for every member in one launch (params_dev[m]: host array of the members' flat vectors); the heads' slot
-// table on the h rows of the running step (outputs strided by `step` floats-rows per rollout step, 0: one call)
+// table on the h rows of the running step (the outputs: wg_policy.h, WgPopOuts)
 int wg_lstm_pop_step_(wg_lstm_pop q, int n_rows, const float* x_dev, const uint8_t* episode_start_dev, const float* state_in_dev,
                       float* state_out_dev, float* h_pi_dev, float* h_vf_dev, int net_mask, void* stream);
 int wg_lstm_pack_pop_(wg_lstm_pop q, const float* const* params_dev, void* stream);
 int wg_lstm_pop_slots_(wg_lstm_pop q, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* h_pi, const float* h_vf,
-                       const float* h_fin, float* action, float* raw, float* logp, float* value, float* final_value, int64_t step,
-                       void* stream);
+                       const float* h_fin, const WgPopOuts* o, void* stream);
 // wg_flow.hip
 void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
 void wg_launch_windspeed(const FlowP* p, const FlowPtrs* d, int e, int farm, const float* xs, int nx, const float* ys, int ny, float z,

@@ -91,9 +91,8 @@ struct wg_lstm_ppo_s;
 struct wg_lstm_pop_s {
     int P, device;
     wg_lstm_s* lstm[WGP_POP_MAX];
-    wg_policy_s* head[WGP_POP_MAX];
     wg_lstm_ppo_s* opt[WGP_POP_MAX];     // all null: a population that only acts
-    wg_pop_s heads;                       // the heads as k_policy_pop sees them: its slot table on the LSTMs' h rows (no optimisers)
+    wg_pop_s heads;                       // the members' MLPs (heads.pol[]) as k_policy_pop sees them: its slot table on the LSTMs' h rows (no optimisers)
     void* seq_dev;                        // [WGP_POP_MAX] WgLstmPopMember: the sequence kernels' member table of the running update
     void* upd_dev;                        // [2][WGP_POP_MAX] WgPopMember of that update: the heads' view (MLP part), Adam's (whole vector)
     void* rows_dev;                       // [WGP_POP_MAX] WgPopHeadRows

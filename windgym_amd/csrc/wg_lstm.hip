@@ -281,42 +281,12 @@ extern "C" int wg_lstm_pack_pop_(wg_lstm_pop q, const float* const* params_dev, 
 
 // The heads' slot table (wg_policy.h: WgPopSlot) on the LSTMs' h rows: P actor slots on h_pi (when an actor output is wanted), P
 // critic slots on h_vf (value), P critic slots on h_fin (final_value), member m on rows [m Bm, (m + 1) Bm).  The h rows are the
-// running step's (no step stride); the outputs are one call's (`step` = 0) or a rollout's [T, B, ..] (`step` = B).
+// running step's (no step stride); the outputs are one call's (o->step = 0) or a rollout's [T, B, ..] (o->step = B).
 extern "C" int wg_lstm_pop_slots_(wg_lstm_pop q, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* h_pi,
-                                  const float* h_vf, const float* h_fin, float* action, float* raw, float* logp, float* value,
-                                  float* final_value, int64_t step, void* stream) {
-    const WgPolicyP& P = q->head[0]->P;
-    const int Bm = n_rows / q->P, H = q->lstm[0]->P.H;
-    const bool actor = action || raw || logp;
-    WgPopSlot tab[WGP_POP_SLOTS] = {};
-    int ns = 0;
-    for (int kind = 0; kind < 3; ++kind) {
-        if (kind == 0 ? !actor : kind == 1 ? !value : !final_value) continue;
-        for (int m = 0; m < q->P; ++m) {
-            WgPopSlot& s = tab[ns++];
-            const size_t row = (size_t)m * Bm;
-            s.packed = q->head[m]->w.packed;
-            s.obs = (kind == 0 ? h_pi : kind == 1 ? h_vf : h_fin) + row * H;
-            s.obs_step = 0; s.act_step = step * P.n_out; s.row_step = step;
-            s.net = kind == 0 ? 0 : 1;
-            s.t_shift = kind == 2 ? -1 : 0;
-            if (kind == 0) {
-                s.action = action ? action + row * P.n_out : nullptr;
-                s.raw = raw ? raw + row * P.n_out : nullptr;
-                s.logp = logp ? logp + row : nullptr;
-                s.seed = seeds[m];
-                s.row_offset = row_offsets ? row_offsets[m] : 0;
-            } else {
-                s.value = (kind == 1 ? value : final_value) + row;
-            }
-        }
-    }
-    q->heads.n_head = (actor ? 1 : 0) + (value ? 1 : 0);
-    q->heads.has_final = final_value ? 1 : 0;
-    q->heads.Bm = Bm;
-    if (ns == 0 || Bm == 0) return 0;
-    if (int rc = wg_use_device(q->device)) return rc;
-    return wg_pop_store_(q->heads.slots_dev, tab, sizeof(WgPopSlot) * ns, stream);
+                                  const float* h_vf, const float* h_fin, const WgPopOuts* o, void* stream) {
+    const int H = q->lstm[0]->P.H;
+    const WgPopKind kinds[3] = {{h_pi, H, 0}, {h_vf, H, 0}, {h_fin, H, 0}};
+    return wg_pop_slots_(&q->heads, n_rows / q->P, kinds, o, seeds, row_offsets, stream);
 }
 
 // The members' LSTM steps and the MLPs behind them: two launches.  The critics' LSTMs run only when the value is wanted.
@@ -325,18 +295,16 @@ extern "C" int wg_lstm_pop_act(wg_lstm_pop q, int n_rows, const float* x_dev, co
                                const uint64_t* row_offsets, float* action_dev, float* raw_dev, float* logp_dev, float* value_dev, void* stream) {
     if (!q || !x_dev || !state_in_dev || !h_dev) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: null argument (q, x_dev, state_in_dev and h_dev are required)");
     if (n_rows < 0) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: n_rows < 0");
-    if (n_rows % q->P != 0)
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: the " + std::to_string(q->P) + " members own equal shares of the rows, and " +
-                                         std::to_string(n_rows) + " rows do not divide by " + std::to_string(q->P));
+    if (int rc = wg_pop_shares("wg_lstm_pop_act", q->P, n_rows, "rows", "", " rows do")) return rc;
     if ((action_dev || raw_dev || logp_dev) && !seeds) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: seeds[P] is required");
-    if ((action_dev || raw_dev || logp_dev) && !q->head[0]->P.has_log_std && (!deterministic || logp_dev))
+    if ((action_dev || raw_dev || logp_dev) && !q->heads.pol[0]->P.has_log_std && (!deterministic || logp_dev))
         return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_act: a stochastic action / a log-probability needs policies with log_std");
     const WgLstmP& L = q->lstm[0]->P;
     const bool two = L.n_nets == 2, critic = two && value_dev;
     float* const h_pi = h_dev;
     float* const h_vf = two ? h_dev + (size_t)n_rows * L.H : h_dev;
-    if (int rc = wg_lstm_pop_slots_(q, n_rows, seeds, row_offsets, h_pi, h_vf, nullptr, action_dev, raw_dev, logp_dev, value_dev, nullptr, 0, stream))
-        return rc;
+    const WgPopOuts o = {action_dev, raw_dev, logp_dev, value_dev, nullptr, 0};
+    if (int rc = wg_lstm_pop_slots_(q, n_rows, seeds, row_offsets, h_pi, h_vf, nullptr, &o, stream)) return rc;
     if (int rc = wg_lstm_pop_step_(q, n_rows, x_dev, episode_start_dev, state_in_dev, state_out_dev, h_pi, critic ? h_vf : nullptr,
                                    WG_LSTM_ACTOR | (critic ? WG_LSTM_CRITIC : 0), stream))
         return rc;

@@ -79,4 +79,26 @@ struct wg_lstm_ppo_s {
     int32_t nksT;
 };
 
+// THE STASH of a handle as the kernels are handed it — the one place that knows the layout above.  q: gates / c / h with their net
+// strides, dh, whhT with whhT_net and nksT, `shared`; the batch and the minibatch are the caller's to add.
+struct WgLstmStash {
+    WgLstmSeq q;
+    float *raw, *logp, *adv, *ret;         // the split of `rows`
+    const float* h[2];                     // the h plane the actor's / the critic's head reads (a shared LSTM: the one it has)
+    float* dh[2];                          // = q.dh, for the heads to write
+};
+inline WgLstmStash wglp_stash(const wg_lstm_ppo_s* o) {
+    const WgLstmP& L = o->lstm->P;
+    const size_t n_max = (size_t)o->T_max * o->Bm_max, npad = (size_t)o->T_max * o->NT_max * WGP_TILE, H = L.H;
+    WgLstmStash s = {};
+    s.q.shared = L.n_nets == 1;
+    s.q.gates = o->gates; s.q.c = o->c; s.q.h = o->h;
+    s.q.net_gates = npad * 4 * H; s.q.net_c = npad * H; s.q.net_h = n_max * H;
+    s.q.dh[0] = s.dh[0] = o->dh; s.q.dh[1] = s.dh[1] = o->dh + n_max * H;
+    s.q.whhT = o->whhT; s.q.whhT_net = o->whhT_net; s.q.nksT = o->nksT;
+    s.raw = o->rows; s.logp = s.raw + n_max * o->pol->P.n_out; s.adv = s.logp + n_max; s.ret = s.adv + n_max;
+    s.h[0] = o->h; s.h[1] = o->h + (size_t)(L.n_nets - 1) * s.q.net_h;
+    return s;
+}
+
 #endif

@@ -534,23 +534,18 @@ static int lp_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_bat
                    float* grad_out, float* stats_out, hipStream_t st) {
     const WgLstmP& L = o->lstm->P;
     const int T = b->T, n = T * Bm, n_out = o->pol->P.n_out;
-    const size_t n_max = (size_t)o->T_max * o->Bm_max, npad = (size_t)o->T_max * o->NT_max * WGP_TILE, H = L.H;
-    WgLstmSeq q = {};
+    const WgLstmStash s = wglp_stash(o);
+    WgLstmSeq q = s.q;
     q.obs = b->obs; q.start = b->episode_start; q.state0 = b->lstm_state0; q.envs = envs_dev;
-    q.T = T; q.B = b->B; q.Bm = Bm; q.NT = (Bm + WGP_TILE - 1) / WGP_TILE; q.shared = L.n_nets == 1;
-    q.gates = o->gates; q.c = o->c; q.h = o->h;
-    q.net_gates = npad * 4 * H; q.net_c = npad * H; q.net_h = n_max * H;
-    q.dh[0] = o->dh; q.dh[1] = o->dh + n_max * H;
-    q.whhT = o->whhT; q.whhT_net = o->whhT_net; q.nksT = o->nksT;
-    float *raw = o->rows, *logp = raw + n_max * n_out, *adv = logp + n_max, *ret = adv + n_max;
+    q.T = T; q.B = b->B; q.Bm = Bm; q.NT = (Bm + WGP_TILE - 1) / WGP_TILE;
     hipLaunchKernelGGL(k_lstm_ppo_pack, dim3((o->whhT_all + 255) / 256), dim3(256), 0, st, L, params_dev, o->whhT, o->whhT_net, o->whhT_all,
                        (uint32_t)o->nksT);
-    hipLaunchKernelGGL(k_lstm_ppo_gather, dim3((n + 255) / 256), dim3(256), 0, st, q, n_out, b->raw, b->logp, b->advantage, b->returns, raw, logp,
-                       adv, ret);
+    hipLaunchKernelGGL(k_lstm_ppo_gather, dim3((n + 255) / 256), dim3(256), 0, st, q, n_out, b->raw, b->logp, b->advantage, b->returns, s.raw, s.logp,
+                       s.adv, s.ret);
     hipLaunchKernelGGL(k_lstm_seq_fwd, dim3(q.NT, L.n_nets), dim3(WGP_WAVES * 64), 0, st, L, o->lstm->w.packed, q);
     WG_HIPCHK(hipGetLastError());
-    if (int rc = wg_ppo_heads_grad_(&o->heads, params_dev + o->n_lstm, o->h, o->h + (size_t)(L.n_nets - 1) * q.net_h, raw, logp, adv, ret, n, hp,
-                                    o->dh, o->dh + n_max * H, grad_out + o->n_lstm, stats_out ? stats_out : o->stats, (void*)st))
+    if (int rc = wg_ppo_heads_grad_(&o->heads, params_dev + o->n_lstm, s.h[0], s.h[1], s.raw, s.logp, s.adv, s.ret, n, hp, s.dh[0], s.dh[1],
+                                    grad_out + o->n_lstm, stats_out ? stats_out : o->stats, (void*)st))
         return rc;
     hipLaunchKernelGGL(k_lstm_seq_bwd, dim3(q.NT, L.n_nets), dim3(WGP_WAVES * 64), 0, st, L, q);
     const int nblk = T * q.NT, S = nblk < WGLP_SPLIT ? nblk : WGLP_SPLIT;
@@ -603,13 +598,12 @@ extern "C" int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lst
 extern "C" int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, const wg_lstm_ppo* opts, int P, wg_lstm_pop* out) {
     if (!lstms || !heads || !out) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_create: null argument");
     *out = nullptr;
-    if (P < 1 || P > WG_POP_MAX)
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_create: a population has 1 .. " + std::to_string(WG_POP_MAX) + " members, not " + std::to_string(P));
+    if (int rc = wg_pop_count("wg_lstm_pop_create", P)) return rc;
     for (int m = 0; m < P; ++m) {
         const std::string who = "wg_lstm_pop_create: member " + std::to_string(m);
         if (!lstms[m] || !heads[m]) return wg_fail(WG_ERR_INVALID, who + " is null");
         const WgLstmP &L0 = lstms[0]->P, &L = lstms[m]->P;
-        const WgPolicyP &A = heads[0]->P, &Q = heads[m]->P;
+        const WgPolicyP& Q = heads[m]->P;
         if (Q.n_in != L.H || Q.n_layers[1] == 0 || Q.n_in_vf != L.H)
             return wg_fail(WG_ERR_INVALID, who + ": its head must map the LSTM's hidden size (" + std::to_string(L.H) + ") with its critic on the same width; it maps " +
                                              std::to_string(Q.n_in) + " inputs, its critic " + std::to_string(Q.n_layers[1] ? Q.n_in_vf : 0));
@@ -617,18 +611,10 @@ extern "C" int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, 
             return wg_fail(WG_ERR_INVALID, who + "'s LSTM maps " + std::to_string(L.n_in) + " -> " + std::to_string(L.H) + " with " + std::to_string(L.n_nets) +
                                              " net(s), member 0's " + std::to_string(L0.n_in) + " -> " + std::to_string(L0.H) + " with " +
                                              std::to_string(L0.n_nets) + ": the members of a population share one n_in, hidden size and number of nets");
-        // the layer table is a function of the wg_policy_desc alone: equal descs <=> equal tables
-        bool same = Q.n_out == A.n_out && Q.activation == A.activation && Q.has_log_std == A.has_log_std && Q.n_layers[0] == A.n_layers[0] &&
-                    Q.n_layers[1] == A.n_layers[1] && Q.n_flat == A.n_flat;
-        for (int net = 0; net < 2 && same; ++net)
-            for (int l = 0; l < Q.n_layers[net]; ++l) same = same && Q.layer[net][l].K == A.layer[net][l].K && Q.layer[net][l].M == A.layer[net][l].M;
-        if (!same) return wg_fail(WG_ERR_INVALID, who + "'s head has another architecture than member 0's: the members of a population share one");
-        if (lstms[m]->w.device != lstms[0]->w.device || heads[m]->w.device != lstms[0]->w.device)
-            return wg_fail(WG_ERR_INVALID, who + " lives on device " + std::to_string(lstms[m]->w.device) + " / " + std::to_string(heads[m]->w.device) +
-                                             " (LSTM / head), member 0 on device " + std::to_string(lstms[0]->w.device));
-        for (int k = 0; k < m; ++k)
-            if (lstms[k] == lstms[m] || heads[k] == heads[m])
-                return wg_fail(WG_ERR_INVALID, who + " holds the same handle as member " + std::to_string(k));
+        if (!wgp_same_arch(heads[0]->P, Q, false))      // (the widths: both are H, above)
+            return wg_fail(WG_ERR_INVALID, who + "'s head has another architecture than member 0's: the members of a population share one");
+        if (int rc = wg_pop_same_device(who, lstms[0]->w.device, " (LSTM / head)", lstms[m]->w.device, heads[m]->w.device)) return rc;
+        if (int rc = wg_pop_given_twice(who, m, " holds the same handle as member ", lstms, heads)) return rc;
         if (opts) {
             if (!opts[m]) return wg_fail(WG_ERR_INVALID, who + ": its wg_lstm_ppo is null (opts = NULL makes a population that only acts)");
             if (opts[m]->lstm != lstms[m] || opts[m]->pol != heads[m])
@@ -639,7 +625,7 @@ extern "C" int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, 
     if (!q) return wg_fail(WG_ERR_NOMEM, "wg_lstm_pop_create: out of host memory");
     q->P = q->heads.P = P;
     q->device = q->heads.device = lstms[0]->w.device;
-    for (int m = 0; m < P; ++m) { q->lstm[m] = lstms[m]; q->head[m] = q->heads.pol[m] = heads[m]; q->opt[m] = opts ? opts[m] : nullptr; }
+    for (int m = 0; m < P; ++m) { q->lstm[m] = lstms[m]; q->heads.pol[m] = heads[m]; q->opt[m] = opts ? opts[m] : nullptr; }
     hipError_t e = hipSetDevice(q->device);
     if (e == hipSuccess) e = hipMalloc((void**)&q->heads.slots_dev, sizeof(WgPopSlot) * WGP_POP_SLOTS);
     if (e == hipSuccess) e = hipMalloc(&q->seq_dev, sizeof(WgLstmPopMember) * WGP_POP_MAX);
@@ -669,18 +655,10 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
                                   wg_ppo_stats* stats_out, void* stream) {
     if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: null argument");
     const int P = q->P;
-    if (!q->opt[0])
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: the population was created without optimisers (opts = NULL): it only acts");
-    if (n_epochs < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: n_epochs must be >= 1");
-    for (int m = 0; m < P; ++m) {
-        const std::string who = "wg_lstm_pop_update: member " + std::to_string(m);
-        if (!params_dev[m]) return wg_fail(WG_ERR_INVALID, who + ": params_dev is null");
-        if (int rc = lp_check(who, q->opt[m], b, &hp[m], envs_per_batch)) return rc;
-        if (!(max_grad_norm[m] > 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": max_grad_norm must be > 0");
-    }
-    if (b->B % P != 0)
-        return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_update: the " + std::to_string(P) + " members own equal shares of the envs, and B = " +
-                                         std::to_string(b->B) + " does not divide by " + std::to_string(P));
+    if (int rc = wg_pop_update_check("wg_lstm_pop_update", q->opt[0], n_epochs >= 1, "n_epochs", P, params_dev, max_grad_norm)) return rc;
+    for (int m = 0; m < P; ++m)
+        if (int rc = lp_check("wg_lstm_pop_update: member " + std::to_string(m), q->opt[m], b, &hp[m], envs_per_batch)) return rc;
+    if (int rc = wg_pop_shares("wg_lstm_pop_update", P, b->B, "envs", "B = ", " does")) return rc;
     if (int rc = wg_use_device(q->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const WgLstmP& L = q->lstm[0]->P;
@@ -693,33 +671,24 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
     WgLstmPopMember seq[WGP_POP_MAX] = {};
     WgPopMember upd[2 * WGP_POP_MAX] = {};
     WgPopHeadRows rows[WGP_POP_MAX] = {};
+    WgAdam* adam[WGP_POP_MAX];
     bool any_norm = false;
     for (int m = 0; m < P; ++m) {
         wg_lstm_ppo_s* o = q->opt[m];
-        const size_t n_max = (size_t)o->T_max * o->Bm_max, npad = (size_t)o->T_max * o->NT_max * WGP_TILE;
+        const WgLstmStash s = wglp_stash(o);
+        adam[m] = &o->adam;
         WgLstmPopMember& S = seq[m];
-        WgLstmSeq& s = S.q;
-        s.obs = b->obs; s.start = b->episode_start; s.envs = perm_dev + (size_t)m * n_epochs * sB;
-        s.state0 = b->lstm_state0 + (size_t)m * L.n_nets * 2 * sB * H - (size_t)m * sB * H;
-        s.T = T; s.B = b->B; s.sB = sB; s.shared = L.n_nets == 1;
-        s.gates = o->gates; s.c = o->c; s.h = o->h;
-        s.net_gates = npad * 4 * H; s.net_c = npad * H; s.net_h = n_max * H;
-        s.dh[0] = o->dh; s.dh[1] = o->dh + n_max * H;
-        s.whhT = o->whhT; s.whhT_net = o->whhT_net; s.nksT = o->nksT;
+        S.q = s.q;
+        S.q.obs = b->obs; S.q.start = b->episode_start; S.q.envs = perm_dev + (size_t)m * n_epochs * sB;
+        S.q.state0 = b->lstm_state0 + (size_t)m * L.n_nets * 2 * sB * H - (size_t)m * sB * H;
+        S.q.T = T; S.q.B = b->B; S.q.sB = sB;
         S.packed = o->lstm->w.packed; S.params = params_dev[m]; S.whhT = o->whhT; S.wpart = o->wpart; S.grad = o->grad;
-        S.raw = o->rows; S.logp = S.raw + n_max * n_out; S.adv = S.logp + n_max; S.ret = S.adv + n_max;
-        WgPopHeadRows& R = rows[m];
-        R.obs[0] = o->h; R.obs[1] = o->h + (size_t)(L.n_nets - 1) * s.net_h;
-        R.raw = S.raw; R.logp_old = S.logp; R.adv = S.adv; R.ret = S.ret;
-        R.dh[0] = o->dh; R.dh[1] = o->dh + n_max * H;
+        S.raw = s.raw; S.logp = s.logp; S.adv = s.adv; S.ret = s.ret;
+        rows[m] = {{s.h[0], s.h[1]}, s.raw, s.logp, s.adv, s.ret, {s.dh[0], s.dh[1]}};
         WgPopMember& M = upd[m];
         M.packed = o->pol->w.packed; M.params = params_dev[m] + o->n_lstm; M.grad = o->grad + o->n_lstm;
         M.part = o->heads.part; M.spart = o->heads.spart; M.advstat = o->heads.advstat;
-        M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->stats;
-        M.stats_step = stats_out ? WGT_NSTAT : 0;
-        M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef;
-        M.normalize = hp[m].normalize_advantage != 0;
-        any_norm = any_norm || M.normalize;
+        any_norm = wgt_pop_member(M, hp, stats_out, m, n_epochs, n_mb, o->stats) || any_norm;
         WgPopMember& A = upd[WGP_POP_MAX + m];
         A.params = params_dev[m]; A.grad = o->grad; A.m = o->adam.m; A.v = o->adam.v; A.blocksq = o->adam.blocksq; A.max_norm = max_grad_norm[m];
     }
@@ -730,7 +699,6 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
     if (int rc = wg_pop_store_(q->upd_dev, upd, sizeof(upd), stream)) return rc;
     if (int rc = wg_pop_store_(q->rows_dev, rows, sizeof(WgPopHeadRows) * P, stream)) return rc;
     const wg_lstm_ppo_s* o0 = q->opt[0];
-    const uint32_t n_flat = o0->adam.n_flat;
     // every member has the architecture of member 0: per minibatch the launches of lp_grad and lp_apply, each with the member axis
     return wg_each_minibatch(sB, n_epochs, envs_per_batch, [&](int mb, int64_t off, int Bm) {
         const int n = T * Bm, NT = (Bm + WGP_TILE - 1) / WGP_TILE;
@@ -747,13 +715,7 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
                            st, L, mt, off, Bm, NT, S);
         hipLaunchKernelGGL(k_lstm_wgrad_reduce_pop, dim3((o0->n_lstm + 255) / 256, P), dim3(256), 0, st, mt, o0->n_lstm, S);
         WG_HIPCHK(hipGetLastError());
-        float step_size[WGP_POP_MAX], bc2_sqrt[WGP_POP_MAX];
-        for (int m = 0; m < P; ++m) {
-            const WgAdamStep s = wg_adam_count(&q->opt[m]->adam, lr[m]);
-            step_size[m] = s.step_size;
-            bc2_sqrt[m] = s.bc2_sqrt;
-        }
-        if (int rc = wg_adam_apply_pop_(ht + WGP_POP_MAX, P, n_flat, step_size, bc2_sqrt, stream)) return rc;
+        if (int rc = wg_adam_apply_pop_(ht + WGP_POP_MAX, P, adam, lr, stream)) return rc;
         if (int rc = wg_lstm_pack_pop_(q, params_dev, stream)) return rc;
         wg_policy_pack_pop_(&PP, ht, P, stream);
         WG_HIPCHK(hipGetLastError());

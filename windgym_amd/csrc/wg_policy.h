@@ -141,14 +141,55 @@ struct wg_pop_s {
     void* upd_dev;                 // [WGP_POP_MAX] WgPopMember: the member table of the running wg_pop_update
 };
 
-// what the slots of a population launch read and write; `B` = rows of one step of every buffer (the stride of a rollout's steps)
-struct WgPopRows {
-    const float* obs;
-    float *action, *raw, *logp, *value;
-    const float* final_obs;
-    float* final_value;
-    int64_t B;
-    int stepped;                   // 1: the buffers are a rollout's [T (+ 1), B, ..]; 0: one call, steps are 0
-};
+// The slot table, stated once for the plain population (rows = observations) and the recurrent one (rows = the LSTMs' h rows).
+// What one KIND of slot reads: member 0's first row, the rows' width, and the floats from one step of a rollout to the next (0: the
+// rows stay where they are); kinds in the order actor, critic, critic on the final rows
+struct WgPopKind { const float* rows; int width; int64_t step; };
+// what the slots write: member 0's first row of each array (null: not wanted; a kind with no output wanted has no slots) and the
+// ROWS from one step to the next of all of them (a rollout's [T, B, ..]: B; one call: 0)
+struct WgPopOuts { float *action, *raw, *logp, *value, *final_value; int64_t step; };
+struct WgPopShape { int ns, n_head, has_final, Bm; };     // slots written; wg_pop_s's three fields
+
+// tab[0 .. ns): per wanted kind P slots, member m on rows [m Bm, (m + 1) Bm) of every array with its own weights packed[m], noise
+// key seeds[m] and first global row row_offsets[m] (null: 0; both are read for actor slots only)
+inline WgPopShape wgp_pop_slots(WgPopSlot* tab, int P, int Bm, int n_out, const float* const* packed, const WgPopKind kinds[3],
+                                const WgPopOuts& o, const uint64_t* seeds, const uint64_t* row_offsets) {
+    const bool actor = o.action || o.raw || o.logp;
+    int ns = 0;
+    for (int kind = 0; kind < 3; ++kind) {
+        if (kind == 0 ? !actor : kind == 1 ? !o.value : !o.final_value) continue;
+        for (int m = 0; m < P; ++m) {
+            WgPopSlot& s = tab[ns++];
+            const size_t row = (size_t)m * Bm;
+            s.packed = packed[m];
+            s.obs = kinds[kind].rows + row * kinds[kind].width;
+            s.obs_step = kinds[kind].step; s.act_step = o.step * n_out; s.row_step = o.step;
+            s.net = kind == 0 ? 0 : 1;
+            s.t_shift = kind == 2 ? -1 : 0;
+            if (kind == 0) {
+                s.action = o.action ? o.action + row * n_out : nullptr;
+                s.raw = o.raw ? o.raw + row * n_out : nullptr;
+                s.logp = o.logp ? o.logp + row : nullptr;
+                s.seed = seeds[m];
+                s.row_offset = row_offsets ? row_offsets[m] : 0;
+            } else {
+                s.value = (kind == 1 ? o.value : o.final_value) + row;
+            }
+        }
+    }
+    return {ns, (actor ? 1 : 0) + (o.value ? 1 : 0), o.final_value ? 1 : 0, Bm};
+}
+
+// Two policies of one population have ONE architecture.  The layer table is a function of the wg_policy_desc alone (equal descs <=>
+// equal tables, and with them equal n_flat).  `widths`: the input widths n_in / n_in_vf take part — not for the heads of a recurrent
+// population, whose widths the check against their LSTMs covers.
+inline bool wgp_same_arch(const WgPolicyP& A, const WgPolicyP& Q, bool widths) {
+    bool same = Q.n_out == A.n_out && Q.activation == A.activation && Q.has_log_std == A.has_log_std && Q.n_layers[0] == A.n_layers[0] &&
+                Q.n_layers[1] == A.n_layers[1] && (!widths || (Q.n_in == A.n_in && Q.n_in_vf == A.n_in_vf));
+    for (int net = 0; net < 2 && same; ++net)
+        for (int l = 0; l < Q.n_layers[net]; ++l)
+            same = same && ((l == 0 && !widths) || Q.layer[net][l].K == A.layer[net][l].K) && Q.layer[net][l].M == A.layer[net][l].M;
+    return same;
+}
 
 #endif

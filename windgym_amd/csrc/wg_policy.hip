@@ -364,52 +364,33 @@ extern "C" void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, i
     hipLaunchKernelGGL(k_policy_pack_pop, dim3((P->n_packed + 255) / 256, n_members), dim3(256), 0, (hipStream_t)stream, *P, mt);
 }
 
-// Write the slot table for `n_rows` rows split evenly among the members: P actor slots (when an actor output is wanted), P critic
-// slots (r->value), P critic slots on the final rows (r->final_value), in this order, stored in stream order (launches enqueued
-// before on the same stream still read the old table: a population is used on one stream at a time).
-extern "C" int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets,
-                               const WgPopRows* r, void* stream) {
+// Write the slot table for `n_rows` rows of observations split evenly among the members: P actor slots (when an actor output is
+// wanted), P critic slots (o->value), P critic slots on the final rows (o->final_value), in this order, stored in stream order
+// (launches enqueued before on the same stream still read the old table: a population is used on one stream at a time).
+extern "C" int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* obs,
+                               const float* final_obs, const WgPopOuts* o, void* stream) {
     const std::string w = who;
     const WgPolicyP& P = q->pol[0]->P;
     if (n_rows < 0) return wg_fail(WG_ERR_INVALID, w + ": n_rows < 0");
-    if (n_rows % q->P != 0)
-        return wg_fail(WG_ERR_INVALID, w + ": the " + std::to_string(q->P) + " members own equal shares of the rows, and " +
-                                         std::to_string(n_rows) + " rows do not divide by " + std::to_string(q->P));
-    const bool actor = r->action || r->raw || r->logp;
-    if ((r->value || r->final_value) && P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, w + ": value requested from policies without a critic");
+    if (int rc = wg_pop_shares(w, q->P, n_rows, "rows", "", " rows do")) return rc;
+    const bool actor = o->action || o->raw || o->logp;
+    if ((o->value || o->final_value) && P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, w + ": value requested from policies without a critic");
     if (actor && !seeds) return wg_fail(WG_ERR_INVALID, w + ": seeds[P] is required");
-    const int Bm = n_rows / q->P;
-    const int64_t step = r->stepped ? r->B : 0;
+    const WgPopKind kinds[3] = {{obs, P.n_in, o->step * P.n_in}, {obs, P.n_in_vf, o->step * P.n_in_vf}, {final_obs, P.n_in_vf, o->step * P.n_in_vf}};
+    return wg_pop_slots_(q, n_rows / q->P, kinds, o, seeds, row_offsets, stream);
+}
+
+// wgp_pop_slots (wg_policy.h) for the members of q on Bm rows each: the table's shape into q, the table into q->slots_dev
+extern "C" int wg_pop_slots_(wg_pop q, int Bm, const WgPopKind* kinds, const WgPopOuts* o, const uint64_t* seeds, const uint64_t* row_offsets,
+                             void* stream) {
+    const float* packed[WGP_POP_MAX];
+    for (int m = 0; m < q->P; ++m) packed[m] = q->pol[m]->w.packed;
     WgPopSlot tab[WGP_POP_SLOTS] = {};
-    int ns = 0;
-    for (int kind = 0; kind < 3; ++kind) {
-        if (kind == 0 ? !actor : kind == 1 ? !r->value : !r->final_value) continue;
-        for (int m = 0; m < q->P; ++m) {
-            WgPopSlot& s = tab[ns++];
-            const size_t row = (size_t)m * Bm;
-            const int width = kind == 0 ? P.n_in : P.n_in_vf;
-            s.packed = q->pol[m]->w.packed;
-            s.obs = (kind == 2 ? r->final_obs : r->obs) + row * width;
-            s.obs_step = step * width; s.act_step = step * P.n_out; s.row_step = step;
-            s.net = kind == 0 ? 0 : 1;
-            s.t_shift = kind == 2 ? -1 : 0;
-            if (kind == 0) {
-                s.action = r->action ? r->action + row * P.n_out : nullptr;
-                s.raw = r->raw ? r->raw + row * P.n_out : nullptr;
-                s.logp = r->logp ? r->logp + row : nullptr;
-                s.seed = seeds[m];
-                s.row_offset = row_offsets ? row_offsets[m] : 0;
-            } else {
-                s.value = (kind == 1 ? r->value : r->final_value) + row;
-            }
-        }
-    }
-    q->n_head = (actor ? 1 : 0) + (r->value ? 1 : 0);
-    q->has_final = r->final_value ? 1 : 0;
-    q->Bm = Bm;
-    if (ns == 0 || Bm == 0) return 0;
+    const WgPopShape s = wgp_pop_slots(tab, q->P, Bm, q->pol[0]->P.n_out, packed, kinds, *o, seeds, row_offsets);
+    q->n_head = s.n_head; q->has_final = s.has_final; q->Bm = s.Bm;
+    if (s.ns == 0 || Bm == 0) return 0;
     if (int rc = wg_use_device(q->device)) return rc;
-    return wg_pop_store_(q->slots_dev, tab, sizeof(WgPopSlot) * ns, stream);
+    return wg_pop_store_(q->slots_dev, tab, sizeof(WgPopSlot) * s.ns, stream);
 }
 
 // ONE launch of k_policy_pop on the prepared table: the kinds of step t's own rows (`head`: actor and / or critic) and / or the
@@ -432,7 +413,7 @@ extern "C" int wg_pop_act(wg_pop q, int n_rows, const float* obs_dev, int determ
     const WgPolicyP& P = q->pol[0]->P;
     if ((action_dev || raw_dev || logp_dev) && !P.has_log_std && (!deterministic || logp_dev))
         return wg_fail(WG_ERR_INVALID, "wg_pop_act: a stochastic action / a log-probability needs policies with log_std");
-    const WgPopRows r = {obs_dev, action_dev, raw_dev, logp_dev, value_dev, nullptr, nullptr, n_rows, 0};
-    if (int rc = wg_pop_prepare_(q, "wg_pop_act", n_rows, seeds, row_offsets, &r, stream)) return rc;
+    const WgPopOuts o = {action_dev, raw_dev, logp_dev, value_dev, nullptr, 0};
+    if (int rc = wg_pop_prepare_(q, "wg_pop_act", n_rows, seeds, row_offsets, obs_dev, nullptr, &o, stream)) return rc;
     return wg_pop_launch_(q, 1, 0, 0, deterministic, counter, stream);
 }

@@ -52,6 +52,16 @@ struct WgPpoGrad {
     float *stats;                         // [WGT_NSTAT] scratch record when the caller wants none
 };
 
+// The hyper-parameter and statistics fields of member m's row of an update's member table (wg_pop_update, wg_lstm_pop_update): the
+// member's [n_epochs][n_mb] records of stats_out, or the one `fallback` record written over and over -> the member normalises
+inline bool wgt_pop_member(WgPopMember& M, const wg_ppo_hyper* hp, wg_ppo_stats* stats_out, int m, int n_epochs, int n_mb, float* fallback) {
+    M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : fallback;
+    M.stats_step = stats_out ? WGT_NSTAT : 0;
+    M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef;
+    M.normalize = hp[m].normalize_advantage != 0;
+    return M.normalize;
+}
+
 struct wg_ppo_s {
     WgPpoGrad g;
     WgAdam adam;                          // over the policy's flat vector, on the policy's device

@@ -819,12 +819,14 @@ extern "C" int wg_ppo_heads_grad_pop_(const WgPpoGrad* g0, const WgPopMember* mt
     return 0;
 }
 
-extern "C" int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, uint32_t n_flat, const float* step_size, const float* bc2_sqrt,
-                                  void* stream) {
+extern "C" int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, WgAdam* const* adam, const float* lr, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t n_blocks = (n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    const uint32_t n_flat = adam[0]->n_flat, n_blocks = (n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
     WgPopAdam A = {};
-    for (int m = 0; m < n_members; ++m) { A.step_size[m] = step_size[m]; A.bc2_sqrt[m] = bc2_sqrt[m]; }
+    for (int m = 0; m < n_members; ++m) {
+        const WgAdamStep s = wg_adam_count(adam[m], lr[m]);
+        A.step_size[m] = s.step_size; A.bc2_sqrt[m] = s.bc2_sqrt;
+    }
     hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat);
     hipLaunchKernelGGL(k_ppo_adam_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat, n_blocks, A, (float)(1.0 - ADAM_B1),
                        (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
@@ -921,26 +923,18 @@ extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b,
 extern "C" int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P, wg_pop* out) {
     if (!members || !out) return wg_fail(WG_ERR_INVALID, "wg_pop_create: null argument");
     *out = nullptr;
-    if (P < 1 || P > WG_POP_MAX)
-        return wg_fail(WG_ERR_INVALID, "wg_pop_create: a population has 1 .. " + std::to_string(WG_POP_MAX) + " members, not " + std::to_string(P));
+    if (int rc = wg_pop_count("wg_pop_create", P)) return rc;
     for (int m = 0; m < P; ++m) {
         const std::string who = "wg_pop_create: member " + std::to_string(m);
         if (!members[m]) return wg_fail(WG_ERR_INVALID, who + " is null");
-        const WgPolicyP &A = members[0]->P, &Q = members[m]->P;
+        const WgPolicyP& Q = members[m]->P;
         if (Q.n_layers[1] != 0 && Q.n_in_vf != Q.n_in)
             return wg_fail(WG_ERR_INVALID, who + " is a split policy (its critic reads " + std::to_string(Q.n_in_vf) + " inputs, its actor " +
                                              std::to_string(Q.n_in) + "): populations take policies whose nets read the same rows");
-        if (members[m]->w.device != members[0]->w.device)
-            return wg_fail(WG_ERR_INVALID, who + " lives on device " + std::to_string(members[m]->w.device) + ", member 0 on device " +
-                                             std::to_string(members[0]->w.device));
-        // the layer table is a function of the wg_policy_desc alone: equal descs <=> equal tables
-        bool same = Q.n_in == A.n_in && Q.n_out == A.n_out && Q.activation == A.activation && Q.has_log_std == A.has_log_std &&
-                    Q.n_in_vf == A.n_in_vf && Q.n_layers[0] == A.n_layers[0] && Q.n_layers[1] == A.n_layers[1] && Q.n_flat == A.n_flat;
-        for (int net = 0; net < 2 && same; ++net)
-            for (int l = 0; l < Q.n_layers[net]; ++l) same = same && Q.layer[net][l].K == A.layer[net][l].K && Q.layer[net][l].M == A.layer[net][l].M;
-        if (!same) return wg_fail(WG_ERR_INVALID, who + " has another architecture than member 0: the members of a population share one");
-        for (int k = 0; k < m; ++k)
-            if (members[k] == members[m]) return wg_fail(WG_ERR_INVALID, who + " is the same policy as member " + std::to_string(k));
+        if (int rc = wg_pop_same_device(who, members[0]->w.device, "", members[m]->w.device)) return rc;
+        if (!wgp_same_arch(members[0]->P, Q, true))
+            return wg_fail(WG_ERR_INVALID, who + " has another architecture than member 0: the members of a population share one");
+        if (int rc = wg_pop_given_twice(who, m, " is the same policy as member ", members)) return rc;
         if (opts) {
             if (!opts[m]) return wg_fail(WG_ERR_INVALID, who + ": its wg_ppo is null (opts = NULL makes a population that only acts)");
             if (opts[m]->g.pol != members[m]) return wg_fail(WG_ERR_INVALID, who + ": opts[" + std::to_string(m) + "] was created for another policy");
@@ -992,18 +986,14 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
                              wg_ppo_stats* stats_out, void* stream) {
     if (!q || !params_dev || !b || !perm_dev || !hp || !lr || !max_grad_norm) return wg_fail(WG_ERR_INVALID, "wg_pop_update: null argument");
     const int P = q->P;
-    if (!q->opt[0]) return wg_fail(WG_ERR_INVALID, "wg_pop_update: the population was created without optimisers (opts = NULL): it only acts");
+    if (int rc = wg_pop_update_check("wg_pop_update", q->opt[0], n_epochs >= 1 && batch_size >= 1, "n_epochs and batch_size", P, params_dev, max_grad_norm))
+        return rc;
     if (int rc = t_check_rows("wg_pop_update", b, b->obs)) return rc;
-    if (b->n_rows % P != 0)
-        return wg_fail(WG_ERR_INVALID, "wg_pop_update: the " + std::to_string(P) + " members own equal shares of the batch, and " +
-                                         std::to_string(b->n_rows) + " rows do not divide by " + std::to_string(P));
-    if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, "wg_pop_update: n_epochs and batch_size must be >= 1");
+    if (int rc = wg_pop_shares("wg_pop_update", P, b->n_rows, "batch", "", " rows do")) return rc;
     if (int rc = wg_use_device(q->device)) return rc;
     for (int m = 0; m < P; ++m) {
         const std::string who = "wg_pop_update: member " + std::to_string(m);
-        if (!params_dev[m]) return wg_fail(WG_ERR_INVALID, who + ": params_dev is null");
         if (!(hp[m].clip_range >= 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": clip_range < 0");
-        if (!(max_grad_norm[m] > 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": max_grad_norm must be > 0");
         if (int rc = t_on_device(params_dev[m], q->device, (who + ": params_dev").c_str())) return rc;
     }
     if (int rc = t_on_device(b->obs, q->device, "wg_pop_update: obs")) return rc;
@@ -1012,25 +1002,23 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     const int64_t rows_m = b->n_rows / P;
     const int n_mb = wg_n_minibatches(rows_m, batch_size);
     WgPopMember tab[WGP_POP_MAX] = {};
+    WgAdam* adam[WGP_POP_MAX];
+    bool any_norm = false;
     for (int m = 0; m < P; ++m) {
         wg_ppo_s* o = q->opt[m];
         WgPopMember& M = tab[m];
+        adam[m] = &o->adam;
         M.packed = o->g.pol->w.packed; M.params = params_dev[m];
         M.m = o->adam.m; M.v = o->adam.v; M.grad = o->grad; M.part = o->g.part; M.spart = o->g.spart; M.advstat = o->g.advstat; M.blocksq = o->adam.blocksq;
         M.perm = perm_dev + (size_t)m * n_epochs * rows_m;
-        M.stats = stats_out ? (float*)(stats_out + (size_t)m * n_epochs * n_mb) : o->g.stats;
-        M.stats_step = stats_out ? WGT_NSTAT : 0;
-        M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef; M.max_norm = max_grad_norm[m];
-        M.normalize = hp[m].normalize_advantage != 0;
+        M.max_norm = max_grad_norm[m];
+        any_norm = wgt_pop_member(M, hp, stats_out, m, n_epochs, n_mb, o->g.stats) || any_norm;
     }
     const WgPopMember* mt = (const WgPopMember*)q->upd_dev;
     if (int rc = wg_pop_store_(q->upd_dev, tab, sizeof(WgPopMember) * P, stream)) return rc;
     // every member has the architecture of member 0: one layer table, one LDS map, one G per minibatch size
     const WgPpoGrad* g0 = &q->opt[0]->g;
-    const WgAdam* a0 = &q->opt[0]->adam;
     const WgPolicyP& PP = g0->pol->P;
-    bool any_norm = false;
-    for (int m = 0; m < P; ++m) any_norm = any_norm || tab[m].normalize;
     return wg_each_minibatch(rows_m, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
         const int G = t_grid(g0, n);
         if (any_norm && n > 1) hipLaunchKernelGGL(k_ppo_advstat_pop, dim3(P), dim3(1024), 0, st, mt, b->advantage, off, n, b->n_rows);
@@ -1039,13 +1027,7 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
         a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
         hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), g0->lds_bytes, st, PP, g0->K, a, mt, off);
         hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(g0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
-        float step_size[WGP_POP_MAX], bc2_sqrt[WGP_POP_MAX];
-        for (int m = 0; m < P; ++m) {
-            const WgAdamStep s = wg_adam_count(&q->opt[m]->adam, lr[m]);
-            step_size[m] = s.step_size;
-            bc2_sqrt[m] = s.bc2_sqrt;
-        }
-        if (int rc = wg_adam_apply_pop_(mt, P, a0->n_flat, step_size, bc2_sqrt, stream)) return rc;
+        if (int rc = wg_adam_apply_pop_(mt, P, adam, lr, stream)) return rc;
         wg_policy_pack_pop_(&PP, mt, P, stream);
         WG_HIPCHK(hipGetLastError());
         return 0;

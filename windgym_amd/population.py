@@ -42,44 +42,54 @@ def global_rows(local, member, n_envs, n_envs_member):
     return (local // Bm) * B + int(member) * Bm + local % Bm
 
 
+def check_member_count(n_members):
+    if not 1 <= n_members <= POP_MAX:
+        raise ValueError(f"a population has 1 .. {POP_MAX} members, not {n_members}")
+
+
 def check_population_shape(n_members, n_envs):
     """-> envs per member; raises ``ValueError`` for what wg_pop_create / wg_pop_rollout would refuse."""
     P, B = int(n_members), int(n_envs)
-    if not 1 <= P <= POP_MAX:
-        raise ValueError(f"a population has 1 .. {POP_MAX} members, not {P}")
+    check_member_count(P)
     if B % P:
         raise ValueError(f"the {P} members own equal shares of the envs: num_envs = {B} does not divide by {P}")
     return B // P
 
 
-class Population:
-    """``P`` :class:`MlpPolicy` objects of one architecture behind one ``wg_pop`` handle: ``act`` / ``value`` are ONE launch of
-    the policy kernel for all members, member ``m`` on rows ``[m * Bm, (m + 1) * Bm)``; ``venv.rollout(pop, T)`` is wg_pop_rollout.
-    ``optimizers``: the members' :class:`PPOOptimizer` objects (needed by wg_pop_update only)."""
+def check_members(members):
+    """The members as a list: 1 .. ``POP_MAX`` of them, no object twice."""
+    members = list(members)
+    check_member_count(len(members))
+    for m, p in enumerate(members):
+        for k in range(m):
+            if p is members[k]:
+                raise ValueError(f"member {m} is the same policy as member {k}")
+    return members
+
+
+class PopulationBase:
+    """What the two acting objects (:class:`Population`, ``recurrent_population.RecurrentPopulation``) share: the members behind one
+    population handle of the library.  A subclass names the check of its members and the entry that destroys its handle, and states
+    ``_create(arr)`` -> the handle, ``arr`` making the ``void*[P]`` of a list of handles."""
+
+    check, destroy = staticmethod(check_members), None
 
     def __init__(self, members, optimizers=None):
         from .binding import _chk
-        members = list(members)
-        if not 1 <= len(members) <= POP_MAX:
-            raise ValueError(f"a population has 1 .. {POP_MAX} members, not {len(members)}")
+        self.members = members = self.check(members)
+        self.optimizers = None if optimizers is None else list(optimizers)
         p0 = members[0]
-        self.members, self.optimizers = members, None if optimizers is None else list(optimizers)
         self.L, self._chk, self.torch, self.device = p0.L, _chk, p0.torch, p0.device
         self.n_members = P = len(members)
-        self.desc, self.n_in, self.n_out, self.n_in_vf = p0.desc, p0.n_in, p0.n_out, p0.n_in_vf
-        self.has_critic, self.split = p0.has_critic, p0.split
-        hs = (C.c_void_p * P)(*[m._h.value for m in members])
-        os_ = None if optimizers is None else (C.c_void_p * P)(*[o._h.value for o in self.optimizers])
-        h = C.c_void_p()
-        _chk(self.L.wg_pop_create(hs, os_, P, C.byref(h)), "wg_pop_create")
-        self._h = h
+        self.desc, self.n_in, self.n_out = p0.desc, p0.n_in, p0.n_out
+        self._h = self._create(lambda hs: (C.c_void_p * P)(*[h.value for h in hs]))
         self._out = {}
 
     population = property(lambda self: self)      # (what venv.rollout looks for)
 
     def close(self):
         if getattr(self, "_h", None):
-            self.L.wg_pop_destroy(self._h)
+            getattr(self.L, self.destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -96,6 +106,29 @@ class Population:
         v = broadcast_hyper("seed / row_offset", default if x is None else x, P)
         return (C.c_uint64 * P)(*[int(i) for i in v])
 
+    def _seeds(self, seed):                       # (default: the members' own)
+        return self._u64(seed, [m.seed for m in self.members])
+
+    def _offsets(self, row_offset, Bm):           # (a scalar: the global row of member 0's first row)
+        if not isinstance(row_offset, (list, tuple, np.ndarray)):
+            row_offset = [int(row_offset) + m * Bm for m in range(self.n_members)]
+        return self._u64(row_offset, 0)
+
+
+class Population(PopulationBase):
+    """``P`` :class:`MlpPolicy` objects of one architecture behind one ``wg_pop`` handle: ``act`` / ``value`` are ONE launch of
+    the policy kernel for all members, member ``m`` on rows ``[m * Bm, (m + 1) * Bm)``; ``venv.rollout(pop, T)`` is wg_pop_rollout.
+    ``optimizers``: the members' :class:`PPOOptimizer` objects (needed by wg_pop_update only)."""
+
+    destroy = "wg_pop_destroy"
+
+    def _create(self, arr):
+        p0, h = self.members[0], C.c_void_p()
+        self.n_in_vf, self.has_critic, self.split = p0.n_in_vf, p0.has_critic, p0.split
+        self._chk(self.L.wg_pop_create(arr([m._h for m in self.members]), None if self.optimizers is None else arr([o._h for o in self.optimizers]),
+                                       self.n_members, C.byref(h)), "wg_pop_create")
+        return h
+
     def act(self, obs, deterministic=False, counter=0, *, seed=None, row_offset=0, value=True, out=None):
         """wg_pop_act on a contiguous float32 CUDA tensor ``[..., n_in]`` whose rows divide evenly among the members ->
         ``(action, raw, logp, value)`` as :meth:`MlpPolicy.act`.  ``seed``: one per member (or a scalar for all; default: the
@@ -109,9 +142,8 @@ class Population:
         a, r, lp, v = out if out is not None else act_buffers(self, n)
         want_v = value and self.has_critic
         ls = self.desc["has_log_std"]
-        offs = row_offset if isinstance(row_offset, (list, tuple, np.ndarray)) else [int(row_offset) + m * Bm for m in range(self.n_members)]
-        self._chk(self.L.wg_pop_act(self._h, n, obs.data_ptr(), int(bool(deterministic)), self._u64(seed, [m.seed for m in self.members]),
-                                    int(counter), self._u64(offs, 0), a.data_ptr(), r.data_ptr(), lp.data_ptr() if ls else None,
+        self._chk(self.L.wg_pop_act(self._h, n, obs.data_ptr(), int(bool(deterministic)), self._seeds(seed),
+                                    int(counter), self._offsets(row_offset, Bm), a.data_ptr(), r.data_ptr(), lp.data_ptr() if ls else None,
                                     v.data_ptr() if want_v else None, self._stream()), "wg_pop_act")
         return a, r, (lp if ls else None), (v if want_v else None)
 
@@ -145,7 +177,8 @@ class PPOPopulation:
     records no powers).  ``members[m]`` is an ordinary policy; ``save(dir)`` writes ``member_00.zip`` ...: plain ``PPO`` zips
     (``PPO.load(zip, shard venv)`` resumes a member alone)."""
 
-    # what recurrent_population.RecurrentPPOPopulation states differently: the policy class by name, and the four hooks below
+    # what recurrent_population.RecurrentPPOPopulation states differently: the policy class by name, and the seven hooks
+    # _check_policy, _minibatches, _build_member, _open (below), _global, _batch and _tensors (next to train and save)
     policy_name = "MlpPolicy"
 
     def _check_policy(self, policy):
@@ -243,24 +276,35 @@ class PPOPopulation:
         out["advantage"], out["returns"] = self._adv, self._ret
         return out
 
+    def _global(self, local, m):                  # member m's permutation of its own rows -> the batch's row ids
+        return global_rows(local, m, self.n_envs, self.n_envs_member)
+
+    def _batch(self, out):
+        """-> (the batch struct of a collected rollout, the update entry that takes it, the entry's minibatch size)."""
+        from .binding import CPpoBatch
+        T = self.n_steps
+        return CPpoBatch(out["obs"][:T].data_ptr(), out["raw"].data_ptr(), out["logp"].data_ptr(), self._adv.data_ptr(),
+                         self._ret.data_ptr(), T * self.n_envs), "wg_pop_update", self.batch_size
+
+    def _tensors(self, m):                        # what member m's checkpoint holds besides a PPO zip's entries
+        return None
+
     def train(self, out, learning_rate, clip_range):
-        """Every member's ``PPO.train`` on its columns of a collected rollout: the members' permutations (drawn as ``PPO`` draws
-        them on ``n_steps * Bm`` rows, mapped to the batch's rows by :func:`global_rows`), then ONE wg_pop_update."""
-        from .binding import CPpoBatch, CPpoHyper
+        """Every member's ``train`` on its columns of a collected rollout: the members' permutations (drawn as the single trainer
+        draws them on its shard, mapped to the batch's ids by :meth:`_global`), then ONE update entry."""
+        from .binding import CPpoHyper
         t, pop, P = self.torch, self.population, self.n_members
         for m in range(P):
             for e in range(self.n_epochs):
-                local = t.randperm(self.n_rows, generator=self._gens[m], device=pop.device)
-                self._perm[m, e].copy_(global_rows(local, m, self.n_envs, self.n_envs_member))
-        T, O, N = self.n_steps, pop.n_in, pop.n_out
-        b = CPpoBatch(out["obs"][:T].data_ptr(), out["raw"].data_ptr(), out["logp"].data_ptr(), self._adv.data_ptr(),
-                      self._ret.data_ptr(), T * self.n_envs)
+                local = t.randperm(self._perm.shape[2], generator=self._gens[m], device=pop.device)
+                self._perm[m, e].copy_(self._global(local, m))
+        b, entry, minibatch = self._batch(out)
         hp = (CPpoHyper * P)(*[CPpoHyper(float(clip_range[m]), float(self.vf_coef[m]), float(self.ent_coef[m]),
                                          int(bool(self.normalize_advantage[m]))) for m in range(P)])
         params = (C.c_void_p * P)(*[p.params.data_ptr() for p in self.members])
-        pop._chk(pop.L.wg_pop_update(pop._h, params, C.byref(b), self._perm.data_ptr(), self.n_epochs, self.batch_size, hp,
-                                     self._floats(learning_rate), self._floats(self.max_grad_norm), self._stats.data_ptr(),
-                                     pop._stream()), "wg_pop_update")
+        pop._chk(getattr(pop.L, entry)(pop._h, params, C.byref(b), self._perm.data_ptr(), self.n_epochs, minibatch, hp,
+                                       self._floats(learning_rate), self._floats(self.max_grad_norm), self._stats.data_ptr(),
+                                       pop._stream()), entry)
         return self._stats
 
     def _member_metrics(self, out):
@@ -310,11 +354,11 @@ class PPOPopulation:
         return d
 
     def save(self, directory):
-        """``directory/member_00.zip`` ...: each a plain ``PPO`` checkpoint (see :meth:`PPO.save`) of the member's run on its shard."""
+        """``directory/member_00.zip`` ...: each the single trainer's checkpoint (see :meth:`PPO.save`) of the member's run on its shard."""
         os.makedirs(directory, exist_ok=True)
         return [write_checkpoint(os.path.join(directory, f"member_{m:02d}.zip"), self.members[m], self.opts[m], self._gens[m],
                                  self.member_hyper(m), self.seed[m], self.num_timesteps, self.iteration, [recs[m] for recs in self.log],
-                                 None, self.venv._policy_steps) for m in range(self.n_members)]
+                                 None, self.venv._policy_steps, tensors=self._tensors(m)) for m in range(self.n_members)]
 
     def close(self):
         self.population.close()

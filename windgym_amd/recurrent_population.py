@@ -18,11 +18,9 @@ architecture or ``n_steps``, ``sample_site``.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 from .policy import act_buffers, device_tensor
-from .population import POP_MAX, PPOPopulation, broadcast_hyper, check_population_shape
-from .ppo import write_checkpoint
+from .population import PopulationBase, PPOPopulation, check_members, check_population_shape
 from .recurrent_ppo import RecurrentPPO, RecurrentPPOOptimizer, envs_per_minibatch
 
 
@@ -42,21 +40,17 @@ def member_minibatch(batch_size, n_steps, n_envs, n_members):
 
 def check_same_architecture(members):
     """``ValueError`` naming the member for what wg_lstm_pop_create would refuse of the policies' shapes."""
-    members = list(members)
-    if not 1 <= len(members) <= POP_MAX:
-        raise ValueError(f"a population has 1 .. {POP_MAX} members, not {len(members)}")
+    members = check_members(members)
     for m, p in enumerate(members):
         if not getattr(p, "recurrent", False):
             raise ValueError(f"member {m} is not a recurrent policy (MlpLstmPolicy): population.Population takes MlpPolicy objects")
         if p.desc != members[0].desc:
             raise ValueError(f"member {m} has another architecture than member 0 (n_in, lstm_hidden_size, shared_lstm, the heads and the "
                              "activation must agree): the members of a population share one")
-        if any(p is q for q in members[:m]):
-            raise ValueError(f"member {m} is the same policy as an earlier member")
     return members
 
 
-class RecurrentPopulation:
+class RecurrentPopulation(PopulationBase):
     """``P`` :class:`MlpLstmPolicy` objects of one architecture behind one ``wg_lstm_pop`` handle: ``act`` is ONE launch of the LSTM
     kernel and ONE of the policy kernel for all members, member ``m`` on rows ``[m * Bm, (m + 1) * Bm)`` with the state ``state[m]``;
     ``venv.rollout(pop, T)`` is wg_lstm_pop_rollout.  ``optimizers``: the members' :class:`RecurrentPPOOptimizer` objects (needed by
@@ -65,41 +59,15 @@ class RecurrentPopulation:
     recurrent = True
     split = False
     has_critic = True
+    check, destroy = staticmethod(check_same_architecture), "wg_lstm_pop_destroy"
 
-    def __init__(self, members, optimizers=None):
-        from .binding import _chk
-        members = check_same_architecture(members)
-        p0 = members[0]
-        self.members, self.optimizers = members, None if optimizers is None else list(optimizers)
-        self.L, self._chk, self.torch, self.device = p0.L, _chk, p0.torch, p0.device
-        self.n_members = P = len(members)
-        self.desc, self.n_in, self.n_out, self.H, self.nets = p0.desc, p0.n_in, p0.n_out, p0.H, p0.nets
-        arr = lambda hs: (C.c_void_p * P)(*[h.value for h in hs])        # noqa: E731
-        h = C.c_void_p()
-        _chk(self.L.wg_lstm_pop_create(arr([m._lstm for m in members]), arr([m.mlp._h for m in members]),
-                                       None if optimizers is None else arr([o._h for o in self.optimizers]), P, C.byref(h)),
-             "wg_lstm_pop_create")
-        self._h = h
-        self._out, self._hbuf = {}, {}
-
-    population = property(lambda self: self)      # (what venv.rollout looks for)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_lstm_pop_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _u64(self, x):
-        return (C.c_uint64 * self.n_members)(*[int(i) for i in broadcast_hyper("seed / row_offset", x, self.n_members)])
+    def _create(self, arr):
+        ms, h = self.members, C.c_void_p()
+        self.H, self.nets, self._hbuf = ms[0].H, ms[0].nets, {}
+        self._chk(self.L.wg_lstm_pop_create(arr([m._lstm for m in ms]), arr([m.mlp._h for m in ms]),
+                                            None if self.optimizers is None else arr([o._h for o in self.optimizers]), self.n_members,
+                                            C.byref(h)), "wg_lstm_pop_create")
+        return h
 
     def initial_state(self, n):
         """The zero state of ``n`` rows shared out among the members: float32 CUDA ``[P, nets, 2, n / P, H]``."""
@@ -129,10 +97,9 @@ class RecurrentPopulation:
         hbuf = self._hbuf.get(n)
         if hbuf is None:
             hbuf = self._hbuf[n] = t.zeros((2, n, self.H), dtype=t.float32, device=self.device)
-        offs = row_offset if isinstance(row_offset, (list, tuple)) else [int(row_offset) + m * Bm for m in range(P)]
         self._chk(self.L.wg_lstm_pop_act(self._h, n, obs.data_ptr(), None if episode_start is None else episode_start.data_ptr(),
                                          state.data_ptr(), state_out.data_ptr(), hbuf.data_ptr(), int(bool(deterministic)),
-                                         self._u64([m.seed for m in self.members] if seed is None else seed), int(counter), self._u64(offs),
+                                         self._seeds(seed), int(counter), self._offsets(row_offset, Bm),
                                          a.data_ptr(), r.data_ptr(), lp.data_ptr(), v.data_ptr() if value else None, self._stream()),
                   "wg_lstm_pop_act")
         return (a, r, lp, (v if value else None)), state_out
@@ -149,7 +116,9 @@ class RecurrentPPOPopulation(PPOPopulation):
     set of envs with all their steps) and defaults to ``n_steps * ceil(Bm / 4)``.  Per epoch and member one permutation of the member's
     ``Bm`` envs is drawn from the member's generator and mapped to the batch's env ids (:func:`global_envs`).
 
-    ``learn``, ``log`` and ``members`` are ``PPOPopulation``'s.  ``save(dir)`` writes ``member_00.zip`` ...: each a ``RecurrentPPO``
+    ``learn``, ``train``, ``log`` and ``members`` are ``PPOPopulation``'s; stated here are its seven hooks: ``_check_policy``,
+    ``_minibatches``, ``_build_member``, ``_open``, ``_global`` (one permutation of the member's ``Bm`` envs per epoch), ``_batch``
+    (wg_lstm_pop_update on a ``CLstmPpoBatch``) and ``_tensors``.  ``save(dir)`` writes ``member_00.zip`` ...: each a ``RecurrentPPO``
     checkpoint with the member's slice of the LSTM state and of the pending episode starts (``RecurrentPPO.load(zip, shard venv)``
     resumes that member alone, bit-identically).  Refused by name: a curriculum, ``normalize``, a ``WindFarmVecEnvMulti``,
     non-recurrent members (``PPOPopulation`` trains those)."""
@@ -172,33 +141,15 @@ class RecurrentPPOPopulation(PPOPopulation):
         self.opts = [RecurrentPPOOptimizer(p, self.n_steps, self.envs_per_batch) for p in members]
         self.population = RecurrentPopulation(members, self.opts)
 
-    def train(self, out, learning_rate, clip_range):
-        """Every member's ``RecurrentPPO.train`` on its columns of a collected rollout: the members' permutations of their envs, then
-        ONE wg_lstm_pop_update."""
-        from .binding import CLstmPpoBatch, CPpoHyper
-        t, pop, P = self.torch, self.population, self.n_members
-        for m in range(P):
-            for e in range(self.n_epochs):
-                local = t.randperm(self.n_envs_member, generator=self._gens[m], device=pop.device)
-                self._perm[m, e].copy_(global_envs(local, m, self.n_envs_member))
-        b = CLstmPpoBatch(out["obs"].data_ptr(), out["raw"].data_ptr(), out["logp"].data_ptr(), self._adv.data_ptr(), self._ret.data_ptr(),
-                          out["episode_start"].data_ptr(), out["lstm_state0"].data_ptr(), self.n_steps, self.n_envs)
-        hp = (CPpoHyper * P)(*[CPpoHyper(float(clip_range[m]), float(self.vf_coef[m]), float(self.ent_coef[m]),
-                                         int(bool(self.normalize_advantage[m]))) for m in range(P)])
-        params = (C.c_void_p * P)(*[p.params.data_ptr() for p in self.members])
-        pop._chk(pop.L.wg_lstm_pop_update(pop._h, params, C.byref(b), self._perm.data_ptr(), self.n_epochs, self.envs_per_batch, hp,
-                                          self._floats(learning_rate), self._floats(self.max_grad_norm), self._stats.data_ptr(),
-                                          pop._stream()), "wg_lstm_pop_update")
-        return self._stats
+    def _global(self, local, m):
+        return global_envs(local, m, self.n_envs_member)
 
-    def save(self, directory):
-        """``directory/member_00.zip`` ...: each a ``RecurrentPPO`` checkpoint (see :meth:`RecurrentPPO.save`) of the member's run on its
-        shard, with ``state[m]`` and the member's pending episode starts."""
-        os.makedirs(directory, exist_ok=True)
-        Bm = self.n_envs_member
-        ent = self.venv._lstm_pair(self.population)
-        return [write_checkpoint(os.path.join(directory, f"member_{m:02d}.zip"), self.members[m], self.opts[m], self._gens[m],
-                                 self.member_hyper(m), self.seed[m], self.num_timesteps, self.iteration, [recs[m] for recs in self.log],
-                                 None, self.venv._policy_steps,
-                                 tensors={"lstm_state.npy": ent[1][m], "episode_start.npy": ent[2][m * Bm:(m + 1) * Bm]})
-                for m in range(self.n_members)]
+    def _batch(self, out):
+        from .binding import CLstmPpoBatch
+        return CLstmPpoBatch(out["obs"].data_ptr(), out["raw"].data_ptr(), out["logp"].data_ptr(), self._adv.data_ptr(), self._ret.data_ptr(),
+                             out["episode_start"].data_ptr(), out["lstm_state0"].data_ptr(), self.n_steps,
+                             self.n_envs), "wg_lstm_pop_update", self.envs_per_batch
+
+    def _tensors(self, m):                        # state[m] and the member's pending episode starts
+        Bm, ent = self.n_envs_member, self.venv._lstm_pair(self.population)
+        return {"lstm_state.npy": ent[1][m], "episode_start.npy": ent[2][m * Bm:(m + 1) * Bm]}
