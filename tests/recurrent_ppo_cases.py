@@ -11,8 +11,8 @@ import functools
 import numpy as np
 import torch
 
-from tests import lstm_bptt_twin as tw
-from tests.rl_helpers import DEEP
+import lstm_bptt_twin as tw
+from rl_helpers import DEEP
 
 KW = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=True)
 EXTRA = 5                                    # envs of an ARCH_CASES rollout that are in no minibatch

@@ -6,12 +6,11 @@ import copy
 
 import numpy as np
 
+from helpers import OBS_ATOL  # noqa: F401  (the step outputs' bar against the CPU oracle)
 from oracle import policy_oracle as po
 from windgym_amd.policy import pack_params
 
 
-# bars of the step outputs against the CPU oracle
-OBS_ATOL = 2e-4
 # Frozen-box inflow (cfg5), with the worst error observed on an MI355X over the 16 sampled envs x 300 steps of the two cfg5 tests of
 # test_gpu_spotcheck.py (small box / reference box) next to each bar; every bar was 30 to 70 times its worst case and is now 3.5 to 5
 # times it:
@@ -59,6 +58,13 @@ def close(a, b, tol=2e-5, rel=0.0):
 def dev(*arrays):
     t = _torch()
     return [t.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+def close_all(*xs):
+    """close() of every handle given, singly or in lists"""
+    for x in xs:
+        for y in (x if isinstance(x, (list, tuple)) else [x]):
+            y.close()
 
 
 def flat_grad(desc, grads):
@@ -246,3 +252,40 @@ def rollout_equals_the_loop(va, vb, p, T, rec=("power_agent", "yaw_agent"), out=
     for x, y in zip(va.step(act), vb.step(act)):
         assert not t.is_tensor(x) or t.equal(x, y)               # (a WindFarmVecEnv's fifth element is its lazy info dict)
     return out
+
+
+# ---- populations (test_gpu_population.py, test_gpu_recurrent_population.py) -----------------------------------------------------------
+def pop_hyper(P):
+    """a different value of every hyper-parameter for each of up to four members"""
+    return dict(gamma=[0.99, 0.9, 0.95, 0.97][:P], gae_lambda=[0.95, 0.9, 1.0, 0.8][:P], ent_coef=[0.0, 0.01, 0.003, 0.0][:P],
+                vf_coef=[0.5, 0.7, 0.4, 0.5][:P], max_grad_norm=[0.5, 0.05, 10.0, 0.5][:P], learning_rate=[3e-4, 1e-3, 0.0, 2e-3][:P],
+                clip_range=[0.2, 0.1, 0.3, 0.2][:P], normalize_advantage=[True, False, True, True][:P])
+
+
+def mlp_members(P, n_in=32, hidden=(64, 64), n_out=16, seed0=3):
+    return [make(n_in, hidden, n_out, seed=seed0 + 7 * m, dtype=np.float64)[0] for m in range(P)]
+
+
+def lstm_members(P, n_in=7, n_out=2, hidden=40, shared=False, heads=(16,), seed0=3):
+    from windgym_amd.recurrent import MlpLstmPolicy
+    return [MlpLstmPolicy(n_in, n_out, hidden, heads, heads, shared_lstm=shared, seed=seed0 + 7 * m) for m in range(P)]
+
+
+# ---- recurrent policies against tests/lstm_bptt_twin.py ---------------------------------------------------------------------------------
+def lstm_policy(spec, flat):
+    """the device policy of a twin's spec with the twin's flat parameters; the two flat layouts are the same, tensor by tensor"""
+    import lstm_bptt_twin as tw
+    from windgym_amd.recurrent import MlpLstmPolicy, param_layout
+    t = _torch()
+    p = MlpLstmPolicy(spec["n_in"], spec["n_out"], spec["H"], spec["hidden_pi"], spec["hidden_vf"], spec["shared"], spec["activation"])
+    assert [(k, tuple(s)) for k, s in param_layout(p.desc)] == [(k, tuple(s)) for k, s in tw.layout(spec)]
+    with t.no_grad():
+        p.params.copy_(t.from_numpy(np.asarray(flat, np.float32)))
+    p.sync()
+    return p
+
+
+def dev_roll(roll):
+    """a twin's rollout (tw.random_rollout) as the device tensors wg_lstm_ppo_grad / _update take"""
+    keys = ("obs", "raw", "logp", "advantage", "returns", "episode_start", "lstm_state0")
+    return dict(zip(keys, dev(*[roll[k] for k in keys])))

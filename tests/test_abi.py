@@ -3,10 +3,10 @@ include/windgym_hip.h declares; the ctypes mirror of wg_config matches the C lay
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+from helpers import c_layout
 from windgym_amd import binding, build
 from windgym_amd.config import CConfig
 
@@ -40,17 +40,11 @@ def test_every_bound_symbol_is_defined_by_a_listed_source():
 
 def test_config_struct_layout_matches_c(tmp_path):
     """sizeof/offsetof of wg_config as gcc sees it == the ctypes mirror."""
-    src = tmp_path / "l.c"
     fields = [f[0] for f in CConfig._fields_]
-    body = "\n".join(f'printf("{f} %zu\\n", offsetof(wg_config, {f}));' for f in fields)
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/windgym_hip.h"\n'
-                   f'int main(){{ printf("sizeof %zu\\n", sizeof(wg_config));\n{body}\nreturn 0; }}')
-    exe = tmp_path / "l"
-    subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(CConfig)
+    out = c_layout("wg_config", fields, tmp_path)
+    assert out["sizeof"] == C.sizeof(CConfig)
     for f in fields:
-        assert int(out[f]) == getattr(CConfig, f).offset, f
+        assert out[f] == getattr(CConfig, f).offset, f
 
 
 def test_no_cpu_fallback_without_gpu():

@@ -83,21 +83,15 @@ HIP_CASES = [(t, b) for t in ("MannFixed", "Random") for b in (64, 256)] + [("Ma
 @pytest.mark.gpu
 @pytest.mark.parametrize("turbtype,block", HIP_CASES)
 def test_hip_matches_oracle_with_added_turbulence(turbtype, block, small_box):
-    import os
     import torch
+    from helpers import make_batch
     from windgym_amd import binding
     cfg = _cfg(turbtype, "iso", n_envs=3)
     envk = isinstance(block, str)
     hooks = {"WG_FLOW_BLOCK": "64" if envk else str(block), "WG_FLOW_ENV": "1" if envk else "0"}
     if envk:
         hooks["WG_ENV_WPE"] = block[-1] if block[-1] in "14" else "2"
-    os.environ.update(hooks)
-    try:
-        env = binding.HipBatch(cfg)
-    finally:
-        for k in hooks:
-            del os.environ[k]
-    assert env.flow_variant()[0] == (64 if envk else block) and env.flow_variant()[2] == (2 if envk else 0)
+    env = make_batch(binding, cfg, hooks, variant=(64 if envk else block, None, 2 if envk else 0))
     o = om.Oracle(cfg)
     if turbtype != "Random":
         env.set_turbulence_box(*small_box)

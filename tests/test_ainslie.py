@@ -117,33 +117,23 @@ def test_ainslie_wake_is_deeper_and_narrower_than_the_gaussian_at_low_ti(oracle_
 
 @pytest.mark.gpu
 def test_uniform_ring_variant_refuses_the_option():
-    import os
     from windgym_amd import binding
-    os.environ["WG_FLOW_BLOCK"] = "256"              # uniform rings / sample-major phases
-    try:
+    with binding.debug_hooks({"WG_FLOW_BLOCK": "256"}):              # uniform rings / sample-major phases
         with pytest.raises(NotImplementedError):
             binding.HipBatch(_cfg(n_envs=2, nx=3, ny=3))
-    finally:
-        del os.environ["WG_FLOW_BLOCK"]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("block,turbtype", [(64, "None"), (256, "None"), (64, "MannFixed"), (64, "Random")])
 def test_hip_matches_oracle_ainslie(block, turbtype, oracle_lib):
-    import os
     import torch
+    from helpers import make_batch
     from windgym_amd import binding
     from windgym_amd.mann import generate_mann_box
     nxy = 6 if block == 256 else 3                   # 36 turbines: the compact variant at 256 threads (large steady farms)
     cfg = _cfg(n_envs=3, turbtype=turbtype, nx=nxy, ny=nxy, ws=10.0, ti=0.08)
     cfg.wd_min, cfg.wd_max = 255.0, 285.0
-    if block != 256:
-        os.environ["WG_FLOW_BLOCK"] = str(block)
-    try:
-        env = binding.HipBatch(cfg)
-    finally:
-        os.environ.pop("WG_FLOW_BLOCK", None)
-    assert env.flow_variant() == (block, True, False)
+    env = make_batch(binding, cfg, {"WG_FLOW_BLOCK": str(block)} if block != 256 else None, variant=(block, True, 0))
     o = oracle_lib.Oracle(cfg)
     if turbtype == "MannFixed":
         box = generate_mann_box((256, 64, 32), (3.0, 3.0, 3.0), seed=9)

@@ -3,18 +3,15 @@ checkpoint reader, the ctypes mirror of wg_ppo_batch_shared, and the float64 ref
 themselves (oracle/ppo_oracle.py: the shared forms against finite differences and against the plain ones, which call them)."""
 import ctypes as C
 import io
-import os
-import subprocess
 import zipfile
 
 import numpy as np
 import pytest
 
+from helpers import c_layout
 from oracle import ppo_oracle as oo
 from windgym_amd import binding
 from windgym_amd.policy import critic_width, make_desc, n_params, pack_params, param_layout, read_sb3_zip, unpack_params
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _random_tensors(desc, seed=0):
@@ -83,17 +80,11 @@ def test_shared_batch_struct_and_symbols_match_the_header(tmp_path):
     for name in ("wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared"):
         assert name in binding.ABI_SYMBOLS
     fields = {"rows": "rows", "rows.n_rows": None, "obs_vf": "obs_vf", "agents": "agents"}
-    body = "\n".join(f'printf("{f} %zu\\n", offsetof(wg_ppo_batch_shared, {f}));' for f in fields)
-    src = tmp_path / "l.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/windgym_hip.h"\n'
-                   f'int main(){{ printf("sizeof %zu\\n", sizeof(wg_ppo_batch_shared));\n{body}\nreturn 0; }}')
-    exe = tmp_path / "l"
-    subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    out = c_layout("wg_ppo_batch_shared", fields, tmp_path)
     S = binding.CPpoBatchShared
-    assert int(out["sizeof"]) == C.sizeof(S)
-    assert int(out["rows"]) == S.rows.offset and int(out["obs_vf"]) == S.obs_vf.offset and int(out["agents"]) == S.agents.offset
-    assert int(out["rows.n_rows"]) == S.rows.offset + binding.CPpoBatch.n_rows.offset
+    assert out["sizeof"] == C.sizeof(S)
+    assert out["rows"] == S.rows.offset and out["obs_vf"] == S.obs_vf.offset and out["agents"] == S.agents.offset
+    assert out["rows.n_rows"] == S.rows.offset + binding.CPpoBatch.n_rows.offset
 
 
 # ----------------------------------------------------------------------------------------------------------------------

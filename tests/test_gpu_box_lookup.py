@@ -12,13 +12,12 @@ which must also agree bit for bit), the block-averaged meandering copy, the wake
 The big boxes are views of ONE buffer of 3 x 2^28 clipped unit normals drawn on the device (3.2 GB) and copied to the host once
 (3.2 GB, the oracle reads it in place): module-scoped, freed when the module ends.
 """
-import os
-
 import numpy as np
 import pytest
 
 import box_reference as br
-from test_gpu_parity import BLOCKS, _make_env, _turb_cfg
+from helpers import BLOCKS, hip, make_env, turb_cfg  # noqa: F401  (hip: the fixture)
+from windgym_amd.binding import debug_hooks
 
 pytestmark = pytest.mark.gpu
 
@@ -37,15 +36,6 @@ BARS = dict(
 # number (|reward| <= 1, |u| <= 20 m/s): failing these is failing those.  Worst observed on that box with the right cells: obs 9.2e-5,
 # reward 1.8e-5, rotor wind 1.73e-3 m/s, power 0.09 of its bar — the rotor-wind bar has no room to tighten there.
 MANN_BARS_IN_USE = dict(obs=5e-4, rew=2e-3, uvw=6e-3, pow_rtol=5e-3, pow_atol=2000.0)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
 
 
 @pytest.fixture(scope="module")
@@ -154,18 +144,11 @@ def _envb_pair(hip, cfg, block, capfd, set_boxes):
     the boxes.  The WG_DEBUG line of build_stencil_records is the witness of which one was built."""
     envs = []
     for no8 in (False, True):
-        os.environ["WG_DEBUG"] = "1"                  # (read at wg_create)
-        try:
-            env = _make_env(hip, cfg, block)
-        finally:
-            del os.environ["WG_DEBUG"]
+        with debug_hooks({"WG_DEBUG": "1"}):                                # (read at wg_create)
+            env = make_env(hip, cfg, block)
         capfd.readouterr()
-        if no8:
-            os.environ["WG_NO_BOX8"] = "1"            # (read by the box setters)
-        try:
+        with debug_hooks({"WG_NO_BOX8": "1"} if no8 else {}):               # (read by the box setters)
             set_boxes(env)
-        finally:
-            os.environ.pop("WG_NO_BOX8", None)
         err = capfd.readouterr().err
         if no8:
             assert err.count("stencil records not built (WG_NO_BOX8)") == 2, err          # fine box and wake-added box
@@ -215,7 +198,7 @@ def test_flow_view_matches_float64_reference_on_white_noise(hip, noise, shape, s
     at negative coordinates and more than ten box lengths away; after the reset and after 300 steps.  Env 0 runs at U = 8 m/s exactly,
     so that its "nodes" are nodes; env 1 at its sampled wind."""
     import torch
-    cfg = _turb_cfg("MannFixed", 2, nx=2, ny=1)
+    cfg = turb_cfg("MannFixed", 2, nx=2, ny=1)
     env = hip.HipBatch(cfg)
     box = _box(noise, shape)
     _set_box(env, None, box, spacing)
@@ -250,7 +233,7 @@ STEPS = 120
 
 
 def _cfg5_shape(turbtype, B):
-    cfg = _turb_cfg(turbtype, B, nx=4, ny=4)
+    cfg = turb_cfg(turbtype, B, nx=4, ny=4)
     assert cfg.n_turb * cfg.n_particles == 2048          # the farm shape bench.py --workload cfg5 runs
     return cfg
 
@@ -263,7 +246,7 @@ def test_rotor_winds_per_slot_kernels_bricks_match_float64_oracle(hip, oracle_li
     shape, spacing, turbtype = BIG[cells]
     B = 5
     cfg = _cfg5_shape(turbtype, B)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     _set_box(env, orc, _box(noise, shape), spacing)
     ab = _added(3)
     env.set_added_turbulence_box(*ab), orc.set_added_turbulence_box(*ab)
@@ -313,7 +296,7 @@ def test_meandering_copy_whose_dims_are_no_powers_of_two_matches_float64_oracle(
     shape, spacing = (2040, 516, 60), (3.0, 3.0, 3.0)
     B = 5
     cfg = _cfg5_shape("MannGenerate", B)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     _set_box(env, orc, _box(noise, shape), spacing)
     ab = _added(3)
     env.set_added_turbulence_box(*ab), orc.set_added_turbulence_box(*ab)
@@ -334,7 +317,7 @@ def test_wake_added_box_larger_than_the_default_matches_float64_oracle(hip, orac
     kernel, abox8 records and the plain / brick-ordered abox4 of k_flow_envb; the added share is first order in the looked-up value"""
     shape, spacing = (256, 64, 32), (3.0, 3.0, 3.0)
     B = 6
-    cfg = _turb_cfg("MannGenerate", B)
+    cfg = turb_cfg("MannGenerate", B)
     box = br.white_noise_box(shape, 8, clip=CLIP)
     ab = _added(9, ashape)
 
@@ -342,7 +325,7 @@ def test_wake_added_box_larger_than_the_default_matches_float64_oracle(hip, orac
         env.set_turbulence_box(box, spacing)
         env.set_added_turbulence_box(*ab)
 
-    slot = _make_env(hip, cfg, 64)
+    slot = make_env(hip, cfg, 64)
     set_boxes(slot)
     envs = _envb_pair(hip, cfg, "envb", capfd, set_boxes)
     ws = []
@@ -381,7 +364,7 @@ def test_pool_of_two_boxes_of_2_26_cells_pinned_to_box_1_matches_reference_and_f
         env.set_added_turbulence_box(*ab)
         env.set_box_ids(1)
 
-    slot = _make_env(hip, cfg, 64)
+    slot = make_env(hip, cfg, 64)
     set_boxes(slot)
     envs = _envb_pair(hip, cfg, "envb4", capfd, set_boxes)
     seeds = 830 + np.arange(B)
@@ -480,7 +463,7 @@ def test_negative_control_oracle_box_rolled_by_one_cell_fails_every_bar(hip, ora
     box = br.white_noise_box(shape, 8, clip=CLIP) if field == "white-noise" else generate_mann_box(shape, spacing, seed=1234)
     rolled = np.ascontiguousarray(np.roll(box, 1, axis={"x": 1, "z": 3}[axis]))
     B = 5
-    cfg = _turb_cfg("MannFixed", B)
+    cfg = turb_cfg("MannFixed", B)
     ab = _added(3)
     env = hip.HipBatch(cfg)
     env.set_turbulence_box(box, spacing), env.set_added_turbulence_box(*ab)

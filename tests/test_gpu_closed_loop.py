@@ -20,12 +20,12 @@ import copy
 import functools
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import rl_helpers
+from helpers import host_shim
 from oracle import policy_oracle as po
 from oracle import ppo_oracle as oo
 from rl_helpers import (LOGP_ATOL, N_SAMPLE, OBS_ATOL, RAW_ATOL, SMALL_BOX, SMALL_BOX_SPACING, TURB_OBS_ATOL, TURB_POW_ATOL, TURB_POW_RTOL,
@@ -79,10 +79,7 @@ CASES = ["cfg2_4096", "cfg2_1024", "cfg2_389", "cfg3_512", "cfg5_1024", "random_
 def plan_of(tmp_path_factory):
     """cfg, box cells -> the plan wg_create makes for it, as a dict of ints (tests/plan_shim.cpp; g++ alone)."""
     from windgym_amd.config import CConfig
-    so = tmp_path_factory.mktemp("plan") / "plan_shim.so"
-    subprocess.run(["g++", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "windgym_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "plan_shim.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = host_shim(tmp_path_factory, "plan", include_header_dir=True)
     lib.plan_dump.argtypes = [C.POINTER(CConfig), C.POINTER(C.c_int), C.c_int, C.c_longlong, C.c_longlong, C.c_char_p, C.c_int]
 
     def plan(cfg, box_cells=0):

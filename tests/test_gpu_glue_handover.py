@@ -9,26 +9,16 @@ where there is one, every step, and the whole state blob at the end.
 twice (asserted), so each run crosses truncating steps (barrier kept, swap), the deferred episode set-up, the first-observation
 launch of a completed background episode and the clone of a parked baseline farm — the paths that keep their own barriers —
 between stretches of ordinary steps, the path that lost its barrier."""
-import os
-
 import numpy as np
 import pytest
 
+from helpers import hip, make_batch  # noqa: F401  (hip: the fixture)
 from variant_census import AllChannelNoiseConfig, _yaml
 
 pytestmark = pytest.mark.gpu
 
 B, STEPS = 6, 150
 WPE_HOOKS = {"wpe1": {"WG_ENV_WPE": "1"}, "wpe2": {"WG_ENV_WPE": "2", "WG_ENV_SPLIT": "0"}}
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
 
 
 def _cfg(case):
@@ -62,15 +52,7 @@ def _run(hip, case, wpe, fused, acts=None):
     """150 steps of one handle -> per step (obs, reward, truncated, final_obs[, per-agent buffer]) as numpy arrays, state blob"""
     cfg, multi = _cfg(case)
     hooks = {"WG_FLOW_ENV": "1", "WG_STEP_FUSED": "1" if fused else "0", **WPE_HOOKS[wpe]}
-    os.environ.update(hooks)
-    try:
-        env = hip.HipBatch(cfg)
-    finally:
-        for k in hooks:
-            del os.environ[k]
-    assert env.flow_variant()[2] == 2               # an env kernel, not the per-slot one
-    if multi:
-        env.fuse_obs_multi()
+    env = make_batch(hip, cfg, hooks, variant=(None, None, 2), multi=multi)      # an env kernel, not the per-slot one
     acts = (_actions(cfg) if acts is None else acts).cuda()
     out = [[env.reset(seeds=3100 + np.arange(B)).cpu().numpy().copy()]]
     for s in range(STEPS):

@@ -8,54 +8,17 @@ yaw |d| <= 1e-4 deg, rotor wind speed rel 1e-4, power rel 2e-4 (+20 W).
 import numpy as np
 import pytest
 
-from helpers import config_from_meta, golden_cases, load_golden, script_tables
+from helpers import (BLOCKS, OBS_ATOL, config_from_meta, golden_cases, hip, load_golden, make_batch, make_env, physics_cfg,  # noqa: F401  (hip: the fixture)
+                     script_tables, turb_cfg)
 
 pytestmark = pytest.mark.gpu
 
-OBS_ATOL = 2e-4
 
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
-
-
-# every k_flow variant the host can select for a small farm (wg_flow.hip's launch table): one workgroup per farm slot, 64 threads on
-# compact rings or 256 threads on uniform rings
-BLOCKS = [64, 256]
 # "env" = k_flow_env, one or two waves per env with lane = farm slot x turbine (small farms: what cfg2 / cfg4 run);
 # "env1" = the same kernel forced to ONE wave per env (WG_ENV_WPE=1: what a batch of more than 2048 envs runs — the headline)
 STEADY_BLOCKS = BLOCKS + ["env", "env1"]
 # frozen-box inflow: the per-slot instantiations and "envb" = k_flow_envb (wg_envb.hip), the one-launch env kernel cfg5 runs
 BOX_BLOCKS = BLOCKS + ["envb4", "envb", "envb1"]      # (four waves per env = one per farm slot: hook only, WG_ENV_WPE=4; two: what cfg5 x 1024 runs; one)
-
-
-def _make_env(hip, cfg, block=None):
-    """HipBatch whose flow kernel is the given instantiation (the hooks are read at wg_create)."""
-    import os
-    if block is None:
-        return hip.HipBatch(cfg)
-    envk = isinstance(block, str) and block.startswith("env")
-    hooks = {"WG_FLOW_BLOCK": "64" if envk else str(block), "WG_FLOW_ENV": "1" if envk else "0"}
-    if envk:
-        hooks["WG_ENV_WPE"] = block[-1] if block[-1] in "14" else "2"
-    os.environ.update(hooks)
-    try:
-        env = hip.HipBatch(cfg)
-    finally:
-        for k in hooks:
-            del os.environ[k]
-    # the variant asked for is the one that runs (a silent fallback would test the wrong kernel)
-    threads, compact, slots = env.flow_variant()
-    if envk:
-        assert threads == 64 and compact and slots == 2
-    else:
-        assert threads == block and not slots
-    return env
 
 
 def _t(hip, a):
@@ -110,19 +73,6 @@ def test_hip_glue_matches_reference_golden(hip, name, n_envs):
     env.close()
 
 
-def _physics_cfg(n_envs, autoreset, n_passthrough, nx=4, ny=4, n_particles=None, **over):
-    from windgym_amd.config import EnvConfig
-    from windgym_amd.turbine import V80
-    _, meta = load_golden("env1")
-    d = meta["cfg"]
-    d["farm"].update(nx=nx, ny=ny)
-    d["ActionMethod"] = "yaw"
-    for k, v in over.items():
-        d[k].update(v) if isinstance(v, dict) else d.__setitem__(k, v)
-    return EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=n_envs, autoreset=autoreset,
-                     n_passthrough=n_passthrough, n_particles=n_particles, n_rotor_pts=16)
-
-
 def _compare_step(env, orc, a, step, check_flow=True, power_rtol=2e-4):
     import torch
     obs, rew, tr, fin = env.step(torch.as_tensor(a, device="cuda"))
@@ -147,8 +97,8 @@ def test_hip_physics_matches_oracle_step_for_step(hip, oracle_lib, block):
     per-slot instantiations of k_flow a small farm can run (64 threads: the compact single-wave kernel, on whose state cfg2 / cfg4's
     env kernel runs; 256: uniform rings) and in that env kernel at two waves and one wave per env."""
     B = 6
-    cfg = _physics_cfg(B, autoreset=False, n_passthrough=5)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    cfg = physics_cfg(B, autoreset=False, n_passthrough=5)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     seeds = 1234 + np.arange(B)
     obs0 = env.reset(seeds=seeds).cpu().numpy()
     o0 = orc.reset(seeds=seeds)
@@ -238,7 +188,7 @@ def test_one_step_episodes_on_the_env_kernel(hip, oracle_lib, block):
     d["ActionMethod"] = "yaw"
     B = 5
     cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=B, autoreset=True, n_passthrough=1, n_rotor_pts=16)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     seeds = 77 + np.arange(B)
     np.testing.assert_allclose(env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds), rtol=0, atol=OBS_ATOL)
     rng = np.random.default_rng(5)
@@ -255,7 +205,7 @@ def test_lds_fallback_to_uniform_rings_matches_oracle(hip, oracle_lib):
     is 64 KB) must fall back to the uniform-ring variant at wg_create — not fail at the first launch — and still match
     the oracle (the fallback also has to drop the single-wave variant's LDS-DMA layout flags)."""
     B = 2
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=0.1, nx=8, ny=4, n_particles=4096)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=0.1, nx=8, ny=4, n_particles=4096)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     block, compact, slots = env.flow_variant()
     assert (block, compact, slots) == (256, False, 0)
@@ -303,8 +253,8 @@ def test_hip_autoreset_pipeline_matches_oracle(hip, oracle_lib, block):
     waves per env at this batch size); "env1" = ONE wave per env, the variant batches above 2048 envs — the headline — run:
     deferred episode set-up, first observation built a launch later, the swap in the wave's own glue tail."""
     B = 12
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=1, nx=3, ny=2)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=1, nx=3, ny=2)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     seeds = 77 + np.arange(B)
     np.testing.assert_allclose(env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds), rtol=0, atol=OBS_ATOL)
     rng = np.random.default_rng(1)
@@ -325,7 +275,7 @@ def test_large_odd_batch_with_rollovers_matches_oracle(hip, oracle_lib):
     rollovers: every batch-size dependent path (block order, context hashing, background scheduling) against the
     oracle, which knows none of them."""
     B = 389
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=1)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=1)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     seeds = 5000 + np.arange(B)
     np.testing.assert_allclose(env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds), rtol=0, atol=OBS_ATOL)
@@ -341,7 +291,7 @@ def test_large_odd_batch_with_rollovers_matches_oracle(hip, oracle_lib):
 
 def test_partial_reset_and_state_roundtrip(hip, oracle_lib):
     B = 4
-    cfg = _physics_cfg(B, autoreset=False, n_passthrough=2, nx=2, ny=2)
+    cfg = physics_cfg(B, autoreset=False, n_passthrough=2, nx=2, ny=2)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     seeds = np.array([5, 6, 7, 8], dtype=np.uint64)
     env.reset(seeds=seeds), orc.reset(seeds=seeds)
@@ -368,7 +318,7 @@ def test_partial_reset_and_state_roundtrip(hip, oracle_lib):
 
 
 def test_step_after_truncation_is_an_error(hip):
-    cfg = _physics_cfg(1, autoreset=False, n_passthrough=0.05, nx=2, ny=1)
+    cfg = physics_cfg(1, autoreset=False, n_passthrough=0.05, nx=2, ny=1)
     env = hip.HipBatch(cfg)
     env.reset(seeds=[3])
     import torch
@@ -392,7 +342,6 @@ def test_horns_rev_80_turbines_matches_oracle(hip, oracle_lib, variant):
     pruning, (target, sample)-major phases), still the one turbulent large farms run.  "..._small_staging": the same
     kernel with room for 96 candidate results at a time (WG_LF_CAP), so that the ~500 candidates of a flow step take six
     rounds through the staging region — same sums in the same order."""
-    import os
     from windgym_amd.config import EnvConfig
     from windgym_amd.presets import horns_rev1_layout, horns_rev_config
     from windgym_amd.turbine import V80
@@ -400,15 +349,10 @@ def test_horns_rev_80_turbines_matches_oracle(hip, oracle_lib, variant):
     cfg = EnvConfig(turbine=V80(), yaml_dict=horns_rev_config(), turbtype="None", n_envs=3, autoreset=True,
                     n_passthrough=0.2, x_pos=x, y_pos=y)
     assert cfg.n_turb == 80
-    os.environ["WG_FLOW_RES"] = "1" if variant.startswith("compact_pairmajor") else "0"
+    hooks = {"WG_FLOW_RES": "1" if variant.startswith("compact_pairmajor") else "0"}
     if variant.endswith("small_staging"):
-        os.environ["WG_LF_CAP"] = "96"
-    try:
-        env = hip.HipBatch(cfg)
-    finally:
-        os.environ.pop("WG_FLOW_RES", None)
-        os.environ.pop("WG_LF_CAP", None)
-    assert env.flow_variant()[:2] == (256, variant.startswith("compact_pairmajor"))
+        hooks["WG_LF_CAP"] = "96"
+    env = make_batch(hip, cfg, hooks, variant=(256, variant.startswith("compact_pairmajor"), None))
     orc = oracle_lib.Oracle(cfg)
     seeds = 500 + np.arange(3)
     np.testing.assert_allclose(env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds), rtol=0, atol=OBS_ATOL)
@@ -494,7 +438,7 @@ def test_noise_normal_matches_oracle_stream(hip, oracle_lib, block):
     d["mes_level"].update(turb_wd=True)
     d["wd_mes"].update(wd_current=True, wd_rolling_mean=True)
     cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=5, autoreset=True, n_passthrough=1)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     seeds = 11 + np.arange(5)
     g0, o0 = env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds)
     np.testing.assert_allclose(g0, o0, rtol=0, atol=5e-4)
@@ -548,19 +492,6 @@ def test_midepisode_reset_starts_a_new_noise_stream(hip, oracle_lib):
     env.check()
 
 
-def _turb_cfg(turbtype, n_envs, autoreset=True, n_passthrough=1.0, nx=3, ny=2):
-    from windgym_amd.config import EnvConfig
-    from windgym_amd.presets import env1_config
-    from windgym_amd.turbine import V80
-    d = env1_config()
-    d["ActionMethod"] = "yaw"
-    d["farm"].update(nx=nx, ny=ny)
-    d["mes_level"].update(turb_wd=True, turb_TI=True)
-    d["wd_mes"].update(wd_rolling_mean=True)
-    return EnvConfig(turbine=V80(), yaml_dict=d, turbtype=turbtype, n_envs=n_envs, autoreset=autoreset,
-                     n_passthrough=n_passthrough, n_rotor_pts=16)
-
-
 @pytest.fixture(scope="module")
 def small_mann_box():
     from windgym_amd.mann import generate_mann_box
@@ -596,8 +527,8 @@ def test_random_inflow_matches_oracle(hip, oracle_lib, block):
     instantiations without sensor noise and with the Gaussian deficit, <64, compact> and <256, uniform rings> (the other six:
     tests/test_gpu_variant_census.py)."""
     B = 6
-    cfg = _turb_cfg("Random", B)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    cfg = turb_cfg("Random", B)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     seeds = 300 + np.arange(B)
     np.testing.assert_allclose(env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds), rtol=0, atol=TURB_OBS_ATOL)
     v = env.info("rotor_uvw_agent").cpu().numpy()[..., 1]
@@ -616,8 +547,8 @@ def test_mann_box_inflow_matches_oracle(hip, oracle_lib, small_mann_box, turbtyp
     k_flow_envb with two waves / one wave per env."""
     box, spacing = small_mann_box
     B = 5
-    cfg = _turb_cfg(turbtype, B)
-    env, orc = _make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
+    cfg = turb_cfg(turbtype, B)
+    env, orc = make_env(hip, cfg, block), oracle_lib.Oracle(cfg)
     env.set_turbulence_box(box, spacing), orc.set_turbulence_box(box, spacing)
     seeds = 700 + np.arange(B)
     np.testing.assert_allclose(env.reset(seeds=seeds).cpu().numpy(), orc.reset(seeds=seeds), rtol=0, atol=TURB_OBS_ATOL)
@@ -639,7 +570,7 @@ def test_cfg5_shape_runs_the_instantiation_the_bench_runs(hip, oracle_lib, dims,
     covers k_flow<64, RANDOM> at the same shape (one case: it reads no box)."""
     from windgym_amd.mann import generate_mann_box
     B = 4
-    cfg = _turb_cfg(turbtype, B, nx=4, ny=4)
+    cfg = turb_cfg(turbtype, B, nx=4, ny=4)
     assert cfg.n_turb * cfg.n_particles == 2048
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     if turbtype != "Random":
@@ -658,7 +589,7 @@ def test_mann_box_ragged_dims_matches_oracle(hip, oracle_lib):
     from windgym_amd.mann import generate_mann_box
     box, spacing = generate_mann_box((90, 30, 18), (4.0, 5.0, 6.0), seed=4), (4.0, 5.0, 6.0)
     B = 3
-    cfg = _turb_cfg("MannGenerate", B)
+    cfg = turb_cfg("MannGenerate", B)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     env.set_turbulence_box(box, spacing), orc.set_turbulence_box(box, spacing)
     seeds = 900 + np.arange(B)
@@ -673,7 +604,7 @@ def test_flow_field_view_matches_oracle(hip, oracle_lib, small_mann_box, turbtyp
     grid, agent and baseline farm, with and without wakes, after the farms were yawed for a while."""
     import torch
     B = 3
-    cfg = _turb_cfg(turbtype, B)
+    cfg = turb_cfg(turbtype, B)
     cfg.advect_full_chains = True          # the view reaches 1000 m behind the last row: no chain pruning
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     if turbtype != "None":
@@ -713,19 +644,14 @@ def test_chain_pruning_changes_no_output_and_streams_fewer_particles(hip):
     """wg_config.full_chains = 0 (default for batches): particles behind the most downstream turbine are not advected
     (compiled into the 256-thread, large-farm variant of k_flow — selected here with WG_FLOW_BLOCK).  Every output of
     step() must be bit-identical to the run that advects all P slots."""
-    import os
     import torch
     B = 8
     outs = []
     streamed = []
     for full in (False, True):
-        cfg = _turb_cfg("None", B)
+        cfg = turb_cfg("None", B)
         cfg.advect_full_chains = full
-        os.environ["WG_FLOW_BLOCK"] = "256"
-        try:
-            env = hip.HipBatch(cfg)
-        finally:
-            del os.environ["WG_FLOW_BLOCK"]
+        env = make_batch(hip, cfg, {"WG_FLOW_BLOCK": "256"}, variant=(256, None, 0))
         env.reset(seeds=60 + np.arange(B))
         env.kernel_timing(1)
         rng = np.random.default_rng(13)
@@ -784,7 +710,7 @@ def test_results_do_not_depend_on_batch_composition(hip, turbtype):
 
 
 def test_mann_box_required(hip):
-    cfg = _turb_cfg("MannFixed", 2)
+    cfg = turb_cfg("MannFixed", 2)
     env = hip.HipBatch(cfg)
     with pytest.raises(ValueError):
         env.reset(seeds=[1, 2])
@@ -835,7 +761,7 @@ def test_box_pool_draws_like_np_random_choice_and_matches_oracle(hip, oracle_lib
     spacing = (3.0, 3.0, 3.0)
     boxes = [generate_mann_box((128, 64, 32), spacing, seed=s) for s in (1, 2, 3)]
     B = 6
-    cfg = _turb_cfg("MannLoad", B)
+    cfg = turb_cfg("MannLoad", B)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     env.set_turbulence_boxes(boxes, spacing), orc.set_turbulence_boxes(boxes, spacing)
     seeds = 2100 + np.arange(B)
@@ -868,7 +794,7 @@ def test_manngenerate_pool_seed_picks_box_and_offset(hip, oracle_lib):
     spacing = (3.0, 3.0, 3.0)
     boxes = [generate_mann_box((128, 64, 32), spacing, seed=s) for s in (11, 12, 13)]
     B = 6
-    cfg = _turb_cfg("MannGenerate", B)
+    cfg = turb_cfg("MannGenerate", B)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     env.set_turbulence_boxes(boxes, spacing), orc.set_turbulence_boxes(boxes, spacing)
     seeds = 3100 + np.arange(B)
@@ -949,7 +875,7 @@ def test_prepared_first_observation_survives_buffer_switches(hip, oracle_lib):
     hand out the first observation of an episode that has since been replaced: every step against the oracle."""
     import torch
     B = 6
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=0.25)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=0.25)
     env, orc = hip.HipBatch(cfg), oracle_lib.Oracle(cfg)
     assert env.flow_variant() == (64, True, 2)          # k_flow_env (two waves per env) prepares the first observation too
     seeds = 900 + np.arange(B)
@@ -980,7 +906,7 @@ def test_checkpoint_resume_is_bit_identical_across_rollovers(hip):
     episodes, so the restored handle rebuilds them at the swap (lean_swap's fallback): both paths use one arithmetic."""
     import torch
     B = 8
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=0.25)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=0.25)
     a_env, b_env = hip.HipBatch(cfg), hip.HipBatch(cfg)
     assert a_env.flow_variant() == (64, True, 2)
     seeds = 300 + np.arange(B)
@@ -1005,7 +931,7 @@ def test_checkpoint_resume_is_bit_identical_across_rollovers(hip):
 
 
 @pytest.mark.parametrize("case", ["env1_4x4", "generic_ti_farm_current", "per_agent_buffer"])
-def test_lean_glue_equals_the_ring_staging_glue(hip, monkeypatch, case):
+def test_lean_glue_equals_the_ring_staging_glue(hip, case):
     """k_glue_lean (running window sums, sums mode) against k_glue (rings staged and summed every step, WG_SUMS=0) on the
     same handle configuration, step for step across rollovers: observations, final observations, rewards, truncations —
     two independently written kernels, one answer (to float rounding: exact double sums vs float sums)."""
@@ -1035,9 +961,7 @@ def test_lean_glue_equals_the_ring_staging_glue(hip, monkeypatch, case):
     kw = dict(extra_timestep_inc=True) if multi else {}
     cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=B, autoreset=True, n_passthrough=0.3, n_rotor_pts=16, **kw)
     lean = hip.HipBatch(cfg)
-    monkeypatch.setenv("WG_SUMS", "0")
-    ring = hip.HipBatch(cfg)
-    monkeypatch.delenv("WG_SUMS")
+    ring = make_batch(hip, cfg, {"WG_SUMS": "0"})
     ml = lean.fuse_obs_multi() if multi else None
     mr = ring.fuse_obs_multi() if multi else None
     seeds = 70 + np.arange(B)

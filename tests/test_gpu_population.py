@@ -7,20 +7,10 @@ import pytest
 
 import rl_helpers
 from population_twin import MemberLoop, twin_rollout, twin_train
-from rl_helpers import _torch, _venv, rollout_equals_the_loop
+from rl_helpers import _torch, _venv, close_all, mlp_members, pop_hyper, rollout_equals_the_loop
 
 pytestmark = pytest.mark.gpu
 make = functools.partial(rl_helpers.make, dtype=np.float64)        # (test_gpu_ppo.py's policies)
-
-
-def _members(P, n_in=32, hidden=(64, 64), n_out=16, seed0=3):
-    return [make(n_in, hidden, n_out, seed=seed0 + 7 * m)[0] for m in range(P)]
-
-
-def _close(*xs):
-    for x in xs:
-        for y in (x if isinstance(x, (list, tuple)) else [x]):
-            y.close()
 
 
 # 1 ---------------------------------------------------------------------------------------------------------------------
@@ -29,7 +19,7 @@ def _close(*xs):
 def test_act_equals_the_single_calls(P, Bm, deterministic):
     from windgym_amd.population import Population
     t = _torch()
-    ms = _members(P)
+    ms = mlp_members(P)
     pop, loop = Population(ms), MemberLoop(ms)
     obs = t.rand((P * Bm, 32), device="cuda") * 2 - 1
     seeds, offs = [11 + 3 * m for m in range(P)], [1000 * m + 5 for m in range(P)]
@@ -40,7 +30,7 @@ def test_act_equals_the_single_calls(P, Bm, deterministic):
     assert t.equal(pop.value(obs), loop.value(obs))
     if P > 1 and not deterministic:
         assert not t.equal(got[1][:Bm], got[1][Bm:2 * Bm])
-    _close(pop, ms)
+    close_all(pop, ms)
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------------
@@ -48,18 +38,18 @@ def test_act_equals_the_single_calls(P, Bm, deterministic):
 def test_rollout_equals_the_loop_of_single_calls(P):
     from windgym_amd.population import Population
     va, vb = _venv(48), _venv(48)
-    ms = _members(P, va.batch.obs_dim, (64, 64), va.n_turb)
+    ms = mlp_members(P, va.batch.obs_dim, (64, 64), va.n_turb)
     pop, T, rec = Population(ms), 300, ("power_agent", "yaw_agent")
     out = va.rollout(pop, T, record=rec)
     rollout_equals_the_loop(va, vb, MemberLoop(ms), T, rec=rec, out=out)       # buffers, wg_state blob, persistent outputs
-    _close(pop, ms, va, vb)
+    close_all(pop, ms, va, vb)
 
 
 def test_equal_members_roll_out_what_one_policy_does():
     from windgym_amd.population import Population
     t = _torch()
     va, vb = _venv(64), _venv(64)
-    ms = _members(4, va.batch.obs_dim, (64, 64), va.n_turb)
+    ms = mlp_members(4, va.batch.obs_dim, (64, 64), va.n_turb)
     for m in ms[1:]:
         m.load_state_dict(ms[0].state_dict())
     pop = Population(ms)
@@ -68,16 +58,10 @@ def test_equal_members_roll_out_what_one_policy_does():
     for k in a:
         assert t.equal(a[k], b[k]), k
     assert va.batch.get_state() == vb.batch.get_state()
-    _close(pop, ms, va, vb)
+    close_all(pop, ms, va, vb)
 
 
 # 3, 5, 6, 8 ------------------------------------------------------------------------------------------------------------
-def _hyper(P):
-    return dict(gamma=[0.99, 0.9, 0.95, 0.97][:P], gae_lambda=[0.95, 0.9, 1.0, 0.8][:P], ent_coef=[0.0, 0.01, 0.003, 0.0][:P],
-                vf_coef=[0.5, 0.7, 0.4, 0.5][:P], max_grad_norm=[0.5, 0.05, 10.0, 0.5][:P], learning_rate=[3e-4, 1e-3, 0.0, 2e-3][:P],
-                clip_range=[0.2, 0.1, 0.3, 0.2][:P], normalize_advantage=[True, False, True, True][:P])
-
-
 def _twin_population(pp, vb):
     """single-policy twins of a PPOPopulation's members (same initial weights), their optimisers and generators"""
     from windgym_amd.policy import MlpPolicy
@@ -104,7 +88,7 @@ def test_learn_equals_the_twin_of_single_policy_entries(P, B, T, bs):
     t = _torch()
     va, vb = _venv(B), _venv(B)
     E = 3
-    pp = PPOPopulation("MlpPolicy", va, n_members=P, n_steps=T, n_epochs=E, batch_size=bs, seed=list(range(5, 5 + P)), **_hyper(P))
+    pp = PPOPopulation("MlpPolicy", va, n_members=P, n_steps=T, n_epochs=E, batch_size=bs, seed=list(range(5, 5 + P)), **pop_hyper(P))
     tw, opts, gens = _twin_population(pp, vb)
     loop = MemberLoop(tw)
     hyper = [pp.member_hyper(m) for m in range(P)]
@@ -131,7 +115,7 @@ def test_learn_equals_the_twin_of_single_policy_entries(P, B, T, bs):
     x = t.rand((64, pp.members[0].n_in), device="cuda")
     for m in range(P):                                                    # the packed copies followed (repack after every step)
         assert t.equal(pp.members[m].act(x, deterministic=True)[1], tw[m].act(x, deterministic=True)[1])
-    pp.close(); _close(opts, tw, pp.members, va, vb)
+    pp.close(); close_all(opts, tw, pp.members, va, vb)
 
 
 def test_population_of_one_is_ppo():
@@ -147,7 +131,7 @@ def test_population_of_one_is_ppo():
     assert va.batch.get_state() == vb.batch.get_state()
     for k in ("loss", "pi_loss", "v_loss", "approx_kl", "explained_variance"):
         assert pp.log[-1][0][k] == ppo.log[-1][k], k
-    pp.close(); ppo.close(); _close(pp.members, ppo.policy, va, vb)
+    pp.close(); ppo.close(); close_all(pp.members, ppo.policy, va, vb)
 
 
 # 4 ---------------------------------------------------------------------------------------------------------------------
@@ -156,18 +140,18 @@ def test_members_are_independent():
     from windgym_amd.population import PPOPopulation
     t = _torch()
     P, B, T = 3, 48, 8
-    hy = _hyper(3)
+    hy = pop_hyper(3)
 
     def run(others_changed):
         v = _venv(B)
         kw, sd = dict(hy), [5, 6, 7]
         if others_changed:
             sd = [5, 91, 92]
-            kw = {k: [x[0]] + [_hyper(4)[k][3]] * 2 for k, x in hy.items()}
+            kw = {k: [x[0]] + [pop_hyper(4)[k][3]] * 2 for k, x in hy.items()}
         pp = PPOPopulation("MlpPolicy", v, n_members=P, n_steps=T, n_epochs=2, seed=sd, **kw).learn(2 * T * B // P)
         bufs = {k: x.clone() for k, x in next(iter(v._rollout_bufs.values())).items()}
         params = [m.params.clone() for m in pp.members]
-        pp.close(); _close(pp.members, v)
+        pp.close(); close_all(pp.members, v)
         return bufs, params
     (base, pb), (other, po) = run(False), run(True)
     Bm = B // P
@@ -209,7 +193,7 @@ def test_update_is_permuted_with_the_members():
         pop._chk(pop.L.wg_pop_update(pop._h, params, C.byref(b), perm.data_ptr(), E, bs, hp, lr, mg, None, pop._stream()), "wg_pop_update")
         out = {i: pol[m].params.clone() for m, i in enumerate(order)}
         res.append(out)
-        _close(pop, opts, pol)
+        close_all(pop, opts, pol)
     for i in range(P):
         assert t.equal(res[0][i], res[1][i]), i
 
@@ -224,7 +208,7 @@ def test_member_equals_ppo_on_its_shard():
     t = _torch()
     P, B, T = 2, 32, 16
     va = _venv(B)
-    hy = {k: x[:P] for k, x in _hyper(P).items()}
+    hy = {k: x[:P] for k, x in pop_hyper(P).items()}
     pp = PPOPopulation("MlpPolicy", va, n_members=P, n_steps=T, n_epochs=2, seed=[5, 6], **hy).learn(3 * T * B // P)
     for m in range(P):
         vs = WindFarmVecEnv(V80(), B // P, yaml_dict=presets.bench_cfg2_config(), seed=77, as_torch=True, turbtype="None", n_passthrough=1,
@@ -233,21 +217,21 @@ def test_member_equals_ppo_on_its_shard():
         ppo = PPO("MlpPolicy", vs, seed=5 + m, **pp.member_hyper(m))
         ppo.learn(3 * T * B // P)
         assert t.equal(ppo.policy.params, pp.members[m].params), m
-        ppo.close(); _close(ppo.policy, vs)
-    pp.close(); _close(pp.members, va)
+        ppo.close(); close_all(ppo.policy, vs)
+    pp.close(); close_all(pp.members, va)
 
 
 # 8 ---------------------------------------------------------------------------------------------------------------------
 def test_widest_layers():
     from windgym_amd.population import Population
     t = _torch()
-    ms = _members(2, 2048, (256, 256), 16)
+    ms = mlp_members(2, 2048, (256, 256), 16)
     pop, loop = Population(ms), MemberLoop(ms)
     obs = t.rand((2 * 40, 2048), device="cuda") * 2 - 1
     got = [x.clone() for x in pop.act(obs, counter=2, seed=[1, 2], row_offset=[0, 7])]
     for g, w in zip(got, loop.act(obs, counter=2, seed=[1, 2], row_offset=[0, 7])):
         assert t.equal(g, w)
-    _close(pop, ms)
+    close_all(pop, ms)
 
 
 def test_refusals():
@@ -256,7 +240,7 @@ def test_refusals():
     from windgym_amd.population import Population, PPOPopulation
     from windgym_amd.ppo import PPOOptimizer
     t = _torch()
-    a, b = _members(2)
+    a, b = mlp_members(2)
     with pytest.raises(ValueError, match="1 .. 16 members"):
         Population([])
     with pytest.raises(ValueError, match="member 1 is the same policy as member 0"):
@@ -293,10 +277,10 @@ def test_refusals():
     v = _venv(9)
     with pytest.raises(ValueError, match="does not divide by 2"):
         PPOPopulation("MlpPolicy", v, n_members=2)
-    pv = Population(_members(2, v.batch.obs_dim, (64, 64), v.n_turb))
+    pv = Population(mlp_members(2, v.batch.obs_dim, (64, 64), v.n_turb))
     with pytest.raises(ValueError, match="does not divide by 2"):
         v.rollout(pv, 4)
     g = (C.c_float * 2)(0.9, 0.9)
     with pytest.raises(ValueError, match="wg_gae_pop: P = 2"):
         pop._chk(pop.L.wg_gae_pop(2, 7, 2, x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), g, g, x.data_ptr(), x.data_ptr(), None), "wg_gae_pop")
-    _close(pop, pop2, pv, oa, ob, a, b, c, s, v)
+    close_all(pop, pop2, pv, oa, ob, a, b, c, s, v)

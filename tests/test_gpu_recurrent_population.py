@@ -9,24 +9,13 @@ import numpy as np
 import pytest
 
 from recurrent_population_twin import LstmMemberLoop, pop_update, single_update, twin_rollout
-from rl_helpers import _torch, _venv, dev
-from test_gpu_population import _hyper
-from tests import lstm_bptt_twin as tw
+import lstm_bptt_twin as tw
+from recurrent_ppo_cases import make_spec
+from rl_helpers import _torch, _venv, close_all, dev, lstm_members, lstm_policy, pop_hyper
 
 pytestmark = pytest.mark.gpu
 
-N_IN, H = 7, 40             # H: not a multiple of the 32 units of a tile
-
-
-def _members(P, n_in=N_IN, n_out=2, hidden=H, shared=False, heads=(16,), seed0=3):
-    from windgym_amd.recurrent import MlpLstmPolicy
-    return [MlpLstmPolicy(n_in, n_out, hidden, heads, heads, shared_lstm=shared, seed=seed0 + 7 * m) for m in range(P)]
-
-
-def _close(*xs):
-    for x in xs:
-        for y in (x if isinstance(x, (list, tuple)) else [x]):
-            y.close()
+N_IN, H = 7, 40             # H: not a multiple of the 32 units of a tile (the defaults of rl_helpers.lstm_members)
 
 
 # 1 ---------------------------------------------------------------------------------------------------------------------
@@ -36,7 +25,7 @@ def _close(*xs):
 def test_act_equals_the_single_calls(P, Bm, shared, deterministic):
     from windgym_amd.recurrent_population import RecurrentPopulation
     t = _torch()
-    ms = _members(P, shared=shared)
+    ms = lstm_members(P, shared=shared)
     pop, loop = RecurrentPopulation(ms), LstmMemberLoop(ms)
     n = P * Bm
     g = t.Generator(device="cuda"); g.manual_seed(P * 100 + Bm)
@@ -58,7 +47,7 @@ def test_act_equals_the_single_calls(P, Bm, shared, deterministic):
     assert got[3] is None and t.equal(got[1], want[1]) and t.equal(new, wnew)
     if P > 1 and not deterministic:
         assert not t.equal(got[1][:Bm], got[1][Bm:2 * Bm])
-    _close(pop, ms)
+    close_all(pop, ms)
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------------
@@ -71,7 +60,7 @@ def test_rollout_equals_the_loop_of_single_calls(P, B, T, shared):
     from windgym_amd.recurrent_population import RecurrentPopulation
     t = _torch()
     va, vb = _venv(B), _venv(B)
-    ms = _members(P, va.batch.obs_dim, va.n_turb, 48, shared, (64, 64))
+    ms = lstm_members(P, va.batch.obs_dim, va.n_turb, 48, shared, (64, 64))
     pop, loop, rec = RecurrentPopulation(ms), LstmMemberLoop(ms), ("power_agent",)
     out = va.rollout(pop, T, record=rec)
     ref, ref_state = twin_rollout(vb, loop, T, pop.initial_state(B), t.ones(B, dtype=t.uint8, device="cuda"), rec=rec)
@@ -100,7 +89,7 @@ def test_rollout_equals_the_loop_of_single_calls(P, B, T, shared):
     va.reset(seed=5)
     o2 = va.rollout(pop, 2, state=state_T)
     assert bool((o2["episode_start"][0] == 1).all()) and t.equal(o2["lstm_state0"], state_T)
-    _close(pop, ms, va, vb)
+    close_all(pop, ms, va, vb)
 
 
 def test_equal_members_roll_out_what_one_policy_does():
@@ -108,7 +97,7 @@ def test_equal_members_roll_out_what_one_policy_does():
     t = _torch()
     P, B, T = 4, 64, 40
     va, vb = _venv(B), _venv(B)
-    ms = _members(P, va.batch.obs_dim, va.n_turb, 48, False, (64, 64))
+    ms = lstm_members(P, va.batch.obs_dim, va.n_turb, 48, False, (64, 64))
     for m in ms[1:]:
         m.load_state_dict(ms[0].state_dict())
     pop = RecurrentPopulation(ms)
@@ -119,31 +108,17 @@ def test_equal_members_roll_out_what_one_policy_does():
     for k in ("lstm_state0", "lstm_state"):                              # [P, nets, 2, Bm, H] against [nets, 2, B, H]
         assert t.equal(a[k].permute(1, 2, 0, 3, 4).reshape(b[k].shape), b[k]), k
     assert va.batch.get_state() == vb.batch.get_state()
-    _close(pop, ms, va, vb)
+    close_all(pop, ms, va, vb)
 
 
 # 3, 4 ------------------------------------------------------------------------------------------------------------------
 P3, BM, EPB, E = 3, 40, 16, 2            # minibatches of 16, 16 and 8 envs
 
 
-def _spec(shared):
-    return dict(n_in=N_IN, H=H, n_out=2, hidden_pi=(16,), hidden_vf=(16,), shared=shared, activation="tanh")
-
-
-def _policy(spec, flat):
-    from windgym_amd.recurrent import MlpLstmPolicy
-    t = _torch()
-    p = MlpLstmPolicy(spec["n_in"], spec["n_out"], spec["H"], spec["hidden_pi"], spec["hidden_vf"], spec["shared"], spec["activation"])
-    with t.no_grad():
-        p.params.copy_(t.from_numpy(np.asarray(flat, np.float32)))
-    p.sync()
-    return p
-
-
 @functools.lru_cache(maxsize=None)
 def _shards(shared, T):
     """Per member id 0 .. 3: (flat parameters, its own rollout [T (+ 1), BM, ..] as recurrent_ppo_cases makes them, its local permutations)."""
-    spec = _spec(shared)
+    spec = make_spec(N_IN, H, shared)
     out = []
     for i in range(4):
         flat = tw.random_params(spec, seed=4 + 10 * i)
@@ -184,15 +159,15 @@ def _run_pop(shared, T, order, nan=(), bad_ids=None, epb=EPB):
     if bad_ids is not None:
         for e, pos, val in bad_ids[1]:
             perm[order.index(bad_ids[0]), e, pos] = val
-    ps = [_policy(spec, f) for f in flats]
+    ps = [lstm_policy(spec, f) for f in flats]
     opts = [RecurrentPPOOptimizer(p, T, epb) for p in ps]
     pop = RecurrentPopulation(ps, opts)
-    hy = {k: [_hyper(4)[k][i] for i in order] for k in _hyper(4)}
+    hy = {k: [pop_hyper(4)[k][i] for i in order] for k in pop_hyper(4)}
     keys = list(roll)
     d = dict(zip(keys, dev(*[roll[k] for k in keys])))
     st = pop_update(pop, d, dev(perm)[0], epb, hy)
     res = {i: _result(ps[m], opts[m], st[m]) for m, i in enumerate(order)}
-    _close(pop, opts, ps)
+    close_all(pop, opts, ps)
     return res
 
 
@@ -210,13 +185,13 @@ def _run_single(shared, T, i, bad=(), epb=EPB):
     perms = perms.copy()
     for e, pos, val in bad:
         perms[e, pos] = val
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, T, epb)
     keys = list(roll)
     d = dict(zip(keys, dev(*[roll[k] for k in keys])))
-    st = single_update(opt, d, dev(perms)[0], epb, _hyper(4), i)
+    st = single_update(opt, d, dev(perms)[0], epb, pop_hyper(4), i)
     res = _result(p, opt, st)
-    _close(opt, p)
+    close_all(opt, p)
     return res
 
 
@@ -235,7 +210,7 @@ def test_update_equals_the_single_updates(shared, T):
         assert np.array_equal(pop[i][1], one[1]) and pop[i][2] == one[2], ("adam", i)
         assert t.equal(pop[i][3], one[3]), ("stats", i)
         moved = not t.equal(one[0].cpu(), t.from_numpy(sh[i][0]))
-        assert moved == (_hyper(4)["learning_rate"][i] != 0.0) and np.abs(one[1]).max() > 0
+        assert moved == (pop_hyper(4)["learning_rate"][i] != 0.0) and np.abs(one[1]).max() > 0
     assert float(pop[1][3][..., 7].min()) == 1.0 and float(pop[0][3][..., 7].max()) != 1.0      # adv_std: member 1 does not normalise
 
 
@@ -295,7 +270,7 @@ def test_learn_equals_the_twin_of_single_policy_entries(tmp_path):
     P, B, T = 2, 16, 8
     Bm = B // P
     va, vb = _venv(B), _venv(B)
-    hy = {k: x[:P] for k, x in _hyper(P).items()}
+    hy = {k: x[:P] for k, x in pop_hyper(P).items()}
     pp = RecurrentPPOPopulation("MlpLstmPolicy", va, n_members=P, n_steps=T, n_epochs=E, seed=[5, 6],
                                 policy_kwargs=dict(lstm_hidden_size=40, net_arch=dict(pi=[16], vf=[16])), **hy)
     assert pp.envs_per_batch == 2 and pp.batch_size == 2 * T and pp.n_minibatches == 4
@@ -357,7 +332,7 @@ def test_learn_equals_the_twin_of_single_policy_entries(tmp_path):
     assert sa == sb == 4 * E * pp.n_minibatches and np.array_equal(mva, mvb)
     assert t.equal(vs._lstm_pair(one.policy)[1], va._lstm_pair(pp.population)[1][m])
     one.close(); pp.close()
-    _close(one.policy, opts, twins, pp.members, va, vb, vs)
+    close_all(one.policy, opts, twins, pp.members, va, vb, vs)
 
 
 # 6 ---------------------------------------------------------------------------------------------------------------------
@@ -366,7 +341,7 @@ def test_refusals():
     from windgym_amd.recurrent_ppo import RecurrentPPOOptimizer
     from windgym_amd.site import hornsrev1_site
     t = _torch()
-    a, b = _members(2)
+    a, b = lstm_members(2)
     arr = lambda hs: (C.c_void_p * len(hs))(*[h.value for h in hs])        # noqa: E731
     L, h = a.L, C.c_void_p()
 
@@ -375,7 +350,7 @@ def test_refusals():
         _chk(L.wg_lstm_pop_create(arr([m._lstm for m in ms]), arr([m.mlp._h for m in ms]), None if opts is None else arr([o._h for o in opts]),
                                   len(ms), C.byref(h)), "wg_lstm_pop_create")
     # the classes refuse on the host, the ABI by name where a caller goes past them
-    wide, one_net, heads = _members(1, hidden=48)[0], _members(1, shared=True)[0], _members(1, heads=(16, 16))[0]
+    wide, one_net, heads = lstm_members(1, hidden=48)[0], lstm_members(1, shared=True)[0], lstm_members(1, heads=(16, 16))[0]
     for bad in (wide, one_net, heads):
         with pytest.raises(ValueError, match="member 1 has another architecture"):
             RecurrentPopulation([a, bad])
@@ -398,12 +373,12 @@ def test_refusals():
     with pytest.raises(ValueError, match="does not divide by 2"):
         pop.act(t.zeros((7, N_IN), device="cuda"), t.zeros((2, 2, 2, 3, H), device="cuda"))
     # the update: no optimisers, B % P, T > T_max, a minibatch > Bm_max, max_grad_norm — nothing is enqueued
-    spec = _spec(False)
+    spec = make_spec(N_IN, H, False)
     roll = tw.random_rollout(spec, tw.random_params(spec, 1), 4, 8, seed=2)
     roll["lstm_state0"] = np.stack([roll["lstm_state0"][:, :, :4], roll["lstm_state0"][:, :, 4:]])
     d = dict(zip(roll, dev(*roll.values())))
     perm = dev(np.stack([np.arange(4, dtype=np.int32)[None], 4 + np.arange(4, dtype=np.int32)[None]]))[0]
-    hy = {k: x[:2] for k, x in _hyper(2).items()}
+    hy = {k: x[:2] for k, x in pop_hyper(2).items()}
     w0 = [a.params.clone(), b.params.clone()]
     with pytest.raises(ValueError, match="created without optimisers"):
         pop_update(pop, d, perm, 4, hy)
@@ -422,7 +397,7 @@ def test_refusals():
     # the closed loop: B % P, sample_site, a multi-agent env; a refused rollout leaves the env as it was
     v = _venv(9)
     blob = v.batch.get_state()
-    pv = RecurrentPopulation(_members(2, v.batch.obs_dim, v.n_turb))
+    pv = RecurrentPopulation(lstm_members(2, v.batch.obs_dim, v.n_turb))
     with pytest.raises(ValueError, match="does not divide by 2"):
         v.rollout(pv, 4)
     with pytest.raises(ValueError, match="does not divide by 2"):
@@ -448,7 +423,7 @@ def test_refusals():
             RecurrentPPOPopulation("MlpLstmPolicy", v, n_members=3, **{k: object()})
     with pytest.raises(ValueError, match="multiple of n_steps"):
         RecurrentPPOPopulation("MlpLstmPolicy", v, n_members=3, n_steps=8, batch_size=20)
-    _close(pop, pop2, pop3, pv, oa, ob, o3, a, b, wide, one_net, heads, pv.members, v, vs)
+    close_all(pop, pop2, pop3, pv, oa, ob, o3, a, b, wide, one_net, heads, pv.members, v, vs)
 
 
 # the tool --------------------------------------------------------------------------------------------------------------

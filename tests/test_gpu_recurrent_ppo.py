@@ -10,32 +10,13 @@ import os
 import numpy as np
 import pytest
 
-from tests import lstm_bptt_twin as tw
-from tests.rl_helpers import _torch, _venv, dev
+import lstm_bptt_twin as tw
+from recurrent_ppo_cases import make_spec
+from rl_helpers import _torch, _venv, dev, dev_roll, lstm_policy
 
 pytestmark = pytest.mark.gpu
 
 KW = dict(clip_range=0.2, vf_coef=0.5, ent_coef=0.01, normalize_advantage=True)
-
-
-def _spec(n_in, H, shared, n_out=2, hidden_pi=(16,), hidden_vf=(16,)):
-    return dict(n_in=n_in, H=H, n_out=n_out, hidden_pi=hidden_pi, hidden_vf=hidden_vf, shared=shared, activation="tanh")
-
-
-def _policy(spec, flat):
-    from windgym_amd.recurrent import MlpLstmPolicy, param_layout
-    t = _torch()
-    p = MlpLstmPolicy(spec["n_in"], spec["n_out"], spec["H"], spec["hidden_pi"], spec["hidden_vf"], spec["shared"], spec["activation"])
-    assert [(k, tuple(s)) for k, s in param_layout(p.desc)] == [(k, tuple(s)) for k, s in tw.layout(spec)]
-    with t.no_grad():
-        p.params.copy_(t.from_numpy(np.asarray(flat, np.float32)))
-    p.sync()
-    return p
-
-
-def _dev_roll(roll):
-    keys = ("obs", "raw", "logp", "advantage", "returns", "episode_start", "lstm_state0")
-    return dict(zip(keys, dev(*[roll[k] for k in keys])))
 
 
 def _long_starts(T, B):
@@ -58,15 +39,15 @@ def test_grad_vs_twin(case):
     from windgym_amd.recurrent_ppo import RecurrentPPOOptimizer
     t = _torch()
     n_in, H, T, Bm, shared = case
-    spec = _spec(n_in, H, shared)
+    spec = make_spec(n_in, H, shared)
     extra = 5
     B = Bm + extra
     flat = tw.random_params(spec, seed=Bm + T)
     roll = tw.random_rollout(spec, flat, T, B, seed=H + T, starts=_long_starts(T, B) if T == 64 else None)
     envs = np.random.default_rng(n_in).permutation(B)[:Bm].astype(np.int32)
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, T, Bm)
-    g, st = opt.grad(_dev_roll(roll), dev(envs)[0], **KW)
+    g, st = opt.grad(dev_roll(roll), dev(envs)[0], **KW)
     g, st = g.cpu().numpy().astype(np.float64), st.cpu().numpy()
     _, rs, ref, ratio = tw.loss_and_grad(spec, flat, roll, envs, **KW)
     d32 = np.abs(tw.loss_and_grad(spec, flat, roll, envs, dtype=t.float32, **KW)[2] - ref)
@@ -95,7 +76,7 @@ def test_grad_vs_twin(case):
 
 
 def _small(shared=False, T=6, B=40, H=40, n_in=7, seed=0, **kw):
-    spec = _spec(n_in, H, shared)
+    spec = make_spec(n_in, H, shared)
     flat = tw.random_params(spec, seed=seed)
     return spec, flat, tw.random_rollout(spec, flat, T, B, seed=seed + 1, **kw)
 
@@ -106,13 +87,13 @@ def test_fresh_rows_never_read_their_state():
     spec, flat, roll = _small(T=5, B=37)
     fresh = roll["episode_start"][0] != 0
     assert fresh.any() and not fresh.all()
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, 5, 37)
     envs = dev(np.random.default_rng(1).permutation(37).astype(np.int32))[0]
     roll["lstm_state0"][:, :, fresh] = 0.0
-    g0, s0 = (x.clone() for x in opt.grad(_dev_roll(roll), envs, **KW))
+    g0, s0 = (x.clone() for x in opt.grad(dev_roll(roll), envs, **KW))
     roll["lstm_state0"][:, :, fresh] = np.nan
-    g1, s1 = opt.grad(_dev_roll(roll), envs, **KW)
+    g1, s1 = opt.grad(dev_roll(roll), envs, **KW)
     assert bool(t.isfinite(g1).all()) and t.equal(g0, g1) and t.equal(s0, s1)
     opt.close(); p.close()
 
@@ -121,20 +102,20 @@ def test_deterministic_and_independent_of_other_envs():
     from windgym_amd.recurrent_ppo import RecurrentPPOOptimizer
     t = _torch()
     spec, flat, roll = _small(shared=True)
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, 6, 33)
     perm = np.random.default_rng(2).permutation(40)
     inside, outside = perm[:33], perm[33:]
     envs = dev(inside.astype(np.int32))[0]
-    g0, s0 = (x.clone() for x in opt.grad(_dev_roll(roll), envs, **KW))
-    g1, s1 = opt.grad(_dev_roll(roll), envs, **KW)
+    g0, s0 = (x.clone() for x in opt.grad(dev_roll(roll), envs, **KW))
+    g1, s1 = opt.grad(dev_roll(roll), envs, **KW)
     assert t.equal(g0, g1) and t.equal(s0, s1) and float(g0.abs().max()) > 0
     rng = np.random.default_rng(3)
     for k in ("obs", "raw", "logp", "advantage", "returns"):
         roll[k][:, outside] = rng.uniform(-7, 7, roll[k][:, outside].shape).astype(np.float32)
     roll["lstm_state0"][:, :, outside] = 5.0
     roll["episode_start"][:, outside] ^= 1
-    g2, s2 = opt.grad(_dev_roll(roll), envs, **KW)
+    g2, s2 = opt.grad(dev_roll(roll), envs, **KW)
     assert t.equal(g0, g2) and t.equal(s0, s2)
     opt.close(); p.close()
 
@@ -145,9 +126,9 @@ def _update_and_loop(shared, n_epochs=2, B=40, Bm=16, T=6, lr=3e-4):
     t = _torch()
     spec, flat, roll = _small(shared=shared, T=T, B=B, seed=4)
     perms = np.stack([np.random.default_rng(10 + e).permutation(B) for e in range(n_epochs)]).astype(np.int32)
-    d, perm = _dev_roll(roll), dev(perms)[0]
+    d, perm = dev_roll(roll), dev(perms)[0]
     kw = {k: v for k, v in KW.items()}
-    pa, pb = _policy(spec, flat), _policy(spec, flat)
+    pa, pb = lstm_policy(spec, flat), lstm_policy(spec, flat)
     oa, ob = RecurrentPPOOptimizer(pa, T, Bm), RecurrentPPOOptimizer(pb, T, Bm)
     sa = oa.update(d, perm, Bm, learning_rate=lr, max_grad_norm=0.5, **kw)
     n_mb = -(-B // Bm)
@@ -177,8 +158,8 @@ def test_adam_state_moves_between_handles(shared):
     t = _torch()
     T, Bm, k = 3, 5, 3
     spec, flat, roll = _small(shared=shared, T=T, B=Bm, H=40, n_in=7, seed=6)
-    d, envs = _dev_roll(roll), dev(np.arange(Bm, dtype=np.int32))[0]
-    pa, pb = _policy(spec, flat), _policy(spec, flat)
+    d, envs = dev_roll(roll), dev(np.arange(Bm, dtype=np.int32))[0]
+    pa, pb = lstm_policy(spec, flat), lstm_policy(spec, flat)
     oa, ob = RecurrentPPOOptimizer(pa, T, Bm), RecurrentPPOOptimizer(pb, T, Bm)
     n = pa.params.numel()
     mv0, step0 = oa.state()
@@ -318,13 +299,13 @@ def test_refusals():
         RecurrentPPO("MlpLstmPolicy", Multi())
     # the ABI (binding._chk: WG_ERR_INVALID is a ValueError, WG_ERR_UNSUPPORTED a NotImplementedError)
     spec, flat, roll = _small(T=4, B=6, H=8)
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     with pytest.raises(ValueError, match="T_max and Bm_max must be >= 1"):
         RecurrentPPOOptimizer(p, 0, 4)
     with pytest.raises(NotImplementedError, match=r"T_max = 16777216 steps of Bm_max = 1024 envs"):
         RecurrentPPOOptimizer(p, 1 << 24, 1024)
     opt = RecurrentPPOOptimizer(p, 3, 4)
-    d = _dev_roll(roll)
+    d = dev_roll(roll)
     envs = dev(np.arange(6, dtype=np.int32))[0]
     with pytest.raises(NotImplementedError, match="T = 4 > the T_max = 3"):
         opt.grad(d, envs[:4], **KW)

@@ -12,10 +12,9 @@ and the worst ratio per tensor class; profiles/r22_lstm_ppo_limits_errors.txt ke
 import numpy as np
 import pytest
 
-from tests import lstm_bptt_twin as tw
-from tests import recurrent_ppo_cases as rc
-from tests.rl_helpers import _torch, _venv, dev
-from tests.test_gpu_recurrent_ppo import _dev_roll, _policy
+import lstm_bptt_twin as tw
+import recurrent_ppo_cases as rc
+from rl_helpers import _torch, _venv, dev, dev_roll, lstm_policy
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +52,7 @@ def check_against_twin(tag, g, st, ref):
 
 def _grad(opt, roll, envs, kw):
     """One wg_lstm_ppo_grad -> (gradient, stats), copies of their own."""
-    g, st = opt.grad(_dev_roll(roll), dev(np.asarray(envs, np.int32))[0], **kw)
+    g, st = opt.grad(dev_roll(roll), dev(np.asarray(envs, np.int32))[0], **kw)
     return g.clone(), st.clone()
 
 
@@ -62,7 +61,7 @@ def test_arch_grad_vs_twin(i):
     from windgym_amd.recurrent_ppo import RecurrentPPOOptimizer
     (spec, flat, roll, envs, kw), ref = rc.arch(i)
     T = roll["raw"].shape[0]
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, T, len(envs))
     g, st = _grad(opt, roll, envs, kw)
     check_against_twin(f"arch {rc.arch_id(rc.ARCH_CASES[i])}", g, st, ref)
@@ -75,7 +74,7 @@ def test_cell_edge_grad_vs_twin(name):
     t = _torch()
     (spec, flat, roll, envs, kw), ref = rc.edge(name)
     T = roll["raw"].shape[0]
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, T, len(envs))
     g, st = _grad(opt, roll, envs, kw)
     got = tw.views(spec, check_against_twin(f"edge {name}", g, st, ref))
@@ -106,7 +105,7 @@ def test_handle_reuse_is_bit_identical(shared):
     t = _torch()
     spec = rc.make_spec(7, 40, shared)
     flat = tw.random_params(spec, seed=21)
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     opt = RecurrentPPOOptimizer(p, 9, 40)
     B = 44
     for call, (T, Bm) in enumerate(REUSE_CALLS):
@@ -135,7 +134,7 @@ def test_entry_outside_the_rollout():
     valid = envs.copy()
     envs[[0, 32]] = -1
     envs[[31, 36]] = B
-    p = _policy(spec, flat)
+    p = lstm_policy(spec, flat)
     a = RecurrentPPOOptimizer(p, T, Bm)
     ga, sa = _grad(a, roll, envs, rc.KW)
     b = RecurrentPPOOptimizer(p, T, Bm)

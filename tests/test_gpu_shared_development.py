@@ -6,14 +6,13 @@ same arithmetic on the same bits — for every instantiation (one / two waves pe
 different fill lengths of the two farms, across a checkpoint taken while slots are parked, and for the per-slot kernels that
 continue from such a checkpoint.  And the work must really be gone: the device's own flow-step counters say so."""
 import math
-import os
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from helpers import ab_actions, ab_cases, hip, make_ab, same_fields  # noqa: F401  (hip: the fixture)
 
-FIELDS = ["yaw_agent", "yaw_base", "rotor_uvw_agent", "rotor_uvw_base", "power_turb_agent", "power_turb_base"]
+pytestmark = pytest.mark.gpu
 
 # kernel instantiations: one wave per env, two, a pass wave for the running episode's context, pass waves for both
 VARIANTS = {
@@ -24,59 +23,11 @@ VARIANTS = {
 }
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
-
-
-def _make(hip, d, B, hooks, multi=False, **kw):
-    from windgym_amd.config import EnvConfig
-    from windgym_amd.turbine import V80
-    os.environ.update(hooks)
-    try:
-        cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=B, autoreset=True, n_rotor_pts=16, **kw)
-        env = hip.HipBatch(cfg)
-    finally:
-        for k in hooks:
-            del os.environ[k]
-    if multi:
-        env.fuse_obs_multi()
-    return cfg, env
-
-
-def _cases():
-    from windgym_amd import presets
-    return {
-        "cfg2_4x4": (presets.bench_cfg2_config(), dict(n_passthrough=1, n_particles=128), False),
-        "cfg4_3x3_per_agent_buffer": (presets.multi_3x3_config(), dict(n_passthrough=0.5, n_particles=96, extra_timestep_inc=True), True),
-        "two_turb_noise_K": (presets.two_turb_config(), dict(n_passthrough=1), False),
-        "cfg2_one_farm": (presets._upd(presets.bench_cfg2_config(), power_def=dict(Power_reward="Power_avg")),
-                          dict(n_passthrough=1, n_particles=128), False),
-    }
+ENV_KERNEL = (None, None, 2)      # flow_variant() of a handle on k_flow_env, whatever its threads and rings
 
 
 def _hooks(variant, fused, share):
     return {"WG_FLOW_ENV": "1", "WG_STEP_FUSED": "1" if fused else "0", "WG_ENV_SHARE_DEV": "1" if share else "0", **VARIANTS[variant]}
-
-
-def _same_fields(a_env, b_env, tag):
-    import torch
-    for f in FIELDS:
-        try:
-            x, y = a_env.info(f), b_env.info(f)
-        except Exception:  # noqa: BLE001  (one-farm configurations have no baseline fields)
-            continue
-        assert torch.equal(x, y), f"{tag}: {f}"
-
-
-def _acts(cfg, B, seed=5):
-    import torch
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return (torch.rand((64, B, cfg.n_turb), generator=g) * 2 - 1).cuda()
 
 
 def _lockstep(a_env, b_env, acts, s0, s1, multi=False, fields_every=50):
@@ -93,23 +44,22 @@ def _lockstep(a_env, b_env, acts, s0, s1, multi=False, fields_every=50):
             assert torch.equal(a_env._multi_buf, b_env._multi_buf), f"per-agent buffer step {s}"
         n_tr += int(ra[2].sum())
         if s % fields_every == fields_every - 1:
-            _same_fields(a_env, b_env, f"step {s}")
+            same_fields(a_env, b_env, f"step {s}")
     return n_tr
 
 
 def _on_off(hip, case, B, variant, fused, steps, **over):
     import torch
-    d, kw, multi = _cases()[case]
+    d, kw, multi = ab_cases()[case]
     kw = {**kw, **over}
-    cfg, a_env = _make(hip, d, B, _hooks(variant, fused, True), multi=multi, **kw)
-    _, b_env = _make(hip, d, B, _hooks(variant, fused, False), multi=multi, **kw)
-    assert a_env.flow_variant()[2] == 2 and b_env.flow_variant()[2] == 2
+    cfg, a_env = make_ab(hip, d, B, _hooks(variant, fused, True), multi=multi, variant=ENV_KERNEL, **kw)
+    _, b_env = make_ab(hip, d, B, _hooks(variant, fused, False), multi=multi, variant=ENV_KERNEL, **kw)
     seeds = 900 + np.arange(B)
     assert torch.equal(a_env.reset(seeds=seeds), b_env.reset(seeds=seeds)), "reset obs"
-    _same_fields(a_env, b_env, "after reset")
+    same_fields(a_env, b_env, "after reset")
     a_env.check(); b_env.check()
-    n_tr = _lockstep(a_env, b_env, _acts(cfg, B), 0, steps, multi=multi)
-    _same_fields(a_env, b_env, "end")
+    n_tr = _lockstep(a_env, b_env, ab_actions(cfg, B), 0, steps, multi=multi)
+    same_fields(a_env, b_env, "end")
     a_env.check(); b_env.check()          # (an episode that is not ready at its swap latches the status word)
     a_env.close(); b_env.close()
     return n_tr
@@ -130,7 +80,7 @@ def test_sharing_on_equals_off_bit_for_bit(hip, case, B, variant, fused):
 def test_farms_with_different_fill_lengths(hip, fill_window, variant):
     """fill_window=False / an integer below hist_max: the agent farm fills 1 / 7 env steps, the baseline farm hist_max — its fill
     only starts at the clone, and the episode must still be ready WG_SHADOW_MARGIN steps before the truncation (check())."""
-    d, kw, _ = _cases()["cfg2_4x4"]
+    d, kw, _ = ab_cases()["cfg2_4x4"]
     from windgym_amd.config import EnvConfig
     from windgym_amd.turbine import V80
     cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=4, fill_window=fill_window, **kw)
@@ -145,12 +95,12 @@ def test_checkpoint_with_parked_slots_replays(hip, variant):
     different winds: every offset catches parked ones), restored into a fresh handle:
     the continuation equals the uninterrupted run bit for bit, through the next rollovers."""
     import torch
-    d, kw, _ = _cases()["cfg2_4x4"]
+    d, kw, _ = ab_cases()["cfg2_4x4"]
     B = 64
-    cfg, ref = _make(hip, d, B, _hooks(variant, True, True), **kw)
+    cfg, ref = make_ab(hip, d, B, _hooks(variant, True, True), variant=ENV_KERNEL, **kw)
     seeds = 40 + np.arange(B)
     ref.reset(seeds=seeds)
-    acts = _acts(cfg, B, seed=11)
+    acts = ab_actions(cfg, B, seed=11)
     outs, blobs = [], {}
     for s in range(420):
         if s in (30, 95, 170):
@@ -158,7 +108,7 @@ def test_checkpoint_with_parked_slots_replays(hip, variant):
         outs.append([x.clone() for x in ref.step(acts[s % 64])])
     ref.check()
     for s0, blob in blobs.items():
-        _, env = _make(hip, d, B, _hooks(variant, True, True), **kw)
+        _, env = make_ab(hip, d, B, _hooks(variant, True, True), variant=ENV_KERNEL, **kw)
         env.reset(seeds=seeds + 1000)              # (another state, overwritten by the blob)
         env.set_state(blob)
         for s in range(s0, 420):
@@ -176,14 +126,13 @@ def test_per_slot_kernels_continue_from_a_parked_checkpoint(hip):
     on their own.  Through the next rollover of every env: check() clean, decisions exact, values within the 1e-5 the
     k_flow_env / k_flow pair is held to (tests/test_gpu_variant_ab.py, "gl")."""
     import torch
-    d, kw, _ = _cases()["cfg2_4x4"]
+    d, kw, _ = ab_cases()["cfg2_4x4"]
     B = 64
-    cfg, a_env = _make(hip, d, B, _hooks("wpe1", False, True), **kw)
-    _, b_env = _make(hip, d, B, {"WG_FLOW_ENV": "0"}, **kw)
-    assert a_env.flow_variant()[2] == 2 and b_env.flow_variant()[2] == 0
+    cfg, a_env = make_ab(hip, d, B, _hooks("wpe1", False, True), variant=ENV_KERNEL, **kw)
+    _, b_env = make_ab(hip, d, B, {"WG_FLOW_ENV": "0"}, variant=(None, None, 0), **kw)
     seeds = 77 + np.arange(B)
     a_env.reset(seeds=seeds); b_env.reset(seeds=seeds + 5)
-    acts = _acts(cfg, B, seed=3)
+    acts = ab_actions(cfg, B, seed=3)
     for s in range(60):
         a_env.step(acts[s % 64])
     b_env.set_state(a_env.get_state())
@@ -226,14 +175,14 @@ def test_the_duplicate_flow_steps_are_gone(hip, variant):
     diagonal, as wg_plan_reset_launches bounds it) over all background flow-steps counted with sharing off.  The run is long
     enough for w < 0.2; the ratio itself is ~0.55 against 1 without the change."""
     import torch
-    d, kw, _ = _cases()["cfg2_4x4"]
+    d, kw, _ = ab_cases()["cfg2_4x4"]
     B, steps = 64, 6000
-    cfg, a_env = _make(hip, d, B, _hooks(variant, True, True), **kw)
-    _, b_env = _make(hip, d, B, _hooks(variant, True, False), **kw)
+    cfg, a_env = make_ab(hip, d, B, _hooks(variant, True, True), variant=ENV_KERNEL, **kw)
+    _, b_env = make_ab(hip, d, B, _hooks(variant, True, False), variant=ENV_KERNEL, **kw)
     seeds = 300 + np.arange(B)
     a_env.reset(seeds=seeds); b_env.reset(seeds=seeds)
     a_env.kernel_timing(True); b_env.kernel_timing(True)          # (marks the counters: the window starts here)
-    acts = _acts(cfg, B, seed=21)
+    acts = ab_actions(cfg, B, seed=21)
     K = cfg.sim_steps_per_env_step
     fills = K * (cfg.steps_on_reset + cfg.hist_max)
     num = den = 0
@@ -268,14 +217,14 @@ def test_the_duplicate_flow_steps_are_gone(hip, variant):
 
 def test_one_farm_handle_is_untouched(hip):
     """F = 1: no baseline farm, the flag is off whatever the hook says — same flow-step count, same state blob."""
-    d, kw, _ = _cases()["cfg2_one_farm"]
+    d, kw, _ = ab_cases()["cfg2_one_farm"]
     B = 64
-    cfg, a_env = _make(hip, d, B, _hooks("wpe1", True, True), **kw)
-    _, b_env = _make(hip, d, B, _hooks("wpe1", True, False), **kw)
+    cfg, a_env = make_ab(hip, d, B, _hooks("wpe1", True, True), variant=ENV_KERNEL, **kw)
+    _, b_env = make_ab(hip, d, B, _hooks("wpe1", True, False), variant=ENV_KERNEL, **kw)
     seeds = 5 + np.arange(B)
     a_env.reset(seeds=seeds); b_env.reset(seeds=seeds)
     a_env.kernel_timing(True); b_env.kernel_timing(True)
-    _lockstep(a_env, b_env, _acts(cfg, B), 0, 300)
+    _lockstep(a_env, b_env, ab_actions(cfg, B), 0, 300)
     assert a_env.kernel_timing(False)[3] == b_env.kernel_timing(False)[3]
     assert a_env.get_state() == b_env.get_state()
     a_env.close(); b_env.close()

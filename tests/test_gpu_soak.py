@@ -8,18 +8,11 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import hip  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
 
 
 def _soak(env, cfg, B, steps, min_roll, check_every=500):

@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import hip  # noqa: F401  (the fixture)
 from rl_helpers import (N_SAMPLE, OBS_ATOL, TURB_OBS_ATOL, TURB_POW_ATOL, TURB_POW_RTOL, TURB_REW_ATOL, TURB_REW_RTOL, TURB_UVW_ATOL,
                         TURB_UVW_RTOL)
 
@@ -20,15 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = 300
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
 
 
 def _cfgs(workload, B, n_passthrough):

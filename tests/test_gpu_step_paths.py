@@ -5,18 +5,9 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import OBS_ATOL, _physics_cfg
+from helpers import OBS_ATOL, hip, physics_cfg  # noqa: F401  (hip: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
 
 
 def test_graph_step_is_bit_identical_to_direct_launches(hip):
@@ -25,7 +16,7 @@ def test_graph_step_is_bit_identical_to_direct_launches(hip):
     autoreset."""
     import torch
     B = 9
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=0.3)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=0.3)
     a_env, g_env = hip.HipBatch(cfg), hip.HipBatch(cfg)
     g_env.set_step_graph(True)
     seeds = 77 + np.arange(B)
@@ -59,7 +50,7 @@ def test_sharded_metrics_over_rccl_world_size_one(hip):
     import torch.distributed as dist
     from windgym_amd.parallel import METRIC_NAMES, ShardedMetrics
     B = 16
-    cfg = _physics_cfg(B, autoreset=True, n_passthrough=0.3)
+    cfg = physics_cfg(B, autoreset=True, n_passthrough=0.3)
     env = hip.HipBatch(cfg)
     env.reset(seeds=np.arange(B))
     gen = torch.Generator().manual_seed(0)
@@ -89,7 +80,7 @@ def test_reset_with_wind_override_below_the_sampling_range(hip, oracle_lib):
     wake and filled sensor windows (parity with the synchronous oracle reset), on the host table and the device table."""
     import torch
     B = 4
-    cfg = _physics_cfg(B, autoreset=False, n_passthrough=1.0, nx=3, ny=1)
+    cfg = physics_cfg(B, autoreset=False, n_passthrough=1.0, nx=3, ny=1)
     assert cfg.to_c().ws_min >= 7.0
     ws = np.array([4.0, 4.5, 9.0, 3.6])
     orc = oracle_lib.Oracle(cfg)
@@ -109,7 +100,7 @@ def test_reset_with_wind_override_below_the_sampling_range(hip, oracle_lib):
             # the oracle has no override hook: pin against an oracle whose sampling range is the override itself
             ref = []
             for b in range(B):
-                c1 = _physics_cfg(1, autoreset=False, n_passthrough=1.0, nx=3, ny=1,
+                c1 = physics_cfg(1, autoreset=False, n_passthrough=1.0, nx=3, ny=1,
                                   wind=dict(ws_min=float(ws[b]), ws_max=float(ws[b])))
                 o1 = oracle_lib.Oracle(c1)
                 ref.append((o1, o1.reset(seeds=[5 + b])[0]))
@@ -124,8 +115,8 @@ def test_reset_with_wind_override_below_the_sampling_range(hip, oracle_lib):
 
 
 def test_state_blob_is_rejected_by_a_differently_configured_handle(hip):
-    cfg_a = _physics_cfg(4, autoreset=True, n_passthrough=1.0, nx=2, ny=2)
-    cfg_b = _physics_cfg(4, autoreset=True, n_passthrough=1.0, nx=2, ny=2, power_def=dict(Power_avg=11))
+    cfg_a = physics_cfg(4, autoreset=True, n_passthrough=1.0, nx=2, ny=2)
+    cfg_b = physics_cfg(4, autoreset=True, n_passthrough=1.0, nx=2, ny=2, power_def=dict(Power_avg=11))
     a, b = hip.HipBatch(cfg_a), hip.HipBatch(cfg_b)
     a.reset(seeds=np.arange(4))
     blob = a.get_state()

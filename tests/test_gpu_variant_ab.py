@@ -14,38 +14,13 @@ never runs).  Every pair runs the SAME handle configuration through two kernel v
 
 at B = 64 and B = 389 (not a multiple of anything) through several episode rollovers, + one 5000-step run of the fused pair
 (the glue's header / deque loads are plain global loads now, wg_glue_lean.h: what used to rest on a register pin)."""
-import os
-
 import numpy as np
 import pytest
 
+from helpers import FIELDS, ab_actions, ab_cases, hip, make_ab, make_batch, same_fields  # noqa: F401  (hip: the fixture)
+from windgym_amd.binding import debug_hooks
+
 pytestmark = pytest.mark.gpu
-
-FIELDS = ["yaw_agent", "yaw_base", "rotor_uvw_agent", "rotor_uvw_base", "power_turb_agent", "power_turb_base"]
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
-
-
-def _make(hip, d, B, hooks, multi=False, **kw):
-    from windgym_amd.config import EnvConfig
-    from windgym_amd.turbine import V80
-    os.environ.update(hooks)
-    try:
-        cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="None", n_envs=B, autoreset=True, n_rotor_pts=16, **kw)
-        env = hip.HipBatch(cfg)
-    finally:
-        for k in hooks:
-            del os.environ[k]
-    if multi:
-        env.fuse_obs_multi()
-    return cfg, env
 
 
 def _pair(mode):
@@ -60,24 +35,12 @@ def _pair(mode):
     return {"WG_FLOW_ENV": "1"}, {"WG_FLOW_ENV": "0"}, False
 
 
-def _cases():
-    from windgym_amd import presets
-    return {
-        "cfg2_4x4": (presets.bench_cfg2_config(), dict(n_passthrough=1, n_particles=128), False),
-        "cfg4_3x3_per_agent_buffer": (presets.multi_3x3_config(), dict(n_passthrough=0.5, n_particles=96, extra_timestep_inc=True), True),
-        "two_turb_noise_K": (presets.two_turb_config(), dict(n_passthrough=1), False),
-        "cfg2_one_farm": (presets._upd(presets.bench_cfg2_config(), power_def=dict(Power_reward="Power_avg")),
-                          dict(n_passthrough=1, n_particles=128), False),
-    }
-
-
 def _ab(hip, mode, case, B, steps):
     import torch
-    d, kw, multi = _cases()[case]
+    d, kw, multi = ab_cases()[case]
     ha, hb, exact = _pair(mode)
-    cfg, a_env = _make(hip, d, B, ha, multi=multi, **kw)
-    _, b_env = _make(hip, d, B, hb, multi=multi, **kw)
-    assert a_env.flow_variant()[2] == 2 and b_env.flow_variant()[2] == (0 if mode == "gl" else 2)
+    cfg, a_env = make_ab(hip, d, B, ha, multi=multi, variant=(None, None, 2), **kw)
+    _, b_env = make_ab(hip, d, B, hb, multi=multi, variant=(None, None, 0 if mode == "gl" else 2), **kw)
 
     def same(x, y, what, rtol=1e-5, atol=1e-5):
         if exact:
@@ -86,18 +49,10 @@ def _ab(hip, mode, case, B, steps):
             fx, fy = x.float(), y.float()
             assert ((fx - fy).abs() <= atol + rtol * fy.abs()).all(), (what, float((fx - fy).abs().max()))
 
-    def same_fields(tag):
-        for f in FIELDS:
-            try:
-                x, y = a_env.info(f), b_env.info(f)
-            except Exception:  # noqa: BLE001  (one-farm configurations have no baseline fields)
-                continue
-            same(x, y, f"{tag}: {f}", atol=20.0 if f.startswith("power") else 1e-5)
     seeds = 900 + np.arange(B)
     same(a_env.reset(seeds=seeds), b_env.reset(seeds=seeds), "reset obs")
-    same_fields("after reset")
-    g = torch.Generator(device="cpu").manual_seed(5)
-    acts = (torch.rand((64, B, cfg.n_turb), generator=g) * 2 - 1).cuda()
+    same_fields(a_env, b_env, "after reset", same)
+    acts = ab_actions(cfg, B, seed=5)
     n_tr = 0
     for s in range(steps):
         ra, rb = a_env.step(acts[s % 64]), b_env.step(acts[s % 64])
@@ -109,7 +64,7 @@ def _ab(hip, mode, case, B, steps):
             same(a_env._multi_buf, b_env._multi_buf, f"per-agent buffer step {s}")
         n_tr += int(ra[2].sum())
         if s % 50 == 49:
-            same_fields(f"step {s}")
+            same_fields(a_env, b_env, f"step {s}", same)
     a_env.check(); b_env.check()
     if mode in ("fused", "split", "split_both"):
         # particles, rings, headers, window sums: the whole state.  (Not for "wpe": one wave per env defers a retired context's
@@ -157,25 +112,18 @@ def test_box_env_kernel_agrees_with_the_per_slot_kernel(hip, wpe):
     B = 48
     box, spacing = generate_mann_box((256, 64, 32), (3.0, 3.0, 3.0), seed=1234), (3.0, 3.0, 3.0)
 
-    def make(hooks):
-        os.environ.update(hooks)
-        try:
-            cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="MannGenerate", n_envs=B, autoreset=True, n_rotor_pts=16,
-                            n_passthrough=1, n_particles=128)
-            env = hip.HipBatch(cfg)
-        finally:
-            for k in hooks:
-                del os.environ[k]
+    def make(hooks, variant):
+        cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="MannGenerate", n_envs=B, autoreset=True, n_rotor_pts=16,
+                        n_passthrough=1, n_particles=128)
+        env = make_batch(hip, cfg, hooks, variant=variant)
         env.set_turbulence_box(box, spacing)
         return cfg, env
-    cfg, a_env = make({"WG_FLOW_ENV": "1", "WG_ENV_WPE": wpe})
-    _, b_env = make({"WG_FLOW_ENV": "0"})
-    assert a_env.flow_variant() == (64, True, 2) and b_env.flow_variant() == (64, True, 0)
+    cfg, a_env = make({"WG_FLOW_ENV": "1", "WG_ENV_WPE": wpe}, (64, True, 2))
+    _, b_env = make({"WG_FLOW_ENV": "0"}, (64, True, 0))
     seeds = 700 + np.arange(B)
     oa, ob = a_env.reset(seeds=seeds), b_env.reset(seeds=seeds)
     assert (oa - ob).abs().max().item() <= 2e-5
-    g = torch.Generator(device="cpu").manual_seed(7)
-    acts = (torch.rand((64, B, cfg.n_turb), generator=g) * 2 - 1).cuda()
+    acts = ab_actions(cfg, B, seed=7)
     n_tr = 0
     for s in range(360):
         ra, rb = a_env.step(acts[s % 64]), b_env.step(acts[s % 64])
@@ -211,22 +159,16 @@ def test_stencil_records_equal_the_brick_ordered_box_bit_for_bit(hip):
     for no8 in (False, True):
         cfg = EnvConfig(turbine=V80(), yaml_dict=d, turbtype="MannGenerate", n_envs=B, autoreset=True, n_rotor_pts=16,
                         n_passthrough=1, n_particles=128)
-        env = hip.HipBatch(cfg)
-        assert env.flow_variant() == (64, True, 2)
-        if no8:
-            os.environ["WG_NO_BOX8"] = "1"
-        try:
+        env = make_batch(hip, cfg, variant=(64, True, 2))
+        with debug_hooks({"WG_NO_BOX8": "1"} if no8 else {}):
             env.set_turbulence_box(box, spacing)
             from windgym_amd.mann import default_added_box
             env.set_added_turbulence_box(*default_added_box())
-        finally:
-            os.environ.pop("WG_NO_BOX8", None)
         envs.append(env)
     a_env, b_env = envs
     seeds = 70 + np.arange(B)
     assert torch.equal(a_env.reset(seeds=seeds), b_env.reset(seeds=seeds))
-    g = torch.Generator(device="cpu").manual_seed(9)
-    acts = (torch.rand((32, B, cfg.n_turb), generator=g) * 2 - 1).cuda()
+    acts = ab_actions(cfg, B, seed=9, n=32)
     n_tr = 0
     for s_ in range(260):
         ra, rb = a_env.step(acts[s_ % 32]), b_env.step(acts[s_ % 32])

@@ -9,7 +9,6 @@ The worst error per quantity is printed per case (pytest -s; the committed table
 worst |d| and as its ratio to the bar, atol + rtol |reference|; a case asserts after its whole run that every ratio is <= 1."""
 import contextlib
 import faulthandler
-import os
 import sys
 import time
 
@@ -17,6 +16,7 @@ import numpy as np
 import pytest
 
 import variant_census as vc
+from helpers import hip, make_batch  # noqa: F401  (hip: the fixture)
 from test_plan import shim  # noqa: F401  (the g++-only plan fixture)
 
 pytestmark = pytest.mark.gpu
@@ -37,15 +37,6 @@ def time_limit(seconds):
         faulthandler.cancel_dump_traceback_later()
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    from windgym_amd import binding
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    binding.load_library()
-    return binding
-
-
 _REF = {}
 
 
@@ -61,14 +52,7 @@ def _make_env(hip, cs, plan):
     """HipBatch under the case's hooks (read at wg_create); the variant the plan names is the one that runs — a silent fallback
     would test the wrong kernel"""
     hooks = {vc.HOOK_ENV[k]: str(v) for k, v in cs.hooks}
-    os.environ.update(hooks)
-    try:
-        env = hip.HipBatch(cs.cfg())
-    finally:
-        for k in hooks:
-            del os.environ[k]
-    assert env.flow_variant() == (plan["block"], bool(plan["res"]), 2 if plan["path_envw"] else 0), (cs.name, env.flow_variant(), plan)
-    return env
+    return make_batch(hip, cs.cfg(), hooks, variant=(plan["block"], bool(plan["res"]), 2 if plan["path_envw"] else 0))
 
 
 class Worst:

@@ -6,7 +6,6 @@ are the same in the header, the built library and the ctypes mirror; the float64
 import ctypes as C
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 
 from oracle import ppo_oracle as oo
 from oracle.ppo_oracle import gae_shared, gae_shared_brute
+from helpers import c_layout
 from windgym_amd import binding, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,16 +44,10 @@ def test_rollout_multi_bufs_layout_matches_c(tmp_path):
     m = re.search(r"typedef struct wg_rollout_multi_bufs \{(.*?)\} wg_rollout_multi_bufs;", _header(), flags=re.S)
     declared = re.findall(r"(\w+)\s*;", m.group(1))
     assert declared == fields                  # same members, same order
-    body = "\n".join(f'printf("{f} %zu\\n", offsetof(wg_rollout_multi_bufs, {f}));' for f in fields)
-    src = tmp_path / "l.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/windgym_hip.h"\n'
-                   f'int main(){{ printf("sizeof %zu\\n", sizeof(wg_rollout_multi_bufs));\n{body}\nreturn 0; }}')
-    exe = tmp_path / "l"
-    subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(binding.CRolloutMultiBufs)
+    out = c_layout("wg_rollout_multi_bufs", fields, tmp_path)
+    assert out["sizeof"] == C.sizeof(binding.CRolloutMultiBufs)
     for f in fields:
-        assert int(out[f]) == getattr(binding.CRolloutMultiBufs, f).offset, f
+        assert out[f] == getattr(binding.CRolloutMultiBufs, f).offset, f
 
 
 @pytest.mark.parametrize("T,B,A,p", [(1, 3, 2, 0.5), (7, 5, 9, 0.3), (30, 4, 3, 0.0), (30, 4, 3, 1.0)])

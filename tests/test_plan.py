@@ -10,23 +10,22 @@ import numpy as np
 import pytest
 
 import bench
+from helpers import host_shim
 from windgym_amd import presets
+from windgym_amd.binding import HOOK_ENV
 from windgym_amd.config import CConfig, EnvConfig
 from windgym_amd.turbine import V80
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "windgym_amd", "csrc")
-HOOKS = ["flow_block", "flow_res", "flow_env", "env_wpe", "env_split", "step_fused", "sums", "lds_pad", "lf_cap", "pstride_pad"]
+HOOKS = list(HOOK_ENV)[:10]      # the plan's ten integer hooks, flow_block .. pstride_pad: the layout of plan_shim.cpp's array
 WG_ERR_UNSUPPORTED = -2
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     """g++ alone, no ROCm include path: the plan must stay free of HIP headers."""
-    so = tmp_path_factory.mktemp("plan") / "plan_shim.so"
-    subprocess.run(["g++", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(ROOT, "tests", "plan_shim.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = host_shim(tmp_path_factory, "plan", include_header_dir=True)
     lib.plan_dump.argtypes = [C.POINTER(CConfig), C.POINTER(C.c_int), C.c_int, C.c_longlong, C.c_longlong, C.c_char_p, C.c_int]
     lib.plan_table.argtypes = [C.POINTER(CConfig), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)]
 

@@ -2,26 +2,20 @@
 pure function of the configuration and the WG_ENV_SHARE_DEV hook — k_flow_env's handles with a baseline farm, nothing else —
 and it must not move a single member of FlowP or the RESET launch count (tests/plan_share_shim.cpp hands both back)."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import bench
+from helpers import host_shim
 from windgym_amd.config import CConfig
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "windgym_amd", "csrc")
 HOOKS = ["flow_env", "flow_block", "env_wpe", "env_split", "share_dev"]
 OUT = ["env_share", "envw", "env_wpe", "env_split", "reset_launches", "F", "turb_mode"]
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = tmp_path_factory.mktemp("plan_share") / "plan_share_shim.so"
-    subprocess.run(["g++", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(ROOT, "tests", "plan_share_shim.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = host_shim(tmp_path_factory, "plan_share", include_header_dir=True)
     lib.plan_share.argtypes = [C.POINTER(CConfig), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
     lib.plan_share_layout.argtypes = [C.POINTER(C.c_int)]
 

@@ -3,12 +3,12 @@ import ctypes as C
 import io
 import json
 import os
-import subprocess
 import zipfile
 
 import numpy as np
 import pytest
 
+from helpers import c_layout
 from oracle import policy_oracle as po
 from windgym_amd import policy as pol
 from windgym_amd.binding import CPolicyDesc, CRolloutBufs
@@ -122,16 +122,10 @@ def test_flat_parameter_order_roundtrip(n_in, hp, hv, n_out, ls):
 def test_policy_struct_layouts_match_c(tmp_path, cls, cname):
     """sizeof / offsetof as gcc sees them == the ctypes mirrors."""
     fields = [f[0] for f in cls._fields_]
-    body = "\n".join(f'printf("{f} %zu\\n", offsetof({cname}, {f}));' for f in fields)
-    src = tmp_path / "lay.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void) {\nprintf("sizeof %%zu\\n", sizeof(%s));\n%s\nreturn 0; }\n'
-                   % (os.path.join(ROOT, "include", "windgym_hip.h"), cname, body))
-    exe = tmp_path / "lay"
-    subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["sizeof"]) == C.sizeof(cls)
+    got = c_layout(cname, fields, tmp_path)
+    assert got["sizeof"] == C.sizeof(cls)
     for f in fields:
-        assert int(got[f]) == getattr(cls, f).offset, f
+        assert got[f] == getattr(cls, f).offset, f
 
 
 def test_policy_noise_stream(oracle_lib):

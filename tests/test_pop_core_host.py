@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import host_shim
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "windgym_amd", "csrc")
 ACTION, RAW, LOGP, VALUE, FINAL = 1, 2, 4, 8, 16
@@ -18,10 +20,7 @@ ACTION, RAW, LOGP, VALUE, FINAL = 1, 2, 4, 8, 16
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     """g++ alone, no ROCm include path: the headers must stay free of HIP headers."""
-    so = tmp_path_factory.mktemp("pop_core") / "pop_core_shim.so"
-    subprocess.run(["g++", "-std=c++17", "-shared", "-fPIC", "-I", CSRC, os.path.join(ROOT, "tests", "pop_core_shim.cpp"), "-o", str(so)],
-                   check=True)
-    lib = C.CDLL(str(so))
+    lib = host_shim(tmp_path_factory, "pop_core")
     lib.pop_slots.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pop_slots.restype = None
     lib.pop_members.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

@@ -48,7 +48,7 @@ def test_sb3_vecenv_abstract_methods_and_signatures():
 
 def test_sb3_vecenv_attributes_wrappers_read():
     """VecEnvWrapper / VecMonitor / evaluate_policy read these attributes of the wrapped VecEnv"""
-    from tests.test_sb3_adapter import _FakeVec
+    from test_sb3_adapter import _FakeVec
     from windgym_amd.envs import SB3VecEnv
     env = SB3VecEnv(_FakeVec())
     for attr in ("num_envs", "observation_space", "action_space", "render_mode"):

@@ -2,11 +2,11 @@
 no device, and the C structs the new entries take against their ctypes mirrors (gcc sizeof / offsetof)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers import c_layout
 from windgym_amd import binding
 from windgym_amd.recurrent_population import check_same_architecture, global_envs, member_minibatch
 
@@ -107,16 +107,10 @@ def test_the_plain_populations_still_refuse_a_recurrent_policy():
 def test_structs_of_the_population_entries_match_c(tmp_path, name, mirror):
     """sizeof / offsetof of every struct wg_lstm_pop_rollout and wg_lstm_pop_update take, as gcc sees them == the ctypes mirrors."""
     fields = [f[0] for f in mirror._fields_]
-    body = "\n".join(f'printf("{f} %zu\\n", offsetof({name}, {f}));' for f in fields)
-    src = tmp_path / "l.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/windgym_hip.h"\n'
-                   f'int main(){{ printf("sizeof %zu\\n", sizeof({name}));\n{body}\nreturn 0; }}')
-    exe = tmp_path / "l"
-    subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(mirror)
+    out = c_layout(name, fields, tmp_path)
+    assert out["sizeof"] == C.sizeof(mirror)
     for f in fields:
-        assert int(out[f]) == getattr(mirror, f).offset, f
+        assert out[f] == getattr(mirror, f).offset, f
 
 
 def test_new_entries_are_declared_and_bound():

@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import lstm_bptt_twin as tw
-from tests import recurrent_ppo_cases as rc
+import lstm_bptt_twin as tw
+import recurrent_ppo_cases as rc
 
 
 def _conditions(built, ref, zero=lambda name: False):

@@ -4,8 +4,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import lstm_bptt_twin as tw
-from tests import lstm_twin
+import lstm_bptt_twin as tw
+import lstm_twin
 
 SPEC = dict(n_in=5, H=7, n_out=2, hidden_pi=(6,), hidden_vf=(4, 3), shared=False, activation="tanh")
 

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import host_shim
 from windgym_amd.binding import CLstmDesc, CPolicyDesc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,10 +21,7 @@ GROUP, SLACK = 8, 8 * 64                                    # the header's WGP_G
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     """g++ alone, no ROCm include path: the layout half must stay free of HIP headers."""
-    so = tmp_path_factory.mktemp("tile") / "tile_shim.so"
-    subprocess.run(["g++", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(ROOT, "tests", "tile_shim.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = host_shim(tmp_path_factory, "tile", include_header_dir=True)
     lib.tile_wsize.restype = lib.tile_bsize.restype = C.c_uint
     return lib
 

@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import host_shim
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "windgym_amd", "csrc")
 STEPS = [1, 2, 10, 1000, 10 ** 6, 2 ** 32 + 1]
@@ -18,10 +20,7 @@ LOOPS = [(1, 1, 1), (7, 2, 3), (8, 2, 4), (5, 3, 8), (33, 1, 32)]          # (ro
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     """g++ alone, no ROCm include path: the header must stay free of HIP headers."""
-    so = tmp_path_factory.mktemp("train") / "train_shim.so"
-    subprocess.run(["g++", "-std=c++17", "-shared", "-fPIC", "-I", CSRC, os.path.join(ROOT, "tests", "train_shim.cpp"), "-o", str(so)],
-                   check=True)
-    lib = C.CDLL(str(so))
+    lib = host_shim(tmp_path_factory, "train")
     lib.adam_scalars.argtypes = [C.c_uint64, C.c_float, C.c_void_p]
     lib.adam_count_twice.argtypes = [C.c_uint64, C.c_float, C.c_void_p]
     lib.adam_count_twice.restype = C.c_uint64

@@ -10,6 +10,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from windgym_amd import presets
+from windgym_amd.binding import HOOK_ENV  # noqa: F401  (plan hook name -> WG_* variable: Case.hooks)
 from windgym_amd.config import EnvConfig
 from windgym_amd.turbine import V80
 
@@ -38,9 +39,6 @@ ALL_KEYS = K_FLOW_KEYS + K_FLOW_ENV_KEYS + K_FLOW_ENVB_KEYS
 # Keys no config and hook brings the plan to select, with the evidence from the shim: none.  (A key listed here is left out of
 # the equality test_variant_census.py asserts, nothing else.)
 UNREACHABLE = {}
-
-HOOK_ENV = {"flow_block": "WG_FLOW_BLOCK", "flow_env": "WG_FLOW_ENV", "env_wpe": "WG_ENV_WPE", "env_split": "WG_ENV_SPLIT",
-            "step_fused": "WG_STEP_FUSED", "sums": "WG_SUMS"}
 
 BOX_DIMS, BOX_SPACING, BOX_SEED = (256, 64, 32), (3.0, 3.0, 3.0), 1234      # the Mann box of tests/test_gpu_parity.py
 

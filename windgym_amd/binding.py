@@ -6,6 +6,7 @@ the built library or without a GPU raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -26,6 +27,37 @@ if _HOOKS and os.environ.get("WG_LIB"):
 _NOCHECK = bool(_HOOKS and os.environ.get("WG_NOCHECK"))
 if _NOCHECK:
     print("[windgym] WG_DEBUG_HOOKS: WG_NOCHECK set — HipBatch.check() does not read the device error word", file=sys.stderr)
+# The library's own hooks (wg_api.hip: wg_hooks_read), by the name of the WgHooks field each one fills: what selects a kernel
+# variant or a step path.  The first ten are the plan's integer hooks in the order of tests/plan_shim.cpp's array.
+HOOK_ENV = {
+    "flow_block": "WG_FLOW_BLOCK", "flow_res": "WG_FLOW_RES", "flow_env": "WG_FLOW_ENV", "env_wpe": "WG_ENV_WPE",
+    "env_split": "WG_ENV_SPLIT", "step_fused": "WG_STEP_FUSED", "sums": "WG_SUMS", "lds_pad": "WG_LDS_PAD", "lf_cap": "WG_LF_CAP",
+    "pstride_pad": "WG_PSTRIDE_PAD", "step_graph": "WG_STEP_GRAPH", "share_dev": "WG_ENV_SHARE_DEV",
+    "first_obs_gl_only": "WG_FIRST_OBS_GL_ONLY", "no_box8": "WG_NO_BOX8",
+}
+# ... and the two that select nothing: WG_DEBUG prints the plan of a handle, WG_TIMELINE_OUT names the file of a -DWG_TIMELINE build
+HOOK_ENV_DIAGNOSTIC = {"debug": "WG_DEBUG", "timeline_out": "WG_TIMELINE_OUT"}
+
+
+@contextlib.contextmanager
+def debug_hooks(mapping):
+    """The given WG_* variables for the length of the block (the library reads them at wg_create, WG_NO_BOX8 again in the box
+    setters); afterwards every one is what it was before — its old value or unset — whatever happened inside.  Refuses where
+    WG_DEBUG_HOOKS is not "1": the library would ignore the hooks and the caller would measure or test the default kernel."""
+    if mapping and os.environ.get("WG_DEBUG_HOOKS") != "1":
+        raise WindGymHipError(f"debug_hooks({sorted(mapping)}): WG_DEBUG_HOOKS is not 1 in the environment, the library ignores its hooks")
+    before = {k: os.environ.get(k) for k in mapping}
+    os.environ.update({k: str(v) for k, v in mapping.items()})
+    try:
+        yield
+    finally:
+        for k, v in before.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 UINT64_MAX = 0xFFFFFFFFFFFFFFFF
 
 # every symbol include/windgym_hip.h declares (tests check the built library exports all of them)
