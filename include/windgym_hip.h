@@ -673,6 +673,53 @@ int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared*
                          int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
 /* -----------------------------------------------------------------------------------------------------------------
+ * Behaviour cloning: a SUPERVISED loss on the same handle — the optimiser's Adam state, its scratch and wg_ppo_apply are the
+ * ones above, and k_bc_grad is k_ppo_grad's forward and backward with another loss head (windgym_amd/csrc/wg_ppo.hip).  The
+ * expert's actions come from wg_expert_labels below.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define WG_BC_MSE 0
+#define WG_BC_NLL 1
+
+typedef struct wg_bc_batch {
+    const float* obs;        /* [n_rows, n_in]  */
+    const float* target;     /* [n_rows, n_out] the expert's actions */
+    const float* returns;    /* [n_rows], or NULL: no critic term    */
+    int64_t n_rows;
+} wg_bc_batch;
+
+typedef struct wg_bc_hyper {
+    int32_t loss;            /* WG_BC_MSE, WG_BC_NLL */
+    float ent_coef, vf_coef; /* ent_coef: WG_BC_NLL only; vf_coef: only with returns */
+} wg_bc_hyper;
+
+typedef struct wg_bc_stats {       /* means over the minibatch; mse, nll, entropy and mean_abs_err whichever loss was chosen */
+    float loss, mse, nll, entropy, v_loss, mean_abs_err, reserved[2];
+} wg_bc_stats;
+
+/* One minibatch, loss and gradient only; the rows are chosen as wg_ppo_grad chooses them (index_dev[0 .. n-1] with entries
+ * outside [0, n_rows) skipped, or first .. first + n - 1; every mean divides by n).  With mean = the actor's output, logp and H
+ * as wg_ppo_grad defines them (`target` in place of `raw`):
+ *   mse = mean_rows((1 / n_out) sum_j (mean_j - target_j)^2),   nll = -mean_rows(logp(target)),   entropy = H,
+ *   mean_abs_err = mean_rows((1 / n_out) sum_j |mean_j - target_j|),   v_loss = mean_rows((returns - V)^2) (0 without returns),
+ *   WG_BC_MSE: loss = mse                       — the gradient of every log_std entry is exactly 0.0f;
+ *   WG_BC_NLL: loss = nll - ent_coef * H;
+ *   with returns both add vf_coef * v_loss; without, every critic entry of grad_out is exactly 0.0f (the critic's workgroups are
+ *   not launched) and v_loss is 0 — also on a handle whose scratch an earlier wg_ppo_grad or wg_bc_grad filled.
+ * Deterministic as wg_ppo_grad.  WG_ERR_INVALID: null / out-of-range arguments, an unknown loss, a split policy
+ * (wg_policy_create_vf) — nothing is enqueued.                                                                          */
+int wg_bc_grad(wg_ppo o, const float* params_dev, const wg_bc_batch* batch, const int32_t* index_dev, int64_t first, int n,
+               const wg_bc_hyper* hp, float* grad_out, wg_bc_stats* stats_out, void* stream);
+
+/* n_epochs passes over the batch in minibatches of batch_size rows (the last one shorter), as wg_ppo_update walks them:
+ * perm_dev int32[n_epochs, n_rows], stats_out (device, may be NULL) wg_bc_stats[n_epochs, n_mb], n_mb = ceil(n_rows / batch_size).
+ * Bit-identical to
+ *     for e in 0 .. n_epochs-1:  for k in 0 .. n_mb-1:
+ *         wg_bc_grad(o, params_dev, batch, perm_dev + e * n_rows + k * batch_size, 0, min(batch_size, n_rows - k * batch_size),
+ *                    hp, g, stats_out + e * n_mb + k);   wg_ppo_apply(o, params_dev, g, lr, max_grad_norm)                      */
+int wg_bc_update(wg_ppo o, float* params_dev, const wg_bc_batch* batch, const int32_t* perm_dev, int n_epochs, int batch_size,
+                 const wg_bc_hyper* hp, float lr, float max_grad_norm, wg_bc_stats* stats_out, void* stream);
+
+/* -----------------------------------------------------------------------------------------------------------------
  * Populations: P policies of ONE architecture collected and trained in the kernel launches of one (seeds of a result,
  * a sweep of gamma / learning rate / ent_coef: longer_steps_example.py + submit.sh run such sweeps as job arrays).
  * A population is P existing handles plus a small object that lets the kernels find them; the members stay ordinary
@@ -791,6 +838,33 @@ int wg_curriculum_shape(wg_curriculum c, int T,
         float* yaw_diff_out,            /* [T, B]    or NULL: d of every step                                */
         float* yaw_out,                 /* [T, B, N] or NULL: y of every step                                */
         void* stream);
+
+/* The expert's actions for a rollout of T steps on `h` (behaviour cloning from the yaw optimiser; wg_bc_update fits a policy to
+ * them): ONE launch of k_expert_labels, one thread per env walking its T steps, asynchronous on `stream`, allocates nothing.
+ * For step t, env b, turbine i:  prev = yaw0 for t = 0, else yaw_after[t - 1] — the yaw the observation of step t belongs to, a
+ * new episode's initial yaw after a reset;  g = the env's running target in targets_dev, which becomes row ep_row_dev[t, b] of
+ * ep_target_dev AFTER step t where truncated_dev[t, b] != 0 and that entry is >= 0 (k_curriculum's order).  The label is the
+ * action that the env's actuation rule (yaw_min / yaw_max / yaw_step and the action method of `h`, as floats widened to double)
+ * turns into the largest move towards g, computed in double and rounded once:
+ *     WG_ACT_WIND:  a = (g - yaw_min) / (yaw_max - yaw_min) * 2 - 1        WG_ACT_YAW:  a = clamp((g - prev) / yaw_step, -1, 1)
+ * yaw_diff_out[t, b] = (sum_i |prev_i - g_i|, in index order, in double) / N.  targets_dev is read and updated in place: after the
+ * call it is what the next rollout starts from.  An ep_row_dev entry >= C is skipped and latched in err_dev (int32[4], device,
+ * zeroed by the caller once; may be NULL: not latched), as wg_curriculum_shape latches it: wg_expert_labels_check synchronises
+ * the device and returns WG_ERR_INVALID once, naming ep_row_dev, t, b and the entry.  WG_ERR_INVALID, nothing enqueued: a null
+ * required buffer (ep_target_dev may be NULL with C == 0), T < 0, C < 0, a buffer off the handle's device.  T == 0 does nothing. */
+int wg_expert_labels(wg_handle h, int T,
+        const float* yaw0_dev,          /* [B, N]                                                            */
+        const float* yaw_after_dev,     /* [T, B, N] WG_INFO_YAW_AGENT recorded per step (AFTER an autoreset) */
+        const uint8_t* truncated_dev,   /* [T, B]                                                            */
+        const int32_t* ep_row_dev,      /* [T, B]    -1, or the row of ep_target that applies from step t + 1 */
+        const double* ep_target_dev,    /* [C, N]                                                            */
+        int C,
+        double* targets_dev,            /* [B, N]    the running targets, in and out                         */
+        float* labels_out,              /* [T, B, N]                                                         */
+        float* yaw_diff_out,            /* [T, B]    or NULL                                                 */
+        int32_t* err_dev,               /* [4]       or NULL                                                 */
+        void* stream);
+int wg_expert_labels_check(wg_handle h, int32_t* err_dev);
 
 /* -----------------------------------------------------------------------------------------------------------------
  * VecNormalize: running observation / return statistics for PPO, restated from stable-baselines3 2.x

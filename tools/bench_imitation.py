@@ -1,0 +1,227 @@
+#!/usr/bin/env python
+"""Behaviour cloning on the device: one iteration of ``BehaviorCloning.learn`` and its parts, and the supervised update beside
+PPO's — one JSON line.
+
+Workloads of tools/bench_ppo.py: cfg2 (4x4 farm, 16 turbines, `--envs` 4096 by default) or, with --multi, the 3x3 preset with ONE
+policy shared by the turbines (2048 envs, rows = agent rows); SB3's default MlpPolicy shape, T = `--n-steps` steps per rollout,
+`--epochs` epochs, minibatches of `--batch-size` rows (default: a quarter of the rollout).  Legs, each warmed up, then timed
+`--reps` times between two device synchronisations (median, and every sample):
+
+  iteration      ``learn`` end to end, log_interval=None                                     (ms per iteration)
+  parts          ``collect(timing=...)``: rollout / serial_refine (with the number of conditions C) / labels (k_expert_labels) /
+                 plumbing, then the update (wg_bc_update), with device synchronisations between the parts
+  update_bc      ONE wg_bc_update, actor only (no returns), from the same starting weights and a zeroed Adam every time
+  update_bc_vf   the same with returns (the critic's workgroups run too)
+  update_ppo     ONE wg_ppo_update on the same policy, rows, minibatch size, epochs and permutations
+the three updates ALTERNATING in one process.  The statement checked: update_bc is not slower than update_ppo (it does a subset of
+its work: no critic workgroups, no advantage statistics launch).
+
+With --effect the tool records what cloning does instead, on the "wind" env of `presets.env1_config()` (`--envs` 256 by default): mean_yaw_diff
+(mean distance to the expert's yaws over a deterministic rollout of `--n-steps` steps, degrees) and mean_episode_power of that
+rollout before cloning, after `--iterations` iterations, and for ``PyWakeVecAgent`` stepped through the same env — each on a fresh env
+of the same seed, so the three see the same winds and episodes.  The preset's observation holds rolling-mean wind speeds and yaws and
+NO wind direction, which the expert's yaws are a function of; `--observe-wd` switches the wind-direction sensors on.
+
+usage: python tools/bench_imitation.py [--envs N] [--n-steps 128] [--epochs 4] [--reps 5] [--multi] [--effect [--iterations 40] [--observe-wd]]
+"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def effect(args, torch, dev):
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.imitation import BehaviorCloning
+    from windgym_amd.parallel import METRIC_NAMES, derive
+    from windgym_amd.steady import PyWakeVecAgent
+    from windgym_amd.turbine import V80
+    B, T = args.envs or 256, args.n_steps
+
+    cfg = presets.env1_config()
+    if args.observe_wd:                                     # the preset observes wind speeds and yaws only: add the wind direction
+        cfg["mes_level"].update(turb_wd=True, farm_wd=True)
+        cfg["wd_mes"].update(wd_current=True)
+
+    def env():
+        v = WindFarmVecEnv(V80(), B, yaml_dict=copy.deepcopy(cfg), seed=1234, device=0, as_torch=True, turbtype="None", n_passthrough=1,
+                           n_rotor_pts=16)
+        v.reset(seed=1234)
+        return v
+
+    def measure(bc):
+        """a deterministic rollout of the policy on the trainer's env: the labels' yaw_diff and the episode metrics of exactly it"""
+        bc.venv.batch.metrics(reset_after=True)
+        det, bc.deterministic = bc.deterministic, True
+        out = bc.collect()
+        bc.deterministic = det
+        m = derive(bc.venv.batch.metrics(reset_after=True).double().cpu().numpy()[:len(METRIC_NAMES)])
+        return {"mean_yaw_diff": float(out["yaw_diff"].double().mean()), "mean_episode_power": m["mean_episode_power"],
+                "n_episodes": m["n_episodes"], "mean_step_reward": m["mean_step_reward"]}
+
+    v = env()
+    assert v.cfg.ActionMethod == "wind"
+    bc = BehaviorCloning("MlpPolicy", v, n_steps=T, n_epochs=args.epochs, seed=1234)
+    res = {"metric": "behaviour cloning from the yaw optimiser, env1 preset ('wind' actions) x %d envs, deterministic rollouts of %d steps" % (B, T),
+           "envs": B, "n_steps": T, "epochs": args.epochs, "iterations": args.iterations, "expert": bc.expert, "loss": bc.loss,
+           "observe_wd": bool(args.observe_wd), "obs_dim": int(v.batch.obs_dim)}
+
+    def fresh_measure():
+        """the policy as it is now on a FRESH env (same seed: the same winds and episodes for every measurement)"""
+        u = env()
+        m = BehaviorCloning(bc.policy, u, n_steps=T, n_epochs=1, seed=1234)
+        out = measure(m)
+        u.batch.check()
+        m.close(); u.close()
+        return out
+
+    res["before"] = fresh_measure()
+    bc.learn(args.iterations * T * B, log_interval=max(1, args.iterations // 8))
+    res["log"] = [{k: round(r[k], 6) for k in ("iteration", "loss", "mean_abs_err", "mean_yaw_diff")} for r in bc.log]
+    res["after"] = fresh_measure()
+    # the expert itself through a fresh env of the same seed: its yaw_diff is measured against its own
+    # targets by the same kernel (a twin trainer that only labels; its policy never acts)
+    w = env()
+    ref = BehaviorCloning("MlpPolicy", w, n_steps=T, n_epochs=1, seed=1234)
+    agent = PyWakeVecAgent(env=w, yaw_max=w.cfg.yaw_max, yaw_min=w.cfg.yaw_min)
+    w.batch.metrics(reset_after=True)
+    yaw0 = w.batch.info("yaw_agent").clone()
+    yaws, truncs, winds = [], [], []
+    for _ in range(T):
+        a, _ = agent.predict()
+        _, _, _, tr, _ = w.step(a)
+        yaws.append(w.batch.info("yaw_agent").clone()); truncs.append(w.batch.truncated.clone()); winds.append(w.batch.info("wind_f64").clone())
+    out = dict(truncated=torch.stack(truncs).contiguous(), wind_f64=torch.stack(winds).contiguous())
+    from windgym_amd.curriculum import new_episode_targets
+    n_new, ep_target = new_episode_targets(torch, out, ref._ep_row, ref._optimize, ref._no_targets)
+    ref._lab.labels(T, yaw0, torch.stack(yaws).contiguous(), out["truncated"], ref._ep_row, ep_target, n_new, ref.targets, ref._labels,
+                    ref._yaw_diff)
+    m = derive(w.batch.metrics(reset_after=True).double().cpu().numpy()[:len(METRIC_NAMES)])
+    res["pywake_agent"] = {"mean_yaw_diff": float(ref._yaw_diff.double().mean()), "mean_episode_power": m["mean_episode_power"],
+                           "n_episodes": m["n_episodes"], "mean_step_reward": m["mean_step_reward"]}
+    v.batch.check(); w.batch.check()
+    for x in (bc, ref):
+        x.close(); x.policy.close()
+    v.close(); w.close()
+    print(json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=None, help="default: 4096 (--multi: 2048, --effect: 256)")
+    ap.add_argument("--multi", action="store_true", help="the 3x3 preset: one policy shared by the turbines")
+    ap.add_argument("--n-steps", type=int, default=128)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--preroll", type=int, default=300)
+    ap.add_argument("--effect", action="store_true", help="record mean_yaw_diff / mean_episode_power before and after cloning and for the expert")
+    ap.add_argument("--iterations", type=int, default=40, help="with --effect: iterations of learn")
+    ap.add_argument("--observe-wd", action="store_true", help="with --effect: switch the preset's wind-direction sensors on")
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_imitation.py: no HIP device (there is no CPU path to time)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    if args.effect:
+        return effect(args, torch, dev)
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv, WindFarmVecEnvMulti
+    from windgym_amd.imitation import BehaviorCloning
+    from windgym_amd.turbine import V80
+    B, T, E = args.envs or (2048 if args.multi else 4096), args.n_steps, args.epochs
+    if args.multi:
+        venv = WindFarmVecEnvMulti(V80(), B, yaml_dict=presets.multi_3x3_config(), seed=1234, device=0, turbtype="None", n_passthrough=5,
+                                   n_rotor_pts=16)
+    else:
+        venv = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
+                              n_passthrough=5, n_rotor_pts=16)
+    venv.reset(seed=1234)
+    bc = BehaviorCloning("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=args.batch_size, seed=1234)
+    pol, n_rows, bs = bc.policy, bc.n_rows, bc.batch_size
+    zero = torch.zeros((B, venv.n_turb), device=dev)
+    for _ in range(args.preroll):
+        venv.step(zero)
+    bc.reset_targets()
+    med = statistics.median
+    res = {"metric": "behaviour cloning on the device, %s x %d envs x %d steps, %d epochs, one GPU"
+                     % ("3x3 farm, one policy shared by 9 agents" if args.multi else "16-turbine farm", B, T, E),
+           "envs": B, "n_steps": T, "epochs": E, "rows": n_rows, "minibatch": bs, "reps": args.reps, "expert": bc.expert}
+    # the iteration, end to end
+    iters = 3
+    bc.learn(T * B, log_interval=None)
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        bc.learn(iters * T * B, log_interval=None)
+        torch.cuda.synchronize(dev)
+        ms.append((time.perf_counter() - t0) * 1e3 / iters)
+    res["iteration"] = {"ms_per_iteration": med(ms), "ms_all": [round(x, 3) for x in ms], "env_steps_per_s": B * T / (med(ms) * 1e-3)}
+    # its parts
+    parts = []
+    for _ in range(args.reps):
+        d = {}
+        out = bc.collect(timing=d)
+        t0 = d.pop("_t")
+        bc.train(out, 1e-3)
+        torch.cuda.synchronize(dev)
+        d["update"] = (time.perf_counter() - t0) * 1e3
+        d["C"] = bc.last_n_targets
+        parts.append({k: round(v, 3) if k != "C" else v for k, v in d.items()})
+    res["parts_ms"] = {k: med([p.get(k, 0.0) for p in parts]) for k in ("rollout", "serial_refine", "labels", "plumbing", "update", "C")}
+    res["parts_all"] = parts
+    # one update of each kind on the same rows: a plain rollout's, with its GAE for PPO's columns; the expert's actions are the
+    # labels of the rollout before it (the time does not depend on their values)
+    roll = venv.rollout(pol, T, record=("yaw_agent", "wind_f64"))
+    adv, ret = bc.opt.gae(roll["reward"], roll["value"], roll["final_value"], roll["truncated"], 0.99, 0.95)
+    O, N = pol.n_in, pol.n_out
+    obs, raw, lpo = roll["obs"][:T].reshape(-1, O).clone(), roll["raw"].reshape(-1, N).clone(), roll["logp"].reshape(-1).clone()
+    adv, ret = adv.reshape(-1).clone(), ret.reshape(-1).clone()
+    labels = bc._labels.view(-1, N).clone()
+    perm = torch.stack([torch.randperm(n_rows, device=dev) for _ in range(E)]).to(torch.int32).contiguous()
+    start = pol.params.clone()
+    zeros = torch.zeros(2 * start.numel()).numpy()
+
+    def fresh():
+        with torch.no_grad():
+            pol.params.copy_(start)
+        pol.sync()
+        bc.opt.load_state(zeros, 0)
+
+    legs = {"update_bc": lambda: bc.opt.bc_update(obs, labels, None, perm, bs, learning_rate=1e-3, max_grad_norm=0.5),
+            "update_bc_vf": lambda: bc.opt.bc_update(obs, labels, ret, perm, bs, vf_coef=0.5, learning_rate=1e-3, max_grad_norm=0.5),
+            "update_ppo": lambda: bc.opt.update(obs, raw, lpo, adv, ret, perm, bs, learning_rate=3e-4, max_grad_norm=0.5)}
+    for fn in legs.values():
+        fresh(); fn()
+    torch.cuda.synchronize(dev)
+    ms = {k: [] for k in legs}
+    for _ in range(args.reps):                               # every leg once per round: the legs alternate
+        for k, fn in legs.items():
+            fresh()
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    for k in legs:
+        res[k] = {"ms": med(ms[k]), "min": round(min(ms[k]), 3), "max": round(max(ms[k]), 3), "ms_all": [round(x, 3) for x in ms[k]],
+                  "trained_samples_per_s": n_rows * E / (med(ms[k]) * 1e-3)}
+    res["update_bc_over_update_ppo"] = res["update_bc"]["ms"] / res["update_ppo"]["ms"]
+    fresh()
+    venv.batch.check()
+    bc.close(); pol.close(); venv.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

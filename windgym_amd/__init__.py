@@ -41,6 +41,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name == "YawCurriculum":
         from .curriculum import YawCurriculum
         return YawCurriculum
+    if name == "BehaviorCloning":
+        from .imitation import BehaviorCloning
+        return BehaviorCloning
     if name == "VecNormalize":
         from .normalize import VecNormalize
         return VecNormalize

@@ -72,6 +72,7 @@ ABI_SYMBOLS = (
     "wg_pop_create", "wg_pop_destroy", "wg_pop_act", "wg_pop_rollout", "wg_gae_pop", "wg_pop_update",
     "wg_curriculum_create", "wg_curriculum_destroy", "wg_curriculum_get_state", "wg_curriculum_set_state", "wg_curriculum_set_targets",
     "wg_curriculum_shape",
+    "wg_bc_grad", "wg_bc_update", "wg_expert_labels", "wg_expert_labels_check",
     "wg_norm_create", "wg_norm_destroy", "wg_norm_get_state", "wg_norm_set_state", "wg_norm_set_training", "wg_norm_reset_returns",
     "wg_norm_obs", "wg_norm_reward", "wg_rollout_norm",
     "wg_lstm_create", "wg_lstm_destroy", "wg_lstm_n_params", "wg_lstm_set_params", "wg_lstm_step", "wg_lstm_act", "wg_rollout_lstm",
@@ -150,6 +151,18 @@ class CLstmPpoBatch(C.Structure):
                 ("episode_start", C.c_void_p), ("lstm_state0", C.c_void_p), ("T", C.c_int32), ("B", C.c_int32)]
 
 
+class CBcBatch(C.Structure):
+    """wg_bc_batch"""
+    _fields_ = [("obs", C.c_void_p), ("target", C.c_void_p), ("returns", C.c_void_p), ("n_rows", C.c_int64)]
+
+
+class CBcHyper(C.Structure):
+    """wg_bc_hyper"""
+    _fields_ = [("loss", C.c_int32), ("ent_coef", C.c_float), ("vf_coef", C.c_float)]
+
+
+BC_LOSS = {"mse": 0, "nll": 1}          # WG_BC_MSE / WG_BC_NLL
+BC_STATS = ("loss", "mse", "nll", "entropy", "v_loss", "mean_abs_err", "reserved0", "reserved1")   # wg_bc_stats
 PPO_STATS = ("pi_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "loss", "adv_mean", "adv_std")   # wg_ppo_stats
 
 
@@ -240,6 +253,12 @@ def load_library():
                                 C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     L.wg_ppo_grad_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_grad.argtypes[3:]
     L.wg_ppo_update_shared.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatchShared)] + L.wg_ppo_update.argtypes[3:]
+    L.wg_bc_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CBcBatch), C.c_void_p, C.c_int64, C.c_int,
+                             C.POINTER(CBcHyper), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_bc_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CBcBatch), C.c_void_p, C.c_int, C.c_int,
+                               C.POINTER(CBcHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.wg_expert_labels.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
+    L.wg_expert_labels_check.argtypes = [C.c_void_p, C.c_void_p]
     L.wg_pop_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
     L.wg_pop_destroy.argtypes = [C.c_void_p]
     L.wg_pop_act.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
@@ -785,6 +804,39 @@ class Curriculum:
             ptrs.append(None if x is None else x.data_ptr())
         _chk(self.L.wg_curriculum_shape(self._h, T, *ptrs[:6], int(n_targets), ptrs[6], float(momentum), *ptrs[7:], self.batch._stream()),
              "wg_curriculum_shape")
+
+
+class ExpertLabels:
+    """wg_expert_labels on one :class:`HipBatch`: the expert's action for every step of a rollout, from the yaws the rollout
+    recorded and the Serial-Refine targets of its episodes (include/windgym_hip.h states the rule;
+    ``windgym_amd.imitation.BehaviorCloning`` is the user-facing class).  It owns the latch of a bad ``ep_row`` entry; the running
+    target table is the caller's.  ``labels`` enqueues on torch's current stream and synchronises nothing; ``check`` synchronises."""
+
+    def __init__(self, batch: HipBatch):
+        self.batch, self.L, self.torch = batch, batch.L, batch.torch
+        self.B, self.N = batch.B, batch.N
+        self._err = self.torch.zeros(4, dtype=self.torch.int32, device=batch.device)
+
+    def labels(self, T, yaw0, yaw_after, truncated, ep_row, ep_target, n_targets, targets, labels, yaw_diff=None):
+        """``targets`` float64 ``[B, N]`` is read and updated in place; ``labels`` float32 ``[T, B, N]`` and ``yaw_diff [T, B]``
+        (``None`` = NULL) are written.  Sizes are checked here, values by the library."""
+        t, B, N, T = self.torch, self.B, self.N, int(T)
+        ptrs = []
+        for name, x, dtype, numel in (("yaw0", yaw0, t.float32, B * N), ("yaw_after", yaw_after, t.float32, T * B * N),
+                                      ("truncated", truncated, t.uint8, T * B), ("ep_row", ep_row, t.int32, T * B),
+                                      ("ep_target", ep_target, t.float64, int(n_targets) * N), ("targets", targets, t.float64, B * N),
+                                      ("labels", labels, t.float32, T * B * N), ("yaw_diff", yaw_diff, t.float32, T * B)):
+            if x is not None and not (t.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= max(numel, 0)):
+                raise ValueError(f"labels(): {name} must be a contiguous {dtype} CUDA tensor of at least {numel} elements")
+            ptrs.append(None if x is None else x.data_ptr())
+        _chk(self.L.wg_expert_labels(self.batch._h, T, *ptrs[:5], int(n_targets), *ptrs[5:], self._err.data_ptr(), self.batch._stream()),
+             "wg_expert_labels")
+        return labels
+
+    def check(self):
+        """``ValueError`` once, naming ``ep_row_dev``, when an earlier :meth:`labels` met an ``ep_row`` entry that was no row of
+        ``ep_target`` (the kernel skipped it).  Synchronises."""
+        _chk(self.L.wg_expert_labels_check(self.batch._h, self._err.data_ptr()), "wg_expert_labels_check")
 
 
 class Norm:

@@ -127,6 +127,43 @@ __global__ __launch_bounds__(64) void k_curriculum(const CurP p, const CurState 
     s.n[b] = n; s.osc[b] = osc; s.cum[b] = cum; s.last[b] = last;
 }
 
+// The expert's action for every step of a rollout (wg_expert_labels): the action that cur_adjust_yaw turns into the largest move
+// from the yaw the step's observation belongs to towards the env's running target — the inverse of the actuation rule, in double,
+// rounded once.  One thread per env walks t as k_curriculum does, with its order of target switches; `g` is the caller's table.
+__global__ __launch_bounds__(64) void k_expert_labels(const CurP p, double* __restrict__ targets, int* __restrict__ err,
+                                                      const float* __restrict__ yaw0, const float* __restrict__ yaw_after,
+                                                      const uint8_t* __restrict__ truncated, const int32_t* __restrict__ ep_row,
+                                                      const double* __restrict__ ep_target, float* __restrict__ labels,
+                                                      float* __restrict__ yaw_diff) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= p.B) return;
+    const int N = p.N;
+    const size_t sb = (size_t)b * N;
+    double* const g = targets + sb;
+    const double dN = (double)N, lo = (double)p.yaw_min, hi = (double)p.yaw_max, step = (double)p.yaw_step;
+    for (int t = 0; t < p.T; ++t) {
+        const size_t row = (size_t)t * p.B + b;
+        const float* const prev = t == 0 ? yaw0 + sb : yaw_after + (row - p.B) * N;
+        double d = 0.0;
+        for (int i = 0; i < N; ++i) {
+            const double y = (double)prev[i], gi = g[i];
+            const double a = p.action_method == WG_ACT_YAW ? fmin(fmax((gi - y) / step, -1.0), 1.0) : (gi - lo) / (hi - lo) * 2.0 - 1.0;
+            labels[row * N + i] = (float)a;
+            d += fabs(y - gi);
+        }
+        if (yaw_diff) yaw_diff[row] = (float)(d / dN);
+        if (truncated[row]) {
+            const int r = ep_row[row];
+            if (r >= p.C) {
+                if (err && atomicCAS(&err[0], 0, 1) == 0) { err[1] = t; err[2] = b; err[3] = r; }
+            } else if (r >= 0) {
+                const double* const src = ep_target + (size_t)r * N;
+                for (int i = 0; i < N; ++i) g[i] = src[i];
+            }
+        }
+    }
+}
+
 
 }  // namespace
 
@@ -278,4 +315,66 @@ extern "C" int wg_curriculum_shape(wg_curriculum c, int T, const float* yaw0_dev
                        yaw_after_dev, truncated_dev, ep_row_dev, ep_target_dev, weight_dev, reward_dev, shaped_out, yaw_diff_out, yaw_out);
     WG_HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// expert labels (windgym_hip.h: wg_expert_labels) — no handle of its own: the actuation rule is read from `h`, the running
+// targets and the latch of a bad ep_row entry are the caller's
+// ---------------------------------------------------------------------------------------------------------------------
+static int lab_on_device(int device, const void* ptr, const char* name) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return wg_fail(WG_ERR_INVALID, std::string("wg_expert_labels: ") + name + " is not a device pointer");
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != device)
+        return wg_fail(WG_ERR_INVALID, std::string("wg_expert_labels: ") + name + " is not memory of device " + std::to_string(device) +
+                                        ", the handle's device");
+    return 0;
+}
+
+extern "C" int wg_expert_labels(wg_handle h, int T, const float* yaw0_dev, const float* yaw_after_dev, const uint8_t* truncated_dev,
+                                const int32_t* ep_row_dev, const double* ep_target_dev, int C, double* targets_dev, float* labels_out,
+                                float* yaw_diff_out, int32_t* err_dev, void* stream) {
+    WgActuation a;
+    if (!h) return wg_fail(WG_ERR_INVALID, "wg_expert_labels: null handle");
+    if (int rc = wg_handle_actuation_(h, &a)) return rc;
+    if (T < 0) return wg_fail(WG_ERR_INVALID, "wg_expert_labels: T must be >= 0, got " + std::to_string(T));
+    if (C < 0) return wg_fail(WG_ERR_INVALID, "wg_expert_labels: C must be >= 0, got " + std::to_string(C));
+    const struct { const void* ptr; const char* name; bool required; } args[] = {
+        {yaw0_dev, "yaw0_dev", true}, {yaw_after_dev, "yaw_after_dev", true}, {truncated_dev, "truncated_dev", true},
+        {ep_row_dev, "ep_row_dev", true}, {ep_target_dev, "ep_target_dev", C > 0}, {targets_dev, "targets_dev", true},
+        {labels_out, "labels_out", true}, {yaw_diff_out, "yaw_diff_out", false}, {err_dev, "err_dev", false}};
+    for (const auto& g : args) {
+        if (!g.ptr) {
+            if (g.required) return wg_fail(WG_ERR_INVALID, std::string("wg_expert_labels: ") + g.name + " is null");
+            continue;
+        }
+        if (int rc = lab_on_device(a.device, g.ptr, g.name)) return rc;
+    }
+    if (T == 0) return 0;
+    if (int rc = wg_use_device(a.device)) return rc;
+    CurP p;
+    p.B = a.B; p.N = a.N; p.T = T; p.C = C; p.action_method = a.action_method;
+    p.yaw_min = a.yaw_min; p.yaw_max = a.yaw_max; p.yaw_step = a.yaw_step;
+    p.yaw_max_d = a.yaw_max_d; p.momentum = 0.0;
+    hipLaunchKernelGGL(k_expert_labels, dim3((p.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, p, targets_dev, (int*)err_dev, yaw0_dev,
+                       yaw_after_dev, truncated_dev, ep_row_dev, ep_target_dev, labels_out, yaw_diff_out);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_expert_labels_check(wg_handle h, int32_t* err_dev) {
+    WgActuation a;
+    if (!h || !err_dev) return wg_fail(WG_ERR_INVALID, "wg_expert_labels_check: null argument");
+    if (int rc = wg_handle_actuation_(h, &a)) return rc;
+    if (int rc = lab_on_device(a.device, err_dev, "err_dev")) return rc;
+    if (int rc = wg_use_device(a.device)) return rc;
+    WG_HIPCHK(hipDeviceSynchronize());
+    int err[4];
+    WG_HIPCHK(hipMemcpy(err, err_dev, sizeof(err), hipMemcpyDeviceToHost));
+    if (!err[0]) return 0;
+    WG_HIPCHK(hipMemset(err_dev, 0, sizeof(err)));
+    return wg_fail(WG_ERR_INVALID, "wg_expert_labels: ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
+                                    std::to_string(err[3]) + " is not a row of ep_target_dev (C rows); the entry was skipped");
 }

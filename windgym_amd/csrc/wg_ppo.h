@@ -22,6 +22,11 @@
 #define WGT_PART_BYTES (256u << 20)   // most bytes of gradient partials (bounds g_max for very large nets)
 #define WGT_NSTAT 8               // floats of a wg_ppo_stats record
 #define WGT_BLOCK 256             // threads of the element-wise kernels (reduce, sum of squares, Adam)
+// the actor's loss head, a compile-time choice of the gradient kernel's body: PPO's clipped surrogate (k_ppo_grad*), or the
+// supervised loss of k_bc_grad, whose spart[g] holds the sums of the rows' squared error / n_out, -logp(target) and absolute error /
+// n_out (actor) and of L_v (critic, only with returns) and is read by k_bc_reduce alone
+#define WGT_HEAD_PPO 0
+#define WGT_HEAD_BC 1
 
 // LDS map of one net (offsets in floats; S = R + 1 floats per feature row, conflict-free for row- and feature-major reads)
 struct WgPpoLds {

@@ -8,6 +8,8 @@
 //                  of another input width) the critic gathers the entry's ENV row = entry / agents from a stream of its own, and
 //                  advantage / returns are indexed by env row.  agents = 1 on one stream is the plain batch.
 //   k_ppo_reduce   partials -> flat gradient + statistics record, summed in workgroup order.
+//   k_bc_grad      k_ppo_grad with the supervised loss head (behaviour cloning: MSE or -logp of the expert's actions) in place of
+//                  the clipped surrogate — the same forward, dW and dX, instantiated from the same body; k_bc_reduce is its reduce.
 //   k_ppo_sumsq / k_ppo_adam   global L2 norm, clipping, Adam on the caller's flat parameters in place.
 //
 // k_ppo_grad: a workgroup of 4 waves owns ONE net (blockIdx.y: actor / critic — the two gradients share nothing but the
@@ -152,6 +154,7 @@ struct WgPpoArgs {
     float* part;               // [G][n_flat]
     float* spart;              // [G][4]
     float* dh[2];              // k_ppo_grad_dh only: per net [n_total][the net's input width] d loss / d obs rows (wg_lstm_ppo.hip)
+    int32_t bc_loss;           // k_bc_grad only: WG_BC_MSE / WG_BC_NLL (there `raw` holds the expert's actions)
 };
 
 // (`a`: what the launch's workgroups share; the remaining arguments are `a`'s own for one policy, the member's for a population)
@@ -160,7 +163,10 @@ struct WgPpoArgs {
 // With DH = false the code is what it was before the flag: the same instructions, the same bits.
 // `rw`: the rows a workgroup reads and the dh rows it writes (obs, raw, logp_old, adv, ret, dh) — `a` itself, or the member's row of
 // a recurrent population's table (WgPopHeadRows), read where it lies: the nets index obs and dh by blockIdx.y.
-template <bool DH, class Rows>
+// HEAD: the actor's loss head (wg_ppo.h) — WGT_HEAD_PPO the clipped surrogate, WGT_HEAD_BC the supervised loss of k_bc_grad, which
+// reads the expert's actions where PPO reads `raw` and needs neither logp_old nor the advantages.  A compile-time choice as DH is
+// one: with WGT_HEAD_PPO the code is what it was before the parameter.  The critic's head, forward, dW and dX are the same for both.
+template <bool DH, int HEAD, class Rows>
 __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, const WgPpoArgs& a, const Rows& rw, const float* a_packed,
                                          const float* a_flat, const int32_t* a_index, const int a_normalize, const float a_clip,
                                          const float a_vf_coef, const float* a_advstat, float* a_part, float* a_spart) {
@@ -249,7 +255,44 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
         // ---- loss head: dZ of the head into d[0], per-row statistics into rowv ------------------------------------------
         float* hb = lds + M.act[L - 1];                    // [output][row]
         float* d0 = lds + M.d[0];
-        if (net == 0) {
+        if (HEAD == WGT_HEAD_BC && net == 0) {
+            // L = mean_rows(sum_j (mean_j - target_j)^2 / n_out)  or  -mean_rows(logp(target)): the row's thread writes dZ itself;
+            // rowv = the row's weight 1/n (0: no row), its squared error / n_out, its -logp, its absolute error / n_out
+            const int n_out = P.n_out;
+            const bool nll = a.bc_loss == WG_BC_NLL;
+            const float inv_no = 1.0f / (float)n_out;
+            if (tid < R) {
+                const int id = rid[tid];
+                float w = 0.0f, sq = 0.0f, nl = 0.0f, ab = 0.0f;
+                if (id >= 0) {
+                    w = inv_n;
+                    for (int j = 0; j < n_out; ++j) {
+                        const float ls = a_flat[P.log_std_flat + j];
+                        const float sd = expf(ls);
+                        const float e = hb[j * S + tid] - rw.raw[(size_t)id * n_out + j];
+                        const float z = -e / sd;
+                        sq += e * e;
+                        ab += fabsf(e);
+                        nl += 0.5f * z * z + ls + WGT_HALF_LOG_2PI;
+                        hb[j * S + tid] = z;
+                        d0[j * S + tid] = nll ? -(z / sd) * inv_n : 2.0f * e * inv_no * inv_n;
+                    }
+                } else {
+                    for (int j = 0; j < n_out; ++j) { hb[j * S + tid] = 0.0f; d0[j * S + tid] = 0.0f; }
+                }
+                rowv[tid] = w; rowv[32 + tid] = sq * inv_no; rowv[64 + tid] = nl; rowv[96 + tid] = ab * inv_no;
+            }
+            __syncthreads();
+            if (tid < n_out) {                              // d(-logp) / d log_std_j: sum_row (1 - z^2) / n; under MSE exactly 0, WRITTEN
+                float s = 0.0f;                             // all the same: the slot may hold what an earlier call left there
+                if (nll)
+                    for (int row = 0; row < R; ++row) { const float z = hb[tid * S + row]; s += rowv[row] * (1.0f - z * z); }
+                float* o = part + P.log_std_flat + tid;
+                *o = first ? s : *o + s;
+            }
+            if (tid == 0)
+                for (int row = 0; row < R; ++row) { st0 += rowv[32 + row]; st1 += rowv[64 + row]; st2 += rowv[96 + row]; }
+        } else if (net == 0) {
             const int n_out = P.n_out;
             if (tid < R) {
                 const int id = rid[tid];
@@ -402,19 +445,25 @@ __device__ __forceinline__ void ppo_grad(const WgPolicyP& P, const WgPpoK& K, co
 }
 
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
-    ppo_grad<false>(P, K, a, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+    ppo_grad<false, WGT_HEAD_PPO>(P, K, a, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
 }
 
 // k_ppo_grad with the input-row gradients (a.dh) as well: the heads of a recurrent policy on the LSTMs' h rows
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_dh(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
-    ppo_grad<true>(P, K, a, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+    ppo_grad<true, WGT_HEAD_PPO>(P, K, a, a, a.packed, a.flat, a.index, a.normalize, a.clip, a.vf_coef, a.advstat, a.part, a.spart);
+}
+
+// The supervised gradient (wg_bc_grad): the BC head on the expert's actions a.raw; grid (G, 2) with returns, (G, 1) — the actor's
+// workgroups alone — without.  a.logp_old, a.adv, a.advstat and the clip are not read.
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_bc_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
+    ppo_grad<false, WGT_HEAD_BC>(P, K, a, a, a.packed, a.flat, a.index, 0, 0.0f, a.vf_coef, nullptr, a.part, a.spart);
 }
 
 // grid (G, 2, P); `c` carries what the members share (the batch, n, G), the member's row the rest
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_pop(const WgPolicyP P, const WgPpoK K, const WgPpoArgs c,
                                                                  const WgPopMember* __restrict__ mt, const int64_t off) {
     const WgPopMember* __restrict__ M = mt + blockIdx.z;
-    ppo_grad<false>(P, K, c, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+    ppo_grad<false, WGT_HEAD_PPO>(P, K, c, c, M->packed, M->params, M->perm + off, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
 }
 
 // The heads of a recurrent population: grid (G, 2, P); member blockIdx.z reads ITS rows (row m of `rt`: the h rows of its LSTMs and
@@ -423,7 +472,7 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_dh_pop(const WgPoli
                                                                     const WgPopMember* __restrict__ mt,
                                                                     const WgPopHeadRows* __restrict__ rt) {
     const WgPopMember* __restrict__ M = mt + blockIdx.z;
-    ppo_grad<true>(P, K, c, rt[blockIdx.z], M->packed, M->params, nullptr, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
+    ppo_grad<true, WGT_HEAD_PPO>(P, K, c, rt[blockIdx.z], M->packed, M->params, nullptr, M->normalize && c.n > 1, M->clip, M->vf_coef, M->advstat, M->part, M->spart);
 }
 
 __global__ __launch_bounds__(1024) void k_ppo_advstat_rows_pop(const WgPopMember* __restrict__ mt, const WgPopHeadRows* __restrict__ rt,
@@ -433,6 +482,21 @@ __global__ __launch_bounds__(1024) void k_ppo_advstat_rows_pop(const WgPopMember
     ppo_advstat(rt[blockIdx.x].adv, nullptr, 0, n, n, 1, M->advstat);
 }
 
+// entry p of the partials' rows 0 .. G-1, added in index order
+__device__ __forceinline__ float ppo_part_sum(const float* __restrict__ part, const int G, const uint32_t n_flat, const uint32_t p) {
+    float s = 0.0f;
+    int g = 0;
+    for (; g + 8 <= G; g += 8) {                           // eight loads in flight, added in index order
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(g + u) * n_flat + p];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += x[u];
+    }
+    for (; g < G; ++g) s += part[(size_t)g * n_flat + p];
+    return s;
+}
+
 // partials -> flat gradient (+ the entropy term's constant gradient on log_std) and the statistics record
 __device__ __forceinline__ void ppo_reduce(const WgPolicyP& P, const float* __restrict__ part, const float* __restrict__ spart,
                                            const int G, const int n, const float vf_coef, const float ent_coef, const int normalize,
@@ -440,16 +504,7 @@ __device__ __forceinline__ void ppo_reduce(const WgPolicyP& P, const float* __re
                                            float* __restrict__ grad, float* __restrict__ stats) {
     const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
     if (p < P.n_flat) {
-        float s = 0.0f;
-        int g = 0;
-        for (; g + 8 <= G; g += 8) {                       // eight loads in flight, added in index order
-            float x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(g + u) * P.n_flat + p];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += x[u];
-        }
-        for (; g < G; ++g) s += part[(size_t)g * P.n_flat + p];
+        float s = ppo_part_sum(part, G, P.n_flat, p);
         if (p >= P.log_std_flat) s -= ent_coef;
         grad[p] = s;
     }
@@ -481,6 +536,37 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_reduce_pop(const WgPolicyP P,
     const WgPopMember* __restrict__ M = mt + blockIdx.y;
     ppo_reduce(P, M->part, M->spart, G, n, M->vf_coef, M->ent_coef, M->normalize && n > 1, M->advstat, M->params, M->grad,
                M->stats + (size_t)mb * M->stats_step);
+}
+
+// k_bc_grad's partials -> flat gradient and the wg_bc_stats record.  A reduce of its own: the four spart slots of a workgroup hold
+// BC's sums (actor: squared error, -logp, absolute error; critic: L_v), and what no workgroup wrote in THIS call is never read —
+// without returns the critic's workgroups were not launched, their rows of `part` and slot 3 hold an earlier call's values, and
+// the critic's entries [critic_from, log_std_flat) are 0.0f.  Under MSE log_std gets the sum of the G zeros the actor wrote.
+__global__ __launch_bounds__(WGT_BLOCK) void k_bc_reduce(const WgPolicyP P, const float* __restrict__ part,
+                                                          const float* __restrict__ spart, const int G, const int n,
+                                                          const uint32_t critic_from, const int has_ret, const int nll,
+                                                          const float vf_coef, const float ent_coef, const float* __restrict__ flat,
+                                                          float* __restrict__ grad, float* __restrict__ stats) {
+    const uint32_t p = blockIdx.x * WGT_BLOCK + threadIdx.x;
+    if (p < P.n_flat) {
+        float s = 0.0f;
+        if (has_ret || p < critic_from || p >= P.log_std_flat) s = ppo_part_sum(part, G, P.n_flat, p);
+        if (nll && p >= P.log_std_flat) s -= ent_coef;
+        grad[p] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int g = 0; g < G; ++g)
+            for (int k = 0; k < (has_ret ? 4 : 3); ++k) s[k] += spart[(size_t)g * 4 + k];
+        float H = 0.0f;
+        for (int j = 0; j < P.n_out; ++j) H += 0.5f + WGT_HALF_LOG_2PI + flat[P.log_std_flat + j];
+        const float inv_n = 1.0f / (float)n;
+        const float mse = s[0] * inv_n, nl = s[1] * inv_n, lv = s[3] * inv_n;
+        float loss = nll ? nl - ent_coef * H : mse;
+        if (has_ret) loss += vf_coef * lv;
+        stats[0] = loss; stats[1] = mse; stats[2] = nl; stats[3] = H; stats[4] = lv; stats[5] = s[2] * inv_n;
+        stats[6] = 0.0f; stats[7] = 0.0f;
+    }
 }
 
 // blocksq[b] = sum of squares of block b's 256 gradient entries (fixed tree)
@@ -782,7 +868,7 @@ static int t_grad(WgPpoGrad* o, const float* params_dev, const wg_ppo_batch_shar
     a.packed = o->pol->w.packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = sb->obs_vf; a.agents = sb->agents; a.raw = b->raw; a.logp_old = b->logp; a.adv = b->advantage;
     a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G; a.normalize = normalize;
     a.clip = hp->clip_range; a.vf_coef = hp->vf_coef; a.advstat = o->advstat; a.part = o->part; a.spart = o->spart;
-    a.dh[0] = dh_pi; a.dh[1] = dh_vf;
+    a.dh[0] = dh_pi; a.dh[1] = dh_vf; a.bc_loss = 0;
     if (dh_pi && dh_vf) hipLaunchKernelGGL(k_ppo_grad_dh, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
     else hipLaunchKernelGGL(k_ppo_grad, dim3(G, 2), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
     hipLaunchKernelGGL(k_ppo_reduce, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, P, o->part, o->spart, G, n, hp->vf_coef,
@@ -915,6 +1001,67 @@ extern "C" int wg_ppo_update(wg_ppo o, float* params_dev, const wg_ppo_batch* b,
     if (int rc = t_refuse_split("wg_ppo_update", o)) return rc;
     const wg_ppo_batch_shared sb = {*b, b->obs, 1};
     return update_entry("wg_ppo_update", o, params_dev, &sb, perm_dev, n_epochs, batch_size, hp, lr, max_grad_norm, stats_out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// behaviour cloning (windgym_hip.h: wg_bc_*): the supervised gradient on the wg_ppo handle — its scratch, its Adam, wg_ppo_apply
+// ---------------------------------------------------------------------------------------------------------------------
+static int bc_check(const std::string& w, wg_ppo o, const float* params_dev, const wg_bc_batch* b, const wg_bc_hyper* hp) {
+    if (!o || !params_dev || !b || !hp) return wg_fail(WG_ERR_INVALID, w + ": null argument");
+    const WgPolicyP& P = o->g.pol->P;
+    if (P.n_in_vf != P.n_in)             // as wg_ppo_grad refuses it: one obs stream of the actor's width, which the critic cannot read
+        return wg_fail(WG_ERR_INVALID, w + ": the policy's critic reads rows of " + std::to_string(P.n_in_vf) + " inputs, its actor rows of " +
+                                         std::to_string(P.n_in) + ": cloning a split policy (wg_policy_create_vf) is not implemented");
+    if (!b->obs || !b->target) return wg_fail(WG_ERR_INVALID, w + ": a batch pointer is null (only returns may be)");
+    if (b->n_rows < 1 || b->n_rows > 0x7fffffff) return wg_fail(WG_ERR_INVALID, w + ": n_rows out of range");
+    if (hp->loss != WG_BC_MSE && hp->loss != WG_BC_NLL)
+        return wg_fail(WG_ERR_INVALID, w + ": loss must be WG_BC_MSE or WG_BC_NLL, got " + std::to_string(hp->loss));
+    if (int rc = wg_use_device(o->adam.device)) return rc;
+    if (int rc = t_on_device(params_dev, o->adam.device, (w + ": params_dev").c_str())) return rc;
+    if (int rc = t_on_device(b->obs, o->adam.device, (w + ": obs").c_str())) return rc;
+    return t_on_device(b->target, o->adam.device, (w + ": target").c_str());
+}
+
+// the launches of one supervised gradient, no argument checks
+static int t_bc_grad(WgPpoGrad* o, const float* params_dev, const wg_bc_batch* b, const int32_t* index_dev, int64_t first, int n,
+                     const wg_bc_hyper* hp, float* grad_out, float* stats_out, hipStream_t st) {
+    const WgPolicyP& P = o->pol->P;
+    const int G = t_grid(o, n);
+    const int has_ret = b->returns != nullptr, nll = hp->loss == WG_BC_NLL;
+    WgPpoArgs a = {};
+    a.packed = o->pol->w.packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = b->obs; a.agents = 1; a.raw = b->target;
+    a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G;
+    a.vf_coef = hp->vf_coef; a.part = o->part; a.spart = o->spart; a.bc_loss = hp->loss;
+    hipLaunchKernelGGL(k_bc_grad, dim3(G, has_ret ? 2 : 1), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
+    hipLaunchKernelGGL(k_bc_reduce, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, P, o->part, o->spart, G, n, P.layer[1][0].w_flat,
+                       has_ret, nll, hp->vf_coef, hp->ent_coef, params_dev, grad_out, stats_out ? stats_out : o->stats);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_bc_grad(wg_ppo o, const float* params_dev, const wg_bc_batch* b, const int32_t* index_dev, int64_t first, int n,
+                          const wg_bc_hyper* hp, float* grad_out, wg_bc_stats* stats_out, void* stream) {
+    const std::string w = "wg_bc_grad";
+    if (!grad_out) return wg_fail(WG_ERR_INVALID, w + ": null argument");
+    if (int rc = bc_check(w, o, params_dev, b, hp)) return rc;
+    if (n < 1) return wg_fail(WG_ERR_INVALID, w + ": n < 1");
+    if (!index_dev && (first < 0 || first + n > b->n_rows)) return wg_fail(WG_ERR_INVALID, w + ": rows first .. first + n - 1 leave the batch");
+    return t_bc_grad(&o->g, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+}
+
+extern "C" int wg_bc_update(wg_ppo o, float* params_dev, const wg_bc_batch* b, const int32_t* perm_dev, int n_epochs, int batch_size,
+                            const wg_bc_hyper* hp, float lr, float max_grad_norm, wg_bc_stats* stats_out, void* stream) {
+    const std::string w = "wg_bc_update";
+    if (!perm_dev) return wg_fail(WG_ERR_INVALID, w + ": null argument");
+    if (int rc = bc_check(w, o, params_dev, b, hp)) return rc;
+    if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
+    if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
+    if (int rc = t_on_device(perm_dev, o->adam.device, (w + ": perm_dev").c_str())) return rc;
+    return wg_each_minibatch(b->n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
+        float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
+        if (int rc = t_bc_grad(&o->g, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        return t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

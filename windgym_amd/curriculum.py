@@ -93,6 +93,36 @@ def targets_per_step(initial, truncated, new_targets):
     return np.stack(out)
 
 
+def lap_ms(t, device, timing, key):
+    """Measurement only (``rollout(timing=...)``): synchronise and add the milliseconds since the last lap to ``timing[key]``."""
+    if timing is None:
+        return
+    t.cuda.synchronize(device)
+    now = time.perf_counter()
+    if key is not None:
+        timing[key] = timing.get(key, 0.0) + (now - timing["_t"]) * 1e3
+    timing["_t"] = now
+
+
+def new_episode_targets(t, out, ep_row, optimize, no_targets, lap=lambda key: None):
+    """The new-episode plumbing of a rollout recorded with ``wind_f64`` (:meth:`YawCurriculum.rollout`,
+    ``imitation.BehaviorCloning.collect``): the episodes that began inside it get their targets from ONE Serial-Refine launch over
+    exactly their C wind conditions.  Fills ``ep_row [T, B]`` (int32: -1, or the row of the step's new episode, numbered in (t, env)
+    order) -> ``(C, ep_target [C, N])`` (``no_targets`` when no env truncated).  ``optimize(ws, wd, ti) -> [C, N]`` float64;
+    ``lap(key)`` closes a part of the caller's timing split.  Compacting the flags is ONE host synchronisation."""
+    idx = out["truncated"].view(-1).nonzero().view(-1)            # the rollout's one host synchronisation; sorted by (t, env)
+    n_new = int(idx.numel())
+    ep_row.fill_(-1)
+    ep_target = no_targets
+    if n_new:
+        ep_row.view(-1)[idx] = t.arange(n_new, dtype=t.int32, device=ep_row.device)
+        wind = out["wind_f64"].view(-1, 3)[idx]                   # recorded after the autoreset: the new episode's wind
+        lap("plumbing")
+        ep_target = optimize(wind[:, 0], wind[:, 1], wind[:, 2]).contiguous()
+        lap("serial_refine")
+    return n_new, ep_target
+
+
 class YawCurriculum:
     """The curriculum of one ``WindFarmVecEnv`` / ``WindFarmVecEnvMulti`` (``as_torch=True``; arguments: the reference's
     ``CurriculumWrapper(env, curriculum_steps, pure_similarity_steps)`` plus the optimiser's — ``model`` ``"blondel_jimenez"`` (the
@@ -157,14 +187,7 @@ class YawCurriculum:
         return curriculum_weights(num_timesteps, n_steps, self.venv.num_envs, self.curriculum_steps, self.pure_similarity_steps)
 
     def _lap(self, timing, key):
-        """Measurement only (``rollout(timing=...)``): synchronise and add the milliseconds since the last lap to ``timing[key]``."""
-        if timing is None:
-            return
-        self.torch.cuda.synchronize(self.batch.device)
-        now = time.perf_counter()
-        if key is not None:
-            timing[key] = timing.get(key, 0.0) + (now - timing["_t"]) * 1e3
-        timing["_t"] = now
+        lap_ms(self.torch, self.batch.device, timing, key)
 
     def rollout(self, policy, n_steps, num_timesteps=0, *, deterministic=False, record=(), values=True, yaw_out=False, timing=None):
         """``venv.rollout(policy, n_steps)`` with the reward shaped: the returned dict has ``reward [T, B]`` replaced by the
@@ -200,17 +223,8 @@ class YawCurriculum:
                         yaw_held=t.zeros((T, B, N), **f32) if yaw_out else None)
             self._bufs[(T, bool(yaw_out))] = bufs
         bufs["weight"].copy_(t.from_numpy(w_host))
-        idx = out["truncated"].view(-1).nonzero().view(-1)            # the rollout's one host synchronisation; sorted by (t, env)
-        n_new = int(idx.numel())
         ep_row = bufs["ep_row"]
-        ep_row.fill_(-1)
-        ep_target = self._no_targets
-        if n_new:
-            ep_row.view(-1)[idx] = t.arange(n_new, dtype=t.int32, device=b.device)
-            wind = out["wind_f64"].view(-1, 3)[idx]                   # recorded after the autoreset: the new episode's wind
-            self._lap(timing, "plumbing")
-            ep_target = self._optimize(wind[:, 0], wind[:, 1], wind[:, 2]).contiguous()
-            self._lap(timing, "serial_refine")
+        n_new, ep_target = new_episode_targets(t, out, ep_row, self._optimize, self._no_targets, lambda key: self._lap(timing, key))
         self.last_n_targets = n_new
         self._lap(timing, "plumbing")
         self._cur.shape(T, self._yaw0, out["actions"], out["yaw_agent"], out["truncated"], ep_row, ep_target, n_new, bufs["weight"],

@@ -1,0 +1,216 @@
+"""Behaviour cloning from the yaw optimiser on the device: a supervised start for wake steering.
+
+The reference's aid for the hard start is its curriculum (examples/curriculum.py:335-429; ``curriculum.YawCurriculum`` here), which
+pays the agent through the reward for holding yaws near the Serial-Refine optimum of its episode's wind: imitation by way of a
+shaped reward and a policy gradient.  :class:`BehaviorCloning` fits the policy to the expert's ACTIONS directly.  One iteration is
+DAgger with the learner in the loop from the start:
+
+    ``venv.rollout(policy, n_steps)`` (the learner acts) -> ONE Serial-Refine launch for the episodes that began inside the rollout
+    (``curriculum.new_episode_targets``, the plumbing ``YawCurriculum.rollout`` uses) -> wg_expert_labels (k_expert_labels: the
+    expert's action for every visited state) -> with ``vf_coef > 0`` wg_gae for the critic's targets -> ONE wg_bc_update
+    (``n_epochs`` x minibatches of k_bc_grad + clipping + Adam + repack, on the ``wg_ppo`` handle ``PPO`` trains with).
+
+The label is a function of the state alone — the episode's wind fixes the target yaws, the current yaw fixes the largest move the
+env's actuation rule allows towards them — so the labels on the learner's own trajectories are exact.  Mixing expert actions into
+the closed loop (DAgger's beta) and aggregating the data of earlier rollouts exist to approximate that and are not needed for it:
+both are out of scope, every update sees the states of the current policy only.
+
+There is no CPU fallback: :class:`BehaviorCloning` needs the built library and a GPU.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .policy import MlpPolicy, refuse_recurrent
+from .ppo import PPO, PPOOptimizer, Trainer, check_batch_size, read_checkpoint, write_checkpoint
+
+LOSSES = ("mse", "nll")
+ARGS = ("expert", "loss", "deterministic", "refine_pass_n", "yaw_n", "search_yaw_max")
+
+
+def check_env(venv, policy, who="BehaviorCloning"):
+    """The refusals that need no device: what kind of env and policy these are."""
+    refuse_recurrent(policy, who)
+    if getattr(venv, "population", None) is not None or getattr(policy, "population", None) is not None:
+        raise NotImplementedError(f"{who}: cloning into a population is not implemented (clone one policy, then copy its weights)")
+    if not (hasattr(venv, "batch") and hasattr(venv, "rollout")):
+        raise ValueError(f"{who}: venv must be a WindFarmVecEnv or a WindFarmVecEnvMulti")
+    if not getattr(venv, "as_torch", True):           # (a WindFarmVecEnvMulti has no such switch: always CUDA tensors)
+        raise ValueError(f"{who}: venv works on CUDA tensors here: construct the env with as_torch=True")
+    if not isinstance(policy, str) and getattr(policy, "split", False):
+        raise NotImplementedError(f"{who}: a split policy (a centralised critic, n_in_vf = {policy.n_in_vf}) is not implemented: its "
+                                  "critic reads other rows than its actor; clone an MlpPolicy whose nets read the same rows")
+
+
+class BehaviorCloning(Trainer):
+    """Fit an :class:`MlpPolicy` to the Serial-Refine yaw optimiser by supervised learning on the states the policy itself visits
+    (the module docstring states the iteration).  On a ``WindFarmVecEnv`` the policy maps ``obs_dim -> n_turb``; on a
+    ``WindFarmVecEnvMulti`` it is the ONE policy shared by the turbines (``obs_len -> 1``): a row is an agent row, the labels
+    ``[T, B, N]`` are read as ``[T * B * N, 1]`` and the critic's targets come from wg_gae_shared.
+
+    ``expert``: the wake model the optimiser runs on — ``"blondel_jimenez"`` (what ``PyWakeVecAgent`` steers by) or ``"m0"`` (the
+    env's own); ``refine_pass_n`` x ``yaw_n`` candidates within ``search_yaw_max`` degrees, as ``YawCurriculum`` takes them.
+    ``policy``: an :class:`MlpPolicy` or ``"MlpPolicy"`` (built as ``PPO`` builds it, ``policy_kwargs`` included).
+
+    ``loss="mse"`` (the default) is the mean squared error of the actor's mean; ``"nll"`` is the negative log-likelihood of the
+    expert's action less ``ent_coef`` x the entropy.  MSE is the default because the expert is deterministic: under NLL nothing
+    stops ``log_std`` from falling for as long as the mean keeps improving, and a policy handed to ``PPO`` afterwards would have
+    nothing left to explore with.  MSE leaves ``log_std`` exactly where it was (its gradient is 0.0).  With ``vf_coef > 0`` the
+    critic is fitted to the GAE returns (``gamma``, ``gae_lambda``) of the learner's rollouts; with 0 it is left untouched (its
+    gradient is 0.0) and the rollouts skip it.  ``deterministic``: whether the learner acts by its mean while it collects.
+
+    ``learn`` / ``log`` / ``predict`` / ``save`` are the trainers' (``log`` records: ``loss``, ``mse``, ``nll``, ``entropy``,
+    ``v_loss``, ``mean_abs_err``, ``mean_yaw_diff`` — the rollout's mean distance to the expert's yaws in degrees — and the episode
+    means and ``fps`` of ``PPO``'s).  ``PPO(bc.policy, venv)`` fine-tunes: a fresh optimiser on the cloned weights.  ``save`` writes
+    ``PPO``'s zip (``policy.pth`` that ``MlpPolicy.from_sb3_zip`` reads, Adam's state, the permutation generator, the counters)
+    plus the JSON key ``bc`` (the arguments above) and the running target table as ``bc_targets.npy``; :meth:`load` resumes
+    bit-identically on an env in the same state.
+
+    Refused: a recurrent policy, a population, a split / central-critic policy (``NotImplementedError``); ``as_torch=False``, an
+    unknown ``loss`` or ``expert`` (``ValueError``)."""
+
+    def __init__(self, policy, venv, expert="blondel_jimenez", n_steps=128, batch_size=None, n_epochs=4, learning_rate=1e-3,
+                 loss="mse", ent_coef=0.0, vf_coef=0.0, gamma=0.99, gae_lambda=0.95, max_grad_norm=0.5, deterministic=False,
+                 refine_pass_n=8, yaw_n=9, search_yaw_max=30.0, policy_kwargs=None, seed=None):
+        from .steady import MODEL_IDS
+        check_env(venv, policy)
+        if loss not in LOSSES:
+            raise ValueError(f"BehaviorCloning: loss must be one of {list(LOSSES)}, not {loss!r}")
+        if not isinstance(expert, str) or expert not in MODEL_IDS:
+            raise ValueError(f"BehaviorCloning: expert must be one of {sorted(MODEL_IDS)}, not {expert!r}")
+        if not float(vf_coef) >= 0.0 or not float(ent_coef) >= 0.0:
+            raise ValueError("BehaviorCloning: vf_coef and ent_coef must be >= 0")
+        self._setup(n_steps, n_epochs, gamma, gae_lambda, 0.0, ent_coef, vf_coef, max_grad_norm, learning_rate, False, seed, None, None, False)
+        self.expert, self.loss, self.deterministic = expert, loss, bool(deterministic)
+        self.refine_pass_n, self.yaw_n, self.search_yaw_max = int(refine_pass_n), int(yaw_n), float(search_yaw_max)
+        n_steps = self.n_steps
+        multi = getattr(venv, "possible_agents", None) is not None       # WindFarmVecEnvMulti: one row per (env, turbine)
+        n_agents = int(venv.n_turb) if multi else 1
+        n_rows = n_steps * int(venv.num_envs) * n_agents
+        batch_size = check_batch_size(batch_size, n_rows, f"n_steps * num_envs{' * n_turb' if multi else ''}")
+        if isinstance(policy, str) and policy != "MlpPolicy":
+            raise ValueError(f"unknown policy {policy!r}: only 'MlpPolicy'")
+        if policy_kwargs and not isinstance(policy, str):
+            raise ValueError("policy_kwargs only applies to policy='MlpPolicy'")
+        want = (int(venv.obs_len), 1) if multi else (int(venv.batch.obs_dim), int(venv.n_turb))
+        if isinstance(policy, str):
+            policy = PPO._build_policy(venv, want, dict(policy_kwargs or {}), 0 if seed is None else int(seed))
+        if (policy.n_in, policy.n_out) != want:
+            raise ValueError(f"the policy maps {policy.n_in} -> {policy.n_out}, this env needs {want[0]} -> {want[1]} (obs_dim -> n_turb "
+                             "on a WindFarmVecEnv, obs_len -> 1 — one policy shared by the turbines — on a WindFarmVecEnvMulti)")
+        self.policy, self.venv, self.torch, self.batch = policy, venv, policy.torch, venv.batch
+        self.critic = "agent" if multi else None
+        self.batch_size, self.n_rows = batch_size, n_rows
+        self.multi, self.n_agents, self.n_env_steps = multi, n_agents, n_steps * int(venv.num_envs)
+        self.opt = PPOOptimizer(policy)
+        self._alloc(n_rows, (n_steps, venv.num_envs) + ((n_agents,) if multi else ()), -(-n_rows // batch_size))
+        from .binding import ExpertLabels
+        t, b = self.torch, self.batch
+        self._lab = ExpertLabels(b)
+        f32 = dict(dtype=t.float32, device=b.device)
+        self._yaw0 = t.zeros((b.B, b.N), **f32)
+        self._labels = t.zeros((n_steps, b.B, b.N), **f32)
+        self._yaw_diff = t.zeros((n_steps, b.B), **f32)
+        self._ep_row = t.zeros((n_steps, b.B), dtype=t.int32, device=b.device)
+        self._no_targets = t.zeros((0, b.N), dtype=t.float64, device=b.device)
+        self.last_n_targets = 0                       # Serial-Refine conditions the last collect() served
+        self.reset_targets()
+
+    def _optimize(self, ws, wd, ti):
+        return self.batch.steady_optimize(ws, wd, ti, model=self.expert, refine_pass_n=self.refine_pass_n, yaw_n=self.yaw_n,
+                                          yaw_max=self.search_yaw_max)[0]
+
+    def reset_targets(self):
+        """Every env's running target becomes the expert's yaws for its CURRENT wind (call it after resetting the env by hand);
+        ``targets`` is that table, ``[B, N]`` float64 on the device, advanced in place by every :meth:`collect`."""
+        self.targets = self.batch.optimal_yaws(model=self.expert, refine_pass_n=self.refine_pass_n, yaw_n=self.yaw_n,
+                                               yaw_max=self.search_yaw_max).contiguous()
+        return self.targets
+
+    # -- training -------------------------------------------------------------------------------------------------
+    def collect(self, timing=None):
+        """One rollout of the learner + the expert's labels for it -> the rollout dict with ``labels [T, B, N]``, ``yaw_diff
+        [T, B]`` and, with ``vf_coef > 0``, ``advantage`` / ``returns`` added.  One host synchronisation (the new episodes' count).
+        ``timing``: a dict that receives the milliseconds of ``rollout``, ``serial_refine``, ``labels`` and ``plumbing``, measured
+        between device synchronisations (tools/bench_imitation.py's split; it slows the call)."""
+        from .curriculum import lap_ms, new_episode_targets
+        lap = lambda key: lap_ms(self.torch, self.batch.device, timing, key)
+        lap(None)
+        self.batch.info("yaw_agent", out=self._yaw0)
+        out = self.venv.rollout(self.policy, self.n_steps, deterministic=self.deterministic, record=("yaw_agent", "wind_f64"),
+                                values=self.vf_coef > 0.0)
+        lap("rollout")
+        n_new, ep_target = new_episode_targets(self.torch, out, self._ep_row, self._optimize, self._no_targets, lap)
+        self.last_n_targets = n_new
+        lap("plumbing")
+        self._lab.labels(self.n_steps, self._yaw0, out["yaw_agent"], out["truncated"], self._ep_row, ep_target, n_new, self.targets,
+                         self._labels, self._yaw_diff)
+        lap("labels")
+        out["labels"], out["yaw_diff"] = self._labels, self._yaw_diff
+        if self.vf_coef > 0.0:
+            self.opt.gae(out["reward"], out["value"], out["final_value"], out["truncated"], self.gamma, self.gae_lambda,
+                         out=(self._adv, self._ret))
+            out["advantage"], out["returns"] = self._adv, self._ret
+        lap("plumbing")
+        return out
+
+    def train(self, out, learning_rate, clip_range=None):
+        """The epochs' permutations, then ONE wg_bc_update on the rollout's rows."""
+        t = self.torch
+        for e in range(self.n_epochs):
+            self._perm[e].copy_(t.randperm(self.n_rows, generator=self._gen, device=self.policy.device))
+        T, O, N = self.n_steps, self.policy.n_in, self.policy.n_out
+        return self.opt.bc_update(out["obs"][:T].view(-1, O), out["labels"].view(-1, N),
+                                  self._ret.view(-1) if self.vf_coef > 0.0 else None, self._perm, self.batch_size, loss=self.loss,
+                                  ent_coef=self.ent_coef, vf_coef=self.vf_coef, learning_rate=learning_rate,
+                                  max_grad_norm=self.max_grad_norm, stats=self._stats)
+
+    def _record(self, out, stats, lr, clip, fps):
+        from .binding import BC_STATS
+        from .parallel import METRIC_NAMES, derive
+        t = self.torch
+        vec = t.cat([stats.double().mean(dim=(0, 1)), out["yaw_diff"].double().mean().reshape(1),
+                     self.venv.batch.metrics(reset_after=True).double().reshape(-1)])
+        host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
+        rec = dict(zip(BC_STATS[:6], host[:6].tolist()))
+        m = derive(host[9:9 + len(METRIC_NAMES)])
+        rec.update(mean_yaw_diff=float(host[8]), iteration=self.iteration, num_timesteps=self.num_timesteps, learning_rate=lr,
+                   n_episodes=m["n_episodes"], mean_episode_return=m["mean_episode_return"],
+                   mean_episode_power=m["mean_episode_power"], mean_step_reward=m["mean_step_reward"], fps=fps())
+        return rec
+
+    # -- checkpoints ----------------------------------------------------------------------------------------------
+    def args(self):
+        """The constructor's own arguments (what ``save`` stores under the JSON key ``bc``)."""
+        return {k: getattr(self, k) for k in ARGS}
+
+    def save(self, path):
+        """Everything a bit-identical resume needs except the env itself.  Synchronises; a bad ``ep_row`` entry that a
+        :meth:`collect` met is reported here (``ValueError``)."""
+        from .ppo import HYPER
+        self._lab.check()
+        return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
+                                self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps,
+                                tensors={"bc_targets.npy": self.targets}, extra=dict(bc=self.args()))
+
+    @classmethod
+    def load(cls, path, venv, learning_rate=None, device=None):
+        """Resume: the policy, Adam's state, the permutation generator, the counters and the target table continue where ``save``
+        left them, so that on an env in the same state ``learn(..., reset_num_timesteps=False)`` computes what the uninterrupted
+        run would have.  ``learning_rate``: the schedule again, when the saved run used a callable."""
+        from .policy import read_sb3_zip
+        meta, members = read_checkpoint(path, learning_rate, None, needs=("bc_targets.npy",),
+                                        refusal="not a windgym_amd BehaviorCloning checkpoint")
+        if "bc" not in meta:
+            raise ValueError("not a windgym_amd BehaviorCloning checkpoint")
+        desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
+        pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
+                        device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"],
+                        n_in_vf=desc["n_in_vf"])
+        pol.load_state_dict(tensors)
+        pol.counter = int(meta["policy_counter"])
+        hy = {k: v for k, v in meta["hyper"].items() if k not in ("clip_range", "normalize_advantage")}
+        self = cls(pol, venv, seed=meta["seed"], **meta["bc"], **hy)
+        self._restore(meta, members)
+        self.targets = self.torch.from_numpy(np.ascontiguousarray(members["bc_targets.npy"], dtype=np.float64)).to(self.batch.device)
+        return self

@@ -206,6 +206,53 @@ class PPOOptimizer(HandleOptimizer):
             st.data_ptr(), self.policy._stream()), entry)
         return st
 
+    # -- the supervised loss on the same handle (imitation.BehaviorCloning) --------------------------------------------------
+    def _bc_batch(self, obs, target, returns, loss, ent_coef, vf_coef):
+        from .binding import BC_LOSS, CBcBatch, CBcHyper
+        p = self.policy
+        if loss not in BC_LOSS:
+            raise ValueError(f"loss must be one of {sorted(BC_LOSS)}, not {loss!r}")
+        if p.split:
+            raise ValueError(f"the policy's critic reads {p.n_in_vf} inputs: cloning a split policy is not implemented")
+        n = target.numel() // p.n_out
+        self._f32(obs, (n, p.n_in), "obs"); self._f32(target, (n, p.n_out), "target")
+        if returns is not None:
+            self._f32(returns, (n,), "returns")
+        b = CBcBatch(obs.data_ptr(), target.data_ptr(), None if returns is None else returns.data_ptr(), n)
+        return b, n, CBcHyper(BC_LOSS[loss], float(ent_coef), float(vf_coef))
+
+    def bc_grad(self, obs, target, returns=None, *, index=None, first=0, n=None, loss="mse", ent_coef=0.0, vf_coef=0.0, out=None,
+                stats=None):
+        """wg_bc_grad: one minibatch of the supervised loss on the expert's actions ``target [rows, n_out]`` -> (flat gradient
+        ``[n_params]``, statistics ``[8]`` in the order of binding.BC_STATS).  ``returns`` ``None``: no critic term."""
+        t = self.torch
+        b, rows, hp = self._bc_batch(obs, target, returns, loss, ent_coef, vf_coef)
+        if index is not None:
+            n = index.numel() if n is None else int(n)
+            self._index(index, n)
+        elif n is None:
+            n = rows - int(first)
+        g = self.grad_buf if out is None else out
+        st = t.zeros(8, dtype=t.float32, device=self.policy.device) if stats is None else stats
+        self._chk(self.L.wg_bc_grad(self._h, self.policy.params.data_ptr(), C.byref(b), None if index is None else index.data_ptr(),
+                                    int(first), int(n), C.byref(hp), g.data_ptr(), st.data_ptr(), self.policy._stream()), "wg_bc_grad")
+        return g, st
+
+    def bc_update(self, obs, target, returns, perm, batch_size, *, loss="mse", ent_coef=0.0, vf_coef=0.0, learning_rate=1e-3,
+                  max_grad_norm=0.5, stats=None):
+        """wg_bc_update: ``perm`` int32 ``[n_epochs, n_rows]`` -> statistics ``[n_epochs, n_minibatches, 8]``."""
+        t = self.torch
+        b, rows, hp = self._bc_batch(obs, target, returns, loss, ent_coef, vf_coef)
+        if perm.ndim != 2 or perm.shape[1] != rows:
+            raise ValueError(f"perm must be [n_epochs, {rows}]")
+        self._index(perm, rows)
+        n_epochs, n_mb = perm.shape[0], -(-rows // int(batch_size))
+        st = t.zeros((n_epochs, n_mb, 8), dtype=t.float32, device=self.policy.device) if stats is None else stats
+        self._chk(self.L.wg_bc_update(self._h, self.policy.params.data_ptr(), C.byref(b), perm.data_ptr(), n_epochs, int(batch_size),
+                                      C.byref(hp), float(learning_rate), float(max_grad_norm), st.data_ptr(), self.policy._stream()),
+                  "wg_bc_update")
+        return st
+
 
 def _schedule(x, name):
     if callable(x):
@@ -269,12 +316,13 @@ def hyper_json(hyper):
 
 
 def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps, curriculum=None,
-                     normalize=None, tensors=None):
+                     normalize=None, tensors=None, extra=None):
     """The zip of :meth:`PPO.save` (format: the class docstring) from what it holds: the policy, its :class:`PPOOptimizer`, the
     permutation generator, the ``HYPER`` dict, the trainer's seed, its counters and log, the critic mode and the env's count of
     policy steps; with a ``curriculum`` (a ``YawCurriculum``) also its arguments (JSON key ``curriculum``) and its state blob
     (member ``curriculum_state.bin``); with ``normalize`` (a ``VecNormalize``) its arguments (JSON key ``normalize``) and its state
-    blob (member ``normalize_state.bin``); ``tensors``: {member name: tensor}, written as further npy members."""
+    blob (member ``normalize_state.bin``); ``tensors``: {member name: tensor}, written as further npy members; ``extra``: further
+    keys of the JSON (``imitation.BehaviorCloning``: ``bc``)."""
     import torch
     mv, step = opt.state()
     sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
@@ -292,6 +340,7 @@ def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iterati
         meta["curriculum"] = curriculum.args()
     if normalize is not None:
         meta["normalize"] = normalize.args()
+    meta.update(extra or {})
     with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
         z.writestr("policy.pth", pth.getvalue())
         z.writestr("adam_state.npy", npy(mv))
