@@ -867,6 +867,64 @@ int wg_expert_labels(wg_handle h, int T,
 int wg_expert_labels_check(wg_handle h, int32_t* err_dev);
 
 /* -----------------------------------------------------------------------------------------------------------------
+ * Yaw table: the Serial-Refine optimiser's yaws on a grid of wind conditions, resident on the device, looked up by the NEAREST
+ * node (windgym_amd/csrc/wg_yaw_table.hip; the node rule is stated once, in windgym_amd/csrc/wg_yaw_table.h).  Three axes of
+ * float64 nodes, each strictly ascending, in the order ti (slowest), ws, wd (fastest); C = n_ti * n_ws * n_wd rows of N yaws
+ * (degrees).  For one axis a_0 < ... < a_{n-1} and a value x, in double:
+ *     i = the number of midpoints m_k = (a_k + a_{k+1}) / 2, k = 0 .. n-2, with m_k < x
+ * (a tie goes to the lower node, x outside the axis to the end node);  row = (i_ti * n_ws + i_ws) * n_wd + i_wd;  a wind with a
+ * non-finite component has row -1.  wrap_wd != 0 (the caller's statement that wd covers the full circle): x is first reduced by
+ *     r = fmod(x - a_0, 360);  if (r < 0) r += 360;  x = a_0 + r
+ * and a virtual node a_0 + 360 maps to index 0.  Nothing is interpolated: the optimum is an argmax over discrete candidates and
+ * is not continuous in the wind.  A wind is three doubles (ws, wd, ti), the layout of WG_INFO_WIND_F64.  No kernel here sums,
+ * uses atomics or allocates; every value is a fixed fp64 expression rounded at most once.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_yaw_table_s* wg_yaw_table;
+
+/* The table on `device`: the axes are HOST arrays, yaw f64[C, N] is a host array or (on_device != 0) memory of `device`; both are
+ * copied into ONE allocation, which is all the table ever allocates.  Synchronises the device.  WG_ERR_INVALID, the message naming
+ * the argument: out / an axis / yaw null, an axis empty, not finite or not strictly ascending, wrap_wd with wd[n_wd - 1] - wd[0]
+ * >= 360, N < 1, yaw (on_device) not memory of `device`.  WG_ERR_UNSUPPORTED: more than 1024 nodes on the three axes together
+ * (what a workgroup stages in LDS), more than 2^31 entries.                                                              */
+int wg_yaw_table_create(int device, const double* ti, int n_ti, const double* ws, int n_ws, const double* wd, int n_wd,
+                        int wrap_wd, int N, const double* yaw, int on_device, wg_yaw_table* out);
+int wg_yaw_table_destroy(wg_yaw_table tab);
+
+/* The row of each of n winds: ONE launch of k_yaw_table_rows (one thread per wind), asynchronous on `stream`.  Reads wind_dev
+ * f64[n, 3] and mask_dev u8[n] (may be NULL: every wind is looked up); writes rows_out i32[n]: the row, or -1 where the mask is 0
+ * or the wind is not finite.  With the recorded WG_INFO_WIND_F64 and truncated of a rollout (n = T * B) rows_out is the ep_row_dev
+ * of wg_curriculum_shape / wg_expert_labels, whose ep_target_dev is then the table's yaw and whose C its row count.
+ * WG_ERR_INVALID, nothing enqueued: tab / wind_dev / rows_out null, n < 0, a buffer that is not memory of the table's device.
+ * n == 0 does nothing.                                                                                                  */
+int wg_yaw_table_rows(wg_yaw_table tab, int n, const double* wind_dev, const uint8_t* mask_dev, int32_t* rows_out, void* stream);
+
+/* The yaws of each of n winds: ONE launch of k_yaw_table_targets (one thread per (wind, turbine)), asynchronous on `stream`.
+ * Reads wind_dev f64[n, 3]; writes targets_out f64[n, N] = the table's row of every wind; the output row of a wind without a row
+ * (-1) is left as it was.  WG_ERR_INVALID, nothing enqueued: tab / wind_dev / targets_out null, n < 0, a buffer that is not memory
+ * of the table's device; WG_ERR_UNSUPPORTED: n * N > 2^31.  n == 0 does nothing.                                           */
+int wg_yaw_table_targets(wg_yaw_table tab, int n, const double* wind_dev, double* targets_out, void* stream);
+
+/* The table as a scripted agent: ONE launch of k_yaw_table_act (one thread per (env, turbine)), asynchronous on `stream`, no
+ * state.  Reads, on the device, every env's current wind and the agent farm's current yaws (what WG_INFO_WIND_F64 and
+ * WG_INFO_YAW_AGENT report) and writes action_out f32[B, N]: with g = the table's yaw of the wind's row and prev = the current
+ * yaw, the action of wg_expert_labels, in double, rounded once:
+ *     WG_ACT_WIND:  a = (g - yaw_min) / (yaw_max - yaw_min) * 2 - 1        WG_ACT_YAW:  a = clamp((g - prev) / yaw_step, -1, 1)
+ * (a wind without a row, which no env samples: a = 0).  The lookup is repeated from the env's current wind on every call, so a
+ * same-step autoreset needs no bookkeeping.  WG_ERR_INVALID, nothing enqueued: h / tab / action_out null, tab created for another
+ * N than the handle's n_turb or on another device.                                                                       */
+int wg_yaw_table_act(wg_handle h, wg_yaw_table tab, float* action_out, void* stream);
+
+/* wg_rollout with the table in the policy's place: per step ONE launch of k_yaw_table_act -> actions[t], then the step and the
+ * info recordings of wg_rollout.  Buffers and the handle's state afterwards are BIT-IDENTICAL to
+ *     for t in 0 .. T-1:
+ *         wg_yaw_table_act(h, tab, actions[t])
+ *         wg_step(h, actions[t], obs[t+1], reward[t], truncated[t], final_obs[t])
+ *         wg_get_info(h, info_fields[i], info_out[i] + t * <size of the field>)       for every i
+ * WG_ERR_INVALID, nothing enqueued: a null argument, what wg_yaw_table_act refuses of tab, n_steps < 0, obs / actions / reward /
+ * truncated missing, raw / logp / value / final_value not NULL (a table samples nothing and has no critic), bad info arguments. */
+int wg_rollout_table(wg_handle h, wg_yaw_table tab, int n_steps, const wg_rollout_bufs* bufs, void* stream);
+
+/* -----------------------------------------------------------------------------------------------------------------
  * VecNormalize: running observation / return statistics for PPO, restated from stable-baselines3 2.x
  * (common/vec_env/vec_normalize.py, common/running_mean_std.py; windgym_amd/csrc/wg_norm.hip).
  *   RunningMeanStd(shape): mean = 0, var = 1, count = 1e-4 (float64).  update(batch [n, ...]):

@@ -73,6 +73,7 @@ ABI_SYMBOLS = (
     "wg_curriculum_create", "wg_curriculum_destroy", "wg_curriculum_get_state", "wg_curriculum_set_state", "wg_curriculum_set_targets",
     "wg_curriculum_shape",
     "wg_bc_grad", "wg_bc_update", "wg_expert_labels", "wg_expert_labels_check",
+    "wg_yaw_table_create", "wg_yaw_table_destroy", "wg_yaw_table_rows", "wg_yaw_table_targets", "wg_yaw_table_act", "wg_rollout_table",
     "wg_norm_create", "wg_norm_destroy", "wg_norm_get_state", "wg_norm_set_state", "wg_norm_set_training", "wg_norm_reset_returns",
     "wg_norm_obs", "wg_norm_reward", "wg_rollout_norm",
     "wg_lstm_create", "wg_lstm_destroy", "wg_lstm_n_params", "wg_lstm_set_params", "wg_lstm_step", "wg_lstm_act", "wg_rollout_lstm",
@@ -259,6 +260,12 @@ def load_library():
                                C.POINTER(CBcHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     L.wg_expert_labels.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
     L.wg_expert_labels_check.argtypes = [C.c_void_p, C.c_void_p]
+    L.wg_yaw_table_create.argtypes = [C.c_int] + [C.c_void_p, C.c_int] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.wg_yaw_table_destroy.argtypes = [C.c_void_p]
+    L.wg_yaw_table_rows.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.wg_yaw_table_targets.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    L.wg_yaw_table_act.argtypes = [C.c_void_p] * 4
+    L.wg_rollout_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CRolloutBufs), C.c_void_p]
     L.wg_pop_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
     L.wg_pop_destroy.argtypes = [C.c_void_p]
     L.wg_pop_act.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
@@ -420,6 +427,12 @@ class HipBatch:
     def rollout(self, *args):
         """wg_rollout(policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset); ``bufs`` keyed by wg_rollout_bufs' fields."""
         self._rollout("wg_rollout", CRolloutBufs, self.ROLLOUT_KEYS, *args)
+
+    def rollout_table(self, table, n_steps, bufs, record):
+        """wg_rollout_table: a :class:`YawTableHandle` in the policy's place; ``bufs`` as for :meth:`rollout`, without ``raw`` /
+        ``logp`` / ``value`` / ``final_value`` (the library refuses them)."""
+        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
+        _chk(self.L.wg_rollout_table(self._h, table._h, int(n_steps), C.byref(cb), self._stream()), "wg_rollout_table")
 
     def rollout_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
         """wg_pop_rollout, the arguments of :meth:`rollout` with a ``population.Population`` in the policy's place: every member
@@ -837,6 +850,76 @@ class ExpertLabels:
         """``ValueError`` once, naming ``ep_row_dev``, when an earlier :meth:`labels` met an ``ep_row`` entry that was no row of
         ``ep_target`` (the kernel skipped it).  Synchronises."""
         _chk(self.L.wg_expert_labels_check(self.batch._h, self._err.data_ptr()), "wg_expert_labels_check")
+
+
+class YawTableHandle:
+    """A ``wg_yaw_table`` handle: the axes and the yaws ``[C, N]`` of a yaw table on one device and its lookup kernels
+    (include/windgym_hip.h states the node rule; ``windgym_amd.yaw_table.YawTable`` is the user-facing class).  ``rows``, ``targets``
+    and ``act`` enqueue on torch's current stream and synchronise nothing."""
+
+    def __init__(self, torch, device, ti, ws, wd, wrap_wd, yaw):
+        self.torch, self.L, self.device = torch, load_library(), device
+        ax = [np.ascontiguousarray(a, dtype=np.float64) for a in (ti, ws, wd)]
+        if not (torch.is_tensor(yaw) and yaw.is_cuda and yaw.dtype == torch.float64 and yaw.is_contiguous() and yaw.dim() == 2):
+            raise ValueError("yaw must be a contiguous float64 CUDA tensor [C, N]")
+        self.N = int(yaw.shape[1])
+        args = [x for a in ax for x in (a.ctypes.data_as(C.c_void_p), len(a))]
+        h = C.c_void_p()
+        _chk(self.L.wg_yaw_table_create(device.index, *args, int(bool(wrap_wd)), self.N, yaw.data_ptr(), 1, C.byref(h)), "wg_yaw_table_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.wg_yaw_table_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _wind(self, who, wind):
+        t = self.torch
+        if not (t.is_tensor(wind) and wind.is_cuda and wind.dtype == t.float64 and wind.is_contiguous() and wind.dim() >= 1 and wind.shape[-1] == 3):
+            raise ValueError(f"{who}: wind must be a contiguous float64 CUDA tensor [..., 3] (ws, wd, ti)")
+        return wind.numel() // 3
+
+    def rows(self, wind, mask=None, out=None):
+        """wg_yaw_table_rows: ``wind [..., 3]`` float64, ``mask [...]`` uint8 or ``None`` -> int32 ``[...]``."""
+        t = self.torch
+        n = self._wind("rows()", wind)
+        if mask is not None and not (t.is_tensor(mask) and mask.is_cuda and mask.dtype == t.uint8 and mask.is_contiguous() and mask.numel() == n):
+            raise ValueError(f"rows(): mask must be a contiguous uint8 CUDA tensor of {n} elements")
+        if out is None:
+            out = t.empty(tuple(wind.shape[:-1]), dtype=t.int32, device=wind.device)
+        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.int32 and out.is_contiguous() and out.numel() == n):
+            raise ValueError(f"rows(): out must be a contiguous int32 CUDA tensor of {n} elements")
+        _chk(self.L.wg_yaw_table_rows(self._h, n, wind.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr(), self._stream()),
+             "wg_yaw_table_rows")
+        return out
+
+    def targets(self, wind, out=None):
+        """wg_yaw_table_targets: ``wind [..., 3]`` float64 -> float64 ``[..., N]``; a row of ``out`` whose wind has no row stays."""
+        t = self.torch
+        n = self._wind("targets()", wind)
+        if out is None:
+            out = t.zeros(tuple(wind.shape[:-1]) + (self.N,), dtype=t.float64, device=wind.device)
+        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float64 and out.is_contiguous() and out.numel() == n * self.N):
+            raise ValueError(f"targets(): out must be a contiguous float64 CUDA tensor of {n * self.N} elements")
+        _chk(self.L.wg_yaw_table_targets(self._h, n, wind.data_ptr(), out.data_ptr(), self._stream()), "wg_yaw_table_targets")
+        return out
+
+    def act(self, batch, out):
+        """wg_yaw_table_act on ``batch`` (a :class:`HipBatch`): ``out`` float32 ``[B, N]``."""
+        t = self.torch
+        if not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and out.numel() == batch.B * batch.N):
+            raise ValueError(f"act(): out must be a contiguous float32 CUDA tensor [{batch.B}, {batch.N}]")
+        _chk(self.L.wg_yaw_table_act(batch._h, self._h, out.data_ptr(), batch._stream()), "wg_yaw_table_act")
+        return out
 
 
 class Norm:

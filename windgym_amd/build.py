@@ -8,7 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwindgym_hip.so")
-SOURCES = ["wg_flow.hip", "wg_env.hip", "wg_envb.hip", "wg_kernels.hip", "wg_api.hip", "wg_mann.hip", "wg_steady.hip", "wg_policy.hip", "wg_ppo.hip", "wg_curriculum.hip", "wg_norm.hip", "wg_lstm.hip", "wg_lstm_ppo.hip"]
+SOURCES = ["wg_flow.hip", "wg_env.hip", "wg_envb.hip", "wg_kernels.hip", "wg_api.hip", "wg_mann.hip", "wg_steady.hip", "wg_policy.hip", "wg_ppo.hip", "wg_curriculum.hip", "wg_yaw_table.hip", "wg_norm.hip", "wg_lstm.hip", "wg_lstm_ppo.hip"]
 
 
 def _headers():

@@ -838,6 +838,9 @@ struct RolloutRows {
     // non-null: a population of recurrent policies (wg_lstm_pop_rollout) — `lstm` is member 0's (the members share its shape), the
     // LSTMs' launches are wg_lstm_pop_step_ on lb's state in the population's layout, and `pop` is its heads' slot table
     wg_lstm_pop_s* lpop;
+    // non-null: a yaw table acts in the policy's place (wg_rollout_table) — a step's one launch of the policy kernel is
+    // k_yaw_table_act on the env's current wind and yaws; there is no policy, so nothing of one is checked, sampled or valued
+    wg_yaw_table_s* table;
 };
 
 static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
@@ -846,16 +849,21 @@ static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, i
     if (n_steps < 0) return wg_fail(WG_ERR_INVALID, who + "n_steps < 0");
     if (!o.obs_multi || !o.actions || !o.reward || !o.truncated)
         return wg_fail(WG_ERR_INVALID, who + g.obs_name + ", actions, reward and truncated buffers are required");
-    if (p->w.device != h->device) return wg_fail(WG_ERR_INVALID, who + "policy and handle live on different devices");
-    if (p->P.n_in != g.n_in || p->P.n_out != g.n_out || (p->P.n_layers[1] != 0 && p->P.n_in_vf != g.v_in))
-        return wg_fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
-                                        (p->P.n_in_vf != p->P.n_in ? " (its critic reads " + std::to_string(p->P.n_in_vf) + " inputs)" : std::string()) + g.needs);
-    if (g.unready) return wg_fail(WG_ERR_INVALID, who + g.unready);
-    if (!g.v_obs) return wg_fail(WG_ERR_INVALID, who + "a centralised critic reads the flat observation: obs is required (slot 0 is input)");
-    if (o.final_value && !g.v_fin) return wg_fail(WG_ERR_INVALID, who + "final_value needs " + g.fin_name);
-    if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
-    if (!p->P.has_log_std && (!deterministic || o.logp))
-        return wg_fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
+    if (g.table) {
+        if (o.raw || o.logp || o.value || o.final_value)
+            return wg_fail(WG_ERR_INVALID, who + "raw, logp, value and final_value must be NULL: a yaw table samples nothing and has no critic");
+    } else {
+        if (p->w.device != h->device) return wg_fail(WG_ERR_INVALID, who + "policy and handle live on different devices");
+        if (p->P.n_in != g.n_in || p->P.n_out != g.n_out || (p->P.n_layers[1] != 0 && p->P.n_in_vf != g.v_in))
+            return wg_fail(WG_ERR_INVALID, who + "the policy maps " + std::to_string(p->P.n_in) + " -> " + std::to_string(p->P.n_out) +
+                                            (p->P.n_in_vf != p->P.n_in ? " (its critic reads " + std::to_string(p->P.n_in_vf) + " inputs)" : std::string()) + g.needs);
+        if (g.unready) return wg_fail(WG_ERR_INVALID, who + g.unready);
+        if (!g.v_obs) return wg_fail(WG_ERR_INVALID, who + "a centralised critic reads the flat observation: obs is required (slot 0 is input)");
+        if (o.final_value && !g.v_fin) return wg_fail(WG_ERR_INVALID, who + "final_value needs " + g.fin_name);
+        if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
+        if (!p->P.has_log_std && (!deterministic || o.logp))
+            return wg_fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
+    }
     if (o.n_info < 0 || (o.n_info > 0 && (!o.info_fields || !o.info_out))) return wg_fail(WG_ERR_INVALID, who + "bad info arguments");
     for (int i = 0; i < o.n_info; ++i) {
         if (o.info_fields[i] < 0 || o.info_fields[i] > WG_INFO_BOX_ID) return wg_fail(WG_ERR_INVALID, who + "unknown info field");
@@ -910,7 +918,9 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
         int nv = 0;
         if (o.value) v[nv++] = {g.lstm ? h_vf : g.v_obs + t * sVO, o.value + t * sV, V};
         if (o.final_value && t > 0) v[nv++] = {g.lstm ? h_fin : g.v_fin + (t - 1) * sVO, o.final_value + (t - 1) * sV, V};
-        if (g.lstm) {
+        if (g.table) {
+            wg_launch_yaw_table_act_(g.table, &h->p, &h->d, o.actions + t * sRN, st);
+        } else if (g.lstm) {
             // (the final rows of step t - 1 first: they read the state that step t's launch then advances in place; the episode
             // starts of step t > 0 are read where the step before wrote them, truncated[t - 1] = what episode_start[t] will hold)
             if (o.final_value && t > 0) rc = lstm_final(t - 1);
@@ -1022,6 +1032,39 @@ extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int determinis
     const WgPopOuts out = {o->actions, o->raw, o->logp, o->value, o->final_value, B};
     if (int rc = wg_pop_prepare_(q, "wg_pop_rollout", B, seeds, row_offsets, o->obs, o->final_obs, &out, stream)) return rc;
     return rollout_loop(h, q->pol[0], n_steps, deterministic, 0, counter0, 0, g, stream);
+}
+
+// what wg_yaw_table_act and wg_rollout_table refuse alike: a table for another turbine count or on another device
+static int table_fits(const char* who, const wg_env_s* h, wg_yaw_table tab) {
+    int N = 0, device = 0;
+    if (int rc = wg_yaw_table_geometry_(tab, &N, &device)) return rc;
+    if (N != h->p.N)
+        return wg_fail(WG_ERR_INVALID, std::string(who) + ": tab holds yaws of " + std::to_string(N) + " turbines, the handle's n_turb is " + std::to_string(h->p.N));
+    if (device != h->device) return wg_fail(WG_ERR_INVALID, std::string(who) + ": tab and handle live on different devices");
+    return 0;
+}
+
+extern "C" int wg_yaw_table_act(wg_handle h, wg_yaw_table tab, float* action_out, void* stream) {
+    if (!h) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_act: null handle");
+    if (!tab) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_act: tab is null");
+    if (!action_out) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_act: action_out is null");
+    if (int rc = table_fits("wg_yaw_table_act", h, tab)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
+    wg_launch_yaw_table_act_(tab, &h->p, &h->d, action_out, (hipStream_t)stream);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The table in the policy's place: wg_rollout's checks of the buffers, none of a policy, and rollout_loop with k_yaw_table_act as
+// a step's first launch.
+extern "C" int wg_rollout_table(wg_handle h, wg_yaw_table tab, int n_steps, const wg_rollout_bufs* o, void* stream) {
+    if (!h || !tab || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout_table: null argument");
+    if (int rc = table_fits("wg_rollout_table", h, tab)) return rc;
+    RolloutRows g = env_rows(h, o, "wg_rollout_table", h->p.obs_dim, "", o->obs, o->final_obs);
+    g.table = tab;
+    if (int rc = rollout_check(h, nullptr, n_steps, 1, g)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
+    return rollout_loop(h, nullptr, n_steps, 1, 0, 0, 0, g, stream);
 }
 
 extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,

@@ -17,6 +17,7 @@
 
 #include "../../include/windgym_hip.h"
 #include "wg_host.h"
+#include "wg_yaw_table.h"
 
 namespace {
 
@@ -147,8 +148,7 @@ __global__ __launch_bounds__(64) void k_expert_labels(const CurP p, double* __re
         double d = 0.0;
         for (int i = 0; i < N; ++i) {
             const double y = (double)prev[i], gi = g[i];
-            const double a = p.action_method == WG_ACT_YAW ? fmin(fmax((gi - y) / step, -1.0), 1.0) : (gi - lo) / (hi - lo) * 2.0 - 1.0;
-            labels[row * N + i] = (float)a;
+            labels[row * N + i] = (float)wg_expert_action(p.action_method, gi, y, lo, hi, step);
             d += fabs(y - gi);
         }
         if (yaw_diff) yaw_diff[row] = (float)(d / dN);

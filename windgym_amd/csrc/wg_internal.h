@@ -95,6 +95,10 @@ int wg_lstm_pop_step_(wg_lstm_pop q, int n_rows, const float* x_dev, const uint8
 int wg_lstm_pack_pop_(wg_lstm_pop q, const float* const* params_dev, void* stream);
 int wg_lstm_pop_slots_(wg_lstm_pop q, int n_rows, const uint64_t* seeds, const uint64_t* row_offsets, const float* h_pi, const float* h_vf,
                        const float* h_fin, const WgPopOuts* o, void* stream);
+// wg_yaw_table.hip: the turbine count a wg_yaw_table was created for and its device (wg_yaw_table_act's and wg_rollout_table's
+// checks); ONE launch of k_yaw_table_act — the table's action for every env's current wind and yaws -> action_out f32[B, N]
+int wg_yaw_table_geometry_(wg_yaw_table t, int* N, int* device);
+void wg_launch_yaw_table_act_(wg_yaw_table t, const WgParams* p, const WgPtrs* d, float* action_out, hipStream_t st);
 // wg_flow.hip
 void wg_launch_flow(const FlowP* p, const FlowPtrs* d, int mode, const float* actions, const uint8_t* mask, int chunk, hipStream_t st);
 void wg_launch_windspeed(const FlowP* p, const FlowPtrs* d, int e, int farm, const float* xs, int nx, const float* ys, int ny, float z,

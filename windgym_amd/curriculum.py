@@ -104,12 +104,18 @@ def lap_ms(t, device, timing, key):
     timing["_t"] = now
 
 
-def new_episode_targets(t, out, ep_row, optimize, no_targets, lap=lambda key: None):
+def new_episode_targets(t, out, ep_row, optimize, no_targets, lap=lambda key: None, table=None):
     """The new-episode plumbing of a rollout recorded with ``wind_f64`` (:meth:`YawCurriculum.rollout`,
     ``imitation.BehaviorCloning.collect``): the episodes that began inside it get their targets from ONE Serial-Refine launch over
     exactly their C wind conditions.  Fills ``ep_row [T, B]`` (int32: -1, or the row of the step's new episode, numbered in (t, env)
     order) -> ``(C, ep_target [C, N])`` (``no_targets`` when no env truncated).  ``optimize(ws, wd, ti) -> [C, N]`` float64;
-    ``lap(key)`` closes a part of the caller's timing split.  Compacting the flags is ONE host synchronisation."""
+    ``lap(key)`` closes a part of the caller's timing split.  Compacting the flags is ONE host synchronisation.
+
+    ``table`` (a ``yaw_table.YawTable``): the targets are the table's — ``ep_row`` becomes the table row of every new episode's wind
+    (ONE launch of k_yaw_table_rows) -> ``(table.n_rows, table.yaw)``: no ``nonzero()``, no Serial-Refine launch, no synchronisation."""
+    if table is not None:
+        table.rows(out["wind_f64"], out["truncated"], out=ep_row)
+        return table.n_rows, table.yaw
     idx = out["truncated"].view(-1).nonzero().view(-1)            # the rollout's one host synchronisation; sorted by (t, env)
     n_new = int(idx.numel())
     ep_row.fill_(-1)
@@ -130,10 +136,15 @@ class YawCurriculum:
     degrees — and ``reward_momentum``).  Construction and :meth:`reset` set every env's running target to the optimum of its
     current wind (``HipBatch.optimal_yaws``); ``targets`` is that table, ``[B, N]`` float64 on the device.  The shaping state (the
     wrapper's ``previous_yaws``, change history and ``last_reward``) is never cleared, as in the reference; :meth:`state` /
-    :meth:`load_state` checkpoint it.  ``PPO(..., curriculum=...)`` trains on the shaped reward."""
+    :meth:`load_state` checkpoint it.  ``PPO(..., curriculum=...)`` trains on the shaped reward.
+
+    ``targets=`` a ``yaw_table.YawTable`` of this env's farm and device: every target is the table's row of the episode's wind
+    instead.  Construction, :meth:`reset` and :meth:`rollout` then launch no Serial-Refine and synchronise nothing, the optimiser's
+    arguments are the table's own, and ``last_n_targets`` is ``None`` (counting the new episodes is the synchronisation this mode
+    removes).  The default, ``None``, is the optimiser per rollout."""
 
     def __init__(self, venv, curriculum_steps, pure_similarity_steps, model="blondel_jimenez", refine_pass_n=8, yaw_n=9,
-                 search_yaw_max=30.0, reward_momentum=0.9):
+                 search_yaw_max=30.0, reward_momentum=0.9, targets=None):
         from .binding import Curriculum
         from .steady import MODEL_IDS
         self.curriculum_steps, self.pure_similarity_steps = check_steps(curriculum_steps, pure_similarity_steps)
@@ -146,11 +157,16 @@ class YawCurriculum:
         if not getattr(venv, "as_torch", True):
             raise ValueError("YawCurriculum works on CUDA tensors: construct the env with as_torch=True")
         self.venv, self.batch, self.torch = venv, venv.batch, venv.batch.torch
+        self.table = targets
+        if targets is not None:
+            if not hasattr(targets, "check_env"):
+                raise ValueError("targets must be a yaw_table.YawTable (or None: the optimiser runs for every new episode)")
+            targets.check_env(venv, "YawCurriculum(targets=)")
         self.model, self.refine_pass_n, self.yaw_n = model, int(refine_pass_n), int(yaw_n)
         self.search_yaw_max, self.reward_momentum = float(search_yaw_max), float(reward_momentum)
         self._cur = Curriculum(self.batch)
         self._bufs = {}
-        self.last_n_targets = 0                       # Serial-Refine conditions the last rollout() served
+        self.last_n_targets = 0 if targets is None else None      # Serial-Refine conditions the last rollout() served (a table: not counted)
         self.last_rollout = None                      # the dict the last rollout() returned (valid until the next one)
         t, b = self.torch, self.batch
         self._yaw0 = t.zeros((b.B, b.N), dtype=t.float32, device=b.device)
@@ -168,6 +184,10 @@ class YawCurriculum:
     def reset(self):
         """``CurriculumWrapper.reset`` for the whole batch: every env's target becomes the optimum of its current wind.  The
         shaping state stays, as in the reference."""
+        if self.table is not None:
+            self.targets = self.table.targets(self.batch.info("wind_f64"))
+            self._cur.set_targets(self.targets)
+            return self.targets
         self.targets = self.batch.optimal_yaws(model=self.model, refine_pass_n=self.refine_pass_n, yaw_n=self.yaw_n,
                                                yaw_max=self.search_yaw_max).contiguous()
         self._cur.set_targets(self.targets)
@@ -199,7 +219,8 @@ class YawCurriculum:
         Episodes that began inside the rollout get their targets from ONE Serial-Refine launch over exactly those C wind
         conditions (none when no env truncated).  Finding them compacts the truncation flags (``nonzero``): ONE host
         synchronisation per rollout, after the closed loop has been enqueued — ``PPO.learn(log_interval=None)`` with a
-        curriculum is therefore not free of synchronisation, as it is without one.  The buffers are reused like
+        curriculum is therefore not free of synchronisation, as it is without one.  With ``targets=`` a ``YawTable`` neither
+        happens: the rows come from one k_yaw_table_rows launch and ``learn`` synchronises nothing again.  The buffers are reused like
         ``venv.rollout``'s: valid until the next call.  ``timing``: a dict that receives the milliseconds of the parts
         (``rollout``, ``serial_refine``, ``k_curriculum``, ``plumbing`` = everything else), measured between device
         synchronisations — tools/bench_ppo.py's split; it slows the call."""
@@ -224,13 +245,18 @@ class YawCurriculum:
             self._bufs[(T, bool(yaw_out))] = bufs
         bufs["weight"].copy_(t.from_numpy(w_host))
         ep_row = bufs["ep_row"]
-        n_new, ep_target = new_episode_targets(t, out, ep_row, self._optimize, self._no_targets, lambda key: self._lap(timing, key))
-        self.last_n_targets = n_new
+        n_new, ep_target = new_episode_targets(t, out, ep_row, self._optimize, self._no_targets, lambda key: self._lap(timing, key),
+                                               table=self.table)
+        self.last_n_targets = n_new if self.table is None else None
         self._lap(timing, "plumbing")
         self._cur.shape(T, self._yaw0, out["actions"], out["yaw_agent"], out["truncated"], ep_row, ep_target, n_new, bufs["weight"],
                         self.reward_momentum, out["reward"], bufs["shaped"], bufs["yaw_diff"], bufs["yaw_held"])
         self._lap(timing, "k_curriculum")
-        if n_new:
+        if self.table is not None:
+            # the mirror of the kernel's running targets: an env's target is always the table's row of its episode's wind, and the
+            # wind recorded after the last step is that of the episode the env is in now
+            self.table.targets(out["wind_f64"][T - 1], out=self.targets)
+        elif n_new:
             # the mirror of the kernel's running targets: rows are numbered in step order, so an env's LAST new episode has its largest
             last = ep_row.max(dim=0).values.long()
             self.targets = t.where((last >= 0).unsqueeze(1), ep_target[last.clamp(min=0)], self.targets)

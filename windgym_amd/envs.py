@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import copy
 import math
+import types
 import weakref
 from collections import deque
 from typing import Optional
@@ -324,8 +325,14 @@ class WindFarmVecEnv(_gym_vector_base()):
 
         ``policy`` may be a ``recurrent_population.RecurrentPopulation`` (or a ``RecurrentPPOPopulation``): wg_lstm_pop_rollout, the
         dict of a recurrent rollout with ``lstm_state0`` / ``lstm_state`` ``[P, nets, 2, Bm, H]`` — entry ``m`` is exactly the
-        member's tensor alone — and the state of the (population, env) pair kept as for one policy."""
+        member's tensor alone — and the state of the (population, env) pair kept as for one policy.
+
+        ``policy`` may be a ``yaw_table.YawTableAgent``: the table acts in the policy's place (wg_rollout_table, one lookup launch
+        per step).  Nothing is sampled or valued — the dict has no ``raw`` / ``logp`` / ``value`` / ``final_value``, ``deterministic``
+        and ``values`` mean nothing, the noise counter stays where it is.  ``sample_site`` is not supported with it."""
         b = self.batch
+        if getattr(policy, "yaw_table_agent", False):
+            return self._rollout_table(policy, n_steps, record)
         pop = getattr(policy, "population", None)      # a population / its trainer: wg_pop_rollout / wg_lstm_pop_rollout, member m on its envs
         if pop is not None and self.num_envs % pop.n_members:
             raise ValueError(f"rollout(): the {pop.n_members} members own equal shares of the envs: num_envs = {self.num_envs} "
@@ -337,6 +344,24 @@ class WindFarmVecEnv(_gym_vector_base()):
         return self._rollout(policy if pop is None else pop, n_steps, deterministic, record, values, rows=(self.num_envs,),
                              shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
                              slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout if pop is None else b.rollout_pop)
+
+    def _rollout_table(self, agent, n_steps, record):
+        """``rollout()`` of a ``yaw_table.YawTableAgent``: :meth:`_rollout` with wg_rollout_table as the loop.  Nothing is sampled or
+        valued: the dict has no ``raw`` / ``logp`` / ``value`` / ``final_value``, and the noise counter stays where it was."""
+        b = self.batch
+        if self._site is not None:
+            raise NotImplementedError("rollout(): a YawTableAgent with sample_site is not implemented")
+        tab = agent.table.check_env(self, "rollout()")
+        rows = types.SimpleNamespace(n_in=b.obs_dim, n_out=self.n_turb, has_critic=False, split=False, desc=dict(has_log_std=False))
+        steps = self._policy_steps
+        try:
+            out = self._rollout(rows, n_steps, True, record, False, rows=(self.num_envs,), shape=(b.obs_dim, self.n_turb), needs="",
+                                slots=(("obs", "final_obs", b.obs, b.final_obs),),
+                                run=lambda _, n, bufs, rec, *a: b.rollout_table(tab, n, {k: v for k, v in bufs.items() if k != "raw"}, rec))
+        finally:
+            self._policy_steps = steps
+        del out["raw"]
+        return out
 
     def _lstm_pair(self, policy):
         """This env's entry of the (policy, env) pair — [weakref, LSTM state, pending episode starts, buffers] — made on first use:
@@ -1218,6 +1243,8 @@ class WindFarmVecEnvMulti:
         ``[T, B]``."""
         if getattr(policy, "recurrent", False):
             raise NotImplementedError("WindFarmVecEnvMulti.rollout(): a recurrent policy (MlpLstmPolicy) shared by the turbines is not implemented")
+        if getattr(policy, "yaw_table_agent", False):
+            raise NotImplementedError("WindFarmVecEnvMulti.rollout(): a YawTableAgent is not implemented (it acts on a WindFarmVecEnv)")
         b = self.batch
         return self.venv._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs, self.n_turb),
                                   shape=(self.obs_len, 1),

@@ -50,6 +50,9 @@ class BehaviorCloning(Trainer):
 
     ``expert``: the wake model the optimiser runs on — ``"blondel_jimenez"`` (what ``PyWakeVecAgent`` steers by) or ``"m0"`` (the
     env's own); ``refine_pass_n`` x ``yaw_n`` candidates within ``search_yaw_max`` degrees, as ``YawCurriculum`` takes them.
+    ``expert`` may also be a ``yaw_table.YawTable`` of this env's farm and device: the targets are then the table's rows of the
+    episodes' winds — no Serial-Refine launch and no host synchronisation in :meth:`collect` (``last_n_targets`` is ``None``), the
+    optimiser's arguments are the table's own.
     ``policy``: an :class:`MlpPolicy` or ``"MlpPolicy"`` (built as ``PPO`` builds it, ``policy_kwargs`` included).
 
     ``loss="mse"`` (the default) is the mean squared error of the actor's mean; ``"nll"`` is the negative log-likelihood of the
@@ -63,7 +66,8 @@ class BehaviorCloning(Trainer):
     ``v_loss``, ``mean_abs_err``, ``mean_yaw_diff`` — the rollout's mean distance to the expert's yaws in degrees — and the episode
     means and ``fps`` of ``PPO``'s).  ``PPO(bc.policy, venv)`` fine-tunes: a fresh optimiser on the cloned weights.  ``save`` writes
     ``PPO``'s zip (``policy.pth`` that ``MlpPolicy.from_sb3_zip`` reads, Adam's state, the permutation generator, the counters)
-    plus the JSON key ``bc`` (the arguments above) and the running target table as ``bc_targets.npy``; :meth:`load` resumes
+    plus the JSON key ``bc`` (the arguments above), the running target table as ``bc_targets.npy`` and, when the expert is a
+    ``YawTable``, that table as ``bc_table.npz``; :meth:`load` resumes
     bit-identically on an env in the same state.
 
     Refused: a recurrent policy, a population, a split / central-critic policy (``NotImplementedError``); ``as_torch=False``, an
@@ -76,8 +80,11 @@ class BehaviorCloning(Trainer):
         check_env(venv, policy)
         if loss not in LOSSES:
             raise ValueError(f"BehaviorCloning: loss must be one of {list(LOSSES)}, not {loss!r}")
-        if not isinstance(expert, str) or expert not in MODEL_IDS:
-            raise ValueError(f"BehaviorCloning: expert must be one of {sorted(MODEL_IDS)}, not {expert!r}")
+        self.table = expert if hasattr(expert, "check_env") else None
+        if self.table is not None:
+            self.table.check_env(venv, "BehaviorCloning(expert=)")
+        elif not isinstance(expert, str) or expert not in MODEL_IDS:
+            raise ValueError(f"BehaviorCloning: expert must be one of {sorted(MODEL_IDS)} or a YawTable, not {expert!r}")
         if not float(vf_coef) >= 0.0 or not float(ent_coef) >= 0.0:
             raise ValueError("BehaviorCloning: vf_coef and ent_coef must be >= 0")
         self._setup(n_steps, n_epochs, gamma, gae_lambda, 0.0, ent_coef, vf_coef, max_grad_norm, learning_rate, False, seed, None, None, False)
@@ -113,7 +120,7 @@ class BehaviorCloning(Trainer):
         self._yaw_diff = t.zeros((n_steps, b.B), **f32)
         self._ep_row = t.zeros((n_steps, b.B), dtype=t.int32, device=b.device)
         self._no_targets = t.zeros((0, b.N), dtype=t.float64, device=b.device)
-        self.last_n_targets = 0                       # Serial-Refine conditions the last collect() served
+        self.last_n_targets = 0 if self.table is None else None      # Serial-Refine conditions the last collect() served (a table: not counted)
         self.reset_targets()
 
     def _optimize(self, ws, wd, ti):
@@ -123,6 +130,9 @@ class BehaviorCloning(Trainer):
     def reset_targets(self):
         """Every env's running target becomes the expert's yaws for its CURRENT wind (call it after resetting the env by hand);
         ``targets`` is that table, ``[B, N]`` float64 on the device, advanced in place by every :meth:`collect`."""
+        if self.table is not None:
+            self.targets = self.table.targets(self.batch.info("wind_f64"))
+            return self.targets
         self.targets = self.batch.optimal_yaws(model=self.expert, refine_pass_n=self.refine_pass_n, yaw_n=self.yaw_n,
                                                yaw_max=self.search_yaw_max).contiguous()
         return self.targets
@@ -140,8 +150,8 @@ class BehaviorCloning(Trainer):
         out = self.venv.rollout(self.policy, self.n_steps, deterministic=self.deterministic, record=("yaw_agent", "wind_f64"),
                                 values=self.vf_coef > 0.0)
         lap("rollout")
-        n_new, ep_target = new_episode_targets(self.torch, out, self._ep_row, self._optimize, self._no_targets, lap)
-        self.last_n_targets = n_new
+        n_new, ep_target = new_episode_targets(self.torch, out, self._ep_row, self._optimize, self._no_targets, lap, table=self.table)
+        self.last_n_targets = n_new if self.table is None else None
         lap("plumbing")
         self._lab.labels(self.n_steps, self._yaw0, out["yaw_agent"], out["truncated"], self._ep_row, ep_target, n_new, self.targets,
                          self._labels, self._yaw_diff)
@@ -182,7 +192,10 @@ class BehaviorCloning(Trainer):
     # -- checkpoints ----------------------------------------------------------------------------------------------
     def args(self):
         """The constructor's own arguments (what ``save`` stores under the JSON key ``bc``)."""
-        return {k: getattr(self, k) for k in ARGS}
+        args = {k: getattr(self, k) for k in ARGS}
+        if self.table is not None:
+            args["expert"] = None                     # (no JSON: the table travels as the member bc_table.npz)
+        return args
 
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself.  Synchronises; a bad ``ep_row`` entry that a
@@ -191,7 +204,8 @@ class BehaviorCloning(Trainer):
         self._lab.check()
         return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
                                 self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps,
-                                tensors={"bc_targets.npy": self.targets}, extra=dict(bc=self.args()))
+                                tensors={"bc_targets.npy": self.targets}, extra=dict(bc=self.args()),
+                                blobs={} if self.table is None else {"bc_table.npz": self.table.to_bytes()})
 
     @classmethod
     def load(cls, path, venv, learning_rate=None, device=None):
@@ -210,7 +224,11 @@ class BehaviorCloning(Trainer):
         pol.load_state_dict(tensors)
         pol.counter = int(meta["policy_counter"])
         hy = {k: v for k, v in meta["hyper"].items() if k not in ("clip_range", "normalize_advantage")}
-        self = cls(pol, venv, seed=meta["seed"], **meta["bc"], **hy)
+        bc = dict(meta["bc"])
+        if "bc_table.npz" in members:
+            from .yaw_table import YawTable
+            bc["expert"] = YawTable.from_bytes(members["bc_table.npz"], venv)
+        self = cls(pol, venv, seed=meta["seed"], **bc, **hy)
         self._restore(meta, members)
         self.targets = self.torch.from_numpy(np.ascontiguousarray(members["bc_targets.npy"], dtype=np.float64)).to(self.batch.device)
         return self

@@ -12,7 +12,7 @@ import json
 
 import numpy as np
 
-from .policy import refuse_recurrent
+from .policy import refuse_recurrent, refuse_table_agent
 
 ARGS = ("norm_obs", "norm_reward", "clip_obs", "clip_reward", "gamma", "epsilon", "training")
 
@@ -215,6 +215,7 @@ class VecNormalize:
         equivalent loop of ``act``, ``step``, wg_norm_obs from Python, as ``venv.rollout`` does).  ``normalize_reward=False`` leaves
         ``reward`` the env's and the return statistics untouched: :meth:`reward_pass` is then the caller's to run."""
         refuse_recurrent(policy, "VecNormalize.rollout()")
+        refuse_table_agent(policy, "VecNormalize.rollout()")
         if getattr(policy, "population", None) is not None:
             raise NotImplementedError("VecNormalize.rollout(): policy is a population — per-member statistics are not implemented")
         v, b = self.venv, self.batch

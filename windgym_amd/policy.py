@@ -208,6 +208,14 @@ def refuse_recurrent(policy, who):
                                   "venv.rollout(policy, T) and eval_sweep run it")
 
 
+def refuse_table_agent(policy, who):
+    """What the trainers, the populations and the wrappers say to a ``yaw_table.YawTableAgent`` (or a list holding one): it is a
+    scripted agent with nothing to train, sample or normalise for."""
+    if any(getattr(p, "yaw_table_agent", False) for p in (policy if isinstance(policy, (list, tuple)) else (policy,))):
+        raise NotImplementedError(f"{who}: a YawTableAgent is a scripted agent, not a policy: this is not implemented for it; "
+                                  "venv.rollout(agent, T), AgentEval and eval_sweep run it")
+
+
 def act_buffers(owner, n):
     """The persistent ``(action, raw, logp, value)`` outputs of ``act()`` on ``n`` rows, made once per ``n`` and kept in
     ``owner._out`` (``owner``: a policy or a population — ``torch``, ``device``, ``n_out``)."""

@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from .policy import act_buffers, device_tensor, refuse_recurrent
+from .policy import act_buffers, device_tensor, refuse_recurrent, refuse_table_agent
 from .ppo import PPO, PPOOptimizer, _schedule, check_batch_size, check_hyper, learn_loop, write_checkpoint
 
 POP_MAX = 16            # WG_POP_MAX
@@ -59,6 +59,7 @@ def check_population_shape(n_members, n_envs):
 def check_members(members):
     """The members as a list: 1 .. ``POP_MAX`` of them, no object twice."""
     members = list(members)
+    refuse_table_agent(members, "a population")
     check_member_count(len(members))
     for m, p in enumerate(members):
         for k in range(m):
@@ -183,6 +184,7 @@ class PPOPopulation:
 
     def _check_policy(self, policy):
         refuse_recurrent(policy, "PPOPopulation")
+        refuse_table_agent(policy, "PPOPopulation")
 
     def _minibatches(self, batch_size):
         """``batch_size`` as given -> (rows of a minibatch, width of a member's permutation, minibatches per epoch)."""

@@ -18,7 +18,7 @@ import zipfile
 
 import numpy as np
 
-from .policy import MlpPolicy, device_tensor, param_layout, refuse_recurrent
+from .policy import MlpPolicy, device_tensor, param_layout, refuse_recurrent, refuse_table_agent
 
 HYPER = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
          "learning_rate", "normalize_advantage")
@@ -316,13 +316,14 @@ def hyper_json(hyper):
 
 
 def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iteration, log, critic, env_policy_steps, curriculum=None,
-                     normalize=None, tensors=None, extra=None):
+                     normalize=None, tensors=None, extra=None, blobs=None):
     """The zip of :meth:`PPO.save` (format: the class docstring) from what it holds: the policy, its :class:`PPOOptimizer`, the
     permutation generator, the ``HYPER`` dict, the trainer's seed, its counters and log, the critic mode and the env's count of
     policy steps; with a ``curriculum`` (a ``YawCurriculum``) also its arguments (JSON key ``curriculum``) and its state blob
-    (member ``curriculum_state.bin``); with ``normalize`` (a ``VecNormalize``) its arguments (JSON key ``normalize``) and its state
+    (member ``curriculum_state.bin``) and, when its targets come from a ``YawTable``, that table (member
+    ``curriculum_table.npz``); with ``normalize`` (a ``VecNormalize``) its arguments (JSON key ``normalize``) and its state
     blob (member ``normalize_state.bin``); ``tensors``: {member name: tensor}, written as further npy members; ``extra``: further
-    keys of the JSON (``imitation.BehaviorCloning``: ``bc``)."""
+    keys of the JSON (``imitation.BehaviorCloning``: ``bc``); ``blobs``: {member name: bytes}, written as they are."""
     import torch
     mv, step = opt.state()
     sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
@@ -348,10 +349,14 @@ def write_checkpoint(path, policy, opt, gen, hyper, seed, num_timesteps, iterati
         z.writestr("windgym_ppo.json", json.dumps(meta))
         if curriculum is not None:
             z.writestr("curriculum_state.bin", curriculum.state())
+            if getattr(curriculum, "table", None) is not None:
+                z.writestr("curriculum_table.npz", curriculum.table.to_bytes())
         if normalize is not None:
             z.writestr("normalize_state.bin", normalize.state())
         for name, x in (tensors or {}).items():
             z.writestr(name, npy(x.detach().cpu().numpy()))
+        for name, x in (blobs or {}).items():
+            z.writestr(name, x)
     return path
 
 
@@ -485,7 +490,8 @@ class PPO(Trainer):
     iteration.  Not implemented (``NotImplementedError``): ``target_kl``, ``clip_range_vf``, ``use_sde``.
 
     ``curriculum``: a ``curriculum.YawCurriculum`` of this env, or a dict of its arguments — the reference's
-    examples/curriculum.py: rollouts come from ``curriculum.rollout`` (one host synchronisation per rollout, see there), GAE and the
+    examples/curriculum.py: rollouts come from ``curriculum.rollout`` (one host synchronisation per rollout, see there; none with
+    ``targets=`` a ``yaw_table.YawTable`` among the arguments, which ``save`` then stores as ``curriculum_table.npz``), GAE and the
     update run on the shaped reward, the log gains ``curriculum_weight`` (mean of the rollout) and ``mean_yaw_diff`` while
     ``mean_step_reward`` / ``mean_episode_return`` stay the env's own.  ``None`` changes nothing.
 
@@ -505,6 +511,7 @@ class PPO(Trainer):
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
                  seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None, normalize=None):
         refuse_recurrent(policy, "PPO")
+        refuse_table_agent(policy, "PPO")
         self._setup(n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
                     normalize_advantage, seed, target_kl, clip_range_vf, use_sde)
         n_steps = self.n_steps
@@ -620,6 +627,9 @@ class PPO(Trainer):
                         n_in_vf=desc["n_in_vf"])
         pol.load_state_dict(tensors)
         pol.counter = int(meta["policy_counter"])
+        if "curriculum_table.npz" in members:
+            from .yaw_table import YawTable
+            meta["curriculum"] = dict(meta["curriculum"], targets=YawTable.from_bytes(members["curriculum_table.npz"], venv))
         self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), curriculum=meta.get("curriculum"),
                    normalize=meta.get("normalize"), **meta["hyper"])   # (no key: written before there was one)
         if self.normalize is not None and "normalize_state.bin" in members:
