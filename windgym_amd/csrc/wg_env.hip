@@ -281,23 +281,15 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             // The glue's step-independent inputs, fetched now — the main wave's glue then has no load on its common path: the old
             // window sums and leaving samples of the glue lane's turbine, the deque entries this step's powers replace, the
             // metrics.  Nothing in this launch writes them before the glue does (the rings' leaving slots are not the slot the
-            // step pushes into: a ring holds one sample more than its deque).
+            // step pushes into: a ring holds one sample more than its deque).  (lean_early_load: the kernels without a pass wave
+            // request the same words at the head of their per-turbine tail.)
             const EnvKArgsPtr kz = (EnvKArgsPtr)wg_cold_args();
-            const WgParams& zp = *(const WgParams*)&kz->gp;
-            const WgPtrs& zd = *(const WgPtrs*)&kz->gd;
-#define WG_HDR_Z(f) __builtin_amdgcn_readlane(hw, (int)(offsetof(WgEnv, f) / 4))
-            const int z_np = WG_HDR_Z(n_pushed_live), z_fn = WG_HDR_Z(farm_pow_n), z_bn = WG_HDR_Z(base_pow_n);
-#undef WG_HDR_Z
-            const int PA = zp.power_avg;
-            const SumsRaw zr = wg_sums_load<false, false>(zp, zd, e, e * 2 + env_live, tid < N ? tid : 0, z_np);
-            const float z_fo = zd.farm_pow[(size_t)e * PA + z_fn % PA];
-            const float z_bo = F == 2 ? zd.base_pow[(size_t)e * PA + z_bn % PA] : 0.f;
-            const float z_met = tid < WG_N_METRICS ? zd.metrics[(size_t)e * WG_N_METRICS + tid] : 0.f;
+            const LeanEarly zr = lean_early_load(*(const WgParams*)&kz->gp, *(const WgPtrs*)&kz->gd, e, N, F, tid, hw);
             double* const zs = reinterpret_cast<double*>(zone);
 #pragma unroll
             for (int sI = 0; sI < WG_N_CH; ++sI) { zs[LEAN_PRE_S(sI, tid)] = zr.S[sI]; zone[LEAN_PRE_LV(sI, tid)] = zr.lv[sI]; }
-            zone[LEAN_PRE_MET(tid)] = z_met;
-            if (tid == 0) { zone[LEAN_PRE_FOLD] = z_fo; zone[LEAN_PRE_BOLD] = z_bo; }
+            zone[LEAN_PRE_MET(tid)] = zr.met;
+            if (tid == 0) { zone[LEAN_PRE_FOLD] = zr.f_old; zone[LEAN_PRE_BOLD] = zr.b_old; }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (tid == 0) env_flag_set(reinterpret_cast<int*>(zone) + LEAN_PRE_FLAG);
         }
@@ -466,6 +458,24 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
     lds_barrier<64>();
     WG_STAMP(1);
 
+    // (GLUE != 0, no pass wave) the glue's step-independent inputs by value: lean_early_load for this wave's glue lane, addresses
+    // from the header's LDS copy alone.  No store of this launch between a request and the glue touches the words: the walk at
+    // k_flow_env's barrier branch.  The rare long paths between the tail and the glue (clone, first observation, deferred set-up)
+    // request AGAIN at their ends instead of carrying 15 registers through themselves.
+    auto glue_early = [&]() __attribute__((always_inline)) {
+        if (GLUE != 0 && SPLIT == 0) {
+            if (WPE == 2 && wv != env_live) {
+                // (the background context's wave runs no glue: zeros — defined on this arm too, so still nothing is carried round
+                // the loop.  Its development steps have a short tail, and the next round's barrier waited for the whole trip:
+                // cfg4, whose launch ends with such waves taking two rounds, lost 4 % with the request in every wave.)
+                out.g_early = LeanEarly{};
+            } else {
+                const EnvKArgsPtr kz = (EnvKArgsPtr)wg_cold_args();
+                const int hwl = reinterpret_cast<const int*>(smem + WG_ENV_OFF_HDR)[tid & 31];
+                out.g_early = lean_early_load(*(const WgParams*)&kz->gp, *(const WgPtrs*)&kz->gd, e, N, F, tid, hwl);
+            }
+        }
+    };
     for (int round = 0;; ++round) {
         bool stepping, is_dev;
         int sub, K;
@@ -490,6 +500,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                     due_m &= ~(((1ull << N) - 1ull) << (kd * N));
                 }
                 lds_barrier<64>();
+                glue_early();      // (requested again: nothing of the last tail's request is carried through the clone)
             }
         }
         {
@@ -915,6 +926,12 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             if (stepping) reinterpret_cast<float4*>(wg_cold_args()->d.bnd)[(unsigned)((e * 2 * F + kbase) * N + g)].x = Lsrc2[g].x;
             return;
         }
+        // The glue's step-independent inputs, requested HERE: their round trip flies during this tail, the loop's re-check, the
+        // epilogue and the hand-over (no vector-memory wait in any of them), and the glue finds them landed (LeanFused::early).
+        // Defined unconditionally in every round's tail — no phi that would live through the next round's candidate pass,
+        // evaluation and advection (the loop exits at its top): a launch of several rounds simply requests again, a done env
+        // requests the same valid words for nothing, and the background context's wave (WPE 2) defines zeros (glue_early).
+        glue_early();
 
         // per-turbine tail: the step's emissions are in the ring now; power / thrust with the current yaw (model M0 step 5),
         // WindFarmEnv._take_measurements (Wind_Farm_Env.py:480-495) accumulated over the K sub-steps and, at the end of the env
@@ -1091,6 +1108,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             out.first_obs = 1;
             full_barrier<64>();                            // the ring pushes have left the wave
             env_first_obs<GLUE != 0>(bctx, np, tid);
+            glue_early();      // (requested again, as after the clone)
         }
     }
     if (defer_init) {
@@ -1103,6 +1121,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             my.dev_rem = slot.dev_remaining; my.fill_rem = slot.fill_remaining;
         }
         lds_barrier<64>();
+        glue_early();      // (requested again)
     }
 }
 
@@ -1149,8 +1168,10 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
         // next_obs / next_obs_ok, pend_farm / pend_base, slot words and — lean_swap's fallback — its rings and window sums), and
         // in the kernels with a pass wave, which stay as they were.  On every other step the glue takes what this launch produced
         // from the flow part's registers (LeanFused::regs: newest ring samples, yaw before / after, powers) and LDS (farm powers,
-        // the background slots' work, the header as the prologue loaded it), and its remaining loads are of words no store of
-        // the flow part aliases.  The walk through lean_step<., false, true> (the compiler checks none of this):
+        // the background slots' work, the header as the prologue loaded it), and its remaining inputs are words no store of
+        // the flow part aliases — without a pass wave they are requested at the head of the last round's per-turbine tail
+        // (env_flow: glue_early, lean_early_load) and arrive by value (LeanFused::early), so those loads sit IN FRONT of the
+        // tail's, the epilogue's and the rare paths' stores.  The walk through them (the compiler checks none of this):
         //   * wsum[live ctx] (old window sums): written by wg_sums_apply / the swaps alone — the glue itself; env_first_obs and
         //     the episode set-up write the BACKGROUND context's sums;
         //   * ring[live ctx], the leaving samples, row (np - W) % cap: the step pushed row np % cap, and W <= H < cap = H + 1
@@ -1159,6 +1180,21 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
         //     the swaps — the flow part writes step_farm_pow / step_base_pow and the background context's pend_farm / pend_base;
         //   * metrics[e]: the glue alone;
         //   * the parameter blocks and the kernel's arguments: never written.
+        // The stores that now FOLLOW a request (same wave, or the other wave of a WPE 2 env), each against those words:
+        //   * the tail's ring push, row np % cap of ring[ctx]: the live context's np is the header's n_pushed_live, the leaving
+        //     row is (np - W) % cap with 1 <= W <= H < cap, never the pushed row — also at W = H = 1, cap = 2, where it is the
+        //     pushed row's only neighbour; a background context's push goes to its own rings;
+        //   * the farm-ring push (fring): not among the words (no farm-level entries on this path: GEN = false);
+        //   * cur_ws / cur_wd, step_farm_pow / step_base_pow, pend_farm / pend_base, old_yaw: arrays of their own — the deques
+        //     the glue reads are farm_pow / base_pow, which the flow part never writes;
+        //   * the epilogue: turbine state (yaw, u, v, w, ti_loc, power, ct, bnd), slot and context headers — no window sum, ring
+        //     row, deque entry or metric;
+        //   * env_first_obs and the deferred set-up (wg_ctx_init): wsum, rings, next_obs, slots and headers of the BACKGROUND
+        //     context e * 2 + (live ^ 1) — the request is for context e * 2 + live; the clone copies particles between the two
+        //     farms of a developing (background) context.  Each of the three requests again at its end (glue_early), so the
+        //     values the glue takes were loaded after them anyway;
+        //   * a later round's request (K > 1, a background slot's second step) follows the live ring push of an earlier round:
+        //     the same rows as above, the same values.
         // Stores to a word both parts write (the background context's init_pending) leave the wave in program order.
         // env_first_obs and the deferred set-up keep their own barriers (env_flow); LDS still holds the slots' records.
         if (SPLIT != 0 || fo.truncates) full_barrier<64>();
@@ -1192,14 +1228,20 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
             if (WPE == 1) for (int f = 0; f < F; ++f) work = max(work, SLa[lb + f].dev_rem + K * SLa[lb + f].fill_rem);
             const int hw = reinterpret_cast<const int*>(sm + WG_ENV_OFF_HDR)[threadIdx.x & 31];
             LeanFused fz;
-            fz.pre = nullptr; fz.regs = SPLIT == 0;
+            fz.pre = nullptr; fz.regs = SPLIT == 0; fz.early = SPLIT == 0;
             // the glue's inputs: the step's own from the flow part's registers; the rest from the pass wave's fetch (long done) or,
-            // without a pass wave, by the glue's own loads
+            // without a pass wave, from the flow part's request at the head of its tail (by glue lane: no shuffle)
+            if (SPLIT == 0) fz.ev = fo.g_early;
             if (SPLIT) {
                 if (!env_flag_wait(reinterpret_cast<int*>(zone) + LEAN_PRE_FLAG)) atomicOr(kg->d.status, WG_STATUS_BIT_STATE);
                 fz.pre = zone;
             }
-            const int gl = (int)(threadIdx.x & 63), own = gl < kg->p.N ? gl : 0;
+            // (the glue's lane in a register of its own: as ONE value with the flow part's, `lane + 64` — the advection pass's request
+            // index, the glue's loops over farms of more than 64 turbines — was kept from the head of the round loop to the swap, and
+            // with the early request's registers beside it, spilled there)
+            int gl = (int)(threadIdx.x & 63);
+            asm volatile("" : "+v"(gl));
+            const int own = gl < kg->p.N ? gl : 0;
             if (WPE == 2) {      // (lane t of the live context's wave is the glue's lane t)
 #pragma unroll
                 for (int ch = 0; ch < WG_N_CH; ++ch) fz.nw[ch] = __shfl(fo.g_nw[ch], own, 64);
@@ -1212,7 +1254,7 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
                 fz.pw = __shfl(fo.g_pw, src, 64); fz.pwb = __shfl(fo.g_pwb, src, 64);
             }
             WG_STAMP(12);
-            env_glue<GLUE, WPE>(kg, fz, fp, bp, work, fo, hw);
+            env_glue<GLUE, WPE>(kg, fz, fp, bp, work, fo, hw, gl);
             WG_STAMP(13);
         }
     }

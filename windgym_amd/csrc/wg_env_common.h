@@ -165,6 +165,9 @@ struct EnvFlowOut {          // what the flow part hands to the glue tail of k_s
     // (k_flow_env with a glue tail, the lanes of the running episode's agent farm) per-lane values of the step for the glue: the
     // samples the lane's turbine pushed into its rings, its yaw before / after, its power and its baseline twin's
     float g_nw[WG_N_CH], g_yaw, g_old, g_pw, g_pwb;
+    // (k_flow_env with a glue tail and no pass wave, by GLUE lane) the glue's step-independent inputs, requested at the head of the
+    // last flow round's per-turbine tail (lean_early_load)
+    LeanEarly g_early;
 };
 
 // ---- the tail of the one-launch kernels (k_flow_env / k_flow_envb<., GLUE != 0>), after the flow part ---------------------------
@@ -184,17 +187,18 @@ __device__ __forceinline__ void env_bg_plan(const EnvKArgsPtr kb, const int work
 // The glue (lean_step) as the tail of the live wave's flow step.  fp / bp: the step's farm powers (agent / baseline farm); work:
 // the background context's remaining work where this wave plans it (WPE 1), else 0; hw: the lane's word of the env header as the
 // prologue loaded it; fz: `pre` and what goes with it, set by the caller (k_flow_env's pass-wave zone, or nullptr).
+// lane: the wave's lane, 0 .. 63 (k_flow_env hands in its own copy, see there).
 // (kg: the glue's parameter blocks are read where they are used, through the opaque kernarg pointer: by value they were all
 // fetched at the kernel's entry and 130 of them parked in VGPR lanes across the flow step.)
 template <int GLUE, int WPE>
 __device__ __forceinline__ void env_glue(const EnvKArgsPtr kg, LeanFused& fz, const float fp, const float bp, const int work,
-                                         const EnvFlowOut& fo, const int hw) {
+                                         const EnvFlowOut& fo, const int hw, const int lane = (int)(threadIdx.x & 63)) {
     fz.fp = fp; fz.bp = bp; fz.work = work;
     fz.bg_init_pending = WPE >= 2 ? 0 : fo.bg_init_pending;
     fz.plan_elsewhere = WPE >= 2;
     fz.hw = hw;
     lean_step<GLUE == 2, false, true>(*(const WgParams*)&kg->gp, *(const WgPtrs*)&kg->gd, kg->d.gp, kg->d.gd, (int)blockIdx.x,
-                                      (int)(threadIdx.x & 63), kg->obs, kg->reward, kg->trunc, kg->final_obs, nullptr, fz);
+                                      lane, kg->obs, kg->reward, kg->trunc, kg->final_obs, nullptr, fz);
 }
 
 // host: a kernel of either family, as its launch table hands it out

@@ -1115,7 +1115,7 @@ k_flow_envb(const FlowP p_, const FlowPtrs d_, const int mode, const float* __re
                 if (WPE == 1) for (int f = 0; f < F; ++f) work = max(work, SLa[lb + f].dev_rem + K * SLa[lb + f].fill_rem);
             }
             LeanFused fz;
-            fz.pre = nullptr; fz.regs = 0;      // (no hand-over here: the glue reads the step's values back, behind the barrier above)
+            fz.pre = nullptr; fz.regs = 0; fz.early = 0;      // (no hand-over here: the glue reads the step's values back, behind the barrier above)
             env_glue<GLUE, WPE>(kg, fz, fp, bp, work, fo, reinterpret_cast<const int*>(sm + LO::HDR)[threadIdx.x & 31]);
         }
     }

@@ -303,8 +303,34 @@ __device__ __attribute__((noinline)) void lean_swap(const WgParams* gp, const Wg
 __device__ __forceinline__ int wg_uni(const int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ float wg_uni(const float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
+// The glue's step-independent inputs, for the glue lane `lane` of env e: the old window sums and leaving samples of the lane's
+// turbine, the deque entries this step's powers replace, the lane's metric.  Nothing but the glue itself (and the swaps) writes
+// these words, so a step kernel may request them long before its glue runs (the walk: k_flow_env, wg_env.hip).  Their addresses
+// need the env header alone — `hw`: word (lane & 31) of it, as loaded before any wave of the launch can have rewritten it.
+// Stated once for both users: k_flow_env's pass wave (head of the launch, parked in its LDS zone) and the kernels without one
+// (head of the per-turbine tail, kept in registers: LeanFused::early).  N, F: the farm's shape as the caller holds it.
+struct LeanEarly {
+    double S[WG_N_CH];
+    float lv[WG_N_CH], f_old, b_old, met;
+};
+__device__ __forceinline__ LeanEarly lean_early_load(const WgParams& p, const WgPtrs& d, const int e, const int N, const int F,
+                                                     const int lane, const int hw) {
+#define WG_HDR_Z(f) __builtin_amdgcn_readlane(hw, (int)(offsetof(WgEnv, f) / 4))
+    const int z_live = WG_HDR_Z(live), z_np = WG_HDR_Z(n_pushed_live), z_fn = WG_HDR_Z(farm_pow_n), z_bn = WG_HDR_Z(base_pow_n);
+#undef WG_HDR_Z
+    const int PA = p.power_avg;
+    const SumsRaw zr = wg_sums_load<false, false, true>(p, d, e, e * 2 + z_live, lane < N ? lane : 0, z_np);      // (a turbine: lane < N)
+    LeanEarly q;
+#pragma unroll
+    for (int s = 0; s < WG_N_CH; ++s) { q.S[s] = zr.S[s]; q.lv[s] = zr.lv[s]; }
+    q.f_old = d.farm_pow[(size_t)e * PA + z_fn % PA];
+    q.b_old = F == 2 ? d.base_pow[(size_t)e * PA + z_bn % PA] : 0.f;
+    q.met = lane < WG_N_METRICS ? d.metrics[(size_t)e * WG_N_METRICS + lane] : 0.f;
+    return q;
+}
+
 struct LeanFused {
-    float fp, bp;             // farm power of the step: agent farm, baseline farm (WgPtrs::step_farm_pow / step_base_pow)
+    float fp, bp;           // farm power of the step: agent farm, baseline farm (WgPtrs::step_farm_pow / step_base_pow)
     int work;                 // remaining development work of the background episode: max over its farms of dev + K * fill
     int bg_init_pending;      // the background context's set-up flag was pending at the head of this launch
     int plan_elsewhere;       // the background context's own wave plans its next share (WgEnv::shadow_iters) unless the env truncates
@@ -320,6 +346,11 @@ struct LeanFused {
     // through them: k_flow_env, wg_env.hip).
     int regs;
     float nw[WG_N_CH], yaw, old_yaw, pw, pwb;
+    // k_flow_env without a pass wave (`early`, with `regs`): what the step did not touch arrives BY VALUE too — the flow part
+    // requested it at the head of its per-turbine tail (lean_early_load), and the trip flew during the tail and the epilogue.
+    // NO load left on the glue's common path; the truncating step keeps its barrier and the swap's loads.  0: off.
+    int early;
+    LeanEarly ev;
 };
 // LDS zone of the pre-fetched glue inputs (floats; lane = the glue's lane): S[s] as doubles | lv[s] | metrics | deque entries | flag
 #define LEAN_PRE_S(s, lane) ((s) * 64 + (lane))                    // index into (const double*)pre
@@ -390,6 +421,7 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
     // ---- every load of the step, issued together ----
     const bool pre = FUSED && !GEN && fz.pre != nullptr;
     const bool regs = FUSED && !GEN && !pre && fz.regs != 0;
+    const bool early = regs && fz.early != 0;
     SumsRaw raw;
     // (farms with more than 64 turbines, cfg3: the lane's SECOND turbine is requested with the first — the observation loop
     // below would otherwise take a second memory round trip for it)
@@ -414,6 +446,14 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
         }
         f_old = wg_uni(fz.pre[LEAN_PRE_FOLD]); b_old = F == 2 ? wg_uni(fz.pre[LEAN_PRE_BOLD]) : 0.f;
         l_met = lane < WG_N_METRICS ? fz.pre[LEAN_PRE_MET(lane)] : 0.f;
+    } else if (early) {
+        // (by value: lean_early_load has masked the slots and the metric lanes as the loads below would)
+#pragma unroll
+        for (int s = 0; s < WG_N_SUMS; ++s) { raw.S[s] = 0.0; raw.lv[s] = 0.f; }
+#pragma unroll
+        for (int s = 0; s < WG_N_CH; ++s) { raw.S[s] = fz.ev.S[s]; raw.lv[s] = fz.ev.lv[s]; }
+        f_old = wg_uni(fz.ev.f_old); b_old = F == 2 ? wg_uni(fz.ev.b_old) : 0.f;
+        l_met = fz.ev.met;
     } else {
         raw = regs ? wg_sums_load<GEN, false>(p, d, e, ctx_id, own, n_pushed_live) : wg_sums_load<GEN>(p, d, e, ctx_id, own, n_pushed_live);
         if (have2) raw2 = wg_sums_load<GEN>(p, d, e, ctx_id, lane + WG_WAVE, n_pushed_live);

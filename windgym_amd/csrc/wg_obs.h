@@ -217,9 +217,13 @@ __device__ __forceinline__ int wg_umod(int n, int H, unsigned magic) {
 struct SumsEnt {            // where entity `ent` lives
     const float* rb; int stride; bool farm; unsigned sm, cm;
 };
+// (TURB: the caller's entity is a turbine, never the farm-level one — a per-lane `ent == N` makes every choice between a turbine's
+// and the farm's parameter a per-lane one, and the compiler fetches such a parameter with a VECTOR load from the argument block,
+// waited for before the ring address can be formed: a second round trip in front of the leaving samples)
+template <bool TURB = false>
 __device__ __forceinline__ SumsEnt wg_sums_ent(const WgParams& p, const WgPtrs& d, const int ctx_id, const int ent) {
     SumsEnt q;
-    q.farm = ent == p.N;
+    q.farm = TURB ? false : ent == p.N;
     q.rb = q.farm ? d.fring + (size_t)ctx_id * p.fring_stride : d.ring + (size_t)ctx_id * p.ring_stride + ent;
     q.stride = q.farm ? 1 : p.N;
     q.sm = q.farm ? p.sum_mask_f : p.sum_mask_t;
@@ -229,11 +233,11 @@ __device__ __forceinline__ SumsEnt wg_sums_ent(const WgParams& p, const WgPtrs& 
 // the loads of one step's update: `np` pushes are in the sums, the flow kernel has pushed sample number np since
 // (NEWEST = false: only what does not depend on the step in flight — the old sums and the leaving samples; k_flow_env's pass wave
 // fetches those while the step runs)
-template <bool GEN, bool NEWEST = true>
+template <bool GEN, bool NEWEST = true, bool TURB = false>
 __device__ inline SumsRaw wg_sums_load(const WgParams& p, const WgPtrs& d, const int e, const int ctx_id, const int ent, const int np) {
     constexpr int NSL = GEN ? WG_N_SUMS : WG_N_CH;        // (without TI entries only the four window slots exist)
     SumsRaw r;
-    const SumsEnt q = wg_sums_ent(p, d, ctx_id, ent);
+    const SumsEnt q = wg_sums_ent<TURB>(p, d, ctx_id, ent);
     const int NS = p.N + 1;
     const double* ws_ = d.wsum + (size_t)ctx_id * WG_N_SUMS * NS + ent;
     const unsigned ti = GEN ? q.sm >> WG_SUM_TI1 : 0u;      // (the TI slots read the ws channel)
