@@ -453,7 +453,7 @@ def test_refusals():
     z = lambda *shape, dtype=t.float32: t.zeros(shape, dtype=dtype, device=b.device)          # noqa: E731
     bufs = dict(obs=z(T + 1, B, O), actions=z(T, B, N), raw=z(T, B, N), logp=z(T, B), value=z(T, B), final_obs=z(T, B, O),
                 final_value=z(T, B), reward=z(T, B), truncated=z(T, B, dtype=t.uint8), norm_obs=z(T + 1, B, O), norm_final_obs=z(T, B, O))
-    run = lambda n, bf: b.rollout_norm(n, p, T, bf, (), False, 0, 0, 0)                       # noqa: E731
+    run = lambda n, bf: b.rollout("wg_rollout_norm", (p._h, n._h), T, bf, (), (False, 0, 0, 0), tail=("norm_obs", "norm_final_obs"))   # noqa: E731
     state = b.get_state()
     for n_obs, n_envs in ((O + 1, B), (O, B + 1)):
         n = _norm(n_obs, n_envs)

@@ -349,7 +349,7 @@ def test_refusals(small_env):
     state = big.batch.get_state()
     assert state != before
     with pytest.raises(ValueError, match=f"wg_rollout_table: tab holds yaws of {N} turbines"):
-        big.batch.rollout_table(tab._tab, 2, bufs, ())
+        big.batch.rollout("wg_rollout_table", (tab._tab._h,), 2, bufs, ())
     for call, msg in ((lambda: agent.predict(None), f"table holds yaws of {N} turbines"), (lambda: big.rollout(agent, 2), f"table holds yaws of {N} turbines"),
                       (lambda: YawCurriculum(big, 100, 10, targets=tab), rf"YawCurriculum\(targets=\): table holds yaws of {N} "),
                       (lambda: BehaviorCloning("MlpPolicy", big, expert=tab), rf"BehaviorCloning\(expert=\): table holds yaws of {N} "),
@@ -364,9 +364,9 @@ def test_refusals(small_env):
                      (dict(plain, final_value=bufs["final_value"]), "must be NULL"),
                      ({k: x for k, x in plain.items() if k != "obs"}, "wg_rollout_table: obs, actions, reward and truncated buffers are required")):
         with pytest.raises(ValueError, match=msg):
-            big.batch.rollout_table(tab16._tab, 2, bad, ())
+            big.batch.rollout("wg_rollout_table", (tab16._tab._h,), 2, bad, ())
     with pytest.raises(ValueError, match="wg_rollout_table: n_steps < 0"):
-        big.batch.rollout_table(tab16._tab, -1, plain, ())
+        big.batch.rollout("wg_rollout_table", (tab16._tab._h,), -1, plain, ())
     with pytest.raises(ValueError, match="unknown info field"):
         big.rollout(YawTableAgent(tab16, env=big), 2, record=("no_such_field",))
     with pytest.raises(ValueError, match="n_steps must be >= 1"):

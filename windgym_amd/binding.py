@@ -408,77 +408,34 @@ class HipBatch:
             _chk(rc, "wg_step")
         return self.obs, self.reward, self.truncated, self.final_obs
 
-    ROLLOUT_KEYS = ("obs", "actions", "raw", "logp", "value", "final_obs", "final_value", "reward", "truncated")   # wg_rollout_bufs
+    # a rollout's ``bufs`` are keyed by the field names of wg_rollout_bufs; these fields go by another key
+    MULTI_KEYS = {"obs_multi": "obs", "final_obs_multi": "final_obs", "obs": "flat_obs", "final_obs": "flat_final_obs"}   # wg_rollout_multi_bufs
+    LSTM_KEYS = {"state": "lstm_state", "state0": "lstm_state0", "scratch": "lstm_scratch"}                             # wg_rollout_lstm_bufs
 
-    @staticmethod
-    def _rollout_bufs(cls, keys, bufs, record):
-        """``cls`` (wg_rollout_bufs / wg_rollout_multi_bufs) from contiguous CUDA tensors: ``bufs[k]`` for its pointer fields in
-        order (``keys``; a missing one is NULL = not wanted), ``bufs[name]`` for every info name in ``record``."""
-        n = len(record)
-        return cls(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n,
-                   (C.c_int32 * max(1, n))(*[INFO[r] for r in record]), (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))
-
-    def _rollout(self, entry, cls, keys, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
-        """The closed loop ``entry`` (wg_rollout / wg_rollout_multi) into the tensors of :meth:`_rollout_bufs`."""
-        cb = self._rollout_bufs(cls, keys, bufs, record)
-        _chk(getattr(self.L, entry)(self._h, policy._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
-                                    C.byref(cb), self._stream()), entry)
-
-    def rollout(self, *args):
-        """wg_rollout(policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset); ``bufs`` keyed by wg_rollout_bufs' fields."""
-        self._rollout("wg_rollout", CRolloutBufs, self.ROLLOUT_KEYS, *args)
-
-    def rollout_table(self, table, n_steps, bufs, record):
-        """wg_rollout_table: a :class:`YawTableHandle` in the policy's place; ``bufs`` as for :meth:`rollout`, without ``raw`` /
-        ``logp`` / ``value`` / ``final_value`` (the library refuses them)."""
-        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        _chk(self.L.wg_rollout_table(self._h, table._h, int(n_steps), C.byref(cb), self._stream()), "wg_rollout_table")
-
-    def rollout_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
-        """wg_pop_rollout, the arguments of :meth:`rollout` with a ``population.Population`` in the policy's place: every member
-        samples with the one ``seed``, member ``m``'s noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
-        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        seeds, offs = self._pop_noise(pop, seed, row_offset)
-        _chk(self.L.wg_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), seeds, counter0, offs, C.byref(cb), self._stream()),
-             "wg_pop_rollout")
-
-    def _pop_noise(self, pop, seed, row_offset):
-        """``seeds[P]`` / ``row_offsets[P]`` of a population's rollout that samples as ONE policy on the whole batch would."""
-        P = pop.n_members
-        return (C.c_uint64 * P)(*[int(seed)] * P), (C.c_uint64 * P)(*[int(row_offset) + m * (self.B // P) for m in range(P)])
-
-    @staticmethod
-    def _lstm_bufs(bufs):
-        return CRolloutLstmBufs(*[bufs[k].data_ptr() for k in ("lstm_state", "lstm_state0", "episode_start", "lstm_scratch")])
-
-    def rollout_norm(self, norm, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
-        """wg_rollout_norm, the arguments of :meth:`rollout` after a :class:`Norm`: ``bufs`` also holds ``norm_obs`` ``[T+1, B, O]``
-        (slot 0 is input) and ``norm_final_obs`` ``[T, B, O]``, the rows the policy reads."""
-        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        _chk(self.L.wg_rollout_norm(self._h, policy._h, norm._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
-                                    C.byref(cb), bufs["norm_obs"].data_ptr(), bufs["norm_final_obs"].data_ptr(), self._stream()),
-             "wg_rollout_norm")
-
-    def rollout_lstm(self, policy, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
-        """wg_rollout_lstm, the arguments of :meth:`rollout` with a ``recurrent.MlpLstmPolicy``: ``bufs`` also holds ``lstm_state``
-        (in / out), ``lstm_state0``, ``episode_start`` ``[T+1, B]`` (slot 0 is input) and ``lstm_scratch``."""
-        cb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record)
-        lb = self._lstm_bufs(bufs)
-        _chk(self.L.wg_rollout_lstm(self._h, policy._lstm, policy.mlp._h, int(n_steps), int(bool(deterministic)), seed, counter0, row_offset,
-                                    C.byref(cb), C.byref(lb), self._stream()), "wg_rollout_lstm")
-
-    def rollout_lstm_pop(self, pop, n_steps, bufs, record, deterministic, seed, counter0, row_offset):
-        """wg_lstm_pop_rollout, the arguments of :meth:`rollout_lstm` with a ``recurrent_population.RecurrentPopulation`` in the policy's
-        place (``lstm_state`` / ``lstm_state0`` ``[P, nets, 2, Bm, H]``): every member samples with the one ``seed``, member ``m``'s
-        noise rows start at ``row_offset + m * Bm`` — the noise of one policy."""
-        cb, lb = self._rollout_bufs(CRolloutBufs, self.ROLLOUT_KEYS, bufs, record), self._lstm_bufs(bufs)
-        seeds, offs = self._pop_noise(pop, seed, row_offset)
-        _chk(self.L.wg_lstm_pop_rollout(self._h, pop._h, int(n_steps), int(bool(deterministic)), seeds, counter0, offs, C.byref(cb), C.byref(lb),
-                                        self._stream()), "wg_lstm_pop_rollout")
-
-    def rollout_multi(self, *args):
-        """wg_rollout_multi, same arguments: ``obs`` / ``final_obs`` are the per-agent rows, ``flat_obs`` / ``flat_final_obs`` the flat ones."""
-        self._rollout("wg_rollout_multi", CRolloutMultiBufs, self.ROLLOUT_KEYS + ("flat_obs", "flat_final_obs"), *args)
+    def rollout(self, entry, handles, n_steps, bufs, record, noise=None, members=None, tail=()):
+        """The closed-loop entry ``entry`` (windgym_hip.h: wg_rollout, wg_rollout_multi, wg_rollout_norm, wg_rollout_table,
+        wg_pop_rollout, wg_rollout_lstm, wg_lstm_pop_rollout) on ``handles``, the raw handles its signature names after the env's.
+        ``bufs``: contiguous CUDA tensors, one per pointer field of the buffer structs the entry takes, in the order of their
+        ``_fields_`` (a missing one of wg_rollout_bufs / wg_rollout_multi_bufs is NULL = not wanted), one per info name in
+        ``record``, and one per key in ``tail``, the pointers that end the signature.  ``noise``: ``(deterministic, seed, counter0,
+        row_offset)``, or None for an entry that samples nothing; with ``members = P`` the per-member arrays of a population that
+        samples as ONE policy on the whole batch would: every member the one seed, member ``m``'s rows from ``row_offset + m * B / P``."""
+        fn = getattr(self.L, entry)
+        multi = C.POINTER(CRolloutMultiBufs) in fn.argtypes
+        cls, n = CRolloutMultiBufs if multi else CRolloutBufs, len(record)
+        keys = [self.MULTI_KEYS.get(f, f) if multi else f for f, ty in cls._fields_ if ty is C.c_void_p]
+        structs = [cls(*[bufs[k].data_ptr() if k in bufs else None for k in keys], n, (C.c_int32 * max(1, n))(*[INFO[r] for r in record]),
+                       (C.c_void_p * max(1, n))(*[bufs[r].data_ptr() for r in record]))]
+        if C.POINTER(CRolloutLstmBufs) in fn.argtypes:
+            structs.append(CRolloutLstmBufs(*[bufs[self.LSTM_KEYS.get(f, f)].data_ptr() for f, _ in CRolloutLstmBufs._fields_]))
+        if noise is not None:
+            deterministic, seed, counter0, row_offset = noise
+            if members:
+                P = int(members)
+                seed, row_offset = (C.c_uint64 * P)(*[int(seed)] * P), (C.c_uint64 * P)(*[int(row_offset) + m * (self.B // P) for m in range(P)])
+            noise = (int(bool(deterministic)), seed, counter0, row_offset)
+        _chk(fn(self._h, *handles, int(n_steps), *(noise or ()), *[C.byref(x) for x in structs], *[bufs[k].data_ptr() for k in tail],
+                self._stream()), entry)
 
     def set_step_graph(self, enable=True):
         """step() as one hipGraphLaunch (captured per distinct set of I/O pointers) instead of direct launches."""

@@ -811,45 +811,63 @@ static size_t info_bytes(const wg_env_s* h, int field) {
     }
 }
 
-// The closed loop policy -> step -> record (windgym_hip.h: wg_rollout, wg_rollout_multi) exists once; this is what differs
-// between the two entries and, for wg_rollout_multi, between its per-agent and its central mode.
+// The closed loop policy -> step -> record (windgym_hip.h: the wg_rollout* entries) exists once: rollout_loop.  An entry describes
+// its call in two parts, each filled by name: the rows (RolloutRows: the env side) and what acts on them (RolloutActor).
+//
+// The env side: which rows the steps write and the actor reads, how many per env, what the critic reads, the messages' names.
 struct RolloutRows {
-    const char *who, *obs_name;    // prefix of every message; the buffer the policy reads, as the messages name it
-    int per_env, n_in, n_out;      // policy rows per env; the shape the policy must have ...
+    const char *who, *obs_name;    // prefix of every message; the buffer the actor reads, as the messages name it
+    int per_env, width, n_out;     // actor rows per env, their width, actions per row
+    int n_in;                      // the inputs a policy must map: `width`, or the hidden size of the LSTMs in front of it ...
     std::string needs;             // ... and the end of the message that says so
     const char* unready;           // non-null: refused with this message
-    bool per_agent;                // the steps write the policy's rows through WgPtrs::multi_out / multi_fin, re-aimed per step
+    bool per_agent;                // the steps write the actor's rows through WgPtrs::multi_out / multi_fin, re-aimed per step
     wg_rollout_multi_bufs o;       // obs_multi / final_obs_multi: what the ACTOR reads; obs / final_obs: the steps' flat rows
     // what the CRITIC reads: v_env rows per env of v_in inputs, slots [T+1] of v_obs and [T] of v_fin (null: no final rows given,
     // named fin_name in the refusal) — the actor's own rows, or the flat rows under a centralised critic
     int v_env, v_in;
     const float *v_obs, *v_fin;
     const char* fin_name;
-    // non-null: a population acts in the policy's place (wg_pop_rollout) — its slot table is prepared for these buffers, and a
-    // step's one launch of the policy kernel is wg_pop_launch_ on it instead of wg_policy_eval_
-    wg_pop_s* pop;
-    // non-null: the policy's rows are NORMALISED copies of the steps' flat rows (wg_rollout_norm) — after every step the
+    // non-null: the actor's rows are NORMALISED copies of the steps' flat rows (wg_rollout_norm) — after every step the
     // observation half of this wg_norm is enqueued: o.obs[t + 1] -> o.obs_multi[t + 1], o.final_obs[t] -> o.final_obs_multi[t]
     wg_norm_s* norm;
-    // non-null: a recurrent policy (wg_rollout_lstm) — the observation rows go through this wg_lstm first (state and episode starts
-    // in `lb`), and the policy, which maps the LSTM's hidden size, reads the h' rows of lb->scratch instead of the observations
-    wg_lstm_s* lstm;
-    const wg_rollout_lstm_bufs* lb;
-    // non-null: a population of recurrent policies (wg_lstm_pop_rollout) — `lstm` is member 0's (the members share its shape), the
-    // LSTMs' launches are wg_lstm_pop_step_ on lb's state in the population's layout, and `pop` is its heads' slot table
-    wg_lstm_pop_s* lpop;
-    // non-null: a yaw table acts in the policy's place (wg_rollout_table) — a step's one launch of the policy kernel is
-    // k_yaw_table_act on the env's current wind and yaws; there is no policy, so nothing of one is checked, sampled or valued
-    wg_yaw_table_s* table;
 };
 
-static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, int deterministic, const RolloutRows& g) {
+// The LSTMs in front of a recurrent actor's heads (wg_rollout_lstm: `lstm`; wg_lstm_pop_rollout: `lpop`, `lstm` its member 0's) and
+// the layout of their scratch [3, B, H], stated here once: the heads read the h' rows of the step — h_pi the actor, h_vf the critic,
+// h_fin the critic on the final rows — and a shared LSTM's critic reads h_pi (its "critic net" is the one net it has).
+struct RolloutLstm {
+    wg_lstm_s* lstm;               // null: no front stage
+    wg_lstm_pop_s* lpop;
+    const wg_rollout_lstm_bufs* lb;
+    int B, H, nets;
+    bool two() const { return nets == 2; }
+    size_t sH() const { return (size_t)B * H; }
+    float* h_pi() const { return lb->scratch; }
+    float* h_vf() const { return two() ? h_pi() + sH() : h_pi(); }
+    float* h_fin() const { return h_pi() + 2 * sH(); }
+};
+
+// What acts: a step's ONE act launch (`act`, chosen by the entry), its noise, and the optional front stage.  Built by name; a
+// member an entry does not name is zero.
+struct RolloutActor {
+    enum Act { POLICY, POPULATION, TABLE } act;
+    wg_policy_s* p;                // POLICY: the policy; POPULATION: member 0, checked in every member's place; TABLE: null
+    wg_pop_s* pop;                 // POPULATION: the slot table, prepared for these buffers (it carries the members' seeds and row offsets)
+    wg_yaw_table_s* table;         // TABLE: k_yaw_table_act on the env's current wind and yaws; nothing is sampled or valued
+    int deterministic;
+    uint64_t seed, counter0, row_offset;      // (a population's entries leave seed and row_offset 0: the slot table carries the members' own)
+    RolloutLstm front;
+};
+
+static int rollout_check(const wg_env_s* h, int n_steps, const RolloutRows& g, const RolloutActor& a) {
     const wg_rollout_multi_bufs& o = g.o;
+    const wg_policy_s* p = a.p;
     const std::string who = std::string(g.who) + ": ";
     if (n_steps < 0) return wg_fail(WG_ERR_INVALID, who + "n_steps < 0");
     if (!o.obs_multi || !o.actions || !o.reward || !o.truncated)
         return wg_fail(WG_ERR_INVALID, who + g.obs_name + ", actions, reward and truncated buffers are required");
-    if (g.table) {
+    if (!p) {      // (no policy: nothing of one is checked)
         if (o.raw || o.logp || o.value || o.final_value)
             return wg_fail(WG_ERR_INVALID, who + "raw, logp, value and final_value must be NULL: a yaw table samples nothing and has no critic");
     } else {
@@ -861,7 +879,7 @@ static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, i
         if (!g.v_obs) return wg_fail(WG_ERR_INVALID, who + "a centralised critic reads the flat observation: obs is required (slot 0 is input)");
         if (o.final_value && !g.v_fin) return wg_fail(WG_ERR_INVALID, who + "final_value needs " + g.fin_name);
         if ((o.value || o.final_value) && p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, who + "value requested from a policy without a critic");
-        if (!p->P.has_log_std && (!deterministic || o.logp))
+        if (!p->P.has_log_std && (!a.deterministic || o.logp))
             return wg_fail(WG_ERR_INVALID, who + "a stochastic rollout / log-probabilities need a policy with log_std");
     }
     if (o.n_info < 0 || (o.n_info > 0 && (!o.info_fields || !o.info_out))) return wg_fail(WG_ERR_INVALID, who + "bad info arguments");
@@ -872,70 +890,60 @@ static int rollout_check(const wg_env_s* h, const wg_policy_s* p, int n_steps, i
     return 0;
 }
 
-static int lstm_nets(const RolloutRows& g) {
-    int n_in = 0, H = 0, nets = 0, dev = 0;
-    (void)wg_lstm_geometry_(g.lstm, &n_in, &H, &nets, &dev);
-    return nets;
-}
-
+// A step is: the front stage (the LSTMs), ONE act launch, the step kernels with the info recordings, the after stage (the wg_norm).
 // The per-agent buffers of step t are the kernel arguments of that step's launches (WgPtrs travels by value), so pointing the
 // handle's two per-agent pointers at slot t on the host between launches is all "wg_set_obs_multi_buffer per step" takes: no
 // device copy of the parameter block is read for them, nothing is synchronised.
-static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
-                        uint64_t row_offset, const RolloutRows& g, void* stream) {
+static int rollout_loop(wg_env_s* h, int n_steps, const RolloutRows& g, const RolloutActor& a, void* stream) {
     const wg_rollout_multi_bufs& o = g.o;
+    const RolloutLstm& f = a.front;
     hipStream_t st = (hipStream_t)stream;
     const int B = h->p.B, R = B * g.per_env, V = B * g.v_env;
-    const size_t sBO = (size_t)B * h->p.obs_dim, sR = (size_t)R, sRO = g.lstm ? sBO : sR * g.n_in, sRN = sR * g.n_out;
-    const size_t sV = (size_t)V, sVO = sV * g.v_in;
+    const size_t sBO = (size_t)B * h->p.obs_dim, sR = (size_t)R, sRO = sR * g.width, sRN = sR * g.n_out, sV = (size_t)V;
     float* const multi0 = h->d.multi_out;
     float* const fin0 = h->d.multi_fin;
     int rc = 0;
-    // a recurrent policy: the rows the policy reads are the LSTMs' h' of the step (scratch: h_pi, h_vf, h_fin); a shared LSTM's
-    // critic reads h_pi, and its "critic net" is the one net it has
-    const bool two = g.lstm && lstm_nets(g) == 2;
-    const size_t sH = g.lstm ? (size_t)B * g.n_in : 0;
-    float* const h_pi = g.lstm ? g.lb->scratch : nullptr;
-    float* const h_vf = two ? h_pi + sH : h_pi;
-    float* const h_fin = g.lstm ? h_pi + 2 * sH : nullptr;
-    // the critic's LSTM on the final rows of step t, from the state after step t, which stays as it is -> h_fin
+    // the rows the act launch reads at step t: slot t of the env side's (actor, critic, critic on the final rows), or — behind
+    // a front stage — the one block of h' rows that the LSTMs fill every step
+    struct { const float *pi, *vf, *fin; size_t s_pi, s_vf; } rd = {o.obs_multi, g.v_obs, g.v_fin, sRO, sV * g.v_in};
+    if (f.lstm) rd = {f.h_pi(), f.h_vf(), f.h_fin(), 0, 0};
     auto lstm_step = [&](const float* x, const uint8_t* start, float* state_out, float* hp, float* hv, int net_mask) {
-        return g.lpop ? wg_lstm_pop_step_(g.lpop, B, x, start, g.lb->state, state_out, hp, hv, net_mask, stream)
-                      : wg_lstm_step(g.lstm, B, x, start, g.lb->state, state_out, hp, hv, net_mask, stream);
+        return f.lpop ? wg_lstm_pop_step_(f.lpop, B, x, start, f.lb->state, state_out, hp, hv, net_mask, stream)
+                      : wg_lstm_step(f.lstm, B, x, start, f.lb->state, state_out, hp, hv, net_mask, stream);
     };
+    // the critic's LSTM on the final rows of step t, from the state after step t, which stays as it is -> h_fin
     auto lstm_final = [&](int t) {
-        return lstm_step(o.final_obs + t * sBO, nullptr, nullptr, two ? nullptr : h_fin, two ? h_fin : nullptr, two ? WG_LSTM_CRITIC : WG_LSTM_ACTOR);
+        return lstm_step(o.final_obs + t * sBO, nullptr, nullptr, f.two() ? nullptr : f.h_fin(), f.two() ? f.h_fin() : nullptr, f.two() ? WG_LSTM_CRITIC : WG_LSTM_ACTOR);
     };
-    if (g.lstm && g.lb->state0 && n_steps > 0) {
-        const hipError_t ce = hipMemcpyAsync(g.lb->state0, g.lb->state, sizeof(float) * (two ? 2 : 1) * 2 * sH, hipMemcpyDeviceToDevice, st);
+    if (f.lstm && f.lb->state0 && n_steps > 0) {
+        const hipError_t ce = hipMemcpyAsync(f.lb->state0, f.lb->state, sizeof(float) * f.nets * 2 * f.sH(), hipMemcpyDeviceToDevice, st);
         if (ce != hipSuccess) return wg_fail(WG_ERR_HIP, std::string(g.who) + ": copy of the initial state failed: " + hipGetErrorString(ce));
     }
-    // ONE launch of k_policy per step: the actor on step t's rows and, as further slots, the critic on its rows of step t and
-    // final_value[t - 1] = V(final rows of step t - 1) (a row's value does not depend on what else the launch computes); the last
-    // final_value by a launch of its own
     for (int t = 0; t < n_steps && !rc; ++t) {
-        WgValueRows v[2];
-        int nv = 0;
-        if (o.value) v[nv++] = {g.lstm ? h_vf : g.v_obs + t * sVO, o.value + t * sV, V};
-        if (o.final_value && t > 0) v[nv++] = {g.lstm ? h_fin : g.v_fin + (t - 1) * sVO, o.final_value + (t - 1) * sV, V};
-        if (g.table) {
-            wg_launch_yaw_table_act_(g.table, &h->p, &h->d, o.actions + t * sRN, st);
-        } else if (g.lstm) {
+        if (f.lstm) {
             // (the final rows of step t - 1 first: they read the state that step t's launch then advances in place; the episode
             // starts of step t > 0 are read where the step before wrote them, truncated[t - 1] = what episode_start[t] will hold)
             if (o.final_value && t > 0) rc = lstm_final(t - 1);
             if (!rc)
-                rc = lstm_step(o.obs_multi + t * sRO, t == 0 ? g.lb->episode_start : o.truncated + (size_t)(t - 1) * B, g.lb->state, h_pi,
-                               two ? h_vf : nullptr, two ? WG_LSTM_ACTOR | WG_LSTM_CRITIC : WG_LSTM_ACTOR);
-            if (!rc && g.pop) rc = wg_pop_launch_(g.pop, 1, t > 0, t, deterministic, counter0 + (uint64_t)t, stream);
-            else if (!rc)
-                rc = wg_policy_eval_(p, R, h_pi, deterministic, seed, counter0 + (uint64_t)t, row_offset, o.actions + t * sRN,
-                                     o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
-        } else if (g.pop)      // (the same rows, found through the population's slot table: step t's own and the final rows of t - 1)
-            rc = wg_pop_launch_(g.pop, 1, t > 0, t, deterministic, counter0 + (uint64_t)t, stream);
-        else
-            rc = wg_policy_eval_(p, R, o.obs_multi + t * sRO, deterministic, seed, counter0 + (uint64_t)t, row_offset * (uint64_t)g.per_env,
+                rc = lstm_step(o.obs_multi + t * sRO, t == 0 ? f.lb->episode_start : o.truncated + (size_t)(t - 1) * B, f.lb->state, f.h_pi(),
+                               f.two() ? f.h_vf() : nullptr, f.two() ? WG_LSTM_ACTOR | WG_LSTM_CRITIC : WG_LSTM_ACTOR);
+            if (rc) break;
+        }
+        // ONE act launch per step.  k_policy: the actor on step t's rows and, as further slots, the critic on its rows of step t and
+        // final_value[t - 1] = V(final rows of step t - 1) (a row's value does not depend on what else the launch computes); the last
+        // final_value by a launch of its own.  A population finds the same rows through its slot table.
+        WgValueRows v[2];
+        int nv = 0;
+        if (o.value) v[nv++] = {rd.vf + t * rd.s_vf, o.value + t * sV, V};
+        if (o.final_value && t > 0) v[nv++] = {rd.fin + (t - 1) * rd.s_vf, o.final_value + (t - 1) * sV, V};
+        switch (a.act) {
+        case RolloutActor::TABLE: wg_launch_yaw_table_act_(a.table, &h->p, &h->d, o.actions + t * sRN, st); break;
+        case RolloutActor::POPULATION: rc = wg_pop_launch_(a.pop, 1, t > 0, t, a.deterministic, a.counter0 + (uint64_t)t, stream); break;
+        case RolloutActor::POLICY:
+            rc = wg_policy_eval_(a.p, R, rd.pi + t * rd.s_pi, a.deterministic, a.seed, a.counter0 + (uint64_t)t, a.row_offset * (uint64_t)g.per_env,
                                  o.actions + t * sRN, o.raw ? o.raw + t * sRN : nullptr, o.logp ? o.logp + t * sR : nullptr, v, nv, stream);
+            break;
+        }
         if (rc) break;
         if (g.per_agent) {
             h->d.multi_out = o.obs_multi + (t + 1) * sRO;
@@ -954,27 +962,41 @@ static int rollout_loop(wg_env_s* h, wg_policy p, int n_steps, int deterministic
     }
     h->d.multi_out = multi0;      // the handle's own per-agent buffers again, on every way out (the device copies never changed)
     h->d.multi_fin = fin0;
-    if (!rc && g.lstm && n_steps > 0) {      // episode_start[t + 1] = truncated[t] for every t: one contiguous block
-        const hipError_t ce = hipMemcpyAsync(g.lb->episode_start + B, o.truncated, (size_t)n_steps * B, hipMemcpyDeviceToDevice, st);
+    if (!rc && f.lstm && n_steps > 0) {      // episode_start[t + 1] = truncated[t] for every t: one contiguous block
+        const hipError_t ce = hipMemcpyAsync(f.lb->episode_start + B, o.truncated, (size_t)n_steps * B, hipMemcpyDeviceToDevice, st);
         if (ce != hipSuccess) rc = wg_fail(WG_ERR_HIP, std::string(g.who) + ": copy of the episode starts failed: " + hipGetErrorString(ce));
         if (!rc && o.final_value) rc = lstm_final(n_steps - 1);
     }
     if (!rc && o.final_value && n_steps > 0) {
-        const WgValueRows v = {g.lstm ? h_fin : g.v_fin + (n_steps - 1) * sVO, o.final_value + (n_steps - 1) * sV, V};
-        if (g.pop) rc = wg_pop_launch_(g.pop, 0, 1, n_steps, 1, 0, stream);
-        else rc = wg_policy_eval_(p, 0, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, &v, 1, stream);
+        const WgValueRows v = {rd.fin + (n_steps - 1) * rd.s_vf, o.final_value + (n_steps - 1) * sV, V};
+        rc = a.act == RolloutActor::POPULATION ? wg_pop_launch_(a.pop, 0, 1, n_steps, 1, 0, stream)
+                                               : wg_policy_eval_(a.p, 0, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, &v, 1, stream);
     }
     return rc;
 }
 
-// One policy row per env (every closed-loop entry but wg_rollout_multi): the rows the policy reads (`rows` / `fin`, named obs_name /
-// fin_name) are the steps' flat rows or stand in their place; the policy maps n_in -> n_turb, or the refusal ends in `needs`
+// what the entries without a preparation of their own end in
+static int rollout_run(wg_env_s* h, int n_steps, const RolloutRows& g, const RolloutActor& a, void* stream) {
+    if (int rc = rollout_check(h, n_steps, g, a)) return rc;
+    if (int rc = wg_use_device(h->device)) return rc;
+    return rollout_loop(h, n_steps, g, a, stream);
+}
+
+// One actor row per env (every closed-loop entry but wg_rollout_multi): the rows the actor reads (`rows` / `fin`, named obs_name /
+// fin_name) are the steps' flat rows or stand in their place; a policy maps n_in -> n_turb, or the refusal ends in `needs`
 static RolloutRows env_rows(const wg_env_s* h, const wg_rollout_bufs* o, const char* who, int n_in, const std::string& needs, float* rows,
                             float* fin, const char* obs_name = "obs", const char* fin_name = "final_obs") {
-    return {who, obs_name, 1, n_in, h->p.N, needs + std::to_string(n_in) + " / " + std::to_string(h->p.N), nullptr, false,
-            {rows, o->actions, o->raw, o->logp, o->value, fin, o->final_value, o->reward, o->truncated, o->obs, o->final_obs, o->n_info,
-             o->info_fields, o->info_out},
-            1, n_in, rows, fin, fin_name};
+    RolloutRows g = {};
+    g.who = who; g.obs_name = obs_name; g.fin_name = fin_name;
+    g.per_env = 1; g.width = h->p.obs_dim; g.n_out = h->p.N;
+    g.n_in = n_in;
+    g.needs = needs + std::to_string(n_in) + " / " + std::to_string(h->p.N);
+    g.o.obs_multi = rows; g.o.final_obs_multi = fin;
+    g.o.actions = o->actions; g.o.raw = o->raw; g.o.logp = o->logp; g.o.value = o->value; g.o.final_value = o->final_value;
+    g.o.reward = o->reward; g.o.truncated = o->truncated; g.o.obs = o->obs; g.o.final_obs = o->final_obs;
+    g.o.n_info = o->n_info; g.o.info_fields = o->info_fields; g.o.info_out = o->info_out;
+    g.v_env = 1; g.v_in = n_in; g.v_obs = rows; g.v_fin = fin;
+    return g;
 }
 
 // the LSTM side of a recurrent entry: lstm_bufs, and an LSTM (or the population's: `whose` words both) that reads the handle's rows
@@ -991,9 +1013,7 @@ extern "C" int wg_rollout(wg_handle h, wg_policy p, int n_steps, int determinist
                           uint64_t row_offset, const wg_rollout_bufs* o, void* stream) {
     if (!h || !p || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout: null argument");
     const RolloutRows g = env_rows(h, o, "wg_rollout", h->p.obs_dim, ", the handle's obs_dim / n_turb are ", o->obs, o->final_obs);
-    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (int rc = wg_use_device(h->device)) return rc;
-    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+    return rollout_run(h, n_steps, g, {.act = RolloutActor::POLICY, .p = p, .deterministic = deterministic, .seed = seed, .counter0 = counter0, .row_offset = row_offset}, stream);
 }
 
 // The policy on normalised rows: the actor and the critic read norm_obs / norm_final_obs, the steps write bufs->obs / final_obs,
@@ -1013,25 +1033,24 @@ extern "C" int wg_rollout_norm(wg_handle h, wg_policy p, wg_norm n, int n_steps,
         return wg_fail(WG_ERR_INVALID, "wg_rollout_norm: obs, final_obs (the env's own rows) and norm_final_obs are required");
     RolloutRows g = env_rows(h, o, "wg_rollout_norm", O, ", the handle's obs_dim / n_turb are ", norm_obs_dev, norm_final_obs_dev, "norm_obs", "norm_final_obs");
     g.norm = n;
-    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (int rc = wg_use_device(h->device)) return rc;
-    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+    return rollout_run(h, n_steps, g, {.act = RolloutActor::POLICY, .p = p, .deterministic = deterministic, .seed = seed, .counter0 = counter0, .row_offset = row_offset}, stream);
 }
 
 // The population in the policy's place: the checks are wg_rollout's on member 0 (the members share one architecture and device),
-// the loop is rollout_loop with the population's slot table prepared for these buffers.
+// the act is the population's slot table prepared for these buffers — which carries the members' seeds and row offsets: the
+// loop's own are 0.
 extern "C" int wg_pop_rollout(wg_handle h, wg_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
                               const uint64_t* row_offsets, const wg_rollout_bufs* o, void* stream) {
     if (!h || !q || !o || !seeds) return wg_fail(WG_ERR_INVALID, "wg_pop_rollout: null argument");
     const int B = h->p.B;
-    RolloutRows g = env_rows(h, o, "wg_pop_rollout", h->p.obs_dim, ", the handle's obs_dim / n_turb are ", o->obs, o->final_obs);
-    g.pop = q;
-    if (int rc = rollout_check(h, q->pol[0], n_steps, deterministic, g)) return rc;
+    const RolloutRows g = env_rows(h, o, "wg_pop_rollout", h->p.obs_dim, ", the handle's obs_dim / n_turb are ", o->obs, o->final_obs);
+    const RolloutActor a = {.act = RolloutActor::POPULATION, .p = q->pol[0], .pop = q, .deterministic = deterministic, .counter0 = counter0};
+    if (int rc = rollout_check(h, n_steps, g, a)) return rc;
     if (int rc = wg_pop_shares(g.who, q->P, B, "envs", "n_envs = ", " does")) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
     const WgPopOuts out = {o->actions, o->raw, o->logp, o->value, o->final_value, B};
     if (int rc = wg_pop_prepare_(q, "wg_pop_rollout", B, seeds, row_offsets, o->obs, o->final_obs, &out, stream)) return rc;
-    return rollout_loop(h, q->pol[0], n_steps, deterministic, 0, counter0, 0, g, stream);
+    return rollout_loop(h, n_steps, g, a, stream);
 }
 
 // what wg_yaw_table_act and wg_rollout_table refuse alike: a table for another turbine count or on another device
@@ -1055,16 +1074,12 @@ extern "C" int wg_yaw_table_act(wg_handle h, wg_yaw_table tab, float* action_out
     return 0;
 }
 
-// The table in the policy's place: wg_rollout's checks of the buffers, none of a policy, and rollout_loop with k_yaw_table_act as
-// a step's first launch.
+// The table in the policy's place: wg_rollout's checks of the buffers, none of a policy, and k_yaw_table_act as the act.
 extern "C" int wg_rollout_table(wg_handle h, wg_yaw_table tab, int n_steps, const wg_rollout_bufs* o, void* stream) {
     if (!h || !tab || !o) return wg_fail(WG_ERR_INVALID, "wg_rollout_table: null argument");
     if (int rc = table_fits("wg_rollout_table", h, tab)) return rc;
-    RolloutRows g = env_rows(h, o, "wg_rollout_table", h->p.obs_dim, "", o->obs, o->final_obs);
-    g.table = tab;
-    if (int rc = rollout_check(h, nullptr, n_steps, 1, g)) return rc;
-    if (int rc = wg_use_device(h->device)) return rc;
-    return rollout_loop(h, nullptr, n_steps, 1, 0, 0, 0, g, stream);
+    const RolloutRows g = env_rows(h, o, "wg_rollout_table", h->p.obs_dim, "", o->obs, o->final_obs);
+    return rollout_run(h, n_steps, g, {.act = RolloutActor::TABLE, .table = tab, .deterministic = 1}, stream);
 }
 
 extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
@@ -1073,26 +1088,30 @@ extern "C" int wg_rollout_multi(wg_handle h, wg_policy p, int n_steps, int deter
     const int B = h->p.B, N = h->p.N, O = h->p.obs_dim, Om = h->p.obs_dim_multi;
     // central mode: the policy's critic has the flat observation's width (and not the actor's): it reads the steps' flat rows
     const bool central = p->P.n_layers[1] != 0 && p->P.n_in_vf != p->P.n_in && p->P.n_in_vf == O;
-    const RolloutRows g = {"wg_rollout_multi", "obs_multi", N, Om, 1,
-                           ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) +
-                               " -> 1, its critic on the same " + std::to_string(Om) + " inputs (one value per agent) or on obs_dim = " +
-                               std::to_string(O) + " (a centralised critic: wg_policy_create_vf)",
-                           h->d.multi_out ? nullptr : "register a per-agent buffer first (wg_set_obs_multi_buffer); obs_multi[0] is what it held",
-                           true, *o,
-                           central ? 1 : N, central ? O : Om, central ? o->obs : o->obs_multi, central ? o->final_obs : o->final_obs_multi,
-                           central ? "final_obs (a centralised critic reads the flat rows)" : "final_obs_multi"};
-    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
+    RolloutRows g = {};
+    g.who = "wg_rollout_multi"; g.obs_name = "obs_multi";
+    g.per_env = N; g.width = g.n_in = Om; g.n_out = 1;
+    g.needs = ", a shared per-turbine policy of this handle maps obs_dim_multi = " + std::to_string(Om) +
+              " -> 1, its critic on the same " + std::to_string(Om) + " inputs (one value per agent) or on obs_dim = " +
+              std::to_string(O) + " (a centralised critic: wg_policy_create_vf)";
+    if (!h->d.multi_out) g.unready = "register a per-agent buffer first (wg_set_obs_multi_buffer); obs_multi[0] is what it held";
+    g.per_agent = true;
+    g.o = *o;
+    g.v_env = central ? 1 : N; g.v_in = central ? O : Om;
+    g.v_obs = central ? o->obs : o->obs_multi; g.v_fin = central ? o->final_obs : o->final_obs_multi;
+    g.fin_name = central ? "final_obs (a centralised critic reads the flat rows)" : "final_obs_multi";
+    const RolloutActor a = {.act = RolloutActor::POLICY, .p = p, .deterministic = deterministic, .seed = seed, .counter0 = counter0, .row_offset = row_offset};
+    if (int rc = rollout_check(h, n_steps, g, a)) return rc;
     if ((long long)B * N > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, "wg_rollout_multi: more than 2^31 agent rows");
     if (int rc = wg_use_device(h->device)) return rc;
     // the step kernels always build the flat observation: without a caller's buffer it goes to a row block of the handle's own
     // (allocated by the first call that needs it, before anything is enqueued)
     if (!o->obs && !h->flat_scratch)
         if (int rc = dev_alloc(h, &h->flat_scratch, (size_t)B * h->p.obs_dim, false)) return rc;
-    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+    return rollout_loop(h, n_steps, g, a, stream);
 }
 
-// A recurrent policy: the checks are wg_rollout's with the policy on the LSTM's hidden rows, the loop is rollout_loop with the LSTM's
-// launches in front of the policy's.
+// A recurrent policy: the checks are wg_rollout's with the policy on the LSTM's hidden rows, the LSTM's launches are the front stage.
 extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_steps, int deterministic, uint64_t seed, uint64_t counter0,
                                uint64_t row_offset, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
     if (!h || !lstm || !p || !o || !lb) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: null argument");
@@ -1100,34 +1119,30 @@ extern "C" int wg_rollout_lstm(wg_handle h, wg_lstm lstm, wg_policy p, int n_ste
     if (int rc = wg_lstm_geometry_(lstm, &l_in, &H, &nets, &l_device)) return rc;
     if (int rc = lstm_rows_check("wg_rollout_lstm", h, lb, l_in, l_device, ": lstm reads", ": lstm")) return rc;
     if (p->P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_rollout_lstm: p needs a critic (on the LSTM's hidden rows)");
-    RolloutRows g = env_rows(h, o, "wg_rollout_lstm", H, ": p reads the LSTM's hidden rows, and lstm's hidden size / the handle's n_turb are ", o->obs, o->final_obs);
-    g.lstm = lstm; g.lb = lb;
-    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
-    if (int rc = wg_use_device(h->device)) return rc;
-    return rollout_loop(h, p, n_steps, deterministic, seed, counter0, row_offset, g, stream);
+    const RolloutRows g = env_rows(h, o, "wg_rollout_lstm", H, ": p reads the LSTM's hidden rows, and lstm's hidden size / the handle's n_turb are ", o->obs, o->final_obs);
+    return rollout_run(h, n_steps, g, {.act = RolloutActor::POLICY, .p = p, .deterministic = deterministic, .seed = seed, .counter0 = counter0,
+                                       .row_offset = row_offset, .front = {.lstm = lstm, .lb = lb, .B = h->p.B, .H = H, .nets = nets}}, stream);
 }
 
 // A population of recurrent policies in the pair's place: the checks are wg_rollout_lstm's on member 0 (the members share one
-// architecture and device), the loop is rollout_loop with the members' LSTM launches and the heads' slot table.
+// architecture and device), the front stage is the members' LSTM launches, the act the heads' slot table on the h' rows.
 extern "C" int wg_lstm_pop_rollout(wg_handle h, wg_lstm_pop q, int n_steps, int deterministic, const uint64_t* seeds, uint64_t counter0,
                                    const uint64_t* row_offsets, const wg_rollout_bufs* o, const wg_rollout_lstm_bufs* lb, void* stream) {
     if (!h || !q || !o || !lb || !seeds) return wg_fail(WG_ERR_INVALID, "wg_lstm_pop_rollout: null argument");
     const int B = h->p.B;
     wg_lstm_s* lstm = q->lstm[0];
-    wg_policy_s* p = q->heads.pol[0];
     const int H = lstm->P.H;
     if (int rc = lstm_rows_check("wg_lstm_pop_rollout", h, lb, lstm->P.n_in, q->device, ": the LSTMs read", ": population")) return rc;
-    RolloutRows g = env_rows(h, o, "wg_lstm_pop_rollout", H, ": the heads read the LSTMs' hidden rows, and their hidden size / the handle's n_turb are ", o->obs,
-                             o->final_obs);
-    g.pop = &q->heads; g.lstm = lstm; g.lb = lb; g.lpop = q;
-    if (int rc = rollout_check(h, p, n_steps, deterministic, g)) return rc;
+    const RolloutRows g = env_rows(h, o, "wg_lstm_pop_rollout", H, ": the heads read the LSTMs' hidden rows, and their hidden size / the handle's n_turb are ", o->obs,
+                                   o->final_obs);
+    const RolloutActor a = {.act = RolloutActor::POPULATION, .p = q->heads.pol[0], .pop = &q->heads, .deterministic = deterministic, .counter0 = counter0,
+                            .front = {.lstm = lstm, .lpop = q, .lb = lb, .B = B, .H = H, .nets = lstm->P.n_nets}};
+    if (int rc = rollout_check(h, n_steps, g, a)) return rc;
     if (int rc = wg_pop_shares(g.who, q->P, B, "envs", "n_envs = ", " does")) return rc;
     if (int rc = wg_use_device(h->device)) return rc;
-    float* const h_pi = lb->scratch;
-    const size_t sH = (size_t)B * H;
     const WgPopOuts out = {o->actions, o->raw, o->logp, o->value, o->final_value, B};
-    if (int rc = wg_lstm_pop_slots_(q, B, seeds, row_offsets, h_pi, lstm->P.n_nets == 2 ? h_pi + sH : h_pi, h_pi + 2 * sH, &out, stream)) return rc;
-    return rollout_loop(h, p, n_steps, deterministic, 0, counter0, 0, g, stream);
+    if (int rc = wg_lstm_pop_slots_(q, B, seeds, row_offsets, a.front.h_pi(), a.front.h_vf(), a.front.h_fin(), &out, stream)) return rc;
+    return rollout_loop(h, n_steps, g, a, stream);
 }
 
 extern "C" int wg_metrics(wg_handle h, float* out_dev, int reset_after, void* stream) {

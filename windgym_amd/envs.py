@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import copy
 import math
-import types
 import weakref
 from collections import deque
 from typing import Optional
@@ -224,7 +223,7 @@ class WindFarmVecEnv(_gym_vector_base()):
         self._global_offset = 0          # first global env index of this shard (set by shard())
         self._was_reset = False          # the first reset() without a seed uses the base seed
         self._policy_steps = 0           # rollout()'s noise counter: policy steps taken so far (PPO.save / load keep it)
-        self._rollout_bufs = {}          # rollout()'s buffers by (rows, T, record, values, stochastic_ok)
+        self._rollout_bufs = {}          # rollout()'s buffers by (rows, critic's rows, T, record, values, samples, log_std, normalised)
         self._lstm = {}                  # rollout() of recurrent policies: id(policy) -> [weakref, LSTM state, pending episode starts]
         self._actions = self.torch.zeros((self.num_envs, self.n_turb), dtype=self.torch.float32,
                                          device=self.batch.device)
@@ -330,38 +329,19 @@ class WindFarmVecEnv(_gym_vector_base()):
         ``policy`` may be a ``yaw_table.YawTableAgent``: the table acts in the policy's place (wg_rollout_table, one lookup launch
         per step).  Nothing is sampled or valued — the dict has no ``raw`` / ``logp`` / ``value`` / ``final_value``, ``deterministic``
         and ``values`` mean nothing, the noise counter stays where it is.  ``sample_site`` is not supported with it."""
-        b = self.batch
-        if getattr(policy, "yaw_table_agent", False):
-            return self._rollout_table(policy, n_steps, record)
-        pop = getattr(policy, "population", None)      # a population / its trainer: wg_pop_rollout / wg_lstm_pop_rollout, member m on its envs
-        if pop is not None and self.num_envs % pop.n_members:
-            raise ValueError(f"rollout(): the {pop.n_members} members own equal shares of the envs: num_envs = {self.num_envs} "
-                             f"does not divide by {pop.n_members}")
-        if getattr(policy if pop is None else pop, "recurrent", False):
-            return self._rollout_recurrent(policy if pop is None else pop, n_steps, deterministic, record, values, state)
+        actor = policy.rollout_actor(self)
+        if actor.lstm:
+            return self._rollout_recurrent(actor, n_steps, deterministic, record, values, state)
         if state is not None:
             raise ValueError("rollout(): state= applies to a recurrent policy (MlpLstmPolicy)")
-        return self._rollout(policy if pop is None else pop, n_steps, deterministic, record, values, rows=(self.num_envs,),
-                             shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
-                             slots=(("obs", "final_obs", b.obs, b.final_obs),), run=b.rollout if pop is None else b.rollout_pop)
+        return self._rollout(actor, n_steps, deterministic, record, values, **self._env_rows())
 
-    def _rollout_table(self, agent, n_steps, record):
-        """``rollout()`` of a ``yaw_table.YawTableAgent``: :meth:`_rollout` with wg_rollout_table as the loop.  Nothing is sampled or
-        valued: the dict has no ``raw`` / ``logp`` / ``value`` / ``final_value``, and the noise counter stays where it was."""
+    def _env_rows(self, norm=None):
+        """The env side of this class's closed loops, as :meth:`_rollout`'s keywords: one row per env, the flat observation.  With
+        ``norm`` (of a ``normalize.VecNormalize``) the actor reads normalised copies of these rows (wg_rollout_norm)."""
         b = self.batch
-        if self._site is not None:
-            raise NotImplementedError("rollout(): a YawTableAgent with sample_site is not implemented")
-        tab = agent.table.check_env(self, "rollout()")
-        rows = types.SimpleNamespace(n_in=b.obs_dim, n_out=self.n_turb, has_critic=False, split=False, desc=dict(has_log_std=False))
-        steps = self._policy_steps
-        try:
-            out = self._rollout(rows, n_steps, True, record, False, rows=(self.num_envs,), shape=(b.obs_dim, self.n_turb), needs="",
-                                slots=(("obs", "final_obs", b.obs, b.final_obs),),
-                                run=lambda _, n, bufs, rec, *a: b.rollout_table(tab, n, {k: v for k, v in bufs.items() if k != "raw"}, rec))
-        finally:
-            self._policy_steps = steps
-        del out["raw"]
-        return out
+        return dict(rows=(self.num_envs,), shape=(b.obs_dim, self.n_turb), needs=f"the env needs {b.obs_dim} -> {self.n_turb}",
+                    slots=(("obs", "final_obs", b.obs, b.final_obs),), entry="wg_rollout_norm" if norm else None, norm=norm)
 
     def _lstm_pair(self, policy):
         """This env's entry of the (policy, env) pair — [weakref, LSTM state, pending episode starts, buffers] — made on first use:
@@ -374,15 +354,12 @@ class WindFarmVecEnv(_gym_vector_base()):
                                             t.ones(B, dtype=t.uint8, device=self.batch.device), {}]
         return ent
 
-    def _rollout_recurrent(self, policy, n_steps, deterministic, record, values, state):
-        """``rollout()`` of an ``MlpLstmPolicy`` or a ``RecurrentPopulation``: :meth:`_rollout` with wg_rollout_lstm /
-        wg_lstm_pop_rollout as the loop, around the pair's kept state."""
+    def _rollout_recurrent(self, actor, n_steps, deterministic, record, values, state):
+        """``rollout()`` of an actor with an LSTM state (``MlpLstmPolicy``, ``RecurrentPopulation``): :meth:`_rollout` around the pair's
+        kept state."""
         t, b = self.torch, self.batch
         T, B = int(n_steps), self.num_envs
-        if self._site is not None:
-            raise NotImplementedError("rollout(): a recurrent policy with sample_site is not implemented")
-        ent = self._lstm_pair(policy)
-        loop = b.rollout_lstm_pop if getattr(policy, "population", None) is not None else b.rollout_lstm
+        ent = self._lstm_pair(actor.obj)
         if state is not None:
             if not (isinstance(state, t.Tensor) and tuple(state.shape) == tuple(ent[1].shape)):
                 raise ValueError(f"rollout(): state must be a tensor {tuple(ent[1].shape)} ((members,) nets, h | c, envs, H)")
@@ -393,53 +370,56 @@ class WindFarmVecEnv(_gym_vector_base()):
         if extra is None:
             extra = ent[3][T] = dict(lstm_state=ent[1], lstm_state0=t.zeros_like(ent[1]),
                                      episode_start=t.zeros((T + 1, B), dtype=t.uint8, device=b.device),
-                                     lstm_scratch=t.zeros((3, B, policy.H), dtype=t.float32, device=b.device))
+                                     lstm_scratch=t.zeros((3, B, actor.obj.H), dtype=t.float32, device=b.device))
         extra["episode_start"][0].copy_(ent[2])
-        out = self._rollout(policy, T, deterministic, record, values, rows=(B,), shape=(b.obs_dim, self.n_turb),
-                            needs=f"the env needs {b.obs_dim} -> {self.n_turb}", slots=(("obs", "final_obs", b.obs, b.final_obs),),
-                            run=lambda pol, n, bufs, *a: loop(pol, n, {**bufs, **extra}, *a))
+        out = self._rollout(actor, T, deterministic, record, values, extra=extra, **self._env_rows())
         ent[2].copy_(extra["episode_start"][T])
         out.update(episode_start=extra["episode_start"], lstm_state0=extra["lstm_state0"], lstm_state=ent[1])
         return out
 
-    def _rollout(self, policy, n_steps, deterministic, record, values, *, rows, shape, needs, slots, run, critic=None, norm=None):
-        """``rollout()`` of this class and of :class:`WindFarmVecEnvMulti`.  ``rows``: the axes of the policy's rows, ``(B,)`` or
-        ``(B, N)``; ``shape`` / ``needs``: the ``(n_in, n_out)`` the policy must have and how the refusal says so; ``slots``: per
-        observation the steps write, ``(key, key of its final rows, persistent tensor, persistent final tensor)`` — slot 0 is
-        seeded from the persistent tensor, which receives slot T (final: T-1) afterwards; the policy reads ``"obs"``; ``run``: the
-        ``HipBatch`` call that enqueues the loop.  ``critic``: ``(key, key of its final rows, axes of its rows)`` of what a SPLIT
-        policy's critic reads (its width must be that buffer's); ``None``: a split policy is refused.  ``norm``: ``(binding.Norm,
-        normalised current observation)`` of a ``normalize.VecNormalize`` — the policy then reads ``norm_obs`` / ``norm_final_obs``,
-        two further buffers that ``run`` fills (wg_rollout_norm) next to the env's own rows; slot 0 is seeded from the given
-        tensor, which receives slot T afterwards."""
+    def _rollout(self, actor, n_steps, deterministic, record, values, *, rows, shape, needs, slots, entry=None, critic=None, norm=None, extra=None):
+        """``rollout()`` of this class, of :class:`WindFarmVecEnvMulti` and of ``normalize.VecNormalize``: ``actor`` (a
+        ``policy.RolloutActor``) on the env side the keywords state.  ``rows``: the axes of the actor's rows, ``(B,)`` or ``(B, N)``;
+        ``shape`` / ``needs``: the ``(n_in, n_out)`` a policy on them must have and how the refusal says so; ``slots``: per observation
+        the steps write, ``(key, key of its final rows, persistent tensor, persistent final tensor)`` — slot 0 is seeded from the
+        persistent tensor, which receives slot T (final: T-1) afterwards; the actor reads ``"obs"``.  ``entry``: the library's entry for
+        a policy on these rows (``None``: the actor's own).  ``critic``: ``(key, key of its final rows, axes of its rows)`` of what a
+        SPLIT policy's critic reads (its width must be that buffer's); ``None``: a split policy is refused.  ``norm``: ``(binding.Norm,
+        normalised current observation)`` — the actor then reads ``norm_obs`` / ``norm_final_obs``, two further buffers that the loop
+        fills next to the env's own rows; slot 0 is seeded from the given tensor, which receives slot T afterwards.  ``extra``: further
+        tensors for the library's call, which :meth:`_rollout_recurrent` owns."""
         from .config import INFO
         t, b = self.torch, self.batch
         T, B, N = int(n_steps), self.num_envs, self.n_turb
         if T < 1:
             raise ValueError("rollout(): n_steps must be >= 1")
-        if (policy.n_in, policy.n_out) != shape:
-            raise ValueError(f"rollout(): the policy maps {policy.n_in} -> {policy.n_out}, {needs}")
-        split = policy.has_critic and policy.split
+        if actor.shape not in (None, shape):
+            raise ValueError(f"rollout(): the policy maps {actor.shape[0]} -> {actor.shape[1]}, {needs}")
+        split = actor.critic not in (None, shape[0])
         vk, vkf, vrows = critic if split and critic is not None else ("obs", "final_obs", rows)
-        if split and (critic is None or policy.n_in_vf != dict((k, cur) for k, _, cur, _ in slots)[vk].shape[-1]):
-            raise ValueError(f"rollout(): the policy's critic reads {policy.n_in_vf} inputs, {needs}")
+        if split and (critic is None or actor.critic != dict((k, cur) for k, _, cur, _ in slots)[vk].shape[-1]):
+            raise ValueError(f"rollout(): the policy's critic reads {actor.critic} inputs, {needs}")
+        if entry is not None and actor.entry != "wg_rollout":          # an env side with an entry of its own takes what wg_rollout takes
+            raise NotImplementedError(f"rollout(): {actor.entry} in the place of wg_rollout inside {entry} is not implemented")
+        entry, handles, tail = entry or actor.entry, actor.handles, ()
         record = tuple(record)
         for name in record:
             if name not in INFO:
                 raise ValueError(f"rollout(): unknown info field {name!r}")
-        values = bool(values) and policy.has_critic
-        stochastic_ok = policy.desc["has_log_std"]
-        key = (rows, vrows, T, record, values, stochastic_ok, norm is not None)
+        values = bool(values) and actor.critic is not None
+        key = (rows, vrows, T, record, values, actor.samples, actor.log_std, norm is not None)
         bufs = self._rollout_bufs.get(key)
         if bufs is None:
             f32 = dict(dtype=t.float32, device=b.device)
-            bufs = dict(actions=t.zeros((T, B, N), **f32), raw=t.zeros((T, B, N), **f32), reward=t.zeros((T, B), **f32),
+            bufs = dict(actions=t.zeros((T, B, N), **f32), reward=t.zeros((T, B), **f32),
                         truncated=t.zeros((T, B), dtype=t.uint8, device=b.device))
             for k, kf, cur, fin in slots:
                 bufs[k], bufs[kf] = t.zeros((T + 1,) + tuple(cur.shape), **f32), t.zeros((T,) + tuple(fin.shape), **f32)
             if norm is not None:
                 bufs["norm_obs"], bufs["norm_final_obs"] = t.zeros_like(bufs["obs"]), t.zeros_like(bufs["final_obs"])
-            if stochastic_ok:
+            if actor.samples:
+                bufs["raw"] = t.zeros((T, B, N), **f32)
+            if actor.log_std:
                 bufs["logp"] = t.zeros((T,) + rows, **f32)
             if values:
                 bufs["value"], bufs["final_value"] = t.zeros((T,) + vrows, **f32), t.zeros((T,) + vrows, **f32)
@@ -453,14 +433,17 @@ class WindFarmVecEnv(_gym_vector_base()):
         if norm is not None:
             bufs[pk][0].copy_(norm[1])
             vk, vkf = pk, pkf
+            handles, tail = handles + (norm[0]._h,), (pk, pkf)
         seed = 0 if self._base_seed is None else int(self._base_seed)
         counter0 = self._policy_steps
-        self._policy_steps = counter0 + T
+        if actor.samples:
+            self._policy_steps = counter0 + T
         if self._site is not None:
+            policy = actor.obj
             for i in range(T):
                 policy.act(bufs[pk][i], deterministic=deterministic, counter=counter0 + i, seed=seed,
                            row_offset=self._global_offset * math.prod(rows[1:]), value=values,
-                           out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if stochastic_ok else None,
+                           out=(bufs["actions"][i], bufs["raw"][i], bufs["logp"][i] if actor.log_std else None,
                                 bufs["value"][i] if values else None))
                 if values and split:                   # (act() on a split policy is the actor alone: the critic reads its own rows)
                     policy.value(bufs[vk][i], out=bufs["value"][i])
@@ -477,7 +460,8 @@ class WindFarmVecEnv(_gym_vector_base()):
             if norm is not None:
                 norm[1].copy_(bufs[pk][T])
             return dict(bufs)
-        run(policy, T, bufs, record, deterministic, seed, counter0, self._global_offset)
+        b.rollout(entry, handles, T, bufs if extra is None else {**bufs, **extra}, record,
+                  (deterministic, seed, counter0, self._global_offset) if actor.samples else None, actor.members, tail)
         if norm is not None:
             norm[1].copy_(bufs[pk][T])
         # the persistent outputs follow, as after a step()
@@ -1246,13 +1230,13 @@ class WindFarmVecEnvMulti:
         if getattr(policy, "yaw_table_agent", False):
             raise NotImplementedError("WindFarmVecEnvMulti.rollout(): a YawTableAgent is not implemented (it acts on a WindFarmVecEnv)")
         b = self.batch
-        return self.venv._rollout(policy, n_steps, deterministic, record, values, rows=(self.num_envs, self.n_turb),
+        return self.venv._rollout(policy.rollout_actor(self.venv), n_steps, deterministic, record, values, rows=(self.num_envs, self.n_turb),
                                   shape=(self.obs_len, 1),
                                   needs=f"a policy shared by the turbines of this env maps {self.obs_len} -> 1, its critic on the "
                                         f"same {self.obs_len} inputs (one value per agent) or on the flat observation's "
                                         f"{b.obs_dim} (a centralised critic)",
                                   slots=(("obs", "final_obs", self._obs, self._final_obs),
-                                         ("flat_obs", "flat_final_obs", b.obs, b.final_obs)), run=b.rollout_multi,
+                                         ("flat_obs", "flat_final_obs", b.obs, b.final_obs)), entry="wg_rollout_multi",
                                   critic=("flat_obs", "flat_final_obs", (self.num_envs,)))
 
     def infos(self, step=False):

@@ -218,10 +218,8 @@ class VecNormalize:
         refuse_table_agent(policy, "VecNormalize.rollout()")
         if getattr(policy, "population", None) is not None:
             raise NotImplementedError("VecNormalize.rollout(): policy is a population — per-member statistics are not implemented")
-        v, b = self.venv, self.batch
-        out = v._rollout(policy, n_steps, deterministic, record, values, rows=(v.num_envs,), shape=(b.obs_dim, v.n_turb),
-                         needs=f"the env needs {b.obs_dim} -> {v.n_turb}", slots=(("obs", "final_obs", b.obs, b.final_obs),),
-                         run=lambda *a: b.rollout_norm(self._norm, *a), norm=(self._norm, self._cur))
+        v = self.venv
+        out = v._rollout(policy.rollout_actor(v), n_steps, deterministic, record, values, **v._env_rows(norm=(self._norm, self._cur)))
         out["env_obs"], out["env_final_obs"], out["env_reward"] = out["obs"], out["final_obs"], out["reward"]
         out["obs"], out["final_obs"] = out.pop("norm_obs"), out.pop("norm_final_obs")
         if normalize_reward:

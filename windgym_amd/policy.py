@@ -23,6 +23,7 @@ import io
 import json
 import re
 import zipfile
+from typing import NamedTuple
 
 import numpy as np
 
@@ -216,6 +217,26 @@ def refuse_table_agent(policy, who):
                                   "venv.rollout(agent, T), AgentEval and eval_sweep run it")
 
 
+class RolloutActor(NamedTuple):
+    """How an object enters the closed loop of ``WindFarmVecEnv.rollout``: every object that method accepts states one, in its
+    ``rollout_actor(venv)``, which also makes the object's own refusals of ``venv``."""
+    obj: object                 # what acts: its ``act`` / ``value`` stand in under ``sample_site``, its identity keys a kept LSTM state
+    entry: str                  # the library's closed-loop entry, and the handles its signature names after the env's
+    handles: tuple
+    shape: tuple = None         # the (n_in, n_out) it maps; None: it reads no rows
+    samples: bool = True        # ``raw`` exists, ``deterministic`` and the noise counter apply ...
+    log_std: bool = False       # ... and so does ``logp``, a stochastic rollout is possible
+    critic: int = None          # the width of the rows its critic reads (``shape[0]``: the actor's own rows); None: no critic
+    lstm: bool = False          # the env keeps an LSTM state pair for it
+    members: int = None         # a population: its members, each on an equal share of the envs
+
+
+def refuse_site(venv, what):
+    """What an actor without a Python loop of ``act`` + ``step`` says to an env with ``sample_site``."""
+    if venv._site is not None:
+        raise NotImplementedError(f"rollout(): {what} with sample_site is not implemented")
+
+
 def act_buffers(owner, n):
     """The persistent ``(action, raw, logp, value)`` outputs of ``act()`` on ``n`` rows, made once per ``n`` and kept in
     ``owner._out`` (``owner``: a policy or a population — ``torch``, ``device``, ``n_out``)."""
@@ -300,6 +321,10 @@ class MlpPolicy:
             self.close()
         except Exception:
             pass
+
+    def rollout_actor(self, venv):
+        return RolloutActor(self, "wg_rollout", (self._h,), (self.n_in, self.n_out), log_std=self.desc["has_log_std"],
+                            critic=self.n_in_vf if self.has_critic else None)
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)

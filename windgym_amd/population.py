@@ -86,7 +86,14 @@ class PopulationBase:
         self._h = self._create(lambda hs: (C.c_void_p * P)(*[h.value for h in hs]))
         self._out = {}
 
-    population = property(lambda self: self)      # (what venv.rollout looks for)
+    population = property(lambda self: self)      # (what the trainers and the wrappers look for)
+
+    def rollout_actor(self, venv):
+        """Member 0's statement (the members share one architecture) with the population in its place, on equal shares of the envs."""
+        if venv.num_envs % self.n_members:
+            raise ValueError(f"rollout(): the {self.n_members} members own equal shares of the envs: num_envs = {venv.num_envs} "
+                             f"does not divide by {self.n_members}")
+        return self.members[0].rollout_actor(venv)._replace(obj=self, entry=self.rollout_entry, handles=(self._h,), members=self.n_members)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -121,7 +128,7 @@ class Population(PopulationBase):
     the policy kernel for all members, member ``m`` on rows ``[m * Bm, (m + 1) * Bm)``; ``venv.rollout(pop, T)`` is wg_pop_rollout.
     ``optimizers``: the members' :class:`PPOOptimizer` objects (needed by wg_pop_update only)."""
 
-    destroy = "wg_pop_destroy"
+    destroy, rollout_entry = "wg_pop_destroy", "wg_pop_rollout"
 
     def _create(self, arr):
         p0, h = self.members[0], C.c_void_p()
@@ -181,6 +188,9 @@ class PPOPopulation:
     # what recurrent_population.RecurrentPPOPopulation states differently: the policy class by name, and the seven hooks
     # _check_policy, _minibatches, _build_member, _open (below), _global, _batch and _tensors (next to train and save)
     policy_name = "MlpPolicy"
+
+    def rollout_actor(self, venv):
+        return self.population.rollout_actor(venv)
 
     def _check_policy(self, policy):
         refuse_recurrent(policy, "PPOPopulation")

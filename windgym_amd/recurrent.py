@@ -210,6 +210,10 @@ class MlpLstmPolicy:
         except Exception:
             pass
 
+    def rollout_actor(self, venv):
+        _mlp.refuse_site(venv, "a recurrent policy")
+        return _mlp.RolloutActor(self, "wg_rollout_lstm", (self._lstm, self.mlp._h), (self.n_in, self.n_out), log_std=True, critic=self.n_in, lstm=True)
+
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 

@@ -59,7 +59,7 @@ class RecurrentPopulation(PopulationBase):
     recurrent = True
     split = False
     has_critic = True
-    check, destroy = staticmethod(check_same_architecture), "wg_lstm_pop_destroy"
+    check, destroy, rollout_entry = staticmethod(check_same_architecture), "wg_lstm_pop_destroy", "wg_lstm_pop_rollout"
 
     def _create(self, arr):
         ms, h = self.members, C.c_void_p()

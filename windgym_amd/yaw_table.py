@@ -28,6 +28,7 @@ import json
 import numpy as np
 
 from .agents import BaseAgent
+from .policy import RolloutActor, refuse_site
 
 MAX_NODES = 1024          # WG_YT_MAX_NODES: nodes of the three axes together
 CHUNK = 8192              # node winds per Serial-Refine launch of build()
@@ -223,6 +224,10 @@ class YawTableAgent(BaseAgent):
         self.UseEnv = True
         self.table, self.env = table, env
         self._out = None
+
+    def rollout_actor(self, venv):
+        refuse_site(venv, "a YawTableAgent")
+        return RolloutActor(self, "wg_rollout_table", (self.table.check_env(venv, "rollout()")._h,), samples=False)
 
     def _batch(self):
         if self.env is None:
