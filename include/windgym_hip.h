@@ -1152,6 +1152,51 @@ int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_ppo_batch
                        int envs_per_batch, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Behaviour cloning into a recurrent policy: the SUPERVISED loss of wg_bc_grad on the wg_lstm_ppo handle — its buffers, its Adam
+ * state and wg_lstm_ppo_apply are the ones above, as wg_bc_* sits on wg_ppo; k_bc_grad_dh is k_bc_grad with the gradients of the h
+ * rows, which the BPTT kernels above carry through time.  The expert's actions come from wg_expert_labels.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct wg_lstm_bc_batch {
+    const float*   obs;            /* [T (+ 1), B, n_in]   the first T slots are read                                  */
+    const float*   target;         /* [T, B, n_out]        the expert's actions                                        */
+    const float*   returns;        /* [T, B] or NULL: the critic is left alone                                         */
+    const uint8_t* episode_start;  /* [T (+ 1), B]         the first T slots are read                                  */
+    const float*   lstm_state0;    /* [nets][2][B][H]      the state the rollout began from                            */
+    int32_t T, B;
+} wg_lstm_bc_batch;
+
+/* Loss and gradient of ONE minibatch of WHOLE env sequences, n = T * n_envs rows: wg_lstm_ppo_grad's rule with wg_bc_grad's loss.
+ *   forward and backward through time:  exactly wg_lstm_ppo_grad's — lstm_state0 is DATA, episode_start[t] is the cell's SELECT, and
+ *     the gradient stops at a step with episode_start[t] != 0;
+ *   loss:  exactly wg_bc_grad's over the n rows, the actor's MLP on the actor LSTM's h_t and the critic's on the critic LSTM's (the same
+ *     rows when the LSTM is shared), `target` in place of `raw`:
+ *       WG_BC_MSE: loss = mse                — the gradient of every log_std entry is exactly 0.0f;
+ *       WG_BC_NLL: loss = nll - ent_coef * H;
+ *       with returns both add vf_coef * v_loss, and with a shared LSTM dh_t is the actor head's input gradient plus the critic head's,
+ *       in that order;
+ *       without returns v_loss is 0 and the critic gets NO gradient: every critic entry of grad_out — the critic's MLP, and with two
+ *       LSTMs the critic LSTM's whole block — is exactly +0.0f, with a shared LSTM dh_t is the actor head's term alone, and the
+ *       critic's side of the kernels is not launched (with two LSTMs: half of the sequence work) — also on a handle whose scratch an
+ *       earlier wg_lstm_ppo_grad or wg_lstm_bc_grad filled: nothing such a call left behind is read;
+ *   an entry of envs_dev outside [0, B):  never dereferenced.  Its T rows reach the heads as h = 0 with target = returns = 0, count in
+ *     n, and send nothing into the LSTM.  The rows of target / returns that no column of the minibatch names are not read.
+ * grad_out f32[wg_lstm_ppo_n_params]; stats_out (device, may be NULL) wg_bc_grad's record.  Deterministic as wg_lstm_ppo_grad;
+ * params_dev as there.  WG_ERR_INVALID: null arguments (the message names the batch pointer; only returns may be null), T / B /
+ * n_envs < 1, a loss other than WG_BC_MSE / WG_BC_NLL, vf_coef or ent_coef < 0.  WG_ERR_UNSUPPORTED: T > T_max or n_envs > Bm_max. */
+int wg_lstm_bc_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_bc_batch* batch, const int32_t* envs_dev, int n_envs,
+                    const wg_bc_hyper* hp, float* grad_out, wg_bc_stats* stats_out, void* stream);
+
+/* All epochs and minibatches of one rollout, as wg_lstm_ppo_update walks them (perm_dev int32[n_epochs, B], n_mb = ceil(B /
+ * envs_per_batch), the last minibatch shorter), enqueued by one call with no host round trip and no atomics; stats_out (device, may
+ * be NULL) is wg_bc_stats[n_epochs, n_mb].  Bit-identical to
+ *     for e in 0 .. n_epochs-1:  for k in 0 .. n_mb-1:
+ *         wg_lstm_bc_grad(o, params_dev, batch, perm_dev + e * B + k * envs_per_batch, min(envs_per_batch, B - k * envs_per_batch),
+ *                         hp, g, stats_out + e * n_mb + k);   wg_lstm_ppo_apply(o, params_dev, g, lr, max_grad_norm)
+ * WG_ERR_INVALID / WG_ERR_UNSUPPORTED: what the two calls refuse, n_epochs < 1.                                                 */
+int wg_lstm_bc_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_bc_batch* batch, const int32_t* perm_dev, int n_epochs,
+                      int envs_per_batch, const wg_bc_hyper* hp, float lr, float max_grad_norm, wg_bc_stats* stats_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Populations of recurrent policies: P pairs (wg_lstm, wg_policy) of ONE architecture — the same n_in, hidden size, number of
  * LSTMs, heads and activation — collected and trained in the kernel launches of one (a seed sweep of small recurrent runs, each of
  * which leaves most of the device idle: one workgroup of the sequence kernels owns 32 envs for all T steps).  The population

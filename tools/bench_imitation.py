@@ -22,7 +22,13 @@ rollout before cloning, after `--iterations` iterations, and for ``PyWakeVecAgen
 of the same seed, so the three see the same winds and episodes.  The preset's observation holds rolling-mean wind speeds and yaws and
 NO wind direction, which the expert's yaws are a function of; `--observe-wd` switches the wind-direction sensors on.
 
-usage: python tools/bench_imitation.py [--envs N] [--n-steps 128] [--epochs 4] [--reps 5] [--multi] [--effect [--iterations 40] [--observe-wd]]
+With --recurrent the learner is an ``MlpLstmPolicy`` at the shipped recurrent shape (`--lstm-hidden-size` 256, pi = vf = [64, 64]) on
+cfg2 and the trainer ``RecurrentBehaviorCloning``: the iteration and its parts as above, then ONE wg_lstm_bc_update without returns
+(update_bc: the critic's LSTM and head do not run) and with them (update_bc_vf) beside ONE wg_lstm_ppo_update (update_recurrent_ppo) on
+the same rollout, permutations and minibatches (`--batch-size` in env steps, a multiple of `--n-steps`), alternating.
+
+usage: python tools/bench_imitation.py [--envs N] [--n-steps 128] [--epochs 4] [--reps 5] [--multi] [--recurrent [--lstm-hidden-size 256]]
+                                       [--effect [--iterations 40] [--observe-wd]]
 """
 import argparse
 import copy
@@ -114,8 +120,95 @@ def effect(args, torch, dev):
     print(json.dumps(res))
 
 
+def recurrent(args, torch, dev):
+    """--recurrent: one iteration of ``RecurrentBehaviorCloning`` at the shipped recurrent shape and its split, and ONE
+    wg_lstm_bc_update (actor only; with returns) beside ONE wg_lstm_ppo_update on the same rollout, permutations and minibatches,
+    alternating in one process, each from the same starting weights and a zeroed Adam."""
+    from windgym_amd import presets
+    from windgym_amd.envs import WindFarmVecEnv
+    from windgym_amd.recurrent_imitation import RecurrentBehaviorCloning
+    from windgym_amd.turbine import V80
+    B, T, E, H = args.envs or 4096, args.n_steps, args.epochs, args.lstm_hidden_size
+    venv = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
+                          n_passthrough=5, n_rotor_pts=16)
+    venv.reset(seed=1234)
+    bc = RecurrentBehaviorCloning("MlpLstmPolicy", venv, n_steps=T, n_epochs=E, batch_size=args.batch_size, seed=1234,
+                                  policy_kwargs=dict(lstm_hidden_size=H, net_arch=dict(pi=[64, 64], vf=[64, 64])))
+    pol, Bm = bc.policy, bc.envs_per_batch
+    zero = torch.zeros((B, venv.n_turb), device=dev)
+    for _ in range(args.preroll):
+        venv.step(zero)
+    bc.reset_targets()
+    med = statistics.median
+    res = {"metric": "behaviour cloning into MlpLstmPolicy on the device, 16-turbine farm x %d envs x %d steps, H = %d, pi = vf = [64, 64], "
+                     "%d epochs, one GPU" % (B, T, H, E),
+           "envs": B, "n_steps": T, "epochs": E, "lstm_hidden_size": H, "envs_per_minibatch": Bm, "reps": args.reps, "expert": bc.expert}
+    bc.learn(T * B, log_interval=None)
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        bc.learn(T * B, log_interval=None)
+        torch.cuda.synchronize(dev)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    res["iteration"] = {"ms_per_iteration": med(ms), "ms_all": [round(x, 3) for x in ms], "env_steps_per_s": B * T / (med(ms) * 1e-3)}
+    parts = []
+    for _ in range(args.reps):
+        d = {}
+        out = bc.collect(timing=d)
+        t0 = d.pop("_t")
+        bc.train(out, 1e-3)
+        torch.cuda.synchronize(dev)
+        d["update"] = (time.perf_counter() - t0) * 1e3
+        d["C"] = bc.last_n_targets
+        parts.append({k: round(v, 3) if k != "C" else v for k, v in d.items()})
+    res["parts_ms"] = {k: med([p.get(k, 0.0) for p in parts]) for k in ("rollout", "serial_refine", "labels", "plumbing", "update", "C")}
+    res["parts_all"] = parts
+    # the updates on ONE rollout: the learner's own, with its values and GAE for PPO's columns and the critic's targets
+    bc.vf_coef, keep = 0.5, bc.vf_coef                       # (collect() then records the values and runs wg_gae)
+    roll = dict(bc.collect())
+    bc.vf_coef = keep
+    roll["labels"] = roll["labels"].clone()
+    actor_only = dict(roll, returns=None)
+    perm = torch.stack([torch.randperm(B, device=dev) for _ in range(E)]).to(torch.int32).contiguous()
+    start = pol.params.clone()
+    zeros = torch.zeros(2 * start.numel()).numpy()
+
+    def fresh():
+        with torch.no_grad():
+            pol.params.copy_(start)
+        pol.sync()
+        bc.opt.load_state(zeros, 0)
+
+    legs = {"update_bc": lambda: bc.opt.bc_update(actor_only, perm, Bm, learning_rate=1e-3, max_grad_norm=0.5),
+            "update_bc_vf": lambda: bc.opt.bc_update(roll, perm, Bm, vf_coef=0.5, learning_rate=1e-3, max_grad_norm=0.5),
+            "update_recurrent_ppo": lambda: bc.opt.update(roll, perm, Bm, learning_rate=3e-4, max_grad_norm=0.5)}
+    for fn in legs.values():
+        fresh(); fn()
+    torch.cuda.synchronize(dev)
+    ms = {k: [] for k in legs}
+    for _ in range(args.reps):                               # every leg once per round: the legs alternate
+        for k, fn in legs.items():
+            fresh()
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    for k in legs:
+        res[k] = {"ms": med(ms[k]), "min": round(min(ms[k]), 3), "max": round(max(ms[k]), 3), "ms_all": [round(x, 3) for x in ms[k]],
+                  "trained_samples_per_s": B * T * E / (med(ms[k]) * 1e-3)}
+    res["update_bc_over_update_recurrent_ppo"] = res["update_bc"]["ms"] / res["update_recurrent_ppo"]["ms"]
+    fresh()
+    venv.batch.check()
+    bc.close(); pol.close(); venv.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--recurrent", action="store_true", help="RecurrentBehaviorCloning at the shipped recurrent shape beside RecurrentPPO's update")
+    ap.add_argument("--lstm-hidden-size", type=int, default=256, help="with --recurrent")
     ap.add_argument("--envs", type=int, default=None, help="default: 4096 (--multi: 2048, --effect: 256)")
     ap.add_argument("--multi", action="store_true", help="the 3x3 preset: one policy shared by the turbines")
     ap.add_argument("--n-steps", type=int, default=128)
@@ -134,6 +227,8 @@ def main():
     torch.cuda.set_device(dev)
     if args.effect:
         return effect(args, torch, dev)
+    if args.recurrent:
+        return recurrent(args, torch, dev)
     from windgym_amd import presets
     from windgym_amd.envs import WindFarmVecEnv, WindFarmVecEnvMulti
     from windgym_amd.imitation import BehaviorCloning

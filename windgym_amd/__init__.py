@@ -44,6 +44,9 @@ def __getattr__(name):   # lazy: importing the env classes pulls in torch
     if name == "BehaviorCloning":
         from .imitation import BehaviorCloning
         return BehaviorCloning
+    if name == "RecurrentBehaviorCloning":
+        from .recurrent_imitation import RecurrentBehaviorCloning
+        return RecurrentBehaviorCloning
     if name in ("YawTable", "YawTableAgent"):
         from . import yaw_table
         return getattr(yaw_table, name)

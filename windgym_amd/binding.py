@@ -78,7 +78,7 @@ ABI_SYMBOLS = (
     "wg_norm_obs", "wg_norm_reward", "wg_rollout_norm",
     "wg_lstm_create", "wg_lstm_destroy", "wg_lstm_n_params", "wg_lstm_set_params", "wg_lstm_step", "wg_lstm_act", "wg_rollout_lstm",
     "wg_lstm_ppo_create", "wg_lstm_ppo_destroy", "wg_lstm_ppo_n_params", "wg_lstm_ppo_get_state", "wg_lstm_ppo_set_state",
-    "wg_lstm_ppo_grad", "wg_lstm_ppo_apply", "wg_lstm_ppo_update",
+    "wg_lstm_ppo_grad", "wg_lstm_ppo_apply", "wg_lstm_ppo_update", "wg_lstm_bc_grad", "wg_lstm_bc_update",
     "wg_lstm_pop_create", "wg_lstm_pop_destroy", "wg_lstm_pop_act", "wg_lstm_pop_rollout", "wg_lstm_pop_update",
 )
 
@@ -150,6 +150,12 @@ class CLstmPpoBatch(C.Structure):
     """wg_lstm_ppo_batch"""
     _fields_ = [("obs", C.c_void_p), ("raw", C.c_void_p), ("logp", C.c_void_p), ("advantage", C.c_void_p), ("returns", C.c_void_p),
                 ("episode_start", C.c_void_p), ("lstm_state0", C.c_void_p), ("T", C.c_int32), ("B", C.c_int32)]
+
+
+class CLstmBcBatch(C.Structure):
+    """wg_lstm_bc_batch"""
+    _fields_ = [("obs", C.c_void_p), ("target", C.c_void_p), ("returns", C.c_void_p), ("episode_start", C.c_void_p),
+                ("lstm_state0", C.c_void_p), ("T", C.c_int32), ("B", C.c_int32)]
 
 
 class CBcBatch(C.Structure):
@@ -306,6 +312,10 @@ def load_library():
                                    C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_lstm_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmPpoBatch), C.c_void_p, C.c_int, C.c_int,
                                      C.POINTER(CPpoHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.wg_lstm_bc_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmBcBatch), C.c_void_p, C.c_int, C.POINTER(CBcHyper),
+                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wg_lstm_bc_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CLstmBcBatch), C.c_void_p, C.c_int, C.c_int,
+                                    C.POINTER(CBcHyper), C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     L.wg_lstm_pop_create.argtypes = [C.POINTER(C.c_void_p)] * 3 + [C.c_int, C.POINTER(C.c_void_p)]
     L.wg_lstm_pop_destroy.argtypes = [C.c_void_p]
     L.wg_lstm_pop_act.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)] + [C.c_void_p] * 5

@@ -76,6 +76,12 @@ void wg_ppo_grad_free_(WgPpoGrad* g);
 int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw, const float* logp,
                        const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi, float* dh_vf, float* grad_out,
                        float* stats_out, void* stream);
+// wg_ppo.hip: wg_ppo_heads_grad_ with k_bc_grad's loss (k_bc_grad_dh + k_bc_reduce) on the expert's actions target [n][n_out]; ret
+// [n] or null: no critic term — then the critic's workgroups are not launched, dh_vf is NOT written and the critic's entries of
+// grad_out are 0.0f
+int wg_ppo_heads_bc_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* target,
+                          const float* ret, int n, const wg_bc_hyper* hp, float* dh_pi, float* dh_vf, float* grad_out, float* stats_out,
+                          void* stream);
 // k_policy_pack for each of the n_members rows of a member table (device)
 void wg_policy_pack_pop_(const WgPolicyP* P, const WgPopMember* mt, int n_members, void* stream);
 // wg_ppo.hip: wg_ppo_heads_grad_ for the n_members heads of a recurrent population in the launches of one — member m's scratch, flat

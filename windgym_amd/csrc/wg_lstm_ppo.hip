@@ -1,6 +1,7 @@
 // wg_lstm_ppo.hip — training recurrent policies on the device: backpropagation through time over one rollout of wg_rollout_lstm, for
 // the LSTMs of wg_lstm.hip in front of the MLP heads of wg_policy.hip, and the wg_lstm_ppo_* entries of include/windgym_hip.h
-// (wg_lstm_ppo.h states the stash and the transposed packed block).
+// (wg_lstm_ppo.h states the stash and the transposed packed block); the wg_lstm_bc_* entries, the supervised head on the same handle,
+// are above the populations' host side.
 //
 // THE RULE.  A minibatch is Bm envs with all T steps of each; row (t, j) is env envs[j] at step t, n = T Bm rows.
 //   forward    per net, (h, c)_{-1} = lstm_state0[net][., env] — data, not a function of the parameters; for t = 0 .. T-1:
@@ -379,6 +380,27 @@ __global__ void k_lstm_ppo_gather(const WgLstmSeq q, const int n_out, const floa
     lstm_ppo_gather(q, n_out, raw, logp, adv, ret, raw_o, logp_o, adv_o, ret_o);
 }
 
+// The supervised head's rows (wg_lstm_bc_grad): the expert's actions [T, B, n_out], and the returns [T, B] when given, -> row order
+// t Bm + j (a column without an env: zeros).  ret = null: ret_o is not touched.
+__global__ void k_lstm_bc_gather(const WgLstmSeq q, const int n_out, const float* __restrict__ target, const float* __restrict__ ret,
+                                 float* __restrict__ target_o, float* __restrict__ ret_o) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= q.T * q.Bm) return;
+    const int t = row / q.Bm, j = row - t * q.Bm, env = wglp_env(q, j);
+    const size_t src = (size_t)t * q.B + (env >= 0 ? env : 0);
+    if (ret) ret_o[row] = env >= 0 ? ret[src] : 0.0f;
+    for (int a = 0; a < n_out; ++a) target_o[(size_t)row * n_out + a] = env >= 0 ? target[src * n_out + a] : 0.0f;
+}
+
+// k_lstm_wgrad_reduce when only the nets in front of the flat vector ran (wg_lstm_bc_grad without returns: the actor's LSTM alone):
+// the entries [0, n_live) are the splits' sums, the entries [n_live, n) — the nets that were not launched — are 0.0f, and their
+// columns of `part`, which hold what an earlier call left there, are not read.
+__global__ void k_lstm_wgrad_reduce_live(const float* __restrict__ part, const uint32_t n, const uint32_t n_live, const int S,
+                                         float* __restrict__ grad) {
+    if (blockIdx.x * blockDim.x + threadIdx.x < n_live) lstm_wgrad_reduce(part, n, S, grad);
+    else if (blockIdx.x * blockDim.x + threadIdx.x < n) grad[blockIdx.x * blockDim.x + threadIdx.x] = 0.0f;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The population's kernels: one more grid axis = member, whose row of the member table (wg_lstm_ppo.h: WgLstmPopMember) holds what
 // the single-policy kernel takes as arguments.  The member is a function of blockIdx alone, so the row is read by scalar loads into
@@ -514,17 +536,23 @@ extern "C" int wg_lstm_ppo_set_state(wg_lstm_ppo o, const float* mv_host, size_t
 }
 
 // what grad and update check of a batch and the hyper-parameters; `who` names the entry
-static int lp_check(const std::string& who, wg_lstm_ppo o, const wg_lstm_ppo_batch* b, const wg_ppo_hyper* hp, int n_envs) {
-    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !b->episode_start || !b->lstm_state0)
-        return wg_fail(WG_ERR_INVALID, who + ": a batch pointer is null");
-    if (b->T < 1 || b->B < 1) return wg_fail(WG_ERR_INVALID, who + ": T and B must be >= 1");
+// (the sizes: what the PPO and the supervised entries check alike)
+static int lp_check_sizes(const std::string& who, wg_lstm_ppo o, int T, int B, int n_envs) {
+    if (T < 1 || B < 1) return wg_fail(WG_ERR_INVALID, who + ": T and B must be >= 1");
     if (n_envs < 1) return wg_fail(WG_ERR_INVALID, who + ": a minibatch has at least one env");
-    if (b->T > o->T_max)
-        return wg_fail(WG_ERR_UNSUPPORTED, who + ": T = " + std::to_string(b->T) + " > the T_max = " + std::to_string(o->T_max) + " the handle was created for");
+    if (T > o->T_max)
+        return wg_fail(WG_ERR_UNSUPPORTED, who + ": T = " + std::to_string(T) + " > the T_max = " + std::to_string(o->T_max) + " the handle was created for");
     if (n_envs > o->Bm_max)
         return wg_fail(WG_ERR_UNSUPPORTED, who + ": " + std::to_string(n_envs) + " envs in a minibatch > the Bm_max = " + std::to_string(o->Bm_max) +
                                              " the handle was created for");
-    if ((long long)b->T * b->B > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, who + ": more than 2^31 rows T * B");
+    if ((long long)T * B > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, who + ": more than 2^31 rows T * B");
+    return 0;
+}
+
+static int lp_check(const std::string& who, wg_lstm_ppo o, const wg_lstm_ppo_batch* b, const wg_ppo_hyper* hp, int n_envs) {
+    if (!b->obs || !b->raw || !b->logp || !b->advantage || !b->returns || !b->episode_start || !b->lstm_state0)
+        return wg_fail(WG_ERR_INVALID, who + ": a batch pointer is null");
+    if (int rc = lp_check_sizes(who, o, b->T, b->B, n_envs)) return rc;
     if (!(hp->clip_range >= 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": clip_range < 0");
     return 0;
 }
@@ -588,6 +616,83 @@ extern "C" int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lst
     return wg_each_minibatch(b->B, n_epochs, envs_per_batch, [&](int mb, int64_t off, int Bm) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
         if (int rc = lp_grad(o, params_dev, b, perm_dev + off, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        return lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// behaviour cloning into a recurrent policy (windgym_hip.h: wg_lstm_bc_*): the supervised head on the wg_lstm_ppo handle — its
+// stash, its Adam, wg_lstm_ppo_apply.  THE RULE is the one at the head of this file with wg_bc_grad's loss in place of k_ppo_grad's
+// (k_bc_grad_dh) and `target` in place of raw / logp / advantage.  WITHOUT RETURNS the critic gets no gradient, so nothing of its
+// side runs: the heads launch the actor's workgroups alone (dh[1] is not written), and with two LSTMs the three sequence kernels run
+// on grid nets = 1 — the actor's LSTM is net 0 and leads the flat vector — while k_lstm_wgrad_reduce_live writes the critic LSTM's
+// block as 0.0f.  With a shared LSTM the one net runs with dh_t = the actor head's term alone (q.shared = 0: lstm_seq_bwd then does
+// not read dh[1]).  So no dh[1] row, wpart column or spart slot that an earlier call left on the handle is ever read.
+// ---------------------------------------------------------------------------------------------------------------------
+static int lb_check(const std::string& who, wg_lstm_ppo o, const wg_lstm_bc_batch* b, const wg_bc_hyper* hp, int n_envs) {
+    const char* null_is = !b->obs ? "obs" : !b->target ? "target" : !b->episode_start ? "episode_start" : !b->lstm_state0 ? "lstm_state0" : nullptr;
+    if (null_is) return wg_fail(WG_ERR_INVALID, who + ": the batch's " + null_is + " is null (only returns may be)");
+    if (int rc = lp_check_sizes(who, o, b->T, b->B, n_envs)) return rc;
+    if (hp->loss != WG_BC_MSE && hp->loss != WG_BC_NLL)
+        return wg_fail(WG_ERR_INVALID, who + ": loss must be WG_BC_MSE or WG_BC_NLL, got " + std::to_string(hp->loss));
+    if (!(hp->vf_coef >= 0.0f) || !(hp->ent_coef >= 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": vf_coef and ent_coef must be >= 0");
+    return 0;
+}
+
+// the launches of one supervised gradient, no argument checks
+static int lb_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_bc_batch* b, const int32_t* envs_dev, int Bm, const wg_bc_hyper* hp,
+                   float* grad_out, float* stats_out, hipStream_t st) {
+    const WgLstmP& L = o->lstm->P;
+    const int T = b->T, n = T * Bm, n_out = o->pol->P.n_out;
+    const bool has_ret = b->returns != nullptr;
+    const int nets = has_ret ? L.n_nets : 1;               // the nets that run: without returns the actor's (net 0) alone
+    const WgLstmStash s = wglp_stash(o);
+    WgLstmSeq q = s.q;
+    q.obs = b->obs; q.start = b->episode_start; q.state0 = b->lstm_state0; q.envs = envs_dev;
+    q.T = T; q.B = b->B; q.Bm = Bm; q.NT = (Bm + WGP_TILE - 1) / WGP_TILE;
+    if (!has_ret) q.shared = 0;                            // dh_t is the actor head's term alone
+    // (the pack stays whole, the skipped critic net's W_hh^T block included, on purpose: one element-wise launch over at most 2 x 4H x H
+    // floats, and what lies behind the actor's block is then this call's packed data, as the layout of wg_lstm_ppo.h says — not an
+    // earlier call's, which a cut-off pack would leave where the GEMM loop's last prefetch reads one group past its tile: wg_tile.h,
+    // invariant 3)
+    hipLaunchKernelGGL(k_lstm_ppo_pack, dim3((o->whhT_all + 255) / 256), dim3(256), 0, st, L, params_dev, o->whhT, o->whhT_net, o->whhT_all,
+                       (uint32_t)o->nksT);
+    hipLaunchKernelGGL(k_lstm_bc_gather, dim3((n + 255) / 256), dim3(256), 0, st, q, n_out, b->target, b->returns, s.raw, s.ret);
+    hipLaunchKernelGGL(k_lstm_seq_fwd, dim3(q.NT, nets), dim3(WGP_WAVES * 64), 0, st, L, o->lstm->w.packed, q);
+    WG_HIPCHK(hipGetLastError());
+    // (without returns the critic's head is not launched: the h plane it would read may hold an earlier call's rows)
+    if (int rc = wg_ppo_heads_bc_grad_(&o->heads, params_dev + o->n_lstm, s.h[0], s.h[1], s.raw, has_ret ? s.ret : nullptr, n, hp, s.dh[0], s.dh[1],
+                                       grad_out + o->n_lstm, stats_out ? stats_out : o->stats, (void*)st))
+        return rc;
+    hipLaunchKernelGGL(k_lstm_seq_bwd, dim3(q.NT, nets), dim3(WGP_WAVES * 64), 0, st, L, q);
+    const int nblk = T * q.NT, S = nblk < WGLP_SPLIT ? nblk : WGLP_SPLIT;
+    hipLaunchKernelGGL(k_lstm_wgrad, dim3((L.K + 31) / 32, (4 * L.H + WGLP_WI - 1) / WGLP_WI, nets * S), dim3(WGP_WAVES * 64), 0, st, L, q, o->wpart,
+                       S);
+    const uint32_t n_live = nets == L.n_nets ? o->n_lstm : L.net[1].wih_flat;
+    hipLaunchKernelGGL(k_lstm_wgrad_reduce_live, dim3((o->n_lstm + 255) / 256), dim3(256), 0, st, o->wpart, o->n_lstm, n_live, S, grad_out);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_lstm_bc_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_bc_batch* b, const int32_t* envs_dev, int n_envs,
+                               const wg_bc_hyper* hp, float* grad_out, wg_bc_stats* stats_out, void* stream) {
+    if (!o || !params_dev || !b || !envs_dev || !hp || !grad_out) return wg_fail(WG_ERR_INVALID, "wg_lstm_bc_grad: null argument");
+    if (int rc = lb_check("wg_lstm_bc_grad", o, b, hp, n_envs)) return rc;
+    if (int rc = wg_use_device(o->adam.device)) return rc;
+    return lb_grad(o, params_dev, b, envs_dev, n_envs, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+}
+
+extern "C" int wg_lstm_bc_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_bc_batch* b, const int32_t* perm_dev, int n_epochs,
+                                 int envs_per_batch, const wg_bc_hyper* hp, float lr, float max_grad_norm, wg_bc_stats* stats_out,
+                                 void* stream) {
+    if (!o || !params_dev || !b || !perm_dev || !hp) return wg_fail(WG_ERR_INVALID, "wg_lstm_bc_update: null argument");
+    if (n_epochs < 1) return wg_fail(WG_ERR_INVALID, "wg_lstm_bc_update: n_epochs must be >= 1");
+    if (int rc = lb_check("wg_lstm_bc_update", o, b, hp, envs_per_batch)) return rc;
+    if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_lstm_bc_update: max_grad_norm must be > 0");
+    if (int rc = wg_use_device(o->adam.device)) return rc;
+    return wg_each_minibatch(b->B, n_epochs, envs_per_batch, [&](int mb, int64_t off, int Bm) {
+        float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
+        if (int rc = lb_grad(o, params_dev, b, perm_dev + off, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
         return lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
     });
 }

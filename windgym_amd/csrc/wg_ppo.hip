@@ -10,6 +10,7 @@
 //   k_ppo_reduce   partials -> flat gradient + statistics record, summed in workgroup order.
 //   k_bc_grad      k_ppo_grad with the supervised loss head (behaviour cloning: MSE or -logp of the expert's actions) in place of
 //                  the clipped surrogate — the same forward, dW and dX, instantiated from the same body; k_bc_reduce is its reduce.
+//                  k_bc_grad_dh: the same with the gradients of the input rows, for the LSTMs of a recurrent policy.
 //   k_ppo_sumsq / k_ppo_adam   global L2 norm, clipping, Adam on the caller's flat parameters in place.
 //
 // k_ppo_grad: a workgroup of 4 waves owns ONE net (blockIdx.y: actor / critic — the two gradients share nothing but the
@@ -457,6 +458,12 @@ __global__ __launch_bounds__(WGT_WAVES * 64) void k_ppo_grad_dh(const WgPolicyP 
 // workgroups alone — without.  a.logp_old, a.adv, a.advstat and the clip are not read.
 __global__ __launch_bounds__(WGT_WAVES * 64) void k_bc_grad(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
     ppo_grad<false, WGT_HEAD_BC>(P, K, a, a, a.packed, a.flat, a.index, 0, 0.0f, a.vf_coef, nullptr, a.part, a.spart);
+}
+
+// k_bc_grad with the input-row gradients (a.dh) as well: the supervised head on the LSTMs' h rows (wg_lstm_bc_grad).  The same grid
+// rule: without returns the critic's workgroups are not launched and a.dh[1] is not written.
+__global__ __launch_bounds__(WGT_WAVES * 64) void k_bc_grad_dh(const WgPolicyP P, const WgPpoK K, const WgPpoArgs a) {
+    ppo_grad<true, WGT_HEAD_BC>(P, K, a, a, a.packed, a.flat, a.index, 0, 0.0f, a.vf_coef, nullptr, a.part, a.spart);
 }
 
 // grid (G, 2, P); `c` carries what the members share (the batch, n, G), the member's row the rest
@@ -1023,16 +1030,21 @@ static int bc_check(const std::string& w, wg_ppo o, const float* params_dev, con
 }
 
 // the launches of one supervised gradient, no argument checks
-static int t_bc_grad(WgPpoGrad* o, const float* params_dev, const wg_bc_batch* b, const int32_t* index_dev, int64_t first, int n,
-                     const wg_bc_hyper* hp, float* grad_out, float* stats_out, hipStream_t st) {
+// (obs_vf: the rows the critic reads — b->obs for a plain batch; dh_pi / dh_vf both given: k_bc_grad_dh, which also writes the
+// gradients of the gathered rows — wg_ppo_heads_bc_grad_)
+static int t_bc_grad(WgPpoGrad* o, const float* params_dev, const wg_bc_batch* b, const float* obs_vf, const int32_t* index_dev, int64_t first,
+                     int n, const wg_bc_hyper* hp, float* grad_out, float* stats_out, hipStream_t st, float* dh_pi = nullptr,
+                     float* dh_vf = nullptr) {
     const WgPolicyP& P = o->pol->P;
     const int G = t_grid(o, n);
     const int has_ret = b->returns != nullptr, nll = hp->loss == WG_BC_NLL;
     WgPpoArgs a = {};
-    a.packed = o->pol->w.packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = b->obs; a.agents = 1; a.raw = b->target;
+    a.packed = o->pol->w.packed; a.flat = params_dev; a.obs[0] = b->obs; a.obs[1] = obs_vf; a.agents = 1; a.raw = b->target;
     a.ret = b->returns; a.index = index_dev; a.first = first; a.n_total = b->n_rows; a.n = n; a.G = G;
     a.vf_coef = hp->vf_coef; a.part = o->part; a.spart = o->spart; a.bc_loss = hp->loss;
-    hipLaunchKernelGGL(k_bc_grad, dim3(G, has_ret ? 2 : 1), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
+    a.dh[0] = dh_pi; a.dh[1] = dh_vf;
+    if (dh_pi && dh_vf) hipLaunchKernelGGL(k_bc_grad_dh, dim3(G, has_ret ? 2 : 1), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
+    else hipLaunchKernelGGL(k_bc_grad, dim3(G, has_ret ? 2 : 1), dim3(WGT_WAVES * 64), o->lds_bytes, st, P, o->K, a);
     hipLaunchKernelGGL(k_bc_reduce, dim3(o->n_blocks), dim3(WGT_BLOCK), 0, st, P, o->part, o->spart, G, n, P.layer[1][0].w_flat,
                        has_ret, nll, hp->vf_coef, hp->ent_coef, params_dev, grad_out, stats_out ? stats_out : o->stats);
     WG_HIPCHK(hipGetLastError());
@@ -1046,7 +1058,7 @@ extern "C" int wg_bc_grad(wg_ppo o, const float* params_dev, const wg_bc_batch* 
     if (int rc = bc_check(w, o, params_dev, b, hp)) return rc;
     if (n < 1) return wg_fail(WG_ERR_INVALID, w + ": n < 1");
     if (!index_dev && (first < 0 || first + n > b->n_rows)) return wg_fail(WG_ERR_INVALID, w + ": rows first .. first + n - 1 leave the batch");
-    return t_bc_grad(&o->g, params_dev, b, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
+    return t_bc_grad(&o->g, params_dev, b, b->obs, index_dev, first, n, hp, grad_out, (float*)stats_out, (hipStream_t)stream);
 }
 
 extern "C" int wg_bc_update(wg_ppo o, float* params_dev, const wg_bc_batch* b, const int32_t* perm_dev, int n_epochs, int batch_size,
@@ -1059,9 +1071,17 @@ extern "C" int wg_bc_update(wg_ppo o, float* params_dev, const wg_bc_batch* b, c
     if (int rc = t_on_device(perm_dev, o->adam.device, (w + ": perm_dev").c_str())) return rc;
     return wg_each_minibatch(b->n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
-        if (int rc = t_bc_grad(&o->g, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        if (int rc = t_bc_grad(&o->g, params_dev, b, b->obs, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
         return t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
     });
+}
+
+// wg_internal.h: the supervised heads of a recurrent policy (wg_lstm_ppo.hip)
+extern "C" int wg_ppo_heads_bc_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* target,
+                                     const float* ret, int n, const wg_bc_hyper* hp, float* dh_pi, float* dh_vf, float* grad_out,
+                                     float* stats_out, void* stream) {
+    const wg_bc_batch b = {h_pi, target, ret, n};
+    return t_bc_grad(g, mlp_params_dev, &b, h_vf, nullptr, 0, n, hp, grad_out, stats_out, (hipStream_t)stream, dh_pi, dh_vf);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

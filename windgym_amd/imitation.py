@@ -28,9 +28,11 @@ LOSSES = ("mse", "nll")
 ARGS = ("expert", "loss", "deterministic", "refine_pass_n", "yaw_n", "search_yaw_max")
 
 
-def check_env(venv, policy, who="BehaviorCloning"):
-    """The refusals that need no device: what kind of env and policy these are."""
-    refuse_recurrent(policy, who)
+def check_env(venv, policy, who="BehaviorCloning", recurrent=False):
+    """The refusals that need no device: what kind of env and policy these are.  ``recurrent``: the caller clones INTO a recurrent
+    policy (``recurrent_imitation.RecurrentBehaviorCloning``) and checks the policy's kind itself."""
+    if not recurrent:
+        refuse_recurrent(policy, who)
     if getattr(venv, "population", None) is not None or getattr(policy, "population", None) is not None:
         raise NotImplementedError(f"{who}: cloning into a population is not implemented (clone one policy, then copy its weights)")
     if not (hasattr(venv, "batch") and hasattr(venv, "rollout")):
@@ -70,26 +72,15 @@ class BehaviorCloning(Trainer):
     ``YawTable``, that table as ``bc_table.npz``; :meth:`load` resumes
     bit-identically on an env in the same state.
 
-    Refused: a recurrent policy, a population, a split / central-critic policy (``NotImplementedError``); ``as_torch=False``, an
-    unknown ``loss`` or ``expert`` (``ValueError``)."""
+    Refused: a recurrent policy (``recurrent_imitation.RecurrentBehaviorCloning`` clones into one), a population, a split /
+    central-critic policy (``NotImplementedError``); ``as_torch=False``, an unknown ``loss`` or ``expert`` (``ValueError``)."""
 
     def __init__(self, policy, venv, expert="blondel_jimenez", n_steps=128, batch_size=None, n_epochs=4, learning_rate=1e-3,
                  loss="mse", ent_coef=0.0, vf_coef=0.0, gamma=0.99, gae_lambda=0.95, max_grad_norm=0.5, deterministic=False,
                  refine_pass_n=8, yaw_n=9, search_yaw_max=30.0, policy_kwargs=None, seed=None):
-        from .steady import MODEL_IDS
         check_env(venv, policy)
-        if loss not in LOSSES:
-            raise ValueError(f"BehaviorCloning: loss must be one of {list(LOSSES)}, not {loss!r}")
-        self.table = expert if hasattr(expert, "check_env") else None
-        if self.table is not None:
-            self.table.check_env(venv, "BehaviorCloning(expert=)")
-        elif not isinstance(expert, str) or expert not in MODEL_IDS:
-            raise ValueError(f"BehaviorCloning: expert must be one of {sorted(MODEL_IDS)} or a YawTable, not {expert!r}")
-        if not float(vf_coef) >= 0.0 or not float(ent_coef) >= 0.0:
-            raise ValueError("BehaviorCloning: vf_coef and ent_coef must be >= 0")
-        self._setup(n_steps, n_epochs, gamma, gae_lambda, 0.0, ent_coef, vf_coef, max_grad_norm, learning_rate, False, seed, None, None, False)
-        self.expert, self.loss, self.deterministic = expert, loss, bool(deterministic)
-        self.refine_pass_n, self.yaw_n, self.search_yaw_max = int(refine_pass_n), int(yaw_n), float(search_yaw_max)
+        self._setup_expert("BehaviorCloning", venv, expert, loss, ent_coef, vf_coef, deterministic, refine_pass_n, yaw_n, search_yaw_max,
+                           n_steps, n_epochs, gamma, gae_lambda, max_grad_norm, learning_rate, seed)
         n_steps = self.n_steps
         multi = getattr(venv, "possible_agents", None) is not None       # WindFarmVecEnvMulti: one row per (env, turbine)
         n_agents = int(venv.n_turb) if multi else 1
@@ -111,7 +102,30 @@ class BehaviorCloning(Trainer):
         self.multi, self.n_agents, self.n_env_steps = multi, n_agents, n_steps * int(venv.num_envs)
         self.opt = PPOOptimizer(policy)
         self._alloc(n_rows, (n_steps, venv.num_envs) + ((n_agents,) if multi else ()), -(-n_rows // batch_size))
+        self._alloc_expert()
+
+    def _setup_expert(self, who, venv, expert, loss, ent_coef, vf_coef, deterministic, refine_pass_n, yaw_n, search_yaw_max, n_steps,
+                      n_epochs, gamma, gae_lambda, max_grad_norm, learning_rate, seed):
+        """The arguments every cloning trainer takes (this class and ``recurrent_imitation.RecurrentBehaviorCloning``, ``who`` in the
+        messages): checked without a device, then kept."""
+        from .steady import MODEL_IDS
+        if loss not in LOSSES:
+            raise ValueError(f"{who}: loss must be one of {list(LOSSES)}, not {loss!r}")
+        self.table = expert if hasattr(expert, "check_env") else None
+        if self.table is not None:
+            self.table.check_env(venv, f"{who}(expert=)")
+        elif not isinstance(expert, str) or expert not in MODEL_IDS:
+            raise ValueError(f"{who}: expert must be one of {sorted(MODEL_IDS)} or a YawTable, not {expert!r}")
+        if not float(vf_coef) >= 0.0 or not float(ent_coef) >= 0.0:
+            raise ValueError(f"{who}: vf_coef and ent_coef must be >= 0")
+        self._setup(n_steps, n_epochs, gamma, gae_lambda, 0.0, ent_coef, vf_coef, max_grad_norm, learning_rate, False, seed, None, None, False)
+        self.expert, self.loss, self.deterministic = expert, loss, bool(deterministic)
+        self.refine_pass_n, self.yaw_n, self.search_yaw_max = int(refine_pass_n), int(yaw_n), float(search_yaw_max)
+
+    def _alloc_expert(self):
+        """The label kernel's handle and buffers and the running target table (after ``policy`` / ``batch`` / ``n_steps`` are set)."""
         from .binding import ExpertLabels
+        n_steps = self.n_steps
         t, b = self.torch, self.batch
         self._lab = ExpertLabels(b)
         f32 = dict(dtype=t.float32, device=b.device)
@@ -217,6 +231,8 @@ class BehaviorCloning(Trainer):
                                         refusal="not a windgym_amd BehaviorCloning checkpoint")
         if "bc" not in meta:
             raise ValueError("not a windgym_amd BehaviorCloning checkpoint")
+        if "lstm_state.npy" in members:
+            raise ValueError("not a windgym_amd BehaviorCloning checkpoint: RecurrentBehaviorCloning wrote it, and its load() resumes it")
         desc, tensors = read_sb3_zip(path, activation=meta["desc"]["activation"])
         pol = MlpPolicy(desc["n_in"], desc["n_out"], desc["hidden_pi"], desc["hidden_vf"], desc["activation"],
                         device=venv.batch.device.index if device is None else device, seed=meta["policy_seed"],

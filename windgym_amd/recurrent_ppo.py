@@ -103,6 +103,59 @@ class RecurrentPPOOptimizer(HandleOptimizer):
                                             float(max_grad_norm), st.data_ptr(), self.policy._stream()), "wg_lstm_ppo_update")
         return st
 
+    # -- the supervised loss on the same handle (recurrent_imitation.RecurrentBehaviorCloning) ------------------------------------
+    def _bc_batch(self, roll, loss, ent_coef, vf_coef):
+        """-> (wg_lstm_bc_batch, T, B, wg_bc_hyper) of a rollout that carries ``labels [T, B, n_out]`` (the expert's actions) and,
+        optionally, ``returns [T, B]`` (absent or ``None``: the critic is left alone)."""
+        from .binding import BC_LOSS, CBcHyper, CLstmBcBatch
+        t, p = self.torch, self.policy
+        if loss not in BC_LOSS:
+            raise ValueError(f"loss must be one of {sorted(BC_LOSS)}, not {loss!r}")
+        lab, ret = roll["labels"], roll.get("returns")
+        if not (device_tensor(lab, t.float32) and lab.ndim == 3 and lab.shape[2] == p.n_out):
+            raise ValueError(f"labels must be a contiguous float32 CUDA tensor [T, B, {p.n_out}]")
+        T, B = lab.shape[:2]
+        if ret is not None:
+            self._f32(ret, (T, B), "returns")
+        obs, es, s0 = roll["obs"], roll["episode_start"], roll["lstm_state0"]
+        if not (device_tensor(obs, t.float32) and obs.ndim == 3 and obs.shape[0] >= T and tuple(obs.shape[1:]) == (B, p.n_in)):
+            raise ValueError(f"obs must be a contiguous float32 CUDA tensor [>= {T}, {B}, {p.n_in}]")
+        if not (device_tensor(es, t.uint8) and es.ndim == 2 and es.shape[0] >= T and es.shape[1] == B):
+            raise ValueError(f"episode_start must be a contiguous uint8 CUDA tensor [>= {T}, {B}]")
+        if not (device_tensor(s0, t.float32) and tuple(s0.shape) == (p.nets, 2, B, p.H)):
+            raise ValueError(f"lstm_state0 must be a contiguous float32 CUDA tensor [{p.nets}, 2, {B}, {p.H}]")
+        b = CLstmBcBatch(obs.data_ptr(), lab.data_ptr(), None if ret is None else ret.data_ptr(), es.data_ptr(), s0.data_ptr(), int(T), int(B))
+        return b, int(T), int(B), CBcHyper(BC_LOSS[loss], float(ent_coef), float(vf_coef))
+
+    def bc_grad(self, roll, envs, *, loss="mse", ent_coef=0.0, vf_coef=0.0, out=None, stats=None):
+        """wg_lstm_bc_grad: the supervised loss on the expert's actions ``roll["labels"]`` over the minibatch of the envs ``envs``
+        (int32 CUDA) with all their steps -> (flat gradient ``[n_params]``, statistics ``[8]`` in the order of binding.BC_STATS).
+        Without ``roll["returns"]`` there is no critic term."""
+        t = self.torch
+        b, _, _, hp = self._bc_batch(roll, loss, ent_coef, vf_coef)
+        self._index(envs, 1)
+        g = self.grad_buf if out is None else out
+        st = t.zeros(8, dtype=t.float32, device=self.policy.device) if stats is None else stats
+        self._chk(self.L.wg_lstm_bc_grad(self._h, self.policy.params.data_ptr(), C.byref(b), envs.data_ptr(), int(envs.numel()), C.byref(hp),
+                                         g.data_ptr(), st.data_ptr(), self.policy._stream()), "wg_lstm_bc_grad")
+        return g, st
+
+    def bc_update(self, roll, perm, envs_per_batch, *, loss="mse", ent_coef=0.0, vf_coef=0.0, learning_rate=1e-3, max_grad_norm=0.5,
+                  stats=None):
+        """wg_lstm_bc_update: ``perm`` int32 ``[n_epochs, B]``, a permutation of the envs per epoch -> statistics
+        ``[n_epochs, n_minibatches, 8]``."""
+        t = self.torch
+        b, _, B, hp = self._bc_batch(roll, loss, ent_coef, vf_coef)
+        if perm.ndim != 2 or perm.shape[1] != B:
+            raise ValueError(f"perm must be [n_epochs, {B}]")
+        self._index(perm, B)
+        n_epochs, n_mb = perm.shape[0], -(-B // int(envs_per_batch))
+        st = t.zeros((n_epochs, n_mb, 8), dtype=t.float32, device=self.policy.device) if stats is None else stats
+        self._chk(self.L.wg_lstm_bc_update(self._h, self.policy.params.data_ptr(), C.byref(b), perm.data_ptr(), n_epochs, int(envs_per_batch),
+                                           C.byref(hp), float(learning_rate), float(max_grad_norm), st.data_ptr(), self.policy._stream()),
+                  "wg_lstm_bc_update")
+        return st
+
 
 class RecurrentPPO(Trainer):
     """sb3-contrib's ``RecurrentPPO`` on a ``WindFarmVecEnv``: :class:`~windgym_amd.ppo.PPO`'s arguments, defaults, schedules, ``log``
@@ -209,6 +262,9 @@ class RecurrentPPO(Trainer):
         meta, members = read_checkpoint(path, learning_rate, clip_range, needs=("lstm_state.npy",),
                                         refusal="not a windgym_amd RecurrentPPO checkpoint (an sb3-contrib zip loads with "
                                                 "MlpLstmPolicy.from_sb3_zip, a PPO checkpoint with PPO.load)")
+        if "bc" in meta:
+            raise ValueError("not a windgym_amd RecurrentPPO checkpoint: RecurrentBehaviorCloning wrote it (RecurrentBehaviorCloning.load "
+                             "resumes it; MlpLstmPolicy.from_sb3_zip reads its policy for RecurrentPPO to fine-tune)")
         pol = MlpLstmPolicy.from_sb3_zip(path, activation=meta["desc"]["activation"], device=venv.batch.device.index if device is None else device,
                                          seed=meta["policy_seed"])
         pol.counter = int(meta["policy_counter"])
