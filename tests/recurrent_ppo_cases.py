@@ -3,7 +3,12 @@ and the CPU test of the cases themselves (tests/test_recurrent_ppo_cases.py): pl
 reference of a case, computed once per process.  No GPU import.  TEST INFRASTRUCTURE.
 
 A BUILT case is ``(spec, flat, roll, envs, kw)``: the twin's spec, the flat float32 parameters, the rollout dict of
-``lstm_bptt_twin.random_rollout``, the minibatch's env ids (int32) and the loss arguments."""
+``lstm_bptt_twin.random_rollout``, the minibatch's env ids (int32) and the loss arguments.
+
+THE SUPERVISED HEAD (tests/test_gpu_recurrent_imitation_limits.py, tests/test_bc_cases.py) runs the same tables: ``build_arch`` /
+``build_edge`` take the rollout's generator, and ``lstm_bc_twin.random_rollout`` draws the same buffers from the same seed and adds the
+labels, so a case's parameters, observations, starts and states are the PPO case's.  ``bc_arch`` / ``bc_edge`` hold a built case per
+(loss, returns or not) with its ``BcReference``."""
 from __future__ import annotations
 
 import functools
@@ -11,6 +16,7 @@ import functools
 import numpy as np
 import torch
 
+import lstm_bc_twin as bt
 import lstm_bptt_twin as tw
 from rl_helpers import DEEP
 
@@ -42,12 +48,12 @@ def make_spec(n_in, H, shared, hidden_pi=(16,), hidden_vf=(16,), n_out=2, activa
     return dict(n_in=n_in, H=H, n_out=n_out, hidden_pi=tuple(hidden_pi), hidden_vf=tuple(hidden_vf), shared=shared, activation=activation)
 
 
-def build_arch(case):
+def build_arch(case, rollout=tw.random_rollout):
     n_in, H, T, Bm, shared, hidden_pi, hidden_vf, n_out, activation = case
     spec = make_spec(n_in, H, shared, hidden_pi, hidden_vf, n_out, activation)
     B = Bm + EXTRA
     flat = tw.random_params(spec, seed=Bm + T)
-    roll = tw.random_rollout(spec, flat, T, B, seed=H + T)
+    roll = rollout(spec, flat, T, B, seed=H + T)
     envs = np.random.default_rng(n_in).permutation(B)[:Bm].astype(np.int32)
     return spec, flat, roll, envs, dict(KW)
 
@@ -65,6 +71,13 @@ CELL_EDGES = {
     "constant_advantage": ("lstm_actor.", "mlp_extractor.policy_net.", "action_net."),
 }
 SATURATION = 20.0                            # saturated_gates: every LSTM tensor times this
+# the supervised head's: constant_advantage has no meaning there; its counterpart is labels that ARE the float64 twin's means, rounded
+# to float32 — the actor's path is then small (half an ulp of error per output), not zero
+BC_ONLY_EDGES = ("labels_are_the_means",)
+BC_CELL_EDGES = tuple(e for e in CELL_EDGES if e != "constant_advantage") + BC_ONLY_EDGES
+BC_KW = dict(ent_coef=KW["ent_coef"], vf_coef=KW["vf_coef"])
+BC_COMBOS = [(loss, with_ret) for loss in ("mse", "nll") for with_ret in (True, False)]
+REUSE_CALLS = [(9, 40), (4, 33), (9, 1), (1, 40), (4, 33)]          # (T, Bm) of the handle-reuse tests; the handle is made at (9, 40)
 
 
 def _lstm_slices(spec):
@@ -78,10 +91,10 @@ def _lstm_slices(spec):
     return out
 
 
-def build_edge(edge):
+def build_edge(edge, rollout=tw.random_rollout):
     """Base: n_in = 7, H = 40, T = 6, B = Bm = 37 (a full env tile and five columns, every env in the minibatch), two nets, heads
     (16,), 2 outputs, tanh."""
-    assert edge in CELL_EDGES, edge
+    assert edge in CELL_EDGES or (edge in BC_ONLY_EDGES and rollout is not tw.random_rollout), edge
     n_in, H, T, B = 7, 40, 6, 37
     if edge == "long_carry":
         H, T, B = 64, 128, 3
@@ -103,7 +116,7 @@ def build_edge(edge):
         for name, sl in _lstm_slices(spec).items():
             if name.endswith("bias_ih_l0"):
                 flat[sl][H:2 * H] += np.float32(4.0)          # the forget gate's rows of (i, f, g, o)
-    roll = tw.random_rollout(spec, flat, T, B, seed=12, starts=starts)
+    roll = rollout(spec, flat, T, B, seed=12, starts=starts)
     if edge == "all_fresh":
         roll["lstm_state0"][:] = np.nan
     elif edge == "large_c0":
@@ -142,14 +155,27 @@ class Reference:
     def __init__(self, spec, flat, roll, envs, kw):
         self.loss, self.stats, self.grad, self.ratio = tw.loss_and_grad(spec, flat, roll, envs, **kw)
         self.grad32 = tw.loss_and_grad(spec, flat, roll, envs, dtype=torch.float32, **kw)[2]
+        self._parts(spec, roll["raw"].shape[0], envs)
+
+    def _parts(self, spec, T, envs):
         self.d32 = np.abs(self.grad32 - self.grad)
         self.n_lstm = tw.nets(spec) * 4 * spec["H"] * (spec["n_in"] + spec["H"] + 2)
-        self.rows = roll["raw"].shape[0] * len(envs)
+        self.rows = T * len(envs)
         self.slices, o = [], 0
         for name, shape in tw.layout(spec):
             n = int(np.prod(shape))
             self.slices.append((name, slice(o, o + n)))
             o += n
+
+
+class BcReference(Reference):
+    """The same for the supervised head: ``lstm_bc_twin.loss_and_grad`` in float64 and, for e32, the float32 torch run of the same
+    rule.  ``kw``: ``loss``, ``ent_coef``, ``vf_coef``; ``roll["returns"]`` ``None``: no critic term."""
+
+    def __init__(self, spec, flat, roll, envs, kw):
+        self.loss, self.stats, self.grad = bt.loss_and_grad(spec, flat, roll, envs, **kw)
+        self.grad32 = bt.loss_and_grad(spec, flat, roll, envs, dtype=torch.float32, **kw)[2]
+        self._parts(spec, roll["labels"].shape[0], envs)
 
 
 def compare(ref, g):
@@ -174,6 +200,39 @@ def edge(name):
     """(built case, Reference) of the cell edge ``name``; computed once, read-only."""
     built = build_edge(name)
     return built, Reference(*built)
+
+
+def _bc_case(built, loss, with_ret):
+    spec, flat, roll, envs, kw = built
+    roll = roll if with_ret else dict(roll, returns=None)
+    built = (spec, flat, roll, envs, dict(loss=loss, ent_coef=kw["ent_coef"], vf_coef=kw["vf_coef"]))
+    return built, BcReference(*built)
+
+
+@functools.lru_cache(maxsize=None)
+def _bc_built(kind, key):
+    if kind == "arch":
+        return build_arch(ARCH_CASES[key], rollout=bt.random_rollout)
+    sigma = 0.0 if key == "labels_are_the_means" else 0.3
+    return build_edge(key, rollout=functools.partial(bt.random_rollout, sigma=sigma))
+
+
+@functools.lru_cache(maxsize=None)
+def bc_arch(i, loss, with_ret):
+    """(built case, BcReference) of ARCH_CASES[i] under the supervised ``loss``, with the returns or without; computed once, read-only."""
+    return _bc_case(_bc_built("arch", i), loss, with_ret)
+
+
+@functools.lru_cache(maxsize=None)
+def bc_edge(name, loss, with_ret):
+    """(built case, BcReference) of the cell edge ``name`` of BC_CELL_EDGES; computed once, read-only."""
+    return _bc_case(_bc_built("edge", name), loss, with_ret)
+
+
+def bc_is_zero_tensor(edge, name, loss, with_ret):
+    """What a supervised case makes EXACTLY zero: the cell edge's tensors, the critic's side without returns, log_std under MSE."""
+    critic = name.startswith("lstm_critic.") or "value_net" in name
+    return is_zero_tensor(edge, name) or (critic and not with_ret) or (name == "log_std" and loss == "mse")
 
 
 def tensor_class(name):

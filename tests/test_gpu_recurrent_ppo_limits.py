@@ -93,7 +93,7 @@ def test_cell_edge_grad_vs_twin(name):
     opt.close(); p.close()
 
 
-REUSE_CALLS = [(9, 40), (4, 33), (9, 1), (1, 40), (4, 33)]
+REUSE_CALLS = rc.REUSE_CALLS
 
 
 @pytest.mark.parametrize("shared", [False, True], ids=["two", "shared"])
