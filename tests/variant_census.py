@@ -3,6 +3,9 @@ env_kernel, wg_envb.hip envb_kernel), restated by hand, and a table of small cas
 one.  tests/test_variant_census.py pins on the CPU that the cases reach all of ALL_KEYS (through the plan of
 tests/plan_shim.cpp); tests/test_gpu_variant_census.py runs every case by value against the oracle.
 
+The cases fix the task rules at env1_config's (Baseline reward, Power_avg 10, Power_scaling 1, no action penalty, Local
+controller), with the "yaw" action; tests/rule_cases.py varies them on every step path.
+
 A new template axis of a step kernel adds its values to the key tuples below and a case per new instantiation to CASES."""
 import itertools
 from dataclasses import dataclass
