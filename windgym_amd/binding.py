@@ -339,8 +339,56 @@ def _chk(rc, what):
         raise WindGymHipError(f"{what} failed (rc={rc}): {msg}")
 
 
-class HipBatch:
+def device_tensor(x, dtype):
+    """What every tensor handed to the library must be: a contiguous CUDA tensor of ``dtype`` (its size is the caller's to check)."""
+    import torch
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous()
+
+
+def tensor_ptr(x, dtype, message, numel=None, at_least=None, shape=None, device=None):
+    """``x.data_ptr()`` of a :func:`device_tensor` — where given: of ``numel`` elements, of ``at_least`` that many, of ``shape``, on
+    ``device`` — or ``ValueError(message)``."""
+    if not (device_tensor(x, dtype) and (numel is None or x.numel() == numel) and (at_least is None or x.numel() >= at_least)
+            and (shape is None or tuple(x.shape) == tuple(shape)) and (device is None or x.device == device)):
+        raise ValueError(message)
+    return x.data_ptr()
+
+
+class Handle:
+    """What every wrapper of a handle of the library is: ``L`` the library, the raw handle in ``_h`` (``handle_attr``; None once
+    closed) and ``destroy``, the entry that frees it.  ``_stream`` wants ``torch`` and ``device`` of the subclass."""
+
+    destroy, handle_attr = None, "_h"
+
+    def close(self):
+        """``<destroy>(handle)``, once: a closed or never opened wrapper has nothing to free."""
+        h = getattr(self, self.handle_attr, None)
+        if h:
+            setattr(self, self.handle_attr, None)
+            getattr(self.L, self.destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _blob(self, get_entry):
+        """The handle's state blob by the two calls of ``get_entry``: the size, then the bytes."""
+        get, n = getattr(self.L, get_entry), C.c_size_t(0)
+        _chk(get(self._h, None, C.byref(n)), get_entry)
+        buf = (C.c_char * n.value)()
+        _chk(get(self._h, buf, C.byref(n)), get_entry)
+        return bytes(buf)
+
+
+class HipBatch(Handle):
     """A batch of ``cfg.n_envs`` farms resident on one MI355X."""
+
+    destroy = "wg_destroy"
 
     def __init__(self, cfg: EnvConfig, device: int | None = None):
         import torch
@@ -373,21 +421,6 @@ class HipBatch:
         self._cur_stream = torch.cuda.current_stream
         self._script = None
         self._box = None
-
-    # -- lifetime -----------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     # -- API ----------------------------------------------------------------------------------------
     def reset(self, seeds=None, mask=None):
@@ -531,8 +564,8 @@ class HipBatch:
         shape, dtype = self.info_shape(name)
         if out is None:
             out = t.zeros(shape, dtype=dtype, device=self.device)
-        elif not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape)):
-            raise ValueError(f"info({name!r}, out=): out must be a contiguous CUDA tensor of shape {shape} and dtype {dtype}")
+        else:
+            tensor_ptr(out, dtype, f"info({name!r}, out=): out must be a contiguous CUDA tensor of shape {shape} and dtype {dtype}", shape=shape)
         _chk(self.L.wg_get_info(self._h, INFO[name], C.c_void_p(out.data_ptr()), self._stream()), "wg_get_info")
         return out
 
@@ -569,7 +602,7 @@ class HipBatch:
             _chk(self.L.wg_set_wind_device(self._h, None), "wg_set_wind_device")
             return
         t = self.torch
-        assert wind.is_cuda and wind.dtype == t.float64 and wind.is_contiguous() and tuple(wind.shape) == (self.B, 3)
+        assert device_tensor(wind, t.float64) and tuple(wind.shape) == (self.B, 3)
         self._wind_dev = wind                                   # keep it alive
         _chk(self.L.wg_set_wind_device(self._h, C.c_void_p(wind.data_ptr())), "wg_set_wind_device")
 
@@ -636,11 +669,7 @@ class HipBatch:
         self._box = bs[0]      # (the library keeps its own copies; the caller's tensors may go)
 
     def get_state(self) -> bytes:
-        n = C.c_size_t(0)
-        _chk(self.L.wg_get_state(self._h, None, C.byref(n)), "wg_get_state")
-        buf = (C.c_char * n.value)()
-        _chk(self.L.wg_get_state(self._h, buf, C.byref(n)), "wg_get_state")
-        return bytes(buf)
+        return self._blob("wg_get_state")
 
     def set_state(self, blob: bytes):
         _chk(self.L.wg_set_state(self._h, blob, len(blob)), "wg_set_state")
@@ -718,12 +747,13 @@ class HipBatch:
         return b.value, bool(r.value), d.value
 
 
-class Curriculum:
+class Curriculum(Handle):
     """The ``wg_curriculum`` handle of one :class:`HipBatch`: the per-env state of the yaw-curriculum reward shaping and its one
     kernel, k_curriculum (include/windgym_hip.h states the recurrence; ``windgym_amd.curriculum.YawCurriculum`` is the user-facing
     class).  ``set_targets`` and ``shape`` enqueue on torch's current stream and synchronise nothing."""
 
     HEADER_BYTES = 16        # the state blob: (magic, B, N, reserved) int32, then yprev f64[B, N], the targets g f64[B, N], ...
+    destroy = "wg_curriculum_destroy"
 
     def __init__(self, batch: HipBatch):
         self.batch, self.L, self.torch = batch, batch.L, batch.torch
@@ -732,25 +762,10 @@ class Curriculum:
         _chk(self.L.wg_curriculum_create(batch._h, C.byref(h)), "wg_curriculum_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_curriculum_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def state(self) -> bytes:
         """The state blob (synchronises).  ``ValueError`` once, naming ``ep_row_dev``, when an earlier :meth:`shape` met an
         ``ep_row`` entry that was no row of ``ep_target`` (the kernel skipped it)."""
-        n = C.c_size_t(0)
-        _chk(self.L.wg_curriculum_get_state(self._h, None, C.byref(n)), "wg_curriculum_get_state")
-        buf = (C.c_char * n.value)()
-        _chk(self.L.wg_curriculum_get_state(self._h, buf, C.byref(n)), "wg_curriculum_get_state")
-        return bytes(buf)
+        return self._blob("wg_curriculum_get_state")
 
     def load_state(self, blob: bytes):
         _chk(self.L.wg_curriculum_set_state(self._h, blob, len(blob)), "wg_curriculum_set_state")
@@ -762,10 +777,9 @@ class Curriculum:
 
     def set_targets(self, yaw):
         """wg_curriculum_set_targets: ``yaw`` float64 CUDA ``[B, N]``."""
-        t = self.torch
-        if not (t.is_tensor(yaw) and yaw.is_cuda and yaw.dtype == t.float64 and yaw.is_contiguous() and tuple(yaw.shape) == (self.B, self.N)):
-            raise ValueError(f"set_targets(): yaw must be a contiguous float64 CUDA tensor [{self.B}, {self.N}]")
-        _chk(self.L.wg_curriculum_set_targets(self._h, yaw.data_ptr(), self.batch._stream()), "wg_curriculum_set_targets")
+        ptr = tensor_ptr(yaw, self.torch.float64, f"set_targets(): yaw must be a contiguous float64 CUDA tensor [{self.B}, {self.N}]",
+                         shape=(self.B, self.N))
+        _chk(self.L.wg_curriculum_set_targets(self._h, ptr, self.batch._stream()), "wg_curriculum_set_targets")
 
     def shape(self, T, yaw0, actions, yaw_after, truncated, ep_row, ep_target, n_targets, weight, momentum, reward, shaped,
               yaw_diff=None, yaw_out=None):
@@ -779,9 +793,8 @@ class Curriculum:
                                       ("weight", weight, t.float64, T), ("reward", reward, t.float32, T * B),
                                       ("shaped", shaped, t.float32, T * B), ("yaw_diff", yaw_diff, t.float32, T * B),
                                       ("yaw_out", yaw_out, t.float32, T * B * N)):
-            if x is not None and not (t.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= max(numel, 0)):
-                raise ValueError(f"shape(): {name} must be a contiguous {dtype} CUDA tensor of at least {numel} elements")
-            ptrs.append(None if x is None else x.data_ptr())
+            ptrs.append(None if x is None else tensor_ptr(
+                x, dtype, f"shape(): {name} must be a contiguous {dtype} CUDA tensor of at least {numel} elements", at_least=max(numel, 0)))
         _chk(self.L.wg_curriculum_shape(self._h, T, *ptrs[:6], int(n_targets), ptrs[6], float(momentum), *ptrs[7:], self.batch._stream()),
              "wg_curriculum_shape")
 
@@ -806,9 +819,8 @@ class ExpertLabels:
                                       ("truncated", truncated, t.uint8, T * B), ("ep_row", ep_row, t.int32, T * B),
                                       ("ep_target", ep_target, t.float64, int(n_targets) * N), ("targets", targets, t.float64, B * N),
                                       ("labels", labels, t.float32, T * B * N), ("yaw_diff", yaw_diff, t.float32, T * B)):
-            if x is not None and not (t.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= max(numel, 0)):
-                raise ValueError(f"labels(): {name} must be a contiguous {dtype} CUDA tensor of at least {numel} elements")
-            ptrs.append(None if x is None else x.data_ptr())
+            ptrs.append(None if x is None else tensor_ptr(
+                x, dtype, f"labels(): {name} must be a contiguous {dtype} CUDA tensor of at least {numel} elements", at_least=max(numel, 0)))
         _chk(self.L.wg_expert_labels(self.batch._h, T, *ptrs[:5], int(n_targets), *ptrs[5:], self._err.data_ptr(), self.batch._stream()),
              "wg_expert_labels")
         return labels
@@ -819,15 +831,17 @@ class ExpertLabels:
         _chk(self.L.wg_expert_labels_check(self.batch._h, self._err.data_ptr()), "wg_expert_labels_check")
 
 
-class YawTableHandle:
+class YawTableHandle(Handle):
     """A ``wg_yaw_table`` handle: the axes and the yaws ``[C, N]`` of a yaw table on one device and its lookup kernels
     (include/windgym_hip.h states the node rule; ``windgym_amd.yaw_table.YawTable`` is the user-facing class).  ``rows``, ``targets``
     and ``act`` enqueue on torch's current stream and synchronise nothing."""
 
+    destroy = "wg_yaw_table_destroy"
+
     def __init__(self, torch, device, ti, ws, wd, wrap_wd, yaw):
         self.torch, self.L, self.device = torch, load_library(), device
         ax = [np.ascontiguousarray(a, dtype=np.float64) for a in (ti, ws, wd)]
-        if not (torch.is_tensor(yaw) and yaw.is_cuda and yaw.dtype == torch.float64 and yaw.is_contiguous() and yaw.dim() == 2):
+        if not (device_tensor(yaw, torch.float64) and yaw.dim() == 2):
             raise ValueError("yaw must be a contiguous float64 CUDA tensor [C, N]")
         self.N = int(yaw.shape[1])
         args = [x for a in ax for x in (a.ctypes.data_as(C.c_void_p), len(a))]
@@ -835,23 +849,8 @@ class YawTableHandle:
         _chk(self.L.wg_yaw_table_create(device.index, *args, int(bool(wrap_wd)), self.N, yaw.data_ptr(), 1, C.byref(h)), "wg_yaw_table_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_yaw_table_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def _wind(self, who, wind):
-        t = self.torch
-        if not (t.is_tensor(wind) and wind.is_cuda and wind.dtype == t.float64 and wind.is_contiguous() and wind.dim() >= 1 and wind.shape[-1] == 3):
+        if not (device_tensor(wind, self.torch.float64) and wind.dim() >= 1 and wind.shape[-1] == 3):
             raise ValueError(f"{who}: wind must be a contiguous float64 CUDA tensor [..., 3] (ws, wd, ti)")
         return wind.numel() // 3
 
@@ -859,14 +858,11 @@ class YawTableHandle:
         """wg_yaw_table_rows: ``wind [..., 3]`` float64, ``mask [...]`` uint8 or ``None`` -> int32 ``[...]``."""
         t = self.torch
         n = self._wind("rows()", wind)
-        if mask is not None and not (t.is_tensor(mask) and mask.is_cuda and mask.dtype == t.uint8 and mask.is_contiguous() and mask.numel() == n):
-            raise ValueError(f"rows(): mask must be a contiguous uint8 CUDA tensor of {n} elements")
+        mp = None if mask is None else tensor_ptr(mask, t.uint8, f"rows(): mask must be a contiguous uint8 CUDA tensor of {n} elements", numel=n)
         if out is None:
             out = t.empty(tuple(wind.shape[:-1]), dtype=t.int32, device=wind.device)
-        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.int32 and out.is_contiguous() and out.numel() == n):
-            raise ValueError(f"rows(): out must be a contiguous int32 CUDA tensor of {n} elements")
-        _chk(self.L.wg_yaw_table_rows(self._h, n, wind.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr(), self._stream()),
-             "wg_yaw_table_rows")
+        op = tensor_ptr(out, t.int32, f"rows(): out must be a contiguous int32 CUDA tensor of {n} elements", numel=n)
+        _chk(self.L.wg_yaw_table_rows(self._h, n, wind.data_ptr(), mp, op, self._stream()), "wg_yaw_table_rows")
         return out
 
     def targets(self, wind, out=None):
@@ -875,26 +871,25 @@ class YawTableHandle:
         n = self._wind("targets()", wind)
         if out is None:
             out = t.zeros(tuple(wind.shape[:-1]) + (self.N,), dtype=t.float64, device=wind.device)
-        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float64 and out.is_contiguous() and out.numel() == n * self.N):
-            raise ValueError(f"targets(): out must be a contiguous float64 CUDA tensor of {n * self.N} elements")
-        _chk(self.L.wg_yaw_table_targets(self._h, n, wind.data_ptr(), out.data_ptr(), self._stream()), "wg_yaw_table_targets")
+        op = tensor_ptr(out, t.float64, f"targets(): out must be a contiguous float64 CUDA tensor of {n * self.N} elements", numel=n * self.N)
+        _chk(self.L.wg_yaw_table_targets(self._h, n, wind.data_ptr(), op, self._stream()), "wg_yaw_table_targets")
         return out
 
     def act(self, batch, out):
         """wg_yaw_table_act on ``batch`` (a :class:`HipBatch`): ``out`` float32 ``[B, N]``."""
-        t = self.torch
-        if not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and out.numel() == batch.B * batch.N):
-            raise ValueError(f"act(): out must be a contiguous float32 CUDA tensor [{batch.B}, {batch.N}]")
-        _chk(self.L.wg_yaw_table_act(batch._h, self._h, out.data_ptr(), batch._stream()), "wg_yaw_table_act")
+        op = tensor_ptr(out, self.torch.float32, f"act(): out must be a contiguous float32 CUDA tensor [{batch.B}, {batch.N}]",
+                        numel=batch.B * batch.N)
+        _chk(self.L.wg_yaw_table_act(batch._h, self._h, op, batch._stream()), "wg_yaw_table_act")
         return out
 
 
-class Norm:
+class Norm(Handle):
     """A ``wg_norm`` handle: SB3's VecNormalize statistics on the device (include/windgym_hip.h restates the rules;
     ``windgym_amd.normalize.VecNormalize`` is the user-facing class).  ``obs``, ``reward`` and ``reset_returns`` enqueue on torch's
     current stream and synchronise nothing; ``state`` / ``load_state`` synchronise."""
 
     HEADER_BYTES = 16        # the state blob: (magic, O, B, 0) int32, then float64 obs mean [O], var [O], count, ret mean, var, count, returns [B]
+    destroy = "wg_norm_destroy"
 
     def __init__(self, n_obs, n_envs, device, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99,
                  epsilon=1e-8):
@@ -908,26 +903,8 @@ class Norm:
         _chk(self.L.wg_norm_create(C.byref(d), int(device), C.byref(h)), "wg_norm_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_norm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def state(self) -> bytes:
-        n = C.c_size_t(0)
-        _chk(self.L.wg_norm_get_state(self._h, None, C.byref(n)), "wg_norm_get_state")
-        buf = (C.c_char * n.value)()
-        _chk(self.L.wg_norm_get_state(self._h, buf, C.byref(n)), "wg_norm_get_state")
-        return bytes(buf)
+        return self._blob("wg_norm_get_state")
 
     def load_state(self, blob: bytes):
         _chk(self.L.wg_norm_set_state(self._h, blob, len(blob)), "wg_norm_set_state")
@@ -948,12 +925,8 @@ class Norm:
         _chk(self.L.wg_norm_reset_returns(self._h, mp, self._stream()), "wg_norm_reset_returns")
 
     def _rows(self, name, x, dtype, numel=None):
-        t = self.torch
-        if not (t.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == dtype and x.is_contiguous()
-                and (numel is None or x.numel() == numel)):
-            raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor on {self.device}"
-                             + ("" if numel is None else f" of {numel} elements"))
-        return x.data_ptr()
+        return tensor_ptr(x, dtype, f"{name} must be a contiguous {dtype} CUDA tensor on {self.device}"
+                          + ("" if numel is None else f" of {numel} elements"), numel=numel, device=self.device)
 
     def obs(self, obs, out, extra=None, extra_out=None):
         """wg_norm_obs on ``[n_rows, O]`` float32 tensors (``extra`` / ``extra_out``: the final rows, or both ``None``)."""

@@ -84,7 +84,8 @@ struct wg_env_s {
     void* abox8 = nullptr;
     double* wind_dev = nullptr;      // per-env wind override (wg_set_wind)
     int device;
-    std::vector<Alloc> allocs;      // everything owned by the handle (state blob = allocs flagged `state`)
+    WgDevMem mem;                   // owns every device buffer of the handle, the box copies above included
+    std::vector<Alloc> allocs;      // what wg_create allocated, in order (state blob = allocs flagged `state`)
     std::vector<size_t> state_idx;  // indices into allocs that make up the serialisable state
     uint8_t* mask_dev = nullptr;
     uint64_t* seeds_dev = nullptr;
@@ -135,17 +136,9 @@ static int sync_dev_params(wg_env_s* h) {
 
 template <typename T>
 static int dev_alloc(wg_env_s* h, T** out, size_t n, bool state, bool zero = true) {
-    size_t bytes = sizeof(T) * (n ? n : 1);
-    void* ptr = nullptr;
-    hipError_t e = hipMalloc(&ptr, bytes);
-    if (e != hipSuccess) return wg_fail(WG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if (zero) {
-        e = hipMemset(ptr, 0, bytes);
-        if (e != hipSuccess) return wg_fail(WG_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
-    }
-    h->allocs.push_back({ptr, bytes});
+    if (int rc = h->mem.alloc("wg_create", out, n, zero)) return rc;
+    h->allocs.push_back({*out, sizeof(T) * (n ? n : 1)});
     if (state) h->state_idx.push_back(h->allocs.size() - 1);
-    *out = (T*)ptr;
     return 0;
 }
 template <typename T, typename S>
@@ -288,7 +281,7 @@ extern "C" int wg_create(const wg_config* c, int device, wg_handle* out) {
     }
     std::unique_ptr<wg_env_s, HandleGuard> owner(new wg_env_s());      // (value-initialised: every pointer of d / fd starts null)
     wg_env_s* h = owner.get();
-    h->device = device;
+    h->mem.device = h->device = device;
     h->hooks = wg_hooks_read();
     if (int rc = wg_plan_create(c, h->hooks, lds_limit, &h->plan, &err)) return wg_fail(rc, err);
     h->p = h->plan.p;
@@ -341,12 +334,7 @@ extern "C" int wg_destroy(wg_handle h) {
     drop_step_graphs(h);
     if (h->cap_stream) hipStreamDestroy(h->cap_stream);
     for (auto& e : h->ev) hipEventDestroy(e);
-    for (auto& a : h->allocs) hipFree(a.ptr);
-    if (h->box4) hipFree(h->box4);
-    if (h->box4c) hipFree(h->box4c);
-    if (h->abox4) hipFree(h->abox4);
-    if (h->box8) hipFree(h->box8);
-    if (h->abox8) hipFree(h->abox8);
+    h->mem.release();
     delete h;
     return 0;
 }
@@ -366,6 +354,13 @@ extern "C" int wg_hist_max(wg_handle h, int* hist_max) {
 // Stencil records of a box pool (FlowPtrs::box8 / abox8) for handles that run k_flow_envb: 8 x the interleaved copy.  Built only
 // while the whole pool's records stay below a quarter of the device memory and a box below 2^28 cells (32-bit record offsets);
 // otherwise the kernel keeps reading the brick-ordered box (same cells, same weights: the results are identical either way).
+// a box copy that a setter replaces: forgotten first (a failure must not leave the handle pointing at freed memory), then freed
+static int drop_box(wg_env_s* h, const char* who, void** box) {
+    void* const q = *box;
+    *box = nullptr;
+    return h->mem.free(who, q);
+}
+
 static int build_stencil_records(wg_env_s* h, void** owned, const float4** kernel_ptr, const void* box4, int n_boxes, int nx, int ny, int nz) {
     *kernel_ptr = nullptr;
     if (!(h->fp.envw && h->fp.turb_mode != WG_TURB_NONE)) return 0;      // (no k_flow_envb on this handle: nothing reads them)
@@ -379,7 +374,7 @@ static int build_stencil_records(wg_env_s* h, void** owned, const float4** kerne
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return skip("hipMemGetInfo failed");
     if (n_cells >= ((size_t)1 << 28)) return skip("a box of 2^28 cells or more");
     if (bytes > total_b / 4 || bytes > free_b / 2) return skip("the pool's records exceed a quarter of the device memory or half of what is free");
-    if (hipMalloc(owned, bytes) != hipSuccess) { *owned = nullptr; (void)hipGetLastError(); return skip("hipMalloc failed"); }
+    if (h->mem.alloc_bytes("stencil records", owned, bytes, false)) { (void)hipGetLastError(); return skip("hipMalloc failed"); }
     for (int k = 0; k < n_boxes; ++k)
         wg_launch_box_stencil((const char*)box4 + (size_t)k * n_cells * 16, (char*)*owned + (size_t)k * n_cells * 128, nx, ny, nz, nullptr);
     WG_HIPCHK(hipDeviceSynchronize());
@@ -399,11 +394,10 @@ extern "C" int wg_set_turbulence_boxes(wg_handle h, const float* const* boxes_de
     drop_step_graphs(h);           // the kernel arguments captured in them are about to change
     // the kernel-side pointers are cleared first: a failure below must not leave them dangling
     h->d.box = nullptr; h->fd.box4 = nullptr; h->fd.box4c = nullptr; h->fd.box8 = nullptr; h->fp.coarse = 0;
-    if (h->box8) { void* q = h->box8; h->box8 = nullptr; WG_HIPCHK(hipFree(q)); }
-    if (h->box4) { void* q = h->box4; h->box4 = nullptr; WG_HIPCHK(hipFree(q)); }
-    if (h->box4c) { void* q = h->box4c; h->box4c = nullptr; WG_HIPCHK(hipFree(q)); }
+    for (void** box : {&h->box8, &h->box4, &h->box4c})
+        if (int rc = drop_box(h, "wg_set_turbulence_boxes", box)) return rc;
     const size_t n_cells = (size_t)nx * ny * nz;
-    WG_HIPCHK(hipMalloc(&h->box4, n_cells * 16 * (size_t)n_boxes));
+    if (int rc = h->mem.alloc_bytes("wg_set_turbulence_boxes", &h->box4, n_cells * 16 * (size_t)n_boxes, false)) return rc;
     for (int k = 0; k < n_boxes; ++k)
         wg_launch_box_repack(boxes_dev[k], (char*)h->box4 + (size_t)k * n_cells * 16, nx, ny, nz, nullptr);
     WG_HIPCHK(hipDeviceSynchronize());
@@ -419,7 +413,7 @@ extern "C" int wg_set_turbulence_boxes(wg_handle h, const float* const* boxes_de
     if (h->fp.coarse) {
         const int cx = nx / 4, cy = ny / 4, cz = nz / 4;
         const size_t c_cells = (size_t)cx * cy * cz;
-        WG_HIPCHK(hipMalloc(&h->box4c, c_cells * 16 * (size_t)n_boxes));
+        if (int rc = h->mem.alloc_bytes("wg_set_turbulence_boxes", &h->box4c, c_cells * 16 * (size_t)n_boxes, false)) return rc;
         for (int k = 0; k < n_boxes; ++k)
             wg_launch_box_coarsen((const char*)h->box4 + (size_t)k * n_cells * 16, (char*)h->box4c + (size_t)k * c_cells * 16,
                                   nx, ny, nz, nullptr);
@@ -442,10 +436,10 @@ extern "C" int wg_set_added_turbulence_box(wg_handle h, const float* box_dev, in
     WG_HIPCHK(hipDeviceSynchronize());
     drop_step_graphs(h);
     h->fd.abox4 = nullptr; h->fd.abox8 = nullptr;
-    if (h->abox8) { void* q = h->abox8; h->abox8 = nullptr; WG_HIPCHK(hipFree(q)); }
-    if (h->abox4) { void* q = h->abox4; h->abox4 = nullptr; WG_HIPCHK(hipFree(q)); }
+    for (void** box : {&h->abox8, &h->abox4})
+        if (int rc = drop_box(h, "wg_set_added_turbulence_box", box)) return rc;
     const size_t n_cells = (size_t)nx * ny * nz;
-    WG_HIPCHK(hipMalloc(&h->abox4, n_cells * 16));
+    if (int rc = h->mem.alloc_bytes("wg_set_added_turbulence_box", &h->abox4, n_cells * 16, false)) return rc;
     wg_launch_box_repack(box_dev, h->abox4, nx, ny, nz, nullptr);
     WG_HIPCHK(hipDeviceSynchronize());
     h->fd.abox4 = (const float4*)h->abox4;
@@ -1178,13 +1172,8 @@ extern "C" int wg_get_state(wg_handle h, void* blob_host, size_t* size) {
     if (!h || !size) return wg_fail(WG_ERR_INVALID, "null argument");
     const StateHeader sh = state_header(h);
     const size_t total = sizeof(StateHeader) + sh.payload;
-    if (!blob_host) {
-        *size = total;
-        return 0;
-    }
-    if (*size < total) return wg_fail(WG_ERR_INVALID, "state buffer too small");
-    if (int rc = wg_use_device(h->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
+    if (int rc = wg_blob_get("", h->device, blob_host, size, total)) return rc;
+    if (!blob_host) return 0;
     char* o = (char*)blob_host;
     memcpy(o, &sh, sizeof(sh));
     o += sizeof(sh);
@@ -1198,14 +1187,11 @@ extern "C" int wg_get_state(wg_handle h, void* blob_host, size_t* size) {
 extern "C" int wg_set_state(wg_handle h, const void* blob_host, size_t size) {
     if (!h || !blob_host) return wg_fail(WG_ERR_INVALID, "null argument");
     const StateHeader want = state_header(h);
-    if (size < sizeof(StateHeader)) return wg_fail(WG_ERR_INVALID, "state blob too small");
-    StateHeader got;
-    memcpy(&got, blob_host, sizeof(got));
-    if (got.magic != WG_STATE_MAGIC) return wg_fail(WG_ERR_INVALID, "not a windgym state blob");
-    if (memcmp(&got, &want, sizeof(got)) || size != sizeof(StateHeader) + want.payload)
+    const auto geometry = [&](const StateHeader& got) {
+        if (!memcmp(&got, &want, sizeof(got)) && size == sizeof(StateHeader) + want.payload) return 0;
         return wg_fail(WG_ERR_INVALID, "state blob was taken from a differently configured handle (or another ABI version)");
-    if (int rc = wg_use_device(h->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
+    };
+    if (int rc = wg_blob_set<StateHeader>("", h->device, blob_host, size, WG_STATE_MAGIC, "not a windgym state blob", geometry)) return rc;
     const char* o = (const char*)blob_host + sizeof(StateHeader);
     if (h->d.next_obs_ok) WG_HIPCHK(hipMemset(h->d.next_obs_ok, 0, sizeof(int) * (size_t)h->p.B * 2));      // (derived data, not in the blob)
     for (size_t i : h->state_idx) {

@@ -169,11 +169,31 @@ __global__ __launch_bounds__(64) void k_expert_labels(const CurP p, double* __re
 
 struct wg_curriculum_s {
     WgActuation a;
-    void* mem = nullptr;        // the state: one allocation, CurState points into it
+    WgDevMem mem;               // owns state and err
+    char* state = nullptr;      // the state: one allocation, CurState points into it
     size_t bytes = 0;
     CurState s;
     int* err = nullptr;         // device: {latched, t, b, row} of an ep_row entry >= C
 };
+
+// the kernels' parameter block for T steps on the batch of `a`
+static CurP cur_params(const WgActuation& a, int T, int C, double momentum) {
+    CurP p;
+    p.B = a.B; p.N = a.N; p.T = T; p.C = C; p.action_method = a.action_method;
+    p.yaw_min = a.yaw_min; p.yaw_max = a.yaw_max; p.yaw_step = a.yaw_step;
+    p.yaw_max_d = a.yaw_max_d; p.momentum = momentum;
+    return p;
+}
+
+// the latch of a bad ep_row entry, read on the current, idle device: cleared and reported as `who` when it is set
+static int cur_latch_report(const char* who, int* err_dev) {
+    int err[4];
+    WG_HIPCHK(hipMemcpy(err, err_dev, sizeof(err), hipMemcpyDeviceToHost));
+    if (!err[0]) return 0;
+    WG_HIPCHK(hipMemset(err_dev, 0, sizeof(err)));
+    return wg_fail(WG_ERR_INVALID, std::string(who) + ": ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
+                                    std::to_string(err[3]) + " is not a row of ep_target_dev (C rows); the entry was skipped");
+}
 
 extern "C" int wg_curriculum_create(wg_handle h, wg_curriculum* out) {
     if (!h || !out) return wg_fail(WG_ERR_INVALID, "wg_curriculum_create: null argument");
@@ -182,16 +202,14 @@ extern "C" int wg_curriculum_create(wg_handle h, wg_curriculum* out) {
     if (int rc = wg_handle_actuation_(h, &c->a)) { delete c; return rc; }
     const size_t B = (size_t)c->a.B, BN = B * (size_t)c->a.N;
     c->bytes = 8 * (2 * BN + 4 * B) + 4 * BN;
-    if (int rc = wg_use_device(c->a.device)) { delete c; return rc; }
-    hipError_t e = hipMalloc(&c->mem, c->bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->err, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(c->mem, 0, c->bytes);
-    if (e == hipSuccess) e = hipMemset(c->err, 0, 4 * sizeof(int));
-    if (e != hipSuccess) {
+    c->mem.device = c->a.device;
+    int rc = c->mem.alloc("wg_curriculum_create", &c->state, c->bytes);
+    if (!rc) rc = c->mem.alloc("wg_curriculum_create", &c->err, 4);
+    if (rc) {
         wg_curriculum_destroy(c);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_curriculum_create: ") + hipGetErrorString(e));
+        return rc;
     }
-    char* m = (char*)c->mem;
+    char* m = c->state;
     c->s.yprev = (double*)m; m += 8 * BN;
     c->s.g = (double*)m; m += 8 * BN;
     c->s.cum = (double*)m; m += 8 * B;
@@ -205,13 +223,7 @@ extern "C" int wg_curriculum_create(wg_handle h, wg_curriculum* out) {
 
 extern "C" int wg_curriculum_destroy(wg_curriculum c) {
     if (!c) return 0;
-    if (c->mem || c->err) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != c->a.device) hipSetDevice(c->a.device);
-        hipDeviceSynchronize();
-        if (c->mem) hipFree(c->mem);
-        if (c->err) hipFree(c->err);
-    }
+    c->mem.release();
     delete c;
     return 0;
 }
@@ -225,60 +237,36 @@ static CurHeader cur_header(wg_curriculum c) {
 extern "C" int wg_curriculum_get_state(wg_curriculum c, void* host, size_t* size) {
     if (!c || !size) return wg_fail(WG_ERR_INVALID, "wg_curriculum_get_state: null argument");
     const size_t total = sizeof(CurHeader) + c->bytes;
-    if (!host) {
-        *size = total;
-        return 0;
-    }
-    if (*size < total) return wg_fail(WG_ERR_INVALID, "wg_curriculum_get_state: state buffer too small");
-    if (int rc = wg_use_device(c->a.device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
-    int err[4];
-    WG_HIPCHK(hipMemcpy(err, c->err, sizeof(err), hipMemcpyDeviceToHost));
-    if (err[0]) {
-        WG_HIPCHK(hipMemset(c->err, 0, sizeof(err)));
-        return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
-                                        std::to_string(err[3]) + " is not a row of ep_target_dev (C rows); the entry was skipped");
-    }
+    if (int rc = wg_blob_get("wg_curriculum_get_state: ", c->a.device, host, size, total)) return rc;
+    if (!host) return 0;
+    if (int rc = cur_latch_report("wg_curriculum_shape", c->err)) return rc;
     const CurHeader hd = cur_header(c);
     memcpy(host, &hd, sizeof(hd));
-    WG_HIPCHK(hipMemcpy((char*)host + sizeof(hd), c->mem, c->bytes, hipMemcpyDeviceToHost));
+    WG_HIPCHK(hipMemcpy((char*)host + sizeof(hd), c->state, c->bytes, hipMemcpyDeviceToHost));
     *size = total;
     return 0;
 }
 
 extern "C" int wg_curriculum_set_state(wg_curriculum c, const void* host, size_t size) {
     if (!c || !host) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: null argument");
-    if (size < sizeof(CurHeader)) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: state blob too small");
-    CurHeader got;
-    memcpy(&got, host, sizeof(got));
-    if (got.magic != CUR_MAGIC) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: not a curriculum state blob");
     const CurHeader want = cur_header(c);
-    if (memcmp(&got, &want, sizeof(got)) || size != sizeof(CurHeader) + c->bytes)
+    const auto geometry = [&](const CurHeader& got) {
+        if (!memcmp(&got, &want, sizeof(got)) && size == sizeof(CurHeader) + c->bytes) return 0;
         return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_state: the blob was taken from a curriculum of " + std::to_string(got.B) + " envs x " +
                                         std::to_string(got.N) + " turbines, this one has " + std::to_string(want.B) + " x " + std::to_string(want.N));
-    if (int rc = wg_use_device(c->a.device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
-    WG_HIPCHK(hipMemcpy(c->mem, (const char*)host + sizeof(CurHeader), c->bytes, hipMemcpyHostToDevice));
+    };
+    if (int rc = wg_blob_set<CurHeader>("wg_curriculum_set_state: ", c->a.device, host, size, CUR_MAGIC, "not a curriculum state blob", geometry))
+        return rc;
+    WG_HIPCHK(hipMemcpy(c->state, (const char*)host + sizeof(CurHeader), c->bytes, hipMemcpyHostToDevice));
     return 0;
 }
 
 // a buffer the kernel will touch must be device memory of the curriculum's device (the device of the handle it was created on)
-static int cur_on_device(wg_curriculum c, const void* ptr, const char* name) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return wg_fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not a device pointer");
-    }
-    if (at.type != hipMemoryTypeDevice || at.device != c->a.device)
-        return wg_fail(WG_ERR_INVALID, std::string("wg_curriculum: ") + name + " is not memory of device " + std::to_string(c->a.device) +
-                                        ", the device of the handle the curriculum was created on");
-    return 0;
-}
+static const char* const CUR_WHOSE = ", the device of the handle the curriculum was created on";
 
 extern "C" int wg_curriculum_set_targets(wg_curriculum c, const double* yaw_dev, void* stream) {
     if (!c) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_targets: null curriculum");
-    if (!yaw_dev) return wg_fail(WG_ERR_INVALID, "wg_curriculum_set_targets: yaw_dev is null");
-    if (int rc = cur_on_device(c, yaw_dev, "yaw_dev")) return rc;
+    if (int rc = wg_on_device_all("wg_curriculum_set_targets: ", "wg_curriculum: ", c->a.device, {{yaw_dev, "yaw_dev", true}}, CUR_WHOSE)) return rc;
     if (int rc = wg_use_device(c->a.device)) return rc;
     WG_HIPCHK(hipMemcpyAsync(c->s.g, yaw_dev, sizeof(double) * (size_t)c->a.B * c->a.N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
@@ -293,24 +281,15 @@ extern "C" int wg_curriculum_shape(wg_curriculum c, int T, const float* yaw0_dev
     if (C < 0) return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: C must be >= 0, got " + std::to_string(C));
     if (!(momentum >= 0.0 && momentum < 1.0))
         return wg_fail(WG_ERR_INVALID, "wg_curriculum_shape: momentum must lie in [0, 1), got " + std::to_string(momentum));
-    const struct { const void* ptr; const char* name; bool required; } args[] = {
+    const WgPtrArg args[] = {
         {yaw0_dev, "yaw0_dev", true}, {actions_dev, "actions_dev", true}, {yaw_after_dev, "yaw_after_dev", true},
         {truncated_dev, "truncated_dev", true}, {ep_row_dev, "ep_row_dev", true}, {ep_target_dev, "ep_target_dev", C > 0},
         {weight_dev, "weight_dev", true}, {reward_dev, "reward_dev", true}, {shaped_out, "shaped_out", true},
         {yaw_diff_out, "yaw_diff_out", false}, {yaw_out, "yaw_out", false}};
-    for (const auto& a : args) {
-        if (!a.ptr) {
-            if (a.required) return wg_fail(WG_ERR_INVALID, std::string("wg_curriculum_shape: ") + a.name + " is null");
-            continue;
-        }
-        if (int rc = cur_on_device(c, a.ptr, a.name)) return rc;
-    }
+    if (int rc = wg_on_device_all("wg_curriculum_shape: ", "wg_curriculum: ", c->a.device, args, CUR_WHOSE)) return rc;
     if (T == 0) return 0;
     if (int rc = wg_use_device(c->a.device)) return rc;
-    CurP p;
-    p.B = c->a.B; p.N = c->a.N; p.T = T; p.C = C; p.action_method = c->a.action_method;
-    p.yaw_min = c->a.yaw_min; p.yaw_max = c->a.yaw_max; p.yaw_step = c->a.yaw_step;
-    p.yaw_max_d = c->a.yaw_max_d; p.momentum = momentum;
+    const CurP p = cur_params(c->a, T, C, momentum);
     hipLaunchKernelGGL(k_curriculum, dim3((p.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, p, c->s, c->err, yaw0_dev, actions_dev,
                        yaw_after_dev, truncated_dev, ep_row_dev, ep_target_dev, weight_dev, reward_dev, shaped_out, yaw_diff_out, yaw_out);
     WG_HIPCHK(hipGetLastError());
@@ -321,18 +300,6 @@ extern "C" int wg_curriculum_shape(wg_curriculum c, int T, const float* yaw0_dev
 // expert labels (windgym_hip.h: wg_expert_labels) — no handle of its own: the actuation rule is read from `h`, the running
 // targets and the latch of a bad ep_row entry are the caller's
 // ---------------------------------------------------------------------------------------------------------------------
-static int lab_on_device(int device, const void* ptr, const char* name) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return wg_fail(WG_ERR_INVALID, std::string("wg_expert_labels: ") + name + " is not a device pointer");
-    }
-    if (at.type != hipMemoryTypeDevice || at.device != device)
-        return wg_fail(WG_ERR_INVALID, std::string("wg_expert_labels: ") + name + " is not memory of device " + std::to_string(device) +
-                                        ", the handle's device");
-    return 0;
-}
-
 extern "C" int wg_expert_labels(wg_handle h, int T, const float* yaw0_dev, const float* yaw_after_dev, const uint8_t* truncated_dev,
                                 const int32_t* ep_row_dev, const double* ep_target_dev, int C, double* targets_dev, float* labels_out,
                                 float* yaw_diff_out, int32_t* err_dev, void* stream) {
@@ -341,23 +308,14 @@ extern "C" int wg_expert_labels(wg_handle h, int T, const float* yaw0_dev, const
     if (int rc = wg_handle_actuation_(h, &a)) return rc;
     if (T < 0) return wg_fail(WG_ERR_INVALID, "wg_expert_labels: T must be >= 0, got " + std::to_string(T));
     if (C < 0) return wg_fail(WG_ERR_INVALID, "wg_expert_labels: C must be >= 0, got " + std::to_string(C));
-    const struct { const void* ptr; const char* name; bool required; } args[] = {
+    const WgPtrArg args[] = {
         {yaw0_dev, "yaw0_dev", true}, {yaw_after_dev, "yaw_after_dev", true}, {truncated_dev, "truncated_dev", true},
         {ep_row_dev, "ep_row_dev", true}, {ep_target_dev, "ep_target_dev", C > 0}, {targets_dev, "targets_dev", true},
         {labels_out, "labels_out", true}, {yaw_diff_out, "yaw_diff_out", false}, {err_dev, "err_dev", false}};
-    for (const auto& g : args) {
-        if (!g.ptr) {
-            if (g.required) return wg_fail(WG_ERR_INVALID, std::string("wg_expert_labels: ") + g.name + " is null");
-            continue;
-        }
-        if (int rc = lab_on_device(a.device, g.ptr, g.name)) return rc;
-    }
+    if (int rc = wg_on_device_all("wg_expert_labels: ", "wg_expert_labels: ", a.device, args, ", the handle's device")) return rc;
     if (T == 0) return 0;
     if (int rc = wg_use_device(a.device)) return rc;
-    CurP p;
-    p.B = a.B; p.N = a.N; p.T = T; p.C = C; p.action_method = a.action_method;
-    p.yaw_min = a.yaw_min; p.yaw_max = a.yaw_max; p.yaw_step = a.yaw_step;
-    p.yaw_max_d = a.yaw_max_d; p.momentum = 0.0;
+    const CurP p = cur_params(a, T, C, 0.0);
     hipLaunchKernelGGL(k_expert_labels, dim3((p.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, p, targets_dev, (int*)err_dev, yaw0_dev,
                        yaw_after_dev, truncated_dev, ep_row_dev, ep_target_dev, labels_out, yaw_diff_out);
     WG_HIPCHK(hipGetLastError());
@@ -368,13 +326,8 @@ extern "C" int wg_expert_labels_check(wg_handle h, int32_t* err_dev) {
     WgActuation a;
     if (!h || !err_dev) return wg_fail(WG_ERR_INVALID, "wg_expert_labels_check: null argument");
     if (int rc = wg_handle_actuation_(h, &a)) return rc;
-    if (int rc = lab_on_device(a.device, err_dev, "err_dev")) return rc;
+    if (int rc = wg_on_device("wg_expert_labels: ", a.device, err_dev, "err_dev", ", the handle's device")) return rc;
     if (int rc = wg_use_device(a.device)) return rc;
     WG_HIPCHK(hipDeviceSynchronize());
-    int err[4];
-    WG_HIPCHK(hipMemcpy(err, err_dev, sizeof(err), hipMemcpyDeviceToHost));
-    if (!err[0]) return 0;
-    WG_HIPCHK(hipMemset(err_dev, 0, sizeof(err)));
-    return wg_fail(WG_ERR_INVALID, "wg_expert_labels: ep_row_dev[" + std::to_string(err[1]) + ", " + std::to_string(err[2]) + "] = " +
-                                    std::to_string(err[3]) + " is not a row of ep_target_dev (C rows); the entry was skipped");
+    return cur_latch_report("wg_expert_labels", (int*)err_dev);
 }

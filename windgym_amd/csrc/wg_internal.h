@@ -19,6 +19,7 @@ struct WgPopHeadRows;
 struct WgPacked;
 struct WgAdam;
 struct WgPpoGrad;
+struct WgDevMem;
 struct WgValueRows {           // the critic on n_rows rows: obs [n_rows][critic's input width] -> value [n_rows]
     const float* obs;
     float* value;
@@ -40,11 +41,11 @@ int wg_handle_actuation_(wg_handle h, WgActuation* out);
 int wg_norm_geometry_(wg_norm n, int* n_obs, int* n_envs, int* device);
 // wg_lstm.hip: the shape a wg_lstm was created for and its device (wg_rollout_lstm's checks)
 int wg_lstm_geometry_(wg_lstm l, int* n_in, int* hidden, int* n_nets, int* device);
-// wg_policy.hip: a handle's device copies of its parameters (wg_tile.h: WgPacked) — allocate on `device` (the packed copy zeroed;
-// on failure nothing is left allocated, WG_ERR_NOMEM / WG_ERR_HIP reported as `who`), free after a device synchronisation, and the
-// pointer a set_params' pack kernel reads: `params` itself, or the stage after an asynchronous copy of a host pointer
-int wg_packed_alloc_(WgPacked* w, int device, uint32_t n_flat, uint32_t n_packed, const char* who);
-void wg_packed_free_(WgPacked* w);
+// The three allocators below have one shape: the memory is `mem`'s (wg_host.h: WgDevMem, on mem->device), a failure is reported as
+// `who` and leaves what was allocated to the handle's destroy, which releases `mem`.
+// wg_policy.hip: a handle's device copies of its parameters (wg_tile.h: WgPacked; the packed copy zeroed), and the pointer a
+// set_params' pack kernel reads: `params` itself, or the stage after an asynchronous copy of a host pointer
+int wg_packed_alloc_(WgDevMem* mem, WgPacked* w, uint32_t n_flat, uint32_t n_packed, const char* who);
 int wg_packed_source_(WgPacked* w, const float* params, int on_device, hipStream_t st, const float** src);
 // wg_policy.hip: ONE launch of k_policy — the actor on n_rows rows of obs_dev (when action / raw / logp is wanted) and the critic on
 // each of n_v <= 2 row sets of its own (rows of the critic's input width -> value); a set of no rows is skipped
@@ -58,21 +59,18 @@ int wg_pop_prepare_(wg_pop q, const char* who, int n_rows, const uint64_t* seeds
                     const float* final_obs, const WgPopOuts* o, void* stream);
 int wg_pop_slots_(wg_pop q, int Bm, const WgPopKind* kinds, const WgPopOuts* o, const uint64_t* seeds, const uint64_t* row_offsets, void* stream);
 int wg_pop_launch_(wg_pop q, int head, int fin, int t, int deterministic, uint64_t counter, void* stream);
-// wg_ppo.hip: Adam over one flat vector (wg_train.h: WgAdam).  alloc: moments zeroed, step 0; free (and wg_ppo_grad_free_): on the
-// current, synchronised device — a failed alloc / init leaves the freeing to the caller; get / set_state: the public *_get_state /
-// *_set_state entries, reported as `who`, a null `a` included; apply: counts one step, then clipping by the global norm of grad_dev
-// [n_flat] and that step of Adam on params_dev in place (k_ppo_sumsq + k_ppo_adam)
-hipError_t wg_adam_alloc_(WgAdam* a, int device, uint32_t n_flat);
-void wg_adam_free_(WgAdam* a);
+// wg_ppo.hip: Adam over one flat vector (wg_train.h: WgAdam).  alloc: moments zeroed, step 0; get / set_state: the public
+// *_get_state / *_set_state entries, reported as `who`, a null `a` included; apply: counts one step, then clipping by the global norm
+// of grad_dev [n_flat] and that step of Adam on params_dev in place (k_ppo_sumsq + k_ppo_adam)
+int wg_adam_alloc_(WgDevMem* mem, WgAdam* a, uint32_t n_flat, const char* who);
 int wg_adam_get_state_(WgAdam* a, const char* who, float* mv_host, size_t n, uint64_t* step);
 int wg_adam_set_state_(WgAdam* a, const char* who, const float* mv_host, size_t n, uint64_t step);
 int wg_adam_apply_(WgAdam* a, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st);
-// wg_ppo.hip: the gradient kernel's side of policy p (wg_ppo.h: WgPpoGrad) — the first half of wg_ppo_create, reported under that
-// name.  heads_grad, the heads of a recurrent policy (wg_lstm_ppo.hip): k_ppo_grad's loss on n rows whose actor reads h_pi [n][H] and
+// wg_ppo.hip: the gradient kernel's side of policy p (wg_ppo.h: WgPpoGrad) — the first half of wg_ppo_create; what it refuses about
+// the policy is reported under that name.  heads_grad, the heads of a recurrent policy (wg_lstm_ppo.hip): k_ppo_grad's loss on n rows whose actor reads h_pi [n][H] and
 // whose critic reads h_vf [n][H], raw / logp / adv / ret indexed by the same row -> the MLP's flat gradient, the stats record and the
 // gradients of the rows, dh_pi / dh_vf [n][H] (k_ppo_grad_dh)
-int wg_ppo_grad_init_(WgPpoGrad* g, wg_policy p);
-void wg_ppo_grad_free_(WgPpoGrad* g);
+int wg_ppo_grad_init_(WgDevMem* mem, WgPpoGrad* g, wg_policy p, const char* who);
 int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw, const float* logp,
                        const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi, float* dh_vf, float* grad_out,
                        float* stats_out, void* stream);

@@ -74,6 +74,7 @@ __device__ __forceinline__ float wgl_sigmoid(const float z) { return 1.0f / (1.0
 struct wg_lstm_s {
     WgLstmP P;
     WgPacked w;                // [P.n_flat] / [P.n_packed]
+    WgDevMem mem;              // owns them
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -96,6 +97,7 @@ struct wg_lstm_pop_s {
     void* seq_dev;                        // [WGP_POP_MAX] WgLstmPopMember: the sequence kernels' member table of the running update
     void* upd_dev;                        // [2][WGP_POP_MAX] WgPopMember of that update: the heads' view (MLP part), Adam's (whole vector)
     void* rows_dev;                       // [WGP_POP_MAX] WgPopHeadRows
+    WgDevMem mem;                         // owns the four tables
 };
 
 #endif

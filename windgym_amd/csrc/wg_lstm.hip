@@ -162,8 +162,9 @@ extern "C" int wg_lstm_create(const wg_lstm_desc* d, int device, wg_lstm* out) {
     wg_lstm_s* l = new (std::nothrow) wg_lstm_s();
     if (!l) return wg_fail(WG_ERR_NOMEM, "wg_lstm_create: out of host memory");
     wgl_fill_layout(l->P, d);
-    if (int rc = wg_packed_alloc_(&l->w, device, l->P.n_flat, l->P.n_packed, "wg_lstm_create")) {
-        delete l;
+    l->mem.device = device;
+    if (int rc = wg_packed_alloc_(&l->mem, &l->w, l->P.n_flat, l->P.n_packed, "wg_lstm_create")) {
+        wg_lstm_destroy(l);
         return rc;
     }
     *out = l;
@@ -172,7 +173,7 @@ extern "C" int wg_lstm_create(const wg_lstm_desc* d, int device, wg_lstm* out) {
 
 extern "C" int wg_lstm_destroy(wg_lstm l) {
     if (!l) return 0;
-    wg_packed_free_(&l->w);
+    l->mem.release();
     delete l;
     return 0;
 }

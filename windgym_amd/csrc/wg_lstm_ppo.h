@@ -77,6 +77,7 @@ struct wg_lstm_ppo_s {
     float* wpart;              // [WGLP_SPLIT][n_lstm] the weight gradient's partial sums
     uint32_t whhT_net, whhT_all;
     int32_t nksT;
+    WgDevMem mem;              // owns every device buffer above, the scratch of heads and the moments of adam included
 };
 
 // THE STASH of a handle as the kernels are handed it — the one place that knows the layout above.  q: gates / c / h with their net

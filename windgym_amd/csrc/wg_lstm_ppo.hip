@@ -479,9 +479,10 @@ extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max,
     wg_lstm_ppo_s* o = new (std::nothrow) wg_lstm_ppo_s();
     if (!o) return wg_fail(WG_ERR_NOMEM, "wg_lstm_ppo_create: out of host memory");
     o->lstm = l; o->pol = p;
-    o->adam.device = l->w.device; o->T_max = T_max; o->Bm_max = Bm_max; o->NT_max = (int)NT;
+    o->mem.device = o->adam.device = l->w.device; o->T_max = T_max; o->Bm_max = Bm_max; o->NT_max = (int)NT;
     o->n_lstm = L.n_flat;
-    if (int rc = wg_ppo_grad_init_(&o->heads, p)) {
+    const char* const who = "wg_lstm_ppo_create";
+    if (int rc = wg_ppo_grad_init_(&o->mem, &o->heads, p, who)) {
         wg_lstm_ppo_destroy(o);
         return rc;
     }
@@ -489,19 +490,15 @@ extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max,
     o->whhT_net = wg_tile_wsize(L.nub, o->nksT);
     o->whhT_all = o->whhT_net * L.n_nets + WGP_SLACK;
     const uint32_t n_flat = L.n_flat + p->P.n_flat;
-    hipError_t e = wg_adam_alloc_(&o->adam, l->w.device, n_flat);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->grad, sizeof(float) * (size_t)n_flat);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->stats, sizeof(float) * WGT_NSTAT);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->gates, sizeof(float) * f_gates);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->c, sizeof(float) * f_c);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->h, sizeof(float) * f_h);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->dh, sizeof(float) * f_dh);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->rows, sizeof(float) * f_rows);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->whhT, sizeof(float) * o->whhT_all);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->wpart, sizeof(float) * (size_t)WGLP_SPLIT * o->n_lstm);
-    if (e != hipSuccess) {
+    int rc = wg_adam_alloc_(&o->mem, &o->adam, n_flat, who);
+    const struct { float** out; size_t n; } bufs[] = {{&o->grad, n_flat}, {&o->stats, WGT_NSTAT}, {&o->gates, f_gates}, {&o->c, f_c}, {&o->h, f_h},
+                                                      {&o->dh, f_dh}, {&o->rows, f_rows}, {&o->whhT, o->whhT_all},
+                                                      {&o->wpart, (size_t)WGLP_SPLIT * o->n_lstm}};
+    for (const auto& b : bufs)
+        if (!rc) rc = o->mem.alloc(who, b.out, b.n, false);
+    if (rc) {
         wg_lstm_ppo_destroy(o);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_lstm_ppo_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = o;
     return 0;
@@ -509,14 +506,7 @@ extern "C" int wg_lstm_ppo_create(wg_lstm l, wg_policy p, int T_max, int Bm_max,
 
 extern "C" int wg_lstm_ppo_destroy(wg_lstm_ppo o) {
     if (!o) return 0;
-    if (hipSetDevice(o->adam.device) == hipSuccess) {
-        (void)hipDeviceSynchronize();
-        wg_ppo_grad_free_(&o->heads);
-        wg_adam_free_(&o->adam);
-        float* bufs[] = {o->grad, o->stats, o->gates, o->c, o->h, o->dh, o->rows, o->whhT, o->wpart};
-        for (float* b : bufs)
-            if (b) (void)hipFree(b);
-    }
+    o->mem.release();
     delete o;
     return 0;
 }
@@ -731,14 +721,15 @@ extern "C" int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, 
     q->P = q->heads.P = P;
     q->device = q->heads.device = lstms[0]->w.device;
     for (int m = 0; m < P; ++m) { q->lstm[m] = lstms[m]; q->heads.pol[m] = heads[m]; q->opt[m] = opts ? opts[m] : nullptr; }
-    hipError_t e = hipSetDevice(q->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&q->heads.slots_dev, sizeof(WgPopSlot) * WGP_POP_SLOTS);
-    if (e == hipSuccess) e = hipMalloc(&q->seq_dev, sizeof(WgLstmPopMember) * WGP_POP_MAX);
-    if (e == hipSuccess) e = hipMalloc(&q->upd_dev, sizeof(WgPopMember) * 2 * WGP_POP_MAX);
-    if (e == hipSuccess) e = hipMalloc(&q->rows_dev, sizeof(WgPopHeadRows) * WGP_POP_MAX);
-    if (e != hipSuccess) {
+    q->mem.device = q->device;
+    const char* const who = "wg_lstm_pop_create";
+    int rc = q->mem.alloc(who, &q->heads.slots_dev, WGP_POP_SLOTS, false);
+    if (!rc) rc = q->mem.alloc_bytes(who, &q->seq_dev, sizeof(WgLstmPopMember) * WGP_POP_MAX, false);
+    if (!rc) rc = q->mem.alloc_bytes(who, &q->upd_dev, sizeof(WgPopMember) * 2 * WGP_POP_MAX, false);
+    if (!rc) rc = q->mem.alloc_bytes(who, &q->rows_dev, sizeof(WgPopHeadRows) * WGP_POP_MAX, false);
+    if (rc) {
         wg_lstm_pop_destroy(q);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_lstm_pop_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = q;
     return 0;
@@ -746,11 +737,7 @@ extern "C" int wg_lstm_pop_create(const wg_lstm* lstms, const wg_policy* heads, 
 
 extern "C" int wg_lstm_pop_destroy(wg_lstm_pop q) {
     if (!q) return 0;
-    if (hipSetDevice(q->device) == hipSuccess) {
-        (void)hipDeviceSynchronize();
-        for (void* b : {(void*)q->heads.slots_dev, q->seq_dev, q->upd_dev, q->rows_dev})
-            if (b) (void)hipFree(b);
-    }
+    q->mem.release();
     delete q;
     return 0;
 }

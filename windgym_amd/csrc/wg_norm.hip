@@ -271,7 +271,7 @@ struct wg_norm_s {
     wg_norm_desc d;
     int device = 0, training = 1;
     int cur = 0;                 // which half of stat the next call reads (flips when a call updates: calls go to one stream at a time)
-    double* mem = nullptr;       // one allocation: stat[2][2 O + 1], ret[3] (mean, var, count), returns[B], pmean[C][O], pm2[C][O]
+    WgDevMem mem;                // owns all: one allocation for stat[2][2 O + 1], ret[3] (mean, var, count), returns[B], pmean[C][O], pm2[C][O]
     double *stat[2] = {nullptr, nullptr}, *ret = nullptr, *returns = nullptr, *pmean = nullptr, *pm2 = nullptr;
     uint8_t* mask = nullptr;     // [B] wg_norm_reset_returns' mask on the device
     double* scr = nullptr;       // the reward pass: returns [T, B], then mom [T][2], then var_t [T]; grown by wg_norm_reward
@@ -310,18 +310,16 @@ extern "C" int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out) {
     if (!n) return wg_fail(WG_ERR_NOMEM, "wg_norm_create: out of host memory");
     n->d = *d;
     n->d.norm_obs = d->norm_obs != 0; n->d.norm_reward = d->norm_reward != 0;
-    n->device = device;
+    n->mem.device = n->device = device;
     const size_t O = d->n_obs, B = d->n_envs, C = (B + WGN_ROWS - 1) / WGN_ROWS;
     const size_t words = 2 * (2 * O + 1) + 3 + B + 2 * C * O;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void**)&n->mem, sizeof(double) * words);
-    if (e == hipSuccess) e = hipMalloc((void**)&n->mask, B);
-    if (e == hipSuccess) e = hipMemset(n->mem, 0, sizeof(double) * words);
-    if (e != hipSuccess) {
+    double* m = nullptr;
+    int rc = n->mem.alloc("wg_norm_create", &m, words);
+    if (!rc) rc = n->mem.alloc("wg_norm_create", &n->mask, B, false);
+    if (rc) {
         wg_norm_destroy(n);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_norm_create: ") + hipGetErrorString(e));
+        return rc;
     }
-    double* m = n->mem;
     n->stat[0] = m; m += 2 * O + 1;
     n->stat[1] = m; m += 2 * O + 1;
     n->ret = m; m += 3;
@@ -331,7 +329,7 @@ extern "C" int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out) {
     double* s = new (std::nothrow) double[norm_state_doubles(n)];
     if (!s) { wg_norm_destroy(n); return wg_fail(WG_ERR_NOMEM, "wg_norm_create: out of host memory"); }
     norm_fresh(n, s);
-    const int rc = norm_upload(n, s);
+    rc = norm_upload(n, s);
     delete[] s;
     if (rc) { wg_norm_destroy(n); return rc; }
     *out = n;
@@ -340,14 +338,7 @@ extern "C" int wg_norm_create(const wg_norm_desc* d, int device, wg_norm* out) {
 
 extern "C" int wg_norm_destroy(wg_norm n) {
     if (!n) return 0;
-    if (n->mem || n->mask || n->scr) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != n->device) (void)hipSetDevice(n->device);
-        (void)hipDeviceSynchronize();
-        if (n->mem) (void)hipFree(n->mem);
-        if (n->mask) (void)hipFree(n->mask);
-        if (n->scr) (void)hipFree(n->scr);
-    }
+    n->mem.release();
     delete n;
     return 0;
 }
@@ -362,13 +353,8 @@ extern "C" int wg_norm_get_state(wg_norm n, void* host, size_t* size) {
     if (!n || !size) return wg_fail(WG_ERR_INVALID, "wg_norm_get_state: null argument");
     const size_t O = n->d.n_obs, B = n->d.n_envs;
     const size_t total = sizeof(NormHeader) + sizeof(double) * norm_state_doubles(n);
-    if (!host) {
-        *size = total;
-        return 0;
-    }
-    if (*size < total) return wg_fail(WG_ERR_INVALID, "wg_norm_get_state: state buffer too small");
-    if (int rc = wg_use_device(n->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
+    if (int rc = wg_blob_get("wg_norm_get_state: ", n->device, host, size, total)) return rc;
+    if (!host) return 0;
     const NormHeader hd = {NORM_MAGIC, n->d.n_obs, n->d.n_envs, 0};
     memcpy(host, &hd, sizeof(hd));
     char* at = (char*)host + sizeof(hd);
@@ -380,16 +366,13 @@ extern "C" int wg_norm_get_state(wg_norm n, void* host, size_t* size) {
 
 extern "C" int wg_norm_set_state(wg_norm n, const void* host, size_t size) {
     if (!n || !host) return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: null argument");
-    if (size < sizeof(NormHeader)) return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: state blob too small");
-    NormHeader got;
-    memcpy(&got, host, sizeof(got));
-    if (got.magic != NORM_MAGIC) return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: not a wg_norm state blob");
-    if (got.O != n->d.n_obs || got.B != n->d.n_envs || size != sizeof(NormHeader) + sizeof(double) * norm_state_doubles(n))
+    const auto geometry = [&](const NormHeader& got) {
+        if (got.O == n->d.n_obs && got.B == n->d.n_envs && size == sizeof(NormHeader) + sizeof(double) * norm_state_doubles(n)) return 0;
         return wg_fail(WG_ERR_INVALID, "wg_norm_set_state: the blob holds statistics of " + std::to_string(got.O) + " observation entries x " +
                                         std::to_string(got.B) + " envs, this wg_norm has " + std::to_string(n->d.n_obs) + " x " +
                                         std::to_string(n->d.n_envs));
-    if (int rc = wg_use_device(n->device)) return rc;
-    WG_HIPCHK(hipDeviceSynchronize());
+    };
+    if (int rc = wg_blob_set<NormHeader>("wg_norm_set_state: ", n->device, host, size, NORM_MAGIC, "not a wg_norm state blob", geometry)) return rc;
     // (the payload is copied out first: a blob inside a Python bytes object need not be aligned for doubles)
     const size_t nd = norm_state_doubles(n);
     double* s = new (std::nothrow) double[nd];
@@ -459,10 +442,10 @@ extern "C" int wg_norm_reward(wg_norm n, int T, const float* reward_dev, const u
     hipStream_t st = (hipStream_t)stream;
     const int B = n->d.n_envs;
     if (n->training && T > n->scr_T) {          // grown here, before anything is enqueued (hipFree waits for what still reads the old one)
-        if (n->scr) WG_HIPCHK(hipFree(n->scr));
+        double* const old = n->scr;
         n->scr = nullptr; n->scr_T = 0;
-        const hipError_t e = hipMalloc((void**)&n->scr, sizeof(double) * ((size_t)T * B + 3 * (size_t)T));
-        if (e != hipSuccess) return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_norm_reward: ") + hipGetErrorString(e));
+        if (int rc = n->mem.free("wg_norm_reward", old)) return rc;
+        if (int rc = n->mem.alloc("wg_norm_reward", &n->scr, (size_t)T * B + 3 * (size_t)T, false)) return rc;
         n->scr_T = T;
     }
     double* const mom = n->scr ? n->scr + (size_t)n->scr_T * B : nullptr;

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/windgym_hip.h"
+#include "wg_devmem.h"
 #include "wg_tile.h"         // the tile constants WGP_TILE, WGP_KC, WGP_WAVES, WGP_GROUP and the packed layout
 
 #define WGP_MAX_LAYERS 5     // WG_POLICY_MAX_HIDDEN + the head
@@ -89,6 +90,7 @@ inline void wgp_fill_layout(WgPolicyP& P, const wg_policy_desc* d, int32_t n_in_
 struct wg_policy_s {
     WgPolicyP P;
     WgPacked w;                // [P.n_flat] / [P.n_packed]
+    WgDevMem mem;              // owns them
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -139,6 +141,7 @@ struct wg_pop_s {
     // the slot table's current shape: kinds in the order actor, critic, critic on the final rows; P slots of Bm rows per kind
     int n_head, has_final, Bm;     // n_head = kinds of a step's own rows (actor and / or critic)
     void* upd_dev;                 // [WGP_POP_MAX] WgPopMember: the member table of the running wg_pop_update
+    WgDevMem mem;                  // owns the two tables (a recurrent population's `heads`: empty, wg_lstm_pop_s::mem owns them)
 };
 
 // The slot table, stated once for the plain population (rows = observations) and the recurrent one (rows = the LSTMs' h rows).

@@ -196,24 +196,11 @@ __global__ void k_policy_pack_pop(const WgPolicyP P, const WgPopMember* __restri
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// A handle's device copies (wg_tile.h: WgPacked): the zeroed packed vector and the staging copy, on `device`
-extern "C" int wg_packed_alloc_(WgPacked* w, int device, uint32_t n_flat, uint32_t n_packed, const char* who) {
-    *w = WgPacked{device, nullptr, nullptr, n_flat, n_packed};
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void**)&w->packed, sizeof(float) * n_packed);
-    if (e == hipSuccess) e = hipMalloc((void**)&w->flat_stage, sizeof(float) * n_flat);
-    if (e == hipSuccess) e = hipMemset(w->packed, 0, sizeof(float) * n_packed);
-    if (e == hipSuccess) return 0;
-    if (w->packed) (void)hipFree(w->packed);
-    if (w->flat_stage) (void)hipFree(w->flat_stage);
-    return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-}
-
-extern "C" void wg_packed_free_(WgPacked* w) {
-    if (hipSetDevice(w->device) != hipSuccess) return;
-    (void)hipDeviceSynchronize();
-    (void)hipFree(w->packed);
-    (void)hipFree(w->flat_stage);
+// A handle's device copies (wg_tile.h: WgPacked): the zeroed packed vector and the staging copy, on mem's device
+extern "C" int wg_packed_alloc_(WgDevMem* mem, WgPacked* w, uint32_t n_flat, uint32_t n_packed, const char* who) {
+    *w = WgPacked{mem->device, nullptr, nullptr, n_flat, n_packed};
+    if (int rc = mem->alloc(who, &w->packed, n_packed)) return rc;
+    return mem->alloc(who, &w->flat_stage, n_flat, false);
 }
 
 // what the pack kernel of a set_params reads: a device pointer itself, a host pointer's copy in the stage (in stream order)
@@ -252,8 +239,9 @@ extern "C" int wg_policy_create_vf(const wg_policy_desc* d, int32_t n_in_vf, int
     wg_policy_s* p = new (std::nothrow) wg_policy_s();
     if (!p) return wg_fail(WG_ERR_NOMEM, "wg_policy_create: out of host memory");
     wgp_fill_layout(p->P, d, n_in_vf);
-    if (int rc = wg_packed_alloc_(&p->w, device, p->P.n_flat, p->P.n_packed, "wg_policy_create")) {
-        delete p;
+    p->mem.device = device;
+    if (int rc = wg_packed_alloc_(&p->mem, &p->w, p->P.n_flat, p->P.n_packed, "wg_policy_create")) {
+        wg_policy_destroy(p);
         return rc;
     }
     *out = p;
@@ -267,7 +255,7 @@ extern "C" int wg_policy_create(const wg_policy_desc* d, int device, wg_policy* 
 
 extern "C" int wg_policy_destroy(wg_policy p) {
     if (!p) return 0;
-    wg_packed_free_(&p->w);
+    p->mem.release();
     delete p;
     return 0;
 }

@@ -45,7 +45,7 @@ struct WgPpoK {                           // by-value kernel argument next to Wg
 };
 
 // the gradient kernel's side of a policy: its LDS map, its grid limit and its scratch — all k_ppo_grad* needs on the host.  The
-// recurrent trainer holds one by value for its heads (wg_lstm_ppo.h); wg_ppo_grad_init_ / wg_ppo_grad_free_ of wg_internal.h
+// recurrent trainer holds one by value for its heads (wg_lstm_ppo.h); wg_ppo_grad_init_ of wg_internal.h
 struct WgPpoGrad {
     wg_policy_s* pol;
     WgPpoK K;
@@ -71,6 +71,7 @@ struct wg_ppo_s {
     WgPpoGrad g;
     WgAdam adam;                          // over the policy's flat vector, on the policy's device
     float* grad;                          // [n_flat] gradient of wg_ppo_update's running minibatch
+    WgDevMem mem;                         // owns the scratch of g, the moments of adam and grad
 };
 
 #endif

@@ -636,18 +636,6 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam_pop(const WgPopMember* _
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// a device pointer of another GPU (or a host pointer) -> WG_ERR_INVALID
-static int t_on_device(const void* p, int device, const char* what) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return wg_fail(WG_ERR_INVALID, std::string(what) + " is not a device pointer");
-    }
-    if (at.type != hipMemoryTypeDevice || at.device != device)
-        return wg_fail(WG_ERR_INVALID, std::string(what) + " is not memory of device " + std::to_string(device));
-    return 0;
-}
-
 // The argument checks of every wg_gae* entry.  `who`, `dims` and `rows` name the caller, its sizes and its B * A rows in the
 // messages; `all_there`: no pointer argument is null; P: the members the B envs divide among (1: one policy, always passes).
 static int gae_check(const char* who, const char* dims, const char* rows, bool all_there, int T, int B, int A, int P) {
@@ -716,21 +704,11 @@ static size_t t_lds_map(const WgPolicyP& P, int R, WgPpoK* K) {
 }
 
 // WgAdam (wg_train.h) and WgPpoGrad (wg_ppo.h): wg_internal.h states what each function does
-extern "C" hipError_t wg_adam_alloc_(WgAdam* a, int device, uint32_t n_flat) {
-    *a = {device, n_flat, (n_flat + WGT_BLOCK - 1) / WGT_BLOCK, 0, nullptr, nullptr, nullptr};
-    const size_t nf = sizeof(float) * (size_t)n_flat;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void**)&a->m, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&a->v, nf);
-    if (e == hipSuccess) e = hipMalloc((void**)&a->blocksq, sizeof(float) * a->n_blocks);
-    if (e == hipSuccess) e = hipMemset(a->m, 0, nf);
-    if (e == hipSuccess) e = hipMemset(a->v, 0, nf);
-    return e;
-}
-
-extern "C" void wg_adam_free_(WgAdam* a) {
-    for (float* b : {a->m, a->v, a->blocksq})
-        if (b) (void)hipFree(b);
+extern "C" int wg_adam_alloc_(WgDevMem* mem, WgAdam* a, uint32_t n_flat, const char* who) {
+    *a = {mem->device, n_flat, (n_flat + WGT_BLOCK - 1) / WGT_BLOCK, 0, nullptr, nullptr, nullptr};
+    if (int rc = mem->alloc(who, &a->m, n_flat)) return rc;
+    if (int rc = mem->alloc(who, &a->v, n_flat)) return rc;
+    return mem->alloc(who, &a->blocksq, a->n_blocks, false);
 }
 
 // what get_state / set_state check before they copy: the arguments, the size, the device idle
@@ -767,7 +745,7 @@ extern "C" int wg_adam_apply_(WgAdam* a, float* params_dev, const float* grad_de
     return 0;
 }
 
-extern "C" int wg_ppo_grad_init_(WgPpoGrad* g, wg_policy p) {
+extern "C" int wg_ppo_grad_init_(WgDevMem* mem, WgPpoGrad* g, wg_policy p, const char* who) {
     const WgPolicyP& P = p->P;
     if (P.n_layers[1] == 0) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with a critic");
     if (!P.has_log_std) return wg_fail(WG_ERR_INVALID, "wg_ppo_create: training needs a policy with log_std");
@@ -779,21 +757,10 @@ extern "C" int wg_ppo_grad_init_(WgPpoGrad* g, wg_policy p) {
         return wg_fail(WG_ERR_UNSUPPORTED, "wg_ppo_create: the architecture's activations do not fit the workgroup's LDS");
     size_t gm = WGT_PART_BYTES / (sizeof(float) * (size_t)P.n_flat);
     g->g_max = (int)(gm < 1 ? 1 : gm > WGT_G_MAX ? WGT_G_MAX : gm);
-    hipError_t e = hipSetDevice(p->w.device);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->part, sizeof(float) * (size_t)P.n_flat * g->g_max);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->spart, sizeof(float) * 4 * g->g_max);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->advstat, sizeof(float) * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->stats, sizeof(float) * WGT_NSTAT);
-    if (e == hipSuccess) e = hipMemset(g->spart, 0, sizeof(float) * 4 * g->g_max);
-    if (e == hipSuccess) e = hipMemset(g->advstat, 0, sizeof(float) * 2);
-    if (e != hipSuccess)
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" void wg_ppo_grad_free_(WgPpoGrad* g) {
-    for (float* b : {g->part, g->spart, g->advstat, g->stats})
-        if (b) (void)hipFree(b);
+    if (int rc = mem->alloc(who, &g->part, (size_t)P.n_flat * g->g_max, false)) return rc;
+    if (int rc = mem->alloc(who, &g->spart, (size_t)4 * g->g_max)) return rc;
+    if (int rc = mem->alloc(who, &g->advstat, 2)) return rc;
+    return mem->alloc(who, &g->stats, WGT_NSTAT, false);
 }
 
 extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
@@ -801,14 +768,10 @@ extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
     *out = nullptr;
     wg_ppo_s* o = new (std::nothrow) wg_ppo_s();
     if (!o) return wg_fail(WG_ERR_NOMEM, "wg_ppo_create: out of host memory");
-    o->adam.device = p->w.device;
-    int rc = wg_ppo_grad_init_(&o->g, p);
-    if (!rc) {
-        hipError_t e = wg_adam_alloc_(&o->adam, p->w.device, p->P.n_flat);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->grad, sizeof(float) * (size_t)p->P.n_flat);
-        if (e != hipSuccess)
-            rc = wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_ppo_create: ") + hipGetErrorString(e));
-    }
+    o->mem.device = o->adam.device = p->w.device;
+    int rc = wg_ppo_grad_init_(&o->mem, &o->g, p, "wg_ppo_create");
+    if (!rc) rc = wg_adam_alloc_(&o->mem, &o->adam, p->P.n_flat, "wg_ppo_create");
+    if (!rc) rc = o->mem.alloc("wg_ppo_create", &o->grad, p->P.n_flat, false);
     if (rc) {
         wg_ppo_destroy(o);
         return rc;
@@ -819,12 +782,7 @@ extern "C" int wg_ppo_create(wg_policy p, wg_ppo* out) {
 
 extern "C" int wg_ppo_destroy(wg_ppo o) {
     if (!o) return 0;
-    if (hipSetDevice(o->adam.device) == hipSuccess) {
-        (void)hipDeviceSynchronize();
-        wg_ppo_grad_free_(&o->g);
-        wg_adam_free_(&o->adam);
-        if (o->grad) (void)hipFree(o->grad);
-    }
+    o->mem.release();
     delete o;
     return 0;
 }
@@ -930,9 +888,8 @@ extern "C" int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, WgAdam* 
 // the handle's device becomes the current one; the parameters and the batch's observation streams must live on it
 static int t_use_device(const std::string& w, wg_ppo o, const float* params_dev, const wg_ppo_batch_shared* b) {
     if (int rc = wg_use_device(o->adam.device)) return rc;
-    if (int rc = t_on_device(params_dev, o->adam.device, (w + ": params_dev").c_str())) return rc;
-    if (int rc = t_on_device(b->rows.obs, o->adam.device, (w + ": obs").c_str())) return rc;
-    if (b->obs_vf != b->rows.obs) return t_on_device(b->obs_vf, o->adam.device, (w + ": obs_vf").c_str());
+    if (int rc = wg_on_device_all(w + ": ", w + ": ", o->adam.device, {{params_dev, "params_dev", true}, {b->rows.obs, "obs", true}}, "")) return rc;
+    if (b->obs_vf != b->rows.obs) return wg_on_device(w + ": ", o->adam.device, b->obs_vf, "obs_vf", "");
     return 0;
 }
 
@@ -974,8 +931,8 @@ extern "C" int wg_ppo_apply(wg_ppo o, float* params_dev, const float* grad_dev, 
     if (!o || !params_dev || !grad_dev) return wg_fail(WG_ERR_INVALID, "wg_ppo_apply: null argument");
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_ppo_apply: max_grad_norm must be > 0");
     if (int rc = wg_use_device(o->adam.device)) return rc;
-    if (int rc = t_on_device(params_dev, o->adam.device, "wg_ppo_apply: params_dev")) return rc;
-    if (int rc = t_on_device(grad_dev, o->adam.device, "wg_ppo_apply: grad_dev")) return rc;
+    if (int rc = wg_on_device_all("wg_ppo_apply: ", "wg_ppo_apply: ", o->adam.device, {{params_dev, "params_dev", true}, {grad_dev, "grad_dev", true}}, ""))
+        return rc;
     return t_apply(o, params_dev, grad_dev, lr, max_grad_norm, (hipStream_t)stream);
 }
 
@@ -987,7 +944,7 @@ static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_p
     if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
     if (int rc = t_use_device(w, o, params_dev, b)) return rc;
-    if (int rc = t_on_device(perm_dev, o->adam.device, (w + ": perm_dev").c_str())) return rc;
+    if (int rc = wg_on_device(w + ": ", o->adam.device, perm_dev, "perm_dev", "")) return rc;
     return wg_each_minibatch(b->rows.n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
         if (int rc = t_grad(&o->g, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
@@ -1024,9 +981,7 @@ static int bc_check(const std::string& w, wg_ppo o, const float* params_dev, con
     if (hp->loss != WG_BC_MSE && hp->loss != WG_BC_NLL)
         return wg_fail(WG_ERR_INVALID, w + ": loss must be WG_BC_MSE or WG_BC_NLL, got " + std::to_string(hp->loss));
     if (int rc = wg_use_device(o->adam.device)) return rc;
-    if (int rc = t_on_device(params_dev, o->adam.device, (w + ": params_dev").c_str())) return rc;
-    if (int rc = t_on_device(b->obs, o->adam.device, (w + ": obs").c_str())) return rc;
-    return t_on_device(b->target, o->adam.device, (w + ": target").c_str());
+    return wg_on_device_all(w + ": ", w + ": ", o->adam.device, {{params_dev, "params_dev", true}, {b->obs, "obs", true}, {b->target, "target", true}}, "");
 }
 
 // the launches of one supervised gradient, no argument checks
@@ -1068,7 +1023,7 @@ extern "C" int wg_bc_update(wg_ppo o, float* params_dev, const wg_bc_batch* b, c
     if (int rc = bc_check(w, o, params_dev, b, hp)) return rc;
     if (n_epochs < 1 || batch_size < 1) return wg_fail(WG_ERR_INVALID, w + ": n_epochs and batch_size must be >= 1");
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
-    if (int rc = t_on_device(perm_dev, o->adam.device, (w + ": perm_dev").c_str())) return rc;
+    if (int rc = wg_on_device(w + ": ", o->adam.device, perm_dev, "perm_dev", "")) return rc;
     return wg_each_minibatch(b->n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
         if (int rc = t_bc_grad(&o->g, params_dev, b, b->obs, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
@@ -1112,12 +1067,12 @@ extern "C" int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P
     q->P = P;
     q->device = members[0]->w.device;
     for (int m = 0; m < P; ++m) { q->pol[m] = members[m]; q->opt[m] = opts ? opts[m] : nullptr; }
-    hipError_t e = hipSetDevice(q->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&q->slots_dev, sizeof(WgPopSlot) * WGP_POP_SLOTS);
-    if (e == hipSuccess) e = hipMalloc(&q->upd_dev, sizeof(WgPopMember) * WGP_POP_MAX);
-    if (e != hipSuccess) {
+    q->mem.device = q->device;
+    int rc = q->mem.alloc("wg_pop_create", &q->slots_dev, WGP_POP_SLOTS, false);
+    if (!rc) rc = q->mem.alloc_bytes("wg_pop_create", &q->upd_dev, sizeof(WgPopMember) * WGP_POP_MAX, false);
+    if (rc) {
         wg_pop_destroy(q);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_pop_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = q;
     return 0;
@@ -1125,11 +1080,7 @@ extern "C" int wg_pop_create(const wg_policy* members, const wg_ppo* opts, int P
 
 extern "C" int wg_pop_destroy(wg_pop q) {
     if (!q) return 0;
-    if (hipSetDevice(q->device) == hipSuccess) {
-        (void)hipDeviceSynchronize();
-        if (q->slots_dev) (void)hipFree(q->slots_dev);
-        if (q->upd_dev) (void)hipFree(q->upd_dev);
-    }
+    q->mem.release();
     delete q;
     return 0;
 }
@@ -1161,10 +1112,9 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     for (int m = 0; m < P; ++m) {
         const std::string who = "wg_pop_update: member " + std::to_string(m);
         if (!(hp[m].clip_range >= 0.0f)) return wg_fail(WG_ERR_INVALID, who + ": clip_range < 0");
-        if (int rc = t_on_device(params_dev[m], q->device, (who + ": params_dev").c_str())) return rc;
+        if (int rc = wg_on_device(who + ": ", q->device, params_dev[m], "params_dev", "")) return rc;
     }
-    if (int rc = t_on_device(b->obs, q->device, "wg_pop_update: obs")) return rc;
-    if (int rc = t_on_device(perm_dev, q->device, "wg_pop_update: perm_dev")) return rc;
+    if (int rc = wg_on_device_all("wg_pop_update: ", "wg_pop_update: ", q->device, {{b->obs, "obs", true}, {perm_dev, "perm_dev", true}}, "")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows_m = b->n_rows / P;
     const int n_mb = wg_n_minibatches(rows_m, batch_size);

@@ -23,7 +23,7 @@
 struct wg_yaw_table_s {
     int device = 0, N = 0, n_ti = 0, n_ws = 0, n_wd = 0, wrap_wd = 0;
     long long C = 0;
-    void* mem = nullptr;          // one allocation: the axes (ti, ws, wd back to back), then yaw [C][N]
+    WgDevMem mem;                 // one allocation: the axes (ti, ws, wd back to back), then yaw [C][N]
     const double* axes = nullptr;
     const double* yaw = nullptr;
 };
@@ -104,16 +104,7 @@ int yt_axis_check(const char* name, const double* a, int n) {
 }
 
 // a buffer a kernel will touch must be device memory of the table's device
-int yt_on_device(const char* who, int device, const void* ptr, const char* name) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        return wg_fail(WG_ERR_INVALID, std::string(who) + ": " + name + " is not a device pointer");
-    }
-    if (at.type != hipMemoryTypeDevice || at.device != device)
-        return wg_fail(WG_ERR_INVALID, std::string(who) + ": " + name + " is not memory of device " + std::to_string(device) + ", the table's device");
-    return 0;
-}
+const char* const YT_WHOSE = ", the table's device";
 
 }  // namespace
 
@@ -136,21 +127,24 @@ extern "C" int wg_yaw_table_create(int device, const double* ti, int n_ti, const
     if (C * N > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, "wg_yaw_table_create: more than 2^31 table entries");
     if (int rc = wg_use_device(device)) return rc;
     if (on_device)
-        if (int rc = yt_on_device("wg_yaw_table_create", device, yaw, "yaw")) return rc;
+        if (int rc = wg_on_device("wg_yaw_table_create: ", device, yaw, "yaw", YT_WHOSE)) return rc;
     wg_yaw_table_s* t = new (std::nothrow) wg_yaw_table_s;
     if (!t) return wg_fail(WG_ERR_NOMEM, "wg_yaw_table_create: out of memory");
-    t->device = device; t->N = N; t->n_ti = n_ti; t->n_ws = n_ws; t->n_wd = n_wd; t->wrap_wd = wrap_wd != 0; t->C = C;
-    const size_t ab = sizeof(double) * (size_t)n_all, yb = sizeof(double) * (size_t)C * N;
-    hipError_t e = hipMalloc(&t->mem, ab + yb);
-    double* const ax = (double*)t->mem;
-    if (e == hipSuccess) e = hipMemcpy(ax, ti, sizeof(double) * n_ti, hipMemcpyHostToDevice);
+    t->mem.device = t->device = device; t->N = N; t->n_ti = n_ti; t->n_ws = n_ws; t->n_wd = n_wd; t->wrap_wd = wrap_wd != 0; t->C = C;
+    const size_t yb = sizeof(double) * (size_t)C * N;
+    double* ax = nullptr;
+    if (int rc = t->mem.alloc("wg_yaw_table_create", &ax, (size_t)n_all + (size_t)C * N, false)) {
+        wg_yaw_table_destroy(t);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(ax, ti, sizeof(double) * n_ti, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ax + n_ti, ws, sizeof(double) * n_ws, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ax + n_ti + n_ws, wd, sizeof(double) * n_wd, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ax + n_all, yaw, yb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         wg_yaw_table_destroy(t);
-        return wg_fail(e == hipErrorOutOfMemory ? WG_ERR_NOMEM : WG_ERR_HIP, std::string("wg_yaw_table_create: ") + hipGetErrorString(e));
+        return wg_hip_fail("wg_yaw_table_create", e);
     }
     t->axes = ax; t->yaw = ax + n_all;
     *out = t;
@@ -159,12 +153,7 @@ extern "C" int wg_yaw_table_create(int device, const double* ti, int n_ti, const
 
 extern "C" int wg_yaw_table_destroy(wg_yaw_table t) {
     if (!t) return 0;
-    if (t->mem) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != t->device) hipSetDevice(t->device);
-        hipDeviceSynchronize();
-        hipFree(t->mem);
-    }
+    t->mem.release();
     delete t;
     return 0;
 }
@@ -174,10 +163,8 @@ extern "C" int wg_yaw_table_rows(wg_yaw_table t, int n, const double* wind_dev, 
     if (n < 0) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_rows: n must be >= 0, got " + std::to_string(n));
     if (!wind_dev) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_rows: wind_dev is null");
     if (!rows_out) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_rows: rows_out is null");
-    if (int rc = yt_on_device("wg_yaw_table_rows", t->device, wind_dev, "wind_dev")) return rc;
-    if (mask_dev)
-        if (int rc = yt_on_device("wg_yaw_table_rows", t->device, mask_dev, "mask_dev")) return rc;
-    if (int rc = yt_on_device("wg_yaw_table_rows", t->device, rows_out, "rows_out")) return rc;
+    const WgPtrArg args[] = {{wind_dev, "wind_dev", true}, {mask_dev, "mask_dev", false}, {rows_out, "rows_out", true}};
+    if (int rc = wg_on_device_all("wg_yaw_table_rows: ", "wg_yaw_table_rows: ", t->device, args, YT_WHOSE)) return rc;
     if (n == 0) return 0;
     if (int rc = wg_use_device(t->device)) return rc;
     hipLaunchKernelGGL(k_yaw_table_rows, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, yt_params(t), n, wind_dev, mask_dev, rows_out);
@@ -190,8 +177,8 @@ extern "C" int wg_yaw_table_targets(wg_yaw_table t, int n, const double* wind_de
     if (n < 0) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_targets: n must be >= 0, got " + std::to_string(n));
     if (!wind_dev) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_targets: wind_dev is null");
     if (!targets_out) return wg_fail(WG_ERR_INVALID, "wg_yaw_table_targets: targets_out is null");
-    if (int rc = yt_on_device("wg_yaw_table_targets", t->device, wind_dev, "wind_dev")) return rc;
-    if (int rc = yt_on_device("wg_yaw_table_targets", t->device, targets_out, "targets_out")) return rc;
+    const WgPtrArg args[] = {{wind_dev, "wind_dev", true}, {targets_out, "targets_out", true}};
+    if (int rc = wg_on_device_all("wg_yaw_table_targets: ", "wg_yaw_table_targets: ", t->device, args, YT_WHOSE)) return rc;
     const long long total = (long long)n * t->N;
     if (total > 0x7fffffffLL) return wg_fail(WG_ERR_UNSUPPORTED, "wg_yaw_table_targets: more than 2^31 target entries");
     if (n == 0) return 0;

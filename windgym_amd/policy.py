@@ -27,6 +27,8 @@ from typing import NamedTuple
 
 import numpy as np
 
+from .binding import Handle, device_tensor  # noqa: F401  (device_tensor: re-exported, the trainers import it from here)
+
 MAX_HIDDEN = 4
 
 
@@ -196,12 +198,6 @@ def read_sb3_zip(path, activation="tanh"):
 # ----------------------------------------------------------------------------------------------------------------------
 # the device object
 # ----------------------------------------------------------------------------------------------------------------------
-def device_tensor(x, dtype):
-    """What every tensor handed to the library must be: a contiguous CUDA tensor of ``dtype`` (its size is the caller's to check)."""
-    import torch
-    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous()
-
-
 def refuse_recurrent(policy, who):
     """What the trainers and the wrappers say to a ``recurrent.MlpLstmPolicy`` (or a list holding one): they are not built for it."""
     if any(getattr(p, "recurrent", False) for p in (policy if isinstance(policy, (list, tuple)) else (policy,))):
@@ -247,7 +243,7 @@ def act_buffers(owner, n):
     return b
 
 
-class MlpPolicy:
+class MlpPolicy(Handle):
     """SB3's default ``MlpPolicy`` (actor ``n_in -> hidden_pi -> n_out``, critic ``n_in -> hidden_vf -> 1``) on one GPU.
     With ``n_in_vf`` the critic maps ``n_in_vf -> hidden_vf -> 1`` instead (a split policy: ``act()`` evaluates the actor only,
     ``value()`` takes rows of ``n_in_vf``).
@@ -255,6 +251,8 @@ class MlpPolicy:
     ``params`` is ONE flat float32 CUDA leaf tensor (a torch optimiser can own it); ``state_dict()`` returns views of it
     under SB3's names.  The kernel reads its own packed copy: after changing ``params`` call :meth:`sync`.
     Raises ``WindGymHipError`` without the built library or a GPU — there is no CPU fallback."""
+
+    destroy = "wg_policy_destroy"
 
     def __init__(self, n_in, n_out, hidden_pi=(64, 64), hidden_vf=(64, 64), activation="tanh", device=None, seed=0,
                  has_log_std=True, n_in_vf=None):
@@ -310,24 +308,9 @@ class MlpPolicy:
         p.load_state_dict(tensors)
         return p
 
-    # -- lifetime -----------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.wg_policy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def rollout_actor(self, venv):
         return RolloutActor(self, "wg_rollout", (self._h,), (self.n_in, self.n_out), log_std=self.desc["has_log_std"],
                             critic=self.n_in_vf if self.has_critic else None)
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     # -- parameters ---------------------------------------------------------------------------------
     def state_dict(self):

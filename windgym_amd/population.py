@@ -16,6 +16,7 @@ import os
 
 import numpy as np
 
+from .binding import Handle
 from .policy import act_buffers, device_tensor, refuse_recurrent, refuse_table_agent
 from .ppo import PPO, PPOOptimizer, _schedule, check_batch_size, check_hyper, learn_loop, write_checkpoint
 
@@ -68,7 +69,7 @@ def check_members(members):
     return members
 
 
-class PopulationBase:
+class PopulationBase(Handle):
     """What the two acting objects (:class:`Population`, ``recurrent_population.RecurrentPopulation``) share: the members behind one
     population handle of the library.  A subclass names the check of its members and the entry that destroys its handle, and states
     ``_create(arr)`` -> the handle, ``arr`` making the ``void*[P]`` of a list of handles."""
@@ -94,20 +95,6 @@ class PopulationBase:
             raise ValueError(f"rollout(): the {self.n_members} members own equal shares of the envs: num_envs = {venv.num_envs} "
                              f"does not divide by {self.n_members}")
         return self.members[0].rollout_actor(venv)._replace(obj=self, entry=self.rollout_entry, handles=(self._h,), members=self.n_members)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            getattr(self.L, self.destroy)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def _u64(self, x, default):
         P = self.n_members

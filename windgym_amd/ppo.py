@@ -18,6 +18,7 @@ import zipfile
 
 import numpy as np
 
+from .binding import Handle
 from .policy import MlpPolicy, device_tensor, param_layout, refuse_recurrent, refuse_table_agent
 
 HYPER = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
@@ -49,13 +50,14 @@ def sb3_orthogonal_init(desc, seed):
     return out
 
 
-class HandleOptimizer:
+class HandleOptimizer(Handle):
     """What the ``wg_ppo`` (:class:`PPOOptimizer`) and ``wg_lstm_ppo`` (``recurrent_ppo.RecurrentPPOOptimizer``) handles share: the
     handle's lifetime, the argument checks, wg_gae, the optimiser step and Adam's state.  ``prefix`` names the family's entries,
     ``index_is`` what ``_index`` calls its argument.  All methods enqueue on torch's current stream and synchronise nothing
     (``state()`` / ``load_state()`` excepted)."""
 
     prefix, index_is = None, None
+    destroy = property(lambda self: self.prefix + "_destroy")
 
     def _open(self, policy, *create_args):
         """``<prefix>_create(*create_args, &handle)`` and the gradient buffer of ``policy.params``."""
@@ -69,17 +71,6 @@ class HandleOptimizer:
     def _call(self, entry, *args):
         name = f"{self.prefix}_{entry}"
         self._chk(getattr(self.L, name)(*args), name)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            getattr(self.L, self.prefix + "_destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _f32(self, x, shape, what):
         if not (device_tensor(x, self.torch.float32) and x.numel() == int(np.prod(shape))):

@@ -35,6 +35,7 @@ import ctypes as C
 import numpy as np
 
 from . import policy as _mlp
+from .binding import Handle
 
 MAX_IN, MAX_H = 2048, 256
 
@@ -141,7 +142,7 @@ def read_sb3_lstm_zip(path, activation="tanh"):
 # ----------------------------------------------------------------------------------------------------------------------
 # the device object
 # ----------------------------------------------------------------------------------------------------------------------
-class MlpLstmPolicy:
+class MlpLstmPolicy(Handle):
     """sb3-contrib's ``MlpLstmPolicy`` on one GPU (module docstring).  ``params`` is ONE flat float32 CUDA tensor: the LSTM parameters,
     then the MLP's in ``policy.param_layout`` order; ``state_dict()`` returns views of it under sb3-contrib's names.  The kernels
     read packed copies: after changing ``params`` call :meth:`sync`.  Raises ``WindGymHipError`` without the built library or a
@@ -197,25 +198,16 @@ class MlpLstmPolicy:
         return p
 
     # -- lifetime -----------------------------------------------------------------------------------
+    destroy, handle_attr = "wg_lstm_destroy", "_lstm"      # (``_h`` holds act()'s h' rows here)
+
     def close(self):
-        if getattr(self, "_lstm", None):
-            self.L.wg_lstm_destroy(self._lstm)
-            self._lstm = None
+        super().close()
         if getattr(self, "mlp", None) is not None:
             self.mlp.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def rollout_actor(self, venv):
         _mlp.refuse_site(venv, "a recurrent policy")
         return _mlp.RolloutActor(self, "wg_rollout_lstm", (self._lstm, self.mlp._h), (self.n_in, self.n_out), log_std=True, critic=self.n_in, lstm=True)
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     # -- parameters ---------------------------------------------------------------------------------
     def _views(self, params):

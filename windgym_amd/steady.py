@@ -290,12 +290,6 @@ class SteadyStateYawAgent(BaseAgent):
             self._batch = None
             self.device = "cpu"
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
     def update_wind(self, wind_speed, wind_direction, TI):
         self.wsp, self.wdir, self.TI = np.asarray([wind_speed], float), np.asarray([wind_direction], float), TI
         self.optimized = False
