@@ -672,6 +672,36 @@ int wg_ppo_grad_shared(wg_ppo o, const float* params_dev, const wg_ppo_batch_sha
 int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared* batch, const int32_t* perm_dev, int n_epochs,
                          int batch_size, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
+/* A KL-ADAPTIVE LEARNING RATE on the device (the schedule of rsl_rl / rl_games, minibatch by minibatch): the rate lives in ONE
+ * device float and follows the approx_kl each minibatch's reduce has just written, with no host round trip and no launch of its
+ * own (the Adam kernel reads both words).  THE RULE, from the rule the caller gives (band and `down` computed once in float on
+ * the host: kl_low = desired_kl / 2, kl_high = 2 * desired_kl, up = factor, down = 1 / factor; multiplications only afterwards):
+ *     next(lr, kl):  kl > kl_high              -> max(lr_min, lr * down)
+ *                    kl < kl_low and kl > 0    -> min(lr_max, lr * up)
+ *                    else (inside the band, kl == 0, kl < 0, NaN) -> lr
+ * While set on a handle, wg_ppo_update and wg_ppo_update_shared on it (and wg_pop_update for a member whose opts[m] it is) IGNORE
+ * their lr argument and are bit-identical to wg_ppo_update's loop with
+ *     lr = *lr_dev
+ *     for e, k:  wg_ppo_grad(..., stats + e * n_mb + k)
+ *                if (e, k) != (0, 0):  lr = next(lr, stats[e * n_mb + k].approx_kl)
+ *                wg_ppo_apply(o, params_dev, g, lr, max_grad_norm)
+ *     *lr_dev = lr                      (visible in stream order after the call)
+ * The FIRST minibatch of an update never moves the rate: the parameters are still the rollout's there, ratio = 1 to rounding
+ * (wg_ppo_grad), so the sign and size of its approx_kl are noise.  stats_out = NULL changes nothing (the handle reads its own
+ * record).  Adam's step_size is float((double)lr / (1 - beta1^step)) formed in the kernel from the rate it read: the bits of
+ * wg_ppo_apply with that lr.  wg_ppo_grad, wg_ppo_apply and wg_bc_* are unaffected (apply takes its argument; a supervised
+ * loss has no KL).
+ * lr_dev: one caller-owned device float on the handle's device — the starting rate, updated in place, and it must outlive the
+ * setting.  rule = NULL together with lr_dev = NULL turns the rule off again.  Reads *lr_dev once (synchronises the device).
+ * WG_ERR_INVALID, naming the argument: one of rule / lr_dev null; desired_kl not > 0 or not finite; factor < 1 or not finite;
+ * lr_min not > 0; lr_min > lr_max; lr_dev not memory of the handle's device; a starting rate outside [lr_min, lr_max].        */
+typedef struct wg_kl_lr {
+    float desired_kl;      /* the KL the rate steers toward: it stays while desired_kl / 2 <= approx_kl <= 2 desired_kl */
+    float factor;          /* >= 1: the rate is multiplied by it below the band, by 1 / factor above (rsl_rl: 1.5)      */
+    float lr_min, lr_max;  /* the clamp (rsl_rl: 1e-5, 1e-2)                                                            */
+} wg_kl_lr;
+int wg_ppo_set_kl_lr(wg_ppo o, const wg_kl_lr* rule, float* lr_dev);
+
 /* -----------------------------------------------------------------------------------------------------------------
  * Behaviour cloning: a SUPERVISED loss on the same handle — the optimiser's Adam state, its scratch and wg_ppo_apply are the
  * ones above, and k_bc_grad is k_ppo_grad's forward and backward with another loss head (windgym_amd/csrc/wg_ppo.hip).  The
@@ -772,7 +802,11 @@ int wg_gae_pop(int T, int B, int P, const float* reward_dev, const float* value_
  *     wg_ppo_update(opts[m], params_dev[m], <the member's rows as a contiguous batch>, <the same permutations as local row ids>,
  *                   n_epochs, batch_size, &hp[m], lr[m], max_grad_norm[m], stats_out + m * n_epochs * n_mb, stream)
  * and Adam's step count advances in every member's own wg_ppo.  WG_ERR_INVALID, nothing enqueued: a population created
- * without opts, P not dividing n_rows, what wg_ppo_update refuses (the message names the member).                        */
+ * without opts, P not dividing n_rows, what wg_ppo_update refuses (the message names the member).
+ * With wg_ppo_set_kl_lr on the members' handles every member's rate is its own device word under its own rule (lr[m] is ignored)
+ * and the contract above holds with that rule set on the single-policy call, whatever P, m and the other members' rules; the
+ * launches run in lockstep, so EVERY member is set or none: anything else (or one lr_dev given to two members) is WG_ERR_INVALID
+ * naming the member, nothing enqueued.                                                                                     */
 int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
                   int batch_size, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm, wg_ppo_stats* stats_out,
                   void* stream);
@@ -1151,6 +1185,12 @@ int wg_lstm_ppo_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, f
 int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lstm_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
                        int envs_per_batch, const wg_ppo_hyper* hp, float lr, float max_grad_norm, wg_ppo_stats* stats_out, void* stream);
 
+/* wg_ppo_set_kl_lr (the rule, the loop, the skipped first minibatch and the refusals are stated there) for wg_lstm_ppo_update and,
+ * per member, wg_lstm_pop_update: while set they ignore their lr argument and equal the loop above with the rate read from
+ * *lr_dev and stepped by each minibatch's approx_kl before its wg_lstm_ppo_apply.  wg_lstm_ppo_grad, wg_lstm_ppo_apply and
+ * wg_lstm_bc_* are unaffected.                                                                                                 */
+int wg_lstm_ppo_set_kl_lr(wg_lstm_ppo o, const wg_kl_lr* rule, float* lr_dev);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Behaviour cloning into a recurrent policy: the SUPERVISED loss of wg_bc_grad on the wg_lstm_ppo handle — its buffers, its Adam
  * state and wg_lstm_ppo_apply are the ones above, as wg_bc_* sits on wg_ppo; k_bc_grad_dh is k_bc_grad with the gradients of the h
@@ -1249,7 +1289,8 @@ int wg_lstm_pop_rollout(wg_handle h, wg_lstm_pop q, int n_steps, int determinist
  * and Adam's step count advances in every member's own wg_lstm_ppo.  An env id outside [0, B) is a column of zeros, as in
  * wg_lstm_ppo_grad; one inside [0, B) but outside the member's own envs is not checked (nothing is read out of bounds, but the rows are
  * another member's).  WG_ERR_INVALID / WG_ERR_UNSUPPORTED, nothing enqueued: a population created without opts, P not dividing B,
- * what wg_lstm_ppo_update refuses (T > T_max or envs_per_batch > Bm_max of a member's handle: the message names the member).  */
+ * what wg_lstm_ppo_update refuses (T > T_max or envs_per_batch > Bm_max of a member's handle: the message names the member).
+ * KL-adaptive rates (wg_lstm_ppo_set_kl_lr on the members' handles): as wg_pop_update states it — every member or none.         */
 int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const wg_lstm_ppo_batch* batch, const int32_t* perm_dev, int n_epochs,
                        int envs_per_batch, const wg_ppo_hyper* hp, const float* lr, const float* max_grad_norm, wg_ppo_stats* stats_out,
                        void* stream);

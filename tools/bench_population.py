@@ -10,7 +10,7 @@ two device synchronisations, and the median is reported.  For P in `--members`, 
   seq_collect / seq_train   the same P members as P standalone PPO objects on envs of Bm each, one after the other
                             (P x venv.rollout + wg_gae, P x wg_ppo_update)
 
-usage: python tools/bench_population.py [--members 1 2 4 8 16] [--envs-member 512] [--envs-total 4096] [--out FILE]
+usage: python tools/bench_population.py [--members 1 2 4 8 16] [--envs-member 512] [--envs-total 4096] [--out FILE] [--adaptive-lr]
 """
 import argparse
 import json
@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--preroll", type=int, default=50)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
+    ap.add_argument("--adaptive-lr", action="store_true", help="every trainer with the KL-adaptive learning rate set "
+                    "(adaptive_lr=dict(desired_kl=0.01)): compare with a run without the switch")
     args = ap.parse_args()
     import torch
     from windgym_amd import presets
@@ -46,6 +48,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     T, E = args.n_steps, args.epochs
+    adapt = dict(adaptive_lr=dict(desired_kl=0.01)) if args.adaptive_lr else {}
 
     def venv(B):
         v = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
@@ -72,10 +75,11 @@ def main():
             Bm = args.envs_member if layout == "per_member" else args.envs_total // P
             B = P * Bm
             v = venv(B)
-            pp = PPOPopulation("MlpPolicy", v, n_members=P, n_steps=T, n_epochs=E, seed=list(range(P)))
+            pp = PPOPopulation("MlpPolicy", v, n_members=P, n_steps=T, n_epochs=E, seed=list(range(P)), **adapt)
             lr, clip = [3e-4] * P, [0.2] * P
             rec = {"metric": "PPO population vs the same members one after the other, 16-turbine farm, one GPU", "layout": layout,
-                   "members": P, "envs_member": Bm, "envs": B, "n_steps": T, "epochs": E, "batch_size": pp.batch_size, "unit": "ms, median"}
+                   "members": P, "envs_member": Bm, "envs": B, "n_steps": T, "epochs": E, "batch_size": pp.batch_size, "unit": "ms, median",
+                   "adaptive_lr": bool(args.adaptive_lr)}
             rec["pop_collect"] = timed(pp.collect)
             out = pp.collect()
             rec["pop_train"] = timed(lambda: pp.train(out, lr, clip))
@@ -84,7 +88,7 @@ def main():
                 m.close()
             v.close()
             vs = [venv(Bm) for _ in range(P)]
-            ps = [PPO("MlpPolicy", x, n_steps=T, n_epochs=E, seed=m) for m, x in enumerate(vs)]
+            ps = [PPO("MlpPolicy", x, n_steps=T, n_epochs=E, seed=m, **adapt) for m, x in enumerate(vs)]
             rec["seq_collect"] = timed(lambda: [p.collect() for p in ps])
             outs = [{k: (x.clone() if torch.is_tensor(x) else x) for k, x in p.collect().items()} for p in ps]
             rec["seq_train"] = timed(lambda: [p.train(o, 3e-4, 0.2) for p, o in zip(ps, outs)])

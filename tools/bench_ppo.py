@@ -30,8 +30,12 @@ With --normalize (single-agent workload only) the tool measures what VecNormaliz
 are copies), and PPO.learn per iteration with ``normalize=None`` and with a ``VecNormalize`` — the legs ALTERNATING in one process
 (`--reps` rounds; median, min and max are reported).  The eager-torch legs are skipped.
 
+With --adaptive-lr the trainer is built with ``adaptive_lr=dict(desired_kl=0.01)``: update_hip_<mb> and learn_hip then run with the
+KL-adaptive rate set on the handle (k_ppo_adam_kl in k_ppo_adam's place), the eager-torch legs are skipped; a run without the switch
+on the same machine is the other side of the comparison.
+
 usage: python tools/bench_ppo.py [--envs 4096] [--n-steps 128] [--epochs 10] [--reps 5] [--multi [--critic agent|central]]
-                                 [--curriculum | --normalize]
+                                 [--curriculum | --normalize] [--adaptive-lr]
 """
 import argparse
 import json
@@ -60,6 +64,8 @@ def main():
     ap.add_argument("--preroll", type=int, default=300)
     ap.add_argument("--curriculum", action="store_true", help="measure PPO with and without a YawCurriculum, and the curriculum's parts")
     ap.add_argument("--normalize", action="store_true", help="measure rollouts and PPO with and without a VecNormalize")
+    ap.add_argument("--adaptive-lr", action="store_true", help="every leg with the KL-adaptive learning rate set (adaptive_lr=dict(desired_kl=0.01)); "
+                    "the eager-torch legs are skipped: compare with a run without the switch")
     args = ap.parse_args()
     if (args.curriculum or args.normalize) and args.multi:
         ap.error("--curriculum / --normalize measure the single-agent workload")
@@ -86,7 +92,8 @@ def main():
     n_rows = B * T * A
     mbs = args.minibatches or sorted({min(4096, n_rows), max(1, n_rows // 4)})
     venv.reset(seed=1234)
-    ppo = PPO("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=mbs[0], seed=1234, critic=args.critic if args.multi else None)
+    ppo = PPO("MlpPolicy", venv, n_steps=T, n_epochs=E, batch_size=mbs[0], seed=1234, critic=args.critic if args.multi else None,
+              adaptive_lr=dict(desired_kl=0.01) if args.adaptive_lr else None)
     pol = ppo.policy
     zero = torch.zeros((B, venv.n_turb), device=dev)
     for _ in range(args.preroll):
@@ -237,7 +244,13 @@ def main():
         ppo.opt.load_state(torch.zeros(2 * start.numel()).numpy(), 0)
         ppo.opt.update(obs, raw, lpo, adv, ret, perm, bs, learning_rate=3e-4, max_grad_norm=0.5, **shared)
 
+    out["adaptive_lr"] = bool(args.adaptive_lr)
     for bs in mbs:
+        if args.adaptive_lr:                    # (the rule is set on the handle: wg_ppo_update reads the rate from ppo.lr)
+            el, ts = timed(lambda: update_hip(bs), args.reps)
+            out["update_hip_%d" % bs] = {"value": n_rows * E / el, "unit": "trained samples/s", "ms": el * 1e3,
+                                         "ms_all": [round(x * 1e3, 3) for x in ts]}
+            continue
         el, ts = timed(lambda: update_torch(bs), args.torch_reps)
         out["update_torch_%d" % bs] = {"value": n_rows * E / el, "unit": "trained samples/s", "ms": el * 1e3,
                                        "ms_all": [round(x * 1e3, 3) for x in ts]}

@@ -56,7 +56,8 @@ def leg(args):
     venv = WindFarmVecEnv(V80(), B, yaml_dict=presets.bench_cfg2_config(), seed=1234, device=0, as_torch=True, turbtype="None",
                           n_passthrough=5, n_rotor_pts=16)
     venv.reset(seed=1234)
-    ppo = RecurrentPPO("MlpLstmPolicy", venv, n_steps=T, n_epochs=E, batch_size=Bm * T, seed=1234, policy_kwargs=dict(lstm_hidden_size=H))
+    ppo = RecurrentPPO("MlpLstmPolicy", venv, n_steps=T, n_epochs=E, batch_size=Bm * T, seed=1234, policy_kwargs=dict(lstm_hidden_size=H),
+                       adaptive_lr=dict(desired_kl=0.01) if args.adaptive_lr else None)
     pol = ppo.policy
     zero = torch.zeros((B, venv.n_turb), device=dev)
     for _ in range(args.preroll):
@@ -159,7 +160,8 @@ def members_leg(args):
     Bm, H = (int(x) for x in args.leg_size.split("x"))
     T, E = args.n_steps, args.epochs
     epb = -(-Bm // args.minibatches)
-    kw = dict(n_steps=T, n_epochs=E, batch_size=epb * T, policy_kwargs=dict(lstm_hidden_size=H))
+    kw = dict(n_steps=T, n_epochs=E, batch_size=epb * T, policy_kwargs=dict(lstm_hidden_size=H),
+              adaptive_lr=dict(desired_kl=0.01) if args.adaptive_lr else None)
     seeds = [1234 + m for m in range(P)]
 
     def env(n):
@@ -225,11 +227,11 @@ def members_main(args):
                          "population (pop) against the runs one after another (seq), per iteration of all runs"
                          % (args.members, Bm, args.n_steps, H, args.epochs, args.minibatches),
                "members": args.members, "envs_per_member": Bm, "hidden": H, "n_steps": args.n_steps, "epochs": args.epochs,
-               "minibatches": args.minibatches}
+               "minibatches": args.minibatches, "adaptive_lr": bool(args.adaptive_lr)}
         for name in legs:
             cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--leg-size", size, "--members", str(args.members), "--n-steps",
                    str(args.n_steps), "--epochs", str(args.epochs), "--minibatches", str(args.minibatches), "--reps", str(args.reps),
-                   "--preroll", str(args.preroll)]
+                   "--preroll", str(args.preroll)] + (["--adaptive-lr"] if args.adaptive_lr else [])
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.leg_timeout)
                 lines = [x for x in r.stdout.splitlines() if x.startswith("LEG ")]
@@ -262,6 +264,8 @@ def main():
     ap.add_argument("--legs", nargs="*", default=["hip", "torch_a", "torch_b"])
     ap.add_argument("--leg-timeout", type=float, default=240.0, help="seconds each leg's process may take")
     ap.add_argument("--members", type=int, default=0, help="P > 0: the sizes are envs per member, the legs `pop` and `seq` (module docstring)")
+    ap.add_argument("--adaptive-lr", action="store_true", help="the device legs (hip, pop, seq) with the KL-adaptive learning rate set "
+                    "(adaptive_lr=dict(desired_kl=0.01)): compare with a run without the switch")
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--leg-size", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -273,11 +277,12 @@ def main():
         B, H = (int(x) for x in size.split("x"))
         res = {"metric": "RecurrentPPO on the device, 16-turbine farm x %d envs x %d steps, LSTM H = %d, %d epochs x %d minibatches, one GPU"
                          % (B, args.n_steps, H, args.epochs, args.minibatches),
-               "envs": B, "hidden": H, "n_steps": args.n_steps, "epochs": args.epochs, "minibatches": args.minibatches}
+               "envs": B, "hidden": H, "n_steps": args.n_steps, "epochs": args.epochs, "minibatches": args.minibatches,
+               "adaptive_lr": bool(args.adaptive_lr)}
         for name in args.legs:
             cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--leg-size", size, "--n-steps", str(args.n_steps), "--epochs",
                    str(args.epochs), "--minibatches", str(args.minibatches), "--reps", str(args.reps), "--torch-reps", str(args.torch_reps),
-                   "--preroll", str(args.preroll)]
+                   "--preroll", str(args.preroll)] + (["--adaptive-lr"] if args.adaptive_lr else [])
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.leg_timeout)
                 lines = [x for x in r.stdout.splitlines() if x.startswith("LEG ")]

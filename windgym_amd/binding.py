@@ -68,7 +68,7 @@ ABI_SYMBOLS = (
     "wg_get_info", "wg_get_measurements", "wg_get_windspeed", "wg_metrics", "wg_get_state", "wg_set_state", "wg_generate_mann_box", "wg_mann_beta_table", "wg_steady_power", "wg_steady_optimize", "wg_kernel_timing", "wg_added_lookups", "wg_algorithmic_bytes", "wg_flow_variant",
     "wg_policy_create", "wg_policy_destroy", "wg_policy_set_params", "wg_policy_n_params", "wg_policy_act", "wg_rollout",
     "wg_gae", "wg_ppo_create", "wg_ppo_destroy", "wg_ppo_get_state", "wg_ppo_set_state", "wg_ppo_grad", "wg_ppo_apply", "wg_ppo_update",
-    "wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared",
+    "wg_policy_create_vf", "wg_ppo_grad_shared", "wg_ppo_update_shared", "wg_ppo_set_kl_lr", "wg_lstm_ppo_set_kl_lr",
     "wg_pop_create", "wg_pop_destroy", "wg_pop_act", "wg_pop_rollout", "wg_gae_pop", "wg_pop_update",
     "wg_curriculum_create", "wg_curriculum_destroy", "wg_curriculum_get_state", "wg_curriculum_set_state", "wg_curriculum_set_targets",
     "wg_curriculum_shape",
@@ -127,6 +127,11 @@ class CPpoBatchShared(C.Structure):
 class CPpoHyper(C.Structure):
     """wg_ppo_hyper"""
     _fields_ = [("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("normalize_advantage", C.c_int32)]
+
+
+class CKlLr(C.Structure):
+    """wg_kl_lr"""
+    _fields_ = [("desired_kl", C.c_float), ("factor", C.c_float), ("lr_min", C.c_float), ("lr_max", C.c_float)]
 
 
 class CNormDesc(C.Structure):
@@ -254,6 +259,7 @@ def load_library():
         getattr(L, fam + "_get_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         getattr(L, fam + "_set_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]
         getattr(L, fam + "_apply").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+        getattr(L, fam + "_set_kl_lr").argtypes = [C.c_void_p, C.POINTER(CKlLr), C.c_void_p]
     L.wg_ppo_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int64, C.c_int,
                               C.POINTER(CPpoHyper), C.c_void_p, C.c_void_p, C.c_void_p]
     L.wg_ppo_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CPpoBatch), C.c_void_p, C.c_int, C.c_int,

@@ -66,6 +66,13 @@ int wg_adam_alloc_(WgDevMem* mem, WgAdam* a, uint32_t n_flat, const char* who);
 int wg_adam_get_state_(WgAdam* a, const char* who, float* mv_host, size_t n, uint64_t* step);
 int wg_adam_set_state_(WgAdam* a, const char* who, const float* mv_host, size_t n, uint64_t step);
 int wg_adam_apply_(WgAdam* a, float* params_dev, const float* grad_dev, float lr, float max_grad_norm, hipStream_t st);
+// wg_ppo.hip, the KL-adaptive rate (wg_train.h: WgKlLr).  set_kl_lr: the public *_set_kl_lr entries, reported as `who`, a null `a`
+// included; the first rule set on a handle allocates its two slots from `mem`, the handle's owner (none is ever set: nothing);
+// apply_kl: wg_adam_apply_ for minibatch mb (`last`: the final one) of an update while a rule is set — the rate comes from the
+// handle's device words and is stepped by approx_kl of the record at stats_dev first, mb = 0 excepted (k_ppo_sumsq + k_ppo_adam_kl)
+int wg_adam_set_kl_lr_(WgDevMem* mem, WgAdam* a, const char* who, const wg_kl_lr* rule, float* lr_dev);
+int wg_adam_apply_kl_(WgAdam* a, float* params_dev, const float* grad_dev, const float* stats_dev, int mb, int last, float max_grad_norm,
+                      hipStream_t st);
 // wg_ppo.hip: the gradient kernel's side of policy p (wg_ppo.h: WgPpoGrad) — the first half of wg_ppo_create; what it refuses about
 // the policy is reported under that name.  heads_grad, the heads of a recurrent policy (wg_lstm_ppo.hip): k_ppo_grad's loss on n rows whose actor reads h_pi [n][H] and
 // whose critic reads h_vf [n][H], raw / logp / adv / ret indexed by the same row -> the MLP's flat gradient, the stats record and the
@@ -91,6 +98,11 @@ int wg_ppo_heads_grad_pop_(const WgPpoGrad* g0, const WgPopMember* mt, const WgP
 // Adam over each of the n_members rows of a member table (device): counts one step of adam[m], then clipping by the member's own
 // norm and that step with the member's own lr[m] (k_ppo_sumsq_pop + k_ppo_adam_pop) on vectors of adam[0]->n_flat floats
 int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, WgAdam* const* adam, const float* lr, void* stream);
+// ... with KL-adaptive rates: *on = every member has a rule set, or none has — anything else is refused as `who`, naming the member
+// (so is a rate word two members share); apply_kl_pop: wg_adam_apply_kl_ per member, whose words, rule and stats records are its row's
+// (k_ppo_sumsq_pop + k_ppo_adam_kl_pop)
+int wg_pop_kl_lr_(const char* who, int n_members, WgAdam* const* adam, int* on);
+int wg_adam_apply_kl_pop_(const WgPopMember* mt, int n_members, WgAdam* const* adam, int mb, int last, void* stream);
 // wg_lstm.hip, populations of recurrent policies (wg_lstm.h): wg_lstm_step for every member in ONE launch of k_lstm_pop on n_rows =
 // P Bm rows; k_lstm_pack for every member in one launch (params_dev[m]: host array of the members' flat vectors); the heads' slot
 // table on the h rows of the running step (the outputs: wg_policy.h, WgPopOuts)

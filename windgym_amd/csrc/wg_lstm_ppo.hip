@@ -580,6 +580,18 @@ static int lp_apply(wg_lstm_ppo o, float* params_dev, const float* grad_dev, flo
     return wg_policy_set_params(o->pol, params_dev + o->n_lstm, o->adam.n_flat - o->n_lstm, 1, (void*)st);
 }
 
+// ... of minibatch mb of an update under the handle's KL rule (wg_adam_apply_kl_)
+static int lp_apply_kl(wg_lstm_ppo o, float* params_dev, const float* grad_dev, const float* stats_dev, int mb, int last, float max_grad_norm,
+                       hipStream_t st) {
+    if (int rc = wg_adam_apply_kl_(&o->adam, params_dev, grad_dev, stats_dev, mb, last, max_grad_norm, st)) return rc;
+    if (int rc = wg_lstm_set_params(o->lstm, params_dev, o->n_lstm, 1, (void*)st)) return rc;
+    return wg_policy_set_params(o->pol, params_dev + o->n_lstm, o->adam.n_flat - o->n_lstm, 1, (void*)st);
+}
+
+extern "C" int wg_lstm_ppo_set_kl_lr(wg_lstm_ppo o, const wg_kl_lr* rule, float* lr_dev) {
+    return wg_adam_set_kl_lr_(o ? &o->mem : nullptr, o ? &o->adam : nullptr, "wg_lstm_ppo_set_kl_lr", rule, lr_dev);
+}
+
 extern "C" int wg_lstm_ppo_grad(wg_lstm_ppo o, const float* params_dev, const wg_lstm_ppo_batch* b, const int32_t* envs_dev, int n_envs,
                                 const wg_ppo_hyper* hp, float* grad_out, wg_ppo_stats* stats_out, void* stream) {
     if (!o || !params_dev || !b || !envs_dev || !hp || !grad_out) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_grad: null argument");
@@ -603,9 +615,12 @@ extern "C" int wg_lstm_ppo_update(wg_lstm_ppo o, float* params_dev, const wg_lst
     if (int rc = lp_check("wg_lstm_ppo_update", o, b, hp, envs_per_batch)) return rc;
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, "wg_lstm_ppo_update: max_grad_norm must be > 0");
     if (int rc = wg_use_device(o->adam.device)) return rc;
+    const bool kl = o->adam.lr_dev != nullptr;                  // wg_lstm_ppo_set_kl_lr: the rate is the handle's device word, `lr` is ignored
+    const int n_all = n_epochs * wg_n_minibatches(b->B, envs_per_batch);
     return wg_each_minibatch(b->B, n_epochs, envs_per_batch, [&](int mb, int64_t off, int Bm) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
         if (int rc = lp_grad(o, params_dev, b, perm_dev + off, Bm, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        if (kl) return lp_apply_kl(o, params_dev, o->grad, so ? so : o->stats, mb, mb == n_all - 1, max_grad_norm, (hipStream_t)stream);
         return lp_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
     });
 }
@@ -764,11 +779,13 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
     WgPopMember upd[2 * WGP_POP_MAX] = {};
     WgPopHeadRows rows[WGP_POP_MAX] = {};
     WgAdam* adam[WGP_POP_MAX];
+    for (int m = 0; m < P; ++m) adam[m] = &q->opt[m]->adam;
+    int kl = 0;                                                 // the members' rates are their device words (every member or none), `lr` is ignored
+    if (int rc = wg_pop_kl_lr_("wg_lstm_pop_update", P, adam, &kl)) return rc;
     bool any_norm = false;
     for (int m = 0; m < P; ++m) {
         wg_lstm_ppo_s* o = q->opt[m];
         const WgLstmStash s = wglp_stash(o);
-        adam[m] = &o->adam;
         WgLstmPopMember& S = seq[m];
         S.q = s.q;
         S.q.obs = b->obs; S.q.start = b->episode_start; S.q.envs = perm_dev + (size_t)m * n_epochs * sB;
@@ -783,6 +800,8 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
         any_norm = wgt_pop_member(M, hp, stats_out, m, n_epochs, n_mb, o->stats) || any_norm;
         WgPopMember& A = upd[WGP_POP_MAX + m];
         A.params = params_dev[m]; A.grad = o->grad; A.m = o->adam.m; A.v = o->adam.v; A.blocksq = o->adam.blocksq; A.max_norm = max_grad_norm[m];
+        A.stats = M.stats; A.stats_step = M.stats_step;           // (the record the heads' reduce writes: what a KL-adaptive rate reads)
+        wgt_pop_member_kl(A, o->adam);
     }
     const WgLstmPopMember* mt = (const WgLstmPopMember*)q->seq_dev;
     const WgPopMember* ht = (const WgPopMember*)q->upd_dev;
@@ -807,7 +826,9 @@ extern "C" int wg_lstm_pop_update(wg_lstm_pop q, float* const* params_dev, const
                            st, L, mt, off, Bm, NT, S);
         hipLaunchKernelGGL(k_lstm_wgrad_reduce_pop, dim3((o0->n_lstm + 255) / 256, P), dim3(256), 0, st, mt, o0->n_lstm, S);
         WG_HIPCHK(hipGetLastError());
-        if (int rc = wg_adam_apply_pop_(ht + WGP_POP_MAX, P, adam, lr, stream)) return rc;
+        if (int rc = kl ? wg_adam_apply_kl_pop_(ht + WGP_POP_MAX, P, adam, mb, mb == n_epochs * n_mb - 1, stream)
+                        : wg_adam_apply_pop_(ht + WGP_POP_MAX, P, adam, lr, stream))
+            return rc;
         if (int rc = wg_lstm_pack_pop_(q, params_dev, stream)) return rc;
         wg_policy_pack_pop_(&PP, ht, P, stream);
         WG_HIPCHK(hipGetLastError());

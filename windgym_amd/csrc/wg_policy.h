@@ -25,6 +25,7 @@
 #include "../../include/windgym_hip.h"
 #include "wg_devmem.h"
 #include "wg_tile.h"         // the tile constants WGP_TILE, WGP_KC, WGP_WAVES, WGP_GROUP and the packed layout
+#include "wg_train.h"        // WgKlLr: a member's learning-rate rule travels in its row of the member table
 
 #define WGP_MAX_LAYERS 5     // WG_POLICY_MAX_HIDDEN + the head
 #define WGP_MAX_IN 2048
@@ -120,8 +121,10 @@ struct WgPopMember {
     float *m, *v, *grad, *part, *spart, *advstat, *blocksq;   // the member's own wg_ppo buffers
     const int32_t* perm;       // [n_epochs][rows_m] GLOBAL row ids of the batch
     float* stats;              // [n_epochs][n_mb][WGT_NSTAT], or the wg_ppo's scratch record with stats_step = 0
+    float *lr_dev, *lr_slots;  // with a KL-adaptive rate (all members or none): the caller's rate word, the member's two slots
     float clip, vf_coef, ent_coef, max_norm;
     int32_t normalize, stats_step;
+    WgKlLr rule;               // ... and the member's rule (k_ppo_adam_kl_pop)
 };
 
 // What the heads of one member of a RECURRENT population read and write in k_ppo_grad_dh_pop (wg_lstm_ppo.hip fills the table): the

@@ -21,6 +21,7 @@
 #define WGT_G_MAX 512             // most workgroups per net
 #define WGT_PART_BYTES (256u << 20)   // most bytes of gradient partials (bounds g_max for very large nets)
 #define WGT_NSTAT 8               // floats of a wg_ppo_stats record
+#define WGT_STAT_KL 3             // ... of which approx_kl is this one (what the KL-adaptive rate reads)
 #define WGT_BLOCK 256             // threads of the element-wise kernels (reduce, sum of squares, Adam)
 // the actor's loss head, a compile-time choice of the gradient kernel's body: PPO's clipped surrogate (k_ppo_grad*), or the
 // supervised loss of k_bc_grad, whose spart[g] holds the sums of the rows' squared error / n_out, -logp(target) and absolute error /
@@ -65,6 +66,11 @@ inline bool wgt_pop_member(WgPopMember& M, const wg_ppo_hyper* hp, wg_ppo_stats*
     M.clip = hp[m].clip_range; M.vf_coef = hp[m].vf_coef; M.ent_coef = hp[m].ent_coef;
     M.normalize = hp[m].normalize_advantage != 0;
     return M.normalize;
+}
+
+// ... and what the row Adam's kernel reads holds of the member's KL-adaptive rate (wg_ppo_set_kl_lr; lr_dev null: none)
+inline void wgt_pop_member_kl(WgPopMember& M, const WgAdam& a) {
+    M.lr_dev = a.lr_dev; M.lr_slots = a.lr_slots; M.rule = a.rule;
 }
 
 struct wg_ppo_s {

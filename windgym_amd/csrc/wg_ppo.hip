@@ -633,6 +633,42 @@ __global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam_pop(const WgPopMember* _
              omb1, beta2, omb2, eps);
 }
 
+// The same step with the KL-adaptive rate (wg_train.h: wg_kl_lr_next, wg_kl_lr_words) — no launch of its own: EVERY block reads the
+// rate of the step before from *lr_in and the minibatch's approx_kl from *kl (null: the update's first minibatch, whose KL is
+// rounding noise — the rate stays) and forms the same new rate; block 0's first thread stores it to *lr_out (null: nothing to
+// store), a word no block reads in this launch.  step_size is wg_adam_scalars' expression on the rate read here.
+__device__ __forceinline__ float ppo_kl_lr(const float* lr_in, float* lr_out, const float* kl, const WgKlLr& rule, const bool writes) {
+    float lr = *lr_in;
+    if (kl) lr = wg_kl_lr_next(lr, *kl, rule);
+    if (writes && lr_out) *lr_out = lr;
+    return lr;
+}
+
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam_kl(float* __restrict__ params, const float* __restrict__ grad,
+                                                            float* __restrict__ m, float* __restrict__ v, const uint32_t n_flat,
+                                                            const float* __restrict__ blocksq, const uint32_t n_blocks,
+                                                            const float max_norm, const float* lr_in, float* lr_out, const float* kl,
+                                                            const WgKlLr rule, const double bc1, const float bc2_sqrt, const float omb1,
+                                                            const float beta2, const float omb2, const float eps) {
+    const float lr = ppo_kl_lr(lr_in, lr_out, kl, rule, blockIdx.x == 0 && threadIdx.x == 0);
+    ppo_adam(params, grad, m, v, n_flat, blocksq, n_blocks, max_norm, (float)((double)lr / bc1), bc2_sqrt, omb1, beta2, omb2, eps);
+}
+
+// (member m's words and rule are its row's; mb: the minibatch's ordinal in the update = its stats slot, last: the update's final one)
+struct WgPopAdamKl { double bc1[WGP_POP_MAX]; float bc2_sqrt[WGP_POP_MAX]; };
+__global__ __launch_bounds__(WGT_BLOCK) void k_ppo_adam_kl_pop(const WgPopMember* __restrict__ mt, const uint32_t n_flat,
+                                                                const uint32_t n_blocks, const WgPopAdamKl A, const int mb, const int last,
+                                                                const float omb1, const float beta2, const float omb2, const float eps) {
+    const WgPopMember* __restrict__ M = mt + blockIdx.y;
+    const float* lr_in;
+    float* lr_out;
+    wg_kl_lr_words(M->lr_dev, M->lr_slots, mb, last, &lr_in, &lr_out);
+    const float* kl = mb == 0 ? nullptr : M->stats + (size_t)mb * M->stats_step + WGT_STAT_KL;
+    const float lr = ppo_kl_lr(lr_in, lr_out, kl, M->rule, blockIdx.x == 0 && threadIdx.x == 0);
+    ppo_adam(M->params, M->grad, M->m, M->v, n_flat, M->blocksq, n_blocks, M->max_norm, (float)((double)lr / A.bc1[blockIdx.y]),
+             A.bc2_sqrt[blockIdx.y], omb1, beta2, omb2, eps);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -705,10 +741,37 @@ static size_t t_lds_map(const WgPolicyP& P, int R, WgPpoK* K) {
 
 // WgAdam (wg_train.h) and WgPpoGrad (wg_ppo.h): wg_internal.h states what each function does
 extern "C" int wg_adam_alloc_(WgDevMem* mem, WgAdam* a, uint32_t n_flat, const char* who) {
-    *a = {mem->device, n_flat, (n_flat + WGT_BLOCK - 1) / WGT_BLOCK, 0, nullptr, nullptr, nullptr};
+    *a = {mem->device, n_flat, (n_flat + WGT_BLOCK - 1) / WGT_BLOCK, 0, nullptr, nullptr, nullptr, nullptr, nullptr, {}};
     if (int rc = mem->alloc(who, &a->m, n_flat)) return rc;
     if (int rc = mem->alloc(who, &a->v, n_flat)) return rc;
     return mem->alloc(who, &a->blocksq, a->n_blocks, false);
+}
+
+extern "C" int wg_adam_set_kl_lr_(WgDevMem* mem, WgAdam* a, const char* who, const wg_kl_lr* rule, float* lr_dev) {
+    const std::string w = who;
+    if (!a || !mem) return wg_fail(WG_ERR_INVALID, w + ": null argument");
+    if (!rule && !lr_dev) {
+        a->lr_dev = nullptr;
+        return 0;
+    }
+    if (!rule) return wg_fail(WG_ERR_INVALID, w + ": rule is null (with lr_dev given; both null turn the rule off)");
+    if (!lr_dev) return wg_fail(WG_ERR_INVALID, w + ": lr_dev is null (with a rule given; both null turn the rule off)");
+    if (const char* bad = wg_kl_lr_refusal(rule->desired_kl, rule->factor, rule->lr_min, rule->lr_max)) return wg_fail(WG_ERR_INVALID, w + ": " + bad);
+    if (int rc = wg_use_device(a->device)) return rc;
+    if (int rc = wg_on_device(w + ": ", a->device, lr_dev, "lr_dev", ", the handle's device")) return rc;
+    float lr0 = 0.0f;
+    WG_HIPCHK(hipDeviceSynchronize());
+    WG_HIPCHK(hipMemcpy(&lr0, lr_dev, sizeof(float), hipMemcpyDeviceToHost));
+    if (!(lr0 >= rule->lr_min && lr0 <= rule->lr_max)) {
+        char says[128];
+        snprintf(says, sizeof(says), ": the starting rate *lr_dev = %g lies outside [lr_min, lr_max] = [%g, %g]", lr0, rule->lr_min, rule->lr_max);
+        return wg_fail(WG_ERR_INVALID, w + says);
+    }
+    if (!a->lr_slots)                                           // the first rule set on this handle: a handle that never takes one allocates nothing
+        if (int rc = mem->alloc(who, &a->lr_slots, 2, false)) return rc;
+    a->rule = wg_kl_lr_rule(rule->desired_kl, rule->factor, rule->lr_min, rule->lr_max);
+    a->lr_dev = lr_dev;
+    return 0;
 }
 
 // what get_state / set_state check before they copy: the arguments, the size, the device idle
@@ -741,6 +804,20 @@ extern "C" int wg_adam_apply_(WgAdam* a, float* params_dev, const float* grad_de
     hipLaunchKernelGGL(k_ppo_sumsq, dim3(a->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, a->n_flat, a->blocksq);
     hipLaunchKernelGGL(k_ppo_adam, dim3(a->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, a->m, a->v, a->n_flat,
                        a->blocksq, a->n_blocks, max_grad_norm, s.step_size, s.bc2_sqrt, (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_adam_apply_kl_(WgAdam* a, float* params_dev, const float* grad_dev, const float* stats_dev, int mb, int last,
+                                 float max_grad_norm, hipStream_t st) {
+    const WgAdamKlStep s = wg_adam_kl_scalars(++a->step);
+    const float* lr_in;
+    float* lr_out;
+    wg_kl_lr_words(a->lr_dev, a->lr_slots, mb, last, &lr_in, &lr_out);
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(a->n_blocks), dim3(WGT_BLOCK), 0, st, grad_dev, a->n_flat, a->blocksq);
+    hipLaunchKernelGGL(k_ppo_adam_kl, dim3(a->n_blocks), dim3(WGT_BLOCK), 0, st, params_dev, grad_dev, a->m, a->v, a->n_flat, a->blocksq,
+                       a->n_blocks, max_grad_norm, lr_in, lr_out, mb == 0 ? nullptr : stats_dev + WGT_STAT_KL, a->rule, s.bc1, s.bc2_sqrt,
+                       (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
     WG_HIPCHK(hipGetLastError());
     return 0;
 }
@@ -847,6 +924,13 @@ static int t_apply(wg_ppo o, float* params_dev, const float* grad_dev, float lr,
     return wg_policy_set_params(o->g.pol, params_dev, o->adam.n_flat, 1, (void*)st);
 }
 
+// ... of minibatch mb of an update under the handle's KL rule: the rate from device memory, stepped by the record at stats_dev
+static int t_apply_kl(wg_ppo o, float* params_dev, const float* grad_dev, const float* stats_dev, int mb, int last, float max_grad_norm,
+                      hipStream_t st) {
+    if (int rc = wg_adam_apply_kl_(&o->adam, params_dev, grad_dev, stats_dev, mb, last, max_grad_norm, st)) return rc;
+    return wg_policy_set_params(o->g.pol, params_dev, o->adam.n_flat, 1, (void*)st);
+}
+
 // wg_internal.h: the heads of a recurrent policy (wg_lstm_ppo.hip)
 extern "C" int wg_ppo_heads_grad_(WgPpoGrad* g, const float* mlp_params_dev, const float* h_pi, const float* h_vf, const float* raw,
                                   const float* logp, const float* adv, const float* ret, int n, const wg_ppo_hyper* hp, float* dh_pi,
@@ -881,6 +965,35 @@ extern "C" int wg_adam_apply_pop_(const WgPopMember* mt, int n_members, WgAdam* 
     hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat);
     hipLaunchKernelGGL(k_ppo_adam_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat, n_blocks, A, (float)(1.0 - ADAM_B1),
                        (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
+    WG_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int wg_pop_kl_lr_(const char* who, int n_members, WgAdam* const* adam, int* on) {
+    *on = adam[0]->lr_dev != nullptr;
+    for (int m = 1; m < n_members; ++m) {
+        const std::string w = std::string(who) + ": member " + std::to_string(m);
+        if ((adam[m]->lr_dev != nullptr) != (*on != 0))
+            return wg_fail(WG_ERR_INVALID, w + (*on ? " has no KL-adaptive rate set while member 0 has one"
+                                                    : " has a KL-adaptive rate set while member 0 has none") +
+                                             ": the members' launches run in lockstep, so every member is set (*_set_kl_lr) or none");
+        for (int k = 0; *on && k < m; ++k)
+            if (adam[k]->lr_dev == adam[m]->lr_dev) return wg_fail(WG_ERR_INVALID, w + ": its lr_dev is member " + std::to_string(k) + "'s");
+    }
+    return 0;
+}
+
+extern "C" int wg_adam_apply_kl_pop_(const WgPopMember* mt, int n_members, WgAdam* const* adam, int mb, int last, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_flat = adam[0]->n_flat, n_blocks = (n_flat + WGT_BLOCK - 1) / WGT_BLOCK;
+    WgPopAdamKl A = {};
+    for (int m = 0; m < n_members; ++m) {
+        const WgAdamKlStep s = wg_adam_kl_scalars(++adam[m]->step);
+        A.bc1[m] = s.bc1; A.bc2_sqrt[m] = s.bc2_sqrt;
+    }
+    hipLaunchKernelGGL(k_ppo_sumsq_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat);
+    hipLaunchKernelGGL(k_ppo_adam_kl_pop, dim3(n_blocks, n_members), dim3(WGT_BLOCK), 0, st, mt, n_flat, n_blocks, A, mb, last,
+                       (float)(1.0 - ADAM_B1), (float)ADAM_B2, (float)(1.0 - ADAM_B2), ADAM_EPS);
     WG_HIPCHK(hipGetLastError());
     return 0;
 }
@@ -945,11 +1058,18 @@ static int update_entry(const char* who, wg_ppo o, float* params_dev, const wg_p
     if (!(max_grad_norm > 0.0f)) return wg_fail(WG_ERR_INVALID, w + ": max_grad_norm must be > 0");
     if (int rc = t_use_device(w, o, params_dev, b)) return rc;
     if (int rc = wg_on_device(w + ": ", o->adam.device, perm_dev, "perm_dev", "")) return rc;
+    const bool kl = o->adam.lr_dev != nullptr;                  // wg_ppo_set_kl_lr: the rate is the handle's device word, `lr` is ignored
+    const int n_all = n_epochs * wg_n_minibatches(b->rows.n_rows, batch_size);
     return wg_each_minibatch(b->rows.n_rows, n_epochs, batch_size, [&](int mb, int64_t off, int n) {
         float* so = stats_out ? (float*)(stats_out + mb) : nullptr;
         if (int rc = t_grad(&o->g, params_dev, b, perm_dev + off, 0, n, hp, o->grad, so, (hipStream_t)stream)) return rc;
+        if (kl) return t_apply_kl(o, params_dev, o->grad, so ? so : o->g.stats, mb, mb == n_all - 1, max_grad_norm, (hipStream_t)stream);
         return t_apply(o, params_dev, o->grad, lr, max_grad_norm, (hipStream_t)stream);
     });
+}
+
+extern "C" int wg_ppo_set_kl_lr(wg_ppo o, const wg_kl_lr* rule, float* lr_dev) {
+    return wg_adam_set_kl_lr_(o ? &o->mem : nullptr, o ? &o->adam : nullptr, "wg_ppo_set_kl_lr", rule, lr_dev);
 }
 
 extern "C" int wg_ppo_update_shared(wg_ppo o, float* params_dev, const wg_ppo_batch_shared* b, const int32_t* perm_dev, int n_epochs,
@@ -1120,11 +1240,14 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
     const int n_mb = wg_n_minibatches(rows_m, batch_size);
     WgPopMember tab[WGP_POP_MAX] = {};
     WgAdam* adam[WGP_POP_MAX];
+    for (int m = 0; m < P; ++m) adam[m] = &q->opt[m]->adam;
+    int kl = 0;                                                 // the members' rates are their device words (every member or none), `lr` is ignored
+    if (int rc = wg_pop_kl_lr_("wg_pop_update", P, adam, &kl)) return rc;
     bool any_norm = false;
     for (int m = 0; m < P; ++m) {
         wg_ppo_s* o = q->opt[m];
         WgPopMember& M = tab[m];
-        adam[m] = &o->adam;
+        wgt_pop_member_kl(M, o->adam);
         M.packed = o->g.pol->w.packed; M.params = params_dev[m];
         M.m = o->adam.m; M.v = o->adam.v; M.grad = o->grad; M.part = o->g.part; M.spart = o->g.spart; M.advstat = o->g.advstat; M.blocksq = o->adam.blocksq;
         M.perm = perm_dev + (size_t)m * n_epochs * rows_m;
@@ -1144,7 +1267,8 @@ extern "C" int wg_pop_update(wg_pop q, float* const* params_dev, const wg_ppo_ba
         a.first = 0; a.n_total = b->n_rows; a.n = n; a.G = G;
         hipLaunchKernelGGL(k_ppo_grad_pop, dim3(G, 2, P), dim3(WGT_WAVES * 64), g0->lds_bytes, st, PP, g0->K, a, mt, off);
         hipLaunchKernelGGL(k_ppo_reduce_pop, dim3(g0->n_blocks, P), dim3(WGT_BLOCK), 0, st, PP, mt, G, n, mb);
-        if (int rc = wg_adam_apply_pop_(mt, P, adam, lr, stream)) return rc;
+        if (int rc = kl ? wg_adam_apply_kl_pop_(mt, P, adam, mb, mb == n_epochs * n_mb - 1, stream) : wg_adam_apply_pop_(mt, P, adam, lr, stream))
+            return rc;
         wg_policy_pack_pop_(&PP, mt, P, stream);
         WG_HIPCHK(hipGetLastError());
         return 0;

@@ -18,7 +18,7 @@ import numpy as np
 
 from .binding import Handle
 from .policy import act_buffers, device_tensor, refuse_recurrent, refuse_table_agent
-from .ppo import PPO, PPOOptimizer, _schedule, check_batch_size, check_hyper, learn_loop, write_checkpoint
+from .ppo import PPO, PPOOptimizer, _schedule, check_adaptive_lr, check_batch_size, check_hyper, learn_loop, write_checkpoint
 
 POP_MAX = 16            # WG_POP_MAX
 PER_MEMBER = ("gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "learning_rate", "normalize_advantage")
@@ -33,6 +33,15 @@ def broadcast_hyper(name, value, n_members):
             raise ValueError(f"{name}: {len(value)} values for {n_members} members (a scalar, or one value per member)")
         return list(value)
     return [value] * n_members
+
+
+def member_adaptive_lr(adaptive_lr, learning_rate, n_members):
+    """A population's ``adaptive_lr`` — a dict whose values are scalars for all members or lists of one value per member — -> the
+    members' rules, each checked against the member's starting rate as :func:`~windgym_amd.ppo.check_adaptive_lr` checks one."""
+    if not isinstance(adaptive_lr, dict):
+        raise ValueError("adaptive_lr must be a dict(desired_kl=..., [factor, lr_min, lr_max]) or None")
+    per = {k: broadcast_hyper(f"adaptive_lr: {k}", v, n_members) for k, v in adaptive_lr.items()}
+    return [check_adaptive_lr({k: v[m] for k, v in per.items()}, learning_rate[m], f"member {m}: ") for m in range(n_members)]
 
 
 def global_rows(local, member, n_envs, n_envs_member):
@@ -163,7 +172,10 @@ class PPOPopulation:
     seeds) or a list of :class:`MlpPolicy` objects of one architecture.  ``n_steps``, ``n_epochs`` and ``batch_size`` (in rows of
     ONE member; default a quarter of ``n_steps * Bm``) are shared — the members' launches run in lockstep; ``gamma``,
     ``gae_lambda``, ``clip_range``, ``ent_coef``, ``vf_coef``, ``max_grad_norm``, ``learning_rate`` (schedules included),
-    ``normalize_advantage`` and ``seed`` are a scalar for all or one value per member.  A member's ``seed`` is what ``PPO``'s is:
+    ``normalize_advantage`` and ``seed`` are a scalar for all or one value per member; so are the values of ``adaptive_lr``
+    (``PPO``'s KL-adaptive learning rate: every member then has a rate of its own on the device, ``self.lr`` float32 ``[P]``,
+    steered by ITS minibatches' ``approx_kl`` toward ITS ``desired_kl`` — a seed or ``gamma`` sweep needs no second sweep over
+    ``learning_rate``; ``learning_rate`` holds the starting rates).  A member's ``seed`` is what ``PPO``'s is:
     initial weights and minibatch permutations; action noise follows ``venv.rollout``'s rule (the env's base seed, its running
     count of policy steps, the global index of each env).
 
@@ -198,7 +210,7 @@ class PPOPopulation:
 
     def __init__(self, policy, venv, n_members=None, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95,
                  clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True,
-                 policy_kwargs=None, seed=None, curriculum=None, normalize=None):
+                 policy_kwargs=None, seed=None, curriculum=None, normalize=None, adaptive_lr=None):
         self._check_policy(policy)
         if curriculum is not None:
             raise NotImplementedError("a curriculum for a population is not implemented (use PPO(..., curriculum=...))")
@@ -227,6 +239,8 @@ class PPOPopulation:
         for k in PER_MEMBER:
             setattr(self, k, broadcast_hyper(k, hyper[k], P))
         self.seed = broadcast_hyper("seed", seed, P)
+        self.adaptive_lr = None if adaptive_lr is None else member_adaptive_lr(adaptive_lr, self.learning_rate, P)
+        self.lr = None
         for m in range(P):
             check_hyper(n_steps, n_epochs, self.gamma[m], self.gae_lambda[m], self.max_grad_norm[m], f"member {m}: ")
         n_steps, n_epochs = int(n_steps), int(n_epochs)
@@ -259,6 +273,10 @@ class PPOPopulation:
         self._ep_return = t.zeros(B, dtype=t.float64, device=dev)          # running return of every env's open episode (for the log)
         self.num_timesteps, self.iteration, self.log = 0, 0, []
         self.n_env_steps = n_steps * Bm
+        if self.adaptive_lr is not None:                                   # the members' rates move to the device: ``lr`` float32 [P]
+            self.lr = t.tensor([float(x) for x in self.learning_rate], dtype=t.float32, device=dev)
+            for m, o in enumerate(self.opts):
+                o.set_kl_lr(self.adaptive_lr[m], self.lr[m:m + 1])
 
     # -- training -------------------------------------------------------------------------------------------------
     def _floats(self, xs):
@@ -333,7 +351,12 @@ class PPOPopulation:
         from .binding import PPO_STATS
         t = self.torch
         self.venv.batch.metrics(reset_after=True)                 # (whole-batch sums, not used: consumed as PPO.learn does)
-        host = t.cat([stats.double().mean(dim=(1, 2)), self._member_metrics(out)], dim=1).cpu().numpy()   # the one copy
+        cols = [stats.double().mean(dim=(1, 2)), self._member_metrics(out)]
+        if self.lr is not None:                                   # the members' rates after the iteration's last minibatch
+            cols.append(self.lr.double().view(-1, 1))
+        host = t.cat(cols, dim=1).cpu().numpy()                   # the one copy
+        if self.lr is not None:
+            lr = host[:, -1].tolist()
         fps = fps()
         recs = []
         for m in range(self.n_members):
@@ -355,9 +378,15 @@ class PPOPopulation:
     def save(self, directory):
         """``directory/member_00.zip`` ...: each the single trainer's checkpoint (see :meth:`PPO.save`) of the member's run on its shard."""
         os.makedirs(directory, exist_ok=True)
-        return [write_checkpoint(os.path.join(directory, f"member_{m:02d}.zip"), self.members[m], self.opts[m], self._gens[m],
-                                 self.member_hyper(m), self.seed[m], self.num_timesteps, self.iteration, [recs[m] for recs in self.log],
-                                 None, self.venv._policy_steps, tensors=self._tensors(m)) for m in range(self.n_members)]
+        paths = []
+        for m in range(self.n_members):
+            tensors, extra = self._tensors(m), None
+            if self.adaptive_lr is not None:          # the member's rule and rate, as PPO.save stores them
+                tensors, extra = dict(tensors or {}, **{"learning_rate.npy": self.lr[m:m + 1]}), dict(adaptive_lr=self.adaptive_lr[m])
+            paths.append(write_checkpoint(os.path.join(directory, f"member_{m:02d}.zip"), self.members[m], self.opts[m], self._gens[m],
+                                          self.member_hyper(m), self.seed[m], self.num_timesteps, self.iteration,
+                                          [recs[m] for recs in self.log], None, self.venv._policy_steps, tensors=tensors, extra=extra))
+        return paths
 
     def close(self):
         self.population.close()

@@ -25,6 +25,40 @@ HYPER = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range
          "learning_rate", "normalize_advantage")
 
 
+ADAPTIVE_LR = dict(factor=1.5, lr_min=1e-5, lr_max=1e-2)      # rsl_rl's constants; desired_kl has no default
+
+
+def check_adaptive_lr(adaptive_lr, learning_rate, who=""):
+    """``adaptive_lr`` as the trainers take it — a dict of ``desired_kl`` and, optionally, ``factor`` / ``lr_min`` / ``lr_max`` — ->
+    the four arguments of wg_kl_lr as Python floats, or ``ValueError`` naming the argument (what ``wg_ppo_set_kl_lr`` refuses, decided
+    without a device): ``desired_kl`` not > 0 or not finite, ``factor`` < 1 or not finite, ``lr_min`` not > 0, ``lr_min > lr_max``, a
+    ``learning_rate`` — the STARTING rate — that is a schedule or lies outside ``[lr_min, lr_max]``.  All comparisons are on the
+    float32 values the device holds.  ``who`` (``"member 3: "``) prefixes the messages."""
+    if not isinstance(adaptive_lr, dict):
+        raise ValueError(f"{who}adaptive_lr must be a dict(desired_kl=..., [factor, lr_min, lr_max]) or None")
+    unknown = sorted(set(adaptive_lr) - {"desired_kl", *ADAPTIVE_LR})
+    if unknown:
+        raise ValueError(f"{who}adaptive_lr: unknown keys {unknown}")
+    if "desired_kl" not in adaptive_lr:
+        raise ValueError(f"{who}adaptive_lr needs desired_kl")
+    if callable(learning_rate):
+        raise ValueError(f"{who}learning_rate is a schedule: with adaptive_lr it is the STARTING rate and must be a number (a schedule "
+                         "and a feedback rule would fight)")
+    r = {k: np.float32(v) for k, v in dict(ADAPTIVE_LR, **adaptive_lr).items()}
+    if not (r["desired_kl"] > 0 and np.isfinite(r["desired_kl"])):
+        raise ValueError(f"{who}adaptive_lr: desired_kl must be > 0 and finite")
+    if not (r["factor"] >= 1 and np.isfinite(r["factor"])):
+        raise ValueError(f"{who}adaptive_lr: factor must be >= 1 and finite")
+    if not r["lr_min"] > 0:
+        raise ValueError(f"{who}adaptive_lr: lr_min must be > 0")
+    if not r["lr_min"] <= r["lr_max"]:
+        raise ValueError(f"{who}adaptive_lr: lr_min must be <= lr_max")
+    if not r["lr_min"] <= np.float32(learning_rate) <= r["lr_max"]:
+        raise ValueError(f"{who}learning_rate = {float(learning_rate):g}, the starting rate of adaptive_lr, lies outside [lr_min, lr_max] = "
+                         f"[{float(r['lr_min']):g}, {float(r['lr_max']):g}]")
+    return {k: float(r[k]) for k in ("desired_kl", "factor", "lr_min", "lr_max")}
+
+
 def sb3_orthogonal_init(desc, seed):
     """{SB3 name: float32 array}: stable-baselines3's ``ortho_init`` — orthogonal weights with gain sqrt(2) for the hidden
     layers, 0.01 for the action head, 1 for the value head, zero biases and ``log_std`` — drawn from a seeded CPU generator
@@ -113,6 +147,21 @@ class HandleOptimizer(Handle):
         g = self.grad_buf if grad is None else grad
         self._call("apply", self._h, self.policy.params.data_ptr(), g.data_ptr(), float(learning_rate), float(max_grad_norm),
                    self.policy._stream())
+
+    def set_kl_lr(self, rule, lr):
+        """``<prefix>_set_kl_lr``: from now on ``update`` ignores its ``learning_rate``, reads the rate from ``lr`` — ONE float32 CUDA
+        element, the starting rate, updated in place and kept alive here — and steps it by every minibatch's ``approx_kl`` but the
+        update's first (``rule``: the dict of :func:`check_adaptive_lr`).  ``rule = lr = None`` turns that off again."""
+        from .binding import CKlLr
+        if rule is None and lr is None:
+            self._call("set_kl_lr", self._h, None, None)
+            self.lr = None
+            return
+        if lr is None or not (device_tensor(lr, self.torch.float32) and lr.numel() == 1):
+            raise ValueError("lr must be a contiguous float32 CUDA tensor of one element")
+        c = None if rule is None else CKlLr(*[float(rule[k]) for k in ("desired_kl", "factor", "lr_min", "lr_max")])
+        self._call("set_kl_lr", self._h, None if c is None else C.byref(c), lr.data_ptr())
+        self.lr = lr
 
     def state(self):
         """(Adam's m then v as one float32 numpy vector ``[2 n_params]``, step count)."""
@@ -377,16 +426,18 @@ class Trainer:
     subclass sets ``policy`` / ``venv`` / ``torch`` / ``opt`` / ``n_rows`` / ``n_env_steps`` / ``batch_size`` and has ``collect`` and
     ``train``; ``curriculum`` / ``normalize`` / ``critic`` stay ``None`` where a trainer offers none."""
 
-    curriculum = normalize = critic = None
+    curriculum = normalize = critic = adaptive_lr = lr = None
 
     def _setup(self, n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
-               normalize_advantage, seed, target_kl, clip_range_vf, use_sde):
+               normalize_advantage, seed, target_kl, clip_range_vf, use_sde, adaptive_lr=None):
         for name, v in (("target_kl", target_kl), ("clip_range_vf", clip_range_vf)):
             if v is not None:
                 raise NotImplementedError(f"{name} is not implemented")
         if use_sde:
             raise NotImplementedError("use_sde (state-dependent exploration) is not implemented")
         check_hyper(n_steps, n_epochs, gamma, gae_lambda, max_grad_norm)
+        if adaptive_lr is not None:
+            self.adaptive_lr = check_adaptive_lr(adaptive_lr, learning_rate)
         self._lr, self._clip = _schedule(learning_rate, "learning_rate"), _schedule(clip_range, "clip_range")
         self.n_steps, self.n_epochs = int(n_steps), int(n_epochs)
         self.gamma, self.gae_lambda, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(ent_coef), float(vf_coef)
@@ -404,6 +455,9 @@ class Trainer:
         self._adv = t.zeros(adv_shape, dtype=t.float32, device=dev)
         self._ret = t.zeros_like(self._adv)
         self._stats = t.zeros((self.n_epochs, n_minibatches, 8), dtype=t.float32, device=dev)
+        if self.adaptive_lr is not None:                          # the rate moves to the device: ``lr`` float32 [1], starting at learning_rate
+            self.lr = t.full((1,), float(self.learning_rate), dtype=t.float32, device=dev)
+            self.opt.set_kl_lr(self.adaptive_lr, self.lr)
 
     def learn(self, total_timesteps, callback=None, log_interval=1, reset_num_timesteps=True):
         """Iterations of rollout + update until ``total_timesteps`` env steps were collected (``reset_num_timesteps=False``:
@@ -423,8 +477,12 @@ class Trainer:
             parts += [out["curriculum_weight"].mean().reshape(1), out["yaw_diff"].double().mean().reshape(1)]
         if self.normalize is not None:
             parts += [out["reward"].double().mean().reshape(1)]
+        if self.lr is not None:
+            parts += [self.lr.double()]
         vec = t.cat(parts)
         host = vec.cpu().numpy()                                  # the iteration's one device-to-host copy
+        if self.lr is not None:                                   # the rate after the iteration's last minibatch (float32, exact in a double)
+            lr, host = float(host[-1]), host[:-1]
         rec = dict(zip(PPO_STATS, host[:8].tolist()))
         rec["explained_variance"] = float(host[8])
         m = derive(host[9:9 + len(METRIC_NAMES)])
@@ -444,13 +502,18 @@ class Trainer:
 
     def save(self, path, tensors=None):
         """Everything a bit-identical resume needs except the env itself (the class docstring states the format)."""
+        extra = None
+        if self.adaptive_lr is not None:
+            tensors, extra = dict(tensors or {}, **{"learning_rate.npy": self.lr}), dict(adaptive_lr=self.adaptive_lr)
         return write_checkpoint(path, self.policy, self.opt, self._gen, {k: getattr(self, k) for k in HYPER}, self.seed,
                                 self.num_timesteps, self.iteration, self.log, self.critic, self.venv._policy_steps, self.curriculum,
-                                self.normalize, tensors)
+                                self.normalize, tensors, extra)
 
     def _restore(self, meta, members):
         """Adam's state, the generator and the counters of a checkpoint (:func:`read_checkpoint`)."""
         self.opt.load_state(members["adam_state.npy"], meta["adam_step"])
+        if self.lr is not None:
+            self.lr.copy_(self.torch.from_numpy(np.asarray(members["learning_rate.npy"], np.float32).reshape(1)))
         self._gen.set_state(self.torch.from_numpy(members["generator_state.npy"]))
         self.num_timesteps, self.iteration, self.log = int(meta["num_timesteps"]), int(meta["iteration"]), list(meta["log"])
         self.venv._policy_steps = int(meta["env_policy_steps"])
@@ -480,6 +543,16 @@ class PPO(Trainer):
     ``learning_rate`` and ``clip_range`` may be callables of ``progress_remaining`` (1 -> 0), evaluated on the host once per
     iteration.  Not implemented (``NotImplementedError``): ``target_kl``, ``clip_range_vf``, ``use_sde``.
 
+    ``adaptive_lr``: ``dict(desired_kl=..., factor=1.5, lr_min=1e-5, lr_max=1e-2)`` — the KL-adaptive learning rate of rsl_rl /
+    rl_games, on the device (wg_ppo_set_kl_lr): ``learning_rate`` is then the STARTING rate and must be a number (a schedule with it is
+    a ``ValueError``), the rate lives in ``self.lr`` (a float32 CUDA tensor ``[1]``) and every minibatch of an update but the first
+    multiplies it by ``1 / factor`` when its ``approx_kl > 2 desired_kl`` and by ``factor`` when ``0 < approx_kl < desired_kl / 2``,
+    clamped to ``[lr_min, lr_max]``, before its optimiser step — inside the Adam kernel, with no launch and no host round trip added
+    (the first minibatch still has the rollout's parameters: its KL is rounding noise).  The log's ``learning_rate`` is then the rate
+    after the iteration's last minibatch, read in the record's one copy; ``save`` stores the arguments under the JSON key
+    ``adaptive_lr`` and the rate as ``learning_rate.npy``.  It works on both env kinds and both critic modes and composes with
+    ``curriculum`` / ``normalize``, which act before the update.  ``None`` changes nothing.
+
     ``curriculum``: a ``curriculum.YawCurriculum`` of this env, or a dict of its arguments — the reference's
     examples/curriculum.py: rollouts come from ``curriculum.rollout`` (one host synchronisation per rollout, see there; none with
     ``targets=`` a ``yaw_table.YawTable`` among the arguments, which ``save`` then stores as ``curriculum_table.npz``), GAE and the
@@ -500,11 +573,12 @@ class PPO(Trainer):
 
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
-                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None, normalize=None):
+                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, critic=None, curriculum=None, normalize=None,
+                 adaptive_lr=None):
         refuse_recurrent(policy, "PPO")
         refuse_table_agent(policy, "PPO")
         self._setup(n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
-                    normalize_advantage, seed, target_kl, clip_range_vf, use_sde)
+                    normalize_advantage, seed, target_kl, clip_range_vf, use_sde, adaptive_lr)
         n_steps = self.n_steps
         if normalize is not None:
             from .normalize import VecNormalize, check_env
@@ -622,7 +696,7 @@ class PPO(Trainer):
             from .yaw_table import YawTable
             meta["curriculum"] = dict(meta["curriculum"], targets=YawTable.from_bytes(members["curriculum_table.npz"], venv))
         self = cls(pol, venv, seed=meta["seed"], critic=meta.get("critic"), curriculum=meta.get("curriculum"),
-                   normalize=meta.get("normalize"), **meta["hyper"])   # (no key: written before there was one)
+                   normalize=meta.get("normalize"), adaptive_lr=meta.get("adaptive_lr"), **meta["hyper"])   # (no key: written before there was one)
         if self.normalize is not None and "normalize_state.bin" in members:
             self.normalize.load_state(members["normalize_state.bin"])
         if self.curriculum is not None and "curriculum_state.bin" in members:

@@ -114,7 +114,8 @@ class RecurrentPPOPopulation(PPOPopulation):
     are built from ``policy_kwargs`` as ``RecurrentPPO`` builds one, each from its member's seed) or a list of :class:`MlpLstmPolicy`
     objects of one architecture.  ``batch_size`` counts env steps of ONE member, must be a multiple of ``n_steps`` (a minibatch is a
     set of envs with all their steps) and defaults to ``n_steps * ceil(Bm / 4)``.  Per epoch and member one permutation of the member's
-    ``Bm`` envs is drawn from the member's generator and mapped to the batch's env ids (:func:`global_envs`).
+    ``Bm`` envs is drawn from the member's generator and mapped to the batch's env ids (:func:`global_envs`).  ``adaptive_lr`` is
+    ``PPOPopulation``'s: a KL-adaptive learning rate per member on the device (wg_lstm_ppo_set_kl_lr on every member's handle).
 
     ``learn``, ``train``, ``log`` and ``members`` are ``PPOPopulation``'s; stated here are its seven hooks: ``_check_policy``,
     ``_minibatches``, ``_build_member``, ``_open``, ``_global`` (one permutation of the member's ``Bm`` envs per epoch), ``_batch``

@@ -172,7 +172,9 @@ class RecurrentPPO(Trainer):
     The LSTM state of the (policy, env) pair carries from rollout to rollout, as ``venv.rollout`` keeps it.  ``predict`` takes
     ``state`` / ``episode_start`` (sb3-contrib's protocol).  Refused by name: a non-recurrent policy (``ValueError`` pointing to
     ``PPO``), a ``WindFarmVecEnvMulti``, ``target_kl``, ``clip_range_vf``, ``use_sde`` (``NotImplementedError``).  A curriculum and
-    ``VecNormalize`` around a recurrent trainer are not offered.
+    ``VecNormalize`` around a recurrent trainer are not offered.  ``adaptive_lr`` is ``PPO``'s (the KL-adaptive learning rate on the
+    device, here wg_lstm_ppo_set_kl_lr: ``learning_rate`` the starting rate, ``self.lr`` the device float, the rule applied before
+    every optimiser step of an update but the first).
 
     ``save`` writes ``PPO.save``'s zip — ``policy.pth`` under sb3-contrib's names, which ``MlpLstmPolicy.from_sb3_zip`` reads back,
     Adam's state, the generator and the counters — plus the pair's LSTM state (``lstm_state.npy``) and the pending episode starts
@@ -180,9 +182,9 @@ class RecurrentPPO(Trainer):
 
     def __init__(self, policy, venv, n_steps=128, batch_size=None, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, learning_rate=3e-4, normalize_advantage=True, policy_kwargs=None,
-                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False):
+                 seed=None, target_kl=None, clip_range_vf=None, use_sde=False, adaptive_lr=None):
         self._setup(n_steps, n_epochs, gamma, gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm, learning_rate,
-                    normalize_advantage, seed, target_kl, clip_range_vf, use_sde)
+                    normalize_advantage, seed, target_kl, clip_range_vf, use_sde, adaptive_lr)
         if getattr(venv, "possible_agents", None) is not None:
             raise NotImplementedError("RecurrentPPO on a WindFarmVecEnvMulti (a recurrent policy shared by the turbines) is not implemented")
         if isinstance(policy, str):
@@ -252,7 +254,7 @@ class RecurrentPPO(Trainer):
     def save(self, path):
         """Everything a bit-identical resume needs except the env itself (the class docstring)."""
         ent = self._pair()
-        return super().save(path, {"lstm_state.npy": ent[1], "episode_start.npy": ent[2]})
+        return super().save(path, {"lstm_state.npy": ent[1], "episode_start.npy": ent[2]})      # (+ the adaptive rate, where there is one)
 
     @classmethod
     def load(cls, path, venv, learning_rate=None, clip_range=None, device=None):
@@ -268,7 +270,7 @@ class RecurrentPPO(Trainer):
         pol = MlpLstmPolicy.from_sb3_zip(path, activation=meta["desc"]["activation"], device=venv.batch.device.index if device is None else device,
                                          seed=meta["policy_seed"])
         pol.counter = int(meta["policy_counter"])
-        self = cls(pol, venv, seed=meta["seed"], **meta["hyper"])
+        self = cls(pol, venv, seed=meta["seed"], adaptive_lr=meta.get("adaptive_lr"), **meta["hyper"])
         self._restore(meta, members)
         ent = self._pair()
         ent[1].copy_(torch.from_numpy(members["lstm_state.npy"]))
