@@ -1,8 +1,9 @@
 """The task rules of the environment on every step path: how an action moves the yaws (ActionMethod yaw / wind), how the baseline
 farm's controller moves its yaws (BaseController Local / Global), the reward (Power_reward Baseline / Power_avg / None / Power_diff,
 Power_avg, Power_scaling) and the action penalty (action_penalty, Change / Total, the `>= 0.001` switch).  The device code states
-them more than once (wg_flow.hip, wg_env.hip, wg_envb.hip: action rule and base controller; k_glue and lean_step: reward head and
-penalty sum, lean_step unfused and as the tail of k_flow_env / k_flow_envb), and tests/variant_census.py fixes them at env1_config's.
+them once, in csrc/wg_rules.h (tests/test_rules_host.py), and calls them on every step path (wg_flow.hip, wg_env.hip, wg_envb.hip:
+action rule and base controller; k_glue and lean_step: reward head and penalty sum, lean_step unfused and as the tail of k_flow_env /
+k_flow_envb; the reward's switch over Power_reward stays in each glue), and tests/variant_census.py fixes them at env1_config's.
 This table varies them: twelve step paths (PATHS, named by what the plan selects) times four rule sets (SETS), and a few extra
 cases at the sizes where the glue takes another branch.  tests/test_rule_cases.py pins coverage, preconditions and the
 reference-side controls on the CPU; tests/test_gpu_rule_cases.py runs every case by value against the oracle."""

@@ -17,6 +17,7 @@
 
 #include "../../include/windgym_hip.h"
 #include "wg_host.h"
+#include "wg_rules.h"
 #include "wg_yaw_table.h"
 
 namespace {
@@ -44,22 +45,6 @@ struct CurHeader {
 };
 const uint32_t CUR_MAGIC = 0x52554357u;      // "WCUR"
 
-// WindFarmEnv._adjust_yaws (Wind_Farm_Env.py:822-864) in float32, as the step kernels evaluate it (wg_flow.hip, wg_env.hip,
-// wg_envb.hip): the yaw an actuation step leaves, from the yaw before it and the action
-__device__ __forceinline__ float cur_adjust_yaw(float yaw, const float a, const CurP& p) {
-    if (p.action_method == WG_ACT_YAW) {
-        yaw = fminf(fmaxf(yaw + a * p.yaw_step, p.yaw_min), p.yaw_max);
-    } else {
-        float tf = a + 1.0f;
-        tf = tf * 0.5f;
-        tf = tf * (p.yaw_max - p.yaw_min);
-        tf = tf + p.yaw_min;
-        const float ny = fminf(fmaxf(tf, yaw - p.yaw_step), yaw + p.yaw_step);
-        yaw = fminf(fmaxf(ny, p.yaw_min), p.yaw_max);
-    }
-    return yaw;
-}
-
 __global__ __launch_bounds__(64) void k_curriculum(const CurP p, const CurState s, int* __restrict__ err, const float* __restrict__ yaw0,
                                                    const float* __restrict__ actions, const float* __restrict__ yaw_after,
                                                    const uint8_t* __restrict__ truncated, const int32_t* __restrict__ ep_row,
@@ -83,7 +68,7 @@ __global__ __launch_bounds__(64) void k_curriculum(const CurP p, const CurState 
         double d = 0.0, csum = 0.0;
         long long dosc = 0;
         for (int i = 0; i < N; ++i) {
-            const float yf = cur_adjust_yaw(prev[i], act[i], p);
+            const float yf = wg_rule_adjust_yaw(p.action_method, prev[i], act[i], p.yaw_min, p.yaw_max, p.yaw_step);      // the step kernels' rule
             if (yaw_out) yaw_out[row * N + i] = yf;
             const double y = (double)yf;
             d += fabs(y - g[i]);

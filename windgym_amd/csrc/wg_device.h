@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wg_rules.h"
 #include "wg_state.h"
 
 #define WG_PI_D 3.14159265358979323846

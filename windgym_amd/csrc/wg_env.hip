@@ -331,9 +331,8 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 full_barrier<64>();
                 load_state();
                 const int fill_max = F == 2 ? max(gp.fill_a, gp.fill_b) : gp.fill_a;
-                const int inc = 1 + (gp.extra_inc ? 1 : 0);
                 const int tm = WPE == 2 ? ki->d.ctx[e * 2 + env_live].time_max : __shfl(time_max_c, env_live * F * N, 64);
-                const long total = (long)((tm + inc - 1) / inc) + 1;
+                const long total = wg_rule_episode_steps(tm, gp.extra_inc);
                 const int dev0 = __shfl(dev_rem, WPE == 2 ? 0 : (env_live ^ 1) * F * N, 64);
                 // (the per-context share, overwritten by the per-farm one below: dead, yet without it the compiler schedules every
                 // instantiation differently — other SGPR spill counts, the pass-wave kernels 41 instructions shorter.  It stays
@@ -347,8 +346,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 // after the agent farm's — below one flow step per two env steps the two never step in the same launch, and a wave
                 // carries 2 F + 1 farm steps where the per-context plan (WgEnv::shadow_iters, ignored here) gave it 2 F or 3 F:
                 // the launch lasts as long as its heaviest wave.
-                const int inc = k0->p.env_inc;
-                const long total = (long)((env_time_max_live + inc - 1) / inc) + 1;
+                const long total = wg_rule_episode_steps_inc(env_time_max_live, k0->p.env_inc);
                 budget = role_dev ? wg_shadow_share(dev_rem + k0->p.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u) : 0;
                 plan_left = total - env_steps_done;
             }
@@ -438,17 +436,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         yaw = l_yaw; tu = l_u; tti = l_ti; oyaw = l_yaw;
         // WindFarmEnv._adjust_yaws (Wind_Farm_Env.py:822-864), float32 like numpy evaluates it on a float32 action
         if (role_live && farm == 0 && valid) {
-            const float a = l_act, ymin = k1->p.yaw_min, ymax = k1->p.yaw_max, ystep = k1->p.yaw_step;
-            if (k1->p.action_method == WG_ACT_YAW) {
-                yaw = fminf(fmaxf(yaw + a * ystep, ymin), ymax);
-            } else {
-                float tf = a + 1.0f;
-                tf = tf * 0.5f;
-                tf = tf * (ymax - ymin);
-                tf = tf + ymin;
-                const float ny = fminf(fmaxf(tf, yaw - ystep), yaw + ystep);
-                yaw = fminf(fmaxf(ny, ymin), ymax);
-            }
+            yaw = wg_rule_adjust_yaw(k1->p.action_method, yaw, l_act, k1->p.yaw_min, k1->p.yaw_max, k1->p.yaw_step);
         }
     }
     float tpow = 0.f, tct = 0.f, cg = 1.f;
@@ -522,12 +510,9 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 const float ystep = kr->p.yaw_step;
                 if (kr->p.base_controller == WG_CTRL_LOCAL) {
                     // (steady inflow: v == 0 exactly — the deficits only act on u — so atan(v / u) = +-0)
-                    const float off = 0.f - yaw;
-                    const float sgn = (float)((off > 0.f) - (off < 0.f));
-                    yaw = yaw + sgn * fminf(fabsf(off), ystep);
+                    yaw = wg_rule_ctrl_local(yaw, 0.f, ystep);
                 } else {
-                    const float sgn = (float)((yaw > 0.f) - (yaw < 0.f));
-                    yaw = yaw - sgn * fminf(fabsf(yaw), ystep);
+                    yaw = wg_rule_ctrl_global(yaw, ystep);
                 }
             }
 

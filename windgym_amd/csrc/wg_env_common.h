@@ -179,8 +179,7 @@ struct EnvFlowOut {          // what the flow part hands to the glue tail of k_s
 __device__ __forceinline__ void env_bg_plan(const EnvKArgsPtr kb, const int work, const EnvFlowOut& fo, const int e) {
     const int steps_done = fo.steps_done + 1, time_max = fo.time_max_live;      // (as the glue sees them: from the prologue's copy —
                                                                               // the live wave may have rewritten the header by now)
-    const int inc = 1 + (kb->gp.extra_inc ? 1 : 0);
-    const long total = (long)((time_max + inc - 1) / inc) + 1;
+    const long total = wg_rule_episode_steps(time_max, kb->gp.extra_inc);
     kb->d.env_rw[e].shadow_iters = work == 0 ? 0 : wg_shadow_share(work, total - steps_done, steps_done, e);
 }
 

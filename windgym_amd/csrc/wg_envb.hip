@@ -339,13 +339,11 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
                 }
                 load_state();
                 const int tm = WPE >= 2 ? ki->d.ctx[e * 2 + env_live].time_max : __shfl(time_max_c, env_live * F, 64);
-                const int inc = 1 + (gp.extra_inc ? 1 : 0);
-                const long total = (long)((tm + inc - 1) / inc) + 1;
+                const long total = wg_rule_episode_steps(tm, gp.extra_inc);
                 budget = wg_shadow_share(dev_rem + gp.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u);
             } else {
                 // the background episode's share of this step, planned per farm half a dither period apart (env_flow)
-                const int inc = k0->p.env_inc;
-                const long total = (long)((env_time_max_live + inc - 1) / inc) + 1;
+                const long total = wg_rule_episode_steps_inc(env_time_max_live, k0->p.env_inc);
                 budget = role_dev ? wg_shadow_share(dev_rem + k0->p.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u) : 0;
             }
         } else {
@@ -410,17 +408,7 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
         yaw = l_yaw; tu = l_u; tv = l_v; tw = l_w; tti = l_ti; oyaw = l_yaw; mvl_bits = l_bnd.w;
         // WindFarmEnv._adjust_yaws (Wind_Farm_Env.py:822-864), float32 like numpy evaluates it on a float32 action
         if (role_live && farm == 0 && valid) {
-            const float a = l_act, ymin = k1->p.yaw_min, ymax = k1->p.yaw_max, ystep = k1->p.yaw_step;
-            if (k1->p.action_method == WG_ACT_YAW) {
-                yaw = fminf(fmaxf(yaw + a * ystep, ymin), ymax);
-            } else {
-                float tf = a + 1.0f;
-                tf = tf * 0.5f;
-                tf = tf * (ymax - ymin);
-                tf = tf + ymin;
-                const float ny = fminf(fmaxf(tf, yaw - ystep), yaw + ystep);
-                yaw = fminf(fmaxf(ny, ymin), ymax);
-            }
+            yaw = wg_rule_adjust_yaw(k1->p.action_method, yaw, l_act, k1->p.yaw_min, k1->p.yaw_max, k1->p.yaw_step);
         }
     }
     float tpow = 0.f, tct = 0.f, cg = 1.f, sg = 0.f;
@@ -450,13 +438,9 @@ __device__ __forceinline__ void envb_flow(char* const smem, char* const wg_share
             if (role_live && farm == 1 && stepping) {
                 const float ystep = kr->p.yaw_step;
                 if (kr->p.base_controller == WG_CTRL_LOCAL) {
-                    const float wdir = atanf(tv / tu) * WG_RAD2DEG_F;
-                    const float off = wdir - yaw;
-                    const float sgn = (float)((off > 0.f) - (off < 0.f));
-                    yaw = yaw + sgn * fminf(fabsf(off), ystep);
+                    yaw = wg_rule_ctrl_local(yaw, atanf(tv / tu) * WG_RAD2DEG_F, ystep);
                 } else {
-                    const float sgn = (float)((yaw > 0.f) - (yaw < 0.f));
-                    yaw = yaw - sgn * fminf(fabsf(yaw), ystep);
+                    yaw = wg_rule_ctrl_global(yaw, ystep);
                 }
             }
             // (0) the slot's clock: travel of its chains over this step, particles released (lane t = 0 publishes)

@@ -1619,9 +1619,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
                 load_state(true);
                 // first share of the background work, planned here because k_glue could not know it yet
                 const int fill_max = F == 2 ? max(gp.fill_a, gp.fill_b) : gp.fill_a;
-                const int inc = 1 + (gp.extra_inc ? 1 : 0);
-                const int tm = d.ctx[e * 2 + env_live].time_max;
-                const long total = (long)((tm + inc - 1) / inc) + 1;
+                const long total = wg_rule_episode_steps(d.ctx[e * 2 + env_live].time_max, gp.extra_inc);
                 budget = wg_shadow_share(dev_rem + p.K * fill_max, total - env.steps_done, env.steps_done, e);
             } else {
                 if (dev_rem == 0 && fill_rem == 0) return;
@@ -1709,17 +1707,7 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
             oyaw[t] = yaw;            // :932 (written to d.old_yaw in the epilogue: a store here is the oldest outstanding memory
                                       // operation when the step's first phases run, and the compiler's waits order behind it)
             const float a = t < NT ? l_act : actions[(size_t)e * N + t];
-            if (p.action_method == WG_ACT_YAW) {
-                yaw = fminf(fmaxf(yaw + a * p.yaw_step, p.yaw_min), p.yaw_max);
-            } else {
-                float tf = a + 1.0f;
-                tf = tf * 0.5f;
-                tf = tf * (p.yaw_max - p.yaw_min);
-                tf = tf + p.yaw_min;
-                const float ny = fminf(fmaxf(tf, yaw - p.yaw_step), yaw + p.yaw_step);
-                yaw = fminf(fmaxf(ny, p.yaw_min), p.yaw_max);
-            }
-            T[t].yaw = yaw;
+            T[t].yaw = wg_rule_adjust_yaw(p.action_method, yaw, a, p.yaw_min, p.yaw_max, p.yaw_step);
         }
     }
     lds_barrier<NT>();   // publishes T, the tables and the rotor offsets
@@ -1748,12 +1736,9 @@ k_flow(const FlowP p, const FlowPtrs d, const int mode, const float* __restrict_
                     // (steady inflow: v == 0 exactly — the deficits only act on u — so atan(v / u) = +-0; the IEEE division + atanf
                     // are ~60 VALU instructions a baseline-farm step need not execute.  Replay mode scripts (u, v, w) freely.)
                     const float wdir = (TURB == WG_TURB_NONE && !REPLAY) ? 0.f : atanf(T[t].v / T[t].u) * WG_RAD2DEG_F;
-                    const float off = wdir - yaw;
-                    const float sgn = (float)((off > 0.f) - (off < 0.f));
-                    yaw = yaw + sgn * fminf(fabsf(off), p.yaw_step);
+                    yaw = wg_rule_ctrl_local(yaw, wdir, p.yaw_step);
                 } else {
-                    const float sgn = (float)((yaw > 0.f) - (yaw < 0.f));
-                    yaw = yaw - sgn * fminf(fabsf(yaw), p.yaw_step);
+                    yaw = wg_rule_ctrl_global(yaw, p.yaw_step);
                 }
                 T[t].yaw = yaw;
             }

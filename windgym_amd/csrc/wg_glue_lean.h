@@ -517,16 +517,18 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
     // action penalty sums (:804-820) and current farm powers ("Power agent", :539)
     float pen_s = 0.f, pnow = 0.f, pbase = 0.f;
     if (lane < N) {
-        pen_s = p.penalty_type == WG_PEN_CHANGE ? fabsf(l_old - l_yaw) : fabsf(l_yaw);
+        // (the type is chosen here, by a branch as before: as an argument it became a select of both arms — DESIGN.md)
+        pen_s = p.penalty_type == WG_PEN_CHANGE ? wg_rule_penalty_term(WG_PEN_CHANGE, l_old, l_yaw) : wg_rule_penalty_term(WG_PEN_TOTAL, 0.f, l_yaw);
         pnow = l_pow; pbase = l_powb;
     }
     for (int t = lane + WG_WAVE; t < N; t += WG_WAVE) {      // farms with more than 64 turbines
         const float y = d.yaw[tb_a + t];
-        pen_s += p.penalty_type == WG_PEN_CHANGE ? fabsf(d.old_yaw[(size_t)e * N + t] - y) : fabsf(y);
+        pen_s += p.penalty_type == WG_PEN_CHANGE ? wg_rule_penalty_term(WG_PEN_CHANGE, d.old_yaw[(size_t)e * N + t], y)
+                                                 : wg_rule_penalty_term(WG_PEN_TOTAL, 0.f, y);
         pnow += d.power[tb_a + t];
         if (F == 2) pbase += d.power[tb_a + N + t];
     }
-    if (p.action_penalty >= 0.001) pen_s = N <= 16 ? wg_row_sum(pen_s) : wg_wave_sum(pen_s);      // (lanes >= N hold 0)
+    if (p.action_penalty >= WG_PENALTY_SWITCH) pen_s = N <= 16 ? wg_row_sum(pen_s) : wg_wave_sum(pen_s);      // (lanes >= N hold 0)
     pnow = N <= 16 ? wg_row_sum(pnow) : wg_wave_sum(pnow);
     if (F == 2) pbase = N <= 16 ? wg_row_sum(pbase) : wg_wave_sum(pbase);
     pen_s = __shfl(pen_s, 0, 64); pnow = __shfl(pnow, 0, 64); pbase = __shfl(pbase, 0, 64);
@@ -558,10 +560,7 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
         break;
     }
     }
-    double pen = 0.0;
-    if (p.action_penalty >= 0.001)
-        pen = p.penalty_type == WG_PEN_CHANGE ? p.action_penalty * ((double)pen_s / N) : p.action_penalty * ((double)pen_s / N / p.yaw_max_d);
-    const float reward = (float)(pr * p.power_scaling + 0.0 - pen);                                       // :989-996
+    const float reward = wg_rule_reward(pr, p.power_scaling, wg_rule_penalty(p.action_penalty, p.penalty_type, pen_s, N, p.yaw_max_d));
     ev.timestep += 1 + (p.extra_inc ? 1 : 0);                                                             // :1027
     ev.steps_done += 1;
     ev.ep_return += reward; ev.ep_power_sum += pnow; ev.ep_len += 1;
@@ -571,17 +570,7 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
         d.last_pow_agent[e] = pnow; d.last_pow_base[e] = pbase;
     }
     if (lane < WG_N_METRICS) {            // lane m owns metric m (recordEpisodeVals.py:31-64)
-        const float trf = truncated ? 1.f : 0.f;
-        float add = 0.f;
-        add = lane == WG_MET_STEP_REWARD_SUM ? reward : add;
-        add = lane == WG_MET_FARM_POWER_SUM ? pnow : add;
-        add = lane == WG_MET_BASE_POWER_SUM ? pbase : add;
-        add = lane == WG_MET_N_STEPS ? 1.f : add;
-        add = lane == WG_MET_EP_RETURN_SUM ? trf * ev.ep_return : add;
-        add = lane == WG_MET_EP_LENGTH_SUM ? trf * (float)ev.ep_len : add;
-        add = lane == WG_MET_EP_MEAN_POWER_SUM ? (truncated ? ev.ep_power_sum / (float)ev.ep_len : 0.f) : add;
-        add = lane == WG_MET_N_EPISODES ? trf : add;
-        met[lane] = l_met + add;
+        met[lane] = l_met + wg_rule_metric_add(lane, reward, pnow, pbase, truncated, ev.ep_return, ev.ep_len, ev.ep_power_sum);
     }
 #if defined(WG_TIMELINE) && defined(WG_STAMP2)
     if (FUSED) WG_STAMP2(18);
@@ -624,8 +613,7 @@ __device__ __forceinline__ void lean_step(const WgParams& p, const WgPtrs& d, co
     if (!p.autoreset || truncated) ev.shadow_iters = 0;      // (after a swap the initialising workgroups plan their own first share)
     else if (work == 0) ev.shadow_iters = 0;
     else {
-        const int inc = 1 + (p.extra_inc ? 1 : 0);
-        const long total = (long)((time_max + inc - 1) / inc) + 1;
+        const long total = wg_rule_episode_steps(time_max, p.extra_inc);
         ev.shadow_iters = wg_shadow_share(work, total - ev.steps_done, ev.steps_done, e);
     }
     env_writeback(env, ev, lane, FUSED && fz.plan_elsewhere && !truncated);

@@ -78,9 +78,7 @@ __device__ inline int plan_shadow(const WgParams& p, const WgPtrs& d, const int 
         if (w > work) work = w;
     }
     if (work == 0) return 0;
-    const int inc = 1 + (p.extra_inc ? 1 : 0);
-    const int tm = d.ctx[e * 2 + live].time_max;
-    const long total = (long)((tm + inc - 1) / inc) + 1;
+    const long total = wg_rule_episode_steps(d.ctx[e * 2 + live].time_max, p.extra_inc);
     return wg_shadow_share(work, total - steps_done, steps_done, e);
 }
 
@@ -291,12 +289,14 @@ k_glue(const WgParams p, const WgPtrs d, const int phase, const uint8_t* __restr
     // action penalty sums (:804-820) and current farm powers ("Power agent", :539)
     float pen_s = 0.f, pnow = 0.f, pbase = 0.f;
     if (lane < N) {
-        pen_s = p.penalty_type == WG_PEN_CHANGE ? fabsf(l_old - l_yaw) : fabsf(l_yaw);
+        // (the type is chosen here, by a branch as before: as an argument it became a select of both arms — DESIGN.md)
+        pen_s = p.penalty_type == WG_PEN_CHANGE ? wg_rule_penalty_term(WG_PEN_CHANGE, l_old, l_yaw) : wg_rule_penalty_term(WG_PEN_TOTAL, 0.f, l_yaw);
         pnow = l_pow; pbase = l_powb;
     }
     for (int t = lane + WG_WAVE; t < N; t += WG_WAVE) {      // farms with more than 64 turbines
         const float y = d.yaw[tb_a + t];
-        pen_s += p.penalty_type == WG_PEN_CHANGE ? fabsf(d.old_yaw[(size_t)e * N + t] - y) : fabsf(y);
+        pen_s += p.penalty_type == WG_PEN_CHANGE ? wg_rule_penalty_term(WG_PEN_CHANGE, d.old_yaw[(size_t)e * N + t], y)
+                                                 : wg_rule_penalty_term(WG_PEN_TOTAL, 0.f, y);
         pnow += d.power[tb_a + t];
         if (p.F == 2) pbase += d.power[tb_a + N + t];
     }
@@ -309,12 +309,7 @@ k_glue(const WgParams p, const WgPtrs d, const int phase, const uint8_t* __restr
     case WG_REW_NONE: pr = 0.0; break;
     case WG_REW_POWER_DIFF: pr = (fl / (double)nl - fo / (double)no) / N; break;      // :904-918
     }
-    double pen = 0.0;
-    if (p.action_penalty >= 0.001) {
-        pen = p.penalty_type == WG_PEN_CHANGE ? p.action_penalty * ((double)pen_s / N)
-                                              : p.action_penalty * ((double)pen_s / N / p.yaw_max_d);
-    }
-    const float reward = (float)(pr * p.power_scaling + 0.0 - pen);                   // :989-996
+    const float reward = wg_rule_reward(pr, p.power_scaling, wg_rule_penalty(p.action_penalty, p.penalty_type, pen_s, N, p.yaw_max_d));
     ev.timestep += 1 + (p.extra_inc ? 1 : 0);                                         // :1027
     ev.steps_done += 1;
     // episode metrics (recordEpisodeVals.py:31-64; longer_steps_example.py:39-124)
@@ -325,18 +320,8 @@ k_glue(const WgParams p, const WgPtrs d, const int phase, const uint8_t* __restr
         d.last_pow_agent[e] = pnow; d.last_pow_base[e] = pbase;
     }
     if (WG_GLUE_ABLATE == 5) return;
-    if (lane < WG_N_METRICS) {            // lane m owns metric m (select chain: a switch became a scratch table)
-        const float trf = truncated ? 1.f : 0.f;
-        float add = 0.f;
-        add = lane == WG_MET_STEP_REWARD_SUM ? reward : add;
-        add = lane == WG_MET_FARM_POWER_SUM ? pnow : add;
-        add = lane == WG_MET_BASE_POWER_SUM ? pbase : add;
-        add = lane == WG_MET_N_STEPS ? 1.f : add;
-        add = lane == WG_MET_EP_RETURN_SUM ? trf * ev.ep_return : add;
-        add = lane == WG_MET_EP_LENGTH_SUM ? trf * (float)ev.ep_len : add;
-        add = lane == WG_MET_EP_MEAN_POWER_SUM ? (truncated ? ev.ep_power_sum / (float)ev.ep_len : 0.f) : add;
-        add = lane == WG_MET_N_EPISODES ? trf : add;
-        met[lane] = l_met + add;
+    if (lane < WG_N_METRICS) {            // lane m owns metric m (wg_rule_metric_add)
+        met[lane] = l_met + wg_rule_metric_add(lane, reward, pnow, pbase, truncated, ev.ep_return, ev.ep_len, ev.ep_power_sum);
     }
     if (WG_GLUE_ABLATE == 6) return;
     WG_GSTAMP(3);
@@ -406,8 +391,7 @@ k_glue(const WgParams p, const WgPtrs d, const int phase, const uint8_t* __restr
         work = __shfl(work, 0, 64);
         if (work == 0) ev.shadow_iters = 0;
         else {
-            const int inc = 1 + (p.extra_inc ? 1 : 0);
-            const long total = (long)((time_max + inc - 1) / inc) + 1;
+            const long total = wg_rule_episode_steps(time_max, p.extra_inc);
             ev.shadow_iters = wg_shadow_share(work, total - ev.steps_done, ev.steps_done, e);
         }
     }
