@@ -30,6 +30,47 @@
 #endif
 #include "wg_env_common.h"
 #include "wg_internal.h"
+#include "wg_plan.h"      // wg_plan_env_hot (host: env_launch)
+
+// k_flow_env's arguments as they lie in the kernarg segment: the arguments the env kernels share, then the hot block (EnvHotP,
+// wg_flow.h).  A phase of the common STEP path copies its group out through a fresh opaque pointer (the discipline of
+// wg_cold_args: nothing is held in SGPRs across phases) — side by side, its words come in a few wide loads behind one wait.
+struct EnvKArgsHot { EnvKArgs a; EnvHotP hot; };
+static_assert(offsetof(EnvKArgsHot, hot) == sizeof(EnvKArgs) && sizeof(EnvKArgs) % alignof(EnvHotP) == 0,
+              "the hot block follows the shared arguments without a gap (the kernarg segment lays it out by the same rule)");
+typedef const __attribute__((address_space(4))) EnvHotP* EnvHotPtr;
+__device__ __forceinline__ EnvHotPtr wg_hot_args() {
+    const __attribute__((address_space(4))) EnvKArgsHot* k = (const __attribute__((address_space(4))) EnvKArgsHot*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return &k->hot;
+}
+// The farm group read member by member out of the big blocks instead: every word is loaded where it is used, as before the hot
+// block.  The kernels with two waves per env take it and the tail group (below) this way: with the two groups' one trip each
+// cfg2 x 2048 measured 0.4-0.7 % below its parent, read this way it measures equal (EXPERIMENTS.md round 36: a switch by
+// measurement, the effect is not explained).  The member lists restate wg_plan_env_hot's; tests/test_gpu_env_hot_params.py
+// compares these kernels bit for bit with the two-launch step under every two-wave hook.
+__device__ __forceinline__ EnvHotFarm env_farm_cold() {
+    const KArgsPtr k = wg_cold_args();
+    EnvHotFarm m;
+    m.fring = k->d.fring; m.step_farm_pow = k->d.step_farm_pow; m.step_base_pow = k->d.step_base_pow; m.pend_farm = k->d.pend_farm;
+    m.pend_base = k->d.pend_base; m.fring_stride = k->p.fring_stride; m.power_avg = k->p.power_avg; m.pavg_magic = k->p.pavg_magic;
+    m.inv_N = k->p.inv_N;
+#pragma unroll
+    for (int i = 0; i < WG_N_CH; ++i) { m.hlen[i] = k->p.hlen[i]; m.fring_off[i] = k->p.fring_off[i]; m.hmagic[i] = k->p.hmagic[i]; }
+    return m;
+}
+// ... and the tail group likewise.
+__device__ __forceinline__ EnvHotTail env_tail_cold() {
+    const KArgsPtr k = wg_cold_args();
+    EnvHotTail m;
+    m.ring = k->d.ring; m.cur_ws = k->d.cur_ws; m.cur_wd = k->d.cur_wd; m.env = k->d.env;
+    m.n_tab = k->p.n_tab; m.tab_x0 = k->p.tab_x0; m.tab_inv_dx = k->p.tab_inv_dx; m.env_off_tab = k->p.env_off_tab; m.ring_stride = k->p.ring_stride;
+#pragma unroll
+    for (int i = 0; i < WG_N_CH; ++i) { m.hlen[i] = k->p.hlen[i]; m.ring_off[i] = k->p.ring_off[i]; m.inv_hlen[i] = k->p.inv_hlen[i]; m.noise_sigma[i] = k->p.noise_sigma[i]; }
+    return m;
+}
+// a group of the hot block by value (the cast leaves the constant address space as wg_cold_args' users do: the loads stay scalar)
+#define WG_HOT(group) (*(const decltype(EnvHotP::group)*)&wg_hot_args()->group)
 
 // Per-slot record in LDS.  Everything here is uniform over the N lanes of a slot: kept in LDS (written by the slot's lane
 // t = 0, read by broadcast) instead of one VGPR per word in every lane — the kernel lives at 128 VGPRs (4 waves per SIMD:
@@ -175,13 +216,11 @@ template <bool NOISE, int WPE, int GLUE, int SPLIT>
 __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass, float* const zone, const int wv, const int role, const int mode,
                                          const float* __restrict__ actions, const uint8_t* __restrict__ mask, const int chunk, EnvFlowOut& out) {
     const int tid = threadIdx.x & 63, e = blockIdx.x;
-    int N, F, NS, NL;
-    float inv_N;
-    {
-        const KArgsPtr ka = wg_cold_args();
-        N = ka->p.N; F = ka->p.F; inv_N = ka->p.inv_N;
-        NS = WPE == 2 ? F : 2 * F; NL = NS * N;              // slots / lanes served by THIS wave
-    }
+    // (the prologue's group of the hot block: every pointer and word it needs up to the roles, ONE scalar trip)
+    const EnvHotPro hp = WG_HOT(pro);
+    const int N = hp.N, F = hp.F;
+    const float inv_N = hp.inv_N;
+    const int NS = WPE == 2 ? F : 2 * F, NL = NS * N;      // slots / lanes served by THIS wave
     const int kbase = WPE == 2 ? wv * F : 0;                // the wave's first slot of the env
     const bool valid = tid < NL;
     const int g = valid ? tid : 0;
@@ -209,17 +248,15 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
     bool parked = false;      // (shared development, env_clone_dev) this lane's baseline slot waits for its agent twin's development
     float yaw, tu, tti, oyaw;
     {
-        const KArgsPtr k0 = wg_cold_args();
         // The env's 128-byte header as ONE coalesced load from the GLOBAL address space (lane i: word i), its fields broadcast
         // with v_readlane below, where the roles are decided — NOT scalar loads through the constant address space: the glue
         // tail of this very launch rewrites the header (such loads may be re-executed after the store, and
         // the scalar cache does not see this launch's vector stores).
         static_assert(sizeof(WgEnv) == 128, "the env header is loaded as 32 words");
-        const int hw = reinterpret_cast<const int*>(k0->d.env + e)[tid & 31];
-        if (GLUE != 0 && tid < 32) reinterpret_cast<int*>(smem + WG_ENV_OFF_HDR)[tid] = hw;      // (handed to the glue tail: no second load)
+        const int hw = reinterpret_cast<const int*>(hp.env + e)[tid & 31];
         out.bg_init_pending = 0; out.rounds = 0; out.first_obs = 0;
         const bool use_mask = mode == WG_MODE_RESET && mask != nullptr;
-        const uint8_t mask_byte = *(use_mask ? mask + e : reinterpret_cast<const uint8_t*>(k0->d.env + e));
+        const uint8_t mask_byte = *(use_mask ? mask + e : reinterpret_cast<const uint8_t*>(hp.env + e));
         const bool masked_out = use_mask && mask_byte == 0;
         const unsigned ctx_id = (unsigned)(e * 2 + c), slot_id = (unsigned)(e * 2 * F + kbase + k);
         const unsigned tb = (unsigned)((e * 2 * F + kbase) * N + g);      // == slot_id * N + t
@@ -231,30 +268,35 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         float ti_f, wd_env, l_yaw, l_u, l_ti, l_act;
         float4 l_bnd;
         int l_roff, l_rnext;
-        auto load_state = [&]() __attribute__((always_inline)) {
-            const KArgsPtr kl = wg_cold_args();
-            const WgSlot& slot = kl->d.slot[slot_id];
-            const WgCtx& cx = kl->d.ctx[ctx_id];
+        // (kl: the prologue's group as the caller holds it — the rare second call, after an episode set-up, fetches it afresh)
+        auto load_state = [&](const EnvHotPro& kl) __attribute__((always_inline)) {
+            const WgSlot& slot = kl.slot[slot_id];
+            const WgCtx& cx = kl.ctx[ctx_id];
             dev_rem = slot.dev_remaining; fill_rem = slot.fill_remaining;
             s_off = slot.s_off; c_time = slot.time; c_head = slot.head; n_valid = slot.n_valid; c_istep = slot.istep;
             n_emitted = slot.n_emitted; c_part = slot.part_count; c_flow = slot.flow_count; c_add = slot.add_count;
             ws = cx.ws; ti_f = (float)cx.ti; wd_env = (float)cx.wd;
-            n_pushed = cx.n_pushed; pend_farm_n = cx.pend_farm_n; pend_base_n = cx.pend_base_n;
-            c_tag = (unsigned)cx.episode_tag; init_pending = cx.init_pending; time_max_c = cx.time_max;
-            const int* ro = kl->d.roff + ctx_id * (unsigned)(N + 1);
+            n_pushed = cx.n_pushed; time_max_c = cx.time_max;
+            // (the context's words 80 .. 95 as ONE 16-byte load, requested with everything else: the set-up flag alone is read on
+            // the STEP arm only, and as a load of its own it was sunk there — a second dependent trip behind the first batch)
+            static_assert(offsetof(WgCtx, episode_tag) == 80 && offsetof(WgCtx, pend_farm_n) == 84 && offsetof(WgCtx, pend_base_n) == 88 &&
+                          offsetof(WgCtx, init_pending) == 92 && alignof(WgCtx) >= 16, "the context's words 80 .. 95 are loaded as one int4");
+            const int4 cw = *reinterpret_cast<const int4*>(&cx.episode_tag);
+            c_tag = (unsigned)cw.x; pend_farm_n = cw.y; pend_base_n = cw.z; init_pending = cw.w;
+            const int* ro = kl.roff + ctx_id * (unsigned)(N + 1);
             l_roff = ro[(unsigned)t]; l_rnext = ro[(unsigned)t + 1u];
-            l_xr = kl->d.xr[tcx]; l_yr = kl->d.yr[tcx];
-            l_yaw = kl->d.yaw[tb]; l_u = kl->d.u[tb]; l_ti = kl->d.ti_loc[tb];
-            l_bnd = reinterpret_cast<const float4*>(kl->d.bnd)[tb];
+            l_xr = kl.xr[tcx]; l_yr = kl.yr[tcx];
+            l_yaw = kl.yaw[tb]; l_u = kl.u[tb]; l_ti = kl.ti_loc[tb];
+            l_bnd = reinterpret_cast<const float4*>(kl.bnd)[tb];
         };
-        load_state();
-        const int n_tab = k0->p.n_tab, S = k0->p.S;
+        load_state(hp);
+        const int n_tab = hp.n_tab, S = hp.S;
         const unsigned i_tab = (unsigned)min(tid, n_tab - 1), i_s = (unsigned)min(tid, S - 1);
-        const float pf_tp = k0->d.tab_power[i_tab], pf_tc = k0->d.tab_ct[i_tab];
-        const float pf_dy = k0->d.rotor_dy[i_s], pf_dz = k0->d.rotor_dz[i_s];
+        const float pf_tp = hp.tab_power[i_tab], pf_tc = hp.tab_ct[i_tab];
+        const float pf_dy = hp.rotor_dy[i_s], pf_dz = hp.rotor_dz[i_s];
         {   // (every agent-farm lane reads its turbine's action; only the running episode's lanes use it)
             const bool has_act = mode == WG_MODE_STEP && farm == 0;
-            const float a = *(has_act ? actions + (unsigned)(e * N + t) : k0->d.tab_ct);
+            const float a = *(has_act ? actions + (unsigned)(e * N + t) : hp.tab_ct);
             l_act = has_act ? a : 0.f;
         }
 
@@ -263,6 +305,10 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         int env_done = WG_HDR_I(done), env_shadow_iters = WG_HDR_I(shadow_iters), env_steps_done = WG_HDR_I(steps_done);
         int env_timestep = WG_HDR_I(timestep), env_time_max_live = WG_HDR_I(time_max_live);
 #undef WG_HDR_I
+        // (handed to the glue tail: no second load.  HERE, where the header has landed anyway and in front of every return: stored
+        // right behind its load, the copy made the wave wait for the header's trip BEFORE it requested its state — vmcnt(0), then
+        // the batch: two vector round trips in a row at the moment all waves of the launch start together)
+        if (GLUE != 0 && tid < 32) reinterpret_cast<int*>(smem + WG_ENV_OFF_HDR)[tid] = hw;
         if (SPLIT && role == 1) {
             // (the pass wave: its flag down, and every word it has requested in its registers, before the barrier lets the main
             // waves go on — they rewrite some of those words at their ends)
@@ -283,8 +329,8 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             // metrics.  Nothing in this launch writes them before the glue does (the rings' leaving slots are not the slot the
             // step pushes into: a ring holds one sample more than its deque).  (lean_early_load: the kernels without a pass wave
             // request the same words at the head of their per-turbine tail.)
-            const EnvKArgsPtr kz = (EnvKArgsPtr)wg_cold_args();
-            const LeanEarly zr = lean_early_load(*(const WgParams*)&kz->gp, *(const WgPtrs*)&kz->gd, e, N, F, tid, hw);
+            const EnvHotReq kz = WG_HOT(req);
+            const LeanEarly zr = lean_early_load(kz, e, N, F, tid, hw);
             double* const zs = reinterpret_cast<double*>(zone);
 #pragma unroll
             for (int sI = 0; sI < WG_N_CH; ++sI) { zs[LEAN_PRE_S(sI, tid)] = zr.S[sI]; zone[LEAN_PRE_LV(sI, tid)] = zr.lv[sI]; }
@@ -304,7 +350,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         //            (Wind_Farm_Env.py:722-796 hidden behind the running episode), the masked envs' live
         //            context in RESET mode
         const bool is_live_c = (c == env_live);
-        const int autoreset = k0->p.autoreset;
+        const int autoreset = hp.autoreset;
         int budget = 0;
         long plan_left = 0;      // env steps the background plan spreads its work over (STEP mode)
         if (mode == WG_MODE_STEP) {
@@ -329,7 +375,10 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 const WgParams& gp = *ki->d.gp;
                 env_init_episode<GLUE != 0>(e, env_live ^ 1, tid);
                 full_barrier<64>();
-                load_state();
+                {
+                    const EnvHotPro hr = WG_HOT(pro);
+                    load_state(hr);
+                }
                 const int fill_max = F == 2 ? max(gp.fill_a, gp.fill_b) : gp.fill_a;
                 const int tm = WPE == 2 ? ki->d.ctx[e * 2 + env_live].time_max : __shfl(time_max_c, env_live * F * N, 64);
                 const long total = wg_rule_episode_steps(tm, gp.extra_inc);
@@ -346,16 +395,19 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 // after the agent farm's — below one flow step per two env steps the two never step in the same launch, and a wave
                 // carries 2 F + 1 farm steps where the per-context plan (WgEnv::shadow_iters, ignored here) gave it 2 F or 3 F:
                 // the launch lasts as long as its heaviest wave.
-                const long total = wg_rule_episode_steps_inc(env_time_max_live, k0->p.env_inc);
-                budget = role_dev ? wg_shadow_share(dev_rem + k0->p.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u) : 0;
+                const long total = wg_rule_episode_steps_inc(env_time_max_live, hp.env_inc);
+                budget = role_dev ? wg_shadow_share(dev_rem + hp.K * fill_rem, total - env_steps_done, env_steps_done, e, farm ? 0x80000000u : 0u) : 0;
                 plan_left = total - env_steps_done;
             }
         } else {
             role_dev = is_live_c && !masked_out;
             budget = chunk;
+            // (the set-up flag has a use on this arm too — an empty one — so its load stays in the prologue's batch: used on the
+            // STEP arm alone, it is sunk there and becomes a dependent trip of its own behind the batch)
+            asm volatile("" : : "v"(init_pending));
         }
         bool clone_here = false;      // (an agent-farm lane) its slot can finish its development in this launch with its twin parked
-        if (k0->p.env_share) {
+        if (hp.env_share) {
             // Shared development (env_clone_dev).  A baseline slot that has never stepped in this episode is parked while its agent
             // twin develops; that one's share covers the critical path meanwhile: its own development, then the longer of the two
             // fills — the baseline's only starts at the clone.  After the clone each farm plans from its own remaining work, as
@@ -365,14 +417,14 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             const int twin_fill = __shfl(parked ? fill_rem + 1 : 0, (tid + N) & 63, 64);      // (agent lanes) > 0: the twin is parked; its fill steps + 1
             const bool lead = valid && role_dev && farm == 0 && twin_fill > 0;
             if (lead && mode == WG_MODE_STEP && !defer_init)
-                budget = wg_shadow_share(dev_rem + k0->p.K * max(fill_rem, twin_fill - 1), plan_left, env_steps_done, e);
+                budget = wg_shadow_share(dev_rem + hp.K * max(fill_rem, twin_fill - 1), plan_left, env_steps_done, e);
             if (parked) budget = 0;      // (it gets what is left of its twin's at the clone)
             clone_here = lead && budget >= dev_rem;
         }
         if (SPLIT) {
             // exactly one flow step for every slot of the wave that steps at all, no episode set-up in this launch
             const bool two = valid && role_dev && budget >= 2;
-            split_on = mode == WG_MODE_STEP && k0->p.K == 1 && (is_live_c || (SPLIT == 2 && !out.bg_init_pending)) && !defer_init && !__ballot(two) &&
+            split_on = mode == WG_MODE_STEP && hp.K == 1 && (is_live_c || (SPLIT == 2 && !out.bg_init_pending)) && !defer_init && !__ballot(two) &&
                        !__ballot(clone_here);      // (the clone copies what the pass of this very launch stores: one wave does both)
             if (role == 1 && !split_on) return;
         }
@@ -397,7 +449,8 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         }
 
         // ---- state into LDS ---------------------------------------------------------------------------------------------
-        const KArgsPtr k1 = wg_cold_args();
+        // (the LDS set-up's group: ONE scalar trip)
+        const EnvHotSet k1 = WG_HOT(set);
         const int rlen = l_rnext - l_roff;
         const int head = n_emitted == 0u ? rlen - 1 : fast_mod((int)(n_emitted - 1u), rlen, __builtin_amdgcn_rcpf((float)rlen));
         const float ws_f = (float)ws;
@@ -410,7 +463,7 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             if (t == 0) {
                 my.dev_rem = dev_rem; my.fill_rem = fill_rem; my.sub = 0; my.budget = budget;
                 my.n_valid = n_valid; my.n_emitted = n_emitted; my.n_emitted0 = n_emitted;
-                my.move_max = fabsf(k1->p.hill) * ws_f * k1->p.dt; my.ti_pow = fast_pow(ti_f, k1->p.tic);
+                my.move_max = fabsf(k1.hill) * ws_f * k1.dt; my.ti_pow = fast_pow(ti_f, k1.tic);
                 my.s_off = s_off; my.ws = ws; my.ws_f = ws_f; my.ti_f = ti_f; my.wd_env = wd_env; my.base_acc = 0.f;
                 my.n_pushed = n_pushed; my.pend_farm_n = pend_farm_n; my.pend_base_n = pend_base_n; my.n_flow = 0;
                 my.bg_init = out.bg_init_pending;
@@ -418,25 +471,25 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             }
         }
         // tables: power | ct | rotor points as (lateral offset, squared vertical offset from the wake centre height)
-        float* const tabp = reinterpret_cast<float*>(smem + k1->p.env_off_tab);
+        float* const tabp = reinterpret_cast<float*>(smem + k1.env_off_tab);
         float* const tabct = tabp + n_tab;
         float2* const rpt = reinterpret_cast<float2*>(tabct + n_tab);
-        const float hub = k1->p.hub;
+        const float hub = k1.hub;
         auto rp = [&](const float dy_, const float dz_) __attribute__((always_inline)) {
             const float dz = hub + dz_ - hub;              // (k_flow: p.hub + rdz - zc, zc = hub under steady inflow)
             return make_float2(dy_, dz * dz);
         };
         if (tid < n_tab) { tabp[tid] = pf_tp; tabct[tid] = pf_tc; }
         if (tid < S) rpt[tid] = rp(pf_dy, pf_dz);
-        for (int i = tid + 64; i < n_tab; i += 64) { tabp[i] = k1->d.tab_power[i]; tabct[i] = k1->d.tab_ct[i]; }
-        for (int i = tid + 64; i < S; i += 64) rpt[i] = rp(k1->d.rotor_dy[i], k1->d.rotor_dz[i]);
+        for (int i = tid + 64; i < n_tab; i += 64) { tabp[i] = k1.tab_power[i]; tabct[i] = k1.tab_ct[i]; }
+        for (int i = tid + 64; i < S; i += 64) rpt[i] = rp(k1.rotor_dy[i], k1.rotor_dz[i]);
 
         // this lane's turbine (registers; the cross-lane fields live in the LDS arrays).  Steady inflow: v = w = 0 exactly
         // (the deficits only act on u), so they are constants here and stored as such.
         yaw = l_yaw; tu = l_u; tti = l_ti; oyaw = l_yaw;
         // WindFarmEnv._adjust_yaws (Wind_Farm_Env.py:822-864), float32 like numpy evaluates it on a float32 action
         if (role_live && farm == 0 && valid) {
-            yaw = wg_rule_adjust_yaw(k1->p.action_method, yaw, l_act, k1->p.yaw_min, k1->p.yaw_max, k1->p.yaw_step);
+            yaw = wg_rule_adjust_yaw(k1.action_method, yaw, l_act, k1.yaw_min, k1.yaw_max, k1.yaw_step);
         }
     }
     float tpow = 0.f, tct = 0.f, cg = 1.f;
@@ -458,9 +511,10 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 // cfg4, whose launch ends with such waves taking two rounds, lost 4 % with the request in every wave.)
                 out.g_early = LeanEarly{};
             } else {
-                const EnvKArgsPtr kz = (EnvKArgsPtr)wg_cold_args();
+                // (the request's group of the hot block by value: one scalar trip, issued with the header's LDS read)
+                const EnvHotReq kz = WG_HOT(req);
                 const int hwl = reinterpret_cast<const int*>(smem + WG_ENV_OFF_HDR)[tid & 31];
-                out.g_early = lean_early_load(*(const WgParams*)&kz->gp, *(const WgPtrs*)&kz->gd, e, N, F, tid, hwl);
+                out.g_early = lean_early_load(kz, e, N, F, tid, hwl);
             }
         }
     };
@@ -923,7 +977,8 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
         // step, farm_mes.add_measurements' ring push (MesClass.py:568-591)
         const bool measuring = stepping && !is_dev;
         const bool unit_end = measuring && (sub + 1 == K);
-        const KArgsPtr kc = wg_cold_args();
+        // (the tail's group of the hot block: the table's grid, the measurement arrays and the four channels' ring words side by side)
+        const EnvHotTail kc = WPE == 2 ? env_tail_cold() : WG_HOT(tail);      // (two waves per env: env_tail_cold)
         const float inv_k = 1.0f / (float)K;
         const unsigned ctx_id = (unsigned)(e * 2 + c);
         if (stepping) {
@@ -936,9 +991,9 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 part_acc += min(my.new_valid, rg.y);          // roofline accounting: particles that can still reach a rotor
             }
             stepped = true;
-            const int n_tab = kc->p.n_tab;
-            const float tab_x0 = kc->p.tab_x0, tab_inv_dx = kc->p.tab_inv_dx;
-            const float* const tabp = reinterpret_cast<const float*>(smem + kc->p.env_off_tab);
+            const int n_tab = kc.n_tab;
+            const float tab_x0 = kc.tab_x0, tab_inv_dx = kc.tab_inv_dx;
+            const float* const tabp = reinterpret_cast<const float*>(smem + kc.env_off_tab);
             const float wsn = fmaxf(tu * cg, 0.0f);
             tpow = env_tab(tabp, tab_x0, tab_inv_dx, n_tab, wsn);
             tct = env_tab(tabp + n_tab, tab_x0, tab_inv_dx, n_tab, wsn) * cg * cg;
@@ -949,26 +1004,26 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
                 if (unit_end) {
                     const int n_pushed = my.n_pushed;
                     const unsigned tcx = ctx_id * (unsigned)N + (unsigned)t;
-                    kc->d.cur_ws[tcx] = wsm;
-                    kc->d.cur_wd[tcx] = wdm;
+                    kc.cur_ws[tcx] = wsm;
+                    kc.cur_wd[tcx] = wdm;
                     if (K != 1) {
 #pragma unroll
                         for (int ch = 0; ch < WG_N_CH; ++ch) val[ch] *= inv_k;
                     }
                     if (NOISE) {
-                        const uint64_t noise_key = ((CEnvPtr)(kc->d.env + e))->noise_key;      // (set by k_init only: read-only in every step kernel)
+                        const uint64_t noise_key = ((CEnvPtr)(kc.env + e))->noise_key;      // (set by k_init only: read-only in every step kernel)
                         const uint32_t episode_tag = my.c_tag;
 #pragma unroll
                         for (int ch = 0; ch < WG_N_CH; ++ch)
-                            if (kc->p.noise_sigma[ch] != 0.f)
-                                val[ch] += kc->p.noise_sigma[ch] * wg_noise_normal(noise_key, (uint32_t)n_pushed, (uint32_t)t,
+                            if (kc.noise_sigma[ch] != 0.f)
+                                val[ch] += kc.noise_sigma[ch] * wg_noise_normal(noise_key, (uint32_t)n_pushed, (uint32_t)t,
                                                                                    (uint32_t)ch, episode_tag);
                     }
-                    float* __restrict__ rbase = kc->d.ring + (size_t)ctx_id * kc->p.ring_stride;
+                    float* __restrict__ rbase = kc.ring + (size_t)ctx_id * kc.ring_stride;
 #pragma unroll
                     for (int ch = 0; ch < WG_N_CH; ++ch) {
-                        const int H = kc->p.hlen[ch];
-                        rbase[(unsigned)(kc->p.ring_off[ch] + fast_mod(n_pushed, H, kc->p.inv_hlen[ch]) * N + t)] = val[ch];      // (time-major: WgRing)
+                        const int H = kc.hlen[ch];
+                        rbase[(unsigned)(kc.ring_off[ch] + fast_mod(n_pushed, H, kc.inv_hlen[ch]) * N + t)] = val[ch];      // (time-major: WgRing)
                     }
                     if (GLUE != 0) {      // (what the glue would read back from the rings)
 #pragma unroll
@@ -997,27 +1052,28 @@ __device__ __forceinline__ void env_flow(char* const smem, char* const smem_pass
             float base_acc = my.base_acc;
             if (measuring && farm == 1) base_acc += a_pw;
             if (unit_end) {
-                const FlowP __attribute__((address_space(4)))& pc = kc->p;
+                // (the farm-level pushes' group; two waves per env: read out of the big blocks as before, env_farm_cold)
+                const EnvHotFarm pc = WPE == 2 ? env_farm_cold() : WG_HOT(farm);
                 if (farm == 0) {
                     const int n_pushed = my.n_pushed, pend_farm_n = my.pend_farm_n;
-                    float* fbase = kc->d.fring + (size_t)ctx_id * pc.fring_stride;
+                    float* fbase = pc.fring + (size_t)ctx_id * pc.fring_stride;
                     fbase[pc.fring_off[WG_CH_WS] + umod_small(n_pushed, pc.hlen[WG_CH_WS], pc.hmagic[WG_CH_WS])] = a_ws * pc.inv_N;
                     fbase[pc.fring_off[WG_CH_WD] + umod_small(n_pushed, pc.hlen[WG_CH_WD], pc.hmagic[WG_CH_WD])] = a_wd * pc.inv_N;
                     fbase[pc.fring_off[WG_CH_POWER] + umod_small(n_pushed, pc.hlen[WG_CH_POWER], pc.hmagic[WG_CH_POWER])] = a_pw;
                     my.out_pw = a_pw;
-                    if (role_live) kc->d.step_farm_pow[e] = a_pw;
+                    if (role_live) pc.step_farm_pow[e] = a_pw;
                     else {
-                        kc->d.pend_farm[(size_t)ctx_id * pc.power_avg + umod_small(pend_farm_n, pc.power_avg, pc.pavg_magic)] = a_pw;
+                        pc.pend_farm[(size_t)ctx_id * pc.power_avg + umod_small(pend_farm_n, pc.power_avg, pc.pavg_magic)] = a_pw;
                         my.pend_farm_n = pend_farm_n + 1;
                     }
                     my.n_pushed = n_pushed + 1;
                 } else {
                     const float bp = K == 1 ? base_acc : base_acc * inv_k;
                     my.out_pw = bp;
-                    if (role_live) kc->d.step_base_pow[e] = bp;
+                    if (role_live) pc.step_base_pow[e] = bp;
                     else {
                         const int pend_base_n = my.pend_base_n;
-                        kc->d.pend_base[(size_t)ctx_id * pc.power_avg + umod_small(pend_base_n, pc.power_avg, pc.pavg_magic)] = bp;
+                        pc.pend_base[(size_t)ctx_id * pc.power_avg + umod_small(pend_base_n, pc.power_avg, pc.pavg_magic)] = bp;
                         my.pend_base_n = pend_base_n + 1;
                     }
                     base_acc = 0.f;
@@ -1120,7 +1176,9 @@ __global__ void __launch_bounds__(64 * (WPE + SPLIT), WG_ENV_WAVES)
 k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __restrict__ actions,
            const uint8_t* __restrict__ mask, const int chunk, const WgParams gp_, const WgPtrs gd_,
            float* __restrict__ obs_out, float* __restrict__ reward_out, uint8_t* __restrict__ trunc_out,
-           float* __restrict__ final_obs_out) {
+           float* __restrict__ final_obs_out, const EnvHotP hot_) {      // (hot_: never named — read through the kernarg segment at
+                                                                         // offsetof(EnvKArgsHot, hot), wg_hot_args: it must stay the LAST argument,
+                                                                         // behind exactly the arguments of EnvKArgs in their order)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef WG_TIMELINE
     if (threadIdx.x == 0) { for (int i = 0; i < 20; ++i) wg_stamps[i] = 0; wg_stamps[14] = wall_clock64(); for (int i = 0; i < 8; ++i) wg_counts[i] = 0; }
@@ -1261,8 +1319,10 @@ k_flow_env(const FlowP p_, const FlowPtrs d_, const int mode, const float* __res
 
 // launch table: (noise, glue, waves per env, pass waves) -> instantiation; 64 threads and FlowP::env_lds bytes of LDS per wave (+ the
 // pre-fetched glue inputs behind the regions of an instantiation with pass waves).  Pass waves exist with a glue tail only.
+// (k_flow_env's own kernel type: the env kernels' shared arguments + the hot block; k_flow_envb keeps EnvKernel)
+typedef void (*EnvHotKernel)(FlowP, FlowPtrs, int, const float*, const uint8_t*, int, WgParams, WgPtrs, float*, float*, uint8_t*, float*, EnvHotP);
 template <bool NZ, int G>
-static EnvKernel env_kernel(const int wpe, const int split) {
+static EnvHotKernel env_kernel(const int wpe, const int split) {
     if constexpr (G != 0) {
         if (split == 2) return k_flow_env<NZ, G, 2, 2>;
         if (split == 1) return k_flow_env<NZ, G, 2, 1>;
@@ -1275,10 +1335,12 @@ static void env_launch(const FlowP* p, const FlowPtrs* d, const int glue, const 
     const int wpe = p->env_wpe == 2 ? 2 : 1;
     const int split = glue != 0 && wpe == 2 && (p->env_split == 1 || p->env_split == 2) ? p->env_split : 0;
     const size_t lds = (size_t)p->env_lds * (wpe + split) + (split ? LEAN_PRE_BYTES : 0);
-    const EnvKernel k = glue == 2 ? (p->noise ? env_kernel<true, 2>(wpe, split) : env_kernel<false, 2>(wpe, split))
+    // the hot block, from the very blocks this launch passes (a setter that changes them between launches changes it with them)
+    const EnvHotP hot = wg_plan_env_hot(*p, *d, *gp, *gd);
+    const EnvHotKernel k = glue == 2 ? (p->noise ? env_kernel<true, 2>(wpe, split) : env_kernel<false, 2>(wpe, split))
                       : glue == 1 ? (p->noise ? env_kernel<true, 1>(wpe, split) : env_kernel<false, 1>(wpe, split))
                                   : (p->noise ? env_kernel<true, 0>(wpe, split) : env_kernel<false, 0>(wpe, split));
-    hipLaunchKernelGGL(k, dim3(p->B), dim3(64 * (wpe + split)), lds, st, *p, *d, mode, actions, mask, chunk, *gp, *gd, obs, reward, trunc, final_obs);
+    hipLaunchKernelGGL(k, dim3(p->B), dim3(64 * (wpe + split)), lds, st, *p, *d, mode, actions, mask, chunk, *gp, *gd, obs, reward, trunc, final_obs, hot);
 }
 
 // the flow step alone: the table's glue == 0 row, no glue arguments

@@ -41,7 +41,9 @@ __device__ __forceinline__ float env_tab(const float* __restrict__ ys, const flo
 // Register discipline (the "register cliff" of k_flow): the by-value parameter blocks are NEVER read directly.
 // Every phase fetches the parameters it needs through a fresh opaque pointer to the kernarg segment (wg_cold_args: scalar
 // loads that hit the constant cache) — nothing is held in SGPRs across phases, so nothing overflows into VGPR lanes
-// (v_readlane / v_writelane are VALU instructions: they were 15 % of what k_flow executed).
+// (v_readlane / v_writelane are VALU instructions: they were 15 % of what k_flow executed).  The price is a scalar load and a wait
+// per word where it is first used; k_flow_env's common STEP path takes the words of its prologue, glue request and tail from a hot
+// block instead, laid out so that a phase's words come in one trip (EnvHotP, wg_flow.h; wg_hot_args, wg_env.hip).
 __device__ __forceinline__ bool role_dev_any(const int autoreset, const int dev_rem, const int fill_rem) {
     return autoreset != 0 && (dev_rem > 0 || fill_rem > 0);
 }

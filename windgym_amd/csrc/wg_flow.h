@@ -121,6 +121,60 @@ struct FlowPtrs {
     WgEnv* env_rw;                // == env; the initialising workgroup of farm 0 commits the advanced generator
 };
 
+// k_flow_env's hot parameter block (wg_env.hip): bit-for-bit copies of the words the common STEP path reads out of FlowP / FlowPtrs
+// and — for the glue's early request — WgParams / WgPtrs, grouped by the phase that uses them, each group aligned to the load that
+// fetches it.  A phase takes its group as ONE struct copy through an opaque pointer to the kernarg segment (wg_hot_args): the
+// words lie side by side, so the copy is a few wide scalar loads behind ONE wait, where the same words read out of the big blocks
+// were a chain of single-dword loads, each waited for at its first use (wg_cold_args keeps doing that on the rare paths).  Built by
+// wg_plan_env_hot (wg_plan.h) inside env_launch from the very blocks the launch passes: it cannot go stale relative to them.
+struct __attribute__((aligned(16))) EnvHotPro {      // prologue: the header's and the state's loads, roles and shares
+    const WgEnv* env; WgSlot* slot; WgCtx* ctx; const int* roff;
+    const double *xr, *yr; float *yaw, *u;
+    float *ti_loc, *bnd; const float *tab_power, *tab_ct;
+    const float *rotor_dy, *rotor_dz;
+    int N, F; float inv_N; int autoreset;
+    int K, n_tab, S, env_inc;
+    int env_share, pad_[3];
+};
+struct __attribute__((aligned(16))) EnvHotSet {      // prologue: state into LDS, the action
+    const float *tab_power, *tab_ct, *rotor_dy, *rotor_dz;
+    int env_off_tab, action_method; float yaw_min, yaw_max;
+    float yaw_step, hill, dt, tic;
+    float hub; int pad_[3];
+};
+struct __attribute__((aligned(16))) EnvHotReq {      // the glue's early request (lean_early_load): WgParams / WgPtrs words, under their names
+    double* wsum; float *ring, *farm_pow, *base_pow;
+    float* metrics; int N, power_avg;
+    int ring_stride; unsigned sum_mask_t, cur_mask_t; int pad_;
+    int ring_off[WG_N_CH], sum_w[WG_N_CH], ring_cap[WG_N_CH];
+    unsigned ring_magic[WG_N_CH];
+};
+struct __attribute__((aligned(16))) EnvHotTail {     // per-turbine tail: power / thrust, measurement, ring push
+    float *ring, *cur_ws, *cur_wd; const WgEnv* env;
+    int n_tab; float tab_x0, tab_inv_dx; int env_off_tab;
+    int ring_stride, pad_[3];
+    int hlen[WG_N_CH], ring_off[WG_N_CH];
+    float inv_hlen[WG_N_CH], noise_sigma[WG_N_CH];
+};
+struct __attribute__((aligned(16))) EnvHotFarm {     // the tail's farm-level pushes (a slot's lane t = 0 at the end of an env step)
+    float *fring, *step_farm_pow, *step_base_pow, *pend_farm;
+    float* pend_base; int fring_stride, power_avg;
+    unsigned pavg_magic; float inv_N; int pad_[2];
+    int hlen[WG_N_CH], fring_off[WG_N_CH];
+    unsigned hmagic[WG_N_CH];
+};
+struct __attribute__((aligned(16))) EnvHotP {
+    EnvHotPro pro;
+    EnvHotSet set;
+    EnvHotReq req;
+    EnvHotTail tail;
+    EnvHotFarm farm;
+};
+#define WG_ENV_HOT_BYTES (160 + 80 + 128 + 128 + 112)
+static_assert(sizeof(EnvHotPro) == 160 && sizeof(EnvHotSet) == 80 && sizeof(EnvHotReq) == 128 && sizeof(EnvHotTail) == 128 &&
+              sizeof(EnvHotFarm) == 112, "EnvHotP: group sizes");
+static_assert(sizeof(EnvHotP) == WG_ENV_HOT_BYTES, "EnvHotP: no padding between the groups");
+
 // k_flow_env's LDS carve (wg_env.hip): fixed part (cross-lane turbine fields: three 16-byte and two 8-byte arrays of 64 entries,
 // then four slot records) | staging: per-candidate deficit, added TI (WG_ENV_CAP floats each), candidate list (u16), aliased by
 // the quad list | tables (FlowP::env_off_tab)

@@ -313,19 +313,22 @@ struct LeanEarly {
     double S[WG_N_CH];
     float lv[WG_N_CH], f_old, b_old, met;
 };
-__device__ __forceinline__ LeanEarly lean_early_load(const WgParams& p, const WgPtrs& d, const int e, const int N, const int F,
-                                                     const int lane, const int hw) {
+// `h`: the words and pointers of the glue's parameter blocks the request needs, as the caller fetched them — k_flow_env's hot block
+// (EnvHotReq, wg_flow.h: WgParams / WgPtrs members under their own names), taken by value in one scalar trip: read out of the big
+// blocks member by member, every channel's window test was followed by a single-dword load and a wait of its own.
+template <typename H>
+__device__ __forceinline__ LeanEarly lean_early_load(const H& h, const int e, const int N, const int F, const int lane, const int hw) {
 #define WG_HDR_Z(f) __builtin_amdgcn_readlane(hw, (int)(offsetof(WgEnv, f) / 4))
     const int z_live = WG_HDR_Z(live), z_np = WG_HDR_Z(n_pushed_live), z_fn = WG_HDR_Z(farm_pow_n), z_bn = WG_HDR_Z(base_pow_n);
 #undef WG_HDR_Z
-    const int PA = p.power_avg;
-    const SumsRaw zr = wg_sums_load<false, false, true>(p, d, e, e * 2 + z_live, lane < N ? lane : 0, z_np);      // (a turbine: lane < N)
+    const int PA = h.power_avg;
+    const SumsRaw zr = wg_sums_load<false, false, true>(h, h, e, e * 2 + z_live, lane < N ? lane : 0, z_np);      // (a turbine: lane < N)
     LeanEarly q;
 #pragma unroll
     for (int s = 0; s < WG_N_CH; ++s) { q.S[s] = zr.S[s]; q.lv[s] = zr.lv[s]; }
-    q.f_old = d.farm_pow[(size_t)e * PA + z_fn % PA];
-    q.b_old = F == 2 ? d.base_pow[(size_t)e * PA + z_bn % PA] : 0.f;
-    q.met = lane < WG_N_METRICS ? d.metrics[(size_t)e * WG_N_METRICS + lane] : 0.f;
+    q.f_old = h.farm_pow[(size_t)e * PA + z_fn % PA];
+    q.b_old = F == 2 ? h.base_pow[(size_t)e * PA + z_bn % PA] : 0.f;
+    q.met = lane < WG_N_METRICS ? h.metrics[(size_t)e * WG_N_METRICS + lane] : 0.f;
     return q;
 }
 

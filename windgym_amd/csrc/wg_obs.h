@@ -220,21 +220,35 @@ struct SumsEnt {            // where entity `ent` lives
 // (TURB: the caller's entity is a turbine, never the farm-level one — a per-lane `ent == N` makes every choice between a turbine's
 // and the farm's parameter a per-lane one, and the compiler fetches such a parameter with a VECTOR load from the argument block,
 // waited for before the ring address can be formed: a second round trip in front of the leaving samples)
-template <bool TURB = false>
-__device__ __forceinline__ SumsEnt wg_sums_ent(const WgParams& p, const WgPtrs& d, const int ctx_id, const int ent) {
+// (P, D: WgParams / WgPtrs — or, TURB only, any block that holds the turbine-level words under the same names: k_flow_env's
+// EnvHotReq, wg_flow.h)
+template <bool TURB = false, typename P, typename D>
+__device__ __forceinline__ SumsEnt wg_sums_ent(const P& p, const D& d, const int ctx_id, const int ent) {
     SumsEnt q;
-    q.farm = TURB ? false : ent == p.N;
-    q.rb = q.farm ? d.fring + (size_t)ctx_id * p.fring_stride : d.ring + (size_t)ctx_id * p.ring_stride + ent;
-    q.stride = q.farm ? 1 : p.N;
-    q.sm = q.farm ? p.sum_mask_f : p.sum_mask_t;
-    q.cm = q.farm ? p.cur_mask_f : p.cur_mask_t;
+    if constexpr (TURB) {
+        q.farm = false;
+        q.rb = d.ring + (size_t)ctx_id * p.ring_stride + ent;
+        q.stride = p.N; q.sm = p.sum_mask_t; q.cm = p.cur_mask_t;
+    } else {
+        q.farm = ent == p.N;
+        q.rb = q.farm ? d.fring + (size_t)ctx_id * p.fring_stride : d.ring + (size_t)ctx_id * p.ring_stride + ent;
+        q.stride = q.farm ? 1 : p.N;
+        q.sm = q.farm ? p.sum_mask_f : p.sum_mask_t;
+        q.cm = q.farm ? p.cur_mask_f : p.cur_mask_t;
+    }
     return q;
+}
+// (a turbine's entity reads the turbine rings' offsets whatever the block: a farm-level offset exists in WgParams alone)
+template <bool TURB, typename P>
+__device__ __forceinline__ int wg_sums_off(const P& p, const bool farm, const int ch) {
+    if constexpr (TURB) return p.ring_off[ch];
+    else return farm ? p.fring_off[ch] : p.ring_off[ch];
 }
 // the loads of one step's update: `np` pushes are in the sums, the flow kernel has pushed sample number np since
 // (NEWEST = false: only what does not depend on the step in flight — the old sums and the leaving samples; k_flow_env's pass wave
 // fetches those while the step runs)
-template <bool GEN, bool NEWEST = true, bool TURB = false>
-__device__ inline SumsRaw wg_sums_load(const WgParams& p, const WgPtrs& d, const int e, const int ctx_id, const int ent, const int np) {
+template <bool GEN, bool NEWEST = true, bool TURB = false, typename P, typename D>
+__device__ inline SumsRaw wg_sums_load(const P& p, const D& d, const int e, const int ctx_id, const int ent, const int np) {
     constexpr int NSL = GEN ? WG_N_SUMS : WG_N_CH;        // (without TI entries only the four window slots exist)
     SumsRaw r;
     const SumsEnt q = wg_sums_ent<TURB>(p, d, ctx_id, ent);
@@ -244,7 +258,7 @@ __device__ inline SumsRaw wg_sums_load(const WgParams& p, const WgPtrs& d, const
 #pragma unroll
     for (int ch = 0; ch < WG_N_CH; ++ch) {
         const bool need = (((q.sm | q.cm) >> ch) & 1u) || (ch == WG_CH_WS && ti);
-        const int off = q.farm ? p.fring_off[ch] : p.ring_off[ch];
+        const int off = wg_sums_off<TURB>(p, q.farm, ch);
         r.nw[ch] = (NEWEST && need) ? q.rb[off + wg_umod(np, p.ring_cap[ch], p.ring_magic[ch]) * q.stride] : 0.f;
     }
 #pragma unroll
@@ -253,7 +267,7 @@ __device__ inline SumsRaw wg_sums_load(const WgParams& p, const WgPtrs& d, const
     for (int s = 0; s < NSL; ++s) {
         if ((q.sm >> s) & 1u) {
             const int ch = s < WG_N_CH ? s : WG_CH_WS;
-            const int off = q.farm ? p.fring_off[ch] : p.ring_off[ch];
+            const int off = wg_sums_off<TURB>(p, q.farm, ch);
             const int Wc = p.sum_w[s];
             r.S[s] = ws_[(size_t)s * NS];
             // (the ring holds one sample more than the deque: the sample pushed Wc <= H pushes before the newest is still there)

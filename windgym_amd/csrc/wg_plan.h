@@ -489,6 +489,38 @@ inline void wg_plan_flow_scalars(const wg_config* c, const WgParams& p, double t
     f.an_inv_ka = (float)(1.0 / wg_defd(c->m0_ka, 0.38));
 }
 
+// ---- k_flow_env's hot parameter block: copies, word for word, of what its common STEP path reads (EnvHotP, wg_flow.h) ------------
+// A function of the four blocks a launch passes and of nothing else: env_launch (wg_env.hip) calls it on its own arguments.  `gp` /
+// `gd` are the glue's blocks (all zeros for a launch without a glue tail, which never reads the request group).
+inline EnvHotP wg_plan_env_hot(const FlowP& f, const FlowPtrs& d, const WgParams& gp, const WgPtrs& gd) {
+    EnvHotP h;
+    memset(&h, 0, sizeof(h));
+    EnvHotPro& a = h.pro;
+    a.env = d.env; a.slot = d.slot; a.ctx = d.ctx; a.roff = d.roff; a.xr = d.xr; a.yr = d.yr; a.yaw = d.yaw; a.u = d.u;
+    a.ti_loc = d.ti_loc; a.bnd = d.bnd; a.tab_power = d.tab_power; a.tab_ct = d.tab_ct; a.rotor_dy = d.rotor_dy; a.rotor_dz = d.rotor_dz;
+    a.N = f.N; a.F = f.F; a.inv_N = f.inv_N; a.autoreset = f.autoreset; a.K = f.K; a.n_tab = f.n_tab; a.S = f.S; a.env_inc = f.env_inc;
+    a.env_share = f.env_share;
+    EnvHotSet& s = h.set;
+    s.tab_power = d.tab_power; s.tab_ct = d.tab_ct; s.rotor_dy = d.rotor_dy; s.rotor_dz = d.rotor_dz;
+    s.env_off_tab = f.env_off_tab; s.action_method = f.action_method; s.yaw_min = f.yaw_min; s.yaw_max = f.yaw_max; s.yaw_step = f.yaw_step;
+    s.hill = f.hill; s.dt = f.dt; s.tic = f.tic; s.hub = f.hub;
+    EnvHotReq& r = h.req;
+    r.wsum = gd.wsum; r.ring = gd.ring; r.farm_pow = gd.farm_pow; r.base_pow = gd.base_pow; r.metrics = gd.metrics;
+    r.N = gp.N; r.power_avg = gp.power_avg; r.ring_stride = gp.ring_stride; r.sum_mask_t = gp.sum_mask_t; r.cur_mask_t = gp.cur_mask_t;
+    EnvHotTail& t = h.tail;
+    t.ring = d.ring; t.cur_ws = d.cur_ws; t.cur_wd = d.cur_wd; t.env = d.env;
+    t.n_tab = f.n_tab; t.tab_x0 = f.tab_x0; t.tab_inv_dx = f.tab_inv_dx; t.env_off_tab = f.env_off_tab; t.ring_stride = f.ring_stride;
+    EnvHotFarm& m = h.farm;
+    m.fring = d.fring; m.step_farm_pow = d.step_farm_pow; m.step_base_pow = d.step_base_pow; m.pend_farm = d.pend_farm; m.pend_base = d.pend_base;
+    m.fring_stride = f.fring_stride; m.power_avg = f.power_avg; m.pavg_magic = f.pavg_magic; m.inv_N = f.inv_N;
+    for (int i = 0; i < WG_N_CH; ++i) {
+        r.ring_off[i] = gp.ring_off[i]; r.sum_w[i] = gp.sum_w[i]; r.ring_cap[i] = gp.ring_cap[i]; r.ring_magic[i] = gp.ring_magic[i];
+        t.hlen[i] = f.hlen[i]; t.ring_off[i] = f.ring_off[i]; t.inv_hlen[i] = f.inv_hlen[i]; t.noise_sigma[i] = f.noise_sigma[i];
+        m.hlen[i] = f.hlen[i]; m.fring_off[i] = f.fring_off[i]; m.hmagic[i] = f.hmagic[i];
+    }
+    return h;
+}
+
 // how many RESET-mode launches develop the slowest possible episode: the chain needs
 // int(2 * dist / ws) steps (dist <= layout diagonal, ws >= ws_min) plus the window fill
 inline int wg_plan_reset_launches(const wg_config* c, const WgParams& p, int reset_chunk) {
